@@ -28,6 +28,7 @@ float64 C oracle on the host cores).  Side blocks: `aux.workloads` (BASELINE con
 15-zone map, steady state + per-step launches + spot check each), `aux.beyond_llc` (PointTSP-25 at
 batches whose per-step output exceeds the 256 MiB Infinity Cache, with the bare store stream of
 the same footprint beside each), `aux.env_overrides` (every switch that changes what is measured).
+--dump-outputs DIR also writes what the timed steps returned after the last of them (dump_outputs).
 """
 import argparse
 import hashlib
@@ -231,6 +232,10 @@ def main():
     ap.add_argument("--print-rank-env", action="store_true",
                     help="diagnostic: print this rank's launch environment (RANK, WORLD_SIZE, rendezvous directory ...) as "
                          "one JSON line and exit -- what tests/test_bench_contract.py checks the self-spawn path with")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what their last step returned (rank 0's envs) as DIR/<name>.npy "
+                         "in float32 / float64, at most 64 MB in all (a fixed, seeded sample of envs beyond that): two "
+                         "builds run with the same arguments can then be compared output for output")
     args = ap.parse_args()
     if args.unfused:
         args.mode = "unfused"
@@ -367,6 +372,8 @@ def main():
     env.sync()
     elapsed = time.perf_counter() - t0
     fence()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(env, Z, args.dump_outputs)
 
     # rank-local results, then the one collective of the job: all-gather of episodic returns
     returns = shard.gather_returns(env)          # float32 [world * n_env] on every rank
@@ -496,6 +503,31 @@ def main():
     if distributed:
         rdzv.close()
     return out
+
+
+DUMP_BYTES = 64 * 10**6     # --dump-outputs: the cap on what one run writes
+DUMP_SEED = 0x5EED          # the row sample taken when a batch's outputs exceed the cap
+
+
+def dump_outputs(env, Z, out_dir):
+    """What the timed rollout returns to its caller after its last step -- obs, zone_obs, reward, done, goal_met (the
+    step results) and each env's last episodic return -- as out_dir/<name>.npy, float32 (float64 for the return).
+    When the batch's rows do not fit DUMP_BYTES, the same seeded sample of env rows is written for every field, and
+    its env indices as env_index.npy."""
+    fields = [("obs", Z.F_OBS, np.float32), ("zone_obs", Z.F_ZONE_OBS, np.float32), ("reward", Z.F_REWARD, np.float32),
+              ("done", Z.F_DONE, np.float32), ("goal_met", Z.F_GOAL_MET, np.float32),
+              ("last_return", Z.F_LAST_RETURN, np.float64)]
+    arrays = [(name, env.get(f).astype(dt, copy=False)) for name, f, dt in fields]
+    n = env.num_envs
+    row_bytes = sum(a.nbytes // max(n, 1) for _, a in arrays)
+    budget = DUMP_BYTES - 4096                      # .npy headers
+    if n * row_bytes > budget:
+        k = budget // (row_bytes + 8)                # + the float64 index of each sampled row
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+        arrays = [(name, a[rows]) for name, a in arrays] + [("env_index", rows.astype(np.float64))]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays:
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def spawn_ranks(n, timeout=None):

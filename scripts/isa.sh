@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage: scripts/isa.sh <mangled-substring>   -> /tmp/kernel.s plus a few stats
-R=/root/repo/combinatorial-rl-tasks_amd
+R="$(cd "$(dirname "$0")/.." && pwd)/combinatorial-rl-tasks_amd"
 hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -Wno-pass-failed -S --cuda-device-only -o /tmp/k.s $R/csrc/kernels.hip || exit 1
 name=$(grep -oE "^_ZN5zenvk[A-Za-z0-9_]*$1[A-Za-z0-9_]*:" /tmp/k.s | head -1 | tr -d ':')
 echo "kernel: $name"

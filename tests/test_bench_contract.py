@@ -165,3 +165,65 @@ def test_bare_gpus_n_spawns_its_own_ranks(zenv_mod):
                        env=env, capture_output=True, text=True, timeout=600)
     if zenv_mod._native.lib().zenv_device_count() < 2:
         assert r.returncode != 0 and "has no device" in r.stderr and "one process per GPU" in r.stderr
+
+
+class _FakeEnv:
+    """Stands in for ZoneVecEnv.get(): every field's rows hold the env index, so a sampled row shows where it came from."""
+
+    def __init__(self, n, zones):
+        import numpy as np
+        self.num_envs, self._np = n, np
+        self._shapes = {0: (8,), 1: (zones, 6), 2: (), 3: (), 4: (), 7: ()}
+
+    def get(self, field):
+        np = self._np
+        shape = self._shapes[field]
+        idx = np.arange(self.num_envs, dtype=np.float64).reshape((-1,) + (1,) * len(shape))
+        return np.broadcast_to(idx, (self.num_envs,) + shape).astype(np.float64 if field == 7 else np.float32)
+
+
+def test_dump_outputs_writes_every_result_and_caps_a_large_batch(tmp_path):
+    import numpy as np
+    import types
+    Z = types.SimpleNamespace(F_OBS=0, F_ZONE_OBS=1, F_REWARD=2, F_DONE=3, F_GOAL_MET=4, F_LAST_RETURN=7)
+    names = ("obs", "zone_obs", "reward", "done", "goal_met", "last_return")
+    bench.dump_outputs(_FakeEnv(1000, 25), Z, str(tmp_path / "small"))
+    got = {n: np.load(tmp_path / "small" / f"{n}.npy") for n in names}
+    assert sorted(os.listdir(tmp_path / "small")) == sorted(n + ".npy" for n in names)
+    assert got["obs"].shape == (1000, 8) and got["zone_obs"].shape == (1000, 25, 6) and got["reward"].shape == (1000,)
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values()) and got["last_return"].dtype == np.float64
+    # a batch whose outputs exceed the cap: one seeded sample of rows, the same for every field and every run
+    for d in ("big1", "big2"):
+        bench.dump_outputs(_FakeEnv(131072, 25), Z, str(tmp_path / d))
+    total = sum(os.path.getsize(tmp_path / "big1" / f) for f in os.listdir(tmp_path / "big1"))
+    assert total <= bench.DUMP_BYTES
+    rows = np.load(tmp_path / "big1" / "env_index.npy")
+    assert 0 < len(rows) < 131072 and np.all(np.diff(rows) > 0)
+    for n in names:
+        a = np.load(tmp_path / "big1" / f"{n}.npy")
+        assert np.array_equal(a, np.load(tmp_path / "big2" / f"{n}.npy"))
+        assert np.array_equal(a.reshape(len(rows), -1)[:, 0], rows)
+
+
+@pytest.mark.gpu
+def test_dump_outputs_is_reproducible_and_follows_steps(zenv_mod, tmp_path):
+    """bench.py --dump-outputs: the same arguments give the same outputs, and --steps sets how far the envs went."""
+    import subprocess
+    import sys
+    import numpy as np
+
+    def run(steps, d):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps),
+                            "--warmup", "2", "--no-settle", "--envs-per-gpu", "4096", "--no-cpu-baseline", "--no-steady",
+                            "--no-mlp", "--no-per-step", "--no-sweep", "--dump-outputs", str(tmp_path / d)],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == steps
+        return {f[:-4]: np.load(tmp_path / d / f) for f in os.listdir(tmp_path / d)}
+
+    a, b, c = run(300, "a"), run(300, "b"), run(301, "c")
+    assert sorted(a) == ["done", "goal_met", "last_return", "obs", "reward", "zone_obs"]
+    assert a["obs"].shape == (4096, 8) and a["zone_obs"].shape == (4096, 25, 6)
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert not np.array_equal(a["obs"], c["obs"])
