@@ -16,6 +16,7 @@ OBS_DIM = 8
 
 TASK_TSP, TASK_TIMED_TSP, TASK_COLOUR_MATCH = 0, 1, 2
 POLICY_UNIFORM, POLICY_GREEDY, POLICY_MLP_MEAN, POLICY_MLP_SAMPLE = 0, 1, 2, 3
+POLICY_HIER_SAMPLE, POLICY_HIER_MEAN = 4, 5     # the Zone-goals hierarchical agent (zenv_hier_load)
 KERNEL_LANE_PER_ENV, KERNEL_WAVE_PER_ENV = 0, 1
 HIP_STREAM_LEGACY = 1       # hipStreamLegacy: the null stream as an explicit handle (hip_runtime_api.h)
 ROLLOUT_UNFUSED = 1
@@ -33,7 +34,7 @@ E_ARG, E_HIP, E_STATE, E_LAYOUT, E_DONE, E_RANGE = -1, -2, -3, -4, -5, -6
  F_SHAPED_REWARD, F_NEED_GOAL, F_AVAILABLE_GOALS, F_GOAL,
  F_EXP_OBS, F_EXP_ZONE_OBS, F_EXP_ACTION, F_EXP_LOG_PROB, F_EXP_VALUE, F_EXP_REWARD, F_EXP_MASK,
  F_EXP_ADVANTAGE, F_EXP_RETURN, F_ORDER_VAL, F_EXCEPTION, F_POLICY_VALUE_SIGMA, F_ORDER_POS,
- F_CHUNK_REWARD, F_CHUNK_DONE, F_CHUNK_ACTIONS) = range(36)
+ F_CHUNK_REWARD, F_CHUNK_DONE, F_CHUNK_ACTIONS, F_HIER_LOGITS, F_HIER_VALUE) = range(38)
 (RESULT_OBS, RESULT_REWARD, RESULT_DONE, RESULT_GOAL_MET, RESULT_EXCEPTION, RESULT_ZONE_OBS) = range(6)
 N_RESULTS = 6
 
@@ -49,6 +50,21 @@ class MlpWeights(C.Structure):
     """struct zenv_mlp_weights (include/zenv.h): host float32 tensors in state_dict layout."""
     _fields_ = [("h_dim", C.c_int32), ("precision", C.c_int32)] + [
         (n, C.c_void_p) for n in MLP_TENSORS + MLP_CRITIC_TENSORS + MLP_SIGMA_TENSORS]
+
+
+# struct zenv_hier_weights (include/zenv.h): hi_model_state / lo_model_state of the Zone-goals agent
+HIER_HI_TENSORS = ("hi_zone_w1", "hi_zone_b1", "hi_zone_w2", "hi_zone_b2", "hi_zone_w3", "hi_zone_b3", "hi_comb_w",
+                   "hi_comb_b", "hi_actor_w1", "hi_actor_b1", "hi_actor_w2", "hi_actor_b2")
+HIER_HI_CRITIC = ("hi_critic_w1", "hi_critic_b1", "hi_critic_w2", "hi_critic_b2")    # optional, all or none
+HIER_LO_TENSORS = ("lo_zone_w1", "lo_zone_b1", "lo_zone_w2", "lo_zone_b2", "lo_zone_w3", "lo_zone_b3", "lo_comb_w",
+                   "lo_comb_b", "lo_enc_w", "lo_enc_b", "lo_mu_w", "lo_mu_b", "lo_std_w", "lo_std_b")
+HIER_LO_CRITIC = ("lo_critic_w1", "lo_critic_b1", "lo_critic_w2", "lo_critic_b2")    # optional, all or none
+
+
+class HierWeights(C.Structure):
+    """struct zenv_hier_weights (include/zenv.h): host float32 tensors in state_dict layout."""
+    _fields_ = [("h_dim", C.c_int32), ("precision", C.c_int32), ("zone_feat", C.c_int32), ("pad", C.c_int32)] + [
+        (n, C.c_void_p) for n in HIER_HI_TENSORS + HIER_HI_CRITIC + HIER_LO_TENSORS + HIER_LO_CRITIC]
 
 
 class ZenvError(RuntimeError):
@@ -122,6 +138,8 @@ _PROTOTYPES = {
     "zenv_solver_goals": (C.c_int, [_H, C.c_void_p]),
     "zenv_mlp_load": (C.c_int, [_H, C.c_void_p]),
     "zenv_mlp_forward": (C.c_int, [_H]),
+    "zenv_hier_load": (C.c_int, [_H, C.c_void_p]),
+    "zenv_hier_forward": (C.c_int, [_H]),
     "zenv_get": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int]),
     "zenv_get_rows": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "zenv_device_ptr": (C.c_int, [_H, C.c_int, C.POINTER(C.c_void_p)]),

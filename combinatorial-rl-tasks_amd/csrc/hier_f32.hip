@@ -1,0 +1,435 @@
+// hier_f32.hip -- the Zone-goals hierarchical agent (zone-goals/src/hier_policy_value_models.py:19-86) in float32, gfx950.
+//
+// Two launches of one kernel template, both on the vector ALU in the layout of mlp_f32.hip's k_mlp_f32: a workgroup of
+// kMlpHP = 192 threads owns EB = 4 consecutive envs, thread j owns hidden feature j, input rows sit in LDS ([k][row]: the
+// same address in every lane = a broadcast), the weights are read transposed ([k][j]) from L2.
+//
+//  * k_hier_f32<0> -- HighPolicyValueModel.  emb = ZoneEnvModel(obs, zone_obs); actor.0 = [W_e | W_z] on [emb, zone row]
+//    splits into W_e emb + b (once per env) + W_z row_z (Z times, F columns), so every logit costs h * F FMAs plus a
+//    length-h dot product with actor.2 (a 6-way split reduction over LDS).  The same kernel masks the unavailable zones
+//    and picks the goal (argmax, or the inverse CDF of softmax(masked logits) on one Philox uniform) into the buffer
+//    launch_goal_set reads.  When it picks, a workgroup none of whose envs needs a goal writes -1 and leaves: the high
+//    level costs what the envs that pick cost (goals change every few hundred steps).
+//  * k_hier_f32<1> -- LoPolicyValueModel.  ZoneEnvGoalModel's [obs, goal] is the same for every zone row of an env:
+//    W_x [obs, goal] + b folds into a per-env bias of zone_net_.0 (and the [obs, goal] columns of combine_net_ into a
+//    per-env term), so the per-zone part has the flat network's shape, F columns.  Then PolicyNetwork's enc_ / mu_ /
+//    std_ and the Normal sample of mlp_head_out.hpp.
+// Only the summation order differs from torch's (and the mean over the zone rows is taken before zone_net_'s third,
+// activation-free layer, with which it commutes): within 1e-5 of the reference's float32 modules.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+#include "hier_f32.hpp"
+#include "mlp_head_out.hpp"
+
+namespace zenvk {
+namespace {
+
+constexpr int HP = kMlpHP;     // 192 threads = hidden features (padded)
+constexpr int RP = 32;         // rows (zone rows of consecutive envs) per pass
+constexpr int EB = 4;          // envs per workgroup
+constexpr int XP = 12;         // per-env input [obs (8), goal (2)], padded
+constexpr int ZF = 8;          // zone row (F <= 7), padded
+constexpr int NQ = HP / RP;    // 6 partial sums per logit
+
+// acc[r] += w * x[k][r] for the RP rows of one pass
+__device__ __forceinline__ void fma_rows(float (&acc)[RP], float w, const float *__restrict__ xk)
+{
+    const float4 *x4 = reinterpret_cast<const float4 *>(xk);
+#pragma unroll
+    for (int q = 0; q < RP / 4; ++q) {
+        const float4 v = x4[q];
+        acc[4 * q + 0] = __builtin_fmaf(w, v.x, acc[4 * q + 0]);
+        acc[4 * q + 1] = __builtin_fmaf(w, v.y, acc[4 * q + 1]);
+        acc[4 * q + 2] = __builtin_fmaf(w, v.z, acc[4 * q + 2]);
+        acc[4 * q + 3] = __builtin_fmaf(w, v.w, acc[4 * q + 3]);
+    }
+}
+
+// out[e] (+)= sum_k wt[k][j] * x[e][k] for the EB env vectors in LDS (x: [EB][stride]); b: bias, or null = accumulate
+__device__ __forceinline__ void matvec(float (&out)[EB], const float *__restrict__ wt, const float *__restrict__ b,
+                                       const float *__restrict__ x, int stride, int n_in, int j)
+{
+    if (b) {
+#pragma unroll
+        for (int e = 0; e < EB; ++e) out[e] = b[j];
+    }
+    for (int k = 0; k < n_in; ++k) {
+        const float w = wt[(size_t)k * HP + j];
+#pragma unroll
+        for (int e = 0; e < EB; ++e) out[e] = __builtin_fmaf(w, x[e * stride + k], out[e]);
+    }
+}
+
+// zone rows r0 .. r0 + RP - 1 of the workgroup's envs (row = e * Z + z) -> x0 [ZF][RP], zeros beyond
+__device__ __forceinline__ void load_rows(float *__restrict__ x0, const float *__restrict__ zone_obs, int env0, int r0,
+                                          int n_rows, int Z, int F, int j)
+{
+    for (int i = j; i < ZF * RP; i += HP) {
+        const int k = i / RP, r = i % RP, row = r0 + r;
+        float v = 0.f;
+        if (row < n_rows && k < F) {
+            const int e = row / Z, z = row - e * Z;
+            v = zone_obs[((size_t)(env0 + e) * Z + z) * F + k];
+        }
+        x0[k * RP + r] = v;
+    }
+}
+
+// acc[r] = bias[e(row)][j] + sum_k wz[k][j] row[k]
+__device__ __forceinline__ void zone_part(float (&acc)[RP], const float *__restrict__ peb, const float *__restrict__ wz,
+                                          const float *__restrict__ x0, int r0, int Z, int F, int j)
+{
+#pragma unroll
+    for (int r = 0; r < RP; ++r) {
+        const int e = min((r0 + r) / Z, EB - 1);
+        acc[r] = peb[e * HP + j];
+    }
+    for (int k = 0; k < F; ++k) fma_rows(acc, wz[(size_t)k * HP + j], x0 + k * RP);
+}
+
+__device__ __forceinline__ void store_rows(float *__restrict__ y, const float (&acc)[RP], float scale, bool live, int j)
+{
+#pragma unroll
+    for (int q = 0; q < RP / 4; ++q)
+        reinterpret_cast<float4 *>(y + j * RP)[q] =
+            live ? make_float4(scale * fmaxf(acc[4 * q], 0.f), scale * fmaxf(acc[4 * q + 1], 0.f),
+                               scale * fmaxf(acc[4 * q + 2], 0.f), scale * fmaxf(acc[4 * q + 3], 0.f))
+                 : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+__device__ __forceinline__ void lo_idle(int env, float *__restrict__ mu, float *__restrict__ stdv, float *__restrict__ value,
+                                        const MlpAction &act)
+{
+    const float2 z = make_float2(0.f, 0.f);
+    reinterpret_cast<float2 *>(mu)[env] = z;
+    reinterpret_cast<float2 *>(stdv)[env] = z;
+    value[env] = 0.f;
+    if (act.mode >= 0) reinterpret_cast<float2 *>(act.actions)[env] = z;
+}
+
+// one uniform in (0, 1) of the goal draw: Philox4x32-10 keyed by (seed, global env, step), a stream of its own (the
+// action draw of mlp_head_out.hpp uses the tag 0x4D4C50)
+__device__ __forceinline__ float goal_uniform(const HierPick &pick, int env)
+{
+    const uint64_t g = pick.env_index0 + (uint64_t)env;
+    uint32_t c[4] = { (uint32_t)g, (uint32_t)(g >> 32), pick.step_index, 0x48474Cu };
+    philox4x32_10(c, (uint32_t)pick.seed, (uint32_t)(pick.seed >> 32));
+    return ((float)(c[0] >> 8) + 0.5f) * 5.9604644775390625e-08f;
+}
+
+// LEVEL 0: HighPolicyValueModel -> out0 = logits [N][Z], out1 = value [N] (+ the goal pick)
+// LEVEL 1: LoPolicyValueModel   -> out0 = mu [N][2], out1 = std [N][2], out2 = value [N] (+ the action)
+template <int LEVEL>
+__global__ __launch_bounds__(HP) void k_hier_f32(HierF32 w, DevParams p, float *__restrict__ out0, float *__restrict__ out1,
+                                                 float *__restrict__ out2, HierPick pick, MlpAction act)
+{
+    constexpr int XIN = LEVEL ? 10 : 8;                 // [obs] or [obs, goal]
+    __shared__ __align__(16) float x0[ZF * RP];         // zone rows of the pass       [k][row]
+    __shared__ __align__(16) float y1[HP * RP];         // activations of the pass     [k][row]
+    __shared__ float xin[EB * XP];                      // per-env input
+    __shared__ float peb[EB * HP];                      // per-env bias of the zone-row layer
+    __shared__ float va[EB * HP];
+    __shared__ float vb[EB * HP];
+    __shared__ float red[NQ * RP];
+    __shared__ float lg[EB * ZENV_MAX_ZONES];
+    __shared__ float hd[EB * 8];
+    __shared__ int on[EB];
+    const int j = threadIdx.x;
+    const int h = w.h, Z = p.Z, F = p.F;
+    const bool live = j < h;                             // padded features stay exactly 0
+    const int env0 = blockIdx.x * EB;
+    const int n_env = min(EB, p.N - env0);
+    const HierEnc &E = LEVEL ? w.lo : w.hi;
+    const bool has_critic = LEVEL ? w.lo_critic : w.hi_critic;
+
+    // ---- which envs are evaluated: high -- all (forward) or those that pick a goal; low -- those with a goal
+    if (j < EB) {
+        int a = 0;
+        if (j < n_env) {
+            const int env = env0 + j;
+            if (LEVEL == 0) a = pick.mode < 0 || (p.need_goal[env] && !p.sched[env].done_state);
+            else a = p.goal[env] >= 0;
+        }
+        on[j] = a;
+    }
+    __syncthreads();
+    if (!(on[0] | on[1] | on[2] | on[3])) {
+        if (j < n_env) {
+            if (LEVEL == 0) {
+                if (pick.mode >= 0) pick.new_goal[env0 + j] = -1;
+            } else {
+                lo_idle(env0 + j, out0, out1, out2, act);
+            }
+        }
+        return;
+    }
+    if (j < EB * XP) {
+        const int e = j / XP, k = j % XP;
+        float v = 0.f;
+        if (e < n_env) {
+            const int env = env0 + e;
+            if (k < 8) {
+                v = p.obs[(size_t)env * 8 + k];
+            } else if (LEVEL == 1 && k < 10 && p.goal[env] >= 0) {
+                // get_goal(): the goal zone's centre / 3 in float64, then float32 (TSP_next_city_env.py:86-88)
+                const double2 zz = p.goal_xy[env];
+                v = (float)((k == 8 ? zz.x : zz.y) / 3.0);
+            }
+        }
+        xin[j] = v;
+    }
+    __syncthreads();
+    float t[EB];
+    matvec(t, E.w1x, E.b1, xin, XP, XIN, j);            // zone_net_.0 on [obs(, goal)] + bias: the same for every row
+#pragma unroll
+    for (int e = 0; e < EB; ++e) peb[e * HP + j] = t[e];
+
+    // ---- zone_net_.0 (zone-row columns), ReLU, zone_net_.2, ReLU on every row; rows summed per env
+    const int n_rows = n_env * Z;
+    float psum[EB];
+#pragma unroll
+    for (int e = 0; e < EB; ++e) psum[e] = 0.f;
+    const float b2 = E.b2[j];
+    for (int r0 = 0; r0 < n_rows; r0 += RP) {
+        __syncthreads();                                  // the previous pass is done with x0 / y1 (and peb is written)
+        load_rows(x0, p.zone_obs, env0, r0, n_rows, Z, F, j);
+        __syncthreads();
+        float acc[RP];
+        zone_part(acc, peb, E.w1z, x0, r0, Z, F, j);
+        store_rows(y1, acc, 1.f, live, j);
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < RP; ++r) acc[r] = b2;
+        for (int k = 0; k < h; ++k) fma_rows(acc, E.w2t[(size_t)k * HP + j], y1 + k * RP);
+#pragma unroll
+        for (int r = 0; r < RP; ++r) {
+            const int row = r0 + r;
+            const int e = row / Z;
+            const float v = fmaxf(acc[r], 0.f);
+#pragma unroll
+            for (int ee = 0; ee < EB; ++ee)
+                if (row < n_rows && e == ee) psum[ee] += v;
+        }
+    }
+
+    // ---- per env: zone_emb = zone_net_.4(mean); emb = combine_net_([obs(, goal), zone_emb])
+    __syncthreads();
+    const float inv_z = 1.0f / (float)Z;
+#pragma unroll
+    for (int e = 0; e < EB; ++e) vb[e * HP + j] = live ? psum[e] * inv_z : 0.f;
+    __syncthreads();
+    matvec(t, E.w3t, E.b3, vb, HP, h, j);
+#pragma unroll
+    for (int e = 0; e < EB; ++e) va[e * HP + j] = live ? t[e] : 0.f;
+    __syncthreads();
+    matvec(t, E.wce, E.bc, va, HP, h, j);
+    matvec(t, E.wcx, nullptr, xin, XP, XIN, j);
+#pragma unroll
+    for (int e = 0; e < EB; ++e) vb[e * HP + j] = live ? t[e] : 0.f;        // emb
+    __syncthreads();
+    float hv[EB];                                                           // critic.0(emb)
+#pragma unroll
+    for (int e = 0; e < EB; ++e) hv[e] = 0.f;
+    if (has_critic) matvec(hv, LEVEL ? w.lv1t : w.hv1t, LEVEL ? w.lv1b : w.hv1b, vb, HP, h, j);
+
+    if (LEVEL == 0) {
+        // ---- actor.0 = W_e emb + b (per env) + W_z zone row (per zone); logit = actor.2(relu(.))
+        matvec(t, w.hae, w.hab, vb, HP, h, j);
+        __syncthreads();                                  // every thread is past its zone_part reads of peb
+#pragma unroll
+        for (int e = 0; e < EB; ++e) {
+            peb[e * HP + j] = live ? t[e] : 0.f;
+            va[e * HP + j] = live ? fmaxf(hv[e], 0.f) : 0.f;
+        }
+        const float a2 = live ? w.ha2[j] : 0.f;
+        for (int r0 = 0; r0 < n_rows; r0 += RP) {
+            __syncthreads();
+            load_rows(x0, p.zone_obs, env0, r0, n_rows, Z, F, j);
+            __syncthreads();
+            float acc[RP];
+            zone_part(acc, peb, w.haz, x0, r0, Z, F, j);
+            store_rows(y1, acc, a2, live, j);            // actor.2's products, summed over the features next
+            __syncthreads();
+            {
+                const int r = j % RP, q = j / RP;
+                float s = 0.f;
+                for (int k = q * RP; k < q * RP + RP; ++k) s += y1[k * RP + r];
+                red[q * RP + r] = s;
+            }
+            __syncthreads();
+            if (j < RP && r0 + j < n_rows) {
+                float s = red[j];
+#pragma unroll
+                for (int q = 1; q < NQ; ++q) s += red[q * RP + j];
+                const int row = r0 + j, e = row / Z;
+                lg[e * ZENV_MAX_ZONES + (row - e * Z)] = s + w.ha2[HP];
+            }
+        }
+        __syncthreads();
+        if (j < n_env && on[j]) {
+            const int env = env0 + j;
+            if (has_critic) {                             // critic.2(relu(critic.0(emb)))
+                float s = w.hv2[HP];
+                for (int k = 0; k < h; ++k) s = __builtin_fmaf(w.hv2[k], va[j * HP + k], s);
+                out1[env] = s;
+            } else {
+                out1[env] = 0.f;
+            }
+            // get_hi_action: logits[~available_goals] = -inf, then Categorical(logits)
+            const uint32_t avail = p.available[env];
+            const float *L = lg + j * ZENV_MAX_ZONES;
+            float m = -INFINITY;
+            int best = -1;
+            for (int z = 0; z < Z; ++z) {
+                const float l = ((avail >> z) & 1u) ? L[z] : -INFINITY;
+                out0[(size_t)env * Z + z] = l;
+                if (l > m) {                              // strict: ties go to the lowest zone
+                    m = l;
+                    best = z;
+                }
+            }
+            if (pick.mode >= 0) {
+                int g = best;                             // -1: no available zone, the env gets no goal
+                if (pick.mode == 1 && best >= 0) {
+                    // inverse CDF of softmax over the available zones, in zone order
+                    float s = 0.f;
+                    for (int z = 0; z < Z; ++z)
+                        if ((avail >> z) & 1u) s += expf(L[z] - m);
+                    const float thr = goal_uniform(pick, env) * s;
+                    float c = 0.f;
+                    for (int z = 0; z < Z; ++z) {
+                        if (!((avail >> z) & 1u)) continue;
+                        c += expf(L[z] - m);
+                        g = z;                            // the last available zone takes what rounding leaves over
+                        if (c > thr) break;
+                    }
+                }
+                pick.new_goal[env] = g;
+            }
+        } else if (j < n_env && pick.mode >= 0) {
+            pick.new_goal[env0 + j] = -1;
+        }
+        return;
+    }
+
+    // ---- low level: a = relu(actor.enc_(emb)); mu_, std_ on a; critic.2 on relu(critic.0(emb))
+    matvec(t, w.encw, w.encb, vb, HP, h, j);
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < EB; ++e) {
+        va[e * HP + j] = live ? fmaxf(t[e], 0.f) : 0.f;
+        peb[e * HP + j] = live ? fmaxf(hv[e], 0.f) : 0.f;
+    }
+    __syncthreads();
+    if (j < EB * 8) {
+        const int e = j >> 3, row = j & 7;
+        float s = 0.f;
+        if (row < 4 || (row == 4 && has_critic)) {
+            const float *wr = row < 4 ? w.heads + (size_t)row * (HP + 1) : w.lv2;
+            const float *x = row < 4 ? va + e * HP : peb + e * HP;
+            s = wr[HP];
+            for (int k = 0; k < h; ++k) s = __builtin_fmaf(wr[k], x[k], s);
+        }
+        hd[j] = s;
+    }
+    __syncthreads();
+    if (j < n_env) {
+        const int env = env0 + j;
+        if (on[j]) {
+            const float *o = hd + 8 * j;
+            out2[env] = o[4];
+            head_outputs(env, o[0], o[1], o[2], o[3], o[4], out0, out1, act);
+        } else {
+            lo_idle(env, out0, out1, out2, act);
+        }
+    }
+}
+
+}  // namespace
+
+size_t pack_hier_f32(const zenv_hier_weights &w, int F, std::vector<float> &out, size_t offs[kHierOffs])
+{
+    const int h = w.h_dim;
+    out.clear();
+    auto put = [&](size_t n) {                             // n zero floats, 16-byte aligned start
+        const size_t at = (out.size() + 3) & ~(size_t)3;
+        out.resize(at + n, 0.f);
+        return at;
+    };
+    // columns col0 .. col0 + n_cols - 1 of W [h][in_stride], transposed -> [rows][HP] (rows >= n_cols, zero-padded)
+    auto cols = [&](const float *W, int in_stride, int col0, int n_cols, int rows) {
+        const size_t at = put((size_t)rows * HP);
+        for (int o = 0; o < h; ++o)
+            for (int k = 0; k < n_cols; ++k) out[at + (size_t)k * HP + o] = W[(size_t)o * in_stride + col0 + k];
+        return at;
+    };
+    auto bias = [&](const float *b) {
+        const size_t at = put(HP);
+        for (int o = 0; o < h; ++o) out[at + o] = b[o];
+        return at;
+    };
+    auto row = [&](const float *W, const float *b) {       // one output row: [HP] weights, bias at HP
+        const size_t at = put(HP + 1);
+        for (int k = 0; k < h; ++k) out[at + k] = W[k];
+        out[at + HP] = b[0];
+        return at;
+    };
+    int i = 0;
+    auto enc = [&](const float *w1, const float *b1, const float *w2, const float *b2, const float *w3, const float *b3,
+                   const float *wc, const float *bc, int xin) {
+        offs[i++] = cols(w1, xin + F, 0, xin, xin);         // zone_net_.0: [obs(, goal)] columns
+        offs[i++] = cols(w1, xin + F, xin, F, ZF);          //              zone-row columns
+        offs[i++] = bias(b1);
+        offs[i++] = cols(w2, h, 0, h, HP);
+        offs[i++] = bias(b2);
+        offs[i++] = cols(w3, h, 0, h, HP);
+        offs[i++] = bias(b3);
+        offs[i++] = cols(wc, xin + h, 0, xin, xin);         // combine_net_: [obs(, goal)] columns
+        offs[i++] = cols(wc, xin + h, xin, h, HP);          //               zone_emb columns
+        offs[i++] = bias(bc);
+    };
+    enc(w.hi_zone_w1, w.hi_zone_b1, w.hi_zone_w2, w.hi_zone_b2, w.hi_zone_w3, w.hi_zone_b3, w.hi_comb_w, w.hi_comb_b, 8);
+    enc(w.lo_zone_w1, w.lo_zone_b1, w.lo_zone_w2, w.lo_zone_b2, w.lo_zone_w3, w.lo_zone_b3, w.lo_comb_w, w.lo_comb_b, 10);
+    offs[i++] = cols(w.hi_actor_w1, h + F, 0, h, HP);       // actor.0: emb columns
+    offs[i++] = cols(w.hi_actor_w1, h + F, h, F, ZF);       //          zone-row columns
+    offs[i++] = bias(w.hi_actor_b1);
+    offs[i++] = row(w.hi_actor_w2, w.hi_actor_b2);
+    const bool hc = w.hi_critic_w1 != nullptr, lc = w.lo_critic_w1 != nullptr;
+    offs[i++] = hc ? cols(w.hi_critic_w1, h, 0, h, HP) : 0;
+    offs[i++] = hc ? bias(w.hi_critic_b1) : 0;
+    offs[i++] = hc ? row(w.hi_critic_w2, w.hi_critic_b2) : 0;
+    offs[i++] = cols(w.lo_enc_w, h, 0, h, HP);
+    offs[i++] = bias(w.lo_enc_b);
+    offs[i] = put(4 * (size_t)(HP + 1));                    // mu_ rows 0-1, std_ rows 2-3
+    for (int r = 0; r < 4; ++r) {
+        const float *W = r < 2 ? w.lo_mu_w + (size_t)r * h : w.lo_std_w + (size_t)(r - 2) * h;
+        const float *b = r < 2 ? w.lo_mu_b + r : w.lo_std_b + (r - 2);
+        for (int k = 0; k < h; ++k) out[offs[i] + (size_t)r * (HP + 1) + k] = W[k];
+        out[offs[i] + (size_t)r * (HP + 1) + HP] = b[0];
+    }
+    ++i;
+    offs[i++] = lc ? cols(w.lo_critic_w1, h, 0, h, HP) : 0;
+    offs[i++] = lc ? bias(w.lo_critic_b1) : 0;
+    offs[i++] = lc ? row(w.lo_critic_w2, w.lo_critic_b2) : 0;
+    return out.size();
+}
+
+hipError_t launch_hier_high(const HierF32 &w, const DevParams &p, float *logits, float *value, const HierPick &pick,
+                            hipStream_t s)
+{
+    hipLaunchKernelGGL(k_hier_f32<0>, dim3((p.N + EB - 1) / EB), dim3(HP), 0, s, w, p, logits, value, nullptr, pick,
+                       no_mlp_action());
+    return hipGetLastError();
+}
+
+hipError_t launch_hier_low(const HierF32 &w, const DevParams &p, float *mu, float *stdv, float *value,
+                           const MlpAction &act, hipStream_t s)
+{
+    const HierPick none{ -1, 0u, 0ull, 0ull, nullptr };
+    hipLaunchKernelGGL(k_hier_f32<1>, dim3((p.N + EB - 1) / EB), dim3(HP), 0, s, w, p, mu, stdv, value, none, act);
+    return hipGetLastError();
+}
+
+}  // namespace zenvk

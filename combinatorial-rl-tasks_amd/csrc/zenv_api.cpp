@@ -21,6 +21,7 @@
 #include "dev_params.hpp"
 #include "host_sampler.hpp"
 #include "kernels.hpp"
+#include "hier_f32.hpp"
 #include "mlp_policy.hpp"
 
 using namespace zenvk;
@@ -101,6 +102,11 @@ struct zenv {
     void *mlp_f32_mem = nullptr;        // float32 path (ZENV_MLP_F32): transposed float32 weights
     MlpF32 mlp_f32{};
     bool mlp_ready = false;
+    // Zone-goals hierarchical agent (zenv_hier_load): float32 weights, the high level's outputs
+    void *hier_mem = nullptr;
+    HierF32 hier{};
+    bool hier_ready = false;
+    float *hier_logits = nullptr, *hier_value = nullptr;
     // goal-conditioned variant (zenv_goal_enable)
     bool goal_enabled = false;
     bool order_enabled = false;   // solver-ordered variant (zenv_order_enable)
@@ -291,6 +297,8 @@ FieldInfo field_info(const zenv *h, int field)
     case ZENV_F_CHUNK_DONE: return { h->chunk_done, h->chunk_done ? N * h->chunk_steps : 0 };
     case ZENV_F_CHUNK_ACTIONS: return { h->chunk_actions, h->chunk_actions ? N * h->chunk_steps * 8 : 0 };
     case ZENV_F_EXCEPTION: return { p.exception, N };
+    case ZENV_F_HIER_LOGITS: return { h->hier_logits, h->hier_logits ? N * p.Z * 4 : 0 };
+    case ZENV_F_HIER_VALUE: return { h->hier_value, h->hier_value ? N * 4 : 0 };
     default: return { nullptr, 0 };
     }
 }
@@ -584,7 +592,7 @@ extern "C" int zenv_destroy(zenv_t *h)
                      (void *)h->p.visit_zone, (void *)h->p.term_xy, (void *)h->p.goal, (void *)h->p.goal_last,
                      (void *)h->p.goal_xy, (void *)h->p.shaped, (void *)h->p.need_goal, (void *)h->p.available,
                      (void *)h->goal_in, (void *)h->goal_bad, h->exp_mem, (void *)h->p.order_pos,
-                     (void *)h->p.order_val })
+                     (void *)h->p.order_val, h->hier_mem, (void *)h->hier_logits, (void *)h->hier_value })
         if (m) (void)hipFree(m);
     for (hipEvent_t ev : h->events) (void)hipEventDestroy(ev);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
@@ -1232,6 +1240,97 @@ extern "C" int zenv_mlp_forward(zenv_t *h)
     return ZENV_OK;
 }
 
+// ============================================================================ Zone-goals hierarchical agent
+extern "C" int zenv_hier_load(zenv_t *h, const zenv_hier_weights *w)
+{
+    if (!h || !w) return fail(ZENV_E_ARG, "null argument");
+    if (!h->goal_enabled) return fail(ZENV_E_STATE, "the hierarchical agent sets goals: zenv_goal_enable first");
+    if (w->h_dim < 1 || w->h_dim >= kMlpHP) return fail(ZENV_E_ARG, "h_dim %d outside 1 .. %d", w->h_dim, kMlpHP - 1);
+    if (w->precision != ZENV_MLP_F32)
+        return fail(ZENV_E_ARG, "zenv_hier_weights.precision %d: only ZENV_MLP_F32 is built", w->precision);
+    if (w->zone_feat != h->p.F)
+        return fail(ZENV_E_ARG, "the weights take zone rows of %d features, this handle's have %d", w->zone_feat, h->p.F);
+    for (const float *t : { w->hi_zone_w1, w->hi_zone_b1, w->hi_zone_w2, w->hi_zone_b2, w->hi_zone_w3, w->hi_zone_b3,
+                            w->hi_comb_w, w->hi_comb_b, w->hi_actor_w1, w->hi_actor_b1, w->hi_actor_w2, w->hi_actor_b2,
+                            w->lo_zone_w1, w->lo_zone_b1, w->lo_zone_w2, w->lo_zone_b2, w->lo_zone_w3, w->lo_zone_b3,
+                            w->lo_comb_w, w->lo_comb_b, w->lo_enc_w, w->lo_enc_b, w->lo_mu_w, w->lo_mu_b, w->lo_std_w,
+                            w->lo_std_b })
+        if (!t) return fail(ZENV_E_ARG, "zenv_hier_weights has a null tensor");
+    const int n_hc = (w->hi_critic_w1 != nullptr) + (w->hi_critic_b1 != nullptr) + (w->hi_critic_w2 != nullptr) +
+                     (w->hi_critic_b2 != nullptr);
+    const int n_lc = (w->lo_critic_w1 != nullptr) + (w->lo_critic_b1 != nullptr) + (w->lo_critic_w2 != nullptr) +
+                     (w->lo_critic_b2 != nullptr);
+    if ((n_hc != 0 && n_hc != 4) || (n_lc != 0 && n_lc != 4))
+        return fail(ZENV_E_ARG, "give all four tensors of a critic or none");
+    std::vector<float> img;
+    size_t o[kHierOffs];
+    pack_hier_f32(*w, h->p.F, img, o);
+    int rc = use_device(h);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const size_t N = (size_t)h->n_env;
+    h->hier_ready = false;
+    if (h->hier_mem) HIP_TRY(hipFree(h->hier_mem));
+    h->hier_mem = nullptr;
+    HIP_TRY(hipMalloc(&h->hier_mem, img.size() * sizeof(float)));
+    HIP_TRY(hipMemcpy(h->hier_mem, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
+    // the low level writes the flat network's output fields (ZENV_F_POLICY_*): allocated by whichever loads first
+    if (!h->mlp_value) HIP_TRY(hipMalloc((void **)&h->mlp_value, N * sizeof(float)));
+    if (!h->mlp_mu) HIP_TRY(hipMalloc((void **)&h->mlp_mu, N * 2 * sizeof(float)));
+    if (!h->mlp_std) HIP_TRY(hipMalloc((void **)&h->mlp_std, N * 2 * sizeof(float)));
+    if (!h->hier_logits) HIP_TRY(hipMalloc((void **)&h->hier_logits, N * h->p.Z * sizeof(float)));
+    if (!h->hier_value) HIP_TRY(hipMalloc((void **)&h->hier_value, N * sizeof(float)));
+    HIP_TRY(hipMemsetAsync(h->hier_logits, 0, N * h->p.Z * sizeof(float), h->stream));
+    HIP_TRY(hipMemsetAsync(h->hier_value, 0, N * sizeof(float), h->stream));
+    const float *b = static_cast<const float *>(h->hier_mem);
+    auto P = [&](int i) { return o[i] ? b + o[i] : nullptr; };   // offset 0 only for an absent critic (the image starts
+                                                                 // with hi.w1x)
+    HierF32 &hw = h->hier;
+    hw.h = w->h_dim;
+    hw.hi_critic = n_hc ? 1 : 0;
+    hw.lo_critic = n_lc ? 1 : 0;
+    hw.pad = 0;
+    HierEnc *enc[2] = { &hw.hi, &hw.lo };
+    for (int l = 0; l < 2; ++l) {
+        const int k = 10 * l;
+        *enc[l] = HierEnc{ b + o[k], P(k + 1), P(k + 2), P(k + 3), P(k + 4), P(k + 5), P(k + 6), P(k + 7), P(k + 8), P(k + 9) };
+    }
+    hw.hae = P(20); hw.haz = P(21); hw.hab = P(22); hw.ha2 = P(23);
+    hw.hv1t = P(24); hw.hv1b = P(25); hw.hv2 = P(26);
+    hw.encw = P(27); hw.encb = P(28); hw.heads = P(29);
+    hw.lv1t = P(30); hw.lv1b = P(31); hw.lv2 = P(32);
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->hier_ready = true;
+    return ZENV_OK;
+}
+
+extern "C" int zenv_hier_forward(zenv_t *h)
+{
+    if (!h) return fail(ZENV_E_ARG, "null handle");
+    if (!h->hier_ready) return fail(ZENV_E_STATE, "zenv_hier_load first");
+    if (!h->was_reset) return fail(ZENV_E_STATE, "reset before asking for actions");
+    int rc = use_device(h);
+    if (rc) return rc;
+    const HierPick none{ -1, 0u, 0ull, 0ull, nullptr };
+    HIP_TRY(launch_hier_high(h->hier, h->p, h->hier_logits, h->hier_value, none, h->stream));
+    HIP_TRY(launch_hier_low(h->hier, h->p, h->mlp_mu, h->mlp_std, h->mlp_value, no_mlp_action(), h->stream));
+    return ZENV_OK;
+}
+
+// one step of evaluate_zone_hrl.py:56-64: goals for the envs that need one (through launch_goal_set, the path of
+// zenv_set_goals), then the low level's action of every env into `out`
+static int run_hier_policy(zenv_t *h, int policy, uint32_t step_index, uint64_t seed, uint64_t env_index0, float *out)
+{
+    if (!h->hier_ready) return fail(ZENV_E_STATE, "zenv_hier_load first");
+    const int mode = policy == ZENV_POLICY_HIER_SAMPLE ? 1 : 0;
+    const HierPick pick{ mode, step_index, seed, env_index0, h->goal_in };
+    HIP_TRY(launch_hier_high(h->hier, h->p, h->hier_logits, h->hier_value, pick, h->stream));
+    HIP_TRY(launch_goal_set(h->p, h->goal_in, h->goal_bad, h->stream));
+    const MlpAction act{ mode, step_index, seed, env_index0, out, MlpRecord{} };
+    HIP_TRY(launch_hier_low(h->hier, h->p, h->mlp_mu, h->mlp_std, h->mlp_value, act, h->stream));
+    return ZENV_OK;
+}
+
 static bool policy_known(int policy) { return policy >= ZENV_POLICY_UNIFORM && policy <= ZENV_POLICY_MLP_SAMPLE; }
 static bool policy_is_mlp(int policy) { return policy == ZENV_POLICY_MLP_MEAN || policy == ZENV_POLICY_MLP_SAMPLE; }
 
@@ -1333,12 +1432,14 @@ extern "C" int zenv_policy(zenv_t *h, int policy, uint64_t policy_seed, uint64_t
 {
     if (!h) return fail(ZENV_E_ARG, "null handle");
     if (!h->was_reset) return fail(ZENV_E_STATE, "reset before asking for actions");
-    if (!policy_known(policy)) return fail(ZENV_E_ARG, "unknown policy %d", policy);
+    const bool hier = policy == ZENV_POLICY_HIER_SAMPLE || policy == ZENV_POLICY_HIER_MEAN;
+    if (!policy_known(policy) && !hier) return fail(ZENV_E_ARG, "unknown policy %d", policy);
     int rc = use_device(h);
     if (rc) return rc;
     const StepPolicy pol{ policy, (uint32_t)h->step_count, policy_seed, env_index0,
                           dst_device ? dst_device : h->p.actions };
     h->act_tag.valid = false;
+    if (hier) return run_hier_policy(h, policy, pol.step_index, policy_seed, env_index0, pol.out);
     return run_policy(h, pol);
 }
 

@@ -3,6 +3,7 @@
 100 maps (env seeds 1000000..1000099) x 5 runs per map, undiscounted episodic return,
 result layout ``{"return": [[r_run0..r_run4] for each map]}`` -- but all maps and runs are
 stepped together as one batch of n_maps*n_runs envs instead of 500 sequential episodes.
+``evaluate_zone_hrl`` does the same for zone-goals/scripts/evaluate_zone_hrl.py with the Zone-goals hierarchical agent.
 """
 import pickle
 
@@ -76,5 +77,72 @@ def evaluate(env_id, policy, n_maps=100, n_runs_per_map=5, env_seed0=EVAL_SEED0,
     env.close()
     if pkl_path:
         with open(pkl_path, "wb") as f:       # evaluate.py:76-78 writes {"return": record_returns}
+            pickle.dump({"return": out["return"]}, f)
+    return out
+
+
+# the goal-conditioned ids (zone-goals/envs/__init__.py) are the task envs of these ids with zenv_goal_enable on
+HIER_BASE_IDS = {"PointTSP-v3": "PointTSP-v0", "PointTTSP-v3": "PointTTSP-v0", "ColourMatch-v3": "ColourMatch-v0"}
+
+
+def load_hier_model_state(model):
+    """``(utils.get_hi_model_state(model_dir), utils.get_lo_model_state(model_dir))`` (zone-goals/src/utils/
+    storage.py:57-61): the ``hi_model_state`` / ``lo_model_state`` entries of a model directory's ``status.pt`` (or of
+    that file named directly)."""
+    import os
+    import torch
+    path = model if os.path.isfile(model) else os.path.join(model, "status.pt")
+    status = torch.load(path, map_location="cpu", weights_only=True)
+    for k in ("hi_model_state", "lo_model_state"):
+        if k not in status:
+            raise KeyError(f"{path} has no {k!r} (keys: {sorted(status)})")
+    return status["hi_model_state"], status["lo_model_state"]
+
+
+def evaluate_zone_hrl(env_id, model, n_maps=100, n_runs_per_map=5, env_seed0=EVAL_SEED0, policy_seed=0, argmax=False,
+                      pkl_path=None, device=0, max_steps=None):
+    """The protocol of zone-goals/scripts/evaluate_zone_hrl.py (100 maps x 5 runs, env seeds 1000000.., undiscounted
+    return) with the Zone-goals hierarchical agent on the device, every map and run stepped together as one batch.
+    Per step (:56-64): an env without a goal gets one from HighPolicyValueModel (a draw from Categorical over the
+    available zones, or the argmax with ``argmax=True``), then LoPolicyValueModel's action (``dist.sample()``, or mu).
+
+    env_id: "PointTSP-v3", "PointTTSP-v3", "ColourMatch-v3" (or any registry id / Config: goals are switched on);
+    model: a model directory, its ``status.pt``, or a ``(hi_state_dict, lo_state_dict)`` pair.
+    Returns ``{"return": [[...]], "length": [[...]], "goal_met": [[...]]}`` as ``evaluate`` does and writes
+    ``{"return": ...}`` to ``pkl_path`` (evaluate_zone_hrl.py:44, :77-79)."""
+    from .vec_env import hier_tensors_from_state_dicts
+    if isinstance(env_id, str):
+        cfg = config_for_id(HIER_BASE_IDS.get(env_id, env_id))
+    else:
+        cfg = env_id
+    hi_sd, lo_sd = load_hier_model_state(model) if isinstance(model, str) else model
+    tensors = hier_tensors_from_state_dicts(hi_sd, lo_sd)
+    n = n_maps * n_runs_per_map
+    env = ZoneVecEnv(cfg, n, device=device)
+    try:
+        env.build_bank(env_seed0, n_maps)
+        env.schedule_sequential(first=np.repeat(np.arange(n_maps, dtype=np.int32), n_runs_per_map), stride=0)
+        env.enable_goals()
+        env.reset()
+        env.load_hier(tensors)
+        policy = nat.POLICY_HIER_MEAN if argmax else nat.POLICY_HIER_SAMPLE
+        goal = np.zeros(n, bool)
+        horizon = cfg.num_steps if max_steps is None else max_steps
+        for t in range(horizon):
+            env.policy(policy, policy_seed=policy_seed)
+            env.step(None, auto_reset=False)
+            _, _, _, d, g, _ = env.step_results(None, copy=False)
+            goal |= g
+            if d.all():                    # every episode finished (evaluate_zone_hrl.py:66-75)
+                break
+        out = {
+            "return": env.get(nat.F_LAST_RETURN).reshape(n_maps, n_runs_per_map).tolist(),
+            "length": env.get(nat.F_LAST_LEN).reshape(n_maps, n_runs_per_map).tolist(),
+            "goal_met": goal.reshape(n_maps, n_runs_per_map).tolist(),
+        }
+    finally:
+        env.close()
+    if pkl_path:
+        with open(pkl_path, "wb") as f:
             pickle.dump({"return": out["return"]}, f)
     return out

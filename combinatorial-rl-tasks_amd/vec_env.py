@@ -23,6 +23,7 @@ _FIELD_DTYPES = {
     nat.F_POLICY_VALUE: np.float32, nat.F_SHAPED_REWARD: np.float64, nat.F_NEED_GOAL: np.uint8,
     nat.F_AVAILABLE_GOALS: np.uint32, nat.F_GOAL: np.int32, nat.F_ORDER_VAL: np.float32,
     nat.F_EXCEPTION: np.uint8, nat.F_POLICY_VALUE_SIGMA: np.float32, nat.F_ORDER_POS: np.int8,
+    nat.F_HIER_LOGITS: np.float32, nat.F_HIER_VALUE: np.float32,
 }
 
 
@@ -86,6 +87,56 @@ def mlp_tensors_from_state_dict(sd):
                       "critic_sigma_w": "critic_sigma.weight", "critic_sigma_b": "critic_sigma.bias"})
     return {k: np.asarray(sd[v].detach().cpu().numpy() if hasattr(sd[v], "detach") else sd[v], np.float32)
             for k, v in names.items()}
+
+
+# zenv_hier_weights name -> state_dict key (zone-goals/src/hier_policy_value_models.py:19-86, env_model.py:48-116,
+# policy_network.py:9-62): hi_model_state and lo_model_state of status.pt (zone-goals/src/utils/storage.py:57-61)
+_HIER_ENC = {"zone_w1": "env_model.zone_net_.0.weight", "zone_b1": "env_model.zone_net_.0.bias",
+             "zone_w2": "env_model.zone_net_.2.weight", "zone_b2": "env_model.zone_net_.2.bias",
+             "zone_w3": "env_model.zone_net_.4.weight", "zone_b3": "env_model.zone_net_.4.bias",
+             "comb_w": "env_model.combine_net_.weight", "comb_b": "env_model.combine_net_.bias"}
+_HIER_CRITIC = {"critic_w1": "critic.0.weight", "critic_b1": "critic.0.bias",
+                "critic_w2": "critic.2.weight", "critic_b2": "critic.2.bias"}
+HIER_HI_KEYS = dict(_HIER_ENC, actor_w1="actor.0.weight", actor_b1="actor.0.bias", actor_w2="actor.2.weight",
+                    actor_b2="actor.2.bias")
+HIER_LO_KEYS = dict(_HIER_ENC, enc_w="actor.enc_.0.0.weight", enc_b="actor.enc_.0.0.bias", mu_w="actor.mu_.weight",
+                    mu_b="actor.mu_.bias", std_w="actor.std_.weight", std_b="actor.std_.bias")
+
+
+def hier_tensor_shapes(h, F):
+    """The shape of every zenv_hier_weights tensor for hidden size h and zone rows of F features."""
+    enc = lambda x: {"zone_w1": (h, x + F), "zone_b1": (h,), "zone_w2": (h, h), "zone_b2": (h,), "zone_w3": (h, h),
+                     "zone_b3": (h,), "comb_w": (h, x + h), "comb_b": (h,)}
+    crit = {"critic_w1": (h, h), "critic_b1": (h,), "critic_w2": (1, h), "critic_b2": (1,)}
+    hi = dict(enc(8), actor_w1=(h, h + F), actor_b1=(h,), actor_w2=(1, h), actor_b2=(1,), **crit)
+    lo = dict(enc(10), enc_w=(h, h), enc_b=(h,), mu_w=(2, h), mu_b=(2,), std_w=(2, h), std_b=(2,), **crit)
+    return dict({"hi_" + k: v for k, v in hi.items()}, **{"lo_" + k: v for k, v in lo.items()})
+
+
+def hier_tensors_from_state_dicts(hi_sd, lo_sd):
+    """HighPolicyValueModel.state_dict() and LoPolicyValueModel.state_dict() -> the tensors ``ZoneVecEnv.load_hier``
+    wants (numpy float32, names of ``_native.HIER_*``).  The critics are taken when present (critic.0 and critic.2
+    both).  A missing key or a tensor whose shape does not fit the others raises ValueError naming it."""
+    out = {}
+    for level, sd, keys in (("hi", hi_sd, HIER_HI_KEYS), ("lo", lo_sd, HIER_LO_KEYS)):
+        names = dict(keys)
+        if "critic.0.weight" in sd or "critic.2.weight" in sd:
+            names.update(_HIER_CRITIC)
+        for name, key in names.items():
+            if key not in sd:
+                raise ValueError(f"{level}_model_state has no {key!r} (needed for {level}_{name})")
+            v = sd[key]
+            out[f"{level}_{name}"] = np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, np.float32)
+    h = out["hi_zone_b1"].shape[0] if out["hi_zone_b1"].ndim == 1 else -1
+    F = out["hi_zone_w1"].shape[1] - 8 if out["hi_zone_w1"].ndim == 2 else -1
+    want = hier_tensor_shapes(h, F)
+    for name, a in out.items():
+        if a.shape != want[name]:
+            level, rest = name.split("_", 1)
+            key = (HIER_HI_KEYS if level == "hi" else HIER_LO_KEYS).get(rest) or _HIER_CRITIC[rest]
+            raise ValueError(f"{level}_model_state[{key!r}] has shape {tuple(a.shape)}, expected {want[name]} "
+                             f"(hidden size {h}, zone rows of {F} features)")
+    return out
 
 
 def zone_feat(cfg):
@@ -425,6 +476,39 @@ class ZoneVecEnv:
                 out += (self.get(nat.F_POLICY_VALUE_SIGMA),)
         return out
 
+    # ------------------------------------------------------------------ Zone-goals hierarchical agent
+    def load_hier(self, tensors, precision="f32"):
+        """HighPolicyValueModel + LoPolicyValueModel (zone-goals/src/hier_policy_value_models.py:19-86) for
+        ``hier_forward`` and the device policies POLICY_HIER_SAMPLE / POLICY_HIER_MEAN.  tensors: dict of float32
+        arrays named as in ``_native.HIER_*`` (see ``hier_tensors_from_state_dicts``); each critic is optional.  Needs
+        ``enable_goals()`` first.  precision: "f32" (the only one built: float32 throughout, within 1e-5 of torch)."""
+        if precision != "f32":
+            raise ValueError(f"precision {precision!r}: the hierarchical agent is built in float32 only")
+        h = int(np.asarray(tensors["hi_zone_b1"]).shape[0])
+        F = int(np.asarray(tensors["hi_zone_w1"]).shape[1]) - 8
+        want = hier_tensor_shapes(h, F)
+        names = nat.HIER_HI_TENSORS + nat.HIER_LO_TENSORS + (
+            nat.HIER_HI_CRITIC if "hi_critic_w1" in tensors else ()) + (
+            nat.HIER_LO_CRITIC if "lo_critic_w1" in tensors else ())
+        w = nat.HierWeights(h_dim=h, precision=nat.MLP_F32, zone_feat=F)
+        keep = {}
+        for name in names:
+            a = np.ascontiguousarray(tensors[name], np.float32)
+            if a.shape != want[name]:
+                raise ValueError(f"{name}: shape {a.shape}, expected {want[name]}")
+            keep[name] = a
+            setattr(w, name, a.ctypes.data)
+        check(lib().zenv_hier_load(self._h, C.byref(w)))
+        self._hier_critics = ("hi_critic_w1" in tensors, "lo_critic_w1" in tensors)
+
+    def hier_forward(self):
+        """Both networks on the current observations: (logits float32 [N,Z] with -inf at unavailable zones, high-level
+        value [N], mu [N,2], std [N,2], low-level value [N]); the low level towards each env's current goal, zeros for
+        an env without one.  Values are 0 without the critic tensors."""
+        check(lib().zenv_hier_forward(self._h))
+        return (self.get(nat.F_HIER_LOGITS), self.get(nat.F_HIER_VALUE), self.get(nat.F_POLICY_MU),
+                self.get(nat.F_POLICY_STD), self.get(nat.F_POLICY_VALUE))
+
     # ------------------------------------------------------------------ one PPO rollout (SURVEY 8(f) row 2)
     def collect(self, frames_per_proc, policy_seed=1, env_index0=0, discount=0.99, gae_lambda=0.95):
         """BaseAlgo.collect_experiences (main/src/torch_ac/algos/base.py:131-227) on the device with the loaded
@@ -522,7 +606,7 @@ class ZoneVecEnv:
         N = self.num_envs
         if field == nat.F_OBS:
             return (N, nat.OBS_DIM)
-        if field in (nat.F_ORDER_VAL, nat.F_ORDER_POS):
+        if field in (nat.F_ORDER_VAL, nat.F_ORDER_POS, nat.F_HIER_LOGITS):
             return (N, self.num_zones)
         if field == nat.F_ZONE_OBS:
             return (N, self.num_zones, self.zone_feat)

@@ -91,7 +91,12 @@ enum {
     ZENV_F_CHUNK_DONE = 34,      /* uint8   [K,N] */
     ZENV_F_CHUNK_ACTIONS = 35,   /* float32 [K,N,2]  the device copy of the last chunk whose actions came from the host (a caller that
                                   *                    replays it passes zenv_device_ptr() of this field back, actions_on_device = 1) */
-    ZENV_F_COUNT = 36
+    /* Zone-goals hierarchical agent (zenv_hier_load): */
+    ZENV_F_HIER_LOGITS = 36,     /* float32 [N,Z]    the high level's logit of every zone, -INFINITY where the zone is not an
+                                  *                    available goal (hier_agent.py get_hi_action: logits[~available] = -inf);
+                                  *                    unnormalised: actor.2's output, not Categorical's log-softmax */
+    ZENV_F_HIER_VALUE = 37,      /* float32 [N]      the high level's critic value (0 without critic tensors) */
+    ZENV_F_COUNT = 38
 };
 
 /* scripted on-device action sources (the build's own; used by bench/tests) */
@@ -99,7 +104,11 @@ enum {
     ZENV_POLICY_UNIFORM = 0,
     ZENV_POLICY_GREEDY = 1,
     ZENV_POLICY_MLP_MEAN = 2,   /* a = mu of the loaded actor network (zenv_mlp_load) */
-    ZENV_POLICY_MLP_SAMPLE = 3  /* a ~ Normal(mu, std), the reference's dist.sample() (utils/agent.py:41-44) */
+    ZENV_POLICY_MLP_SAMPLE = 3, /* a ~ Normal(mu, std), the reference's dist.sample() (utils/agent.py:41-44) */
+    /* the Zone-goals hierarchical agent (zenv_hier_load; goal-conditioned handles only), see zenv_hier_forward */
+    ZENV_POLICY_HIER_SAMPLE = 4, /* goal ~ Categorical(masked logits), a ~ Normal(mu, std): HierAgent.get_hi_action /
+                                  * get_lo_action (zone-goals/src/utils/hier_agent.py) */
+    ZENV_POLICY_HIER_MEAN = 5    /* goal = argmax of the masked logits (ties: lowest zone), a = mu: deterministic */
 };
 
 /* kernel layouts */
@@ -365,6 +374,61 @@ int zenv_mlp_load(zenv_t *h, const zenv_mlp_weights *w);
  * ZENV_F_POLICY_MU / ZENV_F_POLICY_STD (and value = critic(x) into ZENV_F_POLICY_VALUE).  zenv_policy() / zenv_rollout() with ZENV_POLICY_MLP_* call it
  * and turn it into actions (rollouts then run one launch sequence per step). */
 int zenv_mlp_forward(zenv_t *h);
+
+/* ---- the Zone-goals hierarchical agent on the device ----
+ * HighPolicyValueModel and LoPolicyValueModel (zone-goals/src/hier_policy_value_models.py:19-86) with the per-step loop
+ * of zone-goals/scripts/evaluate_zone_hrl.py:52-75: an env without a goal gets one from the high level (set_goal), then
+ * the low level acts towards it.  Checkpoint: status.pt's hi_model_state / lo_model_state (zone-goals/src/utils/
+ * storage.py:57-61).  h = hidden size (--hidden-size, 128 by default), F = zenv_zone_feat(cfg), goal_dim = 2.
+ *   high:  emb = ZoneEnvModel(obs, zone_obs) (zone-goals/src/env_model.py:48-80); for every zone z
+ *          logit_z = actor.2(relu(actor.0([emb, zone_obs[z]]))); value = critic.2(relu(critic.0(emb))).  One actor serves
+ *          every zone, so the weights fit any zone count.
+ *   low:   goal = zone_xy[goal] / 3 (float64, then float32: TSP_next_city_env.py:86-88, colour_match_next_city_env.py:
+ *          143-145); emb = ZoneEnvGoalModel(obs, goal, zone_obs) (env_model.py:82-116: ZoneEnvModel on [obs, goal]);
+ *          Normal(mu, std) = PolicyNetwork(emb) (policy_network.py:40-53); value = critic.2(relu(critic.0(emb))).
+ * Host float32 tensors in the state_dict's layout (row-major [out][in]); each critic is optional (all four of it NULL =
+ * no value output, 0 is written).  These weights are separate from zenv_mlp_load's: loading one leaves the other. */
+typedef struct zenv_hier_weights {
+    int32_t h_dim;                        /* 1 .. 191 */
+    int32_t precision;                    /* ZENV_MLP_F32 only: the float32 vector-ALU kernels of hier_f32.hip */
+    int32_t zone_feat;                    /* F the weights were built for (zone_net_.0 has 8 + F / 10 + F columns) */
+    int32_t pad;
+    /* hi_model_state (HighPolicyValueModel) */
+    const float *hi_zone_w1, *hi_zone_b1; /* env_model.zone_net_.0  [h, 8+F], [h]   input = [obs, zone row] */
+    const float *hi_zone_w2, *hi_zone_b2; /* env_model.zone_net_.2  [h, h],   [h] */
+    const float *hi_zone_w3, *hi_zone_b3; /* env_model.zone_net_.4  [h, h],   [h] */
+    const float *hi_comb_w, *hi_comb_b;   /* env_model.combine_net_ [h, 8+h], [h]   input = [obs, zone_emb] */
+    const float *hi_actor_w1, *hi_actor_b1; /* actor.0              [h, h+F], [h]   input = [emb, zone row] */
+    const float *hi_actor_w2, *hi_actor_b2; /* actor.2              [1, h],   [1] */
+    const float *hi_critic_w1, *hi_critic_b1; /* critic.0           [h, h],   [h]   (optional) */
+    const float *hi_critic_w2, *hi_critic_b2; /* critic.2           [1, h],   [1]   (optional) */
+    /* lo_model_state (LoPolicyValueModel) */
+    const float *lo_zone_w1, *lo_zone_b1; /* env_model.zone_net_.0  [h, 10+F], [h]  input = [obs, goal, zone row] */
+    const float *lo_zone_w2, *lo_zone_b2; /* env_model.zone_net_.2  [h, h],   [h] */
+    const float *lo_zone_w3, *lo_zone_b3; /* env_model.zone_net_.4  [h, h],   [h] */
+    const float *lo_comb_w, *lo_comb_b;   /* env_model.combine_net_ [h, 10+h], [h]  input = [obs, goal, zone_emb] */
+    const float *lo_enc_w, *lo_enc_b;     /* actor.enc_.0.0         [h, h],   [h] */
+    const float *lo_mu_w, *lo_mu_b;       /* actor.mu_              [2, h],   [2] */
+    const float *lo_std_w, *lo_std_b;     /* actor.std_             [2, h],   [2] */
+    const float *lo_critic_w1, *lo_critic_b1; /* critic.0           [h, h],   [h]   (optional) */
+    const float *lo_critic_w2, *lo_critic_b2; /* critic.2           [1, h],   [1]   (optional) */
+} zenv_hier_weights;
+/* ZENV_E_STATE on a handle without zenv_goal_enable(); ZENV_E_ARG for h_dim outside 1 .. 191, a zone_feat other than the
+ * handle's F, a precision other than ZENV_MLP_F32, a null actor tensor or a critic given in part. */
+int zenv_hier_load(zenv_t *h, const zenv_hier_weights *w);
+/* Both networks on the current observations, every env:
+ *   ZENV_F_HIER_LOGITS / ZENV_F_HIER_VALUE  the high level (masked with ZENV_F_AVAILABLE_GOALS)
+ *   ZENV_F_POLICY_MU / _STD / _VALUE        the low level towards the env's current goal (ZENV_F_GOAL); an env without
+ *                                           a goal gets 0 in all three.
+ * zenv_policy(ZENV_POLICY_HIER_*) runs the same two networks as one step of evaluate_zone_hrl.py:56-64, on the device:
+ * every env that needs a goal (ZENV_F_NEED_GOAL) and is not finished (left alone by step_no_reset) picks one among its
+ * available zones -- through the path of zenv_set_goals (last_dist_to_goal, need flag, validity), so that the step that
+ * follows equals zenv_set_goals(those goals) + zenv_step(those actions) -- then the low level writes the action of
+ * every env (0 for an env without a goal, e.g. one with no available zone: not an error).  The high level is evaluated
+ * only for the envs that pick: ZENV_F_HIER_LOGITS / _VALUE are refreshed for those.  Randomness: Philox keyed by
+ * (policy_seed, env_index0 + env, zenv_step_count) with separate streams for the goal and the action draw.  No host
+ * synchronisation.  zenv_rollout() / zenv_collect() do not take these policies. */
+int zenv_hier_forward(zenv_t *h);
 
 /* ---- one PPO rollout on the device: BaseAlgo.collect_experiences, main/src/torch_ac/algos/base.py:131-227 ----
  * T times: (dist, value) = acmodel(obs) [zenv_mlp_forward]; action = dist.sample(); record obs, action, value,
