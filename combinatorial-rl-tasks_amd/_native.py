@@ -34,7 +34,9 @@ E_ARG, E_HIP, E_STATE, E_LAYOUT, E_DONE, E_RANGE = -1, -2, -3, -4, -5, -6
  F_SHAPED_REWARD, F_NEED_GOAL, F_AVAILABLE_GOALS, F_GOAL,
  F_EXP_OBS, F_EXP_ZONE_OBS, F_EXP_ACTION, F_EXP_LOG_PROB, F_EXP_VALUE, F_EXP_REWARD, F_EXP_MASK,
  F_EXP_ADVANTAGE, F_EXP_RETURN, F_ORDER_VAL, F_EXCEPTION, F_POLICY_VALUE_SIGMA, F_ORDER_POS,
- F_CHUNK_REWARD, F_CHUNK_DONE, F_CHUNK_ACTIONS, F_HIER_LOGITS, F_HIER_VALUE) = range(38)
+ F_CHUNK_REWARD, F_CHUNK_DONE, F_CHUNK_ACTIONS, F_HIER_LOGITS, F_HIER_VALUE,
+ F_LO_GOAL, F_LO_ENV_REWARD, F_HI_OBS, F_HI_ZONE_OBS, F_HI_ACTION, F_HI_ACTION_MASK, F_HI_VALUE, F_HI_LOG_PROB,
+ F_HI_ADVANTAGE, F_HI_RETURN, F_HI_REWARD, F_HI_MASK, F_HI_COUNT) = range(51)
 (RESULT_OBS, RESULT_REWARD, RESULT_DONE, RESULT_GOAL_MET, RESULT_EXCEPTION, RESULT_ZONE_OBS) = range(6)
 N_RESULTS = 6
 
@@ -130,6 +132,8 @@ _PROTOTYPES = {
                                C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "zenv_set_rollout_slice": (C.c_int, [_H, C.c_int]),
     "zenv_collect": (C.c_int, [_H, C.c_int, C.c_uint64, C.c_uint64, C.c_float, C.c_float]),
+    "zenv_collect_hier": (C.c_int, [_H, C.c_int, C.c_uint64, C.c_uint64, C.c_float, C.c_float,
+                                    C.POINTER(C.c_int64)]),
     "zenv_order_enable": (C.c_int, [_H]),
     "zenv_order_configure": (C.c_int, [_H, C.c_int]),
     "zenv_route_ranks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),

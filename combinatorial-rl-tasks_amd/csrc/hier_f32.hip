@@ -106,7 +106,32 @@ __device__ __forceinline__ void lo_idle(int env, float *__restrict__ mu, float *
     reinterpret_cast<float2 *>(mu)[env] = z;
     reinterpret_cast<float2 *>(stdv)[env] = z;
     value[env] = 0.f;
-    if (act.mode >= 0) reinterpret_cast<float2 *>(act.actions)[env] = z;
+    if (act.mode < 0) return;
+    reinterpret_cast<float2 *>(act.actions)[env] = z;
+    // zenv_collect_hier: frame t of an env without a goal -- action 0, log_prob 0, value 0; mask and the reward of frame
+    // t-1 as head_outputs records them
+    const MlpRecord &rc = act.rec;
+    if (!rc.action) return;
+    const size_t slot = (size_t)rc.t * rc.N + env;
+    reinterpret_cast<float2 *>(rc.action)[slot] = z;
+    reinterpret_cast<float2 *>(rc.log_prob)[slot] = z;
+    rc.value[slot] = 0.f;
+    if (rc.t == 0) {
+        rc.mask[slot] = rc.cur_mask[env];
+    } else {
+        rc.mask[slot] = rc.prev_done[env] ? 0.f : 1.f;
+        rc.reward[slot - rc.N] = rc.prev_shaped ? (float)rc.prev_shaped[env] : rc.prev_reward[env];
+    }
+}
+
+// zenv_collect_hier: the low level's goal input of frame t, cur_goal of _hier_policy_opt.py -- the last goal's centre / 3
+// (goal_xy survives the goal's clearing and the auto-reset), 0 before the first goal
+__device__ __forceinline__ void lo_record_goal(const DevParams &p, const HierRecord &rec, int env)
+{
+    if (!rec.lo_goal) return;
+    const double2 zz = p.goal_xy[env];
+    reinterpret_cast<float2 *>(rec.lo_goal)[(size_t)rec.t * rec.N + env] =
+        make_float2((float)(zz.x / 3.0), (float)(zz.y / 3.0));
 }
 
 // one uniform in (0, 1) of the goal draw: Philox4x32-10 keyed by (seed, global env, step), a stream of its own (the
@@ -123,7 +148,7 @@ __device__ __forceinline__ float goal_uniform(const HierPick &pick, int env)
 // LEVEL 1: LoPolicyValueModel   -> out0 = mu [N][2], out1 = std [N][2], out2 = value [N] (+ the action)
 template <int LEVEL>
 __global__ __launch_bounds__(HP) void k_hier_f32(HierF32 w, DevParams p, float *__restrict__ out0, float *__restrict__ out1,
-                                                 float *__restrict__ out2, HierPick pick, MlpAction act)
+                                                 float *__restrict__ out2, HierPick pick, MlpAction act, HierRecord rec)
 {
     constexpr int XIN = LEVEL ? 10 : 8;                 // [obs] or [obs, goal]
     __shared__ __align__(16) float x0[ZF * RP];         // zone rows of the pass       [k][row]
@@ -161,6 +186,7 @@ __global__ __launch_bounds__(HP) void k_hier_f32(HierF32 w, DevParams p, float *
                 if (pick.mode >= 0) pick.new_goal[env0 + j] = -1;
             } else {
                 lo_idle(env0 + j, out0, out1, out2, act);
+                lo_record_goal(p, rec, env0 + j);
             }
         }
         return;
@@ -234,6 +260,21 @@ __global__ __launch_bounds__(HP) void k_hier_f32(HierF32 w, DevParams p, float *
     for (int e = 0; e < EB; ++e) hv[e] = 0.f;
     if (has_critic) matvec(hv, LEVEL ? w.lv1t : w.hv1t, LEVEL ? w.lv1b : w.hv1b, vb, HP, h, j);
 
+    if (LEVEL == 0 && pick.mode == -2) {                  // the critic only: value = critic.2(relu(critic.0(emb)))
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < EB; ++e) va[e * HP + j] = live ? fmaxf(hv[e], 0.f) : 0.f;
+        __syncthreads();
+        if (j < n_env) {
+            float s = 0.f;
+            if (has_critic) {
+                s = w.hv2[HP];
+                for (int k = 0; k < h; ++k) s = __builtin_fmaf(w.hv2[k], va[j * HP + k], s);
+            }
+            out1[env0 + j] = s;
+        }
+        return;
+    }
     if (LEVEL == 0) {
         // ---- actor.0 = W_e emb + b (per env) + W_z zone row (per zone); logit = actor.2(relu(.))
         matvec(t, w.hae, w.hab, vb, HP, h, j);
@@ -292,11 +333,13 @@ __global__ __launch_bounds__(HP) void k_hier_f32(HierF32 w, DevParams p, float *
             }
             if (pick.mode >= 0) {
                 int g = best;                             // -1: no available zone, the env gets no goal
-                if (pick.mode == 1 && best >= 0) {
-                    // inverse CDF of softmax over the available zones, in zone order
-                    float s = 0.f;
+                float s = 0.f;                            // sum of exp(l - max) over the available zones
+                if (best >= 0 && (pick.mode == 1 || rec.goal)) {
                     for (int z = 0; z < Z; ++z)
                         if ((avail >> z) & 1u) s += expf(L[z] - m);
+                }
+                if (pick.mode == 1 && best >= 0) {
+                    // inverse CDF of softmax over the available zones, in zone order
                     const float thr = goal_uniform(pick, env) * s;
                     float c = 0.f;
                     for (int z = 0; z < Z; ++z) {
@@ -307,6 +350,16 @@ __global__ __launch_bounds__(HP) void k_hier_f32(HierF32 w, DevParams p, float *
                     }
                 }
                 pick.new_goal[env] = g;
+                if (rec.goal && g >= 0) {
+                    // zenv_collect_hier: a high-level transition opens -- Categorical(masked logits).log_prob(goal) is
+                    // the log-softmax over the available zones
+                    const size_t slot = (size_t)rec.t * rec.N + env;
+                    rec.goal[slot] = g;
+                    rec.value[slot] = out1[env];
+                    rec.log_prob[slot] = (L[g] - m) - logf(s);
+                    rec.avail[slot] = avail;
+                    rec.open[env] = 1;
+                }
             }
         } else if (j < n_env && pick.mode >= 0) {
             pick.new_goal[env0 + j] = -1;
@@ -344,6 +397,7 @@ __global__ __launch_bounds__(HP) void k_hier_f32(HierF32 w, DevParams p, float *
         } else {
             lo_idle(env, out0, out1, out2, act);
         }
+        lo_record_goal(p, rec, env);
     }
 }
 
@@ -417,18 +471,18 @@ size_t pack_hier_f32(const zenv_hier_weights &w, int F, std::vector<float> &out,
 }
 
 hipError_t launch_hier_high(const HierF32 &w, const DevParams &p, float *logits, float *value, const HierPick &pick,
-                            hipStream_t s)
+                            hipStream_t s, const HierRecord &rec)
 {
     hipLaunchKernelGGL(k_hier_f32<0>, dim3((p.N + EB - 1) / EB), dim3(HP), 0, s, w, p, logits, value, nullptr, pick,
-                       no_mlp_action());
+                       no_mlp_action(), rec);
     return hipGetLastError();
 }
 
 hipError_t launch_hier_low(const HierF32 &w, const DevParams &p, float *mu, float *stdv, float *value,
-                           const MlpAction &act, hipStream_t s)
+                           const MlpAction &act, hipStream_t s, const HierRecord &rec)
 {
     const HierPick none{ -1, 0u, 0ull, 0ull, nullptr };
-    hipLaunchKernelGGL(k_hier_f32<1>, dim3((p.N + EB - 1) / EB), dim3(HP), 0, s, w, p, mu, stdv, value, none, act);
+    hipLaunchKernelGGL(k_hier_f32<1>, dim3((p.N + EB - 1) / EB), dim3(HP), 0, s, w, p, mu, stdv, value, none, act, rec);
     return hipGetLastError();
 }
 

@@ -114,6 +114,16 @@ struct zenv {
     // experience buffers (zenv_collect)
     ExpBuffers exp{};
     void *exp_mem = nullptr;
+    // zenv_collect_hier: the per-frame records of one call (T), the state that lives from call to call, the flat
+    // high-level output (capacity hi_cap rows, hi_m of them written by the last call)
+    HierFrames hframes{};
+    void *hframes_mem = nullptr;
+    HierCarry hcarry{};
+    void *hcarry_mem = nullptr;
+    HierOut hout{};
+    void *hout_mem = nullptr;
+    int64_t hi_cap = 0, hi_m = 0;
+    int32_t *hi_total_host = nullptr;   // page-locked word M is read back into
     // staging of zenv_bank_update (page-locked host image + its device copy)
     void *refill_host = nullptr, *refill_dev = nullptr;
     size_t refill_cap = 0;
@@ -299,6 +309,19 @@ FieldInfo field_info(const zenv *h, int field)
     case ZENV_F_EXCEPTION: return { p.exception, N };
     case ZENV_F_HIER_LOGITS: return { h->hier_logits, h->hier_logits ? N * p.Z * 4 : 0 };
     case ZENV_F_HIER_VALUE: return { h->hier_value, h->hier_value ? N * 4 : 0 };
+    case ZENV_F_LO_GOAL: return { h->hframes.lo_goal, h->hframes.lo_goal ? N * h->hframes.T * 2 * 4 : 0 };
+    case ZENV_F_LO_ENV_REWARD: return { h->hframes.env_reward, h->hframes.env_reward ? N * h->hframes.T * 4 : 0 };
+    case ZENV_F_HI_OBS: return { h->hout.obs, h->hi_m * 8 * 4 };
+    case ZENV_F_HI_ZONE_OBS: return { h->hout.zone_obs, h->hi_m * p.Z * p.F * 4 };
+    case ZENV_F_HI_ACTION: return { h->hout.action, h->hi_m * 4 };
+    case ZENV_F_HI_ACTION_MASK: return { h->hout.action_mask, h->hi_m * p.Z };
+    case ZENV_F_HI_VALUE: return { h->hout.value, h->hi_m * 4 };
+    case ZENV_F_HI_LOG_PROB: return { h->hout.log_prob, h->hi_m * 4 };
+    case ZENV_F_HI_ADVANTAGE: return { h->hout.advantage, h->hi_m * 4 };
+    case ZENV_F_HI_RETURN: return { h->hout.returnn, h->hi_m * 4 };
+    case ZENV_F_HI_REWARD: return { h->hout.reward, h->hi_m * 4 };
+    case ZENV_F_HI_MASK: return { h->hout.mask, h->hi_m * 4 };
+    case ZENV_F_HI_COUNT: return { h->hframes.count, h->hframes.count ? N * 4 : 0 };
     default: return { nullptr, 0 };
     }
 }
@@ -585,6 +608,7 @@ extern "C" int zenv_destroy(zenv_t *h)
     if (h->chunk_mem) (void)hipFree(h->chunk_mem);
     if (h->refill_host) (void)hipHostFree(h->refill_host);
     if (h->mlp_range_flag) (void)hipHostFree(h->mlp_range_flag);
+    if (h->hi_total_host) (void)hipHostFree(h->hi_total_host);
     if (h->refill_dev) (void)hipFree(h->refill_dev);
     if (h->refill_done) (void)hipEventDestroy(h->refill_done);
     for (void *m : { h->mlp_mem, h->mlp_f32_mem, (void *)h->mlp_value_sigma, h->mlp_pooled, (void *)h->mlp_mu,
@@ -592,7 +616,8 @@ extern "C" int zenv_destroy(zenv_t *h)
                      (void *)h->p.visit_zone, (void *)h->p.term_xy, (void *)h->p.goal, (void *)h->p.goal_last,
                      (void *)h->p.goal_xy, (void *)h->p.shaped, (void *)h->p.need_goal, (void *)h->p.available,
                      (void *)h->goal_in, (void *)h->goal_bad, h->exp_mem, (void *)h->p.order_pos,
-                     (void *)h->p.order_val, h->hier_mem, (void *)h->hier_logits, (void *)h->hier_value })
+                     (void *)h->p.order_val, h->hier_mem, (void *)h->hier_logits, (void *)h->hier_value,
+                     h->hframes_mem, h->hcarry_mem, h->hout_mem })
         if (m) (void)hipFree(m);
     for (hipEvent_t ev : h->events) (void)hipEventDestroy(ev);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
@@ -928,6 +953,7 @@ extern "C" int zenv_reset(zenv_t *h, const uint8_t *mask)
     HIP_TRY(launch_reset(h->p, dmask, h->stream));
     if (h->goal_enabled) HIP_TRY(launch_goal_clear(h->p, dmask, h->stream));
     if (h->order_enabled) HIP_TRY(launch_order_reset(h->p, dmask, h->stream));
+    if (h->hcarry_mem) HIP_TRY(launch_hier_reset(h->hcarry, dmask, h->n_env, h->stream));
     h->was_reset = true;
     return ZENV_OK;
 }
@@ -1351,20 +1377,10 @@ static int run_policy(zenv_t *h, const StepPolicy &pol, const MlpRecord *rec = n
 }
 
 // ============================================================================ experience collection
-extern "C" int zenv_collect(zenv_t *h, int T, uint64_t policy_seed, uint64_t env_index0, float discount, float gae_lambda)
+// the ZENV_F_EXP_* buffers for T frames (zenv_collect, zenv_collect_hier); self.mask survives a change of T
+static int ensure_exp(zenv_t *h, int T)
 {
-    if (!h) return fail(ZENV_E_ARG, "null handle");
-    if (T < 1) return fail(ZENV_E_ARG, "frames_per_proc must be positive");
-    if (!h->was_reset) return fail(ZENV_E_STATE, "Environment must be reset before stepping");
-    if (!h->mlp_ready || !h->mlp.wv1) return fail(ZENV_E_STATE, "zenv_mlp_load with actor and critic weights first");
-    if (h->host_io_slab) return fail(ZENV_E_STATE, "zenv_collect records on the device: switch zenv_host_io off first");
-    if (h->order_enabled)
-        return fail(ZENV_E_STATE, "solver-ordered envs are stepped with zenv_step (their order feature is not part of "
-                                  "the network input this call evaluates)");
-    int rc = use_device(h);
-    if (rc) return rc;
     const size_t N = (size_t)h->n_env, ZF = (size_t)h->p.Z * h->p.F;
-    h->act_tag.valid = false;
     if (!h->exp_mem || h->exp.T != T) {
         HIP_TRY(hipStreamSynchronize(h->stream));
         std::vector<float> keep_mask;
@@ -1393,6 +1409,25 @@ extern "C" int zenv_collect(zenv_t *h, int T, uint64_t policy_seed, uint64_t env
         if (keep_mask.empty()) keep_mask.assign(N, 1.0f);      // base.py:96 self.mask = ones
         HIP_TRY(hipMemcpy(x.cur_mask, keep_mask.data(), N * 4, hipMemcpyHostToDevice));
     }
+    return ZENV_OK;
+}
+
+extern "C" int zenv_collect(zenv_t *h, int T, uint64_t policy_seed, uint64_t env_index0, float discount, float gae_lambda)
+{
+    if (!h) return fail(ZENV_E_ARG, "null handle");
+    if (T < 1) return fail(ZENV_E_ARG, "frames_per_proc must be positive");
+    if (!h->was_reset) return fail(ZENV_E_STATE, "Environment must be reset before stepping");
+    if (!h->mlp_ready || !h->mlp.wv1) return fail(ZENV_E_STATE, "zenv_mlp_load with actor and critic weights first");
+    if (h->host_io_slab) return fail(ZENV_E_STATE, "zenv_collect records on the device: switch zenv_host_io off first");
+    if (h->order_enabled)
+        return fail(ZENV_E_STATE, "solver-ordered envs are stepped with zenv_step (their order feature is not part of "
+                                  "the network input this call evaluates)");
+    int rc = use_device(h);
+    if (rc) return rc;
+    const size_t N = (size_t)h->n_env, ZF = (size_t)h->p.Z * h->p.F;
+    h->act_tag.valid = false;
+    rc = ensure_exp(h, T);
+    if (rc) return rc;
     // The observations are recorded where they are produced: the policy of frame t reads slot t, the step kernel
     // of frame t writes obs_{t+1} into slot t+1 (the last one into the handle's own buffers again).
     struct ObsRedirect {
@@ -1424,6 +1459,171 @@ extern "C" int zenv_collect(zenv_t *h, int T, uint64_t policy_seed, uint64_t env
     HIP_TRY(launch_mlp_forward(h->mlp, h->n_env, h->p.Z, h->p.F, h->p.obs, h->p.zone_obs, h->mlp_pooled, h->mlp_mu,
                                h->mlp_std, h->mlp_value, h->mlp_value_sigma, no_mlp_action(), h->stream));
     HIP_TRY(launch_exp_gae(h->exp, h->n_env, h->mlp_value, discount, gae_lambda, h->stream));
+    return ZENV_OK;
+}
+
+// ---- zenv_collect_hier: collect_experiences of the Zone-goals agent (zone-goals/src/torch_ac/algos/_hier_policy_opt.py)
+// the per-frame records for T frames; the state carried from call to call is allocated (and zeroed) once
+static int ensure_hier_collect(zenv_t *h, int T)
+{
+    const size_t N = (size_t)h->n_env, ZF = (size_t)h->p.Z * h->p.F;
+    if (!h->hcarry_mem) {
+        const size_t bytes = N * (4 + 1 + 8 * 4 + ZF * 4 + 4 + 4 + 4 + 4 + 8) + 9 * 256;
+        HIP_TRY(hipMalloc(&h->hcarry_mem, bytes));
+        HIP_TRY(hipMemsetAsync(h->hcarry_mem, 0, bytes, h->stream));
+        char *b = static_cast<char *>(h->hcarry_mem);
+        auto take = [&](size_t n) { char *at = b; b += (n + 255) & ~(size_t)255; return at; };
+        HierCarry &c = h->hcarry;
+        c.src = reinterpret_cast<int64_t *>(take(N * 8));
+        c.obs = reinterpret_cast<float *>(take(N * 8 * 4));
+        c.zone_obs = reinterpret_cast<float *>(take(N * ZF * 4));
+        c.hi_reward = reinterpret_cast<float *>(take(N * 4));
+        c.value = reinterpret_cast<float *>(take(N * 4));
+        c.log_prob = reinterpret_cast<float *>(take(N * 4));
+        c.goal = reinterpret_cast<int32_t *>(take(N * 4));
+        c.avail = reinterpret_cast<uint32_t *>(take(N * 4));
+        c.open = reinterpret_cast<uint8_t *>(take(N));
+        if (b > static_cast<char *>(h->hcarry_mem) + bytes) return fail(ZENV_E_HIP, "carry layout overflow");
+    }
+    if (!h->hi_total_host) HIP_TRY(hipHostMalloc((void **)&h->hi_total_host, 4, hipHostMallocDefault));
+    if (h->hframes_mem && h->hframes.T == T) return ZENV_OK;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->hframes_mem) HIP_TRY(hipFree(h->hframes_mem));
+    h->hframes_mem = nullptr;
+    const size_t TN = (size_t)T * N;
+    const size_t bytes = TN * (4 + 4 + 4 + 4 + 4 + 1 + 8 + 4) + N * 8 + 4 + 11 * 256;
+    HIP_TRY(hipMalloc(&h->hframes_mem, bytes));
+    char *b = static_cast<char *>(h->hframes_mem);
+    auto take = [&](size_t n) { char *at = b; b += (n + 255) & ~(size_t)255; return at; };
+    HierFrames &f = h->hframes;
+    f.T = T;
+    f.lo_goal = reinterpret_cast<float *>(take(TN * 8));
+    f.pick_goal = reinterpret_cast<int32_t *>(take(TN * 4));
+    f.pick_value = reinterpret_cast<float *>(take(TN * 4));
+    f.pick_log_prob = reinterpret_cast<float *>(take(TN * 4));
+    f.pick_avail = reinterpret_cast<uint32_t *>(take(TN * 4));
+    f.close_reward = reinterpret_cast<float *>(take(TN * 4));
+    f.env_reward = reinterpret_cast<float *>(take(TN * 4));
+    f.count = reinterpret_cast<int32_t *>(take(N * 4));
+    f.offset = reinterpret_cast<int32_t *>(take(N * 4));
+    f.total = reinterpret_cast<int32_t *>(take(4));
+    f.close_flag = reinterpret_cast<uint8_t *>(take(TN));
+    if (b > static_cast<char *>(h->hframes_mem) + bytes) return fail(ZENV_E_HIP, "frame record layout overflow");
+    HIP_TRY(hipMemsetAsync(h->hframes_mem, 0, bytes, h->stream));
+    return ZENV_OK;
+}
+
+// room for M rows of the flat high-level output (grown by half again, never shrunk)
+static int ensure_hier_out(zenv_t *h, int64_t M)
+{
+    if (M <= h->hi_cap) return ZENV_OK;
+    const int64_t cap = std::max<int64_t>(M, h->hi_cap + h->hi_cap / 2);
+    const size_t Z = (size_t)h->p.Z, ZF = Z * h->p.F, R = (size_t)cap;
+    if (h->hout_mem) HIP_TRY(hipFree(h->hout_mem));
+    h->hout_mem = nullptr;
+    h->hi_cap = 0;
+    const size_t bytes = R * (8 * 4 + ZF * 4 + 4 + Z + 6 * 4 + 4 + 8) + 12 * 256;
+    HIP_TRY(hipMalloc(&h->hout_mem, bytes));
+    char *b = static_cast<char *>(h->hout_mem);
+    auto take = [&](size_t n) { char *at = b; b += (n + 255) & ~(size_t)255; return at; };
+    HierOut &o = h->hout;
+    o.src = reinterpret_cast<int64_t *>(take(R * 8));
+    o.obs = reinterpret_cast<float *>(take(R * 8 * 4));
+    o.zone_obs = reinterpret_cast<float *>(take(R * ZF * 4));
+    o.action = reinterpret_cast<int32_t *>(take(R * 4));
+    o.value = reinterpret_cast<float *>(take(R * 4));
+    o.log_prob = reinterpret_cast<float *>(take(R * 4));
+    o.advantage = reinterpret_cast<float *>(take(R * 4));
+    o.returnn = reinterpret_cast<float *>(take(R * 4));
+    o.reward = reinterpret_cast<float *>(take(R * 4));
+    o.mask = reinterpret_cast<float *>(take(R * 4));
+    o.avail = reinterpret_cast<uint32_t *>(take(R * 4));
+    o.action_mask = reinterpret_cast<uint8_t *>(take(R * Z));
+    if (b > static_cast<char *>(h->hout_mem) + bytes) return fail(ZENV_E_HIP, "output layout overflow");
+    h->hi_cap = cap;
+    return ZENV_OK;
+}
+
+extern "C" int zenv_collect_hier(zenv_t *h, int T, uint64_t policy_seed, uint64_t env_index0, float discount,
+                                 float gae_lambda, int64_t *n_hi)
+{
+    if (!h) return fail(ZENV_E_ARG, "null handle");
+    if (T < 2) return fail(ZENV_E_ARG, "frames_per_proc must be at least 2 (the low level hands out T - 1 frames)");
+    if ((int64_t)T * h->n_env > INT32_MAX) return fail(ZENV_E_ARG, "frames_per_proc x envs must stay below 2^31");
+    if (h->order_enabled)
+        return fail(ZENV_E_STATE, "zenv_collect_hier runs the goal-conditioned agent: this handle is solver-ordered");
+    if (!h->goal_enabled) return fail(ZENV_E_STATE, "zenv_collect_hier needs a goal-conditioned handle: zenv_goal_enable first");
+    if (!h->hier_ready) return fail(ZENV_E_STATE, "zenv_hier_load first");
+    if (!h->hier.hi_critic || !h->hier.lo_critic)
+        return fail(ZENV_E_STATE, "zenv_collect_hier needs both critics (zenv_hier_load with hi_critic_* and lo_critic_*)");
+    if (h->host_io_slab) return fail(ZENV_E_STATE, "zenv_collect_hier records on the device: switch zenv_host_io off first");
+    if (!h->was_reset) return fail(ZENV_E_STATE, "Environment must be reset before stepping");
+    int rc = use_device(h);
+    if (rc) return rc;
+    const size_t N = (size_t)h->n_env, ZF = (size_t)h->p.Z * h->p.F;
+    h->act_tag.valid = false;
+    rc = ensure_exp(h, T);
+    if (rc) return rc;
+    rc = ensure_hier_collect(h, T);
+    if (rc) return rc;
+    const HierFrames &f = h->hframes;
+    const HierCarry &c = h->hcarry;
+    HIP_TRY(hipMemsetAsync(f.pick_goal, 0xFF, (size_t)T * N * 4, h->stream));     // -1: no pick
+    HIP_TRY(hipMemsetAsync(f.close_flag, 0, (size_t)T * N, h->stream));
+    HIP_TRY(hipMemsetAsync(f.count, 0, N * 4, h->stream));
+    // the observations are recorded where they are produced, as in zenv_collect
+    struct ObsRedirect {
+        zenv_t *h;
+        float *obs, *zone_obs;
+        ~ObsRedirect() { h->p.obs = obs; h->p.zone_obs = zone_obs; }
+    } home{ h, h->p.obs, h->p.zone_obs };
+    HIP_TRY(hipMemcpyAsync(h->exp.obs, home.obs, N * 8 * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->exp.zone_obs, home.zone_obs, N * ZF * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    for (int t = 0; t < T; ++t) {
+        h->p.obs = h->exp.obs + (size_t)t * N * 8;
+        h->p.zone_obs = h->exp.zone_obs + (size_t)t * N * ZF;
+        const uint32_t step_index = (uint32_t)h->step_count;
+        const HierRecord hrec{ t, h->n_env, f.pick_goal, f.pick_value, f.pick_log_prob, f.pick_avail, c.open, f.lo_goal };
+        // :14-46 goals for the envs that need one (zenv_policy(ZENV_POLICY_HIER_SAMPLE)'s launches), the pick recorded
+        const HierPick pick{ 1, step_index, policy_seed, env_index0, h->goal_in };
+        HIP_TRY(launch_hier_high(h->hier, h->p, h->hier_logits, h->hier_value, pick, h->stream, hrec));
+        HIP_TRY(launch_goal_set(h->p, h->goal_in, h->goal_bad, h->stream));
+        // :48-64 the low level's action; frame t recorded (and the shaped reward / mask of frame t-1)
+        const MlpRecord rec{ h->exp.action, h->exp.log_prob, h->exp.value, h->exp.mask, h->exp.reward, h->exp.cur_mask,
+                             h->p.reward, h->p.shaped, h->p.done_out, T, t, h->n_env };
+        const MlpAction act{ 1, step_index, policy_seed, env_index0, h->p.actions, rec };
+        HIP_TRY(launch_hier_low(h->hier, h->p, h->mlp_mu, h->mlp_std, h->mlp_value, act, h->stream, hrec));
+        h->p.obs = t + 1 < T ? h->exp.obs + (size_t)(t + 1) * N * 8 : home.obs;
+        h->p.zone_obs = t + 1 < T ? h->exp.zone_obs + (size_t)(t + 1) * N * ZF : home.zone_obs;
+        HIP_TRY(launch_step(h->p, h->p.actions, 1, no_policy(), h->stream));     // ParallelEnv.step: auto-reset
+        HIP_TRY(launch_goal_step(h->p, h->stream));
+        HIP_TRY(launch_hier_close(h->p, f, c, t, h->stream));                     // :66-76
+        h->step_count += 1;
+    }
+    HIP_TRY(launch_exp_reward(h->exp, h->n_env, T - 1, h->p.reward, h->p.shaped, h->p.done_out, h->stream));
+    // next_hi_val = V_hi(obs_T) (:93-95), into ZENV_F_HIER_VALUE
+    const HierPick value_only{ -2, 0u, 0ull, 0ull, nullptr };
+    HIP_TRY(launch_hier_high(h->hier, h->p, h->hier_logits, h->hier_value, value_only, h->stream));
+    // :109-116 the low level over frames 0 .. T-2, no bootstrap: frame T-1 is only the "next" frame of T-2
+    ExpBuffers lo = h->exp;
+    lo.T = T - 1;
+    lo.cur_mask = h->exp.mask + (size_t)(T - 1) * N;
+    HIP_TRY(launch_exp_gae(lo, h->n_env, h->exp.value + (size_t)(T - 1) * N, discount, gae_lambda, h->stream));
+    HIP_TRY(hipMemsetAsync(h->exp.advantage + (size_t)(T - 1) * N, 0, N * 4, h->stream));
+    HIP_TRY(hipMemsetAsync(h->exp.returnn + (size_t)(T - 1) * N, 0, N * 4, h->stream));
+    // the high level's rows: offsets, then M to the host (the one synchronisation of the call)
+    HIP_TRY(launch_hier_count_scan(f, h->n_env, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->hi_total_host, f.total, 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const int64_t M = *h->hi_total_host;
+    h->hi_m = 0;
+    rc = ensure_hier_out(h, M);
+    if (rc) return rc;
+    HIP_TRY(launch_hier_gae(f, c, h->hout, h->n_env, h->hier_value, gae_lambda, h->stream));
+    HIP_TRY(launch_hier_gather(h->hout, c, h->exp.obs, h->exp.zone_obs, M, h->n_env, h->p.Z, h->p.F, h->stream));
+    HIP_TRY(launch_hier_carry(c, h->exp.obs, h->exp.zone_obs, h->n_env, (int)ZF, h->stream));
+    h->hi_m = M;
+    if (n_hi) *n_hi = M;
     return ZENV_OK;
 }
 

@@ -83,6 +83,38 @@ class TorchZoneEnv:
             out[name] = t.transpose(0, 1) if time_major else t        # [N, T, ...] views either way
         return out
 
+    def load_hier(self, hi_state_dict, lo_state_dict):
+        """Put HighPolicyValueModel / LoPolicyValueModel state_dicts (zone-goals/src/hier_policy_value_models.py; torch
+        tensors on any device) into the device agent that ``collect_hier`` runs -- after every update."""
+        from .vec_env import hier_tensors_from_state_dicts
+        self.env.load_hier(hier_tensors_from_state_dicts(hi_state_dict, lo_state_dict))
+
+    def collect_hier(self, frames_per_proc, policy_seed=1, env_index0=0, discount=0.99, gae_lambda=0.95):
+        """HierPolicyAlgo.collect_experiences on the device; returns (lo, hi) as CUDA tensors ALIASING the handle's
+        buffers (named and shaped as ``ZoneVecEnv.collect_hier``: lo [N, T-1, ...] views of time-major memory, hi flat
+        [M, ...], action_mask a bool view of uint8 memory, count [N]).  Valid until the next collect_hier.  Ends with
+        one synchronisation (the host learns M)."""
+        from .vec_env import hier_experience_layout
+        env = self.env
+        T, M = env.collect_hier_on_device(frames_per_proc, policy_seed, env_index0, discount, gae_lambda)
+        lo_l, hi_l = hier_experience_layout(env.num_envs, env.num_zones, env.zone_feat, T, M)
+        torch = self._torch
+        lo = {name: self._alias_typed(field, shape, dt)[:T - 1].transpose(0, 1) for name, (field, shape, dt) in lo_l.items()}
+        hi = {}
+        for name, (field, shape, dt) in hi_l.items():
+            if M:
+                t = self._alias_typed(field, shape, dt)
+            else:
+                t = torch.empty(shape, dtype=getattr(torch, np.dtype(dt).name), device=self.device)
+            hi[name] = t.view(torch.bool) if name == "action_mask" else t
+        hi["count"] = self._alias_typed(nat.F_HI_COUNT, (env.num_envs,), np.int32)
+        return lo, hi
+
+    def _alias_typed(self, field, shape, dtype):
+        t = self._torch.as_tensor(_DeviceView(self.env.device_ptr(field), shape, dtype), device=self.device)
+        assert t.data_ptr() == self.env.device_ptr(field), "torch copied instead of aliasing"
+        return t
+
     def step(self, actions, auto_reset=True):
         """actions: float32 CUDA tensor (N, 2) on the env's device (contiguous).  Asynchronous: the
         step kernel is enqueued behind whatever produced ``actions`` on the shared stream."""

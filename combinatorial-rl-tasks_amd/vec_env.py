@@ -24,6 +24,10 @@ _FIELD_DTYPES = {
     nat.F_AVAILABLE_GOALS: np.uint32, nat.F_GOAL: np.int32, nat.F_ORDER_VAL: np.float32,
     nat.F_EXCEPTION: np.uint8, nat.F_POLICY_VALUE_SIGMA: np.float32, nat.F_ORDER_POS: np.int8,
     nat.F_HIER_LOGITS: np.float32, nat.F_HIER_VALUE: np.float32,
+    nat.F_LO_GOAL: np.float32, nat.F_LO_ENV_REWARD: np.float32, nat.F_HI_OBS: np.float32, nat.F_HI_ZONE_OBS: np.float32,
+    nat.F_HI_ACTION: np.int32, nat.F_HI_ACTION_MASK: np.uint8, nat.F_HI_VALUE: np.float32, nat.F_HI_LOG_PROB: np.float32,
+    nat.F_HI_ADVANTAGE: np.float32, nat.F_HI_RETURN: np.float32, nat.F_HI_REWARD: np.float32, nat.F_HI_MASK: np.float32,
+    nat.F_HI_COUNT: np.int32,
 }
 
 
@@ -137,6 +141,44 @@ def hier_tensors_from_state_dicts(hi_sd, lo_sd):
             raise ValueError(f"{level}_model_state[{key!r}] has shape {tuple(a.shape)}, expected {want[name]} "
                              f"(hidden size {h}, zone rows of {F} features)")
     return out
+
+
+def check_collect_hier_args(frames_per_proc, policy_seed=1, env_index0=0, discount=0.99, gae_lambda=0.95):
+    """What ``ZoneVecEnv.collect_hier`` checks before it calls into the library: T >= 2 frames (the low level hands
+    out T - 1), a discount and a lambda in [0, 1], non-negative 64-bit seeds.  Returns the normalised arguments."""
+    if isinstance(frames_per_proc, bool) or int(frames_per_proc) != frames_per_proc:
+        raise ValueError(f"frames_per_proc must be an integer, got {frames_per_proc!r}")
+    T = int(frames_per_proc)
+    if T < 2:
+        raise ValueError(f"frames_per_proc must be at least 2 (the low level hands out T - 1 frames), got {T}")
+    for name, v in (("discount", discount), ("gae_lambda", gae_lambda)):
+        if not (0.0 <= float(v) <= 1.0):
+            raise ValueError(f"{name} must lie in [0, 1], got {v!r}")
+    for name, v in (("policy_seed", policy_seed), ("env_index0", env_index0)):
+        if int(v) != v or not (0 <= int(v) < 2 ** 64):
+            raise ValueError(f"{name} must be an integer in [0, 2^64), got {v!r}")
+    return T, int(policy_seed), int(env_index0), float(discount), float(gae_lambda)
+
+
+def hier_experience_layout(num_envs, num_zones, zone_feat, frames_per_proc, n_hi):
+    """The buffers one ``collect_hier`` of T frames fills, as (lo, hi): name -> (field id, shape in memory, dtype).
+    lo: time-major [T, N, ...] device buffers, handed out as [N, T-1, ...] views (the names of lo_exps in
+    _hier_policy_opt.py:125-139, plus goal, reward (shaped), env_reward and mask).  hi: flat env-major [M, ...]
+    (hi_exps, :142-161, plus each transition's reward and hi_mask), M = n_hi."""
+    N, Z, F, T, M = int(num_envs), int(num_zones), int(zone_feat), int(frames_per_proc), int(n_hi)
+    f32 = np.float32
+    lo = {"obs": (nat.F_EXP_OBS, (T, N, 8), f32), "zone_obs": (nat.F_EXP_ZONE_OBS, (T, N, Z, F), f32),
+          "goal": (nat.F_LO_GOAL, (T, N, 2), f32), "action": (nat.F_EXP_ACTION, (T, N, 2), f32),
+          "log_prob": (nat.F_EXP_LOG_PROB, (T, N, 2), f32), "value": (nat.F_EXP_VALUE, (T, N), f32),
+          "advantage": (nat.F_EXP_ADVANTAGE, (T, N), f32), "returnn": (nat.F_EXP_RETURN, (T, N), f32),
+          "reward": (nat.F_EXP_REWARD, (T, N), f32), "env_reward": (nat.F_LO_ENV_REWARD, (T, N), f32),
+          "mask": (nat.F_EXP_MASK, (T, N), f32)}
+    hi = {"obs": (nat.F_HI_OBS, (M, 8), f32), "zone_obs": (nat.F_HI_ZONE_OBS, (M, Z, F), f32),
+          "action": (nat.F_HI_ACTION, (M,), np.int32), "action_mask": (nat.F_HI_ACTION_MASK, (M, Z), np.uint8),
+          "value": (nat.F_HI_VALUE, (M,), f32), "log_prob": (nat.F_HI_LOG_PROB, (M,), f32),
+          "advantage": (nat.F_HI_ADVANTAGE, (M,), f32), "returnn": (nat.F_HI_RETURN, (M,), f32),
+          "reward": (nat.F_HI_REWARD, (M,), f32), "mask": (nat.F_HI_MASK, (M,), f32)}
+    return lo, hi
 
 
 def zone_feat(cfg):
@@ -540,6 +582,43 @@ class ZoneVecEnv:
                 "value": (nat.F_EXP_VALUE, (T, N), True), "reward": (nat.F_EXP_REWARD, (T, N), True),
                 "mask": (nat.F_EXP_MASK, (T, N), True), "advantage": (nat.F_EXP_ADVANTAGE, (T, N), True),
                 "returnn": (nat.F_EXP_RETURN, (T, N), True)}
+
+    # ------------------------------------------------------------------ Zone-goals training experience
+    def collect_hier(self, frames_per_proc, policy_seed=1, env_index0=0, discount=0.99, gae_lambda=0.95):
+        """HierPolicyAlgo.collect_experiences (zone-goals/src/torch_ac/algos/_hier_policy_opt.py:9-171) on the device
+        with the loaded hierarchical agent (``load_hier`` with both critics, ``enable_goals``).  Returns (lo, hi), the
+        reference's lo_exps / hi_exps as numpy arrays:
+          lo  [N, T-1, ...]: obs, zone_obs, goal, action, log_prob, value, advantage, returnn, reward (shaped),
+              env_reward, mask -- reshape(N*(T-1), ...) is the reference's flat order
+          hi  [M, ...] env-major: obs, zone_obs, action (int32), action_mask (bool [M, Z]), value, log_prob,
+              advantage, returnn (hi_exps), reward and mask (what the GAE used); and count (int32 [N], rows of every
+              env: sum = M)
+        The transition an env has open at the end stays on the device and is the first of its next call."""
+        T, M = self.collect_hier_on_device(frames_per_proc, policy_seed, env_index0, discount, gae_lambda)
+        lo_l, hi_l = hier_experience_layout(self.num_envs, self.num_zones, self.zone_feat, T, M)
+        lo, hi = {}, {}
+        for name, (field, shape, dt) in lo_l.items():
+            a = np.empty(shape, dt)
+            assert a.nbytes == lib().zenv_field_bytes(self._h, field)
+            check(lib().zenv_get(self._h, field, a.ctypes.data, 0))
+            lo[name] = a[:T - 1].swapaxes(0, 1)
+        for name, (field, shape, dt) in hi_l.items():
+            a = np.empty(shape, dt)
+            if M:
+                assert a.nbytes == lib().zenv_field_bytes(self._h, field)
+                check(lib().zenv_get(self._h, field, a.ctypes.data, 0))
+            hi[name] = a.view(bool) if name == "action_mask" else a
+        hi["count"] = self.get(nat.F_HI_COUNT)
+        return lo, hi
+
+    def collect_hier_on_device(self, frames_per_proc, policy_seed=1, env_index0=0, discount=0.99, gae_lambda=0.95):
+        """The same collection, results left in the handle's device buffers (``hier_experience_layout`` names them).
+        Returns (T, M)."""
+        T, seed, index0, discount, gae_lambda = check_collect_hier_args(frames_per_proc, policy_seed, env_index0,
+                                                                        discount, gae_lambda)
+        m = C.c_int64(0)
+        check(lib().zenv_collect_hier(self._h, T, seed, index0, discount, gae_lambda, C.byref(m)))
+        return T, int(m.value)
 
     def sync(self):
         check(lib().zenv_sync(self._h))

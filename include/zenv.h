@@ -95,8 +95,26 @@ enum {
     ZENV_F_HIER_LOGITS = 36,     /* float32 [N,Z]    the high level's logit of every zone, -INFINITY where the zone is not an
                                   *                    available goal (hier_agent.py get_hi_action: logits[~available] = -inf);
                                   *                    unnormalised: actor.2's output, not Categorical's log-softmax */
-    ZENV_F_HIER_VALUE = 37,      /* float32 [N]      the high level's critic value (0 without critic tensors) */
-    ZENV_F_COUNT = 38
+    ZENV_F_HIER_VALUE = 37,      /* float32 [N]      the high level's critic value (0 without critic tensors); after
+                                  *                    zenv_collect_hier: V_hi(obs_T), the high level's bootstrap value */
+    /* Zone-goals experience of the last zenv_collect_hier().  The low level's other records are the ZENV_F_EXP_* buffers
+     * (time-major [T][N]): obs, zone_obs, action, log_prob, value, reward (= info['shaped_reward']), mask, advantage and
+     * return, the last two over frames 0 .. T-2 only (0 at frame T-1) */
+    ZENV_F_LO_GOAL = 38,         /* float32 [T,N,2]  the low level's goal input (cur_goal): the goal zone's centre / 3 */
+    ZENV_F_LO_ENV_REWARD = 39,   /* float32 [T,N]    the env reward of every frame (what hi_reward sums) */
+    /* the closed high-level transitions, flat and env-major (env 0's in order, then env 1's ...): M rows */
+    ZENV_F_HI_OBS = 40,          /* float32 [M,8]    the observation the goal was picked on */
+    ZENV_F_HI_ZONE_OBS = 41,     /* float32 [M,Z,F] */
+    ZENV_F_HI_ACTION = 42,       /* int32   [M]      the goal zone */
+    ZENV_F_HI_ACTION_MASK = 43,  /* uint8   [M,Z]    the available goals when it was picked (1 = available) */
+    ZENV_F_HI_VALUE = 44,        /* float32 [M]      the high critic's value */
+    ZENV_F_HI_LOG_PROB = 45,     /* float32 [M]      log_prob(goal) of Categorical(masked logits): the log-softmax */
+    ZENV_F_HI_ADVANTAGE = 46,    /* float32 [M] */
+    ZENV_F_HI_RETURN = 47,       /* float32 [M]      value + advantage */
+    ZENV_F_HI_REWARD = 48,       /* float32 [M]      the transition's reward: the env rewards from its pick to its close */
+    ZENV_F_HI_MASK = 49,         /* float32 [M]      hi_mask: 0 when it closed because the episode ended, else 1 */
+    ZENV_F_HI_COUNT = 50,        /* int32   [N]      rows of every env (closed transitions of the last call) */
+    ZENV_F_COUNT = 51
 };
 
 /* scripted on-device action sources (the build's own; used by bench/tests) */
@@ -427,7 +445,8 @@ int zenv_hier_load(zenv_t *h, const zenv_hier_weights *w);
  * every env (0 for an env without a goal, e.g. one with no available zone: not an error).  The high level is evaluated
  * only for the envs that pick: ZENV_F_HIER_LOGITS / _VALUE are refreshed for those.  Randomness: Philox keyed by
  * (policy_seed, env_index0 + env, zenv_step_count) with separate streams for the goal and the action draw.  No host
- * synchronisation.  zenv_rollout() / zenv_collect() do not take these policies. */
+ * synchronisation.  zenv_rollout() / zenv_collect() do not take these policies; zenv_collect_hier() collects training
+ * experience with them. */
 int zenv_hier_forward(zenv_t *h);
 
 /* ---- one PPO rollout on the device: BaseAlgo.collect_experiences, main/src/torch_ac/algos/base.py:131-227 ----
@@ -437,6 +456,31 @@ int zenv_hier_forward(zenv_t *h);
  * next call with a different T or zenv_destroy; self.mask is carried from call to call like the reference's. */
 int zenv_collect(zenv_t *h, int frames_per_proc, uint64_t policy_seed, uint64_t env_index0, float discount,
                  float gae_lambda);
+
+/* ---- the same for the Zone-goals agent: collect_experiences of HierPolicyAlgo,
+ * zone-goals/src/torch_ac/algos/_hier_policy_opt.py:9-171 (zenv_hier_load with BOTH critics, goal-conditioned handle) ----
+ * T frames, each: every env that needs a goal draws one (the launches of zenv_policy(ZENV_POLICY_HIER_SAMPLE)) and opens
+ * a high-level transition -- obs, the goal, the available-goals mask, the high critic's value, log_prob(goal); the low
+ * level acts and frame t is recorded (ZENV_F_EXP_*, ZENV_F_LO_GOAL: obs, goal, action, per-dimension log_prob, value,
+ * mask = 1 - done of the previous step, carried from call to call); the envs step with auto-reset; the low level's reward
+ * is info['shaped_reward'], the env reward goes into ZENV_F_LO_ENV_REWARD and into the env's hi_reward (float32 sum).  An
+ * env whose need_next_goal is set closes its open transition: its reward is hi_reward, its hi_mask 0 if done else 1, and
+ * hi_reward restarts at 0.  Then
+ *   low level:  GAE over frames 0 .. T-2 with no bootstrap value (frame T-1 is only the next frame of T-2):
+ *               delta = r_i + discount v_{i+1} m_{i+1} - v_i, adv_i = delta + discount gae_lambda adv_{i+1} m_{i+1}
+ *   high level: per env over its closed transitions, NO discount (as the reference): delta = r + V_next m - V,
+ *               adv = delta + gae_lambda adv_next m, m = the transition's hi_mask, V_next = the value of the env's
+ *               next transition or, when no goal was picked after the last close, V_hi(obs_T); adv_next = 0 for the last.
+ * The closed transitions are handed out (ZENV_F_HI_*, *n_hi = M); the open one and hi_reward stay on the device and are
+ * the first transition of the next call.  Randomness: that of zenv_policy(ZENV_POLICY_HIER_SAMPLE), keyed by
+ * (policy_seed, env_index0 + env, zenv_step_count): a call is bit-identical to T rounds of zenv_policy + zenv_step.  A
+ * finished env draws nothing; an env with no available zone gets no goal and action 0 (the reference would assert).
+ * One host synchronisation, at the end (to learn M).  ZENV_E_ARG: frames_per_proc < 2; ZENV_E_STATE: no goals, no
+ * zenv_hier_load, a critic missing, zenv_host_io on, a solver-ordered handle.  zenv_reset ends the episodes it resets:
+ * the open transition of such an env is dropped (no row ever refers to it) and its hi_reward restarts at 0, so the
+ * first goal of the new episode opens the env's next transition. */
+int zenv_collect_hier(zenv_t *h, int frames_per_proc, uint64_t policy_seed, uint64_t env_index0, float discount,
+                      float gae_lambda, int64_t *n_hi);
 
 /* ---- results ---- */
 int zenv_get(zenv_t *h, int field, void *dst, int dst_on_device);
