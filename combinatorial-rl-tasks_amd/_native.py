@@ -17,6 +17,8 @@ OBS_DIM = 8
 TASK_TSP, TASK_TIMED_TSP, TASK_COLOUR_MATCH = 0, 1, 2
 POLICY_UNIFORM, POLICY_GREEDY, POLICY_MLP_MEAN, POLICY_MLP_SAMPLE = 0, 1, 2, 3
 POLICY_HIER_SAMPLE, POLICY_HIER_MEAN = 4, 5     # the Zone-goals hierarchical agent (zenv_hier_load)
+POLICY_SKILL_SAMPLE, POLICY_SKILL_MEAN = 6, 7   # the fixed-length-skills agent (zenv_skill_load)
+MAX_SKILLS = 32
 KERNEL_LANE_PER_ENV, KERNEL_WAVE_PER_ENV = 0, 1
 HIP_STREAM_LEGACY = 1       # hipStreamLegacy: the null stream as an explicit handle (hip_runtime_api.h)
 ROLLOUT_UNFUSED = 1
@@ -36,7 +38,8 @@ E_ARG, E_HIP, E_STATE, E_LAYOUT, E_DONE, E_RANGE = -1, -2, -3, -4, -5, -6
  F_EXP_ADVANTAGE, F_EXP_RETURN, F_ORDER_VAL, F_EXCEPTION, F_POLICY_VALUE_SIGMA, F_ORDER_POS,
  F_CHUNK_REWARD, F_CHUNK_DONE, F_CHUNK_ACTIONS, F_HIER_LOGITS, F_HIER_VALUE,
  F_LO_GOAL, F_LO_ENV_REWARD, F_HI_OBS, F_HI_ZONE_OBS, F_HI_ACTION, F_HI_ACTION_MASK, F_HI_VALUE, F_HI_LOG_PROB,
- F_HI_ADVANTAGE, F_HI_RETURN, F_HI_REWARD, F_HI_MASK, F_HI_COUNT) = range(51)
+ F_HI_ADVANTAGE, F_HI_RETURN, F_HI_REWARD, F_HI_MASK, F_HI_COUNT,
+ F_SKILL, F_SKILL_AGE, F_SKILL_LOGITS, F_SKILL_VALUE) = range(55)
 (RESULT_OBS, RESULT_REWARD, RESULT_DONE, RESULT_GOAL_MET, RESULT_EXCEPTION, RESULT_ZONE_OBS) = range(6)
 N_RESULTS = 6
 
@@ -67,6 +70,20 @@ class HierWeights(C.Structure):
     """struct zenv_hier_weights (include/zenv.h): host float32 tensors in state_dict layout."""
     _fields_ = [("h_dim", C.c_int32), ("precision", C.c_int32), ("zone_feat", C.c_int32), ("pad", C.c_int32)] + [
         (n, C.c_void_p) for n in HIER_HI_TENSORS + HIER_HI_CRITIC + HIER_LO_TENSORS + HIER_LO_CRITIC]
+
+
+# struct zenv_skill_weights (include/zenv.h): hi_model_state / lo_model_state of the fixed-length-skills agent
+SKILL_HI_TENSORS = ("hi_zone_w1", "hi_zone_b1", "hi_zone_w2", "hi_zone_b2", "hi_zone_w3", "hi_zone_b3", "hi_comb_w",
+                    "hi_comb_b", "hi_enc_w", "hi_enc_b", "hi_logit_w", "hi_logit_b")
+SKILL_HI_CRITIC = HIER_HI_CRITIC                                                     # optional, all or none
+SKILL_LO_TENSORS = HIER_LO_TENSORS
+SKILL_LO_CRITIC = HIER_LO_CRITIC                                                     # optional, all or none
+
+
+class SkillWeights(C.Structure):
+    """struct zenv_skill_weights (include/zenv.h): host float32 tensors in state_dict layout."""
+    _fields_ = [("h_dim", C.c_int32), ("n_skills", C.c_int32), ("zone_feat", C.c_int32), ("precision", C.c_int32)] + [
+        (n, C.c_void_p) for n in SKILL_HI_TENSORS + SKILL_HI_CRITIC + SKILL_LO_TENSORS + SKILL_LO_CRITIC]
 
 
 class ZenvError(RuntimeError):
@@ -144,6 +161,10 @@ _PROTOTYPES = {
     "zenv_mlp_forward": (C.c_int, [_H]),
     "zenv_hier_load": (C.c_int, [_H, C.c_void_p]),
     "zenv_hier_forward": (C.c_int, [_H]),
+    "zenv_skill_load": (C.c_int, [_H, C.c_void_p]),
+    "zenv_skill_configure": (C.c_int, [_H, C.c_int]),
+    "zenv_set_skills": (C.c_int, [_H, C.c_void_p]),
+    "zenv_skill_forward": (C.c_int, [_H]),
     "zenv_get": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int]),
     "zenv_get_rows": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "zenv_device_ptr": (C.c_int, [_H, C.c_int, C.POINTER(C.c_void_p)]),

@@ -20,84 +20,14 @@
 
 #include <cmath>
 
+#include "hier_enc.hpp"
 #include "hier_f32.hpp"
 #include "mlp_head_out.hpp"
 
 namespace zenvk {
 namespace {
 
-constexpr int HP = kMlpHP;     // 192 threads = hidden features (padded)
-constexpr int RP = 32;         // rows (zone rows of consecutive envs) per pass
-constexpr int EB = 4;          // envs per workgroup
-constexpr int XP = 12;         // per-env input [obs (8), goal (2)], padded
-constexpr int ZF = 8;          // zone row (F <= 7), padded
-constexpr int NQ = HP / RP;    // 6 partial sums per logit
-
-// acc[r] += w * x[k][r] for the RP rows of one pass
-__device__ __forceinline__ void fma_rows(float (&acc)[RP], float w, const float *__restrict__ xk)
-{
-    const float4 *x4 = reinterpret_cast<const float4 *>(xk);
-#pragma unroll
-    for (int q = 0; q < RP / 4; ++q) {
-        const float4 v = x4[q];
-        acc[4 * q + 0] = __builtin_fmaf(w, v.x, acc[4 * q + 0]);
-        acc[4 * q + 1] = __builtin_fmaf(w, v.y, acc[4 * q + 1]);
-        acc[4 * q + 2] = __builtin_fmaf(w, v.z, acc[4 * q + 2]);
-        acc[4 * q + 3] = __builtin_fmaf(w, v.w, acc[4 * q + 3]);
-    }
-}
-
-// out[e] (+)= sum_k wt[k][j] * x[e][k] for the EB env vectors in LDS (x: [EB][stride]); b: bias, or null = accumulate
-__device__ __forceinline__ void matvec(float (&out)[EB], const float *__restrict__ wt, const float *__restrict__ b,
-                                       const float *__restrict__ x, int stride, int n_in, int j)
-{
-    if (b) {
-#pragma unroll
-        for (int e = 0; e < EB; ++e) out[e] = b[j];
-    }
-    for (int k = 0; k < n_in; ++k) {
-        const float w = wt[(size_t)k * HP + j];
-#pragma unroll
-        for (int e = 0; e < EB; ++e) out[e] = __builtin_fmaf(w, x[e * stride + k], out[e]);
-    }
-}
-
-// zone rows r0 .. r0 + RP - 1 of the workgroup's envs (row = e * Z + z) -> x0 [ZF][RP], zeros beyond
-__device__ __forceinline__ void load_rows(float *__restrict__ x0, const float *__restrict__ zone_obs, int env0, int r0,
-                                          int n_rows, int Z, int F, int j)
-{
-    for (int i = j; i < ZF * RP; i += HP) {
-        const int k = i / RP, r = i % RP, row = r0 + r;
-        float v = 0.f;
-        if (row < n_rows && k < F) {
-            const int e = row / Z, z = row - e * Z;
-            v = zone_obs[((size_t)(env0 + e) * Z + z) * F + k];
-        }
-        x0[k * RP + r] = v;
-    }
-}
-
-// acc[r] = bias[e(row)][j] + sum_k wz[k][j] row[k]
-__device__ __forceinline__ void zone_part(float (&acc)[RP], const float *__restrict__ peb, const float *__restrict__ wz,
-                                          const float *__restrict__ x0, int r0, int Z, int F, int j)
-{
-#pragma unroll
-    for (int r = 0; r < RP; ++r) {
-        const int e = min((r0 + r) / Z, EB - 1);
-        acc[r] = peb[e * HP + j];
-    }
-    for (int k = 0; k < F; ++k) fma_rows(acc, wz[(size_t)k * HP + j], x0 + k * RP);
-}
-
-__device__ __forceinline__ void store_rows(float *__restrict__ y, const float (&acc)[RP], float scale, bool live, int j)
-{
-#pragma unroll
-    for (int q = 0; q < RP / 4; ++q)
-        reinterpret_cast<float4 *>(y + j * RP)[q] =
-            live ? make_float4(scale * fmaxf(acc[4 * q], 0.f), scale * fmaxf(acc[4 * q + 1], 0.f),
-                               scale * fmaxf(acc[4 * q + 2], 0.f), scale * fmaxf(acc[4 * q + 3], 0.f))
-                 : make_float4(0.f, 0.f, 0.f, 0.f);
-}
+using namespace hf32;
 
 __device__ __forceinline__ void lo_idle(int env, float *__restrict__ mu, float *__restrict__ stdv, float *__restrict__ value,
                                         const MlpAction &act)
@@ -207,54 +137,9 @@ __global__ __launch_bounds__(HP) void k_hier_f32(HierF32 w, DevParams p, float *
         xin[j] = v;
     }
     __syncthreads();
-    float t[EB];
-    matvec(t, E.w1x, E.b1, xin, XP, XIN, j);            // zone_net_.0 on [obs(, goal)] + bias: the same for every row
-#pragma unroll
-    for (int e = 0; e < EB; ++e) peb[e * HP + j] = t[e];
-
-    // ---- zone_net_.0 (zone-row columns), ReLU, zone_net_.2, ReLU on every row; rows summed per env
+    encode_envs<XIN>(E, p, xin, nullptr, nullptr, nullptr, env0, n_env, h, j, x0, y1, peb, va, vb);
     const int n_rows = n_env * Z;
-    float psum[EB];
-#pragma unroll
-    for (int e = 0; e < EB; ++e) psum[e] = 0.f;
-    const float b2 = E.b2[j];
-    for (int r0 = 0; r0 < n_rows; r0 += RP) {
-        __syncthreads();                                  // the previous pass is done with x0 / y1 (and peb is written)
-        load_rows(x0, p.zone_obs, env0, r0, n_rows, Z, F, j);
-        __syncthreads();
-        float acc[RP];
-        zone_part(acc, peb, E.w1z, x0, r0, Z, F, j);
-        store_rows(y1, acc, 1.f, live, j);
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < RP; ++r) acc[r] = b2;
-        for (int k = 0; k < h; ++k) fma_rows(acc, E.w2t[(size_t)k * HP + j], y1 + k * RP);
-#pragma unroll
-        for (int r = 0; r < RP; ++r) {
-            const int row = r0 + r;
-            const int e = row / Z;
-            const float v = fmaxf(acc[r], 0.f);
-#pragma unroll
-            for (int ee = 0; ee < EB; ++ee)
-                if (row < n_rows && e == ee) psum[ee] += v;
-        }
-    }
-
-    // ---- per env: zone_emb = zone_net_.4(mean); emb = combine_net_([obs(, goal), zone_emb])
-    __syncthreads();
-    const float inv_z = 1.0f / (float)Z;
-#pragma unroll
-    for (int e = 0; e < EB; ++e) vb[e * HP + j] = live ? psum[e] * inv_z : 0.f;
-    __syncthreads();
-    matvec(t, E.w3t, E.b3, vb, HP, h, j);
-#pragma unroll
-    for (int e = 0; e < EB; ++e) va[e * HP + j] = live ? t[e] : 0.f;
-    __syncthreads();
-    matvec(t, E.wce, E.bc, va, HP, h, j);
-    matvec(t, E.wcx, nullptr, xin, XP, XIN, j);
-#pragma unroll
-    for (int e = 0; e < EB; ++e) vb[e * HP + j] = live ? t[e] : 0.f;        // emb
-    __syncthreads();
+    float t[EB];
     float hv[EB];                                                           // critic.0(emb)
 #pragma unroll
     for (int e = 0; e < EB; ++e) hv[e] = 0.f;

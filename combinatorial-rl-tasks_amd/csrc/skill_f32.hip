@@ -1,0 +1,339 @@
+// skill_f32.hip -- the fixed-length-skills agent (main/src/hier_policy_value_models.py:19-76) in float32, gfx950.
+//
+// Two launches of one kernel template on the vector ALU, with the building blocks and the workgroup layout of
+// hier_f32.hip (hier_enc.hpp: 192 threads = hidden features, EB = 4 envs per workgroup):
+//  * k_skill_f32<0> -- HighPolicyValueModel.  emb = ZoneEnvModel(obs, zone_obs) (the flat agent's encoder); logits =
+//    actor.discrete_.0(relu(actor.enc_.0.0(emb))), one length-h dot product per (env, skill) thread; Categorical(logits=
+//    log_softmax(x)); value = critic.2(relu(critic.0(emb))).  When it picks, a workgroup none of whose envs needs a
+//    skill leaves at once: the high level costs what the envs that pick cost (one in skill_len steps).
+//  * k_skill_f32<1> -- LoPolicyValueModel.  The one-hot skill of ZoneEnvSkillModel's [obs, onehot] and of the heads'
+//    [emb, onehot] input selects one weight column: a per-env bias in zone_net_.0, combine_net_, actor.enc_.0.0 and
+//    critic.0, so the per-zone part has the flat network's shape.  Then PolicyNetwork's mu_ / std_ and the Normal sample
+//    of mlp_head_out.hpp, and the skill's age.
+// Only the summation order differs from torch's: within 1e-5 of the reference's float32 modules.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstddef>
+#include <cstring>
+
+#include "hier_enc.hpp"
+#include "mlp_head_out.hpp"
+#include "skill_f32.hpp"
+
+namespace zenvk {
+namespace {
+
+using namespace hf32;
+
+constexpr int SR = kMaxSkills + 1;    // per env: S logit rows, then the critic (row kMaxSkills)
+
+// one uniform in (0, 1) of the skill draw: Philox4x32-10 keyed by (seed, global env, step), a stream of its own (the
+// action draw of mlp_head_out.hpp uses the tag 0x4D4C50, the Zone-goals goal draw 0x48474C)
+__device__ __forceinline__ float skill_uniform(const SkillPick &pick, int env)
+{
+    const uint64_t g = pick.env_index0 + (uint64_t)env;
+    uint32_t c[4] = { (uint32_t)g, (uint32_t)(g >> 32), pick.step_index, 0x534B4Cu };
+    philox4x32_10(c, (uint32_t)pick.seed, (uint32_t)(pick.seed >> 32));
+    return ((float)(c[0] >> 8) + 0.5f) * 5.9604644775390625e-08f;
+}
+
+__device__ __forceinline__ void skill_idle(int env, float *__restrict__ mu, float *__restrict__ stdv,
+                                           float *__restrict__ value, const MlpAction &act)
+{
+    const float2 z = make_float2(0.f, 0.f);
+    reinterpret_cast<float2 *>(mu)[env] = z;
+    reinterpret_cast<float2 *>(stdv)[env] = z;
+    value[env] = 0.f;
+    if (act.mode >= 0) reinterpret_cast<float2 *>(act.actions)[env] = z;
+}
+
+// sum_k w[k] x[k] + w[HP] over the h features (a row of the [.][HP + 1] layout)
+__device__ __forceinline__ float dot_row(const float *__restrict__ w, const float *__restrict__ x, int h)
+{
+    float s = w[HP];
+    for (int k = 0; k < h; ++k) s = __builtin_fmaf(w[k], x[k], s);
+    return s;
+}
+
+// LEVEL 0: HighPolicyValueModel -> out0 = log-softmax logits [N][S], out1 = value [N] (+ the skill pick)
+// LEVEL 1: LoPolicyValueModel   -> out0 = mu [N][2], out1 = std [N][2], out2 = value [N] (+ the action, the age)
+template <int LEVEL>
+__global__ __launch_bounds__(HP) void k_skill_f32(SkillF32 w, DevParams p, SkillState st, float *__restrict__ out0,
+                                                  float *__restrict__ out1, float *__restrict__ out2, SkillPick pick,
+                                                  MlpAction act)
+{
+    __shared__ __align__(16) float x0[ZF * RP];         // zone rows of the pass       [k][row]
+    __shared__ __align__(16) float y1[HP * RP];         // activations of the pass     [k][row]
+    __shared__ float xin[EB * XP];                      // per-env input: obs
+    __shared__ float peb[EB * HP];
+    __shared__ float va[EB * HP];
+    __shared__ float vb[EB * HP];
+    __shared__ float lg[EB * SR];
+    __shared__ int on[EB];
+    __shared__ int sel[EB];                             // the low level's skill column (-1: none)
+    const int j = threadIdx.x;
+    const int h = w.h, S = w.S;
+    const bool live = j < h;
+    const int env0 = blockIdx.x * EB;
+    const int n_env = min(EB, p.N - env0);
+    const bool has_critic = LEVEL ? w.lo_critic : w.hi_critic;
+
+    // ---- which envs are evaluated: high -- all (forward) or those that pick a skill; low -- those with a skill
+    if (j < EB) {
+        int a = 0, s = -1;
+        if (j < n_env) {
+            const int env = env0 + j;
+            if (LEVEL == 0) {
+                const int sk = st.skill[env];
+                a = pick.mode < 0 || ((sk < 0 || st.age[env] >= pick.skill_len) && !p.sched[env].done_state);
+            } else {
+                s = st.skill[env];
+                a = s >= 0;
+            }
+        }
+        on[j] = a;
+        sel[j] = s;
+    }
+    __syncthreads();
+    if (!(on[0] | on[1] | on[2] | on[3])) {
+        if (LEVEL == 1 && j < n_env) skill_idle(env0 + j, out0, out1, out2, act);
+        return;
+    }
+    if (j < EB * XP) {
+        const int e = j / XP, k = j % XP;
+        xin[j] = e < n_env && k < 8 ? p.obs[(size_t)(env0 + e) * 8 + k] : 0.f;
+    }
+    __syncthreads();
+    if (LEVEL == 0)
+        encode_envs<8>(w.hi, p, xin, nullptr, nullptr, nullptr, env0, n_env, h, j, x0, y1, peb, va, vb);
+    else
+        encode_envs<8>(w.lo, p, xin, w.lo_w1s, w.lo_wcs, sel, env0, n_env, h, j, x0, y1, peb, va, vb);
+
+    // ---- vb = emb: a = relu(actor.enc_.0.0(.)) -> va, relu(critic.0(.)) -> peb (the low level adds the skill column)
+    float t[EB], hv[EB];
+#pragma unroll
+    for (int e = 0; e < EB; ++e) hv[e] = 0.f;
+    if (has_critic) {
+        matvec(hv, LEVEL ? w.lv1t : w.hv1t, LEVEL ? w.lv1b : w.hv1b, vb, HP, h, j);
+        if (LEVEL == 1) add_column(hv, w.lv1s, sel, j);
+    }
+    matvec(t, LEVEL ? w.encw : w.hencw, LEVEL ? w.encb : w.hencb, vb, HP, h, j);
+    if (LEVEL == 1) add_column(t, w.encs, sel, j);
+    // (encode_envs ended with a barrier: nobody reads va / peb any more)
+#pragma unroll
+    for (int e = 0; e < EB; ++e) {
+        va[e * HP + j] = live ? fmaxf(t[e], 0.f) : 0.f;
+        peb[e * HP + j] = live ? fmaxf(hv[e], 0.f) : 0.f;
+    }
+    __syncthreads();
+
+    if (LEVEL == 0) {
+        // ---- one thread per (env, row): the S logits, then the critic
+        if (j < EB * SR) {
+            const int e = j / SR, r = j - e * SR;
+            float s = 0.f;
+            if (r < S) s = dot_row(w.hdisc + (size_t)r * (HP + 1), va + e * HP, h);
+            else if (r == kMaxSkills && has_critic) s = dot_row(w.hv2, peb + e * HP, h);
+            lg[j] = s;
+        }
+        __syncthreads();
+        if (j < n_env && on[j]) {
+            const int env = env0 + j;
+            const float *L = lg + j * SR;
+            out1[env] = L[kMaxSkills];
+            // Categorical(logits=log_softmax(x)): x - max - log(sum exp(x - max))
+            float m = L[0];
+            int best = 0;
+            for (int s = 1; s < S; ++s)
+                if (L[s] > m) {                           // strict: ties go to the lowest skill
+                    m = L[s];
+                    best = s;
+                }
+            float sum = 0.f;
+            for (int s = 0; s < S; ++s) sum += expf(L[s] - m);
+            const float lse = logf(sum);
+            for (int s = 0; s < S; ++s) out0[(size_t)env * S + s] = (L[s] - m) - lse;
+            if (pick.mode >= 0) {
+                int g = best;
+                if (pick.mode == 1) {
+                    // inverse CDF of softmax(x) on one uniform, in skill order
+                    const float thr = skill_uniform(pick, env) * sum;
+                    float c = 0.f;
+                    for (int s = 0; s < S; ++s) {
+                        c += expf(L[s] - m);
+                        g = s;                            // the last skill takes what rounding leaves over
+                        if (c > thr) break;
+                    }
+                }
+                st.skill[env] = g;
+                st.age[env] = 0;
+            }
+        }
+        return;
+    }
+
+    // ---- low level: mu_, std_ on va, critic.2 on peb
+    if (j < EB * 8) {
+        const int e = j >> 3, row = j & 7;
+        float s = 0.f;
+        if (row < 4) s = dot_row(w.heads + (size_t)row * (HP + 1), va + e * HP, h);
+        else if (row == 4 && has_critic) s = dot_row(w.lv2, peb + e * HP, h);
+        lg[j] = s;
+    }
+    __syncthreads();
+    if (j < n_env) {
+        const int env = env0 + j;
+        if (on[j]) {
+            const float *o = lg + 8 * j;
+            out2[env] = o[4];
+            head_outputs(env, o[0], o[1], o[2], o[3], o[4], out0, out1, act);
+            if (act.mode >= 0 && !p.sched[env].done_state) st.age[env] += 1;
+        } else {
+            skill_idle(env, out0, out1, out2, act);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_skill_sync(DevParams p, SkillState st, const uint8_t *__restrict__ mask,
+                                                    int force)
+{
+    const int env = blockIdx.x * blockDim.x + threadIdx.x;
+    if (env >= p.N) return;
+    const int32_t k = p.sched[env].episode_idx;
+    if (st.epi[env] != k || (force && (!mask || mask[env]))) {
+        st.skill[env] = -1;
+        st.age[env] = 0;
+        st.epi[env] = k;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_skill_set(DevParams p, SkillState st)
+{
+    const int env = blockIdx.x * blockDim.x + threadIdx.x;
+    if (env >= p.N) return;
+    const int32_t s = st.in[env];
+    if (s < 0) return;
+    st.skill[env] = s;
+    st.age[env] = 0;
+}
+
+}  // namespace
+
+size_t pack_skill_f32(const zenv_skill_weights &w, int F, std::vector<float> &out, size_t offs[kSkillPtrs])
+{
+    const int h = w.h_dim, S = w.n_skills;
+    out.assign(4, 0.f);                                      // no tensor at offset 0: 0 = absent
+    auto put = [&](size_t n) {                               // n zero floats, 16-byte aligned start
+        const size_t at = (out.size() + 3) & ~(size_t)3;
+        out.resize(at + n, 0.f);
+        return at;
+    };
+    // columns col0 .. col0 + n_cols - 1 of W [h][in_stride], transposed -> [rows][HP] (rows >= n_cols, zero-padded)
+    auto cols = [&](const float *W, int in_stride, int col0, int n_cols, int rows) {
+        const size_t at = put((size_t)rows * HP);
+        for (int o = 0; o < h; ++o)
+            for (int k = 0; k < n_cols; ++k) out[at + (size_t)k * HP + o] = W[(size_t)o * in_stride + col0 + k];
+        return at;
+    };
+    auto bias = [&](const float *b) {
+        const size_t at = put(HP);
+        for (int o = 0; o < h; ++o) out[at + o] = b[o];
+        return at;
+    };
+    // n output rows of W [n][h] + b [n] -> [n][HP + 1], bias last
+    auto rows = [&](const float *W, const float *b, int n) {
+        const size_t at = put((size_t)n * (HP + 1));
+        for (int r = 0; r < n; ++r) {
+            for (int k = 0; k < h; ++k) out[at + (size_t)r * (HP + 1) + k] = W[(size_t)r * h + k];
+            out[at + (size_t)r * (HP + 1) + HP] = b[r];
+        }
+        return at;
+    };
+    int i = 0;
+    // ZoneEnvModel: zone_net_.0 on [obs, (onehot,) zone row], combine_net_ on [obs, (onehot,) zone_emb]; xs = S or 0
+    auto enc = [&](const float *w1, const float *b1, const float *w2, const float *b2, const float *w3, const float *b3,
+                   const float *wc, const float *bc, int xs) {
+        offs[i++] = cols(w1, 8 + xs + F, 0, 8, 8);
+        offs[i++] = cols(w1, 8 + xs + F, 8 + xs, F, ZF);
+        offs[i++] = bias(b1);
+        offs[i++] = cols(w2, h, 0, h, HP);
+        offs[i++] = bias(b2);
+        offs[i++] = cols(w3, h, 0, h, HP);
+        offs[i++] = bias(b3);
+        offs[i++] = cols(wc, 8 + xs + h, 0, 8, 8);
+        offs[i++] = cols(wc, 8 + xs + h, 8 + xs, h, HP);
+        offs[i++] = bias(bc);
+    };
+    enc(w.hi_zone_w1, w.hi_zone_b1, w.hi_zone_w2, w.hi_zone_b2, w.hi_zone_w3, w.hi_zone_b3, w.hi_comb_w, w.hi_comb_b, 0);
+    enc(w.lo_zone_w1, w.lo_zone_b1, w.lo_zone_w2, w.lo_zone_b2, w.lo_zone_w3, w.lo_zone_b3, w.lo_comb_w, w.lo_comb_b, S);
+    offs[i++] = cols(w.lo_zone_w1, 8 + S + F, 8, S, S);     // the skill columns
+    offs[i++] = cols(w.lo_comb_w, 8 + S + h, 8, S, S);
+    offs[i++] = cols(w.hi_enc_w, h, 0, h, HP);
+    offs[i++] = bias(w.hi_enc_b);
+    offs[i++] = rows(w.hi_logit_w, w.hi_logit_b, S);
+    const bool hc = w.hi_critic_w1 != nullptr, lc = w.lo_critic_w1 != nullptr;
+    offs[i++] = hc ? cols(w.hi_critic_w1, h, 0, h, HP) : 0;
+    offs[i++] = hc ? bias(w.hi_critic_b1) : 0;
+    offs[i++] = hc ? rows(w.hi_critic_w2, w.hi_critic_b2, 1) : 0;
+    offs[i++] = cols(w.lo_enc_w, h + S, 0, h, HP);
+    offs[i++] = cols(w.lo_enc_w, h + S, h, S, S);
+    offs[i++] = bias(w.lo_enc_b);
+    offs[i] = put(4 * (size_t)(HP + 1));                    // mu_ rows 0-1, std_ rows 2-3
+    for (int r = 0; r < 4; ++r) {
+        const float *W = r < 2 ? w.lo_mu_w + (size_t)r * h : w.lo_std_w + (size_t)(r - 2) * h;
+        const float *b = r < 2 ? w.lo_mu_b + r : w.lo_std_b + (r - 2);
+        for (int k = 0; k < h; ++k) out[offs[i] + (size_t)r * (HP + 1) + k] = W[k];
+        out[offs[i] + (size_t)r * (HP + 1) + HP] = b[0];
+    }
+    ++i;
+    offs[i++] = lc ? cols(w.lo_critic_w1, h + S, 0, h, HP) : 0;
+    offs[i++] = lc ? cols(w.lo_critic_w1, h + S, h, S, S) : 0;
+    offs[i++] = lc ? bias(w.lo_critic_b1) : 0;
+    offs[i++] = lc ? rows(w.lo_critic_w2, w.lo_critic_b2, 1) : 0;
+    return out.size();
+}
+
+SkillF32 skill_f32_at(const zenv_skill_weights &w, const float *base, const size_t offs[kSkillPtrs])
+{
+    SkillF32 s{};
+    s.h = w.h_dim;
+    s.S = w.n_skills;
+    s.hi_critic = w.hi_critic_w1 ? 1 : 0;
+    s.lo_critic = w.lo_critic_w1 ? 1 : 0;
+    // the pointers of SkillF32 in declaration order (static_assert in skill_f32.hpp: nothing else sits between them)
+    const float *ptr[kSkillPtrs];
+    for (int i = 0; i < kSkillPtrs; ++i) ptr[i] = offs[i] ? base + offs[i] : nullptr;
+    std::memcpy(reinterpret_cast<char *>(&s) + offsetof(SkillF32, hi), ptr, sizeof ptr);
+    return s;
+}
+
+hipError_t launch_skill_high(const SkillF32 &w, const DevParams &p, const SkillState &st, float *logits, float *value,
+                             const SkillPick &pick, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_skill_f32<0>, dim3((p.N + EB - 1) / EB), dim3(HP), 0, s, w, p, st, logits, value, nullptr, pick,
+                       no_mlp_action());
+    return hipGetLastError();
+}
+
+hipError_t launch_skill_low(const SkillF32 &w, const DevParams &p, const SkillState &st, float *mu, float *stdv,
+                            float *value, const MlpAction &act, hipStream_t s)
+{
+    const SkillPick none{ -1, 0, 0u, 0ull, 0ull };
+    hipLaunchKernelGGL(k_skill_f32<1>, dim3((p.N + EB - 1) / EB), dim3(HP), 0, s, w, p, st, mu, stdv, value, none, act);
+    return hipGetLastError();
+}
+
+hipError_t launch_skill_sync(const DevParams &p, const SkillState &st, const uint8_t *mask, int force, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_skill_sync, dim3((p.N + 255) / 256), dim3(256), 0, s, p, st, mask, force);
+    return hipGetLastError();
+}
+
+hipError_t launch_skill_set(const DevParams &p, const SkillState &st, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_skill_set, dim3((p.N + 255) / 256), dim3(256), 0, s, p, st);
+    return hipGetLastError();
+}
+
+}  // namespace zenvk

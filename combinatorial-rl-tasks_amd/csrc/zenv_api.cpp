@@ -22,6 +22,7 @@
 #include "host_sampler.hpp"
 #include "kernels.hpp"
 #include "hier_f32.hpp"
+#include "skill_f32.hpp"
 #include "mlp_policy.hpp"
 
 using namespace zenvk;
@@ -107,6 +108,15 @@ struct zenv {
     HierF32 hier{};
     bool hier_ready = false;
     float *hier_logits = nullptr, *hier_value = nullptr;
+    // fixed-length-skills agent (zenv_skill_load): float32 weights, the per-env skill state, the high level's outputs
+    void *skill_mem = nullptr;
+    SkillF32 skill{};
+    bool skill_ready = false;
+    int skill_len = 200;                // evaluate_hier.py:21
+    int skill_n = 0;                    // S the outputs are allocated for
+    SkillState sst{};
+    void *sst_mem = nullptr;
+    float *skill_logits = nullptr, *skill_value = nullptr;
     // goal-conditioned variant (zenv_goal_enable)
     bool goal_enabled = false;
     bool order_enabled = false;   // solver-ordered variant (zenv_order_enable)
@@ -322,14 +332,23 @@ FieldInfo field_info(const zenv *h, int field)
     case ZENV_F_HI_REWARD: return { h->hout.reward, h->hi_m * 4 };
     case ZENV_F_HI_MASK: return { h->hout.mask, h->hi_m * 4 };
     case ZENV_F_HI_COUNT: return { h->hframes.count, h->hframes.count ? N * 4 : 0 };
+    case ZENV_F_SKILL: return { h->sst.skill, h->sst_mem ? N * 4 : 0 };          // (refresh_field() first)
+    case ZENV_F_SKILL_AGE: return { h->sst.age, h->sst_mem ? N * 4 : 0 };
+    case ZENV_F_SKILL_LOGITS: return { h->skill_logits, h->skill_logits ? N * h->skill_n * 4 : 0 };
+    case ZENV_F_SKILL_VALUE: return { h->skill_value, h->skill_value ? N * 4 : 0 };
     default: return { nullptr, 0 };
     }
 }
 
 // ZENV_F_EP_RETURN / ZENV_F_EP_LEN are kept inside the step kernels' 16-byte records: bring the plain arrays a caller
-// sees up to date (stream-ordered, behind every step already enqueued)
+// sees up to date (stream-ordered, behind every step already enqueued).  So is the skill state: the step kernels know
+// nothing of skills, an auto-reset shows as a new episode index (k_skill_sync).
 int refresh_field(zenv *h, int field)
 {
+    if (field == ZENV_F_SKILL || field == ZENV_F_SKILL_AGE) {
+        if (h->sst_mem) HIP_TRY(launch_skill_sync(h->p, h->sst, nullptr, 0, h->stream));
+        return ZENV_OK;
+    }
     if (field != ZENV_F_EP_RETURN && field != ZENV_F_EP_LEN) return ZENV_OK;
     HIP_TRY(launch_unpack_hot(h->p, h->pub_ep_return, h->pub_steps, h->stream));
     return ZENV_OK;
@@ -617,7 +636,8 @@ extern "C" int zenv_destroy(zenv_t *h)
                      (void *)h->p.goal_xy, (void *)h->p.shaped, (void *)h->p.need_goal, (void *)h->p.available,
                      (void *)h->goal_in, (void *)h->goal_bad, h->exp_mem, (void *)h->p.order_pos,
                      (void *)h->p.order_val, h->hier_mem, (void *)h->hier_logits, (void *)h->hier_value,
-                     h->hframes_mem, h->hcarry_mem, h->hout_mem })
+                     h->hframes_mem, h->hcarry_mem, h->hout_mem, h->skill_mem, h->sst_mem, (void *)h->skill_logits,
+                     (void *)h->skill_value })
         if (m) (void)hipFree(m);
     for (hipEvent_t ev : h->events) (void)hipEventDestroy(ev);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
@@ -954,6 +974,7 @@ extern "C" int zenv_reset(zenv_t *h, const uint8_t *mask)
     if (h->goal_enabled) HIP_TRY(launch_goal_clear(h->p, dmask, h->stream));
     if (h->order_enabled) HIP_TRY(launch_order_reset(h->p, dmask, h->stream));
     if (h->hcarry_mem) HIP_TRY(launch_hier_reset(h->hcarry, dmask, h->n_env, h->stream));
+    if (h->sst_mem) HIP_TRY(launch_skill_sync(h->p, h->sst, dmask, 1, h->stream));
     h->was_reset = true;
     return ZENV_OK;
 }
@@ -1357,6 +1378,120 @@ static int run_hier_policy(zenv_t *h, int policy, uint32_t step_index, uint64_t 
     return ZENV_OK;
 }
 
+// ============================================================================ fixed-length-skills agent
+extern "C" int zenv_skill_load(zenv_t *h, const zenv_skill_weights *w)
+{
+    if (!h || !w) return fail(ZENV_E_ARG, "null argument");
+    if (h->goal_enabled || h->order_enabled)
+        return fail(ZENV_E_STATE, "the skill agent steps a plain task handle, not a goal-conditioned / solver-ordered one");
+    if (w->h_dim < 1 || w->h_dim >= kMlpHP) return fail(ZENV_E_ARG, "h_dim %d outside 1 .. %d", w->h_dim, kMlpHP - 1);
+    if (w->n_skills < 1 || w->n_skills > kMaxSkills)
+        return fail(ZENV_E_ARG, "n_skills %d outside 1 .. %d", w->n_skills, kMaxSkills);
+    if (w->precision != ZENV_MLP_F32)
+        return fail(ZENV_E_ARG, "zenv_skill_weights.precision %d: only ZENV_MLP_F32 is built", w->precision);
+    if (w->zone_feat != h->p.F)
+        return fail(ZENV_E_ARG, "the weights take zone rows of %d features, this handle's have %d", w->zone_feat, h->p.F);
+    for (const float *t : { w->hi_zone_w1, w->hi_zone_b1, w->hi_zone_w2, w->hi_zone_b2, w->hi_zone_w3, w->hi_zone_b3,
+                            w->hi_comb_w, w->hi_comb_b, w->hi_enc_w, w->hi_enc_b, w->hi_logit_w, w->hi_logit_b,
+                            w->lo_zone_w1, w->lo_zone_b1, w->lo_zone_w2, w->lo_zone_b2, w->lo_zone_w3, w->lo_zone_b3,
+                            w->lo_comb_w, w->lo_comb_b, w->lo_enc_w, w->lo_enc_b, w->lo_mu_w, w->lo_mu_b, w->lo_std_w,
+                            w->lo_std_b })
+        if (!t) return fail(ZENV_E_ARG, "zenv_skill_weights has a null actor tensor");
+    const int n_hc = (w->hi_critic_w1 != nullptr) + (w->hi_critic_b1 != nullptr) + (w->hi_critic_w2 != nullptr) +
+                     (w->hi_critic_b2 != nullptr);
+    const int n_lc = (w->lo_critic_w1 != nullptr) + (w->lo_critic_b1 != nullptr) + (w->lo_critic_w2 != nullptr) +
+                     (w->lo_critic_b2 != nullptr);
+    if ((n_hc != 0 && n_hc != 4) || (n_lc != 0 && n_lc != 4))
+        return fail(ZENV_E_ARG, "give all four tensors of a critic or none");
+    std::vector<float> img;
+    size_t o[kSkillPtrs];
+    pack_skill_f32(*w, h->p.F, img, o);
+    int rc = use_device(h);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const size_t N = (size_t)h->n_env, S = (size_t)w->n_skills;
+    h->skill_ready = false;
+    if (h->skill_mem) HIP_TRY(hipFree(h->skill_mem));
+    h->skill_mem = nullptr;
+    HIP_TRY(hipMalloc(&h->skill_mem, img.size() * sizeof(float)));
+    HIP_TRY(hipMemcpy(h->skill_mem, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
+    // the low level writes the flat network's output fields (ZENV_F_POLICY_*): allocated by whichever loads first
+    if (!h->mlp_value) HIP_TRY(hipMalloc((void **)&h->mlp_value, N * sizeof(float)));
+    if (!h->mlp_mu) HIP_TRY(hipMalloc((void **)&h->mlp_mu, N * 2 * sizeof(float)));
+    if (!h->mlp_std) HIP_TRY(hipMalloc((void **)&h->mlp_std, N * 2 * sizeof(float)));
+    if (h->skill_logits && h->skill_n != (int)S) {
+        HIP_TRY(hipFree(h->skill_logits));
+        h->skill_logits = nullptr;
+    }
+    if (!h->skill_logits) HIP_TRY(hipMalloc((void **)&h->skill_logits, N * S * sizeof(float)));
+    h->skill_n = (int)S;
+    if (!h->skill_value) HIP_TRY(hipMalloc((void **)&h->skill_value, N * sizeof(float)));
+    if (!h->sst_mem) {
+        HIP_TRY(hipMalloc(&h->sst_mem, 4 * N * sizeof(int32_t)));
+        int32_t *m = static_cast<int32_t *>(h->sst_mem);
+        h->sst = SkillState{ m, m + N, m + 2 * N, m + 3 * N };
+    }
+    HIP_TRY(hipMemsetAsync(h->skill_logits, 0, N * S * sizeof(float), h->stream));
+    HIP_TRY(hipMemsetAsync(h->skill_value, 0, N * sizeof(float), h->stream));
+    HIP_TRY(launch_skill_sync(h->p, h->sst, nullptr, 1, h->stream));     // every env: no skill (the new S may be smaller)
+    h->skill = skill_f32_at(*w, static_cast<const float *>(h->skill_mem), o);
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->skill_ready = true;
+    return ZENV_OK;
+}
+
+extern "C" int zenv_skill_configure(zenv_t *h, int skill_len)
+{
+    if (!h) return fail(ZENV_E_ARG, "null handle");
+    if (skill_len < 1) return fail(ZENV_E_ARG, "skill_len %d: must be >= 1", skill_len);
+    h->skill_len = skill_len;
+    return ZENV_OK;
+}
+
+extern "C" int zenv_set_skills(zenv_t *h, const int32_t *skills)
+{
+    if (!h || !skills) return fail(ZENV_E_ARG, "null argument");
+    if (!h->skill_ready) return fail(ZENV_E_STATE, "zenv_skill_load first");
+    for (int i = 0; i < h->n_env; ++i)
+        if (skills[i] < -1 || skills[i] >= h->skill_n)
+            return fail(ZENV_E_ARG, "env %d: skill %d outside -1 .. %d", i, skills[i], h->skill_n - 1);
+    int rc = use_device(h);
+    if (rc) return rc;
+    HIP_TRY(launch_skill_sync(h->p, h->sst, nullptr, 0, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->sst.in, skills, sizeof(int32_t) * (size_t)h->n_env, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(launch_skill_set(h->p, h->sst, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));      // `skills` is the caller's (pageable) memory
+    return ZENV_OK;
+}
+
+extern "C" int zenv_skill_forward(zenv_t *h)
+{
+    if (!h) return fail(ZENV_E_ARG, "null handle");
+    if (!h->skill_ready) return fail(ZENV_E_STATE, "zenv_skill_load first");
+    if (!h->was_reset) return fail(ZENV_E_STATE, "reset before asking for actions");
+    int rc = use_device(h);
+    if (rc) return rc;
+    HIP_TRY(launch_skill_sync(h->p, h->sst, nullptr, 0, h->stream));
+    const SkillPick none{ -1, h->skill_len, 0u, 0ull, 0ull };
+    HIP_TRY(launch_skill_high(h->skill, h->p, h->sst, h->skill_logits, h->skill_value, none, h->stream));
+    HIP_TRY(launch_skill_low(h->skill, h->p, h->sst, h->mlp_mu, h->mlp_std, h->mlp_value, no_mlp_action(), h->stream));
+    return ZENV_OK;
+}
+
+// one step of evaluate_hier.py:63-67: a skill for the envs whose skill ran out (or that have none), then the low level's
+// action of every env into `out`
+static int run_skill_policy(zenv_t *h, int policy, uint32_t step_index, uint64_t seed, uint64_t env_index0, float *out)
+{
+    if (!h->skill_ready) return fail(ZENV_E_STATE, "zenv_skill_load first");
+    const int mode = policy == ZENV_POLICY_SKILL_SAMPLE ? 1 : 0;
+    HIP_TRY(launch_skill_sync(h->p, h->sst, nullptr, 0, h->stream));
+    const SkillPick pick{ mode, h->skill_len, step_index, seed, env_index0 };
+    HIP_TRY(launch_skill_high(h->skill, h->p, h->sst, h->skill_logits, h->skill_value, pick, h->stream));
+    const MlpAction act{ mode, step_index, seed, env_index0, out, MlpRecord{} };
+    HIP_TRY(launch_skill_low(h->skill, h->p, h->sst, h->mlp_mu, h->mlp_std, h->mlp_value, act, h->stream));
+    return ZENV_OK;
+}
+
 static bool policy_known(int policy) { return policy >= ZENV_POLICY_UNIFORM && policy <= ZENV_POLICY_MLP_SAMPLE; }
 static bool policy_is_mlp(int policy) { return policy == ZENV_POLICY_MLP_MEAN || policy == ZENV_POLICY_MLP_SAMPLE; }
 
@@ -1633,13 +1768,15 @@ extern "C" int zenv_policy(zenv_t *h, int policy, uint64_t policy_seed, uint64_t
     if (!h) return fail(ZENV_E_ARG, "null handle");
     if (!h->was_reset) return fail(ZENV_E_STATE, "reset before asking for actions");
     const bool hier = policy == ZENV_POLICY_HIER_SAMPLE || policy == ZENV_POLICY_HIER_MEAN;
-    if (!policy_known(policy) && !hier) return fail(ZENV_E_ARG, "unknown policy %d", policy);
+    const bool skill = policy == ZENV_POLICY_SKILL_SAMPLE || policy == ZENV_POLICY_SKILL_MEAN;
+    if (!policy_known(policy) && !hier && !skill) return fail(ZENV_E_ARG, "unknown policy %d", policy);
     int rc = use_device(h);
     if (rc) return rc;
     const StepPolicy pol{ policy, (uint32_t)h->step_count, policy_seed, env_index0,
                           dst_device ? dst_device : h->p.actions };
     h->act_tag.valid = false;
     if (hier) return run_hier_policy(h, policy, pol.step_index, policy_seed, env_index0, pol.out);
+    if (skill) return run_skill_policy(h, policy, pol.step_index, policy_seed, env_index0, pol.out);
     return run_policy(h, pol);
 }
 
@@ -2039,7 +2176,7 @@ extern "C" int zenv_device_ptr(zenv_t *h, int field, void **ptr)
     if (!h || !ptr) return fail(ZENV_E_ARG, "null argument");
     const FieldInfo f = field_info(h, field);
     if (!f.ptr) return fail(ZENV_E_ARG, "unknown field %d", field);
-    if (field == ZENV_F_EP_RETURN || field == ZENV_F_EP_LEN) {
+    if (field == ZENV_F_EP_RETURN || field == ZENV_F_EP_LEN || field == ZENV_F_SKILL || field == ZENV_F_SKILL_AGE) {
         // these two live inside the step kernels' records: the pointer is to a plain copy brought up to date by THIS
         // call (stream-ordered), not a live view
         int rc = use_device(h);

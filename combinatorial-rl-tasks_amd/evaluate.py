@@ -3,7 +3,8 @@
 100 maps (env seeds 1000000..1000099) x 5 runs per map, undiscounted episodic return,
 result layout ``{"return": [[r_run0..r_run4] for each map]}`` -- but all maps and runs are
 stepped together as one batch of n_maps*n_runs envs instead of 500 sequential episodes.
-``evaluate_zone_hrl`` does the same for zone-goals/scripts/evaluate_zone_hrl.py with the Zone-goals hierarchical agent.
+``evaluate_zone_hrl`` does the same for zone-goals/scripts/evaluate_zone_hrl.py with the Zone-goals hierarchical agent,
+``evaluate_hier`` for main/scripts/evaluate_hier.py with the fixed-length-skills agent.
 """
 import pickle
 
@@ -134,6 +135,55 @@ def evaluate_zone_hrl(env_id, model, n_maps=100, n_runs_per_map=5, env_seed0=EVA
             _, _, _, d, g, _ = env.step_results(None, copy=False)
             goal |= g
             if d.all():                    # every episode finished (evaluate_zone_hrl.py:66-75)
+                break
+        out = {
+            "return": env.get(nat.F_LAST_RETURN).reshape(n_maps, n_runs_per_map).tolist(),
+            "length": env.get(nat.F_LAST_LEN).reshape(n_maps, n_runs_per_map).tolist(),
+            "goal_met": goal.reshape(n_maps, n_runs_per_map).tolist(),
+        }
+    finally:
+        env.close()
+    if pkl_path:
+        with open(pkl_path, "wb") as f:
+            pickle.dump({"return": out["return"]}, f)
+    return out
+
+
+def evaluate_hier(env_id, model, n_maps=100, n_runs_per_map=5, n_skills=None, skill_len=200, policy_seed=0,
+                  argmax=False, pkl_path=None, device=0, max_steps=None, env_seed0=EVAL_SEED0):
+    """The protocol of main/scripts/evaluate_hier.py (100 maps x 5 runs, env seeds 1000000.., undiscounted return)
+    with the fixed-length-skills agent on the device, every map and run stepped together as one batch.  Per step
+    (:63-67): every ``skill_len`` steps from the episode's reset HighPolicyValueModel picks a skill (a draw from
+    Categorical, or the argmax with ``argmax=True``), then LoPolicyValueModel acts under it (``dist.sample()``, or mu).
+
+    env_id: a registry id ("PointTSP-v0" ...: make_fixed_env(hier=True) is the plain task env) or a Config;
+    model: a model directory, its ``status.pt``, or a ``(hi_state_dict, lo_state_dict)`` pair; n_skills: checked
+    against the checkpoint's when given (evaluate_hier.py builds HierAgent with 5).
+    Returns ``{"return": [[...]], "length": [[...]], "goal_met": [[...]]}`` as ``evaluate`` does and writes
+    ``{"return": ...}`` to ``pkl_path`` (evaluate_hier.py:45, :80-83)."""
+    from .vec_env import skill_tensors_from_state_dicts
+    cfg = config_for_id(env_id) if isinstance(env_id, str) else env_id
+    hi_sd, lo_sd = load_hier_model_state(model) if isinstance(model, str) else model
+    tensors = skill_tensors_from_state_dicts(hi_sd, lo_sd)
+    S = tensors["hi_logit_w"].shape[0]
+    if n_skills is not None and n_skills != S:
+        raise ValueError(f"n_skills={n_skills}, but the checkpoint's high level has {S} skills")
+    n = n_maps * n_runs_per_map
+    env = ZoneVecEnv(cfg, n, device=device)
+    try:
+        env.build_bank(env_seed0, n_maps)
+        env.schedule_sequential(first=np.repeat(np.arange(n_maps, dtype=np.int32), n_runs_per_map), stride=0)
+        env.reset()
+        env.load_skills(tensors, skill_len=skill_len)
+        policy = nat.POLICY_SKILL_MEAN if argmax else nat.POLICY_SKILL_SAMPLE
+        goal = np.zeros(n, bool)
+        horizon = cfg.num_steps if max_steps is None else max_steps
+        for t in range(horizon):
+            env.policy(policy, policy_seed=policy_seed)
+            env.step(None, auto_reset=False)
+            _, _, _, d, g, _ = env.step_results(None, copy=False)
+            goal |= g
+            if d.all():                    # every episode finished (evaluate_hier.py:72-79)
                 break
         out = {
             "return": env.get(nat.F_LAST_RETURN).reshape(n_maps, n_runs_per_map).tolist(),

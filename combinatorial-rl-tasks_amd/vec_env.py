@@ -27,7 +27,8 @@ _FIELD_DTYPES = {
     nat.F_LO_GOAL: np.float32, nat.F_LO_ENV_REWARD: np.float32, nat.F_HI_OBS: np.float32, nat.F_HI_ZONE_OBS: np.float32,
     nat.F_HI_ACTION: np.int32, nat.F_HI_ACTION_MASK: np.uint8, nat.F_HI_VALUE: np.float32, nat.F_HI_LOG_PROB: np.float32,
     nat.F_HI_ADVANTAGE: np.float32, nat.F_HI_RETURN: np.float32, nat.F_HI_REWARD: np.float32, nat.F_HI_MASK: np.float32,
-    nat.F_HI_COUNT: np.int32,
+    nat.F_HI_COUNT: np.int32, nat.F_SKILL: np.int32, nat.F_SKILL_AGE: np.int32, nat.F_SKILL_LOGITS: np.float32,
+    nat.F_SKILL_VALUE: np.float32,
 }
 
 
@@ -179,6 +180,55 @@ def hier_experience_layout(num_envs, num_zones, zone_feat, frames_per_proc, n_hi
           "advantage": (nat.F_HI_ADVANTAGE, (M,), f32), "returnn": (nat.F_HI_RETURN, (M,), f32),
           "reward": (nat.F_HI_REWARD, (M,), f32), "mask": (nat.F_HI_MASK, (M,), f32)}
     return lo, hi
+
+
+# zenv_skill_weights name -> state_dict key (main/src/hier_policy_value_models.py:19-76, env_model.py:81-117,
+# policy_network.py:9-55): hi_model_state and lo_model_state of status.pt (main/scripts/train_skill_planner.py:152-163)
+SKILL_HI_KEYS = dict(_HIER_ENC, enc_w="actor.enc_.0.0.weight", enc_b="actor.enc_.0.0.bias",
+                     logit_w="actor.discrete_.0.weight", logit_b="actor.discrete_.0.bias")
+SKILL_LO_KEYS = HIER_LO_KEYS
+
+
+def skill_tensor_shapes(h, S, F):
+    """The shape of every zenv_skill_weights tensor for hidden size h, S skills and zone rows of F features."""
+    enc = lambda x: {"zone_w1": (h, x + F), "zone_b1": (h,), "zone_w2": (h, h), "zone_b2": (h,), "zone_w3": (h, h),
+                     "zone_b3": (h,), "comb_w": (h, x + h), "comb_b": (h,)}
+    crit = lambda x: {"critic_w1": (h, x), "critic_b1": (h,), "critic_w2": (1, h), "critic_b2": (1,)}
+    hi = dict(enc(8), enc_w=(h, h), enc_b=(h,), logit_w=(S, h), logit_b=(S,), **crit(h))
+    lo = dict(enc(8 + S), enc_w=(h, h + S), enc_b=(h,), mu_w=(2, h), mu_b=(2,), std_w=(2, h), std_b=(2,), **crit(h + S))
+    return dict({"hi_" + k: v for k, v in hi.items()}, **{"lo_" + k: v for k, v in lo.items()})
+
+
+def skill_tensors_from_state_dicts(hi_sd, lo_sd):
+    """HighPolicyValueModel.state_dict() and LoPolicyValueModel.state_dict() of the fixed-length-skills agent -> the
+    tensors ``ZoneVecEnv.load_skills`` wants (numpy float32, names of ``_native.SKILL_*``).  The hidden size h and the
+    number of skills S come from the shapes (actor.discrete_.0 is [S, h]).  The critics are taken when present.  A
+    Zone-goals checkpoint (the same hi_model_state / lo_model_state keys, an actor.0 / actor.2 high level), a missing
+    key or a tensor whose shape does not fit the others raises ValueError naming it."""
+    if "actor.0.weight" in hi_sd or "actor.2.weight" in hi_sd:
+        raise ValueError("hi_model_state has 'actor.0' / 'actor.2': a Zone-goals checkpoint (load it with "
+                         "hier_tensors_from_state_dicts / load_hier), not a skill planner's")
+    out = {}
+    for level, sd, keys in (("hi", hi_sd, SKILL_HI_KEYS), ("lo", lo_sd, SKILL_LO_KEYS)):
+        names = dict(keys)
+        if "critic.0.weight" in sd or "critic.2.weight" in sd:
+            names.update(_HIER_CRITIC)
+        for name, key in names.items():
+            if key not in sd:
+                raise ValueError(f"{level}_model_state has no {key!r} (needed for {level}_{name})")
+            v = sd[key]
+            out[f"{level}_{name}"] = np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, np.float32)
+    logit = out["hi_logit_w"]
+    h, S = (logit.shape[1], logit.shape[0]) if logit.ndim == 2 else (-1, -1)
+    F = out["hi_zone_w1"].shape[1] - 8 if out["hi_zone_w1"].ndim == 2 else -1
+    want = skill_tensor_shapes(h, S, F)
+    for name, a in out.items():
+        if a.shape != want[name]:
+            level, rest = name.split("_", 1)
+            key = (SKILL_HI_KEYS if level == "hi" else SKILL_LO_KEYS).get(rest) or _HIER_CRITIC[rest]
+            raise ValueError(f"{level}_model_state[{key!r}] has shape {tuple(a.shape)}, expected {want[name]} "
+                             f"(hidden size {h}, {S} skills, zone rows of {F} features)")
+    return out
 
 
 def zone_feat(cfg):
@@ -551,6 +601,54 @@ class ZoneVecEnv:
         return (self.get(nat.F_HIER_LOGITS), self.get(nat.F_HIER_VALUE), self.get(nat.F_POLICY_MU),
                 self.get(nat.F_POLICY_STD), self.get(nat.F_POLICY_VALUE))
 
+    # ------------------------------------------------------------------ fixed-length-skills agent
+    def load_skills(self, tensors, skill_len=200, precision="f32"):
+        """HighPolicyValueModel + LoPolicyValueModel of the skill planner (main/src/hier_policy_value_models.py:19-76)
+        for ``skill_forward`` and the device policies POLICY_SKILL_SAMPLE / POLICY_SKILL_MEAN, which pick a new skill
+        every ``skill_len`` steps of an episode (evaluate_hier.py:21, :63-64).  tensors: dict of float32 arrays named
+        as in ``_native.SKILL_*`` (see ``skill_tensors_from_state_dicts``); each critic is optional.  A plain task
+        handle only (not ``enable_goals`` / ``enable_order``).  Every env starts without a skill.  precision: "f32"
+        (the only one built: float32 throughout, within 1e-5 of torch)."""
+        if precision != "f32":
+            raise ValueError(f"precision {precision!r}: the skill agent is built in float32 only")
+        logit = np.asarray(tensors["hi_logit_w"])
+        S, h = int(logit.shape[0]), int(logit.shape[1])
+        F = int(np.asarray(tensors["hi_zone_w1"]).shape[1]) - 8
+        want = skill_tensor_shapes(h, S, F)
+        names = nat.SKILL_HI_TENSORS + nat.SKILL_LO_TENSORS + (
+            nat.SKILL_HI_CRITIC if "hi_critic_w1" in tensors else ()) + (
+            nat.SKILL_LO_CRITIC if "lo_critic_w1" in tensors else ())
+        w = nat.SkillWeights(h_dim=h, n_skills=S, zone_feat=F, precision=nat.MLP_F32)
+        keep = {}
+        for name in names:
+            a = np.ascontiguousarray(tensors[name], np.float32)
+            if a.shape != want[name]:
+                raise ValueError(f"{name}: shape {a.shape}, expected {want[name]}")
+            keep[name] = a
+            setattr(w, name, a.ctypes.data)
+        check(lib().zenv_skill_configure(self._h, int(skill_len)))
+        check(lib().zenv_skill_load(self._h, C.byref(w)))
+        self._skill_n = S
+
+    def configure_skills(self, skill_len):
+        """A new skill every ``skill_len`` steps (>= 1) from the next pick on."""
+        check(lib().zenv_skill_configure(self._h, int(skill_len)))
+
+    def set_skills(self, skills):
+        """skills: int32 [N] in -1 .. S-1; env i gets skills[i] with its age restarting at 0, -1 leaves it alone."""
+        s = np.ascontiguousarray(skills, np.int32)
+        if s.shape != (self.num_envs,):
+            raise ValueError(f"skills must have shape ({self.num_envs},)")
+        check(lib().zenv_set_skills(self._h, s.ctypes.data))
+
+    def skill_forward(self):
+        """Both networks on the current observations: (log-softmax logits float32 [N,S], high-level value [N], mu [N,2],
+        std [N,2], low-level value [N]); the low level under each env's current skill (``get(F_SKILL)``), zeros for an
+        env without one.  Values are 0 without the critic tensors.  The skill state does not move."""
+        check(lib().zenv_skill_forward(self._h))
+        return (self.get(nat.F_SKILL_LOGITS), self.get(nat.F_SKILL_VALUE), self.get(nat.F_POLICY_MU),
+                self.get(nat.F_POLICY_STD), self.get(nat.F_POLICY_VALUE))
+
     # ------------------------------------------------------------------ one PPO rollout (SURVEY 8(f) row 2)
     def collect(self, frames_per_proc, policy_seed=1, env_index0=0, discount=0.99, gae_lambda=0.95):
         """BaseAlgo.collect_experiences (main/src/torch_ac/algos/base.py:131-227) on the device with the loaded
@@ -687,6 +785,8 @@ class ZoneVecEnv:
             return (N, nat.OBS_DIM)
         if field in (nat.F_ORDER_VAL, nat.F_ORDER_POS, nat.F_HIER_LOGITS):
             return (N, self.num_zones)
+        if field == nat.F_SKILL_LOGITS:
+            return (N, getattr(self, "_skill_n", 0))
         if field == nat.F_ZONE_OBS:
             return (N, self.num_zones, self.zone_feat)
         if field in (nat.F_ACTIONS, nat.F_POLICY_MU, nat.F_POLICY_STD):

@@ -114,7 +114,15 @@ enum {
     ZENV_F_HI_REWARD = 48,       /* float32 [M]      the transition's reward: the env rewards from its pick to its close */
     ZENV_F_HI_MASK = 49,         /* float32 [M]      hi_mask: 0 when it closed because the episode ended, else 1 */
     ZENV_F_HI_COUNT = 50,        /* int32   [N]      rows of every env (closed transitions of the last call) */
-    ZENV_F_COUNT = 51
+    /* fixed-length-skills agent (zenv_skill_load).  zenv_reset and every auto-reset (zenv_step, zenv_step_many,
+     * zenv_collect ...) clear the skill state; zenv_get / zenv_device_ptr bring it up to date (like ZENV_F_EP_LEN, a
+     * device pointer of these two is a copy as of that call, not a live view) */
+    ZENV_F_SKILL = 51,           /* int32   [N]      the env's current skill, -1 = none */
+    ZENV_F_SKILL_AGE = 52,       /* int32   [N]      low-level steps taken under the current skill */
+    ZENV_F_SKILL_LOGITS = 53,    /* float32 [N,S]    the high level's log-softmax: what Categorical(logits=log_softmax(x))
+                                  *                    holds (main/src/policy_network.py:40-43) */
+    ZENV_F_SKILL_VALUE = 54,     /* float32 [N]      the high level's critic value (0 without critic tensors) */
+    ZENV_F_COUNT = 55
 };
 
 /* scripted on-device action sources (the build's own; used by bench/tests) */
@@ -126,7 +134,11 @@ enum {
     /* the Zone-goals hierarchical agent (zenv_hier_load; goal-conditioned handles only), see zenv_hier_forward */
     ZENV_POLICY_HIER_SAMPLE = 4, /* goal ~ Categorical(masked logits), a ~ Normal(mu, std): HierAgent.get_hi_action /
                                   * get_lo_action (zone-goals/src/utils/hier_agent.py) */
-    ZENV_POLICY_HIER_MEAN = 5    /* goal = argmax of the masked logits (ties: lowest zone), a = mu: deterministic */
+    ZENV_POLICY_HIER_MEAN = 5,   /* goal = argmax of the masked logits (ties: lowest zone), a = mu: deterministic */
+    /* the fixed-length-skills agent (zenv_skill_load; plain task handles only), see zenv_skill_forward */
+    ZENV_POLICY_SKILL_SAMPLE = 6, /* skill ~ Categorical(logits) every skill_len steps, a ~ Normal(mu, std): HierAgent.
+                                   * get_hi_action / get_lo_action (main/src/utils/hier_agent.py) */
+    ZENV_POLICY_SKILL_MEAN = 7    /* skill = argmax (ties: lowest skill), a = mu: deterministic */
 };
 
 /* kernel layouts */
@@ -448,6 +460,71 @@ int zenv_hier_load(zenv_t *h, const zenv_hier_weights *w);
  * synchronisation.  zenv_rollout() / zenv_collect() do not take these policies; zenv_collect_hier() collects training
  * experience with them. */
 int zenv_hier_forward(zenv_t *h);
+
+/* ---- the fixed-length-skills agent on the device ----
+ * HighPolicyValueModel and LoPolicyValueModel (main/src/hier_policy_value_models.py:19-76) with the per-step loop of
+ * main/scripts/evaluate_hier.py:48-84: every skill_len steps counted from the episode's reset the high level picks one
+ * of S skills, and every step the low level acts under the current one.  DIAYN ("Skills + Diversity") evaluates with
+ * the same two networks.  Checkpoint: status.pt's hi_model_state / lo_model_state (main/scripts/train_skill_planner.py:
+ * 152-163).  h = hidden size (--hidden-size, 128 by default), S = n_skills, F = zenv_zone_feat(cfg).
+ *   high:  emb = ZoneEnvModel(obs, zone_obs) (main/src/env_model.py, the flat agent's encoder);
+ *          logits = actor.discrete_.0(relu(actor.enc_.0.0(emb))), Categorical(logits=log_softmax(logits))
+ *          (policy_network.py:40-43); value = critic.2(relu(critic.0(emb))).
+ *   low:   onehot = one_hot(skill, S); emb = ZoneEnvSkillModel(obs, onehot, zone_obs) (env_model.py:81-117: zone_net_ on
+ *          [obs, onehot, zone row], combine_net_ on [obs, onehot, zone_emb]); x = [emb, onehot];
+ *          Normal(mu, std) = PolicyNetwork(x) (mu = 2 (sigmoid(mu_) - 0.5), std = sigmoid(std_) + 1e-3);
+ *          value = critic.2(relu(critic.0(x))).
+ * Host float32 tensors in the state_dict's layout (row-major [out][in]); each critic is optional (all four of it NULL =
+ * no value output, 0 is written).  These weights are separate from zenv_mlp_load's and zenv_hier_load's: loading one
+ * set leaves the others. */
+typedef struct zenv_skill_weights {
+    int32_t h_dim;                        /* 1 .. 191 */
+    int32_t n_skills;                     /* S: 1 .. 32 */
+    int32_t zone_feat;                    /* F the weights were built for (the handle's zenv_zone_feat) */
+    int32_t precision;                    /* ZENV_MLP_F32 only: the float32 vector-ALU kernels of skill_f32.hip */
+    /* hi_model_state (HighPolicyValueModel) */
+    const float *hi_zone_w1, *hi_zone_b1; /* env_model.zone_net_.0  [h, 8+F],   [h]  input = [obs, zone row] */
+    const float *hi_zone_w2, *hi_zone_b2; /* env_model.zone_net_.2  [h, h],     [h] */
+    const float *hi_zone_w3, *hi_zone_b3; /* env_model.zone_net_.4  [h, h],     [h] */
+    const float *hi_comb_w, *hi_comb_b;   /* env_model.combine_net_ [h, 8+h],   [h]  input = [obs, zone_emb] */
+    const float *hi_enc_w, *hi_enc_b;     /* actor.enc_.0.0         [h, h],     [h]  input = emb */
+    const float *hi_logit_w, *hi_logit_b; /* actor.discrete_.0      [S, h],     [S] */
+    const float *hi_critic_w1, *hi_critic_b1; /* critic.0           [h, h],     [h]  (optional) */
+    const float *hi_critic_w2, *hi_critic_b2; /* critic.2           [1, h],     [1]  (optional) */
+    /* lo_model_state (LoPolicyValueModel) */
+    const float *lo_zone_w1, *lo_zone_b1; /* env_model.zone_net_.0  [h, 8+S+F], [h]  input = [obs, onehot, zone row] */
+    const float *lo_zone_w2, *lo_zone_b2; /* env_model.zone_net_.2  [h, h],     [h] */
+    const float *lo_zone_w3, *lo_zone_b3; /* env_model.zone_net_.4  [h, h],     [h] */
+    const float *lo_comb_w, *lo_comb_b;   /* env_model.combine_net_ [h, 8+S+h], [h]  input = [obs, onehot, zone_emb] */
+    const float *lo_enc_w, *lo_enc_b;     /* actor.enc_.0.0         [h, h+S],   [h]  input = [emb, onehot] */
+    const float *lo_mu_w, *lo_mu_b;       /* actor.mu_              [2, h],     [2] */
+    const float *lo_std_w, *lo_std_b;     /* actor.std_             [2, h],     [2] */
+    const float *lo_critic_w1, *lo_critic_b1; /* critic.0           [h, h+S],   [h]  input = [emb, onehot] (optional) */
+    const float *lo_critic_w2, *lo_critic_b2; /* critic.2           [1, h],     [1]  (optional) */
+} zenv_skill_weights;
+/* ZENV_E_STATE on a goal-conditioned or solver-ordered handle; ZENV_E_ARG for h_dim outside 1 .. 191, n_skills outside
+ * 1 .. 32, a zone_feat other than the handle's F, a precision other than ZENV_MLP_F32, a null actor tensor or a critic
+ * given in part.  Loading allocates the per-env skill state (ZENV_F_SKILL = -1, ZENV_F_SKILL_AGE = 0 for every env). */
+int zenv_skill_load(zenv_t *h, const zenv_skill_weights *w);
+/* skill_len: the high level picks every skill_len steps (evaluate_hier.py:21).  200 until set; ZENV_E_ARG below 1. */
+int zenv_skill_configure(zenv_t *h, int skill_len);
+/* skills [N] from the host: env i gets skill skills[i] with its age restarting at 0; -1 leaves env i alone.
+ * ZENV_E_ARG for a value outside -1 .. S-1 (nothing is changed then); ZENV_E_STATE before zenv_skill_load. */
+int zenv_set_skills(zenv_t *h, const int32_t *skills);
+/* Both networks on the current observations, every env:
+ *   ZENV_F_SKILL_LOGITS / ZENV_F_SKILL_VALUE  the high level
+ *   ZENV_F_POLICY_MU / _STD / _VALUE          the low level under the env's current skill (ZENV_F_SKILL); an env without
+ *                                             one gets 0 in all three.
+ * The skill state does not move.
+ * zenv_policy(ZENV_POLICY_SKILL_*) runs the same two networks as one step of evaluate_hier.py:63-67, on the device:
+ * every env whose skill is -1 or whose age has reached skill_len, and which is not finished (left alone by
+ * step_no_reset), picks a skill (age 0) -- the high level is evaluated only for those, ZENV_F_SKILL_LOGITS / _VALUE are
+ * refreshed for those -- then the low level writes the action of every env (0 for an env without a skill), and the age
+ * of every unfinished env goes up by one.  With the reset clearing the state this is `i % skill_len == 0`, i counted
+ * from the episode's reset.  Randomness: Philox keyed by (policy_seed, env_index0 + env, zenv_step_count) with separate
+ * streams for the skill and the action draw.  No host synchronisation.  zenv_rollout() refuses these policies
+ * (ZENV_E_ARG); zenv_collect() takes none (it runs the flat network). */
+int zenv_skill_forward(zenv_t *h);
 
 /* ---- one PPO rollout on the device: BaseAlgo.collect_experiences, main/src/torch_ac/algos/base.py:131-227 ----
  * T times: (dist, value) = acmodel(obs) [zenv_mlp_forward]; action = dist.sample(); record obs, action, value,
