@@ -9,11 +9,12 @@ import numpy as np
 import pytest
 
 from tests import hier_ref
+from tests.hier_collect_ref import GAMMA, LAM
+from tests.hier_collect_ref import expected_hi as _expected_hi, log_softmax_at as _log_softmax_at, replay as _replay
 
 pytestmark = pytest.mark.gpu
 
 BASE = {"PointTSP-v3": "PointTSP-v0", "PointTTSP-v3": "PointTTSP-v0", "ColourMatch-v3": "ColourMatch-v0"}
-LAM, GAMMA = 0.95, 0.99
 
 
 def _goal_env(Z, env_id, n, seed=11, **over):
@@ -38,88 +39,6 @@ def _raw(Z, env, field, shape, dtype=np.float32):
     assert a.nbytes == env.field_bytes(field)
     Z._native.check(Z._native.lib().zenv_get(env._h, field, a.ctypes.data, 0))
     return a
-
-
-def _replay(Z, env, frames, seed):
-    """Drive `env` with zenv_policy(HIER_SAMPLE) + zenv_step for `frames` frames; the per-frame record."""
-    log = {k: [] for k in ("obs", "zone_obs", "need", "avail", "goal", "pick_value", "logits", "action", "mu", "std",
-                           "value", "reward", "done", "shaped", "need_after")}
-    for _ in range(frames):
-        o, zo = env.observations()
-        _, need, avail, _ = env.goal_info()
-        env.policy(Z.POLICY_HIER_SAMPLE, policy_seed=seed)
-        log["obs"].append(o)
-        log["zone_obs"].append(zo)
-        log["need"].append(need)
-        log["avail"].append(avail)
-        log["goal"].append(env.get(Z.F_GOAL))
-        log["pick_value"].append(env.get(Z.F_HIER_VALUE))
-        log["logits"].append(env.get(Z.F_HIER_LOGITS))
-        log["action"].append(env.get(Z.F_ACTIONS))
-        log["mu"].append(env.get(Z.F_POLICY_MU))
-        log["std"].append(env.get(Z.F_POLICY_STD))
-        log["value"].append(env.get(Z.F_POLICY_VALUE))
-        env.step(None, auto_reset=True)
-        _, _, r, d, _ = env.results()
-        sh, need_after, _, _ = env.goal_info()
-        log["reward"].append(r)
-        log["done"].append(d)
-        log["shaped"].append(sh)
-        log["need_after"].append(need_after)
-    return {k: np.stack(v) for k, v in log.items()}
-
-
-def _log_softmax_at(logits, g):
-    fin = np.isfinite(logits)
-    l64 = logits.astype(np.float64)
-    m = l64[fin].max()
-    return l64[g] - m - np.log(np.exp(l64[fin] - m).sum())
-
-
-def _expected_hi(b, T, n_calls, v_final):
-    """The numpy restatement: per call, per env, the closed transitions in order with their GAE (_hier_policy_opt.py:
-    66-76, 98-107).  v_final[c] = V_hi(obs_T) after call c.  Also returns what the call-boundary cases looked like."""
-    n = b["obs"].shape[1]
-    out = [[[] for _ in range(n)] for _ in range(n_calls)]
-    seen = {"span": 0, "mask0": 0, "mask1": 0, "bootstrap": 0}
-    for j in range(n):
-        hr = np.float32(0)
-        open_t = None
-        events = []                                        # (close frame, pick frame, reward, mask)
-        picks = []
-        for t in range(T * n_calls):
-            if b["need"][t, j] and b["goal"][t, j] >= 0:
-                assert open_t is None
-                open_t = t
-                picks.append(t)
-            hr = np.float32(hr + b["reward"][t, j])
-            if b["need_after"][t, j]:
-                if open_t is not None:
-                    events.append((t, open_t, hr, 0.0 if b["done"][t, j] else 1.0))
-                    open_t = None
-                hr = np.float32(0)
-        for c in range(n_calls):
-            closed = [e for e in events if c * T <= e[0] < (c + 1) * T]
-            rows = []
-            for k, (tc, tp, r, m) in enumerate(closed):
-                nxt = [p for p in picks if p > tp]
-                if nxt and nxt[0] < (c + 1) * T:
-                    vn = b["pick_value"][nxt[0], j]
-                else:
-                    vn = v_final[c][j]
-                    seen["bootstrap"] += m == 1.0                # V_hi(obs_T) enters this row's advantage
-                rows.append(dict(t_pick=tp, t_close=tc, goal=b["goal"][tp, j], value=b["pick_value"][tp, j], reward=r,
-                                 mask=np.float32(m), v_next=np.float32(vn)))
-                seen["span"] += tp < c * T
-                seen["mask0" if m == 0 else "mask1"] += 1
-            an = np.float32(0)
-            for row in reversed(rows):
-                m = row["mask"]
-                delta = row["reward"] + row["v_next"] * m - row["value"]
-                row["adv"] = np.float32(delta + np.float32(LAM) * an * m)
-                an = row["adv"]
-            out[c][j] = rows
-    return out, seen
 
 
 @pytest.mark.parametrize("env_id", ["PointTSP-v3", "PointTTSP-v3", "ColourMatch-v3"])
