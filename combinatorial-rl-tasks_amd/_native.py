@@ -39,7 +39,8 @@ E_ARG, E_HIP, E_STATE, E_LAYOUT, E_DONE, E_RANGE = -1, -2, -3, -4, -5, -6
  F_CHUNK_REWARD, F_CHUNK_DONE, F_CHUNK_ACTIONS, F_HIER_LOGITS, F_HIER_VALUE,
  F_LO_GOAL, F_LO_ENV_REWARD, F_HI_OBS, F_HI_ZONE_OBS, F_HI_ACTION, F_HI_ACTION_MASK, F_HI_VALUE, F_HI_LOG_PROB,
  F_HI_ADVANTAGE, F_HI_RETURN, F_HI_REWARD, F_HI_MASK, F_HI_COUNT,
- F_SKILL, F_SKILL_AGE, F_SKILL_LOGITS, F_SKILL_VALUE) = range(55)
+ F_SKILL, F_SKILL_AGE, F_SKILL_LOGITS, F_SKILL_VALUE,
+ F_LO_SKILL, F_LO_DIVERSITY, F_SKILL_BOOTSTRAP) = range(58)
 (RESULT_OBS, RESULT_REWARD, RESULT_DONE, RESULT_GOAL_MET, RESULT_EXCEPTION, RESULT_ZONE_OBS) = range(6)
 N_RESULTS = 6
 
@@ -84,6 +85,17 @@ class SkillWeights(C.Structure):
     """struct zenv_skill_weights (include/zenv.h): host float32 tensors in state_dict layout."""
     _fields_ = [("h_dim", C.c_int32), ("n_skills", C.c_int32), ("zone_feat", C.c_int32), ("precision", C.c_int32)] + [
         (n, C.c_void_p) for n in SKILL_HI_TENSORS + SKILL_HI_CRITIC + SKILL_LO_TENSORS + SKILL_LO_CRITIC]
+
+
+# struct zenv_skill_inverse_weights (include/zenv.h): InverseModel, DIAYN's discriminator (main/src/inverse_model.py)
+SKILL_INVERSE_TENSORS = ("zone_w1", "zone_b1", "zone_w2", "zone_b2", "zone_w3", "zone_b3", "comb_w1", "comb_b1",
+                         "comb_w2", "comb_b2")
+
+
+class SkillInverseWeights(C.Structure):
+    """struct zenv_skill_inverse_weights (include/zenv.h): host float32 tensors in state_dict layout."""
+    _fields_ = [("h_dim", C.c_int32), ("n_skills", C.c_int32), ("zone_feat", C.c_int32), ("precision", C.c_int32)] + [
+        (n, C.c_void_p) for n in SKILL_INVERSE_TENSORS]
 
 
 class ZenvError(RuntimeError):
@@ -165,6 +177,9 @@ _PROTOTYPES = {
     "zenv_skill_configure": (C.c_int, [_H, C.c_int]),
     "zenv_set_skills": (C.c_int, [_H, C.c_void_p]),
     "zenv_skill_forward": (C.c_int, [_H]),
+    "zenv_skill_inverse_load": (C.c_int, [_H, C.c_void_p]),
+    "zenv_collect_skill": (C.c_int, [_H, C.c_int, C.c_uint64, C.c_uint64, C.c_float, C.c_float, C.c_float, C.c_void_p,
+                                     C.c_int]),
     "zenv_get": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int]),
     "zenv_get_rows": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "zenv_device_ptr": (C.c_int, [_H, C.c_int, C.POINTER(C.c_void_p)]),

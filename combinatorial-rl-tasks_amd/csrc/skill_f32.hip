@@ -29,23 +29,41 @@ using namespace hf32;
 constexpr int SR = kMaxSkills + 1;    // per env: S logit rows, then the critic (row kMaxSkills)
 
 // one uniform in (0, 1) of the skill draw: Philox4x32-10 keyed by (seed, global env, step), a stream of its own (the
-// action draw of mlp_head_out.hpp uses the tag 0x4D4C50, the Zone-goals goal draw 0x48474C)
+// action draw of mlp_head_out.hpp uses the tag 0x4D4C50, the Zone-goals goal draw 0x48474C).  zenv_collect_skill's
+// randint(0, S) draws on the tag 0x534B55 and its bootstrap skill s' on 0x534B42.
 __device__ __forceinline__ float skill_uniform(const SkillPick &pick, int env)
 {
     const uint64_t g = pick.env_index0 + (uint64_t)env;
-    uint32_t c[4] = { (uint32_t)g, (uint32_t)(g >> 32), pick.step_index, 0x534B4Cu };
+    const uint32_t tag = pick.mode == 2 ? 0x534B55u : pick.mode == 3 ? 0x534B42u : 0x534B4Cu;
+    uint32_t c[4] = { (uint32_t)g, (uint32_t)(g >> 32), pick.step_index, tag };
     philox4x32_10(c, (uint32_t)pick.seed, (uint32_t)(pick.seed >> 32));
     return ((float)(c[0] >> 8) + 0.5f) * 5.9604644775390625e-08f;
 }
 
 __device__ __forceinline__ void skill_idle(int env, float *__restrict__ mu, float *__restrict__ stdv,
-                                           float *__restrict__ value, const MlpAction &act)
+                                           float *__restrict__ value, const MlpAction &act, const SkillRecord &sr)
 {
     const float2 z = make_float2(0.f, 0.f);
     reinterpret_cast<float2 *>(mu)[env] = z;
     reinterpret_cast<float2 *>(stdv)[env] = z;
     value[env] = 0.f;
-    if (act.mode >= 0) reinterpret_cast<float2 *>(act.actions)[env] = z;
+    if (act.mode < 0) return;
+    reinterpret_cast<float2 *>(act.actions)[env] = z;
+    // zenv_collect_skill: frame t of an env without a skill -- skill -1, action 0, log_prob 0, value 0; mask and the
+    // reward of frame t-1 as head_outputs records them
+    if (sr.lo_skill) sr.lo_skill[(size_t)sr.t * sr.N + env] = -1;
+    const MlpRecord &rc = act.rec;
+    if (!rc.action) return;
+    const size_t slot = (size_t)rc.t * rc.N + env;
+    reinterpret_cast<float2 *>(rc.action)[slot] = z;
+    reinterpret_cast<float2 *>(rc.log_prob)[slot] = z;
+    rc.value[slot] = 0.f;
+    if (rc.t == 0) {
+        rc.mask[slot] = rc.cur_mask[env];
+    } else {
+        rc.mask[slot] = rc.prev_done[env] ? 0.f : 1.f;
+        rc.reward[slot - rc.N] = rc.prev_shaped ? (float)rc.prev_shaped[env] : rc.prev_reward[env];
+    }
 }
 
 // sum_k w[k] x[k] + w[HP] over the h features (a row of the [.][HP + 1] layout)
@@ -86,7 +104,8 @@ __global__ __launch_bounds__(HP) void k_skill_f32(SkillF32 w, DevParams p, Skill
             const int env = env0 + j;
             if (LEVEL == 0) {
                 const int sk = st.skill[env];
-                a = pick.mode < 0 || ((sk < 0 || st.age[env] >= pick.skill_len) && !p.sched[env].done_state);
+                a = pick.mode < 0 || pick.mode == 3 || pick.every ||
+                    ((sk < 0 || st.age[env] >= pick.skill_len) && !p.sched[env].done_state);
             } else {
                 s = st.skill[env];
                 a = s >= 0;
@@ -97,12 +116,24 @@ __global__ __launch_bounds__(HP) void k_skill_f32(SkillF32 w, DevParams p, Skill
     }
     __syncthreads();
     if (!(on[0] | on[1] | on[2] | on[3])) {
-        if (LEVEL == 1 && j < n_env) skill_idle(env0 + j, out0, out1, out2, act);
+        if (LEVEL == 1 && j < n_env) skill_idle(env0 + j, out0, out1, out2, act, pick.rec);
         return;
     }
     if (j < EB * XP) {
         const int e = j / XP, k = j % XP;
         xin[j] = e < n_env && k < 8 ? p.obs[(size_t)(env0 + e) * 8 + k] : 0.f;
+    }
+    if (LEVEL == 0 && pick.rec.hi_obs) {
+        // zenv_collect_skill: the obs and zone_obs every picking env picks on, into its row env * W + k
+        const SkillRecord &sr = pick.rec;
+        const int ZFn = p.Z * p.F;
+        for (int i = j; i < EB * (8 + ZFn); i += HP) {
+            const int e = i / (8 + ZFn), k = i - e * (8 + ZFn);
+            if (e >= n_env || !on[e]) continue;
+            const size_t env = (size_t)(env0 + e), row = env * sr.W + sr.k;
+            if (k < 8) sr.hi_obs[row * 8 + k] = p.obs[env * 8 + k];
+            else sr.hi_zone_obs[row * ZFn + (k - 8)] = p.zone_obs[env * ZFn + (k - 8)];
+        }
     }
     __syncthreads();
     if (LEVEL == 0)
@@ -156,7 +187,7 @@ __global__ __launch_bounds__(HP) void k_skill_f32(SkillF32 w, DevParams p, Skill
             for (int s = 0; s < S; ++s) out0[(size_t)env * S + s] = (L[s] - m) - lse;
             if (pick.mode >= 0) {
                 int g = best;
-                if (pick.mode == 1) {
+                if (pick.mode == 1 || pick.mode == 3) {
                     // inverse CDF of softmax(x) on one uniform, in skill order
                     const float thr = skill_uniform(pick, env) * sum;
                     float c = 0.f;
@@ -165,9 +196,22 @@ __global__ __launch_bounds__(HP) void k_skill_f32(SkillF32 w, DevParams p, Skill
                         g = s;                            // the last skill takes what rounding leaves over
                         if (c > thr) break;
                     }
+                } else if (pick.mode == 2) {              // randint(0, S); the top uniform is exactly 1.0
+                    g = min((int)(skill_uniform(pick, env) * (float)S), S - 1);
                 }
-                st.skill[env] = g;
-                st.age[env] = 0;
+                if (pick.mode == 3) {
+                    pick.boot[env] = g;
+                } else {
+                    st.skill[env] = g;
+                    st.age[env] = 0;
+                }
+                const SkillRecord &sr = pick.rec;
+                if (sr.hi_skill) {                        // zenv_collect_skill: the pick's row
+                    const size_t row = (size_t)env * sr.W + sr.k;
+                    sr.hi_skill[row] = g;
+                    sr.hi_value[row] = L[kMaxSkills];
+                    sr.hi_log_prob[row] = (L[g] - m) - lse;
+                }
             }
         }
         return;
@@ -189,8 +233,9 @@ __global__ __launch_bounds__(HP) void k_skill_f32(SkillF32 w, DevParams p, Skill
             out2[env] = o[4];
             head_outputs(env, o[0], o[1], o[2], o[3], o[4], out0, out1, act);
             if (act.mode >= 0 && !p.sched[env].done_state) st.age[env] += 1;
+            if (act.mode >= 0 && pick.rec.lo_skill) pick.rec.lo_skill[(size_t)pick.rec.t * pick.rec.N + env] = sel[j];
         } else {
-            skill_idle(env, out0, out1, out2, act);
+            skill_idle(env, out0, out1, out2, act, pick.rec);
         }
     }
 }
@@ -220,40 +265,49 @@ __global__ __launch_bounds__(256) void k_skill_set(DevParams p, SkillState st)
 
 }  // namespace
 
-size_t pack_skill_f32(const zenv_skill_weights &w, int F, std::vector<float> &out, size_t offs[kSkillPtrs])
-{
-    const int h = w.h_dim, S = w.n_skills;
-    out.assign(4, 0.f);                                      // no tensor at offset 0: 0 = absent
-    auto put = [&](size_t n) {                               // n zero floats, 16-byte aligned start
+namespace {
+
+// the float32 image of zenv_skill_load / zenv_skill_inverse_load: every tensor at a 16-byte aligned offset in floats,
+// none at offset 0 (0 = absent)
+struct Packer {
+    std::vector<float> &out;
+    int h;
+    explicit Packer(std::vector<float> &o, int h_) : out(o), h(h_) { out.assign(4, 0.f); }
+    size_t put(size_t n)                                     // n zero floats, 16-byte aligned start
+    {
         const size_t at = (out.size() + 3) & ~(size_t)3;
         out.resize(at + n, 0.f);
         return at;
-    };
+    }
     // columns col0 .. col0 + n_cols - 1 of W [h][in_stride], transposed -> [rows][HP] (rows >= n_cols, zero-padded)
-    auto cols = [&](const float *W, int in_stride, int col0, int n_cols, int rows) {
+    size_t cols(const float *W, int in_stride, int col0, int n_cols, int rows)
+    {
         const size_t at = put((size_t)rows * HP);
         for (int o = 0; o < h; ++o)
             for (int k = 0; k < n_cols; ++k) out[at + (size_t)k * HP + o] = W[(size_t)o * in_stride + col0 + k];
         return at;
-    };
-    auto bias = [&](const float *b) {
+    }
+    size_t bias(const float *b)
+    {
         const size_t at = put(HP);
         for (int o = 0; o < h; ++o) out[at + o] = b[o];
         return at;
-    };
+    }
     // n output rows of W [n][h] + b [n] -> [n][HP + 1], bias last
-    auto rows = [&](const float *W, const float *b, int n) {
+    size_t rows(const float *W, const float *b, int n)
+    {
         const size_t at = put((size_t)n * (HP + 1));
         for (int r = 0; r < n; ++r) {
             for (int k = 0; k < h; ++k) out[at + (size_t)r * (HP + 1) + k] = W[(size_t)r * h + k];
             out[at + (size_t)r * (HP + 1) + HP] = b[r];
         }
         return at;
-    };
-    int i = 0;
-    // ZoneEnvModel: zone_net_.0 on [obs, (onehot,) zone row], combine_net_ on [obs, (onehot,) zone_emb]; xs = S or 0
-    auto enc = [&](const float *w1, const float *b1, const float *w2, const float *b2, const float *w3, const float *b3,
-                   const float *wc, const float *bc, int xs) {
+    }
+    // ZoneEnvModel: zone_net_.0 on [obs, (onehot,) zone row], combine_net_ on [obs, (onehot,) zone_emb]; xs = S or 0.
+    // The ten pointers of HierEnc into offs[i ...]
+    void enc(size_t *offs, int &i, const float *w1, const float *b1, const float *w2, const float *b2, const float *w3,
+             const float *b3, const float *wc, const float *bc, int F, int xs)
+    {
         offs[i++] = cols(w1, 8 + xs + F, 0, 8, 8);
         offs[i++] = cols(w1, 8 + xs + F, 8 + xs, F, ZF);
         offs[i++] = bias(b1);
@@ -264,22 +318,33 @@ size_t pack_skill_f32(const zenv_skill_weights &w, int F, std::vector<float> &ou
         offs[i++] = cols(wc, 8 + xs + h, 0, 8, 8);
         offs[i++] = cols(wc, 8 + xs + h, 8 + xs, h, HP);
         offs[i++] = bias(bc);
-    };
-    enc(w.hi_zone_w1, w.hi_zone_b1, w.hi_zone_w2, w.hi_zone_b2, w.hi_zone_w3, w.hi_zone_b3, w.hi_comb_w, w.hi_comb_b, 0);
-    enc(w.lo_zone_w1, w.lo_zone_b1, w.lo_zone_w2, w.lo_zone_b2, w.lo_zone_w3, w.lo_zone_b3, w.lo_comb_w, w.lo_comb_b, S);
-    offs[i++] = cols(w.lo_zone_w1, 8 + S + F, 8, S, S);     // the skill columns
-    offs[i++] = cols(w.lo_comb_w, 8 + S + h, 8, S, S);
-    offs[i++] = cols(w.hi_enc_w, h, 0, h, HP);
-    offs[i++] = bias(w.hi_enc_b);
-    offs[i++] = rows(w.hi_logit_w, w.hi_logit_b, S);
+    }
+};
+
+}  // namespace
+
+size_t pack_skill_f32(const zenv_skill_weights &w, int F, std::vector<float> &out, size_t offs[kSkillPtrs])
+{
+    const int h = w.h_dim, S = w.n_skills;
+    Packer pk(out, h);
+    int i = 0;
+    pk.enc(offs, i, w.hi_zone_w1, w.hi_zone_b1, w.hi_zone_w2, w.hi_zone_b2, w.hi_zone_w3, w.hi_zone_b3, w.hi_comb_w,
+           w.hi_comb_b, F, 0);
+    pk.enc(offs, i, w.lo_zone_w1, w.lo_zone_b1, w.lo_zone_w2, w.lo_zone_b2, w.lo_zone_w3, w.lo_zone_b3, w.lo_comb_w,
+           w.lo_comb_b, F, S);
+    offs[i++] = pk.cols(w.lo_zone_w1, 8 + S + F, 8, S, S);  // the skill columns
+    offs[i++] = pk.cols(w.lo_comb_w, 8 + S + h, 8, S, S);
+    offs[i++] = pk.cols(w.hi_enc_w, h, 0, h, HP);
+    offs[i++] = pk.bias(w.hi_enc_b);
+    offs[i++] = pk.rows(w.hi_logit_w, w.hi_logit_b, S);
     const bool hc = w.hi_critic_w1 != nullptr, lc = w.lo_critic_w1 != nullptr;
-    offs[i++] = hc ? cols(w.hi_critic_w1, h, 0, h, HP) : 0;
-    offs[i++] = hc ? bias(w.hi_critic_b1) : 0;
-    offs[i++] = hc ? rows(w.hi_critic_w2, w.hi_critic_b2, 1) : 0;
-    offs[i++] = cols(w.lo_enc_w, h + S, 0, h, HP);
-    offs[i++] = cols(w.lo_enc_w, h + S, h, S, S);
-    offs[i++] = bias(w.lo_enc_b);
-    offs[i] = put(4 * (size_t)(HP + 1));                    // mu_ rows 0-1, std_ rows 2-3
+    offs[i++] = hc ? pk.cols(w.hi_critic_w1, h, 0, h, HP) : 0;
+    offs[i++] = hc ? pk.bias(w.hi_critic_b1) : 0;
+    offs[i++] = hc ? pk.rows(w.hi_critic_w2, w.hi_critic_b2, 1) : 0;
+    offs[i++] = pk.cols(w.lo_enc_w, h + S, 0, h, HP);
+    offs[i++] = pk.cols(w.lo_enc_w, h + S, h, S, S);
+    offs[i++] = pk.bias(w.lo_enc_b);
+    offs[i] = pk.put(4 * (size_t)(HP + 1));                 // mu_ rows 0-1, std_ rows 2-3
     for (int r = 0; r < 4; ++r) {
         const float *W = r < 2 ? w.lo_mu_w + (size_t)r * h : w.lo_std_w + (size_t)(r - 2) * h;
         const float *b = r < 2 ? w.lo_mu_b + r : w.lo_std_b + (r - 2);
@@ -287,11 +352,34 @@ size_t pack_skill_f32(const zenv_skill_weights &w, int F, std::vector<float> &ou
         out[offs[i] + (size_t)r * (HP + 1) + HP] = b[0];
     }
     ++i;
-    offs[i++] = lc ? cols(w.lo_critic_w1, h + S, 0, h, HP) : 0;
-    offs[i++] = lc ? cols(w.lo_critic_w1, h + S, h, S, S) : 0;
-    offs[i++] = lc ? bias(w.lo_critic_b1) : 0;
-    offs[i++] = lc ? rows(w.lo_critic_w2, w.lo_critic_b2, 1) : 0;
+    offs[i++] = lc ? pk.cols(w.lo_critic_w1, h + S, 0, h, HP) : 0;
+    offs[i++] = lc ? pk.cols(w.lo_critic_w1, h + S, h, S, S) : 0;
+    offs[i++] = lc ? pk.bias(w.lo_critic_b1) : 0;
+    offs[i++] = lc ? pk.rows(w.lo_critic_w2, w.lo_critic_b2, 1) : 0;
     return out.size();
+}
+
+size_t pack_skill_inverse_f32(const zenv_skill_inverse_weights &w, int F, std::vector<float> &out,
+                              size_t offs[kSkillInvPtrs])
+{
+    Packer pk(out, w.h_dim);
+    int i = 0;
+    pk.enc(offs, i, w.zone_w1, w.zone_b1, w.zone_w2, w.zone_b2, w.zone_w3, w.zone_b3, w.comb_w1, w.comb_b1, F, 0);
+    offs[i++] = pk.rows(w.comb_w2, w.comb_b2, w.n_skills);
+    return out.size();
+}
+
+SkillInvF32 skill_inverse_f32_at(const zenv_skill_inverse_weights &w, const float *base,
+                                 const size_t offs[kSkillInvPtrs])
+{
+    SkillInvF32 s{};
+    s.h = w.h_dim;
+    s.S = w.n_skills;
+    const size_t *o = offs;
+    s.enc = HierEnc{ base + o[0], base + o[1], base + o[2], base + o[3], base + o[4], base + o[5], base + o[6],
+                     base + o[7], base + o[8], base + o[9] };
+    s.head = base + o[10];
+    return s;
 }
 
 SkillF32 skill_f32_at(const zenv_skill_weights &w, const float *base, const size_t offs[kSkillPtrs])
@@ -317,9 +405,10 @@ hipError_t launch_skill_high(const SkillF32 &w, const DevParams &p, const SkillS
 }
 
 hipError_t launch_skill_low(const SkillF32 &w, const DevParams &p, const SkillState &st, float *mu, float *stdv,
-                            float *value, const MlpAction &act, hipStream_t s)
+                            float *value, const MlpAction &act, hipStream_t s, const SkillRecord *rec)
 {
-    const SkillPick none{ -1, 0, 0u, 0ull, 0ull };
+    SkillPick none{ -1, 0, 0u, 0ull, 0ull, 0, nullptr, SkillRecord{} };
+    if (rec) none.rec = *rec;
     hipLaunchKernelGGL(k_skill_f32<1>, dim3((p.N + EB - 1) / EB), dim3(HP), 0, s, w, p, st, mu, stdv, value, none, act);
     return hipGetLastError();
 }

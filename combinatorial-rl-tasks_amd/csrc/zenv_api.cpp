@@ -117,6 +117,17 @@ struct zenv {
     SkillState sst{};
     void *sst_mem = nullptr;
     float *skill_logits = nullptr, *skill_value = nullptr;
+    // DIAYN's discriminator (zenv_skill_inverse_load) and the per-frame records of zenv_collect_skill (T frames):
+    // lo_skill, diversity, env_reward [T][N]; the bootstrap skill and the row count [N]
+    void *skinv_mem = nullptr;
+    SkillInvF32 skinv{};
+    bool skinv_ready = false;
+    struct {
+        int T = 0;
+        int32_t *lo_skill = nullptr, *boot = nullptr, *count = nullptr;
+        float *diversity = nullptr, *env_reward = nullptr;
+    } sk;
+    void *sk_mem = nullptr;
     // goal-conditioned variant (zenv_goal_enable)
     bool goal_enabled = false;
     bool order_enabled = false;   // solver-ordered variant (zenv_order_enable)
@@ -320,22 +331,29 @@ FieldInfo field_info(const zenv *h, int field)
     case ZENV_F_HIER_LOGITS: return { h->hier_logits, h->hier_logits ? N * p.Z * 4 : 0 };
     case ZENV_F_HIER_VALUE: return { h->hier_value, h->hier_value ? N * 4 : 0 };
     case ZENV_F_LO_GOAL: return { h->hframes.lo_goal, h->hframes.lo_goal ? N * h->hframes.T * 2 * 4 : 0 };
-    case ZENV_F_LO_ENV_REWARD: return { h->hframes.env_reward, h->hframes.env_reward ? N * h->hframes.T * 4 : 0 };
+    case ZENV_F_LO_ENV_REWARD:       // zenv_collect_hier's or zenv_collect_skill's (a handle runs one of them)
+        if (h->sk_mem) return { h->sk.env_reward, N * h->sk.T * 4 };
+        return { h->hframes.env_reward, h->hframes.env_reward ? N * h->hframes.T * 4 : 0 };
     case ZENV_F_HI_OBS: return { h->hout.obs, h->hi_m * 8 * 4 };
     case ZENV_F_HI_ZONE_OBS: return { h->hout.zone_obs, h->hi_m * p.Z * p.F * 4 };
     case ZENV_F_HI_ACTION: return { h->hout.action, h->hi_m * 4 };
-    case ZENV_F_HI_ACTION_MASK: return { h->hout.action_mask, h->hi_m * p.Z };
+    case ZENV_F_HI_ACTION_MASK: return { h->hout.action_mask, h->sk_mem ? 0 : h->hi_m * p.Z };   // skills: not written
     case ZENV_F_HI_VALUE: return { h->hout.value, h->hi_m * 4 };
     case ZENV_F_HI_LOG_PROB: return { h->hout.log_prob, h->hi_m * 4 };
     case ZENV_F_HI_ADVANTAGE: return { h->hout.advantage, h->hi_m * 4 };
     case ZENV_F_HI_RETURN: return { h->hout.returnn, h->hi_m * 4 };
     case ZENV_F_HI_REWARD: return { h->hout.reward, h->hi_m * 4 };
     case ZENV_F_HI_MASK: return { h->hout.mask, h->hi_m * 4 };
-    case ZENV_F_HI_COUNT: return { h->hframes.count, h->hframes.count ? N * 4 : 0 };
+    case ZENV_F_HI_COUNT:
+        if (h->sk_mem) return { h->sk.count, N * 4 };
+        return { h->hframes.count, h->hframes.count ? N * 4 : 0 };
     case ZENV_F_SKILL: return { h->sst.skill, h->sst_mem ? N * 4 : 0 };          // (refresh_field() first)
     case ZENV_F_SKILL_AGE: return { h->sst.age, h->sst_mem ? N * 4 : 0 };
     case ZENV_F_SKILL_LOGITS: return { h->skill_logits, h->skill_logits ? N * h->skill_n * 4 : 0 };
     case ZENV_F_SKILL_VALUE: return { h->skill_value, h->skill_value ? N * 4 : 0 };
+    case ZENV_F_LO_SKILL: return { h->sk.lo_skill, h->sk_mem ? N * h->sk.T * 4 : 0 };
+    case ZENV_F_LO_DIVERSITY: return { h->sk.diversity, h->sk_mem ? N * h->sk.T * 4 : 0 };
+    case ZENV_F_SKILL_BOOTSTRAP: return { h->sk.boot, h->sk_mem ? N * 4 : 0 };
     default: return { nullptr, 0 };
     }
 }
@@ -637,7 +655,7 @@ extern "C" int zenv_destroy(zenv_t *h)
                      (void *)h->goal_in, (void *)h->goal_bad, h->exp_mem, (void *)h->p.order_pos,
                      (void *)h->p.order_val, h->hier_mem, (void *)h->hier_logits, (void *)h->hier_value,
                      h->hframes_mem, h->hcarry_mem, h->hout_mem, h->skill_mem, h->sst_mem, (void *)h->skill_logits,
-                     (void *)h->skill_value })
+                     (void *)h->skill_value, h->skinv_mem, h->sk_mem })
         if (m) (void)hipFree(m);
     for (hipEvent_t ev : h->events) (void)hipEventDestroy(ev);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
@@ -1437,6 +1455,35 @@ extern "C" int zenv_skill_load(zenv_t *h, const zenv_skill_weights *w)
     h->skill = skill_f32_at(*w, static_cast<const float *>(h->skill_mem), o);
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->skill_ready = true;
+    if (h->skinv_ready && (h->skinv.h != w->h_dim || h->skinv.S != w->n_skills)) h->skinv_ready = false;
+    return ZENV_OK;
+}
+
+extern "C" int zenv_skill_inverse_load(zenv_t *h, const zenv_skill_inverse_weights *w)
+{
+    if (!h || !w) return fail(ZENV_E_ARG, "null argument");
+    if (!h->skill_ready) return fail(ZENV_E_STATE, "zenv_skill_load first (the inverse model takes its shapes)");
+    if (w->h_dim != h->skill.h || w->n_skills != h->skill.S || w->zone_feat != h->p.F)
+        return fail(ZENV_E_ARG, "inverse model h_dim %d, n_skills %d, zone_feat %d: the skill weights have %d, %d, %d",
+                    w->h_dim, w->n_skills, w->zone_feat, h->skill.h, h->skill.S, h->p.F);
+    if (w->precision != ZENV_MLP_F32)
+        return fail(ZENV_E_ARG, "zenv_skill_inverse_weights.precision %d: only ZENV_MLP_F32 is built", w->precision);
+    for (const float *t : { w->zone_w1, w->zone_b1, w->zone_w2, w->zone_b2, w->zone_w3, w->zone_b3, w->comb_w1,
+                            w->comb_b1, w->comb_w2, w->comb_b2 })
+        if (!t) return fail(ZENV_E_ARG, "zenv_skill_inverse_weights has a null tensor");
+    std::vector<float> img;
+    size_t o[kSkillInvPtrs];
+    pack_skill_inverse_f32(*w, h->p.F, img, o);
+    int rc = use_device(h);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->skinv_ready = false;
+    if (h->skinv_mem) HIP_TRY(hipFree(h->skinv_mem));
+    h->skinv_mem = nullptr;
+    HIP_TRY(hipMalloc(&h->skinv_mem, img.size() * sizeof(float)));
+    HIP_TRY(hipMemcpy(h->skinv_mem, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
+    h->skinv = skill_inverse_f32_at(*w, static_cast<const float *>(h->skinv_mem), o);
+    h->skinv_ready = true;
     return ZENV_OK;
 }
 
@@ -1472,7 +1519,7 @@ extern "C" int zenv_skill_forward(zenv_t *h)
     int rc = use_device(h);
     if (rc) return rc;
     HIP_TRY(launch_skill_sync(h->p, h->sst, nullptr, 0, h->stream));
-    const SkillPick none{ -1, h->skill_len, 0u, 0ull, 0ull };
+    const SkillPick none{ -1, h->skill_len, 0u, 0ull, 0ull, 0, nullptr, SkillRecord{} };
     HIP_TRY(launch_skill_high(h->skill, h->p, h->sst, h->skill_logits, h->skill_value, none, h->stream));
     HIP_TRY(launch_skill_low(h->skill, h->p, h->sst, h->mlp_mu, h->mlp_std, h->mlp_value, no_mlp_action(), h->stream));
     return ZENV_OK;
@@ -1485,7 +1532,7 @@ static int run_skill_policy(zenv_t *h, int policy, uint32_t step_index, uint64_t
     if (!h->skill_ready) return fail(ZENV_E_STATE, "zenv_skill_load first");
     const int mode = policy == ZENV_POLICY_SKILL_SAMPLE ? 1 : 0;
     HIP_TRY(launch_skill_sync(h->p, h->sst, nullptr, 0, h->stream));
-    const SkillPick pick{ mode, h->skill_len, step_index, seed, env_index0 };
+    const SkillPick pick{ mode, h->skill_len, step_index, seed, env_index0, 0, nullptr, SkillRecord{} };
     HIP_TRY(launch_skill_high(h->skill, h->p, h->sst, h->skill_logits, h->skill_value, pick, h->stream));
     const MlpAction act{ mode, step_index, seed, env_index0, out, MlpRecord{} };
     HIP_TRY(launch_skill_low(h->skill, h->p, h->sst, h->mlp_mu, h->mlp_std, h->mlp_value, act, h->stream));
@@ -1762,6 +1809,140 @@ extern "C" int zenv_collect_hier(zenv_t *h, int T, uint64_t policy_seed, uint64_
     return ZENV_OK;
 }
 
+
+// ---- zenv_collect_skill: collect_experiences of the fixed-length-skills agent and DIAYN (main/src/torch_ac/algos/
+// _hier_policy_opt.py:9-233).  The per-frame records for T frames (the ZENV_F_EXP_* buffers aside)
+static int ensure_skill_collect(zenv_t *h, int T)
+{
+    if (h->sk_mem && h->sk.T == T) return ZENV_OK;
+    const size_t N = (size_t)h->n_env, TN = (size_t)T * N;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->sk_mem) HIP_TRY(hipFree(h->sk_mem));
+    h->sk_mem = nullptr;
+    const size_t bytes = TN * 3 * 4 + N * 2 * 4 + 5 * 256;
+    HIP_TRY(hipMalloc(&h->sk_mem, bytes));
+    char *b = static_cast<char *>(h->sk_mem);
+    auto take = [&](size_t n) { char *at = b; b += (n + 255) & ~(size_t)255; return at; };
+    h->sk.lo_skill = reinterpret_cast<int32_t *>(take(TN * 4));
+    h->sk.diversity = reinterpret_cast<float *>(take(TN * 4));
+    h->sk.env_reward = reinterpret_cast<float *>(take(TN * 4));
+    h->sk.boot = reinterpret_cast<int32_t *>(take(N * 4));
+    h->sk.count = reinterpret_cast<int32_t *>(take(N * 4));
+    if (b > static_cast<char *>(h->sk_mem) + bytes) return fail(ZENV_E_HIP, "skill record layout overflow");
+    HIP_TRY(hipMemsetAsync(h->sk_mem, 0, bytes, h->stream));
+    h->sk.T = T;
+    return ZENV_OK;
+}
+
+extern "C" int zenv_collect_skill(zenv_t *h, int T, uint64_t policy_seed, uint64_t env_index0, float discount,
+                                  float gae_lambda, float diversity_coef, const float *skill_prior_logits, int sample_hi)
+{
+    if (!h) return fail(ZENV_E_ARG, "null handle");
+    if (h->order_enabled || h->goal_enabled)
+        return fail(ZENV_E_STATE, "zenv_collect_skill steps a plain task handle, not a goal-conditioned / solver-ordered one");
+    if (!h->skill_ready) return fail(ZENV_E_STATE, "zenv_skill_load first");
+    if (!h->skill.hi_critic || !h->skill.lo_critic)
+        return fail(ZENV_E_STATE, "zenv_collect_skill needs both critics (zenv_skill_load with hi_critic_* and lo_critic_*)");
+    if (h->host_io_slab) return fail(ZENV_E_STATE, "zenv_collect_skill records on the device: switch zenv_host_io off first");
+    if (!h->was_reset) return fail(ZENV_E_STATE, "Environment must be reset before stepping");
+    const int L = h->skill_len, S = h->skill.S;
+    if (T < 1 || T % L != 0)
+        return fail(ZENV_E_ARG, "frames_per_proc %d must be a positive multiple of skill_len %d", T, L);
+    if ((int64_t)T * h->n_env > INT32_MAX) return fail(ZENV_E_ARG, "frames_per_proc x envs must stay below 2^31");
+    if (!std::isfinite(discount) || !std::isfinite(gae_lambda) || !std::isfinite(diversity_coef))
+        return fail(ZENV_E_ARG, "discount, gae_lambda and diversity_coef must be finite");
+    if (discount < 0.f || discount > 1.f || gae_lambda < 0.f || gae_lambda > 1.f)
+        return fail(ZENV_E_ARG, "discount %g and gae_lambda %g must lie in [0, 1]", discount, gae_lambda);
+    if (diversity_coef != 0.f && !h->skinv_ready)
+        return fail(ZENV_E_ARG, "diversity_coef %g without an inverse model (zenv_skill_inverse_load)", diversity_coef);
+    SkillDiv div{};
+    div.N = h->n_env;
+    div.net = h->skinv_ready ? 1 : 0;
+    div.coef = diversity_coef;
+    if (h->skinv_ready) {
+        if (!skill_prior_logits) return fail(ZENV_E_ARG, "skill_prior_logits is null (an inverse model is loaded)");
+        double m = -INFINITY;
+        for (int s = 0; s < S; ++s) {
+            if (!std::isfinite(skill_prior_logits[s])) return fail(ZENV_E_ARG, "skill_prior_logits[%d] is not finite", s);
+            m = std::max(m, (double)skill_prior_logits[s]);
+        }
+        double sum = 0.0;                                        // log_softmax(self.skill_logits, dim=0), once per call
+        for (int s = 0; s < S; ++s) sum += std::exp((double)skill_prior_logits[s] - m);
+        for (int s = 0; s < S; ++s) div.prior[s] = (float)((double)skill_prior_logits[s] - m - std::log(sum));
+    }
+    int rc = use_device(h);
+    if (rc) return rc;
+    const size_t N = (size_t)h->n_env, ZF = (size_t)h->p.Z * h->p.F;
+    const int W = T / L;
+    h->act_tag.valid = false;
+    rc = ensure_exp(h, T);
+    if (rc) return rc;
+    rc = ensure_skill_collect(h, T);
+    if (rc) return rc;
+    h->hi_m = 0;
+    rc = ensure_hier_out(h, (int64_t)N * W);
+    if (rc) return rc;
+    h->hi_m = (int64_t)N * W;
+    const HierOut &o = h->hout;
+    div.skill = h->sk.lo_skill;
+    div.diversity = h->sk.diversity;
+    div.exp_reward = h->exp.reward;
+    // the observations are recorded where they are produced, as in zenv_collect
+    struct ObsRedirect {
+        zenv_t *h;
+        float *obs, *zone_obs;
+        ~ObsRedirect() { h->p.obs = obs; h->p.zone_obs = zone_obs; }
+    } home{ h, h->p.obs, h->p.zone_obs };
+    HIP_TRY(hipMemcpyAsync(h->exp.obs, home.obs, N * 8 * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->exp.zone_obs, home.zone_obs, N * ZF * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    for (int t = 0; t < T; ++t) {
+        h->p.obs = h->exp.obs + (size_t)t * N * 8;
+        h->p.zone_obs = h->exp.zone_obs + (size_t)t * N * ZF;
+        const uint32_t step_index = (uint32_t)h->step_count;
+        SkillRecord sr{ t, h->n_env, W, t / L, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+        if (t % L == 0) {
+            // :28-45 every env picks (hi_dist.sample() or randint), the pick recorded in row env * W + t / L
+            HIP_TRY(launch_skill_sync(h->p, h->sst, nullptr, 0, h->stream));
+            SkillPick pick{ sample_hi ? 1 : 2, L, step_index, policy_seed, env_index0, 1, nullptr, sr };
+            pick.rec.hi_obs = o.obs;
+            pick.rec.hi_zone_obs = o.zone_obs;
+            pick.rec.hi_skill = o.action;
+            pick.rec.hi_value = o.value;
+            pick.rec.hi_log_prob = o.log_prob;
+            HIP_TRY(launch_skill_high(h->skill, h->p, h->sst, h->skill_logits, h->skill_value, pick, h->stream));
+        }
+        // :60-64 the low level's action; frame t recorded (and the env reward / mask of frame t-1)
+        const MlpRecord rec{ h->exp.action, h->exp.log_prob, h->exp.value, h->exp.mask, h->sk.env_reward,
+                             h->exp.cur_mask, h->p.reward, nullptr, h->p.done_out, T, t, h->n_env };
+        const MlpAction act{ 1, step_index, policy_seed, env_index0, h->p.actions, rec };
+        sr.lo_skill = h->sk.lo_skill;
+        HIP_TRY(launch_skill_low(h->skill, h->p, h->sst, h->mlp_mu, h->mlp_std, h->mlp_value, act, h->stream, &sr));
+        h->p.obs = t + 1 < T ? h->exp.obs + (size_t)(t + 1) * N * 8 : home.obs;
+        h->p.zone_obs = t + 1 < T ? h->exp.zone_obs + (size_t)(t + 1) * N * ZF : home.zone_obs;
+        // :68-71 step_no_reset inside a window, step on its last frame
+        HIP_TRY(launch_step(h->p, h->p.actions, (t + 1) % L == 0 ? 1 : 0, no_policy(), h->stream));
+        // :74-91 the diversity reward on obs_{t+1} and the low level's reward
+        div.t = t;
+        HIP_TRY(launch_skill_inverse(h->skinv, h->p, div, h->stream));
+        h->step_count += 1;
+    }
+    {   // the env reward of frame T-1 and self.lo_mask = 1 - done
+        ExpBuffers last = h->exp;
+        last.reward = h->sk.env_reward;
+        HIP_TRY(launch_exp_reward(last, h->n_env, T - 1, h->p.reward, nullptr, h->p.done_out, h->stream));
+    }
+    // :131-139 next_hi_value = V_hi(obs_T); s' ~ hi_dist(obs_T) on a stream of its own; next_lo_value = V_lo(obs_T, s')
+    const SkillPick boot{ 3, L, (uint32_t)h->step_count, policy_seed, env_index0, 1, h->sk.boot, SkillRecord{} };
+    HIP_TRY(launch_skill_high(h->skill, h->p, h->sst, h->skill_logits, h->skill_value, boot, h->stream));
+    SkillState sb = h->sst;
+    sb.skill = h->sk.boot;
+    HIP_TRY(launch_skill_low(h->skill, h->p, sb, h->mlp_mu, h->mlp_std, h->mlp_value, no_mlp_action(), h->stream));
+    // :154-161 the low level over all T frames; :142-151 the high level per env over its windows
+    HIP_TRY(launch_exp_gae(h->exp, h->n_env, h->mlp_value, discount, gae_lambda, h->stream));
+    HIP_TRY(launch_skill_hi_gae(o, T, L, h->n_env, h->sk.env_reward, h->exp.mask, h->exp.cur_mask, h->skill_value,
+                                gae_lambda, h->sk.count, h->stream));
+    return ZENV_OK;
+}
 
 extern "C" int zenv_policy(zenv_t *h, int policy, uint64_t policy_seed, uint64_t env_index0, float *dst_device)
 {

@@ -110,6 +110,38 @@ class TorchZoneEnv:
         hi["count"] = self._alias_typed(nat.F_HI_COUNT, (env.num_envs,), np.int32)
         return lo, hi
 
+    def load_skills(self, hi_state_dict, lo_state_dict, skill_len=200):
+        """Put the skill planner's HighPolicyValueModel / LoPolicyValueModel state_dicts (main/src/
+        hier_policy_value_models.py; torch tensors on any device) into the device agent that ``collect_skills`` runs --
+        after every update."""
+        from .vec_env import skill_tensors_from_state_dicts
+        self.env.load_skills(skill_tensors_from_state_dicts(hi_state_dict, lo_state_dict), skill_len=skill_len)
+
+    def load_skill_inverse(self, state_dict, n_skills):
+        """Put an InverseModel state_dict (main/src/inverse_model.py) into the device discriminator of the diversity
+        reward -- after every update."""
+        from .vec_env import inverse_tensors_from_state_dict
+        self.env.load_skill_inverse(inverse_tensors_from_state_dict(state_dict, n_skills))
+
+    def collect_skills(self, frames_per_proc, policy_seed=1, env_index0=0, discount=0.99, gae_lambda=0.95,
+                       diversity_coef=0.0, skill_prior_logits=None, sample_hi=True):
+        """collect_experiences of the skill planner / DIAYN on the device; returns (lo, hi, inverse, num_frames) named
+        and shaped as ``ZoneVecEnv.collect_skills``: lo and hi are CUDA tensors ALIASING the handle's buffers (lo
+        [N, T, ...] views of time-major memory, hi flat [M, ...]), valid until the next collect; inverse is compacted
+        into new tensors and num_frames is a Python int (both wait for the collection)."""
+        from .vec_env import skill_experience_layout, skill_num_frames
+        env = self.env
+        T, M = env.collect_skills_on_device(frames_per_proc, policy_seed, env_index0, discount, gae_lambda,
+                                            diversity_coef, skill_prior_logits, sample_hi)
+        L = T * env.num_envs // M
+        lo_l, hi_l = skill_experience_layout(env.num_envs, env.num_zones, env.zone_feat, T, L)
+        lo = {name: self._alias_typed(field, shape, dt).transpose(0, 1) for name, (field, shape, dt) in lo_l.items()}
+        hi = {name: self._alias_typed(field, shape, dt) for name, (field, shape, dt) in hi_l.items()}
+        keep = lo["mask"][:, 1:] != 0
+        inverse = {"obs": lo["obs"][:, 1:][keep], "zone_obs": lo["zone_obs"][:, 1:][keep],
+                   "skill": lo["skill"][:, :-1][keep]}
+        return lo, hi, inverse, skill_num_frames(lo["mask"].transpose(0, 1), L)
+
     def _alias_typed(self, field, shape, dtype):
         t = self._torch.as_tensor(_DeviceView(self.env.device_ptr(field), shape, dtype), device=self.device)
         assert t.data_ptr() == self.env.device_ptr(field), "torch copied instead of aliasing"

@@ -28,7 +28,8 @@ _FIELD_DTYPES = {
     nat.F_HI_ACTION: np.int32, nat.F_HI_ACTION_MASK: np.uint8, nat.F_HI_VALUE: np.float32, nat.F_HI_LOG_PROB: np.float32,
     nat.F_HI_ADVANTAGE: np.float32, nat.F_HI_RETURN: np.float32, nat.F_HI_REWARD: np.float32, nat.F_HI_MASK: np.float32,
     nat.F_HI_COUNT: np.int32, nat.F_SKILL: np.int32, nat.F_SKILL_AGE: np.int32, nat.F_SKILL_LOGITS: np.float32,
-    nat.F_SKILL_VALUE: np.float32,
+    nat.F_SKILL_VALUE: np.float32, nat.F_LO_SKILL: np.int32, nat.F_LO_DIVERSITY: np.float32,
+    nat.F_SKILL_BOOTSTRAP: np.int32,
 }
 
 
@@ -229,6 +230,114 @@ def skill_tensors_from_state_dicts(hi_sd, lo_sd):
             raise ValueError(f"{level}_model_state[{key!r}] has shape {tuple(a.shape)}, expected {want[name]} "
                              f"(hidden size {h}, {S} skills, zone rows of {F} features)")
     return out
+
+
+# zenv_skill_inverse_weights name -> state_dict key of InverseModel (main/src/inverse_model.py), DIAYN's discriminator
+INVERSE_KEYS = {"zone_w1": "zone_net.0.weight", "zone_b1": "zone_net.0.bias", "zone_w2": "zone_net.2.weight",
+                "zone_b2": "zone_net.2.bias", "zone_w3": "zone_net.4.weight", "zone_b3": "zone_net.4.bias",
+                "comb_w1": "combine_net.0.weight", "comb_b1": "combine_net.0.bias",
+                "comb_w2": "combine_net.2.weight", "comb_b2": "combine_net.2.bias"}
+
+
+def inverse_tensor_shapes(h, S, F):
+    """The shape of every zenv_skill_inverse_weights tensor for hidden size h, S skills and zone rows of F features."""
+    return {"zone_w1": (h, 8 + F), "zone_b1": (h,), "zone_w2": (h, h), "zone_b2": (h,), "zone_w3": (h, h),
+            "zone_b3": (h,), "comb_w1": (h, 8 + h), "comb_b1": (h,), "comb_w2": (S, h), "comb_b2": (S,)}
+
+
+def inverse_tensors_from_state_dict(state, n_skills):
+    """InverseModel.state_dict() (main/src/inverse_model.py) -> the tensors ``ZoneVecEnv.load_skill_inverse`` wants
+    (numpy float32, names of ``_native.SKILL_INVERSE_TENSORS``).  A dict with other keys (an ACModel, a policy's
+    hi_model_state ...), a missing key, a tensor whose shape does not fit the others or a head of other than n_skills
+    outputs raises ValueError naming it."""
+    extra = sorted(k for k in state if k not in INVERSE_KEYS.values())
+    if extra:
+        raise ValueError(f"not an InverseModel state_dict: unexpected key {extra[0]!r}")
+    out = {}
+    for name, key in INVERSE_KEYS.items():
+        if key not in state:
+            raise ValueError(f"not an InverseModel state_dict: no {key!r}")
+        v = state[key]
+        out[name] = np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, np.float32)
+    w1 = out["zone_w1"]
+    h, F = (w1.shape[0], w1.shape[1] - 8) if w1.ndim == 2 else (-1, -1)
+    want = inverse_tensor_shapes(h, int(n_skills), F)
+    for name, a in out.items():
+        if a.shape != want[name]:
+            raise ValueError(f"InverseModel[{INVERSE_KEYS[name]!r}] has shape {tuple(a.shape)}, expected {want[name]} "
+                             f"(hidden size {h}, {int(n_skills)} skills, zone rows of {F} features)")
+    return out
+
+
+def check_collect_skill_args(frames_per_proc, skill_len, policy_seed=1, env_index0=0, discount=0.99, gae_lambda=0.95,
+                             diversity_coef=0.0, skill_prior_logits=None, n_skills=None, have_inverse=False):
+    """What ``ZoneVecEnv.collect_skills`` checks before it calls into the library: T a positive multiple of skill_len
+    (hrl_policy_planner.py:95), a discount and a lambda in [0, 1], a finite diversity_coef, non-negative 64-bit seeds;
+    with an inverse model a finite prior of n_skills logits, without one diversity_coef = 0.  Returns the normalised
+    arguments (the prior as a contiguous float32 array, or None)."""
+    if isinstance(frames_per_proc, bool) or int(frames_per_proc) != frames_per_proc:
+        raise ValueError(f"frames_per_proc must be an integer, got {frames_per_proc!r}")
+    T, L = int(frames_per_proc), int(skill_len)
+    if T < 1 or L < 1 or T % L:
+        raise ValueError(f"frames_per_proc must be a positive multiple of skill_len {L}, got {T}")
+    for name, v in (("discount", discount), ("gae_lambda", gae_lambda)):
+        if not (0.0 <= float(v) <= 1.0):
+            raise ValueError(f"{name} must lie in [0, 1], got {v!r}")
+    if not np.isfinite(float(diversity_coef)):
+        raise ValueError(f"diversity_coef must be finite, got {diversity_coef!r}")
+    for name, v in (("policy_seed", policy_seed), ("env_index0", env_index0)):
+        if int(v) != v or not (0 <= int(v) < 2 ** 64):
+            raise ValueError(f"{name} must be an integer in [0, 2^64), got {v!r}")
+    prior = None
+    if have_inverse:
+        if skill_prior_logits is None:
+            raise ValueError("skill_prior_logits is needed with an inverse model (the diversity reward's prior)")
+        v = skill_prior_logits
+        prior = np.ascontiguousarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, np.float32).reshape(-1)
+        if n_skills is not None and prior.shape != (int(n_skills),):
+            raise ValueError(f"skill_prior_logits must hold {int(n_skills)} logits, got shape {prior.shape}")
+        if not np.all(np.isfinite(prior)):
+            raise ValueError("skill_prior_logits must be finite")
+    elif float(diversity_coef) != 0.0:
+        raise ValueError("diversity_coef != 0 needs an inverse model (load_skill_inverse)")
+    return T, int(policy_seed), int(env_index0), float(discount), float(gae_lambda), float(diversity_coef), prior
+
+
+def skill_experience_layout(num_envs, num_zones, zone_feat, frames_per_proc, skill_len):
+    """The buffers one ``collect_skills`` of T frames fills, as (lo, hi): name -> (field id, shape in memory, dtype).
+    lo: time-major [T, N, ...] device buffers, handed out as [N, T, ...] views (lo_exps of _hier_policy_opt.py:172-190:
+    obs, zone_obs, skill, action, log_prob, value, advantage, returnn; plus reward = lo_reward, env_reward, diversity
+    and mask).  hi: env-major [M, ...], M = N T / skill_len (hi_exps, :201-212, action = the skill; plus the window's
+    reward and next_mask)."""
+    N, Z, F, T, L = int(num_envs), int(num_zones), int(zone_feat), int(frames_per_proc), int(skill_len)
+    M = N * (T // L)
+    f32 = np.float32
+    lo = {"obs": (nat.F_EXP_OBS, (T, N, 8), f32), "zone_obs": (nat.F_EXP_ZONE_OBS, (T, N, Z, F), f32),
+          "skill": (nat.F_LO_SKILL, (T, N), np.int32), "action": (nat.F_EXP_ACTION, (T, N, 2), f32),
+          "log_prob": (nat.F_EXP_LOG_PROB, (T, N, 2), f32), "value": (nat.F_EXP_VALUE, (T, N), f32),
+          "advantage": (nat.F_EXP_ADVANTAGE, (T, N), f32), "returnn": (nat.F_EXP_RETURN, (T, N), f32),
+          "reward": (nat.F_EXP_REWARD, (T, N), f32), "env_reward": (nat.F_LO_ENV_REWARD, (T, N), f32),
+          "diversity": (nat.F_LO_DIVERSITY, (T, N), f32), "mask": (nat.F_EXP_MASK, (T, N), f32)}
+    hi = {"obs": (nat.F_HI_OBS, (M, 8), f32), "zone_obs": (nat.F_HI_ZONE_OBS, (M, Z, F), f32),
+          "action": (nat.F_HI_ACTION, (M,), np.int32), "value": (nat.F_HI_VALUE, (M,), f32),
+          "log_prob": (nat.F_HI_LOG_PROB, (M,), f32), "advantage": (nat.F_HI_ADVANTAGE, (M,), f32),
+          "returnn": (nat.F_HI_RETURN, (M,), f32), "reward": (nat.F_HI_REWARD, (M,), f32),
+          "mask": (nat.F_HI_MASK, (M,), f32)}
+    return lo, hi
+
+
+def skill_num_frames(mask, skill_len):
+    """logs['num_frames'] of _hier_policy_opt.py:104-124 from the recorded masks [T, N] (numpy or torch): every env's
+    frames of a window up to and including its first done -- frame kL + i counts when mask[kL + 1 .. kL + i] are all
+    1 (mask[t] = 1 - done of frame t - 1)."""
+    T, N = mask.shape
+    L = int(skill_len)
+    if L == 1:
+        return T * N
+    m = mask.reshape(T // L, L, N)[:, 1:, :] != 0
+    if not isinstance(m, np.ndarray):                           # torch
+        return int(T // L * N + m.int().cumprod(dim=1).sum().item())
+    return int(T // L * N + np.cumprod(m, axis=1).sum())
 
 
 def zone_feat(cfg):
@@ -628,11 +737,14 @@ class ZoneVecEnv:
             setattr(w, name, a.ctypes.data)
         check(lib().zenv_skill_configure(self._h, int(skill_len)))
         check(lib().zenv_skill_load(self._h, C.byref(w)))
-        self._skill_n = S
+        if S != getattr(self, "_skill_n", S) or h != getattr(self, "_skill_h", h):
+            self._skill_inverse = False                      # zenv_skill_load dropped an inverse model of other shapes
+        self._skill_n, self._skill_h, self._skill_len = S, h, int(skill_len)
 
     def configure_skills(self, skill_len):
         """A new skill every ``skill_len`` steps (>= 1) from the next pick on."""
         check(lib().zenv_skill_configure(self._h, int(skill_len)))
+        self._skill_len = int(skill_len)
 
     def set_skills(self, skills):
         """skills: int32 [N] in -1 .. S-1; env i gets skills[i] with its age restarting at 0, -1 leaves it alone."""
@@ -648,6 +760,71 @@ class ZoneVecEnv:
         check(lib().zenv_skill_forward(self._h))
         return (self.get(nat.F_SKILL_LOGITS), self.get(nat.F_SKILL_VALUE), self.get(nat.F_POLICY_MU),
                 self.get(nat.F_POLICY_STD), self.get(nat.F_POLICY_VALUE))
+
+    def load_skill_inverse(self, tensors, precision="f32"):
+        """InverseModel, DIAYN's discriminator (main/src/inverse_model.py), for the diversity reward of
+        ``collect_skills``.  tensors: dict of float32 arrays named as in ``_native.SKILL_INVERSE_TENSORS`` (see
+        ``inverse_tensors_from_state_dict``); its h, S and F must be those of the loaded skill weights."""
+        if precision != "f32":
+            raise ValueError(f"precision {precision!r}: the inverse model is built in float32 only")
+        w2 = np.asarray(tensors["comb_w2"])
+        S, h = int(w2.shape[0]), int(w2.shape[1])
+        F = int(np.asarray(tensors["zone_w1"]).shape[1]) - 8
+        want = inverse_tensor_shapes(h, S, F)
+        w = nat.SkillInverseWeights(h_dim=h, n_skills=S, zone_feat=F, precision=nat.MLP_F32)
+        keep = {}
+        for name in nat.SKILL_INVERSE_TENSORS:
+            a = np.ascontiguousarray(tensors[name], np.float32)
+            if a.shape != want[name]:
+                raise ValueError(f"{name}: shape {a.shape}, expected {want[name]}")
+            keep[name] = a
+            setattr(w, name, a.ctypes.data)
+        check(lib().zenv_skill_inverse_load(self._h, C.byref(w)))
+        self._skill_inverse = True
+
+    def collect_skills(self, frames_per_proc, policy_seed=1, env_index0=0, discount=0.99, gae_lambda=0.95,
+                       diversity_coef=0.0, skill_prior_logits=None, sample_hi=True):
+        """HierPolicyAlgo.collect_experiences of the skill planner / DIAYN (main/src/torch_ac/algos/
+        _hier_policy_opt.py:9-233) on the device with the loaded skill agent (``load_skills`` with both critics) and,
+        for the diversity reward, ``load_skill_inverse``.  sample_hi=False is the reference's train_hi == False:
+        uniform skills.  Returns (lo, hi, inverse, num_frames) under the reference's names, numpy:
+          lo  [N, T, ...]: obs, zone_obs, skill, action, log_prob, value, advantage, returnn, reward (lo_reward),
+              env_reward, diversity, mask -- reshape(N*T, ...) is the reference's flat order (lo_exps)
+          hi  [M, ...] env-major, M = N T / skill_len: obs, zone_obs, action (the skill), value, log_prob, advantage,
+              returnn (hi_exps), reward (the window's sum) and mask (its next_mask)
+          inverse  obs, zone_obs, skill: lo obs of frame i+1 with the skill of frame i where mask[i+1], env-major
+          num_frames  logs['num_frames']"""
+        T, M = self.collect_skills_on_device(frames_per_proc, policy_seed, env_index0, discount, gae_lambda,
+                                             diversity_coef, skill_prior_logits, sample_hi)
+        L = T * self.num_envs // M
+        lo_l, hi_l = skill_experience_layout(self.num_envs, self.num_zones, self.zone_feat, T, L)
+        lo, hi = {}, {}
+        for name, (field, shape, dt) in lo_l.items():
+            a = np.empty(shape, dt)
+            assert a.nbytes == lib().zenv_field_bytes(self._h, field)
+            check(lib().zenv_get(self._h, field, a.ctypes.data, 0))
+            lo[name] = a.swapaxes(0, 1)
+        for name, (field, shape, dt) in hi_l.items():
+            a = np.empty(shape, dt)
+            assert a.nbytes == lib().zenv_field_bytes(self._h, field)
+            check(lib().zenv_get(self._h, field, a.ctypes.data, 0))
+            hi[name] = a
+        keep = lo["mask"][:, 1:] != 0                                   # [N, T-1], env-major
+        inverse = {"obs": lo["obs"][:, 1:][keep], "zone_obs": lo["zone_obs"][:, 1:][keep],
+                   "skill": lo["skill"][:, :-1][keep]}
+        return lo, hi, inverse, skill_num_frames(lo["mask"].swapaxes(0, 1), L)
+
+    def collect_skills_on_device(self, frames_per_proc, policy_seed=1, env_index0=0, discount=0.99, gae_lambda=0.95,
+                                 diversity_coef=0.0, skill_prior_logits=None, sample_hi=True):
+        """The same collection, results left in the handle's device buffers (``skill_experience_layout`` names them).
+        Returns (T, M)."""
+        L = getattr(self, "_skill_len", 200)                  # zenv_skill_configure's default until load_skills
+        T, seed, index0, discount, gae_lambda, coef, prior = check_collect_skill_args(
+            frames_per_proc, L, policy_seed, env_index0, discount, gae_lambda, diversity_coef, skill_prior_logits,
+            getattr(self, "_skill_n", None), getattr(self, "_skill_inverse", False))
+        check(lib().zenv_collect_skill(self._h, T, seed, index0, discount, gae_lambda, coef,
+                                       None if prior is None else prior.ctypes.data, 1 if sample_hi else 0))
+        return T, self.num_envs * (T // L)
 
     # ------------------------------------------------------------------ one PPO rollout (SURVEY 8(f) row 2)
     def collect(self, frames_per_proc, policy_seed=1, env_index0=0, discount=0.99, gae_lambda=0.95):

@@ -122,7 +122,15 @@ enum {
     ZENV_F_SKILL_LOGITS = 53,    /* float32 [N,S]    the high level's log-softmax: what Categorical(logits=log_softmax(x))
                                   *                    holds (main/src/policy_network.py:40-43) */
     ZENV_F_SKILL_VALUE = 54,     /* float32 [N]      the high level's critic value (0 without critic tensors) */
-    ZENV_F_COUNT = 55
+    /* fixed-length-skills experience of the last zenv_collect_skill() (before these three fields, ZENV_F_COUNT = 55).
+     * Its other records reuse the Zone-goals fields: ZENV_F_EXP_* (the low level,
+     * time-major [T][N], EXP_REWARD = reward + diversity_coef * diversity), ZENV_F_LO_ENV_REWARD (the env reward) and
+     * the ZENV_F_HI_* rows (M = N * T / skill_len, env-major, ZENV_F_HI_ACTION = the skill; ZENV_F_HI_ACTION_MASK is not
+     * written and has size 0) -- a skill handle is never goal-conditioned, so the two collections never share one */
+    ZENV_F_LO_SKILL = 55,        /* int32   [T,N]    the skill the low level acted under at every frame */
+    ZENV_F_LO_DIVERSITY = 56,    /* float32 [T,N]    DIAYN's diversity reward (0 everywhere without inverse weights) */
+    ZENV_F_SKILL_BOOTSTRAP = 57, /* int32   [N]      s' ~ the high level at obs_T: the skill of next_lo_value */
+    ZENV_F_COUNT = 58
 };
 
 /* scripted on-device action sources (the build's own; used by bench/tests) */
@@ -526,6 +534,26 @@ int zenv_set_skills(zenv_t *h, const int32_t *skills);
  * (ZENV_E_ARG); zenv_collect() takes none (it runs the flat network). */
 int zenv_skill_forward(zenv_t *h);
 
+/* DIAYN's discriminator, InverseModel (main/src/inverse_model.py): logits = combine_net(.2)(relu(combine_net(.0)(
+ * [obs, zone_emb]))), zone_emb = mean over the zones of zone_net([obs, zone row]) -- the skill high level's encoder
+ * followed by ReLU and an S-way head.  Host float32 tensors in the state_dict's layout; a struct of its own, so that
+ * zenv_skill_weights keeps its size. */
+typedef struct zenv_skill_inverse_weights {
+    int32_t h_dim;                        /* must equal the loaded zenv_skill_weights' */
+    int32_t n_skills;                     /* S, the same */
+    int32_t zone_feat;                    /* F, the same */
+    int32_t precision;                    /* ZENV_MLP_F32 only */
+    const float *zone_w1, *zone_b1;       /* zone_net.0     [h, 8+F], [h]  input = [obs, zone row] */
+    const float *zone_w2, *zone_b2;       /* zone_net.2     [h, h],   [h] */
+    const float *zone_w3, *zone_b3;       /* zone_net.4     [h, h],   [h] */
+    const float *comb_w1, *comb_b1;       /* combine_net.0  [h, 8+h], [h]  input = [obs, zone_emb] */
+    const float *comb_w2, *comb_b2;       /* combine_net.2  [S, h],   [S] */
+} zenv_skill_inverse_weights;
+/* ZENV_E_STATE before zenv_skill_load; ZENV_E_ARG for a null tensor, a precision other than ZENV_MLP_F32, or an h_dim,
+ * n_skills or zone_feat that differs from the loaded skill weights'.  A later zenv_skill_load of another shape drops
+ * these weights. */
+int zenv_skill_inverse_load(zenv_t *h, const zenv_skill_inverse_weights *w);
+
 /* ---- one PPO rollout on the device: BaseAlgo.collect_experiences, main/src/torch_ac/algos/base.py:131-227 ----
  * T times: (dist, value) = acmodel(obs) [zenv_mlp_forward]; action = dist.sample(); record obs, action, value,
  * log_prob, mask; step the envs (auto-reset); record the reward.  Then next_value = value(obs_T) and the GAE
@@ -558,6 +586,36 @@ int zenv_collect(zenv_t *h, int frames_per_proc, uint64_t policy_seed, uint64_t 
  * first goal of the new episode opens the env's next transition. */
 int zenv_collect_hier(zenv_t *h, int frames_per_proc, uint64_t policy_seed, uint64_t env_index0, float discount,
                       float gae_lambda, int64_t *n_hi);
+
+/* ---- the same for the fixed-length-skills agent and DIAYN: collect_experiences of HierPolicyAlgo,
+ * main/src/torch_ac/algos/_hier_policy_opt.py:9-233 (zenv_skill_load with BOTH critics, plain task handle) ----
+ * T frames, T a multiple of L = skill_len (zenv_skill_configure), W = T / L windows.  At frames 0, L, 2L ... EVERY env
+ * picks a skill: sample_hi != 0 draws it from the high level (the draw of zenv_policy(ZENV_POLICY_SKILL_SAMPLE)),
+ * sample_hi = 0 draws randint(0, S) on a Philox stream of its own; either way row env * W + k of ZENV_F_HI_* records
+ * the obs, the skill, the high critic's value and log_prob(skill).  Every frame the low level acts under the env's
+ * skill and frame t is recorded (ZENV_F_EXP_*, ZENV_F_LO_SKILL; mask = 1 - done of the previous step, carried from call
+ * to call); the envs step -- step_no_reset, except on a window's last frame, which auto-resets: an env whose episode
+ * ends inside a window idles (zero obs, reward 0, done 1) and its frames are recorded all the same.  Then
+ *   diversity_t = (log_softmax(inverse(obs_{t+1}))[skill_t] - log_softmax(skill_prior_logits)[skill_t]) * (1 - done_t)
+ *   lo_reward_t = reward_t + diversity_coef * diversity_t  (ZENV_F_EXP_REWARD; reward_t in ZENV_F_LO_ENV_REWARD)
+ * Bootstrap: V_hi(obs_T) into ZENV_F_SKILL_VALUE (the log-softmax into ZENV_F_SKILL_LOGITS), s' drawn from the high
+ * level at obs_T on a stream of its own (ZENV_F_SKILL_BOOTSTRAP, also without sample_hi), next_lo_value = V_lo(obs_T,
+ * s') into ZENV_F_POLICY_VALUE.
+ *   low level:  GAE over all T frames with discount, bootstrapped by next_lo_value (the advantage / return fields)
+ *   high level: per env over its W windows, NO discount: ZENV_F_HI_REWARD = the window's sum of env rewards,
+ *               ZENV_F_HI_MASK = next_mask = ZENV_F_EXP_MASK of the next window's first frame (the carried mask for
+ *               the last), delta = reward + V_next * next_mask - V, adv = delta + gae_lambda * adv_next * next_mask
+ * ZENV_F_HI_COUNT = W for every env.  Afterwards ZENV_F_SKILL holds the last window's skill with ZENV_F_SKILL_AGE = L,
+ * so the next zenv_policy(ZENV_POLICY_SKILL_*) picks at once.  Randomness: keyed by (policy_seed, env_index0 + env,
+ * zenv_step_count); with sample_hi a call is bit-identical to T rounds of zenv_policy(ZENV_POLICY_SKILL_SAMPLE) +
+ * zenv_step with auto_reset on each window's last frame only.  No host synchronisation.  skill_prior_logits: float32
+ * [S] host memory, the learned skill prior (read during the call); it may be NULL without inverse weights.
+ * ZENV_E_ARG: T < 1 or not a multiple of L, a non-finite discount / gae_lambda / diversity_coef, a discount or
+ * gae_lambda outside [0, 1], a null or non-finite prior while inverse weights are loaded, diversity_coef != 0 without
+ * them.  ZENV_E_STATE: no zenv_skill_load, a critic missing, zenv_host_io on, a goal-conditioned or solver-ordered
+ * handle. */
+int zenv_collect_skill(zenv_t *h, int frames_per_proc, uint64_t policy_seed, uint64_t env_index0, float discount,
+                       float gae_lambda, float diversity_coef, const float *skill_prior_logits, int sample_hi);
 
 /* ---- results ---- */
 int zenv_get(zenv_t *h, int field, void *dst, int dst_on_device);
