@@ -160,7 +160,8 @@ struct zenv {
     size_t chunk_cap = 0;           // steps * envs the allocation holds
     float *chunk_actions = nullptr, *chunk_reward = nullptr;
     uint8_t *chunk_done = nullptr;
-    int chunk_steps = 0;            // steps of the last zenv_step_many (extent of ZENV_F_CHUNK_*)
+    int chunk_steps = 0;            // steps of the last zenv_step_many (extent of ZENV_F_CHUNK_REWARD / _DONE)
+    int chunk_host_steps = 0;       // steps of the last host-action chunk while chunk_actions holds it, else 0
     // ZENV_F_EP_RETURN / ZENV_F_EP_LEN as plain arrays: the values live in the HotA records, unpacked by refresh_field()
     double *pub_ep_return = nullptr;
     int32_t *pub_steps = nullptr;
@@ -326,7 +327,7 @@ FieldInfo field_info(const zenv *h, int field)
     case ZENV_F_ORDER_POS: return { p.order_pos, p.order_pos ? N * p.Z : 0 };
     case ZENV_F_CHUNK_REWARD: return { h->chunk_reward, h->chunk_reward ? N * h->chunk_steps * 4 : 0 };
     case ZENV_F_CHUNK_DONE: return { h->chunk_done, h->chunk_done ? N * h->chunk_steps : 0 };
-    case ZENV_F_CHUNK_ACTIONS: return { h->chunk_actions, h->chunk_actions ? N * h->chunk_steps * 8 : 0 };
+    case ZENV_F_CHUNK_ACTIONS: return { h->chunk_actions, h->chunk_actions ? N * h->chunk_host_steps * 8 : 0 };
     case ZENV_F_EXCEPTION: return { p.exception, N };
     case ZENV_F_HIER_LOGITS: return { h->hier_logits, h->hier_logits ? N * p.Z * 4 : 0 };
     case ZENV_F_HIER_VALUE: return { h->hier_value, h->hier_value ? N * 4 : 0 };
@@ -1558,6 +1559,19 @@ static int run_policy(zenv_t *h, const StepPolicy &pol, const MlpRecord *rec = n
     return ZENV_OK;
 }
 
+// A ring schedule is only as deep as its `depth` slots per env, and only the HOST refills them (zenv_bank_update), between
+// calls: an env ends at most one episode per auto-resetting step, so a call of up to `depth` such steps cannot outrun
+// its ring; a longer one could wrap onto maps it has already played -- silently.  Refused instead.  `steps` counts the
+// call's auto-resets per env: its steps, frames, or skill windows (zenv_collect_skill resets on a window's last frame).
+static int ring_guard(const zenv *h, int steps, int auto_reset_every_step)
+{
+    if (h->p.sched_mode == SCHED_RING && auto_reset_every_step && steps > h->p.sched_stride)
+        return fail(ZENV_E_STATE, "a ring schedule of depth %d is refilled by the host between calls: %d auto-resetting "
+                    "steps in one call could replay maps (use calls of at most `depth` steps with zenv_bank_update in "
+                    "between, a deeper ring, or a sequential schedule)", h->p.sched_stride, steps);
+    return ZENV_OK;
+}
+
 // ============================================================================ experience collection
 // the ZENV_F_EXP_* buffers for T frames (zenv_collect, zenv_collect_hier); self.mask survives a change of T
 static int ensure_exp(zenv_t *h, int T)
@@ -1604,6 +1618,7 @@ extern "C" int zenv_collect(zenv_t *h, int T, uint64_t policy_seed, uint64_t env
     if (h->order_enabled)
         return fail(ZENV_E_STATE, "solver-ordered envs are stepped with zenv_step (their order feature is not part of "
                                   "the network input this call evaluates)");
+    if (int rr = ring_guard(h, T, 1)) return rr;           // every frame auto-resets
     int rc = use_device(h);
     if (rc) return rc;
     const size_t N = (size_t)h->n_env, ZF = (size_t)h->p.Z * h->p.F;
@@ -1740,6 +1755,7 @@ extern "C" int zenv_collect_hier(zenv_t *h, int T, uint64_t policy_seed, uint64_
         return fail(ZENV_E_STATE, "zenv_collect_hier needs both critics (zenv_hier_load with hi_critic_* and lo_critic_*)");
     if (h->host_io_slab) return fail(ZENV_E_STATE, "zenv_collect_hier records on the device: switch zenv_host_io off first");
     if (!h->was_reset) return fail(ZENV_E_STATE, "Environment must be reset before stepping");
+    if (int rr = ring_guard(h, T, 1)) return rr;           // every frame auto-resets
     int rc = use_device(h);
     if (rc) return rc;
     const size_t N = (size_t)h->n_env, ZF = (size_t)h->p.Z * h->p.F;
@@ -1848,6 +1864,7 @@ extern "C" int zenv_collect_skill(zenv_t *h, int T, uint64_t policy_seed, uint64
     const int L = h->skill_len, S = h->skill.S;
     if (T < 1 || T % L != 0)
         return fail(ZENV_E_ARG, "frames_per_proc %d must be a positive multiple of skill_len %d", T, L);
+    if (int rr = ring_guard(h, T / L, 1)) return rr;       // a window's last frame auto-resets
     if ((int64_t)T * h->n_env > INT32_MAX) return fail(ZENV_E_ARG, "frames_per_proc x envs must stay below 2^31");
     if (!std::isfinite(discount) || !std::isfinite(gae_lambda) || !std::isfinite(diversity_coef))
         return fail(ZENV_E_ARG, "discount, gae_lambda and diversity_coef must be finite");
@@ -1982,18 +1999,6 @@ static int ensure_self(zenv_t *h)
     return ZENV_OK;
 }
 
-// A ring schedule is only as deep as its `depth` slots per env, and only the HOST refills them (zenv_bank_update), between
-// calls: an env ends at most one episode per step, so a call of up to `depth` auto-resetting steps cannot outrun its
-// ring; a longer one could wrap onto maps it has already played -- silently.  Refused instead.
-static int ring_guard(const zenv *h, int steps, int auto_reset_every_step)
-{
-    if (h->p.sched_mode == SCHED_RING && auto_reset_every_step && steps > h->p.sched_stride)
-        return fail(ZENV_E_STATE, "a ring schedule of depth %d is refilled by the host between calls: %d auto-resetting "
-                    "steps in one call could replay maps (use calls of at most `depth` steps with zenv_bank_update in "
-                    "between, a deeper ring, or a sequential schedule)", h->p.sched_stride, steps);
-    return ZENV_OK;
-}
-
 // ============================================================================ action chunks
 // K steps of caller-supplied actions.  With the persistent kernel available (lane layout, a compiled zone count, no
 // goal / order post-kernels) a chunk is one launch per ZENV_ROLLOUT_CHUNK steps and slice; otherwise it is the plain
@@ -2014,13 +2019,15 @@ static int chunk_reserve(zenv *h, int steps, const float *device_actions)
         h->chunk_actions = h->chunk_reward = nullptr;
         h->chunk_done = nullptr;
         h->chunk_cap = 0;
+        h->chunk_host_steps = 0;    // the last host-action chunk went with the old allocation
         HIP_TRY(hipMalloc(&h->chunk_mem, cells * (8 + 4 + 1) + 256));
         h->chunk_actions = static_cast<float *>(h->chunk_mem);                    // [K][N][2] float32
         h->chunk_reward = h->chunk_actions + 2 * cells;                           // [K][N] float32
         h->chunk_done = reinterpret_cast<uint8_t *>(h->chunk_reward + cells);     // [K][N] uint8
         h->chunk_cap = cells;
     } else {
-        // the records of a shorter chunk sit at the front of the same allocation, re-laid-out for this call's K
+        // a chunk that fits keeps the layout of the allocation (fixed on chunk_cap): its actions at the front, its
+        // rewards and done flags at the front of theirs -- a device-action chunk leaves the host chunk's actions alone
         const size_t cap = h->chunk_cap;
         h->chunk_reward = h->chunk_actions + 2 * cap;
         h->chunk_done = reinterpret_cast<uint8_t *>(h->chunk_reward + cap);
@@ -2048,10 +2055,17 @@ extern "C" int zenv_step_many(zenv_t *h, const float *actions, int actions_on_de
     if (!actions_on_device) {
         HIP_TRY(hipMemcpyAsync(h->chunk_actions, actions, sizeof(float) * 2 * N * (size_t)n_steps, hipMemcpyHostToDevice, h->stream));
         d_act = h->chunk_actions;
+        h->chunk_host_steps = n_steps;
         // like n_steps zenv_step() calls with host actions, the handle's action buffer ends up holding the last step's
-        if (!h->host_io_actions)
+        const float *last = actions + 2 * N * (size_t)(n_steps - 1);
+        if (h->host_io_actions) {
+            // the page-locked buffer a kernel may still read: written once the stream has drained, as zenv_step does
+            HIP_TRY(hipStreamSynchronize(h->stream));
+            std::memcpy(h->host_io_actions, last, sizeof(float) * 2 * N);
+        } else {
             HIP_TRY(hipMemcpyAsync(h->p.actions, h->chunk_actions + 2 * N * (size_t)(n_steps - 1), sizeof(float) * 2 * N,
                                    hipMemcpyDeviceToDevice, h->stream));
+        }
     }
     h->chunk_steps = n_steps;
     const bool persistent = rollout_kernel_available(h->p) && !h->goal_enabled && !h->order_enabled;

@@ -28,8 +28,13 @@ class _DeviceView:
 
 class TorchZoneEnv:
     """Tensor view of a ``ZoneVecEnv``: ``obs (N,8)``, ``zone_obs (N,Z,F)``, ``reward (N,)`` float32,
-    ``done``/``goal_met (N,)`` uint8, ``ep_return``/``last_return (N,)`` float64 -- all aliases of the
-    env's device buffers, valid until ``env.close()``; they change in place on every ``step``."""
+    ``done``/``goal_met (N,)`` uint8, ``last_return (N,)`` float64, ``episodes (N,)`` int32 -- aliases of the
+    env's device buffers, valid until ``env.close()``; they change in place on every ``step``.
+
+    ``ep_return (N,)`` float64 and ``ep_len (N,)`` int32 are properties instead: the running episode's figures live
+    inside the step kernels' records, and ``zenv_device_ptr`` hands out a plain copy brought up to date by that call
+    (stream-ordered).  Each access re-aliases that copy, so the tensor read holds every step enqueued before the
+    access; a tensor kept from an earlier access is only brought up to date by a later access (or a get)."""
 
     def __init__(self, env, use_current_stream=True):
         import torch
@@ -44,9 +49,20 @@ class TorchZoneEnv:
             self.reward = self._alias(nat.F_REWARD)
             self.done = self._alias(nat.F_DONE)
             self.goal_met = self._alias(nat.F_GOAL_MET)
-            self.ep_return = self._alias(nat.F_EP_RETURN)
             self.last_return = self._alias(nat.F_LAST_RETURN)
             self.episodes = self._alias(nat.F_EPISODES)
+
+    @property
+    def ep_return(self):
+        """Undiscounted return of the running episode, as of this access (see the class docstring)."""
+        with self._torch.cuda.device(self.device):
+            return self._alias(nat.F_EP_RETURN)
+
+    @property
+    def ep_len(self):
+        """Steps of the running episode, as of this access (see the class docstring)."""
+        with self._torch.cuda.device(self.device):
+            return self._alias(nat.F_EP_LEN)
 
     def _alias(self, field):
         t = self._torch.as_tensor(_DeviceView(self.env.device_ptr(field), self.env._shape(field),

@@ -52,6 +52,8 @@ enum {
     ZENV_F_REWARD = 2,      /* float32 [N] */
     ZENV_F_DONE = 3,        /* uint8   [N]     done flag returned by the last step */
     ZENV_F_GOAL_MET = 4,    /* uint8   [N]     info['goal_met'] (evaluate.py:65) */
+    /* EP_RETURN / EP_LEN live inside the step kernels' records: zenv_get / zenv_device_ptr unpack them (stream-ordered),
+     * and a device pointer of these two is a plain copy as of that call, not a live view */
     ZENV_F_EP_RETURN = 5,   /* float64 [N]     undiscounted return of the running episode */
     ZENV_F_EP_LEN = 6,      /* int32   [N]     steps of the running episode */
     ZENV_F_LAST_RETURN = 7, /* float64 [N]     return of the last finished episode (evaluate.py:62-72) */
@@ -90,7 +92,9 @@ enum {
     ZENV_F_CHUNK_REWARD = 33,    /* float32 [K,N] */
     ZENV_F_CHUNK_DONE = 34,      /* uint8   [K,N] */
     ZENV_F_CHUNK_ACTIONS = 35,   /* float32 [K,N,2]  the device copy of the last chunk whose actions came from the host (a caller that
-                                  *                    replays it passes zenv_device_ptr() of this field back, actions_on_device = 1) */
+                                  *                    replays it passes zenv_device_ptr() of this field back, actions_on_device = 1);
+                                  *                    K is that chunk's length, not the last call's.  0 bytes once a
+                                  *                    device-action chunk has outgrown the buffer (its copy is gone) */
     /* Zone-goals hierarchical agent (zenv_hier_load): */
     ZENV_F_HIER_LOGITS = 36,     /* float32 [N,Z]    the high level's logit of every zone, -INFINITY where the zone is not an
                                   *                    available goal (hier_agent.py get_hi_action: logits[~available] = -inf);
@@ -249,7 +253,10 @@ int zenv_bank_update(zenv_t *h, const int32_t *slots, const int64_t *seeds, int 
 /* slot = (first[i] + k*stride) mod S; first == NULL -> i mod S. */
 int zenv_schedule_sequential(zenv_t *h, const int32_t *first, int32_t stride);
 /* Ring: env i owns the slots first[i] .. first[i] + depth - 1 and takes slot first[i] + (k mod depth) for its k-th
- * episode; the host keeps the ring ahead of the env with zenv_bank_update. */
+ * episode; the host keeps the ring ahead of the env with zenv_bank_update.  Only the host refills the ring, between
+ * calls, so a call that could end more than `depth` episodes of an env is refused with ZENV_E_STATE (it could replay
+ * maps): zenv_rollout with auto_reset and zenv_step_many(RESET_EVERY) beyond `depth` steps, zenv_collect and
+ * zenv_collect_hier beyond `depth` frames, zenv_collect_skill beyond `depth` windows. */
 int zenv_schedule_ring(zenv_t *h, const int32_t *first, int32_t depth);
 /* FixedSeedsWrapper semantics on device: env i draws seeds from its own PCG64 stream
  * default_rng(rng_seeds[i]).integers(min_seed, max_seed+1); the bank must hold
@@ -286,7 +293,9 @@ int zenv_step(zenv_t *h, const float *actions, int actions_on_device, int auto_r
  *                           finishes inside the chunk waits (zero obs, reward 0, done) and comes back at the boundary
  * A NaN action takes Engine.step's exception branch as in zenv_step.  Afterwards obs / zone_obs / reward / done /
  * goal_met hold the LAST step's results; every step's reward and done flag is in ZENV_F_CHUNK_REWARD / _DONE
- * ([n_steps][N], valid until the next zenv_step_many).  On a ring schedule RESET_EVERY is limited to `depth` steps
+ * ([n_steps][N], valid until the next zenv_step_many).  The handle's action buffer (ZENV_F_ACTIONS, what zenv_step(NULL)
+ * replays and snapshots keep) ends as after n_steps zenv_step calls: the last step's actions for host actions, with or
+ * without zenv_host_io; untouched for device actions.  On a ring schedule RESET_EVERY is limited to `depth` steps
  * per call (ZENV_E_STATE beyond: the host refills the ring between calls). */
 enum { ZENV_CHUNK_NO_RESET = 0, ZENV_CHUNK_RESET_EVERY = 1, ZENV_CHUNK_RESET_LAST = 2 };
 int zenv_step_many(zenv_t *h, const float *actions, int actions_on_device, int n_steps, int reset_mode);
@@ -558,7 +567,8 @@ int zenv_skill_inverse_load(zenv_t *h, const zenv_skill_inverse_weights *w);
  * T times: (dist, value) = acmodel(obs) [zenv_mlp_forward]; action = dist.sample(); record obs, action, value,
  * log_prob, mask; step the envs (auto-reset); record the reward.  Then next_value = value(obs_T) and the GAE
  * recursion.  Needs actor AND critic weights (zenv_mlp_load).  The buffers (ZENV_F_EXP_*) stay valid until the
- * next call with a different T or zenv_destroy; self.mask is carried from call to call like the reference's. */
+ * next call with a different T or zenv_destroy; self.mask is carried from call to call like the reference's.  On a
+ * ring schedule (zenv_schedule_ring) T is limited to the ring's depth: ZENV_E_STATE beyond. */
 int zenv_collect(zenv_t *h, int frames_per_proc, uint64_t policy_seed, uint64_t env_index0, float discount,
                  float gae_lambda);
 
@@ -581,7 +591,8 @@ int zenv_collect(zenv_t *h, int frames_per_proc, uint64_t policy_seed, uint64_t 
  * (policy_seed, env_index0 + env, zenv_step_count): a call is bit-identical to T rounds of zenv_policy + zenv_step.  A
  * finished env draws nothing; an env with no available zone gets no goal and action 0 (the reference would assert).
  * One host synchronisation, at the end (to learn M).  ZENV_E_ARG: frames_per_proc < 2; ZENV_E_STATE: no goals, no
- * zenv_hier_load, a critic missing, zenv_host_io on, a solver-ordered handle.  zenv_reset ends the episodes it resets:
+ * zenv_hier_load, a critic missing, zenv_host_io on, a solver-ordered handle, more frames than a ring schedule's depth.
+ * zenv_reset ends the episodes it resets:
  * the open transition of such an env is dropped (no row ever refers to it) and its hi_reward restarts at 0, so the
  * first goal of the new episode opens the env's next transition. */
 int zenv_collect_hier(zenv_t *h, int frames_per_proc, uint64_t policy_seed, uint64_t env_index0, float discount,
@@ -613,7 +624,7 @@ int zenv_collect_hier(zenv_t *h, int frames_per_proc, uint64_t policy_seed, uint
  * ZENV_E_ARG: T < 1 or not a multiple of L, a non-finite discount / gae_lambda / diversity_coef, a discount or
  * gae_lambda outside [0, 1], a null or non-finite prior while inverse weights are loaded, diversity_coef != 0 without
  * them.  ZENV_E_STATE: no zenv_skill_load, a critic missing, zenv_host_io on, a goal-conditioned or solver-ordered
- * handle. */
+ * handle, more windows (T / L) than a ring schedule's depth. */
 int zenv_collect_skill(zenv_t *h, int frames_per_proc, uint64_t policy_seed, uint64_t env_index0, float discount,
                        float gae_lambda, float diversity_coef, const float *skill_prior_logits, int sample_hi);
 
@@ -622,7 +633,9 @@ int zenv_get(zenv_t *h, int field, void *dst, int dst_on_device);
 /* The rows of envs [first_env, first_env + count) of an env-major field (obs, zone_obs, reward, counters ...; not the
  * time-major ZENV_F_EXP_* buffers) into host memory: what a caller that looks at a few envs of a multi-GB batch uses. */
 int zenv_get_rows(zenv_t *h, int field, int first_env, int count, void *dst);
-int zenv_device_ptr(zenv_t *h, int field, void **ptr);  /* zero-copy for GPU consumers */
+/* zero-copy for GPU consumers: the handle's own buffer, live -- except ZENV_F_EP_RETURN / _EP_LEN and ZENV_F_SKILL /
+ * _SKILL_AGE, which are plain copies brought up to date by this call (stream-ordered): call it again for fresh values */
+int zenv_device_ptr(zenv_t *h, int field, void **ptr);
 int64_t zenv_field_bytes(const zenv_t *h, int field);
 int zenv_sync(zenv_t *h);
 int zenv_query(zenv_t *h);   /* non-blocking: 1 = everything enqueued on the handle's stream has finished, 0 = not yet */
