@@ -1573,6 +1573,16 @@ static int ring_guard(const zenv *h, int steps, int auto_reset_every_step)
 }
 
 // ============================================================================ experience collection
+// the three collectors' discount and gae_lambda: finite and in [0, 1] (a NaN would turn every advantage into NaN)
+static int gae_args(float discount, float gae_lambda)
+{
+    if (!std::isfinite(discount) || !std::isfinite(gae_lambda))
+        return fail(ZENV_E_ARG, "discount %g and gae_lambda %g must be finite", discount, gae_lambda);
+    if (discount < 0.f || discount > 1.f || gae_lambda < 0.f || gae_lambda > 1.f)
+        return fail(ZENV_E_ARG, "discount %g and gae_lambda %g must lie in [0, 1]", discount, gae_lambda);
+    return ZENV_OK;
+}
+
 // the ZENV_F_EXP_* buffers for T frames (zenv_collect, zenv_collect_hier); self.mask survives a change of T
 static int ensure_exp(zenv_t *h, int T)
 {
@@ -1612,6 +1622,8 @@ extern "C" int zenv_collect(zenv_t *h, int T, uint64_t policy_seed, uint64_t env
 {
     if (!h) return fail(ZENV_E_ARG, "null handle");
     if (T < 1) return fail(ZENV_E_ARG, "frames_per_proc must be positive");
+    if ((int64_t)T * h->n_env > INT32_MAX) return fail(ZENV_E_ARG, "frames_per_proc x envs must stay below 2^31");
+    if (int ra = gae_args(discount, gae_lambda)) return ra;
     if (!h->was_reset) return fail(ZENV_E_STATE, "Environment must be reset before stepping");
     if (!h->mlp_ready || !h->mlp.wv1) return fail(ZENV_E_STATE, "zenv_mlp_load with actor and critic weights first");
     if (h->host_io_slab) return fail(ZENV_E_STATE, "zenv_collect records on the device: switch zenv_host_io off first");
@@ -1747,6 +1759,7 @@ extern "C" int zenv_collect_hier(zenv_t *h, int T, uint64_t policy_seed, uint64_
     if (!h) return fail(ZENV_E_ARG, "null handle");
     if (T < 2) return fail(ZENV_E_ARG, "frames_per_proc must be at least 2 (the low level hands out T - 1 frames)");
     if ((int64_t)T * h->n_env > INT32_MAX) return fail(ZENV_E_ARG, "frames_per_proc x envs must stay below 2^31");
+    if (int ra = gae_args(discount, gae_lambda)) return ra;
     if (h->order_enabled)
         return fail(ZENV_E_STATE, "zenv_collect_hier runs the goal-conditioned agent: this handle is solver-ordered");
     if (!h->goal_enabled) return fail(ZENV_E_STATE, "zenv_collect_hier needs a goal-conditioned handle: zenv_goal_enable first");
@@ -1866,10 +1879,8 @@ extern "C" int zenv_collect_skill(zenv_t *h, int T, uint64_t policy_seed, uint64
         return fail(ZENV_E_ARG, "frames_per_proc %d must be a positive multiple of skill_len %d", T, L);
     if (int rr = ring_guard(h, T / L, 1)) return rr;       // a window's last frame auto-resets
     if ((int64_t)T * h->n_env > INT32_MAX) return fail(ZENV_E_ARG, "frames_per_proc x envs must stay below 2^31");
-    if (!std::isfinite(discount) || !std::isfinite(gae_lambda) || !std::isfinite(diversity_coef))
-        return fail(ZENV_E_ARG, "discount, gae_lambda and diversity_coef must be finite");
-    if (discount < 0.f || discount > 1.f || gae_lambda < 0.f || gae_lambda > 1.f)
-        return fail(ZENV_E_ARG, "discount %g and gae_lambda %g must lie in [0, 1]", discount, gae_lambda);
+    if (int ra = gae_args(discount, gae_lambda)) return ra;
+    if (!std::isfinite(diversity_coef)) return fail(ZENV_E_ARG, "diversity_coef must be finite");
     if (diversity_coef != 0.f && !h->skinv_ready)
         return fail(ZENV_E_ARG, "diversity_coef %g without an inverse model (zenv_skill_inverse_load)", diversity_coef);
     SkillDiv div{};

@@ -567,8 +567,13 @@ int zenv_skill_inverse_load(zenv_t *h, const zenv_skill_inverse_weights *w);
  * T times: (dist, value) = acmodel(obs) [zenv_mlp_forward]; action = dist.sample(); record obs, action, value,
  * log_prob, mask; step the envs (auto-reset); record the reward.  Then next_value = value(obs_T) and the GAE
  * recursion.  Needs actor AND critic weights (zenv_mlp_load).  The buffers (ZENV_F_EXP_*) stay valid until the
- * next call with a different T or zenv_destroy; self.mask is carried from call to call like the reference's.  On a
- * ring schedule (zenv_schedule_ring) T is limited to the ring's depth: ZENV_E_STATE beyond. */
+ * next call with a different T or zenv_destroy; self.mask is carried from call to call like the reference's, across a
+ * change of T too: frame 0's mask is 1 - done of the last frame of the previous call (1 before the first call).
+ * zenv_reset does not touch it -- self.mask belongs to the algorithm, not to the envs, and the reference's
+ * ParallelEnv.reset() leaves BaseAlgo.mask alone as well -- so after a zenv_reset between two calls frame 0 still
+ * records the previous call's last 1 - done.  ZENV_E_ARG: frames_per_proc < 1, frames_per_proc x envs >= 2^31, a
+ * non-finite discount or gae_lambda, or one outside [0, 1].  On a ring schedule (zenv_schedule_ring) T is limited to
+ * the ring's depth: ZENV_E_STATE beyond. */
 int zenv_collect(zenv_t *h, int frames_per_proc, uint64_t policy_seed, uint64_t env_index0, float discount,
                  float gae_lambda);
 
@@ -590,7 +595,8 @@ int zenv_collect(zenv_t *h, int frames_per_proc, uint64_t policy_seed, uint64_t 
  * the first transition of the next call.  Randomness: that of zenv_policy(ZENV_POLICY_HIER_SAMPLE), keyed by
  * (policy_seed, env_index0 + env, zenv_step_count): a call is bit-identical to T rounds of zenv_policy + zenv_step.  A
  * finished env draws nothing; an env with no available zone gets no goal and action 0 (the reference would assert).
- * One host synchronisation, at the end (to learn M).  ZENV_E_ARG: frames_per_proc < 2; ZENV_E_STATE: no goals, no
+ * One host synchronisation, at the end (to learn M).  ZENV_E_ARG: frames_per_proc < 2, frames_per_proc x envs >= 2^31,
+ * a non-finite discount or gae_lambda, or one outside [0, 1] (as zenv_collect and zenv_collect_skill); ZENV_E_STATE: no goals, no
  * zenv_hier_load, a critic missing, zenv_host_io on, a solver-ordered handle, more frames than a ring schedule's depth.
  * zenv_reset ends the episodes it resets:
  * the open transition of such an env is dropped (no row ever refers to it) and its hi_reward restarts at 0, so the
@@ -621,7 +627,7 @@ int zenv_collect_hier(zenv_t *h, int frames_per_proc, uint64_t policy_seed, uint
  * zenv_step_count); with sample_hi a call is bit-identical to T rounds of zenv_policy(ZENV_POLICY_SKILL_SAMPLE) +
  * zenv_step with auto_reset on each window's last frame only.  No host synchronisation.  skill_prior_logits: float32
  * [S] host memory, the learned skill prior (read during the call); it may be NULL without inverse weights.
- * ZENV_E_ARG: T < 1 or not a multiple of L, a non-finite discount / gae_lambda / diversity_coef, a discount or
+ * ZENV_E_ARG: T < 1 or not a multiple of L, T x envs >= 2^31, a non-finite discount / gae_lambda / diversity_coef, a discount or
  * gae_lambda outside [0, 1], a null or non-finite prior while inverse weights are loaded, diversity_coef != 0 without
  * them.  ZENV_E_STATE: no zenv_skill_load, a critic missing, zenv_host_io on, a goal-conditioned or solver-ordered
  * handle, more windows (T / L) than a ring schedule's depth. */

@@ -43,11 +43,13 @@ def random_tensors(F, h=185, seed=0, bias_scale=0.1, critic=False, distributiona
     return {k: v.numpy().astype(np.float32) for k, v in t.items()}
 
 
-def forward_fp32(t, obs, zone_obs):
-    """The reference computation, float32.  obs [B,8], zone_obs [B,Z,F] -> mu, std [B,2]."""
-    t = {k: torch.as_tensor(v, dtype=torch.float32) for k, v in t.items()}
-    obs = torch.as_tensor(obs, dtype=torch.float32)
-    zo = torch.as_tensor(zone_obs, dtype=torch.float32)
+def forward_fp32(t, obs, zone_obs, dtype=torch.float32):
+    """The reference computation, float32.  obs [B,8], zone_obs [B,Z,F] -> mu, std [B,2].  dtype=torch.float64: the same
+    operations on the same float32 weights and inputs, carried out in float64 (the yardstick the kernels' float32
+    arithmetic is measured against); numpy arrays of `dtype`."""
+    t = {k: torch.as_tensor(v, dtype=torch.float32).to(dtype) for k, v in t.items()}
+    obs = torch.as_tensor(obs, dtype=torch.float32).to(dtype)
+    zo = torch.as_tensor(zone_obs, dtype=torch.float32).to(dtype)
     bs, n_zones = zo.shape[0], zo.shape[1]
     x = torch.cat([obs.view(bs, 1, 8).expand(bs, n_zones, 8), zo], dim=-1)          # env_model.py:75-78
     x = torch.relu(x @ t["zone_w1"].T + t["zone_b1"])

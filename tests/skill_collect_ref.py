@@ -15,22 +15,24 @@ from tests.skill_ref import _lin
 LAM, GAMMA = 0.95, 0.99
 
 
-def random_inverse_state_dict(F, S, h=128, seed=0, bias_scale=0.1):
-    """InverseModel.state_dict() with the reference's key names, float32 torch tensors."""
+def random_inverse_state_dict(F, S, h=128, seed=0, bias_scale=0.1, weight_scale=1.0):
+    """InverseModel.state_dict() with the reference's key names, float32 torch tensors.  weight_scale multiplies every
+    weight row (unit norm by default): larger logits, for the edge sweeps."""
     g = torch.Generator().manual_seed(seed)
     sd = {}
     for name, n_out, n_in in (("zone_net.0", h, 8 + F), ("zone_net.2", h, h), ("zone_net.4", h, h),
                               ("combine_net.0", h, 8 + h), ("combine_net.2", S, h)):
-        w, b = _lin(g, n_out, n_in, bias_scale)
+        w, b = _lin(g, n_out, n_in, bias_scale, weight_scale)
         sd[f"{name}.weight"], sd[f"{name}.bias"] = w * (3.0 if name == "combine_net.2" else 1.0), b
     return sd
 
 
-def inverse_log_softmax(sd, obs, zone_obs):
-    """log_softmax(InverseModel(obs)) [B, S], float32 numpy (InverseModel.forward, then F.log_softmax(dim=-1))."""
-    sd = {k: torch.as_tensor(np.asarray(v)).float() for k, v in sd.items()}
-    o = torch.as_tensor(np.asarray(obs, np.float32))
-    zo = torch.as_tensor(np.asarray(zone_obs, np.float32))
+def inverse_log_softmax(sd, obs, zone_obs, dtype=torch.float32):
+    """log_softmax(InverseModel(obs)) [B, S], float32 numpy (InverseModel.forward, then F.log_softmax(dim=-1));
+    dtype=torch.float64: the same operations on the same float32 weights and inputs in float64."""
+    sd = {k: torch.as_tensor(np.asarray(v)).float().to(dtype) for k, v in sd.items()}
+    o = torch.as_tensor(np.asarray(obs, np.float32)).to(dtype)
+    zo = torch.as_tensor(np.asarray(zone_obs, np.float32)).to(dtype)
     bs, n_zones = zo.shape[0], zo.shape[1]
     x = torch.cat([o.view(bs, 1, 8).expand(bs, n_zones, 8), zo], dim=-1)
     y = torch.relu(x @ sd["zone_net.0.weight"].T + sd["zone_net.0.bias"])

@@ -272,10 +272,10 @@ def test_recorded_networks_match_torch(zenv_mod, env_id, h):
 def test_refusals(zenv_mod):
     Z = zenv_mod
     nat = Z._native
-    raw = lambda env, T: nat.lib().zenv_collect_hier(env._h, T, 1, 0, 0.99, 0.95, C.byref(C.c_int64()))
+    raw = lambda env, T, d=0.99, lam=0.95: nat.lib().zenv_collect_hier(env._h, T, 1, 0, d, lam, C.byref(C.c_int64()))
 
-    def code(env, T=8):
-        rc = raw(env, T)
+    def code(env, T=8, d=0.99, lam=0.95):
+        rc = raw(env, T, d, lam)
         assert rc < 0
         return rc
     cfg = Z.config_for_id("PointTSP-v0")
@@ -295,6 +295,10 @@ def test_refusals(zenv_mod):
         assert code(env) == Z.E_STATE
     env.load_hier(t)
     assert code(env, 1) == Z.E_ARG and code(env, 0) == Z.E_ARG     # T < 2
+    assert code(env, 2 ** 27) == Z.E_ARG                            # T x 16 envs = 2^31
+    for d, lam in ((float("nan"), 0.95), (0.99, float("nan")), (float("inf"), 0.95), (0.99, -float("inf")),
+                   (1.5, 0.95), (0.99, -0.1), (-0.01, 0.5), (0.5, 1.01)):
+        assert code(env, 8, d, lam) == Z.E_ARG, (d, lam)           # as zenv_collect_skill refuses them
     with pytest.raises(ValueError):
         env.collect_hier(1)
     env.host_io(True)
