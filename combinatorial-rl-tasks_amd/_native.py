@@ -18,6 +18,7 @@ TASK_TSP, TASK_TIMED_TSP, TASK_COLOUR_MATCH = 0, 1, 2
 POLICY_UNIFORM, POLICY_GREEDY, POLICY_MLP_MEAN, POLICY_MLP_SAMPLE = 0, 1, 2, 3
 POLICY_HIER_SAMPLE, POLICY_HIER_MEAN = 4, 5     # the Zone-goals hierarchical agent (zenv_hier_load)
 POLICY_SKILL_SAMPLE, POLICY_SKILL_MEAN = 6, 7   # the fixed-length-skills agent (zenv_skill_load)
+POLICY_OPTION_SAMPLE, POLICY_OPTION_MEAN = 8, 9  # the variable-length Options agent (zenv_option_load)
 MAX_SKILLS = 32
 KERNEL_LANE_PER_ENV, KERNEL_WAVE_PER_ENV = 0, 1
 HIP_STREAM_LEGACY = 1       # hipStreamLegacy: the null stream as an explicit handle (hip_runtime_api.h)
@@ -40,7 +41,8 @@ E_ARG, E_HIP, E_STATE, E_LAYOUT, E_DONE, E_RANGE = -1, -2, -3, -4, -5, -6
  F_LO_GOAL, F_LO_ENV_REWARD, F_HI_OBS, F_HI_ZONE_OBS, F_HI_ACTION, F_HI_ACTION_MASK, F_HI_VALUE, F_HI_LOG_PROB,
  F_HI_ADVANTAGE, F_HI_RETURN, F_HI_REWARD, F_HI_MASK, F_HI_COUNT,
  F_SKILL, F_SKILL_AGE, F_SKILL_LOGITS, F_SKILL_VALUE,
- F_LO_SKILL, F_LO_DIVERSITY, F_SKILL_BOOTSTRAP) = range(58)
+ F_LO_SKILL, F_LO_DIVERSITY, F_SKILL_BOOTSTRAP,
+ F_OPTION_TERM_MU, F_OPTION_TERM_STD, F_OPTION_TERM_ACTION, F_OPTION_TERM_PROB, F_OPTION_ENDED) = range(63)
 (RESULT_OBS, RESULT_REWARD, RESULT_DONE, RESULT_GOAL_MET, RESULT_EXCEPTION, RESULT_ZONE_OBS) = range(6)
 N_RESULTS = 6
 
@@ -85,6 +87,11 @@ class SkillWeights(C.Structure):
     """struct zenv_skill_weights (include/zenv.h): host float32 tensors in state_dict layout."""
     _fields_ = [("h_dim", C.c_int32), ("n_skills", C.c_int32), ("zone_feat", C.c_int32), ("precision", C.c_int32)] + [
         (n, C.c_void_p) for n in SKILL_HI_TENSORS + SKILL_HI_CRITIC + SKILL_LO_TENSORS + SKILL_LO_CRITIC]
+
+
+class OptionWeights(C.Structure):
+    """struct zenv_option_weights (include/zenv.h): zenv_skill_weights' members; lo_mu_* / lo_std_* have three rows."""
+    _fields_ = list(SkillWeights._fields_)
 
 
 # struct zenv_skill_inverse_weights (include/zenv.h): InverseModel, DIAYN's discriminator (main/src/inverse_model.py)
@@ -178,6 +185,8 @@ _PROTOTYPES = {
     "zenv_set_skills": (C.c_int, [_H, C.c_void_p]),
     "zenv_skill_forward": (C.c_int, [_H]),
     "zenv_skill_inverse_load": (C.c_int, [_H, C.c_void_p]),
+    "zenv_option_load": (C.c_int, [_H, C.c_void_p]),
+    "zenv_option_forward": (C.c_int, [_H]),
     "zenv_collect_skill": (C.c_int, [_H, C.c_int, C.c_uint64, C.c_uint64, C.c_float, C.c_float, C.c_float, C.c_void_p,
                                      C.c_int]),
     "zenv_get": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int]),

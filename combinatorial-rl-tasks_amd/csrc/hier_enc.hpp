@@ -46,16 +46,17 @@ __device__ __forceinline__ void matvec(float (&out)[EB], const float *__restrict
     }
 }
 
-// zone rows r0 .. r0 + RP - 1 of the workgroup's envs (row = e * Z + z) -> x0 [ZF][RP], zeros beyond
+// zone rows r0 .. r0 + RP - 1 of the workgroup's envs (row = e * Z + z) -> x0 [ZF][RP], zeros beyond; the envs are
+// env0 + e, or envs[e] where a list is given
 __device__ __forceinline__ void load_rows(float *__restrict__ x0, const float *__restrict__ zone_obs, int env0, int r0,
-                                          int n_rows, int Z, int F, int j)
+                                          int n_rows, int Z, int F, int j, const int *envs = nullptr)
 {
     for (int i = j; i < ZF * RP; i += HP) {
         const int k = i / RP, r = i % RP, row = r0 + r;
         float v = 0.f;
         if (row < n_rows && k < F) {
             const int e = row / Z, z = row - e * Z;
-            v = zone_obs[((size_t)(env0 + e) * Z + z) * F + k];
+            v = zone_obs[((size_t)(envs ? envs[e] : env0 + e) * Z + z) * F + k];
         }
         x0[k * RP + r] = v;
     }
@@ -92,7 +93,8 @@ __device__ __forceinline__ void add_column(float (&t)[EB], const float *__restri
         if (sel[e] >= 0) t[e] += col[(size_t)sel[e] * HP + j];
 }
 
-// ZoneEnvModel / ZoneEnvGoalModel / ZoneEnvSkillModel on the workgroup's envs env0 .. env0 + n_env - 1: the per-env input
+// ZoneEnvModel / ZoneEnvGoalModel / ZoneEnvSkillModel on the workgroup's envs env0 .. env0 + n_env - 1, or the n_env envs
+// envs[0 ..] (LDS) where a list is given -- xin, sel and the outputs stay per workgroup slot e either way: the per-env input
 // x (XIN columns of xin [EB][XP], LDS) is the same for every zone row of an env, so W_x x + b of zone_net_.0 is a per-env
 // bias (peb) and the per-zone part has the flat network's shape, F columns.  A one-hot input (the skill) enters the same
 // way, as the column sel[e] of col1 (zone_net_.0) and colc (combine_net_); col1 = colc = null: none.
@@ -102,7 +104,7 @@ __device__ __forceinline__ void encode_envs(const HierEnc &E, const DevParams &p
                                             const float *__restrict__ col1, const float *__restrict__ colc,
                                             const int *sel, int env0, int n_env, int h, int j, float *__restrict__ x0,
                                             float *__restrict__ y1, float *__restrict__ peb, float *__restrict__ va,
-                                            float *__restrict__ vb)
+                                            float *__restrict__ vb, const int *envs = nullptr)
 {
     const int Z = p.Z, F = p.F;
     const bool live = j < h;                             // padded features stay exactly 0
@@ -120,7 +122,7 @@ __device__ __forceinline__ void encode_envs(const HierEnc &E, const DevParams &p
     const float b2 = E.b2[j];
     for (int r0 = 0; r0 < n_rows; r0 += RP) {
         __syncthreads();                                  // the previous pass is done with x0 / y1 (and peb is written)
-        load_rows(x0, p.zone_obs, env0, r0, n_rows, Z, F, j);
+        load_rows(x0, p.zone_obs, env0, r0, n_rows, Z, F, j, envs);
         __syncthreads();
         float acc[RP];
         zone_part(acc, peb, E.w1z, x0, r0, Z, F, j);

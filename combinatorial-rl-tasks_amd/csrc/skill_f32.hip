@@ -17,27 +17,20 @@
 #include <cstddef>
 #include <cstring>
 
-#include "hier_enc.hpp"
-#include "mlp_head_out.hpp"
-#include "skill_f32.hpp"
+#include "skill_net.hpp"
 
 namespace zenvk {
 namespace {
 
 using namespace hf32;
 
-constexpr int SR = kMaxSkills + 1;    // per env: S logit rows, then the critic (row kMaxSkills)
-
 // one uniform in (0, 1) of the skill draw: Philox4x32-10 keyed by (seed, global env, step), a stream of its own (the
 // action draw of mlp_head_out.hpp uses the tag 0x4D4C50, the Zone-goals goal draw 0x48474C).  zenv_collect_skill's
 // randint(0, S) draws on the tag 0x534B55 and its bootstrap skill s' on 0x534B42.
 __device__ __forceinline__ float skill_uniform(const SkillPick &pick, int env)
 {
-    const uint64_t g = pick.env_index0 + (uint64_t)env;
     const uint32_t tag = pick.mode == 2 ? 0x534B55u : pick.mode == 3 ? 0x534B42u : 0x534B4Cu;
-    uint32_t c[4] = { (uint32_t)g, (uint32_t)(g >> 32), pick.step_index, tag };
-    philox4x32_10(c, (uint32_t)pick.seed, (uint32_t)(pick.seed >> 32));
-    return ((float)(c[0] >> 8) + 0.5f) * 5.9604644775390625e-08f;
+    return philox_uniform(pick.seed, pick.env_index0 + (uint64_t)env, pick.step_index, tag);
 }
 
 __device__ __forceinline__ void skill_idle(int env, float *__restrict__ mu, float *__restrict__ stdv,
@@ -66,14 +59,6 @@ __device__ __forceinline__ void skill_idle(int env, float *__restrict__ mu, floa
     }
 }
 
-// sum_k w[k] x[k] + w[HP] over the h features (a row of the [.][HP + 1] layout)
-__device__ __forceinline__ float dot_row(const float *__restrict__ w, const float *__restrict__ x, int h)
-{
-    float s = w[HP];
-    for (int k = 0; k < h; ++k) s = __builtin_fmaf(w[k], x[k], s);
-    return s;
-}
-
 // LEVEL 0: HighPolicyValueModel -> out0 = log-softmax logits [N][S], out1 = value [N] (+ the skill pick)
 // LEVEL 1: LoPolicyValueModel   -> out0 = mu [N][2], out1 = std [N][2], out2 = value [N] (+ the action, the age)
 template <int LEVEL>
@@ -92,7 +77,6 @@ __global__ __launch_bounds__(HP) void k_skill_f32(SkillF32 w, DevParams p, Skill
     __shared__ int sel[EB];                             // the low level's skill column (-1: none)
     const int j = threadIdx.x;
     const int h = w.h, S = w.S;
-    const bool live = j < h;
     const int env0 = blockIdx.x * EB;
     const int n_env = min(EB, p.N - env0);
     const bool has_critic = LEVEL ? w.lo_critic : w.hi_critic;
@@ -142,60 +126,19 @@ __global__ __launch_bounds__(HP) void k_skill_f32(SkillF32 w, DevParams p, Skill
         encode_envs<8>(w.lo, p, xin, w.lo_w1s, w.lo_wcs, sel, env0, n_env, h, j, x0, y1, peb, va, vb);
 
     // ---- vb = emb: a = relu(actor.enc_.0.0(.)) -> va, relu(critic.0(.)) -> peb (the low level adds the skill column)
-    float t[EB], hv[EB];
-#pragma unroll
-    for (int e = 0; e < EB; ++e) hv[e] = 0.f;
-    if (has_critic) {
-        matvec(hv, LEVEL ? w.lv1t : w.hv1t, LEVEL ? w.lv1b : w.hv1b, vb, HP, h, j);
-        if (LEVEL == 1) add_column(hv, w.lv1s, sel, j);
-    }
-    matvec(t, LEVEL ? w.encw : w.hencw, LEVEL ? w.encb : w.hencb, vb, HP, h, j);
-    if (LEVEL == 1) add_column(t, w.encs, sel, j);
-    // (encode_envs ended with a barrier: nobody reads va / peb any more)
-#pragma unroll
-    for (int e = 0; e < EB; ++e) {
-        va[e * HP + j] = live ? fmaxf(t[e], 0.f) : 0.f;
-        peb[e * HP + j] = live ? fmaxf(hv[e], 0.f) : 0.f;
-    }
-    __syncthreads();
+    skill_hidden<LEVEL>(w, has_critic, sel, h, j, va, vb, peb);
 
     if (LEVEL == 0) {
-        // ---- one thread per (env, row): the S logits, then the critic
-        if (j < EB * SR) {
-            const int e = j / SR, r = j - e * SR;
-            float s = 0.f;
-            if (r < S) s = dot_row(w.hdisc + (size_t)r * (HP + 1), va + e * HP, h);
-            else if (r == kMaxSkills && has_critic) s = dot_row(w.hv2, peb + e * HP, h);
-            lg[j] = s;
-        }
-        __syncthreads();
+        skill_logit_rows(w, has_critic, h, j, va, peb, lg);
         if (j < n_env && on[j]) {
             const int env = env0 + j;
             const float *L = lg + j * SR;
             out1[env] = L[kMaxSkills];
-            // Categorical(logits=log_softmax(x)): x - max - log(sum exp(x - max))
-            float m = L[0];
-            int best = 0;
-            for (int s = 1; s < S; ++s)
-                if (L[s] > m) {                           // strict: ties go to the lowest skill
-                    m = L[s];
-                    best = s;
-                }
-            float sum = 0.f;
-            for (int s = 0; s < S; ++s) sum += expf(L[s] - m);
-            const float lse = logf(sum);
-            for (int s = 0; s < S; ++s) out0[(size_t)env * S + s] = (L[s] - m) - lse;
+            const Categorical cat = categorical(L, S, out0 + (size_t)env * S);
             if (pick.mode >= 0) {
-                int g = best;
+                int g = cat.best;
                 if (pick.mode == 1 || pick.mode == 3) {
-                    // inverse CDF of softmax(x) on one uniform, in skill order
-                    const float thr = skill_uniform(pick, env) * sum;
-                    float c = 0.f;
-                    for (int s = 0; s < S; ++s) {
-                        c += expf(L[s] - m);
-                        g = s;                            // the last skill takes what rounding leaves over
-                        if (c > thr) break;
-                    }
+                    g = categorical_draw(L, S, cat, skill_uniform(pick, env));
                 } else if (pick.mode == 2) {              // randint(0, S); the top uniform is exactly 1.0
                     g = min((int)(skill_uniform(pick, env) * (float)S), S - 1);
                 }
@@ -210,7 +153,7 @@ __global__ __launch_bounds__(HP) void k_skill_f32(SkillF32 w, DevParams p, Skill
                     const size_t row = (size_t)env * sr.W + sr.k;
                     sr.hi_skill[row] = g;
                     sr.hi_value[row] = L[kMaxSkills];
-                    sr.hi_log_prob[row] = (L[g] - m) - lse;
+                    sr.hi_log_prob[row] = (L[g] - cat.m) - cat.lse;
                 }
             }
         }
@@ -249,6 +192,7 @@ __global__ __launch_bounds__(256) void k_skill_sync(DevParams p, SkillState st, 
     if (st.epi[env] != k || (force && (!mask || mask[env]))) {
         st.skill[env] = -1;
         st.age[env] = 0;
+        st.ended[env] = 0;
         st.epi[env] = k;
     }
 }
@@ -261,6 +205,7 @@ __global__ __launch_bounds__(256) void k_skill_set(DevParams p, SkillState st)
     if (s < 0) return;
     st.skill[env] = s;
     st.age[env] = 0;
+    st.ended[env] = 0;
 }
 
 }  // namespace
@@ -323,7 +268,7 @@ struct Packer {
 
 }  // namespace
 
-size_t pack_skill_f32(const zenv_skill_weights &w, int F, std::vector<float> &out, size_t offs[kSkillPtrs])
+size_t pack_skill_f32(const zenv_skill_weights &w, int F, std::vector<float> &out, size_t offs[kSkillPtrs], int n_out)
 {
     const int h = w.h_dim, S = w.n_skills;
     Packer pk(out, h);
@@ -344,10 +289,10 @@ size_t pack_skill_f32(const zenv_skill_weights &w, int F, std::vector<float> &ou
     offs[i++] = pk.cols(w.lo_enc_w, h + S, 0, h, HP);
     offs[i++] = pk.cols(w.lo_enc_w, h + S, h, S, S);
     offs[i++] = pk.bias(w.lo_enc_b);
-    offs[i] = pk.put(4 * (size_t)(HP + 1));                 // mu_ rows 0-1, std_ rows 2-3
-    for (int r = 0; r < 4; ++r) {
-        const float *W = r < 2 ? w.lo_mu_w + (size_t)r * h : w.lo_std_w + (size_t)(r - 2) * h;
-        const float *b = r < 2 ? w.lo_mu_b + r : w.lo_std_b + (r - 2);
+    offs[i] = pk.put(2 * n_out * (size_t)(HP + 1));         // the n_out rows of mu_, then those of std_
+    for (int r = 0; r < 2 * n_out; ++r) {
+        const float *W = r < n_out ? w.lo_mu_w + (size_t)r * h : w.lo_std_w + (size_t)(r - n_out) * h;
+        const float *b = r < n_out ? w.lo_mu_b + r : w.lo_std_b + (r - n_out);
         for (int k = 0; k < h; ++k) out[offs[i] + (size_t)r * (HP + 1) + k] = W[k];
         out[offs[i] + (size_t)r * (HP + 1) + HP] = b[0];
     }

@@ -39,8 +39,10 @@ static_assert(sizeof(SkillF32) == 4 * sizeof(int) + kSkillPtrs * sizeof(const fl
 
 // Host packer: the float32 state_dict tensors of zenv_skill_weights -> one buffer; offs[] = offsets in floats of the
 // pointers of SkillF32 in declaration order, 0 for an absent critic (the image starts with 4 floats of padding, so that
-// no tensor sits at offset 0).  skill_f32_at() binds such an image to its device address.
-size_t pack_skill_f32(const zenv_skill_weights &w, int F, std::vector<float> &out, size_t offs[kSkillPtrs]);
+// no tensor sits at offset 0).  skill_f32_at() binds such an image to its device address.  n_out: the rows of
+// lo_mu_w / lo_std_w, 2 (the action) or 3 (the Options agent's, option_f32.hpp: `heads` is then [6][HP + 1]).
+size_t pack_skill_f32(const zenv_skill_weights &w, int F, std::vector<float> &out, size_t offs[kSkillPtrs],
+                      int n_out = 2);
 SkillF32 skill_f32_at(const zenv_skill_weights &w, const float *base, const size_t offs[kSkillPtrs]);
 
 // The per-env skill state, [N] each: skill (-1 = none), age (low-level steps under it), epi (the episode index,
@@ -48,6 +50,8 @@ SkillF32 skill_f32_at(const zenv_skill_weights &w, const float *base, const size
 struct SkillState {
     int32_t *skill, *age, *epi;
     int32_t *in;                   // [N] staging of zenv_set_skills
+    int32_t *ended;                // [N] the Options agent's flag (option_f32.hpp): 1 = the skill's option ended on the
+                                   // last policy call, the env picks on the next; cleared wherever the skill is
 };
 // What zenv_collect_skill (skill_collect.hip) records besides the kernels' outputs, at frame t of T, N envs:
 //   high level, at the first frame of window k (of W = T / L): row env * W + k of the env-major hi rows -- the obs and
@@ -81,9 +85,9 @@ hipError_t launch_skill_high(const SkillF32 &w, const DevParams &p, const SkillS
 // without a skill gets mu = std = value = 0 (and action 0).
 hipError_t launch_skill_low(const SkillF32 &w, const DevParams &p, const SkillState &st, float *mu, float *stdv,
                             float *value, const MlpAction &act, hipStream_t s, const SkillRecord *rec = nullptr);
-// Clear (skill -1, age 0) every env whose episode index moved on, and with force also those in mask (null = all).
+// Clear (skill -1, age 0, not ended) every env whose episode index moved on, and with force also those in mask (null = all).
 hipError_t launch_skill_sync(const DevParams &p, const SkillState &st, const uint8_t *mask, int force, hipStream_t s);
-// st.in -> skill, age 0 for every env whose entry is >= 0
+// st.in -> skill, age 0, not ended for every env whose entry is >= 0
 hipError_t launch_skill_set(const DevParams &p, const SkillState &st, hipStream_t s);
 
 // ---- zenv_collect_skill (skill_collect.hip)

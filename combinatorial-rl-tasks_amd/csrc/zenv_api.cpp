@@ -22,6 +22,7 @@
 #include "host_sampler.hpp"
 #include "kernels.hpp"
 #include "hier_f32.hpp"
+#include "option_f32.hpp"
 #include "skill_f32.hpp"
 #include "mlp_policy.hpp"
 
@@ -117,6 +118,13 @@ struct zenv {
     SkillState sst{};
     void *sst_mem = nullptr;
     float *skill_logits = nullptr, *skill_value = nullptr;
+    // variable-length Options agent (zenv_option_load): it takes the place of the skill agent on the handle -- its
+    // weights live in skill_mem / skill, the state in sst -- plus the picking envs' list and the third output's fields
+    bool option_ready = false;
+    int option_compact = 0;
+    void *opt_mem = nullptr;
+    OptionList olist{};
+    OptionTerm oterm{};
     // DIAYN's discriminator (zenv_skill_inverse_load) and the per-frame records of zenv_collect_skill (T frames):
     // lo_skill, diversity, env_reward [T][N]; the bootstrap skill and the row count [N]
     void *skinv_mem = nullptr;
@@ -355,6 +363,11 @@ FieldInfo field_info(const zenv *h, int field)
     case ZENV_F_LO_SKILL: return { h->sk.lo_skill, h->sk_mem ? N * h->sk.T * 4 : 0 };
     case ZENV_F_LO_DIVERSITY: return { h->sk.diversity, h->sk_mem ? N * h->sk.T * 4 : 0 };
     case ZENV_F_SKILL_BOOTSTRAP: return { h->sk.boot, h->sk_mem ? N * 4 : 0 };
+    case ZENV_F_OPTION_TERM_MU: return { h->oterm.mu, h->opt_mem ? N * 4 : 0 };
+    case ZENV_F_OPTION_TERM_STD: return { h->oterm.stdv, h->opt_mem ? N * 4 : 0 };
+    case ZENV_F_OPTION_TERM_ACTION: return { h->oterm.action, h->opt_mem ? N * 4 : 0 };
+    case ZENV_F_OPTION_TERM_PROB: return { h->oterm.prob, h->opt_mem ? N * 4 : 0 };
+    case ZENV_F_OPTION_ENDED: return { h->sst.ended, h->opt_mem ? N * 4 : 0 };   // (refresh_field() first)
     default: return { nullptr, 0 };
     }
 }
@@ -364,7 +377,7 @@ FieldInfo field_info(const zenv *h, int field)
 // nothing of skills, an auto-reset shows as a new episode index (k_skill_sync).
 int refresh_field(zenv *h, int field)
 {
-    if (field == ZENV_F_SKILL || field == ZENV_F_SKILL_AGE) {
+    if (field == ZENV_F_SKILL || field == ZENV_F_SKILL_AGE || field == ZENV_F_OPTION_ENDED) {
         if (h->sst_mem) HIP_TRY(launch_skill_sync(h->p, h->sst, nullptr, 0, h->stream));
         return ZENV_OK;
     }
@@ -656,7 +669,7 @@ extern "C" int zenv_destroy(zenv_t *h)
                      (void *)h->goal_in, (void *)h->goal_bad, h->exp_mem, (void *)h->p.order_pos,
                      (void *)h->p.order_val, h->hier_mem, (void *)h->hier_logits, (void *)h->hier_value,
                      h->hframes_mem, h->hcarry_mem, h->hout_mem, h->skill_mem, h->sst_mem, (void *)h->skill_logits,
-                     (void *)h->skill_value, h->skinv_mem, h->sk_mem })
+                     (void *)h->skill_value, h->skinv_mem, h->sk_mem, h->opt_mem })
         if (m) (void)hipFree(m);
     for (hipEvent_t ev : h->events) (void)hipEventDestroy(ev);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
@@ -1398,9 +1411,9 @@ static int run_hier_policy(zenv_t *h, int policy, uint32_t step_index, uint64_t 
 }
 
 // ============================================================================ fixed-length-skills agent
-extern "C" int zenv_skill_load(zenv_t *h, const zenv_skill_weights *w)
+// zenv_skill_load (n_out = 2) and zenv_option_load (n_out = 3: the rows of lo_mu_w / lo_std_w)
+static int load_skill_family(zenv_t *h, const zenv_skill_weights *w, int n_out)
 {
-    if (!h || !w) return fail(ZENV_E_ARG, "null argument");
     if (h->goal_enabled || h->order_enabled)
         return fail(ZENV_E_STATE, "the skill agent steps a plain task handle, not a goal-conditioned / solver-ordered one");
     if (w->h_dim < 1 || w->h_dim >= kMlpHP) return fail(ZENV_E_ARG, "h_dim %d outside 1 .. %d", w->h_dim, kMlpHP - 1);
@@ -1415,7 +1428,7 @@ extern "C" int zenv_skill_load(zenv_t *h, const zenv_skill_weights *w)
                             w->lo_zone_w1, w->lo_zone_b1, w->lo_zone_w2, w->lo_zone_b2, w->lo_zone_w3, w->lo_zone_b3,
                             w->lo_comb_w, w->lo_comb_b, w->lo_enc_w, w->lo_enc_b, w->lo_mu_w, w->lo_mu_b, w->lo_std_w,
                             w->lo_std_b })
-        if (!t) return fail(ZENV_E_ARG, "zenv_skill_weights has a null actor tensor");
+        if (!t) return fail(ZENV_E_ARG, "the weights have a null actor tensor");
     const int n_hc = (w->hi_critic_w1 != nullptr) + (w->hi_critic_b1 != nullptr) + (w->hi_critic_w2 != nullptr) +
                      (w->hi_critic_b2 != nullptr);
     const int n_lc = (w->lo_critic_w1 != nullptr) + (w->lo_critic_b1 != nullptr) + (w->lo_critic_w2 != nullptr) +
@@ -1424,12 +1437,12 @@ extern "C" int zenv_skill_load(zenv_t *h, const zenv_skill_weights *w)
         return fail(ZENV_E_ARG, "give all four tensors of a critic or none");
     std::vector<float> img;
     size_t o[kSkillPtrs];
-    pack_skill_f32(*w, h->p.F, img, o);
+    pack_skill_f32(*w, h->p.F, img, o, n_out);
     int rc = use_device(h);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     const size_t N = (size_t)h->n_env, S = (size_t)w->n_skills;
-    h->skill_ready = false;
+    h->skill_ready = h->option_ready = false;           // a handle holds one agent of the skill family
     if (h->skill_mem) HIP_TRY(hipFree(h->skill_mem));
     h->skill_mem = nullptr;
     HIP_TRY(hipMalloc(&h->skill_mem, img.size() * sizeof(float)));
@@ -1446,18 +1459,32 @@ extern "C" int zenv_skill_load(zenv_t *h, const zenv_skill_weights *w)
     h->skill_n = (int)S;
     if (!h->skill_value) HIP_TRY(hipMalloc((void **)&h->skill_value, N * sizeof(float)));
     if (!h->sst_mem) {
-        HIP_TRY(hipMalloc(&h->sst_mem, 4 * N * sizeof(int32_t)));
+        HIP_TRY(hipMalloc(&h->sst_mem, 5 * N * sizeof(int32_t)));
         int32_t *m = static_cast<int32_t *>(h->sst_mem);
-        h->sst = SkillState{ m, m + N, m + 2 * N, m + 3 * N };
+        h->sst = SkillState{ m, m + N, m + 2 * N, m + 3 * N, m + 4 * N };
     }
+    if (n_out == 3 && !h->opt_mem) {
+        HIP_TRY(hipMalloc(&h->opt_mem, (5 * N + 1) * 4));
+        float *m = static_cast<float *>(h->opt_mem);
+        h->oterm = OptionTerm{ m, m + N, m + 2 * N, m + 3 * N };
+        h->olist.list = reinterpret_cast<int32_t *>(m + 4 * N);
+        h->olist.count = h->olist.list + N;
+    }
+    if (h->opt_mem) HIP_TRY(hipMemsetAsync(h->opt_mem, 0, (5 * N + 1) * 4, h->stream));
     HIP_TRY(hipMemsetAsync(h->skill_logits, 0, N * S * sizeof(float), h->stream));
     HIP_TRY(hipMemsetAsync(h->skill_value, 0, N * sizeof(float), h->stream));
     HIP_TRY(launch_skill_sync(h->p, h->sst, nullptr, 1, h->stream));     // every env: no skill (the new S may be smaller)
     h->skill = skill_f32_at(*w, static_cast<const float *>(h->skill_mem), o);
     HIP_TRY(hipStreamSynchronize(h->stream));
-    h->skill_ready = true;
-    if (h->skinv_ready && (h->skinv.h != w->h_dim || h->skinv.S != w->n_skills)) h->skinv_ready = false;
+    (n_out == 3 ? h->option_ready : h->skill_ready) = true;
+    if (n_out == 3 || (h->skinv_ready && (h->skinv.h != w->h_dim || h->skinv.S != w->n_skills))) h->skinv_ready = false;
     return ZENV_OK;
+}
+
+extern "C" int zenv_skill_load(zenv_t *h, const zenv_skill_weights *w)
+{
+    if (!h || !w) return fail(ZENV_E_ARG, "null argument");
+    return load_skill_family(h, w, 2);
 }
 
 extern "C" int zenv_skill_inverse_load(zenv_t *h, const zenv_skill_inverse_weights *w)
@@ -1499,7 +1526,7 @@ extern "C" int zenv_skill_configure(zenv_t *h, int skill_len)
 extern "C" int zenv_set_skills(zenv_t *h, const int32_t *skills)
 {
     if (!h || !skills) return fail(ZENV_E_ARG, "null argument");
-    if (!h->skill_ready) return fail(ZENV_E_STATE, "zenv_skill_load first");
+    if (!h->skill_ready && !h->option_ready) return fail(ZENV_E_STATE, "zenv_skill_load or zenv_option_load first");
     for (int i = 0; i < h->n_env; ++i)
         if (skills[i] < -1 || skills[i] >= h->skill_n)
             return fail(ZENV_E_ARG, "env %d: skill %d outside -1 .. %d", i, skills[i], h->skill_n - 1);
@@ -1537,6 +1564,53 @@ static int run_skill_policy(zenv_t *h, int policy, uint32_t step_index, uint64_t
     HIP_TRY(launch_skill_high(h->skill, h->p, h->sst, h->skill_logits, h->skill_value, pick, h->stream));
     const MlpAction act{ mode, step_index, seed, env_index0, out, MlpRecord{} };
     HIP_TRY(launch_skill_low(h->skill, h->p, h->sst, h->mlp_mu, h->mlp_std, h->mlp_value, act, h->stream));
+    return ZENV_OK;
+}
+
+// ============================================================================ variable-length Options agent
+extern "C" int zenv_option_load(zenv_t *h, const zenv_option_weights *w)
+{
+    if (!h || !w) return fail(ZENV_E_ARG, "null argument");
+    // the same members in the same order: only the rows of lo_mu_* / lo_std_* differ
+    static_assert(sizeof(zenv_option_weights) == sizeof(zenv_skill_weights), "zenv_option_weights layout");
+    zenv_skill_weights sw;
+    std::memcpy(&sw, w, sizeof sw);
+    int rc = load_skill_family(h, &sw, 3);
+    if (rc) return rc;
+    // diagnostic: how the high level finds the envs that pick; the results are the same
+    const char *e = std::getenv("ZENV_OPTION_COMPACT");
+    h->option_compact = e ? std::atoi(e) != 0 : h->n_env > kOptionCompactMinEnvs;
+    return ZENV_OK;
+}
+
+extern "C" int zenv_option_forward(zenv_t *h)
+{
+    if (!h) return fail(ZENV_E_ARG, "null handle");
+    if (!h->option_ready) return fail(ZENV_E_STATE, "zenv_option_load first");
+    if (!h->was_reset) return fail(ZENV_E_STATE, "reset before asking for actions");
+    int rc = use_device(h);
+    if (rc) return rc;
+    HIP_TRY(launch_skill_sync(h->p, h->sst, nullptr, 0, h->stream));
+    const OptionPick none{ -1, 0, 0u, 0ull, 0ull };
+    HIP_TRY(launch_option_high(h->skill, h->p, h->sst, h->olist, h->skill_logits, h->skill_value, none, h->stream));
+    HIP_TRY(launch_option_low(h->skill, h->p, h->sst, h->olist, h->mlp_mu, h->mlp_std, h->mlp_value, h->oterm,
+                              no_mlp_action(), h->stream));
+    return ZENV_OK;
+}
+
+// one step of options/scripts/evaluate_hier.py:63-75: a skill for the envs that have none or whose option ended, then
+// the low level's action of every env into `out` and the termination draw
+static int run_option_policy(zenv_t *h, int policy, uint32_t step_index, uint64_t seed, uint64_t env_index0, float *out)
+{
+    if (!h->option_ready) return fail(ZENV_E_STATE, "zenv_option_load first");
+    const int mode = policy == ZENV_POLICY_OPTION_SAMPLE ? 1 : 0;
+    HIP_TRY(launch_skill_sync(h->p, h->sst, nullptr, 0, h->stream));
+    const OptionPick pick{ mode, h->option_compact, step_index, seed, env_index0 };
+    if (pick.compact) HIP_TRY(launch_option_list(h->p, h->sst, h->olist, h->stream));
+    HIP_TRY(launch_option_high(h->skill, h->p, h->sst, h->olist, h->skill_logits, h->skill_value, pick, h->stream));
+    const MlpAction act{ mode, step_index, seed, env_index0, out, MlpRecord{} };
+    HIP_TRY(launch_option_low(h->skill, h->p, h->sst, h->olist, h->mlp_mu, h->mlp_std, h->mlp_value, h->oterm, act,
+                              h->stream));
     return ZENV_OK;
 }
 
@@ -1978,7 +2052,8 @@ extern "C" int zenv_policy(zenv_t *h, int policy, uint64_t policy_seed, uint64_t
     if (!h->was_reset) return fail(ZENV_E_STATE, "reset before asking for actions");
     const bool hier = policy == ZENV_POLICY_HIER_SAMPLE || policy == ZENV_POLICY_HIER_MEAN;
     const bool skill = policy == ZENV_POLICY_SKILL_SAMPLE || policy == ZENV_POLICY_SKILL_MEAN;
-    if (!policy_known(policy) && !hier && !skill) return fail(ZENV_E_ARG, "unknown policy %d", policy);
+    const bool option = policy == ZENV_POLICY_OPTION_SAMPLE || policy == ZENV_POLICY_OPTION_MEAN;
+    if (!policy_known(policy) && !hier && !skill && !option) return fail(ZENV_E_ARG, "unknown policy %d", policy);
     int rc = use_device(h);
     if (rc) return rc;
     const StepPolicy pol{ policy, (uint32_t)h->step_count, policy_seed, env_index0,
@@ -1986,6 +2061,7 @@ extern "C" int zenv_policy(zenv_t *h, int policy, uint64_t policy_seed, uint64_t
     h->act_tag.valid = false;
     if (hier) return run_hier_policy(h, policy, pol.step_index, policy_seed, env_index0, pol.out);
     if (skill) return run_skill_policy(h, policy, pol.step_index, policy_seed, env_index0, pol.out);
+    if (option) return run_option_policy(h, policy, pol.step_index, policy_seed, env_index0, pol.out);
     return run_policy(h, pol);
 }
 
@@ -2382,7 +2458,8 @@ extern "C" int zenv_device_ptr(zenv_t *h, int field, void **ptr)
     if (!h || !ptr) return fail(ZENV_E_ARG, "null argument");
     const FieldInfo f = field_info(h, field);
     if (!f.ptr) return fail(ZENV_E_ARG, "unknown field %d", field);
-    if (field == ZENV_F_EP_RETURN || field == ZENV_F_EP_LEN || field == ZENV_F_SKILL || field == ZENV_F_SKILL_AGE) {
+    if (field == ZENV_F_EP_RETURN || field == ZENV_F_EP_LEN || field == ZENV_F_SKILL || field == ZENV_F_SKILL_AGE ||
+        field == ZENV_F_OPTION_ENDED) {
         // these two live inside the step kernels' records: the pointer is to a plain copy brought up to date by THIS
         // call (stream-ordered), not a live view
         int rc = use_device(h);

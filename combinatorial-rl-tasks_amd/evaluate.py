@@ -4,7 +4,8 @@
 result layout ``{"return": [[r_run0..r_run4] for each map]}`` -- but all maps and runs are
 stepped together as one batch of n_maps*n_runs envs instead of 500 sequential episodes.
 ``evaluate_zone_hrl`` does the same for zone-goals/scripts/evaluate_zone_hrl.py with the Zone-goals hierarchical agent,
-``evaluate_hier`` for main/scripts/evaluate_hier.py with the fixed-length-skills agent.
+``evaluate_hier`` for main/scripts/evaluate_hier.py with the fixed-length-skills agent, ``evaluate_options`` for
+options/scripts/evaluate_hier.py with the variable-length Options agent.
 """
 import pickle
 
@@ -189,6 +190,58 @@ def evaluate_hier(env_id, model, n_maps=100, n_runs_per_map=5, n_skills=None, sk
             "return": env.get(nat.F_LAST_RETURN).reshape(n_maps, n_runs_per_map).tolist(),
             "length": env.get(nat.F_LAST_LEN).reshape(n_maps, n_runs_per_map).tolist(),
             "goal_met": goal.reshape(n_maps, n_runs_per_map).tolist(),
+        }
+    finally:
+        env.close()
+    if pkl_path:
+        with open(pkl_path, "wb") as f:
+            pickle.dump({"return": out["return"]}, f)
+    return out
+
+
+def evaluate_options(env_id, model, n_maps=100, n_runs_per_map=1, n_skills=None, policy_seed=0, argmax=False,
+                     pkl_path=None, device=0, max_steps=None, env_seed0=EVAL_SEED0):
+    """The protocol of options/scripts/evaluate_hier.py (100 maps x 1 run, env seeds 1000000.., undiscounted return)
+    with the variable-length Options agent on the device, every map and run stepped together as one batch.  Per step
+    (:63-75): an env without a skill -- the episode's first step, or the last option ended -- has HighPolicyValueModel
+    pick one (a draw from Categorical, or the argmax with ``argmax=True``); LoPolicyValueModel acts under it
+    (``dist.sample()``, or mu); the option ends with probability sigmoid(4 a_2 - 3), a_2 the sample's third component
+    (with ``argmax=True``: iff that probability of mu_2 exceeds 0.5).
+
+    env_id, model, n_skills: as ``evaluate_hier`` (the script builds HierAgent with 5 skills).
+    Returns ``{"return": [[...]], "length": [[...]], "goal_met": [[...]], "terminations": [[...]]}`` -- terminations:
+    how many options ended during the episode -- and writes ``{"return": ...}`` to ``pkl_path`` (:45, :88-90)."""
+    from .vec_env import option_tensors_from_state_dicts
+    cfg = config_for_id(env_id) if isinstance(env_id, str) else env_id
+    hi_sd, lo_sd = load_hier_model_state(model) if isinstance(model, str) else model
+    tensors = option_tensors_from_state_dicts(hi_sd, lo_sd)
+    S = tensors["hi_logit_w"].shape[0]
+    if n_skills is not None and n_skills != S:
+        raise ValueError(f"n_skills={n_skills}, but the checkpoint's high level has {S} skills")
+    n = n_maps * n_runs_per_map
+    env = ZoneVecEnv(cfg, n, device=device)
+    try:
+        env.build_bank(env_seed0, n_maps)
+        env.schedule_sequential(first=np.repeat(np.arange(n_maps, dtype=np.int32), n_runs_per_map), stride=0)
+        env.reset()
+        env.load_options(tensors)
+        policy = nat.POLICY_OPTION_MEAN if argmax else nat.POLICY_OPTION_SAMPLE
+        goal = np.zeros(n, bool)
+        ended = np.zeros(n, np.int64)
+        horizon = cfg.num_steps if max_steps is None else max_steps
+        for t in range(horizon):
+            env.policy(policy, policy_seed=policy_seed)
+            ended += env.get(nat.F_OPTION_ENDED)      # 0 for an env that has finished
+            env.step(None, auto_reset=False)
+            _, _, _, d, g, _ = env.step_results(None, copy=False)
+            goal |= g
+            if d.all():                    # every episode finished (evaluate_hier.py:76-85)
+                break
+        out = {
+            "return": env.get(nat.F_LAST_RETURN).reshape(n_maps, n_runs_per_map).tolist(),
+            "length": env.get(nat.F_LAST_LEN).reshape(n_maps, n_runs_per_map).tolist(),
+            "goal_met": goal.reshape(n_maps, n_runs_per_map).tolist(),
+            "terminations": ended.reshape(n_maps, n_runs_per_map).tolist(),
         }
     finally:
         env.close()

@@ -29,7 +29,8 @@ _FIELD_DTYPES = {
     nat.F_HI_ADVANTAGE: np.float32, nat.F_HI_RETURN: np.float32, nat.F_HI_REWARD: np.float32, nat.F_HI_MASK: np.float32,
     nat.F_HI_COUNT: np.int32, nat.F_SKILL: np.int32, nat.F_SKILL_AGE: np.int32, nat.F_SKILL_LOGITS: np.float32,
     nat.F_SKILL_VALUE: np.float32, nat.F_LO_SKILL: np.int32, nat.F_LO_DIVERSITY: np.float32,
-    nat.F_SKILL_BOOTSTRAP: np.int32,
+    nat.F_SKILL_BOOTSTRAP: np.int32, nat.F_OPTION_TERM_MU: np.float32, nat.F_OPTION_TERM_STD: np.float32,
+    nat.F_OPTION_TERM_ACTION: np.float32, nat.F_OPTION_TERM_PROB: np.float32, nat.F_OPTION_ENDED: np.int32,
 }
 
 
@@ -200,15 +201,42 @@ def skill_tensor_shapes(h, S, F):
     return dict({"hi_" + k: v for k, v in hi.items()}, **{"lo_" + k: v for k, v in lo.items()})
 
 
+def option_tensor_shapes(h, S, F):
+    """The shape of every zenv_option_weights tensor: ``skill_tensor_shapes`` with three rows in lo_mu_* / lo_std_*."""
+    return dict(skill_tensor_shapes(h, S, F), lo_mu_w=(3, h), lo_mu_b=(3,), lo_std_w=(3, h), lo_std_b=(3,))
+
+
+def option_tensors_from_state_dicts(hi_sd, lo_sd):
+    """HighPolicyValueModel.state_dict() and LoPolicyValueModel.state_dict() of the variable-length Options agent
+    (options/src/hier_policy_value_models.py) -> the tensors ``ZoneVecEnv.load_options`` wants (numpy float32, names of
+    ``_native.SKILL_*``).  h, S and F come from the shapes; the critics are taken when present.  A skill planner's
+    checkpoint (actor.mu_ / actor.std_ of two rows), a Zone-goals checkpoint, a missing key or a tensor whose shape
+    does not fit the others raises ValueError naming it."""
+    return _skill_family_tensors(hi_sd, lo_sd, 3)
+
+
 def skill_tensors_from_state_dicts(hi_sd, lo_sd):
     """HighPolicyValueModel.state_dict() and LoPolicyValueModel.state_dict() of the fixed-length-skills agent -> the
     tensors ``ZoneVecEnv.load_skills`` wants (numpy float32, names of ``_native.SKILL_*``).  The hidden size h and the
     number of skills S come from the shapes (actor.discrete_.0 is [S, h]).  The critics are taken when present.  A
     Zone-goals checkpoint (the same hi_model_state / lo_model_state keys, an actor.0 / actor.2 high level), a missing
     key or a tensor whose shape does not fit the others raises ValueError naming it."""
+    return _skill_family_tensors(hi_sd, lo_sd, 2)
+
+
+def _skill_family_tensors(hi_sd, lo_sd, n_out):
+    """n_out: the rows of the low level's actor.mu_ / actor.std_ -- 2: a skill planner's, 3: an Options agent's."""
+    kind = "a skill planner's" if n_out == 2 else "an Options agent's"
     if "actor.0.weight" in hi_sd or "actor.2.weight" in hi_sd:
         raise ValueError("hi_model_state has 'actor.0' / 'actor.2': a Zone-goals checkpoint (load it with "
-                         "hier_tensors_from_state_dicts / load_hier), not a skill planner's")
+                         f"hier_tensors_from_state_dicts / load_hier), not {kind}")
+    mu = lo_sd.get("actor.mu_.weight")
+    if n_out == 3 and mu is not None and tuple(mu.shape)[:1] == (2,):
+        raise ValueError("lo_model_state['actor.mu_.weight'] has 2 rows: a skill planner's checkpoint (load it with "
+                         "skill_tensors_from_state_dicts / load_skills), not an Options agent's")
+    if n_out == 2 and mu is not None and tuple(mu.shape)[:1] == (3,):
+        raise ValueError("lo_model_state['actor.mu_.weight'] has 3 rows: an Options agent's checkpoint (load it with "
+                         "option_tensors_from_state_dicts / load_options), not a skill planner's")
     out = {}
     for level, sd, keys in (("hi", hi_sd, SKILL_HI_KEYS), ("lo", lo_sd, SKILL_LO_KEYS)):
         names = dict(keys)
@@ -222,7 +250,7 @@ def skill_tensors_from_state_dicts(hi_sd, lo_sd):
     logit = out["hi_logit_w"]
     h, S = (logit.shape[1], logit.shape[0]) if logit.ndim == 2 else (-1, -1)
     F = out["hi_zone_w1"].shape[1] - 8 if out["hi_zone_w1"].ndim == 2 else -1
-    want = skill_tensor_shapes(h, S, F)
+    want = (skill_tensor_shapes if n_out == 2 else option_tensor_shapes)(h, S, F)
     for name, a in out.items():
         if a.shape != want[name]:
             level, rest = name.split("_", 1)
@@ -760,6 +788,44 @@ class ZoneVecEnv:
         check(lib().zenv_skill_forward(self._h))
         return (self.get(nat.F_SKILL_LOGITS), self.get(nat.F_SKILL_VALUE), self.get(nat.F_POLICY_MU),
                 self.get(nat.F_POLICY_STD), self.get(nat.F_POLICY_VALUE))
+
+    # ------------------------------------------------------------------ variable-length Options agent
+    def load_options(self, tensors, precision="f32"):
+        """HighPolicyValueModel + LoPolicyValueModel of the Options agent (options/src/hier_policy_value_models.py) for
+        ``option_forward`` and the device policies POLICY_OPTION_SAMPLE / POLICY_OPTION_MEAN, which pick a new skill
+        whenever the last one's option ended (options/scripts/evaluate_hier.py:63-75).  tensors: dict of float32 arrays
+        named as in ``_native.SKILL_*`` with three rows in lo_mu_* / lo_std_* (see ``option_tensors_from_state_dicts``);
+        each critic is optional.  A plain task handle only.  A handle holds one agent of the skill family: this drops
+        loaded skill (and inverse) weights, ``load_skills`` drops these.  Every env starts without a skill."""
+        if precision != "f32":
+            raise ValueError(f"precision {precision!r}: the Options agent is built in float32 only")
+        logit = np.asarray(tensors["hi_logit_w"])
+        S, h = int(logit.shape[0]), int(logit.shape[1])
+        F = int(np.asarray(tensors["hi_zone_w1"]).shape[1]) - 8
+        want = option_tensor_shapes(h, S, F)
+        names = nat.SKILL_HI_TENSORS + nat.SKILL_LO_TENSORS + (
+            nat.SKILL_HI_CRITIC if "hi_critic_w1" in tensors else ()) + (
+            nat.SKILL_LO_CRITIC if "lo_critic_w1" in tensors else ())
+        w = nat.OptionWeights(h_dim=h, n_skills=S, zone_feat=F, precision=nat.MLP_F32)
+        keep = {}
+        for name in names:
+            a = np.ascontiguousarray(tensors[name], np.float32)
+            if a.shape != want[name]:
+                raise ValueError(f"{name}: shape {a.shape}, expected {want[name]}")
+            keep[name] = a
+            setattr(w, name, a.ctypes.data)
+        check(lib().zenv_option_load(self._h, C.byref(w)))
+        self._skill_inverse = False
+        self._skill_n, self._skill_h = S, h
+
+    def option_forward(self):
+        """Both networks on the current observations, the state untouched: ``skill_forward``'s five arrays (log-softmax
+        logits [N,S], high-level value [N], mu [N,2], std [N,2], low-level value [N]) and the third actor output as
+        (mu_2, std_2, prob = sigmoid(4 mu_2 - 3)), float32 [N] each; zeros for an env without a skill."""
+        check(lib().zenv_option_forward(self._h))
+        return (self.get(nat.F_SKILL_LOGITS), self.get(nat.F_SKILL_VALUE), self.get(nat.F_POLICY_MU),
+                self.get(nat.F_POLICY_STD), self.get(nat.F_POLICY_VALUE), self.get(nat.F_OPTION_TERM_MU),
+                self.get(nat.F_OPTION_TERM_STD), self.get(nat.F_OPTION_TERM_PROB))
 
     def load_skill_inverse(self, tensors, precision="f32"):
         """InverseModel, DIAYN's discriminator (main/src/inverse_model.py), for the diversity reward of

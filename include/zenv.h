@@ -134,7 +134,17 @@ enum {
     ZENV_F_LO_SKILL = 55,        /* int32   [T,N]    the skill the low level acted under at every frame */
     ZENV_F_LO_DIVERSITY = 56,    /* float32 [T,N]    DIAYN's diversity reward (0 everywhere without inverse weights) */
     ZENV_F_SKILL_BOOTSTRAP = 57, /* int32   [N]      s' ~ the high level at obs_T: the skill of next_lo_value */
-    ZENV_F_COUNT = 58
+    /* variable-length Options agent (zenv_option_load; before these five fields, ZENV_F_COUNT = 58): the third actor
+     * output of the last zenv_policy(ZENV_POLICY_OPTION_*) / zenv_option_forward, 0 for an env that idled.  The agent
+     * shares ZENV_F_SKILL / _SKILL_AGE / _SKILL_LOGITS / _SKILL_VALUE with the fixed-length-skills agent */
+    ZENV_F_OPTION_TERM_MU = 58,     /* float32 [N]   mu_2 */
+    ZENV_F_OPTION_TERM_STD = 59,    /* float32 [N]   std_2 */
+    ZENV_F_OPTION_TERM_ACTION = 60, /* float32 [N]   a_2: the sampled (unclipped) third component, or mu_2 */
+    ZENV_F_OPTION_TERM_PROB = 61,   /* float32 [N]   sigmoid(4 a_2 - 3) */
+    ZENV_F_OPTION_ENDED = 62,       /* int32   [N]   1 = the env's option ended on the last policy call: it picks a new
+                                     *               skill on the next.  Cleared wherever the skill state is (a reset,
+                                     *               zenv_set_skills); brought up to date like ZENV_F_SKILL */
+    ZENV_F_COUNT = 63
 };
 
 /* scripted on-device action sources (the build's own; used by bench/tests) */
@@ -150,7 +160,11 @@ enum {
     /* the fixed-length-skills agent (zenv_skill_load; plain task handles only), see zenv_skill_forward */
     ZENV_POLICY_SKILL_SAMPLE = 6, /* skill ~ Categorical(logits) every skill_len steps, a ~ Normal(mu, std): HierAgent.
                                    * get_hi_action / get_lo_action (main/src/utils/hier_agent.py) */
-    ZENV_POLICY_SKILL_MEAN = 7    /* skill = argmax (ties: lowest skill), a = mu: deterministic */
+    ZENV_POLICY_SKILL_MEAN = 7,   /* skill = argmax (ties: lowest skill), a = mu: deterministic */
+    /* the variable-length Options agent (zenv_option_load; plain task handles only), see zenv_option_forward */
+    ZENV_POLICY_OPTION_SAMPLE = 8, /* skill ~ Categorical(logits) when the last option ended, (a, a_2) ~ Normal(mu, std),
+                                    * the option ends with probability sigmoid(4 a_2 - 3) */
+    ZENV_POLICY_OPTION_MEAN = 9    /* skill = argmax, a = mu, the option ends iff sigmoid(4 mu_2 - 3) > 0.5 */
 };
 
 /* kernel layouts */
@@ -542,6 +556,66 @@ int zenv_set_skills(zenv_t *h, const int32_t *skills);
  * streams for the skill and the action draw.  No host synchronisation.  zenv_rollout() refuses these policies
  * (ZENV_E_ARG); zenv_collect() takes none (it runs the flat network). */
 int zenv_skill_forward(zenv_t *h);
+
+/* ---- the variable-length Options agent on the device ----
+ * HighPolicyValueModel and LoPolicyValueModel of options/src/hier_policy_value_models.py with the per-step loop of
+ * options/scripts/evaluate_hier.py:55-84.  The networks are the skill planner's above, except that the low level's
+ * PolicyNetwork has action_dim + 1 = 3 outputs: the third component of its sample decides whether the skill ends.
+ * There is no skill_len.  Checkpoint: status.pt's hi_model_state / lo_model_state.
+ * The members, their shapes and their checks are zenv_skill_weights' (h 1 .. 191, S 1 .. 32, ZENV_MLP_F32 only, plain
+ * task handles only, each critic optional), except for the four tensors marked below. */
+typedef struct zenv_option_weights {
+    int32_t h_dim;                        /* 1 .. 191 */
+    int32_t n_skills;                     /* S: 1 .. 32 */
+    int32_t zone_feat;                    /* F the weights were built for (the handle's zenv_zone_feat) */
+    int32_t precision;                    /* ZENV_MLP_F32 only: the float32 vector-ALU kernels of option_f32.hip */
+    /* hi_model_state (HighPolicyValueModel) */
+    const float *hi_zone_w1, *hi_zone_b1; /* env_model.zone_net_.0  [h, 8+F],   [h] */
+    const float *hi_zone_w2, *hi_zone_b2; /* env_model.zone_net_.2  [h, h],     [h] */
+    const float *hi_zone_w3, *hi_zone_b3; /* env_model.zone_net_.4  [h, h],     [h] */
+    const float *hi_comb_w, *hi_comb_b;   /* env_model.combine_net_ [h, 8+h],   [h] */
+    const float *hi_enc_w, *hi_enc_b;     /* actor.enc_.0.0         [h, h],     [h] */
+    const float *hi_logit_w, *hi_logit_b; /* actor.discrete_.0      [S, h],     [S] */
+    const float *hi_critic_w1, *hi_critic_b1; /* critic.0           [h, h],     [h]  (optional) */
+    const float *hi_critic_w2, *hi_critic_b2; /* critic.2           [1, h],     [1]  (optional) */
+    /* lo_model_state (LoPolicyValueModel) */
+    const float *lo_zone_w1, *lo_zone_b1; /* env_model.zone_net_.0  [h, 8+S+F], [h] */
+    const float *lo_zone_w2, *lo_zone_b2; /* env_model.zone_net_.2  [h, h],     [h] */
+    const float *lo_zone_w3, *lo_zone_b3; /* env_model.zone_net_.4  [h, h],     [h] */
+    const float *lo_comb_w, *lo_comb_b;   /* env_model.combine_net_ [h, 8+S+h], [h] */
+    const float *lo_enc_w, *lo_enc_b;     /* actor.enc_.0.0         [h, h+S],   [h] */
+    const float *lo_mu_w, *lo_mu_b;       /* actor.mu_              [3, h],     [3]  rows 0-1: the action, row 2: a_2 */
+    const float *lo_std_w, *lo_std_b;     /* actor.std_             [3, h],     [3] */
+    const float *lo_critic_w1, *lo_critic_b1; /* critic.0           [h, h+S],   [h]  (optional) */
+    const float *lo_critic_w2, *lo_critic_b2; /* critic.2           [1, h],     [1]  (optional) */
+} zenv_option_weights;
+/* The error codes of zenv_skill_load.  A handle holds ONE agent of the skill family: zenv_option_load drops loaded
+ * skill weights (and inverse weights), zenv_skill_load drops loaded option weights; either resets the skill state
+ * (ZENV_F_SKILL = -1, ZENV_F_SKILL_AGE = 0, ZENV_F_OPTION_ENDED = 0).  zenv_mlp_load's and zenv_hier_load's weights are
+ * left alone.  zenv_set_skills works with either agent. */
+int zenv_option_load(zenv_t *h, const zenv_option_weights *w);
+/* Both networks on the current observations, every env, the state untouched (zenv_skill_forward's fields, the low level
+ * under the env's current skill, zeros without one) plus ZENV_F_OPTION_TERM_MU / _STD, _TERM_ACTION = mu_2 and
+ * _TERM_PROB = sigmoid(4 mu_2 - 3).
+ * zenv_policy(ZENV_POLICY_OPTION_*) is one step of evaluate_hier.py:63-75 for every env, no host synchronisation:
+ *  1. every unfinished env with ZENV_F_SKILL < 0 or ZENV_F_OPTION_ENDED = 1 picks a skill (age 0): the draw of
+ *     ZENV_POLICY_SKILL_SAMPLE (same Philox stream, same inverse CDF), or the argmax (ties: lowest skill).  The high
+ *     level runs for those envs only; ZENV_F_SKILL_LOGITS / _VALUE are refreshed for them.
+ *  2. the low level of every unfinished env writes ZENV_F_POLICY_MU / _STD [N,2] (the first two components), _VALUE and
+ *     the action [N,2]; SAMPLE draws the two exactly as the skill agent does (Box-Muller on words 0 and 1 of the Philox
+ *     block with tag 0x4D4C50), and a_2 = mu_2 + std_2 sqrt(-2 ln u1') cos(2 pi u2') from words 2 and 3 of that block.
+ *  3. prob = sigmoid(4 a_2 - 3) in float32.  SAMPLE: the option ends iff u < prob, u the uniform of word 0 of the block
+ *     with tag 0x4F5054, keyed by (policy_seed, env_index0 + env, zenv_step_count) like the others.  MEAN: a_2 = mu_2,
+ *     the option ends iff prob > 0.5.  The age goes up by one.
+ * ZENV_F_SKILL keeps the skill the action was taken under; that the option ended is ZENV_F_OPTION_ENDED, consumed by the
+ * next policy call.  A finished env (left alone by step_no_reset) idles: zeros in every output, nothing ends, its skill
+ * and age stay.  zenv_rollout() refuses these policies (ZENV_E_ARG); with option weights loaded zenv_skill_forward,
+ * zenv_collect_skill and ZENV_POLICY_SKILL_* answer ZENV_E_STATE as without skill weights, and so do
+ * zenv_option_forward and ZENV_POLICY_OPTION_* without option weights.
+ * ZENV_OPTION_COMPACT=0 / 1 in the environment at zenv_option_load picks how step 1 finds its envs (diagnostic, same
+ * results): 0 -- workgroup b owns envs 4 b .. 4 b + 3 and leaves when none picks (the default up to 4 096 envs); 1 -- a
+ * list of the picking envs is compacted first and workgroup b owns entries 4 b .. 4 b + 3 of it (the default above). */
+int zenv_option_forward(zenv_t *h);
 
 /* DIAYN's discriminator, InverseModel (main/src/inverse_model.py): logits = combine_net(.2)(relu(combine_net(.0)(
  * [obs, zone_emb]))), zone_emb = mean over the zones of zone_net([obs, zone row]) -- the skill high level's encoder
