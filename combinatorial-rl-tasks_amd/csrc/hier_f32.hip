@@ -19,7 +19,9 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstddef>
 
+#include "f32_packer.hpp"
 #include "hier_enc.hpp"
 #include "hier_f32.hpp"
 #include "mlp_head_out.hpp"
@@ -28,31 +30,6 @@ namespace zenvk {
 namespace {
 
 using namespace hf32;
-
-__device__ __forceinline__ void lo_idle(int env, float *__restrict__ mu, float *__restrict__ stdv, float *__restrict__ value,
-                                        const MlpAction &act)
-{
-    const float2 z = make_float2(0.f, 0.f);
-    reinterpret_cast<float2 *>(mu)[env] = z;
-    reinterpret_cast<float2 *>(stdv)[env] = z;
-    value[env] = 0.f;
-    if (act.mode < 0) return;
-    reinterpret_cast<float2 *>(act.actions)[env] = z;
-    // zenv_collect_hier: frame t of an env without a goal -- action 0, log_prob 0, value 0; mask and the reward of frame
-    // t-1 as head_outputs records them
-    const MlpRecord &rc = act.rec;
-    if (!rc.action) return;
-    const size_t slot = (size_t)rc.t * rc.N + env;
-    reinterpret_cast<float2 *>(rc.action)[slot] = z;
-    reinterpret_cast<float2 *>(rc.log_prob)[slot] = z;
-    rc.value[slot] = 0.f;
-    if (rc.t == 0) {
-        rc.mask[slot] = rc.cur_mask[env];
-    } else {
-        rc.mask[slot] = rc.prev_done[env] ? 0.f : 1.f;
-        rc.reward[slot - rc.N] = rc.prev_shaped ? (float)rc.prev_shaped[env] : rc.prev_reward[env];
-    }
-}
 
 // zenv_collect_hier: the low level's goal input of frame t, cur_goal of _hier_policy_opt.py -- the last goal's centre / 3
 // (goal_xy survives the goal's clearing and the auto-reset), 0 before the first goal
@@ -64,15 +41,8 @@ __device__ __forceinline__ void lo_record_goal(const DevParams &p, const HierRec
         make_float2((float)(zz.x / 3.0), (float)(zz.y / 3.0));
 }
 
-// one uniform in (0, 1) of the goal draw: Philox4x32-10 keyed by (seed, global env, step), a stream of its own (the
-// action draw of mlp_head_out.hpp uses the tag 0x4D4C50)
-__device__ __forceinline__ float goal_uniform(const HierPick &pick, int env)
-{
-    const uint64_t g = pick.env_index0 + (uint64_t)env;
-    uint32_t c[4] = { (uint32_t)g, (uint32_t)(g >> 32), pick.step_index, 0x48474Cu };
-    philox4x32_10(c, (uint32_t)pick.seed, (uint32_t)(pick.seed >> 32));
-    return ((float)(c[0] >> 8) + 0.5f) * 5.9604644775390625e-08f;
-}
+// the goal draw's Philox stream (the action draw of mlp_head_out.hpp uses the tag 0x4D4C50)
+constexpr uint32_t kGoalTag = 0x48474Cu;
 
 // LEVEL 0: HighPolicyValueModel -> out0 = logits [N][Z], out1 = value [N] (+ the goal pick)
 // LEVEL 1: LoPolicyValueModel   -> out0 = mu [N][2], out1 = std [N][2], out2 = value [N] (+ the action)
@@ -115,7 +85,7 @@ __global__ __launch_bounds__(HP) void k_hier_f32(HierF32 w, DevParams p, float *
             if (LEVEL == 0) {
                 if (pick.mode >= 0) pick.new_goal[env0 + j] = -1;
             } else {
-                lo_idle(env0 + j, out0, out1, out2, act);
+                idle_outputs(env0 + j, out0, out1, out2, act);
                 lo_record_goal(p, rec, env0 + j);
             }
         }
@@ -225,7 +195,8 @@ __global__ __launch_bounds__(HP) void k_hier_f32(HierF32 w, DevParams p, float *
                 }
                 if (pick.mode == 1 && best >= 0) {
                     // inverse CDF of softmax over the available zones, in zone order
-                    const float thr = goal_uniform(pick, env) * s;
+                    const float u = philox_uniform(pick.seed, pick.env_index0 + (uint64_t)env, pick.step_index, kGoalTag);
+                    const float thr = u * s;
                     float c = 0.f;
                     for (int z = 0; z < Z; ++z) {
                         if (!((avail >> z) & 1u)) continue;
@@ -280,7 +251,7 @@ __global__ __launch_bounds__(HP) void k_hier_f32(HierF32 w, DevParams p, float *
             out2[env] = o[4];
             head_outputs(env, o[0], o[1], o[2], o[3], o[4], out0, out1, act);
         } else {
-            lo_idle(env, out0, out1, out2, act);
+            idle_outputs(env, out0, out1, out2, act);
         }
         lo_record_goal(p, rec, env);
     }
@@ -291,68 +262,37 @@ __global__ __launch_bounds__(HP) void k_hier_f32(HierF32 w, DevParams p, float *
 size_t pack_hier_f32(const zenv_hier_weights &w, int F, std::vector<float> &out, size_t offs[kHierOffs])
 {
     const int h = w.h_dim;
-    out.clear();
-    auto put = [&](size_t n) {                             // n zero floats, 16-byte aligned start
-        const size_t at = (out.size() + 3) & ~(size_t)3;
-        out.resize(at + n, 0.f);
-        return at;
-    };
-    // columns col0 .. col0 + n_cols - 1 of W [h][in_stride], transposed -> [rows][HP] (rows >= n_cols, zero-padded)
-    auto cols = [&](const float *W, int in_stride, int col0, int n_cols, int rows) {
-        const size_t at = put((size_t)rows * HP);
-        for (int o = 0; o < h; ++o)
-            for (int k = 0; k < n_cols; ++k) out[at + (size_t)k * HP + o] = W[(size_t)o * in_stride + col0 + k];
-        return at;
-    };
-    auto bias = [&](const float *b) {
-        const size_t at = put(HP);
-        for (int o = 0; o < h; ++o) out[at + o] = b[o];
-        return at;
-    };
-    auto row = [&](const float *W, const float *b) {       // one output row: [HP] weights, bias at HP
-        const size_t at = put(HP + 1);
-        for (int k = 0; k < h; ++k) out[at + k] = W[k];
-        out[at + HP] = b[0];
-        return at;
-    };
+    Packer pk(out, h);
     int i = 0;
-    auto enc = [&](const float *w1, const float *b1, const float *w2, const float *b2, const float *w3, const float *b3,
-                   const float *wc, const float *bc, int xin) {
-        offs[i++] = cols(w1, xin + F, 0, xin, xin);         // zone_net_.0: [obs(, goal)] columns
-        offs[i++] = cols(w1, xin + F, xin, F, ZF);          //              zone-row columns
-        offs[i++] = bias(b1);
-        offs[i++] = cols(w2, h, 0, h, HP);
-        offs[i++] = bias(b2);
-        offs[i++] = cols(w3, h, 0, h, HP);
-        offs[i++] = bias(b3);
-        offs[i++] = cols(wc, xin + h, 0, xin, xin);         // combine_net_: [obs(, goal)] columns
-        offs[i++] = cols(wc, xin + h, xin, h, HP);          //               zone_emb columns
-        offs[i++] = bias(bc);
-    };
-    enc(w.hi_zone_w1, w.hi_zone_b1, w.hi_zone_w2, w.hi_zone_b2, w.hi_zone_w3, w.hi_zone_b3, w.hi_comb_w, w.hi_comb_b, 8);
-    enc(w.lo_zone_w1, w.lo_zone_b1, w.lo_zone_w2, w.lo_zone_b2, w.lo_zone_w3, w.lo_zone_b3, w.lo_comb_w, w.lo_comb_b, 10);
-    offs[i++] = cols(w.hi_actor_w1, h + F, 0, h, HP);       // actor.0: emb columns
-    offs[i++] = cols(w.hi_actor_w1, h + F, h, F, ZF);       //          zone-row columns
-    offs[i++] = bias(w.hi_actor_b1);
-    offs[i++] = row(w.hi_actor_w2, w.hi_actor_b2);
+    pk.enc(offs, i, w.hi_zone_w1, w.hi_zone_b1, w.hi_zone_w2, w.hi_zone_b2, w.hi_zone_w3, w.hi_zone_b3, w.hi_comb_w,
+           w.hi_comb_b, F, 8, 0);
+    pk.enc(offs, i, w.lo_zone_w1, w.lo_zone_b1, w.lo_zone_w2, w.lo_zone_b2, w.lo_zone_w3, w.lo_zone_b3, w.lo_comb_w,
+           w.lo_comb_b, F, 10, 0);
+    offs[i++] = pk.cols(w.hi_actor_w1, h + F, 0, h, HP);    // actor.0: emb columns
+    offs[i++] = pk.cols(w.hi_actor_w1, h + F, h, F, ZF);    //          zone-row columns
+    offs[i++] = pk.bias(w.hi_actor_b1);
+    offs[i++] = pk.rows(w.hi_actor_w2, w.hi_actor_b2, 1);
     const bool hc = w.hi_critic_w1 != nullptr, lc = w.lo_critic_w1 != nullptr;
-    offs[i++] = hc ? cols(w.hi_critic_w1, h, 0, h, HP) : 0;
-    offs[i++] = hc ? bias(w.hi_critic_b1) : 0;
-    offs[i++] = hc ? row(w.hi_critic_w2, w.hi_critic_b2) : 0;
-    offs[i++] = cols(w.lo_enc_w, h, 0, h, HP);
-    offs[i++] = bias(w.lo_enc_b);
-    offs[i] = put(4 * (size_t)(HP + 1));                    // mu_ rows 0-1, std_ rows 2-3
-    for (int r = 0; r < 4; ++r) {
-        const float *W = r < 2 ? w.lo_mu_w + (size_t)r * h : w.lo_std_w + (size_t)(r - 2) * h;
-        const float *b = r < 2 ? w.lo_mu_b + r : w.lo_std_b + (r - 2);
-        for (int k = 0; k < h; ++k) out[offs[i] + (size_t)r * (HP + 1) + k] = W[k];
-        out[offs[i] + (size_t)r * (HP + 1) + HP] = b[0];
-    }
-    ++i;
-    offs[i++] = lc ? cols(w.lo_critic_w1, h, 0, h, HP) : 0;
-    offs[i++] = lc ? bias(w.lo_critic_b1) : 0;
-    offs[i++] = lc ? row(w.lo_critic_w2, w.lo_critic_b2) : 0;
+    offs[i++] = hc ? pk.cols(w.hi_critic_w1, h, 0, h, HP) : 0;
+    offs[i++] = hc ? pk.bias(w.hi_critic_b1) : 0;
+    offs[i++] = hc ? pk.rows(w.hi_critic_w2, w.hi_critic_b2, 1) : 0;
+    offs[i++] = pk.cols(w.lo_enc_w, h, 0, h, HP);
+    offs[i++] = pk.bias(w.lo_enc_b);
+    offs[i++] = pk.head_rows(w.lo_mu_w, w.lo_mu_b, w.lo_std_w, w.lo_std_b, 2);
+    offs[i++] = lc ? pk.cols(w.lo_critic_w1, h, 0, h, HP) : 0;
+    offs[i++] = lc ? pk.bias(w.lo_critic_b1) : 0;
+    offs[i++] = lc ? pk.rows(w.lo_critic_w2, w.lo_critic_b2, 1) : 0;
     return out.size();
+}
+
+HierF32 hier_f32_at(const zenv_hier_weights &w, const float *base, const size_t offs[kHierOffs])
+{
+    HierF32 s{};
+    s.h = w.h_dim;
+    s.hi_critic = w.hi_critic_w1 ? 1 : 0;
+    s.lo_critic = w.lo_critic_w1 ? 1 : 0;
+    bind_pointers(s, offsetof(HierF32, hi), base, offs, kHierOffs);
+    return s;
 }
 
 hipError_t launch_hier_high(const HierF32 &w, const DevParams &p, float *logits, float *value, const HierPick &pick,

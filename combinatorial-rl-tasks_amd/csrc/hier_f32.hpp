@@ -37,10 +37,14 @@ struct HierF32 {
     const float *lv2;              // critic.2  [HP + 1]
 };
 
+constexpr int kHierOffs = 33;      // the pointers of HierF32, from hi.w1x on
+static_assert(sizeof(HierF32) == 4 * sizeof(int) + kHierOffs * sizeof(const float *), "HierF32 layout");
+
 // Host packer: the float32 state_dict tensors of zenv_hier_weights -> one buffer; offs[] = offsets in floats of the
-// pointers of HierF32 in declaration order (HierF32 fields from `hi.w1x` on), 0 for an absent critic.
-constexpr int kHierOffs = 33;
+// pointers of HierF32 in declaration order, 0 for an absent critic (the image starts with 4 floats of padding, so that
+// no tensor sits at offset 0).  hier_f32_at() binds such an image to its device address.
 size_t pack_hier_f32(const zenv_hier_weights &w, int F, std::vector<float> &out, size_t offs[kHierOffs]);
+HierF32 hier_f32_at(const zenv_hier_weights &w, const float *base, const size_t offs[kHierOffs]);
 
 // What the high-level kernel does besides the logits / value: nothing (mode < 0: every env is evaluated), or pick a
 // goal for every env that needs one and is not finished -- argmax (0) or a draw from Categorical(logits) (1), keyed by

@@ -139,15 +139,9 @@ __global__ __launch_bounds__(HP) void k_option_low(SkillF32 w, DevParams p, Skil
     if (j >= n_env) return;
     const int env = env0 + j;
     if (sel[j] < 0) {
-        const float2 z = make_float2(0.f, 0.f);
-        reinterpret_cast<float2 *>(out0)[env] = z;
-        reinterpret_cast<float2 *>(out1)[env] = z;
-        out2[env] = 0.f;
+        idle_outputs(env, out0, out1, out2, act);
         term.mu[env] = term.stdv[env] = term.action[env] = term.prob[env] = 0.f;
-        if (acts) {
-            reinterpret_cast<float2 *>(act.actions)[env] = z;
-            st.ended[env] = 0;
-        }
+        if (acts) st.ended[env] = 0;
         return;
     }
     const float *o = lg + 8 * j;
@@ -159,10 +153,8 @@ __global__ __launch_bounds__(HP) void k_option_low(SkillF32 w, DevParams p, Skil
     float a2 = m2;
     if (act.mode == 1) {
         // words 2 and 3 of the action draw's Philox block (mlp_action took 0 and 1)
-        uint32_t c[4] = { (uint32_t)g, (uint32_t)(g >> 32), act.step_index, 0x4D4C50u };
-        philox4x32_10(c, (uint32_t)act.seed, (uint32_t)(act.seed >> 32));
-        const float u1 = ((float)(c[2] >> 8) + 0.5f) * 5.9604644775390625e-08f;
-        const float u2 = ((float)(c[3] >> 8) + 0.5f) * 5.9604644775390625e-08f;
+        const PhiloxWords c = philox_words(act.seed, g, act.step_index, 0x4D4C50u);
+        const float u1 = u01(c.w[2]), u2 = u01(c.w[3]);
         a2 = m2 + sd2 * sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2);
     }
     const float prob = sigmoidf_(4.0f * a2 - 3.0f);

@@ -17,6 +17,7 @@
 #include <cstddef>
 #include <cstring>
 
+#include "f32_packer.hpp"
 #include "skill_net.hpp"
 
 namespace zenvk {
@@ -33,30 +34,12 @@ __device__ __forceinline__ float skill_uniform(const SkillPick &pick, int env)
     return philox_uniform(pick.seed, pick.env_index0 + (uint64_t)env, pick.step_index, tag);
 }
 
+// an env without a skill: idle_outputs, and inside zenv_collect_skill skill -1 for frame t
 __device__ __forceinline__ void skill_idle(int env, float *__restrict__ mu, float *__restrict__ stdv,
                                            float *__restrict__ value, const MlpAction &act, const SkillRecord &sr)
 {
-    const float2 z = make_float2(0.f, 0.f);
-    reinterpret_cast<float2 *>(mu)[env] = z;
-    reinterpret_cast<float2 *>(stdv)[env] = z;
-    value[env] = 0.f;
-    if (act.mode < 0) return;
-    reinterpret_cast<float2 *>(act.actions)[env] = z;
-    // zenv_collect_skill: frame t of an env without a skill -- skill -1, action 0, log_prob 0, value 0; mask and the
-    // reward of frame t-1 as head_outputs records them
-    if (sr.lo_skill) sr.lo_skill[(size_t)sr.t * sr.N + env] = -1;
-    const MlpRecord &rc = act.rec;
-    if (!rc.action) return;
-    const size_t slot = (size_t)rc.t * rc.N + env;
-    reinterpret_cast<float2 *>(rc.action)[slot] = z;
-    reinterpret_cast<float2 *>(rc.log_prob)[slot] = z;
-    rc.value[slot] = 0.f;
-    if (rc.t == 0) {
-        rc.mask[slot] = rc.cur_mask[env];
-    } else {
-        rc.mask[slot] = rc.prev_done[env] ? 0.f : 1.f;
-        rc.reward[slot - rc.N] = rc.prev_shaped ? (float)rc.prev_shaped[env] : rc.prev_reward[env];
-    }
+    idle_outputs(env, mu, stdv, value, act);
+    if (act.mode >= 0 && sr.lo_skill) sr.lo_skill[(size_t)sr.t * sr.N + env] = -1;
 }
 
 // LEVEL 0: HighPolicyValueModel -> out0 = log-softmax logits [N][S], out1 = value [N] (+ the skill pick)
@@ -210,73 +193,15 @@ __global__ __launch_bounds__(256) void k_skill_set(DevParams p, SkillState st)
 
 }  // namespace
 
-namespace {
-
-// the float32 image of zenv_skill_load / zenv_skill_inverse_load: every tensor at a 16-byte aligned offset in floats,
-// none at offset 0 (0 = absent)
-struct Packer {
-    std::vector<float> &out;
-    int h;
-    explicit Packer(std::vector<float> &o, int h_) : out(o), h(h_) { out.assign(4, 0.f); }
-    size_t put(size_t n)                                     // n zero floats, 16-byte aligned start
-    {
-        const size_t at = (out.size() + 3) & ~(size_t)3;
-        out.resize(at + n, 0.f);
-        return at;
-    }
-    // columns col0 .. col0 + n_cols - 1 of W [h][in_stride], transposed -> [rows][HP] (rows >= n_cols, zero-padded)
-    size_t cols(const float *W, int in_stride, int col0, int n_cols, int rows)
-    {
-        const size_t at = put((size_t)rows * HP);
-        for (int o = 0; o < h; ++o)
-            for (int k = 0; k < n_cols; ++k) out[at + (size_t)k * HP + o] = W[(size_t)o * in_stride + col0 + k];
-        return at;
-    }
-    size_t bias(const float *b)
-    {
-        const size_t at = put(HP);
-        for (int o = 0; o < h; ++o) out[at + o] = b[o];
-        return at;
-    }
-    // n output rows of W [n][h] + b [n] -> [n][HP + 1], bias last
-    size_t rows(const float *W, const float *b, int n)
-    {
-        const size_t at = put((size_t)n * (HP + 1));
-        for (int r = 0; r < n; ++r) {
-            for (int k = 0; k < h; ++k) out[at + (size_t)r * (HP + 1) + k] = W[(size_t)r * h + k];
-            out[at + (size_t)r * (HP + 1) + HP] = b[r];
-        }
-        return at;
-    }
-    // ZoneEnvModel: zone_net_.0 on [obs, (onehot,) zone row], combine_net_ on [obs, (onehot,) zone_emb]; xs = S or 0.
-    // The ten pointers of HierEnc into offs[i ...]
-    void enc(size_t *offs, int &i, const float *w1, const float *b1, const float *w2, const float *b2, const float *w3,
-             const float *b3, const float *wc, const float *bc, int F, int xs)
-    {
-        offs[i++] = cols(w1, 8 + xs + F, 0, 8, 8);
-        offs[i++] = cols(w1, 8 + xs + F, 8 + xs, F, ZF);
-        offs[i++] = bias(b1);
-        offs[i++] = cols(w2, h, 0, h, HP);
-        offs[i++] = bias(b2);
-        offs[i++] = cols(w3, h, 0, h, HP);
-        offs[i++] = bias(b3);
-        offs[i++] = cols(wc, 8 + xs + h, 0, 8, 8);
-        offs[i++] = cols(wc, 8 + xs + h, 8 + xs, h, HP);
-        offs[i++] = bias(bc);
-    }
-};
-
-}  // namespace
-
 size_t pack_skill_f32(const zenv_skill_weights &w, int F, std::vector<float> &out, size_t offs[kSkillPtrs], int n_out)
 {
     const int h = w.h_dim, S = w.n_skills;
     Packer pk(out, h);
     int i = 0;
     pk.enc(offs, i, w.hi_zone_w1, w.hi_zone_b1, w.hi_zone_w2, w.hi_zone_b2, w.hi_zone_w3, w.hi_zone_b3, w.hi_comb_w,
-           w.hi_comb_b, F, 0);
+           w.hi_comb_b, F, 8, 0);
     pk.enc(offs, i, w.lo_zone_w1, w.lo_zone_b1, w.lo_zone_w2, w.lo_zone_b2, w.lo_zone_w3, w.lo_zone_b3, w.lo_comb_w,
-           w.lo_comb_b, F, S);
+           w.lo_comb_b, F, 8, S);
     offs[i++] = pk.cols(w.lo_zone_w1, 8 + S + F, 8, S, S);  // the skill columns
     offs[i++] = pk.cols(w.lo_comb_w, 8 + S + h, 8, S, S);
     offs[i++] = pk.cols(w.hi_enc_w, h, 0, h, HP);
@@ -289,14 +214,7 @@ size_t pack_skill_f32(const zenv_skill_weights &w, int F, std::vector<float> &ou
     offs[i++] = pk.cols(w.lo_enc_w, h + S, 0, h, HP);
     offs[i++] = pk.cols(w.lo_enc_w, h + S, h, S, S);
     offs[i++] = pk.bias(w.lo_enc_b);
-    offs[i] = pk.put(2 * n_out * (size_t)(HP + 1));         // the n_out rows of mu_, then those of std_
-    for (int r = 0; r < 2 * n_out; ++r) {
-        const float *W = r < n_out ? w.lo_mu_w + (size_t)r * h : w.lo_std_w + (size_t)(r - n_out) * h;
-        const float *b = r < n_out ? w.lo_mu_b + r : w.lo_std_b + (r - n_out);
-        for (int k = 0; k < h; ++k) out[offs[i] + (size_t)r * (HP + 1) + k] = W[k];
-        out[offs[i] + (size_t)r * (HP + 1) + HP] = b[0];
-    }
-    ++i;
+    offs[i++] = pk.head_rows(w.lo_mu_w, w.lo_mu_b, w.lo_std_w, w.lo_std_b, n_out);
     offs[i++] = lc ? pk.cols(w.lo_critic_w1, h + S, 0, h, HP) : 0;
     offs[i++] = lc ? pk.cols(w.lo_critic_w1, h + S, h, S, S) : 0;
     offs[i++] = lc ? pk.bias(w.lo_critic_b1) : 0;
@@ -309,7 +227,7 @@ size_t pack_skill_inverse_f32(const zenv_skill_inverse_weights &w, int F, std::v
 {
     Packer pk(out, w.h_dim);
     int i = 0;
-    pk.enc(offs, i, w.zone_w1, w.zone_b1, w.zone_w2, w.zone_b2, w.zone_w3, w.zone_b3, w.comb_w1, w.comb_b1, F, 0);
+    pk.enc(offs, i, w.zone_w1, w.zone_b1, w.zone_w2, w.zone_b2, w.zone_w3, w.zone_b3, w.comb_w1, w.comb_b1, F, 8, 0);
     offs[i++] = pk.rows(w.comb_w2, w.comb_b2, w.n_skills);
     return out.size();
 }
@@ -320,10 +238,8 @@ SkillInvF32 skill_inverse_f32_at(const zenv_skill_inverse_weights &w, const floa
     SkillInvF32 s{};
     s.h = w.h_dim;
     s.S = w.n_skills;
-    const size_t *o = offs;
-    s.enc = HierEnc{ base + o[0], base + o[1], base + o[2], base + o[3], base + o[4], base + o[5], base + o[6],
-                     base + o[7], base + o[8], base + o[9] };
-    s.head = base + o[10];
+    static_assert(offsetof(SkillInvF32, head) == offsetof(SkillInvF32, enc) + sizeof(HierEnc), "SkillInvF32 layout");
+    bind_pointers(s, offsetof(SkillInvF32, enc), base, offs, kSkillInvPtrs);
     return s;
 }
 
@@ -334,10 +250,7 @@ SkillF32 skill_f32_at(const zenv_skill_weights &w, const float *base, const size
     s.S = w.n_skills;
     s.hi_critic = w.hi_critic_w1 ? 1 : 0;
     s.lo_critic = w.lo_critic_w1 ? 1 : 0;
-    // the pointers of SkillF32 in declaration order (static_assert in skill_f32.hpp: nothing else sits between them)
-    const float *ptr[kSkillPtrs];
-    for (int i = 0; i < kSkillPtrs; ++i) ptr[i] = offs[i] ? base + offs[i] : nullptr;
-    std::memcpy(reinterpret_cast<char *>(&s) + offsetof(SkillF32, hi), ptr, sizeof ptr);
+    bind_pointers(s, offsetof(SkillF32, hi), base, offs, kSkillPtrs);
     return s;
 }
 

@@ -1,6 +1,6 @@
 // skill_net.hpp -- what the kernels of the skill family share after the encoder (skill_f32.hip: fixed-length skills,
 // option_f32.hip: variable-length Options): the hidden layers of actor and critic on the embedding, the dot-product rows
-// of the heads, Categorical(logits=log_softmax(x)) with its inverse-CDF draw, and one uniform of a Philox stream.
+// of the heads, Categorical(logits=log_softmax(x)) with its inverse-CDF draw.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,14 +12,6 @@ namespace zenvk {
 namespace hf32 {
 
 constexpr int SR = kMaxSkills + 1;    // per env: S logit rows, then the critic (row kMaxSkills)
-
-// one uniform in (0, 1] of the stream `tag`: Philox4x32-10 keyed by (seed, global env, step), word 0
-__device__ __forceinline__ float philox_uniform(uint64_t seed, uint64_t g, uint32_t step_index, uint32_t tag)
-{
-    uint32_t c[4] = { (uint32_t)g, (uint32_t)(g >> 32), step_index, tag };
-    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-    return ((float)(c[0] >> 8) + 0.5f) * 5.9604644775390625e-08f;
-}
 
 // sum_k w[k] x[k] + w[HP] over the h features (a row of the [.][HP + 1] layout)
 __device__ __forceinline__ float dot_row(const float *__restrict__ w, const float *__restrict__ x, int h)

@@ -1,9 +1,6 @@
 // zenv_api.cpp -- the C ABI of include/zenv.h over the gfx950 kernels.
 // Host-side plumbing only: device memory, the layout bank, launches, copies.  There is no
 // CPU compute path here: without a usable HIP device every compute entry point fails.
-#include <hip/hip_runtime_api.h>
-#include <rccl/rccl.h>   // types and prototypes only: librccl is dlopen()ed by the first zenv_comm_* call
-
 #include <dlfcn.h>
 
 #include <algorithm>
@@ -17,20 +14,14 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/zenv.h"
-#include "dev_params.hpp"
 #include "host_sampler.hpp"
-#include "kernels.hpp"
-#include "hier_f32.hpp"
-#include "option_f32.hpp"
-#include "skill_f32.hpp"
-#include "mlp_policy.hpp"
-
-using namespace zenvk;
+#include "zenv_handle.hpp"
 
 namespace {
 
 thread_local std::string g_err;
+
+}  // namespace
 
 int fail(int code, const char *fmt, ...)
 {
@@ -43,137 +34,11 @@ int fail(int code, const char *fmt, ...)
     return code;
 }
 
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t _e = (expr);                                                               \
-        if (_e != hipSuccess)                                                                 \
-            return fail(ZENV_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e),    \
-                        __FILE__, __LINE__);                                                  \
-    } while (0)
-
-struct Alloc {
-    void **slot;
-    size_t bytes;
-    bool is_state;   // part of zenv_get_state/zenv_set_state
-    int64_t slab_off = -1;   // >= 0: lives at this offset of the handle's results slab (one hipMalloc, one download)
-};
-
-}  // namespace
-
-struct zenv {
-    zenv_config cfg{};
-    int n_env = 0;
-    int device = 0;
-    hipStream_t stream = nullptr;       // the stream work is enqueued on
-    hipStream_t own_stream = nullptr;   // created with the handle; `stream` unless zenv_set_stream
-    DevParams p{};
-    DevParams *d_self = nullptr;     // device copy of p (DevParams::self): the persistent kernel reads cold fields from it
-    DevParams self_shadow{};         // what d_self holds
-    bool self_valid = false;
-    std::vector<Alloc> allocs;
-    // The per-step results (obs, reward, done, goal_met, exception, zone_obs) share ONE allocation, 256-byte aligned
-    // pieces in that order, so that a host policy fetches them with one copy (zenv_step_results).
-    void *results_slab = nullptr;
-    // zenv_host_io(): results slab + action buffer in page-locked host memory that the kernels write / read directly
-    void *host_io_slab = nullptr;
-    float *host_io_actions = nullptr, *dev_actions = nullptr;
-    int64_t results_off[ZENV_N_RESULTS] = {};
-    int64_t results_bytes = 0;
-    void *bank_mem[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };   // robot, zone, aux, seed, derived first rows
-    uint8_t *d_mask = nullptr;
-    bool bank_ready = false;
-    bool sched_ready = false;
-    bool was_reset = false;
-    int64_t step_count = 0;
-    // What the internal action buffer holds when a fused rollout left a_{step_count} behind: the next rollout with
-    // the same action source continues from it instead of launching the policy kernel again.
-    struct {
-        bool valid = false;
-        int policy = -1;
-        uint64_t seed = 0, index0 = 0;
-        int64_t step = -1;
-    } act_tag;
-    std::vector<hipEvent_t> events;
-    int rollout_slice_tiles = 1024;   // 64-env tiles per persistent launch (zenv_set_rollout_slice): one per wave slot pair
-    // actor network (zenv_mlp_load)
-    void *mlp_mem = nullptr;
-    MlpImages mlp{};
-    void *mlp_pooled = nullptr;
-    float *mlp_mu = nullptr, *mlp_std = nullptr, *mlp_value = nullptr, *mlp_value_sigma = nullptr;
-    int *mlp_range_flag = nullptr;      // pinned host word, see mlp_range_check()
-    void *mlp_f32_mem = nullptr;        // float32 path (ZENV_MLP_F32): transposed float32 weights
-    MlpF32 mlp_f32{};
-    bool mlp_ready = false;
-    // Zone-goals hierarchical agent (zenv_hier_load): float32 weights, the high level's outputs
-    void *hier_mem = nullptr;
-    HierF32 hier{};
-    bool hier_ready = false;
-    float *hier_logits = nullptr, *hier_value = nullptr;
-    // fixed-length-skills agent (zenv_skill_load): float32 weights, the per-env skill state, the high level's outputs
-    void *skill_mem = nullptr;
-    SkillF32 skill{};
-    bool skill_ready = false;
-    int skill_len = 200;                // evaluate_hier.py:21
-    int skill_n = 0;                    // S the outputs are allocated for
-    SkillState sst{};
-    void *sst_mem = nullptr;
-    float *skill_logits = nullptr, *skill_value = nullptr;
-    // variable-length Options agent (zenv_option_load): it takes the place of the skill agent on the handle -- its
-    // weights live in skill_mem / skill, the state in sst -- plus the picking envs' list and the third output's fields
-    bool option_ready = false;
-    int option_compact = 0;
-    void *opt_mem = nullptr;
-    OptionList olist{};
-    OptionTerm oterm{};
-    // DIAYN's discriminator (zenv_skill_inverse_load) and the per-frame records of zenv_collect_skill (T frames):
-    // lo_skill, diversity, env_reward [T][N]; the bootstrap skill and the row count [N]
-    void *skinv_mem = nullptr;
-    SkillInvF32 skinv{};
-    bool skinv_ready = false;
-    struct {
-        int T = 0;
-        int32_t *lo_skill = nullptr, *boot = nullptr, *count = nullptr;
-        float *diversity = nullptr, *env_reward = nullptr;
-    } sk;
-    void *sk_mem = nullptr;
-    // goal-conditioned variant (zenv_goal_enable)
-    bool goal_enabled = false;
-    bool order_enabled = false;   // solver-ordered variant (zenv_order_enable)
-    int32_t *goal_in = nullptr, *goal_bad = nullptr;
-    // experience buffers (zenv_collect)
-    ExpBuffers exp{};
-    void *exp_mem = nullptr;
-    // zenv_collect_hier: the per-frame records of one call (T), the state that lives from call to call, the flat
-    // high-level output (capacity hi_cap rows, hi_m of them written by the last call)
-    HierFrames hframes{};
-    void *hframes_mem = nullptr;
-    HierCarry hcarry{};
-    void *hcarry_mem = nullptr;
-    HierOut hout{};
-    void *hout_mem = nullptr;
-    int64_t hi_cap = 0, hi_m = 0;
-    int32_t *hi_total_host = nullptr;   // page-locked word M is read back into
-    // staging of zenv_bank_update (page-locked host image + its device copy)
-    void *refill_host = nullptr, *refill_dev = nullptr;
-    size_t refill_cap = 0;
-    hipEvent_t refill_done = nullptr;
-    bool refill_busy = false;
-    // the sharded job's communicator (zenv_comm_init): RCCL over xGMI
-    ncclComm_t comm = nullptr;
-    int comm_rank = 0, comm_world = 0;
-    void *comm_send = nullptr, *comm_recv = nullptr;   // [N] and [world * N] 4-byte elements
-    double *comm_scalar = nullptr;                      // device scratch of the barrier / max-reduce
-    // zenv_step_many: the chunk's actions on the device (when they came from the host) and its time-major records
-    void *chunk_mem = nullptr;
-    size_t chunk_cap = 0;           // steps * envs the allocation holds
-    float *chunk_actions = nullptr, *chunk_reward = nullptr;
-    uint8_t *chunk_done = nullptr;
-    int chunk_steps = 0;            // steps of the last zenv_step_many (extent of ZENV_F_CHUNK_REWARD / _DONE)
-    int chunk_host_steps = 0;       // steps of the last host-action chunk while chunk_actions holds it, else 0
-    // ZENV_F_EP_RETURN / ZENV_F_EP_LEN as plain arrays: the values live in the HotA records, unpacked by refresh_field()
-    double *pub_ep_return = nullptr;
-    int32_t *pub_steps = nullptr;
-};
+int use_device(const zenv *h)
+{
+    HIP_TRY(hipSetDevice(h->device));
+    return ZENV_OK;
+}
 
 namespace {
 
@@ -283,12 +148,6 @@ template <typename T>
 void want(zenv *h, T *&slot, size_t count, bool is_state)
 {
     h->allocs.push_back({ reinterpret_cast<void **>(&slot), count * sizeof(T), is_state });
-}
-
-int use_device(const zenv *h)
-{
-    HIP_TRY(hipSetDevice(h->device));
-    return ZENV_OK;
 }
 
 struct FieldInfo {
@@ -1147,922 +1006,6 @@ extern "C" int zenv_solver_goals(zenv_t *h, int32_t *goals)
     HIP_TRY(hipMemcpyAsync(goals, h->goal_in, sizeof(int32_t) * (size_t)h->n_env, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return ZENV_OK;
-}
-
-// ZENV_MLP_F16X3: the network kernel sets *mlp_range_flag (pinned host memory) when one of its operands left float16's
-// range; every entry point that waits for the device looks at it once the stream has drained
-static int mlp_range_check(zenv *h)
-{
-    if (!h->mlp_range_flag || !*(volatile int *)h->mlp_range_flag) return ZENV_OK;
-    *(volatile int *)h->mlp_range_flag = 0;
-    return fail(ZENV_E_RANGE, "an input or activation of the network reached 65 520, beyond float16 (ZENV_MLP_F16: or an "
-                              "observation beyond 64): the actions since the last synchronising call are invalid -- load these "
-                              "weights with ZENV_MLP_BF16, ZENV_MLP_BF16X3 or ZENV_MLP_F32");
-}
-
-// ============================================================================ actor network
-extern "C" int zenv_mlp_load(zenv_t *h, const zenv_mlp_weights *w)
-{
-    if (!h || !w) return fail(ZENV_E_ARG, "null argument");
-    for (const float *t : { w->zone_w1, w->zone_b1, w->zone_w2, w->zone_b2, w->zone_w3, w->zone_b3, w->comb_w, w->comb_b,
-                            w->enc_w, w->enc_b, w->mu_w, w->mu_b, w->std_w, w->std_b })
-        if (!t) return fail(ZENV_E_ARG, "zenv_mlp_weights has a null tensor");
-    const int n_critic = (w->critic_w1 != nullptr) + (w->critic_b1 != nullptr) + (w->critic_w2 != nullptr) +
-                         (w->critic_b2 != nullptr);
-    if (n_critic != 0 && n_critic != 4) return fail(ZENV_E_ARG, "give all four critic tensors or none");
-    const int n_sigma = (w->critic_sigma_w != nullptr) + (w->critic_sigma_b != nullptr);
-    if (n_sigma == 1 || (n_sigma == 2 && n_critic == 0))
-        return fail(ZENV_E_ARG, "the distributional critic needs critic.0, critic_mu (as critic_w2 / _b2) and critic_sigma");
-    if (w->precision < ZENV_MLP_BF16 || w->precision > ZENV_MLP_F16)
-        return fail(ZENV_E_ARG, "unknown zenv_mlp_weights.precision %d", w->precision);
-    if (w->precision == ZENV_MLP_F16 && w->h_dim >= 1 && w->h_dim < kMlpHP) {
-        // single float16 operands.  (i) every weight must be a finite float16; (ii) the zone layers' activations are bounded
-        // here, over the rows' absolute sums, for observations up to kMlpF16ObsBound and zone rows up to 2 (positions / 3,
-        // flags, timers: bounded by construction) -- the zone kernel has no cycles to spare for watching them; the head
-        // kernel watches its own.
-        const int hd = w->h_dim, F = h->p.F;
-        const struct { const float *t; size_t n; const char *name; } all[] = {
-            { w->zone_w1, (size_t)hd * (8 + F), "zone_net_.0.weight" }, { w->zone_b1, (size_t)hd, "zone_net_.0.bias" },
-            { w->zone_w2, (size_t)hd * hd, "zone_net_.2.weight" },      { w->zone_b2, (size_t)hd, "zone_net_.2.bias" },
-            { w->enc_w, (size_t)hd * hd, "actor.enc_.0.0.weight" },     { w->enc_b, (size_t)hd, "actor.enc_.0.0.bias" },
-            { w->mu_w, (size_t)2 * hd, "actor.mu_.weight" },            { w->mu_b, 2, "actor.mu_.bias" },
-            { w->std_w, (size_t)2 * hd, "actor.std_.weight" },          { w->std_b, 2, "actor.std_.bias" },
-            { w->critic_w1, (size_t)hd * hd, "critic.0.weight" },       { w->critic_b1, (size_t)hd, "critic.0.bias" },
-            { w->critic_w2, (size_t)hd, "critic.2.weight" },            { w->critic_b2, 1, "critic.2.bias" },
-            { w->critic_sigma_w, (size_t)hd, "critic_sigma.weight" },   { w->critic_sigma_b, 1, "critic_sigma.bias" } };
-        for (const auto &a : all)
-            for (size_t i = 0; a.t && i < a.n; ++i)
-                if (!(std::fabs(a.t[i]) < 65504.0f))
-                    return fail(ZENV_E_RANGE, "%s[%zu] = %g is not a finite float16: use ZENV_MLP_BF16 or a split mode",
-                                a.name, i, (double)a.t[i]);
-        double a1 = 0.0, s2 = 0.0, b2 = 0.0;
-        for (int r = 0; r < hd; ++r) {
-            double v = std::fabs((double)w->zone_b1[r]), s = 0.0;
-            for (int k = 0; k < 8 + F; ++k)
-                v += std::fabs((double)w->zone_w1[(size_t)r * (8 + F) + k]) * (k < 8 ? (double)kMlpF16ObsBound : 2.0);
-            a1 = std::max(a1, v);
-            for (int k = 0; k < hd; ++k) s += std::fabs((double)w->zone_w2[(size_t)r * hd + k]);
-            s2 = std::max(s2, s);
-            b2 = std::max(b2, std::fabs((double)w->zone_b2[r]));
-        }
-        if (!(a1 < 65504.0) || !(s2 * a1 + b2 < 65504.0))
-            return fail(ZENV_E_RANGE, "zone_net_'s activations are bounded by %.3g / %.3g for observations up to %g: beyond "
-                                      "float16 -- use ZENV_MLP_BF16 or a split mode for these weights",
-                        a1, s2 * a1 + b2, (double)kMlpF16ObsBound);
-    }
-    if (w->precision == ZENV_MLP_F16X3 && w->h_dim >= 1 && w->h_dim < kMlpHP) {
-        // float16 halves: a weight of 65 520 or more would be inf on the device
-        const int hd = w->h_dim, F = h->p.F;
-        const struct { const float *t; size_t n; const char *name; } all[] = {
-            { w->zone_w1, (size_t)hd * (8 + F), "zone_net_.0.weight" }, { w->zone_b1, (size_t)hd, "zone_net_.0.bias" },
-            { w->zone_w2, (size_t)hd * hd, "zone_net_.2.weight" },      { w->zone_b2, (size_t)hd, "zone_net_.2.bias" },
-            { w->zone_w3, (size_t)hd * hd, "zone_net_.4.weight" },      { w->zone_b3, (size_t)hd, "zone_net_.4.bias" },
-            { w->comb_w, (size_t)hd * (8 + hd), "combine_net_.weight" }, { w->comb_b, (size_t)hd, "combine_net_.bias" },
-            { w->enc_w, (size_t)hd * hd, "actor.enc_.0.0.weight" },     { w->enc_b, (size_t)hd, "actor.enc_.0.0.bias" },
-            { w->mu_w, (size_t)2 * hd, "actor.mu_.weight" },            { w->mu_b, 2, "actor.mu_.bias" },
-            { w->std_w, (size_t)2 * hd, "actor.std_.weight" },          { w->std_b, 2, "actor.std_.bias" },
-            { w->critic_w1, (size_t)hd * hd, "critic.0.weight" },       { w->critic_b1, (size_t)hd, "critic.0.bias" },
-            { w->critic_w2, (size_t)hd, "critic.2.weight" },            { w->critic_b2, 1, "critic.2.bias" },
-            { w->critic_sigma_w, (size_t)hd, "critic_sigma.weight" },   { w->critic_sigma_b, 1, "critic_sigma.bias" } };
-        for (const auto &a : all)
-            for (size_t i = 0; a.t && i < a.n; ++i)
-                if (!(std::fabs(a.t[i]) < 32768.0f))
-                    return fail(ZENV_E_RANGE, "%s[%zu] = %g: ZENV_MLP_F16X3 keeps weights as float16 pairs (|w| < 32 768); use "
-                                              "ZENV_MLP_BF16X3 or ZENV_MLP_F32", a.name, i, (double)a.t[i]);
-    }
-    std::vector<uint16_t> img;
-    size_t offs[8];
-    if (pack_images(*w, h->p.F, img, offs, w->precision == ZENV_MLP_F16) != 0)
-        return fail(ZENV_E_ARG, "h_dim %d outside [1, %d]", w->h_dim, kMlpHP - 1);
-    if (w->precision == ZENV_MLP_F16)        // zone_net_.4 folded into combine_net_: a product that can leave the range
-        for (size_t i = 0; i < img.size(); ++i)
-            if ((img[i] & 0x7C00u) == 0x7C00u)
-                return fail(ZENV_E_RANGE, "combine_net_ folded over zone_net_.4 leaves float16's range: use ZENV_MLP_BF16 or "
-                                          "a split mode for these weights");
-    std::vector<float> f32;         // the float32-grade modes' images (packed before the handle is touched: it can refuse)
-    size_t fo[30];
-    const bool f32_grade = w->precision != ZENV_MLP_BF16 && w->precision != ZENV_MLP_F16;
-    if (f32_grade) {
-        pack_f32(*w, h->p.F, f32, fo);
-        if (w->precision == ZENV_MLP_F16X3) {
-            // the float16 images start at fo[24] (zone_net_.2): combine_net_ arrives with zone_net_.4 folded in, a product of
-            // two in-range matrices that need not be in range itself
-            const uint16_t *hw = reinterpret_cast<const uint16_t *>(f32.data() + fo[24]);
-            const size_t n16 = (f32.size() - fo[24]) * 2;
-            for (size_t i = 0; i < n16; ++i)
-                if ((hw[i] & 0x7C00u) == 0x7C00u)
-                    return fail(ZENV_E_RANGE, "combine_net_ folded over zone_net_.4 leaves float16's range: use ZENV_MLP_BF16X3 "
-                                              "or ZENV_MLP_F32 for these weights");
-        }
-    }
-    int rc = use_device(h);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    const size_t N = (size_t)h->n_env;
-    h->mlp_ready = false;
-    if (h->mlp_mem) HIP_TRY(hipFree(h->mlp_mem));   // its size depends on whether there is a critic
-    h->mlp_mem = nullptr;
-    if (h->mlp_f32_mem) HIP_TRY(hipFree(h->mlp_f32_mem));
-    h->mlp_f32_mem = nullptr;
-    HIP_TRY(hipMalloc(&h->mlp_mem, img.size() * 2));
-    if (!h->mlp_value) HIP_TRY(hipMalloc((void **)&h->mlp_value, N * sizeof(float)));
-    HIP_TRY(hipMemsetAsync(h->mlp_value, 0, N * sizeof(float), h->stream));
-    if (!h->mlp_value_sigma) HIP_TRY(hipMalloc((void **)&h->mlp_value_sigma, N * sizeof(float)));
-    HIP_TRY(hipMemsetAsync(h->mlp_value_sigma, 0, N * sizeof(float), h->stream));
-    if (!h->mlp_pooled) HIP_TRY(hipMalloc(&h->mlp_pooled, N * kMlpHP * sizeof(uint16_t)));
-    if (!h->mlp_mu) HIP_TRY(hipMalloc((void **)&h->mlp_mu, N * 2 * sizeof(float)));
-    if (!h->mlp_std) HIP_TRY(hipMalloc((void **)&h->mlp_std, N * 2 * sizeof(float)));
-    HIP_TRY(hipMemcpy(h->mlp_mem, img.data(), img.size() * 2, hipMemcpyHostToDevice));
-    const char *base = static_cast<const char *>(h->mlp_mem);
-    h->mlp = MlpImages{ base + offs[0], base + offs[1], base + offs[2], base + offs[3], base + offs[4], base + offs[5],
-                        n_critic ? base + offs[6] : nullptr, n_critic ? base + offs[7] : nullptr, nullptr,
-                        n_sigma == 2 ? 1 : 0, 0, nullptr };
-    if (w->precision != ZENV_MLP_BF16 && !h->mlp_range_flag) {
-        HIP_TRY(hipHostMalloc((void **)&h->mlp_range_flag, sizeof(int), hipHostMallocDefault));
-        *h->mlp_range_flag = 0;
-    }
-    if (w->precision == ZENV_MLP_F16) {
-        h->mlp.elem_f16 = 1;
-        h->mlp.range_flag = h->mlp_range_flag;
-    }
-    if (f32_grade) {
-        // (diagnostic: ZENV_MLP_F32_VALU=1 runs the network on the vector ALU, k_mlp_f32, instead of the f32 MFMA)
-        // ZENV_MLP_F32_MFMA=1 the MFMA kernel whatever the batch; default: by batch size, see launch_mlp_forward_f32)
-        const int on_mfma = std::getenv("ZENV_MLP_F32_VALU") ? 0 : std::getenv("ZENV_MLP_F32_MFMA") ? 2 : 1;
-        HIP_TRY(hipMalloc(&h->mlp_f32_mem, f32.size() * sizeof(float)));
-        HIP_TRY(hipMemcpy(h->mlp_f32_mem, f32.data(), f32.size() * sizeof(float), hipMemcpyHostToDevice));
-        const float *fb = static_cast<const float *>(h->mlp_f32_mem);
-        h->mlp_f32 = MlpF32{ w->h_dim, n_sigma == 2 ? 1 : 0, n_critic ? 1 : 0, 0,
-                             fb + fo[0], fb + fo[1], fb + fo[2], fb + fo[3], fb + fo[4], fb + fo[5], fb + fo[6],
-                             fb + fo[7], fb + fo[8], fb + fo[9], n_critic ? fb + fo[10] : nullptr,
-                             n_critic ? fb + fo[11] : nullptr, fb + fo[12], fb + fo[13], fb + fo[14], fb + fo[15], fb + fo[16], fb + fo[17], fb + fo[18],
-                             n_critic ? fb + fo[19] : nullptr, n_critic ? fb + fo[20] : nullptr, on_mfma,
-                             w->precision == ZENV_MLP_BF16X3 ? 1 : w->precision == ZENV_MLP_F16X3 ? 2 : 0,
-                             fb + fo[21], fb + fo[22], fb + fo[23], fb + fo[24], fb + fo[25],
-                             n_critic ? fb + fo[26] : nullptr, fb + fo[27], fb + fo[28], n_critic ? fb + fo[29] : nullptr,
-                             h->mlp_range_flag };
-        h->mlp.f32 = &h->mlp_f32;
-    }
-    h->mlp_ready = true;
-    return ZENV_OK;
-}
-
-extern "C" int zenv_mlp_forward(zenv_t *h)
-{
-    if (!h) return fail(ZENV_E_ARG, "null handle");
-    if (!h->mlp_ready) return fail(ZENV_E_STATE, "zenv_mlp_load first");
-    if (!h->was_reset) return fail(ZENV_E_STATE, "reset before asking for actions");
-    int rc = use_device(h);
-    if (rc) return rc;
-    HIP_TRY(launch_mlp_forward(h->mlp, h->n_env, h->p.Z, h->p.F, h->p.obs, h->p.zone_obs, h->mlp_pooled, h->mlp_mu,
-                               h->mlp_std, h->mlp_value, h->mlp_value_sigma, no_mlp_action(), h->stream));
-    return ZENV_OK;
-}
-
-// ============================================================================ Zone-goals hierarchical agent
-extern "C" int zenv_hier_load(zenv_t *h, const zenv_hier_weights *w)
-{
-    if (!h || !w) return fail(ZENV_E_ARG, "null argument");
-    if (!h->goal_enabled) return fail(ZENV_E_STATE, "the hierarchical agent sets goals: zenv_goal_enable first");
-    if (w->h_dim < 1 || w->h_dim >= kMlpHP) return fail(ZENV_E_ARG, "h_dim %d outside 1 .. %d", w->h_dim, kMlpHP - 1);
-    if (w->precision != ZENV_MLP_F32)
-        return fail(ZENV_E_ARG, "zenv_hier_weights.precision %d: only ZENV_MLP_F32 is built", w->precision);
-    if (w->zone_feat != h->p.F)
-        return fail(ZENV_E_ARG, "the weights take zone rows of %d features, this handle's have %d", w->zone_feat, h->p.F);
-    for (const float *t : { w->hi_zone_w1, w->hi_zone_b1, w->hi_zone_w2, w->hi_zone_b2, w->hi_zone_w3, w->hi_zone_b3,
-                            w->hi_comb_w, w->hi_comb_b, w->hi_actor_w1, w->hi_actor_b1, w->hi_actor_w2, w->hi_actor_b2,
-                            w->lo_zone_w1, w->lo_zone_b1, w->lo_zone_w2, w->lo_zone_b2, w->lo_zone_w3, w->lo_zone_b3,
-                            w->lo_comb_w, w->lo_comb_b, w->lo_enc_w, w->lo_enc_b, w->lo_mu_w, w->lo_mu_b, w->lo_std_w,
-                            w->lo_std_b })
-        if (!t) return fail(ZENV_E_ARG, "zenv_hier_weights has a null tensor");
-    const int n_hc = (w->hi_critic_w1 != nullptr) + (w->hi_critic_b1 != nullptr) + (w->hi_critic_w2 != nullptr) +
-                     (w->hi_critic_b2 != nullptr);
-    const int n_lc = (w->lo_critic_w1 != nullptr) + (w->lo_critic_b1 != nullptr) + (w->lo_critic_w2 != nullptr) +
-                     (w->lo_critic_b2 != nullptr);
-    if ((n_hc != 0 && n_hc != 4) || (n_lc != 0 && n_lc != 4))
-        return fail(ZENV_E_ARG, "give all four tensors of a critic or none");
-    std::vector<float> img;
-    size_t o[kHierOffs];
-    pack_hier_f32(*w, h->p.F, img, o);
-    int rc = use_device(h);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    const size_t N = (size_t)h->n_env;
-    h->hier_ready = false;
-    if (h->hier_mem) HIP_TRY(hipFree(h->hier_mem));
-    h->hier_mem = nullptr;
-    HIP_TRY(hipMalloc(&h->hier_mem, img.size() * sizeof(float)));
-    HIP_TRY(hipMemcpy(h->hier_mem, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
-    // the low level writes the flat network's output fields (ZENV_F_POLICY_*): allocated by whichever loads first
-    if (!h->mlp_value) HIP_TRY(hipMalloc((void **)&h->mlp_value, N * sizeof(float)));
-    if (!h->mlp_mu) HIP_TRY(hipMalloc((void **)&h->mlp_mu, N * 2 * sizeof(float)));
-    if (!h->mlp_std) HIP_TRY(hipMalloc((void **)&h->mlp_std, N * 2 * sizeof(float)));
-    if (!h->hier_logits) HIP_TRY(hipMalloc((void **)&h->hier_logits, N * h->p.Z * sizeof(float)));
-    if (!h->hier_value) HIP_TRY(hipMalloc((void **)&h->hier_value, N * sizeof(float)));
-    HIP_TRY(hipMemsetAsync(h->hier_logits, 0, N * h->p.Z * sizeof(float), h->stream));
-    HIP_TRY(hipMemsetAsync(h->hier_value, 0, N * sizeof(float), h->stream));
-    const float *b = static_cast<const float *>(h->hier_mem);
-    auto P = [&](int i) { return o[i] ? b + o[i] : nullptr; };   // offset 0 only for an absent critic (the image starts
-                                                                 // with hi.w1x)
-    HierF32 &hw = h->hier;
-    hw.h = w->h_dim;
-    hw.hi_critic = n_hc ? 1 : 0;
-    hw.lo_critic = n_lc ? 1 : 0;
-    hw.pad = 0;
-    HierEnc *enc[2] = { &hw.hi, &hw.lo };
-    for (int l = 0; l < 2; ++l) {
-        const int k = 10 * l;
-        *enc[l] = HierEnc{ b + o[k], P(k + 1), P(k + 2), P(k + 3), P(k + 4), P(k + 5), P(k + 6), P(k + 7), P(k + 8), P(k + 9) };
-    }
-    hw.hae = P(20); hw.haz = P(21); hw.hab = P(22); hw.ha2 = P(23);
-    hw.hv1t = P(24); hw.hv1b = P(25); hw.hv2 = P(26);
-    hw.encw = P(27); hw.encb = P(28); hw.heads = P(29);
-    hw.lv1t = P(30); hw.lv1b = P(31); hw.lv2 = P(32);
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    h->hier_ready = true;
-    return ZENV_OK;
-}
-
-extern "C" int zenv_hier_forward(zenv_t *h)
-{
-    if (!h) return fail(ZENV_E_ARG, "null handle");
-    if (!h->hier_ready) return fail(ZENV_E_STATE, "zenv_hier_load first");
-    if (!h->was_reset) return fail(ZENV_E_STATE, "reset before asking for actions");
-    int rc = use_device(h);
-    if (rc) return rc;
-    const HierPick none{ -1, 0u, 0ull, 0ull, nullptr };
-    HIP_TRY(launch_hier_high(h->hier, h->p, h->hier_logits, h->hier_value, none, h->stream));
-    HIP_TRY(launch_hier_low(h->hier, h->p, h->mlp_mu, h->mlp_std, h->mlp_value, no_mlp_action(), h->stream));
-    return ZENV_OK;
-}
-
-// one step of evaluate_zone_hrl.py:56-64: goals for the envs that need one (through launch_goal_set, the path of
-// zenv_set_goals), then the low level's action of every env into `out`
-static int run_hier_policy(zenv_t *h, int policy, uint32_t step_index, uint64_t seed, uint64_t env_index0, float *out)
-{
-    if (!h->hier_ready) return fail(ZENV_E_STATE, "zenv_hier_load first");
-    const int mode = policy == ZENV_POLICY_HIER_SAMPLE ? 1 : 0;
-    const HierPick pick{ mode, step_index, seed, env_index0, h->goal_in };
-    HIP_TRY(launch_hier_high(h->hier, h->p, h->hier_logits, h->hier_value, pick, h->stream));
-    HIP_TRY(launch_goal_set(h->p, h->goal_in, h->goal_bad, h->stream));
-    const MlpAction act{ mode, step_index, seed, env_index0, out, MlpRecord{} };
-    HIP_TRY(launch_hier_low(h->hier, h->p, h->mlp_mu, h->mlp_std, h->mlp_value, act, h->stream));
-    return ZENV_OK;
-}
-
-// ============================================================================ fixed-length-skills agent
-// zenv_skill_load (n_out = 2) and zenv_option_load (n_out = 3: the rows of lo_mu_w / lo_std_w)
-static int load_skill_family(zenv_t *h, const zenv_skill_weights *w, int n_out)
-{
-    if (h->goal_enabled || h->order_enabled)
-        return fail(ZENV_E_STATE, "the skill agent steps a plain task handle, not a goal-conditioned / solver-ordered one");
-    if (w->h_dim < 1 || w->h_dim >= kMlpHP) return fail(ZENV_E_ARG, "h_dim %d outside 1 .. %d", w->h_dim, kMlpHP - 1);
-    if (w->n_skills < 1 || w->n_skills > kMaxSkills)
-        return fail(ZENV_E_ARG, "n_skills %d outside 1 .. %d", w->n_skills, kMaxSkills);
-    if (w->precision != ZENV_MLP_F32)
-        return fail(ZENV_E_ARG, "zenv_skill_weights.precision %d: only ZENV_MLP_F32 is built", w->precision);
-    if (w->zone_feat != h->p.F)
-        return fail(ZENV_E_ARG, "the weights take zone rows of %d features, this handle's have %d", w->zone_feat, h->p.F);
-    for (const float *t : { w->hi_zone_w1, w->hi_zone_b1, w->hi_zone_w2, w->hi_zone_b2, w->hi_zone_w3, w->hi_zone_b3,
-                            w->hi_comb_w, w->hi_comb_b, w->hi_enc_w, w->hi_enc_b, w->hi_logit_w, w->hi_logit_b,
-                            w->lo_zone_w1, w->lo_zone_b1, w->lo_zone_w2, w->lo_zone_b2, w->lo_zone_w3, w->lo_zone_b3,
-                            w->lo_comb_w, w->lo_comb_b, w->lo_enc_w, w->lo_enc_b, w->lo_mu_w, w->lo_mu_b, w->lo_std_w,
-                            w->lo_std_b })
-        if (!t) return fail(ZENV_E_ARG, "the weights have a null actor tensor");
-    const int n_hc = (w->hi_critic_w1 != nullptr) + (w->hi_critic_b1 != nullptr) + (w->hi_critic_w2 != nullptr) +
-                     (w->hi_critic_b2 != nullptr);
-    const int n_lc = (w->lo_critic_w1 != nullptr) + (w->lo_critic_b1 != nullptr) + (w->lo_critic_w2 != nullptr) +
-                     (w->lo_critic_b2 != nullptr);
-    if ((n_hc != 0 && n_hc != 4) || (n_lc != 0 && n_lc != 4))
-        return fail(ZENV_E_ARG, "give all four tensors of a critic or none");
-    std::vector<float> img;
-    size_t o[kSkillPtrs];
-    pack_skill_f32(*w, h->p.F, img, o, n_out);
-    int rc = use_device(h);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    const size_t N = (size_t)h->n_env, S = (size_t)w->n_skills;
-    h->skill_ready = h->option_ready = false;           // a handle holds one agent of the skill family
-    if (h->skill_mem) HIP_TRY(hipFree(h->skill_mem));
-    h->skill_mem = nullptr;
-    HIP_TRY(hipMalloc(&h->skill_mem, img.size() * sizeof(float)));
-    HIP_TRY(hipMemcpy(h->skill_mem, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
-    // the low level writes the flat network's output fields (ZENV_F_POLICY_*): allocated by whichever loads first
-    if (!h->mlp_value) HIP_TRY(hipMalloc((void **)&h->mlp_value, N * sizeof(float)));
-    if (!h->mlp_mu) HIP_TRY(hipMalloc((void **)&h->mlp_mu, N * 2 * sizeof(float)));
-    if (!h->mlp_std) HIP_TRY(hipMalloc((void **)&h->mlp_std, N * 2 * sizeof(float)));
-    if (h->skill_logits && h->skill_n != (int)S) {
-        HIP_TRY(hipFree(h->skill_logits));
-        h->skill_logits = nullptr;
-    }
-    if (!h->skill_logits) HIP_TRY(hipMalloc((void **)&h->skill_logits, N * S * sizeof(float)));
-    h->skill_n = (int)S;
-    if (!h->skill_value) HIP_TRY(hipMalloc((void **)&h->skill_value, N * sizeof(float)));
-    if (!h->sst_mem) {
-        HIP_TRY(hipMalloc(&h->sst_mem, 5 * N * sizeof(int32_t)));
-        int32_t *m = static_cast<int32_t *>(h->sst_mem);
-        h->sst = SkillState{ m, m + N, m + 2 * N, m + 3 * N, m + 4 * N };
-    }
-    if (n_out == 3 && !h->opt_mem) {
-        HIP_TRY(hipMalloc(&h->opt_mem, (5 * N + 1) * 4));
-        float *m = static_cast<float *>(h->opt_mem);
-        h->oterm = OptionTerm{ m, m + N, m + 2 * N, m + 3 * N };
-        h->olist.list = reinterpret_cast<int32_t *>(m + 4 * N);
-        h->olist.count = h->olist.list + N;
-    }
-    if (h->opt_mem) HIP_TRY(hipMemsetAsync(h->opt_mem, 0, (5 * N + 1) * 4, h->stream));
-    HIP_TRY(hipMemsetAsync(h->skill_logits, 0, N * S * sizeof(float), h->stream));
-    HIP_TRY(hipMemsetAsync(h->skill_value, 0, N * sizeof(float), h->stream));
-    HIP_TRY(launch_skill_sync(h->p, h->sst, nullptr, 1, h->stream));     // every env: no skill (the new S may be smaller)
-    h->skill = skill_f32_at(*w, static_cast<const float *>(h->skill_mem), o);
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    (n_out == 3 ? h->option_ready : h->skill_ready) = true;
-    if (n_out == 3 || (h->skinv_ready && (h->skinv.h != w->h_dim || h->skinv.S != w->n_skills))) h->skinv_ready = false;
-    return ZENV_OK;
-}
-
-extern "C" int zenv_skill_load(zenv_t *h, const zenv_skill_weights *w)
-{
-    if (!h || !w) return fail(ZENV_E_ARG, "null argument");
-    return load_skill_family(h, w, 2);
-}
-
-extern "C" int zenv_skill_inverse_load(zenv_t *h, const zenv_skill_inverse_weights *w)
-{
-    if (!h || !w) return fail(ZENV_E_ARG, "null argument");
-    if (!h->skill_ready) return fail(ZENV_E_STATE, "zenv_skill_load first (the inverse model takes its shapes)");
-    if (w->h_dim != h->skill.h || w->n_skills != h->skill.S || w->zone_feat != h->p.F)
-        return fail(ZENV_E_ARG, "inverse model h_dim %d, n_skills %d, zone_feat %d: the skill weights have %d, %d, %d",
-                    w->h_dim, w->n_skills, w->zone_feat, h->skill.h, h->skill.S, h->p.F);
-    if (w->precision != ZENV_MLP_F32)
-        return fail(ZENV_E_ARG, "zenv_skill_inverse_weights.precision %d: only ZENV_MLP_F32 is built", w->precision);
-    for (const float *t : { w->zone_w1, w->zone_b1, w->zone_w2, w->zone_b2, w->zone_w3, w->zone_b3, w->comb_w1,
-                            w->comb_b1, w->comb_w2, w->comb_b2 })
-        if (!t) return fail(ZENV_E_ARG, "zenv_skill_inverse_weights has a null tensor");
-    std::vector<float> img;
-    size_t o[kSkillInvPtrs];
-    pack_skill_inverse_f32(*w, h->p.F, img, o);
-    int rc = use_device(h);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    h->skinv_ready = false;
-    if (h->skinv_mem) HIP_TRY(hipFree(h->skinv_mem));
-    h->skinv_mem = nullptr;
-    HIP_TRY(hipMalloc(&h->skinv_mem, img.size() * sizeof(float)));
-    HIP_TRY(hipMemcpy(h->skinv_mem, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
-    h->skinv = skill_inverse_f32_at(*w, static_cast<const float *>(h->skinv_mem), o);
-    h->skinv_ready = true;
-    return ZENV_OK;
-}
-
-extern "C" int zenv_skill_configure(zenv_t *h, int skill_len)
-{
-    if (!h) return fail(ZENV_E_ARG, "null handle");
-    if (skill_len < 1) return fail(ZENV_E_ARG, "skill_len %d: must be >= 1", skill_len);
-    h->skill_len = skill_len;
-    return ZENV_OK;
-}
-
-extern "C" int zenv_set_skills(zenv_t *h, const int32_t *skills)
-{
-    if (!h || !skills) return fail(ZENV_E_ARG, "null argument");
-    if (!h->skill_ready && !h->option_ready) return fail(ZENV_E_STATE, "zenv_skill_load or zenv_option_load first");
-    for (int i = 0; i < h->n_env; ++i)
-        if (skills[i] < -1 || skills[i] >= h->skill_n)
-            return fail(ZENV_E_ARG, "env %d: skill %d outside -1 .. %d", i, skills[i], h->skill_n - 1);
-    int rc = use_device(h);
-    if (rc) return rc;
-    HIP_TRY(launch_skill_sync(h->p, h->sst, nullptr, 0, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->sst.in, skills, sizeof(int32_t) * (size_t)h->n_env, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(launch_skill_set(h->p, h->sst, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));      // `skills` is the caller's (pageable) memory
-    return ZENV_OK;
-}
-
-extern "C" int zenv_skill_forward(zenv_t *h)
-{
-    if (!h) return fail(ZENV_E_ARG, "null handle");
-    if (!h->skill_ready) return fail(ZENV_E_STATE, "zenv_skill_load first");
-    if (!h->was_reset) return fail(ZENV_E_STATE, "reset before asking for actions");
-    int rc = use_device(h);
-    if (rc) return rc;
-    HIP_TRY(launch_skill_sync(h->p, h->sst, nullptr, 0, h->stream));
-    const SkillPick none{ -1, h->skill_len, 0u, 0ull, 0ull, 0, nullptr, SkillRecord{} };
-    HIP_TRY(launch_skill_high(h->skill, h->p, h->sst, h->skill_logits, h->skill_value, none, h->stream));
-    HIP_TRY(launch_skill_low(h->skill, h->p, h->sst, h->mlp_mu, h->mlp_std, h->mlp_value, no_mlp_action(), h->stream));
-    return ZENV_OK;
-}
-
-// one step of evaluate_hier.py:63-67: a skill for the envs whose skill ran out (or that have none), then the low level's
-// action of every env into `out`
-static int run_skill_policy(zenv_t *h, int policy, uint32_t step_index, uint64_t seed, uint64_t env_index0, float *out)
-{
-    if (!h->skill_ready) return fail(ZENV_E_STATE, "zenv_skill_load first");
-    const int mode = policy == ZENV_POLICY_SKILL_SAMPLE ? 1 : 0;
-    HIP_TRY(launch_skill_sync(h->p, h->sst, nullptr, 0, h->stream));
-    const SkillPick pick{ mode, h->skill_len, step_index, seed, env_index0, 0, nullptr, SkillRecord{} };
-    HIP_TRY(launch_skill_high(h->skill, h->p, h->sst, h->skill_logits, h->skill_value, pick, h->stream));
-    const MlpAction act{ mode, step_index, seed, env_index0, out, MlpRecord{} };
-    HIP_TRY(launch_skill_low(h->skill, h->p, h->sst, h->mlp_mu, h->mlp_std, h->mlp_value, act, h->stream));
-    return ZENV_OK;
-}
-
-// ============================================================================ variable-length Options agent
-extern "C" int zenv_option_load(zenv_t *h, const zenv_option_weights *w)
-{
-    if (!h || !w) return fail(ZENV_E_ARG, "null argument");
-    // the same members in the same order: only the rows of lo_mu_* / lo_std_* differ
-    static_assert(sizeof(zenv_option_weights) == sizeof(zenv_skill_weights), "zenv_option_weights layout");
-    zenv_skill_weights sw;
-    std::memcpy(&sw, w, sizeof sw);
-    int rc = load_skill_family(h, &sw, 3);
-    if (rc) return rc;
-    // diagnostic: how the high level finds the envs that pick; the results are the same
-    const char *e = std::getenv("ZENV_OPTION_COMPACT");
-    h->option_compact = e ? std::atoi(e) != 0 : h->n_env > kOptionCompactMinEnvs;
-    return ZENV_OK;
-}
-
-extern "C" int zenv_option_forward(zenv_t *h)
-{
-    if (!h) return fail(ZENV_E_ARG, "null handle");
-    if (!h->option_ready) return fail(ZENV_E_STATE, "zenv_option_load first");
-    if (!h->was_reset) return fail(ZENV_E_STATE, "reset before asking for actions");
-    int rc = use_device(h);
-    if (rc) return rc;
-    HIP_TRY(launch_skill_sync(h->p, h->sst, nullptr, 0, h->stream));
-    const OptionPick none{ -1, 0, 0u, 0ull, 0ull };
-    HIP_TRY(launch_option_high(h->skill, h->p, h->sst, h->olist, h->skill_logits, h->skill_value, none, h->stream));
-    HIP_TRY(launch_option_low(h->skill, h->p, h->sst, h->olist, h->mlp_mu, h->mlp_std, h->mlp_value, h->oterm,
-                              no_mlp_action(), h->stream));
-    return ZENV_OK;
-}
-
-// one step of options/scripts/evaluate_hier.py:63-75: a skill for the envs that have none or whose option ended, then
-// the low level's action of every env into `out` and the termination draw
-static int run_option_policy(zenv_t *h, int policy, uint32_t step_index, uint64_t seed, uint64_t env_index0, float *out)
-{
-    if (!h->option_ready) return fail(ZENV_E_STATE, "zenv_option_load first");
-    const int mode = policy == ZENV_POLICY_OPTION_SAMPLE ? 1 : 0;
-    HIP_TRY(launch_skill_sync(h->p, h->sst, nullptr, 0, h->stream));
-    const OptionPick pick{ mode, h->option_compact, step_index, seed, env_index0 };
-    if (pick.compact) HIP_TRY(launch_option_list(h->p, h->sst, h->olist, h->stream));
-    HIP_TRY(launch_option_high(h->skill, h->p, h->sst, h->olist, h->skill_logits, h->skill_value, pick, h->stream));
-    const MlpAction act{ mode, step_index, seed, env_index0, out, MlpRecord{} };
-    HIP_TRY(launch_option_low(h->skill, h->p, h->sst, h->olist, h->mlp_mu, h->mlp_std, h->mlp_value, h->oterm, act,
-                              h->stream));
-    return ZENV_OK;
-}
-
-static bool policy_known(int policy) { return policy >= ZENV_POLICY_UNIFORM && policy <= ZENV_POLICY_MLP_SAMPLE; }
-static bool policy_is_mlp(int policy) { return policy == ZENV_POLICY_MLP_MEAN || policy == ZENV_POLICY_MLP_SAMPLE; }
-
-// a_t = pi(obs_t, t) into pol.out, for every kind of action source
-static int run_policy(zenv_t *h, const StepPolicy &pol, const MlpRecord *rec = nullptr)
-{
-    if (!policy_is_mlp(pol.policy)) {
-        HIP_TRY(launch_policy(h->p, pol, h->stream));
-        return ZENV_OK;
-    }
-    if (!h->mlp_ready) return fail(ZENV_E_STATE, "zenv_mlp_load first");
-    // the head kernel also turns (mu, std) into the action
-    const MlpAction act{ pol.policy == ZENV_POLICY_MLP_SAMPLE ? 1 : 0, pol.step_index, pol.seed, pol.env_index0, pol.out,
-                         rec ? *rec : MlpRecord{} };
-    HIP_TRY(launch_mlp_forward(h->mlp, h->n_env, h->p.Z, h->p.F, h->p.obs, h->p.zone_obs, h->mlp_pooled, h->mlp_mu,
-                               h->mlp_std, h->mlp_value, h->mlp_value_sigma, act, h->stream));
-    return ZENV_OK;
-}
-
-// A ring schedule is only as deep as its `depth` slots per env, and only the HOST refills them (zenv_bank_update), between
-// calls: an env ends at most one episode per auto-resetting step, so a call of up to `depth` such steps cannot outrun
-// its ring; a longer one could wrap onto maps it has already played -- silently.  Refused instead.  `steps` counts the
-// call's auto-resets per env: its steps, frames, or skill windows (zenv_collect_skill resets on a window's last frame).
-static int ring_guard(const zenv *h, int steps, int auto_reset_every_step)
-{
-    if (h->p.sched_mode == SCHED_RING && auto_reset_every_step && steps > h->p.sched_stride)
-        return fail(ZENV_E_STATE, "a ring schedule of depth %d is refilled by the host between calls: %d auto-resetting "
-                    "steps in one call could replay maps (use calls of at most `depth` steps with zenv_bank_update in "
-                    "between, a deeper ring, or a sequential schedule)", h->p.sched_stride, steps);
-    return ZENV_OK;
-}
-
-// ============================================================================ experience collection
-// the three collectors' discount and gae_lambda: finite and in [0, 1] (a NaN would turn every advantage into NaN)
-static int gae_args(float discount, float gae_lambda)
-{
-    if (!std::isfinite(discount) || !std::isfinite(gae_lambda))
-        return fail(ZENV_E_ARG, "discount %g and gae_lambda %g must be finite", discount, gae_lambda);
-    if (discount < 0.f || discount > 1.f || gae_lambda < 0.f || gae_lambda > 1.f)
-        return fail(ZENV_E_ARG, "discount %g and gae_lambda %g must lie in [0, 1]", discount, gae_lambda);
-    return ZENV_OK;
-}
-
-// the ZENV_F_EXP_* buffers for T frames (zenv_collect, zenv_collect_hier); self.mask survives a change of T
-static int ensure_exp(zenv_t *h, int T)
-{
-    const size_t N = (size_t)h->n_env, ZF = (size_t)h->p.Z * h->p.F;
-    if (!h->exp_mem || h->exp.T != T) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        std::vector<float> keep_mask;
-        if (h->exp_mem) {       // self.mask survives a change of T
-            keep_mask.resize(N);
-            HIP_TRY(hipMemcpy(keep_mask.data(), h->exp.cur_mask, N * 4, hipMemcpyDeviceToHost));
-            HIP_TRY(hipFree(h->exp_mem));
-            h->exp_mem = nullptr;
-        }
-        const size_t per_slot = 8 + ZF + 2 + 2 + 5;            // floats per (env, t)
-        const size_t total = N * (size_t)T * per_slot + N;
-        HIP_TRY(hipMalloc(&h->exp_mem, total * sizeof(float)));
-        float *f = static_cast<float *>(h->exp_mem);
-        ExpBuffers &x = h->exp;
-        x.T = T;
-        x.obs = f;            f += N * T * 8;
-        x.zone_obs = f;       f += N * T * ZF;
-        x.action = f;         f += N * T * 2;
-        x.log_prob = f;       f += N * T * 2;
-        x.value = f;          f += N * T;
-        x.reward = f;         f += N * T;
-        x.mask = f;           f += N * T;
-        x.advantage = f;      f += N * T;
-        x.returnn = f;        f += N * T;
-        x.cur_mask = f;
-        if (keep_mask.empty()) keep_mask.assign(N, 1.0f);      // base.py:96 self.mask = ones
-        HIP_TRY(hipMemcpy(x.cur_mask, keep_mask.data(), N * 4, hipMemcpyHostToDevice));
-    }
-    return ZENV_OK;
-}
-
-extern "C" int zenv_collect(zenv_t *h, int T, uint64_t policy_seed, uint64_t env_index0, float discount, float gae_lambda)
-{
-    if (!h) return fail(ZENV_E_ARG, "null handle");
-    if (T < 1) return fail(ZENV_E_ARG, "frames_per_proc must be positive");
-    if ((int64_t)T * h->n_env > INT32_MAX) return fail(ZENV_E_ARG, "frames_per_proc x envs must stay below 2^31");
-    if (int ra = gae_args(discount, gae_lambda)) return ra;
-    if (!h->was_reset) return fail(ZENV_E_STATE, "Environment must be reset before stepping");
-    if (!h->mlp_ready || !h->mlp.wv1) return fail(ZENV_E_STATE, "zenv_mlp_load with actor and critic weights first");
-    if (h->host_io_slab) return fail(ZENV_E_STATE, "zenv_collect records on the device: switch zenv_host_io off first");
-    if (h->order_enabled)
-        return fail(ZENV_E_STATE, "solver-ordered envs are stepped with zenv_step (their order feature is not part of "
-                                  "the network input this call evaluates)");
-    if (int rr = ring_guard(h, T, 1)) return rr;           // every frame auto-resets
-    int rc = use_device(h);
-    if (rc) return rc;
-    const size_t N = (size_t)h->n_env, ZF = (size_t)h->p.Z * h->p.F;
-    h->act_tag.valid = false;
-    rc = ensure_exp(h, T);
-    if (rc) return rc;
-    // The observations are recorded where they are produced: the policy of frame t reads slot t, the step kernel
-    // of frame t writes obs_{t+1} into slot t+1 (the last one into the handle's own buffers again).
-    struct ObsRedirect {
-        zenv_t *h;
-        float *obs, *zone_obs;
-        ~ObsRedirect() { h->p.obs = obs; h->p.zone_obs = zone_obs; }
-    } home{ h, h->p.obs, h->p.zone_obs };
-    HIP_TRY(hipMemcpyAsync(h->exp.obs, home.obs, N * 8 * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->exp.zone_obs, home.zone_obs, N * ZF * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    for (int t = 0; t < T; ++t) {
-        h->p.obs = h->exp.obs + (size_t)t * N * 8;
-        h->p.zone_obs = h->exp.zone_obs + (size_t)t * N * ZF;
-        StepPolicy pol{ ZENV_POLICY_MLP_SAMPLE, (uint32_t)h->step_count, policy_seed, env_index0, h->p.actions };
-        // dist, value = acmodel(obs); action = dist.sample(); the head kernel also records frame t (and the reward
-        // of frame t-1, still in the env's reward / done buffers)
-        const MlpRecord rec{ h->exp.action, h->exp.log_prob, h->exp.value, h->exp.mask, h->exp.reward, h->exp.cur_mask,
-                             h->p.reward, h->goal_enabled ? h->p.shaped : nullptr, h->p.done_out, T, t, h->n_env };
-        rc = run_policy(h, pol, &rec);
-        if (rc) return rc;
-        h->p.obs = t + 1 < T ? h->exp.obs + (size_t)(t + 1) * N * 8 : home.obs;
-        h->p.zone_obs = t + 1 < T ? h->exp.zone_obs + (size_t)(t + 1) * N * ZF : home.zone_obs;
-        HIP_TRY(launch_step(h->p, h->p.actions, 1, no_policy(), h->stream));     // ParallelEnv.step: auto-reset
-        if (h->goal_enabled) HIP_TRY(launch_goal_step(h->p, h->stream));
-        h->step_count += 1;
-    }
-    HIP_TRY(launch_exp_reward(h->exp, h->n_env, T - 1, h->p.reward, h->goal_enabled ? h->p.shaped : nullptr,
-                              h->p.done_out, h->stream));
-    // next_value = value(obs_T) (:177-187), then the GAE recursion
-    HIP_TRY(launch_mlp_forward(h->mlp, h->n_env, h->p.Z, h->p.F, h->p.obs, h->p.zone_obs, h->mlp_pooled, h->mlp_mu,
-                               h->mlp_std, h->mlp_value, h->mlp_value_sigma, no_mlp_action(), h->stream));
-    HIP_TRY(launch_exp_gae(h->exp, h->n_env, h->mlp_value, discount, gae_lambda, h->stream));
-    return ZENV_OK;
-}
-
-// ---- zenv_collect_hier: collect_experiences of the Zone-goals agent (zone-goals/src/torch_ac/algos/_hier_policy_opt.py)
-// the per-frame records for T frames; the state carried from call to call is allocated (and zeroed) once
-static int ensure_hier_collect(zenv_t *h, int T)
-{
-    const size_t N = (size_t)h->n_env, ZF = (size_t)h->p.Z * h->p.F;
-    if (!h->hcarry_mem) {
-        const size_t bytes = N * (4 + 1 + 8 * 4 + ZF * 4 + 4 + 4 + 4 + 4 + 8) + 9 * 256;
-        HIP_TRY(hipMalloc(&h->hcarry_mem, bytes));
-        HIP_TRY(hipMemsetAsync(h->hcarry_mem, 0, bytes, h->stream));
-        char *b = static_cast<char *>(h->hcarry_mem);
-        auto take = [&](size_t n) { char *at = b; b += (n + 255) & ~(size_t)255; return at; };
-        HierCarry &c = h->hcarry;
-        c.src = reinterpret_cast<int64_t *>(take(N * 8));
-        c.obs = reinterpret_cast<float *>(take(N * 8 * 4));
-        c.zone_obs = reinterpret_cast<float *>(take(N * ZF * 4));
-        c.hi_reward = reinterpret_cast<float *>(take(N * 4));
-        c.value = reinterpret_cast<float *>(take(N * 4));
-        c.log_prob = reinterpret_cast<float *>(take(N * 4));
-        c.goal = reinterpret_cast<int32_t *>(take(N * 4));
-        c.avail = reinterpret_cast<uint32_t *>(take(N * 4));
-        c.open = reinterpret_cast<uint8_t *>(take(N));
-        if (b > static_cast<char *>(h->hcarry_mem) + bytes) return fail(ZENV_E_HIP, "carry layout overflow");
-    }
-    if (!h->hi_total_host) HIP_TRY(hipHostMalloc((void **)&h->hi_total_host, 4, hipHostMallocDefault));
-    if (h->hframes_mem && h->hframes.T == T) return ZENV_OK;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->hframes_mem) HIP_TRY(hipFree(h->hframes_mem));
-    h->hframes_mem = nullptr;
-    const size_t TN = (size_t)T * N;
-    const size_t bytes = TN * (4 + 4 + 4 + 4 + 4 + 1 + 8 + 4) + N * 8 + 4 + 11 * 256;
-    HIP_TRY(hipMalloc(&h->hframes_mem, bytes));
-    char *b = static_cast<char *>(h->hframes_mem);
-    auto take = [&](size_t n) { char *at = b; b += (n + 255) & ~(size_t)255; return at; };
-    HierFrames &f = h->hframes;
-    f.T = T;
-    f.lo_goal = reinterpret_cast<float *>(take(TN * 8));
-    f.pick_goal = reinterpret_cast<int32_t *>(take(TN * 4));
-    f.pick_value = reinterpret_cast<float *>(take(TN * 4));
-    f.pick_log_prob = reinterpret_cast<float *>(take(TN * 4));
-    f.pick_avail = reinterpret_cast<uint32_t *>(take(TN * 4));
-    f.close_reward = reinterpret_cast<float *>(take(TN * 4));
-    f.env_reward = reinterpret_cast<float *>(take(TN * 4));
-    f.count = reinterpret_cast<int32_t *>(take(N * 4));
-    f.offset = reinterpret_cast<int32_t *>(take(N * 4));
-    f.total = reinterpret_cast<int32_t *>(take(4));
-    f.close_flag = reinterpret_cast<uint8_t *>(take(TN));
-    if (b > static_cast<char *>(h->hframes_mem) + bytes) return fail(ZENV_E_HIP, "frame record layout overflow");
-    HIP_TRY(hipMemsetAsync(h->hframes_mem, 0, bytes, h->stream));
-    return ZENV_OK;
-}
-
-// room for M rows of the flat high-level output (grown by half again, never shrunk)
-static int ensure_hier_out(zenv_t *h, int64_t M)
-{
-    if (M <= h->hi_cap) return ZENV_OK;
-    const int64_t cap = std::max<int64_t>(M, h->hi_cap + h->hi_cap / 2);
-    const size_t Z = (size_t)h->p.Z, ZF = Z * h->p.F, R = (size_t)cap;
-    if (h->hout_mem) HIP_TRY(hipFree(h->hout_mem));
-    h->hout_mem = nullptr;
-    h->hi_cap = 0;
-    const size_t bytes = R * (8 * 4 + ZF * 4 + 4 + Z + 6 * 4 + 4 + 8) + 12 * 256;
-    HIP_TRY(hipMalloc(&h->hout_mem, bytes));
-    char *b = static_cast<char *>(h->hout_mem);
-    auto take = [&](size_t n) { char *at = b; b += (n + 255) & ~(size_t)255; return at; };
-    HierOut &o = h->hout;
-    o.src = reinterpret_cast<int64_t *>(take(R * 8));
-    o.obs = reinterpret_cast<float *>(take(R * 8 * 4));
-    o.zone_obs = reinterpret_cast<float *>(take(R * ZF * 4));
-    o.action = reinterpret_cast<int32_t *>(take(R * 4));
-    o.value = reinterpret_cast<float *>(take(R * 4));
-    o.log_prob = reinterpret_cast<float *>(take(R * 4));
-    o.advantage = reinterpret_cast<float *>(take(R * 4));
-    o.returnn = reinterpret_cast<float *>(take(R * 4));
-    o.reward = reinterpret_cast<float *>(take(R * 4));
-    o.mask = reinterpret_cast<float *>(take(R * 4));
-    o.avail = reinterpret_cast<uint32_t *>(take(R * 4));
-    o.action_mask = reinterpret_cast<uint8_t *>(take(R * Z));
-    if (b > static_cast<char *>(h->hout_mem) + bytes) return fail(ZENV_E_HIP, "output layout overflow");
-    h->hi_cap = cap;
-    return ZENV_OK;
-}
-
-extern "C" int zenv_collect_hier(zenv_t *h, int T, uint64_t policy_seed, uint64_t env_index0, float discount,
-                                 float gae_lambda, int64_t *n_hi)
-{
-    if (!h) return fail(ZENV_E_ARG, "null handle");
-    if (T < 2) return fail(ZENV_E_ARG, "frames_per_proc must be at least 2 (the low level hands out T - 1 frames)");
-    if ((int64_t)T * h->n_env > INT32_MAX) return fail(ZENV_E_ARG, "frames_per_proc x envs must stay below 2^31");
-    if (int ra = gae_args(discount, gae_lambda)) return ra;
-    if (h->order_enabled)
-        return fail(ZENV_E_STATE, "zenv_collect_hier runs the goal-conditioned agent: this handle is solver-ordered");
-    if (!h->goal_enabled) return fail(ZENV_E_STATE, "zenv_collect_hier needs a goal-conditioned handle: zenv_goal_enable first");
-    if (!h->hier_ready) return fail(ZENV_E_STATE, "zenv_hier_load first");
-    if (!h->hier.hi_critic || !h->hier.lo_critic)
-        return fail(ZENV_E_STATE, "zenv_collect_hier needs both critics (zenv_hier_load with hi_critic_* and lo_critic_*)");
-    if (h->host_io_slab) return fail(ZENV_E_STATE, "zenv_collect_hier records on the device: switch zenv_host_io off first");
-    if (!h->was_reset) return fail(ZENV_E_STATE, "Environment must be reset before stepping");
-    if (int rr = ring_guard(h, T, 1)) return rr;           // every frame auto-resets
-    int rc = use_device(h);
-    if (rc) return rc;
-    const size_t N = (size_t)h->n_env, ZF = (size_t)h->p.Z * h->p.F;
-    h->act_tag.valid = false;
-    rc = ensure_exp(h, T);
-    if (rc) return rc;
-    rc = ensure_hier_collect(h, T);
-    if (rc) return rc;
-    const HierFrames &f = h->hframes;
-    const HierCarry &c = h->hcarry;
-    HIP_TRY(hipMemsetAsync(f.pick_goal, 0xFF, (size_t)T * N * 4, h->stream));     // -1: no pick
-    HIP_TRY(hipMemsetAsync(f.close_flag, 0, (size_t)T * N, h->stream));
-    HIP_TRY(hipMemsetAsync(f.count, 0, N * 4, h->stream));
-    // the observations are recorded where they are produced, as in zenv_collect
-    struct ObsRedirect {
-        zenv_t *h;
-        float *obs, *zone_obs;
-        ~ObsRedirect() { h->p.obs = obs; h->p.zone_obs = zone_obs; }
-    } home{ h, h->p.obs, h->p.zone_obs };
-    HIP_TRY(hipMemcpyAsync(h->exp.obs, home.obs, N * 8 * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->exp.zone_obs, home.zone_obs, N * ZF * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    for (int t = 0; t < T; ++t) {
-        h->p.obs = h->exp.obs + (size_t)t * N * 8;
-        h->p.zone_obs = h->exp.zone_obs + (size_t)t * N * ZF;
-        const uint32_t step_index = (uint32_t)h->step_count;
-        const HierRecord hrec{ t, h->n_env, f.pick_goal, f.pick_value, f.pick_log_prob, f.pick_avail, c.open, f.lo_goal };
-        // :14-46 goals for the envs that need one (zenv_policy(ZENV_POLICY_HIER_SAMPLE)'s launches), the pick recorded
-        const HierPick pick{ 1, step_index, policy_seed, env_index0, h->goal_in };
-        HIP_TRY(launch_hier_high(h->hier, h->p, h->hier_logits, h->hier_value, pick, h->stream, hrec));
-        HIP_TRY(launch_goal_set(h->p, h->goal_in, h->goal_bad, h->stream));
-        // :48-64 the low level's action; frame t recorded (and the shaped reward / mask of frame t-1)
-        const MlpRecord rec{ h->exp.action, h->exp.log_prob, h->exp.value, h->exp.mask, h->exp.reward, h->exp.cur_mask,
-                             h->p.reward, h->p.shaped, h->p.done_out, T, t, h->n_env };
-        const MlpAction act{ 1, step_index, policy_seed, env_index0, h->p.actions, rec };
-        HIP_TRY(launch_hier_low(h->hier, h->p, h->mlp_mu, h->mlp_std, h->mlp_value, act, h->stream, hrec));
-        h->p.obs = t + 1 < T ? h->exp.obs + (size_t)(t + 1) * N * 8 : home.obs;
-        h->p.zone_obs = t + 1 < T ? h->exp.zone_obs + (size_t)(t + 1) * N * ZF : home.zone_obs;
-        HIP_TRY(launch_step(h->p, h->p.actions, 1, no_policy(), h->stream));     // ParallelEnv.step: auto-reset
-        HIP_TRY(launch_goal_step(h->p, h->stream));
-        HIP_TRY(launch_hier_close(h->p, f, c, t, h->stream));                     // :66-76
-        h->step_count += 1;
-    }
-    HIP_TRY(launch_exp_reward(h->exp, h->n_env, T - 1, h->p.reward, h->p.shaped, h->p.done_out, h->stream));
-    // next_hi_val = V_hi(obs_T) (:93-95), into ZENV_F_HIER_VALUE
-    const HierPick value_only{ -2, 0u, 0ull, 0ull, nullptr };
-    HIP_TRY(launch_hier_high(h->hier, h->p, h->hier_logits, h->hier_value, value_only, h->stream));
-    // :109-116 the low level over frames 0 .. T-2, no bootstrap: frame T-1 is only the "next" frame of T-2
-    ExpBuffers lo = h->exp;
-    lo.T = T - 1;
-    lo.cur_mask = h->exp.mask + (size_t)(T - 1) * N;
-    HIP_TRY(launch_exp_gae(lo, h->n_env, h->exp.value + (size_t)(T - 1) * N, discount, gae_lambda, h->stream));
-    HIP_TRY(hipMemsetAsync(h->exp.advantage + (size_t)(T - 1) * N, 0, N * 4, h->stream));
-    HIP_TRY(hipMemsetAsync(h->exp.returnn + (size_t)(T - 1) * N, 0, N * 4, h->stream));
-    // the high level's rows: offsets, then M to the host (the one synchronisation of the call)
-    HIP_TRY(launch_hier_count_scan(f, h->n_env, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->hi_total_host, f.total, 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    const int64_t M = *h->hi_total_host;
-    h->hi_m = 0;
-    rc = ensure_hier_out(h, M);
-    if (rc) return rc;
-    HIP_TRY(launch_hier_gae(f, c, h->hout, h->n_env, h->hier_value, gae_lambda, h->stream));
-    HIP_TRY(launch_hier_gather(h->hout, c, h->exp.obs, h->exp.zone_obs, M, h->n_env, h->p.Z, h->p.F, h->stream));
-    HIP_TRY(launch_hier_carry(c, h->exp.obs, h->exp.zone_obs, h->n_env, (int)ZF, h->stream));
-    h->hi_m = M;
-    if (n_hi) *n_hi = M;
-    return ZENV_OK;
-}
-
-
-// ---- zenv_collect_skill: collect_experiences of the fixed-length-skills agent and DIAYN (main/src/torch_ac/algos/
-// _hier_policy_opt.py:9-233).  The per-frame records for T frames (the ZENV_F_EXP_* buffers aside)
-static int ensure_skill_collect(zenv_t *h, int T)
-{
-    if (h->sk_mem && h->sk.T == T) return ZENV_OK;
-    const size_t N = (size_t)h->n_env, TN = (size_t)T * N;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->sk_mem) HIP_TRY(hipFree(h->sk_mem));
-    h->sk_mem = nullptr;
-    const size_t bytes = TN * 3 * 4 + N * 2 * 4 + 5 * 256;
-    HIP_TRY(hipMalloc(&h->sk_mem, bytes));
-    char *b = static_cast<char *>(h->sk_mem);
-    auto take = [&](size_t n) { char *at = b; b += (n + 255) & ~(size_t)255; return at; };
-    h->sk.lo_skill = reinterpret_cast<int32_t *>(take(TN * 4));
-    h->sk.diversity = reinterpret_cast<float *>(take(TN * 4));
-    h->sk.env_reward = reinterpret_cast<float *>(take(TN * 4));
-    h->sk.boot = reinterpret_cast<int32_t *>(take(N * 4));
-    h->sk.count = reinterpret_cast<int32_t *>(take(N * 4));
-    if (b > static_cast<char *>(h->sk_mem) + bytes) return fail(ZENV_E_HIP, "skill record layout overflow");
-    HIP_TRY(hipMemsetAsync(h->sk_mem, 0, bytes, h->stream));
-    h->sk.T = T;
-    return ZENV_OK;
-}
-
-extern "C" int zenv_collect_skill(zenv_t *h, int T, uint64_t policy_seed, uint64_t env_index0, float discount,
-                                  float gae_lambda, float diversity_coef, const float *skill_prior_logits, int sample_hi)
-{
-    if (!h) return fail(ZENV_E_ARG, "null handle");
-    if (h->order_enabled || h->goal_enabled)
-        return fail(ZENV_E_STATE, "zenv_collect_skill steps a plain task handle, not a goal-conditioned / solver-ordered one");
-    if (!h->skill_ready) return fail(ZENV_E_STATE, "zenv_skill_load first");
-    if (!h->skill.hi_critic || !h->skill.lo_critic)
-        return fail(ZENV_E_STATE, "zenv_collect_skill needs both critics (zenv_skill_load with hi_critic_* and lo_critic_*)");
-    if (h->host_io_slab) return fail(ZENV_E_STATE, "zenv_collect_skill records on the device: switch zenv_host_io off first");
-    if (!h->was_reset) return fail(ZENV_E_STATE, "Environment must be reset before stepping");
-    const int L = h->skill_len, S = h->skill.S;
-    if (T < 1 || T % L != 0)
-        return fail(ZENV_E_ARG, "frames_per_proc %d must be a positive multiple of skill_len %d", T, L);
-    if (int rr = ring_guard(h, T / L, 1)) return rr;       // a window's last frame auto-resets
-    if ((int64_t)T * h->n_env > INT32_MAX) return fail(ZENV_E_ARG, "frames_per_proc x envs must stay below 2^31");
-    if (int ra = gae_args(discount, gae_lambda)) return ra;
-    if (!std::isfinite(diversity_coef)) return fail(ZENV_E_ARG, "diversity_coef must be finite");
-    if (diversity_coef != 0.f && !h->skinv_ready)
-        return fail(ZENV_E_ARG, "diversity_coef %g without an inverse model (zenv_skill_inverse_load)", diversity_coef);
-    SkillDiv div{};
-    div.N = h->n_env;
-    div.net = h->skinv_ready ? 1 : 0;
-    div.coef = diversity_coef;
-    if (h->skinv_ready) {
-        if (!skill_prior_logits) return fail(ZENV_E_ARG, "skill_prior_logits is null (an inverse model is loaded)");
-        double m = -INFINITY;
-        for (int s = 0; s < S; ++s) {
-            if (!std::isfinite(skill_prior_logits[s])) return fail(ZENV_E_ARG, "skill_prior_logits[%d] is not finite", s);
-            m = std::max(m, (double)skill_prior_logits[s]);
-        }
-        double sum = 0.0;                                        // log_softmax(self.skill_logits, dim=0), once per call
-        for (int s = 0; s < S; ++s) sum += std::exp((double)skill_prior_logits[s] - m);
-        for (int s = 0; s < S; ++s) div.prior[s] = (float)((double)skill_prior_logits[s] - m - std::log(sum));
-    }
-    int rc = use_device(h);
-    if (rc) return rc;
-    const size_t N = (size_t)h->n_env, ZF = (size_t)h->p.Z * h->p.F;
-    const int W = T / L;
-    h->act_tag.valid = false;
-    rc = ensure_exp(h, T);
-    if (rc) return rc;
-    rc = ensure_skill_collect(h, T);
-    if (rc) return rc;
-    h->hi_m = 0;
-    rc = ensure_hier_out(h, (int64_t)N * W);
-    if (rc) return rc;
-    h->hi_m = (int64_t)N * W;
-    const HierOut &o = h->hout;
-    div.skill = h->sk.lo_skill;
-    div.diversity = h->sk.diversity;
-    div.exp_reward = h->exp.reward;
-    // the observations are recorded where they are produced, as in zenv_collect
-    struct ObsRedirect {
-        zenv_t *h;
-        float *obs, *zone_obs;
-        ~ObsRedirect() { h->p.obs = obs; h->p.zone_obs = zone_obs; }
-    } home{ h, h->p.obs, h->p.zone_obs };
-    HIP_TRY(hipMemcpyAsync(h->exp.obs, home.obs, N * 8 * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->exp.zone_obs, home.zone_obs, N * ZF * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    for (int t = 0; t < T; ++t) {
-        h->p.obs = h->exp.obs + (size_t)t * N * 8;
-        h->p.zone_obs = h->exp.zone_obs + (size_t)t * N * ZF;
-        const uint32_t step_index = (uint32_t)h->step_count;
-        SkillRecord sr{ t, h->n_env, W, t / L, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-        if (t % L == 0) {
-            // :28-45 every env picks (hi_dist.sample() or randint), the pick recorded in row env * W + t / L
-            HIP_TRY(launch_skill_sync(h->p, h->sst, nullptr, 0, h->stream));
-            SkillPick pick{ sample_hi ? 1 : 2, L, step_index, policy_seed, env_index0, 1, nullptr, sr };
-            pick.rec.hi_obs = o.obs;
-            pick.rec.hi_zone_obs = o.zone_obs;
-            pick.rec.hi_skill = o.action;
-            pick.rec.hi_value = o.value;
-            pick.rec.hi_log_prob = o.log_prob;
-            HIP_TRY(launch_skill_high(h->skill, h->p, h->sst, h->skill_logits, h->skill_value, pick, h->stream));
-        }
-        // :60-64 the low level's action; frame t recorded (and the env reward / mask of frame t-1)
-        const MlpRecord rec{ h->exp.action, h->exp.log_prob, h->exp.value, h->exp.mask, h->sk.env_reward,
-                             h->exp.cur_mask, h->p.reward, nullptr, h->p.done_out, T, t, h->n_env };
-        const MlpAction act{ 1, step_index, policy_seed, env_index0, h->p.actions, rec };
-        sr.lo_skill = h->sk.lo_skill;
-        HIP_TRY(launch_skill_low(h->skill, h->p, h->sst, h->mlp_mu, h->mlp_std, h->mlp_value, act, h->stream, &sr));
-        h->p.obs = t + 1 < T ? h->exp.obs + (size_t)(t + 1) * N * 8 : home.obs;
-        h->p.zone_obs = t + 1 < T ? h->exp.zone_obs + (size_t)(t + 1) * N * ZF : home.zone_obs;
-        // :68-71 step_no_reset inside a window, step on its last frame
-        HIP_TRY(launch_step(h->p, h->p.actions, (t + 1) % L == 0 ? 1 : 0, no_policy(), h->stream));
-        // :74-91 the diversity reward on obs_{t+1} and the low level's reward
-        div.t = t;
-        HIP_TRY(launch_skill_inverse(h->skinv, h->p, div, h->stream));
-        h->step_count += 1;
-    }
-    {   // the env reward of frame T-1 and self.lo_mask = 1 - done
-        ExpBuffers last = h->exp;
-        last.reward = h->sk.env_reward;
-        HIP_TRY(launch_exp_reward(last, h->n_env, T - 1, h->p.reward, nullptr, h->p.done_out, h->stream));
-    }
-    // :131-139 next_hi_value = V_hi(obs_T); s' ~ hi_dist(obs_T) on a stream of its own; next_lo_value = V_lo(obs_T, s')
-    const SkillPick boot{ 3, L, (uint32_t)h->step_count, policy_seed, env_index0, 1, h->sk.boot, SkillRecord{} };
-    HIP_TRY(launch_skill_high(h->skill, h->p, h->sst, h->skill_logits, h->skill_value, boot, h->stream));
-    SkillState sb = h->sst;
-    sb.skill = h->sk.boot;
-    HIP_TRY(launch_skill_low(h->skill, h->p, sb, h->mlp_mu, h->mlp_std, h->mlp_value, no_mlp_action(), h->stream));
-    // :154-161 the low level over all T frames; :142-151 the high level per env over its windows
-    HIP_TRY(launch_exp_gae(h->exp, h->n_env, h->mlp_value, discount, gae_lambda, h->stream));
-    HIP_TRY(launch_skill_hi_gae(o, T, L, h->n_env, h->sk.env_reward, h->exp.mask, h->exp.cur_mask, h->skill_value,
-                                gae_lambda, h->sk.count, h->stream));
-    return ZENV_OK;
-}
-
-extern "C" int zenv_policy(zenv_t *h, int policy, uint64_t policy_seed, uint64_t env_index0, float *dst_device)
-{
-    if (!h) return fail(ZENV_E_ARG, "null handle");
-    if (!h->was_reset) return fail(ZENV_E_STATE, "reset before asking for actions");
-    const bool hier = policy == ZENV_POLICY_HIER_SAMPLE || policy == ZENV_POLICY_HIER_MEAN;
-    const bool skill = policy == ZENV_POLICY_SKILL_SAMPLE || policy == ZENV_POLICY_SKILL_MEAN;
-    const bool option = policy == ZENV_POLICY_OPTION_SAMPLE || policy == ZENV_POLICY_OPTION_MEAN;
-    if (!policy_known(policy) && !hier && !skill && !option) return fail(ZENV_E_ARG, "unknown policy %d", policy);
-    int rc = use_device(h);
-    if (rc) return rc;
-    const StepPolicy pol{ policy, (uint32_t)h->step_count, policy_seed, env_index0,
-                          dst_device ? dst_device : h->p.actions };
-    h->act_tag.valid = false;
-    if (hier) return run_hier_policy(h, policy, pol.step_index, policy_seed, env_index0, pol.out);
-    if (skill) return run_skill_policy(h, policy, pol.step_index, policy_seed, env_index0, pol.out);
-    if (option) return run_option_policy(h, policy, pol.step_index, policy_seed, env_index0, pol.out);
-    return run_policy(h, pol);
 }
 
 // steps per launch of the persistent kernel (diagnostic: ZENV_ROLLOUT_CHUNK_EXP=<n> shortens it, e.g. to time the

@@ -1,0 +1,166 @@
+// zenv_handle.hpp -- the handle behind zenv_t and the helpers every translation unit of the C ABI uses (zenv_api.cpp:
+// the environment; zenv_agents.cpp: the networks, the per-step policies, the collectors).  Internal: not installed.
+#pragma once
+#include <hip/hip_runtime_api.h>
+#include <rccl/rccl.h>   // types and prototypes only: librccl is dlopen()ed by the first zenv_comm_* call
+
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+#include "../../include/zenv.h"
+#include "dev_params.hpp"
+#include "kernels.hpp"
+#include "hier_f32.hpp"
+#include "option_f32.hpp"
+#include "skill_f32.hpp"
+#include "mlp_policy.hpp"
+
+using namespace zenvk;
+
+#define ZENV_INTERNAL __attribute__((visibility("hidden")))
+
+// sets the calling thread's zenv_last_error() text and returns `code` (zenv_api.cpp)
+ZENV_INTERNAL int fail(int code, const char *fmt, ...);
+
+#define HIP_TRY(expr)                                                                         \
+    do {                                                                                      \
+        hipError_t _e = (expr);                                                               \
+        if (_e != hipSuccess)                                                                 \
+            return fail(ZENV_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e),    \
+                        __FILE__, __LINE__);                                                  \
+    } while (0)
+
+struct Alloc {
+    void **slot;
+    size_t bytes;
+    bool is_state;   // part of zenv_get_state/zenv_set_state
+    int64_t slab_off = -1;   // >= 0: lives at this offset of the handle's results slab (one hipMalloc, one download)
+};
+
+struct zenv {
+    zenv_config cfg{};
+    int n_env = 0;
+    int device = 0;
+    hipStream_t stream = nullptr;       // the stream work is enqueued on
+    hipStream_t own_stream = nullptr;   // created with the handle; `stream` unless zenv_set_stream
+    DevParams p{};
+    DevParams *d_self = nullptr;     // device copy of p (DevParams::self): the persistent kernel reads cold fields from it
+    DevParams self_shadow{};         // what d_self holds
+    bool self_valid = false;
+    std::vector<Alloc> allocs;
+    // The per-step results (obs, reward, done, goal_met, exception, zone_obs) share ONE allocation, 256-byte aligned
+    // pieces in that order, so that a host policy fetches them with one copy (zenv_step_results).
+    void *results_slab = nullptr;
+    // zenv_host_io(): results slab + action buffer in page-locked host memory that the kernels write / read directly
+    void *host_io_slab = nullptr;
+    float *host_io_actions = nullptr, *dev_actions = nullptr;
+    int64_t results_off[ZENV_N_RESULTS] = {};
+    int64_t results_bytes = 0;
+    void *bank_mem[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };   // robot, zone, aux, seed, derived first rows
+    uint8_t *d_mask = nullptr;
+    bool bank_ready = false;
+    bool sched_ready = false;
+    bool was_reset = false;
+    int64_t step_count = 0;
+    // What the internal action buffer holds when a fused rollout left a_{step_count} behind: the next rollout with
+    // the same action source continues from it instead of launching the policy kernel again.
+    struct {
+        bool valid = false;
+        int policy = -1;
+        uint64_t seed = 0, index0 = 0;
+        int64_t step = -1;
+    } act_tag;
+    std::vector<hipEvent_t> events;
+    int rollout_slice_tiles = 1024;   // 64-env tiles per persistent launch (zenv_set_rollout_slice): one per wave slot pair
+    // actor network (zenv_mlp_load)
+    void *mlp_mem = nullptr;
+    MlpImages mlp{};
+    void *mlp_pooled = nullptr;
+    float *mlp_mu = nullptr, *mlp_std = nullptr, *mlp_value = nullptr, *mlp_value_sigma = nullptr;
+    int *mlp_range_flag = nullptr;      // pinned host word, see mlp_range_check()
+    void *mlp_f32_mem = nullptr;        // float32 path (ZENV_MLP_F32): transposed float32 weights
+    MlpF32 mlp_f32{};
+    bool mlp_ready = false;
+    // Zone-goals hierarchical agent (zenv_hier_load): float32 weights, the high level's outputs
+    void *hier_mem = nullptr;
+    HierF32 hier{};
+    bool hier_ready = false;
+    float *hier_logits = nullptr, *hier_value = nullptr;
+    // fixed-length-skills agent (zenv_skill_load): float32 weights, the per-env skill state, the high level's outputs
+    void *skill_mem = nullptr;
+    SkillF32 skill{};
+    bool skill_ready = false;
+    int skill_len = 200;                // evaluate_hier.py:21
+    int skill_n = 0;                    // S the outputs are allocated for
+    SkillState sst{};
+    void *sst_mem = nullptr;
+    float *skill_logits = nullptr, *skill_value = nullptr;
+    // variable-length Options agent (zenv_option_load): it takes the place of the skill agent on the handle -- its
+    // weights live in skill_mem / skill, the state in sst -- plus the picking envs' list and the third output's fields
+    bool option_ready = false;
+    int option_compact = 0;
+    void *opt_mem = nullptr;
+    OptionList olist{};
+    OptionTerm oterm{};
+    // DIAYN's discriminator (zenv_skill_inverse_load) and the per-frame records of zenv_collect_skill (T frames):
+    // lo_skill, diversity, env_reward [T][N]; the bootstrap skill and the row count [N]
+    void *skinv_mem = nullptr;
+    SkillInvF32 skinv{};
+    bool skinv_ready = false;
+    struct {
+        int T = 0;
+        int32_t *lo_skill = nullptr, *boot = nullptr, *count = nullptr;
+        float *diversity = nullptr, *env_reward = nullptr;
+    } sk;
+    void *sk_mem = nullptr;
+    // goal-conditioned variant (zenv_goal_enable)
+    bool goal_enabled = false;
+    bool order_enabled = false;   // solver-ordered variant (zenv_order_enable)
+    int32_t *goal_in = nullptr, *goal_bad = nullptr;
+    // experience buffers (zenv_collect)
+    ExpBuffers exp{};
+    void *exp_mem = nullptr;
+    // zenv_collect_hier: the per-frame records of one call (T), the state that lives from call to call, the flat
+    // high-level output (capacity hi_cap rows, hi_m of them written by the last call)
+    HierFrames hframes{};
+    void *hframes_mem = nullptr;
+    HierCarry hcarry{};
+    void *hcarry_mem = nullptr;
+    HierOut hout{};
+    void *hout_mem = nullptr;
+    int64_t hi_cap = 0, hi_m = 0;
+    int32_t *hi_total_host = nullptr;   // page-locked word M is read back into
+    // staging of zenv_bank_update (page-locked host image + its device copy)
+    void *refill_host = nullptr, *refill_dev = nullptr;
+    size_t refill_cap = 0;
+    hipEvent_t refill_done = nullptr;
+    bool refill_busy = false;
+    // the sharded job's communicator (zenv_comm_init): RCCL over xGMI
+    ncclComm_t comm = nullptr;
+    int comm_rank = 0, comm_world = 0;
+    void *comm_send = nullptr, *comm_recv = nullptr;   // [N] and [world * N] 4-byte elements
+    double *comm_scalar = nullptr;                      // device scratch of the barrier / max-reduce
+    // zenv_step_many: the chunk's actions on the device (when they came from the host) and its time-major records
+    void *chunk_mem = nullptr;
+    size_t chunk_cap = 0;           // steps * envs the allocation holds
+    float *chunk_actions = nullptr, *chunk_reward = nullptr;
+    uint8_t *chunk_done = nullptr;
+    int chunk_steps = 0;            // steps of the last zenv_step_many (extent of ZENV_F_CHUNK_REWARD / _DONE)
+    int chunk_host_steps = 0;       // steps of the last host-action chunk while chunk_actions holds it, else 0
+    // ZENV_F_EP_RETURN / ZENV_F_EP_LEN as plain arrays: the values live in the HotA records, unpacked by refresh_field()
+    double *pub_ep_return = nullptr;
+    int32_t *pub_steps = nullptr;
+};
+
+ZENV_INTERNAL int use_device(const zenv *h);
+
+// ---- zenv_agents.cpp, as far as the stepping paths of zenv_api.cpp call it
+inline bool policy_known(int policy) { return policy >= ZENV_POLICY_UNIFORM && policy <= ZENV_POLICY_MLP_SAMPLE; }
+inline bool policy_is_mlp(int policy) { return policy == ZENV_POLICY_MLP_MEAN || policy == ZENV_POLICY_MLP_SAMPLE; }
+// a_t = pi(obs_t, t) into pol.out, for every kind of action source
+ZENV_INTERNAL int run_policy(zenv *h, const StepPolicy &pol, const MlpRecord *rec = nullptr);
+// the refusal of a call whose auto-resets could outrun a ring schedule
+ZENV_INTERNAL int ring_guard(const zenv *h, int steps, int auto_reset_every_step);
+// ZENV_E_RANGE once the float16 network kernels have flagged an operand out of range
+ZENV_INTERNAL int mlp_range_check(zenv *h);

@@ -22,11 +22,16 @@ python -m pytest tests/test_oracle_cpu.py tests/test_dynamics_independent.py tes
 nm -D oracle/build/libzenv_oracle.so | grep -q __asan && echo "oracle was built with the sanitizers: clean"
 # ---- pass 2: host side of the product library
 git -C "$root" show HEAD:oracle/oracle.py > oracle/oracle.py && rm -rf oracle/build
-csrc=combinatorial-rl-tasks_amd/csrc
-hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -shared -ffp-contract=off -fno-fast-math -Wno-pass-failed \
+# the library's own source list (build.SOURCES), so that a new translation unit is covered the day it is added
+sources=$(python -c "
+import os, sys
+sys.path.insert(0, 'combinatorial-rl-tasks_amd')
+import build
+print(' '.join(os.path.join(build.CSRC, s) for s in build.SOURCES))")
+# (the device side keeps the shipped -O3: hipcc's -O1 -g device pass crashes on hier_collect.hip, and nothing is sanitized there)
+hipcc --offload-arch=gfx950 -O1 -g -Xarch_device -O3 -std=c++17 -fPIC -shared -ffp-contract=off -fno-fast-math -Wno-pass-failed \
     -mllvm -amdgpu-mfma-vgpr-form -fsanitize=address,undefined -fno-gpu-sanitize -shared-libsan \
-    -o combinatorial-rl-tasks_amd/lib/libzenv_hip.so $csrc/kernels.hip $csrc/mlp_policy.hip $csrc/mlp_policy_f16.hip $csrc/mlp_f32.hip \
-    $csrc/zenv_api.cpp $csrc/host_sampler.cpp 2> /dev/null
+    -o combinatorial-rl-tasks_amd/lib/libzenv_hip.so $sources 2> /dev/null
 rt=$(ls /opt/rocm/lib/llvm/lib/clang/*/lib/linux/libclang_rt.asan-x86_64.so | head -1)
 LD_PRELOAD="$rt" ASAN_OPTIONS=detect_leaks=0:verify_asan_link_order=0 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
 python -m pytest tests/test_host_abi.py tests/test_hard_env_and_exception.py tests/test_oracle_cpu.py -x -q -m "not gpu" \
