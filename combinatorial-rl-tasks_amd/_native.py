@@ -42,7 +42,8 @@ E_ARG, E_HIP, E_STATE, E_LAYOUT, E_DONE, E_RANGE = -1, -2, -3, -4, -5, -6
  F_HI_ADVANTAGE, F_HI_RETURN, F_HI_REWARD, F_HI_MASK, F_HI_COUNT,
  F_SKILL, F_SKILL_AGE, F_SKILL_LOGITS, F_SKILL_VALUE,
  F_LO_SKILL, F_LO_DIVERSITY, F_SKILL_BOOTSTRAP,
- F_OPTION_TERM_MU, F_OPTION_TERM_STD, F_OPTION_TERM_ACTION, F_OPTION_TERM_PROB, F_OPTION_ENDED) = range(63)
+ F_OPTION_TERM_MU, F_OPTION_TERM_STD, F_OPTION_TERM_ACTION, F_OPTION_TERM_PROB, F_OPTION_ENDED,
+ F_LO_TERM_ACTION, F_LO_TERM_LOG_PROB, F_LO_OPTION_ENDED) = range(66)
 (RESULT_OBS, RESULT_REWARD, RESULT_DONE, RESULT_GOAL_MET, RESULT_EXCEPTION, RESULT_ZONE_OBS) = range(6)
 N_RESULTS = 6
 
@@ -189,6 +190,8 @@ _PROTOTYPES = {
     "zenv_option_forward": (C.c_int, [_H]),
     "zenv_collect_skill": (C.c_int, [_H, C.c_int, C.c_uint64, C.c_uint64, C.c_float, C.c_float, C.c_float, C.c_void_p,
                                      C.c_int]),
+    "zenv_collect_option": (C.c_int, [_H, C.c_int, C.c_uint64, C.c_uint64, C.c_float, C.c_float,
+                                      C.POINTER(C.c_int64)]),
     "zenv_get": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int]),
     "zenv_get_rows": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "zenv_device_ptr": (C.c_int, [_H, C.c_int, C.POINTER(C.c_void_p)]),

@@ -216,6 +216,7 @@ __global__ __launch_bounds__(256) void k_hier_gather(HierOut o, HierCarry c, con
     __syncthreads();
     copy_rows(o.obs, src, exp_obs, c.obs, m0, n_rows, 8);
     copy_rows(o.zone_obs, src, exp_zone_obs, c.zone_obs, m0, n_rows, ZF);
+    if (!o.action_mask) return;                                              // zenv_collect_option: skills have no mask
     for (int i = (int)threadIdx.x; i < n_rows * Z; i += (int)blockDim.x) {   // hi_action_masks: available_goals as bool [Z]
         const int r = i / Z, z = i - r * Z;
         o.action_mask[(size_t)(m0 + r) * Z + z] = (uint8_t)((av[r] >> z) & 1u);

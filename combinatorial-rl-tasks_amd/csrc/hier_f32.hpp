@@ -122,7 +122,7 @@ hipError_t launch_hier_count_scan(const HierFrames &f, int N, hipStream_t s);
 // per env, backward over the frames: the high-level GAE, the small fields of its rows, the new carry (value, goal ...)
 hipError_t launch_hier_gae(const HierFrames &f, const HierCarry &c, const HierOut &o, int N, const float *v_final,
                            float gae_lambda, hipStream_t s);
-// the rows' obs / zone_obs / action_mask (M rows), then the carry slot's obs of every env whose open transition began
+// the rows' obs / zone_obs / action_mask (M rows; a null o.action_mask is left out), then the carry slot's obs of every env whose open transition began
 // in this call
 hipError_t launch_hier_gather(const HierOut &o, const HierCarry &c, const float *exp_obs, const float *exp_zone_obs,
                               int64_t M, int N, int Z, int F, hipStream_t s);

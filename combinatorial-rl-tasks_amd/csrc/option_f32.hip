@@ -10,6 +10,7 @@
 //    k_option_list first compacts the picking envs into a list (wave ballot, one atomic per wave) and workgroup b takes
 //    entries 4 b .. 4 b + 3 of it.  An env's result does not depend on its workgroup neighbours, so the order of the
 //    list changes no value.
+// Inside zenv_collect_option both kernels also record frame t (OptionRecord; option_collect.hip has the rest).
 #include <hip/hip_runtime.h>
 
 #include "option_f32.hpp"
@@ -40,7 +41,8 @@ __global__ __launch_bounds__(256) void k_option_list(DevParams p, SkillState st,
 
 // out0 = log-softmax logits [N][S], out1 = value [N] (+ the skill pick)
 __global__ __launch_bounds__(HP) void k_option_high(SkillF32 w, DevParams p, SkillState st, OptionList ol,
-                                                    float *__restrict__ out0, float *__restrict__ out1, OptionPick pick)
+                                                    float *__restrict__ out0, float *__restrict__ out1, OptionPick pick,
+                                                    OptionRecord rec)
 {
     __shared__ __align__(16) float x0[ZF * RP];         // zone rows of the pass       [k][row]
     __shared__ __align__(16) float y1[HP * RP];         // activations of the pass     [k][row]
@@ -89,13 +91,20 @@ __global__ __launch_bounds__(HP) void k_option_high(SkillF32 w, DevParams p, Ski
                                  philox_uniform(pick.seed, pick.env_index0 + (uint64_t)env, pick.step_index, 0x534B4Cu));
         st.skill[env] = g;
         st.age[env] = 0;
+        if (!rec.pick_skill) return;
+        const size_t slot = (size_t)rec.t * rec.N + env;   // the pick opens a high-level transition (:36-40)
+        rec.pick_skill[slot] = g;
+        rec.pick_value[slot] = L[kMaxSkills];
+        rec.pick_log_prob[slot] = (L[g] - cat.m) - cat.lse;
+        rec.open[env] = 1;
     }
 }
 
 // out0 = mu [N][2], out1 = std [N][2], out2 = value [N], term (+ the action, the ended flag, the age)
 __global__ __launch_bounds__(HP) void k_option_low(SkillF32 w, DevParams p, SkillState st, OptionList ol,
                                                    float *__restrict__ out0, float *__restrict__ out1,
-                                                   float *__restrict__ out2, OptionTerm term, MlpAction act)
+                                                   float *__restrict__ out2, OptionTerm term, MlpAction act,
+                                                   OptionRecord rec)
 {
     __shared__ __align__(16) float x0[ZF * RP];
     __shared__ __align__(16) float y1[HP * RP];
@@ -138,10 +147,16 @@ __global__ __launch_bounds__(HP) void k_option_low(SkillF32 w, DevParams p, Skil
     }
     if (j >= n_env) return;
     const int env = env0 + j;
+    const size_t slot = (size_t)rec.t * rec.N + env;
     if (sel[j] < 0) {
         idle_outputs(env, out0, out1, out2, act);
         term.mu[env] = term.stdv[env] = term.action[env] = term.prob[env] = 0.f;
         if (acts) st.ended[env] = 0;
+        if (acts && rec.lo_skill) {
+            rec.lo_skill[slot] = -1;
+            rec.term_action[slot] = rec.term_log_prob[slot] = 0.f;
+            rec.ended[slot] = 0;
+        }
         return;
     }
     const float *o = lg + 8 * j;
@@ -163,8 +178,15 @@ __global__ __launch_bounds__(HP) void k_option_low(SkillF32 w, DevParams p, Skil
     term.action[env] = a2;
     term.prob[env] = prob;
     if (!acts) return;
-    st.ended[env] = act.mode == 1 ? philox_uniform(act.seed, g, act.step_index, kOptionTermTag) < prob : prob > 0.5f;
+    const bool ended = act.mode == 1 ? philox_uniform(act.seed, g, act.step_index, kOptionTermTag) < prob : prob > 0.5f;
+    st.ended[env] = ended;
     st.age[env] += 1;
+    if (!rec.lo_skill) return;
+    rec.lo_skill[slot] = sel[j];
+    rec.term_action[slot] = a2;
+    const float z2 = (a2 - m2) / sd2;                    // Normal(mu_2, std_2).log_prob(a_2), as head_outputs forms the other two
+    rec.term_log_prob[slot] = -0.5f * z2 * z2 - logf(sd2) - 0.91893853320467274178f;
+    rec.ended[slot] = ended;
 }
 
 }  // namespace
@@ -176,17 +198,18 @@ hipError_t launch_option_list(const DevParams &p, const SkillState &st, const Op
 }
 
 hipError_t launch_option_high(const SkillF32 &w, const DevParams &p, const SkillState &st, const OptionList &ol,
-                              float *logits, float *value, const OptionPick &pick, hipStream_t s)
+                              float *logits, float *value, const OptionPick &pick, hipStream_t s, const OptionRecord &rec)
 {
-    hipLaunchKernelGGL(k_option_high, dim3((p.N + EB - 1) / EB), dim3(HP), 0, s, w, p, st, ol, logits, value, pick);
+    hipLaunchKernelGGL(k_option_high, dim3((p.N + EB - 1) / EB), dim3(HP), 0, s, w, p, st, ol, logits, value, pick, rec);
     return hipGetLastError();
 }
 
 hipError_t launch_option_low(const SkillF32 &w, const DevParams &p, const SkillState &st, const OptionList &ol,
                              float *mu, float *stdv, float *value, const OptionTerm &term, const MlpAction &act,
-                             hipStream_t s)
+                             hipStream_t s, const OptionRecord &rec)
 {
-    hipLaunchKernelGGL(k_option_low, dim3((p.N + EB - 1) / EB), dim3(HP), 0, s, w, p, st, ol, mu, stdv, value, term, act);
+    hipLaunchKernelGGL(k_option_low, dim3((p.N + EB - 1) / EB), dim3(HP), 0, s, w, p, st, ol, mu, stdv, value, term, act,
+                       rec);
     return hipGetLastError();
 }
 

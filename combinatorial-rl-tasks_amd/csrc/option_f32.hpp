@@ -36,9 +36,25 @@ struct OptionPick {
     uint32_t step_index;
     uint64_t seed, env_index0;
 };
+// What zenv_collect_option records at frame t besides the kernels' outputs, time-major [T][N] (null pick_skill:
+// nothing is recorded, and every other output is what it is without a record):
+//   high level, for every env that picks: the skill, the critic's value and log_softmax(logits)[skill] into the
+//   HierFrames pick fields (the skill in the goal field), open[env] = 1 (HierCarry: a high-level transition is open)
+//   low level, every env: the skill it acted under (-1: it idled), a_2, Normal(mu_2, std_2).log_prob(a_2) and the
+//   termination draw; the rest of frame t goes through MlpAction::rec (head_outputs / idle_outputs)
+struct OptionRecord {
+    int t, N;
+    int32_t *pick_skill;
+    float *pick_value, *pick_log_prob;
+    uint8_t *open;
+    int32_t *lo_skill;
+    float *term_action, *term_log_prob;
+    uint8_t *ended;
+};
 hipError_t launch_option_list(const DevParams &p, const SkillState &st, const OptionList &ol, hipStream_t s);
 hipError_t launch_option_high(const SkillF32 &w, const DevParams &p, const SkillState &st, const OptionList &ol,
-                              float *logits, float *value, const OptionPick &pick, hipStream_t s);
+                              float *logits, float *value, const OptionPick &pick, hipStream_t s,
+                              const OptionRecord &rec = OptionRecord{});
 // The third component's outputs, [N] each: mu_2, std_2, a_2 (the sample, or mu_2), prob = sigmoid(4 a_2 - 3)
 struct OptionTerm {
     float *mu, *stdv, *action, *prob;
@@ -48,6 +64,19 @@ struct OptionTerm {
 // kOptionTermTag stream, mode 0: prob > 0.5) and age + 1.  Every other env gets zeros everywhere (ended = 0).
 hipError_t launch_option_low(const SkillF32 &w, const DevParams &p, const SkillState &st, const OptionList &ol,
                              float *mu, float *stdv, float *value, const OptionTerm &term, const MlpAction &act,
-                             hipStream_t s);
+                             hipStream_t s, const OptionRecord &rec = OptionRecord{});
+
+// ---- zenv_collect_option (option_collect.hip): the high level's transitions are semi-Markov like the Zone-goals
+// agent's, so the bookkeeping is hier_collect.hip's (HierFrames / HierCarry / HierOut, the skill in the goal field);
+// what differs is when a transition closes and that the skill outlives an auto-reset.
+// Once per call, after launch_skill_sync: an env that enters without a skill has no open transition (hi_reward 0).
+hipError_t launch_option_enter(const SkillState &st, const HierCarry &c, int N, hipStream_t s);
+// After the step of frame t (_hier_policy_opt.py:62-75): env reward, hi_reward, and for every env whose option ended
+// the close of its open transition (reward hi_reward, hi_mask 0 if done else 1; hi_reward restarts at 0 either way).
+// Every env that holds a skill takes the env's current episode index into SkillState::epi, unless its option ended on
+// the step that ended its episode: the skill, its open transition and hi_reward run across the auto-reset
+// (cur_skills[j] is cleared by the termination draw alone, :74).
+hipError_t launch_option_close(const DevParams &p, const SkillState &st, const HierFrames &f, const HierCarry &c, int t,
+                               hipStream_t s);
 
 }  // namespace zenvk

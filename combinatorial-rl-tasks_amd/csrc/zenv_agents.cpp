@@ -1,6 +1,6 @@
 // zenv_agents.cpp -- the networks behind the C ABI of include/zenv.h: the loaders, forwards and per-step policies of the
-// flat actor and of the Zone-goals, fixed-length-skills / DIAYN and Options agents, and the three collectors
-// (zenv_collect, zenv_collect_hier, zenv_collect_skill).  The handle and the environment's own calls: zenv_api.cpp.
+// flat actor and of the Zone-goals, fixed-length-skills / DIAYN and Options agents, and the four collectors
+// (zenv_collect, zenv_collect_hier, zenv_collect_skill, zenv_collect_option).  The handle and the environment's own calls: zenv_api.cpp.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -338,6 +338,8 @@ static int load_skill_family(zenv_t *h, const zenv_skill_weights *w, int n_out)
     HIP_TRY(hipMemsetAsync(h->skill_logits, 0, N * S * sizeof(float), h->stream));
     HIP_TRY(hipMemsetAsync(h->skill_value, 0, N * sizeof(float), h->stream));
     HIP_TRY(launch_skill_sync(h->p, h->sst, nullptr, 1, h->stream));     // every env: no skill (the new S may be smaller)
+    // ... and with the skills go the high-level transitions zenv_collect_option left open
+    if (h->hcarry_mem) HIP_TRY(launch_hier_reset(h->hcarry, nullptr, h->n_env, h->stream));
     h->skill = skill_f32_at(*w, static_cast<const float *>(h->skill_mem), o);
     HIP_TRY(hipStreamSynchronize(h->stream));
     (n_out == 3 ? h->option_ready : h->skill_ready) = true;
@@ -499,7 +501,7 @@ int ring_guard(const zenv *h, int steps, int auto_reset_every_step)
 }
 
 // ============================================================================ experience collection
-// the three collectors' discount and gae_lambda: finite and in [0, 1] (a NaN would turn every advantage into NaN)
+// the collectors' discount and gae_lambda: finite and in [0, 1] (a NaN would turn every advantage into NaN)
 static int gae_args(float discount, float gae_lambda)
 {
     if (!std::isfinite(discount) || !std::isfinite(gae_lambda))
@@ -509,7 +511,7 @@ static int gae_args(float discount, float gae_lambda)
     return ZENV_OK;
 }
 
-// What the three collectors ask before anything else: a handle that was reset and keeps its results on the device,
+// What the collectors ask before anything else: a handle that was reset and keeps its results on the device,
 // T x N frames that fit the kernels' 32-bit slots, sane GAE factors, and no more auto-resets (`resets` per env) than a
 // ring schedule is deep
 static int collect_ready(const zenv *h, const char *who, int T, int resets, float discount, float gae_lambda)
@@ -551,7 +553,7 @@ public:
 
 }  // namespace
 
-// the ZENV_F_EXP_* buffers for T frames (zenv_collect, zenv_collect_hier); self.mask survives a change of T
+// the ZENV_F_EXP_* buffers for T frames (every collector's); self.mask survives a change of T
 static int ensure_exp(zenv_t *h, int T)
 {
     const size_t N = (size_t)h->n_env, ZF = (size_t)h->p.Z * h->p.F;
@@ -622,8 +624,9 @@ extern "C" int zenv_collect(zenv_t *h, int T, uint64_t policy_seed, uint64_t env
 }
 
 // ---- zenv_collect_hier: collect_experiences of the Zone-goals agent (zone-goals/src/torch_ac/algos/_hier_policy_opt.py)
-// the per-frame records for T frames; the state carried from call to call is allocated (and zeroed) once
-static int ensure_hier_collect(zenv_t *h, int T)
+// the per-frame records for T frames; the state carried from call to call is allocated (and zeroed) once.
+// zenv_collect_option shares them and has no goal input to record (with_goal = false)
+static int ensure_hier_collect(zenv_t *h, int T, bool with_goal = true)
 {
     const size_t N = (size_t)h->n_env, ZF = (size_t)h->p.Z * h->p.F;
     if (!h->hcarry_mem) {
@@ -649,7 +652,7 @@ static int ensure_hier_collect(zenv_t *h, int T)
     const size_t TN = (size_t)T * N;
     HierFrames &f = h->hframes;
     Carver cv;
-    cv.piece(f.lo_goal, TN * 2);
+    cv.piece(f.lo_goal, with_goal ? TN * 2 : 0);
     cv.piece(f.pick_goal, TN);
     cv.piece(f.pick_value, TN);
     cv.piece(f.pick_log_prob, TN);
@@ -661,6 +664,7 @@ static int ensure_hier_collect(zenv_t *h, int T)
     cv.piece(f.total, 1);
     cv.piece(f.close_flag, TN);
     if (int rc = cv.alloc(&h->hframes_mem, "frame record")) return rc;
+    if (!with_goal) f.lo_goal = nullptr;                          // ZENV_F_LO_GOAL: 0 bytes
     f.T = T;
     HIP_TRY(hipMemsetAsync(h->hframes_mem, 0, cv.bytes(), h->stream));
     return ZENV_OK;
@@ -709,6 +713,7 @@ extern "C" int zenv_collect_hier(zenv_t *h, int T, uint64_t policy_seed, uint64_
     if (int rc = use_device(h)) return rc;
     const size_t N = (size_t)h->n_env, ZF = (size_t)h->p.Z * h->p.F;
     h->act_tag.valid = false;
+    h->hi_kind = 0;
     if (int rc = ensure_exp(h, T)) return rc;
     if (int rc = ensure_hier_collect(h, T)) return rc;
     const HierFrames &f = h->hframes;
@@ -824,6 +829,7 @@ extern "C" int zenv_collect_skill(zenv_t *h, int T, uint64_t policy_seed, uint64
     if (int rc = ensure_exp(h, T)) return rc;
     if (int rc = ensure_skill_collect(h, T)) return rc;
     h->hi_m = 0;
+    h->hi_kind = 1;
     if (int rc = ensure_hier_out(h, (int64_t)N * W)) return rc;
     h->hi_m = (int64_t)N * W;
     const HierOut &o = h->hout;
@@ -876,6 +882,103 @@ extern "C" int zenv_collect_skill(zenv_t *h, int T, uint64_t policy_seed, uint64
     HIP_TRY(launch_exp_gae(h->exp, h->n_env, h->mlp_value, discount, gae_lambda, h->stream));
     HIP_TRY(launch_skill_hi_gae(o, T, L, h->n_env, h->sk.env_reward, h->exp.mask, h->exp.cur_mask, h->skill_value,
                                 gae_lambda, h->sk.count, h->stream));
+    return ZENV_OK;
+}
+
+// ---- zenv_collect_option: collect_experiences of the Options agent (options/src/torch_ac/algos/_hier_policy_opt.py:
+// 10-205).  The per-frame records for T frames that zenv_collect_hier's (ensure_hier_collect) have no place for
+static int ensure_option_collect(zenv_t *h, int T)
+{
+    if (h->oc_mem && h->oc.T == T) return ZENV_OK;
+    const size_t TN = (size_t)T * h->n_env;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->oc_mem) HIP_TRY(hipFree(h->oc_mem));
+    h->oc_mem = nullptr;
+    Carver cv;
+    cv.piece(h->oc.lo_skill, TN);
+    cv.piece(h->oc.term_action, TN);
+    cv.piece(h->oc.term_log_prob, TN);
+    cv.piece(h->oc.ended, TN);
+    if (int rc = cv.alloc(&h->oc_mem, "option record")) return rc;
+    HIP_TRY(hipMemsetAsync(h->oc_mem, 0, cv.bytes(), h->stream));
+    h->oc.T = T;
+    return ZENV_OK;
+}
+
+extern "C" int zenv_collect_option(zenv_t *h, int T, uint64_t policy_seed, uint64_t env_index0, float discount,
+                                   float gae_lambda, int64_t *n_hi)
+{
+    if (T < 2) return fail(ZENV_E_ARG, "frames_per_proc must be at least 2 (the low level hands out T - 1 frames)");
+    int rc = collect_ready(h, "zenv_collect_option", T, T, discount, gae_lambda);   // every frame auto-resets
+    if (rc) return rc;
+    if (h->order_enabled || h->goal_enabled)
+        return fail(ZENV_E_STATE, "zenv_collect_option steps a plain task handle, not a goal-conditioned / solver-ordered one");
+    if (!h->option_ready) return fail(ZENV_E_STATE, "zenv_option_load first");
+    if (!h->skill.hi_critic || !h->skill.lo_critic)
+        return fail(ZENV_E_STATE, "zenv_collect_option needs both critics (zenv_option_load with hi_critic_* and lo_critic_*)");
+    if (int rc = use_device(h)) return rc;
+    const size_t N = (size_t)h->n_env, ZF = (size_t)h->p.Z * h->p.F;
+    h->act_tag.valid = false;
+    h->hi_m = 0;
+    h->hi_kind = 2;
+    if (int rc = ensure_exp(h, T)) return rc;
+    if (int rc = ensure_hier_collect(h, T, false)) return rc;
+    if (int rc = ensure_option_collect(h, T)) return rc;
+    const HierFrames &f = h->hframes;
+    const HierCarry &c = h->hcarry;
+    HIP_TRY(hipMemsetAsync(f.pick_goal, 0xFF, (size_t)T * N * 4, h->stream));     // -1: no pick
+    HIP_TRY(hipMemsetAsync(f.close_flag, 0, (size_t)T * N, h->stream));
+    HIP_TRY(hipMemsetAsync(f.count, 0, N * 4, h->stream));
+    // the skill state as the policy would find it; an env that enters without a skill has no transition open
+    HIP_TRY(launch_skill_sync(h->p, h->sst, nullptr, 0, h->stream));
+    HIP_TRY(launch_option_enter(h->sst, c, h->n_env, h->stream));
+    const FrameObs frames(h);
+    if (int rc = frames.begin()) return rc;
+    for (int t = 0; t < T; ++t) {
+        frames.read(t);
+        const uint32_t step_index = (uint32_t)h->step_count;
+        const OptionRecord orec{ t, h->n_env, f.pick_goal, f.pick_value, f.pick_log_prob, c.open, h->oc.lo_skill,
+                                 h->oc.term_action, h->oc.term_log_prob, h->oc.ended };
+        // :17-40 a skill for the envs without one (zenv_policy(ZENV_POLICY_OPTION_SAMPLE)'s launches), the pick recorded
+        const OptionPick pick{ 1, h->option_compact, step_index, policy_seed, env_index0 };
+        if (pick.compact) HIP_TRY(launch_option_list(h->p, h->sst, h->olist, h->stream));
+        HIP_TRY(launch_option_high(h->skill, h->p, h->sst, h->olist, h->skill_logits, h->skill_value, pick, h->stream,
+                                   orec));
+        // :42-63 the low level's action and the termination draw; frame t recorded (and reward / mask of frame t-1)
+        const MlpRecord rec{ h->exp.action, h->exp.log_prob, h->exp.value, h->exp.mask, h->exp.reward, h->exp.cur_mask,
+                             h->p.reward, nullptr, h->p.done_out, T, t, h->n_env };
+        const MlpAction act{ 1, step_index, policy_seed, env_index0, h->p.actions, rec };
+        HIP_TRY(launch_option_low(h->skill, h->p, h->sst, h->olist, h->mlp_mu, h->mlp_std, h->mlp_value, h->oterm, act,
+                                  h->stream, orec));
+        frames.write_next(t, T);
+        HIP_TRY(launch_step(h->p, h->p.actions, 1, no_policy(), h->stream));      // self.env.step (:50): auto-reset
+        HIP_TRY(launch_option_close(h->p, h->sst, f, c, t, h->stream));           // :65-75, and the skill's episode index
+        h->step_count += 1;
+    }
+    HIP_TRY(launch_exp_reward(h->exp, h->n_env, T - 1, h->p.reward, nullptr, h->p.done_out, h->stream));
+    // next_hi_val = V_hi(obs_T) (:95-97) of every env, into ZENV_F_SKILL_VALUE; nothing is picked
+    const OptionPick value_only{ -1, 0, 0u, 0ull, 0ull };
+    HIP_TRY(launch_option_high(h->skill, h->p, h->sst, h->olist, h->skill_logits, h->skill_value, value_only, h->stream));
+    // :111-118 the low level over frames 0 .. T-2, no bootstrap: frame T-1 is only the "next" frame of T-2
+    ExpBuffers lo = h->exp;
+    lo.T = T - 1;
+    lo.cur_mask = h->exp.mask + (size_t)(T - 1) * N;
+    HIP_TRY(launch_exp_gae(lo, h->n_env, h->exp.value + (size_t)(T - 1) * N, discount, gae_lambda, h->stream));
+    HIP_TRY(hipMemsetAsync(h->exp.advantage + (size_t)(T - 1) * N, 0, N * 4, h->stream));
+    HIP_TRY(hipMemsetAsync(h->exp.returnn + (size_t)(T - 1) * N, 0, N * 4, h->stream));
+    // :100-108 the high level's rows: offsets, then M to the host (the one synchronisation of the call)
+    HIP_TRY(launch_hier_count_scan(f, h->n_env, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->hi_total_host, f.total, 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const int64_t M = *h->hi_total_host;
+    if (int rc = ensure_hier_out(h, M)) return rc;
+    HierOut rows = h->hout;
+    rows.action_mask = nullptr;                                  // every skill is always available: no mask
+    HIP_TRY(launch_hier_gae(f, c, rows, h->n_env, h->skill_value, gae_lambda, h->stream));
+    HIP_TRY(launch_hier_gather(rows, c, h->exp.obs, h->exp.zone_obs, M, h->n_env, h->p.Z, h->p.F, h->stream));
+    HIP_TRY(launch_hier_carry(c, h->exp.obs, h->exp.zone_obs, h->n_env, (int)ZF, h->stream));
+    h->hi_m = M;
+    if (n_hi) *n_hi = M;
     return ZENV_OK;
 }
 

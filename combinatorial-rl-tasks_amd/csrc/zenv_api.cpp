@@ -199,13 +199,13 @@ FieldInfo field_info(const zenv *h, int field)
     case ZENV_F_HIER_LOGITS: return { h->hier_logits, h->hier_logits ? N * p.Z * 4 : 0 };
     case ZENV_F_HIER_VALUE: return { h->hier_value, h->hier_value ? N * 4 : 0 };
     case ZENV_F_LO_GOAL: return { h->hframes.lo_goal, h->hframes.lo_goal ? N * h->hframes.T * 2 * 4 : 0 };
-    case ZENV_F_LO_ENV_REWARD:       // zenv_collect_hier's or zenv_collect_skill's (a handle runs one of them)
-        if (h->sk_mem) return { h->sk.env_reward, N * h->sk.T * 4 };
+    case ZENV_F_LO_ENV_REWARD:       // zenv_collect_hier's / _option's or zenv_collect_skill's
+        if (h->hi_kind != 2 && h->sk_mem) return { h->sk.env_reward, N * h->sk.T * 4 };
         return { h->hframes.env_reward, h->hframes.env_reward ? N * h->hframes.T * 4 : 0 };
     case ZENV_F_HI_OBS: return { h->hout.obs, h->hi_m * 8 * 4 };
     case ZENV_F_HI_ZONE_OBS: return { h->hout.zone_obs, h->hi_m * p.Z * p.F * 4 };
     case ZENV_F_HI_ACTION: return { h->hout.action, h->hi_m * 4 };
-    case ZENV_F_HI_ACTION_MASK: return { h->hout.action_mask, h->sk_mem ? 0 : h->hi_m * p.Z };   // skills: not written
+    case ZENV_F_HI_ACTION_MASK: return { h->hout.action_mask, h->sk_mem || h->hi_kind == 2 ? 0 : h->hi_m * p.Z };   // skills: not written
     case ZENV_F_HI_VALUE: return { h->hout.value, h->hi_m * 4 };
     case ZENV_F_HI_LOG_PROB: return { h->hout.log_prob, h->hi_m * 4 };
     case ZENV_F_HI_ADVANTAGE: return { h->hout.advantage, h->hi_m * 4 };
@@ -213,13 +213,15 @@ FieldInfo field_info(const zenv *h, int field)
     case ZENV_F_HI_REWARD: return { h->hout.reward, h->hi_m * 4 };
     case ZENV_F_HI_MASK: return { h->hout.mask, h->hi_m * 4 };
     case ZENV_F_HI_COUNT:
-        if (h->sk_mem) return { h->sk.count, N * 4 };
+        if (h->hi_kind != 2 && h->sk_mem) return { h->sk.count, N * 4 };
         return { h->hframes.count, h->hframes.count ? N * 4 : 0 };
     case ZENV_F_SKILL: return { h->sst.skill, h->sst_mem ? N * 4 : 0 };          // (refresh_field() first)
     case ZENV_F_SKILL_AGE: return { h->sst.age, h->sst_mem ? N * 4 : 0 };
     case ZENV_F_SKILL_LOGITS: return { h->skill_logits, h->skill_logits ? N * h->skill_n * 4 : 0 };
     case ZENV_F_SKILL_VALUE: return { h->skill_value, h->skill_value ? N * 4 : 0 };
-    case ZENV_F_LO_SKILL: return { h->sk.lo_skill, h->sk_mem ? N * h->sk.T * 4 : 0 };
+    case ZENV_F_LO_SKILL:
+        if (h->hi_kind == 2) return { h->oc.lo_skill, N * h->oc.T * 4 };
+        return { h->sk.lo_skill, h->sk_mem ? N * h->sk.T * 4 : 0 };
     case ZENV_F_LO_DIVERSITY: return { h->sk.diversity, h->sk_mem ? N * h->sk.T * 4 : 0 };
     case ZENV_F_SKILL_BOOTSTRAP: return { h->sk.boot, h->sk_mem ? N * 4 : 0 };
     case ZENV_F_OPTION_TERM_MU: return { h->oterm.mu, h->opt_mem ? N * 4 : 0 };
@@ -227,6 +229,9 @@ FieldInfo field_info(const zenv *h, int field)
     case ZENV_F_OPTION_TERM_ACTION: return { h->oterm.action, h->opt_mem ? N * 4 : 0 };
     case ZENV_F_OPTION_TERM_PROB: return { h->oterm.prob, h->opt_mem ? N * 4 : 0 };
     case ZENV_F_OPTION_ENDED: return { h->sst.ended, h->opt_mem ? N * 4 : 0 };   // (refresh_field() first)
+    case ZENV_F_LO_TERM_ACTION: return { h->oc.term_action, h->oc_mem ? N * h->oc.T * 4 : 0 };
+    case ZENV_F_LO_TERM_LOG_PROB: return { h->oc.term_log_prob, h->oc_mem ? N * h->oc.T * 4 : 0 };
+    case ZENV_F_LO_OPTION_ENDED: return { h->oc.ended, h->oc_mem ? N * h->oc.T : 0 };
     default: return { nullptr, 0 };
     }
 }
@@ -528,7 +533,7 @@ extern "C" int zenv_destroy(zenv_t *h)
                      (void *)h->goal_in, (void *)h->goal_bad, h->exp_mem, (void *)h->p.order_pos,
                      (void *)h->p.order_val, h->hier_mem, (void *)h->hier_logits, (void *)h->hier_value,
                      h->hframes_mem, h->hcarry_mem, h->hout_mem, h->skill_mem, h->sst_mem, (void *)h->skill_logits,
-                     (void *)h->skill_value, h->skinv_mem, h->sk_mem, h->opt_mem })
+                     (void *)h->skill_value, h->skinv_mem, h->sk_mem, h->opt_mem, h->oc_mem })
         if (m) (void)hipFree(m);
     for (hipEvent_t ev : h->events) (void)hipEventDestroy(ev);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);

@@ -103,6 +103,15 @@ struct zenv {
     void *opt_mem = nullptr;
     OptionList olist{};
     OptionTerm oterm{};
+    // zenv_collect_option: the per-frame records of one call (T frames) that have no place in hframes -- the skill the
+    // low level acted under, a_2 with its log_prob and the termination draw, [T][N] each
+    struct {
+        int T = 0;
+        int32_t *lo_skill = nullptr;
+        float *term_action = nullptr, *term_log_prob = nullptr;
+        uint8_t *ended = nullptr;
+    } oc;
+    void *oc_mem = nullptr;
     // DIAYN's discriminator (zenv_skill_inverse_load) and the per-frame records of zenv_collect_skill (T frames):
     // lo_skill, diversity, env_reward [T][N]; the bootstrap skill and the row count [N]
     void *skinv_mem = nullptr;
@@ -130,6 +139,8 @@ struct zenv {
     HierOut hout{};
     void *hout_mem = nullptr;
     int64_t hi_cap = 0, hi_m = 0;
+    int hi_kind = 0;                    // whose rows and per-frame records the ZENV_F_HI_* / ZENV_F_LO_* fields hold:
+                                        // 0 zenv_collect_hier's, 1 zenv_collect_skill's, 2 zenv_collect_option's
     int32_t *hi_total_host = nullptr;   // page-locked word M is read back into
     // staging of zenv_bank_update (page-locked host image + its device copy)
     void *refill_host = nullptr, *refill_dev = nullptr;

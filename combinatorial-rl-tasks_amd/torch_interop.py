@@ -158,6 +158,38 @@ class TorchZoneEnv:
                    "skill": lo["skill"][:, :-1][keep]}
         return lo, hi, inverse, skill_num_frames(lo["mask"].transpose(0, 1), L)
 
+    def load_options(self, hi_state_dict, lo_state_dict):
+        """Put the Options agent's HighPolicyValueModel / LoPolicyValueModel state_dicts (options/src/
+        hier_policy_value_models.py; torch tensors on any device) into the device agent that ``collect_options`` runs --
+        after every update.  Loading drops the transitions the last collection left open."""
+        from .vec_env import option_tensors_from_state_dicts
+        self.env.load_options(option_tensors_from_state_dicts(hi_state_dict, lo_state_dict))
+
+    def collect_options(self, frames_per_proc, policy_seed=1, env_index0=0, discount=0.99, gae_lambda=0.95):
+        """collect_experiences of the Options agent on the device; returns (lo, hi, termination_rate) as CUDA tensors
+        ALIASING the handle's buffers, named as ``option_experience_layout``: lo [N, T-1, ...] views of time-major
+        memory -- action / log_prob hold the first two components, the third is a tensor of its own (term_action /
+        term_log_prob [N, T-1]; ``torch.cat`` gives the reference's three) and ended is a bool view of uint8 memory --
+        hi flat [M, ...] and count [N].  termination_rate is a 0-d tensor (the mean over all T * N frames), not yet
+        synchronised.  Valid until the next collect_options.  Ends with one synchronisation (the host learns M)."""
+        from .vec_env import option_experience_layout
+        env = self.env
+        T, M = env.collect_options_on_device(frames_per_proc, policy_seed, env_index0, discount, gae_lambda)
+        lo_l, hi_l = option_experience_layout(env.num_envs, env.num_zones, env.zone_feat, T, M)
+        torch = self._torch
+        raw = {name: self._alias_typed(field, shape, dt) for name, (field, shape, dt) in lo_l.items()}
+        rate = raw["ended"].float().mean()
+        raw["ended"] = raw["ended"].view(torch.bool)
+        lo = {name: t[:T - 1].transpose(0, 1) for name, t in raw.items()}
+        hi = {}
+        for name, (field, shape, dt) in hi_l.items():
+            if M:
+                hi[name] = self._alias_typed(field, shape, dt)
+            else:
+                hi[name] = torch.empty(shape, dtype=getattr(torch, np.dtype(dt).name), device=self.device)
+        hi["count"] = self._alias_typed(nat.F_HI_COUNT, (env.num_envs,), np.int32)
+        return lo, hi, rate
+
     def _alias_typed(self, field, shape, dtype):
         t = self._torch.as_tensor(_DeviceView(self.env.device_ptr(field), shape, dtype), device=self.device)
         assert t.data_ptr() == self.env.device_ptr(field), "torch copied instead of aliasing"

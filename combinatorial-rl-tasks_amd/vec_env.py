@@ -31,6 +31,7 @@ _FIELD_DTYPES = {
     nat.F_SKILL_VALUE: np.float32, nat.F_LO_SKILL: np.int32, nat.F_LO_DIVERSITY: np.float32,
     nat.F_SKILL_BOOTSTRAP: np.int32, nat.F_OPTION_TERM_MU: np.float32, nat.F_OPTION_TERM_STD: np.float32,
     nat.F_OPTION_TERM_ACTION: np.float32, nat.F_OPTION_TERM_PROB: np.float32, nat.F_OPTION_ENDED: np.int32,
+    nat.F_LO_TERM_ACTION: np.float32, nat.F_LO_TERM_LOG_PROB: np.float32, nat.F_LO_OPTION_ENDED: np.uint8,
 }
 
 
@@ -265,6 +266,38 @@ INVERSE_KEYS = {"zone_w1": "zone_net.0.weight", "zone_b1": "zone_net.0.bias", "z
                 "zone_b2": "zone_net.2.bias", "zone_w3": "zone_net.4.weight", "zone_b3": "zone_net.4.bias",
                 "comb_w1": "combine_net.0.weight", "comb_b1": "combine_net.0.bias",
                 "comb_w2": "combine_net.2.weight", "comb_b2": "combine_net.2.bias"}
+
+
+def check_collect_option_args(frames_per_proc, policy_seed=1, env_index0=0, discount=0.99, gae_lambda=0.95):
+    """What ``ZoneVecEnv.collect_options`` checks before it calls into the library: the rules of ``collect_hier`` -- T >= 2
+    frames (the low level hands out T - 1), a discount and a lambda in [0, 1], non-negative 64-bit seeds.  Returns the
+    normalised arguments."""
+    return check_collect_hier_args(frames_per_proc, policy_seed, env_index0, discount, gae_lambda)
+
+
+def option_experience_layout(num_envs, num_zones, zone_feat, frames_per_proc, n_hi):
+    """The buffers one ``collect_options`` of T frames fills, as (lo, hi): name -> (field id, shape in memory, dtype).
+    lo: time-major [T, N, ...] device buffers, handed out as [N, T-1, ...] views (lo_exps of options/src/torch_ac/algos/
+    _hier_policy_opt.py:133-147: obs, zone_obs, skill, action, log_prob, value, advantage, returnn; plus reward =
+    env_reward, mask and ended, the termination draw).  The reference's _action and lo_log_probs have three components:
+    the first two are action / log_prob [T, N, 2], the third is term_action / term_log_prob [T, N], buffers of their
+    own.  hi: flat env-major [M, ...] (hi_exps, :152-169, action = the skill; plus each transition's reward and
+    hi_mask), M = n_hi."""
+    N, Z, F, T, M = int(num_envs), int(num_zones), int(zone_feat), int(frames_per_proc), int(n_hi)
+    f32 = np.float32
+    lo = {"obs": (nat.F_EXP_OBS, (T, N, 8), f32), "zone_obs": (nat.F_EXP_ZONE_OBS, (T, N, Z, F), f32),
+          "skill": (nat.F_LO_SKILL, (T, N), np.int32), "action": (nat.F_EXP_ACTION, (T, N, 2), f32),
+          "term_action": (nat.F_LO_TERM_ACTION, (T, N), f32), "log_prob": (nat.F_EXP_LOG_PROB, (T, N, 2), f32),
+          "term_log_prob": (nat.F_LO_TERM_LOG_PROB, (T, N), f32), "ended": (nat.F_LO_OPTION_ENDED, (T, N), np.uint8),
+          "value": (nat.F_EXP_VALUE, (T, N), f32), "advantage": (nat.F_EXP_ADVANTAGE, (T, N), f32),
+          "returnn": (nat.F_EXP_RETURN, (T, N), f32), "reward": (nat.F_EXP_REWARD, (T, N), f32),
+          "env_reward": (nat.F_LO_ENV_REWARD, (T, N), f32), "mask": (nat.F_EXP_MASK, (T, N), f32)}
+    hi = {"obs": (nat.F_HI_OBS, (M, 8), f32), "zone_obs": (nat.F_HI_ZONE_OBS, (M, Z, F), f32),
+          "action": (nat.F_HI_ACTION, (M,), np.int32), "value": (nat.F_HI_VALUE, (M,), f32),
+          "log_prob": (nat.F_HI_LOG_PROB, (M,), f32), "advantage": (nat.F_HI_ADVANTAGE, (M,), f32),
+          "returnn": (nat.F_HI_RETURN, (M,), f32), "reward": (nat.F_HI_REWARD, (M,), f32),
+          "mask": (nat.F_HI_MASK, (M,), f32)}
+    return lo, hi
 
 
 def inverse_tensor_shapes(h, S, F):
@@ -826,6 +859,50 @@ class ZoneVecEnv:
         return (self.get(nat.F_SKILL_LOGITS), self.get(nat.F_SKILL_VALUE), self.get(nat.F_POLICY_MU),
                 self.get(nat.F_POLICY_STD), self.get(nat.F_POLICY_VALUE), self.get(nat.F_OPTION_TERM_MU),
                 self.get(nat.F_OPTION_TERM_STD), self.get(nat.F_OPTION_TERM_PROB))
+
+    def collect_options(self, frames_per_proc, policy_seed=1, env_index0=0, discount=0.99, gae_lambda=0.95):
+        """collect_experiences of the Options agent (options/src/torch_ac/algos/_hier_policy_opt.py:10-205) on the
+        device with the loaded agent (``load_options`` with both critics).  Returns (lo, hi, termination_rate), the
+        reference's lo_exps / hi_exps and logs['termination_rate'], numpy:
+          lo  [N, T-1, ...]: obs, zone_obs, skill, action [.., 3] and log_prob [.., 3] (the third component decides the
+              termination), ended (bool, the termination draw), value, advantage, returnn, reward, env_reward (the
+              same), mask -- reshape(N*(T-1), ...) is the reference's flat order
+          hi  [M, ...] env-major: obs, zone_obs, action (the skill, int32), value, log_prob, advantage, returnn
+              (hi_exps), reward and mask (what the GAE used); and count (int32 [N], rows of every env: sum = M)
+          termination_rate  the share of all T * N frames whose option ended (:182)
+        Unlike the device policies, the collector lets a skill survive an auto-reset, as the reference's training loop
+        does.  The transition an env has open at the end stays on the device and is the first of its next call; the
+        handle must not be stepped by other means in between."""
+        T, M = self.collect_options_on_device(frames_per_proc, policy_seed, env_index0, discount, gae_lambda)
+        lo_l, hi_l = option_experience_layout(self.num_envs, self.num_zones, self.zone_feat, T, M)
+        raw, hi = {}, {}
+        for name, (field, shape, dt) in lo_l.items():
+            a = np.empty(shape, dt)
+            assert a.nbytes == lib().zenv_field_bytes(self._h, field)
+            check(lib().zenv_get(self._h, field, a.ctypes.data, 0))
+            raw[name] = a
+        rate = float(raw["ended"].mean())
+        raw["action"] = np.concatenate([raw["action"], raw.pop("term_action")[..., None]], axis=-1)
+        raw["log_prob"] = np.concatenate([raw["log_prob"], raw.pop("term_log_prob")[..., None]], axis=-1)
+        raw["ended"] = raw["ended"].view(bool)
+        lo = {name: a[:T - 1].swapaxes(0, 1) for name, a in raw.items()}
+        for name, (field, shape, dt) in hi_l.items():
+            a = np.empty(shape, dt)
+            if M:
+                assert a.nbytes == lib().zenv_field_bytes(self._h, field)
+                check(lib().zenv_get(self._h, field, a.ctypes.data, 0))
+            hi[name] = a
+        hi["count"] = self.get(nat.F_HI_COUNT)
+        return lo, hi, rate
+
+    def collect_options_on_device(self, frames_per_proc, policy_seed=1, env_index0=0, discount=0.99, gae_lambda=0.95):
+        """The same collection, results left in the handle's device buffers (``option_experience_layout`` names them).
+        Returns (T, M)."""
+        T, seed, index0, discount, gae_lambda = check_collect_option_args(frames_per_proc, policy_seed, env_index0,
+                                                                          discount, gae_lambda)
+        m = C.c_int64(0)
+        check(lib().zenv_collect_option(self._h, T, seed, index0, discount, gae_lambda, C.byref(m)))
+        return T, int(m.value)
 
     def load_skill_inverse(self, tensors, precision="f32"):
         """InverseModel, DIAYN's discriminator (main/src/inverse_model.py), for the diversity reward of

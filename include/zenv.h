@@ -144,7 +144,15 @@ enum {
     ZENV_F_OPTION_ENDED = 62,       /* int32   [N]   1 = the env's option ended on the last policy call: it picks a new
                                      *               skill on the next.  Cleared wherever the skill state is (a reset,
                                      *               zenv_set_skills); brought up to date like ZENV_F_SKILL */
-    ZENV_F_COUNT = 63
+    /* Options experience of the last zenv_collect_option() (before these three fields, ZENV_F_COUNT = 63).  Its other
+     * records reuse the fields above: ZENV_F_EXP_* (the low level, time-major [T][N], the first two action components;
+     * EXP_REWARD = the env reward), ZENV_F_LO_SKILL, ZENV_F_LO_ENV_REWARD and the ZENV_F_HI_* rows with ZENV_F_HI_COUNT
+     * (M closed transitions, env-major, ZENV_F_HI_ACTION = the skill; ZENV_F_HI_ACTION_MASK is not written and has
+     * size 0) */
+    ZENV_F_LO_TERM_ACTION = 63,     /* float32 [T,N] a_2, the third component of the low level's sample */
+    ZENV_F_LO_TERM_LOG_PROB = 64,   /* float32 [T,N] Normal(mu_2, std_2).log_prob(a_2) */
+    ZENV_F_LO_OPTION_ENDED = 65,    /* uint8   [T,N] the termination draw: 1 = the option ended after this frame */
+    ZENV_F_COUNT = 66
 };
 
 /* scripted on-device action sources (the build's own; used by bench/tests) */
@@ -270,7 +278,7 @@ int zenv_schedule_sequential(zenv_t *h, const int32_t *first, int32_t stride);
  * episode; the host keeps the ring ahead of the env with zenv_bank_update.  Only the host refills the ring, between
  * calls, so a call that could end more than `depth` episodes of an env is refused with ZENV_E_STATE (it could replay
  * maps): zenv_rollout with auto_reset and zenv_step_many(RESET_EVERY) beyond `depth` steps, zenv_collect and
- * zenv_collect_hier beyond `depth` frames, zenv_collect_skill beyond `depth` windows. */
+ * zenv_collect_hier and zenv_collect_option beyond `depth` frames, zenv_collect_skill beyond `depth` windows. */
 int zenv_schedule_ring(zenv_t *h, const int32_t *first, int32_t depth);
 /* FixedSeedsWrapper semantics on device: env i draws seeds from its own PCG64 stream
  * default_rng(rng_seeds[i]).integers(min_seed, max_seed+1); the bank must hold
@@ -611,7 +619,8 @@ int zenv_option_load(zenv_t *h, const zenv_option_weights *w);
  * next policy call.  A finished env (left alone by step_no_reset) idles: zeros in every output, nothing ends, its skill
  * and age stay.  zenv_rollout() refuses these policies (ZENV_E_ARG); with option weights loaded zenv_skill_forward,
  * zenv_collect_skill and ZENV_POLICY_SKILL_* answer ZENV_E_STATE as without skill weights, and so do
- * zenv_option_forward and ZENV_POLICY_OPTION_* without option weights.
+ * zenv_option_forward, zenv_collect_option and ZENV_POLICY_OPTION_* without option weights.  An auto-reset clears the
+ * skill here (evaluate_hier.py starts every episode with cur_skill = None); inside zenv_collect_option it does not.
  * ZENV_OPTION_COMPACT=0 / 1 in the environment at zenv_option_load picks how step 1 finds its envs (diagnostic, same
  * results): 0 -- workgroup b owns envs 4 b .. 4 b + 3 and leaves when none picks (the default up to 4 096 envs); 1 -- a
  * list of the picking envs is compacted first and workgroup b owns entries 4 b .. 4 b + 3 of it (the default above). */
@@ -707,6 +716,51 @@ int zenv_collect_hier(zenv_t *h, int frames_per_proc, uint64_t policy_seed, uint
  * handle, more windows (T / L) than a ring schedule's depth. */
 int zenv_collect_skill(zenv_t *h, int frames_per_proc, uint64_t policy_seed, uint64_t env_index0, float discount,
                        float gae_lambda, float diversity_coef, const float *skill_prior_logits, int sample_hi);
+
+/* ---- the same for the variable-length Options agent: collect_experiences of
+ * options/src/torch_ac/algos/_hier_policy_opt.py:10-205 (zenv_option_load with BOTH critics, plain task handle) ----
+ * T frames, each in this order:
+ *  1. every unfinished env with ZENV_F_SKILL < 0 or ZENV_F_OPTION_ENDED = 1 picks a skill -- the launches of
+ *     zenv_policy(ZENV_POLICY_OPTION_SAMPLE), in either ZENV_OPTION_COMPACT form -- and opens a high-level transition:
+ *     the obs, the skill, the high critic's value and log_softmax(logits)[skill];
+ *  2. the low level acts for every env and frame t is recorded: ZENV_F_EXP_* (obs, the action [T,N,2], its
+ *     per-dimension log_prob [T,N,2], value, mask = 1 - done of the previous step, carried from call to call),
+ *     ZENV_F_LO_SKILL (-1 for an env that idled), ZENV_F_LO_TERM_ACTION / _TERM_LOG_PROB (the third component of the
+ *     reference's _action and lo_log_probs) and ZENV_F_LO_OPTION_ENDED (the termination draw);
+ *  3. the envs step with auto-reset, on every frame; ZENV_F_EXP_REWARD and ZENV_F_LO_ENV_REWARD both hold the env
+ *     reward, and hi_reward[env] += reward (a float32 sum);
+ *  4. an env whose option ended closes its open transition with reward hi_reward and hi_mask = 0 if done else 1;
+ *     hi_reward restarts at 0 whether or not a transition was open.
+ * THE SKILL SURVIVES THE AUTO-RESET, as in the reference's training loop: cur_skills[j] is cleared by the termination
+ * draw alone, so an option, its open transition and its hi_reward run across an episode boundary, and
+ * ZENV_F_SKILL_AGE keeps counting.  This is the collector's rule only: zenv_policy(ZENV_POLICY_OPTION_*) keeps the
+ * evaluation loop's (evaluate_hier.py starts every episode with cur_skill = None), where an auto-reset clears the
+ * skill.  A call is therefore bit-identical to T rounds of zenv_policy(ZENV_POLICY_OPTION_SAMPLE) + zenv_step with
+ * auto-reset in which zenv_set_skills puts back, after every step, the skill of each env that was done and whose
+ * option did not end (up to ZENV_F_SKILL_AGE, which zenv_set_skills restarts).  Then
+ *   bootstrap:  V_hi(obs_T) of every env into ZENV_F_SKILL_VALUE (the log-softmax into ZENV_F_SKILL_LOGITS); nothing
+ *               is picked
+ *   low level:  GAE with discount over frames 0 .. T-2 and no bootstrap value, as zenv_collect_hier; advantage and
+ *               return of frame T-1 are 0
+ *   high level: per env over the transitions closed in this call, NO discount: delta = r + V_next m - V,
+ *               adv = delta + gae_lambda adv_next m, m = the transition's own hi_mask, V_next = the value of the env's
+ *               next transition (which may be the one still open) or, when none was picked after the last close,
+ *               V_hi(obs_T); adv_next = 0 for the last.
+ * The closed transitions are handed out env-major (ZENV_F_HI_OBS / _ZONE_OBS / _ACTION / _VALUE / _LOG_PROB /
+ * _ADVANTAGE / _RETURN / _REWARD / _MASK, ZENV_F_HI_COUNT, *n_hi = M; M = 0 is a valid result).  The open one and
+ * hi_reward stay on the device and are the env's first transition of the next call: THE CARRY ASSUMES THAT THE HANDLE
+ * IS NOT STEPPED BY OTHER MEANS BETWEEN TWO CALLS.  At the start of a call the skill state is brought up to date once,
+ * as the policy does; an env that enters without a skill has its open transition dropped (and hi_reward 0).  A
+ * termination without an open transition -- a skill planted by zenv_set_skills or picked by zenv_policy -- closes
+ * nothing.  zenv_reset drops the open transition of the envs it resets and zeroes their hi_reward (their skill is
+ * cleared as well); zenv_option_load and zenv_skill_load drop every open transition.  A finished env at frame 0 draws
+ * nothing until the frame's auto-reset brings it back.  Randomness: exactly the policy's, Philox keyed by
+ * (policy_seed, env_index0 + env, zenv_step_count) with the same tags.  One host synchronisation, to learn M.
+ * ZENV_E_ARG: frames_per_proc < 2, frames_per_proc x envs >= 2^31, a non-finite discount or gae_lambda, or one
+ * outside [0, 1].  ZENV_E_STATE: no option weights (loaded skill weights included), a critic missing, zenv_host_io on,
+ * a goal-conditioned or solver-ordered handle, more frames than a ring schedule's depth. */
+int zenv_collect_option(zenv_t *h, int frames_per_proc, uint64_t policy_seed, uint64_t env_index0, float discount,
+                        float gae_lambda, int64_t *n_hi);
 
 /* ---- results ---- */
 int zenv_get(zenv_t *h, int field, void *dst, int dst_on_device);
