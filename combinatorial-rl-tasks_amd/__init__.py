@@ -4,6 +4,8 @@ Layout of this package (only what the hot path needs):
   csrc/        HIP kernels (gfx950) + the C ABI of include/zenv.h + the host layout sampler
   _native.py   ctypes binding (no PyTorch, no CPU fallback)
   vec_env.py   ZoneVecEnv: N device-resident envs, struct-of-arrays results
+  agents.py    the four agents' pure host functions: checkpoint -> tensors, tensor shapes, collector argument checks,
+               experience layouts (no shared library needed)
   envs/        host-side mirror of the reference interface (main/envs/*): registry ids,
                TSPEnv/TimedTSPEnv/ColourMatchEnv, FixedSeedsWrapper/ZoneWrapper, make_*_env
   penv.py      ParallelEnv-shaped vector env over one batched handle

@@ -46,39 +46,68 @@ def evaluate(env_id, policy, n_maps=100, n_runs_per_map=5, env_seed0=EVAL_SEED0,
 
     Returns ``{"return": [[...]], "length": [[...]], "goal_met": [[...]]}``."""
     cfg = config_for_id(env_id) if isinstance(env_id, str) else env_id
-    n = n_maps * n_runs_per_map
-    env = ZoneVecEnv(cfg, n, device=device)
-    env.build_bank(env_seed0, n_maps)
-    env.schedule_sequential(first=np.repeat(np.arange(n_maps, dtype=np.int32), n_runs_per_map), stride=0)
-    env.reset()
     if isinstance(policy, str):
         policy = load_model_state(policy)
+    tensors = None
     if isinstance(policy, dict):
         from .vec_env import mlp_tensors_from_state_dict
-        env.load_mlp(mlp_tensors_from_state_dict(policy), precision=precision)
+        tensors = mlp_tensors_from_state_dict(policy)
         policy = nat.POLICY_MLP_MEAN if argmax else nat.POLICY_MLP_SAMPLE
-    goal = np.zeros(n, bool)
-    horizon = cfg.num_steps if max_steps is None else max_steps
-    if callable(policy):
-        o, zo = env.step_results(None, copy=False)[:2]
-    for t in range(horizon):
-        if callable(policy):               # one upload, one launch, one download, one synchronisation per step
-            o, zo, _, d, g, _ = env.step_results(np.asarray(policy(o, zo), np.float32), auto_reset=False, copy=False)
-        else:
-            env.policy(int(policy), policy_seed=policy_seed)
-            env.step(None, auto_reset=False)
-            _, _, _, d, g, _ = env.step_results(None, copy=False)
-        goal |= g
-        if d.all():                        # every episode finished (evaluate.py:64-72)
-            break
-    out = {
-        "return": env.get(nat.F_LAST_RETURN).reshape(n_maps, n_runs_per_map).tolist(),
-        "length": env.get(nat.F_LAST_LEN).reshape(n_maps, n_runs_per_map).tolist(),
-        "goal_met": goal.reshape(n_maps, n_runs_per_map).tolist(),
-    }
-    env.close()
+    o = zo = None                          # a host policy's next input: the last step's observations
+
+    def setup(env):
+        nonlocal o, zo
+        env.reset()
+        if tensors is not None:
+            env.load_mlp(tensors, precision=precision)
+        if callable(policy):
+            o, zo = env.step_results(None, copy=False)[:2]
+
+    def host_step(env):                    # one upload, one launch, one download, one synchronisation per step
+        nonlocal o, zo
+        o, zo, _, d, g, _ = env.step_results(np.asarray(policy(o, zo), np.float32), auto_reset=False, copy=False)
+        return d, g
+
+    return _run_batched(cfg, n_maps, n_runs_per_map, env_seed0, device, max_steps, pkl_path, setup,
+                        host_step if callable(policy) else _device_step(policy, policy_seed))
+
+
+def _device_step(policy, policy_seed):
+    """step(env) of ``_run_batched`` for an on-device policy: pick the actions, step, fetch the flags."""
+    def step(env):
+        env.policy(int(policy), policy_seed=policy_seed)
+        env.step(None, auto_reset=False)
+        return env.step_results(None, copy=False)[3:5]
+    return step
+
+
+def _run_batched(cfg, n_maps, n_runs_per_map, env_seed0, device, max_steps, pkl_path, setup, step):
+    """The protocol all evaluators share: one env per map and run (the maps of env seeds env_seed0 ..), every episode
+    run once, to the horizon or until all are done.  setup(env) switches the variant on, resets and loads the agent;
+    step(env) advances every env by one step without auto-reset and returns that step's (done, goal_met).  Returns
+    ``{"return": [[...]], "length": [[...]], "goal_met": [[...]]}``, [map][run], and writes ``{"return": ...}`` to
+    ``pkl_path`` as the reference's scripts do (evaluate.py:76-78)."""
+    n = n_maps * n_runs_per_map
+    env = ZoneVecEnv(cfg, n, device=device)
+    try:
+        env.build_bank(env_seed0, n_maps)
+        env.schedule_sequential(first=np.repeat(np.arange(n_maps, dtype=np.int32), n_runs_per_map), stride=0)
+        setup(env)
+        goal = np.zeros(n, bool)
+        for t in range(cfg.num_steps if max_steps is None else max_steps):
+            d, g = step(env)
+            goal |= g
+            if d.all():                    # every episode finished (evaluate.py:64-72)
+                break
+        out = {
+            "return": env.get(nat.F_LAST_RETURN).reshape(n_maps, n_runs_per_map).tolist(),
+            "length": env.get(nat.F_LAST_LEN).reshape(n_maps, n_runs_per_map).tolist(),
+            "goal_met": goal.reshape(n_maps, n_runs_per_map).tolist(),
+        }
+    finally:
+        env.close()
     if pkl_path:
-        with open(pkl_path, "wb") as f:       # evaluate.py:76-78 writes {"return": record_returns}
+        with open(pkl_path, "wb") as f:
             pickle.dump({"return": out["return"]}, f)
     return out
 
@@ -119,35 +148,14 @@ def evaluate_zone_hrl(env_id, model, n_maps=100, n_runs_per_map=5, env_seed0=EVA
         cfg = env_id
     hi_sd, lo_sd = load_hier_model_state(model) if isinstance(model, str) else model
     tensors = hier_tensors_from_state_dicts(hi_sd, lo_sd)
-    n = n_maps * n_runs_per_map
-    env = ZoneVecEnv(cfg, n, device=device)
-    try:
-        env.build_bank(env_seed0, n_maps)
-        env.schedule_sequential(first=np.repeat(np.arange(n_maps, dtype=np.int32), n_runs_per_map), stride=0)
+
+    def setup(env):
         env.enable_goals()
         env.reset()
         env.load_hier(tensors)
-        policy = nat.POLICY_HIER_MEAN if argmax else nat.POLICY_HIER_SAMPLE
-        goal = np.zeros(n, bool)
-        horizon = cfg.num_steps if max_steps is None else max_steps
-        for t in range(horizon):
-            env.policy(policy, policy_seed=policy_seed)
-            env.step(None, auto_reset=False)
-            _, _, _, d, g, _ = env.step_results(None, copy=False)
-            goal |= g
-            if d.all():                    # every episode finished (evaluate_zone_hrl.py:66-75)
-                break
-        out = {
-            "return": env.get(nat.F_LAST_RETURN).reshape(n_maps, n_runs_per_map).tolist(),
-            "length": env.get(nat.F_LAST_LEN).reshape(n_maps, n_runs_per_map).tolist(),
-            "goal_met": goal.reshape(n_maps, n_runs_per_map).tolist(),
-        }
-    finally:
-        env.close()
-    if pkl_path:
-        with open(pkl_path, "wb") as f:
-            pickle.dump({"return": out["return"]}, f)
-    return out
+
+    return _run_batched(cfg, n_maps, n_runs_per_map, env_seed0, device, max_steps, pkl_path, setup,
+                        _device_step(nat.POLICY_HIER_MEAN if argmax else nat.POLICY_HIER_SAMPLE, policy_seed))
 
 
 def evaluate_hier(env_id, model, n_maps=100, n_runs_per_map=5, n_skills=None, skill_len=200, policy_seed=0,
@@ -169,34 +177,13 @@ def evaluate_hier(env_id, model, n_maps=100, n_runs_per_map=5, n_skills=None, sk
     S = tensors["hi_logit_w"].shape[0]
     if n_skills is not None and n_skills != S:
         raise ValueError(f"n_skills={n_skills}, but the checkpoint's high level has {S} skills")
-    n = n_maps * n_runs_per_map
-    env = ZoneVecEnv(cfg, n, device=device)
-    try:
-        env.build_bank(env_seed0, n_maps)
-        env.schedule_sequential(first=np.repeat(np.arange(n_maps, dtype=np.int32), n_runs_per_map), stride=0)
+
+    def setup(env):
         env.reset()
         env.load_skills(tensors, skill_len=skill_len)
-        policy = nat.POLICY_SKILL_MEAN if argmax else nat.POLICY_SKILL_SAMPLE
-        goal = np.zeros(n, bool)
-        horizon = cfg.num_steps if max_steps is None else max_steps
-        for t in range(horizon):
-            env.policy(policy, policy_seed=policy_seed)
-            env.step(None, auto_reset=False)
-            _, _, _, d, g, _ = env.step_results(None, copy=False)
-            goal |= g
-            if d.all():                    # every episode finished (evaluate_hier.py:72-79)
-                break
-        out = {
-            "return": env.get(nat.F_LAST_RETURN).reshape(n_maps, n_runs_per_map).tolist(),
-            "length": env.get(nat.F_LAST_LEN).reshape(n_maps, n_runs_per_map).tolist(),
-            "goal_met": goal.reshape(n_maps, n_runs_per_map).tolist(),
-        }
-    finally:
-        env.close()
-    if pkl_path:
-        with open(pkl_path, "wb") as f:
-            pickle.dump({"return": out["return"]}, f)
-    return out
+
+    return _run_batched(cfg, n_maps, n_runs_per_map, env_seed0, device, max_steps, pkl_path, setup,
+                        _device_step(nat.POLICY_SKILL_MEAN if argmax else nat.POLICY_SKILL_SAMPLE, policy_seed))
 
 
 def evaluate_options(env_id, model, n_maps=100, n_runs_per_map=1, n_skills=None, policy_seed=0, argmax=False,
@@ -218,34 +205,20 @@ def evaluate_options(env_id, model, n_maps=100, n_runs_per_map=1, n_skills=None,
     S = tensors["hi_logit_w"].shape[0]
     if n_skills is not None and n_skills != S:
         raise ValueError(f"n_skills={n_skills}, but the checkpoint's high level has {S} skills")
-    n = n_maps * n_runs_per_map
-    env = ZoneVecEnv(cfg, n, device=device)
-    try:
-        env.build_bank(env_seed0, n_maps)
-        env.schedule_sequential(first=np.repeat(np.arange(n_maps, dtype=np.int32), n_runs_per_map), stride=0)
+    policy = nat.POLICY_OPTION_MEAN if argmax else nat.POLICY_OPTION_SAMPLE
+    ended = np.zeros(n_maps * n_runs_per_map, np.int64)
+
+    def setup(env):
         env.reset()
         env.load_options(tensors)
-        policy = nat.POLICY_OPTION_MEAN if argmax else nat.POLICY_OPTION_SAMPLE
-        goal = np.zeros(n, bool)
-        ended = np.zeros(n, np.int64)
-        horizon = cfg.num_steps if max_steps is None else max_steps
-        for t in range(horizon):
-            env.policy(policy, policy_seed=policy_seed)
-            ended += env.get(nat.F_OPTION_ENDED)      # 0 for an env that has finished
-            env.step(None, auto_reset=False)
-            _, _, _, d, g, _ = env.step_results(None, copy=False)
-            goal |= g
-            if d.all():                    # every episode finished (evaluate_hier.py:76-85)
-                break
-        out = {
-            "return": env.get(nat.F_LAST_RETURN).reshape(n_maps, n_runs_per_map).tolist(),
-            "length": env.get(nat.F_LAST_LEN).reshape(n_maps, n_runs_per_map).tolist(),
-            "goal_met": goal.reshape(n_maps, n_runs_per_map).tolist(),
-            "terminations": ended.reshape(n_maps, n_runs_per_map).tolist(),
-        }
-    finally:
-        env.close()
-    if pkl_path:
-        with open(pkl_path, "wb") as f:
-            pickle.dump({"return": out["return"]}, f)
+
+    def step(env):
+        nonlocal ended
+        env.policy(policy, policy_seed=policy_seed)
+        ended += env.get(nat.F_OPTION_ENDED)      # 0 for an env that has finished
+        env.step(None, auto_reset=False)
+        return env.step_results(None, copy=False)[3:5]
+
+    out = _run_batched(cfg, n_maps, n_runs_per_map, env_seed0, device, max_steps, pkl_path, setup, step)
+    out["terminations"] = ended.reshape(n_maps, n_runs_per_map).tolist()
     return out

@@ -64,16 +64,22 @@ class TorchZoneEnv:
         with self._torch.cuda.device(self.device):
             return self._alias(nat.F_EP_LEN)
 
-    def _alias(self, field):
-        t = self._torch.as_tensor(_DeviceView(self.env.device_ptr(field), self.env._shape(field),
-                                              _FIELD_DTYPES[field]), device=self.device)
+    def _alias(self, field, shape=None, dtype=None):
+        """A tensor over a device buffer of the handle; shape and dtype default to the env's own for that field."""
+        view = _DeviceView(self.env.device_ptr(field), self.env._shape(field) if shape is None else shape,
+                           _FIELD_DTYPES[field] if dtype is None else dtype)
+        t = self._torch.as_tensor(view, device=self.device)
         assert t.data_ptr() == self.env.device_ptr(field), "torch copied instead of aliasing"
         return t
 
-    def _alias_raw(self, field, shape):
-        t = self._torch.as_tensor(_DeviceView(self.env.device_ptr(field), shape, np.float32), device=self.device)
-        assert t.data_ptr() == self.env.device_ptr(field), "torch copied instead of aliasing"
-        return t
+    def _alias_layout(self, layout, skip=False):
+        """Every buffer of a layout (name -> (field id, shape, dtype)) aliased.  skip: the buffers hold nothing (no
+        high-level row yet) -- empty tensors of the right dtype on the env's device instead."""
+        torch = self._torch
+        if skip:
+            return {name: torch.empty(shape, dtype=getattr(torch, np.dtype(dt).name), device=self.device)
+                    for name, (_, shape, dt) in layout.items()}
+        return {name: self._alias(field, shape, dt) for name, (field, shape, dt) in layout.items()}
 
     def reset(self, mask=None):
         self.env.reset(mask)
@@ -93,11 +99,8 @@ class TorchZoneEnv:
         transposed views of time-major memory, so ``reshape(N*T, ...)`` copies them once).  Enqueued
         on the shared stream like everything else: no synchronisation, no host copy."""
         self.env.collect_on_device(frames_per_proc, policy_seed, env_index0, discount, gae_lambda)
-        out = {}
-        for name, (field, shape, time_major) in self.env.experience_layout(frames_per_proc).items():
-            t = self._alias_raw(field, shape)
-            out[name] = t.transpose(0, 1) if time_major else t        # [N, T, ...] views either way
-        return out
+        raw = self._alias_layout(self.env._experience_rows(frames_per_proc))
+        return {name: t.transpose(0, 1) for name, t in raw.items()}     # [N, T, ...] views of time-major memory
 
     def load_hier(self, hi_state_dict, lo_state_dict):
         """Put HighPolicyValueModel / LoPolicyValueModel state_dicts (zone-goals/src/hier_policy_value_models.py; torch
@@ -114,16 +117,10 @@ class TorchZoneEnv:
         env = self.env
         T, M = env.collect_hier_on_device(frames_per_proc, policy_seed, env_index0, discount, gae_lambda)
         lo_l, hi_l = hier_experience_layout(env.num_envs, env.num_zones, env.zone_feat, T, M)
-        torch = self._torch
-        lo = {name: self._alias_typed(field, shape, dt)[:T - 1].transpose(0, 1) for name, (field, shape, dt) in lo_l.items()}
-        hi = {}
-        for name, (field, shape, dt) in hi_l.items():
-            if M:
-                t = self._alias_typed(field, shape, dt)
-            else:
-                t = torch.empty(shape, dtype=getattr(torch, np.dtype(dt).name), device=self.device)
-            hi[name] = t.view(torch.bool) if name == "action_mask" else t
-        hi["count"] = self._alias_typed(nat.F_HI_COUNT, (env.num_envs,), np.int32)
+        lo = {name: t[:T - 1].transpose(0, 1) for name, t in self._alias_layout(lo_l).items()}
+        hi = self._alias_layout(hi_l, skip=not M)
+        hi["action_mask"] = hi["action_mask"].view(self._torch.bool)
+        hi["count"] = self._alias(nat.F_HI_COUNT)
         return lo, hi
 
     def load_skills(self, hi_state_dict, lo_state_dict, skill_len=200):
@@ -151,8 +148,8 @@ class TorchZoneEnv:
                                             diversity_coef, skill_prior_logits, sample_hi)
         L = T * env.num_envs // M
         lo_l, hi_l = skill_experience_layout(env.num_envs, env.num_zones, env.zone_feat, T, L)
-        lo = {name: self._alias_typed(field, shape, dt).transpose(0, 1) for name, (field, shape, dt) in lo_l.items()}
-        hi = {name: self._alias_typed(field, shape, dt) for name, (field, shape, dt) in hi_l.items()}
+        lo = {name: t.transpose(0, 1) for name, t in self._alias_layout(lo_l).items()}
+        hi = self._alias_layout(hi_l)
         keep = lo["mask"][:, 1:] != 0
         inverse = {"obs": lo["obs"][:, 1:][keep], "zone_obs": lo["zone_obs"][:, 1:][keep],
                    "skill": lo["skill"][:, :-1][keep]}
@@ -176,24 +173,13 @@ class TorchZoneEnv:
         env = self.env
         T, M = env.collect_options_on_device(frames_per_proc, policy_seed, env_index0, discount, gae_lambda)
         lo_l, hi_l = option_experience_layout(env.num_envs, env.num_zones, env.zone_feat, T, M)
-        torch = self._torch
-        raw = {name: self._alias_typed(field, shape, dt) for name, (field, shape, dt) in lo_l.items()}
+        raw = self._alias_layout(lo_l)
         rate = raw["ended"].float().mean()
-        raw["ended"] = raw["ended"].view(torch.bool)
+        raw["ended"] = raw["ended"].view(self._torch.bool)
         lo = {name: t[:T - 1].transpose(0, 1) for name, t in raw.items()}
-        hi = {}
-        for name, (field, shape, dt) in hi_l.items():
-            if M:
-                hi[name] = self._alias_typed(field, shape, dt)
-            else:
-                hi[name] = torch.empty(shape, dtype=getattr(torch, np.dtype(dt).name), device=self.device)
-        hi["count"] = self._alias_typed(nat.F_HI_COUNT, (env.num_envs,), np.int32)
+        hi = self._alias_layout(hi_l, skip=not M)
+        hi["count"] = self._alias(nat.F_HI_COUNT)
         return lo, hi, rate
-
-    def _alias_typed(self, field, shape, dtype):
-        t = self._torch.as_tensor(_DeviceView(self.env.device_ptr(field), shape, dtype), device=self.device)
-        assert t.data_ptr() == self.env.device_ptr(field), "torch copied instead of aliasing"
-        return t
 
     def step(self, actions, auto_reset=True):
         """actions: float32 CUDA tensor (N, 2) on the env's device (contiguous).  Asynchronous: the

@@ -13,6 +13,12 @@ import numpy as np
 
 from . import _native as nat
 from ._native import Config, ZenvError, check, lib
+from .agents import (_HIER_ENC, _HIER_CRITIC, HIER_HI_KEYS, HIER_LO_KEYS, SKILL_HI_KEYS, SKILL_LO_KEYS,   # noqa: F401
+                     INVERSE_KEYS, _lo_rows, mlp_tensors_from_state_dict, mlp_tensor_shapes, hier_tensor_shapes,
+                     skill_tensor_shapes, option_tensor_shapes, inverse_tensor_shapes, hier_tensors_from_state_dicts,
+                     skill_tensors_from_state_dicts, option_tensors_from_state_dicts, inverse_tensors_from_state_dict,
+                     check_collect_hier_args, check_collect_skill_args, check_collect_option_args,
+                     hier_experience_layout, skill_experience_layout, option_experience_layout, skill_num_frames)
 
 _FIELD_DTYPES = {
     nat.F_OBS: np.float32, nat.F_ZONE_OBS: np.float32, nat.F_REWARD: np.float32,
@@ -75,330 +81,6 @@ def apply_overrides(cfg, overrides):
         else:
             setattr(cfg, k, v)
     return cfg
-
-
-def mlp_tensors_from_state_dict(sd):
-    """ACModel.state_dict() (flat_model.py:24-52) -> the tensors load_mlp wants (numpy float32)."""
-    names = {"zone_w1": "env_model.zone_net_.0.weight", "zone_b1": "env_model.zone_net_.0.bias",
-             "zone_w2": "env_model.zone_net_.2.weight", "zone_b2": "env_model.zone_net_.2.bias",
-             "zone_w3": "env_model.zone_net_.4.weight", "zone_b3": "env_model.zone_net_.4.bias",
-             "comb_w": "env_model.combine_net_.weight", "comb_b": "env_model.combine_net_.bias",
-             "enc_w": "actor.enc_.0.0.weight", "enc_b": "actor.enc_.0.0.bias",
-             "mu_w": "actor.mu_.weight", "mu_b": "actor.mu_.bias",
-             "std_w": "actor.std_.weight", "std_b": "actor.std_.bias"}
-    if "critic.0.weight" in sd and "critic.2.weight" in sd:      # non-distributional critic, flat_model.py:43-47
-        names.update({"critic_w1": "critic.0.weight", "critic_b1": "critic.0.bias",
-                      "critic_w2": "critic.2.weight", "critic_b2": "critic.2.bias"})
-    elif "critic.0.weight" in sd and "critic_mu.weight" in sd:   # distributional_value=True, flat_model.py:35-41
-        names.update({"critic_w1": "critic.0.weight", "critic_b1": "critic.0.bias",
-                      "critic_w2": "critic_mu.weight", "critic_b2": "critic_mu.bias",
-                      "critic_sigma_w": "critic_sigma.weight", "critic_sigma_b": "critic_sigma.bias"})
-    return {k: np.asarray(sd[v].detach().cpu().numpy() if hasattr(sd[v], "detach") else sd[v], np.float32)
-            for k, v in names.items()}
-
-
-# zenv_hier_weights name -> state_dict key (zone-goals/src/hier_policy_value_models.py:19-86, env_model.py:48-116,
-# policy_network.py:9-62): hi_model_state and lo_model_state of status.pt (zone-goals/src/utils/storage.py:57-61)
-_HIER_ENC = {"zone_w1": "env_model.zone_net_.0.weight", "zone_b1": "env_model.zone_net_.0.bias",
-             "zone_w2": "env_model.zone_net_.2.weight", "zone_b2": "env_model.zone_net_.2.bias",
-             "zone_w3": "env_model.zone_net_.4.weight", "zone_b3": "env_model.zone_net_.4.bias",
-             "comb_w": "env_model.combine_net_.weight", "comb_b": "env_model.combine_net_.bias"}
-_HIER_CRITIC = {"critic_w1": "critic.0.weight", "critic_b1": "critic.0.bias",
-                "critic_w2": "critic.2.weight", "critic_b2": "critic.2.bias"}
-HIER_HI_KEYS = dict(_HIER_ENC, actor_w1="actor.0.weight", actor_b1="actor.0.bias", actor_w2="actor.2.weight",
-                    actor_b2="actor.2.bias")
-HIER_LO_KEYS = dict(_HIER_ENC, enc_w="actor.enc_.0.0.weight", enc_b="actor.enc_.0.0.bias", mu_w="actor.mu_.weight",
-                    mu_b="actor.mu_.bias", std_w="actor.std_.weight", std_b="actor.std_.bias")
-
-
-def hier_tensor_shapes(h, F):
-    """The shape of every zenv_hier_weights tensor for hidden size h and zone rows of F features."""
-    enc = lambda x: {"zone_w1": (h, x + F), "zone_b1": (h,), "zone_w2": (h, h), "zone_b2": (h,), "zone_w3": (h, h),
-                     "zone_b3": (h,), "comb_w": (h, x + h), "comb_b": (h,)}
-    crit = {"critic_w1": (h, h), "critic_b1": (h,), "critic_w2": (1, h), "critic_b2": (1,)}
-    hi = dict(enc(8), actor_w1=(h, h + F), actor_b1=(h,), actor_w2=(1, h), actor_b2=(1,), **crit)
-    lo = dict(enc(10), enc_w=(h, h), enc_b=(h,), mu_w=(2, h), mu_b=(2,), std_w=(2, h), std_b=(2,), **crit)
-    return dict({"hi_" + k: v for k, v in hi.items()}, **{"lo_" + k: v for k, v in lo.items()})
-
-
-def hier_tensors_from_state_dicts(hi_sd, lo_sd):
-    """HighPolicyValueModel.state_dict() and LoPolicyValueModel.state_dict() -> the tensors ``ZoneVecEnv.load_hier``
-    wants (numpy float32, names of ``_native.HIER_*``).  The critics are taken when present (critic.0 and critic.2
-    both).  A missing key or a tensor whose shape does not fit the others raises ValueError naming it."""
-    out = {}
-    for level, sd, keys in (("hi", hi_sd, HIER_HI_KEYS), ("lo", lo_sd, HIER_LO_KEYS)):
-        names = dict(keys)
-        if "critic.0.weight" in sd or "critic.2.weight" in sd:
-            names.update(_HIER_CRITIC)
-        for name, key in names.items():
-            if key not in sd:
-                raise ValueError(f"{level}_model_state has no {key!r} (needed for {level}_{name})")
-            v = sd[key]
-            out[f"{level}_{name}"] = np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, np.float32)
-    h = out["hi_zone_b1"].shape[0] if out["hi_zone_b1"].ndim == 1 else -1
-    F = out["hi_zone_w1"].shape[1] - 8 if out["hi_zone_w1"].ndim == 2 else -1
-    want = hier_tensor_shapes(h, F)
-    for name, a in out.items():
-        if a.shape != want[name]:
-            level, rest = name.split("_", 1)
-            key = (HIER_HI_KEYS if level == "hi" else HIER_LO_KEYS).get(rest) or _HIER_CRITIC[rest]
-            raise ValueError(f"{level}_model_state[{key!r}] has shape {tuple(a.shape)}, expected {want[name]} "
-                             f"(hidden size {h}, zone rows of {F} features)")
-    return out
-
-
-def check_collect_hier_args(frames_per_proc, policy_seed=1, env_index0=0, discount=0.99, gae_lambda=0.95):
-    """What ``ZoneVecEnv.collect_hier`` checks before it calls into the library: T >= 2 frames (the low level hands
-    out T - 1), a discount and a lambda in [0, 1], non-negative 64-bit seeds.  Returns the normalised arguments."""
-    if isinstance(frames_per_proc, bool) or int(frames_per_proc) != frames_per_proc:
-        raise ValueError(f"frames_per_proc must be an integer, got {frames_per_proc!r}")
-    T = int(frames_per_proc)
-    if T < 2:
-        raise ValueError(f"frames_per_proc must be at least 2 (the low level hands out T - 1 frames), got {T}")
-    for name, v in (("discount", discount), ("gae_lambda", gae_lambda)):
-        if not (0.0 <= float(v) <= 1.0):
-            raise ValueError(f"{name} must lie in [0, 1], got {v!r}")
-    for name, v in (("policy_seed", policy_seed), ("env_index0", env_index0)):
-        if int(v) != v or not (0 <= int(v) < 2 ** 64):
-            raise ValueError(f"{name} must be an integer in [0, 2^64), got {v!r}")
-    return T, int(policy_seed), int(env_index0), float(discount), float(gae_lambda)
-
-
-def hier_experience_layout(num_envs, num_zones, zone_feat, frames_per_proc, n_hi):
-    """The buffers one ``collect_hier`` of T frames fills, as (lo, hi): name -> (field id, shape in memory, dtype).
-    lo: time-major [T, N, ...] device buffers, handed out as [N, T-1, ...] views (the names of lo_exps in
-    _hier_policy_opt.py:125-139, plus goal, reward (shaped), env_reward and mask).  hi: flat env-major [M, ...]
-    (hi_exps, :142-161, plus each transition's reward and hi_mask), M = n_hi."""
-    N, Z, F, T, M = int(num_envs), int(num_zones), int(zone_feat), int(frames_per_proc), int(n_hi)
-    f32 = np.float32
-    lo = {"obs": (nat.F_EXP_OBS, (T, N, 8), f32), "zone_obs": (nat.F_EXP_ZONE_OBS, (T, N, Z, F), f32),
-          "goal": (nat.F_LO_GOAL, (T, N, 2), f32), "action": (nat.F_EXP_ACTION, (T, N, 2), f32),
-          "log_prob": (nat.F_EXP_LOG_PROB, (T, N, 2), f32), "value": (nat.F_EXP_VALUE, (T, N), f32),
-          "advantage": (nat.F_EXP_ADVANTAGE, (T, N), f32), "returnn": (nat.F_EXP_RETURN, (T, N), f32),
-          "reward": (nat.F_EXP_REWARD, (T, N), f32), "env_reward": (nat.F_LO_ENV_REWARD, (T, N), f32),
-          "mask": (nat.F_EXP_MASK, (T, N), f32)}
-    hi = {"obs": (nat.F_HI_OBS, (M, 8), f32), "zone_obs": (nat.F_HI_ZONE_OBS, (M, Z, F), f32),
-          "action": (nat.F_HI_ACTION, (M,), np.int32), "action_mask": (nat.F_HI_ACTION_MASK, (M, Z), np.uint8),
-          "value": (nat.F_HI_VALUE, (M,), f32), "log_prob": (nat.F_HI_LOG_PROB, (M,), f32),
-          "advantage": (nat.F_HI_ADVANTAGE, (M,), f32), "returnn": (nat.F_HI_RETURN, (M,), f32),
-          "reward": (nat.F_HI_REWARD, (M,), f32), "mask": (nat.F_HI_MASK, (M,), f32)}
-    return lo, hi
-
-
-# zenv_skill_weights name -> state_dict key (main/src/hier_policy_value_models.py:19-76, env_model.py:81-117,
-# policy_network.py:9-55): hi_model_state and lo_model_state of status.pt (main/scripts/train_skill_planner.py:152-163)
-SKILL_HI_KEYS = dict(_HIER_ENC, enc_w="actor.enc_.0.0.weight", enc_b="actor.enc_.0.0.bias",
-                     logit_w="actor.discrete_.0.weight", logit_b="actor.discrete_.0.bias")
-SKILL_LO_KEYS = HIER_LO_KEYS
-
-
-def skill_tensor_shapes(h, S, F):
-    """The shape of every zenv_skill_weights tensor for hidden size h, S skills and zone rows of F features."""
-    enc = lambda x: {"zone_w1": (h, x + F), "zone_b1": (h,), "zone_w2": (h, h), "zone_b2": (h,), "zone_w3": (h, h),
-                     "zone_b3": (h,), "comb_w": (h, x + h), "comb_b": (h,)}
-    crit = lambda x: {"critic_w1": (h, x), "critic_b1": (h,), "critic_w2": (1, h), "critic_b2": (1,)}
-    hi = dict(enc(8), enc_w=(h, h), enc_b=(h,), logit_w=(S, h), logit_b=(S,), **crit(h))
-    lo = dict(enc(8 + S), enc_w=(h, h + S), enc_b=(h,), mu_w=(2, h), mu_b=(2,), std_w=(2, h), std_b=(2,), **crit(h + S))
-    return dict({"hi_" + k: v for k, v in hi.items()}, **{"lo_" + k: v for k, v in lo.items()})
-
-
-def option_tensor_shapes(h, S, F):
-    """The shape of every zenv_option_weights tensor: ``skill_tensor_shapes`` with three rows in lo_mu_* / lo_std_*."""
-    return dict(skill_tensor_shapes(h, S, F), lo_mu_w=(3, h), lo_mu_b=(3,), lo_std_w=(3, h), lo_std_b=(3,))
-
-
-def option_tensors_from_state_dicts(hi_sd, lo_sd):
-    """HighPolicyValueModel.state_dict() and LoPolicyValueModel.state_dict() of the variable-length Options agent
-    (options/src/hier_policy_value_models.py) -> the tensors ``ZoneVecEnv.load_options`` wants (numpy float32, names of
-    ``_native.SKILL_*``).  h, S and F come from the shapes; the critics are taken when present.  A skill planner's
-    checkpoint (actor.mu_ / actor.std_ of two rows), a Zone-goals checkpoint, a missing key or a tensor whose shape
-    does not fit the others raises ValueError naming it."""
-    return _skill_family_tensors(hi_sd, lo_sd, 3)
-
-
-def skill_tensors_from_state_dicts(hi_sd, lo_sd):
-    """HighPolicyValueModel.state_dict() and LoPolicyValueModel.state_dict() of the fixed-length-skills agent -> the
-    tensors ``ZoneVecEnv.load_skills`` wants (numpy float32, names of ``_native.SKILL_*``).  The hidden size h and the
-    number of skills S come from the shapes (actor.discrete_.0 is [S, h]).  The critics are taken when present.  A
-    Zone-goals checkpoint (the same hi_model_state / lo_model_state keys, an actor.0 / actor.2 high level), a missing
-    key or a tensor whose shape does not fit the others raises ValueError naming it."""
-    return _skill_family_tensors(hi_sd, lo_sd, 2)
-
-
-def _skill_family_tensors(hi_sd, lo_sd, n_out):
-    """n_out: the rows of the low level's actor.mu_ / actor.std_ -- 2: a skill planner's, 3: an Options agent's."""
-    kind = "a skill planner's" if n_out == 2 else "an Options agent's"
-    if "actor.0.weight" in hi_sd or "actor.2.weight" in hi_sd:
-        raise ValueError("hi_model_state has 'actor.0' / 'actor.2': a Zone-goals checkpoint (load it with "
-                         f"hier_tensors_from_state_dicts / load_hier), not {kind}")
-    mu = lo_sd.get("actor.mu_.weight")
-    if n_out == 3 and mu is not None and tuple(mu.shape)[:1] == (2,):
-        raise ValueError("lo_model_state['actor.mu_.weight'] has 2 rows: a skill planner's checkpoint (load it with "
-                         "skill_tensors_from_state_dicts / load_skills), not an Options agent's")
-    if n_out == 2 and mu is not None and tuple(mu.shape)[:1] == (3,):
-        raise ValueError("lo_model_state['actor.mu_.weight'] has 3 rows: an Options agent's checkpoint (load it with "
-                         "option_tensors_from_state_dicts / load_options), not a skill planner's")
-    out = {}
-    for level, sd, keys in (("hi", hi_sd, SKILL_HI_KEYS), ("lo", lo_sd, SKILL_LO_KEYS)):
-        names = dict(keys)
-        if "critic.0.weight" in sd or "critic.2.weight" in sd:
-            names.update(_HIER_CRITIC)
-        for name, key in names.items():
-            if key not in sd:
-                raise ValueError(f"{level}_model_state has no {key!r} (needed for {level}_{name})")
-            v = sd[key]
-            out[f"{level}_{name}"] = np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, np.float32)
-    logit = out["hi_logit_w"]
-    h, S = (logit.shape[1], logit.shape[0]) if logit.ndim == 2 else (-1, -1)
-    F = out["hi_zone_w1"].shape[1] - 8 if out["hi_zone_w1"].ndim == 2 else -1
-    want = (skill_tensor_shapes if n_out == 2 else option_tensor_shapes)(h, S, F)
-    for name, a in out.items():
-        if a.shape != want[name]:
-            level, rest = name.split("_", 1)
-            key = (SKILL_HI_KEYS if level == "hi" else SKILL_LO_KEYS).get(rest) or _HIER_CRITIC[rest]
-            raise ValueError(f"{level}_model_state[{key!r}] has shape {tuple(a.shape)}, expected {want[name]} "
-                             f"(hidden size {h}, {S} skills, zone rows of {F} features)")
-    return out
-
-
-# zenv_skill_inverse_weights name -> state_dict key of InverseModel (main/src/inverse_model.py), DIAYN's discriminator
-INVERSE_KEYS = {"zone_w1": "zone_net.0.weight", "zone_b1": "zone_net.0.bias", "zone_w2": "zone_net.2.weight",
-                "zone_b2": "zone_net.2.bias", "zone_w3": "zone_net.4.weight", "zone_b3": "zone_net.4.bias",
-                "comb_w1": "combine_net.0.weight", "comb_b1": "combine_net.0.bias",
-                "comb_w2": "combine_net.2.weight", "comb_b2": "combine_net.2.bias"}
-
-
-def check_collect_option_args(frames_per_proc, policy_seed=1, env_index0=0, discount=0.99, gae_lambda=0.95):
-    """What ``ZoneVecEnv.collect_options`` checks before it calls into the library: the rules of ``collect_hier`` -- T >= 2
-    frames (the low level hands out T - 1), a discount and a lambda in [0, 1], non-negative 64-bit seeds.  Returns the
-    normalised arguments."""
-    return check_collect_hier_args(frames_per_proc, policy_seed, env_index0, discount, gae_lambda)
-
-
-def option_experience_layout(num_envs, num_zones, zone_feat, frames_per_proc, n_hi):
-    """The buffers one ``collect_options`` of T frames fills, as (lo, hi): name -> (field id, shape in memory, dtype).
-    lo: time-major [T, N, ...] device buffers, handed out as [N, T-1, ...] views (lo_exps of options/src/torch_ac/algos/
-    _hier_policy_opt.py:133-147: obs, zone_obs, skill, action, log_prob, value, advantage, returnn; plus reward =
-    env_reward, mask and ended, the termination draw).  The reference's _action and lo_log_probs have three components:
-    the first two are action / log_prob [T, N, 2], the third is term_action / term_log_prob [T, N], buffers of their
-    own.  hi: flat env-major [M, ...] (hi_exps, :152-169, action = the skill; plus each transition's reward and
-    hi_mask), M = n_hi."""
-    N, Z, F, T, M = int(num_envs), int(num_zones), int(zone_feat), int(frames_per_proc), int(n_hi)
-    f32 = np.float32
-    lo = {"obs": (nat.F_EXP_OBS, (T, N, 8), f32), "zone_obs": (nat.F_EXP_ZONE_OBS, (T, N, Z, F), f32),
-          "skill": (nat.F_LO_SKILL, (T, N), np.int32), "action": (nat.F_EXP_ACTION, (T, N, 2), f32),
-          "term_action": (nat.F_LO_TERM_ACTION, (T, N), f32), "log_prob": (nat.F_EXP_LOG_PROB, (T, N, 2), f32),
-          "term_log_prob": (nat.F_LO_TERM_LOG_PROB, (T, N), f32), "ended": (nat.F_LO_OPTION_ENDED, (T, N), np.uint8),
-          "value": (nat.F_EXP_VALUE, (T, N), f32), "advantage": (nat.F_EXP_ADVANTAGE, (T, N), f32),
-          "returnn": (nat.F_EXP_RETURN, (T, N), f32), "reward": (nat.F_EXP_REWARD, (T, N), f32),
-          "env_reward": (nat.F_LO_ENV_REWARD, (T, N), f32), "mask": (nat.F_EXP_MASK, (T, N), f32)}
-    hi = {"obs": (nat.F_HI_OBS, (M, 8), f32), "zone_obs": (nat.F_HI_ZONE_OBS, (M, Z, F), f32),
-          "action": (nat.F_HI_ACTION, (M,), np.int32), "value": (nat.F_HI_VALUE, (M,), f32),
-          "log_prob": (nat.F_HI_LOG_PROB, (M,), f32), "advantage": (nat.F_HI_ADVANTAGE, (M,), f32),
-          "returnn": (nat.F_HI_RETURN, (M,), f32), "reward": (nat.F_HI_REWARD, (M,), f32),
-          "mask": (nat.F_HI_MASK, (M,), f32)}
-    return lo, hi
-
-
-def inverse_tensor_shapes(h, S, F):
-    """The shape of every zenv_skill_inverse_weights tensor for hidden size h, S skills and zone rows of F features."""
-    return {"zone_w1": (h, 8 + F), "zone_b1": (h,), "zone_w2": (h, h), "zone_b2": (h,), "zone_w3": (h, h),
-            "zone_b3": (h,), "comb_w1": (h, 8 + h), "comb_b1": (h,), "comb_w2": (S, h), "comb_b2": (S,)}
-
-
-def inverse_tensors_from_state_dict(state, n_skills):
-    """InverseModel.state_dict() (main/src/inverse_model.py) -> the tensors ``ZoneVecEnv.load_skill_inverse`` wants
-    (numpy float32, names of ``_native.SKILL_INVERSE_TENSORS``).  A dict with other keys (an ACModel, a policy's
-    hi_model_state ...), a missing key, a tensor whose shape does not fit the others or a head of other than n_skills
-    outputs raises ValueError naming it."""
-    extra = sorted(k for k in state if k not in INVERSE_KEYS.values())
-    if extra:
-        raise ValueError(f"not an InverseModel state_dict: unexpected key {extra[0]!r}")
-    out = {}
-    for name, key in INVERSE_KEYS.items():
-        if key not in state:
-            raise ValueError(f"not an InverseModel state_dict: no {key!r}")
-        v = state[key]
-        out[name] = np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, np.float32)
-    w1 = out["zone_w1"]
-    h, F = (w1.shape[0], w1.shape[1] - 8) if w1.ndim == 2 else (-1, -1)
-    want = inverse_tensor_shapes(h, int(n_skills), F)
-    for name, a in out.items():
-        if a.shape != want[name]:
-            raise ValueError(f"InverseModel[{INVERSE_KEYS[name]!r}] has shape {tuple(a.shape)}, expected {want[name]} "
-                             f"(hidden size {h}, {int(n_skills)} skills, zone rows of {F} features)")
-    return out
-
-
-def check_collect_skill_args(frames_per_proc, skill_len, policy_seed=1, env_index0=0, discount=0.99, gae_lambda=0.95,
-                             diversity_coef=0.0, skill_prior_logits=None, n_skills=None, have_inverse=False):
-    """What ``ZoneVecEnv.collect_skills`` checks before it calls into the library: T a positive multiple of skill_len
-    (hrl_policy_planner.py:95), a discount and a lambda in [0, 1], a finite diversity_coef, non-negative 64-bit seeds;
-    with an inverse model a finite prior of n_skills logits, without one diversity_coef = 0.  Returns the normalised
-    arguments (the prior as a contiguous float32 array, or None)."""
-    if isinstance(frames_per_proc, bool) or int(frames_per_proc) != frames_per_proc:
-        raise ValueError(f"frames_per_proc must be an integer, got {frames_per_proc!r}")
-    T, L = int(frames_per_proc), int(skill_len)
-    if T < 1 or L < 1 or T % L:
-        raise ValueError(f"frames_per_proc must be a positive multiple of skill_len {L}, got {T}")
-    for name, v in (("discount", discount), ("gae_lambda", gae_lambda)):
-        if not (0.0 <= float(v) <= 1.0):
-            raise ValueError(f"{name} must lie in [0, 1], got {v!r}")
-    if not np.isfinite(float(diversity_coef)):
-        raise ValueError(f"diversity_coef must be finite, got {diversity_coef!r}")
-    for name, v in (("policy_seed", policy_seed), ("env_index0", env_index0)):
-        if int(v) != v or not (0 <= int(v) < 2 ** 64):
-            raise ValueError(f"{name} must be an integer in [0, 2^64), got {v!r}")
-    prior = None
-    if have_inverse:
-        if skill_prior_logits is None:
-            raise ValueError("skill_prior_logits is needed with an inverse model (the diversity reward's prior)")
-        v = skill_prior_logits
-        prior = np.ascontiguousarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, np.float32).reshape(-1)
-        if n_skills is not None and prior.shape != (int(n_skills),):
-            raise ValueError(f"skill_prior_logits must hold {int(n_skills)} logits, got shape {prior.shape}")
-        if not np.all(np.isfinite(prior)):
-            raise ValueError("skill_prior_logits must be finite")
-    elif float(diversity_coef) != 0.0:
-        raise ValueError("diversity_coef != 0 needs an inverse model (load_skill_inverse)")
-    return T, int(policy_seed), int(env_index0), float(discount), float(gae_lambda), float(diversity_coef), prior
-
-
-def skill_experience_layout(num_envs, num_zones, zone_feat, frames_per_proc, skill_len):
-    """The buffers one ``collect_skills`` of T frames fills, as (lo, hi): name -> (field id, shape in memory, dtype).
-    lo: time-major [T, N, ...] device buffers, handed out as [N, T, ...] views (lo_exps of _hier_policy_opt.py:172-190:
-    obs, zone_obs, skill, action, log_prob, value, advantage, returnn; plus reward = lo_reward, env_reward, diversity
-    and mask).  hi: env-major [M, ...], M = N T / skill_len (hi_exps, :201-212, action = the skill; plus the window's
-    reward and next_mask)."""
-    N, Z, F, T, L = int(num_envs), int(num_zones), int(zone_feat), int(frames_per_proc), int(skill_len)
-    M = N * (T // L)
-    f32 = np.float32
-    lo = {"obs": (nat.F_EXP_OBS, (T, N, 8), f32), "zone_obs": (nat.F_EXP_ZONE_OBS, (T, N, Z, F), f32),
-          "skill": (nat.F_LO_SKILL, (T, N), np.int32), "action": (nat.F_EXP_ACTION, (T, N, 2), f32),
-          "log_prob": (nat.F_EXP_LOG_PROB, (T, N, 2), f32), "value": (nat.F_EXP_VALUE, (T, N), f32),
-          "advantage": (nat.F_EXP_ADVANTAGE, (T, N), f32), "returnn": (nat.F_EXP_RETURN, (T, N), f32),
-          "reward": (nat.F_EXP_REWARD, (T, N), f32), "env_reward": (nat.F_LO_ENV_REWARD, (T, N), f32),
-          "diversity": (nat.F_LO_DIVERSITY, (T, N), f32), "mask": (nat.F_EXP_MASK, (T, N), f32)}
-    hi = {"obs": (nat.F_HI_OBS, (M, 8), f32), "zone_obs": (nat.F_HI_ZONE_OBS, (M, Z, F), f32),
-          "action": (nat.F_HI_ACTION, (M,), np.int32), "value": (nat.F_HI_VALUE, (M,), f32),
-          "log_prob": (nat.F_HI_LOG_PROB, (M,), f32), "advantage": (nat.F_HI_ADVANTAGE, (M,), f32),
-          "returnn": (nat.F_HI_RETURN, (M,), f32), "reward": (nat.F_HI_REWARD, (M,), f32),
-          "mask": (nat.F_HI_MASK, (M,), f32)}
-    return lo, hi
-
-
-def skill_num_frames(mask, skill_len):
-    """logs['num_frames'] of _hier_policy_opt.py:104-124 from the recorded masks [T, N] (numpy or torch): every env's
-    frames of a window up to and including its first done -- frame kL + i counts when mask[kL + 1 .. kL + i] are all
-    1 (mask[t] = 1 - done of frame t - 1)."""
-    T, N = mask.shape
-    L = int(skill_len)
-    if L == 1:
-        return T * N
-    m = mask.reshape(T // L, L, N)[:, 1:, :] != 0
-    if not isinstance(m, np.ndarray):                           # torch
-        return int(T // L * N + m.int().cumprod(dim=1).sum().item())
-    return int(T // L * N + np.cumprod(m, axis=1).sum())
 
 
 def zone_feat(cfg):
@@ -675,6 +357,24 @@ class ZoneVecEnv:
         return (arrays[0].copy(), arrays[1].astype(bool), arrays[2].copy(), arrays[3].copy())
 
     # ------------------------------------------------------------------ actor network
+    @staticmethod
+    def _load_weights(struct, names, tensors, want):
+        """Point struct.<name> at tensors[name], made contiguous float32 and checked against the shape want[name], for
+        every name.  Returns the arrays: the caller holds them until its zenv_*_load call has copied them."""
+        keep = {}
+        for name in names:
+            a = np.ascontiguousarray(tensors[name], np.float32)
+            if a.shape != want[name]:
+                raise ValueError(f"{name}: shape {a.shape}, expected {want[name]}")
+            keep[name] = a
+            setattr(struct, name, a.ctypes.data)
+        return keep
+
+    @staticmethod
+    def _two_level_names(tensors, names, hi_critic, lo_critic):
+        """The tensors a hierarchical agent's load hands over: both networks, and each critic that is there."""
+        return names + (hi_critic if "hi_critic_w1" in tensors else ()) + (lo_critic if "lo_critic_w1" in tensors else ())
+
     def load_mlp(self, tensors, precision="auto"):
         """The reference's ZoneEnvModel + actor (env_model.py:48-79, policy_network.py:12-53) for the
         device policies POLICY_MLP_MEAN / POLICY_MLP_SAMPLE.  tensors: dict of float32 arrays named as in
@@ -702,26 +402,14 @@ class ZoneVecEnv:
                     raise
                 self.load_mlp(tensors, precision="f32")
             return
-        F = self.zone_feat
         h = int(np.asarray(tensors["zone_b1"]).shape[0])
-        want = {"zone_w1": (h, 8 + F), "zone_b1": (h,), "zone_w2": (h, h), "zone_b2": (h,), "zone_w3": (h, h),
-                "zone_b3": (h,), "comb_w": (h, 8 + h), "comb_b": (h,), "enc_w": (h, h), "enc_b": (h,),
-                "mu_w": (2, h), "mu_b": (2,), "std_w": (2, h), "std_b": (2,),
-                "critic_w1": (h, h), "critic_b1": (h,), "critic_w2": (1, h), "critic_b2": (1,),
-                "critic_sigma_w": (1, h), "critic_sigma_b": (1,)}
-        keep = {}
         w = nat.MlpWeights(h_dim=h, precision={"bf16": nat.MLP_BF16, "f32": nat.MLP_F32, "bf16x3": nat.MLP_BF16X3,
                                                    "f16x3": nat.MLP_F16X3, "f16": nat.MLP_F16}[precision])
         names = nat.MLP_TENSORS + (nat.MLP_CRITIC_TENSORS if "critic_w1" in tensors else ()) + (
             nat.MLP_SIGMA_TENSORS if "critic_sigma_w" in tensors else ())
         self._mlp_has_critic = "critic_w1" in tensors
         self._mlp_distributional = "critic_sigma_w" in tensors
-        for name in names:
-            a = np.ascontiguousarray(tensors[name], np.float32)
-            if a.shape != want[name]:
-                raise ValueError(f"{name}: shape {a.shape}, expected {want[name]}")
-            keep[name] = a
-            setattr(w, name, a.ctypes.data)
+        keep = self._load_weights(w, names, tensors, mlp_tensor_shapes(h, self.zone_feat))   # alive across the load
         check(lib().zenv_mlp_load(self._h, C.byref(w)))
         self.mlp_precision = precision
 
@@ -748,18 +436,10 @@ class ZoneVecEnv:
             raise ValueError(f"precision {precision!r}: the hierarchical agent is built in float32 only")
         h = int(np.asarray(tensors["hi_zone_b1"]).shape[0])
         F = int(np.asarray(tensors["hi_zone_w1"]).shape[1]) - 8
-        want = hier_tensor_shapes(h, F)
-        names = nat.HIER_HI_TENSORS + nat.HIER_LO_TENSORS + (
-            nat.HIER_HI_CRITIC if "hi_critic_w1" in tensors else ()) + (
-            nat.HIER_LO_CRITIC if "lo_critic_w1" in tensors else ())
+        names = self._two_level_names(tensors, nat.HIER_HI_TENSORS + nat.HIER_LO_TENSORS, nat.HIER_HI_CRITIC,
+                                      nat.HIER_LO_CRITIC)
         w = nat.HierWeights(h_dim=h, precision=nat.MLP_F32, zone_feat=F)
-        keep = {}
-        for name in names:
-            a = np.ascontiguousarray(tensors[name], np.float32)
-            if a.shape != want[name]:
-                raise ValueError(f"{name}: shape {a.shape}, expected {want[name]}")
-            keep[name] = a
-            setattr(w, name, a.ctypes.data)
+        keep = self._load_weights(w, names, tensors, hier_tensor_shapes(h, F))   # alive across the load
         check(lib().zenv_hier_load(self._h, C.byref(w)))
         self._hier_critics = ("hi_critic_w1" in tensors, "lo_critic_w1" in tensors)
 
@@ -784,18 +464,10 @@ class ZoneVecEnv:
         logit = np.asarray(tensors["hi_logit_w"])
         S, h = int(logit.shape[0]), int(logit.shape[1])
         F = int(np.asarray(tensors["hi_zone_w1"]).shape[1]) - 8
-        want = skill_tensor_shapes(h, S, F)
-        names = nat.SKILL_HI_TENSORS + nat.SKILL_LO_TENSORS + (
-            nat.SKILL_HI_CRITIC if "hi_critic_w1" in tensors else ()) + (
-            nat.SKILL_LO_CRITIC if "lo_critic_w1" in tensors else ())
+        names = self._two_level_names(tensors, nat.SKILL_HI_TENSORS + nat.SKILL_LO_TENSORS, nat.SKILL_HI_CRITIC,
+                                      nat.SKILL_LO_CRITIC)
         w = nat.SkillWeights(h_dim=h, n_skills=S, zone_feat=F, precision=nat.MLP_F32)
-        keep = {}
-        for name in names:
-            a = np.ascontiguousarray(tensors[name], np.float32)
-            if a.shape != want[name]:
-                raise ValueError(f"{name}: shape {a.shape}, expected {want[name]}")
-            keep[name] = a
-            setattr(w, name, a.ctypes.data)
+        keep = self._load_weights(w, names, tensors, skill_tensor_shapes(h, S, F))   # alive across the load
         check(lib().zenv_skill_configure(self._h, int(skill_len)))
         check(lib().zenv_skill_load(self._h, C.byref(w)))
         if S != getattr(self, "_skill_n", S) or h != getattr(self, "_skill_h", h):
@@ -835,18 +507,10 @@ class ZoneVecEnv:
         logit = np.asarray(tensors["hi_logit_w"])
         S, h = int(logit.shape[0]), int(logit.shape[1])
         F = int(np.asarray(tensors["hi_zone_w1"]).shape[1]) - 8
-        want = option_tensor_shapes(h, S, F)
-        names = nat.SKILL_HI_TENSORS + nat.SKILL_LO_TENSORS + (
-            nat.SKILL_HI_CRITIC if "hi_critic_w1" in tensors else ()) + (
-            nat.SKILL_LO_CRITIC if "lo_critic_w1" in tensors else ())
+        names = self._two_level_names(tensors, nat.SKILL_HI_TENSORS + nat.SKILL_LO_TENSORS, nat.SKILL_HI_CRITIC,
+                                      nat.SKILL_LO_CRITIC)
         w = nat.OptionWeights(h_dim=h, n_skills=S, zone_feat=F, precision=nat.MLP_F32)
-        keep = {}
-        for name in names:
-            a = np.ascontiguousarray(tensors[name], np.float32)
-            if a.shape != want[name]:
-                raise ValueError(f"{name}: shape {a.shape}, expected {want[name]}")
-            keep[name] = a
-            setattr(w, name, a.ctypes.data)
+        keep = self._load_weights(w, names, tensors, option_tensor_shapes(h, S, F))   # alive across the load
         check(lib().zenv_option_load(self._h, C.byref(w)))
         self._skill_inverse = False
         self._skill_n, self._skill_h = S, h
@@ -875,23 +539,13 @@ class ZoneVecEnv:
         handle must not be stepped by other means in between."""
         T, M = self.collect_options_on_device(frames_per_proc, policy_seed, env_index0, discount, gae_lambda)
         lo_l, hi_l = option_experience_layout(self.num_envs, self.num_zones, self.zone_feat, T, M)
-        raw, hi = {}, {}
-        for name, (field, shape, dt) in lo_l.items():
-            a = np.empty(shape, dt)
-            assert a.nbytes == lib().zenv_field_bytes(self._h, field)
-            check(lib().zenv_get(self._h, field, a.ctypes.data, 0))
-            raw[name] = a
+        raw = self._download(lo_l)
         rate = float(raw["ended"].mean())
         raw["action"] = np.concatenate([raw["action"], raw.pop("term_action")[..., None]], axis=-1)
         raw["log_prob"] = np.concatenate([raw["log_prob"], raw.pop("term_log_prob")[..., None]], axis=-1)
         raw["ended"] = raw["ended"].view(bool)
         lo = {name: a[:T - 1].swapaxes(0, 1) for name, a in raw.items()}
-        for name, (field, shape, dt) in hi_l.items():
-            a = np.empty(shape, dt)
-            if M:
-                assert a.nbytes == lib().zenv_field_bytes(self._h, field)
-                check(lib().zenv_get(self._h, field, a.ctypes.data, 0))
-            hi[name] = a
+        hi = self._download(hi_l, skip=not M)
         hi["count"] = self.get(nat.F_HI_COUNT)
         return lo, hi, rate
 
@@ -913,15 +567,9 @@ class ZoneVecEnv:
         w2 = np.asarray(tensors["comb_w2"])
         S, h = int(w2.shape[0]), int(w2.shape[1])
         F = int(np.asarray(tensors["zone_w1"]).shape[1]) - 8
-        want = inverse_tensor_shapes(h, S, F)
         w = nat.SkillInverseWeights(h_dim=h, n_skills=S, zone_feat=F, precision=nat.MLP_F32)
-        keep = {}
-        for name in nat.SKILL_INVERSE_TENSORS:
-            a = np.ascontiguousarray(tensors[name], np.float32)
-            if a.shape != want[name]:
-                raise ValueError(f"{name}: shape {a.shape}, expected {want[name]}")
-            keep[name] = a
-            setattr(w, name, a.ctypes.data)
+        keep = self._load_weights(w, nat.SKILL_INVERSE_TENSORS, tensors,   # alive across the load
+                                  inverse_tensor_shapes(h, S, F))
         check(lib().zenv_skill_inverse_load(self._h, C.byref(w)))
         self._skill_inverse = True
 
@@ -941,17 +589,8 @@ class ZoneVecEnv:
                                              diversity_coef, skill_prior_logits, sample_hi)
         L = T * self.num_envs // M
         lo_l, hi_l = skill_experience_layout(self.num_envs, self.num_zones, self.zone_feat, T, L)
-        lo, hi = {}, {}
-        for name, (field, shape, dt) in lo_l.items():
-            a = np.empty(shape, dt)
-            assert a.nbytes == lib().zenv_field_bytes(self._h, field)
-            check(lib().zenv_get(self._h, field, a.ctypes.data, 0))
-            lo[name] = a.swapaxes(0, 1)
-        for name, (field, shape, dt) in hi_l.items():
-            a = np.empty(shape, dt)
-            assert a.nbytes == lib().zenv_field_bytes(self._h, field)
-            check(lib().zenv_get(self._h, field, a.ctypes.data, 0))
-            hi[name] = a
+        lo = {name: a.swapaxes(0, 1) for name, a in self._download(lo_l).items()}
+        hi = self._download(hi_l)
         keep = lo["mask"][:, 1:] != 0                                   # [N, T-1], env-major
         inverse = {"obs": lo["obs"][:, 1:][keep], "zone_obs": lo["zone_obs"][:, 1:][keep],
                    "skill": lo["skill"][:, :-1][keep]}
@@ -977,13 +616,7 @@ class ZoneVecEnv:
         views of time-major buffers: reshape copies them once)."""
         T = int(frames_per_proc)
         self.collect_on_device(T, policy_seed, env_index0, discount, gae_lambda)
-        out = {}
-        for name, (field, shape, time_major) in self.experience_layout(T).items():
-            a = np.empty(shape, np.float32)
-            assert a.nbytes == lib().zenv_field_bytes(self._h, field)
-            check(lib().zenv_get(self._h, field, a.ctypes.data, 0))
-            out[name] = a.swapaxes(0, 1) if time_major else a
-        return out
+        return {name: a.swapaxes(0, 1) for name, a in self._download(self._experience_rows(T)).items()}
 
     def collect_on_device(self, frames_per_proc, policy_seed=1, env_index0=0, discount=0.99, gae_lambda=0.95):
         """The same rollout, results left in the handle's device buffers (``experience_layout`` names them)."""
@@ -994,12 +627,11 @@ class ZoneVecEnv:
         """name -> (field id, shape in memory, time_major) of the float32 buffers one collect of T frames per env
         fills.  Everything is time-major [T, N, ...] in memory (the step kernel writes the observations in place, the
         head kernel and the GAE scan touch whole lines); ``collect`` hands out the [N, T, ...] views."""
-        N, Z, F, T = self.num_envs, self.num_zones, self.zone_feat, int(frames_per_proc)
-        return {"obs": (nat.F_EXP_OBS, (T, N, 8), True), "zone_obs": (nat.F_EXP_ZONE_OBS, (T, N, Z, F), True),
-                "action": (nat.F_EXP_ACTION, (T, N, 2), True), "log_prob": (nat.F_EXP_LOG_PROB, (T, N, 2), True),
-                "value": (nat.F_EXP_VALUE, (T, N), True), "reward": (nat.F_EXP_REWARD, (T, N), True),
-                "mask": (nat.F_EXP_MASK, (T, N), True), "advantage": (nat.F_EXP_ADVANTAGE, (T, N), True),
-                "returnn": (nat.F_EXP_RETURN, (T, N), True)}
+        return {name: (field, shape, True) for name, (field, shape, _) in self._experience_rows(frames_per_proc).items()}
+
+    def _experience_rows(self, frames_per_proc):
+        """The same buffers as name -> (field id, shape in memory, dtype), the form of the agents' layouts."""
+        return _lo_rows(self.num_envs, self.num_zones, self.zone_feat, int(frames_per_proc))
 
     # ------------------------------------------------------------------ Zone-goals training experience
     def collect_hier(self, frames_per_proc, policy_seed=1, env_index0=0, discount=0.99, gae_lambda=0.95):
@@ -1014,18 +646,9 @@ class ZoneVecEnv:
         The transition an env has open at the end stays on the device and is the first of its next call."""
         T, M = self.collect_hier_on_device(frames_per_proc, policy_seed, env_index0, discount, gae_lambda)
         lo_l, hi_l = hier_experience_layout(self.num_envs, self.num_zones, self.zone_feat, T, M)
-        lo, hi = {}, {}
-        for name, (field, shape, dt) in lo_l.items():
-            a = np.empty(shape, dt)
-            assert a.nbytes == lib().zenv_field_bytes(self._h, field)
-            check(lib().zenv_get(self._h, field, a.ctypes.data, 0))
-            lo[name] = a[:T - 1].swapaxes(0, 1)
-        for name, (field, shape, dt) in hi_l.items():
-            a = np.empty(shape, dt)
-            if M:
-                assert a.nbytes == lib().zenv_field_bytes(self._h, field)
-                check(lib().zenv_get(self._h, field, a.ctypes.data, 0))
-            hi[name] = a.view(bool) if name == "action_mask" else a
+        lo = {name: a[:T - 1].swapaxes(0, 1) for name, a in self._download(lo_l).items()}
+        hi = self._download(hi_l, skip=not M)
+        hi["action_mask"] = hi["action_mask"].view(bool)
         hi["count"] = self.get(nat.F_HI_COUNT)
         return lo, hi
 
@@ -1118,6 +741,17 @@ class ZoneVecEnv:
             out = np.empty(self._shape(field), _FIELD_DTYPES[field])
         assert out.nbytes == lib().zenv_field_bytes(self._h, field)
         check(lib().zenv_get(self._h, field, out.ctypes.data, 0))
+        return out
+
+    def _download(self, layout, skip=False):
+        """Every buffer of a layout (name -> (field id, shape, dtype)) as a new host array.  skip: the buffers hold
+        nothing (no high-level row yet) -- the empty arrays, the library untouched."""
+        out = {}
+        for name, (field, shape, dtype) in layout.items():
+            out[name] = a = np.empty(shape, dtype)
+            if not skip:
+                assert a.nbytes == lib().zenv_field_bytes(self._h, field)
+                check(lib().zenv_get(self._h, field, a.ctypes.data, 0))
         return out
 
     def get_head(self, field, count, first_env=0):
