@@ -19,6 +19,7 @@ POLICY_UNIFORM, POLICY_GREEDY, POLICY_MLP_MEAN, POLICY_MLP_SAMPLE = 0, 1, 2, 3
 POLICY_HIER_SAMPLE, POLICY_HIER_MEAN = 4, 5     # the Zone-goals hierarchical agent (zenv_hier_load)
 POLICY_SKILL_SAMPLE, POLICY_SKILL_MEAN = 6, 7   # the fixed-length-skills agent (zenv_skill_load)
 POLICY_OPTION_SAMPLE, POLICY_OPTION_MEAN = 8, 9  # the variable-length Options agent (zenv_option_load)
+POLICY_XY_SAMPLE, POLICY_XY_MEAN = 12, 13       # the xy-goals agent (zenv_xy_load); 10 and 11 stay unknown policies
 MAX_SKILLS = 32
 KERNEL_LANE_PER_ENV, KERNEL_WAVE_PER_ENV = 0, 1
 HIP_STREAM_LEGACY = 1       # hipStreamLegacy: the null stream as an explicit handle (hip_runtime_api.h)
@@ -43,7 +44,8 @@ E_ARG, E_HIP, E_STATE, E_LAYOUT, E_DONE, E_RANGE = -1, -2, -3, -4, -5, -6
  F_SKILL, F_SKILL_AGE, F_SKILL_LOGITS, F_SKILL_VALUE,
  F_LO_SKILL, F_LO_DIVERSITY, F_SKILL_BOOTSTRAP,
  F_OPTION_TERM_MU, F_OPTION_TERM_STD, F_OPTION_TERM_ACTION, F_OPTION_TERM_PROB, F_OPTION_ENDED,
- F_LO_TERM_ACTION, F_LO_TERM_LOG_PROB, F_LO_OPTION_ENDED) = range(66)
+ F_LO_TERM_ACTION, F_LO_TERM_LOG_PROB, F_LO_OPTION_ENDED,
+ F_XY_GOAL, F_XY_GOAL_MU, F_XY_GOAL_STD, F_XY_VALUE, F_XY_GOAL_AGE) = range(71)
 (RESULT_OBS, RESULT_REWARD, RESULT_DONE, RESULT_GOAL_MET, RESULT_EXCEPTION, RESULT_ZONE_OBS) = range(6)
 N_RESULTS = 6
 
@@ -104,6 +106,21 @@ class SkillInverseWeights(C.Structure):
     """struct zenv_skill_inverse_weights (include/zenv.h): host float32 tensors in state_dict layout."""
     _fields_ = [("h_dim", C.c_int32), ("n_skills", C.c_int32), ("zone_feat", C.c_int32), ("precision", C.c_int32)] + [
         (n, C.c_void_p) for n in SKILL_INVERSE_TENSORS]
+
+
+# struct zenv_xy_weights (include/zenv.h): hi_model_state / lo_model_state of the xy-goals agent -- the flat
+# actor-critic's network above the Zone-goals low level
+XY_HI_TENSORS = ("hi_zone_w1", "hi_zone_b1", "hi_zone_w2", "hi_zone_b2", "hi_zone_w3", "hi_zone_b3", "hi_comb_w",
+                 "hi_comb_b", "hi_enc_w", "hi_enc_b", "hi_mu_w", "hi_mu_b", "hi_std_w", "hi_std_b")
+XY_HI_CRITIC = HIER_HI_CRITIC                                                        # optional, all or none
+XY_LO_TENSORS = HIER_LO_TENSORS
+XY_LO_CRITIC = HIER_LO_CRITIC                                                        # optional, all or none
+
+
+class XyWeights(C.Structure):
+    """struct zenv_xy_weights (include/zenv.h): host float32 tensors in state_dict layout."""
+    _fields_ = [("h_dim", C.c_int32), ("zone_feat", C.c_int32), ("precision", C.c_int32), ("pad", C.c_int32)] + [
+        (n, C.c_void_p) for n in XY_HI_TENSORS + XY_HI_CRITIC + XY_LO_TENSORS + XY_LO_CRITIC]
 
 
 class ZenvError(RuntimeError):
@@ -188,6 +205,9 @@ _PROTOTYPES = {
     "zenv_skill_inverse_load": (C.c_int, [_H, C.c_void_p]),
     "zenv_option_load": (C.c_int, [_H, C.c_void_p]),
     "zenv_option_forward": (C.c_int, [_H]),
+    "zenv_xy_load": (C.c_int, [_H, C.c_void_p]),
+    "zenv_set_xy_goals": (C.c_int, [_H, C.c_void_p, C.c_void_p]),
+    "zenv_xy_forward": (C.c_int, [_H]),
     "zenv_collect_skill": (C.c_int, [_H, C.c_int, C.c_uint64, C.c_uint64, C.c_float, C.c_float, C.c_float, C.c_void_p,
                                      C.c_int]),
     "zenv_collect_option": (C.c_int, [_H, C.c_int, C.c_uint64, C.c_uint64, C.c_float, C.c_float,

@@ -1,5 +1,5 @@
-"""What the four device agents -- the flat actor-critic, Zone-goals, fixed-length skills / DIAYN and Options -- need on
-the host before and after a call into the library: checkpoint (state_dict) -> named float32 tensors, the shape every
+"""What the five device agents -- the flat actor-critic, Zone-goals, fixed-length skills / DIAYN, Options and xy-goals
+-- need on the host before and after a call into the library: checkpoint (state_dict) -> named float32 tensors, the shape every
 tensor must have, the argument rules of the collectors and the layout of the experience buffers they fill.
 
 Pure functions of their arguments: numpy and the constants of ``_native`` only, never the shared library.
@@ -32,6 +32,10 @@ HIER_LO_KEYS = dict(_HIER_ENC, enc_w="actor.enc_.0.0.weight", enc_b="actor.enc_.
 SKILL_HI_KEYS = dict(_HIER_ENC, enc_w="actor.enc_.0.0.weight", enc_b="actor.enc_.0.0.bias",
                      logit_w="actor.discrete_.0.weight", logit_b="actor.discrete_.0.bias")
 SKILL_LO_KEYS = HIER_LO_KEYS
+# zenv_xy_weights name -> state_dict key (xy-goals/src/hier_policy_value_models.py:19-72): the high level has the flat
+# ACModel's keys with a plain critic, the low level the Zone-goals low level's
+XY_HI_KEYS = dict(HIER_LO_KEYS)
+XY_LO_KEYS = HIER_LO_KEYS
 # zenv_skill_inverse_weights name -> state_dict key of InverseModel (main/src/inverse_model.py), DIAYN's discriminator
 INVERSE_KEYS = {"zone_w1": "zone_net.0.weight", "zone_b1": "zone_net.0.bias", "zone_w2": "zone_net.2.weight",
                 "zone_b2": "zone_net.2.bias", "zone_w3": "zone_net.4.weight", "zone_b3": "zone_net.4.bias",
@@ -81,6 +85,13 @@ def skill_tensor_shapes(h, S, F):
     """The shape of every zenv_skill_weights tensor for hidden size h, S skills and zone rows of F features."""
     hi = dict(_enc_shapes(h, 8, F), enc_w=(h, h), enc_b=(h,), logit_w=(S, h), logit_b=(S,), **_critic_shapes(h, h))
     lo = dict(_enc_shapes(h, 8 + S, F), **_gaussian_actor_shapes(h, h + S), **_critic_shapes(h, h + S))
+    return _two_level_shapes(hi, lo)
+
+
+def xy_tensor_shapes(h, F):
+    """The shape of every zenv_xy_weights tensor for hidden size h and zone rows of F features."""
+    hi = dict(_enc_shapes(h, 8, F), **_gaussian_actor_shapes(h, h), **_critic_shapes(h, h))
+    lo = dict(_enc_shapes(h, 10, F), **_gaussian_actor_shapes(h, h), **_critic_shapes(h, h))
     return _two_level_shapes(hi, lo)
 
 
@@ -151,6 +162,23 @@ def hier_tensors_from_state_dicts(hi_sd, lo_sd):
     wants (numpy float32, names of ``_native.HIER_*``).  The critics are taken when present (critic.0 and critic.2
     both).  A missing key or a tensor whose shape does not fit the others raises ValueError naming it."""
     return _two_level_tensors(hi_sd, lo_sd, HIER_HI_KEYS, HIER_LO_KEYS, _hier_sizes, hier_tensor_shapes,
+                              "hidden size {}, zone rows of {} features")
+
+
+def xy_tensors_from_state_dicts(hi_sd, lo_sd):
+    """HighPolicyValueModel.state_dict() and LoPolicyValueModel.state_dict() of the xy-goals agent (xy-goals/src/
+    hier_policy_value_models.py) -> the tensors ``ZoneVecEnv.load_xy`` wants (numpy float32, names of ``_native.XY_*``).
+    h and F come from the shapes; the critics are taken when present.  A Zone-goals checkpoint (an actor.0 / actor.2
+    high level), a skill planner's or an Options agent's (actor.discrete_.0), a missing key or a tensor whose shape
+    does not fit the others raises ValueError naming it."""
+    if "actor.0.weight" in hi_sd or "actor.2.weight" in hi_sd:
+        raise ValueError("hi_model_state has 'actor.0' / 'actor.2': a Zone-goals checkpoint (load it with "
+                         "hier_tensors_from_state_dicts / load_hier), not an xy-goals agent's")
+    if "actor.discrete_.0.weight" in hi_sd:
+        raise ValueError("hi_model_state has 'actor.discrete_.0': a skill planner's or an Options agent's checkpoint "
+                         "(load it with skill_tensors_from_state_dicts / load_skills or "
+                         "option_tensors_from_state_dicts / load_options), not an xy-goals agent's")
+    return _two_level_tensors(hi_sd, lo_sd, XY_HI_KEYS, XY_LO_KEYS, _hier_sizes, xy_tensor_shapes,
                               "hidden size {}, zone rows of {} features")
 
 

@@ -1,5 +1,5 @@
 // zenv_agents.cpp -- the networks behind the C ABI of include/zenv.h: the loaders, forwards and per-step policies of the
-// flat actor and of the Zone-goals, fixed-length-skills / DIAYN and Options agents, and the four collectors
+// flat actor and of the Zone-goals, fixed-length-skills / DIAYN, Options and xy-goals agents, and the four collectors
 // (zenv_collect, zenv_collect_hier, zenv_collect_skill, zenv_collect_option).  The handle and the environment's own calls: zenv_api.cpp.
 #include <algorithm>
 #include <cmath>
@@ -312,7 +312,7 @@ static int load_skill_family(zenv_t *h, const zenv_skill_weights *w, int n_out)
     pack_skill_f32(*w, h->p.F, img, o, n_out);
     if (int rc = use_device(h)) return rc;
     const size_t N = (size_t)h->n_env, S = (size_t)w->n_skills;
-    h->skill_ready = h->option_ready = false;           // a handle holds one agent of the skill family
+    h->skill_ready = h->option_ready = h->xy_ready = false;     // a handle holds one agent on the skill state's clock
     if (int rc = replace_image(h, h->skill_mem, img.data(), img.size() * sizeof(float))) return rc;
     if (int rc = ensure_policy_outputs(h)) return rc;
     if (h->skill_logits && h->skill_n != (int)S) {
@@ -468,6 +468,110 @@ static int run_option_policy(zenv_t *h, int policy, uint32_t step_index, uint64_
     const MlpAction act{ mode, step_index, seed, env_index0, out, MlpRecord{} };
     HIP_TRY(launch_option_low(h->skill, h->p, h->sst, h->olist, h->mlp_mu, h->mlp_std, h->mlp_value, h->oterm, act,
                               h->stream));
+    return ZENV_OK;
+}
+
+// ============================================================================ xy-goals hierarchical agent
+extern "C" int zenv_xy_load(zenv_t *h, const zenv_xy_weights *w)
+{
+    if (!h || !w) return fail(ZENV_E_ARG, "null argument");
+    if (h->goal_enabled || h->order_enabled)
+        return fail(ZENV_E_STATE, "the xy-goals agent steps a plain task handle, not a goal-conditioned / solver-ordered one");
+    if (w->h_dim < 1 || w->h_dim >= kMlpHP) return fail(ZENV_E_ARG, "h_dim %d outside 1 .. %d", w->h_dim, kMlpHP - 1);
+    if (w->precision != ZENV_MLP_F32)
+        return fail(ZENV_E_ARG, "zenv_xy_weights.precision %d: only ZENV_MLP_F32 is built", w->precision);
+    if (w->zone_feat != h->p.F)
+        return fail(ZENV_E_ARG, "the weights take zone rows of %d features, this handle's have %d", w->zone_feat, h->p.F);
+    int rc = check_tensors({ w->hi_zone_w1, w->hi_zone_b1, w->hi_zone_w2, w->hi_zone_b2, w->hi_zone_w3, w->hi_zone_b3,
+                             w->hi_comb_w, w->hi_comb_b, w->hi_enc_w, w->hi_enc_b, w->hi_mu_w, w->hi_mu_b, w->hi_std_w,
+                             w->hi_std_b, w->lo_zone_w1, w->lo_zone_b1, w->lo_zone_w2, w->lo_zone_b2, w->lo_zone_w3,
+                             w->lo_zone_b3, w->lo_comb_w, w->lo_comb_b, w->lo_enc_w, w->lo_enc_b, w->lo_mu_w, w->lo_mu_b,
+                             w->lo_std_w, w->lo_std_b },
+                           { w->hi_critic_w1, w->hi_critic_b1, w->hi_critic_w2, w->hi_critic_b2 },
+                           { w->lo_critic_w1, w->lo_critic_b1, w->lo_critic_w2, w->lo_critic_b2 });
+    if (rc) return rc;
+    std::vector<float> img;
+    size_t o[kXyPtrs];
+    pack_xy_f32(*w, h->p.F, img, o);
+    if (int rc = use_device(h)) return rc;
+    const size_t N = (size_t)h->n_env;
+    // the skill state's clock has one owner: the skill planner, the Options agent or this one
+    h->skill_ready = h->option_ready = h->skinv_ready = h->xy_ready = false;
+    if (int rc = replace_image(h, h->xy_mem, img.data(), img.size() * sizeof(float))) return rc;
+    if (int rc = ensure_policy_outputs(h)) return rc;
+    if (!h->sst_mem) {
+        HIP_TRY(hipMalloc(&h->sst_mem, 5 * N * sizeof(int32_t)));
+        int32_t *m = static_cast<int32_t *>(h->sst_mem);
+        h->sst = SkillState{ m, m + N, m + 2 * N, m + 3 * N, m + 4 * N };
+    }
+    Carver cv;
+    if (!h->xy_state_mem) {
+        cv.piece(h->xy_goal, N);
+        cv.piece(h->xy_goal_in, N);
+        cv.piece(h->xy_goal_mu, N * 2);
+        cv.piece(h->xy_goal_std, N * 2);
+        cv.piece(h->xy_value, N);
+        cv.piece(h->xy_age, N);
+        cv.piece(h->xy_mask, N);
+        if (int rc = cv.alloc(&h->xy_state_mem, "xy-goals state")) return rc;
+        HIP_TRY(hipMemsetAsync(h->xy_state_mem, 0, cv.bytes(), h->stream));
+    } else {
+        HIP_TRY(hipMemsetAsync(h->xy_goal, 0, N * sizeof(float2), h->stream));
+        HIP_TRY(hipMemsetAsync(h->xy_goal_mu, 0, N * 2 * sizeof(float), h->stream));
+        HIP_TRY(hipMemsetAsync(h->xy_goal_std, 0, N * 2 * sizeof(float), h->stream));
+        HIP_TRY(hipMemsetAsync(h->xy_value, 0, N * sizeof(float), h->stream));
+    }
+    HIP_TRY(launch_skill_sync(h->p, h->sst, nullptr, 1, h->stream));     // every env: no goal
+    // ... and with the skills go the high-level transitions zenv_collect_option left open
+    if (h->hcarry_mem) HIP_TRY(launch_hier_reset(h->hcarry, nullptr, h->n_env, h->stream));
+    h->xy = xy_f32_at(*w, static_cast<const float *>(h->xy_mem), o);
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->xy_ready = true;
+    return ZENV_OK;
+}
+
+extern "C" int zenv_set_xy_goals(zenv_t *h, const float *goals, const uint8_t *mask)
+{
+    if (!h || !goals) return fail(ZENV_E_ARG, "null argument");
+    if (!h->xy_ready) return fail(ZENV_E_STATE, "zenv_xy_load first");
+    for (int i = 0; i < h->n_env; ++i)
+        if ((!mask || mask[i]) && !(std::isfinite(goals[2 * i]) && std::isfinite(goals[2 * i + 1])))
+            return fail(ZENV_E_ARG, "env %d: goal (%g, %g) is not finite", i, (double)goals[2 * i], (double)goals[2 * i + 1]);
+    if (int rc = use_device(h)) return rc;
+    const size_t N = (size_t)h->n_env;
+    HIP_TRY(launch_skill_sync(h->p, h->sst, nullptr, 0, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->xy_goal_in, goals, N * sizeof(float2), hipMemcpyHostToDevice, h->stream));
+    if (mask) HIP_TRY(hipMemcpyAsync(h->xy_mask, mask, N, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(launch_xy_set(h->p, h->sst, h->xy_goal, h->xy_goal_in, mask ? h->xy_mask : nullptr, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));      // `goals` and `mask` are the caller's (pageable) memory
+    return ZENV_OK;
+}
+
+extern "C" int zenv_xy_forward(zenv_t *h)
+{
+    if (!h) return fail(ZENV_E_ARG, "null handle");
+    if (!h->xy_ready) return fail(ZENV_E_STATE, "zenv_xy_load first");
+    if (!h->was_reset) return fail(ZENV_E_STATE, "reset before asking for actions");
+    if (int rc = use_device(h)) return rc;
+    HIP_TRY(launch_skill_sync(h->p, h->sst, nullptr, 0, h->stream));
+    const XyPick none{ -1, h->skill_len, 0u, 0ull, 0ull };
+    HIP_TRY(launch_xy_high(h->xy, h->p, h->sst, h->xy_goal, h->xy_goal_mu, h->xy_goal_std, h->xy_value, none, h->stream));
+    HIP_TRY(launch_xy_low(h->xy, h->p, h->sst, h->xy_goal, h->mlp_mu, h->mlp_std, h->mlp_value, no_mlp_action(),
+                          h->stream));
+    return ZENV_OK;
+}
+
+// one step of evaluate_xy_hrl.py:62-70: a goal for the envs whose goal ran out (or that have none), then the low level's
+// action of every env into `out`
+static int run_xy_policy(zenv_t *h, int policy, uint32_t step_index, uint64_t seed, uint64_t env_index0, float *out)
+{
+    if (!h->xy_ready) return fail(ZENV_E_STATE, "zenv_xy_load first");
+    const int mode = policy == ZENV_POLICY_XY_SAMPLE ? 1 : 0;
+    HIP_TRY(launch_skill_sync(h->p, h->sst, nullptr, 0, h->stream));
+    const XyPick pick{ mode, h->skill_len, step_index, seed, env_index0 };
+    HIP_TRY(launch_xy_high(h->xy, h->p, h->sst, h->xy_goal, h->xy_goal_mu, h->xy_goal_std, h->xy_value, pick, h->stream));
+    const MlpAction act{ mode, step_index, seed, env_index0, out, MlpRecord{} };
+    HIP_TRY(launch_xy_low(h->xy, h->p, h->sst, h->xy_goal, h->mlp_mu, h->mlp_std, h->mlp_value, act, h->stream));
     return ZENV_OK;
 }
 
@@ -989,7 +1093,8 @@ extern "C" int zenv_policy(zenv_t *h, int policy, uint64_t policy_seed, uint64_t
     const bool hier = policy == ZENV_POLICY_HIER_SAMPLE || policy == ZENV_POLICY_HIER_MEAN;
     const bool skill = policy == ZENV_POLICY_SKILL_SAMPLE || policy == ZENV_POLICY_SKILL_MEAN;
     const bool option = policy == ZENV_POLICY_OPTION_SAMPLE || policy == ZENV_POLICY_OPTION_MEAN;
-    if (!policy_known(policy) && !hier && !skill && !option) return fail(ZENV_E_ARG, "unknown policy %d", policy);
+    const bool xy = policy == ZENV_POLICY_XY_SAMPLE || policy == ZENV_POLICY_XY_MEAN;
+    if (!policy_known(policy) && !hier && !skill && !option && !xy) return fail(ZENV_E_ARG, "unknown policy %d", policy);
     if (int rc = use_device(h)) return rc;
     const StepPolicy pol{ policy, (uint32_t)h->step_count, policy_seed, env_index0,
                           dst_device ? dst_device : h->p.actions };
@@ -997,5 +1102,6 @@ extern "C" int zenv_policy(zenv_t *h, int policy, uint64_t policy_seed, uint64_t
     if (hier) return run_hier_policy(h, policy, pol.step_index, policy_seed, env_index0, pol.out);
     if (skill) return run_skill_policy(h, policy, pol.step_index, policy_seed, env_index0, pol.out);
     if (option) return run_option_policy(h, policy, pol.step_index, policy_seed, env_index0, pol.out);
+    if (xy) return run_xy_policy(h, policy, pol.step_index, policy_seed, env_index0, pol.out);
     return run_policy(h, pol);
 }

@@ -232,6 +232,11 @@ FieldInfo field_info(const zenv *h, int field)
     case ZENV_F_LO_TERM_ACTION: return { h->oc.term_action, h->oc_mem ? N * h->oc.T * 4 : 0 };
     case ZENV_F_LO_TERM_LOG_PROB: return { h->oc.term_log_prob, h->oc_mem ? N * h->oc.T * 4 : 0 };
     case ZENV_F_LO_OPTION_ENDED: return { h->oc.ended, h->oc_mem ? N * h->oc.T : 0 };
+    case ZENV_F_XY_GOAL: return { h->xy_goal, h->xy_state_mem ? N * 2 * 4 : 0 };     // (refresh_field() first)
+    case ZENV_F_XY_GOAL_MU: return { h->xy_goal_mu, h->xy_state_mem ? N * 2 * 4 : 0 };
+    case ZENV_F_XY_GOAL_STD: return { h->xy_goal_std, h->xy_state_mem ? N * 2 * 4 : 0 };
+    case ZENV_F_XY_VALUE: return { h->xy_value, h->xy_state_mem ? N * 4 : 0 };
+    case ZENV_F_XY_GOAL_AGE: return { h->xy_age, h->xy_state_mem ? N * 4 : 0 };      // (refresh_field() first)
     default: return { nullptr, 0 };
     }
 }
@@ -243,6 +248,12 @@ int refresh_field(zenv *h, int field)
 {
     if (field == ZENV_F_SKILL || field == ZENV_F_SKILL_AGE || field == ZENV_F_OPTION_ENDED) {
         if (h->sst_mem) HIP_TRY(launch_skill_sync(h->p, h->sst, nullptr, 0, h->stream));
+        return ZENV_OK;
+    }
+    if (field == ZENV_F_XY_GOAL || field == ZENV_F_XY_GOAL_AGE) {     // the clock is the skill state's
+        if (!h->xy_state_mem) return ZENV_OK;
+        HIP_TRY(launch_skill_sync(h->p, h->sst, nullptr, 0, h->stream));
+        HIP_TRY(launch_xy_age(h->p, h->sst, h->xy_age, h->stream));
         return ZENV_OK;
     }
     if (field != ZENV_F_EP_RETURN && field != ZENV_F_EP_LEN) return ZENV_OK;
@@ -533,7 +544,8 @@ extern "C" int zenv_destroy(zenv_t *h)
                      (void *)h->goal_in, (void *)h->goal_bad, h->exp_mem, (void *)h->p.order_pos,
                      (void *)h->p.order_val, h->hier_mem, (void *)h->hier_logits, (void *)h->hier_value,
                      h->hframes_mem, h->hcarry_mem, h->hout_mem, h->skill_mem, h->sst_mem, (void *)h->skill_logits,
-                     (void *)h->skill_value, h->skinv_mem, h->sk_mem, h->opt_mem, h->oc_mem })
+                     (void *)h->skill_value, h->skinv_mem, h->sk_mem, h->opt_mem, h->oc_mem, h->xy_mem,
+                     h->xy_state_mem })
         if (m) (void)hipFree(m);
     for (hipEvent_t ev : h->events) (void)hipEventDestroy(ev);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
@@ -1407,7 +1419,7 @@ extern "C" int zenv_device_ptr(zenv_t *h, int field, void **ptr)
     const FieldInfo f = field_info(h, field);
     if (!f.ptr) return fail(ZENV_E_ARG, "unknown field %d", field);
     if (field == ZENV_F_EP_RETURN || field == ZENV_F_EP_LEN || field == ZENV_F_SKILL || field == ZENV_F_SKILL_AGE ||
-        field == ZENV_F_OPTION_ENDED) {
+        field == ZENV_F_OPTION_ENDED || field == ZENV_F_XY_GOAL || field == ZENV_F_XY_GOAL_AGE) {
         // these two live inside the step kernels' records: the pointer is to a plain copy brought up to date by THIS
         // call (stream-ordered), not a live view
         int rc = use_device(h);

@@ -14,6 +14,7 @@
 #include "hier_f32.hpp"
 #include "option_f32.hpp"
 #include "skill_f32.hpp"
+#include "xy_f32.hpp"
 #include "mlp_policy.hpp"
 
 using namespace zenvk;
@@ -103,6 +104,17 @@ struct zenv {
     void *opt_mem = nullptr;
     OptionList olist{};
     OptionTerm oterm{};
+    // xy-goals agent (zenv_xy_load): it shares the per-env clock (sst, skill_len) with the skill family -- skill 0 = the
+    // env has a goal -- and takes their place on the handle; its own: float32 weights, one allocation (xy_state_mem) for
+    // the goal, its staging and mask (zenv_set_xy_goals), the high level's outputs and the published age
+    void *xy_mem = nullptr;
+    XyF32 xy{};
+    bool xy_ready = false;
+    void *xy_state_mem = nullptr;
+    float2 *xy_goal = nullptr, *xy_goal_in = nullptr;
+    float *xy_goal_mu = nullptr, *xy_goal_std = nullptr, *xy_value = nullptr;
+    int32_t *xy_age = nullptr;
+    uint8_t *xy_mask = nullptr;
     // zenv_collect_option: the per-frame records of one call (T frames) that have no place in hframes -- the skill the
     // low level acted under, a_2 with its log_prob and the termination draw, [T][N] each
     struct {

@@ -5,7 +5,8 @@ result layout ``{"return": [[r_run0..r_run4] for each map]}`` -- but all maps an
 stepped together as one batch of n_maps*n_runs envs instead of 500 sequential episodes.
 ``evaluate_zone_hrl`` does the same for zone-goals/scripts/evaluate_zone_hrl.py with the Zone-goals hierarchical agent,
 ``evaluate_hier`` for main/scripts/evaluate_hier.py with the fixed-length-skills agent, ``evaluate_options`` for
-options/scripts/evaluate_hier.py with the variable-length Options agent.
+options/scripts/evaluate_hier.py with the variable-length Options agent, ``evaluate_xy_hrl`` for
+xy-goals/scripts/evaluate_xy_hrl.py with the xy-goals agent.
 """
 import pickle
 
@@ -222,3 +223,28 @@ def evaluate_options(env_id, model, n_maps=100, n_runs_per_map=1, n_skills=None,
     out = _run_batched(cfg, n_maps, n_runs_per_map, env_seed0, device, max_steps, pkl_path, setup, step)
     out["terminations"] = ended.reshape(n_maps, n_runs_per_map).tolist()
     return out
+
+
+def evaluate_xy_hrl(env_id, model, n_maps=100, n_runs_per_map=5, skill_len=200, policy_seed=0, argmax=False,
+                    pkl_path=None, device=0, max_steps=None, env_seed0=EVAL_SEED0):
+    """The protocol of xy-goals/scripts/evaluate_xy_hrl.py (100 maps x 5 runs, env seeds 1000000.., undiscounted
+    return) with the xy-goals hierarchical agent on the device, every map and run stepped together as one batch.  Per
+    step (:62-70): every ``skill_len`` steps from the episode's reset HighPolicyValueModel draws a goal in the plane
+    from its Normal (or takes the mean with ``argmax=True``), then LoPolicyValueModel acts under it (``dist.sample()``,
+    or mu).
+
+    env_id: a registry id ("PointTSP-v0" ...: make_fixed_env(hier=True) is the plain task env) or a Config;
+    model: a model directory, its ``status.pt``, or a ``(hi_state_dict, lo_state_dict)`` pair.
+    Returns ``{"return": [[...]], "length": [[...]], "goal_met": [[...]]}`` as ``evaluate`` does and writes
+    ``{"return": ...}`` to ``pkl_path`` (evaluate_xy_hrl.py:44, :79-81)."""
+    from .vec_env import xy_tensors_from_state_dicts
+    cfg = config_for_id(env_id) if isinstance(env_id, str) else env_id
+    hi_sd, lo_sd = load_hier_model_state(model) if isinstance(model, str) else model
+    tensors = xy_tensors_from_state_dicts(hi_sd, lo_sd)
+
+    def setup(env):
+        env.reset()
+        env.load_xy(tensors, skill_len=skill_len)
+
+    return _run_batched(cfg, n_maps, n_runs_per_map, env_seed0, device, max_steps, pkl_path, setup,
+                        _device_step(nat.POLICY_XY_MEAN if argmax else nat.POLICY_XY_SAMPLE, policy_seed))

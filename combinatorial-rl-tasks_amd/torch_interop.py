@@ -130,6 +130,13 @@ class TorchZoneEnv:
         from .vec_env import skill_tensors_from_state_dicts
         self.env.load_skills(skill_tensors_from_state_dicts(hi_state_dict, lo_state_dict), skill_len=skill_len)
 
+    def load_xy(self, hi_state_dict, lo_state_dict, skill_len=200):
+        """Put the xy-goals agent's HighPolicyValueModel / LoPolicyValueModel state_dicts (xy-goals/src/
+        hier_policy_value_models.py; torch tensors on any device) into the device agent that POLICY_XY_SAMPLE /
+        POLICY_XY_MEAN run."""
+        from .vec_env import xy_tensors_from_state_dicts
+        self.env.load_xy(xy_tensors_from_state_dicts(hi_state_dict, lo_state_dict), skill_len=skill_len)
+
     def load_skill_inverse(self, state_dict, n_skills):
         """Put an InverseModel state_dict (main/src/inverse_model.py) into the device discriminator of the diversity
         reward -- after every update."""

@@ -14,6 +14,7 @@ import numpy as np
 from . import _native as nat
 from ._native import Config, ZenvError, check, lib
 from .agents import (_HIER_ENC, _HIER_CRITIC, HIER_HI_KEYS, HIER_LO_KEYS, SKILL_HI_KEYS, SKILL_LO_KEYS,   # noqa: F401
+                     XY_HI_KEYS, XY_LO_KEYS, xy_tensor_shapes, xy_tensors_from_state_dicts,
                      INVERSE_KEYS, _lo_rows, mlp_tensors_from_state_dict, mlp_tensor_shapes, hier_tensor_shapes,
                      skill_tensor_shapes, option_tensor_shapes, inverse_tensor_shapes, hier_tensors_from_state_dicts,
                      skill_tensors_from_state_dicts, option_tensors_from_state_dicts, inverse_tensors_from_state_dict,
@@ -38,6 +39,8 @@ _FIELD_DTYPES = {
     nat.F_SKILL_BOOTSTRAP: np.int32, nat.F_OPTION_TERM_MU: np.float32, nat.F_OPTION_TERM_STD: np.float32,
     nat.F_OPTION_TERM_ACTION: np.float32, nat.F_OPTION_TERM_PROB: np.float32, nat.F_OPTION_ENDED: np.int32,
     nat.F_LO_TERM_ACTION: np.float32, nat.F_LO_TERM_LOG_PROB: np.float32, nat.F_LO_OPTION_ENDED: np.uint8,
+    nat.F_XY_GOAL: np.float32, nat.F_XY_GOAL_MU: np.float32, nat.F_XY_GOAL_STD: np.float32, nat.F_XY_VALUE: np.float32,
+    nat.F_XY_GOAL_AGE: np.int32,
 }
 
 
@@ -558,6 +561,50 @@ class ZoneVecEnv:
         check(lib().zenv_collect_option(self._h, T, seed, index0, discount, gae_lambda, C.byref(m)))
         return T, int(m.value)
 
+    # ------------------------------------------------------------------ xy-goals hierarchical agent
+    def load_xy(self, tensors, skill_len=200, precision="f32"):
+        """HighPolicyValueModel + LoPolicyValueModel of the xy-goals agent (xy-goals/src/hier_policy_value_models.py:
+        19-72) for ``xy_forward`` and the device policies POLICY_XY_SAMPLE / POLICY_XY_MEAN, which draw a new goal in
+        the plane every ``skill_len`` steps of an episode (evaluate_xy_hrl.py:21, :62-66).  tensors: dict of float32
+        arrays named as in ``_native.XY_*`` (see ``xy_tensors_from_state_dicts``); each critic is optional.  A plain
+        task handle only.  The agent runs on the skill family's per-env clock: this drops loaded skill, option and
+        inverse weights, ``load_skills`` / ``load_options`` drop these.  Every env starts without a goal.  precision:
+        "f32" (the only one built: float32 throughout, within 1e-5 of torch)."""
+        if precision != "f32":
+            raise ValueError(f"precision {precision!r}: the xy-goals agent is built in float32 only")
+        h = int(np.asarray(tensors["hi_zone_b1"]).shape[0])
+        F = int(np.asarray(tensors["hi_zone_w1"]).shape[1]) - 8
+        names = self._two_level_names(tensors, nat.XY_HI_TENSORS + nat.XY_LO_TENSORS, nat.XY_HI_CRITIC,
+                                      nat.XY_LO_CRITIC)
+        w = nat.XyWeights(h_dim=h, zone_feat=F, precision=nat.MLP_F32)
+        keep = self._load_weights(w, names, tensors, xy_tensor_shapes(h, F))   # alive across the load
+        check(lib().zenv_skill_configure(self._h, int(skill_len)))
+        check(lib().zenv_xy_load(self._h, C.byref(w)))
+        self._skill_inverse = False
+        self._skill_len = int(skill_len)
+
+    def set_xy_goals(self, goals, mask=None):
+        """goals: float32 [N, 2]; env i with mask[i] (mask None = every env) gets goals[i] with its age restarting at
+        0.  A non-finite goal under the mask is refused (E_ARG) with nothing changed."""
+        g = np.ascontiguousarray(goals, np.float32)
+        if g.shape != (self.num_envs, 2):
+            raise ValueError(f"goals must have shape ({self.num_envs}, 2)")
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+            if m.shape != (self.num_envs,):
+                raise ValueError(f"mask must have shape ({self.num_envs},)")
+        check(lib().zenv_set_xy_goals(self._h, g.ctypes.data, None if m is None else m.ctypes.data))
+
+    def xy_forward(self):
+        """Both networks on the current observations: (goal_mu float32 [N,2], goal_std [N,2], high-level value [N], mu
+        [N,2], std [N,2], low-level value [N]); the low level under each env's current goal (``get(F_XY_GOAL)``), zeros
+        for an env without one (``get(F_XY_GOAL_AGE)`` = -1).  Values are 0 without the critic tensors.  The state does
+        not move."""
+        check(lib().zenv_xy_forward(self._h))
+        return (self.get(nat.F_XY_GOAL_MU), self.get(nat.F_XY_GOAL_STD), self.get(nat.F_XY_VALUE),
+                self.get(nat.F_POLICY_MU), self.get(nat.F_POLICY_STD), self.get(nat.F_POLICY_VALUE))
+
     def load_skill_inverse(self, tensors, precision="f32"):
         """InverseModel, DIAYN's discriminator (main/src/inverse_model.py), for the diversity reward of
         ``collect_skills``.  tensors: dict of float32 arrays named as in ``_native.SKILL_INVERSE_TENSORS`` (see
@@ -732,7 +779,8 @@ class ZoneVecEnv:
             return (N, getattr(self, "_skill_n", 0))
         if field == nat.F_ZONE_OBS:
             return (N, self.num_zones, self.zone_feat)
-        if field in (nat.F_ACTIONS, nat.F_POLICY_MU, nat.F_POLICY_STD):
+        if field in (nat.F_ACTIONS, nat.F_POLICY_MU, nat.F_POLICY_STD, nat.F_XY_GOAL, nat.F_XY_GOAL_MU,
+                     nat.F_XY_GOAL_STD):
             return (N, 2)
         return (N,)
 

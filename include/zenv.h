@@ -152,7 +152,15 @@ enum {
     ZENV_F_LO_TERM_ACTION = 63,     /* float32 [T,N] a_2, the third component of the low level's sample */
     ZENV_F_LO_TERM_LOG_PROB = 64,   /* float32 [T,N] Normal(mu_2, std_2).log_prob(a_2) */
     ZENV_F_LO_OPTION_ENDED = 65,    /* uint8   [T,N] the termination draw: 1 = the option ended after this frame */
-    ZENV_F_COUNT = 66
+    /* xy-goals hierarchical agent (zenv_xy_load; before these five fields, ZENV_F_COUNT = 66): 0 bytes before the load.
+     * zenv_reset and every auto-reset clear the goal as they clear a skill; reading the goal or its age first brings
+     * the state up to date (like ZENV_F_SKILL, a device pointer of the age is a copy as of that call) */
+    ZENV_F_XY_GOAL = 66,            /* float32 [N,2] the env's current goal, meaningful where ZENV_F_XY_GOAL_AGE >= 0 */
+    ZENV_F_XY_GOAL_MU = 67,         /* float32 [N,2] the high level's Normal: 2 (sigmoid(actor.mu_) - 0.5) */
+    ZENV_F_XY_GOAL_STD = 68,        /* float32 [N,2] sigmoid(actor.std_) + 1e-3 */
+    ZENV_F_XY_VALUE = 69,           /* float32 [N]   the high level's critic value (0 without critic tensors) */
+    ZENV_F_XY_GOAL_AGE = 70,        /* int32   [N]   low-level steps taken under the current goal, -1 = no goal */
+    ZENV_F_COUNT = 71
 };
 
 /* scripted on-device action sources (the build's own; used by bench/tests) */
@@ -172,7 +180,12 @@ enum {
     /* the variable-length Options agent (zenv_option_load; plain task handles only), see zenv_option_forward */
     ZENV_POLICY_OPTION_SAMPLE = 8, /* skill ~ Categorical(logits) when the last option ended, (a, a_2) ~ Normal(mu, std),
                                     * the option ends with probability sigmoid(4 a_2 - 3) */
-    ZENV_POLICY_OPTION_MEAN = 9    /* skill = argmax, a = mu, the option ends iff sigmoid(4 mu_2 - 3) > 0.5 */
+    ZENV_POLICY_OPTION_MEAN = 9,   /* skill = argmax, a = mu, the option ends iff sigmoid(4 mu_2 - 3) > 0.5 */
+    /* (10 and 11 are not policies: they stay unknown, ZENV_E_ARG, whatever is loaded)
+     * the xy-goals hierarchical agent (zenv_xy_load; plain task handles only), see zenv_xy_forward */
+    ZENV_POLICY_XY_SAMPLE = 12,    /* goal ~ Normal(goal_mu, goal_std) every skill_len steps, a ~ Normal(mu, std):
+                                    * HierAgent.get_hi_action / get_lo_action (xy-goals/src/utils/hier_agent.py) */
+    ZENV_POLICY_XY_MEAN = 13       /* goal = goal_mu, a = mu: deterministic */
 };
 
 /* kernel layouts */
@@ -645,6 +658,80 @@ typedef struct zenv_skill_inverse_weights {
  * n_skills or zone_feat that differs from the loaded skill weights'.  A later zenv_skill_load of another shape drops
  * these weights. */
 int zenv_skill_inverse_load(zenv_t *h, const zenv_skill_inverse_weights *w);
+
+/* ---- the xy-goals hierarchical agent on the device ----
+ * HighPolicyValueModel and LoPolicyValueModel of xy-goals/src/hier_policy_value_models.py:19-72 with the per-step loop
+ * of xy-goals/scripts/evaluate_xy_hrl.py:48-81 (xy-goals/src/utils/hier_agent.py:38-50): every skill_len steps counted
+ * from the episode's reset the high level draws a continuous goal in the plane, and every step the low level acts under
+ * the current one.  The env is the plain task env: no goal zones, no shaped reward.  Checkpoint: status.pt's
+ * hi_model_state / lo_model_state.  h = hidden size, F = zenv_zone_feat(cfg).
+ *   high:  the flat actor-critic's network.  emb = ZoneEnvModel(obs, zone_obs); x = relu(actor.enc_.0.0(emb));
+ *          goal_mu = 2 (sigmoid(actor.mu_(x)) - 0.5), goal_std = sigmoid(actor.std_(x)) + 1e-3;
+ *          value = critic.2(relu(critic.0(emb))).
+ *   low:   the Zone-goals low level (zenv_hier_weights' lo_* members) under another goal: emb = ZoneEnvGoalModel(obs,
+ *          goal, zone_obs) on [obs, goal(2), zone row]; Normal(mu, std) = PolicyNetwork(emb); value = critic.2(relu(
+ *          critic.0(emb))).  The goal is the high level's float32 sample as it stands: unclipped, not a zone centre,
+ *          not divided by 3.
+ * Host float32 tensors in the state_dict's layout (row-major [out][in]); each critic is optional (all four of it NULL =
+ * no value output, 0 is written). */
+typedef struct zenv_xy_weights {
+    int32_t h_dim;                        /* 1 .. 191 */
+    int32_t zone_feat;                    /* F the weights were built for (the handle's zenv_zone_feat) */
+    int32_t precision;                    /* ZENV_MLP_F32 only: the float32 vector-ALU kernels of xy_f32.hip */
+    int32_t pad;
+    /* hi_model_state (HighPolicyValueModel) */
+    const float *hi_zone_w1, *hi_zone_b1; /* env_model.zone_net_.0  [h, 8+F],  [h]  input = [obs, zone row] */
+    const float *hi_zone_w2, *hi_zone_b2; /* env_model.zone_net_.2  [h, h],    [h] */
+    const float *hi_zone_w3, *hi_zone_b3; /* env_model.zone_net_.4  [h, h],    [h] */
+    const float *hi_comb_w, *hi_comb_b;   /* env_model.combine_net_ [h, 8+h],  [h]  input = [obs, zone_emb] */
+    const float *hi_enc_w, *hi_enc_b;     /* actor.enc_.0.0         [h, h],    [h] */
+    const float *hi_mu_w, *hi_mu_b;       /* actor.mu_              [2, h],    [2] */
+    const float *hi_std_w, *hi_std_b;     /* actor.std_             [2, h],    [2] */
+    const float *hi_critic_w1, *hi_critic_b1; /* critic.0           [h, h],    [h]  (optional) */
+    const float *hi_critic_w2, *hi_critic_b2; /* critic.2           [1, h],    [1]  (optional) */
+    /* lo_model_state (LoPolicyValueModel) */
+    const float *lo_zone_w1, *lo_zone_b1; /* env_model.zone_net_.0  [h, 10+F], [h]  input = [obs, goal, zone row] */
+    const float *lo_zone_w2, *lo_zone_b2; /* env_model.zone_net_.2  [h, h],    [h] */
+    const float *lo_zone_w3, *lo_zone_b3; /* env_model.zone_net_.4  [h, h],    [h] */
+    const float *lo_comb_w, *lo_comb_b;   /* env_model.combine_net_ [h, 10+h], [h]  input = [obs, goal, zone_emb] */
+    const float *lo_enc_w, *lo_enc_b;     /* actor.enc_.0.0         [h, h],    [h] */
+    const float *lo_mu_w, *lo_mu_b;       /* actor.mu_              [2, h],    [2] */
+    const float *lo_std_w, *lo_std_b;     /* actor.std_             [2, h],    [2] */
+    const float *lo_critic_w1, *lo_critic_b1; /* critic.0           [h, h],    [h]  (optional) */
+    const float *lo_critic_w2, *lo_critic_b2; /* critic.2           [1, h],    [1]  (optional) */
+} zenv_xy_weights;
+/* The rules of zenv_skill_load: ZENV_E_STATE on a goal-conditioned or solver-ordered handle; ZENV_E_ARG for h_dim outside
+ * 1 .. 191, a zone_feat other than the handle's F, a precision other than ZENV_MLP_F32, a null actor tensor or a critic
+ * given in part.  Loading leaves every env without a goal (ZENV_F_XY_GOAL_AGE = -1).  The agent shares the per-env
+ * clock with the skill family, so a handle holds ONE of the three: zenv_xy_load drops loaded skill, option and inverse
+ * weights, zenv_skill_load and zenv_option_load drop these.  zenv_mlp_load's and zenv_hier_load's weights are left
+ * alone.  The period is zenv_skill_configure's skill_len (200 until set). */
+int zenv_xy_load(zenv_t *h, const zenv_xy_weights *w);
+/* goals [N][2] from the host: env i with mask[i] != 0 (mask NULL = every env) gets goals[i] with its age restarting at
+ * 0.  ZENV_E_ARG for a non-finite goal under the mask (nothing is changed then); ZENV_E_STATE before zenv_xy_load.  A
+ * goal left over from an episode that has ended since is cleared first. */
+int zenv_set_xy_goals(zenv_t *h, const float *goals, const uint8_t *mask);
+/* Both networks on the current observations, every env:
+ *   ZENV_F_XY_GOAL_MU / _GOAL_STD / ZENV_F_XY_VALUE  the high level
+ *   ZENV_F_POLICY_MU / _STD / _VALUE                 the low level under the env's current goal (ZENV_F_XY_GOAL); an env
+ *                                                    without one gets 0 in all three.
+ * The state does not move.
+ * zenv_policy(ZENV_POLICY_XY_*) runs the same two networks as one step of evaluate_xy_hrl.py:62-70, on the device, with
+ * no host synchronisation:
+ *  1. a goal left over from an episode that has ended since is cleared;
+ *  2. every env without a goal or whose age has reached skill_len, and which is not finished (left alone by
+ *     step_no_reset), gets a goal with age 0: SAMPLE goal_mu + goal_std * n, MEAN goal_mu.  The high level is
+ *     evaluated, and ZENV_F_XY_GOAL_MU / _GOAL_STD / ZENV_F_XY_VALUE refreshed, for those envs only;
+ *  3. the low level writes the action of every env with a goal: SAMPLE a ~ Normal(mu, std), MEAN mu (0 without a goal);
+ *  4. the age of every unfinished env goes up by one.
+ * With the reset clearing the state this is `i % skill_len == 0`, i counted from the episode's reset.  Randomness:
+ * Philox4x32-10, counter (env_index0 + env, zenv_step_count, tag), key policy_seed.  The action draw is the other
+ * agents' (tag 0x4D4C50, words 0-1); the goal draw is a stream of its own, tag 0x585947: n = sqrt(-2 ln u1) (cos, sin)(
+ * 2 pi u2) on words 0 and 1, formed in float32 exactly as the action's.  The policies are numbered 12 and 13: 10 and 11
+ * stay unknown policies.  zenv_rollout() refuses these policies (ZENV_E_ARG) and zenv_collect() takes none; before
+ * zenv_xy_load they answer ZENV_E_STATE, and with these weights loaded so do zenv_skill_forward, zenv_option_forward,
+ * zenv_set_skills, ZENV_POLICY_SKILL_* and ZENV_POLICY_OPTION_*. */
+int zenv_xy_forward(zenv_t *h);
 
 /* ---- one PPO rollout on the device: BaseAlgo.collect_experiences, main/src/torch_ac/algos/base.py:131-227 ----
  * T times: (dist, value) = acmodel(obs) [zenv_mlp_forward]; action = dist.sample(); record obs, action, value,
