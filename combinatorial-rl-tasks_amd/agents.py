@@ -297,6 +297,17 @@ def check_collect_skill_args(frames_per_proc, skill_len, policy_seed=1, env_inde
     return args + (float(diversity_coef), prior)
 
 
+def check_collect_xy_args(frames_per_proc, skill_len, policy_seed=0, env_index0=0, discount=0.99, gae_lambda=0.95):
+    """What ``ZoneVecEnv.collect_xy`` checks before it calls into the library: T a positive multiple of skill_len
+    (xy-goals' hrl_policy_planner.py:71-105 sizes its buffers by T // skill_len), a discount and a lambda in [0, 1],
+    non-negative 64-bit seeds.  Returns the normalised arguments."""
+    args = _check_collect_args(frames_per_proc, policy_seed, env_index0, discount, gae_lambda)
+    T, L = args[0], int(skill_len)
+    if T < 1 or L < 1 or T % L:
+        raise ValueError(f"frames_per_proc must be a positive multiple of skill_len {L}, got {T}")
+    return args
+
+
 def _lo_rows(N, Z, F, T):
     """The per-frame buffers every collector fills, time-major [T, N, ...]: name -> (field id, shape, dtype)."""
     f32 = np.float32
@@ -355,6 +366,23 @@ def option_experience_layout(num_envs, num_zones, zone_feat, frames_per_proc, n_
               term_action=(nat.F_LO_TERM_ACTION, (T, N), f32), term_log_prob=(nat.F_LO_TERM_LOG_PROB, (T, N), f32),
               ended=(nat.F_LO_OPTION_ENDED, (T, N), np.uint8), env_reward=(nat.F_LO_ENV_REWARD, (T, N), f32))
     return lo, _hi_rows(Z, F, M)
+
+
+def xy_experience_layout(num_envs, num_zones, zone_feat, frames_per_proc, skill_len):
+    """The buffers one ``collect_xy`` of T frames fills, as (lo, hi): name -> (field id, shape in memory, dtype).
+    lo: time-major [T, N, ...] device buffers, handed out as [N, T, ...] views (lo_exps of xy-goals/src/torch_ac/algos/
+    _hier_policy_opt.py:145-158: obs, zone_obs, goal, action, log_prob, value, advantage, returnn; plus reward = the
+    distance-to-goal reward, goal_dist, env_reward and mask).  hi: env-major [M, ...], M = N T / skill_len (hi_exps,
+    :162-173: obs, zone_obs, goal, value, log_prob, advantage, returnn; plus the window's reward and next_mask).  The
+    goal is continuous: there is no ``action`` among the high rows."""
+    N, Z, F, T, L = int(num_envs), int(num_zones), int(zone_feat), int(frames_per_proc), int(skill_len)
+    f32 = np.float32
+    M = N * (T // L)
+    lo = dict(_lo_rows(N, Z, F, T), goal=(nat.F_LO_GOAL, (T, N, 2), f32), goal_dist=(nat.F_LO_GOAL_DIST, (T, N), f32),
+              env_reward=(nat.F_LO_ENV_REWARD, (T, N), f32))
+    hi = {name: row for name, row in _hi_rows(Z, F, M).items() if name != "action"}
+    hi["goal"] = (nat.F_HI_GOAL, (M, 2), f32)
+    return lo, hi
 
 
 def skill_num_frames(mask, skill_len):

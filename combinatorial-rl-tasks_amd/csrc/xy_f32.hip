@@ -12,6 +12,9 @@
 //    combine_net_ (k_hier_f32<1>); the goal is the float2 buffer's as it stands -- the high level's float32 sample,
 //    unclipped.  Then PolicyNetwork's mu_ / std_, the Normal sample of mlp_head_out.hpp, and the goal's age.
 // Only the summation order differs from torch's: within 1e-5 of the reference's float32 modules.
+// Inside zenv_collect_xy (xy_collect.hip) both epilogues also record: the high level the pick's row (obs, zone_obs, goal,
+// value, log_prob summed over the goal's dimensions) and, in a bootstrap mode of its own, g'; the low level the goal it
+// acted under and its distance from the robot.  Without an XyRecord the outputs are what they are without the collector.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -27,16 +30,42 @@ namespace {
 using namespace hf32;
 
 // the goal draw's Philox stream (the action draw of mlp_head_out.hpp uses the tag 0x4D4C50, the Zone-goals goal draw
-// 0x48474C, the skill draw 0x534B4C)
+// 0x48474C, the skill draws 0x534B4C / 0x534B55 / 0x534B42, the Options agent's termination 0x4F5054); the bootstrap goal
+// g' of zenv_collect_xy has a stream of its own, so that it is not the first pick of the next call
 constexpr uint32_t kXyGoalTag = 0x585947u;
+constexpr uint32_t kXyBootTag = 0x585942u;
 
 // goal = mu + std * n, n the Box-Muller pair of words 0 and 1 of the goal stream's block: the arithmetic of mlp_action
-__device__ __forceinline__ float2 xy_goal_draw(const XyPick &pick, int env, float2 m, float2 sd)
+__device__ __forceinline__ float2 xy_goal_draw(const XyPick &pick, int env, float2 m, float2 sd, uint32_t tag)
 {
-    const PhiloxWords c = philox_words(pick.seed, pick.env_index0 + (uint64_t)env, pick.step_index, kXyGoalTag);
+    const PhiloxWords c = philox_words(pick.seed, pick.env_index0 + (uint64_t)env, pick.step_index, tag);
     const float u1 = u01(c.w[0]), u2 = u01(c.w[1]);
     const float rad = sqrtf(-2.0f * logf(u1));
     return make_float2(m.x + sd.x * rad * cosf(6.283185307179586f * u2), m.y + sd.y * rad * sinf(6.283185307179586f * u2));
+}
+
+// inside zenv_collect_xy, frame t of the low level: the goal it acted under and its distance from the robot, obs[1:3] of
+// the observation the action is taken on -- torch's float32 pow(pow(goal - xy, 2).sum(-1), 0.5) bit for bit (no FMA)
+__device__ __forceinline__ void xy_record_goal(const XyRecord &xr, int env, float2 g, float x, float y)
+{
+    const size_t slot = (size_t)xr.t * xr.N + env;
+    const float dx = __fsub_rn(g.x, x), dy = __fsub_rn(g.y, y);
+    xr.lo_goal[slot] = g;
+    // the root through float64: HIP's __fsqrt_rn is the hardware's approximate root here (1 ulp off now and then), while
+    // a float64 root of a float32, rounded back to float32, is the correctly rounded float32 root (53 >= 2 * 24 + 2 bits)
+    xr.lo_dist[slot] = (float)sqrt((double)__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)));
+}
+
+// an env without a goal: idle_outputs, and inside zenv_collect_xy goal 0 at distance 0 for frame t
+__device__ __forceinline__ void xy_idle(int env, float *__restrict__ mu, float *__restrict__ stdv,
+                                        float *__restrict__ value, const MlpAction &act, const XyRecord &xr)
+{
+    idle_outputs(env, mu, stdv, value, act);
+    if (act.mode >= 0 && xr.lo_goal) {
+        const size_t slot = (size_t)xr.t * xr.N + env;
+        xr.lo_goal[slot] = make_float2(0.f, 0.f);
+        xr.lo_dist[slot] = 0.f;
+    }
 }
 
 // LEVEL 0: HighPolicyValueModel -> out0 = goal_mu [N][2], out1 = goal_std [N][2], out2 = value [N] (+ the goal pick)
@@ -68,16 +97,16 @@ __global__ __launch_bounds__(HP) void k_xy_f32(XyF32 w, DevParams p, SkillState 
         if (j < n_env) {
             const int env = env0 + j;
             if (LEVEL == 0)
-                a = pick.mode < 0 ||
+                a = pick.mode < 0 || pick.mode == 2 || pick.every ||
                     ((st.skill[env] < 0 || st.age[env] >= pick.skill_len) && !p.sched[env].done_state);
             else
-                a = st.skill[env] >= 0;
+                a = pick.every || st.skill[env] >= 0;
         }
         on[j] = a;
     }
     __syncthreads();
     if (!(on[0] | on[1] | on[2] | on[3])) {
-        if (LEVEL == 1 && j < n_env) idle_outputs(env0 + j, out0, out1, out2, act);
+        if (LEVEL == 1 && j < n_env) xy_idle(env0 + j, out0, out1, out2, act, pick.rec);
         return;
     }
     if (j < EB * XP) {
@@ -93,6 +122,18 @@ __global__ __launch_bounds__(HP) void k_xy_f32(XyF32 w, DevParams p, SkillState 
             }
         }
         xin[j] = v;
+    }
+    if (LEVEL == 0 && pick.rec.hi_obs) {
+        // zenv_collect_xy: the obs and zone_obs every picking env picks on, into its row env * W + k
+        const XyRecord &xr = pick.rec;
+        const int ZFn = p.Z * p.F;
+        for (int i = j; i < EB * (8 + ZFn); i += HP) {
+            const int e = i / (8 + ZFn), k = i - e * (8 + ZFn);
+            if (e >= n_env || !on[e]) continue;
+            const size_t env = (size_t)(env0 + e), row = env * xr.W + xr.k;
+            if (k < 8) xr.hi_obs[row * 8 + k] = p.obs[env * 8 + k];
+            else xr.hi_zone_obs[row * ZFn + (k - 8)] = p.zone_obs[env * ZFn + (k - 8)];
+        }
     }
     __syncthreads();
     encode_envs<XIN>(LEVEL ? w.lo : w.hi, p, xin, nullptr, nullptr, nullptr, env0, n_env, h, j, x0, y1, peb, va, vb);
@@ -132,10 +173,23 @@ __global__ __launch_bounds__(HP) void k_xy_f32(XyF32 w, DevParams p, SkillState 
         reinterpret_cast<float2 *>(out0)[env] = m;
         reinterpret_cast<float2 *>(out1)[env] = sd;
         out2[env] = o[4];
-        if (pick.mode >= 0) {
-            goal[env] = pick.mode == 1 ? xy_goal_draw(pick, env, m, sd) : m;
+        if (pick.mode == 2) {                             // the bootstrap goal: the state stays as it is
+            pick.boot[env] = xy_goal_draw(pick, env, m, sd, kXyBootTag);
+        } else if (pick.mode >= 0) {
+            const float2 g = pick.mode == 1 ? xy_goal_draw(pick, env, m, sd, kXyGoalTag) : m;
+            goal[env] = g;
             st.skill[env] = 0;
             st.age[env] = 0;
+            const XyRecord &xr = pick.rec;
+            if (xr.hi_goal) {                             // zenv_collect_xy: the pick's row
+                const size_t row = (size_t)env * xr.W + xr.k;
+                xr.hi_goal[row] = g;
+                xr.hi_value[row] = o[4];
+                // Normal(goal_mu, goal_std).log_prob(goal).sum(-1), each term as head_outputs forms the action's
+                const float z0 = (g.x - m.x) / sd.x, z1 = (g.y - m.y) / sd.y;
+                xr.hi_log_prob[row] = (-0.5f * z0 * z0 - logf(sd.x) - 0.91893853320467274178f) +
+                                      (-0.5f * z1 * z1 - logf(sd.y) - 0.91893853320467274178f);
+            }
         }
         return;
     }
@@ -143,8 +197,12 @@ __global__ __launch_bounds__(HP) void k_xy_f32(XyF32 w, DevParams p, SkillState 
         out2[env] = o[4];
         head_outputs(env, o[0], o[1], o[2], o[3], o[4], out0, out1, act);
         if (act.mode >= 0 && !p.sched[env].done_state) st.age[env] += 1;
+        if (act.mode >= 0 && pick.rec.lo_goal) {
+            const float *x = xin + j * XP;                // [obs, goal] of this env
+            xy_record_goal(pick.rec, env, make_float2(x[8], x[9]), x[1], x[2]);
+        }
     } else {
-        idle_outputs(env, out0, out1, out2, act);
+        xy_idle(env, out0, out1, out2, act, pick.rec);
     }
 }
 
@@ -212,9 +270,10 @@ hipError_t launch_xy_high(const XyF32 &w, const DevParams &p, const SkillState &
 }
 
 hipError_t launch_xy_low(const XyF32 &w, const DevParams &p, const SkillState &st, const float2 *goal, float *mu,
-                         float *stdv, float *value, const MlpAction &act, hipStream_t s)
+                         float *stdv, float *value, const MlpAction &act, hipStream_t s, const XyRecord *rec, int every)
 {
-    const XyPick none{ -1, 0, 0u, 0ull, 0ull };
+    XyPick none{ -1, 0, 0u, 0ull, 0ull, every, nullptr, XyRecord{} };
+    if (rec) none.rec = *rec;
     hipLaunchKernelGGL(k_xy_f32<1>, dim3((p.N + EB - 1) / EB), dim3(HP), 0, s, w, p, st, const_cast<float2 *>(goal), mu,
                        stdv, value, none, act);
     return hipGetLastError();

@@ -43,26 +43,50 @@ XyF32 xy_f32_at(const zenv_xy_weights &w, const float *base, const size_t offs[k
 // The agent's per-env state is the skill family's SkillState -- skill 0 = the env has a goal, -1 = none; age = low-level
 // steps under it; epi as there, so that k_skill_sync and the reset paths clear a goal as they clear a skill -- with the
 // goal itself beside it: goal [N] (meaningful where skill >= 0).
+// What zenv_collect_xy (xy_collect.hip) records besides the kernels' outputs, at frame t of T, N envs:
+//   high level, at the first frame of window k (of W = T / L): row env * W + k of the env-major hi rows -- the obs and
+//   zone_obs the goal was picked on, the goal, the critic's value, Normal(goal_mu, goal_std).log_prob(goal).sum(-1)
+//   low level, every frame: the goal it acted under into lo_goal [T][N] and its distance from the robot (obs[1:3])
+//   into lo_dist [T][N]; the rest goes through MlpAction::rec
+struct XyRecord {
+    int t, N, W, k;
+    float *hi_obs, *hi_zone_obs;       // [N * W][8], [N * W][Z * F]
+    float2 *hi_goal;                   // [N * W]
+    float *hi_value, *hi_log_prob;     // [N * W]
+    float2 *lo_goal;                   // [T][N]
+    float *lo_dist;                    // [T][N]
+};
 // What the high-level kernel does besides goal_mu / goal_std / value: mode < 0 -- nothing, every env is evaluated; 0 / 1
 // -- every env without a goal or whose age has reached skill_len, and which is not finished, gets one: goal_mu (0) or
 // goal_mu + goal_std * n (1), n a Box-Muller pair keyed by (seed, global env, step) on a Philox stream of its own; only
-// those envs are evaluated and written.
+// those envs are evaluated and written.  zenv_collect_xy adds: every = 1 -- every env picks (a window's first frame);
+// mode 2 -- every env is evaluated and draws g' on a second stream into boot[N], the goal and its clock are not touched
+// (the bootstrap goal).  For the low level, every = 1 evaluates every env whatever its clock says (under boot).
 struct XyPick {
     int mode, skill_len;
     uint32_t step_index;
     uint64_t seed, env_index0;
+    int every;
+    float2 *boot;
+    XyRecord rec;                       // null pointers: nothing is recorded
 };
 hipError_t launch_xy_high(const XyF32 &w, const DevParams &p, const SkillState &st, float2 *goal, float *goal_mu,
                           float *goal_std, float *value, const XyPick &pick, hipStream_t s);
-// Low level for every env with a goal: mu / std / value under goal[env] as it stands, and the action as MlpAction asks;
-// then, when it acts (act.mode >= 0), the age of every unfinished env with a goal goes up by one.  An env without a
-// goal gets mu = std = value = 0 (and action 0).
+// Low level for every env with a goal (every: for every env): mu / std / value under goal[env] as it stands, and the
+// action as MlpAction asks; then, when it acts (act.mode >= 0), the age of every unfinished env with a goal goes up by
+// one.  An env without a goal gets mu = std = value = 0 (and action 0).
 hipError_t launch_xy_low(const XyF32 &w, const DevParams &p, const SkillState &st, const float2 *goal, float *mu,
-                         float *stdv, float *value, const MlpAction &act, hipStream_t s);
+                         float *stdv, float *value, const MlpAction &act, hipStream_t s, const XyRecord *rec = nullptr,
+                         int every = 0);
 // zenv_set_xy_goals: in [N] -> goal, skill 0, age 0 for every env in mask (null = all)
 hipError_t launch_xy_set(const DevParams &p, const SkillState &st, float2 *goal, const float2 *in, const uint8_t *mask,
                          hipStream_t s);
 // ZENV_F_XY_GOAL_AGE: age_out[env] = the env's age, -1 without a goal
 hipError_t launch_xy_age(const DevParams &p, const SkillState &st, int32_t *age_out, hipStream_t s);
+
+// ---- zenv_collect_xy (xy_collect.hip)
+// After the frames, the low level's distance-to-goal reward, elementwise over [T][N]:
+// reward[t] = (dist[t] - dist[t + 1]) * mask[t + 1] * ((t + 1) % L != 0), 0 at frame T - 1
+hipError_t launch_xy_lo_reward(float *reward, const float *dist, const float *mask, int T, int L, int N, hipStream_t s);
 
 }  // namespace zenvk

@@ -1,6 +1,6 @@
 // zenv_agents.cpp -- the networks behind the C ABI of include/zenv.h: the loaders, forwards and per-step policies of the
-// flat actor and of the Zone-goals, fixed-length-skills / DIAYN, Options and xy-goals agents, and the four collectors
-// (zenv_collect, zenv_collect_hier, zenv_collect_skill, zenv_collect_option).  The handle and the environment's own calls: zenv_api.cpp.
+// flat actor and of the Zone-goals, fixed-length-skills / DIAYN, Options and xy-goals agents, and the five collectors
+// (zenv_collect, zenv_collect_hier, zenv_collect_skill, zenv_collect_option, zenv_collect_xy).  The handle and the environment's own calls: zenv_api.cpp.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -554,7 +554,7 @@ extern "C" int zenv_xy_forward(zenv_t *h)
     if (!h->was_reset) return fail(ZENV_E_STATE, "reset before asking for actions");
     if (int rc = use_device(h)) return rc;
     HIP_TRY(launch_skill_sync(h->p, h->sst, nullptr, 0, h->stream));
-    const XyPick none{ -1, h->skill_len, 0u, 0ull, 0ull };
+    const XyPick none{ -1, h->skill_len, 0u, 0ull, 0ull, 0, nullptr, XyRecord{} };
     HIP_TRY(launch_xy_high(h->xy, h->p, h->sst, h->xy_goal, h->xy_goal_mu, h->xy_goal_std, h->xy_value, none, h->stream));
     HIP_TRY(launch_xy_low(h->xy, h->p, h->sst, h->xy_goal, h->mlp_mu, h->mlp_std, h->mlp_value, no_mlp_action(),
                           h->stream));
@@ -568,7 +568,7 @@ static int run_xy_policy(zenv_t *h, int policy, uint32_t step_index, uint64_t se
     if (!h->xy_ready) return fail(ZENV_E_STATE, "zenv_xy_load first");
     const int mode = policy == ZENV_POLICY_XY_SAMPLE ? 1 : 0;
     HIP_TRY(launch_skill_sync(h->p, h->sst, nullptr, 0, h->stream));
-    const XyPick pick{ mode, h->skill_len, step_index, seed, env_index0 };
+    const XyPick pick{ mode, h->skill_len, step_index, seed, env_index0, 0, nullptr, XyRecord{} };
     HIP_TRY(launch_xy_high(h->xy, h->p, h->sst, h->xy_goal, h->xy_goal_mu, h->xy_goal_std, h->xy_value, pick, h->stream));
     const MlpAction act{ mode, step_index, seed, env_index0, out, MlpRecord{} };
     HIP_TRY(launch_xy_low(h->xy, h->p, h->sst, h->xy_goal, h->mlp_mu, h->mlp_std, h->mlp_value, act, h->stream));
@@ -986,6 +986,103 @@ extern "C" int zenv_collect_skill(zenv_t *h, int T, uint64_t policy_seed, uint64
     HIP_TRY(launch_exp_gae(h->exp, h->n_env, h->mlp_value, discount, gae_lambda, h->stream));
     HIP_TRY(launch_skill_hi_gae(o, T, L, h->n_env, h->sk.env_reward, h->exp.mask, h->exp.cur_mask, h->skill_value,
                                 gae_lambda, h->sk.count, h->stream));
+    return ZENV_OK;
+}
+
+// ---- zenv_collect_xy: collect_experiences of the xy-goals agent (xy-goals/src/torch_ac/algos/_hier_policy_opt.py:
+// 10-192).  The per-frame records for T frames in W windows (the ZENV_F_EXP_* buffers aside)
+static int ensure_xy_collect(zenv_t *h, int T, int W)
+{
+    if (h->xc_mem && h->xc.T == T && h->xc.W == W) return ZENV_OK;
+    const size_t N = (size_t)h->n_env, TN = (size_t)T * N;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->xc_mem) HIP_TRY(hipFree(h->xc_mem));
+    h->xc_mem = nullptr;
+    Carver cv;
+    cv.piece(h->xc.lo_goal, TN);
+    cv.piece(h->xc.dist, TN);
+    cv.piece(h->xc.env_reward, TN);
+    cv.piece(h->xc.hi_goal, N * (size_t)W);
+    cv.piece(h->xc.boot, N);
+    cv.piece(h->xc.count, N);
+    if (int rc = cv.alloc(&h->xc_mem, "xy-goals record")) return rc;
+    HIP_TRY(hipMemsetAsync(h->xc_mem, 0, cv.bytes(), h->stream));
+    h->xc.T = T;
+    h->xc.W = W;
+    return ZENV_OK;
+}
+
+extern "C" int zenv_collect_xy(zenv_t *h, int T, uint64_t policy_seed, uint64_t env_index0, float discount,
+                               float gae_lambda)
+{
+    const int L = h ? h->skill_len : 1;
+    int rc = collect_ready(h, "zenv_collect_xy", T, T / L, discount, gae_lambda);     // a window's last frame resets
+    if (rc) return rc;
+    if (h->order_enabled || h->goal_enabled)
+        return fail(ZENV_E_STATE, "zenv_collect_xy steps a plain task handle, not a goal-conditioned / solver-ordered one");
+    if (!h->xy_ready) return fail(ZENV_E_STATE, "zenv_xy_load first");
+    if (!h->xy.hi_critic || !h->xy.lo_critic)
+        return fail(ZENV_E_STATE, "zenv_collect_xy needs both critics (zenv_xy_load with hi_critic_* and lo_critic_*)");
+    if (T < 1 || T % L != 0)
+        return fail(ZENV_E_ARG, "frames_per_proc %d must be a positive multiple of skill_len %d", T, L);
+    if (int rc = use_device(h)) return rc;
+    const size_t N = (size_t)h->n_env;
+    const int W = T / L;
+    h->act_tag.valid = false;
+    if (int rc = ensure_exp(h, T)) return rc;
+    if (int rc = ensure_xy_collect(h, T, W)) return rc;
+    h->hi_m = 0;
+    h->hi_kind = 3;
+    if (int rc = ensure_hier_out(h, (int64_t)N * W)) return rc;
+    h->hi_m = (int64_t)N * W;
+    const HierOut &o = h->hout;
+    const FrameObs frames(h);
+    if (int rc = frames.begin()) return rc;
+    for (int t = 0; t < T; ++t) {
+        frames.read(t);
+        const uint32_t step_index = (uint32_t)h->step_count;
+        XyRecord xr{ t, h->n_env, W, t / L, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+        if (t % L == 0) {
+            // :29-42 every env picks, whatever it held (goal ~ hi_dist), the pick recorded in row env * W + t / L
+            HIP_TRY(launch_skill_sync(h->p, h->sst, nullptr, 0, h->stream));
+            XyPick pick{ 1, L, step_index, policy_seed, env_index0, 1, nullptr, xr };
+            pick.rec.hi_obs = o.obs;
+            pick.rec.hi_zone_obs = o.zone_obs;
+            pick.rec.hi_goal = h->xc.hi_goal;
+            pick.rec.hi_value = o.value;
+            pick.rec.hi_log_prob = o.log_prob;
+            HIP_TRY(launch_xy_high(h->xy, h->p, h->sst, h->xy_goal, h->xy_goal_mu, h->xy_goal_std, h->xy_value, pick,
+                                   h->stream));
+        }
+        // :45-72 the low level's action under the goal; frame t recorded with its goal and distance (and the env
+        // reward / mask of frame t-1)
+        const MlpRecord rec{ h->exp.action, h->exp.log_prob, h->exp.value, h->exp.mask, h->xc.env_reward,
+                             h->exp.cur_mask, h->p.reward, nullptr, h->p.done_out, T, t, h->n_env };
+        const MlpAction act{ 1, step_index, policy_seed, env_index0, h->p.actions, rec };
+        xr.lo_goal = h->xc.lo_goal;
+        xr.lo_dist = h->xc.dist;
+        HIP_TRY(launch_xy_low(h->xy, h->p, h->sst, h->xy_goal, h->mlp_mu, h->mlp_std, h->mlp_value, act, h->stream, &xr));
+        frames.write_next(t, T);
+        // :51-54 step_no_reset inside a window, step on its last frame
+        HIP_TRY(launch_step(h->p, h->p.actions, (t + 1) % L == 0 ? 1 : 0, no_policy(), h->stream));
+        h->step_count += 1;
+    }
+    {   // the env reward of frame T-1 and self.lo_mask = 1 - done
+        ExpBuffers last = h->exp;
+        last.reward = h->xc.env_reward;
+        HIP_TRY(launch_exp_reward(last, h->n_env, T - 1, h->p.reward, nullptr, h->p.done_out, h->stream));
+    }
+    // :98-105 next_hi_value = V_hi(obs_T); g' ~ hi_dist(obs_T) on a stream of its own; next_lo_value = V_lo(obs_T, g')
+    const XyPick boot{ 2, L, (uint32_t)h->step_count, policy_seed, env_index0, 1, h->xc.boot, XyRecord{} };
+    HIP_TRY(launch_xy_high(h->xy, h->p, h->sst, h->xy_goal, h->xy_goal_mu, h->xy_goal_std, h->xy_value, boot, h->stream));
+    HIP_TRY(launch_xy_low(h->xy, h->p, h->sst, h->xc.boot, h->mlp_mu, h->mlp_std, h->mlp_value, no_mlp_action(),
+                          h->stream, nullptr, 1));
+    // :128-131 the low level's reward from the recorded distances, :123-134 its GAE over all T frames; :111-120 the
+    // high level per env over its windows
+    HIP_TRY(launch_xy_lo_reward(h->exp.reward, h->xc.dist, h->exp.mask, T, L, h->n_env, h->stream));
+    HIP_TRY(launch_exp_gae(h->exp, h->n_env, h->mlp_value, discount, gae_lambda, h->stream));
+    HIP_TRY(launch_skill_hi_gae(o, T, L, h->n_env, h->xc.env_reward, h->exp.mask, h->exp.cur_mask, h->xy_value,
+                                gae_lambda, h->xc.count, h->stream));
     return ZENV_OK;
 }
 

@@ -198,14 +198,18 @@ FieldInfo field_info(const zenv *h, int field)
     case ZENV_F_EXCEPTION: return { p.exception, N };
     case ZENV_F_HIER_LOGITS: return { h->hier_logits, h->hier_logits ? N * p.Z * 4 : 0 };
     case ZENV_F_HIER_VALUE: return { h->hier_value, h->hier_value ? N * 4 : 0 };
-    case ZENV_F_LO_GOAL: return { h->hframes.lo_goal, h->hframes.lo_goal ? N * h->hframes.T * 2 * 4 : 0 };
-    case ZENV_F_LO_ENV_REWARD:       // zenv_collect_hier's / _option's or zenv_collect_skill's
+    case ZENV_F_LO_GOAL:
+        if (h->hi_kind == 3) return { h->xc.lo_goal, N * h->xc.T * 2 * 4 };
+        return { h->hframes.lo_goal, h->hframes.lo_goal ? N * h->hframes.T * 2 * 4 : 0 };
+    case ZENV_F_LO_ENV_REWARD:       // zenv_collect_hier's / _option's, zenv_collect_skill's or zenv_collect_xy's
+        if (h->hi_kind == 3) return { h->xc.env_reward, N * h->xc.T * 4 };
         if (h->hi_kind != 2 && h->sk_mem) return { h->sk.env_reward, N * h->sk.T * 4 };
         return { h->hframes.env_reward, h->hframes.env_reward ? N * h->hframes.T * 4 : 0 };
     case ZENV_F_HI_OBS: return { h->hout.obs, h->hi_m * 8 * 4 };
     case ZENV_F_HI_ZONE_OBS: return { h->hout.zone_obs, h->hi_m * p.Z * p.F * 4 };
-    case ZENV_F_HI_ACTION: return { h->hout.action, h->hi_m * 4 };
-    case ZENV_F_HI_ACTION_MASK: return { h->hout.action_mask, h->sk_mem || h->hi_kind == 2 ? 0 : h->hi_m * p.Z };   // skills: not written
+    case ZENV_F_HI_ACTION: return { h->hout.action, h->hi_kind == 3 ? 0 : h->hi_m * 4 };     // xy-goals: ZENV_F_HI_GOAL
+    case ZENV_F_HI_ACTION_MASK:      // skills, options, xy-goals: not written
+        return { h->hout.action_mask, h->sk_mem || h->hi_kind >= 2 ? 0 : h->hi_m * p.Z };
     case ZENV_F_HI_VALUE: return { h->hout.value, h->hi_m * 4 };
     case ZENV_F_HI_LOG_PROB: return { h->hout.log_prob, h->hi_m * 4 };
     case ZENV_F_HI_ADVANTAGE: return { h->hout.advantage, h->hi_m * 4 };
@@ -213,6 +217,7 @@ FieldInfo field_info(const zenv *h, int field)
     case ZENV_F_HI_REWARD: return { h->hout.reward, h->hi_m * 4 };
     case ZENV_F_HI_MASK: return { h->hout.mask, h->hi_m * 4 };
     case ZENV_F_HI_COUNT:
+        if (h->hi_kind == 3) return { h->xc.count, N * 4 };
         if (h->hi_kind != 2 && h->sk_mem) return { h->sk.count, N * 4 };
         return { h->hframes.count, h->hframes.count ? N * 4 : 0 };
     case ZENV_F_SKILL: return { h->sst.skill, h->sst_mem ? N * 4 : 0 };          // (refresh_field() first)
@@ -237,6 +242,9 @@ FieldInfo field_info(const zenv *h, int field)
     case ZENV_F_XY_GOAL_STD: return { h->xy_goal_std, h->xy_state_mem ? N * 2 * 4 : 0 };
     case ZENV_F_XY_VALUE: return { h->xy_value, h->xy_state_mem ? N * 4 : 0 };
     case ZENV_F_XY_GOAL_AGE: return { h->xy_age, h->xy_state_mem ? N * 4 : 0 };      // (refresh_field() first)
+    case ZENV_F_HI_GOAL: return { h->xc.hi_goal, h->hi_kind == 3 ? h->hi_m * 2 * 4 : 0 };
+    case ZENV_F_LO_GOAL_DIST: return { h->xc.dist, h->xc_mem ? N * h->xc.T * 4 : 0 };
+    case ZENV_F_XY_BOOTSTRAP_GOAL: return { h->xc.boot, h->xc_mem ? N * 2 * 4 : 0 };
     default: return { nullptr, 0 };
     }
 }
@@ -545,7 +553,7 @@ extern "C" int zenv_destroy(zenv_t *h)
                      (void *)h->p.order_val, h->hier_mem, (void *)h->hier_logits, (void *)h->hier_value,
                      h->hframes_mem, h->hcarry_mem, h->hout_mem, h->skill_mem, h->sst_mem, (void *)h->skill_logits,
                      (void *)h->skill_value, h->skinv_mem, h->sk_mem, h->opt_mem, h->oc_mem, h->xy_mem,
-                     h->xy_state_mem })
+                     h->xy_state_mem, h->xc_mem })
         if (m) (void)hipFree(m);
     for (hipEvent_t ev : h->events) (void)hipEventDestroy(ev);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);

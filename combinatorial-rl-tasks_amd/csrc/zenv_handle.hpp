@@ -115,6 +115,16 @@ struct zenv {
     float *xy_goal_mu = nullptr, *xy_goal_std = nullptr, *xy_value = nullptr;
     int32_t *xy_age = nullptr;
     uint8_t *xy_mask = nullptr;
+    // zenv_collect_xy: the per-frame records of one call (T frames, W windows) beside the ZENV_F_EXP_* buffers -- the
+    // low level's goal, its distance and the env reward [T][N]; the high level's goal of every row [N * W]; the
+    // bootstrap goal and the row count [N]
+    struct {
+        int T = 0, W = 0;
+        float2 *lo_goal = nullptr, *hi_goal = nullptr, *boot = nullptr;
+        float *dist = nullptr, *env_reward = nullptr;
+        int32_t *count = nullptr;
+    } xc;
+    void *xc_mem = nullptr;
     // zenv_collect_option: the per-frame records of one call (T frames) that have no place in hframes -- the skill the
     // low level acted under, a_2 with its log_prob and the termination draw, [T][N] each
     struct {
@@ -152,7 +162,8 @@ struct zenv {
     void *hout_mem = nullptr;
     int64_t hi_cap = 0, hi_m = 0;
     int hi_kind = 0;                    // whose rows and per-frame records the ZENV_F_HI_* / ZENV_F_LO_* fields hold:
-                                        // 0 zenv_collect_hier's, 1 zenv_collect_skill's, 2 zenv_collect_option's
+                                        // 0 zenv_collect_hier's, 1 zenv_collect_skill's, 2 zenv_collect_option's,
+                                        // 3 zenv_collect_xy's
     int32_t *hi_total_host = nullptr;   // page-locked word M is read back into
     // staging of zenv_bank_update (page-locked host image + its device copy)
     void *refill_host = nullptr, *refill_dev = nullptr;

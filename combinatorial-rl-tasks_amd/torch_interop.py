@@ -137,6 +137,19 @@ class TorchZoneEnv:
         from .vec_env import xy_tensors_from_state_dicts
         self.env.load_xy(xy_tensors_from_state_dicts(hi_state_dict, lo_state_dict), skill_len=skill_len)
 
+    def collect_xy(self, frames_per_proc, policy_seed=0, env_index0=0, discount=0.99, gae_lambda=0.95):
+        """collect_experiences of the xy-goals agent on the device; returns (lo, hi, num_frames) named and shaped as
+        ``ZoneVecEnv.collect_xy``: lo and hi are CUDA tensors ALIASING the handle's buffers (lo [N, T, ...] views of
+        time-major memory, hi flat [M, ...]), valid until the next collect; num_frames is a Python int (it waits for
+        the collection)."""
+        from .vec_env import xy_experience_layout, skill_num_frames
+        env = self.env
+        T, M = env.collect_xy_on_device(frames_per_proc, policy_seed, env_index0, discount, gae_lambda)
+        L = T * env.num_envs // M
+        lo_l, hi_l = xy_experience_layout(env.num_envs, env.num_zones, env.zone_feat, T, L)
+        lo = {name: t.transpose(0, 1) for name, t in self._alias_layout(lo_l).items()}
+        return lo, self._alias_layout(hi_l), skill_num_frames(lo["mask"].transpose(0, 1), L)
+
     def load_skill_inverse(self, state_dict, n_skills):
         """Put an InverseModel state_dict (main/src/inverse_model.py) into the device discriminator of the diversity
         reward -- after every update."""

@@ -19,7 +19,8 @@ from .agents import (_HIER_ENC, _HIER_CRITIC, HIER_HI_KEYS, HIER_LO_KEYS, SKILL_
                      skill_tensor_shapes, option_tensor_shapes, inverse_tensor_shapes, hier_tensors_from_state_dicts,
                      skill_tensors_from_state_dicts, option_tensors_from_state_dicts, inverse_tensors_from_state_dict,
                      check_collect_hier_args, check_collect_skill_args, check_collect_option_args,
-                     hier_experience_layout, skill_experience_layout, option_experience_layout, skill_num_frames)
+                     hier_experience_layout, skill_experience_layout, option_experience_layout, skill_num_frames,
+                     check_collect_xy_args, xy_experience_layout)
 
 _FIELD_DTYPES = {
     nat.F_OBS: np.float32, nat.F_ZONE_OBS: np.float32, nat.F_REWARD: np.float32,
@@ -40,7 +41,8 @@ _FIELD_DTYPES = {
     nat.F_OPTION_TERM_ACTION: np.float32, nat.F_OPTION_TERM_PROB: np.float32, nat.F_OPTION_ENDED: np.int32,
     nat.F_LO_TERM_ACTION: np.float32, nat.F_LO_TERM_LOG_PROB: np.float32, nat.F_LO_OPTION_ENDED: np.uint8,
     nat.F_XY_GOAL: np.float32, nat.F_XY_GOAL_MU: np.float32, nat.F_XY_GOAL_STD: np.float32, nat.F_XY_VALUE: np.float32,
-    nat.F_XY_GOAL_AGE: np.int32,
+    nat.F_XY_GOAL_AGE: np.int32, nat.F_HI_GOAL: np.float32, nat.F_LO_GOAL_DIST: np.float32,
+    nat.F_XY_BOOTSTRAP_GOAL: np.float32,
 }
 
 
@@ -605,6 +607,31 @@ class ZoneVecEnv:
         return (self.get(nat.F_XY_GOAL_MU), self.get(nat.F_XY_GOAL_STD), self.get(nat.F_XY_VALUE),
                 self.get(nat.F_POLICY_MU), self.get(nat.F_POLICY_STD), self.get(nat.F_POLICY_VALUE))
 
+    def collect_xy(self, frames_per_proc, policy_seed=0, env_index0=0, discount=0.99, gae_lambda=0.95):
+        """collect_experiences of the xy-goals agent (xy-goals/src/torch_ac/algos/_hier_policy_opt.py:10-192) on the
+        device with the loaded agent (``load_xy`` with both critics).  Returns (lo, hi, num_frames) under the
+        reference's names, numpy:
+          lo  [N, T, ...]: obs, zone_obs, goal, action, log_prob, value, advantage, returnn, reward (the
+              distance-to-goal reward), goal_dist, env_reward, mask -- reshape(N*T, ...) is the reference's flat order
+          hi  [M, ...] env-major, M = N T / skill_len: obs, zone_obs, goal, value, log_prob (summed over the goal's two
+              dimensions), advantage, returnn (hi_exps), reward (the window's sum of env rewards) and mask (its
+              next_mask)
+          num_frames  logs['num_frames']"""
+        T, M = self.collect_xy_on_device(frames_per_proc, policy_seed, env_index0, discount, gae_lambda)
+        L = T * self.num_envs // M
+        lo_l, hi_l = xy_experience_layout(self.num_envs, self.num_zones, self.zone_feat, T, L)
+        lo = {name: a.swapaxes(0, 1) for name, a in self._download(lo_l).items()}
+        return lo, self._download(hi_l), skill_num_frames(lo["mask"].swapaxes(0, 1), L)
+
+    def collect_xy_on_device(self, frames_per_proc, policy_seed=0, env_index0=0, discount=0.99, gae_lambda=0.95):
+        """The same collection, results left in the handle's device buffers (``xy_experience_layout`` names them).
+        Returns (T, M)."""
+        L = getattr(self, "_skill_len", 200)                  # zenv_skill_configure's default until load_xy
+        T, seed, index0, discount, gae_lambda = check_collect_xy_args(frames_per_proc, L, policy_seed, env_index0,
+                                                                      discount, gae_lambda)
+        check(lib().zenv_collect_xy(self._h, T, seed, index0, discount, gae_lambda))
+        return T, self.num_envs * (T // L)
+
     def load_skill_inverse(self, tensors, precision="f32"):
         """InverseModel, DIAYN's discriminator (main/src/inverse_model.py), for the diversity reward of
         ``collect_skills``.  tensors: dict of float32 arrays named as in ``_native.SKILL_INVERSE_TENSORS`` (see
@@ -780,7 +807,7 @@ class ZoneVecEnv:
         if field == nat.F_ZONE_OBS:
             return (N, self.num_zones, self.zone_feat)
         if field in (nat.F_ACTIONS, nat.F_POLICY_MU, nat.F_POLICY_STD, nat.F_XY_GOAL, nat.F_XY_GOAL_MU,
-                     nat.F_XY_GOAL_STD):
+                     nat.F_XY_GOAL_STD, nat.F_XY_BOOTSTRAP_GOAL):
             return (N, 2)
         return (N,)
 

@@ -160,7 +160,15 @@ enum {
     ZENV_F_XY_GOAL_STD = 68,        /* float32 [N,2] sigmoid(actor.std_) + 1e-3 */
     ZENV_F_XY_VALUE = 69,           /* float32 [N]   the high level's critic value (0 without critic tensors) */
     ZENV_F_XY_GOAL_AGE = 70,        /* int32   [N]   low-level steps taken under the current goal, -1 = no goal */
-    ZENV_F_COUNT = 71
+    /* xy-goals experience of the last zenv_collect_xy() (before these three fields, ZENV_F_COUNT = 71).  Its other
+     * records reuse the fields above: ZENV_F_EXP_* (the low level, time-major [T][N], EXP_REWARD = the distance-to-goal
+     * reward), ZENV_F_LO_GOAL (the goal the low level acted under), ZENV_F_LO_ENV_REWARD (the env reward) and the
+     * ZENV_F_HI_* rows with ZENV_F_HI_COUNT (M = N * T / skill_len, env-major; the goal is continuous, so
+     * ZENV_F_HI_ACTION and ZENV_F_HI_ACTION_MASK are not written and have size 0) */
+    ZENV_F_HI_GOAL = 71,            /* float32 [M,2] the high level's recorded goal */
+    ZENV_F_LO_GOAL_DIST = 72,       /* float32 [T,N] the distance of the goal from the robot (obs[1:3]) at every frame */
+    ZENV_F_XY_BOOTSTRAP_GOAL = 73,  /* float32 [N,2] g' ~ the high level at obs_T: the goal of next_lo_value */
+    ZENV_F_COUNT = 74
 };
 
 /* scripted on-device action sources (the build's own; used by bench/tests) */
@@ -848,6 +856,39 @@ int zenv_collect_skill(zenv_t *h, int frames_per_proc, uint64_t policy_seed, uin
  * a goal-conditioned or solver-ordered handle, more frames than a ring schedule's depth. */
 int zenv_collect_option(zenv_t *h, int frames_per_proc, uint64_t policy_seed, uint64_t env_index0, float discount,
                         float gae_lambda, int64_t *n_hi);
+
+/* ---- the same for the xy-goals agent: collect_experiences of xy-goals/src/torch_ac/algos/_hier_policy_opt.py:10-192
+ * (zenv_xy_load with BOTH critics, plain task handle) ----
+ * T frames, T a multiple of L = skill_len (zenv_skill_configure), W = T / L windows.  At frames 0, L, 2L ... EVERY env
+ * picks a goal, whatever it held before: goal_mu + goal_std * n, the draw of zenv_policy(ZENV_POLICY_XY_SAMPLE); row
+ * env * W + k of the high-level rows records the obs (ZENV_F_HI_OBS / _ZONE_OBS), the goal (ZENV_F_HI_GOAL), the high
+ * critic's value and Normal(goal_mu, goal_std).log_prob(goal) summed over the two dimensions (ZENV_F_HI_LOG_PROB).
+ * Every frame the low level acts under the env's goal and frame t is recorded (ZENV_F_EXP_*, ZENV_F_LO_GOAL; mask = 1 -
+ * done of the previous step, carried from call to call) with
+ *   dist_t = sqrt((goal_x - obs_t[1])^2 + (goal_y - obs_t[2])^2)    (ZENV_F_LO_GOAL_DIST; float32, as torch rounds it)
+ * on the observation the action is taken on; the envs step -- step_no_reset, except on a window's last frame, which
+ * auto-resets: an env whose episode ends inside a window idles (zero obs, reward 0, done 1) and its frames are
+ * evaluated and recorded all the same.  Then
+ *   lo_reward_t = (dist_t - dist_{t+1}) * mask_{t+1} * ((t + 1) % L != 0)   (ZENV_F_EXP_REWARD; 0 at frame T - 1, where
+ *                 the reference's factor is (T % L != 0) = 0); the env reward (ZENV_F_LO_ENV_REWARD) takes no part
+ * Bootstrap: V_hi(obs_T) into ZENV_F_XY_VALUE (its Normal into ZENV_F_XY_GOAL_MU / _GOAL_STD), g' drawn from it on a
+ * stream of its own (tag 0x585942; ZENV_F_XY_BOOTSTRAP_GOAL), next_lo_value = V_lo(obs_T, g') into
+ * ZENV_F_POLICY_VALUE (ZENV_F_POLICY_MU / _STD: the low level under g').  The goal and its clock are left as the last
+ * window left them.
+ *   low level:  GAE over all T frames with discount, bootstrapped by next_lo_value (the advantage / return fields)
+ *   high level: per env over its W windows, NO discount: ZENV_F_HI_REWARD = the window's sum of env rewards,
+ *               ZENV_F_HI_MASK = next_mask = ZENV_F_EXP_MASK of the next window's first frame (the carried mask for
+ *               the last), delta = reward + V_next * next_mask - V, adv = delta + gae_lambda * adv_next * next_mask
+ * ZENV_F_HI_COUNT = W for every env.  Afterwards ZENV_F_XY_GOAL holds the last window's goal with ZENV_F_XY_GOAL_AGE =
+ * L (-1 for an env the last frame reset), so the next zenv_policy(ZENV_POLICY_XY_*) picks at once.  Randomness: keyed
+ * by (policy_seed, env_index0 + env, zenv_step_count); on a handle whose goals are not older than their episode's
+ * windows (a fresh load) a call is bit-identical to T rounds of zenv_policy(ZENV_POLICY_XY_SAMPLE) + zenv_step with
+ * auto_reset on each window's last frame only.  No host synchronisation.
+ * ZENV_E_ARG: T < 1 or not a multiple of L, T x envs >= 2^31, a non-finite discount / gae_lambda or one outside
+ * [0, 1].  ZENV_E_STATE: no zenv_xy_load (another agent's weights loaded included), a critic missing, zenv_host_io on,
+ * a goal-conditioned or solver-ordered handle, more windows (T / L) than a ring schedule's depth. */
+int zenv_collect_xy(zenv_t *h, int frames_per_proc, uint64_t policy_seed, uint64_t env_index0, float discount,
+                    float gae_lambda);
 
 /* ---- results ---- */
 int zenv_get(zenv_t *h, int field, void *dst, int dst_on_device);
