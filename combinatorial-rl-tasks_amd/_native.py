@@ -46,7 +46,7 @@ E_ARG, E_HIP, E_STATE, E_LAYOUT, E_DONE, E_RANGE = -1, -2, -3, -4, -5, -6
  F_OPTION_TERM_MU, F_OPTION_TERM_STD, F_OPTION_TERM_ACTION, F_OPTION_TERM_PROB, F_OPTION_ENDED,
  F_LO_TERM_ACTION, F_LO_TERM_LOG_PROB, F_LO_OPTION_ENDED,
  F_XY_GOAL, F_XY_GOAL_MU, F_XY_GOAL_STD, F_XY_VALUE, F_XY_GOAL_AGE,
- F_HI_GOAL, F_LO_GOAL_DIST, F_XY_BOOTSTRAP_GOAL) = range(74)
+ F_HI_GOAL, F_LO_GOAL_DIST, F_XY_BOOTSTRAP_GOAL, F_PPO_STATS) = range(75)
 (RESULT_OBS, RESULT_REWARD, RESULT_DONE, RESULT_GOAL_MET, RESULT_EXCEPTION, RESULT_ZONE_OBS) = range(6)
 N_RESULTS = 6
 
@@ -122,6 +122,17 @@ class XyWeights(C.Structure):
     """struct zenv_xy_weights (include/zenv.h): host float32 tensors in state_dict layout."""
     _fields_ = [("h_dim", C.c_int32), ("zone_feat", C.c_int32), ("precision", C.c_int32), ("pad", C.c_int32)] + [
         (n, C.c_void_p) for n in XY_HI_TENSORS + XY_HI_CRITIC + XY_LO_TENSORS + XY_LO_CRITIC]
+
+
+PPO_PARAM, PPO_GRAD, PPO_EXP_AVG, PPO_EXP_AVG_SQ = 0, 1, 2, 3
+PPO_STATS = ("entropy", "value", "value_std", "policy_loss", "value_loss", "grad_norm")   # ZENV_F_PPO_STATS' columns
+
+
+class PpoConfig(C.Structure):
+    """struct zenv_ppo_config (include/zenv.h)."""
+    _fields_ = [("lr", C.c_double), ("adam_eps", C.c_double), ("clip_eps", C.c_double), ("entropy_coef", C.c_double),
+                ("value_loss_coef", C.c_double), ("max_grad_norm", C.c_double), ("max_batch", C.c_int32),
+                ("distributional_value", C.c_int32)]
 
 
 class ZenvError(RuntimeError):
@@ -214,6 +225,16 @@ _PROTOTYPES = {
     "zenv_collect_option": (C.c_int, [_H, C.c_int, C.c_uint64, C.c_uint64, C.c_float, C.c_float,
                                       C.POINTER(C.c_int64)]),
     "zenv_collect_xy": (C.c_int, [_H, C.c_int, C.c_uint64, C.c_uint64, C.c_float, C.c_float]),
+    "zenv_ppo_check": (C.c_int, [C.POINTER(Config), C.c_void_p, C.c_void_p]),
+    "zenv_ppo_init": (C.c_int, [_H, C.c_void_p, C.c_void_p]),
+    "zenv_ppo_tensor": (C.c_int, [_H, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    "zenv_ppo_read": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p]),
+    "zenv_ppo_write": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p]),
+    "zenv_ppo_get_step": (C.c_int, [_H, C.POINTER(C.c_int64)]),
+    "zenv_ppo_set_step": (C.c_int, [_H, C.c_int64]),
+    "zenv_ppo_minibatch": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "zenv_ppo_apply": (C.c_int, [_H]),
+    "zenv_ppo_epoch": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "zenv_get": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int]),
     "zenv_get_rows": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "zenv_device_ptr": (C.c_int, [_H, C.c_int, C.POINTER(C.c_void_p)]),

@@ -117,6 +117,32 @@ def mlp_tensors_from_state_dict(sd):
     return {k: _as_f32(sd[v]) for k, v in names.items()}
 
 
+_DIST_CRITIC = {"critic_w1": "critic.0.weight", "critic_b1": "critic.0.bias",
+                "critic_w2": "critic_mu.weight", "critic_b2": "critic_mu.bias",
+                "critic_sigma_w": "critic_sigma.weight", "critic_sigma_b": "critic_sigma.bias"}
+
+
+def ppo_state_dict_keys(distributional=False):
+    """zenv_mlp_weights name -> ACModel state_dict key (flat_model.py:24-52) of every tensor the learner holds, in the
+    arenas' order: 18 tensors, 20 with the distributional critic.  It is also ``ACModel.parameters()``' order, the
+    order of torch Adam's state."""
+    names = dict(HIER_LO_KEYS, **(_DIST_CRITIC if distributional else _HIER_CRITIC))
+    order = nat.MLP_TENSORS + nat.MLP_CRITIC_TENSORS + (nat.MLP_SIGMA_TENSORS if distributional else ())
+    return {name: names[name] for name in order}
+
+
+def ppo_batch_indexes(num_frames, frames_per_proc, batch_num, rng):
+    """The sample order of one epoch: _get_batches_starting_indexes (torch_ac/algos/ppo.py:157-183) for recurrence 1,
+    before it is cut into batches.  A permutation of range(num_frames) from the caller's numpy Generator; on every odd
+    call (batch_num) the indexes with (i + 1) % frames_per_proc == 0 are dropped and the shift is recurrence // 2 = 0
+    -- the reference's quirk, kept."""
+    indexes = rng.permutation(np.arange(0, num_frames, 1))
+    if batch_num % 2 == 1:
+        indexes = indexes[(indexes + 1) % frames_per_proc != 0]
+        indexes = indexes + 0
+    return np.ascontiguousarray(indexes, np.int32)
+
+
 def _two_level_tensors(hi_sd, lo_sd, hi_keys, lo_keys, sizes, want, describe):
     """The walk over a (hi_model_state, lo_model_state) pair: every key of hi_keys / lo_keys, the critics when present
     (critic.0 or critic.2), as numpy float32 under hi_<name> / lo_<name>.  sizes(out) reads the agent's sizes off the

@@ -1,0 +1,571 @@
+// ppo_update.hip -- one PPO minibatch of the flat actor-critic in float32, gfx950: forward, loss, backward, gradient-norm
+// clip and Adam (update_parameters, main/src/torch_ac/algos/ppo.py:30-155, recurrence 1) on the network of
+// mlp_f32.hip -- ZoneEnvModel (main/src/env_model.py:48-79), PolicyNetwork's Box branch (policy_network.py:39-52) and
+// both critics of ACModel (flat_model.py:21-68).
+//
+// Every layer is a product on v_mfma_f32_32x32x2_f32, forward and backward, in one of two shapes:
+//
+//  * k_ppo_nt   Y[row][f] = sum_k W[f][k] X[row][k].  A 32 x 32 result has its row (a zone row or a sample) on the lane
+//    and 16 features in the registers.  Both operands are k-contiguous in memory, so lane (r, half) reads one float4 of
+//    its weight row and one of its activation row per four MFMAs; the k index a lane half feeds to MFMA t of a group is
+//    8 q + 4 half + t for both operands, a permutation of the reduction that leaves the sum what it is.  The forward
+//    layers use the padded weights [out][in], the backward-data products their transposes.
+//  * k_ppo_tn   dW[n][k] = sum_row dY[row][n] X[row][k].  The reduction runs over rows, both operands are read as
+//    they lie (32 consecutive floats of two rows per MFMA).  A wave reduces kPpoChunk rows into a partial of its own;
+//    k_ppo_reduce adds the partials of an element in chunk order, in double.  No atomics: the same call from the same
+//    state gives the same bits.
+//
+// Activations are row-major [row][HP], HP = h rounded up to 32 (h <= 191, so a padded column is always free).  Column
+// h of every activation is the constant 1 of a valid row: the biases ride in column h of the padded weights, and the
+// bias gradients come out as column h of the weight gradients.  Rows past the minibatch are all zero, constant
+// included, so they add nothing to any gradient.  The minibatch is gathered by index straight from the time-major
+// experience buffers (zone_net_.0's input has no copy); an index outside [0, N T) is never dereferenced: its rows
+// read as zero, its sample takes no part in the loss, and a flag tells the host.
+//
+// The weights the products read are padded images of the parameter arena, rebuilt by k_ppo_prep before every
+// minibatch (0.9 MB); the arenas themselves stay in the state_dict's unpadded layout.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+#include "ppo_update.hpp"
+
+namespace zenvk {
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+struct Gather {
+    const float *obs, *zone_obs;
+    const int32_t *idx;
+    int count, N, T, Z, F;
+};
+
+// where a zone row of the minibatch lies in the experience buffers
+struct RowRef {
+    bool ok;
+    size_t slot;     // frame * N + env
+    int z;
+};
+
+__device__ __forceinline__ bool sample_slot(const Gather &g, int b, size_t &slot)
+{
+    if (b >= g.count) return false;
+    const int i = g.idx[b];
+    if (i < 0 || i >= g.N * g.T) return false;       // N T < 2^31: zenv_collect refuses more
+    const int env = i / g.T, t = i - env * g.T;      // exps.* flattens [N][T] (base.py:212-227)
+    slot = (size_t)t * g.N + env;
+    return true;
+}
+
+__device__ __forceinline__ RowRef row_ref(const Gather &g, int row)
+{
+    RowRef r;
+    const int b = row / g.Z;
+    r.z = row - b * g.Z;
+    r.slot = 0;
+    r.ok = sample_slot(g, b, r.slot);
+    return r;
+}
+
+// zone_net_.0's input [obs (8), zone row (F), 0 ..., 1]: column 15 is the constant that carries the bias
+__device__ __forceinline__ float x0_elem(const Gather &g, const RowRef &r, int k)
+{
+    if (!r.ok) return 0.f;
+    if (k < 8) return g.obs[r.slot * 8 + k];
+    if (k < 8 + g.F) return g.zone_obs[(r.slot * g.Z + r.z) * g.F + (k - 8)];
+    return k == 15 ? 1.f : 0.f;
+}
+
+__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c)
+{
+    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
+}
+
+enum { NT_STORE = 0, NT_RELU = 1, NT_MASK = 2, NT_ADD = 3 };
+
+// D[row][f] (op)= sum_k A[f][k] B[row][k]; grid = row tiles, block = (64, feature tiles).  A: [32 x tiles][lda], B:
+// [32 x row tiles][ldb] or the gathered input, K a multiple of 8.  NT_MASK keeps the product where D held a positive
+// activation (the ReLU's derivative) and writes 0 elsewhere; NT_ADD adds to D.
+template <int MODE, bool GATHER>
+__global__ __launch_bounds__(448) void k_ppo_nt(const float *__restrict__ A, int lda, const float *__restrict__ B, int ldb,
+                                                int K, float *D, int ldd, Gather g)
+{
+    const int lane = threadIdx.x, r = lane & 31, hh = lane >> 5;
+    const int row = blockIdx.x * 32 + r, f0 = threadIdx.y * 32;
+    const float *ap = A + (size_t)(f0 + r) * lda + 4 * hh;
+    // eight accumulators, one per MFMA of two groups: chains of K / 16 steps (K / 8 fused multiply-adds) instead of
+    // one of K / 2 -- float32's rounding grows with the chain -- and no MFMA waits for the one before it
+    f32x16 acc8[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc8[u][i] = 0.f;
+    const RowRef ref = GATHER ? row_ref(g, row) : RowRef{ false, 0, 0 };
+    const float *bp = GATHER ? nullptr : B + (size_t)row * ldb + 4 * hh;
+    auto load_b = [&](int q) {
+        if (GATHER) {
+            const int k = 8 * q + 4 * hh;
+            return make_float4(x0_elem(g, ref, k), x0_elem(g, ref, k + 1), x0_elem(g, ref, k + 2), x0_elem(g, ref, k + 3));
+        }
+        return *reinterpret_cast<const float4 *>(bp + 8 * q);
+    };
+    const int groups = K / 8;
+    int q = 0;
+    for (; q + 1 < groups; q += 2) {
+        const float4 a0 = *reinterpret_cast<const float4 *>(ap + 8 * q), a1 = *reinterpret_cast<const float4 *>(ap + 8 * q + 8);
+        const float4 b0 = load_b(q), b1 = load_b(q + 1);
+        acc8[0] = mfma32(a0.x, b0.x, acc8[0]);
+        acc8[1] = mfma32(a0.y, b0.y, acc8[1]);
+        acc8[2] = mfma32(a0.z, b0.z, acc8[2]);
+        acc8[3] = mfma32(a0.w, b0.w, acc8[3]);
+        acc8[4] = mfma32(a1.x, b1.x, acc8[4]);
+        acc8[5] = mfma32(a1.y, b1.y, acc8[5]);
+        acc8[6] = mfma32(a1.z, b1.z, acc8[6]);
+        acc8[7] = mfma32(a1.w, b1.w, acc8[7]);
+    }
+    if (q < groups) {                       // combine_net_'s K = HP + 8: an odd number of groups
+        const float4 a0 = *reinterpret_cast<const float4 *>(ap + 8 * q);
+        const float4 b0 = load_b(q);
+        acc8[0] = mfma32(a0.x, b0.x, acc8[0]);
+        acc8[1] = mfma32(a0.y, b0.y, acc8[1]);
+        acc8[2] = mfma32(a0.z, b0.z, acc8[2]);
+        acc8[3] = mfma32(a0.w, b0.w, acc8[3]);
+    }
+    const f32x16 acc = ((acc8[0] + acc8[1]) + (acc8[2] + acc8[3])) + ((acc8[4] + acc8[5]) + (acc8[6] + acc8[7]));
+    // register i of lane (r, hh) is feature f0 + (i & 3) + 8 (i >> 2) + 4 hh of row r: four float4 stores
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        float4 *dp = reinterpret_cast<float4 *>(D + (size_t)row * ldd + f0 + 8 * q + 4 * hh);
+        float4 v = make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
+        if (MODE == NT_RELU) v = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
+        if (MODE == NT_MASK) {
+            const float4 o = *dp;
+            v = make_float4(o.x > 0.f ? v.x : 0.f, o.y > 0.f ? v.y : 0.f, o.z > 0.f ? v.z : 0.f, o.w > 0.f ? v.w : 0.f);
+        }
+        if (MODE == NT_ADD) {
+            const float4 o = *dp;
+            v = make_float4(o.x + v.x, o.y + v.y, o.z + v.z, o.w + v.w);
+        }
+        *dp = v;
+    }
+}
+
+// part[chunk][n][k] = sum over the chunk's rows of A[row][n] B[row][k]; grid = (chunks, n tiles), block = (64, k
+// tiles).  `rows` is a multiple of 32, so both lane halves make the same number of steps, a multiple of 8.  Columns of B from nB on
+// read as 0; GATHER: B is zone_net_.0's gathered input (16 columns).
+template <bool GATHER>
+__global__ __launch_bounds__(448) void k_ppo_tn(const float *__restrict__ A, int lda, const float *__restrict__ B, int ldb,
+                                                int nB, int rows, float *__restrict__ part, Gather g)
+{
+    const int lane = threadIdx.x, r = lane & 31, hh = lane >> 5;
+    const int i0 = blockIdx.y * 32, j0 = threadIdx.y * 32;
+    const int row_begin = blockIdx.x * kPpoChunk, row_end = min(rows, row_begin + kPpoChunk);
+    const bool col = j0 + r < nB;
+    // eight accumulators taking the row pairs in turn (a chunk's rows are a multiple of 32): chains of 16 steps
+    f32x16 part8[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) part8[u][i] = 0.f;
+    for (int row0 = row_begin + hh; row0 < row_end; row0 += 16) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int row = row0 + 2 * u;
+            const float a = A[(size_t)row * lda + i0 + r];
+            float b = 0.f;
+            if (col) b = GATHER ? x0_elem(g, row_ref(g, row), j0 + r) : B[(size_t)row * ldb + j0 + r];
+            part8[u] = mfma32(a, b, part8[u]);
+        }
+    }
+    const f32x16 acc = ((part8[0] + part8[1]) + (part8[2] + part8[3])) + ((part8[4] + part8[5]) + (part8[6] + part8[7]));
+    const int m_rows = gridDim.y * 32, ldp = blockDim.y * 32;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int n = i0 + (i & 3) + 8 * (i >> 2) + 4 * hh;
+        part[((size_t)blockIdx.x * m_rows + n) * ldp + j0 + r] = acc[i];
+    }
+}
+
+// dst[r][dst_col0 + c] = sum over chunks of part[chunk][src_row0 + r][src_col0 + c], in chunk order, in double
+__global__ void k_ppo_reduce(const float *__restrict__ part, int chunks, int m_rows, int ldp, int src_row0, int src_col0,
+                             float *__restrict__ dst, int dst_ld, int dst_col0, int rows, int cols)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= rows * cols) return;
+    const int r = e / cols, c = e - r * cols;
+    const float *p = part + (size_t)(src_row0 + r) * ldp + src_col0 + c;
+    double s = 0.0;
+    for (int ch = 0; ch < chunks; ++ch) s += (double)p[(size_t)ch * m_rows * ldp];
+    dst[(size_t)r * dst_ld + dst_col0 + c] = (float)s;
+}
+
+// ---- the padded weight images
+__device__ __forceinline__ float img_square(const float *w, const float *b, int h, int r, int c, bool one)
+{
+    if (r < h) return c < h ? w[(size_t)r * h + c] : c == h ? b[r] : 0.f;
+    return one && r == h && c == h ? 1.f : 0.f;
+}
+__device__ __forceinline__ float img_transposed(const float *w, int ld, int col0, int h, int r, int c)
+{
+    return r < h && c < h ? w[(size_t)c * ld + col0 + r] : 0.f;
+}
+
+__global__ void k_ppo_prep(PpoNet n)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x, which = blockIdx.y;
+    const int h = n.h, HP = n.HP;
+    const int ld = which == PPO_I_W1 ? 16 : which == PPO_I_WC ? n.KC : (which == PPO_T_HA || which == PPO_T_HV) ? 32 : HP;
+    const int n_rows = (which == PPO_I_HA || which == PPO_I_HV) ? 32 : HP;
+    if (e >= n_rows * ld) return;
+    const int r = e / ld, c = e - r * ld;
+    auto T = [&](int t) { return n.param + n.off[t]; };
+    float v = 0.f;
+    switch (which) {
+    case PPO_I_W1:
+        if (r < h) v = c < n.K1 ? T(PPO_ZONE_W1)[(size_t)r * n.K1 + c] : c == 15 ? T(PPO_ZONE_B1)[r] : 0.f;
+        else v = r == h && c == 15 ? 1.f : 0.f;
+        break;
+    case PPO_I_W2: v = img_square(T(PPO_ZONE_W2), T(PPO_ZONE_B2), h, r, c, false); break;
+    case PPO_I_W3: v = img_square(T(PPO_ZONE_W3), T(PPO_ZONE_B3), h, r, c, true); break;
+    case PPO_I_WC:
+        if (r < h) {
+            const float *w = T(PPO_COMB_W) + (size_t)r * (8 + h);      // combine_net_'s input is [obs, zone_emb]
+            v = c < h ? w[8 + c] : c == h ? T(PPO_COMB_B)[r] : (c >= HP && c < HP + 8) ? w[c - HP] : 0.f;
+        } else {
+            v = r == h && c == h ? 1.f : 0.f;
+        }
+        break;
+    case PPO_I_WE: v = img_square(T(PPO_ENC_W), T(PPO_ENC_B), h, r, c, true); break;
+    case PPO_I_WV: v = img_square(T(PPO_CRITIC_W1), T(PPO_CRITIC_B1), h, r, c, true); break;
+    case PPO_I_HA:
+        if (r < 4 && c <= h) {
+            const float *w = T(r < 2 ? PPO_MU_W : PPO_STD_W), *b = T(r < 2 ? PPO_MU_B : PPO_STD_B);
+            v = c < h ? w[(size_t)(r & 1) * h + c] : b[r & 1];
+        }
+        break;
+    case PPO_I_HV:
+        if (c <= h && (r == 4 || (r == 5 && n.dist))) {
+            const float *w = T(r == 4 ? PPO_CRITIC_W2 : PPO_SIGMA_W), *b = T(r == 4 ? PPO_CRITIC_B2 : PPO_SIGMA_B);
+            v = c < h ? w[c] : b[0];
+        }
+        break;
+    case PPO_T_W2: v = img_transposed(T(PPO_ZONE_W2), h, 0, h, r, c); break;
+    case PPO_T_W3: v = img_transposed(T(PPO_ZONE_W3), h, 0, h, r, c); break;
+    case PPO_T_WC: v = img_transposed(T(PPO_COMB_W), 8 + h, 8, h, r, c); break;
+    case PPO_T_WE: v = img_transposed(T(PPO_ENC_W), h, 0, h, r, c); break;
+    case PPO_T_WV: v = img_transposed(T(PPO_CRITIC_W1), h, 0, h, r, c); break;
+    case PPO_T_HA:
+        if (r < h && c < 4) v = T(c < 2 ? PPO_MU_W : PPO_STD_W)[(size_t)(c & 1) * h + r];
+        break;
+    case PPO_T_HV:
+        if (r < h && (c == 4 || (c == 5 && n.dist))) v = T(c == 4 ? PPO_CRITIC_W2 : PPO_SIGMA_W)[r];
+        break;
+    default: break;
+    }
+    n.img[which][e] = v;
+}
+
+// ---- the per-sample pieces between the products
+// P = the mean of a sample's zone rows (its column h: the constant), the obs columns of combine_net_'s input; rows from
+// `count` on are zero.  Thread (b, f), f < KC.
+__global__ void k_ppo_pool(PpoNet n, Gather g, int bp)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= bp * n.KC) return;
+    const int b = e / n.KC, f = e - b * n.KC;
+    size_t slot = 0;
+    const bool ok = sample_slot(g, b, slot);
+    if (f == 0 && b < g.count && !ok) *n.bad_index = 1;
+    if (f >= n.HP) {
+        n.CI[(size_t)b * n.KC + f] = ok ? g.obs[slot * 8 + (f - n.HP)] : 0.f;
+        return;
+    }
+    float v = 0.f;
+    if (ok && f < n.h) {
+        const float *a = n.A2 + (size_t)b * g.Z * n.HP + f;
+        float s = 0.f;
+        for (int z = 0; z < g.Z; ++z) s += a[(size_t)z * n.HP];
+        v = s / (float)g.Z;                       // .sum(dim=1) / n_zones (env_model.py:77)
+    } else if (ok && f == n.h) {
+        v = 1.f;
+    }
+    n.P[(size_t)b * n.HP + f] = v;
+}
+
+// dZ2[row][f] = dP[sample][f] / Z where relu(zone_net_.2) was positive, in place over A2
+__global__ void k_ppo_spread(PpoNet n, int Z, int rows)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    const int quads = n.HP / 4;
+    if (e >= rows * quads) return;
+    const int row = e / quads, q = e - row * quads;
+    float4 *ap = reinterpret_cast<float4 *>(n.A2 + (size_t)row * n.HP) + q;
+    const float4 a = *ap;
+    const float4 d = reinterpret_cast<const float4 *>(n.P + (size_t)(row / Z) * n.HP)[q];
+    const float fz = (float)Z;
+    *ap = make_float4(a.x > 0.f ? d.x / fz : 0.f, a.y > 0.f ? d.y / fz : 0.f, a.z > 0.f ? d.z / fz : 0.f,
+                      a.w > 0.f ? d.w / fz : 0.f);
+}
+
+__device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+// The loss of one sample (ppo.py:70-89) and its derivative with respect to the six head pre-activations
+// (PRE: mu_ 0-1, std_ 2-3, critic.2 / critic_mu 4, critic_sigma 5), scaled by the means' 1 / count.
+__global__ void k_ppo_loss(PpoNet n, PpoExp x, Gather g, int bp)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= bp) return;
+    float d[6] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f }, ss[8] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
+    size_t slot = 0;
+    if (sample_slot(g, b, slot)) {
+        const float *pre = n.PRE + (size_t)b * 32;
+        const PpoHyper &hy = n.hyper;
+        const float inv_b = 1.0f / (float)g.count;
+        const float adv = x.advantage[slot], ret = x.returnn[slot];
+        float mu[2], sd[2], smu[2], ssd[2], diff[2], dlp = 0.f, ent = 0.f;
+#pragma unroll
+        for (int o = 0; o < 2; ++o) {
+            smu[o] = sigmoidf(pre[o]);
+            ssd[o] = sigmoidf(pre[2 + o]);
+            mu[o] = 2.0f * (smu[o] - 0.5f);                   // policy_network.py:46-47
+            sd[o] = ssd[o] + 1e-3f;
+            diff[o] = x.action[slot * 2 + o] - mu[o];
+            // Normal.log_prob: -(a - mu)^2 / (2 var) - log(std) - log(sqrt(2 pi))
+            const float lp = -(diff[o] * diff[o]) / (2.0f * (sd[o] * sd[o])) - logf(sd[o]) - 0.9189385332046727f;
+            dlp += lp - x.log_prob[slot * 2 + o];
+            ent += 0.5f + 0.9189385332046727f + logf(sd[o]);  // Normal.entropy
+        }
+        const float ratio = expf(dlp);
+        const float lo = 1.0f - hy.clip_eps, hi = 1.0f + hy.clip_eps;
+        const float surr1 = ratio * adv, surr2 = fminf(fmaxf(ratio, lo), hi) * adv;
+        // d min(surr1, surr2) / d ratio: adv on the unclipped branch, adv inside the clamp's range, 0 outside
+        const float through = surr1 <= surr2 ? 1.0f : (ratio >= lo && ratio <= hi) ? 1.0f : 0.f;
+        const float g_lp = -adv * inv_b * through * ratio;    // d loss / d log_prob(a_o), the same for both o
+#pragma unroll
+        for (int o = 0; o < 2; ++o) {
+            const float var = sd[o] * sd[o];
+            const float g_mu = g_lp * (diff[o] / var);
+            const float g_sd = g_lp * ((diff[o] * diff[o]) / (var * sd[o]) - 1.0f / sd[o])
+                               - hy.entropy_coef * (0.5f * inv_b) / sd[o];          // the entropy's mean is over B x 2
+            d[o] = g_mu * 2.0f * smu[o] * (1.0f - smu[o]);
+            d[2 + o] = g_sd * ssd[o] * (1.0f - ssd[o]);
+        }
+        const float v = pre[4];
+        float vloss, vsig = 0.f;
+        if (n.dist) {
+            const float bx = 0.3f * pre[5];                   // Softplus(beta = 0.3), threshold 20 (flat_model.py:28,62)
+            const float sp = bx > 20.0f ? pre[5] : log1pf(expf(bx)) / 0.3f;
+            const float dsp = bx > 20.0f ? 1.0f : sigmoidf(bx);
+            vsig = sp + 1e-3f;
+            const float dr = ret - v, var = vsig * vsig;
+            vloss = (dr * dr) / (2.0f * var) + logf(vsig) + 0.9189385332046727f;    // -Normal(v, sigma).log_prob(returnn)
+            const float w = hy.value_loss_coef * inv_b;
+            d[4] = w * (-dr / var);
+            d[5] = w * (-(dr * dr) / (var * vsig) + 1.0f / vsig) * dsp;
+        } else {
+            const float old = x.value[slot];
+            const float dv = v - old;
+            const float vc = old + fminf(fmaxf(dv, -hy.clip_eps), hy.clip_eps);
+            const float s1 = (v - ret) * (v - ret), s2 = (vc - ret) * (vc - ret);
+            vloss = fmaxf(s1, s2);
+            const bool inside = dv >= -hy.clip_eps && dv <= hy.clip_eps;
+            const float dl = s1 >= s2 ? 2.0f * (v - ret) : inside ? 2.0f * (vc - ret) : 0.f;
+            d[4] = hy.value_loss_coef * inv_b * dl;
+        }
+        ss[0] = ent;
+        ss[1] = v;
+        ss[2] = vsig;
+        ss[3] = -fminf(surr1, surr2);
+        ss[4] = vloss;
+    }
+    float *dh = n.DH + (size_t)b * 32;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) dh[i] = i < 6 ? d[i] : 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) n.SS[(size_t)b * 8 + i] = ss[i];
+}
+
+// a block's fixed-order sum: every thread's double, then a tree over LDS
+__device__ __forceinline__ double block_sum_256(double v, double *sh)
+{
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    const double out = sh[0];
+    __syncthreads();
+    return out;
+}
+
+// stats[0..4] = the minibatch means of the per-sample terms; one block of 256 threads, thread i adds samples i, i + 256 ...
+__global__ __launch_bounds__(256) void k_ppo_stats(const float *__restrict__ SS, int count, float *__restrict__ stats)
+{
+    __shared__ double sh[256];
+    for (int k = 0; k < 5; ++k) {
+        double s = 0.0;
+        for (int b = threadIdx.x; b < count; b += 256) s += (double)SS[(size_t)b * 8 + k];
+        s = block_sum_256(s, sh);
+        if (threadIdx.x == 0) stats[k] = (float)(s / (k == 0 ? 2.0 * count : (double)count));
+    }
+}
+
+// the gradient norm: a partial per kPpoNormBlock elements, then their sum in order
+__global__ __launch_bounds__(256) void k_ppo_sumsq(const float *__restrict__ grad, int64_t n, double *__restrict__ part)
+{
+    __shared__ double sh[256];
+    const int64_t base = (int64_t)blockIdx.x * kPpoNormBlock;
+    double s = 0.0;
+    for (int i = threadIdx.x; i < kPpoNormBlock; i += 256) {
+        const int64_t e = base + i;
+        if (e < n) {
+            const double v = (double)grad[e];
+            s += v * v;
+        }
+    }
+    s = block_sum_256(s, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+__global__ void k_ppo_norm(const double *__restrict__ part, int n_parts, float *__restrict__ norm, float *__restrict__ stat)
+{
+    double s = 0.0;
+    for (int i = 0; i < n_parts; ++i) s += part[i];
+    const float v = (float)sqrt(s);
+    *norm = v;
+    if (stat) *stat = v;
+}
+
+// clip_grad_norm_ and torch.optim.Adam's single-tensor step (betas 0.9 / 0.999, no weight decay, no amsgrad); the
+// arenas' padding holds zeros and stays zero
+__global__ void k_ppo_adam(PpoNet n, float step_size, float bc2_sqrt)
+{
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n.arena) return;
+    const float clip = fminf(n.hyper.max_grad_norm / (n.scalars[0] + 1e-6f), 1.0f);
+    const float gr = n.grad[e] * clip;
+    const float b2 = 0.999f;
+    const float w1 = (float)(1.0 - 0.9), w2 = (float)(1.0 - 0.999);
+    float m = n.exp_avg[e], v = n.exp_avg_sq[e];
+    m = m + w1 * (gr - m);                        // exp_avg.lerp_(grad, 1 - beta1)
+    v = v * b2 + (w2 * gr) * gr;                  // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
+    const float denom = sqrtf(v) / bc2_sqrt + n.hyper.adam_eps;
+    n.param[e] = n.param[e] + ((-step_size) * m) / denom;        // param.addcdiv_(exp_avg, denom, value = -step_size)
+    n.exp_avg[e] = m;
+    n.exp_avg_sq[e] = v;
+}
+
+Gather no_gather() { return Gather{ nullptr, nullptr, nullptr, 0, 1, 1, 1, 0 }; }
+
+template <int MODE>
+void nt(const float *A, int lda, const float *B, int ldb, int K, float *D, int ldd, int rows, int m_tiles,
+        hipStream_t s)
+{
+    hipLaunchKernelGGL((k_ppo_nt<MODE, false>), dim3(rows / 32), dim3(64, m_tiles), 0, s, A, lda, B, ldb, K, D, ldd,
+                       no_gather());
+}
+
+void tn(const float *A, int lda, int m_tiles, const float *B, int ldb, int nB, int rows, float *part, hipStream_t s)
+{
+    const int chunks = (rows + kPpoChunk - 1) / kPpoChunk;
+    hipLaunchKernelGGL((k_ppo_tn<false>), dim3(chunks, m_tiles), dim3(64, (nB + 31) / 32), 0, s, A, lda, B, ldb, nB, rows,
+                       part, no_gather());
+}
+
+// one piece of a weight gradient out of the partials of the last tn(): rows x cols from (src_row0, src_col0)
+void reduce(const PpoNet &n, int rows_reduced, int m_tiles, int nB, int src_row0, int src_col0, int tensor, int dst_ld,
+            int dst_col0, int rows, int cols, hipStream_t s)
+{
+    const int chunks = (rows_reduced + kPpoChunk - 1) / kPpoChunk;
+    const int total = rows * cols;
+    hipLaunchKernelGGL(k_ppo_reduce, dim3((total + 255) / 256), dim3(256), 0, s, n.partial, chunks, m_tiles * 32,
+                       ((nB + 31) / 32) * 32, src_row0, src_col0, n.grad + n.off[tensor], dst_ld, dst_col0, rows, cols);
+}
+
+void launch_norm(const PpoNet &n, float *stat, hipStream_t s)
+{
+    const int parts = (int)((n.arena + kPpoNormBlock - 1) / kPpoNormBlock);
+    hipLaunchKernelGGL(k_ppo_sumsq, dim3(parts), dim3(256), 0, s, n.grad, n.arena, n.norm_partial);
+    hipLaunchKernelGGL(k_ppo_norm, dim3(1), dim3(1), 0, s, n.norm_partial, parts, n.scalars, stat);
+}
+
+}  // namespace
+
+hipError_t launch_ppo_minibatch(const PpoNet &n, const PpoExp &x, const int32_t *idx, int count, float *stats,
+                                hipStream_t s)
+{
+    const int h = n.h, HP = n.HP, KC = n.KC, NT = HP / 32;
+    const int rp = (count * n.Z + 31) / 32 * 32, bp = (count + 31) / 32 * 32;
+    const Gather g{ x.obs, x.zone_obs, idx, count, x.N, x.T, n.Z, n.F };
+    float *const *I = n.img;
+    hipLaunchKernelGGL(k_ppo_prep, dim3((HP * KC + 255) / 256, PPO_N_IMAGES), dim3(256), 0, s, n);
+    // ---- forward
+    hipLaunchKernelGGL((k_ppo_nt<NT_RELU, true>), dim3(rp / 32), dim3(64, NT), 0, s, I[PPO_I_W1], 16, nullptr, 0, 16, n.A1,
+                       HP, g);                                                            // relu(zone_net_.0)
+    nt<NT_RELU>(I[PPO_I_W2], HP, n.A1, HP, HP, n.A2, HP, rp, NT, s);                      // relu(zone_net_.2)
+    hipLaunchKernelGGL(k_ppo_pool, dim3((bp * KC + 255) / 256), dim3(256), 0, s, n, g, bp);
+    nt<NT_STORE>(I[PPO_I_W3], HP, n.P, HP, HP, n.CI, KC, bp, NT, s);                      // zone_net_.4 of the mean
+    nt<NT_STORE>(I[PPO_I_WC], KC, n.CI, KC, KC, n.C, HP, bp, NT, s);                      // combine_net_
+    nt<NT_RELU>(I[PPO_I_WE], HP, n.C, HP, HP, n.Ha, HP, bp, NT, s);                       // relu(actor.enc_)
+    nt<NT_RELU>(I[PPO_I_WV], HP, n.C, HP, HP, n.Hc, HP, bp, NT, s);                       // relu(critic.0)
+    nt<NT_STORE>(I[PPO_I_HA], HP, n.Ha, HP, HP, n.PRE, 32, bp, 1, s);                     // mu_, std_
+    nt<NT_ADD>(I[PPO_I_HV], HP, n.Hc, HP, HP, n.PRE, 32, bp, 1, s);                       // critic.2 / critic_mu, critic_sigma
+    hipLaunchKernelGGL(k_ppo_loss, dim3((bp + 63) / 64), dim3(64), 0, s, n, x, g, bp);
+    hipLaunchKernelGGL(k_ppo_stats, dim3(1), dim3(256), 0, s, n.SS, count, stats);
+    // ---- backward: every weight gradient is taken before its layer's activations are overwritten by deltas
+    tn(n.DH, 32, 1, n.Ha, HP, HP, bp, n.partial, s);
+    reduce(n, bp, 1, HP, 0, 0, PPO_MU_W, h, 0, 2, h, s);
+    reduce(n, bp, 1, HP, 0, h, PPO_MU_B, 1, 0, 2, 1, s);
+    reduce(n, bp, 1, HP, 2, 0, PPO_STD_W, h, 0, 2, h, s);
+    reduce(n, bp, 1, HP, 2, h, PPO_STD_B, 1, 0, 2, 1, s);
+    tn(n.DH, 32, 1, n.Hc, HP, HP, bp, n.partial, s);
+    reduce(n, bp, 1, HP, 4, 0, PPO_CRITIC_W2, h, 0, 1, h, s);
+    reduce(n, bp, 1, HP, 4, h, PPO_CRITIC_B2, 1, 0, 1, 1, s);
+    if (n.dist) {
+        reduce(n, bp, 1, HP, 5, 0, PPO_SIGMA_W, h, 0, 1, h, s);
+        reduce(n, bp, 1, HP, 5, h, PPO_SIGMA_B, 1, 0, 1, 1, s);
+    }
+    nt<NT_MASK>(I[PPO_T_HA], 32, n.DH, 32, 32, n.Ha, HP, bp, NT, s);                      // delta of actor.enc_
+    nt<NT_MASK>(I[PPO_T_HV], 32, n.DH, 32, 32, n.Hc, HP, bp, NT, s);                      // delta of critic.0
+    tn(n.Ha, HP, NT, n.C, HP, HP, bp, n.partial, s);
+    reduce(n, bp, NT, HP, 0, 0, PPO_ENC_W, h, 0, h, h, s);
+    reduce(n, bp, NT, HP, 0, h, PPO_ENC_B, 1, 0, h, 1, s);
+    tn(n.Hc, HP, NT, n.C, HP, HP, bp, n.partial, s);
+    reduce(n, bp, NT, HP, 0, 0, PPO_CRITIC_W1, h, 0, h, h, s);
+    reduce(n, bp, NT, HP, 0, h, PPO_CRITIC_B1, 1, 0, h, 1, s);
+    nt<NT_STORE>(I[PPO_T_WE], HP, n.Ha, HP, HP, n.C, HP, bp, NT, s);                      // delta of the embedding ...
+    nt<NT_ADD>(I[PPO_T_WV], HP, n.Hc, HP, HP, n.C, HP, bp, NT, s);                        // ... from both heads
+    tn(n.C, HP, NT, n.CI, KC, KC, bp, n.partial, s);
+    reduce(n, bp, NT, KC, 0, 0, PPO_COMB_W, 8 + h, 8, h, h, s);
+    reduce(n, bp, NT, KC, 0, HP, PPO_COMB_W, 8 + h, 0, h, 8, s);
+    reduce(n, bp, NT, KC, 0, h, PPO_COMB_B, 1, 0, h, 1, s);
+    nt<NT_STORE>(I[PPO_T_WC], HP, n.C, HP, HP, n.CI, KC, bp, NT, s);                      // delta of zone_net_.4's output
+    tn(n.CI, KC, NT, n.P, HP, HP, bp, n.partial, s);
+    reduce(n, bp, NT, HP, 0, 0, PPO_ZONE_W3, h, 0, h, h, s);
+    reduce(n, bp, NT, HP, 0, h, PPO_ZONE_B3, 1, 0, h, 1, s);
+    nt<NT_STORE>(I[PPO_T_W3], HP, n.CI, KC, HP, n.P, HP, bp, NT, s);                      // delta of the mean
+    hipLaunchKernelGGL(k_ppo_spread, dim3((rp * (HP / 4) + 255) / 256), dim3(256), 0, s, n, n.Z, rp);
+    tn(n.A2, HP, NT, n.A1, HP, HP, rp, n.partial, s);
+    reduce(n, rp, NT, HP, 0, 0, PPO_ZONE_W2, h, 0, h, h, s);
+    reduce(n, rp, NT, HP, 0, h, PPO_ZONE_B2, 1, 0, h, 1, s);
+    nt<NT_MASK>(I[PPO_T_W2], HP, n.A2, HP, HP, n.A1, HP, rp, NT, s);                      // delta of zone_net_.0
+    {
+        const int chunks = (rp + kPpoChunk - 1) / kPpoChunk;
+        hipLaunchKernelGGL((k_ppo_tn<true>), dim3(chunks, NT), dim3(64, 1), 0, s, n.A1, HP, nullptr, 0, 16, rp, n.partial,
+                           g);
+    }
+    reduce(n, rp, NT, 16, 0, 0, PPO_ZONE_W1, n.K1, 0, h, n.K1, s);
+    reduce(n, rp, NT, 16, 0, 15, PPO_ZONE_B1, 1, 0, h, 1, s);
+    launch_norm(n, stats + 5, s);
+    return hipGetLastError();
+}
+
+hipError_t launch_ppo_apply(const PpoNet &n, float step_size, float bc2_sqrt, hipStream_t s)
+{
+    launch_norm(n, nullptr, s);
+    hipLaunchKernelGGL(k_ppo_adam, dim3((unsigned)((n.arena + 255) / 256)), dim3(256), 0, s, n, step_size, bc2_sqrt);
+    return hipGetLastError();
+}
+
+}  // namespace zenvk

@@ -1,0 +1,64 @@
+// ppo_update.hpp -- the flat actor-critic's PPO update on the device (ppo_update.hip): what zenv_train.cpp hands to
+// the launches.  Internal: not installed.
+#pragma once
+#include <hip/hip_runtime_api.h>
+
+#include <cstdint>
+
+namespace zenvk {
+
+// the tensors of the parameter arena, in zenv_mlp_weights' member order
+enum {
+    PPO_ZONE_W1 = 0, PPO_ZONE_B1, PPO_ZONE_W2, PPO_ZONE_B2, PPO_ZONE_W3, PPO_ZONE_B3, PPO_COMB_W, PPO_COMB_B,
+    PPO_ENC_W, PPO_ENC_B, PPO_MU_W, PPO_MU_B, PPO_STD_W, PPO_STD_B, PPO_CRITIC_W1, PPO_CRITIC_B1, PPO_CRITIC_W2,
+    PPO_CRITIC_B2, PPO_SIGMA_W, PPO_SIGMA_B, PPO_MAX_TENSORS
+};
+// the padded weight images k_ppo_prep rebuilds from the arena before every minibatch (I_*: [out][in] with the bias in
+// column h, the A operand of a forward product; T_*: the transpose, the A operand of a backward-data product)
+enum {
+    PPO_I_W1 = 0, PPO_I_W2, PPO_I_W3, PPO_I_WC, PPO_I_WE, PPO_I_WV, PPO_I_HA, PPO_I_HV,
+    PPO_T_W2, PPO_T_W3, PPO_T_WC, PPO_T_WE, PPO_T_WV, PPO_T_HA, PPO_T_HV, PPO_N_IMAGES
+};
+constexpr int kPpoChunk = 256;      // rows one wave reduces into one partial of a weight gradient
+constexpr int kPpoStats = 6;        // entropy, value, value std, policy loss, value loss, gradient norm
+constexpr int kPpoNormBlock = 4096; // arena elements per partial of the gradient norm
+
+struct PpoHyper {
+    float lr, adam_eps, clip_eps, entropy_coef, value_loss_coef, max_grad_norm;
+};
+
+struct PpoNet {
+    int h, HP, F, Z, K1, KC, dist, n_tensors;
+    int64_t off[PPO_MAX_TENSORS], count[PPO_MAX_TENSORS];   // floats, within an arena
+    int64_t arena;                                          // floats of one arena (a multiple of 64)
+    float *param, *grad, *exp_avg, *exp_avg_sq;
+    float *img[PPO_N_IMAGES];
+    // activation workspace for max_batch samples; the backward pass overwrites every activation with its delta
+    int max_batch;
+    float *A1, *A2;          // [rows][HP], rows = samples x Z rounded up to 32
+    float *P, *C, *Ha, *Hc;  // [samples][HP], samples rounded up to 32
+    float *CI;               // [samples][KC]: zone_net_.4's output (HP columns), then the 8 obs features
+    float *PRE, *DH;         // [samples][32]: the six head pre-activations, their deltas
+    float *SS;               // [samples][8]: the per-sample terms of the statistics
+    float *partial;          // the per-chunk partials of one weight gradient
+    double *norm_partial;    // [arena / kPpoNormBlock + 1]
+    float *scalars;          // [0] the gradient norm of the last launch_ppo_norm
+    int *bad_index;          // page-locked host word: a device index outside [0, N T) was met (and dropped)
+    PpoHyper hyper;
+};
+
+// the handle's experience buffers (time-major) a minibatch is gathered from
+struct PpoExp {
+    const float *obs, *zone_obs, *action, *log_prob, *value, *advantage, *returnn;
+    int N, T;
+};
+
+// forward, loss and backward of the samples idx[0 .. count) (device memory): gradients into net.grad, the six
+// statistics into stats (device memory)
+hipError_t launch_ppo_minibatch(const PpoNet &net, const PpoExp &exp, const int32_t *idx, int count, float *stats,
+                                hipStream_t stream);
+// the clip and Adam step on net.grad; step_size = lr / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t), formed on the
+// host in double as torch forms them
+hipError_t launch_ppo_apply(const PpoNet &net, float step_size, float bc2_sqrt, hipStream_t stream);
+
+}  // namespace zenvk

@@ -80,6 +80,7 @@ public:
 // range; every entry point that waits for the device looks at it once the stream has drained
 int mlp_range_check(zenv *h)
 {
+    if (int rc = ppo_index_check(h)) return rc;
     if (!h->mlp_range_flag || !*(volatile int *)h->mlp_range_flag) return ZENV_OK;
     *(volatile int *)h->mlp_range_flag = 0;
     return fail(ZENV_E_RANGE, "an input or activation of the network reached 65 520, beyond float16 (ZENV_MLP_F16: or an "

@@ -245,6 +245,11 @@ FieldInfo field_info(const zenv *h, int field)
     case ZENV_F_HI_GOAL: return { h->xc.hi_goal, h->hi_kind == 3 ? h->hi_m * 2 * 4 : 0 };
     case ZENV_F_LO_GOAL_DIST: return { h->xc.dist, h->xc_mem ? N * h->xc.T * 4 : 0 };
     case ZENV_F_XY_BOOTSTRAP_GOAL: return { h->xc.boot, h->xc_mem ? N * 2 * 4 : 0 };
+    case ZENV_F_PPO_STATS: {
+        int64_t bytes = 0;
+        void *ptr = ppo_stats(h, &bytes);
+        return { ptr, bytes };
+    }
     default: return { nullptr, 0 };
     }
 }
@@ -529,6 +534,7 @@ extern "C" int zenv_destroy(zenv_t *h)
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->comm) (void)zenv_comm_destroy(h);
+    ppo_free(h);
     if (h->host_io_actions) h->p.actions = h->dev_actions;       // the slot below is the device buffer again
     for (Alloc &a : h->allocs)
         if (*a.slot && a.slab_off < 0) (void)hipFree(*a.slot);

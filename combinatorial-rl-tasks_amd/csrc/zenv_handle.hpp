@@ -1,5 +1,6 @@
 // zenv_handle.hpp -- the handle behind zenv_t and the helpers every translation unit of the C ABI uses (zenv_api.cpp:
-// the environment; zenv_agents.cpp: the networks, the per-step policies, the collectors).  Internal: not installed.
+// the environment; zenv_agents.cpp: the networks, the per-step policies, the collectors; zenv_train.cpp: the flat
+// actor-critic's learner).  Internal: not installed.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>   // types and prototypes only: librccl is dlopen()ed by the first zenv_comm_* call
@@ -38,6 +39,8 @@ struct Alloc {
     bool is_state;   // part of zenv_get_state/zenv_set_state
     int64_t slab_off = -1;   // >= 0: lives at this offset of the handle's results slab (one hipMalloc, one download)
 };
+
+struct PpoState;   // zenv_train.cpp
 
 struct zenv {
     zenv_config cfg{};
@@ -145,6 +148,8 @@ struct zenv {
         float *diversity = nullptr, *env_reward = nullptr;
     } sk;
     void *sk_mem = nullptr;
+    // the flat actor-critic's learner (zenv_ppo_init): arenas, workspace, Adam's step count
+    PpoState *ppo = nullptr;
     // goal-conditioned variant (zenv_goal_enable)
     bool goal_enabled = false;
     bool order_enabled = false;   // solver-ordered variant (zenv_order_enable)
@@ -198,3 +203,10 @@ ZENV_INTERNAL int run_policy(zenv *h, const StepPolicy &pol, const MlpRecord *re
 ZENV_INTERNAL int ring_guard(const zenv *h, int steps, int auto_reset_every_step);
 // ZENV_E_RANGE once the float16 network kernels have flagged an operand out of range
 ZENV_INTERNAL int mlp_range_check(zenv *h);
+
+// ---- zenv_train.cpp
+ZENV_INTERNAL void ppo_free(zenv *h);
+// ZENV_E_ARG once an update has met (and dropped) a device-resident index out of range; mlp_range_check() asks
+ZENV_INTERNAL int ppo_index_check(zenv *h);
+// ZENV_F_PPO_STATS: the buffer and the bytes the last update call filled
+ZENV_INTERNAL void *ppo_stats(const zenv *h, int64_t *bytes);

@@ -102,6 +102,90 @@ class TorchZoneEnv:
         raw = self._alias_layout(self.env._experience_rows(frames_per_proc))
         return {name: t.transpose(0, 1) for name, t in raw.items()}     # [N, T, ...] views of time-major memory
 
+    # ------------------------------------------------------------------ the flat actor-critic's PPO update
+    def _alias_ptr(self, ptr, shape, dtype=np.float32):
+        t = self._torch.as_tensor(_DeviceView(ptr, shape, dtype), device=self.device)
+        assert t.data_ptr() == ptr, "torch copied instead of aliasing"
+        return t
+
+    def ppo_init(self, state_dict, **hyper):
+        """``ZoneVecEnv.ppo_init`` with the four arenas -- parameters, gradients, exp_avg, exp_avg_sq -- as flat float32
+        CUDA tensors ALIASING device memory in ``self.ppo_arenas`` (padding between the tensors included; valid until
+        the next ppo_init or ``env.close()``)."""
+        self.env.ppo_init(state_dict, **hyper)
+        with self._torch.cuda.device(self.device):
+            self.ppo_arenas = {}
+            for name, which in (("param", nat.PPO_PARAM), ("grad", nat.PPO_GRAD), ("exp_avg", nat.PPO_EXP_AVG),
+                                ("exp_avg_sq", nat.PPO_EXP_AVG_SQ)):
+                ptr, count = self.env.ppo_tensor_ptr(which, -1)
+                self.ppo_arenas[name] = self._alias_ptr(ptr, (count,))
+
+    def ppo_views(self, which=nat.PPO_PARAM):
+        """zenv_mlp_weights name -> CUDA tensor ALIASING that tensor of an arena, in its state_dict shape."""
+        from .vec_env import mlp_tensor_shapes
+        shapes = mlp_tensor_shapes(self.env._ppo_h, self.env.zone_feat)
+        with self._torch.cuda.device(self.device):
+            return {name: self._alias_ptr(self.env.ppo_tensor_ptr(which, i)[0], shapes[name])
+                    for i, name in enumerate(self.env._ppo_keys)}
+
+    def ppo_state_dict(self):
+        """The learner's parameters under ACModel's state_dict names, as CUDA tensors ALIASING the parameter arena:
+        ``model.load_state_dict(tenv.ppo_state_dict())`` copies them into a torch module on the shared stream."""
+        views = self.ppo_views()
+        return {key: views[name] for name, key in self.env._ppo_keys.items()}
+
+    def ppo_load_state_dict(self, state_dict):
+        """Overwrite the learner's parameters from an ACModel state_dict (tensors on any device), on the stream."""
+        for key, dst in self.ppo_state_dict().items():
+            dst.copy_(state_dict[key])
+
+    def ppo_optimizer_state(self):
+        """Adam's state in the shape of ``torch.optim.Adam.state_dict()`` (train_ppo.py:116-122): copies, parameter i
+        the i-th of ``ACModel.parameters()``."""
+        torch = self._torch
+        out = self.env.ppo_optimizer_state()
+        out["state"] = {i: {"step": torch.tensor(s["step"]), "exp_avg": torch.from_numpy(s["exp_avg"]).to(self.device),
+                            "exp_avg_sq": torch.from_numpy(s["exp_avg_sq"]).to(self.device)}
+                        for i, s in out["state"].items()}
+        return out
+
+    def ppo_load_optimizer_state(self, state):
+        self.env.ppo_load_optimizer_state(state)
+
+    def _ppo_index_arg(self, idx):
+        torch = self._torch
+        if isinstance(idx, torch.Tensor):
+            if not (idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous() and idx.device == self.device):
+                raise ValueError("device indices must be a contiguous int32 CUDA tensor on the env's device")
+            return idx.data_ptr(), idx.numel()
+        return idx, None
+
+    def ppo_minibatch(self, idx, apply=False):
+        """``ZoneVecEnv.ppo_minibatch``; idx may be an int32 CUDA tensor (never copied, checked on the device)."""
+        ptr, count = self._ppo_index_arg(idx)
+        self.env.ppo_minibatch(ptr, apply=apply, count=count)
+
+    def ppo_apply(self):
+        self.env.ppo_apply()
+
+    def ppo_epoch(self, order, batch_size):
+        """``ZoneVecEnv.ppo_epoch``; order may be an int32 CUDA tensor."""
+        ptr, count = self._ppo_index_arg(order)
+        self.env.ppo_epoch(ptr, batch_size, count=count)
+
+    def ppo_stats(self):
+        """float32 CUDA tensor [minibatches, 6] ALIASING the statistics of the last ppo_minibatch / ppo_epoch (not
+        synchronised)."""
+        rows = self.env.field_bytes(nat.F_PPO_STATS) // 24
+        with self._torch.cuda.device(self.device):
+            return self._alias(nat.F_PPO_STATS, (rows, 6), np.float32)
+
+    def ppo_publish(self, precision="auto"):
+        self.env.ppo_publish(precision=precision)
+
+    def ppo_update(self, epochs, batch_size, rng):
+        return self.env.ppo_update(epochs, batch_size, rng)
+
     def load_hier(self, hi_state_dict, lo_state_dict):
         """Put HighPolicyValueModel / LoPolicyValueModel state_dicts (zone-goals/src/hier_policy_value_models.py; torch
         tensors on any device) into the device agent that ``collect_hier`` runs -- after every update."""

@@ -20,7 +20,7 @@ from .agents import (_HIER_ENC, _HIER_CRITIC, HIER_HI_KEYS, HIER_LO_KEYS, SKILL_
                      skill_tensors_from_state_dicts, option_tensors_from_state_dicts, inverse_tensors_from_state_dict,
                      check_collect_hier_args, check_collect_skill_args, check_collect_option_args,
                      hier_experience_layout, skill_experience_layout, option_experience_layout, skill_num_frames,
-                     check_collect_xy_args, xy_experience_layout)
+                     check_collect_xy_args, xy_experience_layout, ppo_state_dict_keys, ppo_batch_indexes)
 
 _FIELD_DTYPES = {
     nat.F_OBS: np.float32, nat.F_ZONE_OBS: np.float32, nat.F_REWARD: np.float32,
@@ -42,8 +42,19 @@ _FIELD_DTYPES = {
     nat.F_LO_TERM_ACTION: np.float32, nat.F_LO_TERM_LOG_PROB: np.float32, nat.F_LO_OPTION_ENDED: np.uint8,
     nat.F_XY_GOAL: np.float32, nat.F_XY_GOAL_MU: np.float32, nat.F_XY_GOAL_STD: np.float32, nat.F_XY_VALUE: np.float32,
     nat.F_XY_GOAL_AGE: np.int32, nat.F_HI_GOAL: np.float32, nat.F_LO_GOAL_DIST: np.float32,
-    nat.F_XY_BOOTSTRAP_GOAL: np.float32,
+    nat.F_XY_BOOTSTRAP_GOAL: np.float32, nat.F_PPO_STATS: np.float32,
 }
+
+
+def _as_host_f32(v):
+    """A torch tensor (any device) or anything numpy takes -> numpy float32."""
+    return np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, np.float32)
+
+
+def ppo_logs(stats, distributional):
+    """The logs dict of update_parameters (ppo.py:137-153) from the [minibatches, 6] statistics of an epoch."""
+    mean = np.asarray(stats, np.float64).mean(axis=0)
+    return {name: float(mean[i]) for i, name in enumerate(nat.PPO_STATS) if distributional or name != "value_std"}
 
 
 def config_for_id(env_id, **overrides):
@@ -706,6 +717,149 @@ class ZoneVecEnv:
     def _experience_rows(self, frames_per_proc):
         """The same buffers as name -> (field id, shape in memory, dtype), the form of the agents' layouts."""
         return _lo_rows(self.num_envs, self.num_zones, self.zone_feat, int(frames_per_proc))
+
+    # ------------------------------------------------------------------ the flat actor-critic's PPO update
+    def ppo_init(self, state_dict_or_tensors, lr=0.001, adam_eps=1e-8, clip_eps=0.2, entropy_coef=0.01,
+                 value_loss_coef=0.5, max_grad_norm=0.5, max_batch=256, distributional_value=None):
+        """The learner of update_parameters (torch_ac/algos/ppo.py:30-155) on the device: float32 master parameters
+        from an ACModel state_dict (or the named tensors of ``mlp_tensors_from_state_dict``), their gradients and
+        Adam's two moments, and the workspace of minibatches up to max_batch samples.  The defaults are PPOAlgo's
+        (ppo.py:11-14).  distributional_value: None = whatever the tensors hold (critic_sigma).  Separate from
+        ``load_mlp``: ``ppo_publish`` hands the parameters to the acting network."""
+        d = state_dict_or_tensors
+        tensors = dict(d) if "zone_w1" in d else mlp_tensors_from_state_dict(d)
+        if distributional_value is None:
+            distributional_value = "critic_sigma_w" in tensors
+        h = int(np.asarray(tensors["zone_b1"]).shape[0])
+        w = nat.MlpWeights(h_dim=h, precision=nat.MLP_F32)
+        names = [n for n in nat.MLP_TENSORS + nat.MLP_CRITIC_TENSORS + nat.MLP_SIGMA_TENSORS if n in tensors]
+        keep = self._load_weights(w, names, tensors, mlp_tensor_shapes(h, self.zone_feat))   # alive across the call
+        pc = nat.PpoConfig(lr=lr, adam_eps=adam_eps, clip_eps=clip_eps, entropy_coef=entropy_coef,
+                           value_loss_coef=value_loss_coef, max_grad_norm=max_grad_norm, max_batch=int(max_batch),
+                           distributional_value=int(bool(distributional_value)))
+        check(lib().zenv_ppo_init(self._h, C.byref(w), C.byref(pc)))
+        del keep
+        self._ppo_h = h
+        self._ppo_keys = ppo_state_dict_keys(bool(distributional_value))
+        self._ppo_hyper = dict(lr=lr, adam_eps=adam_eps)
+        self.ppo_batch_num = 0          # PPOAlgo.batch_num (ppo.py:28)
+
+    def ppo_tensor_ptr(self, which, index):
+        """(device pointer, element count) of tensor `index` (arena order; -1: the whole arena) of arena `which`
+        (``_native.PPO_PARAM`` / ``PPO_GRAD`` / ``PPO_EXP_AVG`` / ``PPO_EXP_AVG_SQ``)."""
+        p, n = C.c_void_p(), C.c_int64()
+        check(lib().zenv_ppo_tensor(self._h, int(which), int(index), C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def ppo_tensors(self, which=nat.PPO_PARAM):
+        """Every tensor of an arena as a new host array, under its zenv_mlp_weights name."""
+        shapes = mlp_tensor_shapes(self._ppo_h, self.zone_feat)
+        out = {}
+        for i, name in enumerate(self._ppo_keys):
+            out[name] = a = np.empty(shapes[name], np.float32)
+            check(lib().zenv_ppo_read(self._h, int(which), i, a.ctypes.data))
+        return out
+
+    def ppo_set_tensors(self, tensors, which=nat.PPO_PARAM):
+        """Overwrite the tensors of an arena that `tensors` names (zenv_mlp_weights names)."""
+        shapes = mlp_tensor_shapes(self._ppo_h, self.zone_feat)
+        for i, name in enumerate(self._ppo_keys):
+            if name in tensors:
+                a = np.ascontiguousarray(tensors[name], np.float32)
+                if a.shape != shapes[name]:
+                    raise ValueError(f"{name}: shape {a.shape}, expected {shapes[name]}")
+                check(lib().zenv_ppo_write(self._h, int(which), i, a.ctypes.data))
+
+    def ppo_state_dict(self):
+        """The learner's parameters under the reference ACModel's state_dict names (host float32 copies)."""
+        t = self.ppo_tensors()
+        return {key: t[name] for name, key in self._ppo_keys.items()}
+
+    def ppo_load_state_dict(self, state_dict):
+        """Overwrite the learner's parameters from an ACModel state_dict (every key must be there)."""
+        self.ppo_set_tensors({name: _as_host_f32(state_dict[key]) for name, key in self._ppo_keys.items()})
+
+    def ppo_optimizer_state(self):
+        """Adam's state in the shape of ``torch.optim.Adam.state_dict()`` (train_ppo.py:116-122), host arrays: parameter
+        i is the i-th of ``ACModel.parameters()``."""
+        m, v = self.ppo_tensors(nat.PPO_EXP_AVG), self.ppo_tensors(nat.PPO_EXP_AVG_SQ)
+        step = self.ppo_get_step()
+        state = {i: {"step": float(step), "exp_avg": m[name], "exp_avg_sq": v[name]}
+                 for i, name in enumerate(self._ppo_keys)} if step else {}
+        group = {"lr": self._ppo_hyper["lr"], "betas": (0.9, 0.999), "eps": self._ppo_hyper["adam_eps"], "weight_decay": 0,
+                 "amsgrad": False, "params": list(range(len(self._ppo_keys)))}
+        return {"state": state, "param_groups": [group]}
+
+    def ppo_load_optimizer_state(self, state):
+        """Restore Adam's moments and step count from ``ppo_optimizer_state`` / ``torch.optim.Adam.state_dict()``."""
+        names = list(self._ppo_keys)
+        st = state["state"]
+        zeros = {n: np.zeros(s, np.float32) for n, s in mlp_tensor_shapes(self._ppo_h, self.zone_feat).items() if n in names}
+        self.ppo_set_tensors({n: _as_host_f32(st[i]["exp_avg"]) for i, n in enumerate(names)} if st else zeros,
+                             nat.PPO_EXP_AVG)
+        self.ppo_set_tensors({n: _as_host_f32(st[i]["exp_avg_sq"]) for i, n in enumerate(names)} if st else zeros,
+                             nat.PPO_EXP_AVG_SQ)
+        self.ppo_set_step(int(float(st[0]["step"])) if st else 0)
+
+    def ppo_get_step(self):
+        n = C.c_int64()
+        check(lib().zenv_ppo_get_step(self._h, C.byref(n)))
+        return n.value
+
+    def ppo_set_step(self, step):
+        check(lib().zenv_ppo_set_step(self._h, int(step)))
+
+    @staticmethod
+    def _ppo_indices(idx, count):
+        """(address, count, on_device, the array to keep alive) of a host int32 array or a device address."""
+        if isinstance(idx, (int, np.integer)):
+            return int(idx), int(count), 1, None
+        a = np.ascontiguousarray(idx, np.int32).reshape(-1)
+        return a.ctypes.data, a.size, 0, a
+
+    def ppo_minibatch(self, idx, apply=False, count=None):
+        """Forward, loss and backward on the samples idx (host int32 array, or a device address with count): the
+        gradients stay in their arena, the statistics in ``ppo_stats()[0]``; apply: the clip and Adam step too.
+        Index i is env i // T, frame i % T of the last collect.  Asynchronous."""
+        ptr, n, dev, keep = self._ppo_indices(idx, count)
+        check(lib().zenv_ppo_minibatch(self._h, C.c_void_p(ptr), n, dev, int(bool(apply))))
+
+    def ppo_apply(self):
+        """clip_grad_norm_ and one Adam step on whatever the gradient arena holds."""
+        check(lib().zenv_ppo_apply(self._h))
+
+    def ppo_epoch(self, order, batch_size, count=None):
+        """The minibatches order[k * batch_size : (k + 1) * batch_size] in sequence (the last one short), each with
+        its clip and Adam step; no host synchronisation.  ``ppo_stats()`` has a row per minibatch."""
+        ptr, n, dev, keep = self._ppo_indices(order, count)
+        check(lib().zenv_ppo_epoch(self._h, C.c_void_p(ptr), n, int(batch_size), dev))
+
+    def ppo_stats(self):
+        """float32 [minibatches, 6] of the last ppo_minibatch / ppo_epoch: ``_native.PPO_STATS`` names the columns
+        (ppo.py:93-100, :121).  Waits for the device."""
+        rows = lib().zenv_field_bytes(self._h, nat.F_PPO_STATS) // 24
+        out = np.empty((rows, 6), np.float32)
+        if rows:
+            check(lib().zenv_get(self._h, nat.F_PPO_STATS, out.ctypes.data, 0))
+        return out
+
+    def ppo_publish(self, precision="auto"):
+        """Hand the learner's parameters to the acting network: read them back (0.7 MB) and ``load_mlp`` them, so
+        the next collect acts with them.  One synchronisation per update."""
+        self.load_mlp(self.ppo_tensors(), precision=precision)
+
+    def ppo_update(self, epochs, batch_size, rng):
+        """update_parameters (ppo.py:30-155) on the experience of the last collect: `epochs` passes in the order of
+        ``ppo_batch_indexes`` (the permutation from the caller's numpy Generator, ``self.ppo_batch_num`` counting the
+        calls).  Returns the reference's logs: the means over the last epoch's minibatches (ppo.py:137-153)."""
+        T = lib().zenv_field_bytes(self._h, nat.F_EXP_VALUE) // (4 * self.num_envs)
+        if T < 1:
+            raise ZenvError(nat.E_STATE, "collect first: the handle holds no experience")
+        for _ in range(int(epochs)):
+            order = ppo_batch_indexes(self.num_envs * T, T, self.ppo_batch_num, rng)
+            self.ppo_batch_num += 1
+            self.ppo_epoch(order, batch_size)
+        return ppo_logs(self.ppo_stats(), "critic_sigma_w" in self._ppo_keys)
 
     # ------------------------------------------------------------------ Zone-goals training experience
     def collect_hier(self, frames_per_proc, policy_seed=1, env_index0=0, discount=0.99, gae_lambda=0.95):

@@ -8,6 +8,10 @@ torch_ac/algos/ppo.py:32-140, recurrence 1) with ``ParallelEnv`` + ``collect_exp
 into either.
 
     python examples/ppo_torch.py --env PointTSP-v0 --procs 4096 --frames-per-proc 64 --updates 20
+
+``--device-update`` (off by default) runs the update in the library's own HIP kernels instead (``ppo_init`` /
+``ppo_update`` / ``ppo_publish``: float32 forward, loss, backward, clip and Adam on the handle's experience buffers);
+the torch module then only provides the initial parameters and receives the trained ones at the end.
 """
 import argparse
 import os
@@ -92,7 +96,7 @@ def ppo_update(model, opt, exps, epochs, batch_size, clip_eps, entropy_coef, val
 
 def train(env_id="PointTSP-v0", procs=4096, frames_per_proc=64, updates=10, epochs=4, batch_size=16384, lr=3e-4,
           discount=0.99, gae_lambda=0.95, clip_eps=0.2, entropy_coef=0.003, value_loss_coef=0.5, max_grad_norm=0.5,
-          hidden=185, seed=1, log=print):
+          hidden=185, seed=1, log=print, device_update=False):
     torch.manual_seed(seed)
     dev = torch.device("cuda", 0)
     env = Z.ZoneVecEnv(env_id, procs)
@@ -104,13 +108,24 @@ def train(env_id="PointTSP-v0", procs=4096, frames_per_proc=64, updates=10, epoc
     opt = torch.optim.Adam(model.parameters(), lr, eps=1e-8)
     gen = torch.Generator(device=dev).manual_seed(seed)
     history = []
+    if device_update:
+        import numpy as np
+        rng = np.random.default_rng(seed)
+        tenv.ppo_init(model.state_dict(), lr=lr, adam_eps=1e-8, clip_eps=clip_eps, entropy_coef=entropy_coef,
+                      value_loss_coef=value_loss_coef, max_grad_norm=max_grad_norm, max_batch=batch_size)
+        tenv.ppo_publish()
     for u in range(updates):
         t0 = time.perf_counter()
-        tenv.load_state_dict(model.state_dict())
+        if not device_update:
+            tenv.load_state_dict(model.state_dict())
         exps = tenv.collect(frames_per_proc, policy_seed=seed * 1000003 + u, discount=discount, gae_lambda=gae_lambda)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
-        st = ppo_update(model, opt, exps, epochs, batch_size, clip_eps, entropy_coef, value_loss_coef, max_grad_norm, gen)
+        if device_update:
+            st = tenv.ppo_update(epochs, batch_size, rng)
+            tenv.ppo_publish()
+        else:
+            st = ppo_update(model, opt, exps, epochs, batch_size, clip_eps, entropy_coef, value_loss_coef, max_grad_norm, gen)
         torch.cuda.synchronize()
         t2 = time.perf_counter()
         frames = procs * frames_per_proc
@@ -118,6 +133,8 @@ def train(env_id="PointTSP-v0", procs=4096, frames_per_proc=64, updates=10, epoc
                   collect_fps=frames / (t1 - t0), update_fps=frames * epochs / (t2 - t1))
         history.append(st)
         log({k: (round(v, 4) if isinstance(v, float) else v) for k, v in st.items()})
+    if device_update:
+        model.load_state_dict(tenv.ppo_state_dict())
     env.close()
     return model, history
 
@@ -133,5 +150,7 @@ if __name__ == "__main__":
     ap.add_argument("--lr", type=float, default=3e-4)
     ap.add_argument("--hidden-size", type=int, default=185)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--device-update", action="store_true", help="run the update in the library's HIP kernels")
     a = ap.parse_args()
-    train(a.env, a.procs, a.frames_per_proc, a.updates, a.epochs, a.batch_size, a.lr, hidden=a.hidden_size, seed=a.seed)
+    train(a.env, a.procs, a.frames_per_proc, a.updates, a.epochs, a.batch_size, a.lr, hidden=a.hidden_size, seed=a.seed,
+          device_update=a.device_update)

@@ -168,7 +168,12 @@ enum {
     ZENV_F_HI_GOAL = 71,            /* float32 [M,2] the high level's recorded goal */
     ZENV_F_LO_GOAL_DIST = 72,       /* float32 [T,N] the distance of the goal from the robot (obs[1:3]) at every frame */
     ZENV_F_XY_BOOTSTRAP_GOAL = 73,  /* float32 [N,2] g' ~ the high level at obs_T: the goal of next_lo_value */
-    ZENV_F_COUNT = 74
+    /* the flat actor-critic's learner (zenv_ppo_init; before this field, ZENV_F_COUNT = 74): the statistics of the
+     * minibatches of the last zenv_ppo_minibatch (one row) or zenv_ppo_epoch; 0 bytes before the first */
+    ZENV_F_PPO_STATS = 74,          /* float32 [minibatches][6] entropy, value, value std (0 without the distributional
+                                     *               critic), policy loss, value loss, gradient norm before the clip: the
+                                     *               logs of ppo.py:93-100, :121 */
+    ZENV_F_COUNT = 75
 };
 
 /* scripted on-device action sources (the build's own; used by bench/tests) */
@@ -889,6 +894,53 @@ int zenv_collect_option(zenv_t *h, int frames_per_proc, uint64_t policy_seed, ui
  * a goal-conditioned or solver-ordered handle, more windows (T / L) than a ring schedule's depth. */
 int zenv_collect_xy(zenv_t *h, int frames_per_proc, uint64_t policy_seed, uint64_t env_index0, float discount,
                     float gae_lambda);
+
+/* ---- the flat actor-critic's PPO update on the device: update_parameters, main/src/torch_ac/algos/ppo.py:30-155 ----
+ * Forward, loss, backward, gradient-norm clip and Adam of ACModel (flat_model.py:21-68, both critics) in float32, on
+ * the samples of the handle's own ZENV_F_EXP_* buffers, recurrence 1.  Sample index i is env i / T, frame i % T: the
+ * reference's [N][T] flattening (base.py:212-227); the kernels read the time-major buffers in place.  The learner's
+ * parameters are separate from the acting network's: nothing here repacks zenv_mlp_load's images (read the parameters
+ * back and load them to act with them).  Every reduction runs in a fixed order: the same call from the same state
+ * gives the same bits.  The hierarchical agents' updates are not here. */
+typedef struct zenv_ppo_config {
+    double lr, adam_eps;            /* torch.optim.Adam(lr, eps = adam_eps), betas 0.9 / 0.999 */
+    double clip_eps, entropy_coef, value_loss_coef, max_grad_norm;
+    int32_t max_batch;              /* the largest minibatch: sizes the activation workspace */
+    int32_t distributional_value;   /* != 0: PPO-VD's critic (critic_mu, critic_sigma), value loss -log N(returnn) */
+} zenv_ppo_config;
+enum { ZENV_PPO_PARAM = 0, ZENV_PPO_GRAD = 1, ZENV_PPO_EXP_AVG = 2, ZENV_PPO_EXP_AVG_SQ = 3 };
+/* The argument rules of zenv_ppo_init, on the host alone (cfg: the handle's config): ZENV_E_ARG for h_dim outside
+ * 1 .. 191, a null actor tensor, a missing critic, critic_sigma_* without distributional_value or the reverse, a
+ * negative or non-finite hyper-parameter, max_batch < 1, a workspace of 2^31 floats or more. */
+int zenv_ppo_check(const zenv_config *cfg, const zenv_mlp_weights *init, const zenv_ppo_config *pc);
+/* One device arena of float32 master parameters -- each tensor in the state_dict's row-major [out][in] layout, in
+ * zenv_mlp_weights' member order (18 tensors, 20 with the distributional critic), each starting on a 256-byte
+ * boundary with zeros between -- and arenas of the same shape for the gradients, exp_avg and exp_avg_sq; Adam's step
+ * count starts at 0.  init->precision is not used.  A second call replaces the learner. */
+int zenv_ppo_init(zenv_t *h, const zenv_mlp_weights *init, const zenv_ppo_config *pc);
+/* The device pointer and element count of tensor `index` (member order) of arena `which` (ZENV_PPO_*): callers alias,
+ * read and write them on the handle's stream (checkpoints, tests).  index = -1: the whole arena, padding included. */
+int zenv_ppo_tensor(zenv_t *h, int which, int index, void **dev_ptr, int64_t *count);
+/* The same tensor (index = -1: the whole arena) copied to / from host float32 memory, behind everything enqueued on
+ * the handle's stream; both wait for the copy. */
+int zenv_ppo_read(zenv_t *h, int which, int index, float *dst);
+int zenv_ppo_write(zenv_t *h, int which, int index, const float *src);
+int zenv_ppo_get_step(zenv_t *h, int64_t *step);
+int zenv_ppo_set_step(zenv_t *h, int64_t step);
+/* Forward, loss and backward on the samples idx[0 .. count) (host memory, or device memory of the handle's device):
+ * the gradients are left in their arena, the six statistics in row 0 of ZENV_F_PPO_STATS; apply != 0 runs
+ * zenv_ppo_apply behind it.  Asynchronous on the handle's stream.  ZENV_E_STATE without zenv_ppo_init or without
+ * experience on the handle (zenv_collect); ZENV_E_ARG for count outside 1 .. max_batch and for a host index outside
+ * [0, N T).  A device-resident index outside that range is never dereferenced: its sample is dropped (it adds nothing
+ * to the loss; the means still divide by count) and the next call that waits for the device (zenv_get*, zenv_sync ...)
+ * answers ZENV_E_ARG once. */
+int zenv_ppo_minibatch(zenv_t *h, const int32_t *idx, int count, int idx_on_device, int apply);
+/* clip_grad_norm_(max_grad_norm) and one step of torch's Adam on whatever the gradient arena holds (the arena itself
+ * keeps the unclipped gradients). */
+int zenv_ppo_apply(zenv_t *h);
+/* The minibatches order[k B : (k + 1) B], B = batch_size, in sequence, the last one short: each forward, backward,
+ * clip and Adam, with no host synchronisation; minibatch k's statistics in row k of ZENV_F_PPO_STATS. */
+int zenv_ppo_epoch(zenv_t *h, const int32_t *order, int total, int batch_size, int on_device);
 
 /* ---- results ---- */
 int zenv_get(zenv_t *h, int field, void *dst, int dst_on_device);
