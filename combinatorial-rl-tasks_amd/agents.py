@@ -143,6 +143,23 @@ def ppo_batch_indexes(num_frames, frames_per_proc, batch_num, rng):
     return np.ascontiguousarray(indexes, np.int32)
 
 
+def hppo_state_dict_keys():
+    """(hi, lo): zenv_hier_weights name -> state_dict key of every tensor the Zone-goals agent's two learners hold, in
+    their arenas' order -- 16 tensors of HighPolicyValueModel, 18 of LoPolicyValueModel, critics included.  It is also
+    each module's ``parameters()`` order, the order of torch Adam's state."""
+    hi = dict(HIER_HI_KEYS, **_HIER_CRITIC)
+    lo = dict(HIER_LO_KEYS, **_HIER_CRITIC)
+    return ({name: hi[name[3:]] for name in nat.HIER_HI_TENSORS + nat.HIER_HI_CRITIC},
+            {name: lo[name[3:]] for name in nat.HIER_LO_TENSORS + nat.HIER_LO_CRITIC})
+
+
+def hppo_batch_indexes(total, rng):
+    """The sample order of one epoch of either level: _get_batches_starting_indexes_lo / _hi (zone-goals/src/torch_ac/
+    algos/_hier_policy_opt.py:372-420) before it is cut into batches -- a plain permutation of range(total) from the
+    caller's numpy Generator; no frame is dropped and nothing is shifted, unlike ``ppo_batch_indexes``."""
+    return np.ascontiguousarray(rng.permutation(np.arange(0, total, 1)), np.int32)
+
+
 def _two_level_tensors(hi_sd, lo_sd, hi_keys, lo_keys, sizes, want, describe):
     """The walk over a (hi_model_state, lo_model_state) pair: every key of hi_keys / lo_keys, the critics when present
     (critic.0 or critic.2), as numpy float32 under hi_<name> / lo_<name>.  sizes(out) reads the agent's sizes off the

@@ -1,7 +1,9 @@
 // ppo_update.hip -- one PPO minibatch of the flat actor-critic in float32, gfx950: forward, loss, backward, gradient-norm
 // clip and Adam (update_parameters, main/src/torch_ac/algos/ppo.py:30-155, recurrence 1) on the network of
 // mlp_f32.hip -- ZoneEnvModel (main/src/env_model.py:48-79), PolicyNetwork's Box branch (policy_network.py:39-52) and
-// both critics of ACModel (flat_model.py:21-68).
+// both critics of ACModel (flat_model.py:21-68).  The same launches serve the Zone-goals agent's two learners
+// (zone-goals/src/torch_ac/algos/_hier_policy_opt.py:214-370): the low level is this network on [obs, goal] (XD = 10
+// where the flat one has 8), the high level this encoder and critic under a per-zone head (PPO_HEAD_ZONES, below).
 //
 // Every layer is a product on v_mfma_f32_32x32x2_f32, forward and backward, in one of two shapes:
 //
@@ -39,6 +41,8 @@ struct Gather {
     const float *obs, *zone_obs;
     const int32_t *idx;
     int count, N, T, Z, F;
+    const float *goal;      // [slot][2]: columns 8-9 of the per-sample input when XD = 10
+    int XD, W1C;
 };
 
 // where a zone row of the minibatch lies in the experience buffers
@@ -68,13 +72,15 @@ __device__ __forceinline__ RowRef row_ref(const Gather &g, int row)
     return r;
 }
 
-// zone_net_.0's input [obs (8), zone row (F), 0 ..., 1]: column 15 is the constant that carries the bias
+// zone_net_.0's input [obs (8), goal (XD - 8), zone row (F), 0 ..., 1]: the last of the W1C columns (15 for XD = 8, 23
+// for XD = 10) is the constant that carries the bias
 __device__ __forceinline__ float x0_elem(const Gather &g, const RowRef &r, int k)
 {
     if (!r.ok) return 0.f;
     if (k < 8) return g.obs[r.slot * 8 + k];
-    if (k < 8 + g.F) return g.zone_obs[(r.slot * g.Z + r.z) * g.F + (k - 8)];
-    return k == 15 ? 1.f : 0.f;
+    if (k < g.XD) return g.goal[r.slot * 2 + (k - 8)];
+    if (k < g.XD + g.F) return g.zone_obs[(r.slot * g.Z + r.z) * g.F + (k - g.XD)];
+    return k == g.W1C - 1 ? 1.f : 0.f;
 }
 
 __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c)
@@ -153,7 +159,7 @@ __global__ __launch_bounds__(448) void k_ppo_nt(const float *__restrict__ A, int
 
 // part[chunk][n][k] = sum over the chunk's rows of A[row][n] B[row][k]; grid = (chunks, n tiles), block = (64, k
 // tiles).  `rows` is a multiple of 32, so both lane halves make the same number of steps, a multiple of 8.  Columns of B from nB on
-// read as 0; GATHER: B is zone_net_.0's gathered input (16 columns).
+// read as 0; GATHER: B is zone_net_.0's gathered input (W1C columns).
 template <bool GATHER>
 __global__ __launch_bounds__(448) void k_ppo_tn(const float *__restrict__ A, int lda, const float *__restrict__ B, int ldb,
                                                 int nB, int rows, float *__restrict__ part, Gather g)
@@ -200,11 +206,46 @@ __global__ void k_ppo_reduce(const float *__restrict__ part, int chunks, int m_r
     dst[(size_t)r * dst_ld + dst_col0 + c] = (float)s;
 }
 
+// The same sum with kPpoReduceSplit threads per element: thread (segment, element) adds the partials of its
+// contiguous share of the chunks in chunk order in double, the element's first thread then adds the segments in order.
+// One chain per element leaves most of the device idle and waiting on memory when a minibatch has hundreds of
+// partials (960 for zone_net_.2 at 16 384 samples x 15 zones); the order is still fixed.  Block = 32 elements x
+// kPpoReduceSplit segments: a wave half reads 32 consecutive floats.
+__global__ __launch_bounds__(32 * kPpoReduceSplit) void k_ppo_reduce_split(
+    const float *__restrict__ part, int chunks, int m_rows, int ldp, int src_row0, int src_col0, float *__restrict__ dst,
+    int dst_ld, int dst_col0, int rows, int cols)
+{
+    __shared__ double sh[kPpoReduceSplit][32];
+    const int lane = threadIdx.x & 31, seg = threadIdx.x >> 5;
+    const int e = blockIdx.x * 32 + lane;
+    const bool live = e < rows * cols;
+    const int r = live ? e / cols : 0, c = live ? e - r * cols : 0;
+    const int per = (chunks + kPpoReduceSplit - 1) / kPpoReduceSplit;
+    const int ch0 = seg * per, ch1 = min(chunks, ch0 + per);
+    double s = 0.0;
+    if (live) {
+        const float *p = part + (size_t)(src_row0 + r) * ldp + src_col0 + c;
+        for (int ch = ch0; ch < ch1; ++ch) s += (double)p[(size_t)ch * m_rows * ldp];
+    }
+    sh[seg][lane] = s;
+    __syncthreads();
+    if (seg == 0 && live) {
+        double t = sh[0][lane];
+#pragma unroll
+        for (int k = 1; k < kPpoReduceSplit; ++k) t += sh[k][lane];
+        dst[(size_t)r * dst_ld + dst_col0 + c] = (float)t;
+    }
+}
+
 // ---- the padded weight images
+__device__ __forceinline__ float img_square(const float *w, const float *b, int h, int r, int c, bool one, int ld)
+{
+    if (r < h) return c < h ? w[(size_t)r * ld + c] : c == h ? b[r] : 0.f;
+    return one && r == h && c == h ? 1.f : 0.f;
+}
 __device__ __forceinline__ float img_square(const float *w, const float *b, int h, int r, int c, bool one)
 {
-    if (r < h) return c < h ? w[(size_t)r * h + c] : c == h ? b[r] : 0.f;
-    return one && r == h && c == h ? 1.f : 0.f;
+    return img_square(w, b, h, r, c, one, h);
 }
 __device__ __forceinline__ float img_transposed(const float *w, int ld, int col0, int h, int r, int c)
 {
@@ -215,51 +256,60 @@ __global__ void k_ppo_prep(PpoNet n)
 {
     const int e = blockIdx.x * blockDim.x + threadIdx.x, which = blockIdx.y;
     const int h = n.h, HP = n.HP;
-    const int ld = which == PPO_I_W1 ? 16 : which == PPO_I_WC ? n.KC : (which == PPO_T_HA || which == PPO_T_HV) ? 32 : HP;
+    const int ld = which == PPO_I_W1 ? n.W1C : which == PPO_I_WC ? n.KC : (which == PPO_T_HA || which == PPO_T_HV) ? 32 : HP;
     const int n_rows = (which == PPO_I_HA || which == PPO_I_HV) ? 32 : HP;
     if (e >= n_rows * ld) return;
     const int r = e / ld, c = e - r * ld;
     auto T = [&](int t) { return n.param + n.off[t]; };
+    const int XD = n.XD, kb = n.W1C - 1;
+    const bool zones = n.head == PPO_HEAD_ZONES;
+    // the critic's four tensors
+    const float *cw1 = T(n.cr), *cb1 = T(n.cr + 1), *cw2 = T(n.cr + 2), *cb2 = T(n.cr + 3);
     float v = 0.f;
     switch (which) {
     case PPO_I_W1:
-        if (r < h) v = c < n.K1 ? T(PPO_ZONE_W1)[(size_t)r * n.K1 + c] : c == 15 ? T(PPO_ZONE_B1)[r] : 0.f;
-        else v = r == h && c == 15 ? 1.f : 0.f;
+        if (r < h) v = c < n.K1 ? T(PPO_ZONE_W1)[(size_t)r * n.K1 + c] : c == kb ? T(PPO_ZONE_B1)[r] : 0.f;
+        else v = r == h && c == kb ? 1.f : 0.f;
         break;
     case PPO_I_W2: v = img_square(T(PPO_ZONE_W2), T(PPO_ZONE_B2), h, r, c, false); break;
     case PPO_I_W3: v = img_square(T(PPO_ZONE_W3), T(PPO_ZONE_B3), h, r, c, true); break;
     case PPO_I_WC:
         if (r < h) {
-            const float *w = T(PPO_COMB_W) + (size_t)r * (8 + h);      // combine_net_'s input is [obs, zone_emb]
-            v = c < h ? w[8 + c] : c == h ? T(PPO_COMB_B)[r] : (c >= HP && c < HP + 8) ? w[c - HP] : 0.f;
+            const float *w = T(PPO_COMB_W) + (size_t)r * (XD + h);     // combine_net_'s input is [obs (, goal), zone_emb]
+            v = c < h ? w[XD + c] : c == h ? T(PPO_COMB_B)[r] : (c >= HP && c < HP + XD) ? w[c - HP] : 0.f;
         } else {
             v = r == h && c == h ? 1.f : 0.f;
         }
         break;
-    case PPO_I_WE: v = img_square(T(PPO_ENC_W), T(PPO_ENC_B), h, r, c, true); break;
-    case PPO_I_WV: v = img_square(T(PPO_CRITIC_W1), T(PPO_CRITIC_B1), h, r, c, true); break;
+    // PPO_HEAD_ZONES: actor.0.weight = [W_e | W_z], [h][h + F]; this is W_e with actor.0's bias
+    case PPO_I_WE: v = img_square(T(PPO_ENC_W), T(PPO_ENC_B), h, r, c, true, zones ? h + n.F : h); break;
+    case PPO_I_WV: v = img_square(cw1, cb1, h, r, c, true); break;
     case PPO_I_HA:
-        if (r < 4 && c <= h) {
+        if (zones) {                                  // row 0: actor.2
+            if (r == 0 && c <= h) v = c < h ? T(PPO_ACTOR_W2)[c] : T(PPO_ACTOR_B2)[0];
+        } else if (r < 4 && c <= h) {
             const float *w = T(r < 2 ? PPO_MU_W : PPO_STD_W), *b = T(r < 2 ? PPO_MU_B : PPO_STD_B);
             v = c < h ? w[(size_t)(r & 1) * h + c] : b[r & 1];
         }
         break;
     case PPO_I_HV:
         if (c <= h && (r == 4 || (r == 5 && n.dist))) {
-            const float *w = T(r == 4 ? PPO_CRITIC_W2 : PPO_SIGMA_W), *b = T(r == 4 ? PPO_CRITIC_B2 : PPO_SIGMA_B);
+            const float *w = r == 4 ? cw2 : T(PPO_SIGMA_W), *b = r == 4 ? cb2 : T(PPO_SIGMA_B);
             v = c < h ? w[c] : b[0];
         }
         break;
     case PPO_T_W2: v = img_transposed(T(PPO_ZONE_W2), h, 0, h, r, c); break;
     case PPO_T_W3: v = img_transposed(T(PPO_ZONE_W3), h, 0, h, r, c); break;
-    case PPO_T_WC: v = img_transposed(T(PPO_COMB_W), 8 + h, 8, h, r, c); break;
-    case PPO_T_WE: v = img_transposed(T(PPO_ENC_W), h, 0, h, r, c); break;
-    case PPO_T_WV: v = img_transposed(T(PPO_CRITIC_W1), h, 0, h, r, c); break;
+    case PPO_T_WC: v = img_transposed(T(PPO_COMB_W), XD + h, XD, h, r, c); break;
+    case PPO_T_WE: v = img_transposed(T(PPO_ENC_W), zones ? h + n.F : h, 0, h, r, c); break;
+    case PPO_T_WV: v = img_transposed(cw1, h, 0, h, r, c); break;
     case PPO_T_HA:
-        if (r < h && c < 4) v = T(c < 2 ? PPO_MU_W : PPO_STD_W)[(size_t)(c & 1) * h + r];
+        if (zones) {
+            if (r < h && c == 0) v = T(PPO_ACTOR_W2)[r];
+        } else if (r < h && c < 4) v = T(c < 2 ? PPO_MU_W : PPO_STD_W)[(size_t)(c & 1) * h + r];
         break;
     case PPO_T_HV:
-        if (r < h && (c == 4 || (c == 5 && n.dist))) v = T(c == 4 ? PPO_CRITIC_W2 : PPO_SIGMA_W)[r];
+        if (r < h && (c == 4 || (c == 5 && n.dist))) v = (c == 4 ? cw2 : T(PPO_SIGMA_W))[r];
         break;
     default: break;
     }
@@ -267,7 +317,7 @@ __global__ void k_ppo_prep(PpoNet n)
 }
 
 // ---- the per-sample pieces between the products
-// P = the mean of a sample's zone rows (its column h: the constant), the obs columns of combine_net_'s input; rows from
+// P = the mean of a sample's zone rows (its column h: the constant), the XD own columns of combine_net_'s input; rows from
 // `count` on are zero.  Thread (b, f), f < KC.
 __global__ void k_ppo_pool(PpoNet n, Gather g, int bp)
 {
@@ -278,7 +328,8 @@ __global__ void k_ppo_pool(PpoNet n, Gather g, int bp)
     const bool ok = sample_slot(g, b, slot);
     if (f == 0 && b < g.count && !ok) *n.bad_index = 1;
     if (f >= n.HP) {
-        n.CI[(size_t)b * n.KC + f] = ok ? g.obs[slot * 8 + (f - n.HP)] : 0.f;
+        const int k = f - n.HP;
+        n.CI[(size_t)b * n.KC + f] = !ok ? 0.f : k < 8 ? g.obs[slot * 8 + k] : k < g.XD ? g.goal[slot * 2 + (k - 8)] : 0.f;
         return;
     }
     float v = 0.f;
@@ -310,6 +361,32 @@ __global__ void k_ppo_spread(PpoNet n, int Z, int rows)
 
 __device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+// PPO's clipped surrogate of one sample (ppo.py:76-79): returns -min(surr1, surr2); g_lp = d loss / d log_prob(a), the
+// mean's 1 / count included.  dlp = log_prob(a) - the recorded log_prob.
+__device__ __forceinline__ float clipped_policy(float dlp, float adv, float clip_eps, float inv_b, float &g_lp)
+{
+    const float ratio = expf(dlp);
+    const float lo = 1.0f - clip_eps, hi = 1.0f + clip_eps;
+    const float surr1 = ratio * adv, surr2 = fminf(fmaxf(ratio, lo), hi) * adv;
+    // d min(surr1, surr2) / d ratio: adv on the unclipped branch, adv inside the clamp's range, 0 outside
+    const float through = surr1 <= surr2 ? 1.0f : (ratio >= lo && ratio <= hi) ? 1.0f : 0.f;
+    g_lp = -adv * inv_b * through * ratio;
+    return -fminf(surr1, surr2);
+}
+
+// the clipped value loss of one sample (ppo.py:83-86): returns max(s1, s2); dval = d loss / d v with the coefficient
+// and the mean's 1 / count
+__device__ __forceinline__ float clipped_value(float v, float old, float ret, const PpoHyper &hy, float inv_b, float &dval)
+{
+    const float dv = v - old;
+    const float vc = old + fminf(fmaxf(dv, -hy.clip_eps), hy.clip_eps);
+    const float s1 = (v - ret) * (v - ret), s2 = (vc - ret) * (vc - ret);
+    const bool inside = dv >= -hy.clip_eps && dv <= hy.clip_eps;
+    const float dl = s1 >= s2 ? 2.0f * (v - ret) : inside ? 2.0f * (vc - ret) : 0.f;
+    dval = hy.value_loss_coef * inv_b * dl;
+    return fmaxf(s1, s2);
+}
+
 // The loss of one sample (ppo.py:70-89) and its derivative with respect to the six head pre-activations
 // (PRE: mu_ 0-1, std_ 2-3, critic.2 / critic_mu 4, critic_sigma 5), scaled by the means' 1 / count.
 __global__ void k_ppo_loss(PpoNet n, PpoExp x, Gather g, int bp)
@@ -336,12 +413,8 @@ __global__ void k_ppo_loss(PpoNet n, PpoExp x, Gather g, int bp)
             dlp += lp - x.log_prob[slot * 2 + o];
             ent += 0.5f + 0.9189385332046727f + logf(sd[o]);  // Normal.entropy
         }
-        const float ratio = expf(dlp);
-        const float lo = 1.0f - hy.clip_eps, hi = 1.0f + hy.clip_eps;
-        const float surr1 = ratio * adv, surr2 = fminf(fmaxf(ratio, lo), hi) * adv;
-        // d min(surr1, surr2) / d ratio: adv on the unclipped branch, adv inside the clamp's range, 0 outside
-        const float through = surr1 <= surr2 ? 1.0f : (ratio >= lo && ratio <= hi) ? 1.0f : 0.f;
-        const float g_lp = -adv * inv_b * through * ratio;    // d loss / d log_prob(a_o), the same for both o
+        float g_lp;                                           // d loss / d log_prob(a_o), the same for both o
+        const float ploss = clipped_policy(dlp, adv, hy.clip_eps, inv_b, g_lp);
 #pragma unroll
         for (int o = 0; o < 2; ++o) {
             const float var = sd[o] * sd[o];
@@ -364,19 +437,12 @@ __global__ void k_ppo_loss(PpoNet n, PpoExp x, Gather g, int bp)
             d[4] = w * (-dr / var);
             d[5] = w * (-(dr * dr) / (var * vsig) + 1.0f / vsig) * dsp;
         } else {
-            const float old = x.value[slot];
-            const float dv = v - old;
-            const float vc = old + fminf(fmaxf(dv, -hy.clip_eps), hy.clip_eps);
-            const float s1 = (v - ret) * (v - ret), s2 = (vc - ret) * (vc - ret);
-            vloss = fmaxf(s1, s2);
-            const bool inside = dv >= -hy.clip_eps && dv <= hy.clip_eps;
-            const float dl = s1 >= s2 ? 2.0f * (v - ret) : inside ? 2.0f * (vc - ret) : 0.f;
-            d[4] = hy.value_loss_coef * inv_b * dl;
+            vloss = clipped_value(v, x.value[slot], ret, hy, inv_b, d[4]);
         }
         ss[0] = ent;
         ss[1] = v;
         ss[2] = vsig;
-        ss[3] = -fminf(surr1, surr2);
+        ss[3] = ploss;
         ss[4] = vloss;
     }
     float *dh = n.DH + (size_t)b * 32;
@@ -384,6 +450,130 @@ __global__ void k_ppo_loss(PpoNet n, PpoExp x, Gather g, int bp)
     for (int i = 0; i < 32; ++i) dh[i] = i < 6 ? d[i] : 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) n.SS[(size_t)b * 8 + i] = ss[i];
+}
+
+// ---- PPO_HEAD_ZONES: the Zone-goals high level's actor (zone-goals/src/hier_policy_value_models.py:19-56), one logit
+// per zone from actor.2(relu(actor.0([emb, zone row]))).  With actor.0.weight = [W_e | W_z] the emb part E = W_e emb + b
+// is taken once per sample (k_ppo_nt, into Ha; its column h is the constant 1) and
+//   U[row][f] = relu(E[sample][f] + sum_k W_z[f][k] zone row[k]),   k in zone-feature order.
+// Column h of U stays the constant of a valid row; rows of a dropped sample and rows past the minibatch are zero.
+__global__ void k_hppo_head(PpoNet n, Gather g, int rows)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= rows * n.HP) return;
+    const int row = e / n.HP, f = e - row * n.HP;
+    const RowRef r = row_ref(g, row);
+    float v = 0.f;
+    if (r.ok && f <= n.h) {
+        float s = 0.f;
+        if (f < n.h) {
+            const float *w = n.param + n.off[PPO_ACTOR_W1] + (size_t)f * (n.h + g.F) + n.h;
+            const float *zr = g.zone_obs + (r.slot * g.Z + r.z) * g.F;
+            for (int k = 0; k < g.F; ++k) s += w[k] * zr[k];
+        }
+        v = fmaxf(n.Ha[(size_t)(row / g.Z) * n.HP + f] + s, 0.f);
+    }
+    n.U[(size_t)row * n.HP + f] = v;
+}
+
+// The loss of one high-level sample (_hier_policy_opt.py:315-334) and its derivatives: Categorical over the goals that
+// were available at the pick (logits[~mask] = -inf).  With p the masked softmax, H = -sum p log p the entropy and g_lp
+// as in k_ppo_loss,   d loss / d logit_z = g_lp (1[z = a] - p_z) + (entropy_coef / count) p_z (log p_z + H),
+// 0 for an unavailable z.  A recorded goal outside [0, Z) or marked unavailable (a row without an available goal has
+// one) drops the sample like an index out of range.  One thread per sample; L, DL: [rows][32], column 0.
+// The softmax and the derivatives are formed in double (Z <= 32 terms per sample) and rounded once: a row's derivatives
+// sum to zero -- a shift common to its logits changes nothing -- so actor.2.bias' gradient is nothing but what they
+// fail to cancel.  That sum, taken per sample before the rounding, goes out in SS[5]; k_ppo_stats adds it up.
+__global__ void k_hppo_loss(PpoNet n, PpoExp x, Gather g, int bp, int rows)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= bp) return;
+    const int Z = g.Z;
+    float d_value = 0.f, ss[8] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
+    float g_lp = 0.f;
+    double lse = 0.0, H = 0.0, ec = 0.0;
+    size_t slot = 0;
+    bool ok = sample_slot(g, b, slot);
+    int a = -1;
+    const uint8_t *mk = nullptr;
+    const float *lg = n.L + (size_t)b * Z * 32;
+    if (ok) {
+        a = x.hi_action[slot];
+        mk = x.hi_mask + slot * Z;
+        if (a < 0 || a >= Z || !mk[a]) {
+            ok = false;
+            *n.bad_index = 1;
+        }
+    }
+    if (ok) {
+        const PpoHyper &hy = n.hyper;
+        const float inv_b = 1.0f / (float)g.count;
+        double m = (double)lg[(size_t)a * 32];
+        for (int z = 0; z < Z; ++z)
+            if (mk[z]) m = fmax(m, (double)lg[(size_t)z * 32]);
+        double sum = 0.0;
+        for (int z = 0; z < Z; ++z)
+            if (mk[z]) sum += exp((double)lg[(size_t)z * 32] - m);
+        lse = m + log(sum);
+        for (int z = 0; z < Z; ++z)
+            if (mk[z]) {
+                const double lp = (double)lg[(size_t)z * 32] - lse;
+                H -= exp(lp) * lp;
+            }
+        const float lp_a = (float)((double)lg[(size_t)a * 32] - lse);
+        const float ploss = clipped_policy(lp_a - x.log_prob[slot], x.advantage[slot], hy.clip_eps, inv_b, g_lp);
+        const float v = n.PRE[(size_t)b * 32 + 4];
+        const float vloss = clipped_value(v, x.value[slot], x.returnn[slot], hy, inv_b, d_value);
+        ec = (double)hy.entropy_coef * (double)inv_b;
+        ss[0] = (float)H;
+        ss[1] = v;
+        ss[3] = ploss;
+        ss[4] = vloss;
+    }
+    double row_sum = 0.0;
+    for (int z = 0; z < Z; ++z) {
+        const size_t row = (size_t)b * Z + z;
+        if (row >= (size_t)rows) break;
+        double dz = 0.0;
+        if (ok && mk[z]) {
+            const double lp = (double)lg[(size_t)z * 32] - lse, p = exp(lp);
+            dz = (double)g_lp * ((z == a ? 1.0 : 0.0) - p) + ec * p * (lp + H);
+        }
+        row_sum += dz;
+        n.DZ[row] = dz;
+        float4 *dl = reinterpret_cast<float4 *>(n.DL + row * 32);
+        dl[0] = make_float4((float)dz, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int i = 1; i < 8; ++i) dl[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    ss[5] = (float)row_sum;
+    float *dh = n.DH + (size_t)b * 32;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) dh[i] = i == 4 ? d_value : 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) n.SS[(size_t)b * 8 + i] = ss[i];
+}
+
+// S[sample][f] = the sum over the sample's zone rows of actor.0's delta dU[row][f] = [U > 0] actor.2[f] dlogit[row]: the
+// delta of E, into Ha.  A unit that is active on every zone row of a sample sees the sum of the row's dlogit, which is
+// zero: added up in float32 from the rounded deltas it came out as 1e-9 of noise, and Adam (eps 1e-8) turned that into
+// steps of a tenth of lr on rows of W_e whose gradient is zero.  So the sum runs over the unrounded deltas, in z order,
+// in double, times actor.2[f], rounded once.  U still holds the activations here.
+__global__ void k_hppo_sum(PpoNet n, int Z, int bp, int rows)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= bp * n.HP) return;
+    const int b = e / n.HP, f = e - b * n.HP;
+    double s = 0.0;
+    if (f < n.h) {
+        for (int z = 0; z < Z; ++z) {
+            const size_t row = (size_t)b * Z + z;
+            if (row >= (size_t)rows) break;
+            if (n.U[row * n.HP + f] > 0.f) s += n.DZ[row];
+        }
+        s *= (double)n.param[n.off[PPO_ACTOR_W2] + f];
+    }
+    n.Ha[(size_t)b * n.HP + f] = (float)s;
 }
 
 // a block's fixed-order sum: every thread's double, then a tree over LDS
@@ -401,14 +591,23 @@ __device__ __forceinline__ double block_sum_256(double v, double *sh)
 }
 
 // stats[0..4] = the minibatch means of the per-sample terms; one block of 256 threads, thread i adds samples i, i + 256 ...
-__global__ __launch_bounds__(256) void k_ppo_stats(const float *__restrict__ SS, int count, float *__restrict__ stats)
+// ent_terms: the entropy's mean is over count x 2 action components, or over count categoricals.  col5_sum (or null):
+// where the plain sum of column 5 goes -- PPO_HEAD_ZONES: actor.2.bias' gradient, see k_hppo_loss
+__global__ __launch_bounds__(256) void k_ppo_stats(const float *__restrict__ SS, int count, double ent_terms,
+                                                   float *__restrict__ stats, float *__restrict__ col5_sum)
 {
     __shared__ double sh[256];
+    if (col5_sum) {
+        double s = 0.0;
+        for (int b = threadIdx.x; b < count; b += 256) s += (double)SS[(size_t)b * 8 + 5];
+        s = block_sum_256(s, sh);
+        if (threadIdx.x == 0) *col5_sum = (float)s;
+    }
     for (int k = 0; k < 5; ++k) {
         double s = 0.0;
         for (int b = threadIdx.x; b < count; b += 256) s += (double)SS[(size_t)b * 8 + k];
         s = block_sum_256(s, sh);
-        if (threadIdx.x == 0) stats[k] = (float)(s / (k == 0 ? 2.0 * count : (double)count));
+        if (threadIdx.x == 0) stats[k] = (float)(s / (k == 0 ? ent_terms * count : (double)count));
     }
 }
 
@@ -456,7 +655,7 @@ __global__ void k_ppo_adam(PpoNet n, float step_size, float bc2_sqrt)
     n.exp_avg_sq[e] = v;
 }
 
-Gather no_gather() { return Gather{ nullptr, nullptr, nullptr, 0, 1, 1, 1, 0 }; }
+Gather no_gather() { return Gather{ nullptr, nullptr, nullptr, 0, 1, 1, 1, 0, nullptr, 8, 16 }; }
 
 template <int MODE>
 void nt(const float *A, int lda, const float *B, int ldb, int K, float *D, int ldd, int rows, int m_tiles,
@@ -479,6 +678,12 @@ void reduce(const PpoNet &n, int rows_reduced, int m_tiles, int nB, int src_row0
 {
     const int chunks = (rows_reduced + kPpoChunk - 1) / kPpoChunk;
     const int total = rows * cols;
+    if (n.split_reduce && chunks > kPpoReduceSplit) {
+        hipLaunchKernelGGL(k_ppo_reduce_split, dim3((total + 31) / 32), dim3(32 * kPpoReduceSplit), 0, s, n.partial, chunks,
+                           m_tiles * 32, ((nB + 31) / 32) * 32, src_row0, src_col0, n.grad + n.off[tensor], dst_ld, dst_col0,
+                           rows, cols);
+        return;
+    }
     hipLaunchKernelGGL(k_ppo_reduce, dim3((total + 255) / 256), dim3(256), 0, s, n.partial, chunks, m_tiles * 32,
                        ((nB + 31) / 32) * 32, src_row0, src_col0, n.grad + n.off[tensor], dst_ld, dst_col0, rows, cols);
 }
@@ -490,29 +695,17 @@ void launch_norm(const PpoNet &n, float *stat, hipStream_t s)
     hipLaunchKernelGGL(k_ppo_norm, dim3(1), dim3(1), 0, s, n.norm_partial, parts, n.scalars, stat);
 }
 
-}  // namespace
-
-hipError_t launch_ppo_minibatch(const PpoNet &n, const PpoExp &x, const int32_t *idx, int count, float *stats,
-                                hipStream_t s)
+// the two heads between the encoder's forward and backward passes: C holds the embedding going in, its delta coming out
+void gaussian_head(const PpoNet &n, const PpoExp &x, const Gather &g, int bp, float *stats, hipStream_t s)
 {
-    const int h = n.h, HP = n.HP, KC = n.KC, NT = HP / 32;
-    const int rp = (count * n.Z + 31) / 32 * 32, bp = (count + 31) / 32 * 32;
-    const Gather g{ x.obs, x.zone_obs, idx, count, x.N, x.T, n.Z, n.F };
+    const int h = n.h, HP = n.HP, NT = HP / 32, cr = n.cr;
     float *const *I = n.img;
-    hipLaunchKernelGGL(k_ppo_prep, dim3((HP * KC + 255) / 256, PPO_N_IMAGES), dim3(256), 0, s, n);
-    // ---- forward
-    hipLaunchKernelGGL((k_ppo_nt<NT_RELU, true>), dim3(rp / 32), dim3(64, NT), 0, s, I[PPO_I_W1], 16, nullptr, 0, 16, n.A1,
-                       HP, g);                                                            // relu(zone_net_.0)
-    nt<NT_RELU>(I[PPO_I_W2], HP, n.A1, HP, HP, n.A2, HP, rp, NT, s);                      // relu(zone_net_.2)
-    hipLaunchKernelGGL(k_ppo_pool, dim3((bp * KC + 255) / 256), dim3(256), 0, s, n, g, bp);
-    nt<NT_STORE>(I[PPO_I_W3], HP, n.P, HP, HP, n.CI, KC, bp, NT, s);                      // zone_net_.4 of the mean
-    nt<NT_STORE>(I[PPO_I_WC], KC, n.CI, KC, KC, n.C, HP, bp, NT, s);                      // combine_net_
     nt<NT_RELU>(I[PPO_I_WE], HP, n.C, HP, HP, n.Ha, HP, bp, NT, s);                       // relu(actor.enc_)
     nt<NT_RELU>(I[PPO_I_WV], HP, n.C, HP, HP, n.Hc, HP, bp, NT, s);                       // relu(critic.0)
     nt<NT_STORE>(I[PPO_I_HA], HP, n.Ha, HP, HP, n.PRE, 32, bp, 1, s);                     // mu_, std_
     nt<NT_ADD>(I[PPO_I_HV], HP, n.Hc, HP, HP, n.PRE, 32, bp, 1, s);                       // critic.2 / critic_mu, critic_sigma
     hipLaunchKernelGGL(k_ppo_loss, dim3((bp + 63) / 64), dim3(64), 0, s, n, x, g, bp);
-    hipLaunchKernelGGL(k_ppo_stats, dim3(1), dim3(256), 0, s, n.SS, count, stats);
+    hipLaunchKernelGGL(k_ppo_stats, dim3(1), dim3(256), 0, s, n.SS, g.count, 2.0, stats, (float *)nullptr);
     // ---- backward: every weight gradient is taken before its layer's activations are overwritten by deltas
     tn(n.DH, 32, 1, n.Ha, HP, HP, bp, n.partial, s);
     reduce(n, bp, 1, HP, 0, 0, PPO_MU_W, h, 0, 2, h, s);
@@ -520,8 +713,8 @@ hipError_t launch_ppo_minibatch(const PpoNet &n, const PpoExp &x, const int32_t 
     reduce(n, bp, 1, HP, 2, 0, PPO_STD_W, h, 0, 2, h, s);
     reduce(n, bp, 1, HP, 2, h, PPO_STD_B, 1, 0, 2, 1, s);
     tn(n.DH, 32, 1, n.Hc, HP, HP, bp, n.partial, s);
-    reduce(n, bp, 1, HP, 4, 0, PPO_CRITIC_W2, h, 0, 1, h, s);
-    reduce(n, bp, 1, HP, 4, h, PPO_CRITIC_B2, 1, 0, 1, 1, s);
+    reduce(n, bp, 1, HP, 4, 0, cr + 2, h, 0, 1, h, s);
+    reduce(n, bp, 1, HP, 4, h, cr + 3, 1, 0, 1, 1, s);
     if (n.dist) {
         reduce(n, bp, 1, HP, 5, 0, PPO_SIGMA_W, h, 0, 1, h, s);
         reduce(n, bp, 1, HP, 5, h, PPO_SIGMA_B, 1, 0, 1, 1, s);
@@ -532,13 +725,70 @@ hipError_t launch_ppo_minibatch(const PpoNet &n, const PpoExp &x, const int32_t 
     reduce(n, bp, NT, HP, 0, 0, PPO_ENC_W, h, 0, h, h, s);
     reduce(n, bp, NT, HP, 0, h, PPO_ENC_B, 1, 0, h, 1, s);
     tn(n.Hc, HP, NT, n.C, HP, HP, bp, n.partial, s);
-    reduce(n, bp, NT, HP, 0, 0, PPO_CRITIC_W1, h, 0, h, h, s);
-    reduce(n, bp, NT, HP, 0, h, PPO_CRITIC_B1, 1, 0, h, 1, s);
+    reduce(n, bp, NT, HP, 0, 0, cr, h, 0, h, h, s);
+    reduce(n, bp, NT, HP, 0, h, cr + 1, 1, 0, h, 1, s);
     nt<NT_STORE>(I[PPO_T_WE], HP, n.Ha, HP, HP, n.C, HP, bp, NT, s);                      // delta of the embedding ...
     nt<NT_ADD>(I[PPO_T_WV], HP, n.Hc, HP, HP, n.C, HP, bp, NT, s);                        // ... from both heads
+}
+
+void zone_head(const PpoNet &n, const PpoExp &x, const Gather &g, int rp, int bp, float *stats, hipStream_t s)
+{
+    const int h = n.h, HP = n.HP, NT = HP / 32, cr = n.cr, F = n.F;
+    const int chunks = (rp + kPpoChunk - 1) / kPpoChunk;
+    float *const *I = n.img;
+    nt<NT_STORE>(I[PPO_I_WE], HP, n.C, HP, HP, n.Ha, HP, bp, NT, s);                      // E = W_e emb + b
+    nt<NT_RELU>(I[PPO_I_WV], HP, n.C, HP, HP, n.Hc, HP, bp, NT, s);                       // relu(critic.0)
+    hipLaunchKernelGGL(k_hppo_head, dim3((unsigned)(((int64_t)rp * HP + 255) / 256)), dim3(256), 0, s, n, g, rp);
+    nt<NT_STORE>(I[PPO_I_HA], HP, n.U, HP, HP, n.L, 32, rp, 1, s);                        // actor.2: a logit per zone row
+    nt<NT_STORE>(I[PPO_I_HV], HP, n.Hc, HP, HP, n.PRE, 32, bp, 1, s);                     // critic.2
+    hipLaunchKernelGGL(k_hppo_loss, dim3((bp + 63) / 64), dim3(64), 0, s, n, x, g, bp, rp);
+    hipLaunchKernelGGL(k_ppo_stats, dim3(1), dim3(256), 0, s, n.SS, g.count, 1.0, stats,
+                       n.grad + n.off[PPO_ACTOR_B2]);               // and actor.2.bias' gradient
+    // ---- backward
+    tn(n.DL, 32, 1, n.U, HP, HP, rp, n.partial, s);
+    reduce(n, rp, 1, HP, 0, 0, PPO_ACTOR_W2, h, 0, 1, h, s);
+    tn(n.DH, 32, 1, n.Hc, HP, HP, bp, n.partial, s);
+    reduce(n, bp, 1, HP, 4, 0, cr + 2, h, 0, 1, h, s);
+    reduce(n, bp, 1, HP, 4, h, cr + 3, 1, 0, 1, 1, s);
+    hipLaunchKernelGGL(k_hppo_sum, dim3((bp * HP + 255) / 256), dim3(256), 0, s, n, n.Z, bp, rp);   // S, the delta of E
+    nt<NT_MASK>(I[PPO_T_HA], 32, n.DL, 32, 32, n.U, HP, rp, NT, s);                       // dU, the delta of actor.0
+    nt<NT_MASK>(I[PPO_T_HV], 32, n.DH, 32, 32, n.Hc, HP, bp, NT, s);                      // delta of critic.0
+    // d W_z = sum over the zone rows of dU x the row's zone features: columns XD .. XD + F of the gathered input
+    hipLaunchKernelGGL((k_ppo_tn<true>), dim3(chunks, NT), dim3(64, 1), 0, s, n.U, HP, nullptr, 0, n.W1C, rp, n.partial, g);
+    reduce(n, rp, NT, n.W1C, 0, n.XD, PPO_ACTOR_W1, h + F, h, h, F, s);
+    tn(n.Ha, HP, NT, n.C, HP, HP, bp, n.partial, s);                                      // d W_e and actor.0's bias
+    reduce(n, bp, NT, HP, 0, 0, PPO_ACTOR_W1, h + F, 0, h, h, s);
+    reduce(n, bp, NT, HP, 0, h, PPO_ACTOR_B1, 1, 0, h, 1, s);
+    tn(n.Hc, HP, NT, n.C, HP, HP, bp, n.partial, s);
+    reduce(n, bp, NT, HP, 0, 0, cr, h, 0, h, h, s);
+    reduce(n, bp, NT, HP, 0, h, cr + 1, 1, 0, h, 1, s);
+    nt<NT_STORE>(I[PPO_T_WE], HP, n.Ha, HP, HP, n.C, HP, bp, NT, s);                      // delta of the embedding ...
+    nt<NT_ADD>(I[PPO_T_WV], HP, n.Hc, HP, HP, n.C, HP, bp, NT, s);                        // ... from actor and critic
+}
+
+}  // namespace
+
+hipError_t launch_ppo_minibatch(const PpoNet &n, const PpoExp &x, const int32_t *idx, int count, float *stats,
+                                hipStream_t s)
+{
+    const int h = n.h, HP = n.HP, KC = n.KC, NT = HP / 32, XD = n.XD, W1C = n.W1C;
+    const int rp = (count * n.Z + 31) / 32 * 32, bp = (count + 31) / 32 * 32;
+    const Gather g{ x.obs, x.zone_obs, idx, count, x.N, x.T, n.Z, n.F, x.goal, XD, W1C };
+    float *const *I = n.img;
+    hipLaunchKernelGGL(k_ppo_prep, dim3((HP * KC + 255) / 256, PPO_N_IMAGES), dim3(256), 0, s, n);
+    // ---- forward
+    hipLaunchKernelGGL((k_ppo_nt<NT_RELU, true>), dim3(rp / 32), dim3(64, NT), 0, s, I[PPO_I_W1], W1C, nullptr, 0, W1C,
+                       n.A1, HP, g);                                                      // relu(zone_net_.0)
+    nt<NT_RELU>(I[PPO_I_W2], HP, n.A1, HP, HP, n.A2, HP, rp, NT, s);                      // relu(zone_net_.2)
+    hipLaunchKernelGGL(k_ppo_pool, dim3((bp * KC + 255) / 256), dim3(256), 0, s, n, g, bp);
+    nt<NT_STORE>(I[PPO_I_W3], HP, n.P, HP, HP, n.CI, KC, bp, NT, s);                      // zone_net_.4 of the mean
+    nt<NT_STORE>(I[PPO_I_WC], KC, n.CI, KC, KC, n.C, HP, bp, NT, s);                      // combine_net_
+    if (n.head == PPO_HEAD_ZONES) zone_head(n, x, g, rp, bp, stats, s);
+    else gaussian_head(n, x, g, bp, stats, s);
+    // ---- the encoder's backward pass, from the embedding's delta in C
     tn(n.C, HP, NT, n.CI, KC, KC, bp, n.partial, s);
-    reduce(n, bp, NT, KC, 0, 0, PPO_COMB_W, 8 + h, 8, h, h, s);
-    reduce(n, bp, NT, KC, 0, HP, PPO_COMB_W, 8 + h, 0, h, 8, s);
+    reduce(n, bp, NT, KC, 0, 0, PPO_COMB_W, XD + h, XD, h, h, s);
+    reduce(n, bp, NT, KC, 0, HP, PPO_COMB_W, XD + h, 0, h, XD, s);
     reduce(n, bp, NT, KC, 0, h, PPO_COMB_B, 1, 0, h, 1, s);
     nt<NT_STORE>(I[PPO_T_WC], HP, n.C, HP, HP, n.CI, KC, bp, NT, s);                      // delta of zone_net_.4's output
     tn(n.CI, KC, NT, n.P, HP, HP, bp, n.partial, s);
@@ -552,11 +802,11 @@ hipError_t launch_ppo_minibatch(const PpoNet &n, const PpoExp &x, const int32_t 
     nt<NT_MASK>(I[PPO_T_W2], HP, n.A2, HP, HP, n.A1, HP, rp, NT, s);                      // delta of zone_net_.0
     {
         const int chunks = (rp + kPpoChunk - 1) / kPpoChunk;
-        hipLaunchKernelGGL((k_ppo_tn<true>), dim3(chunks, NT), dim3(64, 1), 0, s, n.A1, HP, nullptr, 0, 16, rp, n.partial,
+        hipLaunchKernelGGL((k_ppo_tn<true>), dim3(chunks, NT), dim3(64, 1), 0, s, n.A1, HP, nullptr, 0, W1C, rp, n.partial,
                            g);
     }
-    reduce(n, rp, NT, 16, 0, 0, PPO_ZONE_W1, n.K1, 0, h, n.K1, s);
-    reduce(n, rp, NT, 16, 0, 15, PPO_ZONE_B1, 1, 0, h, 1, s);
+    reduce(n, rp, NT, W1C, 0, 0, PPO_ZONE_W1, n.K1, 0, h, n.K1, s);
+    reduce(n, rp, NT, W1C, 0, W1C - 1, PPO_ZONE_B1, 1, 0, h, 1, s);
     launch_norm(n, stats + 5, s);
     return hipGetLastError();
 }

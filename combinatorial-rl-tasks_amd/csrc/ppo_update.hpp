@@ -1,5 +1,5 @@
-// ppo_update.hpp -- the flat actor-critic's PPO update on the device (ppo_update.hip): what zenv_train.cpp hands to
-// the launches.  Internal: not installed.
+// ppo_update.hpp -- the PPO updates on the device (ppo_update.hip): the flat actor-critic's and the Zone-goals agent's
+// two levels'.  What zenv_train.cpp hands to the launches.  Internal: not installed.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -7,12 +7,17 @@
 
 namespace zenvk {
 
-// the tensors of the parameter arena, in zenv_mlp_weights' member order
+// the tensors of the parameter arena, in zenv_mlp_weights' member order (the Zone-goals low level: the same 18 with
+// [obs, goal] where the flat network has obs)
 enum {
     PPO_ZONE_W1 = 0, PPO_ZONE_B1, PPO_ZONE_W2, PPO_ZONE_B2, PPO_ZONE_W3, PPO_ZONE_B3, PPO_COMB_W, PPO_COMB_B,
     PPO_ENC_W, PPO_ENC_B, PPO_MU_W, PPO_MU_B, PPO_STD_W, PPO_STD_B, PPO_CRITIC_W1, PPO_CRITIC_B1, PPO_CRITIC_W2,
     PPO_CRITIC_B2, PPO_SIGMA_W, PPO_SIGMA_B, PPO_MAX_TENSORS
 };
+// The Zone-goals high level's 16 tensors, zenv_hier_weights' hi_* member order: the encoder's eight as above, then
+// actor.0 / actor.2 where the Gaussian actor has enc_ / mu_, then the critic two places earlier (PpoNet::cr)
+enum { PPO_ACTOR_W1 = PPO_ENC_W, PPO_ACTOR_B1 = PPO_ENC_B, PPO_ACTOR_W2 = PPO_MU_W, PPO_ACTOR_B2 = PPO_MU_B };
+enum { PPO_HEAD_GAUSSIAN = 0, PPO_HEAD_ZONES = 1 };
 // the padded weight images k_ppo_prep rebuilds from the arena before every minibatch (I_*: [out][in] with the bias in
 // column h, the A operand of a forward product; T_*: the transpose, the A operand of a backward-data product)
 enum {
@@ -22,6 +27,7 @@ enum {
 constexpr int kPpoChunk = 256;      // rows one wave reduces into one partial of a weight gradient
 constexpr int kPpoStats = 6;        // entropy, value, value std, policy loss, value loss, gradient norm
 constexpr int kPpoNormBlock = 4096; // arena elements per partial of the gradient norm
+constexpr int kPpoReduceSplit = 16; // k_ppo_reduce_split: segments of the chunk range, one thread each
 
 struct PpoHyper {
     float lr, adam_eps, clip_eps, entropy_coef, value_loss_coef, max_grad_norm;
@@ -29,6 +35,13 @@ struct PpoHyper {
 
 struct PpoNet {
     int h, HP, F, Z, K1, KC, dist, n_tensors;
+    int XD;                  // the per-sample input's width: 8 (obs) or 10 ([obs, goal]); K1 = XD + F
+    int W1C;                 // columns of zone_net_.0's image and gathered input: XD + F + 1 rounded up to 8; the last is
+                             // the constant that carries the bias.  KC = HP + XD rounded up to 8
+    int head;                // PPO_HEAD_GAUSSIAN: enc_, mu_, std_;  PPO_HEAD_ZONES: actor.0 / actor.2 over [emb, zone row]
+    int cr;                  // the arena index of critic.0.weight: PPO_CRITIC_W1, or two less under PPO_HEAD_ZONES
+    int split_reduce;        // the partials of a weight gradient are added by kPpoReduceSplit threads per element
+                             // (k_ppo_reduce_split); 0 for the flat learner, whose sums keep their one chain and bits
     int64_t off[PPO_MAX_TENSORS], count[PPO_MAX_TENSORS];   // floats, within an arena
     int64_t arena;                                          // floats of one arena (a multiple of 64)
     float *param, *grad, *exp_avg, *exp_avg_sq;
@@ -39,6 +52,9 @@ struct PpoNet {
     float *P, *C, *Ha, *Hc;  // [samples][HP], samples rounded up to 32
     float *CI;               // [samples][KC]: zone_net_.4's output (HP columns), then the 8 obs features
     float *PRE, *DH;         // [samples][32]: the six head pre-activations, their deltas
+    // PPO_HEAD_ZONES only: relu(actor.0) of every zone row [rows][HP], the logits and their deltas [rows][32] (column 0)
+    float *U, *L, *DL;
+    double *DZ;              // [rows]: the logits' deltas as k_hppo_loss forms them, before they are rounded into DL
     float *SS;               // [samples][8]: the per-sample terms of the statistics
     float *partial;          // the per-chunk partials of one weight gradient
     double *norm_partial;    // [arena / kPpoNormBlock + 1]
@@ -47,10 +63,15 @@ struct PpoNet {
     PpoHyper hyper;
 };
 
-// the handle's experience buffers (time-major) a minibatch is gathered from
+// The experience a minibatch is gathered from.  Sample index i is env i / T, frame i % T, and lies at slot
+// frame * N + env: the handle's time-major buffers with T the frames an env hands out (all of them; one less for the
+// Zone-goals low level, whose last frame is never read), or dense rows with N = the rows and T = 1.
 struct PpoExp {
     const float *obs, *zone_obs, *action, *log_prob, *value, *advantage, *returnn;
     int N, T;
+    const float *goal;              // [slot][2], XD = 10 only
+    const int32_t *hi_action;       // PPO_HEAD_ZONES: the recorded goal [slot] and the goals available at the pick
+    const uint8_t *hi_mask;         // [slot][Z]
 };
 
 // forward, loss and backward of the samples idx[0 .. count) (device memory): gradients into net.grad, the six

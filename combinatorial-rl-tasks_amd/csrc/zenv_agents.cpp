@@ -662,6 +662,7 @@ public:
 static int ensure_exp(zenv_t *h, int T)
 {
     const size_t N = (size_t)h->n_env, ZF = (size_t)h->p.Z * h->p.F;
+    h->exp_hier = false;        // zenv_collect_hier sets it once its records are complete
     if (!h->exp_mem || h->exp.T != T) {
         HIP_TRY(hipStreamSynchronize(h->stream));
         std::vector<float> keep_mask;
@@ -869,6 +870,7 @@ extern "C" int zenv_collect_hier(zenv_t *h, int T, uint64_t policy_seed, uint64_
     HIP_TRY(launch_hier_gather(h->hout, c, h->exp.obs, h->exp.zone_obs, M, h->n_env, h->p.Z, h->p.F, h->stream));
     HIP_TRY(launch_hier_carry(c, h->exp.obs, h->exp.zone_obs, h->n_env, (int)ZF, h->stream));
     h->hi_m = M;
+    h->exp_hier = true;
     if (n_hi) *n_hi = M;
     return ZENV_OK;
 }

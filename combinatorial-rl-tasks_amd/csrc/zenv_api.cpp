@@ -245,9 +245,11 @@ FieldInfo field_info(const zenv *h, int field)
     case ZENV_F_HI_GOAL: return { h->xc.hi_goal, h->hi_kind == 3 ? h->hi_m * 2 * 4 : 0 };
     case ZENV_F_LO_GOAL_DIST: return { h->xc.dist, h->xc_mem ? N * h->xc.T * 4 : 0 };
     case ZENV_F_XY_BOOTSTRAP_GOAL: return { h->xc.boot, h->xc_mem ? N * 2 * 4 : 0 };
-    case ZENV_F_PPO_STATS: {
+    case ZENV_F_PPO_STATS:
+    case ZENV_F_HPPO_LO_STATS:
+    case ZENV_F_HPPO_HI_STATS: {
         int64_t bytes = 0;
-        void *ptr = ppo_stats(h, &bytes);
+        void *ptr = ppo_stats(h, field == ZENV_F_PPO_STATS ? 0 : field - ZENV_F_HPPO_LO_STATS + 1, &bytes);
         return { ptr, bytes };
     }
     default: return { nullptr, 0 };

@@ -1,6 +1,6 @@
 // zenv_handle.hpp -- the handle behind zenv_t and the helpers every translation unit of the C ABI uses (zenv_api.cpp:
-// the environment; zenv_agents.cpp: the networks, the per-step policies, the collectors; zenv_train.cpp: the flat
-// actor-critic's learner).  Internal: not installed.
+// the environment; zenv_agents.cpp: the networks, the per-step policies, the collectors; zenv_train.cpp: the learners).
+// Internal: not installed.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>   // types and prototypes only: librccl is dlopen()ed by the first zenv_comm_* call
@@ -150,6 +150,8 @@ struct zenv {
     void *sk_mem = nullptr;
     // the flat actor-critic's learner (zenv_ppo_init): arenas, workspace, Adam's step count
     PpoState *ppo = nullptr;
+    // the Zone-goals agent's two learners (zenv_hppo_init): [0] the low level, [1] the high level
+    PpoState *hppo[2] = { nullptr, nullptr };
     // goal-conditioned variant (zenv_goal_enable)
     bool goal_enabled = false;
     bool order_enabled = false;   // solver-ordered variant (zenv_order_enable)
@@ -157,6 +159,7 @@ struct zenv {
     // experience buffers (zenv_collect)
     ExpBuffers exp{};
     void *exp_mem = nullptr;
+    bool exp_hier = false;              // the ZENV_F_EXP_* buffers hold zenv_collect_hier's frames (any other collector clears it)
     // zenv_collect_hier: the per-frame records of one call (T), the state that lives from call to call, the flat
     // high-level output (capacity hi_cap rows, hi_m of them written by the last call)
     HierFrames hframes{};
@@ -208,5 +211,6 @@ ZENV_INTERNAL int mlp_range_check(zenv *h);
 ZENV_INTERNAL void ppo_free(zenv *h);
 // ZENV_E_ARG once an update has met (and dropped) a device-resident index out of range; mlp_range_check() asks
 ZENV_INTERNAL int ppo_index_check(zenv *h);
-// ZENV_F_PPO_STATS: the buffer and the bytes the last update call filled
-ZENV_INTERNAL void *ppo_stats(const zenv *h, int64_t *bytes);
+// ZENV_F_PPO_STATS (which = 0), ZENV_F_HPPO_LO_STATS (1), ZENV_F_HPPO_HI_STATS (2): the buffer and the bytes the last
+// update call of that learner filled
+ZENV_INTERNAL void *ppo_stats(const zenv *h, int which, int64_t *bytes);

@@ -1,5 +1,7 @@
-// zenv_train.cpp -- the learner behind the C ABI of include/zenv.h: the flat actor-critic's PPO update on the handle's own
-// experience buffers (zenv_ppo_*).  The kernels: ppo_update.hip.  The networks that act and collect: zenv_agents.cpp.
+// zenv_train.cpp -- the learners behind the C ABI of include/zenv.h: the flat actor-critic's PPO update on the handle's own
+// experience buffers (zenv_ppo_*) and the Zone-goals agent's two (zenv_hppo_*, level 0 = low, 1 = high) on the records
+// of zenv_collect_hier.  One PpoState each, the same code.  The kernels: ppo_update.hip.  The networks that act and
+// collect: zenv_agents.cpp.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -16,19 +18,30 @@ struct PpoState {
     double lr = 0.0;
     int32_t *idx = nullptr;         // host indices, uploaded
     size_t idx_cap = 0;
-    float *stats = nullptr;         // ZENV_F_PPO_STATS [stats_cap][6]
+    float *stats = nullptr;         // ZENV_F_PPO_STATS / ZENV_F_HPPO_*_STATS [stats_cap][6]
     int stats_cap = 0, stats_rows = 0;
 };
 
 namespace {
 
-// element counts of the 20 tensors for hidden size h and zone rows of F features, zenv_mlp_weights' member order
-void tensor_counts(int h, int F, int64_t (&count)[PPO_MAX_TENSORS])
+// which network a learner trains: the width of its per-sample input and its head
+struct NetKind {
+    int XD, head;
+    int w1c() const { return XD == 8 ? 16 : 24; }       // XD + F + 1 <= 16 / 18 columns, rounded up to 8
+};
+constexpr NetKind kFlat{ 8, PPO_HEAD_GAUSSIAN }, kHierLo{ 10, PPO_HEAD_GAUSSIAN }, kHierHi{ 8, PPO_HEAD_ZONES };
+
+// element counts of the tensors for hidden size h and zone rows of F features: zenv_mlp_weights' member order (20; the
+// Zone-goals low level's 18 with XD = 10), or the 16 of zenv_hier_weights' hi_* members
+void tensor_counts(int h, int F, NetKind k, int64_t (&count)[PPO_MAX_TENSORS])
 {
-    const int64_t hh = (int64_t)h * h;
-    const int64_t c[PPO_MAX_TENSORS] = { (int64_t)h * (8 + F), h, hh, h, hh, h, (int64_t)h * (8 + h), h, hh, h, 2 * h, 2,
+    const int64_t hh = (int64_t)h * h, X = k.XD;
+    const int64_t c[PPO_MAX_TENSORS] = { h * (X + F), h, hh, h, hh, h, h * (X + h), h, hh, h, 2 * h, 2,
                                          2 * h, 2, hh, h, h, 1, h, 1 };
-    std::copy(c, c + PPO_MAX_TENSORS, count);
+    const int64_t z[PPO_MAX_TENSORS] = { h * (X + F), h, hh, h, hh, h, h * (X + h), h, (int64_t)h * (h + F), h, h, 1,
+                                         hh, h, h, 1, 0, 0, 0, 0 };
+    const int64_t *src = k.head == PPO_HEAD_ZONES ? z : c;
+    std::copy(src, src + PPO_MAX_TENSORS, count);
 }
 
 void tensor_list(const zenv_mlp_weights *w, const float *(&t)[PPO_MAX_TENSORS])
@@ -43,22 +56,22 @@ struct Layout {
     int HP, KC, rp, bp;
     int64_t chunks;
     // floats of every workspace piece, in carving order
-    int64_t img[PPO_N_IMAGES], a1, p, ci, pre, ss, partial;
+    int64_t img[PPO_N_IMAGES], a1, p, ci, pre, ss, partial, u, l;
     int64_t total;
 };
 
-Layout layout_for(int h, int Z, int max_batch)
+Layout layout_for(int h, int Z, int max_batch, NetKind k)
 {
     Layout l{};
     l.HP = (h + 32) / 32 * 32;          // h <= 191: at least one padded column, the constant's
-    l.KC = l.HP + 8;
+    l.KC = l.HP + (k.XD + 7) / 8 * 8;
     const int64_t rp = ((int64_t)max_batch * Z + 31) / 32 * 32, bp = ((int64_t)max_batch + 31) / 32 * 32;
     l.rp = (int)std::min<int64_t>(rp, INT32_MAX);
     l.bp = (int)std::min<int64_t>(bp, INT32_MAX);
     l.chunks = (rp + kPpoChunk - 1) / kPpoChunk;
     const int64_t HP = l.HP, KC = l.KC;
     for (int i = 0; i < PPO_N_IMAGES; ++i) l.img[i] = HP * HP;
-    l.img[PPO_I_W1] = HP * 16;
+    l.img[PPO_I_W1] = HP * k.w1c();
     l.img[PPO_I_WC] = HP * KC;
     l.img[PPO_I_HA] = l.img[PPO_I_HV] = 32 * HP;
     l.img[PPO_T_HA] = l.img[PPO_T_HV] = HP * 32;
@@ -68,86 +81,143 @@ Layout layout_for(int h, int Z, int max_batch)
     l.pre = bp * 32;
     l.ss = bp * 8;
     l.partial = l.chunks * HP * (HP + 32);
-    l.total = 2 * l.a1 + 4 * l.p + l.ci + 2 * l.pre + l.ss + l.partial;
+    if (k.head == PPO_HEAD_ZONES) l.u = rp * HP, l.l = rp * 32;
+    l.total = 2 * l.a1 + 4 * l.p + l.ci + 2 * l.pre + l.ss + l.partial + l.u + 2 * l.l + l.l / 16;
     for (int i = 0; i < PPO_N_IMAGES; ++i) l.total += l.img[i];
     return l;
 }
 
 bool bad_hyper(double v) { return !std::isfinite(v) || v < 0.0; }
 
+// the rules every learner's tensors and settings follow (t: the learner's tensors in arena order)
+int learner_check(const zenv_config *cfg, int h_dim, const float *const *t, NetKind k, const zenv_ppo_config *pc,
+                  const char *who)
+{
+    if (h_dim < 1 || h_dim > 191) return fail(ZENV_E_ARG, "%sh_dim %d outside [1, 191]", who, h_dim);
+    if (cfg->num_zones < 1 || cfg->num_zones > ZENV_MAX_ZONES)
+        return fail(ZENV_E_ARG, "num_zones %d outside [1, %d]", cfg->num_zones, ZENV_MAX_ZONES);
+    const int critic = k.head == PPO_HEAD_ZONES ? PPO_CRITIC_W1 - 2 : PPO_CRITIC_W1;
+    for (int i = 0; i < critic; ++i)
+        if (!t[i]) return fail(ZENV_E_ARG, "%sa tensor of the weights is null", who);
+    for (int i = critic; i < critic + 4; ++i)
+        if (!t[i]) return fail(ZENV_E_ARG, "%sthe update needs the critic: critic_w1 / _b1 / _w2 / _b2", who);
+    const bool hier = k.XD != 8 || k.head != PPO_HEAD_GAUSSIAN;
+    if (hier && pc->distributional_value)
+        return fail(ZENV_E_ARG, "%sdistributional_value must be 0: the Zone-goals critics are plain", who);
+    for (double v : { pc->lr, pc->adam_eps, pc->clip_eps, pc->entropy_coef, pc->value_loss_coef })
+        if (bad_hyper(v)) return fail(ZENV_E_ARG, "%sa hyper-parameter is negative or not finite (%g)", who, v);
+    // the Zone-goals reference takes the norm and does not clip: +inf stands for that
+    if (bad_hyper(pc->max_grad_norm) && !(hier && pc->max_grad_norm == INFINITY))
+        return fail(ZENV_E_ARG, "%sa hyper-parameter is negative or not finite (%g)", who, pc->max_grad_norm);
+    if (pc->max_batch < 1) return fail(ZENV_E_ARG, "%smax_batch must be >= 1", who);
+    const Layout l = layout_for(h_dim, cfg->num_zones, pc->max_batch, k);
+    if (l.total >= ((int64_t)1 << 31))
+        return fail(ZENV_E_ARG, "%smax_batch %d x %d zones needs a workspace of %lld floats, the limit is 2^31: use smaller "
+                    "minibatches", who, pc->max_batch, cfg->num_zones, (long long)l.total);
+    return ZENV_OK;
+}
+
+void hier_tensor_lists(const zenv_hier_weights *w, const float *(&lo)[PPO_MAX_TENSORS], const float *(&hi)[PPO_MAX_TENSORS])
+{
+    const float *l[PPO_MAX_TENSORS] = { w->lo_zone_w1, w->lo_zone_b1, w->lo_zone_w2, w->lo_zone_b2, w->lo_zone_w3,
+                                        w->lo_zone_b3, w->lo_comb_w, w->lo_comb_b, w->lo_enc_w, w->lo_enc_b, w->lo_mu_w,
+                                        w->lo_mu_b, w->lo_std_w, w->lo_std_b, w->lo_critic_w1, w->lo_critic_b1,
+                                        w->lo_critic_w2, w->lo_critic_b2, nullptr, nullptr };
+    const float *u[PPO_MAX_TENSORS] = { w->hi_zone_w1, w->hi_zone_b1, w->hi_zone_w2, w->hi_zone_b2, w->hi_zone_w3,
+                                        w->hi_zone_b3, w->hi_comb_w, w->hi_comb_b, w->hi_actor_w1, w->hi_actor_b1,
+                                        w->hi_actor_w2, w->hi_actor_b2, w->hi_critic_w1, w->hi_critic_b1, w->hi_critic_w2,
+                                        w->hi_critic_b2, nullptr, nullptr, nullptr, nullptr };
+    std::copy(l, l + PPO_MAX_TENSORS, lo);
+    std::copy(u, u + PPO_MAX_TENSORS, hi);
+}
+
 }  // namespace
 
 extern "C" int zenv_ppo_check(const zenv_config *cfg, const zenv_mlp_weights *w, const zenv_ppo_config *pc)
 {
     if (!cfg || !w || !pc) return fail(ZENV_E_ARG, "null argument");
-    if (w->h_dim < 1 || w->h_dim > 191) return fail(ZENV_E_ARG, "h_dim %d outside [1, 191]", w->h_dim);
-    if (cfg->num_zones < 1 || cfg->num_zones > ZENV_MAX_ZONES)
-        return fail(ZENV_E_ARG, "num_zones %d outside [1, %d]", cfg->num_zones, ZENV_MAX_ZONES);
     const float *t[PPO_MAX_TENSORS];
     tensor_list(w, t);
-    for (int i = 0; i < PPO_CRITIC_W1; ++i)
-        if (!t[i]) return fail(ZENV_E_ARG, "zenv_mlp_weights has a null tensor");
-    for (int i = PPO_CRITIC_W1; i <= PPO_CRITIC_B2; ++i)
-        if (!t[i]) return fail(ZENV_E_ARG, "the update needs the critic: critic_w1 / _b1 / _w2 / _b2");
+    if (int rc = learner_check(cfg, w->h_dim, t, kFlat, pc, "")) return rc;
     const int n_sigma = (w->critic_sigma_w != nullptr) + (w->critic_sigma_b != nullptr);
     if (pc->distributional_value && n_sigma != 2)
         return fail(ZENV_E_ARG, "distributional_value needs critic_sigma_w and critic_sigma_b");
     if (!pc->distributional_value && n_sigma != 0)
         return fail(ZENV_E_ARG, "critic_sigma_* given without distributional_value");
-    for (double v : { pc->lr, pc->adam_eps, pc->clip_eps, pc->entropy_coef, pc->value_loss_coef, pc->max_grad_norm })
-        if (bad_hyper(v)) return fail(ZENV_E_ARG, "a hyper-parameter is negative or not finite (%g)", v);
-    if (pc->max_batch < 1) return fail(ZENV_E_ARG, "max_batch must be >= 1");
-    const Layout l = layout_for(w->h_dim, cfg->num_zones, pc->max_batch);
-    if (l.total >= ((int64_t)1 << 31))
-        return fail(ZENV_E_ARG, "max_batch %d x %d zones needs a workspace of %lld floats, the limit is 2^31: use smaller "
-                    "minibatches", pc->max_batch, cfg->num_zones, (long long)l.total);
     return ZENV_OK;
 }
 
-void ppo_free(zenv *h)
+extern "C" int zenv_hppo_check(const zenv_config *cfg, const zenv_hier_weights *w, const zenv_ppo_config *lo,
+                               const zenv_ppo_config *hi)
 {
-    PpoState *s = h->ppo;
+    if (!cfg || !w || !lo || !hi) return fail(ZENV_E_ARG, "null argument");
+    if (w->zone_feat != zenv_zone_feat(cfg))
+        return fail(ZENV_E_ARG, "zone_feat %d: the handle's zone rows have %d features", w->zone_feat, zenv_zone_feat(cfg));
+    const float *tl[PPO_MAX_TENSORS], *th[PPO_MAX_TENSORS];
+    hier_tensor_lists(w, tl, th);
+    if (int rc = learner_check(cfg, w->h_dim, tl, kHierLo, lo, "low level: ")) return rc;
+    return learner_check(cfg, w->h_dim, th, kHierHi, hi, "high level: ");
+}
+
+static void learner_free(PpoState *&s)
+{
     if (!s) return;
     for (void *m : { s->arena_mem, s->ws_mem, (void *)s->idx, (void *)s->stats })
         if (m) (void)hipFree(m);
     if (s->net.bad_index) (void)hipHostFree(s->net.bad_index);
     delete s;
-    h->ppo = nullptr;
+    s = nullptr;
+}
+
+void ppo_free(zenv *h)
+{
+    learner_free(h->ppo);
+    learner_free(h->hppo[0]);
+    learner_free(h->hppo[1]);
 }
 
 int ppo_index_check(zenv *h)
 {
-    if (!h->ppo || !h->ppo->net.bad_index || !*(volatile int *)h->ppo->net.bad_index) return ZENV_OK;
-    *(volatile int *)h->ppo->net.bad_index = 0;
-    return fail(ZENV_E_ARG, "a device-resident minibatch index lay outside [0, envs x frames): its sample was dropped and "
-                            "the update since the last synchronising call is invalid");
+    bool bad = false;
+    for (PpoState *s : { h->ppo, h->hppo[0], h->hppo[1] })
+        if (s && s->net.bad_index && *(volatile int *)s->net.bad_index) {
+            *(volatile int *)s->net.bad_index = 0;
+            bad = true;
+        }
+    if (!bad) return ZENV_OK;
+    return fail(ZENV_E_ARG, "a device-resident minibatch index lay outside [0, envs x frames), or a recorded goal was "
+                            "not among its row's available goals: the sample was dropped and the update since the last "
+                            "synchronising call is invalid");
 }
 
-void *ppo_stats(const zenv *h, int64_t *bytes)
+void *ppo_stats(const zenv *h, int which, int64_t *bytes)
 {
-    *bytes = h->ppo ? (int64_t)h->ppo->stats_rows * kPpoStats * 4 : 0;
-    return h->ppo ? h->ppo->stats : nullptr;
+    const PpoState *s = which == 0 ? h->ppo : h->hppo[which - 1];
+    *bytes = s ? (int64_t)s->stats_rows * kPpoStats * 4 : 0;
+    return s ? s->stats : nullptr;
 }
 
-extern "C" int zenv_ppo_init(zenv_t *h, const zenv_mlp_weights *w, const zenv_ppo_config *pc)
+// a learner of kind k in `slot` (replacing what is there) from the tensors t in arena order; checked by the caller
+static int learner_create(zenv *h, PpoState *&slot, int h_dim, const float *const *t, NetKind k, const zenv_ppo_config *pc)
 {
-    if (!h || !w || !pc) return fail(ZENV_E_ARG, "null argument");
-    if (int rc = zenv_ppo_check(&h->cfg, w, pc)) return rc;
     if (int rc = use_device(h)) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
-    ppo_free(h);
+    learner_free(slot);
     PpoState *s = new PpoState();
-    h->ppo = s;
+    slot = s;
     PpoNet &n = s->net;
-    const Layout l = layout_for(w->h_dim, h->p.Z, pc->max_batch);
-    n.h = w->h_dim, n.HP = l.HP, n.F = h->p.F, n.Z = h->p.Z, n.K1 = 8 + h->p.F, n.KC = l.KC;
+    const Layout l = layout_for(h_dim, h->p.Z, pc->max_batch, k);
+    n.h = h_dim, n.HP = l.HP, n.F = h->p.F, n.Z = h->p.Z, n.K1 = k.XD + h->p.F, n.KC = l.KC;
+    n.XD = k.XD, n.W1C = k.w1c(), n.head = k.head;
+    n.cr = k.head == PPO_HEAD_ZONES ? PPO_CRITIC_W1 - 2 : PPO_CRITIC_W1;
+    n.split_reduce = (k.XD != 8 || k.head != PPO_HEAD_GAUSSIAN) ? 1 : 0;     // the Zone-goals learners
     n.dist = pc->distributional_value ? 1 : 0;
-    n.n_tensors = n.dist ? 20 : 18;
+    n.n_tensors = k.head == PPO_HEAD_ZONES ? 16 : n.dist ? 20 : 18;
     n.max_batch = pc->max_batch;
     s->lr = pc->lr;
     n.hyper = PpoHyper{ (float)pc->lr, (float)pc->adam_eps, (float)pc->clip_eps, (float)pc->entropy_coef,
                         (float)pc->value_loss_coef, (float)pc->max_grad_norm };
-    tensor_counts(n.h, n.F, n.count);
+    tensor_counts(n.h, n.F, k, n.count);
     int64_t at = 0;
     for (int i = 0; i < PPO_MAX_TENSORS; ++i) {         // every tensor starts on a 256-byte boundary
         n.off[i] = at;
@@ -157,8 +227,6 @@ extern "C" int zenv_ppo_init(zenv_t *h, const zenv_mlp_weights *w, const zenv_pp
     n.arena = at;
     // ---- the four arenas
     std::vector<float> host((size_t)n.arena, 0.f);
-    const float *t[PPO_MAX_TENSORS];
-    tensor_list(w, t);
     for (int i = 0; i < n.n_tensors; ++i) std::memcpy(host.data() + n.off[i], t[i], (size_t)n.count[i] * sizeof(float));
     const size_t arena_bytes = (size_t)n.arena * sizeof(float);
     HIP_TRY(hipMalloc(&s->arena_mem, 4 * arena_bytes));
@@ -180,6 +248,8 @@ extern "C" int zenv_ppo_init(zenv_t *h, const zenv_mlp_weights *w, const zenv_pp
     n.PRE = take(l.pre), n.DH = take(l.pre);
     n.SS = take(l.ss);
     n.partial = take(l.partial);
+    n.U = take(l.u), n.L = take(l.l), n.DL = take(l.l);
+    n.DZ = reinterpret_cast<double *>(take(l.l / 16));      // rp doubles; every piece before it is a multiple of 32 floats
     n.norm_partial = reinterpret_cast<double *>(f);      // l.total is a multiple of 8 floats: 8-byte aligned
     n.scalars = reinterpret_cast<float *>(n.norm_partial + norm_parts + 1);
     HIP_TRY(hipHostMalloc((void **)&n.bad_index, sizeof(int), hipHostMallocDefault));
@@ -190,11 +260,56 @@ extern "C" int zenv_ppo_init(zenv_t *h, const zenv_mlp_weights *w, const zenv_pp
     return ZENV_OK;
 }
 
-extern "C" int zenv_ppo_tensor(zenv_t *h, int which, int index, void **dev_ptr, int64_t *count)
+extern "C" int zenv_ppo_init(zenv_t *h, const zenv_mlp_weights *w, const zenv_ppo_config *pc)
 {
-    if (!h || !dev_ptr || !count) return fail(ZENV_E_ARG, "null argument");
-    if (!h->ppo) return fail(ZENV_E_STATE, "zenv_ppo_init first");
-    const PpoNet &n = h->ppo->net;
+    if (!h || !w || !pc) return fail(ZENV_E_ARG, "null argument");
+    if (int rc = zenv_ppo_check(&h->cfg, w, pc)) return rc;
+    const float *t[PPO_MAX_TENSORS];
+    tensor_list(w, t);
+    return learner_create(h, h->ppo, w->h_dim, t, kFlat, pc);
+}
+
+extern "C" int zenv_hppo_init(zenv_t *h, const zenv_hier_weights *w, const zenv_ppo_config *lo, const zenv_ppo_config *hi)
+{
+    if (!h || !w || !lo || !hi) return fail(ZENV_E_ARG, "null argument");
+    if (int rc = zenv_hppo_check(&h->cfg, w, lo, hi)) return rc;
+    const float *tl[PPO_MAX_TENSORS], *th[PPO_MAX_TENSORS];
+    hier_tensor_lists(w, tl, th);
+    int rc = learner_create(h, h->hppo[0], w->h_dim, tl, kHierLo, lo);
+    if (!rc) rc = learner_create(h, h->hppo[1], w->h_dim, th, kHierHi, hi);
+    if (rc) {                   // no half-pair: a failed init leaves the handle without either learner
+        learner_free(h->hppo[0]);
+        learner_free(h->hppo[1]);
+    }
+    return rc;
+}
+
+namespace {
+
+// What an entry point works on: the flat learner, or level 0 / 1 of the Zone-goals pair with the experience they read.
+struct Learner {
+    PpoState *s = nullptr;
+    int level = -1;                 // -1: the flat learner
+};
+
+int find_learner(zenv *h, int level, bool hier, Learner &out)
+{
+    if (!h) return fail(ZENV_E_ARG, "null handle");
+    if (!hier) {
+        if (!h->ppo) return fail(ZENV_E_STATE, "zenv_ppo_init first");
+        out = Learner{ h->ppo, -1 };
+        return ZENV_OK;
+    }
+    if (level != 0 && level != 1) return fail(ZENV_E_ARG, "level %d: 0 is the low level, 1 the high level", level);
+    if (!h->hppo[level]) return fail(ZENV_E_STATE, "zenv_hppo_init first");
+    out = Learner{ h->hppo[level], level };
+    return ZENV_OK;
+}
+
+int learner_tensor(const Learner &l, int which, int index, void **dev_ptr, int64_t *count)
+{
+    if (!dev_ptr || !count) return fail(ZENV_E_ARG, "null argument");
+    const PpoNet &n = l.s->net;
     if (which < ZENV_PPO_PARAM || which > ZENV_PPO_EXP_AVG_SQ) return fail(ZENV_E_ARG, "unknown arena %d", which);
     if (index < -1 || index >= n.n_tensors) return fail(ZENV_E_ARG, "tensor index %d outside [-1, %d)", index, n.n_tensors);
     float *base = n.param + (int64_t)which * n.arena;
@@ -204,12 +319,12 @@ extern "C" int zenv_ppo_tensor(zenv_t *h, int which, int index, void **dev_ptr, 
 }
 
 // a tensor (or, index = -1, a whole arena) to or from host memory, behind everything enqueued; both wait for the copy
-static int ppo_copy(zenv_t *h, int which, int index, void *host, bool to_host)
+int learner_copy(zenv *h, const Learner &l, int which, int index, void *host, bool to_host)
 {
     if (!host) return fail(ZENV_E_ARG, "null argument");
     void *dev = nullptr;
     int64_t count = 0;
-    if (int rc = zenv_ppo_tensor(h, which, index, &dev, &count)) return rc;
+    if (int rc = learner_tensor(l, which, index, &dev, &count)) return rc;
     if (int rc = use_device(h)) return rc;
     if (to_host) HIP_TRY(hipMemcpyAsync(host, dev, (size_t)count * 4, hipMemcpyDeviceToHost, h->stream));
     else HIP_TRY(hipMemcpyAsync(dev, host, (size_t)count * 4, hipMemcpyHostToDevice, h->stream));
@@ -217,46 +332,54 @@ static int ppo_copy(zenv_t *h, int which, int index, void *host, bool to_host)
     return mlp_range_check(h);
 }
 
-extern "C" int zenv_ppo_read(zenv_t *h, int which, int index, float *dst) { return ppo_copy(h, which, index, dst, true); }
-
-extern "C" int zenv_ppo_write(zenv_t *h, int which, int index, const float *src)
+int learner_set_step(const Learner &l, int64_t step)
 {
-    return ppo_copy(h, which, index, const_cast<float *>(src), false);
-}
-
-extern "C" int zenv_ppo_get_step(zenv_t *h, int64_t *step)
-{
-    if (!h || !step) return fail(ZENV_E_ARG, "null argument");
-    if (!h->ppo) return fail(ZENV_E_STATE, "zenv_ppo_init first");
-    *step = h->ppo->step;
-    return ZENV_OK;
-}
-
-extern "C" int zenv_ppo_set_step(zenv_t *h, int64_t step)
-{
-    if (!h) return fail(ZENV_E_ARG, "null handle");
-    if (!h->ppo) return fail(ZENV_E_STATE, "zenv_ppo_init first");
     if (step < 0) return fail(ZENV_E_ARG, "the step count must be >= 0");
-    h->ppo->step = step;
+    l.s->step = step;
     return ZENV_OK;
 }
 
-namespace {
+// the experience the learner gathers from, and how many sample indexes it has; ZENV_E_STATE when the handle holds none
+// of the learner's kind
+int learner_exp(const zenv *h, const Learner &l, PpoExp &x, int64_t &samples)
+{
+    const ExpBuffers &e = h->exp;
+    if (l.level < 0) {
+        if (!h->exp_mem) return fail(ZENV_E_STATE, "zenv_collect first: the handle holds no experience");
+        x = PpoExp{ e.obs, e.zone_obs, e.action, e.log_prob, e.value, e.advantage, e.returnn, h->n_env, e.T, nullptr,
+                    nullptr, nullptr };
+        samples = (int64_t)h->n_env * e.T;
+        return ZENV_OK;
+    }
+    if (!h->exp_mem || !h->exp_hier || h->hi_kind != 0 || !h->hframes.lo_goal)
+        return fail(ZENV_E_STATE, "zenv_collect_hier first: the ZENV_F_EXP_* / ZENV_F_LO_* / ZENV_F_HI_* buffers do not "
+                                  "hold its records");
+    if (l.level == 0) {         // frames 0 .. T-2 of every env (hrl_policy_planner.py:68)
+        x = PpoExp{ e.obs, e.zone_obs, e.action, e.log_prob, e.value, e.advantage, e.returnn, h->n_env, e.T - 1,
+                    h->hframes.lo_goal, nullptr, nullptr };
+        samples = (int64_t)h->n_env * (e.T - 1);
+        return ZENV_OK;
+    }
+    if (h->hi_m < 1) return fail(ZENV_E_STATE, "the last zenv_collect_hier closed no high-level transition (M = 0)");
+    const HierOut &o = h->hout;  // dense env-major rows
+    x = PpoExp{ o.obs, o.zone_obs, nullptr, o.log_prob, o.value, o.advantage, o.returnn, (int)h->hi_m, 1, nullptr, o.action,
+                o.action_mask };
+    samples = h->hi_m;
+    return ZENV_OK;
+}
 
 // the checks every update call shares; *idx_dev: the indices on the device
-int ppo_indices(zenv *h, const int32_t *idx, int total, int on_device, const int32_t **idx_dev)
+int learner_indices(zenv *h, PpoState *s, const int32_t *idx, int total, int on_device, int64_t samples,
+                    const int32_t **idx_dev)
 {
-    PpoState *s = h->ppo;
-    if (!h->exp_mem) return fail(ZENV_E_STATE, "zenv_collect first: the handle holds no experience");
     if (int rc = use_device(h)) return rc;
     if (on_device) {
         *idx_dev = idx;
         return ZENV_OK;
     }
-    const int64_t frames = (int64_t)h->n_env * h->exp.T;
     for (int i = 0; i < total; ++i)
-        if (idx[i] < 0 || idx[i] >= frames)
-            return fail(ZENV_E_ARG, "index %d (at %d) outside [0, %lld)", idx[i], i, (long long)frames);
+        if (idx[i] < 0 || idx[i] >= samples)
+            return fail(ZENV_E_ARG, "index %d (at %d) outside [0, %lld)", idx[i], i, (long long)samples);
     if (s->idx_cap < (size_t)total) {
         HIP_TRY(hipStreamSynchronize(h->stream));
         if (s->idx) HIP_TRY(hipFree(s->idx));
@@ -269,9 +392,8 @@ int ppo_indices(zenv *h, const int32_t *idx, int total, int on_device, const int
     return ZENV_OK;
 }
 
-int ppo_stats_rows(zenv *h, int rows)
+int learner_stats_rows(zenv *h, PpoState *s, int rows)
 {
-    PpoState *s = h->ppo;
     if (rows > s->stats_cap) {
         HIP_TRY(hipStreamSynchronize(h->stream));
         HIP_TRY(hipFree(s->stats));
@@ -283,15 +405,8 @@ int ppo_stats_rows(zenv *h, int rows)
     return ZENV_OK;
 }
 
-PpoExp exp_of(const zenv *h)
+int learner_step(zenv *h, PpoState *s)
 {
-    const ExpBuffers &x = h->exp;
-    return PpoExp{ x.obs, x.zone_obs, x.action, x.log_prob, x.value, x.advantage, x.returnn, h->n_env, x.T };
-}
-
-int ppo_step(zenv *h)
-{
-    PpoState *s = h->ppo;
     s->step += 1;
     // torch.optim.Adam forms these in Python floats: step_size = lr / (1 - beta1^t), sqrt(1 - beta2^t)
     const double bc1 = 1.0 - std::pow(0.9, (double)s->step), bc2 = 1.0 - std::pow(0.999, (double)s->step);
@@ -299,45 +414,149 @@ int ppo_step(zenv *h)
     return ZENV_OK;
 }
 
+int learner_minibatch(zenv *h, const Learner &l, const int32_t *idx, int count, int idx_on_device, int apply)
+{
+    if (!idx) return fail(ZENV_E_ARG, "null argument");
+    PpoState *s = l.s;
+    if (count < 1 || count > s->net.max_batch)
+        return fail(ZENV_E_ARG, "count %d outside [1, max_batch = %d]", count, s->net.max_batch);
+    PpoExp x{};
+    int64_t samples = 0;
+    if (int rc = learner_exp(h, l, x, samples)) return rc;
+    const int32_t *idx_dev = nullptr;
+    if (int rc = learner_indices(h, s, idx, count, idx_on_device, samples, &idx_dev)) return rc;
+    if (int rc = learner_stats_rows(h, s, 1)) return rc;
+    HIP_TRY(launch_ppo_minibatch(s->net, x, idx_dev, count, s->stats, h->stream));
+    return apply ? learner_step(h, s) : ZENV_OK;
+}
+
+int learner_apply(zenv *h, const Learner &l)
+{
+    if (int rc = use_device(h)) return rc;
+    return learner_step(h, l.s);
+}
+
+int learner_epoch(zenv *h, const Learner &l, const int32_t *order, int total, int batch_size, int on_device)
+{
+    if (!order) return fail(ZENV_E_ARG, "null argument");
+    PpoState *s = l.s;
+    if (total < 1) return fail(ZENV_E_ARG, "total must be >= 1");
+    if (batch_size < 1 || batch_size > s->net.max_batch)
+        return fail(ZENV_E_ARG, "batch_size %d outside [1, max_batch = %d]", batch_size, s->net.max_batch);
+    PpoExp x{};
+    int64_t samples = 0;
+    if (int rc = learner_exp(h, l, x, samples)) return rc;
+    const int32_t *idx_dev = nullptr;
+    if (int rc = learner_indices(h, s, order, total, on_device, samples, &idx_dev)) return rc;
+    const int n_mb = (total + batch_size - 1) / batch_size;
+    if (int rc = learner_stats_rows(h, s, n_mb)) return rc;
+    for (int k = 0; k < n_mb; ++k) {
+        const int lo = k * batch_size, count = std::min(batch_size, total - lo);
+        HIP_TRY(launch_ppo_minibatch(s->net, x, idx_dev + lo, count, s->stats + (size_t)k * kPpoStats, h->stream));
+        if (int rc = learner_step(h, s)) return rc;
+    }
+    return ZENV_OK;
+}
+
 }  // namespace
 
+// every entry point: find the learner, then the shared body
+#define LEARNER(h, level, hier)                                   \
+    Learner l;                                                    \
+    if (int rc = find_learner(h, level, hier, l)) return rc
+
+extern "C" int zenv_ppo_tensor(zenv_t *h, int which, int index, void **dev_ptr, int64_t *count)
+{
+    if (!h || !dev_ptr || !count) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, 0, false);
+    return learner_tensor(l, which, index, dev_ptr, count);
+}
+extern "C" int zenv_ppo_read(zenv_t *h, int which, int index, float *dst)
+{
+    if (!dst) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, 0, false);
+    return learner_copy(h, l, which, index, dst, true);
+}
+extern "C" int zenv_ppo_write(zenv_t *h, int which, int index, const float *src)
+{
+    if (!src) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, 0, false);
+    return learner_copy(h, l, which, index, const_cast<float *>(src), false);
+}
+extern "C" int zenv_ppo_get_step(zenv_t *h, int64_t *step)
+{
+    if (!h || !step) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, 0, false);
+    *step = l.s->step;
+    return ZENV_OK;
+}
+extern "C" int zenv_ppo_set_step(zenv_t *h, int64_t step)
+{
+    LEARNER(h, 0, false);
+    return learner_set_step(l, step);
+}
 extern "C" int zenv_ppo_minibatch(zenv_t *h, const int32_t *idx, int count, int idx_on_device, int apply)
 {
     if (!h || !idx) return fail(ZENV_E_ARG, "null argument");
-    if (!h->ppo) return fail(ZENV_E_STATE, "zenv_ppo_init first");
-    if (count < 1 || count > h->ppo->net.max_batch)
-        return fail(ZENV_E_ARG, "count %d outside [1, max_batch = %d]", count, h->ppo->net.max_batch);
-    const int32_t *idx_dev = nullptr;
-    if (int rc = ppo_indices(h, idx, count, idx_on_device, &idx_dev)) return rc;
-    if (int rc = ppo_stats_rows(h, 1)) return rc;
-    HIP_TRY(launch_ppo_minibatch(h->ppo->net, exp_of(h), idx_dev, count, h->ppo->stats, h->stream));
-    return apply ? ppo_step(h) : ZENV_OK;
+    LEARNER(h, 0, false);
+    return learner_minibatch(h, l, idx, count, idx_on_device, apply);
 }
-
 extern "C" int zenv_ppo_apply(zenv_t *h)
 {
-    if (!h) return fail(ZENV_E_ARG, "null handle");
-    if (!h->ppo) return fail(ZENV_E_STATE, "zenv_ppo_init first");
-    if (int rc = use_device(h)) return rc;
-    return ppo_step(h);
+    LEARNER(h, 0, false);
+    return learner_apply(h, l);
 }
-
 extern "C" int zenv_ppo_epoch(zenv_t *h, const int32_t *order, int total, int batch_size, int on_device)
 {
     if (!h || !order) return fail(ZENV_E_ARG, "null argument");
-    if (!h->ppo) return fail(ZENV_E_STATE, "zenv_ppo_init first");
-    if (total < 1) return fail(ZENV_E_ARG, "total must be >= 1");
-    if (batch_size < 1 || batch_size > h->ppo->net.max_batch)
-        return fail(ZENV_E_ARG, "batch_size %d outside [1, max_batch = %d]", batch_size, h->ppo->net.max_batch);
-    const int32_t *idx_dev = nullptr;
-    if (int rc = ppo_indices(h, order, total, on_device, &idx_dev)) return rc;
-    const int n_mb = (total + batch_size - 1) / batch_size;
-    if (int rc = ppo_stats_rows(h, n_mb)) return rc;
-    for (int k = 0; k < n_mb; ++k) {
-        const int lo = k * batch_size, count = std::min(batch_size, total - lo);
-        HIP_TRY(launch_ppo_minibatch(h->ppo->net, exp_of(h), idx_dev + lo, count, h->ppo->stats + (size_t)k * kPpoStats,
-                                     h->stream));
-        if (int rc = ppo_step(h)) return rc;
-    }
+    LEARNER(h, 0, false);
+    return learner_epoch(h, l, order, total, batch_size, on_device);
+}
+
+extern "C" int zenv_hppo_tensor(zenv_t *h, int level, int which, int index, void **dev_ptr, int64_t *count)
+{
+    if (!h || !dev_ptr || !count) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, level, true);
+    return learner_tensor(l, which, index, dev_ptr, count);
+}
+extern "C" int zenv_hppo_read(zenv_t *h, int level, int which, int index, float *dst)
+{
+    if (!dst) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, level, true);
+    return learner_copy(h, l, which, index, dst, true);
+}
+extern "C" int zenv_hppo_write(zenv_t *h, int level, int which, int index, const float *src)
+{
+    if (!src) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, level, true);
+    return learner_copy(h, l, which, index, const_cast<float *>(src), false);
+}
+extern "C" int zenv_hppo_get_step(zenv_t *h, int level, int64_t *step)
+{
+    if (!h || !step) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, level, true);
+    *step = l.s->step;
     return ZENV_OK;
+}
+extern "C" int zenv_hppo_set_step(zenv_t *h, int level, int64_t step)
+{
+    LEARNER(h, level, true);
+    return learner_set_step(l, step);
+}
+extern "C" int zenv_hppo_minibatch(zenv_t *h, int level, const int32_t *idx, int count, int idx_on_device, int apply)
+{
+    if (!h || !idx) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, level, true);
+    return learner_minibatch(h, l, idx, count, idx_on_device, apply);
+}
+extern "C" int zenv_hppo_apply(zenv_t *h, int level)
+{
+    LEARNER(h, level, true);
+    return learner_apply(h, l);
+}
+extern "C" int zenv_hppo_epoch(zenv_t *h, int level, const int32_t *order, int total, int batch_size, int on_device)
+{
+    if (!h || !order) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, level, true);
+    return learner_epoch(h, l, order, total, batch_size, on_device);
 }

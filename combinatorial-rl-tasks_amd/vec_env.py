@@ -8,6 +8,7 @@ re-reset inside the same launch and report the next episode's first observation 
 terminal reward/done, exactly like ``worker`` (penv.py:7-11).
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -20,7 +21,8 @@ from .agents import (_HIER_ENC, _HIER_CRITIC, HIER_HI_KEYS, HIER_LO_KEYS, SKILL_
                      skill_tensors_from_state_dicts, option_tensors_from_state_dicts, inverse_tensors_from_state_dict,
                      check_collect_hier_args, check_collect_skill_args, check_collect_option_args,
                      hier_experience_layout, skill_experience_layout, option_experience_layout, skill_num_frames,
-                     check_collect_xy_args, xy_experience_layout, ppo_state_dict_keys, ppo_batch_indexes)
+                     check_collect_xy_args, xy_experience_layout, ppo_state_dict_keys, ppo_batch_indexes,
+                     hppo_state_dict_keys, hppo_batch_indexes)
 
 _FIELD_DTYPES = {
     nat.F_OBS: np.float32, nat.F_ZONE_OBS: np.float32, nat.F_REWARD: np.float32,
@@ -43,12 +45,116 @@ _FIELD_DTYPES = {
     nat.F_XY_GOAL: np.float32, nat.F_XY_GOAL_MU: np.float32, nat.F_XY_GOAL_STD: np.float32, nat.F_XY_VALUE: np.float32,
     nat.F_XY_GOAL_AGE: np.int32, nat.F_HI_GOAL: np.float32, nat.F_LO_GOAL_DIST: np.float32,
     nat.F_XY_BOOTSTRAP_GOAL: np.float32, nat.F_PPO_STATS: np.float32,
+    nat.F_HPPO_LO_STATS: np.float32, nat.F_HPPO_HI_STATS: np.float32,
 }
 
 
 def _as_host_f32(v):
     """A torch tensor (any device) or anything numpy takes -> numpy float32."""
     return np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, np.float32)
+
+
+class _Learner:
+    """One device learner behind the ppo_* (level None: zenv_ppo_*) or hppo_* (zenv_hppo_* with a level) methods: the
+    arenas' tensors under their names, Adam's state, the update calls and the statistics."""
+
+    def __init__(self, handle, level, keys, shapes, lr, adam_eps, stats_field):
+        self._h, self.level, self.keys, self.shapes = handle, level, keys, shapes
+        self.lr, self.adam_eps, self.stats_field = lr, adam_eps, stats_field
+
+    def _call(self, name, *args):
+        if self.level is None:
+            check(getattr(lib(), "zenv_ppo_" + name)(self._h, *args))
+        else:
+            check(getattr(lib(), "zenv_hppo_" + name)(self._h, int(self.level), *args))
+
+    def tensor_ptr(self, which, index):
+        p, n = C.c_void_p(), C.c_int64()
+        self._call("tensor", int(which), int(index), C.byref(p), C.byref(n))
+        return p.value, n.value
+
+    def _need_init(self):
+        """Before the learner's init there are no names to walk: let the library refuse."""
+        if not self.keys:
+            self.tensor_ptr(nat.PPO_PARAM, -1)
+            raise ZenvError(nat.E_STATE, "the learner was not created through this object: call its init here")
+
+    def tensors(self, which=nat.PPO_PARAM):
+        self._need_init()
+        out = {}
+        for i, name in enumerate(self.keys):
+            out[name] = a = np.empty(self.shapes[name], np.float32)
+            self._call("read", int(which), i, a.ctypes.data)
+        return out
+
+    def set_tensors(self, tensors, which=nat.PPO_PARAM):
+        self._need_init()
+        for i, name in enumerate(self.keys):
+            if name in tensors:
+                a = np.ascontiguousarray(tensors[name], np.float32)
+                if a.shape != self.shapes[name]:
+                    raise ValueError(f"{name}: shape {a.shape}, expected {self.shapes[name]}")
+                self._call("write", int(which), i, a.ctypes.data)
+
+    def state_dict(self):
+        t = self.tensors()
+        return {key: t[name] for name, key in self.keys.items()}
+
+    def load_state_dict(self, state_dict):
+        self.set_tensors({name: _as_host_f32(state_dict[key]) for name, key in self.keys.items()})
+
+    def optimizer_state(self):
+        m, v = self.tensors(nat.PPO_EXP_AVG), self.tensors(nat.PPO_EXP_AVG_SQ)
+        step = self.get_step()
+        state = {i: {"step": float(step), "exp_avg": m[name], "exp_avg_sq": v[name]}
+                 for i, name in enumerate(self.keys)} if step else {}
+        group = {"lr": self.lr, "betas": (0.9, 0.999), "eps": self.adam_eps, "weight_decay": 0,
+                 "amsgrad": False, "params": list(range(len(self.keys)))}
+        return {"state": state, "param_groups": [group]}
+
+    def load_optimizer_state(self, state):
+        names = list(self.keys)
+        st = state["state"]
+        zeros = {n: np.zeros(self.shapes[n], np.float32) for n in names}
+        self.set_tensors({n: _as_host_f32(st[i]["exp_avg"]) for i, n in enumerate(names)} if st else zeros,
+                         nat.PPO_EXP_AVG)
+        self.set_tensors({n: _as_host_f32(st[i]["exp_avg_sq"]) for i, n in enumerate(names)} if st else zeros,
+                         nat.PPO_EXP_AVG_SQ)
+        self.set_step(int(float(st[0]["step"])) if st else 0)
+
+    def get_step(self):
+        n = C.c_int64()
+        self._call("get_step", C.byref(n))
+        return n.value
+
+    def set_step(self, step):
+        self._call("set_step", int(step))
+
+    @staticmethod
+    def _indices(idx, count):
+        """(address, count, on_device, the array to keep alive) of a host int32 array or a device address."""
+        if isinstance(idx, (int, np.integer)):
+            return int(idx), int(count), 1, None
+        a = np.ascontiguousarray(idx, np.int32).reshape(-1)
+        return a.ctypes.data, a.size, 0, a
+
+    def minibatch(self, idx, apply=False, count=None):
+        ptr, n, dev, keep = self._indices(idx, count)
+        self._call("minibatch", C.c_void_p(ptr), n, dev, int(bool(apply)))
+
+    def apply(self):
+        self._call("apply")
+
+    def epoch(self, order, batch_size, count=None):
+        ptr, n, dev, keep = self._indices(order, count)
+        self._call("epoch", C.c_void_p(ptr), n, int(batch_size), dev)
+
+    def stats(self):
+        rows = lib().zenv_field_bytes(self._h, self.stats_field) // 24
+        out = np.empty((rows, 6), np.float32)
+        if rows:
+            check(lib().zenv_get(self._h, self.stats_field, out.ctypes.data, 0))
+        return out
 
 
 def ppo_logs(stats, distributional):
@@ -172,6 +278,7 @@ class ZoneVecEnv:
         self.zone_feat = zone_feat(cfg)
         self.device = int(device)
         self._h = C.c_void_p()
+        self._learners = {}         # level (None: the flat learner) -> _Learner, of the learners created through this object
         check(lib().zenv_create(C.byref(cfg), self.num_envs, self.device, C.byref(self._h)))
 
     # ------------------------------------------------------------------ lifecycle
@@ -741,107 +848,76 @@ class ZoneVecEnv:
         del keep
         self._ppo_h = h
         self._ppo_keys = ppo_state_dict_keys(bool(distributional_value))
-        self._ppo_hyper = dict(lr=lr, adam_eps=adam_eps)
+        self._learners[None] = _Learner(self._h, None, self._ppo_keys, mlp_tensor_shapes(h, self.zone_feat), lr,
+                                        adam_eps, nat.F_PPO_STATS)
         self.ppo_batch_num = 0          # PPOAlgo.batch_num (ppo.py:28)
+
+    def _learner(self, level):
+        """The learner of a level; before its init a bare one without tensor names: every call of it goes to the
+        library, which answers ZENV_E_STATE (ZENV_E_ARG for a level that does not exist)."""
+        found = self._learners.get(level if level is None else int(level))
+        field = nat.HPPO_STATS_FIELDS[level] if level in (nat.HPPO_LO, nat.HPPO_HI) else nat.F_PPO_STATS
+        return found or _Learner(self._h, level, {}, {}, 0.0, 0.0, field)
+
+    @property
+    def _ppo(self):
+        return self._learner(None)
 
     def ppo_tensor_ptr(self, which, index):
         """(device pointer, element count) of tensor `index` (arena order; -1: the whole arena) of arena `which`
         (``_native.PPO_PARAM`` / ``PPO_GRAD`` / ``PPO_EXP_AVG`` / ``PPO_EXP_AVG_SQ``)."""
-        p, n = C.c_void_p(), C.c_int64()
-        check(lib().zenv_ppo_tensor(self._h, int(which), int(index), C.byref(p), C.byref(n)))
-        return p.value, n.value
+        return self._ppo.tensor_ptr(which, index)
 
     def ppo_tensors(self, which=nat.PPO_PARAM):
         """Every tensor of an arena as a new host array, under its zenv_mlp_weights name."""
-        shapes = mlp_tensor_shapes(self._ppo_h, self.zone_feat)
-        out = {}
-        for i, name in enumerate(self._ppo_keys):
-            out[name] = a = np.empty(shapes[name], np.float32)
-            check(lib().zenv_ppo_read(self._h, int(which), i, a.ctypes.data))
-        return out
+        return self._ppo.tensors(which)
 
     def ppo_set_tensors(self, tensors, which=nat.PPO_PARAM):
         """Overwrite the tensors of an arena that `tensors` names (zenv_mlp_weights names)."""
-        shapes = mlp_tensor_shapes(self._ppo_h, self.zone_feat)
-        for i, name in enumerate(self._ppo_keys):
-            if name in tensors:
-                a = np.ascontiguousarray(tensors[name], np.float32)
-                if a.shape != shapes[name]:
-                    raise ValueError(f"{name}: shape {a.shape}, expected {shapes[name]}")
-                check(lib().zenv_ppo_write(self._h, int(which), i, a.ctypes.data))
+        self._ppo.set_tensors(tensors, which)
 
     def ppo_state_dict(self):
         """The learner's parameters under the reference ACModel's state_dict names (host float32 copies)."""
-        t = self.ppo_tensors()
-        return {key: t[name] for name, key in self._ppo_keys.items()}
+        return self._ppo.state_dict()
 
     def ppo_load_state_dict(self, state_dict):
         """Overwrite the learner's parameters from an ACModel state_dict (every key must be there)."""
-        self.ppo_set_tensors({name: _as_host_f32(state_dict[key]) for name, key in self._ppo_keys.items()})
+        self._ppo.load_state_dict(state_dict)
 
     def ppo_optimizer_state(self):
         """Adam's state in the shape of ``torch.optim.Adam.state_dict()`` (train_ppo.py:116-122), host arrays: parameter
         i is the i-th of ``ACModel.parameters()``."""
-        m, v = self.ppo_tensors(nat.PPO_EXP_AVG), self.ppo_tensors(nat.PPO_EXP_AVG_SQ)
-        step = self.ppo_get_step()
-        state = {i: {"step": float(step), "exp_avg": m[name], "exp_avg_sq": v[name]}
-                 for i, name in enumerate(self._ppo_keys)} if step else {}
-        group = {"lr": self._ppo_hyper["lr"], "betas": (0.9, 0.999), "eps": self._ppo_hyper["adam_eps"], "weight_decay": 0,
-                 "amsgrad": False, "params": list(range(len(self._ppo_keys)))}
-        return {"state": state, "param_groups": [group]}
+        return self._ppo.optimizer_state()
 
     def ppo_load_optimizer_state(self, state):
         """Restore Adam's moments and step count from ``ppo_optimizer_state`` / ``torch.optim.Adam.state_dict()``."""
-        names = list(self._ppo_keys)
-        st = state["state"]
-        zeros = {n: np.zeros(s, np.float32) for n, s in mlp_tensor_shapes(self._ppo_h, self.zone_feat).items() if n in names}
-        self.ppo_set_tensors({n: _as_host_f32(st[i]["exp_avg"]) for i, n in enumerate(names)} if st else zeros,
-                             nat.PPO_EXP_AVG)
-        self.ppo_set_tensors({n: _as_host_f32(st[i]["exp_avg_sq"]) for i, n in enumerate(names)} if st else zeros,
-                             nat.PPO_EXP_AVG_SQ)
-        self.ppo_set_step(int(float(st[0]["step"])) if st else 0)
+        self._ppo.load_optimizer_state(state)
 
     def ppo_get_step(self):
-        n = C.c_int64()
-        check(lib().zenv_ppo_get_step(self._h, C.byref(n)))
-        return n.value
+        return self._ppo.get_step()
 
     def ppo_set_step(self, step):
-        check(lib().zenv_ppo_set_step(self._h, int(step)))
-
-    @staticmethod
-    def _ppo_indices(idx, count):
-        """(address, count, on_device, the array to keep alive) of a host int32 array or a device address."""
-        if isinstance(idx, (int, np.integer)):
-            return int(idx), int(count), 1, None
-        a = np.ascontiguousarray(idx, np.int32).reshape(-1)
-        return a.ctypes.data, a.size, 0, a
+        self._ppo.set_step(step)
 
     def ppo_minibatch(self, idx, apply=False, count=None):
         """Forward, loss and backward on the samples idx (host int32 array, or a device address with count): the
         gradients stay in their arena, the statistics in ``ppo_stats()[0]``; apply: the clip and Adam step too.
         Index i is env i // T, frame i % T of the last collect.  Asynchronous."""
-        ptr, n, dev, keep = self._ppo_indices(idx, count)
-        check(lib().zenv_ppo_minibatch(self._h, C.c_void_p(ptr), n, dev, int(bool(apply))))
+        self._ppo.minibatch(idx, apply, count)
 
     def ppo_apply(self):
         """clip_grad_norm_ and one Adam step on whatever the gradient arena holds."""
-        check(lib().zenv_ppo_apply(self._h))
+        self._ppo.apply()
 
     def ppo_epoch(self, order, batch_size, count=None):
         """The minibatches order[k * batch_size : (k + 1) * batch_size] in sequence (the last one short), each with
         its clip and Adam step; no host synchronisation.  ``ppo_stats()`` has a row per minibatch."""
-        ptr, n, dev, keep = self._ppo_indices(order, count)
-        check(lib().zenv_ppo_epoch(self._h, C.c_void_p(ptr), n, int(batch_size), dev))
+        self._ppo.epoch(order, batch_size, count)
 
     def ppo_stats(self):
         """float32 [minibatches, 6] of the last ppo_minibatch / ppo_epoch: ``_native.PPO_STATS`` names the columns
         (ppo.py:93-100, :121).  Waits for the device."""
-        rows = lib().zenv_field_bytes(self._h, nat.F_PPO_STATS) // 24
-        out = np.empty((rows, 6), np.float32)
-        if rows:
-            check(lib().zenv_get(self._h, nat.F_PPO_STATS, out.ctypes.data, 0))
-        return out
+        return self._ppo.stats()
 
     def ppo_publish(self, precision="auto"):
         """Hand the learner's parameters to the acting network: read them back (0.7 MB) and ``load_mlp`` them, so
@@ -860,6 +936,118 @@ class ZoneVecEnv:
             self.ppo_batch_num += 1
             self.ppo_epoch(order, batch_size)
         return ppo_logs(self.ppo_stats(), "critic_sigma_w" in self._ppo_keys)
+
+    # ------------------------------------------------------------------ the Zone-goals agent's two PPO updates
+    # the example's hyper-parameters (examples/zone_goals_ppo_torch.py; the reference takes the norm and does not clip)
+    HPPO_LO = dict(lr=3e-4, adam_eps=1e-8, clip_eps=0.2, entropy_coef=0.003, value_loss_coef=0.5, max_grad_norm=math.inf,
+                   max_batch=16384)
+    HPPO_HI = dict(lr=3e-4, adam_eps=1e-8, clip_eps=0.2, entropy_coef=0.01, value_loss_coef=0.5, max_grad_norm=math.inf,
+                   max_batch=4096)
+
+    def hppo_init(self, hi_state_dict, lo_state_dict, lo=None, hi=None):
+        """The two learners of HierPolicyAlgo (zone-goals/src/torch_ac/algos/_hier_policy_opt.py:197-370) on the
+        device, from HighPolicyValueModel / LoPolicyValueModel state_dicts with both critics: float32 master
+        parameters, gradients, Adam's moments and a workspace per level.  lo / hi: dicts of the settings to change from
+        ``HPPO_LO`` / ``HPPO_HI`` (lr, adam_eps, clip_eps, entropy_coef, value_loss_coef, max_grad_norm, max_batch).
+        `level` in the other hppo_* methods: ``_native.HPPO_LO`` = 0, ``HPPO_HI`` = 1.  Separate from ``load_hier``:
+        ``hppo_publish`` hands the parameters to the acting agent."""
+        tensors = hier_tensors_from_state_dicts(hi_state_dict, lo_state_dict)
+        h = int(tensors["hi_zone_b1"].shape[0])
+        F = int(tensors["hi_zone_w1"].shape[1]) - 8
+        hi_keys, lo_keys = hppo_state_dict_keys()
+        missing = [n for n in list(hi_keys) + list(lo_keys) if n not in tensors]
+        if missing:
+            raise ValueError(f"the update needs both critics: no {missing[0]}")
+        shapes = hier_tensor_shapes(h, F)
+        w = nat.HierWeights(h_dim=h, precision=nat.MLP_F32, zone_feat=F)
+        keep = self._load_weights(w, list(hi_keys) + list(lo_keys), tensors, shapes)      # alive across the call
+        cfgs = [nat.PpoConfig(distributional_value=0, **dict(base, **(over or {})))
+                for base, over in ((self.HPPO_LO, lo), (self.HPPO_HI, hi))]
+        check(lib().zenv_hppo_init(self._h, C.byref(w), C.byref(cfgs[0]), C.byref(cfgs[1])))
+        del keep
+        for level, keys in ((nat.HPPO_LO, lo_keys), (nat.HPPO_HI, hi_keys)):
+            self._learners[level] = _Learner(self._h, level, keys, shapes, cfgs[level].lr, cfgs[level].adam_eps,
+                                             nat.HPPO_STATS_FIELDS[level])
+
+    def hppo_tensor_ptr(self, level, which, index):
+        """``ppo_tensor_ptr`` of a level's arenas."""
+        return self._learner(level).tensor_ptr(which, index)
+
+    def hppo_tensors(self, level, which=nat.PPO_PARAM):
+        """Every tensor of a level's arena as a new host array, under its zenv_hier_weights name (hi_* / lo_*)."""
+        return self._learner(level).tensors(which)
+
+    def hppo_set_tensors(self, level, tensors, which=nat.PPO_PARAM):
+        self._learner(level).set_tensors(tensors, which)
+
+    def hppo_state_dicts(self):
+        """(hi_model_state, lo_model_state): both learners' parameters under the reference's names (host copies)."""
+        return self._learner(nat.HPPO_HI).state_dict(), self._learner(nat.HPPO_LO).state_dict()
+
+    def hppo_load_state_dicts(self, hi_state_dict, lo_state_dict):
+        self._learner(nat.HPPO_HI).load_state_dict(hi_state_dict)
+        self._learner(nat.HPPO_LO).load_state_dict(lo_state_dict)
+
+    def hppo_optimizer_state(self, level):
+        """A level's Adam state in the shape of ``torch.optim.Adam.state_dict()``: parameter i is the i-th of the
+        module's ``parameters()``."""
+        return self._learner(level).optimizer_state()
+
+    def hppo_load_optimizer_state(self, level, state):
+        self._learner(level).load_optimizer_state(state)
+
+    def hppo_get_step(self, level):
+        return self._learner(level).get_step()
+
+    def hppo_set_step(self, level, step):
+        self._learner(level).set_step(step)
+
+    def hppo_minibatch(self, level, idx, apply=False, count=None):
+        """``ppo_minibatch`` on the records of the last ``collect_hier``.  Low level: index i is env i // (T-1), frame
+        i % (T-1) (lo_exps' order); high level: row i of the M closed transitions."""
+        self._learner(level).minibatch(idx, apply, count)
+
+    def hppo_apply(self, level):
+        self._learner(level).apply()
+
+    def hppo_epoch(self, level, order, batch_size, count=None):
+        self._learner(level).epoch(order, batch_size, count)
+
+    def hppo_stats(self, level):
+        """float32 [minibatches, 6] of the level's last hppo_minibatch / hppo_epoch (``_native.PPO_STATS``' columns,
+        value_std = 0).  Waits for the device."""
+        return self._learner(level).stats()
+
+    def hppo_publish(self):
+        """Hand both learners' parameters to the acting agent: read them back and ``load_hier`` them, so the next
+        ``collect_hier`` acts with them."""
+        self.load_hier(dict(self.hppo_tensors(nat.HPPO_HI), **self.hppo_tensors(nat.HPPO_LO)))
+
+    def hppo_update(self, epochs, batch_size, hi_epochs, hi_batch_size, rng):
+        """update_parameters (_hier_policy_opt.py:197-212) on the records of the last ``collect_hier``: the high level
+        first, then the low level, each epoch in the order of ``hppo_batch_indexes`` from the caller's numpy Generator.
+        Returns the reference's logs under lo_* / hi_*: the low level's are means over all its minibatches (its lists
+        start before the epoch loop, :215-224), the high level's over the last epoch's (:293-300).  With M = 0 the high
+        level is skipped and its logs are 0.0."""
+        T = lib().zenv_field_bytes(self._h, nat.F_EXP_VALUE) // (4 * self.num_envs)
+        M = lib().zenv_field_bytes(self._h, nat.F_HI_VALUE) // 4
+        if T < 2:
+            raise ZenvError(nat.E_STATE, "collect_hier first: the handle holds no experience")
+        hi, lo = self._learner(nat.HPPO_HI), self._learner(nat.HPPO_LO)
+        names = [(i, n) for i, n in enumerate(nat.PPO_STATS) if n != "value_std"]
+        logs = {"hi_" + n: 0.0 for _, n in names}
+        for _ in range(int(hi_epochs) if M else 0):
+            hi.epoch(hppo_batch_indexes(M, rng), hi_batch_size)
+        if M and int(hi_epochs) > 0:
+            mean = hi.stats().astype(np.float64).mean(axis=0)
+            logs = {"hi_" + n: float(mean[i]) for i, n in names}
+        rows = []
+        for _ in range(int(epochs)):
+            lo.epoch(hppo_batch_indexes(self.num_envs * (T - 1), rng), batch_size)
+            rows.append(lo.stats())
+        mean = np.concatenate(rows).astype(np.float64).mean(axis=0) if rows else np.zeros(6)
+        logs.update({"lo_" + n: float(mean[i]) for i, n in names})
+        return logs
 
     # ------------------------------------------------------------------ Zone-goals training experience
     def collect_hier(self, frames_per_proc, policy_seed=1, env_index0=0, discount=0.99, gae_lambda=0.95):

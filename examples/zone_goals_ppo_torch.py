@@ -9,12 +9,16 @@ parameter names (zone-goals/src/hier_policy_value_models.py, restated in tests/h
 the checkpoint's hi_model_state / lo_model_state; after every update the device agent is reloaded from them.
 
     python examples/zone_goals_ppo_torch.py --env PointTSP-v0 --procs 4096 --frames-per-proc 128 --updates 10
+
+``--device-update`` runs the two updates in the library as well (``TorchZoneEnv.hppo_init`` / ``hppo_update`` /
+``hppo_publish``: zenv_hppo_*, csrc/ppo_update.hip); off by default, the torch path is what it was.
 """
 import argparse
 import os
 import sys
 import time
 
+import numpy as np
 import torch
 import torch.nn as nn
 from torch.distributions import Categorical
@@ -97,11 +101,14 @@ def _ppo_loss(log_prob, old_log_prob, value, sb, clip_eps):
 
 class HierPPO:
     """HierPolicyAlgo's iteration: collect_experiences on the device, then update_hi_parameters and
-    update_lo_parameters (_hier_policy_opt.py:196-330) in torch."""
+    update_lo_parameters (_hier_policy_opt.py:196-330) in torch -- or, with device_update, both updates in the library
+    too (``hppo_init`` once; then ``collect_hier``, ``hppo_update``, ``hppo_publish`` per iteration; hi_net / lo_net get
+    the learners' parameters back when ``train`` ends)."""
 
     def __init__(self, tenv, hi_net, lo_net, frames_per_proc=128, epochs=4, batch_size=16384, hi_epochs=4,
                  hi_batch_size=4096, lr=3e-4, hi_lr=3e-4, discount=0.99, gae_lambda=0.95, clip_eps=0.2,
-                 entropy_coef=0.003, hi_entropy_coef=0.01, value_loss_coef=0.5, hi_value_coef=0.5, seed=1):
+                 entropy_coef=0.003, hi_entropy_coef=0.01, value_loss_coef=0.5, hi_value_coef=0.5, seed=1,
+                 device_update=False):
         self.tenv, self.hi_net, self.lo_net = tenv, hi_net, lo_net
         self.T, self.epochs, self.batch_size = frames_per_proc, epochs, batch_size
         self.hi_epochs, self.hi_batch_size = hi_epochs, hi_batch_size
@@ -112,6 +119,15 @@ class HierPPO:
         self.hi_optimizer = torch.optim.Adam(hi_net.parameters(), hi_lr, eps=1e-8)
         self.gen = torch.Generator(device=tenv.device).manual_seed(seed)
         self.seed, self.it = seed, 0
+        self.device_update = device_update
+        if device_update:
+            self.rng = np.random.default_rng(seed)
+            tenv.hppo_init(hi_net.state_dict(), lo_net.state_dict(),
+                           lo=dict(lr=lr, clip_eps=clip_eps, entropy_coef=entropy_coef, value_loss_coef=value_loss_coef,
+                                   max_batch=batch_size),
+                           hi=dict(lr=hi_lr, clip_eps=clip_eps, entropy_coef=hi_entropy_coef,
+                                   value_loss_coef=hi_value_coef, max_batch=hi_batch_size))
+            tenv.hppo_publish()
 
     def _batches(self, total, size):
         order = torch.randperm(total, device=self.tenv.device, generator=self.gen)
@@ -158,12 +174,17 @@ class HierPPO:
 
     def iteration(self):
         """Reload the device agent, collect, update both levels; returns the logs (lo_* / hi_*)."""
-        self.tenv.load_hier(self.hi_net.state_dict(), self.lo_net.state_dict())
+        if not self.device_update:
+            self.tenv.load_hier(self.hi_net.state_dict(), self.lo_net.state_dict())
         lo, hi = self.tenv.collect_hier(self.T, policy_seed=self.seed * 1000003 + self.it, discount=self.discount,
                                         gae_lambda=self.gae_lambda)
         self.it += 1
         logs = {"frames": lo["obs"].shape[0] * lo["obs"].shape[1], "hi_frames": int(hi["action"].shape[0]),
                 "reward_per_frame": float(lo["env_reward"].mean())}
+        if self.device_update:
+            logs.update(self.tenv.hppo_update(self.epochs, self.batch_size, self.hi_epochs, self.hi_batch_size, self.rng))
+            self.tenv.hppo_publish()
+            return logs
         logs.update({"hi_" + k: v for k, v in self.update_hi_parameters(hi).items()})
         logs.update({"lo_" + k: v for k, v in self.update_lo_parameters(lo).items()})
         return logs
@@ -187,6 +208,10 @@ def train(env_id="PointTSP-v0", procs=4096, frames_per_proc=128, updates=10, hid
         torch.cuda.synchronize()
         logs.update(update=u, seconds=round(time.perf_counter() - t0, 3))
         log({k: (round(v, 4) if isinstance(v, float) else v) for k, v in logs.items()})
+    if algo.device_update:
+        hi_sd, lo_sd = tenv.hppo_state_dicts()
+        hi_net.load_state_dict(hi_sd)
+        lo_net.load_state_dict(lo_sd)
     env.close()
     return hi_net, lo_net
 
@@ -199,5 +224,7 @@ if __name__ == "__main__":
     ap.add_argument("--updates", type=int, default=10)
     ap.add_argument("--hidden-size", type=int, default=128)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--device-update", action="store_true",
+                    help="run both PPO updates in the library (zenv_hppo_*) instead of torch")
     a = ap.parse_args()
-    train(a.env, a.procs, a.frames_per_proc, a.updates, a.hidden_size, a.seed)
+    train(a.env, a.procs, a.frames_per_proc, a.updates, a.hidden_size, a.seed, device_update=a.device_update)

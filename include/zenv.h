@@ -173,7 +173,11 @@ enum {
     ZENV_F_PPO_STATS = 74,          /* float32 [minibatches][6] entropy, value, value std (0 without the distributional
                                      *               critic), policy loss, value loss, gradient norm before the clip: the
                                      *               logs of ppo.py:93-100, :121 */
-    ZENV_F_COUNT = 75
+    /* the Zone-goals agent's two learners (zenv_hppo_init; before these two fields, ZENV_F_COUNT = 75): the statistics
+     * of the minibatches of the level's last zenv_hppo_minibatch (one row) or zenv_hppo_epoch; 0 bytes before the first */
+    ZENV_F_HPPO_LO_STATS = 75,      /* float32 [minibatches][6] the low level's: ZENV_F_PPO_STATS' columns, value std = 0 */
+    ZENV_F_HPPO_HI_STATS = 76,      /* float32 [minibatches][6] the high level's, the same */
+    ZENV_F_COUNT = 77
 };
 
 /* scripted on-device action sources (the build's own; used by bench/tests) */
@@ -901,7 +905,8 @@ int zenv_collect_xy(zenv_t *h, int frames_per_proc, uint64_t policy_seed, uint64
  * reference's [N][T] flattening (base.py:212-227); the kernels read the time-major buffers in place.  The learner's
  * parameters are separate from the acting network's: nothing here repacks zenv_mlp_load's images (read the parameters
  * back and load them to act with them).  Every reduction runs in a fixed order: the same call from the same state
- * gives the same bits.  The hierarchical agents' updates are not here. */
+ * gives the same bits.  The Zone-goals agent's two updates are zenv_hppo_* below; the updates of the skill, Options and
+ * xy-goals agents are not here. */
 typedef struct zenv_ppo_config {
     double lr, adam_eps;            /* torch.optim.Adam(lr, eps = adam_eps), betas 0.9 / 0.999 */
     double clip_eps, entropy_coef, value_loss_coef, max_grad_norm;
@@ -941,6 +946,45 @@ int zenv_ppo_apply(zenv_t *h);
 /* The minibatches order[k B : (k + 1) B], B = batch_size, in sequence, the last one short: each forward, backward,
  * clip and Adam, with no host synchronisation; minibatch k's statistics in row k of ZENV_F_PPO_STATS. */
 int zenv_ppo_epoch(zenv_t *h, const int32_t *order, int total, int batch_size, int on_device);
+
+/* ---- the Zone-goals agent's two PPO updates on the device: update_lo_parameters / update_hi_parameters,
+ * zone-goals/src/torch_ac/algos/_hier_policy_opt.py:214-370 ----
+ * Two learners beside the flat one, each with its own four arenas, Adam step count, workspace and statistics; `level`
+ * 0 is the low level (LoPolicyValueModel), 1 the high level (HighPolicyValueModel).  They read the records of the last
+ * zenv_collect_hier in place:
+ *   low:   the flat learner's network on [obs, goal] (10 inputs), loss and Adam.  Sample index i is env i / (T-1), frame
+ *          i % (T-1) of the ZENV_F_EXP_* buffers and ZENV_F_LO_GOAL: the reference's lo_exps hold T-1 frames per env
+ *          (hrl_policy_planner.py:68); frame T-1 of any buffer is never read.
+ *   high:  sample index i is row i of the ZENV_F_HI_* rows, i in [0, M).  Categorical over the goals of
+ *          ZENV_F_HI_ACTION_MASK (logits[~mask] = -inf), log_prob and entropy of that distribution, the same clipped
+ *          policy and value losses.
+ * The reference takes the gradient norm and does not clip (:272, :349): max_grad_norm = +inf is accepted here and gives
+ * a clip factor of exactly 1.  The arenas' order is zenv_hier_weights' member order, parameters() order of the modules:
+ * 16 tensors for the high level (hi_zone_w1 .. hi_critic_b2), 18 for the low level (lo_zone_w1 .. lo_critic_b2).
+ * Neither touches the acting agent's weights: read the parameters back and zenv_hier_load them to act with them. */
+/* zenv_ppo_check's rules for either level, on the host alone: ZENV_E_ARG for h_dim outside 1 .. 191, a zone_feat other
+ * than zenv_zone_feat(cfg), a null tensor, a missing critic at either level, distributional_value != 0, a negative or
+ * non-finite hyper-parameter (max_grad_norm = +inf excepted), max_batch < 1, a workspace of 2^31 floats or more. */
+int zenv_hppo_check(const zenv_config *cfg, const zenv_hier_weights *init, const zenv_ppo_config *lo,
+                    const zenv_ppo_config *hi);
+/* Both learners from one set of weights (init->precision is not used).  A second call replaces them. */
+int zenv_hppo_init(zenv_t *h, const zenv_hier_weights *init, const zenv_ppo_config *lo, const zenv_ppo_config *hi);
+/* The flat functions with the level after the handle; their semantics are the flat functions'.  ZENV_E_ARG for a level
+ * other than 0 or 1; ZENV_E_STATE without zenv_hppo_init.  The update calls answer ZENV_E_STATE unless the handle's
+ * ZENV_F_EXP_* / ZENV_F_LO_* / ZENV_F_HI_* buffers hold zenv_collect_hier's records (no collect yet, or another
+ * collector ran last), and level 1 when that call closed no transition (M = 0).  Statistics: ZENV_F_HPPO_LO_STATS /
+ * ZENV_F_HPPO_HI_STATS.  A device-resident index outside [0, N (T-1)) (low) or [0, M) (high), and a high-level row whose
+ * recorded goal is outside [0, Z) or not among its available goals (a row without any included), is never
+ * dereferenced past that check: the sample is dropped as zenv_ppo_minibatch drops one, it adds nothing to the loss or to
+ * any gradient, and the next call that waits for the device answers ZENV_E_ARG once. */
+int zenv_hppo_tensor(zenv_t *h, int level, int which, int index, void **dev_ptr, int64_t *count);
+int zenv_hppo_read(zenv_t *h, int level, int which, int index, float *dst);
+int zenv_hppo_write(zenv_t *h, int level, int which, int index, const float *src);
+int zenv_hppo_get_step(zenv_t *h, int level, int64_t *step);
+int zenv_hppo_set_step(zenv_t *h, int level, int64_t step);
+int zenv_hppo_minibatch(zenv_t *h, int level, const int32_t *idx, int count, int idx_on_device, int apply);
+int zenv_hppo_apply(zenv_t *h, int level);
+int zenv_hppo_epoch(zenv_t *h, int level, const int32_t *order, int total, int batch_size, int on_device);
 
 /* ---- results ---- */
 int zenv_get(zenv_t *h, int field, void *dst, int dst_on_device);
