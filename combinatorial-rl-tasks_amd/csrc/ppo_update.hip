@@ -90,6 +90,10 @@ __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c)
 
 enum { NT_STORE = 0, NT_RELU = 1, NT_MASK = 2, NT_ADD = 3 };
 
+// torch.relu: a NaN stays a NaN (fmaxf(x, 0) would answer 0, and a minibatch on NaN observations would report finite
+// losses where the reference reports NaN)
+__device__ __forceinline__ float reluf(float x) { return x < 0.f ? 0.f : x; }
+
 // D[row][f] (op)= sum_k A[f][k] B[row][k]; grid = row tiles, block = (64, feature tiles).  A: [32 x tiles][lda], B:
 // [32 x row tiles][ldb] or the gathered input, K a multiple of 8.  NT_MASK keeps the product where D held a positive
 // activation (the ReLU's derivative) and writes 0 elsewhere; NT_ADD adds to D.
@@ -144,7 +148,7 @@ __global__ __launch_bounds__(448) void k_ppo_nt(const float *__restrict__ A, int
     for (int q = 0; q < 4; ++q) {
         float4 *dp = reinterpret_cast<float4 *>(D + (size_t)row * ldd + f0 + 8 * q + 4 * hh);
         float4 v = make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
-        if (MODE == NT_RELU) v = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
+        if (MODE == NT_RELU) v = make_float4(reluf(v.x), reluf(v.y), reluf(v.z), reluf(v.w));
         if (MODE == NT_MASK) {
             const float4 o = *dp;
             v = make_float4(o.x > 0.f ? v.x : 0.f, o.y > 0.f ? v.y : 0.f, o.z > 0.f ? v.z : 0.f, o.w > 0.f ? v.w : 0.f);
@@ -361,17 +365,21 @@ __global__ void k_ppo_spread(PpoNet n, int Z, int rows)
 
 __device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+// torch.clamp, torch.min and torch.max hand a NaN on where fminf / fmaxf drop it: a NaN ratio or value gives a NaN loss,
+// as in the reference
+__device__ __forceinline__ float clampf(float x, float lo, float hi) { return x < lo ? lo : x > hi ? hi : x; }
+
 // PPO's clipped surrogate of one sample (ppo.py:76-79): returns -min(surr1, surr2); g_lp = d loss / d log_prob(a), the
 // mean's 1 / count included.  dlp = log_prob(a) - the recorded log_prob.
 __device__ __forceinline__ float clipped_policy(float dlp, float adv, float clip_eps, float inv_b, float &g_lp)
 {
     const float ratio = expf(dlp);
     const float lo = 1.0f - clip_eps, hi = 1.0f + clip_eps;
-    const float surr1 = ratio * adv, surr2 = fminf(fmaxf(ratio, lo), hi) * adv;
+    const float surr1 = ratio * adv, surr2 = clampf(ratio, lo, hi) * adv;
     // d min(surr1, surr2) / d ratio: adv on the unclipped branch, adv inside the clamp's range, 0 outside
     const float through = surr1 <= surr2 ? 1.0f : (ratio >= lo && ratio <= hi) ? 1.0f : 0.f;
     g_lp = -adv * inv_b * through * ratio;
-    return -fminf(surr1, surr2);
+    return -(surr1 <= surr2 ? surr1 : surr2);
 }
 
 // the clipped value loss of one sample (ppo.py:83-86): returns max(s1, s2); dval = d loss / d v with the coefficient
@@ -379,12 +387,12 @@ __device__ __forceinline__ float clipped_policy(float dlp, float adv, float clip
 __device__ __forceinline__ float clipped_value(float v, float old, float ret, const PpoHyper &hy, float inv_b, float &dval)
 {
     const float dv = v - old;
-    const float vc = old + fminf(fmaxf(dv, -hy.clip_eps), hy.clip_eps);
+    const float vc = old + clampf(dv, -hy.clip_eps, hy.clip_eps);
     const float s1 = (v - ret) * (v - ret), s2 = (vc - ret) * (vc - ret);
     const bool inside = dv >= -hy.clip_eps && dv <= hy.clip_eps;
     const float dl = s1 >= s2 ? 2.0f * (v - ret) : inside ? 2.0f * (vc - ret) : 0.f;
     dval = hy.value_loss_coef * inv_b * dl;
-    return fmaxf(s1, s2);
+    return s1 >= s2 ? s1 : s2;
 }
 
 // The loss of one sample (ppo.py:70-89) and its derivative with respect to the six head pre-activations
@@ -471,7 +479,7 @@ __global__ void k_hppo_head(PpoNet n, Gather g, int rows)
             const float *zr = g.zone_obs + (r.slot * g.Z + r.z) * g.F;
             for (int k = 0; k < g.F; ++k) s += w[k] * zr[k];
         }
-        v = fmaxf(n.Ha[(size_t)(row / g.Z) * n.HP + f] + s, 0.f);
+        v = reluf(n.Ha[(size_t)(row / g.Z) * n.HP + f] + s);
     }
     n.U[(size_t)row * n.HP + f] = v;
 }
@@ -481,9 +489,10 @@ __global__ void k_hppo_head(PpoNet n, Gather g, int rows)
 // as in k_ppo_loss,   d loss / d logit_z = g_lp (1[z = a] - p_z) + (entropy_coef / count) p_z (log p_z + H),
 // 0 for an unavailable z.  A recorded goal outside [0, Z) or marked unavailable (a row without an available goal has
 // one) drops the sample like an index out of range.  One thread per sample; L, DL: [rows][32], column 0.
-// The softmax and the derivatives are formed in double (Z <= 32 terms per sample) and rounded once: a row's derivatives
-// sum to zero -- a shift common to its logits changes nothing -- so actor.2.bias' gradient is nothing but what they
-// fail to cancel.  That sum, taken per sample before the rounding, goes out in SS[5]; k_ppo_stats adds it up.
+// The softmax and the derivatives are formed in double (Z <= 32 terms per sample) and rounded once.  A row's derivatives
+// sum to zero -- a shift common to its logits changes nothing -- so actor.2.bias' gradient is 0 for every input; any sum
+// of the deltas holds nothing but their rounding (1e-17 even before they are rounded to float32, where float64 autograd
+// gives exactly 0 for two zones), so k_ppo_stats writes the 0 itself.
 __global__ void k_hppo_loss(PpoNet n, PpoExp x, Gather g, int bp, int rows)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -530,7 +539,6 @@ __global__ void k_hppo_loss(PpoNet n, PpoExp x, Gather g, int bp, int rows)
         ss[3] = ploss;
         ss[4] = vloss;
     }
-    double row_sum = 0.0;
     for (int z = 0; z < Z; ++z) {
         const size_t row = (size_t)b * Z + z;
         if (row >= (size_t)rows) break;
@@ -539,14 +547,12 @@ __global__ void k_hppo_loss(PpoNet n, PpoExp x, Gather g, int bp, int rows)
             const double lp = (double)lg[(size_t)z * 32] - lse, p = exp(lp);
             dz = (double)g_lp * ((z == a ? 1.0 : 0.0) - p) + ec * p * (lp + H);
         }
-        row_sum += dz;
         n.DZ[row] = dz;
         float4 *dl = reinterpret_cast<float4 *>(n.DL + row * 32);
         dl[0] = make_float4((float)dz, 0.f, 0.f, 0.f);
 #pragma unroll
         for (int i = 1; i < 8; ++i) dl[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    ss[5] = (float)row_sum;
     float *dh = n.DH + (size_t)b * 32;
 #pragma unroll
     for (int i = 0; i < 32; ++i) dh[i] = i == 4 ? d_value : 0.f;
@@ -591,18 +597,13 @@ __device__ __forceinline__ double block_sum_256(double v, double *sh)
 }
 
 // stats[0..4] = the minibatch means of the per-sample terms; one block of 256 threads, thread i adds samples i, i + 256 ...
-// ent_terms: the entropy's mean is over count x 2 action components, or over count categoricals.  col5_sum (or null):
-// where the plain sum of column 5 goes -- PPO_HEAD_ZONES: actor.2.bias' gradient, see k_hppo_loss
+// ent_terms: the entropy's mean is over count x 2 action components, or over count categoricals.  zero_grad (or null):
+// a gradient that is 0 for every input -- PPO_HEAD_ZONES: actor.2.bias', see k_hppo_loss
 __global__ __launch_bounds__(256) void k_ppo_stats(const float *__restrict__ SS, int count, double ent_terms,
-                                                   float *__restrict__ stats, float *__restrict__ col5_sum)
+                                                   float *__restrict__ stats, float *__restrict__ zero_grad)
 {
     __shared__ double sh[256];
-    if (col5_sum) {
-        double s = 0.0;
-        for (int b = threadIdx.x; b < count; b += 256) s += (double)SS[(size_t)b * 8 + 5];
-        s = block_sum_256(s, sh);
-        if (threadIdx.x == 0) *col5_sum = (float)s;
-    }
+    if (zero_grad && threadIdx.x == 0) *zero_grad = 0.f;
     for (int k = 0; k < 5; ++k) {
         double s = 0.0;
         for (int b = threadIdx.x; b < count; b += 256) s += (double)SS[(size_t)b * 8 + k];

@@ -1,0 +1,173 @@
+"""What the GPU tests of the device learners share (test_gpu_ppo_update.py, test_gpu_hppo_update.py and their *_shapes
+files): handles with a real collect, the planted high-level rows, and the comparison of one minibatch -- every gradient
+tensor and the six statistics -- with the float64 / float32 references under ppo_update_ref.check_rule.  Each test file
+keeps its own cache of handles and its own report list and passes them in."""
+import numpy as np
+import torch
+
+from tests import hier_ref as H
+from tests import hppo_update_ref as RH
+from tests import ppo_update_ref as R
+
+F32, F64 = torch.float32, torch.float64
+HIER_T = 33                 # frames of a collect_hier: with 12-step episodes every env closes two transitions
+LEVELS = {"lo": 0, "hi": 1}
+PLANTED = 8
+
+
+def print_worst(report, label, width):
+    worst = {}
+    for name, e_dev, e32, ratio in report:
+        key = name.split("/")[-1]
+        worst[key] = max(worst.get(key, 0.0), ratio)
+    for k in sorted(worst):
+        print("%s worst e_dev / max(e32, ulp): %-*s %.3f" % (label, width, k, worst[k]))
+
+
+def host(d):
+    return {k: np.ascontiguousarray(v.cpu().numpy()) for k, v in d.items()}
+
+
+# ---------------------------------------------------------------------------------------------- the flat learner
+def flat_setup(Z, cfg, h, N, T, dist, seed, sd=None):
+    """A handle with fresh parameters (or `sd`) loaded into the acting network and one collect."""
+    from combinatorial_rl_tasks_amd import agents
+    env = Z.ZoneVecEnv(cfg, N)
+    env.build_bank(11, 2 * N)
+    env.reset()
+    if sd is None:
+        sd = R.random_state_dict(env.zone_feat, h, dist, seed=seed)
+    env.load_mlp(agents.mlp_tensors_from_state_dict(sd), precision="f32")
+    exps = {k: np.ascontiguousarray(v) for k, v in env.collect(T, policy_seed=5).items()}
+    return dict(env=env, sd=sd, exps=exps, F=env.zone_feat, Z=env.num_zones, h=h, N=N, T=T, dist=dist)
+
+
+def flat_by_key(env, which):
+    t = env.ppo_tensors(which)
+    return {key: t[name] for name, key in env._ppo_keys.items()}
+
+
+def flat_ref_pair(sd, s, idx, hyper):
+    out = []
+    for dt in (F64, F32):
+        model = R.model_from(sd, s["F"], dt)
+        grads, stats = R.gradients(model, R.as_batch(s["exps"], idx, dt), hyper)
+        _, _, outputs = R.loss_and_stats(model, R.as_batch(s["exps"], idx, dt), hyper)
+        out.append((grads, stats, outputs))
+    return out
+
+
+def flat_check_minibatch(Z, s, sd, idx, hyper, tag, report, max_batch=384):
+    """apply = 0 on `sd`: the statistics and every gradient tensor under the rule."""
+    nat = Z._native
+    env = s["env"]
+    env.ppo_init(sd, max_batch=max_batch, **hyper)
+    env.ppo_minibatch(np.asarray(idx, np.int32))
+    stats = env.ppo_stats()[0]
+    grads = flat_by_key(env, nat.PPO_GRAD)
+    (g64, s64, _), (g32, s32, _) = flat_ref_pair(sd, s, idx, hyper)
+    assert len(grads) == (20 if s["dist"] else 18) and set(grads) == set(g64)
+    for i, name in enumerate(R.STATS):
+        R.check_rule(f"{tag}/stat.{name}", stats[i], s64[name], s32[name], report)
+    for key in g64:
+        assert grads[key].shape == tuple(g64[key].shape)
+        R.check_rule(f"{tag}/grad.{key}", grads[key], g64[key].numpy(), g32[key].numpy(), report)
+    return stats, s64, s32
+
+
+# ---------------------------------------------------------------------------------------------- the Zone-goals learners
+def hier_setup(Z, cfg, h, N, seed):
+    """A goal-enabled handle: fresh parameters loaded into the acting agent, one collect_hier of HIER_T frames, rows 0-7
+    of the high level's records planted so that every loss branch is reached by construction."""
+    from combinatorial_rl_tasks_amd.torch_interop import TorchZoneEnv
+    T = HIER_T
+    env = Z.ZoneVecEnv(cfg, N)
+    env.build_bank(11, N)
+    env.schedule_sequential()
+    env.enable_goals()
+    env.reset()
+    F, Zn = env.zone_feat, env.num_zones
+    hi_sd, lo_sd = H.random_state_dicts(F, h=h, seed=seed)
+    env.load_hier(Z.hier_tensors_from_state_dicts(hi_sd, lo_sd))
+    tenv = TorchZoneEnv(env)
+    lo_t, hi_t = tenv.collect_hier(T, policy_seed=5)
+    M = int(hi_t["value"].shape[0])
+    assert M >= 2 * N and M >= PLANTED, (M, N)
+    # ---- the planted rows (the aliases write the handle's own ZENV_F_HI_* buffers)
+    a = hi_t["action"].long()
+    hi_t["action_mask"][0] = False
+    hi_t["action_mask"][0, a[0]] = True                     # one available goal
+    hi_t["action_mask"][1] = True                           # all of them
+    torch.cuda.synchronize()
+    model = RH.model_from("hi", hi_sd, F, F64)
+    rows = {k: v[:PLANTED] for k, v in host(hi_t).items()}
+    b = RH.hi_batch(rows, np.arange(PLANTED), F64)
+    with torch.no_grad():
+        logits, v = model(b["obs"], b["zone_obs"])
+        lp = torch.log_softmax(logits.masked_fill(~b["action_mask"], float("-inf")), dim=1)
+        lp = lp.gather(1, b["action"].view(-1, 1)).squeeze(1)
+    dev = tenv.device
+    # rows 2-3: ratio e^0.5 above the range, rows 4-5: e^-0.5 below it; the advantage's sign picks the branch
+    hi_t["log_prob"][2:4] = (lp[2:4] - 0.5).float().to(dev)
+    hi_t["log_prob"][4:6] = (lp[4:6] + 0.5).float().to(dev)
+    hi_t["advantage"][2:6] = torch.tensor([0.9, -0.8, 0.7, -1.1], device=dev)
+    # rows 6-7: the recorded value 1 away, the return just past the new value: the clipped term is the larger one
+    hi_t["value"][6:8] = (v[6:8] + torch.tensor([-1.0, 1.0], dtype=F64)).float().to(dev)
+    hi_t["returnn"][6:8] = (v[6:8] + torch.tensor([0.05, -0.05], dtype=F64)).float().to(dev)
+    torch.cuda.synchronize()
+    return dict(env=env, tenv=tenv, hi_sd=hi_sd, lo_sd=lo_sd, sd={"hi": hi_sd, "lo": lo_sd}, F=F, Z=Zn, h=h, N=N, M=M,
+                lo_t=lo_t, hi_t=hi_t, lo=host(lo_t), hi=host(hi_t), total={"lo": N * (T - 1), "hi": M})
+
+
+def hier_batch(s, level, idx, dt):
+    return RH.lo_batch(s["lo"], idx, dt) if level == "lo" else RH.hi_batch(s["hi"], idx, dt)
+
+
+def hier_keys(level):
+    from combinatorial_rl_tasks_amd import agents
+    hi, lo = agents.hppo_state_dict_keys()
+    return hi if level == "hi" else lo
+
+
+def hier_by_key(env, level, which):
+    t = env.hppo_tensors(LEVELS[level], which)
+    return {key: t[name] for name, key in hier_keys(level).items()}
+
+
+def hier_init(s, sd=None, lo=None, hi=None):
+    sd = sd or s["sd"]
+    big = dict(max_batch=max(s["total"].values()))
+    s["env"].hppo_init(sd["hi"], sd["lo"], lo=dict(big, **(lo or {})), hi=dict(big, **(hi or {})))
+
+
+def hier_check_minibatch(Z, s, level, sd, idx, hyper, tag, report):
+    """apply = 0 on `sd`: the six statistics and every gradient tensor under the rule."""
+    env = s["env"]
+    over = {k: hyper[k] for k in ("clip_eps", "entropy_coef", "value_loss_coef")}
+    hier_init(s, dict(s["sd"], **{level: sd}), **{level: over})
+    env.hppo_minibatch(LEVELS[level], np.asarray(idx, np.int32))
+    stats = env.hppo_stats(LEVELS[level])[0]
+    grads = hier_by_key(env, level, Z._native.PPO_GRAD)
+    ref = {}
+    for dt in (F64, F32):
+        ref[dt] = RH.gradients(level, RH.model_from(level, sd, s["F"], dt), hier_batch(s, level, idx, dt), hyper)
+    (g64, s64), (g32, s32) = ref[F64], ref[F32]
+    assert len(grads) == (16 if level == "hi" else 18) and set(grads) == set(g64)
+    for i, name in enumerate(RH.STATS):
+        R.check_rule(f"{tag}/{level}.stat.{name}", stats[i], s64[name], s32[name], report)
+    for key in g64:
+        assert grads[key].shape == tuple(g64[key].shape)
+        R.check_rule(f"{tag}/{level}.grad.{key}", grads[key], g64[key].numpy(), g32[key].numpy(), report)
+    return stats, s64, s32
+
+
+def hier_indexes(s, level, batch, seed):
+    """`batch` sample indexes ("all": every one); the last valid index is always among them.  High level: batches
+    smaller than everything come from the rows that are not planted."""
+    total = s["total"][level]
+    if batch == "all":
+        return np.arange(total)
+    first = PLANTED if level == "hi" else 0
+    idx = first + np.random.default_rng(seed).permutation(total - first)[:batch]
+    idx[-1] = total - 1
+    return idx

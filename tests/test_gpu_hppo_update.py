@@ -15,17 +15,18 @@ import torch
 
 from tests import hier_ref as H
 from tests import hppo_update_ref as R
+from tests import ppo_update_dev as D
 from tests import ppo_update_ref as RF
 
 pytestmark = pytest.mark.gpu
 
 F32, F64 = torch.float32, torch.float64
-T = 33
+T = D.HIER_T
 CASES = {"tsp": ("PointTSP-v0", 185, 24), "cm7": ("ColourMatch-v0", 7, 5), "cm64": ("ColourMatch-v0", 64, 5),
          "ttsp": ("PointTTSP-v0", 191, 8), "z25": (None, 32, 4)}
-LEVELS = {"lo": 0, "hi": 1}
+LEVELS = D.LEVELS
 HYPER = {"lo": R.LO_HYPER, "hi": R.HI_HYPER}
-PLANTED = 8
+PLANTED = D.PLANTED
 _SETUPS = {}
 REPORT = []
 
@@ -36,119 +37,25 @@ def _teardown():
     for s in _SETUPS.values():
         s["env"].set_stream(None)
         s["env"].close()
-    worst = {}
-    for name, e_dev, e32, ratio in REPORT:
-        key = name.split("/")[-1]
-        worst[key] = max(worst.get(key, 0.0), ratio)
-    for k in sorted(worst):
-        print("hppo update worst e_dev / max(e32, ulp): %-44s %.3f" % (k, worst[k]))
-
-
-def _host(d):
-    return {k: np.ascontiguousarray(v.cpu().numpy()) for k, v in d.items()}
+    D.print_worst(REPORT, "hppo update", 44)
 
 
 def _setup(Z, case, tag=""):
     """One handle per shape: fresh parameters loaded into the acting agent, one collect_hier, rows 0-7 planted."""
     key = case + tag
-    if key in _SETUPS:
-        return _SETUPS[key]
-    from combinatorial_rl_tasks_amd.torch_interop import TorchZoneEnv
-    env_id, h, N = CASES[case]
-    cfg = (Z.config_for_id(env_id, num_steps=12) if env_id
-           else Z.default_config(0, 25, zones_keepout=0.40, num_steps=12))
-    env = Z.ZoneVecEnv(cfg, N)
-    env.build_bank(11, N)
-    env.schedule_sequential()
-    env.enable_goals()
-    env.reset()
-    F, Zn = env.zone_feat, env.num_zones
-    hi_sd, lo_sd = H.random_state_dicts(F, h=h, seed=list(CASES).index(case))
-    env.load_hier(Z.hier_tensors_from_state_dicts(hi_sd, lo_sd))
-    tenv = TorchZoneEnv(env)
-    lo_t, hi_t = tenv.collect_hier(T, policy_seed=5)
-    M = int(hi_t["value"].shape[0])
-    assert M >= 2 * N and M >= PLANTED, (M, N)
-    # ---- the planted rows (the aliases write the handle's own ZENV_F_HI_* buffers)
-    a = hi_t["action"].long()
-    hi_t["action_mask"][0] = False
-    hi_t["action_mask"][0, a[0]] = True                     # one available goal
-    hi_t["action_mask"][1] = True                           # all of them
-    torch.cuda.synchronize()
-    model = R.model_from("hi", hi_sd, F, F64)
-    rows = {k: v[:PLANTED] for k, v in _host(hi_t).items()}
-    b = R.hi_batch(rows, np.arange(PLANTED), F64)
-    with torch.no_grad():
-        logits, v = model(b["obs"], b["zone_obs"])
-        lp = torch.log_softmax(logits.masked_fill(~b["action_mask"], float("-inf")), dim=1)
-        lp = lp.gather(1, b["action"].view(-1, 1)).squeeze(1)
-    dev = tenv.device
-    # rows 2-3: ratio e^0.5 above the range, rows 4-5: e^-0.5 below it; the advantage's sign picks the branch
-    hi_t["log_prob"][2:4] = (lp[2:4] - 0.5).float().to(dev)
-    hi_t["log_prob"][4:6] = (lp[4:6] + 0.5).float().to(dev)
-    hi_t["advantage"][2:6] = torch.tensor([0.9, -0.8, 0.7, -1.1], device=dev)
-    # rows 6-7: the recorded value 1 away, the return just past the new value: the clipped term is the larger one
-    hi_t["value"][6:8] = (v[6:8] + torch.tensor([-1.0, 1.0], dtype=F64)).float().to(dev)
-    hi_t["returnn"][6:8] = (v[6:8] + torch.tensor([0.05, -0.05], dtype=F64)).float().to(dev)
-    torch.cuda.synchronize()
-    s = dict(env=env, tenv=tenv, hi_sd=hi_sd, lo_sd=lo_sd, sd={"hi": hi_sd, "lo": lo_sd}, F=F, Z=Zn, h=h, N=N, M=M,
-             lo_t=lo_t, hi_t=hi_t, lo=_host(lo_t), hi=_host(hi_t), total={"lo": N * (T - 1), "hi": M})
-    _SETUPS[key] = s
-    return s
+    if key not in _SETUPS:
+        env_id, h, N = CASES[case]
+        cfg = (Z.config_for_id(env_id, num_steps=12) if env_id
+               else Z.default_config(0, 25, zones_keepout=0.40, num_steps=12))
+        _SETUPS[key] = D.hier_setup(Z, cfg, h, N, seed=list(CASES).index(case))
+    return _SETUPS[key]
 
 
-def _batch(s, level, idx, dt):
-    return R.lo_batch(s["lo"], idx, dt) if level == "lo" else R.hi_batch(s["hi"], idx, dt)
-
-
-def _keys(level):
-    from combinatorial_rl_tasks_amd import agents
-    hi, lo = agents.hppo_state_dict_keys()
-    return hi if level == "hi" else lo
-
-
-def _by_key(env, level, which):
-    t = env.hppo_tensors(LEVELS[level], which)
-    return {key: t[name] for name, key in _keys(level).items()}
-
-
-def _init(s, sd=None, lo=None, hi=None):
-    sd = sd or s["sd"]
-    big = dict(max_batch=max(s["total"].values()))
-    s["env"].hppo_init(sd["hi"], sd["lo"], lo=dict(big, **(lo or {})), hi=dict(big, **(hi or {})))
+_batch, _by_key, _init, _indexes = D.hier_batch, D.hier_by_key, D.hier_init, D.hier_indexes
 
 
 def _check_minibatch(Z, s, level, sd, idx, hyper, tag):
-    """apply = 0 on `sd`: the six statistics and every gradient tensor under the rule."""
-    env = s["env"]
-    over = {k: hyper[k] for k in ("clip_eps", "entropy_coef", "value_loss_coef")}
-    _init(s, dict(s["sd"], **{level: sd}), **{level: over})
-    env.hppo_minibatch(LEVELS[level], np.asarray(idx, np.int32))
-    stats = env.hppo_stats(LEVELS[level])[0]
-    grads = _by_key(env, level, Z._native.PPO_GRAD)
-    ref = {}
-    for dt in (F64, F32):
-        ref[dt] = R.gradients(level, R.model_from(level, sd, s["F"], dt), _batch(s, level, idx, dt), hyper)
-    (g64, s64), (g32, s32) = ref[F64], ref[F32]
-    assert len(grads) == (16 if level == "hi" else 18) and set(grads) == set(g64)
-    for i, name in enumerate(R.STATS):
-        R.check_rule(f"{tag}/{level}.stat.{name}", stats[i], s64[name], s32[name], REPORT)
-    for key in g64:
-        assert grads[key].shape == tuple(g64[key].shape)
-        R.check_rule(f"{tag}/{level}.grad.{key}", grads[key], g64[key].numpy(), g32[key].numpy(), REPORT)
-    return stats, s64, s32
-
-
-def _indexes(s, level, batch, seed):
-    """`batch` sample indexes ("all": every one); the last valid index is always among them.  High level: batches
-    smaller than everything come from the rows that are not planted."""
-    total = s["total"][level]
-    if batch == "all":
-        return np.arange(total)
-    first = PLANTED if level == "hi" else 0
-    idx = first + np.random.default_rng(seed).permutation(total - first)[:batch]
-    idx[-1] = total - 1
-    return idx
+    return D.hier_check_minibatch(Z, s, level, sd, idx, hyper, tag, REPORT)
 
 
 LO_FRESH = [("tsp", 1), ("tsp", 37), ("tsp", 100), ("tsp", "all"), ("cm7", "all"), ("cm64", "all"), ("ttsp", "all"),

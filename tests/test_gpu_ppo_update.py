@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import ppo_update_dev as D
 from tests import ppo_update_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -26,62 +27,24 @@ def _teardown():
     yield
     for s in _SETUPS.values():
         s["env"].close()
-    worst = {}
-    for name, e_dev, e32, ratio in REPORT:
-        key = name.split("/")[-1]
-        worst[key] = max(worst.get(key, 0.0), ratio)
-    for k in sorted(worst):
-        print("ppo update worst e_dev / max(e32, ulp): %-40s %.3f" % (k, worst[k]))
+    D.print_worst(REPORT, "ppo update", 40)
 
 
 def _setup(Z, case, dist):
     """One handle per (shape, critic): fresh parameters loaded into the acting network, one collect."""
     key = (case, dist)
     if key not in _SETUPS:
-        from combinatorial_rl_tasks_amd import agents
         env_id, h, N, T = CASES[case]
         cfg = Z.config_for_id(env_id) if env_id else Z.default_config(0, 25, zones_keepout=0.40)
-        env = Z.ZoneVecEnv(cfg, N)
-        env.build_bank(11, 2 * N)
-        env.reset()
-        sd = R.random_state_dict(env.zone_feat, h, dist, seed=len(_SETUPS))
-        env.load_mlp(agents.mlp_tensors_from_state_dict(sd), precision="f32")
-        exps = {k: np.ascontiguousarray(v) for k, v in env.collect(T, policy_seed=5).items()}
-        _SETUPS[key] = dict(env=env, sd=sd, exps=exps, F=env.zone_feat, h=h, N=N, T=T, dist=dist)
+        _SETUPS[key] = D.flat_setup(Z, cfg, h, N, T, dist, seed=len(_SETUPS))
     return _SETUPS[key]
 
 
-def _by_key(env, which):
-    t = env.ppo_tensors(which)
-    return {key: t[name] for name, key in env._ppo_keys.items()}
-
-
-def _ref_pair(sd, s, idx, hyper):
-    out = []
-    for dt in (F64, F32):
-        model = R.model_from(sd, s["F"], dt)
-        grads, stats = R.gradients(model, R.as_batch(s["exps"], idx, dt), hyper)
-        _, _, outputs = R.loss_and_stats(model, R.as_batch(s["exps"], idx, dt), hyper)
-        out.append((grads, stats, outputs))
-    return out
+_by_key = D.flat_by_key
 
 
 def _check_minibatch(Z, s, sd, idx, hyper, tag):
-    """apply = 0 on `sd`: the statistics and every gradient tensor under the rule."""
-    nat = Z._native
-    env = s["env"]
-    env.ppo_init(sd, max_batch=384, **hyper)
-    env.ppo_minibatch(np.asarray(idx, np.int32))
-    stats = env.ppo_stats()[0]
-    grads = _by_key(env, nat.PPO_GRAD)
-    (g64, s64, _), (g32, s32, _) = _ref_pair(sd, s, idx, hyper)
-    assert len(grads) == (20 if s["dist"] else 18) and set(grads) == set(g64)
-    for i, name in enumerate(R.STATS):
-        R.check_rule(f"{tag}/stat.{name}", stats[i], s64[name], s32[name], REPORT)
-    for key in g64:
-        assert grads[key].shape == tuple(g64[key].shape)
-        R.check_rule(f"{tag}/grad.{key}", grads[key], g64[key].numpy(), g32[key].numpy(), REPORT)
-    return stats, s64, s32
+    return D.flat_check_minibatch(Z, s, sd, idx, hyper, tag, REPORT)
 
 
 FRESH = [("tsp", False, 1), ("tsp", False, 37), ("tsp", False, 100), ("tsp", False, 384), ("tsp", True, 100),
