@@ -46,7 +46,8 @@ E_ARG, E_HIP, E_STATE, E_LAYOUT, E_DONE, E_RANGE = -1, -2, -3, -4, -5, -6
  F_OPTION_TERM_MU, F_OPTION_TERM_STD, F_OPTION_TERM_ACTION, F_OPTION_TERM_PROB, F_OPTION_ENDED,
  F_LO_TERM_ACTION, F_LO_TERM_LOG_PROB, F_LO_OPTION_ENDED,
  F_XY_GOAL, F_XY_GOAL_MU, F_XY_GOAL_STD, F_XY_VALUE, F_XY_GOAL_AGE,
- F_HI_GOAL, F_LO_GOAL_DIST, F_XY_BOOTSTRAP_GOAL, F_PPO_STATS, F_HPPO_LO_STATS, F_HPPO_HI_STATS) = range(77)
+ F_HI_GOAL, F_LO_GOAL_DIST, F_XY_BOOTSTRAP_GOAL, F_PPO_STATS, F_HPPO_LO_STATS, F_HPPO_HI_STATS,
+ F_XYPPO_LO_STATS, F_XYPPO_HI_STATS) = range(79)
 (RESULT_OBS, RESULT_REWARD, RESULT_DONE, RESULT_GOAL_MET, RESULT_EXCEPTION, RESULT_ZONE_OBS) = range(6)
 N_RESULTS = 6
 
@@ -128,6 +129,8 @@ PPO_PARAM, PPO_GRAD, PPO_EXP_AVG, PPO_EXP_AVG_SQ = 0, 1, 2, 3
 PPO_STATS = ("entropy", "value", "value_std", "policy_loss", "value_loss", "grad_norm")   # ZENV_F_PPO_STATS' columns
 HPPO_LO, HPPO_HI = 0, 1                                       # the `level` of the zenv_hppo_* functions
 HPPO_STATS_FIELDS = (F_HPPO_LO_STATS, F_HPPO_HI_STATS)        # by level
+XYPPO_LO, XYPPO_HI = 0, 1                                     # the `level` of the zenv_xyppo_* functions
+XYPPO_STATS_FIELDS = (F_XYPPO_LO_STATS, F_XYPPO_HI_STATS)     # by level
 
 
 class PpoConfig(C.Structure):
@@ -247,6 +250,16 @@ _PROTOTYPES = {
     "zenv_hppo_minibatch": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "zenv_hppo_apply": (C.c_int, [_H, C.c_int]),
     "zenv_hppo_epoch": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "zenv_xyppo_check": (C.c_int, [C.POINTER(Config), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "zenv_xyppo_init": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "zenv_xyppo_tensor": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    "zenv_xyppo_read": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "zenv_xyppo_write": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "zenv_xyppo_get_step": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int64)]),
+    "zenv_xyppo_set_step": (C.c_int, [_H, C.c_int, C.c_int64]),
+    "zenv_xyppo_minibatch": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "zenv_xyppo_apply": (C.c_int, [_H, C.c_int]),
+    "zenv_xyppo_epoch": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "zenv_get": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int]),
     "zenv_get_rows": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "zenv_device_ptr": (C.c_int, [_H, C.c_int, C.POINTER(C.c_void_p)]),

@@ -4,6 +4,9 @@
 // both critics of ACModel (flat_model.py:21-68).  The same launches serve the Zone-goals agent's two learners
 // (zone-goals/src/torch_ac/algos/_hier_policy_opt.py:214-370): the low level is this network on [obs, goal] (XD = 10
 // where the flat one has 8), the high level this encoder and critic under a per-zone head (PPO_HEAD_ZONES, below).
+// And the xy-goals agent's two (xy-goals/src/torch_ac/algos/_hier_policy_opt.py:195-363): its low level is the
+// Zone-goals low level on all T frames of an env, its high level the flat network on the dense rows of its windows with
+// the loss of k_xyppo_hi_loss.
 //
 // Every layer is a product on v_mfma_f32_32x32x2_f32, forward and backward, in one of two shapes:
 //
@@ -460,6 +463,58 @@ __global__ void k_ppo_loss(PpoNet n, PpoExp x, Gather g, int bp)
     for (int i = 0; i < 8; ++i) n.SS[(size_t)b * 8 + i] = ss[i];
 }
 
+// The loss of one row of the xy-goals agent's high level (xy-goals/src/torch_ac/algos/_hier_policy_opt.py:288-363) and
+// its derivative with respect to the head pre-activations (PRE: mu_ 0-1, std_ 2-3, critic.2 4).  The network is the flat
+// one; the "action" is the recorded goal x.action [slot][2], and three things differ from k_ppo_loss:
+//   * x.log_prob holds ONE float per row, the recorded log_prob already summed over the goal's two dimensions:
+//     dlp = (lp_0 + lp_1) - log_prob[slot];
+//   * the entropy is summed over the two dimensions before the mean over rows (k_ppo_stats divides by count, not by
+//     2 count), so d loss / d std_o carries entropy_coef / (count std_o) where the flat loss has half of it;
+//   * the value loss is always the clipped one: the agent has no distributional critic.
+__global__ void k_xyppo_hi_loss(PpoNet n, PpoExp x, Gather g, int bp)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= bp) return;
+    float d[6] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f }, ss[8] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
+    size_t slot = 0;
+    if (sample_slot(g, b, slot)) {
+        const float *pre = n.PRE + (size_t)b * 32;
+        const PpoHyper &hy = n.hyper;
+        const float inv_b = 1.0f / (float)g.count;
+        float sd[2], smu[2], ssd[2], diff[2], lp[2], ent = 0.f;
+#pragma unroll
+        for (int o = 0; o < 2; ++o) {
+            smu[o] = sigmoidf(pre[o]);
+            ssd[o] = sigmoidf(pre[2 + o]);
+            const float mu = 2.0f * (smu[o] - 0.5f);          // policy_network.py:46-47
+            sd[o] = ssd[o] + 1e-3f;
+            diff[o] = x.action[slot * 2 + o] - mu;
+            lp[o] = -(diff[o] * diff[o]) / (2.0f * (sd[o] * sd[o])) - logf(sd[o]) - 0.9189385332046727f;
+            ent += 0.5f + 0.9189385332046727f + logf(sd[o]);  // Normal.entropy, .sum(dim=-1)
+        }
+        float g_lp;                                           // d loss / d log_prob(goal_o), the same for both o
+        const float ploss = clipped_policy((lp[0] + lp[1]) - x.log_prob[slot], x.advantage[slot], hy.clip_eps, inv_b, g_lp);
+#pragma unroll
+        for (int o = 0; o < 2; ++o) {
+            const float var = sd[o] * sd[o];
+            const float g_mu = g_lp * (diff[o] / var);
+            const float g_sd = g_lp * ((diff[o] * diff[o]) / (var * sd[o]) - 1.0f / sd[o]) - hy.entropy_coef * inv_b / sd[o];
+            d[o] = g_mu * 2.0f * smu[o] * (1.0f - smu[o]);
+            d[2 + o] = g_sd * ssd[o] * (1.0f - ssd[o]);
+        }
+        const float v = pre[4];
+        ss[0] = ent;
+        ss[1] = v;
+        ss[3] = ploss;
+        ss[4] = clipped_value(v, x.value[slot], x.returnn[slot], hy, inv_b, d[4]);
+    }
+    float *dh = n.DH + (size_t)b * 32;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) dh[i] = i < 6 ? d[i] : 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) n.SS[(size_t)b * 8 + i] = ss[i];
+}
+
 // ---- PPO_HEAD_ZONES: the Zone-goals high level's actor (zone-goals/src/hier_policy_value_models.py:19-56), one logit
 // per zone from actor.2(relu(actor.0([emb, zone row]))).  With actor.0.weight = [W_e | W_z] the emb part E = W_e emb + b
 // is taken once per sample (k_ppo_nt, into Ha; its column h is the constant 1) and
@@ -597,7 +652,8 @@ __device__ __forceinline__ double block_sum_256(double v, double *sh)
 }
 
 // stats[0..4] = the minibatch means of the per-sample terms; one block of 256 threads, thread i adds samples i, i + 256 ...
-// ent_terms: the entropy's mean is over count x 2 action components, or over count categoricals.  zero_grad (or null):
+// ent_terms: the entropy's mean is over count x 2 action components, or over count categoricals or rows whose two
+// components' entropies are already summed (k_xyppo_hi_loss).  zero_grad (or null):
 // a gradient that is 0 for every input -- PPO_HEAD_ZONES: actor.2.bias', see k_hppo_loss
 __global__ __launch_bounds__(256) void k_ppo_stats(const float *__restrict__ SS, int count, double ent_terms,
                                                    float *__restrict__ stats, float *__restrict__ zero_grad)
@@ -705,8 +761,13 @@ void gaussian_head(const PpoNet &n, const PpoExp &x, const Gather &g, int bp, fl
     nt<NT_RELU>(I[PPO_I_WV], HP, n.C, HP, HP, n.Hc, HP, bp, NT, s);                       // relu(critic.0)
     nt<NT_STORE>(I[PPO_I_HA], HP, n.Ha, HP, HP, n.PRE, 32, bp, 1, s);                     // mu_, std_
     nt<NT_ADD>(I[PPO_I_HV], HP, n.Hc, HP, HP, n.PRE, 32, bp, 1, s);                       // critic.2 / critic_mu, critic_sigma
-    hipLaunchKernelGGL(k_ppo_loss, dim3((bp + 63) / 64), dim3(64), 0, s, n, x, g, bp);
-    hipLaunchKernelGGL(k_ppo_stats, dim3(1), dim3(256), 0, s, n.SS, g.count, 2.0, stats, (float *)nullptr);
+    if (n.loss == PPO_LOSS_JOINT_GOAL) {                      // the entropy's mean is over the rows alone
+        hipLaunchKernelGGL(k_xyppo_hi_loss, dim3((bp + 63) / 64), dim3(64), 0, s, n, x, g, bp);
+        hipLaunchKernelGGL(k_ppo_stats, dim3(1), dim3(256), 0, s, n.SS, g.count, 1.0, stats, (float *)nullptr);
+    } else {
+        hipLaunchKernelGGL(k_ppo_loss, dim3((bp + 63) / 64), dim3(64), 0, s, n, x, g, bp);
+        hipLaunchKernelGGL(k_ppo_stats, dim3(1), dim3(256), 0, s, n.SS, g.count, 2.0, stats, (float *)nullptr);
+    }
     // ---- backward: every weight gradient is taken before its layer's activations are overwritten by deltas
     tn(n.DH, 32, 1, n.Ha, HP, HP, bp, n.partial, s);
     reduce(n, bp, 1, HP, 0, 0, PPO_MU_W, h, 0, 2, h, s);

@@ -1,5 +1,5 @@
-// ppo_update.hpp -- the PPO updates on the device (ppo_update.hip): the flat actor-critic's and the Zone-goals agent's
-// two levels'.  What zenv_train.cpp hands to the launches.  Internal: not installed.
+// ppo_update.hpp -- the PPO updates on the device (ppo_update.hip): the flat actor-critic's, the Zone-goals agent's two
+// levels' and the xy-goals agent's two levels'.  What zenv_train.cpp hands to the launches.  Internal: not installed.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -18,6 +18,9 @@ enum {
 // actor.0 / actor.2 where the Gaussian actor has enc_ / mu_, then the critic two places earlier (PpoNet::cr)
 enum { PPO_ACTOR_W1 = PPO_ENC_W, PPO_ACTOR_B1 = PPO_ENC_B, PPO_ACTOR_W2 = PPO_MU_W, PPO_ACTOR_B2 = PPO_MU_B };
 enum { PPO_HEAD_GAUSSIAN = 0, PPO_HEAD_ZONES = 1 };
+// what the Gaussian head's loss is taken of: the flat learner's action with a recorded log_prob per component
+// (k_ppo_loss), or the xy-goals high level's goal with one recorded log_prob per row (k_xyppo_hi_loss)
+enum { PPO_LOSS_ACTION = 0, PPO_LOSS_JOINT_GOAL = 1 };
 // the padded weight images k_ppo_prep rebuilds from the arena before every minibatch (I_*: [out][in] with the bias in
 // column h, the A operand of a forward product; T_*: the transpose, the A operand of a backward-data product)
 enum {
@@ -39,6 +42,7 @@ struct PpoNet {
     int W1C;                 // columns of zone_net_.0's image and gathered input: XD + F + 1 rounded up to 8; the last is
                              // the constant that carries the bias.  KC = HP + XD rounded up to 8
     int head;                // PPO_HEAD_GAUSSIAN: enc_, mu_, std_;  PPO_HEAD_ZONES: actor.0 / actor.2 over [emb, zone row]
+    int loss;                // PPO_LOSS_ACTION, or PPO_LOSS_JOINT_GOAL: the xy-goals high level (PPO_HEAD_GAUSSIAN only)
     int cr;                  // the arena index of critic.0.weight: PPO_CRITIC_W1, or two less under PPO_HEAD_ZONES
     int split_reduce;        // the partials of a weight gradient are added by kPpoReduceSplit threads per element
                              // (k_ppo_reduce_split); 0 for the flat learner, whose sums keep their one chain and bits
@@ -66,6 +70,8 @@ struct PpoNet {
 // The experience a minibatch is gathered from.  Sample index i is env i / T, frame i % T, and lies at slot
 // frame * N + env: the handle's time-major buffers with T the frames an env hands out (all of them; one less for the
 // Zone-goals low level, whose last frame is never read), or dense rows with N = the rows and T = 1.
+// PPO_LOSS_JOINT_GOAL: action is the recorded goal [slot][2] and log_prob one float per slot, the sum over both
+// dimensions.
 struct PpoExp {
     const float *obs, *zone_obs, *action, *log_prob, *value, *advantage, *returnn;
     int N, T;

@@ -663,6 +663,7 @@ static int ensure_exp(zenv_t *h, int T)
 {
     const size_t N = (size_t)h->n_env, ZF = (size_t)h->p.Z * h->p.F;
     h->exp_hier = false;        // zenv_collect_hier sets it once its records are complete
+    h->exp_xy = false;          // zenv_collect_xy, the same
     if (!h->exp_mem || h->exp.T != T) {
         HIP_TRY(hipStreamSynchronize(h->stream));
         std::vector<float> keep_mask;
@@ -1086,6 +1087,7 @@ extern "C" int zenv_collect_xy(zenv_t *h, int T, uint64_t policy_seed, uint64_t 
     HIP_TRY(launch_exp_gae(h->exp, h->n_env, h->mlp_value, discount, gae_lambda, h->stream));
     HIP_TRY(launch_skill_hi_gae(o, T, L, h->n_env, h->xc.env_reward, h->exp.mask, h->exp.cur_mask, h->xy_value,
                                 gae_lambda, h->xc.count, h->stream));
+    h->exp_xy = true;
     return ZENV_OK;
 }
 

@@ -247,9 +247,11 @@ FieldInfo field_info(const zenv *h, int field)
     case ZENV_F_XY_BOOTSTRAP_GOAL: return { h->xc.boot, h->xc_mem ? N * 2 * 4 : 0 };
     case ZENV_F_PPO_STATS:
     case ZENV_F_HPPO_LO_STATS:
-    case ZENV_F_HPPO_HI_STATS: {
+    case ZENV_F_HPPO_HI_STATS:
+    case ZENV_F_XYPPO_LO_STATS:
+    case ZENV_F_XYPPO_HI_STATS: {       // five consecutive fields, ppo_stats' order
         int64_t bytes = 0;
-        void *ptr = ppo_stats(h, field == ZENV_F_PPO_STATS ? 0 : field - ZENV_F_HPPO_LO_STATS + 1, &bytes);
+        void *ptr = ppo_stats(h, field - ZENV_F_PPO_STATS, &bytes);
         return { ptr, bytes };
     }
     default: return { nullptr, 0 };

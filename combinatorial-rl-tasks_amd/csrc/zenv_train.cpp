@@ -1,7 +1,7 @@
 // zenv_train.cpp -- the learners behind the C ABI of include/zenv.h: the flat actor-critic's PPO update on the handle's own
 // experience buffers (zenv_ppo_*) and the Zone-goals agent's two (zenv_hppo_*, level 0 = low, 1 = high) on the records
-// of zenv_collect_hier.  One PpoState each, the same code.  The kernels: ppo_update.hip.  The networks that act and
-// collect: zenv_agents.cpp.
+// of zenv_collect_hier, and the xy-goals agent's two (zenv_xyppo_*, the same levels) on the records of zenv_collect_xy.
+// One PpoState each, the same code.  The kernels: ppo_update.hip.  The networks that act and collect: zenv_agents.cpp.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -18,18 +18,23 @@ struct PpoState {
     double lr = 0.0;
     int32_t *idx = nullptr;         // host indices, uploaded
     size_t idx_cap = 0;
-    float *stats = nullptr;         // ZENV_F_PPO_STATS / ZENV_F_HPPO_*_STATS [stats_cap][6]
+    float *stats = nullptr;         // ZENV_F_PPO_STATS / ZENV_F_HPPO_*_STATS / ZENV_F_XYPPO_*_STATS [stats_cap][6]
     int stats_cap = 0, stats_rows = 0;
 };
 
 namespace {
 
-// which network a learner trains: the width of its per-sample input and its head
+// which network a learner trains: the width of its per-sample input, its head and what the head's loss is taken of
 struct NetKind {
-    int XD, head;
+    int XD, head, loss;
     int w1c() const { return XD == 8 ? 16 : 24; }       // XD + F + 1 <= 16 / 18 columns, rounded up to 8
+    // the flat actor-critic's learner; every other one belongs to a hierarchical agent
+    bool flat() const { return XD == 8 && head == PPO_HEAD_GAUSSIAN && loss == PPO_LOSS_ACTION; }
 };
-constexpr NetKind kFlat{ 8, PPO_HEAD_GAUSSIAN }, kHierLo{ 10, PPO_HEAD_GAUSSIAN }, kHierHi{ 8, PPO_HEAD_ZONES };
+constexpr NetKind kFlat{ 8, PPO_HEAD_GAUSSIAN, PPO_LOSS_ACTION }, kHierLo{ 10, PPO_HEAD_GAUSSIAN, PPO_LOSS_ACTION },
+    kHierHi{ 8, PPO_HEAD_ZONES, PPO_LOSS_ACTION };
+// the xy-goals agent: its low level is the Zone-goals low level, its high level the flat network under the joint loss
+constexpr NetKind kXyLo = kHierLo, kXyHi{ 8, PPO_HEAD_GAUSSIAN, PPO_LOSS_JOINT_GOAL };
 
 // element counts of the tensors for hidden size h and zone rows of F features: zenv_mlp_weights' member order (20; the
 // Zone-goals low level's 18 with XD = 10), or the 16 of zenv_hier_weights' hi_* members
@@ -101,12 +106,12 @@ int learner_check(const zenv_config *cfg, int h_dim, const float *const *t, NetK
         if (!t[i]) return fail(ZENV_E_ARG, "%sa tensor of the weights is null", who);
     for (int i = critic; i < critic + 4; ++i)
         if (!t[i]) return fail(ZENV_E_ARG, "%sthe update needs the critic: critic_w1 / _b1 / _w2 / _b2", who);
-    const bool hier = k.XD != 8 || k.head != PPO_HEAD_GAUSSIAN;
+    const bool hier = !k.flat();
     if (hier && pc->distributional_value)
-        return fail(ZENV_E_ARG, "%sdistributional_value must be 0: the Zone-goals critics are plain", who);
+        return fail(ZENV_E_ARG, "%sdistributional_value must be 0: the hierarchical agents' critics are plain", who);
     for (double v : { pc->lr, pc->adam_eps, pc->clip_eps, pc->entropy_coef, pc->value_loss_coef })
         if (bad_hyper(v)) return fail(ZENV_E_ARG, "%sa hyper-parameter is negative or not finite (%g)", who, v);
-    // the Zone-goals reference takes the norm and does not clip: +inf stands for that
+    // the hierarchical agents' references take the norm and do not clip: +inf stands for that
     if (bad_hyper(pc->max_grad_norm) && !(hier && pc->max_grad_norm == INFINITY))
         return fail(ZENV_E_ARG, "%sa hyper-parameter is negative or not finite (%g)", who, pc->max_grad_norm);
     if (pc->max_batch < 1) return fail(ZENV_E_ARG, "%smax_batch must be >= 1", who);
@@ -127,6 +132,20 @@ void hier_tensor_lists(const zenv_hier_weights *w, const float *(&lo)[PPO_MAX_TE
                                         w->hi_zone_b3, w->hi_comb_w, w->hi_comb_b, w->hi_actor_w1, w->hi_actor_b1,
                                         w->hi_actor_w2, w->hi_actor_b2, w->hi_critic_w1, w->hi_critic_b1, w->hi_critic_w2,
                                         w->hi_critic_b2, nullptr, nullptr, nullptr, nullptr };
+    std::copy(l, l + PPO_MAX_TENSORS, lo);
+    std::copy(u, u + PPO_MAX_TENSORS, hi);
+}
+
+void xy_tensor_lists(const zenv_xy_weights *w, const float *(&lo)[PPO_MAX_TENSORS], const float *(&hi)[PPO_MAX_TENSORS])
+{
+    const float *l[PPO_MAX_TENSORS] = { w->lo_zone_w1, w->lo_zone_b1, w->lo_zone_w2, w->lo_zone_b2, w->lo_zone_w3,
+                                        w->lo_zone_b3, w->lo_comb_w, w->lo_comb_b, w->lo_enc_w, w->lo_enc_b, w->lo_mu_w,
+                                        w->lo_mu_b, w->lo_std_w, w->lo_std_b, w->lo_critic_w1, w->lo_critic_b1,
+                                        w->lo_critic_w2, w->lo_critic_b2, nullptr, nullptr };
+    const float *u[PPO_MAX_TENSORS] = { w->hi_zone_w1, w->hi_zone_b1, w->hi_zone_w2, w->hi_zone_b2, w->hi_zone_w3,
+                                        w->hi_zone_b3, w->hi_comb_w, w->hi_comb_b, w->hi_enc_w, w->hi_enc_b, w->hi_mu_w,
+                                        w->hi_mu_b, w->hi_std_w, w->hi_std_b, w->hi_critic_w1, w->hi_critic_b1,
+                                        w->hi_critic_w2, w->hi_critic_b2, nullptr, nullptr };
     std::copy(l, l + PPO_MAX_TENSORS, lo);
     std::copy(u, u + PPO_MAX_TENSORS, hi);
 }
@@ -159,6 +178,18 @@ extern "C" int zenv_hppo_check(const zenv_config *cfg, const zenv_hier_weights *
     return learner_check(cfg, w->h_dim, th, kHierHi, hi, "high level: ");
 }
 
+extern "C" int zenv_xyppo_check(const zenv_config *cfg, const zenv_xy_weights *w, const zenv_ppo_config *lo,
+                                const zenv_ppo_config *hi)
+{
+    if (!cfg || !w || !lo || !hi) return fail(ZENV_E_ARG, "null argument");
+    if (w->zone_feat != zenv_zone_feat(cfg))
+        return fail(ZENV_E_ARG, "zone_feat %d: the handle's zone rows have %d features", w->zone_feat, zenv_zone_feat(cfg));
+    const float *tl[PPO_MAX_TENSORS], *th[PPO_MAX_TENSORS];
+    xy_tensor_lists(w, tl, th);
+    if (int rc = learner_check(cfg, w->h_dim, tl, kXyLo, lo, "low level: ")) return rc;
+    return learner_check(cfg, w->h_dim, th, kXyHi, hi, "high level: ");
+}
+
 static void learner_free(PpoState *&s)
 {
     if (!s) return;
@@ -174,12 +205,14 @@ void ppo_free(zenv *h)
     learner_free(h->ppo);
     learner_free(h->hppo[0]);
     learner_free(h->hppo[1]);
+    learner_free(h->xyppo[0]);
+    learner_free(h->xyppo[1]);
 }
 
 int ppo_index_check(zenv *h)
 {
     bool bad = false;
-    for (PpoState *s : { h->ppo, h->hppo[0], h->hppo[1] })
+    for (PpoState *s : { h->ppo, h->hppo[0], h->hppo[1], h->xyppo[0], h->xyppo[1] })
         if (s && s->net.bad_index && *(volatile int *)s->net.bad_index) {
             *(volatile int *)s->net.bad_index = 0;
             bad = true;
@@ -192,7 +225,7 @@ int ppo_index_check(zenv *h)
 
 void *ppo_stats(const zenv *h, int which, int64_t *bytes)
 {
-    const PpoState *s = which == 0 ? h->ppo : h->hppo[which - 1];
+    const PpoState *s = which == 0 ? h->ppo : which <= 2 ? h->hppo[which - 1] : h->xyppo[which - 3];
     *bytes = s ? (int64_t)s->stats_rows * kPpoStats * 4 : 0;
     return s ? s->stats : nullptr;
 }
@@ -208,9 +241,9 @@ static int learner_create(zenv *h, PpoState *&slot, int h_dim, const float *cons
     PpoNet &n = s->net;
     const Layout l = layout_for(h_dim, h->p.Z, pc->max_batch, k);
     n.h = h_dim, n.HP = l.HP, n.F = h->p.F, n.Z = h->p.Z, n.K1 = k.XD + h->p.F, n.KC = l.KC;
-    n.XD = k.XD, n.W1C = k.w1c(), n.head = k.head;
+    n.XD = k.XD, n.W1C = k.w1c(), n.head = k.head, n.loss = k.loss;
     n.cr = k.head == PPO_HEAD_ZONES ? PPO_CRITIC_W1 - 2 : PPO_CRITIC_W1;
-    n.split_reduce = (k.XD != 8 || k.head != PPO_HEAD_GAUSSIAN) ? 1 : 0;     // the Zone-goals learners
+    n.split_reduce = k.flat() ? 0 : 1;                  // the hierarchical agents' learners
     n.dist = pc->distributional_value ? 1 : 0;
     n.n_tensors = k.head == PPO_HEAD_ZONES ? 16 : n.dist ? 20 : 18;
     n.max_batch = pc->max_batch;
@@ -284,25 +317,50 @@ extern "C" int zenv_hppo_init(zenv_t *h, const zenv_hier_weights *w, const zenv_
     return rc;
 }
 
+extern "C" int zenv_xyppo_init(zenv_t *h, const zenv_xy_weights *w, const zenv_ppo_config *lo, const zenv_ppo_config *hi)
+{
+    if (!h || !w || !lo || !hi) return fail(ZENV_E_ARG, "null argument");
+    if (int rc = zenv_xyppo_check(&h->cfg, w, lo, hi)) return rc;
+    const float *tl[PPO_MAX_TENSORS], *th[PPO_MAX_TENSORS];
+    xy_tensor_lists(w, tl, th);
+    int rc = learner_create(h, h->xyppo[0], w->h_dim, tl, kXyLo, lo);
+    if (!rc) rc = learner_create(h, h->xyppo[1], w->h_dim, th, kXyHi, hi);
+    if (rc) {                   // no half-pair
+        learner_free(h->xyppo[0]);
+        learner_free(h->xyppo[1]);
+    }
+    return rc;
+}
+
 namespace {
 
-// What an entry point works on: the flat learner, or level 0 / 1 of the Zone-goals pair with the experience they read.
+enum { AGENT_FLAT = 0, AGENT_HIER = 1, AGENT_XY = 2 };
+
+// What an entry point works on: the flat learner, or level 0 / 1 of the Zone-goals or the xy-goals pair with the
+// experience they read.
 struct Learner {
     PpoState *s = nullptr;
     int level = -1;                 // -1: the flat learner
+    int agent = AGENT_FLAT;
 };
 
-int find_learner(zenv *h, int level, bool hier, Learner &out)
+int find_learner(zenv *h, int level, int agent, Learner &out)
 {
     if (!h) return fail(ZENV_E_ARG, "null handle");
+    const bool hier = agent != AGENT_FLAT;
     if (!hier) {
         if (!h->ppo) return fail(ZENV_E_STATE, "zenv_ppo_init first");
-        out = Learner{ h->ppo, -1 };
+        out = Learner{ h->ppo, -1, AGENT_FLAT };
         return ZENV_OK;
     }
     if (level != 0 && level != 1) return fail(ZENV_E_ARG, "level %d: 0 is the low level, 1 the high level", level);
+    if (agent == AGENT_XY) {
+        if (!h->xyppo[level]) return fail(ZENV_E_STATE, "zenv_xyppo_init first");
+        out = Learner{ h->xyppo[level], level, AGENT_XY };
+        return ZENV_OK;
+    }
     if (!h->hppo[level]) return fail(ZENV_E_STATE, "zenv_hppo_init first");
-    out = Learner{ h->hppo[level], level };
+    out = Learner{ h->hppo[level], level, AGENT_HIER };
     return ZENV_OK;
 }
 
@@ -349,6 +407,23 @@ int learner_exp(const zenv *h, const Learner &l, PpoExp &x, int64_t &samples)
         x = PpoExp{ e.obs, e.zone_obs, e.action, e.log_prob, e.value, e.advantage, e.returnn, h->n_env, e.T, nullptr,
                     nullptr, nullptr };
         samples = (int64_t)h->n_env * e.T;
+        return ZENV_OK;
+    }
+    if (l.agent == AGENT_XY) {
+        if (!h->exp_mem || !h->exp_xy || h->hi_kind != 3 || !h->xc_mem || h->xc.T != e.T)
+            return fail(ZENV_E_STATE, "zenv_collect_xy first: the ZENV_F_EXP_* / ZENV_F_LO_* / ZENV_F_HI_* buffers do not "
+                                      "hold its records");
+        if (l.level == 0) {     // ALL T frames of every env (_hier_policy_opt.py:147-158), the goal the frame was acted under
+            x = PpoExp{ e.obs, e.zone_obs, e.action, e.log_prob, e.value, e.advantage, e.returnn, h->n_env, e.T,
+                        reinterpret_cast<const float *>(h->xc.lo_goal), nullptr, nullptr };
+            samples = (int64_t)h->n_env * e.T;
+            return ZENV_OK;
+        }
+        // the dense env-major rows of the windows: M = N W, the goal as the action, one log_prob per row
+        const HierOut &o = h->hout;
+        x = PpoExp{ o.obs, o.zone_obs, reinterpret_cast<const float *>(h->xc.hi_goal), o.log_prob, o.value, o.advantage,
+                    o.returnn, (int)h->hi_m, 1, nullptr, nullptr, nullptr };
+        samples = h->hi_m;
         return ZENV_OK;
     }
     if (!h->exp_mem || !h->exp_hier || h->hi_kind != 0 || !h->hframes.lo_goal)
@@ -461,102 +536,150 @@ int learner_epoch(zenv *h, const Learner &l, const int32_t *order, int total, in
 }  // namespace
 
 // every entry point: find the learner, then the shared body
-#define LEARNER(h, level, hier)                                   \
+#define LEARNER(h, level, agent)                                  \
     Learner l;                                                    \
-    if (int rc = find_learner(h, level, hier, l)) return rc
+    if (int rc = find_learner(h, level, agent, l)) return rc
 
 extern "C" int zenv_ppo_tensor(zenv_t *h, int which, int index, void **dev_ptr, int64_t *count)
 {
     if (!h || !dev_ptr || !count) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, 0, false);
+    LEARNER(h, 0, AGENT_FLAT);
     return learner_tensor(l, which, index, dev_ptr, count);
 }
 extern "C" int zenv_ppo_read(zenv_t *h, int which, int index, float *dst)
 {
     if (!dst) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, 0, false);
+    LEARNER(h, 0, AGENT_FLAT);
     return learner_copy(h, l, which, index, dst, true);
 }
 extern "C" int zenv_ppo_write(zenv_t *h, int which, int index, const float *src)
 {
     if (!src) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, 0, false);
+    LEARNER(h, 0, AGENT_FLAT);
     return learner_copy(h, l, which, index, const_cast<float *>(src), false);
 }
 extern "C" int zenv_ppo_get_step(zenv_t *h, int64_t *step)
 {
     if (!h || !step) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, 0, false);
+    LEARNER(h, 0, AGENT_FLAT);
     *step = l.s->step;
     return ZENV_OK;
 }
 extern "C" int zenv_ppo_set_step(zenv_t *h, int64_t step)
 {
-    LEARNER(h, 0, false);
+    LEARNER(h, 0, AGENT_FLAT);
     return learner_set_step(l, step);
 }
 extern "C" int zenv_ppo_minibatch(zenv_t *h, const int32_t *idx, int count, int idx_on_device, int apply)
 {
     if (!h || !idx) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, 0, false);
+    LEARNER(h, 0, AGENT_FLAT);
     return learner_minibatch(h, l, idx, count, idx_on_device, apply);
 }
 extern "C" int zenv_ppo_apply(zenv_t *h)
 {
-    LEARNER(h, 0, false);
+    LEARNER(h, 0, AGENT_FLAT);
     return learner_apply(h, l);
 }
 extern "C" int zenv_ppo_epoch(zenv_t *h, const int32_t *order, int total, int batch_size, int on_device)
 {
     if (!h || !order) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, 0, false);
+    LEARNER(h, 0, AGENT_FLAT);
     return learner_epoch(h, l, order, total, batch_size, on_device);
 }
 
 extern "C" int zenv_hppo_tensor(zenv_t *h, int level, int which, int index, void **dev_ptr, int64_t *count)
 {
     if (!h || !dev_ptr || !count) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, level, true);
+    LEARNER(h, level, AGENT_HIER);
     return learner_tensor(l, which, index, dev_ptr, count);
 }
 extern "C" int zenv_hppo_read(zenv_t *h, int level, int which, int index, float *dst)
 {
     if (!dst) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, level, true);
+    LEARNER(h, level, AGENT_HIER);
     return learner_copy(h, l, which, index, dst, true);
 }
 extern "C" int zenv_hppo_write(zenv_t *h, int level, int which, int index, const float *src)
 {
     if (!src) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, level, true);
+    LEARNER(h, level, AGENT_HIER);
     return learner_copy(h, l, which, index, const_cast<float *>(src), false);
 }
 extern "C" int zenv_hppo_get_step(zenv_t *h, int level, int64_t *step)
 {
     if (!h || !step) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, level, true);
+    LEARNER(h, level, AGENT_HIER);
     *step = l.s->step;
     return ZENV_OK;
 }
 extern "C" int zenv_hppo_set_step(zenv_t *h, int level, int64_t step)
 {
-    LEARNER(h, level, true);
+    LEARNER(h, level, AGENT_HIER);
     return learner_set_step(l, step);
 }
 extern "C" int zenv_hppo_minibatch(zenv_t *h, int level, const int32_t *idx, int count, int idx_on_device, int apply)
 {
     if (!h || !idx) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, level, true);
+    LEARNER(h, level, AGENT_HIER);
     return learner_minibatch(h, l, idx, count, idx_on_device, apply);
 }
 extern "C" int zenv_hppo_apply(zenv_t *h, int level)
 {
-    LEARNER(h, level, true);
+    LEARNER(h, level, AGENT_HIER);
     return learner_apply(h, l);
 }
 extern "C" int zenv_hppo_epoch(zenv_t *h, int level, const int32_t *order, int total, int batch_size, int on_device)
 {
     if (!h || !order) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, level, true);
+    LEARNER(h, level, AGENT_HIER);
+    return learner_epoch(h, l, order, total, batch_size, on_device);
+}
+
+extern "C" int zenv_xyppo_tensor(zenv_t *h, int level, int which, int index, void **dev_ptr, int64_t *count)
+{
+    if (!h || !dev_ptr || !count) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, level, AGENT_XY);
+    return learner_tensor(l, which, index, dev_ptr, count);
+}
+extern "C" int zenv_xyppo_read(zenv_t *h, int level, int which, int index, float *dst)
+{
+    if (!dst) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, level, AGENT_XY);
+    return learner_copy(h, l, which, index, dst, true);
+}
+extern "C" int zenv_xyppo_write(zenv_t *h, int level, int which, int index, const float *src)
+{
+    if (!src) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, level, AGENT_XY);
+    return learner_copy(h, l, which, index, const_cast<float *>(src), false);
+}
+extern "C" int zenv_xyppo_get_step(zenv_t *h, int level, int64_t *step)
+{
+    if (!h || !step) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, level, AGENT_XY);
+    *step = l.s->step;
+    return ZENV_OK;
+}
+extern "C" int zenv_xyppo_set_step(zenv_t *h, int level, int64_t step)
+{
+    LEARNER(h, level, AGENT_XY);
+    return learner_set_step(l, step);
+}
+extern "C" int zenv_xyppo_minibatch(zenv_t *h, int level, const int32_t *idx, int count, int idx_on_device, int apply)
+{
+    if (!h || !idx) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, level, AGENT_XY);
+    return learner_minibatch(h, l, idx, count, idx_on_device, apply);
+}
+extern "C" int zenv_xyppo_apply(zenv_t *h, int level)
+{
+    LEARNER(h, level, AGENT_XY);
+    return learner_apply(h, l);
+}
+extern "C" int zenv_xyppo_epoch(zenv_t *h, int level, const int32_t *order, int total, int batch_size, int on_device)
+{
+    if (!h || !order) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, level, AGENT_XY);
     return learner_epoch(h, l, order, total, batch_size, on_device);
 }

@@ -22,7 +22,7 @@ from .agents import (_HIER_ENC, _HIER_CRITIC, HIER_HI_KEYS, HIER_LO_KEYS, SKILL_
                      check_collect_hier_args, check_collect_skill_args, check_collect_option_args,
                      hier_experience_layout, skill_experience_layout, option_experience_layout, skill_num_frames,
                      check_collect_xy_args, xy_experience_layout, ppo_state_dict_keys, ppo_batch_indexes,
-                     hppo_state_dict_keys, hppo_batch_indexes)
+                     hppo_state_dict_keys, hppo_batch_indexes, xyppo_state_dict_keys)
 
 _FIELD_DTYPES = {
     nat.F_OBS: np.float32, nat.F_ZONE_OBS: np.float32, nat.F_REWARD: np.float32,
@@ -46,6 +46,7 @@ _FIELD_DTYPES = {
     nat.F_XY_GOAL_AGE: np.int32, nat.F_HI_GOAL: np.float32, nat.F_LO_GOAL_DIST: np.float32,
     nat.F_XY_BOOTSTRAP_GOAL: np.float32, nat.F_PPO_STATS: np.float32,
     nat.F_HPPO_LO_STATS: np.float32, nat.F_HPPO_HI_STATS: np.float32,
+    nat.F_XYPPO_LO_STATS: np.float32, nat.F_XYPPO_HI_STATS: np.float32,
 }
 
 
@@ -55,18 +56,19 @@ def _as_host_f32(v):
 
 
 class _Learner:
-    """One device learner behind the ppo_* (level None: zenv_ppo_*) or hppo_* (zenv_hppo_* with a level) methods: the
-    arenas' tensors under their names, Adam's state, the update calls and the statistics."""
+    """One device learner behind the ppo_* (level None: zenv_ppo_*), hppo_* (zenv_hppo_* with a level) or xyppo_*
+    (prefix "zenv_xyppo_") methods: the arenas' tensors under their names, Adam's state, the update calls and the
+    statistics."""
 
-    def __init__(self, handle, level, keys, shapes, lr, adam_eps, stats_field):
+    def __init__(self, handle, level, keys, shapes, lr, adam_eps, stats_field, prefix="zenv_hppo_"):
         self._h, self.level, self.keys, self.shapes = handle, level, keys, shapes
-        self.lr, self.adam_eps, self.stats_field = lr, adam_eps, stats_field
+        self.lr, self.adam_eps, self.stats_field, self.prefix = lr, adam_eps, stats_field, prefix
 
     def _call(self, name, *args):
         if self.level is None:
             check(getattr(lib(), "zenv_ppo_" + name)(self._h, *args))
         else:
-            check(getattr(lib(), "zenv_hppo_" + name)(self._h, int(self.level), *args))
+            check(getattr(lib(), self.prefix + name)(self._h, int(self.level), *args))
 
     def tensor_ptr(self, which, index):
         p, n = C.c_void_p(), C.c_int64()
@@ -1044,6 +1046,123 @@ class ZoneVecEnv:
         rows = []
         for _ in range(int(epochs)):
             lo.epoch(hppo_batch_indexes(self.num_envs * (T - 1), rng), batch_size)
+            rows.append(lo.stats())
+        mean = np.concatenate(rows).astype(np.float64).mean(axis=0) if rows else np.zeros(6)
+        logs.update({"lo_" + n: float(mean[i]) for i, n in names})
+        return logs
+
+    # ------------------------------------------------------------------ the xy-goals agent's two PPO updates
+    # the example's hyper-parameters (examples/xy_goals_ppo_torch.py; the reference takes the norm and does not clip)
+    XYPPO_LO = dict(lr=3e-4, adam_eps=1e-8, clip_eps=0.2, entropy_coef=0.003, value_loss_coef=0.5, max_grad_norm=math.inf,
+                    max_batch=16384)
+    XYPPO_HI = dict(lr=3e-4, adam_eps=1e-8, clip_eps=0.2, entropy_coef=0.01, value_loss_coef=0.5, max_grad_norm=math.inf,
+                    max_batch=4096)
+
+    def _xy_learner(self, level):
+        """``_learner`` for the xy-goals pair."""
+        found = self._learners.get(("xy", int(level)))
+        field = nat.XYPPO_STATS_FIELDS[level] if level in (nat.XYPPO_LO, nat.XYPPO_HI) else nat.F_XYPPO_LO_STATS
+        return found or _Learner(self._h, level, {}, {}, 0.0, 0.0, field, "zenv_xyppo_")
+
+    def xyppo_init(self, hi_state_dict, lo_state_dict, lo=None, hi=None):
+        """The two learners of the xy-goals agent (xy-goals/src/torch_ac/algos/_hier_policy_opt.py:195-363) on the
+        device, from its HighPolicyValueModel / LoPolicyValueModel state_dicts with both critics: float32 master
+        parameters, gradients, Adam's moments and a workspace per level.  lo / hi: dicts of the settings to change from
+        ``XYPPO_LO`` / ``XYPPO_HI``.  `level` in the other xyppo_* methods: ``_native.XYPPO_LO`` = 0, ``XYPPO_HI`` = 1.
+        Separate from ``load_xy``: ``xyppo_publish`` hands the parameters to the acting agent."""
+        tensors = xy_tensors_from_state_dicts(hi_state_dict, lo_state_dict)
+        h = int(tensors["hi_zone_b1"].shape[0])
+        F = int(tensors["hi_zone_w1"].shape[1]) - 8
+        hi_keys, lo_keys = xyppo_state_dict_keys()
+        missing = [n for n in list(hi_keys) + list(lo_keys) if n not in tensors]
+        if missing:
+            raise ValueError(f"the update needs both critics: no {missing[0]}")
+        shapes = xy_tensor_shapes(h, F)
+        w = nat.XyWeights(h_dim=h, zone_feat=F, precision=nat.MLP_F32)
+        keep = self._load_weights(w, list(hi_keys) + list(lo_keys), tensors, shapes)      # alive across the call
+        cfgs = [nat.PpoConfig(distributional_value=0, **dict(base, **(over or {})))
+                for base, over in ((self.XYPPO_LO, lo), (self.XYPPO_HI, hi))]
+        check(lib().zenv_xyppo_init(self._h, C.byref(w), C.byref(cfgs[0]), C.byref(cfgs[1])))
+        del keep
+        for level, keys in ((nat.XYPPO_LO, lo_keys), (nat.XYPPO_HI, hi_keys)):
+            self._learners[("xy", level)] = _Learner(self._h, level, keys, shapes, cfgs[level].lr, cfgs[level].adam_eps,
+                                                     nat.XYPPO_STATS_FIELDS[level], "zenv_xyppo_")
+
+    def xyppo_tensor_ptr(self, level, which, index):
+        """``ppo_tensor_ptr`` of a level's arenas."""
+        return self._xy_learner(level).tensor_ptr(which, index)
+
+    def xyppo_tensors(self, level, which=nat.PPO_PARAM):
+        """Every tensor of a level's arena as a new host array, under its zenv_xy_weights name (hi_* / lo_*)."""
+        return self._xy_learner(level).tensors(which)
+
+    def xyppo_set_tensors(self, level, tensors, which=nat.PPO_PARAM):
+        self._xy_learner(level).set_tensors(tensors, which)
+
+    def xyppo_state_dicts(self):
+        """(hi_model_state, lo_model_state): both learners' parameters under the reference's names (host copies)."""
+        return self._xy_learner(nat.XYPPO_HI).state_dict(), self._xy_learner(nat.XYPPO_LO).state_dict()
+
+    def xyppo_load_state_dicts(self, hi_state_dict, lo_state_dict):
+        self._xy_learner(nat.XYPPO_HI).load_state_dict(hi_state_dict)
+        self._xy_learner(nat.XYPPO_LO).load_state_dict(lo_state_dict)
+
+    def xyppo_optimizer_state(self, level):
+        """A level's Adam state in the shape of ``torch.optim.Adam.state_dict()``: parameter i is the i-th of the
+        module's ``parameters()``."""
+        return self._xy_learner(level).optimizer_state()
+
+    def xyppo_load_optimizer_state(self, level, state):
+        self._xy_learner(level).load_optimizer_state(state)
+
+    def xyppo_get_step(self, level):
+        return self._xy_learner(level).get_step()
+
+    def xyppo_set_step(self, level, step):
+        self._xy_learner(level).set_step(step)
+
+    def xyppo_minibatch(self, level, idx, apply=False, count=None):
+        """``ppo_minibatch`` on the records of the last ``collect_xy``.  Low level: index i is env i // T, frame i % T
+        (lo_exps' order, every frame); high level: row i of the M = N T / skill_len windows."""
+        self._xy_learner(level).minibatch(idx, apply, count)
+
+    def xyppo_apply(self, level):
+        self._xy_learner(level).apply()
+
+    def xyppo_epoch(self, level, order, batch_size, count=None):
+        self._xy_learner(level).epoch(order, batch_size, count)
+
+    def xyppo_stats(self, level):
+        """float32 [minibatches, 6] of the level's last xyppo_minibatch / xyppo_epoch (``_native.PPO_STATS``' columns,
+        value_std = 0).  Waits for the device."""
+        return self._xy_learner(level).stats()
+
+    def xyppo_publish(self):
+        """Hand both learners' parameters to the acting agent: read them back and ``load_xy`` them with the handle's
+        current skill_len, so the next ``collect_xy`` acts with them."""
+        self.load_xy(dict(self.xyppo_tensors(nat.XYPPO_HI), **self.xyppo_tensors(nat.XYPPO_LO)),
+                     skill_len=getattr(self, "_skill_len", 200))
+
+    def xyppo_update(self, epochs, batch_size, hi_epochs, hi_batch_size, rng):
+        """update_parameters (xy-goals' _hier_policy_opt.py:195-197) on the records of the last ``collect_xy``: the high
+        level first, then the low level, each epoch in the order of ``hppo_batch_indexes`` from the caller's numpy
+        Generator.  Returns the reference's logs under lo_* / hi_*: the low level's are means over all its minibatches
+        (its lists start before the epoch loop), the high level's over the last epoch's."""
+        T = lib().zenv_field_bytes(self._h, nat.F_EXP_VALUE) // (4 * self.num_envs)
+        M = lib().zenv_field_bytes(self._h, nat.F_HI_GOAL) // 8
+        if T < 1 or M < 1:
+            raise ZenvError(nat.E_STATE, "collect_xy first: the handle holds no experience of the xy-goals agent")
+        hi, lo = self._xy_learner(nat.XYPPO_HI), self._xy_learner(nat.XYPPO_LO)
+        names = [(i, n) for i, n in enumerate(nat.PPO_STATS) if n != "value_std"]
+        logs = {"hi_" + n: 0.0 for _, n in names}
+        for _ in range(int(hi_epochs)):
+            hi.epoch(hppo_batch_indexes(M, rng), hi_batch_size)
+        if int(hi_epochs) > 0:
+            mean = hi.stats().astype(np.float64).mean(axis=0)
+            logs = {"hi_" + n: float(mean[i]) for i, n in names}
+        rows = []
+        for _ in range(int(epochs)):
+            lo.epoch(hppo_batch_indexes(self.num_envs * T, rng), batch_size)
             rows.append(lo.stats())
         mean = np.concatenate(rows).astype(np.float64).mean(axis=0) if rows else np.zeros(6)
         logs.update({"lo_" + n: float(mean[i]) for i, n in names})

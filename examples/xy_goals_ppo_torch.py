@@ -9,12 +9,16 @@ loop replaced by ``TorchZoneEnv.collect_xy``.  The modules carry the reference's
 after every update the device agent is reloaded from them.
 
     python examples/xy_goals_ppo_torch.py --env PointTSP-v0 --procs 4096 --skill-len 20 --frames-per-proc 100
+
+``--device-update`` runs the two updates in the library as well (``TorchZoneEnv.xyppo_init`` / ``xyppo_update`` /
+``xyppo_publish``: zenv_xyppo_*, csrc/ppo_update.hip); off by default, the torch path is what it was.
 """
 import argparse
 import os
 import sys
 import time
 
+import numpy as np
 import torch
 import torch.nn as nn
 from torch.distributions import Normal
@@ -94,11 +98,13 @@ def _ppo_loss(log_prob, old_log_prob, value, sb, clip_eps):
 class XyGoalsPPO:
     """One iteration of the xy-goals agent: collect_experiences on the device, then the two updates of
     _hier_policy_opt.py:195-363 in torch -- hi PPO on the windows (batches of batch_size // skill_len rows), lo PPO on
-    the frames."""
+    the frames.  With device_update both updates run in the library too (``xyppo_init`` once; then ``collect_xy``,
+    ``xyppo_update``, ``xyppo_publish`` per iteration; the modules get the learners' parameters back when ``train``
+    ends)."""
 
     def __init__(self, tenv, h=128, skill_len=20, frames_per_proc=100, epochs=4, batch_size=16384, hi_epochs=4, lr=3e-4,
                  hi_lr=3e-4, discount=0.99, gae_lambda=0.95, clip_eps=0.2, entropy_coef=0.003, hi_entropy_coef=0.01,
-                 value_loss_coef=0.5, hi_value_coef=0.5, seed=1):
+                 value_loss_coef=0.5, hi_value_coef=0.5, seed=1, device_update=False):
         self.tenv, self.L, self.T = tenv, skill_len, frames_per_proc
         dev, F_ = tenv.device, tenv.env.zone_feat
         self.hi = HighPolicyValueModel(F_, h).to(dev)
@@ -112,14 +118,26 @@ class XyGoalsPPO:
         self.hi_optimizer = torch.optim.Adam(self.hi.parameters(), hi_lr, eps=1e-8)
         self.gen = torch.Generator(device=dev).manual_seed(seed)
         self.seed, self.it = seed, 0
+        self.device_update = device_update
+        if device_update:
+            self.rng = np.random.default_rng(seed)
+            tenv.xyppo_init(self.hi.state_dict(), self.lo.state_dict(),
+                            lo=dict(lr=lr, clip_eps=clip_eps, entropy_coef=entropy_coef, value_loss_coef=value_loss_coef,
+                                    max_batch=batch_size),
+                            hi=dict(lr=hi_lr, clip_eps=clip_eps, entropy_coef=hi_entropy_coef,
+                                    value_loss_coef=hi_value_coef, max_batch=self.hi_batch_size))
+            tenv.env.configure_skills(skill_len)          # the period xyppo_publish hands on
+            tenv.xyppo_publish()
 
     def _batches(self, total, size):
         order = torch.randperm(total, device=self.tenv.device, generator=self.gen)
         return [order[i:i + size] for i in range(0, total, size)]
 
     def collect(self):
-        """Reload the device agent from the modules, collect; (lo, hi, num_frames) of TorchZoneEnv.collect_xy."""
-        self.tenv.load_xy(self.hi.state_dict(), self.lo.state_dict(), skill_len=self.L)
+        """Reload the device agent from the modules (device_update: xyppo_publish has), collect; (lo, hi, num_frames)
+        of TorchZoneEnv.collect_xy."""
+        if not self.device_update:
+            self.tenv.load_xy(self.hi.state_dict(), self.lo.state_dict(), skill_len=self.L)
         out = self.tenv.collect_xy(self.T, policy_seed=self.seed * 1000003 + self.it, discount=self.discount,
                                    gae_lambda=self.gae_lambda)
         self.it += 1
@@ -168,6 +186,10 @@ class XyGoalsPPO:
         lo, hi, num_frames = self.collect()
         logs = {"num_frames": num_frames, "reward_per_frame": float(lo["env_reward"].mean()),
                 "lo_reward_per_frame": float(lo["reward"].mean())}
+        if self.device_update:
+            logs.update(self.tenv.xyppo_update(self.epochs, self.batch_size, self.hi_epochs, self.hi_batch_size, self.rng))
+            self.tenv.xyppo_publish()
+            return logs
         logs.update(self.update(lo, hi))
         return logs
 
@@ -187,6 +209,10 @@ def train(env_id="PointTSP-v0", procs=4096, skill_len=20, frames_per_proc=100, u
         torch.cuda.synchronize()
         logs.update(update=u, seconds=round(time.perf_counter() - t0, 3))
         log({k: (round(v, 4) if isinstance(v, float) else v) for k, v in logs.items()})
+    if algo.device_update:
+        hi_sd, lo_sd = tenv.xyppo_state_dicts()
+        algo.hi.load_state_dict(hi_sd)
+        algo.lo.load_state_dict(lo_sd)
     env.close()
     return algo
 
@@ -200,5 +226,8 @@ if __name__ == "__main__":
     ap.add_argument("--updates", type=int, default=10)
     ap.add_argument("--hidden-size", type=int, default=128)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--device-update", action="store_true",
+                    help="run both PPO updates in the library (zenv_xyppo_*) instead of torch")
     a = ap.parse_args()
-    train(a.env, a.procs, a.skill_len, a.frames_per_proc, a.updates, a.hidden_size, a.seed)
+    train(a.env, a.procs, a.skill_len, a.frames_per_proc, a.updates, a.hidden_size, a.seed,
+          device_update=a.device_update)

@@ -177,7 +177,13 @@ enum {
      * of the minibatches of the level's last zenv_hppo_minibatch (one row) or zenv_hppo_epoch; 0 bytes before the first */
     ZENV_F_HPPO_LO_STATS = 75,      /* float32 [minibatches][6] the low level's: ZENV_F_PPO_STATS' columns, value std = 0 */
     ZENV_F_HPPO_HI_STATS = 76,      /* float32 [minibatches][6] the high level's, the same */
-    ZENV_F_COUNT = 77
+    /* the xy-goals agent's two learners (zenv_xyppo_init): the statistics of the minibatches of the level's last
+     * zenv_xyppo_minibatch (one row) or zenv_xyppo_epoch; 0 bytes before the first.  Before these two fields,
+     * ZENV_F_COUNT = 77
+     */
+    ZENV_F_XYPPO_LO_STATS = 77,     /* float32 [minibatches][6] the low level's: ZENV_F_PPO_STATS' columns, value std = 0 */
+    ZENV_F_XYPPO_HI_STATS = 78,     /* float32 [minibatches][6] the high level's, the same */
+    ZENV_F_COUNT = 79
 };
 
 /* scripted on-device action sources (the build's own; used by bench/tests) */
@@ -905,8 +911,8 @@ int zenv_collect_xy(zenv_t *h, int frames_per_proc, uint64_t policy_seed, uint64
  * reference's [N][T] flattening (base.py:212-227); the kernels read the time-major buffers in place.  The learner's
  * parameters are separate from the acting network's: nothing here repacks zenv_mlp_load's images (read the parameters
  * back and load them to act with them).  Every reduction runs in a fixed order: the same call from the same state
- * gives the same bits.  The Zone-goals agent's two updates are zenv_hppo_* below; the updates of the skill, Options and
- * xy-goals agents are not here. */
+ * gives the same bits.  The Zone-goals agent's two updates are zenv_hppo_* below, the xy-goals agent's two zenv_xyppo_*;
+ * the updates of the skill and Options agents are not here. */
 typedef struct zenv_ppo_config {
     double lr, adam_eps;            /* torch.optim.Adam(lr, eps = adam_eps), betas 0.9 / 0.999 */
     double clip_eps, entropy_coef, value_loss_coef, max_grad_norm;
@@ -985,6 +991,46 @@ int zenv_hppo_set_step(zenv_t *h, int level, int64_t step);
 int zenv_hppo_minibatch(zenv_t *h, int level, const int32_t *idx, int count, int idx_on_device, int apply);
 int zenv_hppo_apply(zenv_t *h, int level);
 int zenv_hppo_epoch(zenv_t *h, int level, const int32_t *order, int total, int batch_size, int on_device);
+
+/* ---- the xy-goals agent's two PPO updates on the device: update_hi_parameters / update_lo_parameters,
+ * xy-goals/src/torch_ac/algos/_hier_policy_opt.py:195-363 ----
+ * Two more learners, each with its own four arenas, Adam step count, workspace and statistics; `level` 0 is the low
+ * level (LoPolicyValueModel), 1 the high level (HighPolicyValueModel).  They read the records of the last
+ * zenv_collect_xy in place:
+ *   low:   the Zone-goals low level's network, loss and Adam on [obs, goal] (10 inputs).  Sample index i is env i / T,
+ *          frame i % T of the ZENV_F_EXP_* buffers and ZENV_F_LO_GOAL: this agent's lo_exps hold ALL T frames per env
+ *          (:147-158), frame T-1 included.
+ *   high:  the flat actor-critic's network (8 inputs, Normal over two dimensions) on row i of the ZENV_F_HI_* rows,
+ *          i in [0, M), M = N T / skill_len.  The action is the recorded goal (ZENV_F_HI_GOAL); ZENV_F_HI_LOG_PROB is
+ *          one float per row, so the ratio is exp(log_prob(goal).sum(-1) - recorded); the entropy is
+ *          entropy().sum(-1).mean(): summed over the two dimensions, then the mean over rows.  The clipped policy and
+ *          value losses are the other learners'.
+ * The reference takes the gradient norm and does not clip: max_grad_norm = +inf is accepted and gives a clip factor of
+ * exactly 1.  The arenas' order is zenv_xy_weights' member order, parameters() order of the modules: 18 tensors for the
+ * high level (hi_zone_w1 .. hi_critic_b2), 18 for the low level (lo_zone_w1 .. lo_critic_b2).  Neither touches the
+ * acting agent's weights: read the parameters back and zenv_xy_load them to act with them. */
+/* zenv_hppo_check's rules for either level, on the host alone: ZENV_E_ARG for h_dim outside 1 .. 191, a zone_feat other
+ * than zenv_zone_feat(cfg), a null tensor, a missing critic at either level, distributional_value != 0, a negative or
+ * non-finite hyper-parameter (max_grad_norm = +inf excepted), max_batch < 1, a workspace of 2^31 floats or more. */
+int zenv_xyppo_check(const zenv_config *cfg, const zenv_xy_weights *init, const zenv_ppo_config *lo,
+                     const zenv_ppo_config *hi);
+/* Both learners from one set of weights (init->precision is not used).  A second call replaces them. */
+int zenv_xyppo_init(zenv_t *h, const zenv_xy_weights *init, const zenv_ppo_config *lo, const zenv_ppo_config *hi);
+/* The flat functions with the level after the handle; their semantics are the flat functions'.  ZENV_E_ARG for a level
+ * other than 0 or 1; ZENV_E_STATE without zenv_xyppo_init.  The update calls answer ZENV_E_STATE unless the handle's
+ * ZENV_F_EXP_* / ZENV_F_LO_* / ZENV_F_HI_* buffers hold a completed zenv_collect_xy's records (no collect yet, or another
+ * collector ran last); zenv_hppo_* refuses these records in turn.  Statistics: ZENV_F_XYPPO_LO_STATS /
+ * ZENV_F_XYPPO_HI_STATS.  A host index outside [0, N T) (low) or [0, M) (high) is ZENV_E_ARG; a device-resident one is
+ * never dereferenced: the sample is dropped as zenv_ppo_minibatch drops one, it adds nothing to the loss or to any
+ * gradient, and the next call that waits for the device answers ZENV_E_ARG once. */
+int zenv_xyppo_tensor(zenv_t *h, int level, int which, int index, void **dev_ptr, int64_t *count);
+int zenv_xyppo_read(zenv_t *h, int level, int which, int index, float *dst);
+int zenv_xyppo_write(zenv_t *h, int level, int which, int index, const float *src);
+int zenv_xyppo_get_step(zenv_t *h, int level, int64_t *step);
+int zenv_xyppo_set_step(zenv_t *h, int level, int64_t step);
+int zenv_xyppo_minibatch(zenv_t *h, int level, const int32_t *idx, int count, int idx_on_device, int apply);
+int zenv_xyppo_apply(zenv_t *h, int level);
+int zenv_xyppo_epoch(zenv_t *h, int level, const int32_t *order, int total, int batch_size, int on_device);
 
 /* ---- results ---- */
 int zenv_get(zenv_t *h, int field, void *dst, int dst_on_device);
