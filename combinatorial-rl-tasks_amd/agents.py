@@ -164,6 +164,17 @@ def xyppo_state_dict_keys():
             {name: lo[name[3:]] for name in nat.XY_LO_TENSORS + nat.XY_LO_CRITIC})
 
 
+def skppo_state_dict_keys():
+    """(hi, lo): zenv_skill_weights name -> state_dict key of every tensor the fixed-length-skills agent's two learners
+    hold, in their arenas' order -- 16 tensors of HighPolicyValueModel, 18 of LoPolicyValueModel (main/src/
+    hier_policy_value_models.py:19-76), critics included.  It is also each module's ``parameters()`` order, the order
+    of torch Adam's state."""
+    hi = dict(SKILL_HI_KEYS, **_HIER_CRITIC)
+    lo = dict(SKILL_LO_KEYS, **_HIER_CRITIC)
+    return ({name: hi[name[3:]] for name in nat.SKILL_HI_TENSORS + nat.SKILL_HI_CRITIC},
+            {name: lo[name[3:]] for name in nat.SKILL_LO_TENSORS + nat.SKILL_LO_CRITIC})
+
+
 def hppo_batch_indexes(total, rng):
     """The sample order of one epoch of either level: _get_batches_starting_indexes_lo / _hi (zone-goals/src/torch_ac/
     algos/_hier_policy_opt.py:372-420) before it is cut into batches -- a plain permutation of range(total) from the

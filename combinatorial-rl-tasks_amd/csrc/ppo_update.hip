@@ -7,6 +7,11 @@
 // And the xy-goals agent's two (xy-goals/src/torch_ac/algos/_hier_policy_opt.py:195-363): its low level is the
 // Zone-goals low level on all T frames of an env, its high level the flat network on the dense rows of its windows with
 // the loss of k_xyppo_hi_loss.
+// And the fixed-length-skills agent's two (main/src/torch_ac/algos/_hier_policy_opt.py:265-419): its low level is the
+// Gaussian network on [obs, onehot(skill)] (XD = 8 + S; the one-hot is formed from the recorded skill wherever a product
+// reads it and is never stored per zone row), with actor.enc_.0.0 and critic.0 reading [emb, onehot] from an embedding
+// buffer 32 columns wider (PpoNet::LDC); its high level is the flat encoder and critic under a Categorical over the S
+// skills (PPO_HEAD_SKILLS, k_skppo_hi_loss).
 //
 // Every layer is a product on v_mfma_f32_32x32x2_f32, forward and backward, in one of two shapes:
 //
@@ -46,6 +51,8 @@ struct Gather {
     int count, N, T, Z, F;
     const float *goal;      // [slot][2]: columns 8-9 of the per-sample input when XD = 10
     int XD, W1C;
+    const int32_t *skill;   // [slot]: columns 8 .. 8 + S of the per-sample input are onehot(skill) (S > 0; else null)
+    int S;
 };
 
 // where a zone row of the minibatch lies in the experience buffers
@@ -53,16 +60,28 @@ struct RowRef {
     bool ok;
     size_t slot;     // frame * N + env
     int z;
+    int sk;          // the frame's skill (Gather::skill), checked
 };
 
-__device__ __forceinline__ bool sample_slot(const Gather &g, int b, size_t &slot)
+// sk: the frame's recorded skill where the learner has one (g.skill); one outside [0, S) drops the sample as an index
+// out of range does
+__device__ __forceinline__ bool sample_slot(const Gather &g, int b, size_t &slot, int &sk)
 {
     if (b >= g.count) return false;
     const int i = g.idx[b];
     if (i < 0 || i >= g.N * g.T) return false;       // N T < 2^31: zenv_collect refuses more
     const int env = i / g.T, t = i - env * g.T;      // exps.* flattens [N][T] (base.py:212-227)
     slot = (size_t)t * g.N + env;
+    if (g.skill) {
+        sk = g.skill[slot];
+        if (sk < 0 || sk >= g.S) return false;
+    }
     return true;
+}
+__device__ __forceinline__ bool sample_slot(const Gather &g, int b, size_t &slot)
+{
+    int sk = -1;
+    return sample_slot(g, b, slot, sk);
 }
 
 __device__ __forceinline__ RowRef row_ref(const Gather &g, int row)
@@ -71,17 +90,18 @@ __device__ __forceinline__ RowRef row_ref(const Gather &g, int row)
     const int b = row / g.Z;
     r.z = row - b * g.Z;
     r.slot = 0;
-    r.ok = sample_slot(g, b, r.slot);
+    r.sk = -1;
+    r.ok = sample_slot(g, b, r.slot, r.sk);
     return r;
 }
 
-// zone_net_.0's input [obs (8), goal (XD - 8), zone row (F), 0 ..., 1]: the last of the W1C columns (15 for XD = 8, 23
-// for XD = 10) is the constant that carries the bias
+// zone_net_.0's input [obs (8), goal or onehot(skill) (XD - 8), zone row (F), 0 ..., 1]: the last of the W1C columns (15
+// for XD = 8, 23 for XD = 10) is the constant that carries the bias
 __device__ __forceinline__ float x0_elem(const Gather &g, const RowRef &r, int k)
 {
     if (!r.ok) return 0.f;
     if (k < 8) return g.obs[r.slot * 8 + k];
-    if (k < g.XD) return g.goal[r.slot * 2 + (k - 8)];
+    if (k < g.XD) return g.skill ? (k - 8 == r.sk ? 1.f : 0.f) : g.goal[r.slot * 2 + (k - 8)];
     if (k < g.XD + g.F) return g.zone_obs[(r.slot * g.Z + r.z) * g.F + (k - g.XD)];
     return k == g.W1C - 1 ? 1.f : 0.f;
 }
@@ -114,7 +134,7 @@ __global__ __launch_bounds__(448) void k_ppo_nt(const float *__restrict__ A, int
     for (int u = 0; u < 8; ++u)
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc8[u][i] = 0.f;
-    const RowRef ref = GATHER ? row_ref(g, row) : RowRef{ false, 0, 0 };
+    const RowRef ref = GATHER ? row_ref(g, row) : RowRef{ false, 0, 0, -1 };
     const float *bp = GATHER ? nullptr : B + (size_t)row * ldb + 4 * hh;
     auto load_b = [&](int q) {
         if (GATHER) {
@@ -263,13 +283,17 @@ __global__ void k_ppo_prep(PpoNet n)
 {
     const int e = blockIdx.x * blockDim.x + threadIdx.x, which = blockIdx.y;
     const int h = n.h, HP = n.HP;
-    const int ld = which == PPO_I_W1 ? n.W1C : which == PPO_I_WC ? n.KC : (which == PPO_T_HA || which == PPO_T_HV) ? 32 : HP;
+    const int ld = which == PPO_I_W1 ? n.W1C : which == PPO_I_WC ? n.KC : (which == PPO_T_HA || which == PPO_T_HV) ? 32
+                   : (which == PPO_I_WE || which == PPO_I_WV) ? n.LDC : HP;
     const int n_rows = (which == PPO_I_HA || which == PPO_I_HV) ? 32 : HP;
     if (e >= n_rows * ld) return;
     const int r = e / ld, c = e - r * ld;
     auto T = [&](int t) { return n.param + n.off[t]; };
     const int XD = n.XD, kb = n.W1C - 1;
-    const bool zones = n.head == PPO_HEAD_ZONES;
+    const bool zones = n.head == PPO_HEAD_ZONES, skills = n.head == PPO_HEAD_SKILLS;
+    // the skills agent's low level: actor.enc_.0.0 and critic.0 are [h][h + S] over [emb, onehot]; the onehot's columns
+    // lie at HP .. HP + S of their images
+    const int tail = n.LDC > HP ? n.S : 0;
     // the critic's four tensors
     const float *cw1 = T(n.cr), *cb1 = T(n.cr + 1), *cw2 = T(n.cr + 2), *cb2 = T(n.cr + 3);
     float v = 0.f;
@@ -289,11 +313,19 @@ __global__ void k_ppo_prep(PpoNet n)
         }
         break;
     // PPO_HEAD_ZONES: actor.0.weight = [W_e | W_z], [h][h + F]; this is W_e with actor.0's bias
-    case PPO_I_WE: v = img_square(T(PPO_ENC_W), T(PPO_ENC_B), h, r, c, true, zones ? h + n.F : h); break;
-    case PPO_I_WV: v = img_square(cw1, cb1, h, r, c, true); break;
+    case PPO_I_WE:
+        if (c >= HP) v = r < h && c - HP < tail ? T(PPO_ENC_W)[(size_t)r * (h + tail) + h + (c - HP)] : 0.f;
+        else v = img_square(T(PPO_ENC_W), T(PPO_ENC_B), h, r, c, true, zones ? h + n.F : h + tail);
+        break;
+    case PPO_I_WV:
+        if (c >= HP) v = r < h && c - HP < tail ? cw1[(size_t)r * (h + tail) + h + (c - HP)] : 0.f;
+        else v = img_square(cw1, cb1, h, r, c, true, h + tail);
+        break;
     case PPO_I_HA:
         if (zones) {                                  // row 0: actor.2
             if (r == 0 && c <= h) v = c < h ? T(PPO_ACTOR_W2)[c] : T(PPO_ACTOR_B2)[0];
+        } else if (skills) {                          // rows 0 .. S: actor.discrete_.0
+            if (r < n.S && c <= h) v = c < h ? T(PPO_ACTOR_W2)[(size_t)r * h + c] : T(PPO_ACTOR_B2)[r];
         } else if (r < 4 && c <= h) {
             const float *w = T(r < 2 ? PPO_MU_W : PPO_STD_W), *b = T(r < 2 ? PPO_MU_B : PPO_STD_B);
             v = c < h ? w[(size_t)(r & 1) * h + c] : b[r & 1];
@@ -308,11 +340,13 @@ __global__ void k_ppo_prep(PpoNet n)
     case PPO_T_W2: v = img_transposed(T(PPO_ZONE_W2), h, 0, h, r, c); break;
     case PPO_T_W3: v = img_transposed(T(PPO_ZONE_W3), h, 0, h, r, c); break;
     case PPO_T_WC: v = img_transposed(T(PPO_COMB_W), XD + h, XD, h, r, c); break;
-    case PPO_T_WE: v = img_transposed(T(PPO_ENC_W), zones ? h + n.F : h, 0, h, r, c); break;
-    case PPO_T_WV: v = img_transposed(cw1, h, 0, h, r, c); break;
+    case PPO_T_WE: v = img_transposed(T(PPO_ENC_W), zones ? h + n.F : h + tail, 0, h, r, c); break;
+    case PPO_T_WV: v = img_transposed(cw1, h + tail, 0, h, r, c); break;
     case PPO_T_HA:
         if (zones) {
             if (r < h && c == 0) v = T(PPO_ACTOR_W2)[r];
+        } else if (skills) {
+            if (r < h && c < n.S) v = T(PPO_ACTOR_W2)[(size_t)c * h + r];
         } else if (r < h && c < 4) v = T(c < 2 ? PPO_MU_W : PPO_STD_W)[(size_t)(c & 1) * h + r];
         break;
     case PPO_T_HV:
@@ -332,11 +366,15 @@ __global__ void k_ppo_pool(PpoNet n, Gather g, int bp)
     if (e >= bp * n.KC) return;
     const int b = e / n.KC, f = e - b * n.KC;
     size_t slot = 0;
-    const bool ok = sample_slot(g, b, slot);
+    int sk = -1;
+    const bool ok = sample_slot(g, b, slot, sk);
     if (f == 0 && b < g.count && !ok) *n.bad_index = 1;
     if (f >= n.HP) {
         const int k = f - n.HP;
-        n.CI[(size_t)b * n.KC + f] = !ok ? 0.f : k < 8 ? g.obs[slot * 8 + k] : k < g.XD ? g.goal[slot * 2 + (k - 8)] : 0.f;
+        float v = 0.f;
+        if (ok && k < 8) v = g.obs[slot * 8 + k];
+        else if (ok && k < g.XD) v = g.skill ? (k - 8 == sk ? 1.f : 0.f) : g.goal[slot * 2 + (k - 8)];
+        n.CI[(size_t)b * n.KC + f] = v;
         return;
     }
     float v = 0.f;
@@ -515,6 +553,14 @@ __global__ void k_xyppo_hi_loss(PpoNet n, PpoExp x, Gather g, int bp)
     for (int i = 0; i < 8; ++i) n.SS[(size_t)b * 8 + i] = ss[i];
 }
 
+// d loss / d logit of one category of a Categorical(logits) whose log-probability is lp (p = exp(lp)) and entropy H:
+// g_lp (1[this is the recorded one] - p) from the policy loss, ec p (lp + H) from the entropy's term -ec H.  In double.
+__device__ __forceinline__ double categorical_dlogit(float g_lp, double ec, double lp, double H, bool recorded)
+{
+    const double p = exp(lp);
+    return (double)g_lp * ((recorded ? 1.0 : 0.0) - p) + ec * p * (lp + H);
+}
+
 // ---- PPO_HEAD_ZONES: the Zone-goals high level's actor (zone-goals/src/hier_policy_value_models.py:19-56), one logit
 // per zone from actor.2(relu(actor.0([emb, zone row]))).  With actor.0.weight = [W_e | W_z] the emb part E = W_e emb + b
 // is taken once per sample (k_ppo_nt, into Ha; its column h is the constant 1) and
@@ -599,8 +645,7 @@ __global__ void k_hppo_loss(PpoNet n, PpoExp x, Gather g, int bp, int rows)
         if (row >= (size_t)rows) break;
         double dz = 0.0;
         if (ok && mk[z]) {
-            const double lp = (double)lg[(size_t)z * 32] - lse, p = exp(lp);
-            dz = (double)g_lp * ((z == a ? 1.0 : 0.0) - p) + ec * p * (lp + H);
+            dz = categorical_dlogit(g_lp, ec, (double)lg[(size_t)z * 32] - lse, H, z == a);
         }
         n.DZ[row] = dz;
         float4 *dl = reinterpret_cast<float4 *>(n.DL + row * 32);
@@ -637,6 +682,148 @@ __global__ void k_hppo_sum(PpoNet n, int Z, int bp, int rows)
     n.Ha[(size_t)b * n.HP + f] = (float)s;
 }
 
+// ---- PPO_HEAD_SKILLS: the fixed-length-skills agent's high level (main/src/hier_policy_value_models.py:19-43):
+// logits = actor.discrete_.0(relu(actor.enc_.0.0(emb))), Categorical(logits = log_softmax(logits)), unmasked.
+// The loss of one row (_hier_policy_opt.py:345-419) and its derivatives with respect to the S logits (L, DL: [samples]
+// [32], columns 0 .. S) and the value (PRE / DH, column 4): k_hppo_loss' with every skill available and the logits of
+// a row side by side.  The log-softmax, the entropy and the derivatives are formed in double and rounded once.  With
+// S = 1 the one probability is exactly 1 and every derivative exactly 0, as float64 autograd gives it.  A recorded
+// skill outside [0, S) drops the row like an index out of range.  One thread per row.
+__global__ void k_skppo_hi_loss(PpoNet n, PpoExp x, Gather g, int bp)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= bp) return;
+    const int S = n.S;
+    float d_value = 0.f, ss[8] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
+    float g_lp = 0.f;
+    double lse = 0.0, H = 0.0, ec = 0.0;
+    size_t slot = 0;
+    bool ok = sample_slot(g, b, slot);
+    int a = -1;
+    const float *lg = n.L + (size_t)b * 32;
+    if (ok) {
+        a = x.hi_action[slot];
+        if (a < 0 || a >= S) {
+            ok = false;
+            *n.bad_index = 1;
+        }
+    }
+    if (ok) {
+        const PpoHyper &hy = n.hyper;
+        const float inv_b = 1.0f / (float)g.count;
+        double m = (double)lg[a];
+        for (int s = 0; s < S; ++s) m = fmax(m, (double)lg[s]);
+        double sum = 0.0;
+        for (int s = 0; s < S; ++s) sum += exp((double)lg[s] - m);
+        lse = m + log(sum);
+        for (int s = 0; s < S; ++s) {
+            const double lp = (double)lg[s] - lse;
+            H -= exp(lp) * lp;
+        }
+        const float lp_a = (float)((double)lg[a] - lse);
+        const float ploss = clipped_policy(lp_a - x.log_prob[slot], x.advantage[slot], hy.clip_eps, inv_b, g_lp);
+        const float v = n.PRE[(size_t)b * 32 + 4];
+        const float vloss = clipped_value(v, x.value[slot], x.returnn[slot], hy, inv_b, d_value);
+        ec = (double)hy.entropy_coef * (double)inv_b;
+        ss[0] = (float)H;
+        ss[1] = v;
+        ss[3] = ploss;
+        ss[4] = vloss;
+    }
+    float *dl = n.DL + (size_t)b * 32, *dh = n.DH + (size_t)b * 32;
+    for (int s = 0; s < 32; ++s)
+        dl[s] = ok && s < S ? (float)categorical_dlogit(g_lp, ec, (double)lg[s] - lse, H, s == a) : 0.f;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) dh[i] = i == 4 ? d_value : 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) n.SS[(size_t)b * 8 + i] = ss[i];
+}
+
+// The loss of one sample of the skills agent's low level: k_ppo_loss' loss with the plain critic -- a recorded log_prob
+// per action component, the entropy's mean over count x 2 -- formed in double from the float32 pre-activations and
+// rounded once, as the high level's is.  In float32 the head's own arithmetic (sigmoid, log_prob, ratio and the products
+// of the derivative) is the largest part of the error of the gradients of actor.mu_.bias and actor.std_.bias, two sums
+// over the minibatch that cancel to a tenth of their terms: 1e-8 .. 7e-8 at 96 samples, where float32 torch has
+// 5e-9 .. 8e-8 and the rounding of the pre-activations adds 1e-9 (DESIGN K15).  The five deltas also go to DZ [samples]
+// [5] before they are rounded: k_skppo_head_bias adds them up for the three head biases.  The flat learner's k_ppo_loss
+// stays as it is, and with it the bits of every other learner.
+__device__ __forceinline__ double sigmoidd(double x) { return 1.0 / (1.0 + exp(-x)); }
+
+__global__ void k_skppo_lo_loss(PpoNet n, PpoExp x, Gather g, int bp)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= bp) return;
+    float d[6] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f }, ss[8] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
+    double dd[5] = { 0.0, 0.0, 0.0, 0.0, 0.0 };
+    size_t slot = 0;
+    if (sample_slot(g, b, slot)) {
+        const float *pre = n.PRE + (size_t)b * 32;
+        const PpoHyper &hy = n.hyper;
+        const double inv_b = 1.0 / (double)g.count, eps = (double)hy.clip_eps;
+        const double adv = (double)x.advantage[slot], ret = (double)x.returnn[slot];
+        const double half_log_2pi = 0.9189385332046727;
+        double sd[2], smu[2], ssd[2], diff[2], dlp = 0.0, ent = 0.0;
+#pragma unroll
+        for (int o = 0; o < 2; ++o) {
+            smu[o] = sigmoidd((double)pre[o]);
+            ssd[o] = sigmoidd((double)pre[2 + o]);
+            const double mu = 2.0 * (smu[o] - 0.5);               // policy_network.py:46-47
+            sd[o] = ssd[o] + 1e-3;
+            diff[o] = (double)x.action[slot * 2 + o] - mu;
+            const double lp = -(diff[o] * diff[o]) / (2.0 * (sd[o] * sd[o])) - log(sd[o]) - half_log_2pi;
+            dlp += lp - (double)x.log_prob[slot * 2 + o];
+            ent += 0.5 + half_log_2pi + log(sd[o]);                // Normal.entropy
+        }
+        // clipped_policy and clipped_value in double: comparisons, so that a NaN ratio or value gives a NaN loss
+        const double ratio = exp(dlp), lo = 1.0 - eps, hi = 1.0 + eps;
+        const double surr1 = ratio * adv, surr2 = (ratio < lo ? lo : ratio > hi ? hi : ratio) * adv;
+        const double through = surr1 <= surr2 ? 1.0 : (ratio >= lo && ratio <= hi) ? 1.0 : 0.0;
+        const double g_lp = -adv * inv_b * through * ratio;
+#pragma unroll
+        for (int o = 0; o < 2; ++o) {
+            const double var = sd[o] * sd[o];
+            const double g_mu = g_lp * (diff[o] / var);
+            const double g_sd = g_lp * ((diff[o] * diff[o]) / (var * sd[o]) - 1.0 / sd[o])
+                                - (double)hy.entropy_coef * (0.5 * inv_b) / sd[o];  // the entropy's mean is over B x 2
+            dd[o] = g_mu * 2.0 * smu[o] * (1.0 - smu[o]);
+            dd[2 + o] = g_sd * ssd[o] * (1.0 - ssd[o]);
+        }
+        const double v = (double)pre[4], old = (double)x.value[slot], dv = v - old;
+        const double vc = old + (dv < -eps ? -eps : dv > eps ? eps : dv);
+        const double s1 = (v - ret) * (v - ret), s2 = (vc - ret) * (vc - ret);
+        const bool inside = dv >= -eps && dv <= eps;
+        const double dl = s1 >= s2 ? 2.0 * (v - ret) : inside ? 2.0 * (vc - ret) : 0.0;
+        dd[4] = (double)hy.value_loss_coef * inv_b * dl;
+#pragma unroll
+        for (int i = 0; i < 5; ++i) d[i] = (float)dd[i];
+        ss[0] = (float)ent;
+        ss[1] = pre[4];
+        ss[3] = (float)(-(surr1 <= surr2 ? surr1 : surr2));
+        ss[4] = (float)(s1 >= s2 ? s1 : s2);
+    }
+#pragma unroll
+    for (int i = 0; i < 5; ++i) n.DZ[(size_t)b * 5 + i] = dd[i];
+    float *dh = n.DH + (size_t)b * 32;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) dh[i] = i < 6 ? d[i] : 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) n.SS[(size_t)b * 8 + i] = ss[i];
+}
+
+// The skills agent's low level: onehot(skill) of every sample into columns HP .. HP + 32 of C, beside the embedding that
+// combine_net_ writes into columns 0 .. HP: the input [emb, onehot] of actor.enc_.0.0 and critic.0.  Rows of a dropped
+// sample and rows past the minibatch are zero.  Thread (b, k), k < 32.
+__global__ void k_skppo_onehot(PpoNet n, Gather g, int bp)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= bp * 32) return;
+    const int b = e >> 5, k = e & 31;
+    size_t slot = 0;
+    int sk = -1;
+    const bool ok = sample_slot(g, b, slot, sk);
+    n.C[(size_t)b * n.LDC + n.HP + k] = ok && k == sk ? 1.f : 0.f;
+}
+
 // a block's fixed-order sum: every thread's double, then a tree over LDS
 __device__ __forceinline__ double block_sum_256(double v, double *sh)
 {
@@ -649,6 +836,24 @@ __device__ __forceinline__ double block_sum_256(double v, double *sh)
     const double out = sh[0];
     __syncthreads();
     return out;
+}
+
+// The skills agent's low level: the gradients of actor.mu_.bias, actor.std_.bias and critic.2.bias are the sums of the
+// head's deltas over the minibatch.  As column h of a float32 product the sum of deltas that are each of order 1 where the
+// policy's std is small, and cancel, carried 1e-7 of rounding into gradients of 0.1; so the sums run over the unrounded
+// deltas (DZ, k_skppo_lo_loss), in double, in a fixed order, and are rounded once.  Block c of 256 threads: delta c.
+__global__ __launch_bounds__(256) void k_skppo_head_bias(PpoNet n, int bp)
+{
+    __shared__ double sh[256];
+    const int c = blockIdx.x;
+    double s = 0.0;
+    for (int b = threadIdx.x; b < bp; b += 256) s += n.DZ[(size_t)b * 5 + c];
+    s = block_sum_256(s, sh);
+    if (threadIdx.x == 0) {
+        float *dst = c < 2 ? n.grad + n.off[PPO_MU_B] + c : c < 4 ? n.grad + n.off[PPO_STD_B] + (c - 2)
+                                                                  : n.grad + n.off[n.cr + 3];
+        *dst = (float)s;
+    }
 }
 
 // stats[0..4] = the minibatch means of the per-sample terms; one block of 256 threads, thread i adds samples i, i + 256 ...
@@ -712,7 +917,7 @@ __global__ void k_ppo_adam(PpoNet n, float step_size, float bc2_sqrt)
     n.exp_avg_sq[e] = v;
 }
 
-Gather no_gather() { return Gather{ nullptr, nullptr, nullptr, 0, 1, 1, 1, 0, nullptr, 8, 16 }; }
+Gather no_gather() { return Gather{ nullptr, nullptr, nullptr, 0, 1, 1, 1, 0, nullptr, 8, 16, nullptr, 0 }; }
 
 template <int MODE>
 void nt(const float *A, int lda, const float *B, int ldb, int K, float *D, int ldd, int rows, int m_tiles,
@@ -755,33 +960,71 @@ void launch_norm(const PpoNet &n, float *stat, hipStream_t s)
 // the two heads between the encoder's forward and backward passes: C holds the embedding going in, its delta coming out
 void gaussian_head(const PpoNet &n, const PpoExp &x, const Gather &g, int bp, float *stats, hipStream_t s)
 {
-    const int h = n.h, HP = n.HP, NT = HP / 32, cr = n.cr;
+    const int h = n.h, HP = n.HP, NT = HP / 32, cr = n.cr, LDC = n.LDC;
+    // the skills agent's low level: C is [emb | onehot(skill)] and actor.enc_.0.0 / critic.0 are [h][h + S]
+    const int tail = LDC > HP ? n.S : 0, ldw = h + tail;
     float *const *I = n.img;
-    nt<NT_RELU>(I[PPO_I_WE], HP, n.C, HP, HP, n.Ha, HP, bp, NT, s);                       // relu(actor.enc_)
-    nt<NT_RELU>(I[PPO_I_WV], HP, n.C, HP, HP, n.Hc, HP, bp, NT, s);                       // relu(critic.0)
+    if (tail) hipLaunchKernelGGL(k_skppo_onehot, dim3((bp * 32 + 255) / 256), dim3(256), 0, s, n, g, bp);
+    nt<NT_RELU>(I[PPO_I_WE], LDC, n.C, LDC, LDC, n.Ha, HP, bp, NT, s);                    // relu(actor.enc_)
+    nt<NT_RELU>(I[PPO_I_WV], LDC, n.C, LDC, LDC, n.Hc, HP, bp, NT, s);                    // relu(critic.0)
     nt<NT_STORE>(I[PPO_I_HA], HP, n.Ha, HP, HP, n.PRE, 32, bp, 1, s);                     // mu_, std_
     nt<NT_ADD>(I[PPO_I_HV], HP, n.Hc, HP, HP, n.PRE, 32, bp, 1, s);                       // critic.2 / critic_mu, critic_sigma
     if (n.loss == PPO_LOSS_JOINT_GOAL) {                      // the entropy's mean is over the rows alone
         hipLaunchKernelGGL(k_xyppo_hi_loss, dim3((bp + 63) / 64), dim3(64), 0, s, n, x, g, bp);
         hipLaunchKernelGGL(k_ppo_stats, dim3(1), dim3(256), 0, s, n.SS, g.count, 1.0, stats, (float *)nullptr);
     } else {
-        hipLaunchKernelGGL(k_ppo_loss, dim3((bp + 63) / 64), dim3(64), 0, s, n, x, g, bp);
+        if (tail) hipLaunchKernelGGL(k_skppo_lo_loss, dim3((bp + 63) / 64), dim3(64), 0, s, n, x, g, bp);
+        else hipLaunchKernelGGL(k_ppo_loss, dim3((bp + 63) / 64), dim3(64), 0, s, n, x, g, bp);
         hipLaunchKernelGGL(k_ppo_stats, dim3(1), dim3(256), 0, s, n.SS, g.count, 2.0, stats, (float *)nullptr);
     }
     // ---- backward: every weight gradient is taken before its layer's activations are overwritten by deltas
     tn(n.DH, 32, 1, n.Ha, HP, HP, bp, n.partial, s);
     reduce(n, bp, 1, HP, 0, 0, PPO_MU_W, h, 0, 2, h, s);
-    reduce(n, bp, 1, HP, 0, h, PPO_MU_B, 1, 0, 2, 1, s);
+    if (!tail) reduce(n, bp, 1, HP, 0, h, PPO_MU_B, 1, 0, 2, 1, s);
     reduce(n, bp, 1, HP, 2, 0, PPO_STD_W, h, 0, 2, h, s);
-    reduce(n, bp, 1, HP, 2, h, PPO_STD_B, 1, 0, 2, 1, s);
+    if (!tail) reduce(n, bp, 1, HP, 2, h, PPO_STD_B, 1, 0, 2, 1, s);
     tn(n.DH, 32, 1, n.Hc, HP, HP, bp, n.partial, s);
     reduce(n, bp, 1, HP, 4, 0, cr + 2, h, 0, 1, h, s);
-    reduce(n, bp, 1, HP, 4, h, cr + 3, 1, 0, 1, 1, s);
+    if (!tail) reduce(n, bp, 1, HP, 4, h, cr + 3, 1, 0, 1, 1, s);
+    else hipLaunchKernelGGL(k_skppo_head_bias, dim3(5), dim3(256), 0, s, n, bp);          // the three head biases
     if (n.dist) {
         reduce(n, bp, 1, HP, 5, 0, PPO_SIGMA_W, h, 0, 1, h, s);
         reduce(n, bp, 1, HP, 5, h, PPO_SIGMA_B, 1, 0, 1, 1, s);
     }
     nt<NT_MASK>(I[PPO_T_HA], 32, n.DH, 32, 32, n.Ha, HP, bp, NT, s);                      // delta of actor.enc_
+    nt<NT_MASK>(I[PPO_T_HV], 32, n.DH, 32, 32, n.Hc, HP, bp, NT, s);                      // delta of critic.0
+    tn(n.Ha, HP, NT, n.C, LDC, LDC, bp, n.partial, s);
+    reduce(n, bp, NT, LDC, 0, 0, PPO_ENC_W, ldw, 0, h, h, s);
+    if (tail) reduce(n, bp, NT, LDC, 0, HP, PPO_ENC_W, ldw, h, h, tail, s);               // the onehot's columns
+    reduce(n, bp, NT, LDC, 0, h, PPO_ENC_B, 1, 0, h, 1, s);
+    tn(n.Hc, HP, NT, n.C, LDC, LDC, bp, n.partial, s);
+    reduce(n, bp, NT, LDC, 0, 0, cr, ldw, 0, h, h, s);
+    if (tail) reduce(n, bp, NT, LDC, 0, HP, cr, ldw, h, h, tail, s);
+    reduce(n, bp, NT, LDC, 0, h, cr + 1, 1, 0, h, 1, s);
+    // the onehot has no delta: the embedding's comes from the first h columns of both weights
+    nt<NT_STORE>(I[PPO_T_WE], HP, n.Ha, HP, HP, n.C, LDC, bp, NT, s);                     // delta of the embedding ...
+    nt<NT_ADD>(I[PPO_T_WV], HP, n.Hc, HP, HP, n.C, LDC, bp, NT, s);                       // ... from both heads
+}
+
+// PPO_HEAD_SKILLS: gaussian_head with the S logits of actor.discrete_.0 in L / DL where it has mu_ and std_ in PRE / DH
+void skill_head(const PpoNet &n, const PpoExp &x, const Gather &g, int bp, float *stats, hipStream_t s)
+{
+    const int h = n.h, HP = n.HP, NT = HP / 32, cr = n.cr, S = n.S;
+    float *const *I = n.img;
+    nt<NT_RELU>(I[PPO_I_WE], HP, n.C, HP, HP, n.Ha, HP, bp, NT, s);                       // relu(actor.enc_)
+    nt<NT_RELU>(I[PPO_I_WV], HP, n.C, HP, HP, n.Hc, HP, bp, NT, s);                       // relu(critic.0)
+    nt<NT_STORE>(I[PPO_I_HA], HP, n.Ha, HP, HP, n.L, 32, bp, 1, s);                       // actor.discrete_.0: S logits
+    nt<NT_STORE>(I[PPO_I_HV], HP, n.Hc, HP, HP, n.PRE, 32, bp, 1, s);                     // critic.2
+    hipLaunchKernelGGL(k_skppo_hi_loss, dim3((bp + 63) / 64), dim3(64), 0, s, n, x, g, bp);
+    hipLaunchKernelGGL(k_ppo_stats, dim3(1), dim3(256), 0, s, n.SS, g.count, 1.0, stats, (float *)nullptr);
+    // ---- backward
+    tn(n.DL, 32, 1, n.Ha, HP, HP, bp, n.partial, s);
+    reduce(n, bp, 1, HP, 0, 0, PPO_ACTOR_W2, h, 0, S, h, s);
+    reduce(n, bp, 1, HP, 0, h, PPO_ACTOR_B2, 1, 0, S, 1, s);
+    tn(n.DH, 32, 1, n.Hc, HP, HP, bp, n.partial, s);
+    reduce(n, bp, 1, HP, 4, 0, cr + 2, h, 0, 1, h, s);
+    reduce(n, bp, 1, HP, 4, h, cr + 3, 1, 0, 1, 1, s);
+    nt<NT_MASK>(I[PPO_T_HA], 32, n.DL, 32, 32, n.Ha, HP, bp, NT, s);                      // delta of actor.enc_
     nt<NT_MASK>(I[PPO_T_HV], 32, n.DH, 32, 32, n.Hc, HP, bp, NT, s);                      // delta of critic.0
     tn(n.Ha, HP, NT, n.C, HP, HP, bp, n.partial, s);
     reduce(n, bp, NT, HP, 0, 0, PPO_ENC_W, h, 0, h, h, s);
@@ -790,7 +1033,7 @@ void gaussian_head(const PpoNet &n, const PpoExp &x, const Gather &g, int bp, fl
     reduce(n, bp, NT, HP, 0, 0, cr, h, 0, h, h, s);
     reduce(n, bp, NT, HP, 0, h, cr + 1, 1, 0, h, 1, s);
     nt<NT_STORE>(I[PPO_T_WE], HP, n.Ha, HP, HP, n.C, HP, bp, NT, s);                      // delta of the embedding ...
-    nt<NT_ADD>(I[PPO_T_WV], HP, n.Hc, HP, HP, n.C, HP, bp, NT, s);                        // ... from both heads
+    nt<NT_ADD>(I[PPO_T_WV], HP, n.Hc, HP, HP, n.C, HP, bp, NT, s);                        // ... from actor and critic
 }
 
 void zone_head(const PpoNet &n, const PpoExp &x, const Gather &g, int rp, int bp, float *stats, hipStream_t s)
@@ -816,7 +1059,8 @@ void zone_head(const PpoNet &n, const PpoExp &x, const Gather &g, int rp, int bp
     nt<NT_MASK>(I[PPO_T_HA], 32, n.DL, 32, 32, n.U, HP, rp, NT, s);                       // dU, the delta of actor.0
     nt<NT_MASK>(I[PPO_T_HV], 32, n.DH, 32, 32, n.Hc, HP, bp, NT, s);                      // delta of critic.0
     // d W_z = sum over the zone rows of dU x the row's zone features: columns XD .. XD + F of the gathered input
-    hipLaunchKernelGGL((k_ppo_tn<true>), dim3(chunks, NT), dim3(64, 1), 0, s, n.U, HP, nullptr, 0, n.W1C, rp, n.partial, g);
+    hipLaunchKernelGGL((k_ppo_tn<true>), dim3(chunks, NT), dim3(64, (n.W1C + 31) / 32), 0, s, n.U, HP, nullptr, 0, n.W1C, rp,
+                       n.partial, g);
     reduce(n, rp, NT, n.W1C, 0, n.XD, PPO_ACTOR_W1, h + F, h, h, F, s);
     tn(n.Ha, HP, NT, n.C, HP, HP, bp, n.partial, s);                                      // d W_e and actor.0's bias
     reduce(n, bp, NT, HP, 0, 0, PPO_ACTOR_W1, h + F, 0, h, h, s);
@@ -833,26 +1077,39 @@ void zone_head(const PpoNet &n, const PpoExp &x, const Gather &g, int rp, int bp
 hipError_t launch_ppo_minibatch(const PpoNet &n, const PpoExp &x, const int32_t *idx, int count, float *stats,
                                 hipStream_t s)
 {
-    const int h = n.h, HP = n.HP, KC = n.KC, NT = HP / 32, XD = n.XD, W1C = n.W1C;
+    const int h = n.h, HP = n.HP, KC = n.KC, NT = HP / 32, XD = n.XD, W1C = n.W1C, LDC = n.LDC;
     const int rp = (count * n.Z + 31) / 32 * 32, bp = (count + 31) / 32 * 32;
-    const Gather g{ x.obs, x.zone_obs, idx, count, x.N, x.T, n.Z, n.F, x.goal, XD, W1C };
+    const Gather g{ x.obs, x.zone_obs, idx, count, x.N, x.T, n.Z, n.F, x.goal, XD, W1C, x.skill, x.skill ? n.S : 0 };
     float *const *I = n.img;
-    hipLaunchKernelGGL(k_ppo_prep, dim3((HP * KC + 255) / 256, PPO_N_IMAGES), dim3(256), 0, s, n);
+    // the widest image: combine_net_'s [HP][KC], or actor.enc_.0.0's [HP][LDC] (zone_net_.0's W1C <= 48 <= KC)
+    const int wide = KC > LDC ? KC : LDC;
+    hipLaunchKernelGGL(k_ppo_prep, dim3((HP * wide + 255) / 256, PPO_N_IMAGES), dim3(256), 0, s, n);
     // ---- forward
     hipLaunchKernelGGL((k_ppo_nt<NT_RELU, true>), dim3(rp / 32), dim3(64, NT), 0, s, I[PPO_I_W1], W1C, nullptr, 0, W1C,
                        n.A1, HP, g);                                                      // relu(zone_net_.0)
     nt<NT_RELU>(I[PPO_I_W2], HP, n.A1, HP, HP, n.A2, HP, rp, NT, s);                      // relu(zone_net_.2)
     hipLaunchKernelGGL(k_ppo_pool, dim3((bp * KC + 255) / 256), dim3(256), 0, s, n, g, bp);
     nt<NT_STORE>(I[PPO_I_W3], HP, n.P, HP, HP, n.CI, KC, bp, NT, s);                      // zone_net_.4 of the mean
-    nt<NT_STORE>(I[PPO_I_WC], KC, n.CI, KC, KC, n.C, HP, bp, NT, s);                      // combine_net_
+    nt<NT_STORE>(I[PPO_I_WC], KC, n.CI, KC, KC, n.C, LDC, bp, NT, s);                     // combine_net_
     if (n.head == PPO_HEAD_ZONES) zone_head(n, x, g, rp, bp, stats, s);
+    else if (n.head == PPO_HEAD_SKILLS) skill_head(n, x, g, bp, stats, s);
     else gaussian_head(n, x, g, bp, stats, s);
     // ---- the encoder's backward pass, from the embedding's delta in C
-    tn(n.C, HP, NT, n.CI, KC, KC, bp, n.partial, s);
-    reduce(n, bp, NT, KC, 0, 0, PPO_COMB_W, XD + h, XD, h, h, s);
-    reduce(n, bp, NT, KC, 0, HP, PPO_COMB_W, XD + h, 0, h, XD, s);
-    reduce(n, bp, NT, KC, 0, h, PPO_COMB_B, 1, 0, h, 1, s);
-    nt<NT_STORE>(I[PPO_T_WC], HP, n.C, HP, HP, n.CI, KC, bp, NT, s);                      // delta of zone_net_.4's output
+    if ((KC + 31) / 32 <= 7) {
+        tn(n.C, LDC, NT, n.CI, KC, KC, bp, n.partial, s);
+        reduce(n, bp, NT, KC, 0, 0, PPO_COMB_W, XD + h, XD, h, h, s);
+        reduce(n, bp, NT, KC, 0, HP, PPO_COMB_W, XD + h, 0, h, XD, s);
+        reduce(n, bp, NT, KC, 0, h, PPO_COMB_B, 1, 0, h, 1, s);
+    } else {
+        // HP = 192 with more than 32 own columns: eight k tiles would be 512 threads where k_ppo_tn is built for 448.
+        // The product is taken in two by columns, zone_emb's HP and the own ones; an element's sum is what it would be.
+        tn(n.C, LDC, NT, n.CI, KC, HP, bp, n.partial, s);
+        reduce(n, bp, NT, HP, 0, 0, PPO_COMB_W, XD + h, XD, h, h, s);
+        reduce(n, bp, NT, HP, 0, h, PPO_COMB_B, 1, 0, h, 1, s);
+        tn(n.C, LDC, NT, n.CI + HP, KC, KC - HP, bp, n.partial, s);
+        reduce(n, bp, NT, KC - HP, 0, 0, PPO_COMB_W, XD + h, 0, h, XD, s);
+    }
+    nt<NT_STORE>(I[PPO_T_WC], HP, n.C, LDC, HP, n.CI, KC, bp, NT, s);                     // delta of zone_net_.4's output
     tn(n.CI, KC, NT, n.P, HP, HP, bp, n.partial, s);
     reduce(n, bp, NT, HP, 0, 0, PPO_ZONE_W3, h, 0, h, h, s);
     reduce(n, bp, NT, HP, 0, h, PPO_ZONE_B3, 1, 0, h, 1, s);
@@ -864,8 +1121,8 @@ hipError_t launch_ppo_minibatch(const PpoNet &n, const PpoExp &x, const int32_t 
     nt<NT_MASK>(I[PPO_T_W2], HP, n.A2, HP, HP, n.A1, HP, rp, NT, s);                      // delta of zone_net_.0
     {
         const int chunks = (rp + kPpoChunk - 1) / kPpoChunk;
-        hipLaunchKernelGGL((k_ppo_tn<true>), dim3(chunks, NT), dim3(64, 1), 0, s, n.A1, HP, nullptr, 0, W1C, rp, n.partial,
-                           g);
+        hipLaunchKernelGGL((k_ppo_tn<true>), dim3(chunks, NT), dim3(64, (W1C + 31) / 32), 0, s, n.A1, HP, nullptr, 0, W1C,
+                           rp, n.partial, g);
     }
     reduce(n, rp, NT, W1C, 0, 0, PPO_ZONE_W1, n.K1, 0, h, n.K1, s);
     reduce(n, rp, NT, W1C, 0, W1C - 1, PPO_ZONE_B1, 1, 0, h, 1, s);

@@ -1,5 +1,5 @@
 // ppo_update.hpp -- the PPO updates on the device (ppo_update.hip): the flat actor-critic's, the Zone-goals agent's two
-// levels' and the xy-goals agent's two levels'.  What zenv_train.cpp hands to the launches.  Internal: not installed.
+// levels', the xy-goals agent's two levels' and the fixed-length-skills agent's two levels'.  What zenv_train.cpp hands to the launches.  Internal: not installed.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -17,7 +17,10 @@ enum {
 // The Zone-goals high level's 16 tensors, zenv_hier_weights' hi_* member order: the encoder's eight as above, then
 // actor.0 / actor.2 where the Gaussian actor has enc_ / mu_, then the critic two places earlier (PpoNet::cr)
 enum { PPO_ACTOR_W1 = PPO_ENC_W, PPO_ACTOR_B1 = PPO_ENC_B, PPO_ACTOR_W2 = PPO_MU_W, PPO_ACTOR_B2 = PPO_MU_B };
-enum { PPO_HEAD_GAUSSIAN = 0, PPO_HEAD_ZONES = 1 };
+// The fixed-length-skills agent's high level has the same 16 places: actor.enc_.0.0 [h, h] / actor.discrete_.0 [S, h]
+// where the Zone-goals one has actor.0 / actor.2 (PPO_HEAD_SKILLS).  Its low level is the Gaussian network on
+// [obs, onehot(skill)] (XD = 8 + S) whose actor.enc_.0.0 and critic.0 read [emb, onehot]: [h, h + S] (PpoNet::S).
+enum { PPO_HEAD_GAUSSIAN = 0, PPO_HEAD_ZONES = 1, PPO_HEAD_SKILLS = 2 };
 // what the Gaussian head's loss is taken of: the flat learner's action with a recorded log_prob per component
 // (k_ppo_loss), or the xy-goals high level's goal with one recorded log_prob per row (k_xyppo_hi_loss)
 enum { PPO_LOSS_ACTION = 0, PPO_LOSS_JOINT_GOAL = 1 };
@@ -38,10 +41,15 @@ struct PpoHyper {
 
 struct PpoNet {
     int h, HP, F, Z, K1, KC, dist, n_tensors;
-    int XD;                  // the per-sample input's width: 8 (obs) or 10 ([obs, goal]); K1 = XD + F
+    int XD;                  // the per-sample input's width: 8 (obs), 10 ([obs, goal]) or 8 + S ([obs, onehot(skill)]);
+                             // K1 = XD + F
     int W1C;                 // columns of zone_net_.0's image and gathered input: XD + F + 1 rounded up to 8; the last is
                              // the constant that carries the bias.  KC = HP + XD rounded up to 8
-    int head;                // PPO_HEAD_GAUSSIAN: enc_, mu_, std_;  PPO_HEAD_ZONES: actor.0 / actor.2 over [emb, zone row]
+    int S;                   // the fixed-length-skills agent's learners: the number of skills (1 .. 32); 0 for every other
+    int LDC;                 // the leading dimension of C and of the images of actor.enc_.0.0 and critic.0: HP, or HP + 32
+                             // for the skills agent's low level, whose columns HP .. HP + S hold onehot(skill)
+    int head;                // PPO_HEAD_GAUSSIAN: enc_, mu_, std_;  PPO_HEAD_ZONES: actor.0 / actor.2 over [emb, zone row];
+                             // PPO_HEAD_SKILLS: enc_, discrete_ (a Categorical over S skills)
     int loss;                // PPO_LOSS_ACTION, or PPO_LOSS_JOINT_GOAL: the xy-goals high level (PPO_HEAD_GAUSSIAN only)
     int cr;                  // the arena index of critic.0.weight: PPO_CRITIC_W1, or two less under PPO_HEAD_ZONES
     int split_reduce;        // the partials of a weight gradient are added by kPpoReduceSplit threads per element
@@ -53,17 +61,20 @@ struct PpoNet {
     // activation workspace for max_batch samples; the backward pass overwrites every activation with its delta
     int max_batch;
     float *A1, *A2;          // [rows][HP], rows = samples x Z rounded up to 32
-    float *P, *C, *Ha, *Hc;  // [samples][HP], samples rounded up to 32
-    float *CI;               // [samples][KC]: zone_net_.4's output (HP columns), then the 8 obs features
+    float *P, *C, *Ha, *Hc;  // [samples][HP] (C: [samples][LDC]), samples rounded up to 32
+    float *CI;               // [samples][KC]: zone_net_.4's output (HP columns), then the XD own features
     float *PRE, *DH;         // [samples][32]: the six head pre-activations, their deltas
     // PPO_HEAD_ZONES only: relu(actor.0) of every zone row [rows][HP], the logits and their deltas [rows][32] (column 0)
+    // PPO_HEAD_SKILLS: L, DL are the S logits of a sample and their deltas [samples][32]; the value stays in PRE / DH
     float *U, *L, *DL;
-    double *DZ;              // [rows]: the logits' deltas as k_hppo_loss forms them, before they are rounded into DL
+    double *DZ;              // [rows]: the logits' deltas as k_hppo_loss forms them, before they are rounded into DL;
+                             // the skills agent's low level: [samples][5], the head's deltas before they are rounded
     float *SS;               // [samples][8]: the per-sample terms of the statistics
     float *partial;          // the per-chunk partials of one weight gradient
     double *norm_partial;    // [arena / kPpoNormBlock + 1]
     float *scalars;          // [0] the gradient norm of the last launch_ppo_norm
-    int *bad_index;          // page-locked host word: a device index outside [0, N T) was met (and dropped)
+    int *bad_index;          // page-locked host word: a device index outside [0, N T), or a recorded goal or skill
+                             // outside its range, was met (and dropped)
     PpoHyper hyper;
 };
 
@@ -76,8 +87,9 @@ struct PpoExp {
     const float *obs, *zone_obs, *action, *log_prob, *value, *advantage, *returnn;
     int N, T;
     const float *goal;              // [slot][2], XD = 10 only
-    const int32_t *hi_action;       // PPO_HEAD_ZONES: the recorded goal [slot] and the goals available at the pick
-    const uint8_t *hi_mask;         // [slot][Z]
+    const int32_t *hi_action;       // PPO_HEAD_ZONES: the recorded goal [slot] and the goals available at the pick;
+    const uint8_t *hi_mask;         // [slot][Z].  PPO_HEAD_SKILLS: the recorded skill [slot], no mask
+    const int32_t *skill = nullptr; // [slot]: the skill a frame was acted under (XD = 8 + S only)
 };
 
 // forward, loss and backward of the samples idx[0 .. count) (device memory): gradients into net.grad, the six

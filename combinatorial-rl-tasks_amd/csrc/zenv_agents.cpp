@@ -664,6 +664,7 @@ static int ensure_exp(zenv_t *h, int T)
     const size_t N = (size_t)h->n_env, ZF = (size_t)h->p.Z * h->p.F;
     h->exp_hier = false;        // zenv_collect_hier sets it once its records are complete
     h->exp_xy = false;          // zenv_collect_xy, the same
+    h->exp_skill = false;       // zenv_collect_skill, the same
     if (!h->exp_mem || h->exp.T != T) {
         HIP_TRY(hipStreamSynchronize(h->stream));
         std::vector<float> keep_mask;
@@ -990,6 +991,7 @@ extern "C" int zenv_collect_skill(zenv_t *h, int T, uint64_t policy_seed, uint64
     HIP_TRY(launch_exp_gae(h->exp, h->n_env, h->mlp_value, discount, gae_lambda, h->stream));
     HIP_TRY(launch_skill_hi_gae(o, T, L, h->n_env, h->sk.env_reward, h->exp.mask, h->exp.cur_mask, h->skill_value,
                                 gae_lambda, h->sk.count, h->stream));
+    h->exp_skill = true;
     return ZENV_OK;
 }
 

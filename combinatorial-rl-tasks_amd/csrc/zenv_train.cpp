@@ -1,6 +1,7 @@
 // zenv_train.cpp -- the learners behind the C ABI of include/zenv.h: the flat actor-critic's PPO update on the handle's own
 // experience buffers (zenv_ppo_*) and the Zone-goals agent's two (zenv_hppo_*, level 0 = low, 1 = high) on the records
-// of zenv_collect_hier, and the xy-goals agent's two (zenv_xyppo_*, the same levels) on the records of zenv_collect_xy.
+// of zenv_collect_hier, the xy-goals agent's two (zenv_xyppo_*, the same levels) on the records of zenv_collect_xy, and
+// the fixed-length-skills agent's two (zenv_skppo_*) on the records of zenv_collect_skill.
 // One PpoState each, the same code.  The kernels: ppo_update.hip.  The networks that act and collect: zenv_agents.cpp.
 #include <algorithm>
 #include <cmath>
@@ -18,7 +19,8 @@ struct PpoState {
     double lr = 0.0;
     int32_t *idx = nullptr;         // host indices, uploaded
     size_t idx_cap = 0;
-    float *stats = nullptr;         // ZENV_F_PPO_STATS / ZENV_F_HPPO_*_STATS / ZENV_F_XYPPO_*_STATS [stats_cap][6]
+    float *stats = nullptr;         // ZENV_F_PPO_STATS / ZENV_F_HPPO_*_STATS / ZENV_F_XYPPO_*_STATS / ZENV_F_SKPPO_*_STATS
+                                    // [stats_cap][6]
     int stats_cap = 0, stats_rows = 0;
 };
 
@@ -27,7 +29,11 @@ namespace {
 // which network a learner trains: the width of its per-sample input, its head and what the head's loss is taken of
 struct NetKind {
     int XD, head, loss;
-    int w1c() const { return XD == 8 ? 16 : 24; }       // XD + F + 1 <= 16 / 18 columns, rounded up to 8
+    int S = 0;                      // the fixed-length-skills agent's learners: the number of skills
+    // XD + F + 1 <= 16 / 18 columns, rounded up to 8; the skills agent's low level: 8 + S + F + 1 <= 48 of them
+    int w1c(int F) const { return S && XD > 8 ? (XD + F + 1 + 7) / 8 * 8 : XD == 8 ? 16 : 24; }
+    // the skills agent's low level: actor.enc_.0.0 and critic.0 read [emb, onehot], S columns more
+    int tail() const { return S && XD > 8 ? S : 0; }
     // the flat actor-critic's learner; every other one belongs to a hierarchical agent
     bool flat() const { return XD == 8 && head == PPO_HEAD_GAUSSIAN && loss == PPO_LOSS_ACTION; }
 };
@@ -35,17 +41,23 @@ constexpr NetKind kFlat{ 8, PPO_HEAD_GAUSSIAN, PPO_LOSS_ACTION }, kHierLo{ 10, P
     kHierHi{ 8, PPO_HEAD_ZONES, PPO_LOSS_ACTION };
 // the xy-goals agent: its low level is the Zone-goals low level, its high level the flat network under the joint loss
 constexpr NetKind kXyLo = kHierLo, kXyHi{ 8, PPO_HEAD_GAUSSIAN, PPO_LOSS_JOINT_GOAL };
+// the fixed-length-skills agent: the Gaussian network on [obs, onehot(skill)], and the flat encoder under a Categorical
+NetKind sk_lo(int S) { return NetKind{ 8 + S, PPO_HEAD_GAUSSIAN, PPO_LOSS_ACTION, S }; }
+NetKind sk_hi(int S) { return NetKind{ 8, PPO_HEAD_SKILLS, PPO_LOSS_ACTION, S }; }
 
 // element counts of the tensors for hidden size h and zone rows of F features: zenv_mlp_weights' member order (20; the
-// Zone-goals low level's 18 with XD = 10), or the 16 of zenv_hier_weights' hi_* members
+// Zone-goals low level's 18 with XD = 10; the skills agent's low level's 18 with XD = 8 + S and [h, h + S] in
+// actor.enc_.0.0 and critic.0), or the 16 of zenv_hier_weights' hi_* members, or the 16 of zenv_skill_weights'
 void tensor_counts(int h, int F, NetKind k, int64_t (&count)[PPO_MAX_TENSORS])
 {
-    const int64_t hh = (int64_t)h * h, X = k.XD;
-    const int64_t c[PPO_MAX_TENSORS] = { h * (X + F), h, hh, h, hh, h, h * (X + h), h, hh, h, 2 * h, 2,
-                                         2 * h, 2, hh, h, h, 1, h, 1 };
+    const int64_t hh = (int64_t)h * h, X = k.XD, he = (int64_t)h * (h + k.tail()), S = k.S;
+    const int64_t c[PPO_MAX_TENSORS] = { h * (X + F), h, hh, h, hh, h, h * (X + h), h, he, h, 2 * h, 2,
+                                         2 * h, 2, he, h, h, 1, h, 1 };
     const int64_t z[PPO_MAX_TENSORS] = { h * (X + F), h, hh, h, hh, h, h * (X + h), h, (int64_t)h * (h + F), h, h, 1,
                                          hh, h, h, 1, 0, 0, 0, 0 };
-    const int64_t *src = k.head == PPO_HEAD_ZONES ? z : c;
+    const int64_t d[PPO_MAX_TENSORS] = { h * (X + F), h, hh, h, hh, h, h * (X + h), h, hh, h, S * h, S,
+                                         hh, h, h, 1, 0, 0, 0, 0 };
+    const int64_t *src = k.head == PPO_HEAD_ZONES ? z : k.head == PPO_HEAD_SKILLS ? d : c;
     std::copy(src, src + PPO_MAX_TENSORS, count);
 }
 
@@ -58,36 +70,44 @@ void tensor_list(const zenv_mlp_weights *w, const float *(&t)[PPO_MAX_TENSORS])
 }
 
 struct Layout {
-    int HP, KC, rp, bp;
+    int HP, KC, LDC, rp, bp;
     int64_t chunks;
     // floats of every workspace piece, in carving order
-    int64_t img[PPO_N_IMAGES], a1, p, ci, pre, ss, partial, u, l;
+    int64_t img[PPO_N_IMAGES], a1, p, c, ci, pre, ss, partial, u, l, dz;
     int64_t total;
 };
 
-Layout layout_for(int h, int Z, int max_batch, NetKind k)
+Layout layout_for(int h, int Z, int F, int max_batch, NetKind k)
 {
     Layout l{};
     l.HP = (h + 32) / 32 * 32;          // h <= 191: at least one padded column, the constant's
     l.KC = l.HP + (k.XD + 7) / 8 * 8;
+    l.LDC = k.tail() ? l.HP + 32 : l.HP;
     const int64_t rp = ((int64_t)max_batch * Z + 31) / 32 * 32, bp = ((int64_t)max_batch + 31) / 32 * 32;
     l.rp = (int)std::min<int64_t>(rp, INT32_MAX);
     l.bp = (int)std::min<int64_t>(bp, INT32_MAX);
     l.chunks = (rp + kPpoChunk - 1) / kPpoChunk;
     const int64_t HP = l.HP, KC = l.KC;
     for (int i = 0; i < PPO_N_IMAGES; ++i) l.img[i] = HP * HP;
-    l.img[PPO_I_W1] = HP * k.w1c();
+    l.img[PPO_I_W1] = HP * k.w1c(F);
     l.img[PPO_I_WC] = HP * KC;
+    l.img[PPO_I_WE] = l.img[PPO_I_WV] = HP * l.LDC;
     l.img[PPO_I_HA] = l.img[PPO_I_HV] = 32 * HP;
     l.img[PPO_T_HA] = l.img[PPO_T_HV] = HP * 32;
     l.a1 = rp * HP;
     l.p = bp * HP;
+    l.c = bp * l.LDC;
     l.ci = bp * KC;
     l.pre = bp * 32;
     l.ss = bp * 8;
-    l.partial = l.chunks * HP * (HP + 32);
+    // the widest product of the learner: a partial is [HP][its columns rounded up to 32]; HP + 32 covers every product
+    // but combine_net_'s, whose KC columns pass HP + 32 once the own ones pass 32 (the skills agent, S > 24)
+    l.partial = l.chunks * HP * std::max<int64_t>(HP + 32, (KC + 31) / 32 * 32);
     if (k.head == PPO_HEAD_ZONES) l.u = rp * HP, l.l = rp * 32;
-    l.total = 2 * l.a1 + 4 * l.p + l.ci + 2 * l.pre + l.ss + l.partial + l.u + 2 * l.l + l.l / 16;
+    if (k.head == PPO_HEAD_SKILLS) l.l = bp * 32;       // the S logits of a sample, their deltas
+    // DZ, in floats: a double per zone row (the per-zone head), or five per sample (the skills agent's low level)
+    l.dz = k.tail() ? bp * 10 : l.l / 16;
+    l.total = 2 * l.a1 + 3 * l.p + l.c + l.ci + 2 * l.pre + l.ss + l.partial + l.u + 2 * l.l + l.dz;
     for (int i = 0; i < PPO_N_IMAGES; ++i) l.total += l.img[i];
     return l;
 }
@@ -101,7 +121,7 @@ int learner_check(const zenv_config *cfg, int h_dim, const float *const *t, NetK
     if (h_dim < 1 || h_dim > 191) return fail(ZENV_E_ARG, "%sh_dim %d outside [1, 191]", who, h_dim);
     if (cfg->num_zones < 1 || cfg->num_zones > ZENV_MAX_ZONES)
         return fail(ZENV_E_ARG, "num_zones %d outside [1, %d]", cfg->num_zones, ZENV_MAX_ZONES);
-    const int critic = k.head == PPO_HEAD_ZONES ? PPO_CRITIC_W1 - 2 : PPO_CRITIC_W1;
+    const int critic = k.head != PPO_HEAD_GAUSSIAN ? PPO_CRITIC_W1 - 2 : PPO_CRITIC_W1;
     for (int i = 0; i < critic; ++i)
         if (!t[i]) return fail(ZENV_E_ARG, "%sa tensor of the weights is null", who);
     for (int i = critic; i < critic + 4; ++i)
@@ -115,7 +135,7 @@ int learner_check(const zenv_config *cfg, int h_dim, const float *const *t, NetK
     if (bad_hyper(pc->max_grad_norm) && !(hier && pc->max_grad_norm == INFINITY))
         return fail(ZENV_E_ARG, "%sa hyper-parameter is negative or not finite (%g)", who, pc->max_grad_norm);
     if (pc->max_batch < 1) return fail(ZENV_E_ARG, "%smax_batch must be >= 1", who);
-    const Layout l = layout_for(h_dim, cfg->num_zones, pc->max_batch, k);
+    const Layout l = layout_for(h_dim, cfg->num_zones, zenv_zone_feat(cfg), pc->max_batch, k);
     if (l.total >= ((int64_t)1 << 31))
         return fail(ZENV_E_ARG, "%smax_batch %d x %d zones needs a workspace of %lld floats, the limit is 2^31: use smaller "
                     "minibatches", who, pc->max_batch, cfg->num_zones, (long long)l.total);
@@ -146,6 +166,21 @@ void xy_tensor_lists(const zenv_xy_weights *w, const float *(&lo)[PPO_MAX_TENSOR
                                         w->hi_zone_b3, w->hi_comb_w, w->hi_comb_b, w->hi_enc_w, w->hi_enc_b, w->hi_mu_w,
                                         w->hi_mu_b, w->hi_std_w, w->hi_std_b, w->hi_critic_w1, w->hi_critic_b1,
                                         w->hi_critic_w2, w->hi_critic_b2, nullptr, nullptr };
+    std::copy(l, l + PPO_MAX_TENSORS, lo);
+    std::copy(u, u + PPO_MAX_TENSORS, hi);
+}
+
+void skill_tensor_lists(const zenv_skill_weights *w, const float *(&lo)[PPO_MAX_TENSORS],
+                        const float *(&hi)[PPO_MAX_TENSORS])
+{
+    const float *l[PPO_MAX_TENSORS] = { w->lo_zone_w1, w->lo_zone_b1, w->lo_zone_w2, w->lo_zone_b2, w->lo_zone_w3,
+                                        w->lo_zone_b3, w->lo_comb_w, w->lo_comb_b, w->lo_enc_w, w->lo_enc_b, w->lo_mu_w,
+                                        w->lo_mu_b, w->lo_std_w, w->lo_std_b, w->lo_critic_w1, w->lo_critic_b1,
+                                        w->lo_critic_w2, w->lo_critic_b2, nullptr, nullptr };
+    const float *u[PPO_MAX_TENSORS] = { w->hi_zone_w1, w->hi_zone_b1, w->hi_zone_w2, w->hi_zone_b2, w->hi_zone_w3,
+                                        w->hi_zone_b3, w->hi_comb_w, w->hi_comb_b, w->hi_enc_w, w->hi_enc_b,
+                                        w->hi_logit_w, w->hi_logit_b, w->hi_critic_w1, w->hi_critic_b1, w->hi_critic_w2,
+                                        w->hi_critic_b2, nullptr, nullptr, nullptr, nullptr };
     std::copy(l, l + PPO_MAX_TENSORS, lo);
     std::copy(u, u + PPO_MAX_TENSORS, hi);
 }
@@ -190,6 +225,20 @@ extern "C" int zenv_xyppo_check(const zenv_config *cfg, const zenv_xy_weights *w
     return learner_check(cfg, w->h_dim, th, kXyHi, hi, "high level: ");
 }
 
+extern "C" int zenv_skppo_check(const zenv_config *cfg, const zenv_skill_weights *w, const zenv_ppo_config *lo,
+                                const zenv_ppo_config *hi)
+{
+    if (!cfg || !w || !lo || !hi) return fail(ZENV_E_ARG, "null argument");
+    if (w->n_skills < 1 || w->n_skills > kMaxSkills)
+        return fail(ZENV_E_ARG, "n_skills %d outside [1, %d]", w->n_skills, kMaxSkills);
+    if (w->zone_feat != zenv_zone_feat(cfg))
+        return fail(ZENV_E_ARG, "zone_feat %d: the handle's zone rows have %d features", w->zone_feat, zenv_zone_feat(cfg));
+    const float *tl[PPO_MAX_TENSORS], *th[PPO_MAX_TENSORS];
+    skill_tensor_lists(w, tl, th);
+    if (int rc = learner_check(cfg, w->h_dim, tl, sk_lo(w->n_skills), lo, "low level: ")) return rc;
+    return learner_check(cfg, w->h_dim, th, sk_hi(w->n_skills), hi, "high level: ");
+}
+
 static void learner_free(PpoState *&s)
 {
     if (!s) return;
@@ -207,25 +256,28 @@ void ppo_free(zenv *h)
     learner_free(h->hppo[1]);
     learner_free(h->xyppo[0]);
     learner_free(h->xyppo[1]);
+    learner_free(h->skppo[0]);
+    learner_free(h->skppo[1]);
 }
 
 int ppo_index_check(zenv *h)
 {
     bool bad = false;
-    for (PpoState *s : { h->ppo, h->hppo[0], h->hppo[1], h->xyppo[0], h->xyppo[1] })
+    for (PpoState *s : { h->ppo, h->hppo[0], h->hppo[1], h->xyppo[0], h->xyppo[1], h->skppo[0], h->skppo[1] })
         if (s && s->net.bad_index && *(volatile int *)s->net.bad_index) {
             *(volatile int *)s->net.bad_index = 0;
             bad = true;
         }
     if (!bad) return ZENV_OK;
     return fail(ZENV_E_ARG, "a device-resident minibatch index lay outside [0, envs x frames), or a recorded goal was "
-                            "not among its row's available goals: the sample was dropped and the update since the last "
+                            "not among its row's available goals, or a recorded skill lay outside [0, n_skills): the sample was dropped and the update since the last "
                             "synchronising call is invalid");
 }
 
 void *ppo_stats(const zenv *h, int which, int64_t *bytes)
 {
-    const PpoState *s = which == 0 ? h->ppo : which <= 2 ? h->hppo[which - 1] : h->xyppo[which - 3];
+    const PpoState *s = which == 0 ? h->ppo : which <= 2 ? h->hppo[which - 1] : which <= 4 ? h->xyppo[which - 3]
+                                                                                            : h->skppo[which - 5];
     *bytes = s ? (int64_t)s->stats_rows * kPpoStats * 4 : 0;
     return s ? s->stats : nullptr;
 }
@@ -239,13 +291,13 @@ static int learner_create(zenv *h, PpoState *&slot, int h_dim, const float *cons
     PpoState *s = new PpoState();
     slot = s;
     PpoNet &n = s->net;
-    const Layout l = layout_for(h_dim, h->p.Z, pc->max_batch, k);
+    const Layout l = layout_for(h_dim, h->p.Z, h->p.F, pc->max_batch, k);
     n.h = h_dim, n.HP = l.HP, n.F = h->p.F, n.Z = h->p.Z, n.K1 = k.XD + h->p.F, n.KC = l.KC;
-    n.XD = k.XD, n.W1C = k.w1c(), n.head = k.head, n.loss = k.loss;
-    n.cr = k.head == PPO_HEAD_ZONES ? PPO_CRITIC_W1 - 2 : PPO_CRITIC_W1;
+    n.XD = k.XD, n.W1C = k.w1c(h->p.F), n.head = k.head, n.loss = k.loss, n.S = k.S, n.LDC = l.LDC;
+    n.cr = k.head != PPO_HEAD_GAUSSIAN ? PPO_CRITIC_W1 - 2 : PPO_CRITIC_W1;
     n.split_reduce = k.flat() ? 0 : 1;                  // the hierarchical agents' learners
     n.dist = pc->distributional_value ? 1 : 0;
-    n.n_tensors = k.head == PPO_HEAD_ZONES ? 16 : n.dist ? 20 : 18;
+    n.n_tensors = k.head != PPO_HEAD_GAUSSIAN ? 16 : n.dist ? 20 : 18;
     n.max_batch = pc->max_batch;
     s->lr = pc->lr;
     n.hyper = PpoHyper{ (float)pc->lr, (float)pc->adam_eps, (float)pc->clip_eps, (float)pc->entropy_coef,
@@ -276,13 +328,13 @@ static int learner_create(zenv *h, PpoState *&slot, int h_dim, const float *cons
     auto take = [&f](int64_t count) { float *p = f; f += count; return p; };
     for (int i = 0; i < PPO_N_IMAGES; ++i) n.img[i] = take(l.img[i]);
     n.A1 = take(l.a1), n.A2 = take(l.a1);
-    n.P = take(l.p), n.C = take(l.p), n.Ha = take(l.p), n.Hc = take(l.p);
+    n.P = take(l.p), n.C = take(l.c), n.Ha = take(l.p), n.Hc = take(l.p);
     n.CI = take(l.ci);
     n.PRE = take(l.pre), n.DH = take(l.pre);
     n.SS = take(l.ss);
     n.partial = take(l.partial);
     n.U = take(l.u), n.L = take(l.l), n.DL = take(l.l);
-    n.DZ = reinterpret_cast<double *>(take(l.l / 16));      // rp doubles; every piece before it is a multiple of 32 floats
+    n.DZ = reinterpret_cast<double *>(take(l.dz));          // doubles; every piece before it is a multiple of 32 floats
     n.norm_partial = reinterpret_cast<double *>(f);      // l.total is a multiple of 8 floats: 8-byte aligned
     n.scalars = reinterpret_cast<float *>(n.norm_partial + norm_parts + 1);
     HIP_TRY(hipHostMalloc((void **)&n.bad_index, sizeof(int), hipHostMallocDefault));
@@ -332,9 +384,24 @@ extern "C" int zenv_xyppo_init(zenv_t *h, const zenv_xy_weights *w, const zenv_p
     return rc;
 }
 
+extern "C" int zenv_skppo_init(zenv_t *h, const zenv_skill_weights *w, const zenv_ppo_config *lo, const zenv_ppo_config *hi)
+{
+    if (!h || !w || !lo || !hi) return fail(ZENV_E_ARG, "null argument");
+    if (int rc = zenv_skppo_check(&h->cfg, w, lo, hi)) return rc;
+    const float *tl[PPO_MAX_TENSORS], *th[PPO_MAX_TENSORS];
+    skill_tensor_lists(w, tl, th);
+    int rc = learner_create(h, h->skppo[0], w->h_dim, tl, sk_lo(w->n_skills), lo);
+    if (!rc) rc = learner_create(h, h->skppo[1], w->h_dim, th, sk_hi(w->n_skills), hi);
+    if (rc) {                   // no half-pair
+        learner_free(h->skppo[0]);
+        learner_free(h->skppo[1]);
+    }
+    return rc;
+}
+
 namespace {
 
-enum { AGENT_FLAT = 0, AGENT_HIER = 1, AGENT_XY = 2 };
+enum { AGENT_FLAT = 0, AGENT_HIER = 1, AGENT_XY = 2, AGENT_SKILL = 3 };
 
 // What an entry point works on: the flat learner, or level 0 / 1 of the Zone-goals or the xy-goals pair with the
 // experience they read.
@@ -357,6 +424,11 @@ int find_learner(zenv *h, int level, int agent, Learner &out)
     if (agent == AGENT_XY) {
         if (!h->xyppo[level]) return fail(ZENV_E_STATE, "zenv_xyppo_init first");
         out = Learner{ h->xyppo[level], level, AGENT_XY };
+        return ZENV_OK;
+    }
+    if (agent == AGENT_SKILL) {
+        if (!h->skppo[level]) return fail(ZENV_E_STATE, "zenv_skppo_init first");
+        out = Learner{ h->skppo[level], level, AGENT_SKILL };
         return ZENV_OK;
     }
     if (!h->hppo[level]) return fail(ZENV_E_STATE, "zenv_hppo_init first");
@@ -423,6 +495,26 @@ int learner_exp(const zenv *h, const Learner &l, PpoExp &x, int64_t &samples)
         const HierOut &o = h->hout;
         x = PpoExp{ o.obs, o.zone_obs, reinterpret_cast<const float *>(h->xc.hi_goal), o.log_prob, o.value, o.advantage,
                     o.returnn, (int)h->hi_m, 1, nullptr, nullptr, nullptr };
+        samples = h->hi_m;
+        return ZENV_OK;
+    }
+    if (l.agent == AGENT_SKILL) {
+        if (!h->exp_mem || !h->exp_skill || h->hi_kind != 1 || !h->sk_mem || h->sk.T != e.T || h->hi_m < 1)
+            return fail(ZENV_E_STATE, "zenv_collect_skill first: the ZENV_F_EXP_* / ZENV_F_LO_* / ZENV_F_HI_* buffers do "
+                                      "not hold its records");
+        if (!h->skill_ready || h->skill.S != l.s->net.S)
+            return fail(ZENV_E_STATE, "the records are of an agent with another number of skills than the learner's %d",
+                        l.s->net.S);
+        if (l.level == 0) {     // ALL T frames of every env (_hier_policy_opt.py:188-199), the skill the frame was acted under
+            x = PpoExp{ e.obs, e.zone_obs, e.action, e.log_prob, e.value, e.advantage, e.returnn, h->n_env, e.T, nullptr,
+                        nullptr, nullptr, h->sk.lo_skill };
+            samples = (int64_t)h->n_env * e.T;
+            return ZENV_OK;
+        }
+        // the dense env-major rows of the windows: M = N T / skill_len, the skill as the action, one log_prob per row
+        const HierOut &o = h->hout;
+        x = PpoExp{ o.obs, o.zone_obs, nullptr, o.log_prob, o.value, o.advantage, o.returnn, (int)h->hi_m, 1, nullptr,
+                    o.action, nullptr, nullptr };
         samples = h->hi_m;
         return ZENV_OK;
     }
@@ -681,5 +773,53 @@ extern "C" int zenv_xyppo_epoch(zenv_t *h, int level, const int32_t *order, int 
 {
     if (!h || !order) return fail(ZENV_E_ARG, "null argument");
     LEARNER(h, level, AGENT_XY);
+    return learner_epoch(h, l, order, total, batch_size, on_device);
+}
+
+extern "C" int zenv_skppo_tensor(zenv_t *h, int level, int which, int index, void **dev_ptr, int64_t *count)
+{
+    if (!h || !dev_ptr || !count) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, level, AGENT_SKILL);
+    return learner_tensor(l, which, index, dev_ptr, count);
+}
+extern "C" int zenv_skppo_read(zenv_t *h, int level, int which, int index, float *dst)
+{
+    if (!dst) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, level, AGENT_SKILL);
+    return learner_copy(h, l, which, index, dst, true);
+}
+extern "C" int zenv_skppo_write(zenv_t *h, int level, int which, int index, const float *src)
+{
+    if (!src) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, level, AGENT_SKILL);
+    return learner_copy(h, l, which, index, const_cast<float *>(src), false);
+}
+extern "C" int zenv_skppo_get_step(zenv_t *h, int level, int64_t *step)
+{
+    if (!h || !step) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, level, AGENT_SKILL);
+    *step = l.s->step;
+    return ZENV_OK;
+}
+extern "C" int zenv_skppo_set_step(zenv_t *h, int level, int64_t step)
+{
+    LEARNER(h, level, AGENT_SKILL);
+    return learner_set_step(l, step);
+}
+extern "C" int zenv_skppo_minibatch(zenv_t *h, int level, const int32_t *idx, int count, int idx_on_device, int apply)
+{
+    if (!h || !idx) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, level, AGENT_SKILL);
+    return learner_minibatch(h, l, idx, count, idx_on_device, apply);
+}
+extern "C" int zenv_skppo_apply(zenv_t *h, int level)
+{
+    LEARNER(h, level, AGENT_SKILL);
+    return learner_apply(h, l);
+}
+extern "C" int zenv_skppo_epoch(zenv_t *h, int level, const int32_t *order, int total, int batch_size, int on_device)
+{
+    if (!h || !order) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, level, AGENT_SKILL);
     return learner_epoch(h, l, order, total, batch_size, on_device);
 }

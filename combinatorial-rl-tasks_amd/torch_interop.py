@@ -344,6 +344,85 @@ class TorchZoneEnv:
     def xyppo_update(self, epochs, batch_size, hi_epochs, hi_batch_size, rng):
         return self.env.xyppo_update(epochs, batch_size, hi_epochs, hi_batch_size, rng)
 
+    # ------------------------------------------------------------------ the fixed-length-skills agent's two PPO updates
+    def skppo_init(self, hi_state_dict, lo_state_dict, lo=None, hi=None):
+        """``ZoneVecEnv.skppo_init`` with each level's four arenas as flat float32 CUDA tensors ALIASING device memory in
+        ``self.skppo_arenas[level]`` (valid until the next skppo_init or ``env.close()``)."""
+        self.env.skppo_init(hi_state_dict, lo_state_dict, lo=lo, hi=hi)
+        with self._torch.cuda.device(self.device):
+            self.skppo_arenas = {}
+            for level in (nat.SKPPO_LO, nat.SKPPO_HI):
+                self.skppo_arenas[level] = {}
+                for name, which in (("param", nat.PPO_PARAM), ("grad", nat.PPO_GRAD), ("exp_avg", nat.PPO_EXP_AVG),
+                                    ("exp_avg_sq", nat.PPO_EXP_AVG_SQ)):
+                    ptr, count = self.env.skppo_tensor_ptr(level, which, -1)
+                    self.skppo_arenas[level][name] = self._alias_ptr(ptr, (count,))
+
+    def skppo_tensors(self, level, which=nat.PPO_PARAM):
+        """zenv_skill_weights name -> CUDA tensor ALIASING that tensor of a level's arena, in its state_dict shape."""
+        learner = self.env._sk_learner(level)
+        with self._torch.cuda.device(self.device):
+            return {name: self._alias_ptr(learner.tensor_ptr(which, i)[0], learner.shapes[name])
+                    for i, name in enumerate(learner.keys)}
+
+    def skppo_set_tensors(self, level, tensors, which=nat.PPO_PARAM):
+        """Overwrite the tensors of a level's arena that `tensors` names (tensors on any device), on the stream."""
+        views = self.skppo_tensors(level, which)
+        for name, src in tensors.items():
+            views[name].copy_(self._torch.as_tensor(src))
+
+    def skppo_state_dicts(self):
+        """(hi_model_state, lo_model_state) as CUDA tensors ALIASING the two parameter arenas."""
+        out = []
+        for level in (nat.SKPPO_HI, nat.SKPPO_LO):
+            views = self.skppo_tensors(level)
+            out.append({key: views[name] for name, key in self.env._sk_learner(level).keys.items()})
+        return tuple(out)
+
+    def skppo_load_state_dicts(self, hi_state_dict, lo_state_dict):
+        for dst_sd, src_sd in zip(self.skppo_state_dicts(), (hi_state_dict, lo_state_dict)):
+            for key, dst in dst_sd.items():
+                dst.copy_(src_sd[key])
+
+    def skppo_optimizer_state(self, level):
+        """``ZoneVecEnv.skppo_optimizer_state`` with the moments as CUDA copies."""
+        torch = self._torch
+        out = self.env.skppo_optimizer_state(level)
+        out["state"] = {i: {"step": torch.tensor(s["step"]), "exp_avg": torch.from_numpy(s["exp_avg"]).to(self.device),
+                            "exp_avg_sq": torch.from_numpy(s["exp_avg_sq"]).to(self.device)}
+                        for i, s in out["state"].items()}
+        return out
+
+    def skppo_load_optimizer_state(self, level, state):
+        self.env.skppo_load_optimizer_state(level, state)
+
+    def skppo_minibatch(self, level, idx, apply=False):
+        """``ZoneVecEnv.skppo_minibatch``; idx may be an int32 CUDA tensor (never copied, checked on the device)."""
+        ptr, count = self._ppo_index_arg(idx)
+        self.env.skppo_minibatch(level, ptr, apply=apply, count=count)
+
+    def skppo_apply(self, level):
+        self.env.skppo_apply(level)
+
+    def skppo_epoch(self, level, order, batch_size):
+        """``ZoneVecEnv.skppo_epoch``; order may be an int32 CUDA tensor."""
+        ptr, count = self._ppo_index_arg(order)
+        self.env.skppo_epoch(level, ptr, batch_size, count=count)
+
+    def skppo_stats(self, level):
+        """float32 CUDA tensor [minibatches, 6] ALIASING the statistics of the level's last skppo_minibatch / skppo_epoch
+        (not synchronised)."""
+        field = nat.SKPPO_STATS_FIELDS[level]
+        rows = self.env.field_bytes(field) // 24
+        with self._torch.cuda.device(self.device):
+            return self._alias(field, (rows, 6), np.float32)
+
+    def skppo_publish(self):
+        self.env.skppo_publish()
+
+    def skppo_update(self, epochs, batch_size, hi_epochs, hi_batch_size, rng):
+        return self.env.skppo_update(epochs, batch_size, hi_epochs, hi_batch_size, rng)
+
     def load_hier(self, hi_state_dict, lo_state_dict):
         """Put HighPolicyValueModel / LoPolicyValueModel state_dicts (zone-goals/src/hier_policy_value_models.py; torch
         tensors on any device) into the device agent that ``collect_hier`` runs -- after every update."""

@@ -22,7 +22,7 @@ from .agents import (_HIER_ENC, _HIER_CRITIC, HIER_HI_KEYS, HIER_LO_KEYS, SKILL_
                      check_collect_hier_args, check_collect_skill_args, check_collect_option_args,
                      hier_experience_layout, skill_experience_layout, option_experience_layout, skill_num_frames,
                      check_collect_xy_args, xy_experience_layout, ppo_state_dict_keys, ppo_batch_indexes,
-                     hppo_state_dict_keys, hppo_batch_indexes, xyppo_state_dict_keys)
+                     hppo_state_dict_keys, hppo_batch_indexes, xyppo_state_dict_keys, skppo_state_dict_keys)
 
 _FIELD_DTYPES = {
     nat.F_OBS: np.float32, nat.F_ZONE_OBS: np.float32, nat.F_REWARD: np.float32,
@@ -47,6 +47,7 @@ _FIELD_DTYPES = {
     nat.F_XY_BOOTSTRAP_GOAL: np.float32, nat.F_PPO_STATS: np.float32,
     nat.F_HPPO_LO_STATS: np.float32, nat.F_HPPO_HI_STATS: np.float32,
     nat.F_XYPPO_LO_STATS: np.float32, nat.F_XYPPO_HI_STATS: np.float32,
+    nat.F_SKPPO_LO_STATS: np.float32, nat.F_SKPPO_HI_STATS: np.float32,
 }
 
 
@@ -56,9 +57,9 @@ def _as_host_f32(v):
 
 
 class _Learner:
-    """One device learner behind the ppo_* (level None: zenv_ppo_*), hppo_* (zenv_hppo_* with a level) or xyppo_*
-    (prefix "zenv_xyppo_") methods: the arenas' tensors under their names, Adam's state, the update calls and the
-    statistics."""
+    """One device learner behind the ppo_* (level None: zenv_ppo_*), hppo_* (zenv_hppo_* with a level), xyppo_*
+    (prefix "zenv_xyppo_") or skppo_* (prefix "zenv_skppo_") methods: the arenas' tensors under their names, Adam's
+    state, the update calls and the statistics."""
 
     def __init__(self, handle, level, keys, shapes, lr, adam_eps, stats_field, prefix="zenv_hppo_"):
         self._h, self.level, self.keys, self.shapes = handle, level, keys, shapes
@@ -1153,6 +1154,123 @@ class ZoneVecEnv:
         if T < 1 or M < 1:
             raise ZenvError(nat.E_STATE, "collect_xy first: the handle holds no experience of the xy-goals agent")
         hi, lo = self._xy_learner(nat.XYPPO_HI), self._xy_learner(nat.XYPPO_LO)
+        names = [(i, n) for i, n in enumerate(nat.PPO_STATS) if n != "value_std"]
+        logs = {"hi_" + n: 0.0 for _, n in names}
+        for _ in range(int(hi_epochs)):
+            hi.epoch(hppo_batch_indexes(M, rng), hi_batch_size)
+        if int(hi_epochs) > 0:
+            mean = hi.stats().astype(np.float64).mean(axis=0)
+            logs = {"hi_" + n: float(mean[i]) for i, n in names}
+        rows = []
+        for _ in range(int(epochs)):
+            lo.epoch(hppo_batch_indexes(self.num_envs * T, rng), batch_size)
+            rows.append(lo.stats())
+        mean = np.concatenate(rows).astype(np.float64).mean(axis=0) if rows else np.zeros(6)
+        logs.update({"lo_" + n: float(mean[i]) for i, n in names})
+        return logs
+
+    # ------------------------------------------------------------------ the fixed-length-skills agent's two PPO updates
+    # the example's hyper-parameters (examples/skill_planner_ppo_torch.py; the reference takes the norm and does not clip)
+    SKPPO_LO = dict(lr=3e-4, adam_eps=1e-8, clip_eps=0.2, entropy_coef=0.003, value_loss_coef=0.5, max_grad_norm=math.inf,
+                    max_batch=16384)
+    SKPPO_HI = dict(lr=3e-4, adam_eps=1e-8, clip_eps=0.2, entropy_coef=0.01, value_loss_coef=0.5, max_grad_norm=math.inf,
+                    max_batch=4096)
+
+    def _sk_learner(self, level):
+        """``_learner`` for the fixed-length-skills pair."""
+        found = self._learners.get(("sk", int(level)))
+        field = nat.SKPPO_STATS_FIELDS[level] if level in (nat.SKPPO_LO, nat.SKPPO_HI) else nat.F_SKPPO_LO_STATS
+        return found or _Learner(self._h, level, {}, {}, 0.0, 0.0, field, "zenv_skppo_")
+
+    def skppo_init(self, hi_state_dict, lo_state_dict, lo=None, hi=None):
+        """The two learners of the fixed-length-skills agent (main/src/torch_ac/algos/_hier_policy_opt.py:265-419; DIAYN
+        trains the same two) on the device, from its HighPolicyValueModel / LoPolicyValueModel state_dicts with both
+        critics: float32 master parameters, gradients, Adam's moments and a workspace per level.  lo / hi: dicts of the
+        settings to change from ``SKPPO_LO`` / ``SKPPO_HI``.  `level` in the other skppo_* methods: ``_native.SKPPO_LO``
+        = 0, ``SKPPO_HI`` = 1.  Separate from ``load_skills``: ``skppo_publish`` hands the parameters to the acting
+        agent.  The inverse model's and the skill prior's updates stay with the caller."""
+        tensors = skill_tensors_from_state_dicts(hi_state_dict, lo_state_dict)
+        S, h = (int(v) for v in tensors["hi_logit_w"].shape)
+        F = int(tensors["hi_zone_w1"].shape[1]) - 8
+        hi_keys, lo_keys = skppo_state_dict_keys()
+        missing = [n for n in list(hi_keys) + list(lo_keys) if n not in tensors]
+        if missing:
+            raise ValueError(f"the update needs both critics: no {missing[0]}")
+        shapes = skill_tensor_shapes(h, S, F)
+        w = nat.SkillWeights(h_dim=h, n_skills=S, zone_feat=F, precision=nat.MLP_F32)
+        keep = self._load_weights(w, list(hi_keys) + list(lo_keys), tensors, shapes)      # alive across the call
+        cfgs = [nat.PpoConfig(distributional_value=0, **dict(base, **(over or {})))
+                for base, over in ((self.SKPPO_LO, lo), (self.SKPPO_HI, hi))]
+        check(lib().zenv_skppo_init(self._h, C.byref(w), C.byref(cfgs[0]), C.byref(cfgs[1])))
+        del keep
+        for level, keys in ((nat.SKPPO_LO, lo_keys), (nat.SKPPO_HI, hi_keys)):
+            self._learners[("sk", level)] = _Learner(self._h, level, keys, shapes, cfgs[level].lr, cfgs[level].adam_eps,
+                                                     nat.SKPPO_STATS_FIELDS[level], "zenv_skppo_")
+    def skppo_tensor_ptr(self, level, which, index):
+        """``ppo_tensor_ptr`` of a level's arenas."""
+        return self._sk_learner(level).tensor_ptr(which, index)
+
+    def skppo_tensors(self, level, which=nat.PPO_PARAM):
+        """Every tensor of a level's arena as a new host array, under its zenv_skill_weights name (hi_* / lo_*)."""
+        return self._sk_learner(level).tensors(which)
+
+    def skppo_set_tensors(self, level, tensors, which=nat.PPO_PARAM):
+        self._sk_learner(level).set_tensors(tensors, which)
+
+    def skppo_state_dicts(self):
+        """(hi_model_state, lo_model_state): both learners' parameters under the reference's names (host copies)."""
+        return self._sk_learner(nat.SKPPO_HI).state_dict(), self._sk_learner(nat.SKPPO_LO).state_dict()
+
+    def skppo_load_state_dicts(self, hi_state_dict, lo_state_dict):
+        self._sk_learner(nat.SKPPO_HI).load_state_dict(hi_state_dict)
+        self._sk_learner(nat.SKPPO_LO).load_state_dict(lo_state_dict)
+
+    def skppo_optimizer_state(self, level):
+        """A level's Adam state in the shape of ``torch.optim.Adam.state_dict()``: parameter i is the i-th of the
+        module's ``parameters()``."""
+        return self._sk_learner(level).optimizer_state()
+
+    def skppo_load_optimizer_state(self, level, state):
+        self._sk_learner(level).load_optimizer_state(state)
+
+    def skppo_get_step(self, level):
+        return self._sk_learner(level).get_step()
+
+    def skppo_set_step(self, level, step):
+        self._sk_learner(level).set_step(step)
+
+    def skppo_minibatch(self, level, idx, apply=False, count=None):
+        """``ppo_minibatch`` on the records of the last ``collect_skills``.  Low level: index i is env i // T, frame i % T
+        (lo_exps' order, every frame); high level: row i of the M = N T / skill_len windows."""
+        self._sk_learner(level).minibatch(idx, apply, count)
+
+    def skppo_apply(self, level):
+        self._sk_learner(level).apply()
+
+    def skppo_epoch(self, level, order, batch_size, count=None):
+        self._sk_learner(level).epoch(order, batch_size, count)
+
+    def skppo_stats(self, level):
+        """float32 [minibatches, 6] of the level's last skppo_minibatch / skppo_epoch (``_native.PPO_STATS``' columns,
+        value_std = 0).  Waits for the device."""
+        return self._sk_learner(level).stats()
+
+    def skppo_publish(self):
+        """Hand both learners' parameters to the acting agent: read them back and ``load_skills`` them with the
+        handle's current skill_len, so the next ``collect_skills`` acts with them.  A loaded inverse model stays."""
+        self.load_skills(dict(self.skppo_tensors(nat.SKPPO_HI), **self.skppo_tensors(nat.SKPPO_LO)),
+                     skill_len=getattr(self, "_skill_len", 200))
+
+    def skppo_update(self, epochs, batch_size, hi_epochs, hi_batch_size, rng):
+        """update_parameters (main's _hier_policy_opt.py:254-263, train_lo and train_hi) on the records of the last ``collect_skills``: the high
+        level first, then the low level, each epoch in the order of ``hppo_batch_indexes`` from the caller's numpy
+        Generator.  Returns the reference's logs under lo_* / hi_*: the low level's are means over all its minibatches
+        (its lists start before the epoch loop), the high level's over the last epoch's."""
+        T = lib().zenv_field_bytes(self._h, nat.F_EXP_VALUE) // (4 * self.num_envs)
+        M = lib().zenv_field_bytes(self._h, nat.F_HI_ACTION) // 4
+        if T < 1 or M < 1:
+            raise ZenvError(nat.E_STATE, "collect_skills first: the handle holds no experience of the fixed-length-skills agent")
+        hi, lo = self._sk_learner(nat.SKPPO_HI), self._sk_learner(nat.SKPPO_LO)
         names = [(i, n) for i, n in enumerate(nat.PPO_STATS) if n != "value_std"]
         logs = {"hi_" + n: 0.0 for _, n in names}
         for _ in range(int(hi_epochs)):

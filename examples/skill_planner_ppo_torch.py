@@ -10,12 +10,17 @@ tests/skill_ref.py and tests/skill_collect_ref.py), so their state_dicts are the
 device agent is reloaded from them.
 
     python examples/skill_planner_ppo_torch.py --env PointTSP-v0 --procs 4096 --skill-len 20 --frames-per-proc 100
+
+``--device-update`` runs the low and the high level's updates in the library as well (``TorchZoneEnv.skppo_init`` /
+``skppo_update`` / ``skppo_publish``: zenv_skppo_*, csrc/ppo_update.hip); the inverse model's and the skill prior's stay
+in torch on the same collection.  Off by default, the torch path is what it was.
 """
 import argparse
 import os
 import sys
 import time
 
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -117,13 +122,16 @@ def _ppo_loss(log_prob, old_log_prob, value, sb, clip_eps):
 
 class SkillPlannerPPO:
     """One iteration of the skill planner: collect_experiences on the device, then the four updates of
-    _hier_policy_opt.py:265-466 in torch -- lo PPO, hi PPO, the inverse model's cross-entropy, the skill prior's."""
+    _hier_policy_opt.py:265-466 in torch -- lo PPO, hi PPO, the inverse model's cross-entropy, the skill prior's.  With
+    device_update the lo and hi PPO run in the library (``skppo_init`` once; then ``collect_skills``, ``skppo_update``,
+    ``skppo_publish`` per iteration, and the modules get the learners' parameters back after every update); the other
+    two stay in torch."""
 
     def __init__(self, tenv, n_skills=5, h=128, skill_len=20, frames_per_proc=100, diversity_coef=0.1, train_hi=True,
                  epochs=4, batch_size=16384, hi_epochs=4, hi_batch_size=4096, inverse_epochs=4,
                  inverse_batch_size=16384, lr=3e-4, hi_lr=3e-4, inverse_lr=3e-4, discount=0.99, gae_lambda=0.95,
                  clip_eps=0.2, entropy_coef=0.003, hi_entropy_coef=0.01, value_loss_coef=0.5, hi_value_coef=0.5,
-                 seed=1):
+                 seed=1, device_update=False):
         self.tenv, self.S, self.L, self.T = tenv, n_skills, skill_len, frames_per_proc
         dev, F_ = tenv.device, tenv.env.zone_feat
         self.hi_net = HighPolicyValueModel(F_, n_skills, h).to(dev)
@@ -142,14 +150,26 @@ class SkillPlannerPPO:
         self.skill_logit_optimizer = torch.optim.Adam([self.skill_logits], 1e-2, eps=1e-8)
         self.gen = torch.Generator(device=dev).manual_seed(seed)
         self.seed, self.it = seed, 0
+        self.device_update = device_update
+        if device_update:
+            self.rng = np.random.default_rng(seed)
+            tenv.skppo_init(self.hi_net.state_dict(), self.lo_net.state_dict(),
+                            lo=dict(lr=lr, clip_eps=clip_eps, entropy_coef=entropy_coef, value_loss_coef=value_loss_coef,
+                                    max_batch=batch_size),
+                            hi=dict(lr=hi_lr, clip_eps=clip_eps, entropy_coef=hi_entropy_coef,
+                                    value_loss_coef=hi_value_coef, max_batch=hi_batch_size))
+            tenv.env.configure_skills(skill_len)          # the period skppo_publish hands on
+            tenv.skppo_publish()
 
     def _batches(self, total, size):
         order = torch.randperm(total, device=self.tenv.device, generator=self.gen)
         return [order[i:i + size] for i in range(0, total, size)]
 
     def collect(self):
-        """Reload the device agent from the modules, collect; (lo, hi, inverse, num_frames) of TorchZoneEnv."""
-        self.tenv.load_skills(self.hi_net.state_dict(), self.lo_net.state_dict(), skill_len=self.L)
+        """Reload the device agent from the modules (device_update: skppo_publish has), collect; (lo, hi, inverse,
+        num_frames) of TorchZoneEnv."""
+        if not self.device_update:
+            self.tenv.load_skills(self.hi_net.state_dict(), self.lo_net.state_dict(), skill_len=self.L)
         self.tenv.load_skill_inverse(self.inverse.state_dict(), self.S)
         out = self.tenv.collect_skills(self.T, policy_seed=self.seed * 1000003 + self.it, discount=self.discount,
                                        gae_lambda=self.gae_lambda, diversity_coef=self.diversity_coef,
@@ -215,9 +235,17 @@ class SkillPlannerPPO:
 
     def update(self, lo, hi, inverse):
         """The four updates on one collection (before the next collect overwrites its buffers)."""
-        logs = {"lo_" + k: v for k, v in self.update_lo_parameters(lo).items()}
-        if self.train_hi:
-            logs.update({"hi_" + k: v for k, v in self.update_hi_parameters(hi).items()})
+        if self.device_update:
+            logs = self.tenv.skppo_update(self.epochs, self.batch_size, self.hi_epochs if self.train_hi else 0,
+                                          self.hi_batch_size, self.rng)
+            self.tenv.skppo_publish()
+            hi_sd, lo_sd = self.tenv.skppo_state_dicts()  # the modules follow the learners
+            self.hi_net.load_state_dict(hi_sd)
+            self.lo_net.load_state_dict(lo_sd)
+        else:
+            logs = {"lo_" + k: v for k, v in self.update_lo_parameters(lo).items()}
+            if self.train_hi:
+                logs.update({"hi_" + k: v for k, v in self.update_hi_parameters(hi).items()})
         logs.update({"inverse_" + k: v for k, v in self.update_inverse_parameters(inverse).items()})
         logs.update({"prior_" + k: v for k, v in self.update_skill_prior(hi).items()})
         return logs
@@ -231,14 +259,15 @@ class SkillPlannerPPO:
 
 
 def train(env_id="PointTSP-v0", procs=4096, skill_len=20, frames_per_proc=100, updates=10, n_skills=5, hidden=128,
-          diversity_coef=0.1, seed=1, log=print, **kw):
+          diversity_coef=0.1, seed=1, log=print, device_update=False, **kw):
     torch.manual_seed(seed)
     env = Z.ZoneVecEnv(env_id, procs)
     env.build_bank(seed, 4 * procs)
     env.schedule_sequential(stride=procs)
     tenv = TorchZoneEnv(env)
     tenv.reset()
-    algo = SkillPlannerPPO(tenv, n_skills, hidden, skill_len, frames_per_proc, diversity_coef, seed=seed, **kw)
+    algo = SkillPlannerPPO(tenv, n_skills, hidden, skill_len, frames_per_proc, diversity_coef, seed=seed,
+                           device_update=device_update, **kw)
     for u in range(updates):
         t0 = time.perf_counter()
         logs = algo.iteration()
@@ -260,6 +289,8 @@ if __name__ == "__main__":
     ap.add_argument("--hidden-size", type=int, default=128)
     ap.add_argument("--diversity-coef", type=float, default=0.1)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--device-update", action="store_true",
+                    help="run the low and high level's PPO updates in the library (zenv_skppo_*) instead of torch")
     a = ap.parse_args()
     train(a.env, a.procs, a.skill_len, a.frames_per_proc, a.updates, a.n_skills, a.hidden_size, a.diversity_coef,
-          a.seed)
+          a.seed, device_update=a.device_update)

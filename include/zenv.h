@@ -183,7 +183,13 @@ enum {
      */
     ZENV_F_XYPPO_LO_STATS = 77,     /* float32 [minibatches][6] the low level's: ZENV_F_PPO_STATS' columns, value std = 0 */
     ZENV_F_XYPPO_HI_STATS = 78,     /* float32 [minibatches][6] the high level's, the same */
-    ZENV_F_COUNT = 79
+    /* the fixed-length-skills agent's two learners (zenv_skppo_init): the statistics of the minibatches of the level's
+     * last zenv_skppo_minibatch (one row) or zenv_skppo_epoch; 0 bytes before the first.  Before these two fields,
+     * ZENV_F_COUNT = 79
+     */
+    ZENV_F_SKPPO_LO_STATS = 79,     /* float32 [minibatches][6] the low level's: ZENV_F_PPO_STATS' columns, value std = 0 */
+    ZENV_F_SKPPO_HI_STATS = 80,     /* float32 [minibatches][6] the high level's, the same */
+    ZENV_F_COUNT = 81
 };
 
 /* scripted on-device action sources (the build's own; used by bench/tests) */
@@ -911,8 +917,9 @@ int zenv_collect_xy(zenv_t *h, int frames_per_proc, uint64_t policy_seed, uint64
  * reference's [N][T] flattening (base.py:212-227); the kernels read the time-major buffers in place.  The learner's
  * parameters are separate from the acting network's: nothing here repacks zenv_mlp_load's images (read the parameters
  * back and load them to act with them).  Every reduction runs in a fixed order: the same call from the same state
- * gives the same bits.  The Zone-goals agent's two updates are zenv_hppo_* below, the xy-goals agent's two zenv_xyppo_*;
- * the updates of the skill and Options agents are not here. */
+ * gives the same bits.  The Zone-goals agent's two updates are zenv_hppo_* below, the xy-goals agent's two zenv_xyppo_*,
+ * the fixed-length-skills agent's two zenv_skppo_*; the updates of DIAYN's inverse model and skill prior and of the
+ * Options agent are not here. */
 typedef struct zenv_ppo_config {
     double lr, adam_eps;            /* torch.optim.Adam(lr, eps = adam_eps), betas 0.9 / 0.999 */
     double clip_eps, entropy_coef, value_loss_coef, max_grad_norm;
@@ -1031,6 +1038,51 @@ int zenv_xyppo_set_step(zenv_t *h, int level, int64_t step);
 int zenv_xyppo_minibatch(zenv_t *h, int level, const int32_t *idx, int count, int idx_on_device, int apply);
 int zenv_xyppo_apply(zenv_t *h, int level);
 int zenv_xyppo_epoch(zenv_t *h, int level, const int32_t *order, int total, int batch_size, int on_device);
+
+/* ---- the fixed-length-skills agent's two PPO updates on the device: update_lo_parameters / update_hi_parameters,
+ * main/src/torch_ac/algos/_hier_policy_opt.py:265-419 ----
+ * Two more learners, each with its own four arenas, Adam step count, workspace and statistics; `level` 0 is the low
+ * level (LoPolicyValueModel), 1 the high level (HighPolicyValueModel), S = init->n_skills.  They read the records of the
+ * last zenv_collect_skill in place (DIAYN collects with the same call; its inverse model's and skill prior's updates
+ * stay with the caller):
+ *   low:   the flat learner's loss (a recorded log_prob per action component, the entropy's mean over both) on the
+ *          network of [obs, onehot(skill)] (8 + S inputs) whose actor.enc_.0.0 and critic.0 read [emb, onehot].  Sample
+ *          index i is env i / T, frame i % T of the ZENV_F_EXP_* buffers, all T frames; the skill is ZENV_F_LO_SKILL of
+ *          that frame and the one-hot is formed from it on the fly.
+ *   high:  the flat encoder and critic under logits = actor.discrete_.0(relu(actor.enc_.0.0(emb))),
+ *          Categorical(logits = log_softmax(logits)) over the S skills, unmasked, on row i of the ZENV_F_HI_* rows,
+ *          i in [0, M), M = N T / skill_len.  The action is the recorded skill (ZENV_F_HI_ACTION); ZENV_F_HI_LOG_PROB is
+ *          one float per row; the entropy is the mean over rows.  The clipped policy and value losses are the other
+ *          learners'.
+ * The reference takes the gradient norm and does not clip: max_grad_norm = +inf is accepted and gives a clip factor of
+ * exactly 1.  The arenas' order is zenv_skill_weights' member order, parameters() order of the modules: 16 tensors for
+ * the high level (hi_zone_w1 .. hi_critic_b2), 18 for the low level (lo_zone_w1 .. lo_critic_b2).  Neither touches the
+ * acting agent's weights: read the parameters back and zenv_skill_load them to act with them. */
+/* zenv_hppo_check's rules for either level, on the host alone: ZENV_E_ARG for h_dim outside 1 .. 191, n_skills outside
+ * 1 .. 32, a zone_feat other than zenv_zone_feat(cfg), a null tensor, a missing critic at either level,
+ * distributional_value != 0, a negative or non-finite hyper-parameter (max_grad_norm = +inf excepted), max_batch < 1, a
+ * workspace of 2^31 floats or more. */
+int zenv_skppo_check(const zenv_config *cfg, const zenv_skill_weights *init, const zenv_ppo_config *lo,
+                     const zenv_ppo_config *hi);
+/* Both learners from one set of weights (init->precision is not used).  A second call replaces them. */
+int zenv_skppo_init(zenv_t *h, const zenv_skill_weights *init, const zenv_ppo_config *lo, const zenv_ppo_config *hi);
+/* The flat functions with the level after the handle; their semantics are the flat functions'.  ZENV_E_ARG for a level
+ * other than 0 or 1; ZENV_E_STATE without zenv_skppo_init.  The update calls answer ZENV_E_STATE unless the handle's
+ * ZENV_F_EXP_* / ZENV_F_LO_* / ZENV_F_HI_* buffers hold a completed zenv_collect_skill's records of an agent with S skills
+ * (no collect yet, or another collector ran last); zenv_hppo_* and zenv_xyppo_* refuse these records in turn.
+ * Statistics: ZENV_F_SKPPO_LO_STATS / ZENV_F_SKPPO_HI_STATS.  A host index outside [0, N T) (low) or [0, M) (high) is
+ * ZENV_E_ARG; a device-resident one is never dereferenced: the sample is dropped as zenv_ppo_minibatch drops one, it adds
+ * nothing to the loss or to any gradient, and the next call that waits for the device answers ZENV_E_ARG once.  A
+ * recorded skill outside [0, S) -- a frame's ZENV_F_LO_SKILL or a row's ZENV_F_HI_ACTION -- drops its sample the same
+ * way. */
+int zenv_skppo_tensor(zenv_t *h, int level, int which, int index, void **dev_ptr, int64_t *count);
+int zenv_skppo_read(zenv_t *h, int level, int which, int index, float *dst);
+int zenv_skppo_write(zenv_t *h, int level, int which, int index, const float *src);
+int zenv_skppo_get_step(zenv_t *h, int level, int64_t *step);
+int zenv_skppo_set_step(zenv_t *h, int level, int64_t step);
+int zenv_skppo_minibatch(zenv_t *h, int level, const int32_t *idx, int count, int idx_on_device, int apply);
+int zenv_skppo_apply(zenv_t *h, int level);
+int zenv_skppo_epoch(zenv_t *h, int level, const int32_t *order, int total, int batch_size, int on_device);
 
 /* ---- results ---- */
 int zenv_get(zenv_t *h, int field, void *dst, int dst_on_device);
