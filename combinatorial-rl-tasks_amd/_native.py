@@ -47,7 +47,8 @@ E_ARG, E_HIP, E_STATE, E_LAYOUT, E_DONE, E_RANGE = -1, -2, -3, -4, -5, -6
  F_LO_TERM_ACTION, F_LO_TERM_LOG_PROB, F_LO_OPTION_ENDED,
  F_XY_GOAL, F_XY_GOAL_MU, F_XY_GOAL_STD, F_XY_VALUE, F_XY_GOAL_AGE,
  F_HI_GOAL, F_LO_GOAL_DIST, F_XY_BOOTSTRAP_GOAL, F_PPO_STATS, F_HPPO_LO_STATS, F_HPPO_HI_STATS,
- F_XYPPO_LO_STATS, F_XYPPO_HI_STATS, F_SKPPO_LO_STATS, F_SKPPO_HI_STATS) = range(81)
+ F_XYPPO_LO_STATS, F_XYPPO_HI_STATS, F_SKPPO_LO_STATS, F_SKPPO_HI_STATS, F_OPPPO_LO_STATS,
+ F_OPPPO_HI_STATS) = range(83)
 (RESULT_OBS, RESULT_REWARD, RESULT_DONE, RESULT_GOAL_MET, RESULT_EXCEPTION, RESULT_ZONE_OBS) = range(6)
 N_RESULTS = 6
 
@@ -133,6 +134,8 @@ XYPPO_LO, XYPPO_HI = 0, 1                                     # the `level` of t
 XYPPO_STATS_FIELDS = (F_XYPPO_LO_STATS, F_XYPPO_HI_STATS)     # by level
 SKPPO_LO, SKPPO_HI = 0, 1                                     # the `level` of the zenv_skppo_* functions
 SKPPO_STATS_FIELDS = (F_SKPPO_LO_STATS, F_SKPPO_HI_STATS)     # by level
+OPPPO_LO, OPPPO_HI = 0, 1                                     # the `level` of the zenv_opppo_* functions
+OPPPO_STATS_FIELDS = (F_OPPPO_LO_STATS, F_OPPPO_HI_STATS)     # by level
 
 
 class PpoConfig(C.Structure):
@@ -272,6 +275,16 @@ _PROTOTYPES = {
     "zenv_skppo_minibatch": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "zenv_skppo_apply": (C.c_int, [_H, C.c_int]),
     "zenv_skppo_epoch": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "zenv_opppo_check": (C.c_int, [C.POINTER(Config), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "zenv_opppo_init": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "zenv_opppo_tensor": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    "zenv_opppo_read": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "zenv_opppo_write": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "zenv_opppo_get_step": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int64)]),
+    "zenv_opppo_set_step": (C.c_int, [_H, C.c_int, C.c_int64]),
+    "zenv_opppo_minibatch": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "zenv_opppo_apply": (C.c_int, [_H, C.c_int]),
+    "zenv_opppo_epoch": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "zenv_get": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int]),
     "zenv_get_rows": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "zenv_device_ptr": (C.c_int, [_H, C.c_int, C.POINTER(C.c_void_p)]),

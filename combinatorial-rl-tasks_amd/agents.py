@@ -175,6 +175,14 @@ def skppo_state_dict_keys():
             {name: lo[name[3:]] for name in nat.SKILL_LO_TENSORS + nat.SKILL_LO_CRITIC})
 
 
+def opppo_state_dict_keys():
+    """(hi, lo): zenv_option_weights name -> state_dict key of every tensor the Options agent's two learners hold, in
+    their arenas' order -- 16 tensors of HighPolicyValueModel, 18 of LoPolicyValueModel (options/src/
+    hier_policy_value_models.py), critics included; the names are the skill planner's, actor.mu_ / actor.std_ have three
+    rows.  It is also each module's ``parameters()`` order, the order of torch Adam's state."""
+    return skppo_state_dict_keys()
+
+
 def hppo_batch_indexes(total, rng):
     """The sample order of one epoch of either level: _get_batches_starting_indexes_lo / _hi (zone-goals/src/torch_ac/
     algos/_hier_policy_opt.py:372-420) before it is cut into batches -- a plain permutation of range(total) from the

@@ -12,6 +12,9 @@
 // reads it and is never stored per zone row), with actor.enc_.0.0 and critic.0 reading [emb, onehot] from an embedding
 // buffer 32 columns wider (PpoNet::LDC); its high level is the flat encoder and critic under a Categorical over the S
 // skills (PPO_HEAD_SKILLS, k_skppo_hi_loss).
+// And the Options agent's two (options/src/torch_ac/algos/_hier_policy_opt.py:208-381): its high level is the skills
+// agent's on the rows of the transitions a collection closed, its low level the skills agent's with a third Gaussian
+// component (PpoNet::NA = 3) on frames 0 .. T-2, the third component's records read from buffers of their own.
 //
 // Every layer is a product on v_mfma_f32_32x32x2_f32, forward and backward, in one of two shapes:
 //
@@ -294,6 +297,8 @@ __global__ void k_ppo_prep(PpoNet n)
     // the skills agent's low level: actor.enc_.0.0 and critic.0 are [h][h + S] over [emb, onehot]; the onehot's columns
     // lie at HP .. HP + S of their images
     const int tail = n.LDC > HP ? n.S : 0;
+    // the Gaussian head's columns: NA of mu, NA of std, then the value (the distributional critic's sigma: 5, NA = 2)
+    const int NA = n.NA, vr = 2 * NA;
     // the critic's four tensors
     const float *cw1 = T(n.cr), *cb1 = T(n.cr + 1), *cw2 = T(n.cr + 2), *cb2 = T(n.cr + 3);
     float v = 0.f;
@@ -326,14 +331,15 @@ __global__ void k_ppo_prep(PpoNet n)
             if (r == 0 && c <= h) v = c < h ? T(PPO_ACTOR_W2)[c] : T(PPO_ACTOR_B2)[0];
         } else if (skills) {                          // rows 0 .. S: actor.discrete_.0
             if (r < n.S && c <= h) v = c < h ? T(PPO_ACTOR_W2)[(size_t)r * h + c] : T(PPO_ACTOR_B2)[r];
-        } else if (r < 4 && c <= h) {
-            const float *w = T(r < 2 ? PPO_MU_W : PPO_STD_W), *b = T(r < 2 ? PPO_MU_B : PPO_STD_B);
-            v = c < h ? w[(size_t)(r & 1) * h + c] : b[r & 1];
+        } else if (r < 2 * NA && c <= h) {            // rows 0 .. NA: actor.mu_, NA .. 2 NA: actor.std_
+            const float *w = T(r < NA ? PPO_MU_W : PPO_STD_W), *b = T(r < NA ? PPO_MU_B : PPO_STD_B);
+            const int o = r < NA ? r : r - NA;
+            v = c < h ? w[(size_t)o * h + c] : b[o];
         }
         break;
-    case PPO_I_HV:
-        if (c <= h && (r == 4 || (r == 5 && n.dist))) {
-            const float *w = r == 4 ? cw2 : T(PPO_SIGMA_W), *b = r == 4 ? cb2 : T(PPO_SIGMA_B);
+    case PPO_I_HV:                                    // row 2 NA: critic.2 (4 under the other two heads)
+        if (c <= h && (r == vr || (r == 5 && n.dist))) {
+            const float *w = r == vr ? cw2 : T(PPO_SIGMA_W), *b = r == vr ? cb2 : T(PPO_SIGMA_B);
             v = c < h ? w[c] : b[0];
         }
         break;
@@ -347,10 +353,10 @@ __global__ void k_ppo_prep(PpoNet n)
             if (r < h && c == 0) v = T(PPO_ACTOR_W2)[r];
         } else if (skills) {
             if (r < h && c < n.S) v = T(PPO_ACTOR_W2)[(size_t)c * h + r];
-        } else if (r < h && c < 4) v = T(c < 2 ? PPO_MU_W : PPO_STD_W)[(size_t)(c & 1) * h + r];
+        } else if (r < h && c < 2 * NA) v = T(c < NA ? PPO_MU_W : PPO_STD_W)[(size_t)(c < NA ? c : c - NA) * h + r];
         break;
     case PPO_T_HV:
-        if (r < h && (c == 4 || (c == 5 && n.dist))) v = (c == 4 ? cw2 : T(PPO_SIGMA_W))[r];
+        if (r < h && (c == vr || (c == 5 && n.dist))) v = (c == vr ? cw2 : T(PPO_SIGMA_W))[r];
         break;
     default: break;
     }
@@ -744,17 +750,25 @@ __global__ void k_skppo_hi_loss(PpoNet n, PpoExp x, Gather g, int bp)
 // rounded once, as the high level's is.  In float32 the head's own arithmetic (sigmoid, log_prob, ratio and the products
 // of the derivative) is the largest part of the error of the gradients of actor.mu_.bias and actor.std_.bias, two sums
 // over the minibatch that cancel to a tenth of their terms: 1e-8 .. 7e-8 at 96 samples, where float32 torch has
-// 5e-9 .. 8e-8 and the rounding of the pre-activations adds 1e-9 (DESIGN K15).  The five deltas also go to DZ [samples]
-// [5] before they are rounded: k_skppo_head_bias adds them up for the three head biases.  The flat learner's k_ppo_loss
-// stays as it is, and with it the bits of every other learner.
+// 5e-9 .. 8e-8 and the rounding of the pre-activations adds 1e-9 (DESIGN K15).  The 2 NA + 1 deltas also go to DZ
+// [samples][2 NA + 1] before they are rounded: k_skppo_head_bias adds them up for the three head biases.  The flat
+// learner's k_ppo_loss stays as it is, and with it the bits of every other learner.
 __device__ __forceinline__ double sigmoidd(double x) { return 1.0 / (1.0 + exp(-x)); }
 
+// NA: the action's components, 2 (the skills agent) or 3 (the Options agent, whose third component a_2 is recorded in
+// buffers of its own: PpoExp::term_action / term_log_prob [slot]).  The ratio is over all NA components, the entropy's
+// mean over count x NA; the head's columns are mu 0 .. NA, std NA .. 2 NA, the value 2 NA.  The NA = 2 instantiation is
+// K15's kernel operation for operation.
+template <int NA>
 __global__ void k_skppo_lo_loss(PpoNet n, PpoExp x, Gather g, int bp)
 {
+    constexpr int ND = 2 * NA + 1;
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= bp) return;
-    float d[6] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f }, ss[8] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
-    double dd[5] = { 0.0, 0.0, 0.0, 0.0, 0.0 };
+    float d[ND], ss[8] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
+    double dd[ND];
+#pragma unroll
+    for (int i = 0; i < ND; ++i) d[i] = 0.f, dd[i] = 0.0;
     size_t slot = 0;
     if (sample_slot(g, b, slot)) {
         const float *pre = n.PRE + (size_t)b * 32;
@@ -762,16 +776,20 @@ __global__ void k_skppo_lo_loss(PpoNet n, PpoExp x, Gather g, int bp)
         const double inv_b = 1.0 / (double)g.count, eps = (double)hy.clip_eps;
         const double adv = (double)x.advantage[slot], ret = (double)x.returnn[slot];
         const double half_log_2pi = 0.9189385332046727;
-        double sd[2], smu[2], ssd[2], diff[2], dlp = 0.0, ent = 0.0;
+        // the entropy's mean is over B x NA
+        const double ent_w = NA == 2 ? 0.5 * inv_b : inv_b / (double)NA;
+        double sd[NA], smu[NA], ssd[NA], diff[NA], dlp = 0.0, ent = 0.0;
 #pragma unroll
-        for (int o = 0; o < 2; ++o) {
+        for (int o = 0; o < NA; ++o) {
             smu[o] = sigmoidd((double)pre[o]);
-            ssd[o] = sigmoidd((double)pre[2 + o]);
+            ssd[o] = sigmoidd((double)pre[NA + o]);
             const double mu = 2.0 * (smu[o] - 0.5);               // policy_network.py:46-47
             sd[o] = ssd[o] + 1e-3;
-            diff[o] = (double)x.action[slot * 2 + o] - mu;
+            const float a = o < 2 ? x.action[slot * 2 + o] : x.term_action[slot];
+            const float old_lp = o < 2 ? x.log_prob[slot * 2 + o] : x.term_log_prob[slot];
+            diff[o] = (double)a - mu;
             const double lp = -(diff[o] * diff[o]) / (2.0 * (sd[o] * sd[o])) - log(sd[o]) - half_log_2pi;
-            dlp += lp - (double)x.log_prob[slot * 2 + o];
+            dlp += lp - (double)old_lp;
             ent += 0.5 + half_log_2pi + log(sd[o]);                // Normal.entropy
         }
         // clipped_policy and clipped_value in double: comparisons, so that a NaN ratio or value gives a NaN loss
@@ -780,32 +798,32 @@ __global__ void k_skppo_lo_loss(PpoNet n, PpoExp x, Gather g, int bp)
         const double through = surr1 <= surr2 ? 1.0 : (ratio >= lo && ratio <= hi) ? 1.0 : 0.0;
         const double g_lp = -adv * inv_b * through * ratio;
 #pragma unroll
-        for (int o = 0; o < 2; ++o) {
+        for (int o = 0; o < NA; ++o) {
             const double var = sd[o] * sd[o];
             const double g_mu = g_lp * (diff[o] / var);
             const double g_sd = g_lp * ((diff[o] * diff[o]) / (var * sd[o]) - 1.0 / sd[o])
-                                - (double)hy.entropy_coef * (0.5 * inv_b) / sd[o];  // the entropy's mean is over B x 2
+                                - (double)hy.entropy_coef * ent_w / sd[o];
             dd[o] = g_mu * 2.0 * smu[o] * (1.0 - smu[o]);
-            dd[2 + o] = g_sd * ssd[o] * (1.0 - ssd[o]);
+            dd[NA + o] = g_sd * ssd[o] * (1.0 - ssd[o]);
         }
-        const double v = (double)pre[4], old = (double)x.value[slot], dv = v - old;
+        const double v = (double)pre[2 * NA], old = (double)x.value[slot], dv = v - old;
         const double vc = old + (dv < -eps ? -eps : dv > eps ? eps : dv);
         const double s1 = (v - ret) * (v - ret), s2 = (vc - ret) * (vc - ret);
         const bool inside = dv >= -eps && dv <= eps;
         const double dl = s1 >= s2 ? 2.0 * (v - ret) : inside ? 2.0 * (vc - ret) : 0.0;
-        dd[4] = (double)hy.value_loss_coef * inv_b * dl;
+        dd[2 * NA] = (double)hy.value_loss_coef * inv_b * dl;
 #pragma unroll
-        for (int i = 0; i < 5; ++i) d[i] = (float)dd[i];
+        for (int i = 0; i < ND; ++i) d[i] = (float)dd[i];
         ss[0] = (float)ent;
-        ss[1] = pre[4];
+        ss[1] = pre[2 * NA];
         ss[3] = (float)(-(surr1 <= surr2 ? surr1 : surr2));
         ss[4] = (float)(s1 >= s2 ? s1 : s2);
     }
 #pragma unroll
-    for (int i = 0; i < 5; ++i) n.DZ[(size_t)b * 5 + i] = dd[i];
+    for (int i = 0; i < ND; ++i) n.DZ[(size_t)b * ND + i] = dd[i];
     float *dh = n.DH + (size_t)b * 32;
 #pragma unroll
-    for (int i = 0; i < 32; ++i) dh[i] = i < 6 ? d[i] : 0.f;
+    for (int i = 0; i < 32; ++i) dh[i] = i < ND ? d[i] : 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) n.SS[(size_t)b * 8 + i] = ss[i];
 }
@@ -841,24 +859,26 @@ __device__ __forceinline__ double block_sum_256(double v, double *sh)
 // The skills agent's low level: the gradients of actor.mu_.bias, actor.std_.bias and critic.2.bias are the sums of the
 // head's deltas over the minibatch.  As column h of a float32 product the sum of deltas that are each of order 1 where the
 // policy's std is small, and cancel, carried 1e-7 of rounding into gradients of 0.1; so the sums run over the unrounded
-// deltas (DZ, k_skppo_lo_loss), in double, in a fixed order, and are rounded once.  Block c of 256 threads: delta c.
+// deltas (DZ, k_skppo_lo_loss), in double, in a fixed order, and are rounded once.  Block c of 256 threads: delta c of
+// the 2 NA + 1 (NA mu, NA std, critic.2.bias).
 __global__ __launch_bounds__(256) void k_skppo_head_bias(PpoNet n, int bp)
 {
     __shared__ double sh[256];
     const int c = blockIdx.x;
     double s = 0.0;
-    for (int b = threadIdx.x; b < bp; b += 256) s += n.DZ[(size_t)b * 5 + c];
+    const int NA = n.NA, ND = 2 * NA + 1;
+    for (int b = threadIdx.x; b < bp; b += 256) s += n.DZ[(size_t)b * ND + c];
     s = block_sum_256(s, sh);
     if (threadIdx.x == 0) {
-        float *dst = c < 2 ? n.grad + n.off[PPO_MU_B] + c : c < 4 ? n.grad + n.off[PPO_STD_B] + (c - 2)
-                                                                  : n.grad + n.off[n.cr + 3];
+        float *dst = c < NA ? n.grad + n.off[PPO_MU_B] + c : c < 2 * NA ? n.grad + n.off[PPO_STD_B] + (c - NA)
+                                                                        : n.grad + n.off[n.cr + 3];
         *dst = (float)s;
     }
 }
 
 // stats[0..4] = the minibatch means of the per-sample terms; one block of 256 threads, thread i adds samples i, i + 256 ...
-// ent_terms: the entropy's mean is over count x 2 action components, or over count categoricals or rows whose two
-// components' entropies are already summed (k_xyppo_hi_loss).  zero_grad (or null):
+// ent_terms: the entropy's mean is over count x 2 (the Options agent's low level: 3) action components, or over count
+// categoricals or rows whose two components' entropies are already summed (k_xyppo_hi_loss).  zero_grad (or null):
 // a gradient that is 0 for every input -- PPO_HEAD_ZONES: actor.2.bias', see k_hppo_loss
 __global__ __launch_bounds__(256) void k_ppo_stats(const float *__restrict__ SS, int count, double ent_terms,
                                                    float *__restrict__ stats, float *__restrict__ zero_grad)
@@ -963,6 +983,7 @@ void gaussian_head(const PpoNet &n, const PpoExp &x, const Gather &g, int bp, fl
     const int h = n.h, HP = n.HP, NT = HP / 32, cr = n.cr, LDC = n.LDC;
     // the skills agent's low level: C is [emb | onehot(skill)] and actor.enc_.0.0 / critic.0 are [h][h + S]
     const int tail = LDC > HP ? n.S : 0, ldw = h + tail;
+    const int NA = n.NA;        // the action's components: mu in columns 0 .. NA of PRE / DH, std NA .. 2 NA, the value 2 NA
     float *const *I = n.img;
     if (tail) hipLaunchKernelGGL(k_skppo_onehot, dim3((bp * 32 + 255) / 256), dim3(256), 0, s, n, g, bp);
     nt<NT_RELU>(I[PPO_I_WE], LDC, n.C, LDC, LDC, n.Ha, HP, bp, NT, s);                    // relu(actor.enc_)
@@ -973,20 +994,21 @@ void gaussian_head(const PpoNet &n, const PpoExp &x, const Gather &g, int bp, fl
         hipLaunchKernelGGL(k_xyppo_hi_loss, dim3((bp + 63) / 64), dim3(64), 0, s, n, x, g, bp);
         hipLaunchKernelGGL(k_ppo_stats, dim3(1), dim3(256), 0, s, n.SS, g.count, 1.0, stats, (float *)nullptr);
     } else {
-        if (tail) hipLaunchKernelGGL(k_skppo_lo_loss, dim3((bp + 63) / 64), dim3(64), 0, s, n, x, g, bp);
+        if (tail && NA == 3) hipLaunchKernelGGL(k_skppo_lo_loss<3>, dim3((bp + 63) / 64), dim3(64), 0, s, n, x, g, bp);
+        else if (tail) hipLaunchKernelGGL(k_skppo_lo_loss<2>, dim3((bp + 63) / 64), dim3(64), 0, s, n, x, g, bp);
         else hipLaunchKernelGGL(k_ppo_loss, dim3((bp + 63) / 64), dim3(64), 0, s, n, x, g, bp);
-        hipLaunchKernelGGL(k_ppo_stats, dim3(1), dim3(256), 0, s, n.SS, g.count, 2.0, stats, (float *)nullptr);
+        hipLaunchKernelGGL(k_ppo_stats, dim3(1), dim3(256), 0, s, n.SS, g.count, (double)NA, stats, (float *)nullptr);
     }
     // ---- backward: every weight gradient is taken before its layer's activations are overwritten by deltas
     tn(n.DH, 32, 1, n.Ha, HP, HP, bp, n.partial, s);
-    reduce(n, bp, 1, HP, 0, 0, PPO_MU_W, h, 0, 2, h, s);
-    if (!tail) reduce(n, bp, 1, HP, 0, h, PPO_MU_B, 1, 0, 2, 1, s);
-    reduce(n, bp, 1, HP, 2, 0, PPO_STD_W, h, 0, 2, h, s);
-    if (!tail) reduce(n, bp, 1, HP, 2, h, PPO_STD_B, 1, 0, 2, 1, s);
+    reduce(n, bp, 1, HP, 0, 0, PPO_MU_W, h, 0, NA, h, s);
+    if (!tail) reduce(n, bp, 1, HP, 0, h, PPO_MU_B, 1, 0, NA, 1, s);
+    reduce(n, bp, 1, HP, NA, 0, PPO_STD_W, h, 0, NA, h, s);
+    if (!tail) reduce(n, bp, 1, HP, NA, h, PPO_STD_B, 1, 0, NA, 1, s);
     tn(n.DH, 32, 1, n.Hc, HP, HP, bp, n.partial, s);
-    reduce(n, bp, 1, HP, 4, 0, cr + 2, h, 0, 1, h, s);
-    if (!tail) reduce(n, bp, 1, HP, 4, h, cr + 3, 1, 0, 1, 1, s);
-    else hipLaunchKernelGGL(k_skppo_head_bias, dim3(5), dim3(256), 0, s, n, bp);          // the three head biases
+    reduce(n, bp, 1, HP, 2 * NA, 0, cr + 2, h, 0, 1, h, s);
+    if (!tail) reduce(n, bp, 1, HP, 2 * NA, h, cr + 3, 1, 0, 1, 1, s);
+    else hipLaunchKernelGGL(k_skppo_head_bias, dim3(2 * NA + 1), dim3(256), 0, s, n, bp); // the three head biases
     if (n.dist) {
         reduce(n, bp, 1, HP, 5, 0, PPO_SIGMA_W, h, 0, 1, h, s);
         reduce(n, bp, 1, HP, 5, h, PPO_SIGMA_B, 1, 0, 1, 1, s);

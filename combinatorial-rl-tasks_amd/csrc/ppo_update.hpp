@@ -1,5 +1,6 @@
 // ppo_update.hpp -- the PPO updates on the device (ppo_update.hip): the flat actor-critic's, the Zone-goals agent's two
-// levels', the xy-goals agent's two levels' and the fixed-length-skills agent's two levels'.  What zenv_train.cpp hands to the launches.  Internal: not installed.
+// levels', the xy-goals agent's two levels', the fixed-length-skills agent's two levels' and the Options agent's two
+// levels'.  What zenv_train.cpp hands to the launches.  Internal: not installed.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -45,7 +46,11 @@ struct PpoNet {
                              // K1 = XD + F
     int W1C;                 // columns of zone_net_.0's image and gathered input: XD + F + 1 rounded up to 8; the last is
                              // the constant that carries the bias.  KC = HP + XD rounded up to 8
-    int S;                   // the fixed-length-skills agent's learners: the number of skills (1 .. 32); 0 for every other
+    int S;                   // the fixed-length-skills and Options agents' learners: the number of skills (1 .. 32); 0 for
+                             // every other
+    int NA;                  // the Gaussian head's action components: 2, or 3 for the Options agent's low level, whose
+                             // third, a_2, decides whether the option ends.  PRE / DH hold mu in columns 0 .. NA, std in
+                             // NA .. 2 NA and the value in 2 NA (4 under every other head)
     int LDC;                 // the leading dimension of C and of the images of actor.enc_.0.0 and critic.0: HP, or HP + 32
                              // for the skills agent's low level, whose columns HP .. HP + S hold onehot(skill)
     int head;                // PPO_HEAD_GAUSSIAN: enc_, mu_, std_;  PPO_HEAD_ZONES: actor.0 / actor.2 over [emb, zone row];
@@ -63,12 +68,13 @@ struct PpoNet {
     float *A1, *A2;          // [rows][HP], rows = samples x Z rounded up to 32
     float *P, *C, *Ha, *Hc;  // [samples][HP] (C: [samples][LDC]), samples rounded up to 32
     float *CI;               // [samples][KC]: zone_net_.4's output (HP columns), then the XD own features
-    float *PRE, *DH;         // [samples][32]: the six head pre-activations, their deltas
+    float *PRE, *DH;         // [samples][32]: the six (NA = 3: seven) head pre-activations, their deltas
     // PPO_HEAD_ZONES only: relu(actor.0) of every zone row [rows][HP], the logits and their deltas [rows][32] (column 0)
     // PPO_HEAD_SKILLS: L, DL are the S logits of a sample and their deltas [samples][32]; the value stays in PRE / DH
     float *U, *L, *DL;
     double *DZ;              // [rows]: the logits' deltas as k_hppo_loss forms them, before they are rounded into DL;
-                             // the skills agent's low level: [samples][5], the head's deltas before they are rounded
+                             // the skills / Options agents' low level: [samples][2 NA + 1], the head's deltas before they
+                             // are rounded
     float *SS;               // [samples][8]: the per-sample terms of the statistics
     float *partial;          // the per-chunk partials of one weight gradient
     double *norm_partial;    // [arena / kPpoNormBlock + 1]
@@ -90,6 +96,8 @@ struct PpoExp {
     const int32_t *hi_action;       // PPO_HEAD_ZONES: the recorded goal [slot] and the goals available at the pick;
     const uint8_t *hi_mask;         // [slot][Z].  PPO_HEAD_SKILLS: the recorded skill [slot], no mask
     const int32_t *skill = nullptr; // [slot]: the skill a frame was acted under (XD = 8 + S only)
+    // NA = 3: the third action component and its recorded log_prob [slot]; components 0-1 stay in action / log_prob [slot][2]
+    const float *term_action = nullptr, *term_log_prob = nullptr;
 };
 
 // forward, loss and backward of the samples idx[0 .. count) (device memory): gradients into net.grad, the six

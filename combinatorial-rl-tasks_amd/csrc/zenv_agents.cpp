@@ -665,6 +665,7 @@ static int ensure_exp(zenv_t *h, int T)
     h->exp_hier = false;        // zenv_collect_hier sets it once its records are complete
     h->exp_xy = false;          // zenv_collect_xy, the same
     h->exp_skill = false;       // zenv_collect_skill, the same
+    h->exp_option = false;      // zenv_collect_option, the same
     if (!h->exp_mem || h->exp.T != T) {
         HIP_TRY(hipStreamSynchronize(h->stream));
         std::vector<float> keep_mask;
@@ -1186,6 +1187,7 @@ extern "C" int zenv_collect_option(zenv_t *h, int T, uint64_t policy_seed, uint6
     HIP_TRY(launch_hier_gather(rows, c, h->exp.obs, h->exp.zone_obs, M, h->n_env, h->p.Z, h->p.F, h->stream));
     HIP_TRY(launch_hier_carry(c, h->exp.obs, h->exp.zone_obs, h->n_env, (int)ZF, h->stream));
     h->hi_m = M;
+    h->exp_option = true;
     if (n_hi) *n_hi = M;
     return ZENV_OK;
 }

@@ -251,7 +251,9 @@ FieldInfo field_info(const zenv *h, int field)
     case ZENV_F_XYPPO_LO_STATS:
     case ZENV_F_XYPPO_HI_STATS:
     case ZENV_F_SKPPO_LO_STATS:
-    case ZENV_F_SKPPO_HI_STATS: {       // seven consecutive fields, ppo_stats' order
+    case ZENV_F_SKPPO_HI_STATS:
+    case ZENV_F_OPPPO_LO_STATS:
+    case ZENV_F_OPPPO_HI_STATS: {       // nine consecutive fields, ppo_stats' order
         int64_t bytes = 0;
         void *ptr = ppo_stats(h, field - ZENV_F_PPO_STATS, &bytes);
         return { ptr, bytes };

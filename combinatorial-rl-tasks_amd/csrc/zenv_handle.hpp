@@ -156,6 +156,8 @@ struct zenv {
     PpoState *xyppo[2] = { nullptr, nullptr };
     // the fixed-length-skills agent's two learners (zenv_skppo_init): [0] the low level, [1] the high level
     PpoState *skppo[2] = { nullptr, nullptr };
+    // the Options agent's two learners (zenv_opppo_init): [0] the low level, [1] the high level
+    PpoState *opppo[2] = { nullptr, nullptr };
     // goal-conditioned variant (zenv_goal_enable)
     bool goal_enabled = false;
     bool order_enabled = false;   // solver-ordered variant (zenv_order_enable)
@@ -166,6 +168,7 @@ struct zenv {
     bool exp_hier = false;              // the ZENV_F_EXP_* buffers hold zenv_collect_hier's frames (any other collector clears it)
     bool exp_xy = false;                // ... zenv_collect_xy's, the same
     bool exp_skill = false;             // ... zenv_collect_skill's, the same
+    bool exp_option = false;            // ... zenv_collect_option's, the same
     // zenv_collect_hier: the per-frame records of one call (T), the state that lives from call to call, the flat
     // high-level output (capacity hi_cap rows, hi_m of them written by the last call)
     HierFrames hframes{};
@@ -218,6 +221,6 @@ ZENV_INTERNAL void ppo_free(zenv *h);
 // ZENV_E_ARG once an update has met (and dropped) a device-resident index out of range; mlp_range_check() asks
 ZENV_INTERNAL int ppo_index_check(zenv *h);
 // ZENV_F_PPO_STATS (which = 0), ZENV_F_HPPO_LO_STATS (1), ZENV_F_HPPO_HI_STATS (2), ZENV_F_XYPPO_LO_STATS (3),
-// ZENV_F_XYPPO_HI_STATS (4), ZENV_F_SKPPO_LO_STATS (5), ZENV_F_SKPPO_HI_STATS (6): the buffer and the bytes the last
-// update call of that learner filled
+// ZENV_F_XYPPO_HI_STATS (4), ZENV_F_SKPPO_LO_STATS (5), ZENV_F_SKPPO_HI_STATS (6), ZENV_F_OPPPO_LO_STATS (7),
+// ZENV_F_OPPPO_HI_STATS (8): the buffer and the bytes the last update call of that learner filled
 ZENV_INTERNAL void *ppo_stats(const zenv *h, int which, int64_t *bytes);

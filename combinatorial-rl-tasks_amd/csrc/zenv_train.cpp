@@ -1,7 +1,8 @@
 // zenv_train.cpp -- the learners behind the C ABI of include/zenv.h: the flat actor-critic's PPO update on the handle's own
 // experience buffers (zenv_ppo_*) and the Zone-goals agent's two (zenv_hppo_*, level 0 = low, 1 = high) on the records
 // of zenv_collect_hier, the xy-goals agent's two (zenv_xyppo_*, the same levels) on the records of zenv_collect_xy, and
-// the fixed-length-skills agent's two (zenv_skppo_*) on the records of zenv_collect_skill.
+// the fixed-length-skills agent's two (zenv_skppo_*) on the records of zenv_collect_skill, and the Options agent's two
+// (zenv_opppo_*) on the records of zenv_collect_option.
 // One PpoState each, the same code.  The kernels: ppo_update.hip.  The networks that act and collect: zenv_agents.cpp.
 #include <algorithm>
 #include <cmath>
@@ -19,7 +20,8 @@ struct PpoState {
     double lr = 0.0;
     int32_t *idx = nullptr;         // host indices, uploaded
     size_t idx_cap = 0;
-    float *stats = nullptr;         // ZENV_F_PPO_STATS / ZENV_F_HPPO_*_STATS / ZENV_F_XYPPO_*_STATS / ZENV_F_SKPPO_*_STATS
+    float *stats = nullptr;         // ZENV_F_PPO_STATS / ZENV_F_HPPO_*_STATS / ZENV_F_XYPPO_*_STATS / ZENV_F_SKPPO_*_STATS /
+                                    // ZENV_F_OPPPO_*_STATS
                                     // [stats_cap][6]
     int stats_cap = 0, stats_rows = 0;
 };
@@ -29,7 +31,8 @@ namespace {
 // which network a learner trains: the width of its per-sample input, its head and what the head's loss is taken of
 struct NetKind {
     int XD, head, loss;
-    int S = 0;                      // the fixed-length-skills agent's learners: the number of skills
+    int S = 0;                      // the fixed-length-skills and Options agents' learners: the number of skills
+    int NA = 2;                     // the Gaussian head's action components: 3 for the Options agent's low level
     // XD + F + 1 <= 16 / 18 columns, rounded up to 8; the skills agent's low level: 8 + S + F + 1 <= 48 of them
     int w1c(int F) const { return S && XD > 8 ? (XD + F + 1 + 7) / 8 * 8 : XD == 8 ? 16 : 24; }
     // the skills agent's low level: actor.enc_.0.0 and critic.0 read [emb, onehot], S columns more
@@ -44,15 +47,18 @@ constexpr NetKind kXyLo = kHierLo, kXyHi{ 8, PPO_HEAD_GAUSSIAN, PPO_LOSS_JOINT_G
 // the fixed-length-skills agent: the Gaussian network on [obs, onehot(skill)], and the flat encoder under a Categorical
 NetKind sk_lo(int S) { return NetKind{ 8 + S, PPO_HEAD_GAUSSIAN, PPO_LOSS_ACTION, S }; }
 NetKind sk_hi(int S) { return NetKind{ 8, PPO_HEAD_SKILLS, PPO_LOSS_ACTION, S }; }
+// the Options agent: the skills agent's high level as it stands (sk_hi), its low level with a third action component
+NetKind op_lo(int S) { return NetKind{ 8 + S, PPO_HEAD_GAUSSIAN, PPO_LOSS_ACTION, S, 3 }; }
 
 // element counts of the tensors for hidden size h and zone rows of F features: zenv_mlp_weights' member order (20; the
 // Zone-goals low level's 18 with XD = 10; the skills agent's low level's 18 with XD = 8 + S and [h, h + S] in
-// actor.enc_.0.0 and critic.0), or the 16 of zenv_hier_weights' hi_* members, or the 16 of zenv_skill_weights'
+// actor.enc_.0.0 and critic.0; the Options agent's the same with [3, h] / [3] in actor.mu_ / actor.std_), or the 16 of
+// zenv_hier_weights' hi_* members, or the 16 of zenv_skill_weights' / zenv_option_weights'
 void tensor_counts(int h, int F, NetKind k, int64_t (&count)[PPO_MAX_TENSORS])
 {
-    const int64_t hh = (int64_t)h * h, X = k.XD, he = (int64_t)h * (h + k.tail()), S = k.S;
-    const int64_t c[PPO_MAX_TENSORS] = { h * (X + F), h, hh, h, hh, h, h * (X + h), h, he, h, 2 * h, 2,
-                                         2 * h, 2, he, h, h, 1, h, 1 };
+    const int64_t hh = (int64_t)h * h, X = k.XD, he = (int64_t)h * (h + k.tail()), S = k.S, A = k.NA;
+    const int64_t c[PPO_MAX_TENSORS] = { h * (X + F), h, hh, h, hh, h, h * (X + h), h, he, h, A * h, A,
+                                         A * h, A, he, h, h, 1, h, 1 };
     const int64_t z[PPO_MAX_TENSORS] = { h * (X + F), h, hh, h, hh, h, h * (X + h), h, (int64_t)h * (h + F), h, h, 1,
                                          hh, h, h, 1, 0, 0, 0, 0 };
     const int64_t d[PPO_MAX_TENSORS] = { h * (X + F), h, hh, h, hh, h, h * (X + h), h, hh, h, S * h, S,
@@ -105,8 +111,9 @@ Layout layout_for(int h, int Z, int F, int max_batch, NetKind k)
     l.partial = l.chunks * HP * std::max<int64_t>(HP + 32, (KC + 31) / 32 * 32);
     if (k.head == PPO_HEAD_ZONES) l.u = rp * HP, l.l = rp * 32;
     if (k.head == PPO_HEAD_SKILLS) l.l = bp * 32;       // the S logits of a sample, their deltas
-    // DZ, in floats: a double per zone row (the per-zone head), or five per sample (the skills agent's low level)
-    l.dz = k.tail() ? bp * 10 : l.l / 16;
+    // DZ, in floats: a double per zone row (the per-zone head), or 2 NA + 1 per sample (the skills and Options agents' low
+    // level)
+    l.dz = k.tail() ? bp * 2 * (2 * k.NA + 1) : l.l / 16;
     l.total = 2 * l.a1 + 3 * l.p + l.c + l.ci + 2 * l.pre + l.ss + l.partial + l.u + 2 * l.l + l.dz;
     for (int i = 0; i < PPO_N_IMAGES; ++i) l.total += l.img[i];
     return l;
@@ -170,8 +177,9 @@ void xy_tensor_lists(const zenv_xy_weights *w, const float *(&lo)[PPO_MAX_TENSOR
     std::copy(u, u + PPO_MAX_TENSORS, hi);
 }
 
-void skill_tensor_lists(const zenv_skill_weights *w, const float *(&lo)[PPO_MAX_TENSORS],
-                        const float *(&hi)[PPO_MAX_TENSORS])
+// W: zenv_skill_weights or zenv_option_weights, the same members
+template <class W>
+void skill_tensor_lists(const W *w, const float *(&lo)[PPO_MAX_TENSORS], const float *(&hi)[PPO_MAX_TENSORS])
 {
     const float *l[PPO_MAX_TENSORS] = { w->lo_zone_w1, w->lo_zone_b1, w->lo_zone_w2, w->lo_zone_b2, w->lo_zone_w3,
                                         w->lo_zone_b3, w->lo_comb_w, w->lo_comb_b, w->lo_enc_w, w->lo_enc_b, w->lo_mu_w,
@@ -239,6 +247,20 @@ extern "C" int zenv_skppo_check(const zenv_config *cfg, const zenv_skill_weights
     return learner_check(cfg, w->h_dim, th, sk_hi(w->n_skills), hi, "high level: ");
 }
 
+extern "C" int zenv_opppo_check(const zenv_config *cfg, const zenv_option_weights *w, const zenv_ppo_config *lo,
+                                const zenv_ppo_config *hi)
+{
+    if (!cfg || !w || !lo || !hi) return fail(ZENV_E_ARG, "null argument");
+    if (w->n_skills < 1 || w->n_skills > kMaxSkills)
+        return fail(ZENV_E_ARG, "n_skills %d outside [1, %d]", w->n_skills, kMaxSkills);
+    if (w->zone_feat != zenv_zone_feat(cfg))
+        return fail(ZENV_E_ARG, "zone_feat %d: the handle's zone rows have %d features", w->zone_feat, zenv_zone_feat(cfg));
+    const float *tl[PPO_MAX_TENSORS], *th[PPO_MAX_TENSORS];
+    skill_tensor_lists(w, tl, th);
+    if (int rc = learner_check(cfg, w->h_dim, tl, op_lo(w->n_skills), lo, "low level: ")) return rc;
+    return learner_check(cfg, w->h_dim, th, sk_hi(w->n_skills), hi, "high level: ");
+}
+
 static void learner_free(PpoState *&s)
 {
     if (!s) return;
@@ -258,12 +280,15 @@ void ppo_free(zenv *h)
     learner_free(h->xyppo[1]);
     learner_free(h->skppo[0]);
     learner_free(h->skppo[1]);
+    learner_free(h->opppo[0]);
+    learner_free(h->opppo[1]);
 }
 
 int ppo_index_check(zenv *h)
 {
     bool bad = false;
-    for (PpoState *s : { h->ppo, h->hppo[0], h->hppo[1], h->xyppo[0], h->xyppo[1], h->skppo[0], h->skppo[1] })
+    for (PpoState *s : { h->ppo, h->hppo[0], h->hppo[1], h->xyppo[0], h->xyppo[1], h->skppo[0], h->skppo[1],
+                          h->opppo[0], h->opppo[1] })
         if (s && s->net.bad_index && *(volatile int *)s->net.bad_index) {
             *(volatile int *)s->net.bad_index = 0;
             bad = true;
@@ -277,7 +302,7 @@ int ppo_index_check(zenv *h)
 void *ppo_stats(const zenv *h, int which, int64_t *bytes)
 {
     const PpoState *s = which == 0 ? h->ppo : which <= 2 ? h->hppo[which - 1] : which <= 4 ? h->xyppo[which - 3]
-                                                                                            : h->skppo[which - 5];
+                                                 : which <= 6 ? h->skppo[which - 5] : h->opppo[which - 7];
     *bytes = s ? (int64_t)s->stats_rows * kPpoStats * 4 : 0;
     return s ? s->stats : nullptr;
 }
@@ -293,7 +318,7 @@ static int learner_create(zenv *h, PpoState *&slot, int h_dim, const float *cons
     PpoNet &n = s->net;
     const Layout l = layout_for(h_dim, h->p.Z, h->p.F, pc->max_batch, k);
     n.h = h_dim, n.HP = l.HP, n.F = h->p.F, n.Z = h->p.Z, n.K1 = k.XD + h->p.F, n.KC = l.KC;
-    n.XD = k.XD, n.W1C = k.w1c(h->p.F), n.head = k.head, n.loss = k.loss, n.S = k.S, n.LDC = l.LDC;
+    n.XD = k.XD, n.W1C = k.w1c(h->p.F), n.head = k.head, n.loss = k.loss, n.S = k.S, n.NA = k.NA, n.LDC = l.LDC;
     n.cr = k.head != PPO_HEAD_GAUSSIAN ? PPO_CRITIC_W1 - 2 : PPO_CRITIC_W1;
     n.split_reduce = k.flat() ? 0 : 1;                  // the hierarchical agents' learners
     n.dist = pc->distributional_value ? 1 : 0;
@@ -399,9 +424,25 @@ extern "C" int zenv_skppo_init(zenv_t *h, const zenv_skill_weights *w, const zen
     return rc;
 }
 
+extern "C" int zenv_opppo_init(zenv_t *h, const zenv_option_weights *w, const zenv_ppo_config *lo,
+                               const zenv_ppo_config *hi)
+{
+    if (!h || !w || !lo || !hi) return fail(ZENV_E_ARG, "null argument");
+    if (int rc = zenv_opppo_check(&h->cfg, w, lo, hi)) return rc;
+    const float *tl[PPO_MAX_TENSORS], *th[PPO_MAX_TENSORS];
+    skill_tensor_lists(w, tl, th);
+    int rc = learner_create(h, h->opppo[0], w->h_dim, tl, op_lo(w->n_skills), lo);
+    if (!rc) rc = learner_create(h, h->opppo[1], w->h_dim, th, sk_hi(w->n_skills), hi);
+    if (rc) {                   // no half-pair
+        learner_free(h->opppo[0]);
+        learner_free(h->opppo[1]);
+    }
+    return rc;
+}
+
 namespace {
 
-enum { AGENT_FLAT = 0, AGENT_HIER = 1, AGENT_XY = 2, AGENT_SKILL = 3 };
+enum { AGENT_FLAT = 0, AGENT_HIER = 1, AGENT_XY = 2, AGENT_SKILL = 3, AGENT_OPTION = 4 };
 
 // What an entry point works on: the flat learner, or level 0 / 1 of the Zone-goals or the xy-goals pair with the
 // experience they read.
@@ -429,6 +470,11 @@ int find_learner(zenv *h, int level, int agent, Learner &out)
     if (agent == AGENT_SKILL) {
         if (!h->skppo[level]) return fail(ZENV_E_STATE, "zenv_skppo_init first");
         out = Learner{ h->skppo[level], level, AGENT_SKILL };
+        return ZENV_OK;
+    }
+    if (agent == AGENT_OPTION) {
+        if (!h->opppo[level]) return fail(ZENV_E_STATE, "zenv_opppo_init first");
+        out = Learner{ h->opppo[level], level, AGENT_OPTION };
         return ZENV_OK;
     }
     if (!h->hppo[level]) return fail(ZENV_E_STATE, "zenv_hppo_init first");
@@ -512,6 +558,27 @@ int learner_exp(const zenv *h, const Learner &l, PpoExp &x, int64_t &samples)
             return ZENV_OK;
         }
         // the dense env-major rows of the windows: M = N T / skill_len, the skill as the action, one log_prob per row
+        const HierOut &o = h->hout;
+        x = PpoExp{ o.obs, o.zone_obs, nullptr, o.log_prob, o.value, o.advantage, o.returnn, (int)h->hi_m, 1, nullptr,
+                    o.action, nullptr, nullptr };
+        samples = h->hi_m;
+        return ZENV_OK;
+    }
+    if (l.agent == AGENT_OPTION) {
+        if (!h->exp_mem || !h->exp_option || h->hi_kind != 2 || !h->oc_mem || h->oc.T != e.T)
+            return fail(ZENV_E_STATE, "zenv_collect_option first: the ZENV_F_EXP_* / ZENV_F_LO_* / ZENV_F_HI_* buffers do "
+                                      "not hold its records");
+        if (!h->option_ready || h->skill.S != l.s->net.S)
+            return fail(ZENV_E_STATE, "the records are of an agent with another number of skills than the learner's %d",
+                        l.s->net.S);
+        if (l.level == 0) {     // frames 0 .. T-2 of every env (_hier_policy_opt.py:111-118); a_2's records are the oc ones
+            x = PpoExp{ e.obs, e.zone_obs, e.action, e.log_prob, e.value, e.advantage, e.returnn, h->n_env, e.T - 1, nullptr,
+                        nullptr, nullptr, h->oc.lo_skill, h->oc.term_action, h->oc.term_log_prob };
+            samples = (int64_t)h->n_env * (e.T - 1);
+            return ZENV_OK;
+        }
+        if (h->hi_m < 1) return fail(ZENV_E_STATE, "the last zenv_collect_option closed no high-level transition (M = 0)");
+        // the dense env-major rows of the closed transitions, the skill as the action, one log_prob per row
         const HierOut &o = h->hout;
         x = PpoExp{ o.obs, o.zone_obs, nullptr, o.log_prob, o.value, o.advantage, o.returnn, (int)h->hi_m, 1, nullptr,
                     o.action, nullptr, nullptr };
@@ -821,5 +888,53 @@ extern "C" int zenv_skppo_epoch(zenv_t *h, int level, const int32_t *order, int 
 {
     if (!h || !order) return fail(ZENV_E_ARG, "null argument");
     LEARNER(h, level, AGENT_SKILL);
+    return learner_epoch(h, l, order, total, batch_size, on_device);
+}
+
+extern "C" int zenv_opppo_tensor(zenv_t *h, int level, int which, int index, void **dev_ptr, int64_t *count)
+{
+    if (!h || !dev_ptr || !count) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, level, AGENT_OPTION);
+    return learner_tensor(l, which, index, dev_ptr, count);
+}
+extern "C" int zenv_opppo_read(zenv_t *h, int level, int which, int index, float *dst)
+{
+    if (!dst) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, level, AGENT_OPTION);
+    return learner_copy(h, l, which, index, dst, true);
+}
+extern "C" int zenv_opppo_write(zenv_t *h, int level, int which, int index, const float *src)
+{
+    if (!src) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, level, AGENT_OPTION);
+    return learner_copy(h, l, which, index, const_cast<float *>(src), false);
+}
+extern "C" int zenv_opppo_get_step(zenv_t *h, int level, int64_t *step)
+{
+    if (!h || !step) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, level, AGENT_OPTION);
+    *step = l.s->step;
+    return ZENV_OK;
+}
+extern "C" int zenv_opppo_set_step(zenv_t *h, int level, int64_t step)
+{
+    LEARNER(h, level, AGENT_OPTION);
+    return learner_set_step(l, step);
+}
+extern "C" int zenv_opppo_minibatch(zenv_t *h, int level, const int32_t *idx, int count, int idx_on_device, int apply)
+{
+    if (!h || !idx) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, level, AGENT_OPTION);
+    return learner_minibatch(h, l, idx, count, idx_on_device, apply);
+}
+extern "C" int zenv_opppo_apply(zenv_t *h, int level)
+{
+    LEARNER(h, level, AGENT_OPTION);
+    return learner_apply(h, l);
+}
+extern "C" int zenv_opppo_epoch(zenv_t *h, int level, const int32_t *order, int total, int batch_size, int on_device)
+{
+    if (!h || !order) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, level, AGENT_OPTION);
     return learner_epoch(h, l, order, total, batch_size, on_device);
 }

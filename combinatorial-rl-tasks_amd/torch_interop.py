@@ -423,6 +423,94 @@ class TorchZoneEnv:
     def skppo_update(self, epochs, batch_size, hi_epochs, hi_batch_size, rng):
         return self.env.skppo_update(epochs, batch_size, hi_epochs, hi_batch_size, rng)
 
+    # ------------------------------------------------------------------ the Options agent's two PPO updates
+    def opppo_init(self, hi_state_dict, lo_state_dict, lo=None, hi=None):
+        """``ZoneVecEnv.opppo_init`` with each level's four arenas as flat float32 CUDA tensors ALIASING device memory in
+        ``self.opppo_arenas[level]`` (valid until the next opppo_init or ``env.close()``)."""
+        self.env.opppo_init(hi_state_dict, lo_state_dict, lo=lo, hi=hi)
+        with self._torch.cuda.device(self.device):
+            self.opppo_arenas = {}
+            for level in (nat.OPPPO_LO, nat.OPPPO_HI):
+                self.opppo_arenas[level] = {}
+                for name, which in (("param", nat.PPO_PARAM), ("grad", nat.PPO_GRAD), ("exp_avg", nat.PPO_EXP_AVG),
+                                    ("exp_avg_sq", nat.PPO_EXP_AVG_SQ)):
+                    ptr, count = self.env.opppo_tensor_ptr(level, which, -1)
+                    self.opppo_arenas[level][name] = self._alias_ptr(ptr, (count,))
+
+    def opppo_tensors(self, level, which=nat.PPO_PARAM):
+        """zenv_option_weights name -> CUDA tensor ALIASING that tensor of a level's arena, in its state_dict shape."""
+        learner = self.env._op_learner(level)
+        with self._torch.cuda.device(self.device):
+            return {name: self._alias_ptr(learner.tensor_ptr(which, i)[0], learner.shapes[name])
+                    for i, name in enumerate(learner.keys)}
+
+    def opppo_set_tensors(self, level, tensors, which=nat.PPO_PARAM):
+        """Overwrite the tensors of a level's arena that `tensors` names (tensors on any device), on the stream."""
+        views = self.opppo_tensors(level, which)
+        for name, src in tensors.items():
+            views[name].copy_(self._torch.as_tensor(src))
+
+    def opppo_state_dicts(self):
+        """(hi_model_state, lo_model_state) as CUDA tensors ALIASING the two parameter arenas."""
+        out = []
+        for level in (nat.OPPPO_HI, nat.OPPPO_LO):
+            views = self.opppo_tensors(level)
+            out.append({key: views[name] for name, key in self.env._op_learner(level).keys.items()})
+        return tuple(out)
+
+    def opppo_load_state_dicts(self, hi_state_dict, lo_state_dict):
+        for dst_sd, src_sd in zip(self.opppo_state_dicts(), (hi_state_dict, lo_state_dict)):
+            for key, dst in dst_sd.items():
+                dst.copy_(src_sd[key])
+
+    def opppo_tensor_ptr(self, level, which, index):
+        return self.env.opppo_tensor_ptr(level, which, index)
+
+    def opppo_get_step(self, level):
+        return self.env.opppo_get_step(level)
+
+    def opppo_set_step(self, level, step):
+        self.env.opppo_set_step(level, step)
+
+    def opppo_optimizer_state(self, level):
+        """``ZoneVecEnv.opppo_optimizer_state`` with the moments as CUDA copies."""
+        torch = self._torch
+        out = self.env.opppo_optimizer_state(level)
+        out["state"] = {i: {"step": torch.tensor(s["step"]), "exp_avg": torch.from_numpy(s["exp_avg"]).to(self.device),
+                            "exp_avg_sq": torch.from_numpy(s["exp_avg_sq"]).to(self.device)}
+                        for i, s in out["state"].items()}
+        return out
+
+    def opppo_load_optimizer_state(self, level, state):
+        self.env.opppo_load_optimizer_state(level, state)
+
+    def opppo_minibatch(self, level, idx, apply=False):
+        """``ZoneVecEnv.opppo_minibatch``; idx may be an int32 CUDA tensor (never copied, checked on the device)."""
+        ptr, count = self._ppo_index_arg(idx)
+        self.env.opppo_minibatch(level, ptr, apply=apply, count=count)
+
+    def opppo_apply(self, level):
+        self.env.opppo_apply(level)
+
+    def opppo_epoch(self, level, order, batch_size):
+        """``ZoneVecEnv.opppo_epoch``; order may be an int32 CUDA tensor."""
+        ptr, count = self._ppo_index_arg(order)
+        self.env.opppo_epoch(level, ptr, batch_size, count=count)
+
+    def opppo_stats(self, level):
+        """float32 CUDA tensor [minibatches, 6] ALIASING the statistics of the level's last opppo_minibatch / opppo_epoch
+        (not synchronised)."""
+        field = nat.OPPPO_STATS_FIELDS[level]
+        rows = self.env.field_bytes(field) // 24
+        with self._torch.cuda.device(self.device):
+            return self._alias(field, (rows, 6), np.float32)
+
+    def opppo_publish(self):
+        self.env.opppo_publish()
+
+    def opppo_update(self, epochs, batch_size, hi_epochs, hi_batch_size, rng):
+        return self.env.opppo_update(epochs, batch_size, hi_epochs, hi_batch_size, rng)
+
     def load_hier(self, hi_state_dict, lo_state_dict):
         """Put HighPolicyValueModel / LoPolicyValueModel state_dicts (zone-goals/src/hier_policy_value_models.py; torch
         tensors on any device) into the device agent that ``collect_hier`` runs -- after every update."""

@@ -22,7 +22,8 @@ from .agents import (_HIER_ENC, _HIER_CRITIC, HIER_HI_KEYS, HIER_LO_KEYS, SKILL_
                      check_collect_hier_args, check_collect_skill_args, check_collect_option_args,
                      hier_experience_layout, skill_experience_layout, option_experience_layout, skill_num_frames,
                      check_collect_xy_args, xy_experience_layout, ppo_state_dict_keys, ppo_batch_indexes,
-                     hppo_state_dict_keys, hppo_batch_indexes, xyppo_state_dict_keys, skppo_state_dict_keys)
+                     hppo_state_dict_keys, hppo_batch_indexes, xyppo_state_dict_keys, skppo_state_dict_keys,
+                     opppo_state_dict_keys)
 
 _FIELD_DTYPES = {
     nat.F_OBS: np.float32, nat.F_ZONE_OBS: np.float32, nat.F_REWARD: np.float32,
@@ -48,6 +49,7 @@ _FIELD_DTYPES = {
     nat.F_HPPO_LO_STATS: np.float32, nat.F_HPPO_HI_STATS: np.float32,
     nat.F_XYPPO_LO_STATS: np.float32, nat.F_XYPPO_HI_STATS: np.float32,
     nat.F_SKPPO_LO_STATS: np.float32, nat.F_SKPPO_HI_STATS: np.float32,
+    nat.F_OPPPO_LO_STATS: np.float32, nat.F_OPPPO_HI_STATS: np.float32,
 }
 
 
@@ -58,7 +60,7 @@ def _as_host_f32(v):
 
 class _Learner:
     """One device learner behind the ppo_* (level None: zenv_ppo_*), hppo_* (zenv_hppo_* with a level), xyppo_*
-    (prefix "zenv_xyppo_") or skppo_* (prefix "zenv_skppo_") methods: the arenas' tensors under their names, Adam's
+    (prefix "zenv_xyppo_"), skppo_* (prefix "zenv_skppo_") or opppo_* (prefix "zenv_opppo_") methods: the arenas' tensors under their names, Adam's
     state, the update calls and the statistics."""
 
     def __init__(self, handle, level, keys, shapes, lr, adam_eps, stats_field, prefix="zenv_hppo_"):
@@ -1281,6 +1283,126 @@ class ZoneVecEnv:
         rows = []
         for _ in range(int(epochs)):
             lo.epoch(hppo_batch_indexes(self.num_envs * T, rng), batch_size)
+            rows.append(lo.stats())
+        mean = np.concatenate(rows).astype(np.float64).mean(axis=0) if rows else np.zeros(6)
+        logs.update({"lo_" + n: float(mean[i]) for i, n in names})
+        return logs
+
+    # ------------------------------------------------------------------ the Options agent's two PPO updates
+    # the example's hyper-parameters (examples/options_ppo_torch.py; the reference takes the norm and does not clip)
+    OPPPO_LO = dict(lr=3e-4, adam_eps=1e-8, clip_eps=0.2, entropy_coef=0.003, value_loss_coef=0.5, max_grad_norm=math.inf,
+                    max_batch=16384)
+    OPPPO_HI = dict(lr=3e-4, adam_eps=1e-8, clip_eps=0.2, entropy_coef=0.01, value_loss_coef=0.5, max_grad_norm=math.inf,
+                    max_batch=4096)
+
+    def _op_learner(self, level):
+        """``_learner`` for the Options pair."""
+        found = self._learners.get(("op", int(level)))
+        field = nat.OPPPO_STATS_FIELDS[level] if level in (nat.OPPPO_LO, nat.OPPPO_HI) else nat.F_OPPPO_LO_STATS
+        return found or _Learner(self._h, level, {}, {}, 0.0, 0.0, field, "zenv_opppo_")
+
+    def opppo_init(self, hi_state_dict, lo_state_dict, lo=None, hi=None):
+        """The two learners of the Options agent (options/src/torch_ac/algos/_hier_policy_opt.py:208-381) on the device,
+        from its HighPolicyValueModel / LoPolicyValueModel state_dicts with both critics: float32 master parameters,
+        gradients, Adam's moments and a workspace per level.  lo / hi: dicts of the settings to change from ``OPPPO_LO``
+        / ``OPPPO_HI``.  `level` in the other opppo_* methods: ``_native.OPPPO_LO`` = 0, ``OPPPO_HI`` = 1.  Separate from
+        ``load_options``: ``opppo_publish`` hands the parameters to the acting agent."""
+        tensors = option_tensors_from_state_dicts(hi_state_dict, lo_state_dict)
+        S, h = (int(v) for v in tensors["hi_logit_w"].shape)
+        F = int(tensors["hi_zone_w1"].shape[1]) - 8
+        hi_keys, lo_keys = opppo_state_dict_keys()
+        missing = [n for n in list(hi_keys) + list(lo_keys) if n not in tensors]
+        if missing:
+            raise ValueError(f"the update needs both critics: no {missing[0]}")
+        shapes = option_tensor_shapes(h, S, F)
+        w = nat.OptionWeights(h_dim=h, n_skills=S, zone_feat=F, precision=nat.MLP_F32)
+        keep = self._load_weights(w, list(hi_keys) + list(lo_keys), tensors, shapes)      # alive across the call
+        cfgs = [nat.PpoConfig(distributional_value=0, **dict(base, **(over or {})))
+                for base, over in ((self.OPPPO_LO, lo), (self.OPPPO_HI, hi))]
+        check(lib().zenv_opppo_init(self._h, C.byref(w), C.byref(cfgs[0]), C.byref(cfgs[1])))
+        del keep
+        for level, keys in ((nat.OPPPO_LO, lo_keys), (nat.OPPPO_HI, hi_keys)):
+            self._learners[("op", level)] = _Learner(self._h, level, keys, shapes, cfgs[level].lr, cfgs[level].adam_eps,
+                                                     nat.OPPPO_STATS_FIELDS[level], "zenv_opppo_")
+
+    def opppo_tensor_ptr(self, level, which, index):
+        """``ppo_tensor_ptr`` of a level's arenas."""
+        return self._op_learner(level).tensor_ptr(which, index)
+
+    def opppo_tensors(self, level, which=nat.PPO_PARAM):
+        """Every tensor of a level's arena as a new host array, under its zenv_option_weights name (hi_* / lo_*)."""
+        return self._op_learner(level).tensors(which)
+
+    def opppo_set_tensors(self, level, tensors, which=nat.PPO_PARAM):
+        self._op_learner(level).set_tensors(tensors, which)
+
+    def opppo_state_dicts(self):
+        """(hi_model_state, lo_model_state): both learners' parameters under the reference's names (host copies)."""
+        return self._op_learner(nat.OPPPO_HI).state_dict(), self._op_learner(nat.OPPPO_LO).state_dict()
+
+    def opppo_load_state_dicts(self, hi_state_dict, lo_state_dict):
+        self._op_learner(nat.OPPPO_HI).load_state_dict(hi_state_dict)
+        self._op_learner(nat.OPPPO_LO).load_state_dict(lo_state_dict)
+
+    def opppo_optimizer_state(self, level):
+        """A level's Adam state in the shape of ``torch.optim.Adam.state_dict()``: parameter i is the i-th of the
+        module's ``parameters()``."""
+        return self._op_learner(level).optimizer_state()
+
+    def opppo_load_optimizer_state(self, level, state):
+        self._op_learner(level).load_optimizer_state(state)
+
+    def opppo_get_step(self, level):
+        return self._op_learner(level).get_step()
+
+    def opppo_set_step(self, level, step):
+        self._op_learner(level).set_step(step)
+
+    def opppo_minibatch(self, level, idx, apply=False, count=None):
+        """``ppo_minibatch`` on the records of the last ``collect_options``.  Low level: index i is env i // (T - 1), frame
+        i % (T - 1) (lo_exps' order; frame T - 1 is never read); high level: row i of the M closed transitions (M >= 1)."""
+        self._op_learner(level).minibatch(idx, apply, count)
+
+    def opppo_apply(self, level):
+        self._op_learner(level).apply()
+
+    def opppo_epoch(self, level, order, batch_size, count=None):
+        self._op_learner(level).epoch(order, batch_size, count)
+
+    def opppo_stats(self, level):
+        """float32 [minibatches, 6] of the level's last opppo_minibatch / opppo_epoch (``_native.PPO_STATS``' columns,
+        value_std = 0).  Waits for the device."""
+        return self._op_learner(level).stats()
+
+    def opppo_publish(self):
+        """Hand both learners' parameters to the acting agent: read them back and ``load_options`` them, so the next
+        ``collect_options`` acts with them.  Like every ``load_options`` this drops the transitions the last collection
+        left open, exactly as the torch example's reload does: an option still running when a collection ends is not
+        trained on, its skill is picked again."""
+        self.load_options(dict(self.opppo_tensors(nat.OPPPO_HI), **self.opppo_tensors(nat.OPPPO_LO)))
+
+    def opppo_update(self, epochs, batch_size, hi_epochs, hi_batch_size, rng):
+        """update_hi_parameters, then update_lo_parameters (options/src/torch_ac/algos/_hier_policy_opt.py:208-381) on the
+        records of the last ``collect_options``: the high level first and only if some transition closed (M >= 1; with
+        M = 0 the hi_* logs are zeros), then the low level over N (T - 1) indexes, each epoch in the order of
+        ``hppo_batch_indexes`` from the caller's numpy Generator.  Returns the reference's logs under lo_* / hi_*: the low
+        level's are means over all its minibatches, the high level's over the last epoch's."""
+        T = lib().zenv_field_bytes(self._h, nat.F_EXP_VALUE) // (4 * self.num_envs)
+        M = lib().zenv_field_bytes(self._h, nat.F_HI_ACTION) // 4
+        if T < 2:
+            raise ZenvError(nat.E_STATE, "collect_options first: the handle holds no experience of the Options agent")
+        hi, lo = self._op_learner(nat.OPPPO_HI), self._op_learner(nat.OPPPO_LO)
+        names = [(i, n) for i, n in enumerate(nat.PPO_STATS) if n != "value_std"]
+        logs = {"hi_" + n: 0.0 for _, n in names}
+        if M >= 1:
+            for _ in range(int(hi_epochs)):
+                hi.epoch(hppo_batch_indexes(M, rng), hi_batch_size)
+            if int(hi_epochs) > 0:
+                mean = hi.stats().astype(np.float64).mean(axis=0)
+                logs = {"hi_" + n: float(mean[i]) for i, n in names}
+        rows = []
+        for _ in range(int(epochs)):
+            lo.epoch(hppo_batch_indexes(self.num_envs * (T - 1), rng), batch_size)
             rows.append(lo.stats())
         mean = np.concatenate(rows).astype(np.float64).mean(axis=0) if rows else np.zeros(6)
         logs.update({"lo_" + n: float(mean[i]) for i, n in names})

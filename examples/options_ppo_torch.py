@@ -10,12 +10,17 @@ after every update the device agent is reloaded from them.  Reloading drops the 
 open: an option that is still running when a collection ends is not trained on, its skill is picked again.
 
     python examples/options_ppo_torch.py --env PointTSP-v0 --procs 4096 --frames-per-proc 100
+
+``--device-update`` runs both levels' updates in the library as well (``TorchZoneEnv.opppo_init`` / ``opppo_update`` /
+``opppo_publish``: zenv_opppo_*, csrc/ppo_update.hip).  ``opppo_publish`` reloads the device agent as the torch path's
+reload does, open transitions dropped alike.  Off by default, the torch path is what it was.
 """
 import argparse
 import os
 import sys
 import time
 
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -103,11 +108,14 @@ def _ppo_loss(log_prob, old_log_prob, value, sb, clip_eps):
 class OptionsPPO:
     """One iteration of the Options agent: collect_experiences on the device, then the two updates of
     _hier_policy_opt.py:227-381 in torch -- the high level's PPO on the closed transitions, the low level's on the
-    T - 1 frames of every env, its ratio over all three components of the action."""
+    T - 1 frames of every env, its ratio over all three components of the action.  With device_update both run in the
+    library (``opppo_init`` once; then ``collect_options``, ``opppo_update``, ``opppo_publish`` per iteration, and the
+    modules get the learners' parameters back after every update)."""
 
     def __init__(self, tenv, n_skills=5, h=128, frames_per_proc=100, epochs=4, batch_size=16384, hi_epochs=4,
                  hi_batch_size=4096, lr=3e-4, hi_lr=3e-4, discount=0.99, gae_lambda=0.95, clip_eps=0.2,
-                 entropy_coef=0.003, hi_entropy_coef=0.01, value_loss_coef=0.5, hi_value_coef=0.5, seed=1):
+                 entropy_coef=0.003, hi_entropy_coef=0.01, value_loss_coef=0.5, hi_value_coef=0.5, seed=1,
+                 device_update=False):
         self.tenv, self.S, self.T = tenv, n_skills, frames_per_proc
         dev, F_ = tenv.device, tenv.env.zone_feat
         self.hi_net = HighPolicyValueModel(F_, n_skills, h).to(dev)
@@ -120,14 +128,25 @@ class OptionsPPO:
         self.hi_optimizer = torch.optim.Adam(self.hi_net.parameters(), hi_lr, eps=1e-8)
         self.gen = torch.Generator(device=dev).manual_seed(seed)
         self.seed, self.it = seed, 0
+        self.device_update = device_update
+        if device_update:
+            self.rng = np.random.default_rng(seed)
+            tenv.opppo_init(self.hi_net.state_dict(), self.lo_net.state_dict(),
+                            lo=dict(lr=lr, clip_eps=clip_eps, entropy_coef=entropy_coef, value_loss_coef=value_loss_coef,
+                                    max_batch=batch_size),
+                            hi=dict(lr=hi_lr, clip_eps=clip_eps, entropy_coef=hi_entropy_coef,
+                                    value_loss_coef=hi_value_coef, max_batch=hi_batch_size))
+            tenv.opppo_publish()
 
     def _batches(self, total, size):
         order = torch.randperm(total, device=self.tenv.device, generator=self.gen)
         return [order[i:i + size] for i in range(0, total, size)]
 
     def collect(self):
-        """Reload the device agent from the modules, collect; (lo, hi, termination_rate) of TorchZoneEnv."""
-        self.tenv.load_options(self.hi_net.state_dict(), self.lo_net.state_dict())
+        """Reload the device agent from the modules (device_update: opppo_publish has), collect; (lo, hi,
+        termination_rate) of TorchZoneEnv."""
+        if not self.device_update:
+            self.tenv.load_options(self.hi_net.state_dict(), self.lo_net.state_dict())
         out = self.tenv.collect_options(self.T, policy_seed=self.seed * 1000003 + self.it, discount=self.discount,
                                         gae_lambda=self.gae_lambda)
         self.it += 1
@@ -172,6 +191,13 @@ class OptionsPPO:
     def update(self, lo, hi):
         """Both updates on one collection (before the next collect overwrites its buffers); the high level's only when
         some transition closed."""
+        if self.device_update:
+            logs = self.tenv.opppo_update(self.epochs, self.batch_size, self.hi_epochs, self.hi_batch_size, self.rng)
+            self.tenv.opppo_publish()
+            hi_sd, lo_sd = self.tenv.opppo_state_dicts()  # the modules follow the learners
+            self.hi_net.load_state_dict(hi_sd)
+            self.lo_net.load_state_dict(lo_sd)
+            return logs
         logs = {}
         if hi["action"].shape[0]:
             logs.update({"hi_" + k: v for k, v in self.update_hi_parameters(hi).items()})
@@ -187,14 +213,14 @@ class OptionsPPO:
 
 
 def train(env_id="PointTSP-v0", procs=4096, frames_per_proc=100, updates=10, n_skills=5, hidden=128, seed=1, log=print,
-          **kw):
+          device_update=False, **kw):
     torch.manual_seed(seed)
     env = Z.ZoneVecEnv(env_id, procs)
     env.build_bank(seed, 4 * procs)
     env.schedule_sequential(stride=procs)
     tenv = TorchZoneEnv(env)
     tenv.reset()
-    algo = OptionsPPO(tenv, n_skills, hidden, frames_per_proc, seed=seed, **kw)
+    algo = OptionsPPO(tenv, n_skills, hidden, frames_per_proc, seed=seed, device_update=device_update, **kw)
     for u in range(updates):
         t0 = time.perf_counter()
         logs = algo.iteration()
@@ -214,5 +240,7 @@ if __name__ == "__main__":
     ap.add_argument("--n-skills", type=int, default=5)
     ap.add_argument("--hidden-size", type=int, default=128)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--device-update", action="store_true",
+                    help="run both levels' PPO updates in the library (zenv_opppo_*) instead of torch")
     a = ap.parse_args()
-    train(a.env, a.procs, a.frames_per_proc, a.updates, a.n_skills, a.hidden_size, a.seed)
+    train(a.env, a.procs, a.frames_per_proc, a.updates, a.n_skills, a.hidden_size, a.seed, device_update=a.device_update)

@@ -189,7 +189,13 @@ enum {
      */
     ZENV_F_SKPPO_LO_STATS = 79,     /* float32 [minibatches][6] the low level's: ZENV_F_PPO_STATS' columns, value std = 0 */
     ZENV_F_SKPPO_HI_STATS = 80,     /* float32 [minibatches][6] the high level's, the same */
-    ZENV_F_COUNT = 81
+    /* the Options agent's two learners (zenv_opppo_init): the statistics of the minibatches of the level's last
+     * zenv_opppo_minibatch (one row) or zenv_opppo_epoch; 0 bytes before the first.  Before these two fields,
+     * ZENV_F_COUNT = 81
+     */
+    ZENV_F_OPPPO_LO_STATS = 81,     /* float32 [minibatches][6] the low level's: ZENV_F_PPO_STATS' columns, value std = 0 */
+    ZENV_F_OPPPO_HI_STATS = 82,     /* float32 [minibatches][6] the high level's, the same */
+    ZENV_F_COUNT = 83
 };
 
 /* scripted on-device action sources (the build's own; used by bench/tests) */
@@ -918,8 +924,8 @@ int zenv_collect_xy(zenv_t *h, int frames_per_proc, uint64_t policy_seed, uint64
  * parameters are separate from the acting network's: nothing here repacks zenv_mlp_load's images (read the parameters
  * back and load them to act with them).  Every reduction runs in a fixed order: the same call from the same state
  * gives the same bits.  The Zone-goals agent's two updates are zenv_hppo_* below, the xy-goals agent's two zenv_xyppo_*,
- * the fixed-length-skills agent's two zenv_skppo_*; the updates of DIAYN's inverse model and skill prior and of the
- * Options agent are not here. */
+ * the fixed-length-skills agent's two zenv_skppo_*, the Options agent's two zenv_opppo_*; the updates of DIAYN's
+ * inverse model and skill prior are not here. */
 typedef struct zenv_ppo_config {
     double lr, adam_eps;            /* torch.optim.Adam(lr, eps = adam_eps), betas 0.9 / 0.999 */
     double clip_eps, entropy_coef, value_loss_coef, max_grad_norm;
@@ -1083,6 +1089,51 @@ int zenv_skppo_set_step(zenv_t *h, int level, int64_t step);
 int zenv_skppo_minibatch(zenv_t *h, int level, const int32_t *idx, int count, int idx_on_device, int apply);
 int zenv_skppo_apply(zenv_t *h, int level);
 int zenv_skppo_epoch(zenv_t *h, int level, const int32_t *order, int total, int batch_size, int on_device);
+
+/* ---- the Options agent's two PPO updates on the device: update_lo_parameters / update_hi_parameters,
+ * options/src/torch_ac/algos/_hier_policy_opt.py:208-381 ----
+ * Two more learners, as zenv_skppo_*'s are; `level` 0 is the low level (LoPolicyValueModel), 1 the high level
+ * (HighPolicyValueModel), S = init->n_skills.  They read the records of the last zenv_collect_option in place:
+ *   low:   zenv_skppo_*'s low level with a third Gaussian component: actor.mu_ / actor.std_ are [3, h] / [3], the ratio is
+ *          exp(sum over the three components of log_prob - recorded), the entropy's mean is over B x 3.  Components 0-1
+ *          and their log_probs are ZENV_F_EXP_ACTION / ZENV_F_EXP_LOG_PROB [slot][2]; component 2, a_2, and its log_prob
+ *          are ZENV_F_LO_TERM_ACTION / ZENV_F_LO_TERM_LOG_PROB [slot].  a_2 is a third action dimension and nothing more:
+ *          the termination probability sigmoid(4 a_2 - 3) and the recorded draw play no part in the loss.  Sample index
+ *          i is env i / (T - 1), frame i % (T - 1): frames 0 .. T-2 of every env, frame T-1 is never read.  The skill is
+ *          ZENV_F_LO_SKILL of that frame.
+ *   high:  zenv_skppo_*'s high level on row i of the ZENV_F_HI_* rows, i in [0, M), M the transitions the call closed.
+ *          The action is the recorded skill (ZENV_F_HI_ACTION), ZENV_F_HI_LOG_PROB one float per row; no mask.
+ * max_grad_norm = +inf is accepted.  The arenas' order is zenv_option_weights' member order, parameters() order of the
+ * modules: 16 tensors for the high level, 18 for the low level (lo_mu_w / lo_std_w of 3 h, lo_mu_b / lo_std_b of 3
+ * elements).  Neither touches the acting agent's weights: read the parameters back and zenv_option_load them to act with
+ * them -- which drops the transitions the last collection left open. */
+/* zenv_skppo_check's rules: ZENV_E_ARG for h_dim outside 1 .. 191, n_skills outside 1 .. 32, a zone_feat other than
+ * zenv_zone_feat(cfg), a null tensor, a missing critic at either level, distributional_value != 0, a negative or
+ * non-finite hyper-parameter (max_grad_norm = +inf excepted), max_batch < 1, a workspace of 2^31 floats or more. */
+int zenv_opppo_check(const zenv_config *cfg, const zenv_option_weights *init, const zenv_ppo_config *lo,
+                     const zenv_ppo_config *hi);
+/* Both learners from one set of weights (init->precision is not used).  A second call replaces them; a failed one
+ * leaves neither. */
+int zenv_opppo_init(zenv_t *h, const zenv_option_weights *init, const zenv_ppo_config *lo, const zenv_ppo_config *hi);
+/* The flat functions with the level after the handle.  ZENV_E_ARG for a level other than 0 or 1; ZENV_E_STATE without
+ * zenv_opppo_init.  The update calls answer ZENV_E_STATE unless the handle's ZENV_F_EXP_* / ZENV_F_LO_* / ZENV_F_HI_*
+ * buffers hold a completed zenv_collect_option's records with the experience's T and option weights with S skills are
+ * loaded (no collect yet, another collector ran last, or zenv_skill_load replaced the weights); zenv_hppo_*, zenv_xyppo_*
+ * and zenv_skppo_* refuse these records in turn.  The high level also answers ZENV_E_STATE when the last call closed no
+ * transition (M = 0); the low level works then.  Statistics: ZENV_F_OPPPO_LO_STATS / ZENV_F_OPPPO_HI_STATS.  A host
+ * index outside [0, N (T - 1)) (low) or [0, M) (high) is ZENV_E_ARG; a device-resident one is never dereferenced: the
+ * sample is dropped as zenv_ppo_minibatch drops one, it adds nothing to the loss or to any gradient, the divisor stays
+ * the minibatch's count, and the next call that waits for the device answers ZENV_E_ARG once.  A recorded skill outside
+ * [0, S) -- a frame's ZENV_F_LO_SKILL or a row's ZENV_F_HI_ACTION -- drops its sample the same way; the -1 of a frame
+ * on which the env idled is refused this way too. */
+int zenv_opppo_tensor(zenv_t *h, int level, int which, int index, void **dev_ptr, int64_t *count);
+int zenv_opppo_read(zenv_t *h, int level, int which, int index, float *dst);
+int zenv_opppo_write(zenv_t *h, int level, int which, int index, const float *src);
+int zenv_opppo_get_step(zenv_t *h, int level, int64_t *step);
+int zenv_opppo_set_step(zenv_t *h, int level, int64_t step);
+int zenv_opppo_minibatch(zenv_t *h, int level, const int32_t *idx, int count, int idx_on_device, int apply);
+int zenv_opppo_apply(zenv_t *h, int level);
+int zenv_opppo_epoch(zenv_t *h, int level, const int32_t *order, int total, int batch_size, int on_device);
 
 /* ---- results ---- */
 int zenv_get(zenv_t *h, int field, void *dst, int dst_on_device);
