@@ -48,7 +48,7 @@ E_ARG, E_HIP, E_STATE, E_LAYOUT, E_DONE, E_RANGE = -1, -2, -3, -4, -5, -6
  F_XY_GOAL, F_XY_GOAL_MU, F_XY_GOAL_STD, F_XY_VALUE, F_XY_GOAL_AGE,
  F_HI_GOAL, F_LO_GOAL_DIST, F_XY_BOOTSTRAP_GOAL, F_PPO_STATS, F_HPPO_LO_STATS, F_HPPO_HI_STATS,
  F_XYPPO_LO_STATS, F_XYPPO_HI_STATS, F_SKPPO_LO_STATS, F_SKPPO_HI_STATS, F_OPPPO_LO_STATS,
- F_OPPPO_HI_STATS) = range(83)
+ F_OPPPO_HI_STATS, F_DIAYN_STATS, F_DIAYN_SAMPLES) = range(85)
 (RESULT_OBS, RESULT_REWARD, RESULT_DONE, RESULT_GOAL_MET, RESULT_EXCEPTION, RESULT_ZONE_OBS) = range(6)
 N_RESULTS = 6
 
@@ -136,6 +136,7 @@ SKPPO_LO, SKPPO_HI = 0, 1                                     # the `level` of t
 SKPPO_STATS_FIELDS = (F_SKPPO_LO_STATS, F_SKPPO_HI_STATS)     # by level
 OPPPO_LO, OPPPO_HI = 0, 1                                     # the `level` of the zenv_opppo_* functions
 OPPPO_STATS_FIELDS = (F_OPPPO_LO_STATS, F_OPPPO_HI_STATS)     # by level
+DIAYN_STATS = ("loss", "", "", "", "", "grad_norm")           # ZENV_F_DIAYN_STATS' columns (1-4 are 0)
 
 
 class PpoConfig(C.Structure):
@@ -285,6 +286,21 @@ _PROTOTYPES = {
     "zenv_opppo_minibatch": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "zenv_opppo_apply": (C.c_int, [_H, C.c_int]),
     "zenv_opppo_epoch": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "zenv_diayn_check": (C.c_int, [C.POINTER(Config), C.c_void_p, C.c_void_p]),
+    "zenv_diayn_init": (C.c_int, [_H, C.c_void_p, C.c_void_p]),
+    "zenv_diayn_tensor": (C.c_int, [_H, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    "zenv_diayn_read": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p]),
+    "zenv_diayn_write": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p]),
+    "zenv_diayn_get_step": (C.c_int, [_H, C.POINTER(C.c_int64)]),
+    "zenv_diayn_set_step": (C.c_int, [_H, C.c_int64]),
+    "zenv_diayn_samples": (C.c_int, [_H, C.POINTER(C.c_int64)]),
+    "zenv_diayn_minibatch": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "zenv_diayn_apply": (C.c_int, [_H]),
+    "zenv_diayn_epoch": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "zenv_diayn_prior_init": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_double, C.c_double]),
+    "zenv_diayn_prior_update": (C.c_int, [_H]),
+    "zenv_diayn_prior_read": (C.c_int, [_H, C.c_void_p]),
+    "zenv_diayn_prior_write": (C.c_int, [_H, C.c_void_p]),
     "zenv_get": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int]),
     "zenv_get_rows": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "zenv_device_ptr": (C.c_int, [_H, C.c_int, C.POINTER(C.c_void_p)]),

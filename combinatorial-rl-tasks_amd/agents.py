@@ -183,6 +183,20 @@ def opppo_state_dict_keys():
     return skppo_state_dict_keys()
 
 
+def diayn_state_dict_keys():
+    """zenv_skill_inverse_weights name -> state_dict key of the 10 tensors DIAYN's inverse-model learner holds, in its
+    arena's order: InverseModel's ``parameters()`` order (main/src/inverse_model.py), the order of torch Adam's state."""
+    return {name: INVERSE_KEYS[name] for name in nat.SKILL_INVERSE_TENSORS}
+
+
+def diayn_kept_samples(mask):
+    """The sample indexes the inverse model trains on (main's _hier_policy_opt.py:193-199) from the collection's mask
+    [N, T]: sample i = env * (T - 1) + f pairs the observation of frame f + 1 with the skill of frame f and is kept where
+    mask[env, f + 1] is not 0.  Ascending int32: the reference's env-major order, what ``diayn_samples`` gives."""
+    keep = np.asarray(mask)[:, 1:] != 0
+    return np.flatnonzero(keep.reshape(-1)).astype(np.int32)
+
+
 def hppo_batch_indexes(total, rng):
     """The sample order of one epoch of either level: _get_batches_starting_indexes_lo / _hi (zone-goals/src/torch_ac/
     algos/_hier_policy_opt.py:372-420) before it is cut into batches -- a plain permutation of range(total) from the

@@ -15,6 +15,10 @@
 // And the Options agent's two (options/src/torch_ac/algos/_hier_policy_opt.py:208-381): its high level is the skills
 // agent's on the rows of the transitions a collection closed, its low level the skills agent's with a third Gaussian
 // component (PpoNet::NA = 3) on frames 0 .. T-2, the third component's records read from buffers of their own.
+// And DIAYN's discriminator (update_inverse_parameters, main/src/torch_ac/algos/_hier_policy_opt.py:421-447): the flat
+// encoder with a ReLU after combine_net.0 under an S-way cross-entropy head (PPO_HEAD_INVERSE, k_inv_loss) on the pairs
+// (observation of frame f + 1, skill of frame f) the collection kept (k_inv_count / _scan / _scatter); and the histogram
+// of the recorded picks for the learned skill prior's step (k_prior_hist).
 //
 // Every layer is a product on v_mfma_f32_32x32x2_f32, forward and backward, in one of two shapes:
 //
@@ -39,6 +43,7 @@
 // minibatch (0.9 MB); the arenas themselves stay in the state_dict's unpadded layout.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 
 #include "ppo_update.hpp"
@@ -56,6 +61,10 @@ struct Gather {
     int XD, W1C;
     const int32_t *skill;   // [slot]: columns 8 .. 8 + S of the per-sample input are onehot(skill) (S > 0; else null)
     int S;
+    // DIAYN's inverse model: the observation's frame is the sample's plus `shift` (the skill stays the sample's frame's),
+    // and a sample whose keep flag [the observation's slot] is 0 is dropped.  0 and null for every other learner.
+    int shift;
+    const float *keep;
 };
 
 // where a zone row of the minibatch lies in the experience buffers
@@ -74,11 +83,12 @@ __device__ __forceinline__ bool sample_slot(const Gather &g, int b, size_t &slot
     const int i = g.idx[b];
     if (i < 0 || i >= g.N * g.T) return false;       // N T < 2^31: zenv_collect refuses more
     const int env = i / g.T, t = i - env * g.T;      // exps.* flattens [N][T] (base.py:212-227)
-    slot = (size_t)t * g.N + env;
+    slot = (size_t)(t + g.shift) * g.N + env;
     if (g.skill) {
-        sk = g.skill[slot];
+        sk = g.skill[(size_t)t * g.N + env];
         if (sk < 0 || sk >= g.S) return false;
     }
+    if (g.keep && g.keep[slot] == 0.f) return false;
     return true;
 }
 __device__ __forceinline__ bool sample_slot(const Gather &g, int b, size_t &slot)
@@ -286,6 +296,12 @@ __global__ void k_ppo_prep(PpoNet n)
 {
     const int e = blockIdx.x * blockDim.x + threadIdx.x, which = blockIdx.y;
     const int h = n.h, HP = n.HP;
+    // DIAYN's inverse model has no enc_ layer and no critic: their images are not allocated.  Its head, combine_net.2,
+    // is the skills agent's actor.discrete_.0 in another place of the arena.
+    const bool inverse = n.head == PPO_HEAD_INVERSE;
+    if (inverse && (which == PPO_I_WE || which == PPO_I_WV || which == PPO_I_HV || which == PPO_T_WE || which == PPO_T_WV ||
+                    which == PPO_T_HV))
+        return;
     const int ld = which == PPO_I_W1 ? n.W1C : which == PPO_I_WC ? n.KC : (which == PPO_T_HA || which == PPO_T_HV) ? 32
                    : (which == PPO_I_WE || which == PPO_I_WV) ? n.LDC : HP;
     const int n_rows = (which == PPO_I_HA || which == PPO_I_HV) ? 32 : HP;
@@ -293,7 +309,8 @@ __global__ void k_ppo_prep(PpoNet n)
     const int r = e / ld, c = e - r * ld;
     auto T = [&](int t) { return n.param + n.off[t]; };
     const int XD = n.XD, kb = n.W1C - 1;
-    const bool zones = n.head == PPO_HEAD_ZONES, skills = n.head == PPO_HEAD_SKILLS;
+    const bool zones = n.head == PPO_HEAD_ZONES, skills = n.head == PPO_HEAD_SKILLS || inverse;
+    const int hw = inverse ? PPO_INV_W2 : PPO_ACTOR_W2, hb = inverse ? PPO_INV_B2 : PPO_ACTOR_B2;    // the S-way head
     // the skills agent's low level: actor.enc_.0.0 and critic.0 are [h][h + S] over [emb, onehot]; the onehot's columns
     // lie at HP .. HP + S of their images
     const int tail = n.LDC > HP ? n.S : 0;
@@ -330,7 +347,7 @@ __global__ void k_ppo_prep(PpoNet n)
         if (zones) {                                  // row 0: actor.2
             if (r == 0 && c <= h) v = c < h ? T(PPO_ACTOR_W2)[c] : T(PPO_ACTOR_B2)[0];
         } else if (skills) {                          // rows 0 .. S: actor.discrete_.0
-            if (r < n.S && c <= h) v = c < h ? T(PPO_ACTOR_W2)[(size_t)r * h + c] : T(PPO_ACTOR_B2)[r];
+            if (r < n.S && c <= h) v = c < h ? T(hw)[(size_t)r * h + c] : T(hb)[r];
         } else if (r < 2 * NA && c <= h) {            // rows 0 .. NA: actor.mu_, NA .. 2 NA: actor.std_
             const float *w = T(r < NA ? PPO_MU_W : PPO_STD_W), *b = T(r < NA ? PPO_MU_B : PPO_STD_B);
             const int o = r < NA ? r : r - NA;
@@ -352,7 +369,7 @@ __global__ void k_ppo_prep(PpoNet n)
         if (zones) {
             if (r < h && c == 0) v = T(PPO_ACTOR_W2)[r];
         } else if (skills) {
-            if (r < h && c < n.S) v = T(PPO_ACTOR_W2)[(size_t)c * h + r];
+            if (r < h && c < n.S) v = T(hw)[(size_t)c * h + r];
         } else if (r < h && c < 2 * NA) v = T(c < NA ? PPO_MU_W : PPO_STD_W)[(size_t)(c < NA ? c : c - NA) * h + r];
         break;
     case PPO_T_HV:
@@ -876,6 +893,164 @@ __global__ __launch_bounds__(256) void k_skppo_head_bias(PpoNet n, int bp)
     }
 }
 
+// ---- PPO_HEAD_INVERSE: DIAYN's discriminator (main/src/inverse_model.py), logits = combine_net.2(relu(combine_net.0(
+// [obs, zone_emb]))), trained by update_inverse_parameters (main/src/torch_ac/algos/_hier_policy_opt.py:421-447):
+// CrossEntropyLoss(logits, skill).mean().  The loss of one sample and its derivative with respect to the S logits (L,
+// DL: [samples][32], columns 0 .. S): with p = softmax(logits), loss = -log p[skill] and d loss / d logit_s =
+// (p_s - 1[s = skill]) / count.  The log-softmax and the derivatives are formed in double and rounded once into DL; the
+// unrounded ones go to DZ [samples][S] for k_inv_head_bias.  With S = 1 the one probability is exactly 1: the loss and
+// every derivative are exactly 0.  The skill is the one of the sample's own frame, the observation the next frame's
+// (Gather::shift); a sample that sample_slot drops -- index, skill or keep flag -- adds nothing.  SS column 0: the loss;
+// columns 1-4 stay 0 (k_ppo_stats turns them into the statistics row).  One thread per sample, rows up to bp written.
+__global__ void k_inv_loss(PpoNet n, Gather g, int bp)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= bp) return;
+    const int S = n.S;
+    size_t slot = 0;
+    int a = -1;
+    const bool ok = sample_slot(g, b, slot, a);
+    const float *lg = n.L + (size_t)b * 32;
+    double lse = 0.0, inv_b = 0.0;
+    float loss = 0.f;
+    if (ok) {
+        inv_b = 1.0 / (double)g.count;
+        double m = (double)lg[a];
+        for (int s = 0; s < S; ++s) {
+            const double v = (double)lg[s];
+            m = v > m ? v : m;
+        }
+        double sum = 0.0;
+        for (int s = 0; s < S; ++s) sum += exp((double)lg[s] - m);
+        lse = m + log(sum);
+        loss = (float)(lse - (double)lg[a]);
+    }
+    float *dl = n.DL + (size_t)b * 32;
+    for (int s = 0; s < 32; ++s) {
+        double dz = 0.0;
+        if (ok && s < S) dz = (exp((double)lg[s] - lse) - (s == a ? 1.0 : 0.0)) * inv_b;
+        if (s < S) n.DZ[(size_t)b * S + s] = dz;
+        dl[s] = (float)dz;
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) n.SS[(size_t)b * 8 + i] = i == 0 ? loss : 0.f;
+}
+
+// combine_net.2.bias' gradient: the sum over the minibatch of the logits' deltas.  A column's deltas cancel -- p_s over
+// every sample against the 1 of the samples of skill s -- so, as k_skppo_head_bias does, the sum runs over the unrounded
+// deltas (DZ), in double, in a fixed order, and is rounded once.  Block s of 256 threads: skill s.
+__global__ __launch_bounds__(256) void k_inv_head_bias(PpoNet n, int bp)
+{
+    __shared__ double sh[256];
+    const int c = blockIdx.x, S = n.S;
+    double s = 0.0;
+    for (int b = threadIdx.x; b < bp; b += 256) s += n.DZ[(size_t)b * S + c];
+    s = block_sum_256(s, sh);
+    if (threadIdx.x == 0) n.grad[n.off[PPO_INV_B2] + c] = (float)s;
+}
+
+// ---- DIAYN's kept samples (_hier_policy_opt.py:193-199): the sample indexes i in [0, N (T - 1)) whose keep flag --
+// the mask of frame i % (T - 1) + 1 of env i / (T - 1) -- is not 0, ascending, which is the reference's env-major
+// order.  Three launches: a count per block of kInvBlock indexes, an exclusive scan of the counts, and a scatter in
+// which thread t of a block writes its four consecutive indexes behind those of threads 0 .. t - 1.  Every position
+// is a sum of integer counts of lower indexes: no atomics, and nothing depends on the order blocks or waves run in.
+__device__ __forceinline__ bool inv_kept(const float *mask, int N, int T1, int64_t total, int64_t i)
+{
+    if (i >= total) return false;
+    const int env = (int)(i / T1), f = (int)(i - (int64_t)env * T1);
+    return mask[(size_t)(f + 1) * N + env] != 0.f;
+}
+
+// the kept ones among a thread's four indexes (bit k: index first + k), and the exclusive sum of the counts of the
+// block's threads before it; *block_total: the block's count.  256 threads.
+__device__ __forceinline__ int inv_thread_prefix(const float *mask, int N, int T1, int64_t total, unsigned &bits,
+                                                 int *sh, int &block_total)
+{
+    const int64_t first = (int64_t)blockIdx.x * kInvBlock + 4 * (int64_t)threadIdx.x;
+    bits = 0;
+    int c = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (inv_kept(mask, N, T1, total, first + k)) bits |= 1u << k, ++c;
+    // an inclusive scan over the 256 counts (Hillis-Steele, two buffers)
+    int *src = sh, *dst = sh + 256;
+    src[threadIdx.x] = c;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {
+        dst[threadIdx.x] = src[threadIdx.x] + ((int)threadIdx.x >= d ? src[threadIdx.x - d] : 0);
+        __syncthreads();
+        int *t = src;
+        src = dst;
+        dst = t;
+    }
+    block_total = src[255];
+    return src[threadIdx.x] - c;
+}
+
+__global__ __launch_bounds__(256) void k_inv_count(const float *__restrict__ mask, int N, int T1, int64_t total,
+                                                   int32_t *__restrict__ block_count)
+{
+    __shared__ int sh[512];
+    unsigned bits;
+    int block_total;
+    (void)inv_thread_prefix(mask, N, T1, total, bits, sh, block_total);
+    if (threadIdx.x == 0) block_count[blockIdx.x] = block_total;
+}
+
+// block_count[b] becomes the sum of the counts of blocks 0 .. b - 1, block_count[blocks] and *total the sum of all.  One
+// wave: tiles of kInvScan counts in turn, an inclusive scan across the lanes, the tiles before as a carry.
+__global__ __launch_bounds__(kInvScan) void k_inv_scan(int32_t *block_count, int blocks, int32_t *total)
+{
+    const int lane = threadIdx.x;
+    int carry = 0;
+    for (int b0 = 0; b0 < blocks; b0 += kInvScan) {
+        const int c = b0 + lane < blocks ? block_count[b0 + lane] : 0;
+        int v = c;
+#pragma unroll
+        for (int d = 1; d < kInvScan; d <<= 1) {
+            const int u = __shfl_up(v, d, kInvScan);
+            if (lane >= d) v += u;
+        }
+        if (b0 + lane < blocks) block_count[b0 + lane] = carry + v - c;
+        carry += __shfl(v, kInvScan - 1, kInvScan);
+    }
+    if (lane == 0) {
+        block_count[blocks] = carry;
+        *total = carry;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_inv_scatter(const float *__restrict__ mask, int N, int T1, int64_t total,
+                                                     const int32_t *__restrict__ block_offset, int32_t *__restrict__ list)
+{
+    __shared__ int sh[512];
+    unsigned bits;
+    int block_total;
+    int at = block_offset[blockIdx.x] + inv_thread_prefix(mask, N, T1, total, bits, sh, block_total);
+    const int64_t first = (int64_t)blockIdx.x * kInvBlock + 4 * (int64_t)threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (bits & (1u << k)) list[at++] = (int32_t)(first + k);
+}
+
+// ---- the learned skill prior (update_skill_prior, _hier_policy_opt.py:449-464): the histogram of the M recorded picks.
+// Integer counters in LDS, then one integer add per skill and block to the global counters: integer sums do not depend
+// on their order.  A pick outside [0, S) is dropped and flagged.
+__global__ __launch_bounds__(256) void k_prior_hist(const int32_t *__restrict__ action, int64_t M, int S,
+                                                    int32_t *__restrict__ counts, int *bad)
+{
+    __shared__ int sh[32];
+    if (threadIdx.x < 32) sh[threadIdx.x] = 0;
+    __syncthreads();
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < M; i += (int64_t)gridDim.x * 256) {
+        const int a = action[i];
+        if (a >= 0 && a < S) atomicAdd(&sh[a], 1);
+        else *bad = 1;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < S && sh[threadIdx.x]) atomicAdd(&counts[threadIdx.x], sh[threadIdx.x]);
+}
+
 // stats[0..4] = the minibatch means of the per-sample terms; one block of 256 threads, thread i adds samples i, i + 256 ...
 // ent_terms: the entropy's mean is over count x 2 (the Options agent's low level: 3) action components, or over count
 // categoricals or rows whose two components' entropies are already summed (k_xyppo_hi_loss).  zero_grad (or null):
@@ -937,7 +1112,7 @@ __global__ void k_ppo_adam(PpoNet n, float step_size, float bc2_sqrt)
     n.exp_avg_sq[e] = v;
 }
 
-Gather no_gather() { return Gather{ nullptr, nullptr, nullptr, 0, 1, 1, 1, 0, nullptr, 8, 16, nullptr, 0 }; }
+Gather no_gather() { return Gather{ nullptr, nullptr, nullptr, 0, 1, 1, 1, 0, nullptr, 8, 16, nullptr, 0, 0, nullptr }; }
 
 template <int MODE>
 void nt(const float *A, int lda, const float *B, int ldb, int K, float *D, int ldd, int rows, int m_tiles,
@@ -1058,6 +1233,21 @@ void skill_head(const PpoNet &n, const PpoExp &x, const Gather &g, int bp, float
     nt<NT_ADD>(I[PPO_T_WV], HP, n.Hc, HP, HP, n.C, HP, bp, NT, s);                        // ... from actor and critic
 }
 
+// PPO_HEAD_INVERSE: C holds relu(combine_net.0) going in, combine_net.0's delta coming out
+void inverse_head(const PpoNet &n, const Gather &g, int bp, float *stats, hipStream_t s)
+{
+    const int h = n.h, HP = n.HP, NT = HP / 32, S = n.S;
+    float *const *I = n.img;
+    nt<NT_STORE>(I[PPO_I_HA], HP, n.C, HP, HP, n.L, 32, bp, 1, s);                        // combine_net.2: S logits
+    hipLaunchKernelGGL(k_inv_loss, dim3((bp + 63) / 64), dim3(64), 0, s, n, g, bp);
+    hipLaunchKernelGGL(k_ppo_stats, dim3(1), dim3(256), 0, s, n.SS, g.count, 1.0, stats, (float *)nullptr);
+    // ---- backward
+    tn(n.DL, 32, 1, n.C, HP, HP, bp, n.partial, s);
+    reduce(n, bp, 1, HP, 0, 0, PPO_INV_W2, h, 0, S, h, s);
+    hipLaunchKernelGGL(k_inv_head_bias, dim3(S), dim3(256), 0, s, n, bp);                 // combine_net.2.bias
+    nt<NT_MASK>(I[PPO_T_HA], 32, n.DL, 32, 32, n.C, HP, bp, NT, s);                       // delta of combine_net.0
+}
+
 void zone_head(const PpoNet &n, const PpoExp &x, const Gather &g, int rp, int bp, float *stats, hipStream_t s)
 {
     const int h = n.h, HP = n.HP, NT = HP / 32, cr = n.cr, F = n.F;
@@ -1101,7 +1291,8 @@ hipError_t launch_ppo_minibatch(const PpoNet &n, const PpoExp &x, const int32_t 
 {
     const int h = n.h, HP = n.HP, KC = n.KC, NT = HP / 32, XD = n.XD, W1C = n.W1C, LDC = n.LDC;
     const int rp = (count * n.Z + 31) / 32 * 32, bp = (count + 31) / 32 * 32;
-    const Gather g{ x.obs, x.zone_obs, idx, count, x.N, x.T, n.Z, n.F, x.goal, XD, W1C, x.skill, x.skill ? n.S : 0 };
+    const Gather g{ x.obs, x.zone_obs, idx, count, x.N, x.T, n.Z, n.F, x.goal, XD, W1C, x.skill, x.skill ? n.S : 0,
+                    x.obs_shift, x.keep };
     float *const *I = n.img;
     // the widest image: combine_net_'s [HP][KC], or actor.enc_.0.0's [HP][LDC] (zone_net_.0's W1C <= 48 <= KC)
     const int wide = KC > LDC ? KC : LDC;
@@ -1112,10 +1303,15 @@ hipError_t launch_ppo_minibatch(const PpoNet &n, const PpoExp &x, const int32_t 
     nt<NT_RELU>(I[PPO_I_W2], HP, n.A1, HP, HP, n.A2, HP, rp, NT, s);                      // relu(zone_net_.2)
     hipLaunchKernelGGL(k_ppo_pool, dim3((bp * KC + 255) / 256), dim3(256), 0, s, n, g, bp);
     nt<NT_STORE>(I[PPO_I_W3], HP, n.P, HP, HP, n.CI, KC, bp, NT, s);                      // zone_net_.4 of the mean
-    nt<NT_STORE>(I[PPO_I_WC], KC, n.CI, KC, KC, n.C, LDC, bp, NT, s);                     // combine_net_
-    if (n.head == PPO_HEAD_ZONES) zone_head(n, x, g, rp, bp, stats, s);
-    else if (n.head == PPO_HEAD_SKILLS) skill_head(n, x, g, bp, stats, s);
-    else gaussian_head(n, x, g, bp, stats, s);
+    if (n.head == PPO_HEAD_INVERSE) {
+        nt<NT_RELU>(I[PPO_I_WC], KC, n.CI, KC, KC, n.C, LDC, bp, NT, s);                  // relu(combine_net.0)
+        inverse_head(n, g, bp, stats, s);
+    } else {
+        nt<NT_STORE>(I[PPO_I_WC], KC, n.CI, KC, KC, n.C, LDC, bp, NT, s);                 // combine_net_
+        if (n.head == PPO_HEAD_ZONES) zone_head(n, x, g, rp, bp, stats, s);
+        else if (n.head == PPO_HEAD_SKILLS) skill_head(n, x, g, bp, stats, s);
+        else gaussian_head(n, x, g, bp, stats, s);
+    }
     // ---- the encoder's backward pass, from the embedding's delta in C
     if ((KC + 31) / 32 <= 7) {
         tn(n.C, LDC, NT, n.CI, KC, KC, bp, n.partial, s);
@@ -1156,6 +1352,26 @@ hipError_t launch_ppo_apply(const PpoNet &n, float step_size, float bc2_sqrt, hi
 {
     launch_norm(n, nullptr, s);
     hipLaunchKernelGGL(k_ppo_adam, dim3((unsigned)((n.arena + 255) / 256)), dim3(256), 0, s, n, step_size, bc2_sqrt);
+    return hipGetLastError();
+}
+
+hipError_t launch_inv_compact(const float *mask, int N, int T, int32_t *block_count, int32_t *list, int32_t *total,
+                              hipStream_t s)
+{
+    const int64_t samples = (int64_t)N * (T - 1);
+    const int blocks = (int)((samples + kInvBlock - 1) / kInvBlock);
+    hipLaunchKernelGGL(k_inv_count, dim3(blocks), dim3(256), 0, s, mask, N, T - 1, samples, block_count);
+    hipLaunchKernelGGL(k_inv_scan, dim3(1), dim3(kInvScan), 0, s, block_count, blocks, total);
+    hipLaunchKernelGGL(k_inv_scatter, dim3(blocks), dim3(256), 0, s, mask, N, T - 1, samples, block_count, list);
+    return hipGetLastError();
+}
+
+hipError_t launch_prior_hist(const int32_t *action, int64_t M, int S, int32_t *counts, int *bad, hipStream_t s)
+{
+    hipError_t e = hipMemsetAsync(counts, 0, 32 * sizeof(int32_t), s);
+    if (e != hipSuccess) return e;
+    const int blocks = (int)std::min<int64_t>((M + 255) / 256, 1024);
+    hipLaunchKernelGGL(k_prior_hist, dim3(blocks), dim3(256), 0, s, action, M, S, counts, bad);
     return hipGetLastError();
 }
 

@@ -21,7 +21,11 @@ enum { PPO_ACTOR_W1 = PPO_ENC_W, PPO_ACTOR_B1 = PPO_ENC_B, PPO_ACTOR_W2 = PPO_MU
 // The fixed-length-skills agent's high level has the same 16 places: actor.enc_.0.0 [h, h] / actor.discrete_.0 [S, h]
 // where the Zone-goals one has actor.0 / actor.2 (PPO_HEAD_SKILLS).  Its low level is the Gaussian network on
 // [obs, onehot(skill)] (XD = 8 + S) whose actor.enc_.0.0 and critic.0 read [emb, onehot]: [h, h + S] (PpoNet::S).
-enum { PPO_HEAD_GAUSSIAN = 0, PPO_HEAD_ZONES = 1, PPO_HEAD_SKILLS = 2 };
+enum { PPO_HEAD_GAUSSIAN = 0, PPO_HEAD_ZONES = 1, PPO_HEAD_SKILLS = 2, PPO_HEAD_INVERSE = 3 };
+// DIAYN's discriminator (InverseModel, zenv_skill_inverse_weights' member order: 10 tensors): the encoder's eight as
+// above with a ReLU after combine_net.0, then combine_net.2 [S, h] / [S] straight on it -- no enc_ layer, no critic
+// (PPO_HEAD_INVERSE).  Its head uses the image slots PPO_I_HA / PPO_T_HA.
+enum { PPO_INV_W2 = PPO_ENC_W, PPO_INV_B2 = PPO_ENC_B, PPO_INV_TENSORS = 10 };
 // what the Gaussian head's loss is taken of: the flat learner's action with a recorded log_prob per component
 // (k_ppo_loss), or the xy-goals high level's goal with one recorded log_prob per row (k_xyppo_hi_loss)
 enum { PPO_LOSS_ACTION = 0, PPO_LOSS_JOINT_GOAL = 1 };
@@ -35,6 +39,8 @@ constexpr int kPpoChunk = 256;      // rows one wave reduces into one partial of
 constexpr int kPpoStats = 6;        // entropy, value, value std, policy loss, value loss, gradient norm
 constexpr int kPpoNormBlock = 4096; // arena elements per partial of the gradient norm
 constexpr int kPpoReduceSplit = 16; // k_ppo_reduce_split: segments of the chunk range, one thread each
+constexpr int kInvBlock = 1024;     // k_inv_count / k_inv_scatter: sample indexes per block (256 threads x 4 consecutive)
+constexpr int kInvScan = 64;        // k_inv_scan: block counts per tile of the exclusive scan (one wave)
 
 struct PpoHyper {
     float lr, adam_eps, clip_eps, entropy_coef, value_loss_coef, max_grad_norm;
@@ -71,10 +77,11 @@ struct PpoNet {
     float *PRE, *DH;         // [samples][32]: the six (NA = 3: seven) head pre-activations, their deltas
     // PPO_HEAD_ZONES only: relu(actor.0) of every zone row [rows][HP], the logits and their deltas [rows][32] (column 0)
     // PPO_HEAD_SKILLS: L, DL are the S logits of a sample and their deltas [samples][32]; the value stays in PRE / DH
+    // PPO_HEAD_INVERSE: L, DL the same; Ha, Hc, PRE, DH and the images of enc_ and the critic are not allocated
     float *U, *L, *DL;
     double *DZ;              // [rows]: the logits' deltas as k_hppo_loss forms them, before they are rounded into DL;
                              // the skills / Options agents' low level: [samples][2 NA + 1], the head's deltas before they
-                             // are rounded
+                             // are rounded; PPO_HEAD_INVERSE: [samples][S], the logits' deltas the same way
     float *SS;               // [samples][8]: the per-sample terms of the statistics
     float *partial;          // the per-chunk partials of one weight gradient
     double *norm_partial;    // [arena / kPpoNormBlock + 1]
@@ -98,6 +105,11 @@ struct PpoExp {
     const int32_t *skill = nullptr; // [slot]: the skill a frame was acted under (XD = 8 + S only)
     // NA = 3: the third action component and its recorded log_prob [slot]; components 0-1 stay in action / log_prob [slot][2]
     const float *term_action = nullptr, *term_log_prob = nullptr;
+    // PPO_HEAD_INVERSE: sample i (env i / T, frame f = i % T, T = the collection's frames - 1) reads its observation and
+    // zone rows at frame f + obs_shift, its skill at frame f, and is dropped where keep [slot of frame f + obs_shift]
+    // is 0.  Every other learner: 0 and null.
+    int obs_shift = 0;
+    const float *keep = nullptr;
 };
 
 // forward, loss and backward of the samples idx[0 .. count) (device memory): gradients into net.grad, the six
@@ -107,5 +119,14 @@ hipError_t launch_ppo_minibatch(const PpoNet &net, const PpoExp &exp, const int3
 // the clip and Adam step on net.grad; step_size = lr / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t), formed on the
 // host in double as torch forms them
 hipError_t launch_ppo_apply(const PpoNet &net, float step_size, float bc2_sqrt, hipStream_t stream);
+
+// DIAYN's kept samples: list[0 .. *total) = the sample indexes i in [0, N (T - 1)), ascending, whose keep flag
+// mask[(i % (T - 1) + 1) N + i / (T - 1)] is not 0 (mask: [T][N]).  block_count: [blocks + 1] ints, blocks =
+// ceil(N (T - 1) / kInvBlock); total: one int (device memory).
+hipError_t launch_inv_compact(const float *mask, int N, int T, int32_t *block_count, int32_t *list, int32_t *total,
+                              hipStream_t stream);
+// counts[s] += the rows of action[0 .. M) that equal s, s in [0, S); a row outside [0, S) is dropped and sets *bad.
+// counts is zeroed first.
+hipError_t launch_prior_hist(const int32_t *action, int64_t M, int S, int32_t *counts, int *bad, hipStream_t stream);
 
 }  // namespace zenvk

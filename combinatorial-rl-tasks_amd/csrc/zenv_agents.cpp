@@ -666,6 +666,7 @@ static int ensure_exp(zenv_t *h, int T)
     h->exp_xy = false;          // zenv_collect_xy, the same
     h->exp_skill = false;       // zenv_collect_skill, the same
     h->exp_option = false;      // zenv_collect_option, the same
+    h->diayn_kept = -1;         // zenv_diayn_samples' list was of the records this call overwrites
     if (!h->exp_mem || h->exp.T != T) {
         HIP_TRY(hipStreamSynchronize(h->stream));
         std::vector<float> keep_mask;

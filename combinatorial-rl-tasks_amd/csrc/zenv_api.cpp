@@ -253,11 +253,13 @@ FieldInfo field_info(const zenv *h, int field)
     case ZENV_F_SKPPO_LO_STATS:
     case ZENV_F_SKPPO_HI_STATS:
     case ZENV_F_OPPPO_LO_STATS:
-    case ZENV_F_OPPPO_HI_STATS: {       // nine consecutive fields, ppo_stats' order
+    case ZENV_F_OPPPO_HI_STATS:
+    case ZENV_F_DIAYN_STATS: {          // ten consecutive fields, ppo_stats' order
         int64_t bytes = 0;
         void *ptr = ppo_stats(h, field - ZENV_F_PPO_STATS, &bytes);
         return { ptr, bytes };
     }
+    case ZENV_F_DIAYN_SAMPLES: return { h->diayn_list, h->diayn_kept > 0 ? h->diayn_kept * 4 : 0 };
     default: return { nullptr, 0 };
     }
 }

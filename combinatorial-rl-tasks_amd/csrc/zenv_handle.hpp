@@ -158,6 +158,25 @@ struct zenv {
     PpoState *skppo[2] = { nullptr, nullptr };
     // the Options agent's two learners (zenv_opppo_init): [0] the low level, [1] the high level
     PpoState *opppo[2] = { nullptr, nullptr };
+    // DIAYN's inverse-model learner (zenv_diayn_init); it never touches the acting discriminator (skinv)
+    PpoState *diayn = nullptr;
+    // zenv_diayn_samples: the kept sample indexes of the last zenv_collect_skill (ZENV_F_DIAYN_SAMPLES), capacity
+    // diayn_cap, and the compaction's block counts behind them in the same allocation; diayn_kept < 0: not taken since
+    // the last collection (every collector resets it)
+    void *diayn_mem = nullptr;
+    int32_t *diayn_list = nullptr, *diayn_blocks = nullptr;
+    int64_t diayn_cap = 0, diayn_kept = -1;
+    // the learned skill prior (zenv_diayn_prior_init): logits, Adam's moments and step count on the host; the device
+    // histogram [32 counters, the compaction's total] and its page-locked flag (a pick outside [0, S))
+    struct {
+        bool ready = false;
+        int S = 0;
+        double lr = 0.0, adam_eps = 0.0;
+        int64_t step = 0;
+        float logits[32] = {}, exp_avg[32] = {}, exp_avg_sq[32] = {};
+    } prior;
+    int32_t *diayn_counts = nullptr;
+    int *diayn_flag = nullptr;
     // goal-conditioned variant (zenv_goal_enable)
     bool goal_enabled = false;
     bool order_enabled = false;   // solver-ordered variant (zenv_order_enable)
@@ -222,5 +241,5 @@ ZENV_INTERNAL void ppo_free(zenv *h);
 ZENV_INTERNAL int ppo_index_check(zenv *h);
 // ZENV_F_PPO_STATS (which = 0), ZENV_F_HPPO_LO_STATS (1), ZENV_F_HPPO_HI_STATS (2), ZENV_F_XYPPO_LO_STATS (3),
 // ZENV_F_XYPPO_HI_STATS (4), ZENV_F_SKPPO_LO_STATS (5), ZENV_F_SKPPO_HI_STATS (6), ZENV_F_OPPPO_LO_STATS (7),
-// ZENV_F_OPPPO_HI_STATS (8): the buffer and the bytes the last update call of that learner filled
+// ZENV_F_OPPPO_HI_STATS (8), ZENV_F_DIAYN_STATS (9): the buffer and the bytes the last update call of that learner filled
 ZENV_INTERNAL void *ppo_stats(const zenv *h, int which, int64_t *bytes);

@@ -2,7 +2,8 @@
 // experience buffers (zenv_ppo_*) and the Zone-goals agent's two (zenv_hppo_*, level 0 = low, 1 = high) on the records
 // of zenv_collect_hier, the xy-goals agent's two (zenv_xyppo_*, the same levels) on the records of zenv_collect_xy, and
 // the fixed-length-skills agent's two (zenv_skppo_*) on the records of zenv_collect_skill, and the Options agent's two
-// (zenv_opppo_*) on the records of zenv_collect_option.
+// (zenv_opppo_*) on the records of zenv_collect_option, and DIAYN's inverse model's (zenv_diayn_*, no level) on the
+// records of zenv_collect_skill, with the kept-sample list and the learned skill prior's step beside it.
 // One PpoState each, the same code.  The kernels: ppo_update.hip.  The networks that act and collect: zenv_agents.cpp.
 #include <algorithm>
 #include <cmath>
@@ -49,6 +50,8 @@ NetKind sk_lo(int S) { return NetKind{ 8 + S, PPO_HEAD_GAUSSIAN, PPO_LOSS_ACTION
 NetKind sk_hi(int S) { return NetKind{ 8, PPO_HEAD_SKILLS, PPO_LOSS_ACTION, S }; }
 // the Options agent: the skills agent's high level as it stands (sk_hi), its low level with a third action component
 NetKind op_lo(int S) { return NetKind{ 8 + S, PPO_HEAD_GAUSSIAN, PPO_LOSS_ACTION, S, 3 }; }
+// DIAYN's inverse model: the flat encoder with a ReLU on it under an S-way head, no enc_ layer and no critic
+NetKind inv_kind(int S) { return NetKind{ 8, PPO_HEAD_INVERSE, PPO_LOSS_ACTION, S }; }
 
 // element counts of the tensors for hidden size h and zone rows of F features: zenv_mlp_weights' member order (20; the
 // Zone-goals low level's 18 with XD = 10; the skills agent's low level's 18 with XD = 8 + S and [h, h + S] in
@@ -63,7 +66,9 @@ void tensor_counts(int h, int F, NetKind k, int64_t (&count)[PPO_MAX_TENSORS])
                                          hh, h, h, 1, 0, 0, 0, 0 };
     const int64_t d[PPO_MAX_TENSORS] = { h * (X + F), h, hh, h, hh, h, h * (X + h), h, hh, h, S * h, S,
                                          hh, h, h, 1, 0, 0, 0, 0 };
-    const int64_t *src = k.head == PPO_HEAD_ZONES ? z : k.head == PPO_HEAD_SKILLS ? d : c;
+    // zenv_skill_inverse_weights' 10: the encoder's eight, combine_net.2 [S, h] / [S]
+    const int64_t v[PPO_MAX_TENSORS] = { h * (X + F), h, hh, h, hh, h, h * (X + h), h, S * h, S };
+    const int64_t *src = k.head == PPO_HEAD_ZONES ? z : k.head == PPO_HEAD_SKILLS ? d : k.head == PPO_HEAD_INVERSE ? v : c;
     std::copy(src, src + PPO_MAX_TENSORS, count);
 }
 
@@ -79,7 +84,7 @@ struct Layout {
     int HP, KC, LDC, rp, bp;
     int64_t chunks;
     // floats of every workspace piece, in carving order
-    int64_t img[PPO_N_IMAGES], a1, p, c, ci, pre, ss, partial, u, l, dz;
+    int64_t img[PPO_N_IMAGES], a1, p, hd, c, ci, pre, ss, partial, u, l, dz;
     int64_t total;
 };
 
@@ -100,21 +105,26 @@ Layout layout_for(int h, int Z, int F, int max_batch, NetKind k)
     l.img[PPO_I_WE] = l.img[PPO_I_WV] = HP * l.LDC;
     l.img[PPO_I_HA] = l.img[PPO_I_HV] = 32 * HP;
     l.img[PPO_T_HA] = l.img[PPO_T_HV] = HP * 32;
+    // DIAYN's inverse model has no enc_ layer and no critic: no image of theirs, no Ha / Hc, no PRE / DH
+    const bool inverse = k.head == PPO_HEAD_INVERSE;
+    if (inverse)
+        for (int i : { PPO_I_WE, PPO_I_WV, PPO_I_HV, PPO_T_WE, PPO_T_WV, PPO_T_HV }) l.img[i] = 0;
     l.a1 = rp * HP;
     l.p = bp * HP;
+    l.hd = inverse ? 0 : bp * HP;
     l.c = bp * l.LDC;
     l.ci = bp * KC;
-    l.pre = bp * 32;
+    l.pre = inverse ? 0 : bp * 32;
     l.ss = bp * 8;
     // the widest product of the learner: a partial is [HP][its columns rounded up to 32]; HP + 32 covers every product
     // but combine_net_'s, whose KC columns pass HP + 32 once the own ones pass 32 (the skills agent, S > 24)
     l.partial = l.chunks * HP * std::max<int64_t>(HP + 32, (KC + 31) / 32 * 32);
     if (k.head == PPO_HEAD_ZONES) l.u = rp * HP, l.l = rp * 32;
-    if (k.head == PPO_HEAD_SKILLS) l.l = bp * 32;       // the S logits of a sample, their deltas
+    if (k.head == PPO_HEAD_SKILLS || inverse) l.l = bp * 32;       // the S logits of a sample, their deltas
     // DZ, in floats: a double per zone row (the per-zone head), or 2 NA + 1 per sample (the skills and Options agents' low
-    // level)
-    l.dz = k.tail() ? bp * 2 * (2 * k.NA + 1) : l.l / 16;
-    l.total = 2 * l.a1 + 3 * l.p + l.c + l.ci + 2 * l.pre + l.ss + l.partial + l.u + 2 * l.l + l.dz;
+    // level), or S per sample (the inverse model)
+    l.dz = k.tail() ? bp * 2 * (2 * k.NA + 1) : inverse ? bp * 2 * k.S : l.l / 16;
+    l.total = 2 * l.a1 + l.p + 2 * l.hd + l.c + l.ci + 2 * l.pre + l.ss + l.partial + l.u + 2 * l.l + l.dz;
     for (int i = 0; i < PPO_N_IMAGES; ++i) l.total += l.img[i];
     return l;
 }
@@ -128,10 +138,11 @@ int learner_check(const zenv_config *cfg, int h_dim, const float *const *t, NetK
     if (h_dim < 1 || h_dim > 191) return fail(ZENV_E_ARG, "%sh_dim %d outside [1, 191]", who, h_dim);
     if (cfg->num_zones < 1 || cfg->num_zones > ZENV_MAX_ZONES)
         return fail(ZENV_E_ARG, "num_zones %d outside [1, %d]", cfg->num_zones, ZENV_MAX_ZONES);
-    const int critic = k.head != PPO_HEAD_GAUSSIAN ? PPO_CRITIC_W1 - 2 : PPO_CRITIC_W1;
+    const bool inverse = k.head == PPO_HEAD_INVERSE;    // ten tensors, no critic
+    const int critic = inverse ? PPO_INV_TENSORS : k.head != PPO_HEAD_GAUSSIAN ? PPO_CRITIC_W1 - 2 : PPO_CRITIC_W1;
     for (int i = 0; i < critic; ++i)
         if (!t[i]) return fail(ZENV_E_ARG, "%sa tensor of the weights is null", who);
-    for (int i = critic; i < critic + 4; ++i)
+    for (int i = critic; i < critic + (inverse ? 0 : 4); ++i)
         if (!t[i]) return fail(ZENV_E_ARG, "%sthe update needs the critic: critic_w1 / _b1 / _w2 / _b2", who);
     const bool hier = !k.flat();
     if (hier && pc->distributional_value)
@@ -261,6 +272,26 @@ extern "C" int zenv_opppo_check(const zenv_config *cfg, const zenv_option_weight
     return learner_check(cfg, w->h_dim, th, sk_hi(w->n_skills), hi, "high level: ");
 }
 
+static void inverse_tensor_list(const zenv_skill_inverse_weights *w, const float *(&t)[PPO_MAX_TENSORS])
+{
+    const float *l[PPO_MAX_TENSORS] = { w->zone_w1, w->zone_b1, w->zone_w2, w->zone_b2, w->zone_w3, w->zone_b3,
+                                        w->comb_w1, w->comb_b1, w->comb_w2, w->comb_b2 };
+    std::copy(l, l + PPO_MAX_TENSORS, t);
+}
+
+extern "C" int zenv_diayn_check(const zenv_config *cfg, const zenv_skill_inverse_weights *w, const zenv_ppo_config *pc)
+{
+    if (!cfg || !w || !pc) return fail(ZENV_E_ARG, "null argument");
+    if (w->n_skills < 1 || w->n_skills > kMaxSkills)
+        return fail(ZENV_E_ARG, "n_skills %d outside [1, %d]", w->n_skills, kMaxSkills);
+    if (w->zone_feat != zenv_zone_feat(cfg))
+        return fail(ZENV_E_ARG, "zone_feat %d: the handle's zone rows have %d features", w->zone_feat, zenv_zone_feat(cfg));
+    if (w->precision != ZENV_MLP_F32) return fail(ZENV_E_ARG, "precision %d: the inverse model is float32 only", w->precision);
+    const float *t[PPO_MAX_TENSORS];
+    inverse_tensor_list(w, t);
+    return learner_check(cfg, w->h_dim, t, inv_kind(w->n_skills), pc, "inverse model: ");
+}
+
 static void learner_free(PpoState *&s)
 {
     if (!s) return;
@@ -282,27 +313,39 @@ void ppo_free(zenv *h)
     learner_free(h->skppo[1]);
     learner_free(h->opppo[0]);
     learner_free(h->opppo[1]);
+    learner_free(h->diayn);
+    if (h->diayn_mem) (void)hipFree(h->diayn_mem);
+    if (h->diayn_counts) (void)hipFree(h->diayn_counts);
+    if (h->diayn_flag) (void)hipHostFree(h->diayn_flag);
+    h->diayn_mem = nullptr, h->diayn_list = h->diayn_blocks = h->diayn_counts = nullptr, h->diayn_flag = nullptr;
+    h->diayn_cap = 0, h->diayn_kept = -1;
+    h->prior.ready = false;
 }
 
 int ppo_index_check(zenv *h)
 {
     bool bad = false;
     for (PpoState *s : { h->ppo, h->hppo[0], h->hppo[1], h->xyppo[0], h->xyppo[1], h->skppo[0], h->skppo[1],
-                          h->opppo[0], h->opppo[1] })
+                          h->opppo[0], h->opppo[1], h->diayn })
         if (s && s->net.bad_index && *(volatile int *)s->net.bad_index) {
             *(volatile int *)s->net.bad_index = 0;
             bad = true;
         }
+    if (h->diayn_flag && *(volatile int *)h->diayn_flag) {      // the skill prior's histogram met a pick outside [0, S)
+        *(volatile int *)h->diayn_flag = 0;
+        bad = true;
+    }
     if (!bad) return ZENV_OK;
     return fail(ZENV_E_ARG, "a device-resident minibatch index lay outside [0, envs x frames), or a recorded goal was "
-                            "not among its row's available goals, or a recorded skill lay outside [0, n_skills): the sample was dropped and the update since the last "
+                            "not among its row's available goals, or a recorded skill lay outside [0, n_skills), or the inverse model's sample was one the collection did not keep: the sample was dropped and the update since the last "
                             "synchronising call is invalid");
 }
 
 void *ppo_stats(const zenv *h, int which, int64_t *bytes)
 {
     const PpoState *s = which == 0 ? h->ppo : which <= 2 ? h->hppo[which - 1] : which <= 4 ? h->xyppo[which - 3]
-                                                 : which <= 6 ? h->skppo[which - 5] : h->opppo[which - 7];
+                                                 : which <= 6 ? h->skppo[which - 5] : which <= 8 ? h->opppo[which - 7]
+                                                 : h->diayn;
     *bytes = s ? (int64_t)s->stats_rows * kPpoStats * 4 : 0;
     return s ? s->stats : nullptr;
 }
@@ -319,10 +362,11 @@ static int learner_create(zenv *h, PpoState *&slot, int h_dim, const float *cons
     const Layout l = layout_for(h_dim, h->p.Z, h->p.F, pc->max_batch, k);
     n.h = h_dim, n.HP = l.HP, n.F = h->p.F, n.Z = h->p.Z, n.K1 = k.XD + h->p.F, n.KC = l.KC;
     n.XD = k.XD, n.W1C = k.w1c(h->p.F), n.head = k.head, n.loss = k.loss, n.S = k.S, n.NA = k.NA, n.LDC = l.LDC;
-    n.cr = k.head != PPO_HEAD_GAUSSIAN ? PPO_CRITIC_W1 - 2 : PPO_CRITIC_W1;
+    const bool inverse = k.head == PPO_HEAD_INVERSE;    // no critic: cr names a tensor that exists and is never read
+    n.cr = inverse ? 0 : k.head != PPO_HEAD_GAUSSIAN ? PPO_CRITIC_W1 - 2 : PPO_CRITIC_W1;
     n.split_reduce = k.flat() ? 0 : 1;                  // the hierarchical agents' learners
     n.dist = pc->distributional_value ? 1 : 0;
-    n.n_tensors = k.head != PPO_HEAD_GAUSSIAN ? 16 : n.dist ? 20 : 18;
+    n.n_tensors = inverse ? PPO_INV_TENSORS : k.head != PPO_HEAD_GAUSSIAN ? 16 : n.dist ? 20 : 18;
     n.max_batch = pc->max_batch;
     s->lr = pc->lr;
     n.hyper = PpoHyper{ (float)pc->lr, (float)pc->adam_eps, (float)pc->clip_eps, (float)pc->entropy_coef,
@@ -353,7 +397,7 @@ static int learner_create(zenv *h, PpoState *&slot, int h_dim, const float *cons
     auto take = [&f](int64_t count) { float *p = f; f += count; return p; };
     for (int i = 0; i < PPO_N_IMAGES; ++i) n.img[i] = take(l.img[i]);
     n.A1 = take(l.a1), n.A2 = take(l.a1);
-    n.P = take(l.p), n.C = take(l.c), n.Ha = take(l.p), n.Hc = take(l.p);
+    n.P = take(l.p), n.C = take(l.c), n.Ha = take(l.hd), n.Hc = take(l.hd);
     n.CI = take(l.ci);
     n.PRE = take(l.pre), n.DH = take(l.pre);
     n.SS = take(l.ss);
@@ -440,9 +484,20 @@ extern "C" int zenv_opppo_init(zenv_t *h, const zenv_option_weights *w, const ze
     return rc;
 }
 
+extern "C" int zenv_diayn_init(zenv_t *h, const zenv_skill_inverse_weights *w, const zenv_ppo_config *pc)
+{
+    if (!h || !w || !pc) return fail(ZENV_E_ARG, "null argument");
+    if (int rc = zenv_diayn_check(&h->cfg, w, pc)) return rc;
+    const float *t[PPO_MAX_TENSORS];
+    inverse_tensor_list(w, t);
+    const int rc = learner_create(h, h->diayn, w->h_dim, t, inv_kind(w->n_skills), pc);
+    if (rc) learner_free(h->diayn);     // no half-built learner
+    return rc;
+}
+
 namespace {
 
-enum { AGENT_FLAT = 0, AGENT_HIER = 1, AGENT_XY = 2, AGENT_SKILL = 3, AGENT_OPTION = 4 };
+enum { AGENT_FLAT = 0, AGENT_HIER = 1, AGENT_XY = 2, AGENT_SKILL = 3, AGENT_OPTION = 4, AGENT_DIAYN = 5 };
 
 // What an entry point works on: the flat learner, or level 0 / 1 of the Zone-goals or the xy-goals pair with the
 // experience they read.
@@ -459,6 +514,11 @@ int find_learner(zenv *h, int level, int agent, Learner &out)
     if (!hier) {
         if (!h->ppo) return fail(ZENV_E_STATE, "zenv_ppo_init first");
         out = Learner{ h->ppo, -1, AGENT_FLAT };
+        return ZENV_OK;
+    }
+    if (agent == AGENT_DIAYN) {         // one learner: the inverse model's
+        if (!h->diayn) return fail(ZENV_E_STATE, "zenv_diayn_init first");
+        out = Learner{ h->diayn, 0, AGENT_DIAYN };
         return ZENV_OK;
     }
     if (level != 0 && level != 1) return fail(ZENV_E_ARG, "level %d: 0 is the low level, 1 the high level", level);
@@ -515,6 +575,53 @@ int learner_set_step(const Learner &l, int64_t step)
     return ZENV_OK;
 }
 
+// what DIAYN's two updates read: a completed zenv_collect_skill of at least two frames
+int diayn_records(const zenv *h)
+{
+    if (!h->exp_mem || !h->exp_skill || h->hi_kind != 1 || !h->sk_mem || h->sk.T != h->exp.T || h->hi_m < 1)
+        return fail(ZENV_E_STATE, "zenv_collect_skill first: the ZENV_F_EXP_* / ZENV_F_LO_* / ZENV_F_HI_* buffers do "
+                                  "not hold its records");
+    if (h->exp.T < 2)
+        return fail(ZENV_E_STATE, "a collection of one frame has no (next observation, skill) pair for the inverse model");
+    return ZENV_OK;
+}
+
+// The kept samples of the handle's records into diayn_list (k_inv_count / _scan / _scatter), their number into
+// diayn_kept; waits for the device.
+int diayn_compact(zenv *h)
+{
+    if (int rc = diayn_records(h)) return rc;
+    if (int rc = use_device(h)) return rc;
+    const int64_t samples = (int64_t)h->n_env * (h->exp.T - 1);
+    const int64_t blocks = (samples + kInvBlock - 1) / kInvBlock;
+    if (h->diayn_cap < samples) {
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        if (h->diayn_mem) HIP_TRY(hipFree(h->diayn_mem));
+        h->diayn_mem = nullptr, h->diayn_list = h->diayn_blocks = nullptr, h->diayn_cap = 0, h->diayn_kept = -1;
+        HIP_TRY(hipMalloc(&h->diayn_mem, (size_t)(samples + blocks + 2) * sizeof(int32_t)));
+        h->diayn_list = static_cast<int32_t *>(h->diayn_mem);
+        h->diayn_blocks = h->diayn_list + samples;      // [blocks + 1], then the total
+        h->diayn_cap = samples;
+    }
+    h->diayn_kept = -1;
+    int32_t *total = h->diayn_blocks + (h->diayn_cap + kInvBlock - 1) / kInvBlock + 1;
+    HIP_TRY(launch_inv_compact(h->exp.mask, h->n_env, h->exp.T, h->diayn_blocks, h->diayn_list, total, h->stream));
+    int32_t kept = 0;
+    HIP_TRY(hipMemcpyAsync(&kept, total, sizeof(kept), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->diayn_kept = kept;
+    return ZENV_OK;
+}
+
+// minibatch / epoch: ZENV_E_STATE when the collection kept no sample (the list is taken here if it was not yet)
+int diayn_any_kept(zenv *h)
+{
+    if (h->diayn_kept < 0)
+        if (int rc = diayn_compact(h)) return rc;
+    if (h->diayn_kept == 0) return fail(ZENV_E_STATE, "the last zenv_collect_skill kept no sample for the inverse model");
+    return ZENV_OK;
+}
+
 // the experience the learner gathers from, and how many sample indexes it has; ZENV_E_STATE when the handle holds none
 // of the learner's kind
 int learner_exp(const zenv *h, const Learner &l, PpoExp &x, int64_t &samples)
@@ -525,6 +632,18 @@ int learner_exp(const zenv *h, const Learner &l, PpoExp &x, int64_t &samples)
         x = PpoExp{ e.obs, e.zone_obs, e.action, e.log_prob, e.value, e.advantage, e.returnn, h->n_env, e.T, nullptr,
                     nullptr, nullptr };
         samples = (int64_t)h->n_env * e.T;
+        return ZENV_OK;
+    }
+    if (l.agent == AGENT_DIAYN) {
+        if (int rc = diayn_records(h)) return rc;
+        if (!h->skill_ready || h->skill.S != l.s->net.S)
+            return fail(ZENV_E_STATE, "the records are of an agent with another number of skills than the learner's %d",
+                        l.s->net.S);
+        // the pairs (obs of frame f + 1, skill of frame f), f in 0 .. T-2, where the mask of frame f + 1 is not 0
+        // (_hier_policy_opt.py:193-199)
+        x = PpoExp{ e.obs, e.zone_obs, nullptr, nullptr, nullptr, nullptr, nullptr, h->n_env, e.T - 1, nullptr, nullptr,
+                    nullptr, h->sk.lo_skill, nullptr, nullptr, 1, e.mask };
+        samples = (int64_t)h->n_env * (e.T - 1);
         return ZENV_OK;
     }
     if (l.agent == AGENT_XY) {
@@ -937,4 +1056,142 @@ extern "C" int zenv_opppo_epoch(zenv_t *h, int level, const int32_t *order, int 
     if (!h || !order) return fail(ZENV_E_ARG, "null argument");
     LEARNER(h, level, AGENT_OPTION);
     return learner_epoch(h, l, order, total, batch_size, on_device);
+}
+
+// ---- DIAYN: the inverse model's learner (one: no level) and the learned skill prior
+extern "C" int zenv_diayn_tensor(zenv_t *h, int which, int index, void **dev_ptr, int64_t *count)
+{
+    if (!h || !dev_ptr || !count) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, 0, AGENT_DIAYN);
+    return learner_tensor(l, which, index, dev_ptr, count);
+}
+extern "C" int zenv_diayn_read(zenv_t *h, int which, int index, float *dst)
+{
+    if (!dst) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, 0, AGENT_DIAYN);
+    return learner_copy(h, l, which, index, dst, true);
+}
+extern "C" int zenv_diayn_write(zenv_t *h, int which, int index, const float *src)
+{
+    if (!src) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, 0, AGENT_DIAYN);
+    return learner_copy(h, l, which, index, const_cast<float *>(src), false);
+}
+extern "C" int zenv_diayn_get_step(zenv_t *h, int64_t *step)
+{
+    if (!h || !step) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, 0, AGENT_DIAYN);
+    *step = l.s->step;
+    return ZENV_OK;
+}
+extern "C" int zenv_diayn_set_step(zenv_t *h, int64_t step)
+{
+    LEARNER(h, 0, AGENT_DIAYN);
+    return learner_set_step(l, step);
+}
+extern "C" int zenv_diayn_samples(zenv_t *h, int64_t *count)
+{
+    if (!h || !count) return fail(ZENV_E_ARG, "null argument");
+    if (int rc = diayn_compact(h)) return rc;
+    *count = h->diayn_kept;
+    return mlp_range_check(h);
+}
+extern "C" int zenv_diayn_minibatch(zenv_t *h, const int32_t *idx, int count, int idx_on_device, int apply)
+{
+    if (!h || !idx) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, 0, AGENT_DIAYN);
+    if (int rc = diayn_any_kept(h)) return rc;
+    return learner_minibatch(h, l, idx, count, idx_on_device, apply);
+}
+extern "C" int zenv_diayn_apply(zenv_t *h)
+{
+    LEARNER(h, 0, AGENT_DIAYN);
+    return learner_apply(h, l);
+}
+extern "C" int zenv_diayn_epoch(zenv_t *h, const int32_t *order, int total, int batch_size, int on_device)
+{
+    if (!h || !order) return fail(ZENV_E_ARG, "null argument");
+    LEARNER(h, 0, AGENT_DIAYN);
+    if (int rc = diayn_any_kept(h)) return rc;
+    return learner_epoch(h, l, order, total, batch_size, on_device);
+}
+
+extern "C" int zenv_diayn_prior_init(zenv_t *h, const float *logits, int n_skills, double lr, double adam_eps)
+{
+    if (!h || !logits) return fail(ZENV_E_ARG, "null argument");
+    if (n_skills < 1 || n_skills > kMaxSkills) return fail(ZENV_E_ARG, "n_skills %d outside [1, %d]", n_skills, kMaxSkills);
+    for (double v : { lr, adam_eps })
+        if (bad_hyper(v)) return fail(ZENV_E_ARG, "a hyper-parameter is negative or not finite (%g)", v);
+    for (int s = 0; s < n_skills; ++s)
+        if (!std::isfinite(logits[s])) return fail(ZENV_E_ARG, "logits[%d] is not finite", s);
+    if (int rc = use_device(h)) return rc;
+    if (!h->diayn_counts) HIP_TRY(hipMalloc((void **)&h->diayn_counts, 32 * sizeof(int32_t)));
+    if (!h->diayn_flag) {
+        HIP_TRY(hipHostMalloc((void **)&h->diayn_flag, sizeof(int), hipHostMallocDefault));
+        *h->diayn_flag = 0;
+    }
+    auto &p = h->prior;
+    p = {};
+    p.S = n_skills, p.lr = lr, p.adam_eps = adam_eps;
+    std::copy(logits, logits + n_skills, p.logits);
+    p.ready = true;
+    return ZENV_OK;
+}
+
+// update_skill_prior (_hier_policy_opt.py:449-464): one Adam step on the mean cross-entropy of the logits against the
+// M picks of the last zenv_collect_skill.  d loss / d logit_s = softmax(logits)_s - count_s / M, formed in double from
+// the device histogram and rounded to float32; the step in float32 as k_ppo_adam forms it.
+extern "C" int zenv_diayn_prior_update(zenv_t *h)
+{
+    if (!h) return fail(ZENV_E_ARG, "null handle");
+    auto &p = h->prior;
+    if (!p.ready) return fail(ZENV_E_STATE, "zenv_diayn_prior_init first");
+    if (!h->exp_mem || !h->exp_skill || h->hi_kind != 1 || !h->sk_mem || h->hi_m < 1)
+        return fail(ZENV_E_STATE, "zenv_collect_skill first: the ZENV_F_HI_* rows do not hold its picks (M = 0)");
+    if (!h->skill_ready || h->skill.S != p.S)
+        return fail(ZENV_E_STATE, "the records are of an agent with another number of skills than the prior's %d", p.S);
+    if (int rc = use_device(h)) return rc;
+    const int S = p.S;
+    HIP_TRY(launch_prior_hist(h->hout.action, h->hi_m, S, h->diayn_counts, h->diayn_flag, h->stream));
+    int32_t counts[32];
+    HIP_TRY(hipMemcpyAsync(counts, h->diayn_counts, sizeof(counts), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    double m = (double)p.logits[0];
+    for (int s = 1; s < S; ++s) m = std::max(m, (double)p.logits[s]);
+    double sum = 0.0;
+    for (int s = 0; s < S; ++s) sum += std::exp((double)p.logits[s] - m);
+    const double lse = m + std::log(sum);
+    p.step += 1;
+    const double bc1 = 1.0 - std::pow(0.9, (double)p.step), bc2 = 1.0 - std::pow(0.999, (double)p.step);
+    const float step_size = (float)(p.lr / bc1), bc2_sqrt = (float)std::sqrt(bc2), eps = (float)p.adam_eps;
+    const float b2 = 0.999f, w1 = (float)(1.0 - 0.9), w2 = (float)(1.0 - 0.999);
+    for (int s = 0; s < S; ++s) {
+        // S = 1: the softmax is exactly 1 and, with every pick counted, the gradient exactly 0
+        const float gr = (float)(std::exp((double)p.logits[s] - lse) - (double)counts[s] / (double)h->hi_m);
+        float mo = p.exp_avg[s], v = p.exp_avg_sq[s];
+        mo = mo + w1 * (gr - mo);
+        v = v * b2 + (w2 * gr) * gr;
+        const float denom = std::sqrt(v) / bc2_sqrt + eps;
+        p.logits[s] = p.logits[s] + ((-step_size) * mo) / denom;
+        p.exp_avg[s] = mo, p.exp_avg_sq[s] = v;
+    }
+    return mlp_range_check(h);
+}
+
+extern "C" int zenv_diayn_prior_read(zenv_t *h, float *logits)
+{
+    if (!h || !logits) return fail(ZENV_E_ARG, "null argument");
+    if (!h->prior.ready) return fail(ZENV_E_STATE, "zenv_diayn_prior_init first");
+    std::copy(h->prior.logits, h->prior.logits + h->prior.S, logits);
+    return ZENV_OK;
+}
+
+extern "C" int zenv_diayn_prior_write(zenv_t *h, const float *logits)
+{
+    if (!h || !logits) return fail(ZENV_E_ARG, "null argument");
+    if (!h->prior.ready) return fail(ZENV_E_STATE, "zenv_diayn_prior_init first");
+    for (int s = 0; s < h->prior.S; ++s)
+        if (!std::isfinite(logits[s])) return fail(ZENV_E_ARG, "logits[%d] is not finite", s);
+    std::copy(logits, logits + h->prior.S, h->prior.logits);
+    return ZENV_OK;
 }

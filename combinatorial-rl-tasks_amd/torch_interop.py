@@ -423,6 +423,121 @@ class TorchZoneEnv:
     def skppo_update(self, epochs, batch_size, hi_epochs, hi_batch_size, rng):
         return self.env.skppo_update(epochs, batch_size, hi_epochs, hi_batch_size, rng)
 
+    # ------------------------------------------------------------------ DIAYN's inverse model and learned skill prior
+    def diayn_init(self, inverse_state_dict, n_skills, prior_logits=None, prior=None, **hyper):
+        """``ZoneVecEnv.diayn_init`` from an InverseModel state_dict (tensors on any device), with the four arenas as flat
+        float32 CUDA tensors ALIASING device memory in ``self.diayn_arenas`` (valid until the next diayn_init or
+        ``env.close()``)."""
+        from .vec_env import inverse_tensors_from_state_dict
+        if not any(k in inverse_state_dict for k in nat.SKILL_INVERSE_TENSORS):
+            inverse_state_dict = inverse_tensors_from_state_dict(inverse_state_dict, n_skills)
+        self.env.diayn_init(inverse_state_dict, n_skills, prior_logits=prior_logits, prior=prior, **hyper)
+        with self._torch.cuda.device(self.device):
+            self.diayn_arenas = {}
+            for name, which in (("param", nat.PPO_PARAM), ("grad", nat.PPO_GRAD), ("exp_avg", nat.PPO_EXP_AVG),
+                                ("exp_avg_sq", nat.PPO_EXP_AVG_SQ)):
+                ptr, count = self.env.diayn_tensor_ptr(which, -1)
+                self.diayn_arenas[name] = self._alias_ptr(ptr, (count,))
+
+    def diayn_tensors(self, which=nat.PPO_PARAM):
+        """zenv_skill_inverse_weights name -> CUDA tensor ALIASING that tensor of the arena, in its state_dict shape."""
+        learner = self.env._diayn_learner()
+        with self._torch.cuda.device(self.device):
+            return {name: self._alias_ptr(learner.tensor_ptr(which, i)[0], learner.shapes[name])
+                    for i, name in enumerate(learner.keys)}
+
+    def diayn_set_tensors(self, tensors, which=nat.PPO_PARAM):
+        views = self.diayn_tensors(which)
+        for name, src in tensors.items():
+            views[name].copy_(self._torch.as_tensor(src))
+
+    def diayn_state_dict(self):
+        """InverseModel's state_dict as CUDA tensors ALIASING the parameter arena."""
+        views = self.diayn_tensors()
+        return {key: views[name] for name, key in self.env._diayn_learner().keys.items()}
+
+    def diayn_load_state_dict(self, state_dict):
+        for key, dst in self.diayn_state_dict().items():
+            dst.copy_(state_dict[key])
+
+    def diayn_tensor_ptr(self, which, index):
+        return self.env.diayn_tensor_ptr(which, index)
+
+    def diayn_get_step(self):
+        return self.env.diayn_get_step()
+
+    def diayn_set_step(self, step):
+        self.env.diayn_set_step(step)
+
+    def diayn_optimizer_state(self):
+        """``ZoneVecEnv.diayn_optimizer_state`` with the moments as CUDA copies."""
+        torch = self._torch
+        out = self.env.diayn_optimizer_state()
+        out["state"] = {i: {"step": torch.tensor(s["step"]), "exp_avg": torch.from_numpy(s["exp_avg"]).to(self.device),
+                            "exp_avg_sq": torch.from_numpy(s["exp_avg_sq"]).to(self.device)}
+                        for i, s in out["state"].items()}
+        return out
+
+    def diayn_load_optimizer_state(self, state):
+        self.env.diayn_load_optimizer_state(state)
+
+    def diayn_samples(self):
+        """int32 CUDA tensor [count] ALIASING the kept sample indexes of the last ``collect_skills`` (compacted on the
+        device; the call waits for the count).  Valid until the next diayn_samples or collection."""
+        count = self.env.diayn_samples_on_device()
+        with self._torch.cuda.device(self.device):
+            if not count:
+                return self._torch.empty(0, dtype=self._torch.int32, device=self.device)
+            return self._alias(nat.F_DIAYN_SAMPLES, (count,), np.int32)
+
+    def diayn_minibatch(self, idx, apply=False):
+        """``ZoneVecEnv.diayn_minibatch``; idx may be an int32 CUDA tensor (never copied, checked on the device)."""
+        ptr, count = self._ppo_index_arg(idx)
+        self.env.diayn_minibatch(ptr, apply=apply, count=count)
+
+    def diayn_apply(self):
+        self.env.diayn_apply()
+
+    def diayn_epoch(self, order, batch_size):
+        """``ZoneVecEnv.diayn_epoch``; order may be an int32 CUDA tensor."""
+        ptr, count = self._ppo_index_arg(order)
+        self.env.diayn_epoch(ptr, batch_size, count=count)
+
+    def diayn_stats(self):
+        """float32 CUDA tensor [minibatches, 6] ALIASING the statistics of the last diayn_minibatch / diayn_epoch (not
+        synchronised)."""
+        rows = self.env.field_bytes(nat.F_DIAYN_STATS) // 24
+        with self._torch.cuda.device(self.device):
+            return self._alias(nat.F_DIAYN_STATS, (rows, 6), np.float32)
+
+    def diayn_update(self, epochs, batch_size, generator=None):
+        """``ZoneVecEnv.diayn_update`` with the list, the permutations (``torch.randperm`` from `generator`, a CUDA
+        torch.Generator or None) and the indexing on the device: nothing but the count reaches the host."""
+        torch = self._torch
+        kept = self.diayn_samples()
+        rows = None
+        for e in range(int(epochs)):
+            if not kept.numel():
+                break
+            order = kept[torch.randperm(kept.numel(), device=self.device, generator=generator)].contiguous()
+            self.diayn_epoch(order, batch_size)
+            if e == 0:
+                rows = self.diayn_stats().clone()         # the next epoch overwrites the buffer
+        self.env._diayn_first_epoch = None if rows is None else rows.cpu().numpy()
+        return self.env.diayn_logs()
+
+    def diayn_logs(self):
+        return self.env.diayn_logs()
+
+    def diayn_prior_update(self):
+        return self.env.diayn_prior_update()
+
+    def diayn_prior_logits(self):
+        return self.env.diayn_prior_logits()
+
+    def diayn_publish(self):
+        self.env.diayn_publish()
+
     # ------------------------------------------------------------------ the Options agent's two PPO updates
     def opppo_init(self, hi_state_dict, lo_state_dict, lo=None, hi=None):
         """``ZoneVecEnv.opppo_init`` with each level's four arenas as flat float32 CUDA tensors ALIASING device memory in

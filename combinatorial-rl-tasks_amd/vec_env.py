@@ -23,7 +23,7 @@ from .agents import (_HIER_ENC, _HIER_CRITIC, HIER_HI_KEYS, HIER_LO_KEYS, SKILL_
                      hier_experience_layout, skill_experience_layout, option_experience_layout, skill_num_frames,
                      check_collect_xy_args, xy_experience_layout, ppo_state_dict_keys, ppo_batch_indexes,
                      hppo_state_dict_keys, hppo_batch_indexes, xyppo_state_dict_keys, skppo_state_dict_keys,
-                     opppo_state_dict_keys)
+                     opppo_state_dict_keys, diayn_state_dict_keys, diayn_kept_samples)
 
 _FIELD_DTYPES = {
     nat.F_OBS: np.float32, nat.F_ZONE_OBS: np.float32, nat.F_REWARD: np.float32,
@@ -50,6 +50,7 @@ _FIELD_DTYPES = {
     nat.F_XYPPO_LO_STATS: np.float32, nat.F_XYPPO_HI_STATS: np.float32,
     nat.F_SKPPO_LO_STATS: np.float32, nat.F_SKPPO_HI_STATS: np.float32,
     nat.F_OPPPO_LO_STATS: np.float32, nat.F_OPPPO_HI_STATS: np.float32,
+    nat.F_DIAYN_STATS: np.float32, nat.F_DIAYN_SAMPLES: np.int32,
 }
 
 
@@ -68,8 +69,9 @@ class _Learner:
         self.lr, self.adam_eps, self.stats_field, self.prefix = lr, adam_eps, stats_field, prefix
 
     def _call(self, name, *args):
-        if self.level is None:
-            check(getattr(lib(), "zenv_ppo_" + name)(self._h, *args))
+        if self.level is None:          # the learners without a level: the flat one's and DIAYN's inverse model's
+            prefix = self.prefix if self.prefix == "zenv_diayn_" else "zenv_ppo_"
+            check(getattr(lib(), prefix + name)(self._h, *args))
         else:
             check(getattr(lib(), self.prefix + name)(self._h, int(self.level), *args))
 
@@ -1190,7 +1192,7 @@ class ZoneVecEnv:
         critics: float32 master parameters, gradients, Adam's moments and a workspace per level.  lo / hi: dicts of the
         settings to change from ``SKPPO_LO`` / ``SKPPO_HI``.  `level` in the other skppo_* methods: ``_native.SKPPO_LO``
         = 0, ``SKPPO_HI`` = 1.  Separate from ``load_skills``: ``skppo_publish`` hands the parameters to the acting
-        agent.  The inverse model's and the skill prior's updates stay with the caller."""
+        agent.  The inverse model's and the skill prior's updates are the ``diayn_*`` methods'."""
         tensors = skill_tensors_from_state_dicts(hi_state_dict, lo_state_dict)
         S, h = (int(v) for v in tensors["hi_logit_w"].shape)
         F = int(tensors["hi_zone_w1"].shape[1]) - 8
@@ -1287,6 +1289,159 @@ class ZoneVecEnv:
         mean = np.concatenate(rows).astype(np.float64).mean(axis=0) if rows else np.zeros(6)
         logs.update({"lo_" + n: float(mean[i]) for i, n in names})
         return logs
+
+    # ------------------------------------------------------------------ DIAYN's inverse model and learned skill prior
+    # the example's hyper-parameters (examples/skill_planner_ppo_torch.py; the reference does not clip this optimiser);
+    # clip_eps, entropy_coef and value_loss_coef belong to zenv_ppo_config and are not used
+    DIAYN = dict(lr=3e-4, adam_eps=1e-8, clip_eps=0.0, entropy_coef=0.0, value_loss_coef=0.0, max_grad_norm=math.inf,
+                 max_batch=16384)
+    DIAYN_PRIOR = dict(lr=1e-2, adam_eps=1e-8)
+
+    def _diayn_learner(self):
+        """``_learner`` for the inverse model's."""
+        found = self._learners.get(("diayn", None))
+        return found or _Learner(self._h, None, {}, {}, 0.0, 0.0, nat.F_DIAYN_STATS, "zenv_diayn_")
+
+    def diayn_init(self, inverse_tensors, n_skills, prior_logits=None, prior=None, **hyper):
+        """DIAYN's two remaining updates on the device (main/src/torch_ac/algos/_hier_policy_opt.py:421-464): a learner
+        for InverseModel -- float32 master parameters, gradients, Adam's moments and a workspace -- from its tensors
+        (``inverse_tensors_from_state_dict``; a state_dict is converted) and, with prior_logits (an array of n_skills
+        logits), the learned skill prior with its own Adam state.  hyper: the settings to change from ``DIAYN``; prior:
+        from ``DIAYN_PRIOR``.  Separate from ``load_skill_inverse``: ``diayn_publish`` hands the parameters to the acting
+        discriminator."""
+        if any(k in inverse_tensors for k in nat.SKILL_INVERSE_TENSORS):
+            tensors = {k: _as_host_f32(v) for k, v in inverse_tensors.items()}
+        else:
+            tensors = inverse_tensors_from_state_dict(inverse_tensors, n_skills)
+        S, h = (int(v) for v in np.asarray(tensors["comb_w2"]).shape)
+        if S != int(n_skills):
+            raise ValueError(f"combine_net.2 has {S} outputs, n_skills is {int(n_skills)}")
+        F = int(np.asarray(tensors["zone_w1"]).shape[1]) - 8
+        keys = diayn_state_dict_keys()
+        shapes = inverse_tensor_shapes(h, S, F)
+        w = nat.SkillInverseWeights(h_dim=h, n_skills=S, zone_feat=F, precision=nat.MLP_F32)
+        keep = self._load_weights(w, list(keys), tensors, shapes)                 # alive across the call
+        cfg = nat.PpoConfig(distributional_value=0, **dict(self.DIAYN, **hyper))
+        check(lib().zenv_diayn_init(self._h, C.byref(w), C.byref(cfg)))
+        del keep
+        self._learners[("diayn", None)] = _Learner(self._h, None, keys, shapes, cfg.lr, cfg.adam_eps, nat.F_DIAYN_STATS,
+                                                   "zenv_diayn_")
+        self._diayn_S = S
+        if prior_logits is not None:
+            logits = np.ascontiguousarray(_as_host_f32(prior_logits).reshape(-1))
+            if logits.size != S:
+                raise ValueError(f"prior_logits has {logits.size} entries, n_skills is {S}")
+            p = dict(self.DIAYN_PRIOR, **(prior or {}))
+            check(lib().zenv_diayn_prior_init(self._h, logits.ctypes.data, S, float(p["lr"]), float(p["adam_eps"])))
+
+    def diayn_tensor_ptr(self, which, index):
+        """``ppo_tensor_ptr`` of the inverse model's arenas."""
+        return self._diayn_learner().tensor_ptr(which, index)
+
+    def diayn_tensors(self, which=nat.PPO_PARAM):
+        """Every tensor of the arena as a new host array, under its zenv_skill_inverse_weights name."""
+        return self._diayn_learner().tensors(which)
+
+    def diayn_set_tensors(self, tensors, which=nat.PPO_PARAM):
+        self._diayn_learner().set_tensors(tensors, which)
+
+    def diayn_state_dict(self):
+        """The learner's parameters under InverseModel's names (host copies)."""
+        return self._diayn_learner().state_dict()
+
+    def diayn_load_state_dict(self, state_dict):
+        self._diayn_learner().load_state_dict(state_dict)
+
+    def diayn_optimizer_state(self):
+        """Adam's state in the shape of ``torch.optim.Adam.state_dict()``: parameter i is the i-th of ``parameters()``."""
+        return self._diayn_learner().optimizer_state()
+
+    def diayn_load_optimizer_state(self, state):
+        self._diayn_learner().load_optimizer_state(state)
+
+    def diayn_get_step(self):
+        return self._diayn_learner().get_step()
+
+    def diayn_set_step(self, step):
+        self._diayn_learner().set_step(step)
+
+    def diayn_samples_on_device(self):
+        """Compact the kept sample indexes of the last ``collect_skills`` on the device (``_native.F_DIAYN_SAMPLES``);
+        returns their number.  Waits for the device."""
+        n = C.c_int64()
+        check(lib().zenv_diayn_samples(self._h, C.byref(n)))
+        return n.value
+
+    def diayn_samples(self):
+        """int32 [count]: the sample indexes the inverse model trains on, ascending -- sample i = env * (T - 1) + f pairs
+        the observation of frame f + 1 with the skill of frame f, kept where the mask of frame f + 1 is not 0
+        (``diayn_kept_samples`` is the same rule on the host)."""
+        count = self.diayn_samples_on_device()
+        out = np.empty(count, np.int32)
+        if count:
+            check(lib().zenv_get(self._h, nat.F_DIAYN_SAMPLES, out.ctypes.data, 0))
+        return out
+
+    def diayn_minibatch(self, idx, apply=False, count=None):
+        """``ppo_minibatch`` of the inverse model on the sample indexes idx (entries of ``diayn_samples()``)."""
+        self._diayn_learner().minibatch(idx, apply, count)
+
+    def diayn_apply(self):
+        self._diayn_learner().apply()
+
+    def diayn_epoch(self, order, batch_size, count=None):
+        self._diayn_learner().epoch(order, batch_size, count)
+
+    def diayn_stats(self):
+        """float32 [minibatches, 6] of the last diayn_minibatch / diayn_epoch: column 0 the cross-entropy loss, column
+        5 the gradient norm, columns 1-4 zero.  Waits for the device."""
+        return self._diayn_learner().stats()
+
+    def diayn_update(self, epochs, batch_size, rng):
+        """update_inverse_parameters (main's _hier_policy_opt.py:421-447) on the records of the last ``collect_skills``:
+        every epoch a permutation of the kept samples from the caller's numpy Generator, cut into batches.  Stores and
+        returns ``diayn_logs()``.  With no kept sample the inverse model is left alone and the loss is nan."""
+        kept = self.diayn_samples()
+        rows = None
+        for e in range(int(epochs)):
+            if not kept.size:
+                break
+            self._diayn_learner().epoch(kept[hppo_batch_indexes(kept.size, rng)], batch_size)
+            if e == 0:
+                rows = self.diayn_stats()
+        self._diayn_first_epoch = rows
+        return self.diayn_logs()
+
+    def diayn_logs(self):
+        """{"loss": the mean cross-entropy over the first epoch's minibatches of the last ``diayn_update``}, as the
+        reference logs it; nan when nothing was trained."""
+        rows = getattr(self, "_diayn_first_epoch", None)
+        return {"loss": float(np.asarray(rows, np.float64)[:, 0].mean()) if rows is not None and len(rows) else math.nan}
+
+    def diayn_prior_update(self):
+        """update_skill_prior (main's _hier_policy_opt.py:449-464): one Adam step of the skill prior's logits on the
+        picks of the last ``collect_skills``.  Returns the new logits."""
+        check(lib().zenv_diayn_prior_update(self._h))
+        return self.diayn_prior_logits()
+
+    def diayn_prior_logits(self):
+        """float32 [S]: the learned skill prior's logits -- what the next ``collect_skills`` takes as
+        ``skill_prior_logits``."""
+        S = getattr(self, "_diayn_S", None) or getattr(self, "_skill_n", None) or 32
+        out = np.zeros(32, np.float32)
+        check(lib().zenv_diayn_prior_read(self._h, out.ctypes.data))
+        return out[:S].copy()
+
+    def diayn_set_prior_logits(self, logits):
+        a = np.zeros(32, np.float32)
+        v = _as_host_f32(logits).reshape(-1)
+        a[:v.size] = v
+        check(lib().zenv_diayn_prior_write(self._h, a.ctypes.data))
+
+    def diayn_publish(self):
+        """Hand the learner's parameters to the acting discriminator: read the 10 tensors back and
+        ``load_skill_inverse`` them, so the next ``collect_skills`` takes its diversity reward from them."""
+        self.load_skill_inverse(self.diayn_tensors())
 
     # ------------------------------------------------------------------ the Options agent's two PPO updates
     # the example's hyper-parameters (examples/options_ppo_torch.py; the reference takes the norm and does not clip)

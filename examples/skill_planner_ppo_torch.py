@@ -11,9 +11,10 @@ device agent is reloaded from them.
 
     python examples/skill_planner_ppo_torch.py --env PointTSP-v0 --procs 4096 --skill-len 20 --frames-per-proc 100
 
-``--device-update`` runs the low and the high level's updates in the library as well (``TorchZoneEnv.skppo_init`` /
-``skppo_update`` / ``skppo_publish``: zenv_skppo_*, csrc/ppo_update.hip); the inverse model's and the skill prior's stay
-in torch on the same collection.  Off by default, the torch path is what it was.
+``--device-update`` runs all four updates in the library as well: the low and the high level's (``TorchZoneEnv.skppo_init``
+/ ``skppo_update`` / ``skppo_publish``: zenv_skppo_*, csrc/ppo_update.hip) and the inverse model's and the skill prior's
+(``diayn_init`` / ``diayn_update`` / ``diayn_prior_update`` / ``diayn_publish``: zenv_diayn_*).  Off by default, the
+torch path is what it was.
 """
 import argparse
 import os
@@ -124,8 +125,8 @@ class SkillPlannerPPO:
     """One iteration of the skill planner: collect_experiences on the device, then the four updates of
     _hier_policy_opt.py:265-466 in torch -- lo PPO, hi PPO, the inverse model's cross-entropy, the skill prior's.  With
     device_update the lo and hi PPO run in the library (``skppo_init`` once; then ``collect_skills``, ``skppo_update``,
-    ``skppo_publish`` per iteration, and the modules get the learners' parameters back after every update); the other
-    two stay in torch."""
+    ``skppo_publish`` per iteration, and the modules get the learners' parameters back after every update), and so do
+    the other two (``diayn_init`` once; ``diayn_update``, ``diayn_prior_update``, ``diayn_publish`` per iteration)."""
 
     def __init__(self, tenv, n_skills=5, h=128, skill_len=20, frames_per_proc=100, diversity_coef=0.1, train_hi=True,
                  epochs=4, batch_size=16384, hi_epochs=4, hi_batch_size=4096, inverse_epochs=4,
@@ -160,6 +161,9 @@ class SkillPlannerPPO:
                                     value_loss_coef=hi_value_coef, max_batch=hi_batch_size))
             tenv.env.configure_skills(skill_len)          # the period skppo_publish hands on
             tenv.skppo_publish()
+            tenv.diayn_init(self.inverse.state_dict(), n_skills, prior_logits=self.skill_logits.detach(),
+                            lr=inverse_lr, max_batch=inverse_batch_size)
+            tenv.diayn_publish()
 
     def _batches(self, total, size):
         order = torch.randperm(total, device=self.tenv.device, generator=self.gen)
@@ -170,10 +174,11 @@ class SkillPlannerPPO:
         num_frames) of TorchZoneEnv."""
         if not self.device_update:
             self.tenv.load_skills(self.hi_net.state_dict(), self.lo_net.state_dict(), skill_len=self.L)
-        self.tenv.load_skill_inverse(self.inverse.state_dict(), self.S)
+            self.tenv.load_skill_inverse(self.inverse.state_dict(), self.S)
+        prior = self.tenv.diayn_prior_logits() if self.device_update else self.skill_logits.detach()
         out = self.tenv.collect_skills(self.T, policy_seed=self.seed * 1000003 + self.it, discount=self.discount,
                                        gae_lambda=self.gae_lambda, diversity_coef=self.diversity_coef,
-                                       skill_prior_logits=self.skill_logits.detach(), sample_hi=self.train_hi)
+                                       skill_prior_logits=prior, sample_hi=self.train_hi)
         self.it += 1
         return out
 
@@ -242,10 +247,19 @@ class SkillPlannerPPO:
             hi_sd, lo_sd = self.tenv.skppo_state_dicts()  # the modules follow the learners
             self.hi_net.load_state_dict(hi_sd)
             self.lo_net.load_state_dict(lo_sd)
-        else:
-            logs = {"lo_" + k: v for k, v in self.update_lo_parameters(lo).items()}
-            if self.train_hi:
-                logs.update({"hi_" + k: v for k, v in self.update_hi_parameters(hi).items()})
+            logs.update({"inverse_" + k: v for k, v in
+                         self.tenv.diayn_update(self.inverse_epochs, self.inverse_batch_size, self.gen).items()})
+            new_logits = self.tenv.diayn_prior_update()
+            self.tenv.diayn_publish()
+            self.inverse.load_state_dict(self.tenv.diayn_state_dict())
+            with torch.no_grad():
+                self.skill_logits.copy_(torch.as_tensor(new_logits))
+            probs = F.softmax(self.skill_logits.detach(), dim=0)
+            logs.update({"prior_" + str(i): float(p) for i, p in enumerate(probs)})
+            return logs
+        logs = {"lo_" + k: v for k, v in self.update_lo_parameters(lo).items()}
+        if self.train_hi:
+            logs.update({"hi_" + k: v for k, v in self.update_hi_parameters(hi).items()})
         logs.update({"inverse_" + k: v for k, v in self.update_inverse_parameters(inverse).items()})
         logs.update({"prior_" + k: v for k, v in self.update_skill_prior(hi).items()})
         return logs
@@ -290,7 +304,7 @@ if __name__ == "__main__":
     ap.add_argument("--diversity-coef", type=float, default=0.1)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--device-update", action="store_true",
-                    help="run the low and high level's PPO updates in the library (zenv_skppo_*) instead of torch")
+                    help="run the four updates in the library (zenv_skppo_*, zenv_diayn_*) instead of torch")
     a = ap.parse_args()
     train(a.env, a.procs, a.skill_len, a.frames_per_proc, a.updates, a.n_skills, a.hidden_size, a.diversity_coef,
           a.seed, device_update=a.device_update)

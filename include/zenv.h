@@ -195,7 +195,14 @@ enum {
      */
     ZENV_F_OPPPO_LO_STATS = 81,     /* float32 [minibatches][6] the low level's: ZENV_F_PPO_STATS' columns, value std = 0 */
     ZENV_F_OPPPO_HI_STATS = 82,     /* float32 [minibatches][6] the high level's, the same */
-    ZENV_F_COUNT = 83
+    /* DIAYN's inverse-model learner (zenv_diayn_init): the statistics of the minibatches of its last
+     * zenv_diayn_minibatch (one row) or zenv_diayn_epoch, and the kept sample indexes of the last zenv_diayn_samples; 0
+     * bytes before the first.  Before these two fields,
+     * ZENV_F_COUNT = 83
+     */
+    ZENV_F_DIAYN_STATS = 83,        /* float32 [minibatches][6] column 0 the cross-entropy loss, 5 the gradient norm, 1-4 = 0 */
+    ZENV_F_DIAYN_SAMPLES = 84,      /* int32   [count]          the kept sample indexes, ascending (= env-major) */
+    ZENV_F_COUNT = 85
 };
 
 /* scripted on-device action sources (the build's own; used by bench/tests) */
@@ -925,7 +932,7 @@ int zenv_collect_xy(zenv_t *h, int frames_per_proc, uint64_t policy_seed, uint64
  * back and load them to act with them).  Every reduction runs in a fixed order: the same call from the same state
  * gives the same bits.  The Zone-goals agent's two updates are zenv_hppo_* below, the xy-goals agent's two zenv_xyppo_*,
  * the fixed-length-skills agent's two zenv_skppo_*, the Options agent's two zenv_opppo_*; the updates of DIAYN's
- * inverse model and skill prior are not here. */
+ * inverse model and skill prior are zenv_diayn_*. */
 typedef struct zenv_ppo_config {
     double lr, adam_eps;            /* torch.optim.Adam(lr, eps = adam_eps), betas 0.9 / 0.999 */
     double clip_eps, entropy_coef, value_loss_coef, max_grad_norm;
@@ -1050,7 +1057,7 @@ int zenv_xyppo_epoch(zenv_t *h, int level, const int32_t *order, int total, int 
  * Two more learners, each with its own four arenas, Adam step count, workspace and statistics; `level` 0 is the low
  * level (LoPolicyValueModel), 1 the high level (HighPolicyValueModel), S = init->n_skills.  They read the records of the
  * last zenv_collect_skill in place (DIAYN collects with the same call; its inverse model's and skill prior's updates
- * stay with the caller):
+ * are zenv_diayn_* below):
  *   low:   the flat learner's loss (a recorded log_prob per action component, the entropy's mean over both) on the
  *          network of [obs, onehot(skill)] (8 + S inputs) whose actor.enc_.0.0 and critic.0 read [emb, onehot].  Sample
  *          index i is env i / T, frame i % T of the ZENV_F_EXP_* buffers, all T frames; the skill is ZENV_F_LO_SKILL of
@@ -1134,6 +1141,53 @@ int zenv_opppo_set_step(zenv_t *h, int level, int64_t step);
 int zenv_opppo_minibatch(zenv_t *h, int level, const int32_t *idx, int count, int idx_on_device, int apply);
 int zenv_opppo_apply(zenv_t *h, int level);
 int zenv_opppo_epoch(zenv_t *h, int level, const int32_t *order, int total, int batch_size, int on_device);
+
+/* ---- DIAYN's inverse model and learned skill prior on the device: update_inverse_parameters / update_skill_prior,
+ * main/src/torch_ac/algos/_hier_policy_opt.py:421-464 ----
+ * One more learner, with its own four arenas, Adam step count, workspace and statistics: InverseModel
+ * (zenv_skill_inverse_weights' 10 tensors in member order: the flat encoder, a ReLU on combine_net.0, combine_net.2 as
+ * an S-way head; no critic) under CrossEntropyLoss(logits, skill).mean(), Adam without a clip (max_grad_norm = +inf;
+ * clip_eps, entropy_coef and value_loss_coef of zenv_ppo_config are checked and not used).  It reads the records of the
+ * last zenv_collect_skill in place.  Sample index i in [0, N (T - 1)) is env i / (T - 1), frame f = i % (T - 1): the
+ * observation and zone rows of frame f + 1 with the skill (ZENV_F_LO_SKILL) of frame f, kept where ZENV_F_EXP_MASK of
+ * frame f + 1 is not 0 (_hier_policy_opt.py:193-199).  zenv_diayn_samples compacts the kept indexes on the device,
+ * ascending -- the reference's env-major order -- into ZENV_F_DIAYN_SAMPLES, waits and returns their number: callers
+ * permute [0, count), index the list with the permutation and pass the sample indexes to the update calls.  The list is
+ * of the records it was taken from: the next collection empties it.  The learner never touches the acting
+ * discriminator: read the parameters back and zenv_skill_inverse_load them.  Statistics: ZENV_F_DIAYN_STATS. */
+/* On the host alone: ZENV_E_ARG for h_dim outside 1 .. 191, n_skills outside 1 .. 32, a zone_feat other than
+ * zenv_zone_feat(cfg), a null tensor, a precision other than ZENV_MLP_F32, distributional_value != 0, a negative or
+ * non-finite hyper-parameter (max_grad_norm = +inf excepted), max_batch < 1, a workspace of 2^31 floats or more. */
+int zenv_diayn_check(const zenv_config *cfg, const zenv_skill_inverse_weights *init, const zenv_ppo_config *pc);
+/* A second call replaces the learner; a failed one leaves none. */
+int zenv_diayn_init(zenv_t *h, const zenv_skill_inverse_weights *init, const zenv_ppo_config *pc);
+/* The flat functions; their semantics are the flat functions'.  ZENV_E_STATE without zenv_diayn_init.  The update calls
+ * and zenv_diayn_samples answer ZENV_E_STATE unless the handle's buffers hold a completed zenv_collect_skill's records
+ * (of an agent with the learner's S skills) of at least two frames -- zenv_collect_option's are refused -- and
+ * zenv_diayn_minibatch / _epoch also when the collection kept no sample.  A host index outside [0, N (T - 1)) is
+ * ZENV_E_ARG.  A device-resident index outside that range, a sample whose keep flag is 0 and a recorded skill outside
+ * [0, S) are never trained on: the sample is dropped as zenv_ppo_minibatch drops one, it adds nothing to the loss or to
+ * any gradient, and the next call that waits for the device answers ZENV_E_ARG once. */
+int zenv_diayn_tensor(zenv_t *h, int which, int index, void **dev_ptr, int64_t *count);
+int zenv_diayn_read(zenv_t *h, int which, int index, float *dst);
+int zenv_diayn_write(zenv_t *h, int which, int index, const float *src);
+int zenv_diayn_get_step(zenv_t *h, int64_t *step);
+int zenv_diayn_set_step(zenv_t *h, int64_t step);
+int zenv_diayn_samples(zenv_t *h, int64_t *count);
+int zenv_diayn_minibatch(zenv_t *h, const int32_t *idx, int count, int idx_on_device, int apply);
+int zenv_diayn_apply(zenv_t *h);
+int zenv_diayn_epoch(zenv_t *h, const int32_t *order, int total, int batch_size, int on_device);
+/* The learned skill prior: skill_logits [n_skills], Adam's moments and step count in the handle (host memory).
+ * zenv_diayn_prior_update takes one Adam step (torch.optim.Adam(lr, eps = adam_eps); the reference: 1e-2, 1e-8) on the
+ * mean cross-entropy of the logits against the M picks (ZENV_F_HI_ACTION) of the last zenv_collect_skill: the picks are
+ * counted on the device, the gradient softmax(logits)_s - count_s / M is formed in double on the host.  A pick outside
+ * [0, S) is not counted and the call answers ZENV_E_ARG.  ZENV_E_STATE without zenv_diayn_prior_init, without such
+ * records (M = 0) or with records of an agent with another S.  What the next zenv_collect_skill takes as
+ * skill_prior_logits is zenv_diayn_prior_read's. */
+int zenv_diayn_prior_init(zenv_t *h, const float *logits, int n_skills, double lr, double adam_eps);
+int zenv_diayn_prior_update(zenv_t *h);
+int zenv_diayn_prior_read(zenv_t *h, float *logits);
+int zenv_diayn_prior_write(zenv_t *h, const float *logits);
 
 /* ---- results ---- */
 int zenv_get(zenv_t *h, int field, void *dst, int dst_on_device);

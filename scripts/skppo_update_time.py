@@ -6,7 +6,7 @@ collected experience, at two shapes:
                S = 5 skills
     reference  16 procs x 2 000 frames, skill_len 20, minibatches of 1 600 (low) / 80 (high)
 
-The inverse model's and the skill prior's updates are torch's on either path and are not timed.
+The inverse model's and the skill prior's updates are not timed here: scripts/diayn_update_time.py times them.
 
 Both on the same box in the same run, alternating, REPEATS windows each; a window is one whole update (high level, then
 low level, then handing the parameters to the acting agent), wall clock around a synchronise.
