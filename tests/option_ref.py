@@ -10,20 +10,21 @@ termination uniform from word 0 of a block with the tag 0x4F5054 (tests/philox_r
 import numpy as np
 import torch
 
-from tests import philox_ref, skill_ref
+from tests import philox_ref, skill_ref, xy_ref
 
 TAG_OPTION_TERM = 0x4F5054
 
 
 def random_state_dicts(F, S, h=128, seed=0, critics=True, term_bias=None, **kw):
-    """skill_ref.random_state_dicts with the low level's two heads widened to three rows (a generator of their own).
+    """skill_ref.random_state_dicts with the low level's two heads widened to three rows (a generator of their own;
+    weight_scale multiplies them like every other weight row).
     term_bias: the third row of actor.mu_ becomes weight 0, bias term_bias, and the third row of actor.std_ weight 0,
     bias -100 -- mu_2 = 2 (sigmoid(term_bias) - 0.5) for every input, std_2 at its floor of 1e-3."""
     hi, lo = skill_ref.random_state_dicts(F, S, h=h, seed=seed, critics=critics, **kw)
     g = torch.Generator().manual_seed(seed + 7919)
     for name in ("actor.mu_", "actor.std_"):
         w = torch.randn(1, h, generator=g)
-        w = w / torch.sqrt(w.pow(2).sum(1, keepdim=True))
+        w = w / torch.sqrt(w.pow(2).sum(1, keepdim=True)) * kw.get("weight_scale", 1.0)
         b = 0.1 * torch.randn(1, generator=g)
         lo[f"{name}.weight"] = torch.cat([lo[f"{name}.weight"], w], dim=0)
         lo[f"{name}.bias"] = torch.cat([lo[f"{name}.bias"], b], dim=0)
@@ -50,6 +51,21 @@ def low(lo_sd, obs, zone_obs, skill, S, dtype=torch.float32):
     """skill [B] in 0 .. S-1 -> mu [B,3], std [B,3], value [B]; numpy arrays of `dtype`.  skill_ref.low is written for
     any number of head rows."""
     return skill_ref.low(lo_sd, obs, zone_obs, skill, S, dtype)
+
+
+def normalise_heads(lo_sd, obs, zone_obs, skill, S):
+    """xy_ref.scale_head_rows on the low level's three mu_ and three std_ rows for one batch: the envs with skill >= 0,
+    under their skill.  In place.  -> float64 pre-activations [(skill >= 0).sum(), 6] of the rescaled heads."""
+    has = np.asarray(skill) >= 0
+    if not has.any():
+        return xy_ref.scale_head_rows(lo_sd, np.zeros((0, lo_sd["actor.mu_.weight"].shape[1])))
+    sd = skill_ref._t(lo_sd, torch.float64)
+    onehot = torch.nn.functional.one_hot(torch.as_tensor(np.asarray(skill)[has], dtype=torch.int64), S).to(torch.float64)
+    obs = skill_ref._x(np.asarray(obs, np.float32)[has], torch.float64)
+    zo = skill_ref._x(np.asarray(zone_obs, np.float32)[has], torch.float64)
+    emb = skill_ref._encoder(sd, torch.cat([obs, onehot], dim=-1), zo)
+    a = torch.relu(torch.cat([emb, onehot], dim=-1) @ sd["actor.enc_.0.0.weight"].T + sd["actor.enc_.0.0.bias"])
+    return xy_ref.scale_head_rows(lo_sd, a.numpy())
 
 
 def term_prob(a2):

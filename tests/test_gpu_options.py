@@ -117,20 +117,17 @@ def test_networks_match_torch(zenv_mod, name, h, S, n):
     env.close()
 
 
-@pytest.mark.parametrize("seed", [4, 0xDEADBEEF12345])
-def test_draws_are_exact(zenv_mod, seed):
-    """OPTION_SAMPLE, every env, several steps: ENDED == (u < TERM_PROB) with the host's uniform, exactly; TERM_ACTION is
+def check_draws(Z, seed, n=1501, S=5, steps=6, index0=123457):
+    """OPTION_SAMPLE, every env, `steps` steps: ENDED == (u < TERM_PROB) with the host's uniform, exactly; TERM_ACTION is
     mu_2 + std_2 * z at the host's normal; TERM_PROB is sigmoid(4 a_2 - 3) of the device's own a_2; the skill and the
     first two action components are, bit for bit, those of a skill-agent handle holding the same tensors minus the
-    third rows, in the same state, on the same seed."""
-    Z = zenv_mod
-    n, index0, S = 1501, 123457, 5
+    third rows, in the same state, on the same seed.  Returns the worst distance of a_2 in ulps."""
     a_env = _env(Z, "PointTSP-25", n, num_steps=150)
     b_env = _env(Z, "PointTSP-25", n, num_steps=150)
     hi, lo = _load(Z, a_env, S, seed=17)
     b_env.load_skills(Z.skill_tensors_from_state_dicts(hi, option_ref.skill_planner_part(lo)), skill_len=10 ** 6)
     n_ended, worst = 0, 0.0
-    for t in range(6):
+    for t in range(steps):
         step = a_env.step_count
         assert b_env.step_count == step
         a_env.policy(Z.POLICY_OPTION_SAMPLE, policy_seed=seed, env_index0=index0)
@@ -172,6 +169,13 @@ def test_draws_are_exact(zenv_mod, seed):
     print("worst a_2 ulps", worst)
     a_env.close()
     b_env.close()
+    return worst
+
+
+@pytest.mark.parametrize("seed", [4, 0xDEADBEEF12345])
+def test_draws_are_exact(zenv_mod, seed):
+    """check_draws on 1 501 envs, S = 5, six steps."""
+    check_draws(zenv_mod, seed)
 
 
 def test_option_clock(zenv_mod):

@@ -16,13 +16,14 @@ from tests import hier_ref, philox_ref
 TAG_XY_GOAL = 0x585947
 
 
-def random_state_dicts(F, h=128, seed=0, critics=True, bias_scale=0.1):
+def random_state_dicts(F, h=128, seed=0, critics=True, bias_scale=0.1, weight_scale=1.0):
     """(hi_state_dict, lo_state_dict) with the reference's key names, float32 torch tensors: rows of N(0, 1) normalised
-    to unit norm, biases of scale 0.1 (so that the bias path is exercised)."""
+    to unit norm, biases of scale 0.1 (so that the bias path is exercised).  weight_scale multiplies every weight row,
+    as in hier_ref.random_state_dicts: larger activations, for the precision sweeps."""
     g = torch.Generator().manual_seed(seed)
 
     def lin(n_out, n_in):
-        return hier_ref._lin(g, n_out, n_in, bias_scale)
+        return hier_ref._lin(g, n_out, n_in, bias_scale, weight_scale)
 
     hi, lo = {}, {}
     for sd, x in ((hi, 8), (lo, 10)):
@@ -52,6 +53,45 @@ def high(hi_sd, obs, zone_obs, dtype=torch.float32):
 
 
 low = hier_ref.low
+
+
+def scale_head_rows(sd, a, names=("actor.mu_", "actor.std_")):
+    """Keeps the sigmoid heads `names` of state dict `sd` out of saturation on a batch, in place.  a: float64 [B, h], the
+    heads' input (relu(actor.enc_.0.0(.)) of the batch).  Every head weight row w is divided by max(1, max_b |w . a_b| /
+    3) (float64, rounded to float32 once); the biases stay.  -> float64 [B, rows]: the pre-activations w . a_b + bias of
+    the rows of all `names` with the weights as they are afterwards.  With B = 0 nothing changes."""
+    a = torch.as_tensor(np.asarray(a, np.float64))
+    out = []
+    for name in names:
+        w = sd[f"{name}.weight"].to(torch.float64)
+        if a.shape[0]:
+            div = torch.clamp((a @ w.T).abs().max(dim=0).values / 3.0, min=1.0)
+            sd[f"{name}.weight"] = (w / div[:, None]).to(torch.float32)
+        out.append(a @ sd[f"{name}.weight"].to(torch.float64).T + sd[f"{name}.bias"].to(torch.float64))
+    return torch.cat(out, dim=1).numpy()
+
+
+def _head_input(sd, x, zone_obs):
+    """float64 relu(actor.enc_.0.0(emb)) of the per-env input x (obs, or [obs, goal]): what mu_ / std_ are applied to."""
+    sd = {k: torch.as_tensor(np.asarray(v)).to(torch.float64) for k, v in sd.items()}
+    x = torch.as_tensor(np.asarray(x, np.float32)).to(torch.float64)
+    zo = torch.as_tensor(np.asarray(zone_obs, np.float32)).to(torch.float64)
+    if not len(x):
+        return torch.zeros(0, sd["actor.enc_.0.0.bias"].shape[0], dtype=torch.float64)
+    emb = hier_ref._encoder(sd, x, zo)
+    return torch.relu(emb @ sd["actor.enc_.0.0.weight"].T + sd["actor.enc_.0.0.bias"])
+
+
+def normalise_heads(hi_sd, lo_sd, obs, zone_obs, goal, has_goal):
+    """scale_head_rows on both levels for one batch: the high level's goal_mu / goal_std rows on every env, the low
+    level's mu / std rows on the envs with has_goal under their goal [B, 2].  In place.  -> (hi, lo) float64
+    pre-activations [B, 4] and [has_goal.sum(), 4] of the rescaled heads."""
+    has = np.asarray(has_goal, bool)
+    obs, zone_obs = np.asarray(obs, np.float32), np.asarray(zone_obs, np.float32)
+    pre_hi = scale_head_rows(hi_sd, _head_input(hi_sd, obs, zone_obs))
+    x = np.concatenate([obs, np.asarray(goal, np.float32)], axis=1)[has]
+    pre_lo = scale_head_rows(lo_sd, _head_input(lo_sd, x, zone_obs[has]))
+    return pre_hi, pre_lo
 
 
 def goal_noise(n, seed, env_index0, step):
