@@ -146,6 +146,15 @@ class PpoConfig(C.Structure):
                 ("distributional_value", C.c_int32)]
 
 
+RENDER_CURRENT, RENDER_EXPERIENCE = 0, 1                      # zenv_render_config.source
+
+
+class RenderConfig(C.Structure):
+    """struct zenv_render_config (include/zenv.h)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("source", C.c_int32), ("env", C.c_int32),
+                ("view", C.c_float), ("robot_radius", C.c_float)]
+
+
 class ZenvError(RuntimeError):
     def __init__(self, code, message):
         super().__init__(f"zenv error {code}: {message}")
@@ -322,6 +331,8 @@ _PROTOTYPES = {
     "zenv_allgather": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int]),
     "zenv_comm_barrier": (C.c_int, [_H]),
     "zenv_comm_allreduce_max": (C.c_int, [_H, C.POINTER(C.c_double)]),
+    "zenv_render_check": (C.c_int, [C.POINTER(Config), C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "zenv_render": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "zenv_probe_store_stream": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.POINTER(C.c_float)]),
     "zenv_step_count": (C.c_int64, [_H]),

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "host_sampler.hpp"
+#include "render.hpp"
 #include "zenv_handle.hpp"
 
 namespace {
@@ -556,6 +557,8 @@ extern "C" int zenv_destroy(zenv_t *h)
     if (h->d_mask) (void)hipFree(h->d_mask);
     if (h->d_self) (void)hipFree(h->d_self);
     if (h->chunk_mem) (void)hipFree(h->chunk_mem);
+    if (h->render_marks) (void)hipFree(h->render_marks);
+    if (h->render_stage) (void)hipFree(h->render_stage);
     if (h->refill_host) (void)hipHostFree(h->refill_host);
     if (h->mlp_range_flag) (void)hipHostFree(h->mlp_range_flag);
     if (h->hi_total_host) (void)hipHostFree(h->hi_total_host);
@@ -1641,6 +1644,97 @@ extern "C" int zenv_comm_allreduce_max(zenv_t *h, double *value)
     RCCL_TRY(api, api->AllReduce(h->comm_scalar, h->comm_scalar + 1, 1, ncclFloat64, ncclMax, h->comm, h->stream));
     HIP_TRY(hipMemcpyAsync(value, h->comm_scalar + 1, sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
+    return ZENV_OK;
+}
+
+// ============================================================================ rendering (K18, render.hip)
+extern "C" int zenv_render_check(const zenv_config *cfg, const zenv_render_config *rc, int n_env, int first, int count)
+{
+    if (!cfg || !rc) return fail(ZENV_E_ARG, "null argument");
+    if (rc->width < 1 || rc->width > 4096) return fail(ZENV_E_ARG, "width %d outside [1, 4096]", rc->width);
+    if (rc->height < 1 || rc->height > 4096) return fail(ZENV_E_ARG, "height %d outside [1, 4096]", rc->height);
+    if (!std::isfinite(rc->view) || !(rc->view > 0.0f)) return fail(ZENV_E_ARG, "view must be positive and finite");
+    if (!std::isfinite(rc->robot_radius) || rc->robot_radius < 0.0f)
+        return fail(ZENV_E_ARG, "robot_radius must be non-negative and finite");
+    if (rc->source != ZENV_RENDER_CURRENT && rc->source != ZENV_RENDER_EXPERIENCE)
+        return fail(ZENV_E_ARG, "unknown source %d", rc->source);
+    if (n_env < 1) return fail(ZENV_E_ARG, "n_env must be >= 1");
+    if (count < 1) return fail(ZENV_E_ARG, "count must be >= 1");
+    if (first < 0) return fail(ZENV_E_ARG, "first must be >= 0");
+    if (rc->source == ZENV_RENDER_CURRENT && (int64_t)first + count > n_env)
+        return fail(ZENV_E_ARG, "first + count = %lld is beyond the %d envs", (long long)first + count, n_env);
+    if (rc->source == ZENV_RENDER_EXPERIENCE && (rc->env < 0 || rc->env >= n_env))
+        return fail(ZENV_E_ARG, "env %d outside [0, %d)", rc->env, n_env);
+    if ((int64_t)count * rc->width * rc->height * 3 >= ((int64_t)1 << 31))
+        return fail(ZENV_E_ARG, "count * width * height * 3 must stay below 2^31 bytes: draw fewer images per call");
+    return ZENV_OK;
+}
+
+// grow-only device scratch of zenv_render (the stream is drained before an old buffer goes)
+static int render_scratch(zenv *h, void *&buf, size_t &cap, size_t bytes)
+{
+    if (cap >= bytes) return ZENV_OK;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (buf) (void)hipFree(buf);
+    buf = nullptr;
+    cap = 0;
+    HIP_TRY(hipMalloc(&buf, bytes));
+    cap = bytes;
+    return ZENV_OK;
+}
+
+extern "C" int zenv_render(zenv_t *h, const zenv_render_config *rc, int first, int count, const float *marks,
+                           int marks_on_device, uint8_t *dst, int dst_on_device)
+{
+    if (!h || !rc || !dst) return fail(ZENV_E_ARG, "null argument");
+    if (int rv = zenv_render_check(&h->cfg, rc, h->n_env, first, count)) return rv;
+    const int64_t N = h->n_env, ZF = (int64_t)h->p.Z * h->p.F;
+    RenderParams rp{};
+    if (rc->source == ZENV_RENDER_CURRENT) {
+        if (!h->was_reset) return fail(ZENV_E_STATE, "reset first: the handle holds no observation");
+        rp.obs = h->p.obs + (int64_t)first * 8;          // (page-locked host memory under zenv_host_io)
+        rp.zone_obs = h->p.zone_obs + (int64_t)first * ZF;
+        rp.obs_stride = 8;
+        rp.zone_stride = ZF;
+    } else {
+        if (!h->exp_mem) return fail(ZENV_E_STATE, "collect first: the handle holds no experience");
+        if ((int64_t)first + count > h->exp.T)
+            return fail(ZENV_E_ARG, "first + count = %lld is beyond the %d recorded frames", (long long)first + count,
+                        h->exp.T);
+        rp.obs = h->exp.obs + ((int64_t)first * N + rc->env) * 8;
+        rp.zone_obs = h->exp.zone_obs + ((int64_t)first * N + rc->env) * ZF;
+        rp.obs_stride = N * 8;
+        rp.zone_stride = N * ZF;
+    }
+    if (int rv = use_device(h)) return rv;
+    const size_t bytes = (size_t)count * rc->width * rc->height * 3;
+    if (marks && !marks_on_device) {
+        const size_t mark_bytes = (size_t)count * 2 * sizeof(float);
+        if (int rv = render_scratch(h, h->render_marks, h->render_marks_cap, mark_bytes)) return rv;
+        HIP_TRY(hipMemcpyAsync(h->render_marks, marks, mark_bytes, hipMemcpyHostToDevice, h->stream));
+        marks = static_cast<const float *>(h->render_marks);
+    }
+    if (!dst_on_device)
+        if (int rv = render_scratch(h, h->render_stage, h->render_stage_cap, bytes)) return rv;
+    rp.marks = marks;
+    rp.dst = dst_on_device ? dst : static_cast<uint8_t *>(h->render_stage);
+    rp.count = count;
+    rp.W = rc->width;
+    rp.H = rc->height;
+    rp.Z = h->p.Z;
+    rp.F = h->p.F;
+    rp.timed = h->cfg.task == ZENV_TASK_TIMED_TSP;
+    rp.view = rc->view;
+    rp.sx = (2.0f * rc->view) / (float)rc->width;
+    rp.sy = (2.0f * rc->view) / (float)rc->height;
+    rp.rz = (float)(h->cfg.zones_size / 3.0);
+    rp.rr = rc->robot_radius / 3.0f;
+    HIP_TRY(launch_render(rp, h->stream));
+    if (!dst_on_device) {
+        HIP_TRY(hipMemcpyAsync(dst, h->render_stage, bytes, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        if (int rr = mlp_range_check(h)) return rr;
+    }
     return ZENV_OK;
 }
 

@@ -221,6 +221,9 @@ struct zenv {
     // ZENV_F_EP_RETURN / ZENV_F_EP_LEN as plain arrays: the values live in the HotA records, unpacked by refresh_field()
     double *pub_ep_return = nullptr;
     int32_t *pub_steps = nullptr;
+    // zenv_render: the device copies of a host caller's marks and of the frames on their way to host memory
+    void *render_marks = nullptr, *render_stage = nullptr;
+    size_t render_marks_cap = 0, render_stage_cap = 0;
 };
 
 ZENV_INTERNAL int use_device(const zenv *h);

@@ -47,7 +47,7 @@ class ZoneEnvBase:
     """Common part of the three task envs (Engine + ZoneEnvBase of the reference)."""
 
     _TASK = None
-    metadata = {"render.modes": []}
+    metadata = {"render.modes": ["rgb_array"]}
     reward_range = (-float("inf"), float("inf"))
 
     def __init__(self, config, device=0, **native_overrides):
@@ -125,8 +125,14 @@ class ZoneEnvBase:
     def close(self):
         self._vec.close()
 
-    def render(self, *args, **kwargs):
-        raise NotImplementedError("rendering (mujoco-py viewers) is outside the hot path")
+    def render(self, mode="rgb_array", width=100, height=100):
+        """ZoneEnvBase.render (ZoneEnvBase.py:243-336; 100 x 100 is its DEFAULT_WIDTH / DEFAULT_HEIGHT):
+        mode='rgb_array' -> uint8 [height, width, 3], drawn on the device from the last observation.  Not MuJoCo's
+        camera: the orthographic top-down drawing of ``ZoneVecEnv.render``, the goal city ringed on
+        the goal-conditioned envs.  mode='human' would need a window (mujoco-py's viewer): not implemented."""
+        if mode != "rgb_array":
+            raise NotImplementedError(f"render mode {mode!r}: there is no window, use mode='rgb_array'")
+        return self._vec.render(0, 1, width=width, height=height)[0]
 
     # ------------------------------------------------------------------ observations
     def build_observation_space(self):

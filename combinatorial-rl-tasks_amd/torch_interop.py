@@ -725,6 +725,79 @@ class TorchZoneEnv:
         hi["count"] = self._alias(nat.F_HI_COUNT)
         return lo, hi, rate
 
+    # ------------------------------------------------------------------ rendering (K18)
+    def _render_marks(self, marks, count, auto):
+        """marks argument -> contiguous float32 CUDA tensor [count, 2] or None; auto() builds the "auto" ones."""
+        torch = self._torch
+        if isinstance(marks, str):
+            if marks != "auto":
+                raise ValueError('marks is "auto", None or [count, 2]')
+            marks = auto()
+        if marks is None:
+            return None
+        marks = torch.as_tensor(marks, dtype=torch.float32, device=self.device).contiguous()
+        if tuple(marks.shape) != (count, 2):
+            raise ValueError(f"marks must have shape ({count}, 2)")
+        return marks
+
+    def _render_into(self, source, env, first, count, width, height, view, robot_radius, marks, out):
+        torch = self._torch
+        self.env.render_check(source, env, first, count, width, height, view, robot_radius)
+        shape = (int(count), int(height), int(width), 3)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        elif not (out.is_cuda and out.device == self.device and out.dtype == torch.uint8 and out.is_contiguous()
+                  and tuple(out.shape) == shape):
+            raise ValueError(f"out must be a contiguous uint8 CUDA tensor of shape {shape} on the env's device")
+        self.env._render(source, env, first, count, width, height, view, robot_radius,
+                         None if marks is None else marks.data_ptr(), True, out.data_ptr(), True)
+        return out
+
+    def _auto_marks(self, first, count):
+        """``ZoneVecEnv._auto_marks`` on the device: no copy to the host, no synchronisation."""
+        torch, env = self._torch, self.env
+        nan = torch.full((), float("nan"), dtype=torch.float32, device=self.device)
+        if env.field_bytes(nat.F_GOAL):
+            goal = self._alias(nat.F_GOAL)[first:first + count].long()
+            rows = self.zone_obs[first:first + count]
+            picked = rows[torch.arange(count, device=self.device), goal.clamp(min=0)]
+            shown = (goal >= 0) & (picked[:, 5] != 0)
+            return torch.where(shown[:, None], picked[:, :2], nan)
+        if env.field_bytes(nat.F_XY_GOAL):
+            goal = self._alias(nat.F_XY_GOAL)[first:first + count]
+            age = self._alias(nat.F_XY_GOAL_AGE)[first:first + count]
+            return torch.where((age >= 0)[:, None], goal, nan)
+        return None
+
+    def render(self, first=0, count=None, width=100, height=100, view=1.25, robot_radius=0.1, marks="auto", out=None):
+        """``ZoneVecEnv.render`` into a ``torch.uint8`` CUDA tensor [count, height, width, 3] that the kernel fills in
+        place (``out=`` reuses one): enqueued on the shared stream, no host copy, no synchronisation.  marks may be a
+        CUDA tensor [count, 2]."""
+        first = int(first)
+        count = self.env.num_envs - first if count is None else int(count)
+        with self._torch.cuda.device(self.device):
+            self.env.render_check(nat.RENDER_CURRENT, 0, first, count, width, height, view, robot_radius)
+            marks = self._render_marks(marks, count, lambda: self._auto_marks(first, count))
+            return self._render_into(nat.RENDER_CURRENT, 0, first, count, width, height, view, robot_radius, marks, out)
+
+    def render_experience(self, env, first=0, count=None, width=100, height=100, view=1.25, robot_radius=0.1,
+                          marks="auto", out=None):
+        """``ZoneVecEnv.render_experience`` into a ``torch.uint8`` CUDA tensor [count, height, width, 3]: the film of
+        one env of the last collection, one launch on the shared stream, nothing brought to the host."""
+        venv = self.env
+        first, T = int(first), venv.experience_frames()
+        count = max(T - first, 1) if count is None else int(count)
+
+        def auto():
+            if not (T and getattr(venv, "_exp_has_goals", False) and 0 <= first and first + count <= T
+                    and 0 <= int(env) < venv.num_envs):
+                return None
+            return self._alias(nat.F_LO_GOAL, (T, venv.num_envs, 2), np.float32)[first:first + count, int(env)]
+        with self._torch.cuda.device(self.device):
+            marks = self._render_marks(marks, count, auto)
+            return self._render_into(nat.RENDER_EXPERIENCE, env, first, count, width, height, view, robot_radius,
+                                     marks, out)
+
     def step(self, actions, auto_reset=True):
         """actions: float32 CUDA tensor (N, 2) on the env's device (contiguous).  Asynchronous: the
         step kernel is enqueued behind whatever produced ``actions`` on the shared stream."""

@@ -686,6 +686,7 @@ class ZoneVecEnv:
                                                                           discount, gae_lambda)
         m = C.c_int64(0)
         check(lib().zenv_collect_option(self._h, T, seed, index0, discount, gae_lambda, C.byref(m)))
+        self._exp_has_goals = False
         return T, int(m.value)
 
     # ------------------------------------------------------------------ xy-goals hierarchical agent
@@ -755,6 +756,7 @@ class ZoneVecEnv:
         T, seed, index0, discount, gae_lambda = check_collect_xy_args(frames_per_proc, L, policy_seed, env_index0,
                                                                       discount, gae_lambda)
         check(lib().zenv_collect_xy(self._h, T, seed, index0, discount, gae_lambda))
+        self._exp_has_goals = True          # ZENV_F_LO_GOAL holds this collection's goals (render_experience's marks)
         return T, self.num_envs * (T // L)
 
     def load_skill_inverse(self, tensors, precision="f32"):
@@ -805,6 +807,7 @@ class ZoneVecEnv:
             getattr(self, "_skill_n", None), getattr(self, "_skill_inverse", False))
         check(lib().zenv_collect_skill(self._h, T, seed, index0, discount, gae_lambda, coef,
                                        None if prior is None else prior.ctypes.data, 1 if sample_hi else 0))
+        self._exp_has_goals = False
         return T, self.num_envs * (T // L)
 
     # ------------------------------------------------------------------ one PPO rollout
@@ -821,6 +824,7 @@ class ZoneVecEnv:
         """The same rollout, results left in the handle's device buffers (``experience_layout`` names them)."""
         check(lib().zenv_collect(self._h, int(frames_per_proc), int(policy_seed), int(env_index0),
                                  float(discount), float(gae_lambda)))
+        self._exp_has_goals = False
 
     def experience_layout(self, frames_per_proc):
         """name -> (field id, shape in memory, time_major) of the float32 buffers one collect of T frames per env
@@ -1589,6 +1593,7 @@ class ZoneVecEnv:
                                                                         discount, gae_lambda)
         m = C.c_int64(0)
         check(lib().zenv_collect_hier(self._h, T, seed, index0, discount, gae_lambda, C.byref(m)))
+        self._exp_has_goals = True          # ZENV_F_LO_GOAL holds this collection's goals (render_experience's marks)
         return T, int(m.value)
 
     def sync(self):
@@ -1807,6 +1812,92 @@ class ZoneVecEnv:
     def results(self):
         """(obs, zone_obs, reward, done, goal_met) of the last step, as host arrays."""
         return self.step_results(None)[:5]
+
+    # ------------------------------------------------------------------ rendering (K18, DESIGN.md 4)
+    def _render(self, source, env, first, count, width, height, view, robot_radius, marks_ptr, marks_on_device,
+                dst_ptr, dst_on_device):
+        """zenv_render with raw addresses (marks_ptr None: no marks)."""
+        rc = nat.RenderConfig(int(width), int(height), int(source), int(env), float(view), float(robot_radius))
+        check(lib().zenv_render(self._h, C.byref(rc), int(first), int(count),
+                                None if marks_ptr is None else C.c_void_p(int(marks_ptr)), int(bool(marks_on_device)),
+                                C.c_void_p(int(dst_ptr)), int(bool(dst_on_device))))
+
+    def render_check(self, source, env, first, count, width, height, view, robot_radius):
+        """zenv_render_check for this handle's config and batch: raises ZenvError(E_ARG) naming the argument."""
+        rc = nat.RenderConfig(int(width), int(height), int(source), int(env), float(view), float(robot_radius))
+        check(lib().zenv_render_check(C.byref(self.cfg), C.byref(rc), self.num_envs, int(first), int(count)))
+
+    def _render_host(self, source, env, first, count, width, height, view, robot_radius, marks, out):
+        self.render_check(source, env, first, count, width, height, view, robot_radius)
+        shape = (int(count), int(height), int(width), 3)
+        if out is None:
+            out = np.empty(shape, np.uint8)
+        elif out.dtype != np.uint8 or out.shape != shape or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a contiguous uint8 array of shape {shape}")
+        if marks is not None:
+            marks = np.ascontiguousarray(marks, np.float32)
+            if marks.shape != (int(count), 2):
+                raise ValueError(f"marks must have shape ({int(count)}, 2)")
+        self._render(source, env, first, count, width, height, view, robot_radius,
+                     None if marks is None else marks.ctypes.data, False, out.ctypes.data, False)
+        return out
+
+    def _auto_marks(self, first, count):
+        """What render() marks by itself: the goal zone's centre / 3 where ZENV_F_GOAL >= 0 -- a goal-conditioned
+        handle's goal, a solver-ordered handle's next city of the route --, the current goal on an xy-goals handle,
+        else nothing.  float32 [count, 2] with NaN rows for the envs without a goal, or None."""
+        if self.field_bytes(nat.F_GOAL):
+            goal = self.get_head(nat.F_GOAL, count, first)
+            rows = self.get_head(nat.F_ZONE_OBS, count, first)
+            marks = np.full((count, 2), np.nan, np.float32)
+            idx = np.nonzero(goal >= 0)[0]
+            picked = rows[idx, goal[idx]]
+            drawn = picked[:, 5] != 0                   # (an idle env's all-zero observation has no goal to show)
+            marks[idx[drawn]] = picked[drawn, :2]
+            return marks
+        if self.field_bytes(nat.F_XY_GOAL):
+            goal = self.get_head(nat.F_XY_GOAL, count, first)
+            age = self.get_head(nat.F_XY_GOAL_AGE, count, first)
+            return np.where(age[:, None] >= 0, goal, np.float32(np.nan)).astype(np.float32)
+        return None
+
+    def render(self, first=0, count=None, width=100, height=100, view=1.25, robot_radius=0.1, marks="auto", out=None):
+        """Envs first .. first + count - 1 (count None: to the last) as they were last observed, drawn top-down on the
+        device (zenv_render, ZENV_RENDER_CURRENT): np.uint8 [count, height, width, 3], RGB, row 0 at +y.  The square
+        shown is [-view, view]^2 in observation units (world / 3: the arena's extent 3 is 1.0).  marks: "auto" (see
+        _auto_marks), None, or float32 [count, 2] points to ring (a NaN row: none).  What the reference's
+        ZoneEnvBase.render(mode='rgb_array') is for, without MuJoCo's camera: DESIGN.md 4 K18 has the drawing rules."""
+        first = int(first)
+        count = self.num_envs - first if count is None else int(count)
+        if isinstance(marks, str):
+            if marks != "auto":
+                raise ValueError('marks is "auto", None or an array [count, 2]')
+            self.render_check(nat.RENDER_CURRENT, 0, first, count, width, height, view, robot_radius)
+            marks = self._auto_marks(first, count)
+        return self._render_host(nat.RENDER_CURRENT, 0, first, count, width, height, view, robot_radius, marks, out)
+
+    def experience_frames(self):
+        """T of the last collection (0: the handle holds no experience)."""
+        return int(self.field_bytes(nat.F_EXP_OBS) // (self.num_envs * nat.OBS_DIM * 4))
+
+    def render_experience(self, env, first=0, count=None, width=100, height=100, view=1.25, robot_radius=0.1,
+                          marks="auto", out=None):
+        """Frames first .. first + count - 1 (count None: to the last recorded) of ONE env of the last collection
+        (any collect_*), drawn in a single launch from the time-major experience buffers (zenv_render,
+        ZENV_RENDER_EXPERIENCE): np.uint8 [count, height, width, 3].  marks "auto": the goal the low level acted under
+        (ZENV_F_LO_GOAL) where the last collection recorded one -- collect_hier, collect_xy -- else none."""
+        first, T = int(first), self.experience_frames()
+        if count is None:
+            count = max(T - first, 1)           # (no experience: the library answers E_STATE)
+        count = int(count)
+        if isinstance(marks, str):
+            if marks != "auto":
+                raise ValueError('marks is "auto", None or an array [count, 2]')
+            marks = None
+            if T and getattr(self, "_exp_has_goals", False) and 0 <= first and first + count <= T \
+                    and 0 <= int(env) < self.num_envs:
+                marks = self.get(nat.F_LO_GOAL, np.empty((T, self.num_envs, 2), np.float32))[first:first + count, int(env)]
+        return self._render_host(nat.RENDER_EXPERIENCE, env, first, count, width, height, view, robot_radius, marks, out)
 
     # ------------------------------------------------------------------ snapshots / debug
     def get_state(self):

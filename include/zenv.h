@@ -1268,6 +1268,42 @@ int zenv_allgather(zenv_t *h, int field, void *dst, int dst_on_device);
 int zenv_comm_barrier(zenv_t *h);
 int zenv_comm_allreduce_max(zenv_t *h, double *value);
 
+/* ---- rendering: observations and recorded experience as RGB frames (K18) ----
+ * What the reference looks at through ZoneEnvBase.render (main/envs/zone_envs/ZoneEnvBase.py:243-336) and the loops of
+ * scripts/visualize.py / visualize_hier.py.  Not MuJoCo's perspective camera: an exact orthographic, top-down drawing
+ * of what the agent observes -- the zone rows (centre / 3, RGBA, the task's extra feature) and the robot's position and
+ * heading (obs[1:3], obs[3:5]) -- in float32 by fixed rules, so that a frame is reproducible bit for bit.
+ * dst: uint8 [count][height][width][3], RGB, row 0 at the top (+y); pixel (r, c) has its centre at
+ * x = (c + 0.5) sx - view, y = view - (r + 0.5) sy with sx = 2 view / width, sy = 2 view / height, in observation
+ * units (world / 3).  Painter's order, opaque: background (224, 224, 224); the zones in index order -- a disc of radius
+ * zones_size / 3 in the row's colour, a row with alpha 0 (WaitWrapper's all-zero observation) skipped, an unvisited
+ * TimedTSP zone (0, 1, 1) drawn as the reference fades it, (1 - t, max(0, t), max(0, t)) with t = row[6]
+ * (TTSP_env.py:52-58); the image's mark, a ring from 1 to 1.35 zone radii in (255, 0, 255) around marks[i] (marks NULL
+ * or a NaN component: none); the robot, a disc of radius robot_radius / 3 in (32, 32, 32) whose pixels more than 0.4
+ * radii ahead of the centre along the heading are the nose (255, 255, 255).
+ *   ZENV_RENDER_CURRENT     image i = env first + i, from the observation of the last reset / step (wherever the
+ *                           handle published it: zenv_host_io's page-locked slab included)
+ *   ZENV_RENDER_EXPERIENCE  image i = frame first + i of env `env` in the ZENV_F_EXP_* buffers of the last
+ *                           collection (any of the five collectors): a film of one env's trajectory in one launch
+ * zenv_render_check applies the rules that need no handle (ZENV_E_ARG: a null argument, a size outside 1 .. 4096, a
+ * view that is not positive and finite, a robot_radius that is negative or not finite, an unknown source, count < 1,
+ * first < 0, first + count beyond the envs (CURRENT), env outside [0, n_env) (EXPERIENCE), count * width * height * 3
+ * >= 2^31).  zenv_render adds ZENV_E_STATE for a handle never reset (CURRENT) or without experience (EXPERIENCE) and
+ * ZENV_E_ARG for first + count beyond the recorded frames.  marks: float32 [count][2], host or device memory.  With
+ * dst in device memory the call is asynchronous on the handle's stream and dst may have any alignment; with a host
+ * dst the frames are staged on the device, copied and waited for. */
+enum { ZENV_RENDER_CURRENT = 0, ZENV_RENDER_EXPERIENCE = 1 };
+typedef struct zenv_render_config {
+    int32_t width, height;   /* 1 .. 4096 each */
+    int32_t source;          /* ZENV_RENDER_CURRENT / ZENV_RENDER_EXPERIENCE */
+    int32_t env;             /* ZENV_RENDER_EXPERIENCE: the env whose frames are drawn */
+    float view;              /* half-width of the square shown, observation units; > 0, finite */
+    float robot_radius;      /* world units; >= 0, finite */
+} zenv_render_config;
+int zenv_render_check(const zenv_config *cfg, const zenv_render_config *rc, int n_env, int first, int count);
+int zenv_render(zenv_t *h, const zenv_render_config *rc, int first, int count, const float *marks,
+                int marks_on_device, uint8_t *dst, int dst_on_device);
+
 /* Measurement utility (bench.py `store_stream_ceiling`; not part of the env path): n_tiles waves each rewrite their
  * own contiguous tile_bytes (a multiple of 16, >= 1024) `steps` times with 1 KiB dwordx4 bursts under cache_policy
  * (0 plain, 2 non-temporal, 16 sc1 = write-through) -- the row stream of the step kernels with the env taken away.
