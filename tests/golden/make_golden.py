@@ -1,7 +1,8 @@
 """Generate the golden vectors of the RNG / layout half of reset().
 
-The reference's env modules cannot be imported in the build image (gym, safety_gym and
-mujoco_py are absent: ordinary ModuleNotFoundError), so these vectors are produced with the
+The reference's env modules cannot be run in the build image (gym, safety_gym and
+mujoco_py are absent, and the environments need MuJoCo; the agents are plain torch and do
+import behind stand-in modules, see make_agent_goldens.py), so these vectors are produced with the
 one reference dependency that IS here: numpy's legacy ``RandomState`` (the reference pins
 numpy==1.21.1 in requirements.txt:4; the legacy stream is frozen across versions).  The
 sampling logic below restates, in plain Python on top of real ``RandomState`` draws,

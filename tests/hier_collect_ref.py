@@ -43,16 +43,18 @@ def log_softmax_at(logits, g):
     return l64[g] - m - np.log(np.exp(l64[fin] - m).sum())
 
 
-def expected_hi(b, T, n_calls, v_final):
+def expected_hi(b, T, n_calls, v_final, dtype=np.float32):
     """The numpy restatement: per call, per env, the closed transitions in order with their GAE (_hier_policy_opt.py:
     66-76, 98-107).  T: frames per call, or a list of them (calls of different lengths); v_final[c] = V_hi(obs_T) after
-    call c.  Also returns what the call-boundary cases looked like."""
+    call c.  dtype: the arithmetic's (float32: the device's; float64 for a float64 recording).  Also returns what the
+    call-boundary cases looked like."""
+    f = dtype
     n = b["obs"].shape[1]
     starts = np.concatenate([[0], np.cumsum([T] * n_calls if np.isscalar(T) else T)]).astype(int)
     out = [[[] for _ in range(n)] for _ in range(n_calls)]
     seen = {"span": 0, "mask0": 0, "mask1": 0, "bootstrap": 0}
     for j in range(n):
-        hr = np.float32(0)
+        hr = f(0)
         open_t = None
         events = []                                        # (close frame, pick frame, reward, mask)
         picks = []
@@ -61,12 +63,12 @@ def expected_hi(b, T, n_calls, v_final):
                 assert open_t is None
                 open_t = t
                 picks.append(t)
-            hr = np.float32(hr + b["reward"][t, j])
+            hr = f(hr + b["reward"][t, j])
             if b["need_after"][t, j]:
                 if open_t is not None:
                     events.append((t, open_t, hr, 0.0 if b["done"][t, j] else 1.0))
                     open_t = None
-                hr = np.float32(0)
+                hr = f(0)
         for c in range(n_calls):
             closed = [e for e in events if starts[c] <= e[0] < starts[c + 1]]
             rows = []
@@ -78,14 +80,14 @@ def expected_hi(b, T, n_calls, v_final):
                     vn = v_final[c][j]
                     seen["bootstrap"] += m == 1.0                # V_hi(obs_T) enters this row's advantage
                 rows.append(dict(t_pick=tp, t_close=tc, goal=b["goal"][tp, j], value=b["pick_value"][tp, j], reward=r,
-                                 mask=np.float32(m), v_next=np.float32(vn)))
+                                 mask=f(m), v_next=f(vn)))
                 seen["span"] += tp < starts[c]
                 seen["mask0" if m == 0 else "mask1"] += 1
-            an = np.float32(0)
+            an = f(0)
             for row in reversed(rows):
                 m = row["mask"]
                 delta = row["reward"] + row["v_next"] * m - row["value"]
-                row["adv"] = np.float32(delta + np.float32(LAM) * an * m)
+                row["adv"] = f(delta + f(LAM) * an * m)
                 an = row["adv"]
             out[c][j] = rows
     return out, seen

@@ -52,23 +52,24 @@ def expected_age(b, upto=None):
     return (frames - last).astype(np.int32)
 
 
-def expected_hi(b, T, n_calls, v_final, lam=LAM):
+def expected_hi(b, T, n_calls, v_final, lam=LAM, dtype=np.float32):
     """The numpy restatement: per call, per env, the closed transitions in order with their GAE.  b: pick, ended, done
     (bool [frames, n]), reward, pick_value (float32 [frames, n]), skill (int [frames, n]).  T: frames per call, or a list
-    of them; v_final[c] = V_hi(obs_T) after call c.  Also returns how often each boundary case was met:
+    of them; v_final[c] = V_hi(obs_T) after call c; dtype: the arithmetic's.  Also returns how often each boundary case was met:
       span       a row whose pick lies in an earlier call
       mask0 / mask1   rows closed with hi_mask 0 / 1
       bootstrap  a row with hi_mask 1 whose V_next is V_hi(obs_T)
       survived   a row whose option ran across an auto-reset (a done between its pick and its close): the reward sums
                  two episodes
       no_rows    (call, env) pairs without a row"""
+    f = dtype                                             # float32: the device's arithmetic; float64 for a float64 record
     n = b["pick"].shape[1]
     starts = np.concatenate([[0], np.cumsum([T] * n_calls if np.isscalar(T) else T)]).astype(int)
     out = [[[] for _ in range(n)] for _ in range(n_calls)]
     seen = {"span": 0, "mask0": 0, "mask1": 0, "bootstrap": 0, "survived": 0, "no_rows": 0}
-    lam = np.float32(lam)
+    lam = f(lam)
     for j in range(n):
-        hr = np.float32(0)
+        hr = f(0)
         open_t = None
         events = []                                        # (close frame, pick frame, reward, mask)
         picks = []
@@ -77,12 +78,12 @@ def expected_hi(b, T, n_calls, v_final, lam=LAM):
                 assert open_t is None
                 open_t = t
                 picks.append(t)
-            hr = np.float32(hr + np.float32(b["reward"][t, j]))
+            hr = f(hr + f(b["reward"][t, j]))
             if b["ended"][t, j]:
                 if open_t is not None:
                     events.append((t, open_t, hr, 0.0 if b["done"][t, j] else 1.0))
                     open_t = None
-                hr = np.float32(0)
+                hr = f(0)
         for c in range(n_calls):
             closed = [e for e in events if starts[c] <= e[0] < starts[c + 1]]
             rows = []
@@ -94,17 +95,17 @@ def expected_hi(b, T, n_calls, v_final, lam=LAM):
                     vn = v_final[c][j]
                     seen["bootstrap"] += m == 1.0
                 rows.append(dict(t_pick=tp, t_close=tc, skill=int(b["skill"][tp, j]),
-                                 value=np.float32(b["pick_value"][tp, j]), reward=r, mask=np.float32(m),
-                                 v_next=np.float32(vn)))
+                                 value=f(b["pick_value"][tp, j]), reward=r, mask=f(m),
+                                 v_next=f(vn)))
                 seen["span"] += tp < starts[c]
                 seen["mask0" if m == 0 else "mask1"] += 1
                 seen["survived"] += bool(b["done"][tp:tc, j].any())
             seen["no_rows"] += not rows
-            an = np.float32(0)
+            an = f(0)
             for row in reversed(rows):
                 m = row["mask"]
                 delta = row["reward"] + row["v_next"] * m - row["value"]
-                row["adv"] = np.float32(delta + lam * an * m)
+                row["adv"] = f(delta + lam * an * m)
                 an = row["adv"]
             out[c][j] = rows
     return out, seen

@@ -71,12 +71,12 @@ def replay(Z, env, frames, L, seed):
 
 
 def bookkeeping(reward, lo_reward, mask, cur_mask, lo_value, hi_value, next_lo_value, next_hi_value, L,
-                discount=GAMMA, gae_lambda=LAM):
+                discount=GAMMA, gae_lambda=LAM, dtype=np.float32):
     """_hier_policy_opt.py:104-161 in numpy float32, on time-major records: reward / lo_reward / mask / lo_value [T, N],
     hi_value [W, N], cur_mask (self.lo_mask after the frames), next_*_value [N].  Returns the low-level advantage
     [T, N]; the high-level reward, next_mask and advantage [W, N]; num_frames; the inverse-exps selection as
     (frame i, env j) index arrays in env-major order."""
-    f = np.float32
+    f = dtype                                             # float32: the device's arithmetic; float64 for a float64 record
     reward, lo_reward, mask = (np.asarray(a, f) for a in (reward, lo_reward, mask))
     T, N = reward.shape
     W = T // L

@@ -1,0 +1,682 @@
+"""The restatements the device agents are tested against, pinned to what the reference's own code computes.
+
+tests/golden/agent_*.npz were recorded by tests/golden/make_agent_goldens.py, which imports the reference's models,
+``collect_experiences`` and update functions at run time and stores the data they consume and produce, once in float32
+(the reference as it stands) and once in float64 (the same float32 weights and inputs widened).  Here the very
+functions the GPU tests call are fed the recorded inputs; nothing reads the reference tree.
+
+Bounds.  float64 restatement against float64 recording: |a - b| <= 1e-9 max(1, |b|) -- both sides do the same
+operations and differ only by the reassociation of dot products of at most a few hundred float64 terms (order 1e-13); a
+misread formula moves results by 1e-4 or more.  float32 against float32: ``ppo_update_ref.check_rule`` with the float64
+recording as the yardstick (no equality: another machine's BLAS may order sums differently).
+
+What is pinned and what is not: DESIGN.md section 0."""
+import numpy as np
+import pytest
+import torch
+
+from tests import collect_ref, hier_ref, hppo_update_ref as RH, option_ref, ppo_update_ref as R, skill_collect_ref
+from tests import diayn_update_ref as RD, opppo_update_ref as RO, skill_ref, skppo_update_ref as RS, xy_ref
+from tests import xyppo_update_ref as RX
+from tests.agent_goldens import load, sub
+
+F32, F64 = torch.float32, torch.float64
+WORST = {}
+
+
+def close64(family, name, got, want):
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    assert got.shape == want.shape, (name, got.shape, want.shape)
+    fin = np.isfinite(want)
+    assert np.array_equal(fin, np.isfinite(got)), name
+    err = np.abs(got[fin] - want[fin]) / np.maximum(1.0, np.abs(want[fin]))
+    worst = float(err.max()) if err.size else 0.0
+    WORST[family] = max(WORST.get(family, 0.0), worst)
+    print(f"f64 {family}/{name}: {worst:.3e}")
+    assert worst <= 1e-9, f"{name}: float64 restatement and float64 recording differ by {worst:.3e}"
+
+
+def rule32(name, got32, rec64, rec32):
+    fin = np.isfinite(np.asarray(rec64))
+    assert np.array_equal(fin, np.isfinite(np.asarray(got32))), name
+    R.check_rule(name, np.asarray(got32)[fin], np.asarray(rec64)[fin], np.asarray(rec32)[fin])
+
+
+def both(family, name, fn, rec):
+    """fn(dtype) -> array; against the recordings rec['f64/..'], rec['f32/..'] under the two bounds."""
+    close64(family, name, fn(F64), rec[f"f64/{name}"])
+    rule32(f"{family}/{name}", fn(F32), rec[f"f64/{name}"], rec[f"f32/{name}"])
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _report():
+    yield
+    for k in sorted(WORST):
+        print(f"largest float64 difference, {k}: {WORST[k]:.3e}")
+
+
+def _log_softmax(x):
+    return torch.log_softmax(torch.as_tensor(np.asarray(x)), dim=-1).numpy()
+
+
+def _bits(avail):
+    return (avail.astype(np.uint64) << np.arange(avail.shape[1], dtype=np.uint64)).sum(axis=1).astype(np.uint32)
+
+
+# ------------------------------------------------------------------------------------------------ networks
+@pytest.mark.parametrize("tag", ["plain", "dist"])
+def test_flat_network(tag, zenv_mod):
+    rec = sub(load("main", "networks"), f"flat_{tag}/")
+    sd, x = sub(rec, "sd/"), sub(rec, "in/")
+    F = x["zone_obs"].shape[2]
+    assert ("critic_sigma.weight" in sd) == (tag == "dist")
+
+    def run(dt):
+        with torch.no_grad():
+            return R.model_from(sd, F, dt)(torch.as_tensor(x["obs"]).to(dt), torch.as_tensor(x["zone_obs"]).to(dt))
+
+    for i, name in enumerate(("mu", "std", "value") + (("value_sigma",) if tag == "dist" else ())):
+        both("networks", f"out/{name}", lambda dt: run(dt)[i].numpy(), rec)
+    # the loader takes the module's full key set
+    from combinatorial_rl_tasks_amd import agents
+    t = agents.mlp_tensors_from_state_dict(sd)
+    assert len(t) == (20 if tag == "dist" else 18) == len(sd)
+
+
+def test_flat_network_oracle_policy_ref(zenv_mod):
+    """oracle/policy_ref.forward_fp32 on the tensors the loader makes of the recorded state_dict."""
+    from combinatorial_rl_tasks_amd import agents
+    from oracle import policy_ref
+    rec = sub(load("main", "networks"), "flat_plain/")
+    t = {k: torch.as_tensor(v) for k, v in agents.mlp_tensors_from_state_dict(sub(rec, "sd/")).items()}
+    x = sub(rec, "in/")
+    for dt, p in ((F64, "f64"), (F32, "f32")):
+        out = policy_ref.forward_fp32(t, x["obs"], x["zone_obs"], dt)
+        for name, got in zip(("mu", "std"), out):
+            got = got.numpy() if isinstance(got, torch.Tensor) else np.asarray(got)
+            if dt == F64:
+                close64("networks", f"policy_ref/{name}", got, rec[f"f64/out/{name}"])
+            else:
+                rule32(f"policy_ref/{name}", got, rec[f"f64/out/{name}"], rec[f"f32/out/{name}"])
+
+
+def test_zone_goals_networks():
+    rec = sub(load("zone-goals", "networks"), "zone_goals/")
+    hi_sd, lo_sd, x = sub(rec, "hi_sd/"), sub(rec, "lo_sd/"), sub(rec, "in/")
+    Z, F = x["zone_obs"].shape[1:]
+    every = np.full(len(x["obs"]), (1 << Z) - 1, np.uint32)
+    both("networks", "hi_out/raw_logits", lambda dt: hier_ref.high(hi_sd, x["obs"], x["zone_obs"], every, dt)[0], rec)
+    both("networks", "hi_out/value", lambda dt: hier_ref.high(hi_sd, x["obs"], x["zone_obs"], every, dt)[1], rec)
+    # HighPolicyValueModel hands out Categorical(logits=raw) (zone-goals/src/hier_policy_value_models.py:51), which keeps
+    # raw - logsumexp(raw); the restatement returns the raw actor output.  On purpose: compared shift-invariantly.
+    both("networks", "hi_out/logits",
+         lambda dt: _log_softmax(hier_ref.high(hi_sd, x["obs"], x["zone_obs"], every, dt)[0]), rec)
+    # masked goals (_hier_policy_opt.py:32-33): -inf where a goal is unavailable, then a second normalisation
+    avail = x["available"]
+    assert rec["count/masked_goals"] > 0 and rec["count/rows_with_one_goal"] > 0 and rec["count/rows_with_every_goal"] > 0
+    both("networks", "hi_out/masked_logits",
+         lambda dt: _log_softmax(hier_ref.high(hi_sd, x["obs"], x["zone_obs"], _bits(avail), dt)[0]), rec)
+    for i, name in enumerate(("mu", "std", "value")):
+        both("networks", f"lo_out/{name}", lambda dt: hier_ref.low(lo_sd, x["obs"], x["zone_obs"], x["goal"], dt)[i], rec)
+    # the learners' modules
+    for dt, p in ((F64, "f64"), (F32, "f32")):
+        t = {k: torch.as_tensor(v).to(dt) for k, v in x.items() if k != "available"}
+        with torch.no_grad():
+            lg, v = RH.model_from("hi", hi_sd, F, dt)(t["obs"], t["zone_obs"])
+            mu, std, lv = RH.model_from("lo", lo_sd, F, dt)(t["obs"], t["zone_obs"], t["goal"])
+        for name, got in (("hi_out/raw_logits", lg), ("hi_out/value", v), ("lo_out/mu", mu), ("lo_out/std", std),
+                          ("lo_out/value", lv)):
+            if dt == F64:
+                close64("networks", "modelref/" + name, got.numpy(), rec[f"f64/{name}"])
+            else:
+                rule32("modelref/" + name, got.numpy(), rec[f"f64/{name}"], rec[f"f32/{name}"])
+    from combinatorial_rl_tasks_amd import agents
+    assert len(agents.hier_tensors_from_state_dicts(hi_sd, lo_sd)) == len(hi_sd) + len(lo_sd) == 34
+
+
+def _modelref(rec, models, x, extra):
+    """The learners' own modules (the *ModelRef classes) on the recorded state_dicts: models(dt) -> (hi, lo)."""
+    for dt, p in ((F64, "f64"), (F32, "f32")):
+        t = {k: torch.as_tensor(v).to(dt) if np.asarray(v).dtype.kind == "f" else torch.as_tensor(v) for k, v in x.items()}
+        hi, lo = models(dt)
+        with torch.no_grad():
+            h_out, l_out = hi(t["obs"], t["zone_obs"]), lo(t["obs"], t["zone_obs"], t[extra])
+        names = [("hi_out/mu", h_out[0]), ("hi_out/std", h_out[1])] if len(h_out) == 3 else \
+            [("hi_out/logits", torch.log_softmax(h_out[0], dim=1))]
+        names += [("hi_out/value", h_out[-1]), ("lo_out/mu", l_out[0]), ("lo_out/std", l_out[1]), ("lo_out/value", l_out[2])]
+        for name, got in names:
+            if dt == F64:
+                close64("networks", "modelref/" + name, got.numpy(), rec[f"f64/{name}"])
+            else:
+                rule32("modelref/" + name, got.numpy(), rec[f"f64/{name}"], rec[f"f32/{name}"])
+
+
+def test_xy_goals_networks():
+    rec = sub(load("xy-goals", "networks"), "xy_goals/")
+    hi_sd, lo_sd, x = sub(rec, "hi_sd/"), sub(rec, "lo_sd/"), sub(rec, "in/")
+    for i, name in enumerate(("mu", "std", "value")):
+        both("networks", f"hi_out/{name}", lambda dt: xy_ref.high(hi_sd, x["obs"], x["zone_obs"], dt)[i], rec)
+        both("networks", f"lo_out/{name}", lambda dt: xy_ref.low(lo_sd, x["obs"], x["zone_obs"], x["goal"], dt)[i], rec)
+    F = x["zone_obs"].shape[2]
+    _modelref(rec, lambda dt: (RX.model_from("hi", hi_sd, F, dt), RX.model_from("lo", lo_sd, F, dt)), x, "goal")
+    # the head helpers on copies: on this batch no head row's pre-activation leaves [-3, 3], so normalise_heads rescales
+    # nothing and its pre-activations are those of the recorded heads, at both levels
+    hi_c = {k: torch.as_tensor(v).clone() for k, v in hi_sd.items()}
+    lo_c = {k: torch.as_tensor(v).clone() for k, v in lo_sd.items()}
+    pre_hi, pre_lo = xy_ref.normalise_heads(hi_c, lo_c, x["obs"], x["zone_obs"], x["goal"], np.ones(len(x["obs"]), bool))
+    for c, sd in ((hi_c, hi_sd), (lo_c, lo_sd)):
+        assert all(torch.equal(c[k], torch.as_tensor(sd[k])) for k in c), "a head row was rescaled: choose another batch"
+    sig = lambda a: 1.0 / (1.0 + np.exp(-a))
+    for level, pre in (("hi", pre_hi), ("lo", pre_lo)):
+        assert np.abs(pre).max() < 3.0 + 0.5
+        close64("networks", f"xy {level} head pre-activations -> mu", 2.0 * (sig(pre[:, :2]) - 0.5), rec[f"f64/{level}_out/mu"])
+        close64("networks", f"xy {level} head pre-activations -> std", sig(pre[:, 2:]) + 1e-3, rec[f"f64/{level}_out/std"])
+    from combinatorial_rl_tasks_amd import agents
+    assert len(agents.xy_tensors_from_state_dicts(hi_sd, lo_sd)) == len(hi_sd) + len(lo_sd) == 36
+
+
+@pytest.mark.parametrize("agent", ["skills", "options"])
+def test_skill_family_networks(agent):
+    rec = sub(load("main", "skill_networks") if agent == "skills" else load("options", "networks"), f"{agent}/")
+    hi_sd, lo_sd, x = sub(rec, "hi_sd/"), sub(rec, "lo_sd/"), sub(rec, "in/")
+    S = int(x["n_skills"])
+    ref = skill_ref if agent == "skills" else option_ref
+    assert lo_sd["actor.mu_.weight"].shape[0] == (2 if agent == "skills" else 3)
+    # PolicyNetwork's Discrete branch: Categorical(logits=log_softmax(x)) -- the restatement returns the log-softmax
+    both("networks", "hi_out/logits", lambda dt: ref.high(hi_sd, x["obs"], x["zone_obs"], dt)[0], rec)
+    both("networks", "hi_out/value", lambda dt: ref.high(hi_sd, x["obs"], x["zone_obs"], dt)[1], rec)
+    for i, name in enumerate(("mu", "std", "value")):
+        both("networks", f"lo_out/{name}", lambda dt: ref.low(lo_sd, x["obs"], x["zone_obs"], x["skill"], S, dt)[i], rec)
+    F, RM = x["zone_obs"].shape[2], RS if agent == "skills" else RO
+    _modelref(rec, lambda dt: (RM.model_from("hi", hi_sd, F, dt), RM.model_from("lo", lo_sd, F, dt)), x, "skill")
+    from combinatorial_rl_tasks_amd import agents
+    load_fn = agents.skill_tensors_from_state_dicts if agent == "skills" else agents.option_tensors_from_state_dicts
+    assert len(load_fn(hi_sd, lo_sd)) == len(hi_sd) + len(lo_sd) == 34
+
+
+def test_inverse_network():
+    rec = sub(load("main", "skill_networks"), "inverse/")
+    sd, x = sub(rec, "sd/"), sub(rec, "in/")
+    close64("networks", "inverse log_softmax",
+            skill_collect_ref.inverse_log_softmax(sd, x["obs"], x["zone_obs"], F64), _log_softmax(rec["f64/out/logits"]))
+    R.check_rule("inverse/log_softmax", skill_collect_ref.inverse_log_softmax(sd, x["obs"], x["zone_obs"], F32),
+                 _log_softmax(rec["f64/out/logits"]), _log_softmax(rec["f32/out/logits"]))
+    for dt, p in ((F64, "f64"), (F32, "f32")):
+        with torch.no_grad():
+            got = RD.model_from(sd, x["zone_obs"].shape[2], dt)(torch.as_tensor(x["obs"]).to(dt),
+                                                                torch.as_tensor(x["zone_obs"]).to(dt)).numpy()
+        if dt == F64:
+            close64("networks", "InverseRef logits", got, rec["f64/out/logits"])
+        else:
+            rule32("InverseRef/logits", got, rec["f64/out/logits"], rec["f32/out/logits"])
+    from combinatorial_rl_tasks_amd import agents
+    assert len(agents.inverse_tensors_from_state_dict(sd, int(x["n_skills"]))) == len(sd) == 10
+
+
+# ------------------------------------------------------------------------------------------------ updates
+BRANCHES = ("ratio_clipped_high", "ratio_clipped_low", "ratio_unclipped", "value_clipped_term_larger",
+            "value_unclipped_term_larger")
+
+
+def _check_update(family, rec, make_learner, make_batch, first_gradients, full):
+    """Two minibatches with Adam applied.  Parameters after Adam: one step's sensitivity to a gradient error d is
+    lr eps / (|g| + eps)^2 d at the first step (m / sqrt(v) = sign(g) there) and at most lr / (|g| + eps) d later;
+    with lr 3e-4 and eps 1e-8 a 1e-13 reassociation error stays many decades inside the 1e-9 bound."""
+    for b in BRANCHES:
+        assert rec[f"count/{b}"] > 0, b
+    idx = [rec["index0"], rec["index1"]]
+    for dt, p in ((F64, "f64"), (F32, "f32")):
+        grads = first_gradients(dt, make_batch(idx[0], dt))
+        learner = make_learner(dt)
+        stats = np.array([learner.minibatch(make_batch(i, dt)) for i in idx], np.float64)
+        want = sub(rec, f"{p}/grad/")
+        assert len(want) == (len(grads) if full else sum(g.numel() <= 256 for g in grads.values())) and len(want) >= 9
+        state = {k: learner.opt.state[q] for k, q in learner.model.named_parameters()}
+        after = dict(learner.model.named_parameters())
+        checks = [(f"grad/{k}", grads[k].numpy()) for k in want]
+        for k in sub(rec, f"{p}/param/"):
+            checks += [(f"param/{k}", after[k].detach().numpy()), (f"exp_avg/{k}", state[k]["exp_avg"].numpy()),
+                       (f"exp_avg_sq/{k}", state[k]["exp_avg_sq"].numpy())]
+        for i, name in enumerate(R.STATS):
+            if f"{p}/log/{name}" in rec:
+                checks.append((f"log/{name}", stats[:, i]))
+        assert sum(n.startswith("log/") for n, _ in checks) >= 5 and sum(n.startswith("param/") for n, _ in checks) >= 9
+        for name, got in checks:
+            if dt == F64:
+                close64(family, name, got, rec[f"f64/{name}"])
+            else:
+                rule32(f"{family}/{name}", got, rec[f"f64/{name}"], rec[f"f32/{name}"])
+
+
+@pytest.mark.parametrize("tag", ["plain", "dist"])
+def test_flat_update(tag):
+    rec = sub(load("main", "flat_update"), f"flat_{tag}_update/")
+    sd = sub(load("main", "networks"), f"flat_{tag}/sd/")
+    e, h = sub(rec, "exp/"), sub(rec, "hyper/")
+    F = e["zone_obs"].shape[2]
+    hyper = {k: float(h[k]) for k in ("lr", "adam_eps", "clip_eps", "entropy_coef", "value_loss_coef", "max_grad_norm")}
+
+    def batch(idx, dt):
+        return {k: torch.as_tensor(v[idx]).to(dt) for k, v in e.items()}
+
+    def clipped_gradients(dt, b):
+        """The recorder read .grad inside optimizer.step: after clip_grad_norm_ (ppo.py:122), so scaled by its factor."""
+        grads, stats = R.gradients(R.model_from(sd, F, dt), b, hyper)
+        coef = R.clip_coef(stats["grad_norm"], hyper["max_grad_norm"])
+        assert coef < 1.0                                   # the clip is active in the recording
+        return {k: g * coef for k, g in grads.items()}
+
+    _check_update(f"flat_{tag}_update", rec, lambda dt: R.RefLearner(sd, F, dt, hyper), batch, clipped_gradients,
+                  full=tag == "plain")
+
+
+@pytest.mark.parametrize("level", ["hi", "lo"])
+def test_zone_goals_update(level):
+    rec = sub(load("zone-goals", f"{level}_update"), f"zone_goals_{level}_update/")
+    sd = sub(load("zone-goals", "networks"), f"zone_goals/{level}_sd/")
+    e, h = sub(rec, "exp/"), sub(rec, "hyper/")
+    F = e["zone_obs"].shape[2]
+    pre = "hi_" if level == "hi" else ""
+    # the reference's clip_grad_norm_ is commented out at both levels (_hier_policy_opt.py:272, :349): no clip
+    hyper = dict(lr=float(h[pre + "lr"]), adam_eps=float(h["optim_eps"]), clip_eps=float(h["clip_eps"]),
+                 entropy_coef=float(h[pre + "entropy_coef"]),
+                 value_loss_coef=float(h["hi_value_coef" if level == "hi" else "value_loss_coef"]),
+                 max_grad_norm=float("inf"))
+    if level == "hi":
+        assert rec["count/masked_goals"] > 0
+
+    def batch(idx, dt):
+        out = {k: torch.as_tensor(v[idx]) for k, v in e.items()}
+        return {k: v.to(dt) if v.is_floating_point() else v for k, v in out.items()}
+
+    _check_update(f"zone_goals_{level}_update", rec, lambda dt: RH.RefLearner(level, sd, F, dt, hyper), batch,
+                  lambda dt, b: RH.gradients(level, RH.model_from(level, sd, F, dt), b, hyper)[0], full=True)
+
+
+def _hier_hyper(h, level):
+    """The reference clips at neither level (its clip_grad_norm_ lines are commented out in every variant)."""
+    pre = "hi_" if level == "hi" else ""
+    return dict(lr=float(h[pre + "lr"]), adam_eps=float(h["optim_eps"]), clip_eps=float(h["clip_eps"]),
+                entropy_coef=float(h[pre + "entropy_coef"]),
+                value_loss_coef=float(h["hi_value_coef" if level == "hi" else "value_loss_coef"]),
+                max_grad_norm=float("inf"))
+
+
+@pytest.mark.parametrize("level", ["hi", "lo"])
+@pytest.mark.parametrize("agent", ["xy_goals", "skills", "options"])
+def test_other_two_level_updates(agent, level):
+    """update_hi_parameters / update_lo_parameters of the xy-goals, fixed-length-skills and Options variants against
+    xyppo / skppo / opppo_update_ref.RefLearner.  The fixtures keep the tensors of at most 256 elements (every bias and
+    head) for these learners; the skill families' batches leave one skill without a sample."""
+    variant, part, net, RM = {"xy_goals": ("xy-goals", "updates", "networks", RX),
+                              "skills": ("main", "skill_updates", "skill_networks", RS),
+                              "options": ("options", "updates", "networks", RO)}[agent]
+    rec = sub(load(variant, part), f"{agent}_{level}_update/")
+    sd = sub(load(variant, net), f"{agent}/{level}_sd/")
+    e, hyper = sub(rec, "exp/"), _hier_hyper(sub(rec, "hyper/"), level)
+    F = e["zone_obs"].shape[2]
+    if agent != "xy_goals":
+        assert rec["count/skills_without_a_sample"] > 0
+
+    def batch(idx, dt):
+        out = {k: torch.as_tensor(v[idx]) for k, v in e.items()}
+        return {k: v.to(dt) if v.is_floating_point() else v for k, v in out.items()}
+
+    _check_update(f"{agent}_{level}_update", rec, lambda dt: RM.RefLearner(level, sd, F, dt, hyper), batch,
+                  lambda dt, b: RM.gradients(level, RM.model_from(level, sd, F, dt), b, hyper)[0], full=False)
+
+
+def test_inverse_update():
+    """update_inverse_parameters (main/src/torch_ac/algos/_hier_policy_opt.py:421-447) against diayn_update_ref."""
+    rec = sub(load("main", "skill_updates"), "inverse_update/")
+    sd = sub(load("main", "skill_networks"), "inverse/sd/")
+    e = sub(rec, "exp/")
+    F = e["zone_obs"].shape[2]
+    assert rec["count/skills_without_a_sample"] > 0
+    hyper = dict(lr=float(rec["hyper/lr"]), adam_eps=float(rec["hyper/optim_eps"]))
+    idx = [rec["index0"], rec["index1"]]
+    for dt, p in ((F64, "f64"), (F32, "f32")):
+        b = [{"obs": torch.as_tensor(e["obs"][i]).to(dt), "zone_obs": torch.as_tensor(e["zone_obs"][i]).to(dt),
+              "skill": torch.as_tensor(e["skill"][i])} for i in idx]
+        grads, _ = RD.gradients(RD.model_from(sd, F, dt), b[0])
+        learner = RD.RefLearner(sd, F, dt, hyper)
+        losses = np.array([learner.minibatch(x)["loss"] for x in b])
+        state = {k: learner.opt.state[q] for k, q in learner.model.named_parameters()}
+        after = dict(learner.model.named_parameters())
+        checks = [("log/loss", losses)] + [(f"grad/{k}", grads[k].numpy()) for k in sub(rec, f"{p}/grad/")]
+        for k in sub(rec, f"{p}/param/"):
+            checks += [(f"param/{k}", after[k].detach().numpy()), (f"exp_avg/{k}", state[k]["exp_avg"].numpy()),
+                       (f"exp_avg_sq/{k}", state[k]["exp_avg_sq"].numpy())]
+        assert len(checks) >= 1 + 6 + 18
+        for name, got in checks:
+            if dt == F64:
+                close64("inverse_update", name, got, rec[f"f64/{name}"])
+            else:
+                rule32(f"inverse_update/{name}", got, rec[f"f64/{name}"], rec[f"f32/{name}"])
+
+
+def test_skill_prior_update():
+    """Two update_skill_prior steps (:449-464; Adam, lr 1e-2) against PriorRef and prior_step_numpy."""
+    rec = sub(load("main", "skill_updates"), "prior_update/")
+    assert rec["count/skills_without_a_sample"] > 0
+    actions = rec["actions"]
+    hyper = dict(lr=float(rec["hyper/lr"]), adam_eps=float(rec["hyper/optim_eps"]))
+    S = len(rec["f64/logits0"])
+    for dt, p in ((F64, "f64"), (F32, "f32")):
+        ref = RD.PriorRef(rec[f"{p}/logits0"], dt, hyper)
+        for step in (1, 2):
+            got = ref.step(actions)
+            probs = torch.softmax(torch.as_tensor(got), dim=0).numpy()
+            if dt == F64:
+                close64("prior_update", f"logits{step}", got, rec[f"f64/logits{step}"])
+                close64("prior_update", f"probs{step}", probs, rec[f"f64/probs{step}"])
+            else:
+                rule32(f"prior_update/logits{step}", got, rec[f"f64/logits{step}"], rec[f"f32/logits{step}"])
+    z = rec["f64/logits0"].astype(np.float64).copy()
+    m, v = np.zeros(S), np.zeros(S)
+    for step in (1, 2):
+        RD.prior_step_numpy(z, m, v, actions, step, hyper)
+        close64("prior_update", f"numpy logits{step}", z, rec[f"f64/logits{step}"])
+
+
+# ------------------------------------------------------------------------------------------------ collection
+def test_flat_collection_bookkeeping():
+    """Two consecutive collect_experiences calls of BaseAlgo (main/src/torch_ac/algos/base.py:131-227) over scripted
+    environments: which reward enters (info['shaped_reward'] where present), the mask one frame behind done and carried
+    across calls, the GAE with the bootstrap value of the observation after the window, and the [env][frame] row order."""
+    rec = sub(load("main", "flat_collect"), "flat_collect/")
+    for k in ("episode_end_inside_window", "episode_end_on_window_last_frame", "env_without_episode_end",
+              "episode_end_on_window_first_frame"):
+        assert rec[f"count/{k}"] > 0, k
+    N, T = (int(v) for v in rec["shape/NT"])
+    g, lam = float(rec["hyper/discount"]), float(rec["hyper/gae_lambda"])
+    done, shaped = rec["stream/done"], rec["stream/shaped_reward"]
+    assert done.shape == (2 * T, N) and not np.array_equal(shaped, rec["stream/reward"])
+    for p in ("f64", "f32"):
+        for call in range(2):
+            x = sub(rec, f"{p}/call{call}/")
+            frames = slice(call * T, (call + 1) * T)
+            # mask[i] = 1 - done of the frame before, 1 before the very first frame
+            before = np.concatenate([np.zeros((1, N), bool), done])[frames]
+            mask = 1.0 - before.astype(np.float64)
+            cur_mask = 1.0 - done[(call + 1) * T - 1].astype(np.float64)
+            np.testing.assert_array_equal(x["cur_mask"], cur_mask)
+            np.testing.assert_array_equal(x["masks"], mask)            # self.masks [T, N]: one frame behind done
+            value = x["exps.value"].reshape(N, T).T
+            adv, ret, _ = collect_ref.gae(shaped[frames], value, mask, cur_mask, x["next_value"], g, lam)
+            flat = lambda a: np.ascontiguousarray(a.T).reshape(-1)          # [T, N] -> the reference's [env][frame] rows
+            np.testing.assert_array_equal(x["exps.reward"], flat(shaped[frames]).astype(x["exps.reward"].dtype))
+            np.testing.assert_array_equal(x["exps.obs.obs"], np.ascontiguousarray(
+                rec["stream/obs"][frames].swapaxes(0, 1)).reshape(N * T, 8))
+            np.testing.assert_array_equal(x["exps.action"].reshape(N, T, 2).swapaxes(0, 1), rec[f"{p}/stream/action"][frames])
+            if p == "f64":
+                close64("flat_collect", f"call{call}/advantage", flat(adv), x["exps.advantage"])
+                close64("flat_collect", f"call{call}/returnn", flat(ret), x["exps.returnn"])
+            else:
+                x64 = sub(rec, f"f64/call{call}/")
+                # float32 records: the recursion on the float32 run's own values, against that run's advantages; the two
+                # runs drew different actions, so the float64 run is no yardstick here -- float32 rounding of a T-frame
+                # recursion whose terms are of order 1: 2^-24 * magnitude per step, a few steps deep
+                _, _, mag = collect_ref.gae(shaped[frames], value, mask, cur_mask, x["next_value"], g, lam)
+                err = np.abs(flat(adv) - x["exps.advantage"])
+                assert np.all(err <= 4 * 2.0 ** -24 * flat(mag)), float((err / flat(mag)).max())
+                assert x64["exps.advantage"].dtype == np.float64
+
+
+def test_zone_goals_collection_bookkeeping():
+    """Two consecutive collect_experiences calls of the Zone-goals HierPolicyAlgo (zone-goals/src/torch_ac/algos/
+    _hier_policy_opt.py:9-194) over scripted goal environments, against hier_collect_ref.expected_hi (the high level:
+    which transitions close in which call, their rewards, masks, bootstrap values, the undiscounted GAE, the
+    [env][transition] row order) and collect_ref.gae on the first T - 1 frames (the low level: frame T - 1 only lends
+    its value and mask, its own advantage stays 0 and it is cut from lo_exps)."""
+    from tests import hier_collect_ref
+    rec = sub(load("zone-goals", "collect"), "zone_goals_collect/")
+    for k in ("transition_closed_by_episode_end", "transition_closed_by_reaching_the_goal", "transition_spanning_two_calls",
+              "env_that_never_closes_a_transition", "episode_end_inside_window", "episode_end_on_window_last_frame",
+              "goal_reached_on_the_step_the_episode_ends", "goal_reached_on_window_last_frame", "masked_goals_at_a_pick"):
+        assert rec[f"count/{k}"] > 0, k
+    N, T = (int(v) for v in rec["shape/NT"])
+    g, lam = float(rec["hyper/discount"]), float(rec["hyper/gae_lambda"])
+    assert lam == hier_collect_ref.LAM and g == hier_collect_ref.GAMMA
+    done, shaped, reward = rec["stream/done"], rec["stream/shaped_reward"], rec["stream/reward"]
+    for p, np_dt in (("f64", np.float64), ("f32", np.float32)):
+        b = {"obs": rec["stream/obs"][:-1], "need": rec["stream/need"], "goal": rec[f"{p}/stream/goal"],
+             "reward": reward.astype(np_dt), "need_after": rec["stream/need_after"], "done": done,
+             "pick_value": rec[f"{p}/stream/pick_value"].astype(np_dt)}
+        exp, seen = hier_collect_ref.expected_hi(b, T, 2, rec[f"{p}/stream/v_final"].astype(np_dt), dtype=np_dt)
+        cur_goal = rec[f"{p}/stream/goal_xy"].copy()            # get_goal() at the picks; cur_goal stays until the next
+        for t in range(1, len(cur_goal)):
+            keep = b["goal"][t] < 0
+            cur_goal[t, keep] = cur_goal[t - 1, keep]
+        assert seen["span"] > 0 and seen["mask0"] > 0 and seen["mask1"] > 0 and seen["bootstrap"] > 0
+        for call in range(2):
+            x = sub(rec, f"{p}/call{call}/")
+            fr = slice(call * T, (call + 1) * T)
+            rows = [r for j in range(N) for r in exp[call][j]]                  # [env][transition]
+            assert len(rows) == len(x["hi_exps.action"]) and len(rows) > 0
+            np.testing.assert_array_equal([r["goal"] for r in rows], x["hi_exps.action"])
+            np.testing.assert_array_equal(np.stack([rec["stream/obs"][r["t_pick"], j] for j in range(N)
+                                                    for r in exp[call][j]]), x["hi_exps.obs.obs"])
+            np.testing.assert_array_equal(np.stack([rec["stream/available"][r["t_pick"], j] for j in range(N)
+                                                    for r in exp[call][j]]), x["hi_exps.action_mask"])
+            got = {"value": [r["value"] for r in rows], "advantage": [r["adv"] for r in rows],
+                   "returnn": [r["value"] + r["adv"] for r in rows]}
+            # low level
+            mask = 1.0 - np.concatenate([np.zeros((1, N), bool), done])[fr].astype(np.float64)
+            np.testing.assert_array_equal(x["lo_masks"], mask)
+            np.testing.assert_array_equal(x["lo_rewards"], shaped[fr].astype(np_dt))
+            np.testing.assert_array_equal(x["rewards"], reward[fr].astype(np_dt))
+            v = x["lo_values"]
+            adv, ret, mag = collect_ref.gae(shaped[fr][:T - 1], v[:T - 1], mask[:T - 1], mask[T - 1], v[T - 1], g, lam)
+            flat = lambda a: np.ascontiguousarray(a.T).reshape(-1)
+            assert not x["lo_advantages"][T - 1].any() and x["lo_exps.value"].shape == (N * (T - 1),)
+            np.testing.assert_array_equal(x["lo_exps.value"], flat(v[:T - 1]))
+            np.testing.assert_array_equal(x["lo_exps.obs.obs"], np.ascontiguousarray(
+                rec["stream/obs"][fr][:T - 1].swapaxes(0, 1)).reshape(N * (T - 1), 8))
+            np.testing.assert_array_equal(x["lo_exps.obs.goal"], np.ascontiguousarray(
+                cur_goal[fr][:T - 1].swapaxes(0, 1)).reshape(N * (T - 1), 2).astype(np_dt))
+            if p == "f64":
+                for k, a in got.items():
+                    close64("zone_goals_collect", f"call{call}/hi_exps.{k}", a, x[f"hi_exps.{k}"])
+                close64("zone_goals_collect", f"call{call}/lo_exps.advantage", flat(adv), x["lo_exps.advantage"])
+                close64("zone_goals_collect", f"call{call}/lo_exps.returnn", flat(ret), x["lo_exps.returnn"])
+            else:
+                # the float32 run drew its own goals and actions, so the float64 run is no yardstick: float32 rounding of
+                # short recursions whose terms are of order 1 -- 4 x 2^-24 x the terms' magnitude (collect_ref.gae's)
+                err = np.abs(flat(adv) - x["lo_exps.advantage"])
+                assert np.all(err <= 4 * 2.0 ** -24 * flat(mag)), float((err / flat(mag)).max())
+                hi_mag = np.array([abs(r["reward"]) + abs(r["v_next"]) + abs(r["value"]) for r in rows]) + \
+                    np.abs(x["hi_exps.advantage"])
+                for k, a in got.items():
+                    err = np.abs(np.asarray(a, np.float64) - x[f"hi_exps.{k}"])
+                    assert np.all(err <= 4 * len(rows) * 2.0 ** -24 * hi_mag.max()), (k, float(err.max()))
+
+
+def test_skills_collection_bookkeeping():
+    """Two consecutive collect_experiences calls of main's HierPolicyAlgo (main/src/torch_ac/algos/_hier_policy_opt.py:
+    10-233) over the reference's WaitWrapper around scripted environments, against skill_collect_ref.bookkeeping (both
+    GAEs, the window sums, next_mask, num_frames, the inverse-exps selection) and inverse_log_softmax (the diversity
+    reward: the next observation, or on a window's last frame of a finished env the one before the step)."""
+    rec = sub(load("main", "skill_collect"), "skills_collect/")
+    for k in ("episode_end_inside_a_skill", "episode_end_on_a_skill_last_frame", "noop_frames_after_an_episode_end",
+              "env_without_episode_end", "episode_end_in_the_windows_last_skill"):
+        assert rec[f"count/{k}"] > 0, k
+    inv_sd = sub(load("main", "skill_networks"), "inverse/sd/")
+    N, T, L = (int(v) for v in rec["shape/NTL"])
+    g, lam, coef = (float(rec[f"hyper/{k}"]) for k in ("discount", "gae_lambda", "diversity_coef"))
+    done, reward, obs, zone = rec["stream/done"], rec["stream/reward"], rec["stream/obs"], rec["stream/zone_obs"]
+    flat = lambda a: np.ascontiguousarray(np.swapaxes(a, 0, 1)).reshape((-1,) + a.shape[2:])   # [T, N] -> [env][frame]
+    for p, np_dt, dt in (("f64", np.float64, F64), ("f32", np.float32, F32)):
+        prior = _log_softmax(rec[f"{p}/skill_logits"].astype(np.float64))
+        for call in range(2):
+            x = sub(rec, f"{p}/call{call}/")
+            fr = np.arange(call * T, (call + 1) * T)
+            mask = 1.0 - np.concatenate([np.zeros((1, N), bool), done])[fr].astype(np.float64)
+            cur_mask = 1.0 - done[fr[-1]].astype(np.float64)
+            np.testing.assert_array_equal(x["lo_masks"], mask)
+            np.testing.assert_array_equal(x["lo_mask"], cur_mask)
+            np.testing.assert_array_equal(x["rewards"], reward[fr].astype(np_dt))
+            skills = x["lo_skills"]
+            assert np.array_equal(skills, np.repeat(skills[::L], L, axis=0))            # one skill per window
+            # the diversity reward
+            last = (fr % L == L - 1)[:, None] & done[fr]
+            nxt = np.where(last, fr[:, None], fr[:, None] + 1)                            # [T, N] frame of next_obs
+            jj = np.broadcast_to(np.arange(N), (T, N))
+            lsm = skill_collect_ref.inverse_log_softmax(inv_sd, obs[nxt, jj].reshape(T * N, 8),
+                                                        zone[nxt, jj].reshape((T * N,) + zone.shape[2:]), dt)
+            lsm = np.asarray(lsm, np.float64).reshape(T, N, -1)
+            div = (np.take_along_axis(lsm, skills[..., None], axis=2)[..., 0] - prior[skills]) * ~done[fr]
+            want_lo_reward = reward[fr] + coef * div
+            bk = skill_collect_ref.bookkeeping(reward[fr], x["lo_rewards"], mask, cur_mask, x["lo_values"], x["hi_values"],
+                                               x["next_lo_value"], x["next_hi_value"], L, g, lam, dtype=np_dt)
+            assert bk["num_frames"] == int(rec[f"call{call}/num_frames"])
+            ii, jx = bk["inverse_idx"]
+            np.testing.assert_array_equal(x["inverse_exps.obs.obs"], obs[fr][ii + 1, jx])
+            np.testing.assert_array_equal(x["inverse_exps.skill"], skills[ii, jx])
+            np.testing.assert_array_equal(x["lo_exps.obs.obs"], flat(obs[fr]))
+            np.testing.assert_array_equal(x["lo_exps.obs.skill"], flat(skills))
+            np.testing.assert_array_equal(x["hi_exps.obs.obs"], flat(obs[fr][::L]))
+            np.testing.assert_array_equal(x["hi_exps.action"], flat(skills[::L]))
+            np.testing.assert_array_equal(x["hi_exps.value"], flat(x["hi_values"]))
+            np.testing.assert_array_equal(x["lo_exps.value"], flat(x["lo_values"]))
+            pairs = [("lo_rewards", want_lo_reward, x["lo_rewards"]), ("hi_rewards", bk["hi_reward"], x["hi_rewards"]),
+                     ("lo_exps.advantage", flat(bk["lo_adv"]), x["lo_exps.advantage"]),
+                     ("hi_exps.advantage", flat(bk["hi_adv"]), x["hi_exps.advantage"]),
+                     ("lo_exps.returnn", flat(bk["lo_adv"] + x["lo_values"]), x["lo_exps.returnn"]),
+                     ("hi_exps.returnn", flat(bk["hi_adv"] + x["hi_values"]), x["hi_exps.returnn"])]
+            for name, got, want in pairs:
+                if p == "f64":
+                    close64("skills_collect", f"call{call}/{name}", got, want)
+                else:
+                    # the float32 run drew its own skills and actions: no float64 yardstick.  Recursions of at most T
+                    # float32 steps on terms of order 1 to 10: T x 4 x 2^-24 x the largest magnitude involved
+                    scale = max(1.0, float(np.abs(want).max()), float(np.abs(x["lo_values"]).max()))
+                    assert np.abs(np.asarray(got, np.float64) - want).max() <= T * 4 * 2.0 ** -24 * scale, name
+
+
+def test_options_collection_bookkeeping():
+    """Two consecutive collect_experiences calls of the Options HierPolicyAlgo (options/src/torch_ac/algos/
+    _hier_policy_opt.py:10-195) over scripted environments, against option_collect_ref.expected_hi, collect_ref.gae on
+    the first T - 1 frames, and option_ref.term_prob: an option ends where the recorded uniform lies below
+    sigmoid(4 a_2 - 3) of the recorded third action component (:48, :70)."""
+    from tests import option_collect_ref
+    rec = sub(load("options", "collect"), "options_collect/")
+    N, T = (int(v) for v in rec["shape/NT"])
+    g, lam = float(rec["hyper/discount"]), float(rec["hyper/gae_lambda"])
+    done, reward, obs = rec["stream/done"], rec["stream/reward"], rec["stream/obs"]
+    flat = lambda a: np.ascontiguousarray(np.swapaxes(a, 0, 1)).reshape((-1,) + a.shape[2:])
+    for p, np_dt in (("f64", np.float64), ("f32", np.float32)):
+        for k in ("option_ended_by_its_own_termination", "option_ended_on_an_episode_end",
+                  "option_surviving_an_episode_end", "env_frames_without_a_pick"):
+            assert rec[f"{p}/count/{k}"] > 0, k
+        pick, ended, skill = (rec[f"{p}/stream/{k}"] for k in ("pick", "ended", "skill"))
+        actions = np.concatenate([rec[f"{p}/call{c}/lo_actions"] for c in range(2)])          # [2T, N, 3]
+        # the termination test; a draw within float rounding of the probability would be undecided, none is
+        prob, u = option_ref.term_prob(actions[..., 2]), rec[f"{p}/stream/term_uniform"]
+        assert np.abs(u - prob).min() > 1e-6
+        np.testing.assert_array_equal(ended, u < prob)
+        assert np.ptp(prob) > 0.2 and ended.any() and not ended.all()             # the head is exercised over a range
+        # a pick follows every end, and the very first frame
+        np.testing.assert_array_equal(pick, np.concatenate([np.ones((1, N), bool), ended[:-1]]))
+        b = {"pick": pick, "ended": ended, "done": done, "reward": reward.astype(np_dt), "skill": skill,
+             "pick_value": rec[f"{p}/stream/pick_value"].astype(np_dt)}
+        exp, seen = option_collect_ref.expected_hi(b, T, 2, rec[f"{p}/stream/v_final"].astype(np_dt), lam, dtype=np_dt)
+        assert seen["mask0"] > 0 and seen["mask1"] > 0 and seen["survived"] > 0 and seen["span"] > 0
+        for call in range(2):
+            x = sub(rec, f"{p}/call{call}/")
+            fr = slice(call * T, (call + 1) * T)
+            rows = [r for j in range(N) for r in exp[call][j]]
+            assert len(rows) == len(x["hi_exps.action"]) > 0
+            np.testing.assert_array_equal([r["skill"] for r in rows], x["hi_exps.action"])
+            np.testing.assert_array_equal(np.stack([obs[r["t_pick"], j] for j in range(N) for r in exp[call][j]]),
+                                          x["hi_exps.obs.obs"])
+            got = {"value": [r["value"] for r in rows], "advantage": [r["adv"] for r in rows],
+                   "returnn": [r["value"] + r["adv"] for r in rows]}
+            mask = 1.0 - np.concatenate([np.zeros((1, N), bool), done])[fr].astype(np.float64)
+            np.testing.assert_array_equal(x["lo_masks"], mask)
+            np.testing.assert_array_equal(x["lo_rewards"], reward[fr].astype(np_dt))
+            v = x["lo_values"]
+            adv, ret, mag = collect_ref.gae(reward[fr][:T - 1], v[:T - 1], mask[:T - 1], mask[T - 1], v[T - 1], g, lam)
+            assert not x["lo_advantages"][T - 1].any() and x["lo_exps.value"].shape == (N * (T - 1),)
+            np.testing.assert_array_equal(x["lo_exps.action"], flat(x["lo_actions"][:T - 1]))
+            np.testing.assert_array_equal(x["lo_exps.obs.skill"], flat(skill[fr][:T - 1]))
+            np.testing.assert_array_equal(x["lo_exps.obs.obs"], flat(obs[fr][:T - 1]))
+            if p == "f64":
+                for k, a in got.items():
+                    close64("options_collect", f"call{call}/hi_exps.{k}", a, x[f"hi_exps.{k}"])
+                close64("options_collect", f"call{call}/lo_exps.advantage", flat(adv), x["lo_exps.advantage"])
+                close64("options_collect", f"call{call}/lo_exps.returnn", flat(ret), x["lo_exps.returnn"])
+            else:
+                # the float32 run drew for itself: no float64 yardstick.  Short float32 recursions on terms of order 1
+                err = np.abs(flat(adv) - x["lo_exps.advantage"])
+                assert np.all(err <= 4 * 2.0 ** -24 * flat(mag)), float((err / flat(mag)).max())
+                scale = max(1.0, max(abs(r["reward"]) + abs(r["v_next"]) + abs(r["value"]) for r in rows),
+                            float(np.abs(x["hi_exps.advantage"]).max()))
+                for k, a in got.items():
+                    err = np.abs(np.asarray(a, np.float64) - x[f"hi_exps.{k}"])
+                    assert np.all(err <= 4 * len(rows) * 2.0 ** -24 * scale), (k, float(err.max()))
+
+
+def test_xy_goals_collection_bookkeeping():
+    """Two consecutive collect_experiences calls of the xy-goals HierPolicyAlgo (xy-goals/src/torch_ac/algos/
+    _hier_policy_opt.py:10-192) over the reference's WaitWrapper around scripted environments, against xy_collect_ref:
+    goal_dist (the goal's distance from obs[1:3]), bookkeeping (the distance reward inside a window, both GAEs, the
+    window sums, next_mask, num_frames), hi_log_prob, and the goal carried over its window."""
+    from tests import xy_collect_ref as XC
+    rec = sub(load("xy-goals", "collect"), "xy_goals_collect/")
+    for k in ("episode_end_inside_a_window", "episode_end_on_a_window_last_frame", "noop_frames_after_an_episode_end",
+              "env_without_episode_end", "episode_end_in_the_calls_last_window"):
+        assert rec[f"count/{k}"] > 0, k
+    hi_sd = sub(load("xy-goals", "networks"), "xy_goals/hi_sd/")
+    N, T, L = (int(v) for v in rec["shape/NTL"])
+    g, lam = float(rec["hyper/discount"]), float(rec["hyper/gae_lambda"])
+    done, reward, obs, zone = rec["stream/done"], rec["stream/reward"], rec["stream/obs"], rec["stream/zone_obs"]
+    flat = lambda a: np.ascontiguousarray(np.swapaxes(a, 0, 1)).reshape((-1,) + a.shape[2:])   # [T, N] -> [env][frame]
+    for p, np_dt, dt in (("f64", np.float64, F64), ("f32", np.float32, F32)):
+        for call in range(2):
+            x = sub(rec, f"{p}/call{call}/")
+            fr = np.arange(call * T, (call + 1) * T)
+            mask = 1.0 - np.concatenate([np.zeros((1, N), bool), done])[fr].astype(np.float64)
+            cur_mask = 1.0 - done[fr[-1]].astype(np.float64)
+            np.testing.assert_array_equal(x["lo_masks"], mask)
+            np.testing.assert_array_equal(x["lo_mask"], cur_mask)
+            np.testing.assert_array_equal(x["rewards"], reward[fr].astype(np_dt))
+            np.testing.assert_array_equal(x["lo_goals"], np.repeat(x["hi_goals"], L, axis=0))   # one goal per window
+            np.testing.assert_array_equal(x["lo_exps.obs.obs"], flat(obs[fr]))
+            np.testing.assert_array_equal(x["lo_exps.obs.goal"], flat(x["lo_goals"]))
+            np.testing.assert_array_equal(x["lo_exps.value"], flat(x["lo_values"]))
+            np.testing.assert_array_equal(x["hi_exps.obs.obs"], flat(obs[fr][::L]))
+            np.testing.assert_array_equal(x["hi_exps.goal"], flat(x["hi_goals"]))
+            np.testing.assert_array_equal(x["hi_exps.value"], flat(x["hi_values"]))
+            np.testing.assert_array_equal(x["hi_exps.log_prob"], flat(x["hi_log_probs"]))
+            dist = XC.goal_dist(obs[fr], x["lo_goals"], dtype=np_dt)
+            bk = XC.bookkeeping(dist, reward[fr], mask, cur_mask, x["lo_values"], x["hi_values"], x["next_lo_value"],
+                                x["next_hi_value"], L, g, lam, dtype=np_dt)
+            assert bk["num_frames"] == int(rec[f"call{call}/num_frames"])
+            assert not bk["lo_reward"][L - 1::L].any() and bk["lo_reward"].any()
+            pairs = [("lo_dists_to_goal", dist, x["lo_dists_to_goal"]), ("hi_rewards", bk["hi_reward"], x["hi_rewards"]),
+                     ("lo_exps.advantage", flat(bk["lo_adv"]), x["lo_exps.advantage"]),
+                     ("hi_exps.advantage", flat(bk["hi_adv"]), x["hi_exps.advantage"]),
+                     ("lo_exps.returnn", flat(bk["lo_adv"] + x["lo_values"]), x["lo_exps.returnn"]),
+                     ("hi_exps.returnn", flat(bk["hi_adv"] + x["hi_values"]), x["hi_exps.returnn"])]
+            for name, got, want in pairs:
+                if p == "f64":
+                    close64("xy_goals_collect", f"call{call}/{name}", got, want)
+                else:
+                    # the float32 run drew its own goals and actions: no float64 yardstick.  Recursions of at most T
+                    # float32 steps on terms of order 1 to 10: T x 4 x 2^-24 x the largest magnitude involved
+                    scale = max(1.0, float(np.abs(want).max()), float(np.abs(x["lo_values"]).max()))
+                    assert np.abs(np.asarray(got, np.float64) - want).max() <= T * 4 * 2.0 ** -24 * scale, name
+            if p == "f32":
+                # hi_log_prob is float64 arithmetic on float32 operands: against the float32 run's own record, whose
+                # three terms per dimension are rounded to float32 -- 8 x 2^-24 x the sum of the terms' magnitudes
+                picks = obs[fr][::L].reshape(-1, 8), zone[fr][::L].reshape((-1,) + zone.shape[2:])
+                mu, std, _ = xy_ref.high(hi_sd, picks[0], picks[1], F32)
+                goal = x["hi_goals"].reshape(-1, 2)
+                got = XC.hi_log_prob(goal, mu, std)
+                zz = ((goal - mu) / std).astype(np.float64)
+                mag = (0.5 * zz * zz + np.abs(np.log(std.astype(np.float64))) + 0.92).sum(-1)
+                # mu and std come from a float32 forward of another batch shape: their few-ulp change moves the
+                # quadratic term by |z| (|z| + 1) ulp
+                mag = mag + (np.abs(zz) * (np.abs(zz) + 1.0) * 4).sum(-1)
+                assert np.all(np.abs(got - x["hi_log_probs"].reshape(-1)) <= 8 * 2.0 ** -24 * mag)

@@ -17,19 +17,20 @@ LAM, GAMMA = 0.95, 0.99
 TAG_XY_BOOT = 0x585942
 
 
-def goal_dist(obs, goal):
-    """float32 [..]: sqrt((goal_x - obs[1])^2 + (goal_y - obs[2])^2), every operation rounded to float32."""
-    f = np.float32
+def goal_dist(obs, goal, dtype=np.float32):
+    """float32 [..]: sqrt((goal_x - obs[1])^2 + (goal_y - obs[2])^2), every operation rounded to float32 (or carried
+    out in `dtype`: float64 for a float64 record)."""
+    f = dtype
     obs, goal = np.asarray(obs, f), np.asarray(goal, f)
     dx = (goal[..., 0] - obs[..., 1]).astype(f)
     dy = (goal[..., 1] - obs[..., 2]).astype(f)
     return np.sqrt(((dx * dx).astype(f) + (dy * dy).astype(f)).astype(f)).astype(f)
 
 
-def lo_reward(dist, mask, L):
+def lo_reward(dist, mask, L, dtype=np.float32):
     """float32 [T, N]: (dist[t] - dist[t+1]) * (mask[t+1] * ((t+1) % L != 0)); frame T-1 is 0 (T is a multiple of L:
-    the reference multiplies it by (T % L != 0) = 0)."""
-    f = np.float32
+    the reference multiplies it by (T % L != 0) = 0).  dtype: the arithmetic's."""
+    f = dtype
     dist, mask = np.asarray(dist, f), np.asarray(mask, f)
     T = dist.shape[0]
     out = np.zeros_like(dist)
@@ -40,11 +41,12 @@ def lo_reward(dist, mask, L):
 
 
 def bookkeeping(dist, env_reward, mask, cur_mask, lo_value, hi_value, next_lo_value, next_hi_value, L,
-                discount=GAMMA, gae_lambda=LAM):
+                discount=GAMMA, gae_lambda=LAM, dtype=np.float32):
     """On time-major records: dist / env_reward / mask / lo_value [T, N], hi_value [W, N], cur_mask (the mask after the
     frames, carried into the next call), next_*_value [N].  Returns the low level's reward and advantage [T, N]; the
-    high level's reward, next_mask and advantage [W, N]; num_frames."""
-    f = np.float32
+    high level's reward, next_mask and advantage [W, N]; num_frames.  dtype: the arithmetic's (float32: the device's;
+    float64 for a float64 record)."""
+    f = dtype
     env_reward, mask, lo_value = (np.asarray(a, f) for a in (env_reward, mask, lo_value))
     hi_value = np.asarray(hi_value, f)
     cur_mask = np.asarray(cur_mask, f)
@@ -63,7 +65,7 @@ def bookkeeping(dist, env_reward, mask, cur_mask, lo_value, hi_value, next_lo_va
         delta = r + nv * nm - hi_value[k]                           # no discount
         hi_adv[k] = delta + f(gae_lambda) * na * nm
         hi_reward[k], hi_mask[k] = r, nm
-    lo_r = lo_reward(dist, mask, L)
+    lo_r = lo_reward(dist, mask, L, dtype)
     lo_adv = np.zeros((T, N), f)
     for i in reversed(range(T)):
         nm = mask[i + 1] if i < T - 1 else cur_mask
