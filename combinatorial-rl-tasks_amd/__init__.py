@@ -5,7 +5,7 @@ Layout of this package (only what the hot path needs):
   _native.py   ctypes binding (no PyTorch, no CPU fallback)
   vec_env.py   ZoneVecEnv: N device-resident envs, struct-of-arrays results
   agents.py    the five agents' pure host functions: checkpoint -> tensors, tensor shapes, collector argument checks,
-               experience layouts (no shared library needed)
+               experience layouts, the keys of each collector's episode logs (no shared library needed)
   envs/        host-side mirror of the reference interface (main/envs/*): registry ids,
                TSPEnv/TimedTSPEnv/ColourMatchEnv, FixedSeedsWrapper/ZoneWrapper, make_*_env
   penv.py      ParallelEnv-shaped vector env over one batched handle
@@ -38,6 +38,7 @@ from .vec_env import (ZoneVecEnv, config_for_id, default_config, sample_layout,
                       xy_tensors_from_state_dicts, xy_experience_layout, check_collect_xy_args,
                       mlp_tensors_from_state_dict, ppo_state_dict_keys, ppo_batch_indexes, ppo_logs,
                       hppo_state_dict_keys, hppo_batch_indexes, xyppo_state_dict_keys, skppo_state_dict_keys,
-                      opppo_state_dict_keys, diayn_state_dict_keys, diayn_kept_samples)
+                      opppo_state_dict_keys, diayn_state_dict_keys, diayn_kept_samples,
+                      EPISODE_LOG_KEYS, episode_log_columns, episode_log_keys, synthesize_stats)
 
 __version__ = "0.1.0"

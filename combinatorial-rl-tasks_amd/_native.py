@@ -155,6 +155,18 @@ class RenderConfig(C.Structure):
                 ("view", C.c_float), ("robot_radius", C.c_float)]
 
 
+# the columns of zenv_episode_log (ZENV_EPLOG_*) and the key each has in the reference's `logs`
+(EPLOG_RETURN, EPLOG_RESHAPED_RETURN, EPLOG_NUM_FRAMES, EPLOG_DIVERSITY, EPLOG_PREDICTION, EPLOG_ENV) = range(6)
+EPLOG_COUNT = 6
+EPLOG_KEYS = ("return_per_episode", "reshaped_return_per_episode", "num_frames_per_episode", "diversity_per_episode",
+              "prediction_per_episode", "env_per_episode")
+
+
+class EpisodeLogInfo(C.Structure):
+    """struct zenv_episode_log_info (include/zenv.h)."""
+    _fields_ = [("kept", C.c_int64), ("done", C.c_int64), ("num_frames", C.c_int64), ("columns", C.c_int64)]
+
+
 class ZenvError(RuntimeError):
     def __init__(self, code, message):
         super().__init__(f"zenv error {code}: {message}")
@@ -333,6 +345,11 @@ _PROTOTYPES = {
     "zenv_comm_allreduce_max": (C.c_int, [_H, C.POINTER(C.c_double)]),
     "zenv_render_check": (C.c_int, [C.POINTER(Config), C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "zenv_render": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    "zenv_episode_log": (C.c_int, [_H, C.POINTER(EpisodeLogInfo)]),
+    "zenv_episode_log_tensor": (C.c_int, [_H, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    "zenv_episode_log_read": (C.c_int, [_H, C.c_int, C.c_void_p]),
+    "zenv_episode_log_stats": (C.c_int, [_H, C.c_int, C.POINTER(C.c_double)]),
+    "zenv_episode_log_reset": (C.c_int, [_H]),
     "zenv_probe_store_stream": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.POINTER(C.c_float)]),
     "zenv_step_count": (C.c_int64, [_H]),

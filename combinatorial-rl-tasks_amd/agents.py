@@ -1,6 +1,7 @@
 """What the five device agents -- the flat actor-critic, Zone-goals, fixed-length skills / DIAYN, Options and xy-goals
 -- need on the host before and after a call into the library: checkpoint (state_dict) -> named float32 tensors, the shape every
-tensor must have, the argument rules of the collectors and the layout of the experience buffers they fill.
+tensor must have, the argument rules of the collectors, the layout of the experience buffers they fill and the keys of
+the per-episode logs each reports.
 
 Pure functions of their arguments: numpy and the constants of ``_native`` only, never the shared library.
 ``vec_env`` imports every public name back, so ``vec_env.hier_tensors_from_state_dicts`` etc. stay valid.
@@ -484,3 +485,46 @@ def skill_num_frames(mask, skill_len):
     if not isinstance(m, np.ndarray):                           # torch
         return int(T // L * N + m.int().cumprod(dim=1).sum().item())
     return int(T // L * N + np.cumprod(m, axis=1).sum())
+
+
+# The keys of the `logs` each collector's collect_experiences returns (main/src/torch_ac/algos/base.py:237-242; the
+# four trees' _hier_policy_opt.py where they build `logs`), by the collector's name here.  ``ZoneVecEnv.episode_logs``
+# adds ``env_per_episode`` to each.
+_EPISODE_LOG_BASE = ("return_per_episode", "reshaped_return_per_episode", "num_frames_per_episode", "num_frames")
+EPISODE_LOG_KEYS = {
+    "collect": _EPISODE_LOG_BASE,
+    "collect_hier": _EPISODE_LOG_BASE,
+    "collect_options": _EPISODE_LOG_BASE,
+    "collect_skills": _EPISODE_LOG_BASE + ("diversity_per_episode", "prediction_per_episode"),
+    "collect_xy": _EPISODE_LOG_BASE + ("prediction_per_episode",),
+}
+
+
+def episode_log_columns(collector):
+    """The ``_native.EPLOG_*`` columns of ``EPISODE_LOG_KEYS[collector]``, as the bit set zenv_episode_log reports."""
+    return sum(1 << nat.EPLOG_KEYS.index(k) for k in EPISODE_LOG_KEYS[collector] if k != "num_frames")
+
+
+def episode_log_keys(columns):
+    """The per-episode keys of a zenv_episode_log column bit set, in column order."""
+    return tuple(k for c, k in enumerate(nat.EPLOG_KEYS[:nat.EPLOG_ENV]) if columns >> c & 1)
+
+
+def synthesize_stats(stats):
+    """utils.synthesize (main/src/utils/other.py) from zenv_episode_log_stats' (count, sum, sum of squares about the
+    mean, min, max): mean / std / min / max, std the population's as numpy.std."""
+    count, total, ssq, lo, hi = (float(v) for v in stats)
+    return {"mean": total / count, "std": (ssq / count) ** 0.5, "min": lo, "max": hi}
+
+
+def episode_log_history(stats, num_frames, keys=("return_per_episode", "num_frames_per_episode")):
+    """The flat entries a training loop keeps of one collection's logs, named as train_ppo.py / train_skill_planner.py
+    name their columns: ``return_mean`` / ``_std`` / ``_min`` / ``_max`` and the same for ``num_frames_per_episode``
+    (``num_frames_*``) and any further key (``diversity_*``) out of ``episode_log_stats()``, and ``num_frames``, the
+    frames of the call."""
+    out = {}
+    for key in keys:
+        name = {"num_frames_per_episode": "num_frames"}.get(key, key[:-len("_per_episode")])
+        out.update({f"{name}_{k}": v for k, v in stats[key].items()})
+    out["num_frames"] = int(num_frames)
+    return out

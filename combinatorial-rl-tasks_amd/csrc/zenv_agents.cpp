@@ -667,6 +667,7 @@ static int ensure_exp(zenv_t *h, int T)
     h->exp_skill = false;       // zenv_collect_skill, the same
     h->exp_option = false;      // zenv_collect_option, the same
     h->diayn_kept = -1;         // zenv_diayn_samples' list was of the records this call overwrites
+    h->eplog.source = 0;        // zenv_episode_log: every collector arms it once its records are complete
     if (!h->exp_mem || h->exp.T != T) {
         HIP_TRY(hipStreamSynchronize(h->stream));
         std::vector<float> keep_mask;
@@ -709,6 +710,8 @@ extern "C" int zenv_collect(zenv_t *h, int T, uint64_t policy_seed, uint64_t env
     if (int rc = use_device(h)) return rc;
     h->act_tag.valid = false;
     if (int rc = ensure_exp(h, T)) return rc;
+    if (h->goal_enabled)
+        if (int rc = eplog_flat_reward(h, T)) return rc;
     const FrameObs frames(h);
     if (int rc = frames.begin()) return rc;
     for (int t = 0; t < T; ++t) {
@@ -721,7 +724,12 @@ extern "C" int zenv_collect(zenv_t *h, int T, uint64_t policy_seed, uint64_t env
         if (int rc = run_policy(h, pol, &rec)) return rc;
         frames.write_next(t, T);
         HIP_TRY(launch_step(h->p, h->p.actions, 1, no_policy(), h->stream));     // ParallelEnv.step: auto-reset
-        if (h->goal_enabled) HIP_TRY(launch_goal_step(h->p, h->stream));
+        if (h->goal_enabled) {
+            HIP_TRY(launch_goal_step(h->p, h->stream));
+            // the env reward beside the shaped one the record keeps: zenv_episode_log's return (base.py:169)
+            HIP_TRY(hipMemcpyAsync(h->eplog.flat_reward + (size_t)t * h->n_env, h->p.reward, (size_t)h->n_env * 4,
+                                   hipMemcpyDeviceToDevice, h->stream));
+        }
         h->step_count += 1;
     }
     HIP_TRY(launch_exp_reward(h->exp, h->n_env, T - 1, h->p.reward, h->goal_enabled ? h->p.shaped : nullptr,
@@ -730,6 +738,7 @@ extern "C" int zenv_collect(zenv_t *h, int T, uint64_t policy_seed, uint64_t env
     HIP_TRY(launch_mlp_forward(h->mlp, h->n_env, h->p.Z, h->p.F, h->p.obs, h->p.zone_obs, h->mlp_pooled, h->mlp_mu,
                                h->mlp_std, h->mlp_value, h->mlp_value_sigma, no_mlp_action(), h->stream));
     HIP_TRY(launch_exp_gae(h->exp, h->n_env, h->mlp_value, discount, gae_lambda, h->stream));
+    h->eplog.source = 1;
     return ZENV_OK;
 }
 
@@ -875,6 +884,7 @@ extern "C" int zenv_collect_hier(zenv_t *h, int T, uint64_t policy_seed, uint64_
     HIP_TRY(launch_hier_carry(c, h->exp.obs, h->exp.zone_obs, h->n_env, (int)ZF, h->stream));
     h->hi_m = M;
     h->exp_hier = true;
+    h->eplog.source = 2;
     if (n_hi) *n_hi = M;
     return ZENV_OK;
 }
@@ -994,6 +1004,7 @@ extern "C" int zenv_collect_skill(zenv_t *h, int T, uint64_t policy_seed, uint64
     HIP_TRY(launch_skill_hi_gae(o, T, L, h->n_env, h->sk.env_reward, h->exp.mask, h->exp.cur_mask, h->skill_value,
                                 gae_lambda, h->sk.count, h->stream));
     h->exp_skill = true;
+    h->eplog.source = 3;
     return ZENV_OK;
 }
 
@@ -1092,6 +1103,7 @@ extern "C" int zenv_collect_xy(zenv_t *h, int T, uint64_t policy_seed, uint64_t 
     HIP_TRY(launch_skill_hi_gae(o, T, L, h->n_env, h->xc.env_reward, h->exp.mask, h->exp.cur_mask, h->xy_value,
                                 gae_lambda, h->xc.count, h->stream));
     h->exp_xy = true;
+    h->eplog.source = 5;
     return ZENV_OK;
 }
 
@@ -1189,6 +1201,7 @@ extern "C" int zenv_collect_option(zenv_t *h, int T, uint64_t policy_seed, uint6
     HIP_TRY(launch_hier_carry(c, h->exp.obs, h->exp.zone_obs, h->n_env, (int)ZF, h->stream));
     h->hi_m = M;
     h->exp_option = true;
+    h->eplog.source = 4;
     if (n_hi) *n_hi = M;
     return ZENV_OK;
 }

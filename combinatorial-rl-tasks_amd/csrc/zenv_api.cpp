@@ -546,6 +546,7 @@ extern "C" int zenv_destroy(zenv_t *h)
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->comm) (void)zenv_comm_destroy(h);
     ppo_free(h);
+    eplog_free(h);
     if (h->host_io_actions) h->p.actions = h->dev_actions;       // the slot below is the device buffer again
     for (Alloc &a : h->allocs)
         if (*a.slot && a.slab_off < 0) (void)hipFree(*a.slot);

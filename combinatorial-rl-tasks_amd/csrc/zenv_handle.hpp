@@ -1,5 +1,6 @@
 // zenv_handle.hpp -- the handle behind zenv_t and the helpers every translation unit of the C ABI uses (zenv_api.cpp:
-// the environment; zenv_agents.cpp: the networks, the per-step policies, the collectors; zenv_train.cpp: the learners).
+// the environment; zenv_agents.cpp: the networks, the per-step policies, the collectors; zenv_train.cpp: the learners;
+// zenv_episode_log.cpp: the collectors' per-episode logs).
 // Internal: not installed.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -17,6 +18,7 @@
 #include "skill_f32.hpp"
 #include "xy_f32.hpp"
 #include "mlp_policy.hpp"
+#include "episode_log.hpp"
 
 using namespace zenvk;
 
@@ -221,6 +223,25 @@ struct zenv {
     // ZENV_F_EP_RETURN / ZENV_F_EP_LEN as plain arrays: the values live in the HotA records, unpacked by refresh_field()
     double *pub_ep_return = nullptr;
     int32_t *pub_steps = nullptr;
+    // zenv_episode_log (zenv_episode_log.cpp): the reference's `logs` of the last collection.  source: which collector
+    // armed it (0 none / taken; 1 zenv_collect, 2 _hier, 3 _skill, 4 _option, 5 _xy), every collector sets it on
+    // success and ensure_exp clears it.  state_mem: the four running sums [N] and the two tails (ping-pong, `cur` the
+    // live one); res_mem: the result's columns, capacity `cap` entries; ws_mem: the (frame, wave) counts, the scan's
+    // levels and totals (D, the active frames); the reduction's partial results lie behind the result.  flat_reward: the env reward
+    // [T][N] of zenv_collect on a goal-conditioned handle, whose ZENV_F_EXP_REWARD holds the shaped one
+    struct {
+        int source = 0;
+        void *state_mem = nullptr, *res_mem = nullptr, *ws_mem = nullptr;
+        float *carry[4] = {};
+        EpLogList tail[2] = {}, res{};
+        int cur = 0;
+        int64_t cap = 0, ws_counts = 0;
+        int32_t *counts = nullptr, *active = nullptr, *levels = nullptr, *totals = nullptr;
+        double *stat_ws = nullptr, *stat_fin = nullptr;
+        int64_t kept = -1, done = 0, num_frames = 0, columns = 0;
+        float *flat_reward = nullptr;
+        int flat_T = 0;
+    } eplog;
     // zenv_render: the device copies of a host caller's marks and of the frames on their way to host memory
     void *render_marks = nullptr, *render_stage = nullptr;
     size_t render_marks_cap = 0, render_stage_cap = 0;
@@ -237,6 +258,11 @@ ZENV_INTERNAL int run_policy(zenv *h, const StepPolicy &pol, const MlpRecord *re
 ZENV_INTERNAL int ring_guard(const zenv *h, int steps, int auto_reset_every_step);
 // ZENV_E_RANGE once the float16 network kernels have flagged an operand out of range
 ZENV_INTERNAL int mlp_range_check(zenv *h);
+
+// ---- zenv_episode_log.cpp
+ZENV_INTERNAL void eplog_free(zenv *h);
+// room for the env reward of T frames beside the shaped one (zenv_collect on a goal-conditioned handle)
+ZENV_INTERNAL int eplog_flat_reward(zenv *h, int T);
 
 // ---- zenv_train.cpp
 ZENV_INTERNAL void ppo_free(zenv *h);

@@ -102,11 +102,37 @@ class TorchZoneEnv:
         raw = self._alias_layout(self.env._experience_rows(frames_per_proc))
         return {name: t.transpose(0, 1) for name, t in raw.items()}     # [N, T, ...] views of time-major memory
 
-    # ------------------------------------------------------------------ the flat actor-critic's PPO update
     def _alias_ptr(self, ptr, shape, dtype=np.float32):
         t = self._torch.as_tensor(_DeviceView(ptr, shape, dtype), device=self.device)
         assert t.data_ptr() == ptr, "torch copied instead of aliasing"
         return t
+
+    # ------------------------------------------------------------------ the collectors' per-episode logs (K19)
+    def episode_logs(self):
+        """``ZoneVecEnv.episode_logs`` for the collector that ran last, the per-episode values as CUDA tensors
+        (float32; ``env_per_episode`` int32) ALIASING the handle's result buffers: they stay valid until the next
+        ``episode_logs`` call, which overwrites (and may reallocate) them.  ``num_frames`` is an int.  Once per
+        collection; waits for the device once, to learn how many episodes ended."""
+        from .vec_env import episode_log_keys
+        info = self.env.episode_log_on_device()
+        out = {}
+        with self._torch.cuda.device(self.device):
+            for key in episode_log_keys(info.columns) + (nat.EPLOG_KEYS[nat.EPLOG_ENV],):
+                column = nat.EPLOG_KEYS.index(key)
+                ptr, count = self.env.episode_log_ptr(column)
+                out[key] = self._alias_ptr(ptr, (count,), np.int32 if column == nat.EPLOG_ENV else np.float32)
+        out["num_frames"] = int(info.num_frames)
+        return out
+
+    def episode_log_stats(self):
+        """``ZoneVecEnv.episode_log_stats``: {key: {"mean", "std", "min", "max"}} of the last ``episode_logs``."""
+        return self.env.episode_log_stats()
+
+    def episode_log_reset(self):
+        """``ZoneVecEnv.episode_log_reset``: the logs of a fresh algo object."""
+        self.env.episode_log_reset()
+
+    # ------------------------------------------------------------------ the flat actor-critic's PPO update
 
     def ppo_init(self, state_dict, **hyper):
         """``ZoneVecEnv.ppo_init`` with the four arenas -- parameters, gradients, exp_avg, exp_avg_sq -- as flat float32

@@ -23,7 +23,8 @@ from .agents import (_HIER_ENC, _HIER_CRITIC, HIER_HI_KEYS, HIER_LO_KEYS, SKILL_
                      hier_experience_layout, skill_experience_layout, option_experience_layout, skill_num_frames,
                      check_collect_xy_args, xy_experience_layout, ppo_state_dict_keys, ppo_batch_indexes,
                      hppo_state_dict_keys, hppo_batch_indexes, xyppo_state_dict_keys, skppo_state_dict_keys,
-                     opppo_state_dict_keys, diayn_state_dict_keys, diayn_kept_samples)
+                     opppo_state_dict_keys, diayn_state_dict_keys, diayn_kept_samples,
+                     EPISODE_LOG_KEYS, episode_log_columns, episode_log_keys, synthesize_stats)
 
 _FIELD_DTYPES = {
     nat.F_OBS: np.float32, nat.F_ZONE_OBS: np.float32, nat.F_REWARD: np.float32,
@@ -835,6 +836,56 @@ class ZoneVecEnv:
     def _experience_rows(self, frames_per_proc):
         """The same buffers as name -> (field id, shape in memory, dtype), the form of the agents' layouts."""
         return _lo_rows(self.num_envs, self.num_zones, self.zone_feat, int(frames_per_proc))
+
+    # ------------------------------------------------------------------ the collectors' per-episode logs (K19)
+    def episode_log_on_device(self):
+        """zenv_episode_log: the reference's ``logs`` of the last collection (any of the five collectors), left in
+        device buffers.  Once per collection; waits for the device once.  Returns the ``EpisodeLogInfo`` (kept, done,
+        num_frames, columns)."""
+        info = nat.EpisodeLogInfo()
+        check(lib().zenv_episode_log(self._h, C.byref(info)))
+        self._eplog_info = info
+        return info
+
+    def episode_log_ptr(self, column):
+        """(device pointer, count) of a ``_native.EPLOG_*`` column of the last ``episode_log_on_device``."""
+        ptr, count = C.c_void_p(), C.c_int64()
+        check(lib().zenv_episode_log_tensor(self._h, int(column), C.byref(ptr), C.byref(count)))
+        return ptr.value, count.value
+
+    def episode_logs(self):
+        """The second value of collect_experiences (main/src/torch_ac/algos/base.py:233-247 and the four trees'
+        _hier_policy_opt.py), for the collector that ran last: ``return_per_episode``, ``reshaped_return_per_episode``
+        and ``num_frames_per_episode`` (numpy float32 [max(done, N)]), ``num_frames`` (int), ``diversity_per_episode`` /
+        ``prediction_per_episode`` where the reference's dict has them (``agents.EPISODE_LOG_KEYS``), and
+        ``env_per_episode`` (int32, -1 for the initial zero entries).  The running sums and the last N entries are
+        carried from call to call as the algo object carries them.  Once per collection."""
+        info = self.episode_log_on_device()
+        out = {}
+        for key in episode_log_keys(info.columns) + (nat.EPLOG_KEYS[nat.EPLOG_ENV],):
+            column = nat.EPLOG_KEYS.index(key)
+            a = np.empty(info.kept, np.int32 if column == nat.EPLOG_ENV else np.float32)
+            check(lib().zenv_episode_log_read(self._h, column, a.ctypes.data))
+            out[key] = a
+        out["num_frames"] = int(info.num_frames)
+        return out
+
+    def episode_log_stats(self):
+        """{key: {"mean", "std", "min", "max"}} of every per-episode key of the last ``episode_logs`` /
+        ``episode_log_on_device``: utils.synthesize (main/src/utils/other.py:15-21) reduced on the device in float64,
+        std the population's as ``numpy.std``."""
+        info = getattr(self, "_eplog_info", None)
+        columns = info.columns if info is not None else 1          # no log yet: the library answers E_STATE
+        out = {}
+        for key in episode_log_keys(columns):
+            stats = (C.c_double * 5)()
+            check(lib().zenv_episode_log_stats(self._h, nat.EPLOG_KEYS.index(key), stats))
+            out[key] = synthesize_stats(stats)
+        return out
+
+    def episode_log_reset(self):
+        """Zero the running sums and the tail: the logs of a fresh algo object."""
+        check(lib().zenv_episode_log_reset(self._h))
 
     # ------------------------------------------------------------------ the flat actor-critic's PPO update
     def ppo_init(self, state_dict_or_tensors, lr=0.001, adam_eps=1e-8, clip_eps=0.2, entropy_coef=0.01,

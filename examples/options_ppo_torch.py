@@ -28,6 +28,7 @@ from torch.distributions import Categorical, Normal
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import combinatorial_rl_tasks_amd as Z  # noqa: E402
+from combinatorial_rl_tasks_amd.agents import episode_log_history  # noqa: E402
 from combinatorial_rl_tasks_amd.torch_interop import TorchZoneEnv  # noqa: E402
 
 
@@ -208,6 +209,8 @@ class OptionsPPO:
         lo, hi, rate = self.collect()
         logs = {"num_frames_hi": int(hi["action"].shape[0]), "termination_rate": float(rate),
                 "reward_per_frame": float(lo["env_reward"].mean())}
+        num_frames = self.tenv.episode_logs()["num_frames"]      # logs of collect_experiences, synthesized
+        logs.update(episode_log_history(self.tenv.episode_log_stats(), num_frames))
         logs.update(self.update(lo, hi))
         return logs
 

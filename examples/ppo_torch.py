@@ -23,6 +23,7 @@ import torch.nn as nn
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import combinatorial_rl_tasks_amd as Z  # noqa: E402
+from combinatorial_rl_tasks_amd.agents import episode_log_history  # noqa: E402
 from combinatorial_rl_tasks_amd.torch_interop import TorchZoneEnv  # noqa: E402
 
 
@@ -131,6 +132,9 @@ def train(env_id="PointTSP-v0", procs=4096, frames_per_proc=64, updates=10, epoc
         frames = procs * frames_per_proc
         st.update(update=u, frames=frames * (u + 1), reward_per_frame=float(exps["reward"].mean()),
                   collect_fps=frames / (t1 - t0), update_fps=frames * epochs / (t2 - t1))
+        # logs of collect_experiences (base.py:233-247), synthesized as train_ppo.py:175-177 does
+        num_frames = tenv.episode_logs()["num_frames"]
+        st.update(episode_log_history(tenv.episode_log_stats(), num_frames))
         history.append(st)
         log({k: (round(v, 4) if isinstance(v, float) else v) for k, v in st.items()})
     if device_update:

@@ -29,6 +29,7 @@ from torch.distributions import Categorical
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import combinatorial_rl_tasks_amd as Z  # noqa: E402
+from combinatorial_rl_tasks_amd.agents import episode_log_history  # noqa: E402
 from combinatorial_rl_tasks_amd.torch_interop import TorchZoneEnv  # noqa: E402
 
 
@@ -268,6 +269,10 @@ class SkillPlannerPPO:
         lo, hi, inverse, num_frames = self.collect()
         logs = {"num_frames": num_frames, "reward_per_frame": float(lo["env_reward"].mean()),
                 "diversity_per_frame": float(lo["diversity"].mean())}
+        # logs of collect_experiences, synthesized as train_skill_planner.py:233-250 does
+        assert self.tenv.episode_logs()["num_frames"] == num_frames
+        logs.update(episode_log_history(self.tenv.episode_log_stats(), num_frames,
+                                        ("return_per_episode", "num_frames_per_episode", "diversity_per_episode")))
         logs.update(self.update(lo, hi, inverse))
         return logs
 

@@ -25,6 +25,7 @@ from torch.distributions import Normal
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import combinatorial_rl_tasks_amd as Z  # noqa: E402
+from combinatorial_rl_tasks_amd.agents import episode_log_history  # noqa: E402
 from combinatorial_rl_tasks_amd.torch_interop import TorchZoneEnv  # noqa: E402
 
 
@@ -186,6 +187,8 @@ class XyGoalsPPO:
         lo, hi, num_frames = self.collect()
         logs = {"num_frames": num_frames, "reward_per_frame": float(lo["env_reward"].mean()),
                 "lo_reward_per_frame": float(lo["reward"].mean())}
+        assert self.tenv.episode_logs()["num_frames"] == num_frames     # logs of collect_experiences, synthesized
+        logs.update(episode_log_history(self.tenv.episode_log_stats(), num_frames))
         if self.device_update:
             logs.update(self.tenv.xyppo_update(self.epochs, self.batch_size, self.hi_epochs, self.hi_batch_size, self.rng))
             self.tenv.xyppo_publish()

@@ -25,6 +25,7 @@ from torch.distributions import Categorical
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import combinatorial_rl_tasks_amd as Z  # noqa: E402
+from combinatorial_rl_tasks_amd.agents import episode_log_history  # noqa: E402
 from combinatorial_rl_tasks_amd.torch_interop import TorchZoneEnv  # noqa: E402
 
 
@@ -181,6 +182,8 @@ class HierPPO:
         self.it += 1
         logs = {"frames": lo["obs"].shape[0] * lo["obs"].shape[1], "hi_frames": int(hi["action"].shape[0]),
                 "reward_per_frame": float(lo["env_reward"].mean())}
+        num_frames = self.tenv.episode_logs()["num_frames"]      # logs of collect_experiences, synthesized
+        logs.update(episode_log_history(self.tenv.episode_log_stats(), num_frames))
         if self.device_update:
             logs.update(self.tenv.hppo_update(self.epochs, self.batch_size, self.hi_epochs, self.hi_batch_size, self.rng))
             self.tenv.hppo_publish()

@@ -1304,6 +1304,59 @@ int zenv_render_check(const zenv_config *cfg, const zenv_render_config *rc, int 
 int zenv_render(zenv_t *h, const zenv_render_config *rc, int first, int count, const float *marks,
                 int marks_on_device, uint8_t *dst, int dst_on_device);
 
+/* ---- the per-episode training logs of collect_experiences (K19) ----
+ * The second value every collect_experiences of the reference returns: `logs` (main/src/torch_ac/algos/base.py:233-247,
+ * main/src/torch_ac/algos/_hier_policy_opt.py:216-232 and the other trees' _hier_policy_opt.py at the same place),
+ * computed on the device from the records the last collector left, in float32 and in the reference's order of
+ * operations.  Per handle, zero at first and after zenv_episode_log_reset: the running sums log_episode_return,
+ * _reshaped_return, _num_frames and _diversity [N] (base.py:101-103), and the tail, the last N entries of the lists
+ * (N entries of 0, `[0] * num_procs`, base.py:106-108).  For frame t of the collection, done_t = 1 - mask[t + 1]
+ * (1 - the mask carried into the next call for the last frame): the sums take += value (base.py:169-171), an env
+ * whose episode is done appends an entry -- the frames in order, the envs ascending inside a frame, as `for i, done_ in
+ * enumerate(done)` does (base.py:173-178) -- and the sums are multiplied by 1 - done_t (base.py:180-182).
+ *   collector                  return +=              reshaped +=         an entry when          num_frames
+ *   zenv_collect               env reward             ZENV_F_EXP_REWARD   done_t                 T N
+ *   zenv_collect_hier/_option  ZENV_F_LO_ENV_REWARD   the same            done_t                 T N
+ *   zenv_collect_skill / _xy   ZENV_F_LO_ENV_REWARD   the same            done_t and the env is  the active envs of
+ *                                                                         active in its window   every frame, summed
+ * An env is active from every frame t with t % skill_len == 0 until its first done_t of the window
+ * (_hier_policy_opt.py:29-31, 112-116); an idle env keeps counting frames into its sum, which the mask zeroes again.
+ * zenv_collect_skill also sums ZENV_F_LO_DIVERSITY, the diversity reward without diversity_coef (:109); the prediction
+ * column of the skills and xy-goals agents is never added to and stays 0.
+ * The result is the last max(D, N) entries of (tail + the D new entries) (base.py:235-240); the tail becomes the last N
+ * of the same list (:245-247).  Beside the reference's columns every entry carries the env that produced it (-1 for the
+ * initial zero entries).
+ *
+ * zenv_episode_log: once after a collection; it synchronises the stream once, to size the result.  ZENV_E_ARG on a
+ * null argument; ZENV_E_STATE when no collection has run or this collection's log was already taken (every collector
+ * re-arms it).  info.columns: the ZENV_EPLOG_* columns the collector's `logs` has, as bits (1 << column).
+ * zenv_episode_log_tensor: the device pointer of a column of the last result and its length (float32; int32 for
+ * ZENV_EPLOG_ENV), valid until the next zenv_episode_log.  zenv_episode_log_read copies a column to host memory.
+ * zenv_episode_log_stats: out = count, sum, the sum of squares about the mean (sum / count), min, max of a float
+ * column, reduced in float64 by a fixed tree.  All three: ZENV_E_STATE before the first zenv_episode_log, ZENV_E_ARG for an
+ * unknown column (the env column has no statistics) or a null argument.
+ * zenv_episode_log_reset zeroes the sums and the tail, as a fresh algo object. */
+enum {
+    ZENV_EPLOG_RETURN = 0,            /* return_per_episode */
+    ZENV_EPLOG_RESHAPED_RETURN = 1,   /* reshaped_return_per_episode */
+    ZENV_EPLOG_NUM_FRAMES = 2,        /* num_frames_per_episode */
+    ZENV_EPLOG_DIVERSITY = 3,         /* diversity_per_episode (zenv_collect_skill) */
+    ZENV_EPLOG_PREDICTION = 4,        /* prediction_per_episode (zenv_collect_skill, zenv_collect_xy) */
+    ZENV_EPLOG_ENV = 5,               /* the env of every entry, int32 */
+    ZENV_EPLOG_COUNT = 6
+};
+typedef struct zenv_episode_log_info {
+    int64_t kept;          /* entries of the result: max(done, N) */
+    int64_t done;          /* D: entries this collection appended (log_done_counter) */
+    int64_t num_frames;    /* logs["num_frames"] */
+    int64_t columns;       /* bit (1 << ZENV_EPLOG_*) for every column the collector's logs define */
+} zenv_episode_log_info;
+int zenv_episode_log(zenv_t *h, zenv_episode_log_info *out);
+int zenv_episode_log_tensor(zenv_t *h, int column, void **ptr, int64_t *count);
+int zenv_episode_log_read(zenv_t *h, int column, void *dst);
+int zenv_episode_log_stats(zenv_t *h, int column, double out[5]);
+int zenv_episode_log_reset(zenv_t *h);
+
 /* Measurement utility (bench.py `store_stream_ceiling`; not part of the env path): n_tiles waves each rewrite their
  * own contiguous tile_bytes (a multiple of 16, >= 1024) `steps` times with 1 KiB dwordx4 bursts under cache_policy
  * (0 plain, 2 non-temporal, 16 sc1 = write-through) -- the row stream of the step kernels with the env taken away.
