@@ -147,6 +147,9 @@ class PpoConfig(C.Structure):
 
 
 RENDER_CURRENT, RENDER_EXPERIENCE = 0, 1                      # zenv_render_config.source
+# layouts sampled on the device: ZENV_DEVICE_RESTARTS, ZENV_SAMPLE_STATUS_CAP, the codes of zenv_sample_status
+DEVICE_RESTARTS, SAMPLE_STATUS_CAP = 256, 1024
+SAMPLE_UNFINISHED, SAMPLE_SEED_RANGE = 1, 2
 
 
 class RenderConfig(C.Structure):
@@ -219,6 +222,17 @@ _PROTOTYPES = {
     "zenv_bank_set": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "zenv_bank_size": (C.c_int, [_H]),
     "zenv_bank_update": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "zenv_sample_layout_shared": (C.c_int, [C.POINTER(Config), C.c_int64, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.POINTER(C.c_int32)]),
+    "zenv_layout_thresholds": (C.c_int, [C.POINTER(Config), C.c_void_p, C.c_void_p]),
+    "zenv_bank_build_device": (C.c_int, [_H, C.c_int64, C.c_int]),
+    "zenv_bank_build_seeds_device": (C.c_int, [_H, C.c_void_p, C.c_int]),
+    "zenv_bank_update_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int]),
+    "zenv_ring_stream": (C.c_int, [_H, C.c_void_p, C.c_int32]),
+    "zenv_ring_refill": (C.c_int, [_H]),
+    "zenv_sample_status": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int32),
+                                     C.POINTER(C.c_int64)]),
+    "zenv_bank_read": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "zenv_schedule_ring": (C.c_int, [_H, C.c_void_p, C.c_int32]),
     "zenv_schedule_sequential": (C.c_int, [_H, C.c_void_p, C.c_int32]),
     "zenv_schedule_fixed_seeds": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int64]),

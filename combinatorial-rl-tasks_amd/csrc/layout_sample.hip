@@ -1,0 +1,134 @@
+// layout_sample.hip -- K20: Engine.reset()'s random half on gfx950 (see layout_sampler.hpp for the arithmetic, which
+// is the host's, and DESIGN.md 4 for the choice of mapping).
+//
+// One wave64 per env seed.  The generator's 624 words live in LDS (2 496 B per wave, so LDS never limits occupancy:
+// the 32-waves-per-CU cap does); the twist runs 64 words at a time, every draw is a broadcast ds_read of one word that
+// all lanes temper alike; placed object j (0 = the robot, 1 .. Z = the zones) sits in lane j's registers, so the
+// keepout test of a candidate against everything placed is one compare per lane and one ballot.  Control flow is
+// wave-uniform throughout: rejection loops of different seeds never share a wave, so they do not diverge.
+#include <hip/hip_runtime.h>
+
+#include "layout_sample.hpp"
+
+namespace zenvk {
+namespace {
+
+constexpr int kWave = 64;
+
+struct WaveLanes {
+    static constexpr int kLanes = kWave;
+    uint32_t *mt;      // LDS, 624 words
+    int ln;
+    double x, y;       // the object this lane holds
+    int32_t aux;       // lane z + 1: zone z's aux value
+    __device__ __forceinline__ int lane() const { return ln; }
+    // a block is one wave: the barrier costs nothing, the fence orders the wave's LDS stores before its LDS loads
+    __device__ __forceinline__ void sync() { __syncthreads(); }
+    __device__ __forceinline__ bool any(bool b) const { return __builtin_amdgcn_ballot_w64(b) != 0ull; }
+    __device__ __forceinline__ uint32_t word(int i) const { return mt[i]; }
+    __device__ __forceinline__ void set_word(int i, uint32_t v) { mt[i] = v; }
+    __device__ __forceinline__ double px(int) const { return x; }      // asked for by lane j only (kLanes > Z)
+    __device__ __forceinline__ double py(int) const { return y; }
+    __device__ __forceinline__ void place(int j, double xx, double yy)
+    {
+        if (ln == j) { x = xx; y = yy; }
+    }
+    __device__ __forceinline__ void set_aux(int z, int32_t v)
+    {
+        if (ln == z + 1) aux = v;
+    }
+};
+static_assert(ZENV_MAX_ZONES + 1 <= kWave, "one lane per placed object");
+
+template <int TASK>
+__global__ __launch_bounds__(kWave) void k_layout_sample(LayoutSampleArgs a)
+{
+    __shared__ uint32_t mt[624];
+    const int lane = threadIdx.x, Z = a.c.Z;
+    const uint32_t n = a.count_dev ? *a.count_dev : (uint32_t)a.count;
+    uint32_t written = 0;
+    for (uint32_t e = blockIdx.x; e < n; e += gridDim.x) {
+        const int slot = a.slots ? a.slots[e] : (int)e;
+        const int64_t seed = a.seeds[e];
+        if (slot < 0 || slot >= a.bank_size) continue;      // the host checked its lists; a device-made list is in range
+        WaveLanes st;
+        st.mt = mt;
+        st.ln = lane;
+        st.x = st.y = 0.0;
+        st.aux = 0;
+        double rot = 0.0;
+        int32_t restarts = 0;
+        int code = SAMPLE_SEED_RANGE;                        // Engine.seed: 'Seed must be between 0 and 2**32 - 1'
+        if (seed >= 0 && seed + 1 <= 0xFFFFFFFFll)
+            code = sample_layout_shared(a.c, TASK == ZENV_TASK_COLOUR_MATCH, (uint32_t)seed, kSamplerDeviceAttempts, st,
+                                        rot, restarts);
+        if (code == SAMPLE_OK) {
+            if (lane == 0) {
+                double s, c;
+                det_sincos_inl(rot / 2, s, c);               // world.py rot2quat: [cos(rot/2), 0, 0, sin(rot/2)]
+                double2 *br = reinterpret_cast<double2 *>(a.bank_robot + 4 * (size_t)slot);
+                br[0] = make_double2(st.x, st.y);
+                br[1] = make_double2(c, s);
+                a.bank_seed[slot] = seed;
+            } else if (lane <= Z) {
+                const size_t bi = (size_t)slot * Z + (lane - 1);
+                reinterpret_cast<double2 *>(a.bank_zone)[bi] = make_double2(st.x, st.y);
+                a.bank_aux[bi] = st.aux;
+            }
+            written++;
+        } else if (lane == 0) {
+            // the slot stays as it was; the host hears of it (zenv_sample_status)
+            const uint32_t i = atomicAdd(&a.status->n_failed, 1u);
+            if (i < (uint32_t)ZENV_SAMPLE_STATUS_CAP) {
+                a.status->slots[i] = slot;
+                a.status->codes[i] = code;
+                a.status->seeds[i] = seed;
+            }
+        }
+        __syncthreads();                                     // the next entry's seeding stores behind this one's loads
+    }
+    if (lane == 0 && written) atomicAdd(&a.status->n_sampled, (unsigned long long)written);
+}
+
+__global__ __launch_bounds__(256) void k_ring_stale(DevParams p, const int64_t *__restrict__ seed0,
+                                                    int32_t *__restrict__ list_slots, int64_t *__restrict__ list_seeds,
+                                                    uint32_t *__restrict__ count)
+{
+    const int depth = p.sched_stride;
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long long)p.N * depth) return;
+    const int env = (int)(t / depth), j = (int)(t % depth);
+    const int k = p.sched[env].episode_idx;                  // episodes started so far = the next episode's index
+    const int ahead = (j - k % depth + depth) % depth;       // e_j = k + ahead: the smallest e >= k with e mod depth == j
+    const int slot = p.slot_first[env] + j;
+    if (slot < 0 || slot >= p.bank_size) return;
+    const int64_t want = seed0[env] + (int64_t)k + ahead;
+    if (p.bank_seed[slot] != want) {
+        const uint32_t i = atomicAdd(count, 1u);             // at most N * depth entries: the lists' size
+        list_slots[i] = slot;
+        list_seeds[i] = want;
+    }
+}
+
+}  // namespace
+
+hipError_t launch_layout_sample(const LayoutSampleArgs &a, int grid, hipStream_t s)
+{
+    if (grid < 1) return hipSuccess;
+    if (a.c.task == ZENV_TASK_COLOUR_MATCH)
+        hipLaunchKernelGGL(k_layout_sample<ZENV_TASK_COLOUR_MATCH>, dim3(grid), dim3(kWave), 0, s, a);
+    else
+        hipLaunchKernelGGL(k_layout_sample<ZENV_TASK_TSP>, dim3(grid), dim3(kWave), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_ring_stale(const DevParams &p, const int64_t *seed0, int32_t *list_slots, int64_t *list_seeds,
+                             uint32_t *count, hipStream_t s)
+{
+    const long long n = (long long)p.N * p.sched_stride;
+    hipLaunchKernelGGL(k_ring_stale, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, seed0, list_slots, list_seeds,
+                       count);
+    return hipGetLastError();
+}
+
+}  // namespace zenvk

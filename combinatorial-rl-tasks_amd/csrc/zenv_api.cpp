@@ -41,8 +41,6 @@ int use_device(const zenv *h)
     return ZENV_OK;
 }
 
-namespace {
-
 int validate_config(const zenv_config &c)
 {
     if (c.task < ZENV_TASK_TSP || c.task > ZENV_TASK_COLOUR_MATCH) return fail(ZENV_E_ARG, "unknown task %d", c.task);
@@ -91,6 +89,8 @@ int validate_config(const zenv_config &c)
         return fail(ZENV_E_ARG, "visited0 leaves no zone to visit");
     return ZENV_OK;
 }
+
+namespace {
 
 void derive_constants(const zenv_config &c, DevParams &p)
 {
@@ -547,6 +547,7 @@ extern "C" int zenv_destroy(zenv_t *h)
     if (h->comm) (void)zenv_comm_destroy(h);
     ppo_free(h);
     eplog_free(h);
+    layout_free(h);
     if (h->host_io_actions) h->p.actions = h->dev_actions;       // the slot below is the device buffer again
     for (Alloc &a : h->allocs)
         if (*a.slot && a.slab_off < 0) (void)hipFree(*a.slot);
@@ -610,7 +611,6 @@ static int upload_bank(zenv *h, const std::vector<double> &robot4, const std::ve
     // allocate and fill the new bank first; the handle switches to it only when all of it is on the device (a failure
     // half way leaves the old bank -- and bank_ready -- exactly as they were)
     const size_t S = seeds.size();
-    const int32_t S_old = h->p.bank_size;
     const size_t bytes[5] = { robot4.size() * sizeof(double), zone.size() * sizeof(double), aux.size() * sizeof(int32_t),
                               S * sizeof(int64_t), S * 3 * sizeof(float4) };
     const void *src[5] = { robot4.data(), zone.data(), aux.data(), seeds.data(), nullptr };
@@ -625,6 +625,12 @@ static int upload_bank(zenv *h, const std::vector<double> &robot4, const std::ve
             if (m) (void)hipFree(m);
         return fail(ZENV_E_HIP, "uploading the layout bank: %s", hipGetErrorString(err));
     }
+    return adopt_bank(h, fresh, S);
+}
+
+int adopt_bank(zenv *h, void *const fresh[5], size_t S)
+{
+    const int32_t S_old = h->p.bank_size;
     for (int i = 0; i < 5; ++i) {
         if (h->bank_mem[i]) (void)hipFree(h->bank_mem[i]);
         h->bank_mem[i] = fresh[i];
@@ -835,6 +841,7 @@ extern "C" int zenv_schedule_sequential(zenv_t *h, const int32_t *first, int32_t
     HIP_TRY(hipStreamSynchronize(h->stream));
     HIP_TRY(hipMemcpy(h->p.slot_first, f.data(), f.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     h->p.sched_mode = SCHED_SEQUENTIAL;
+    h->ls.ring_streamed = false;
     h->p.sched_stride = stride % S;
     HIP_TRY(launch_sched_sync(h->p, 1, h->stream));   // episode 0, next_slot = first (on the handle's stream)
     h->sched_ready = true;
@@ -855,6 +862,7 @@ extern "C" int zenv_schedule_ring(zenv_t *h, const int32_t *first, int32_t depth
     HIP_TRY(hipStreamSynchronize(h->stream));
     HIP_TRY(hipMemcpy(h->p.slot_first, first, (size_t)h->n_env * sizeof(int32_t), hipMemcpyHostToDevice));
     h->p.sched_mode = SCHED_RING;
+    h->ls.ring_streamed = false;
     h->p.sched_stride = depth;
     HIP_TRY(launch_sched_sync(h->p, 1, h->stream));
     h->sched_ready = true;
@@ -881,6 +889,7 @@ extern "C" int zenv_schedule_fixed_seeds(zenv_t *h, const uint64_t *rng_seeds, i
     HIP_TRY(hipMemcpy(h->p.pcg, st.data(), st.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
     HIP_TRY(hipMemsetAsync(h->p.pcg_buf, 0, 2 * (size_t)h->n_env * sizeof(uint32_t), h->stream));
     h->p.sched_mode = SCHED_FIXED_SEEDS;
+    h->ls.ring_streamed = false;
     h->p.seed_min = min_seed;
     h->p.seed_max = max_seed;
     HIP_TRY(launch_sched_sync(h->p, 1, h->stream));

@@ -19,6 +19,7 @@
 #include "xy_f32.hpp"
 #include "mlp_policy.hpp"
 #include "episode_log.hpp"
+#include "layout_sample.hpp"
 
 using namespace zenvk;
 
@@ -208,6 +209,25 @@ struct zenv {
     size_t refill_cap = 0;
     hipEvent_t refill_done = nullptr;
     bool refill_busy = false;
+    // device layout sampling (zenv_layout.cpp): the status block and the stale-list count in one allocation; the slot /
+    // seed lists the kernels walk (capacity list_cap entries); the page-locked image zenv_bank_update_device stages its
+    // 12 bytes per layout in; a streamed ring's first seeds [N] and whether zenv_ring_stream made the current schedule
+    struct {
+        void *mem = nullptr;
+        SampleStatus *status = nullptr;
+        uint32_t *count = nullptr;
+        double *zones_locations = nullptr;   // device copy of cfg.zones_locations (the same allocation)
+        void *list_mem = nullptr;
+        int32_t *list_slots = nullptr;
+        int64_t *list_seeds = nullptr;
+        size_t list_cap = 0;
+        void *stage_host = nullptr;
+        size_t stage_cap = 0;
+        hipEvent_t stage_done = nullptr;
+        bool stage_busy = false;
+        int64_t *ring_seed0 = nullptr;
+        bool ring_streamed = false;
+    } ls;
     // the sharded job's communicator (zenv_comm_init): RCCL over xGMI
     ncclComm_t comm = nullptr;
     int comm_rank = 0, comm_world = 0;
@@ -258,6 +278,15 @@ ZENV_INTERNAL int run_policy(zenv *h, const StepPolicy &pol, const MlpRecord *re
 ZENV_INTERNAL int ring_guard(const zenv *h, int steps, int auto_reset_every_step);
 // ZENV_E_RANGE once the float16 network kernels have flagged an operand out of range
 ZENV_INTERNAL int mlp_range_check(zenv *h);
+
+// ---- zenv_api.cpp, as far as zenv_layout.cpp calls it
+ZENV_INTERNAL int validate_config(const zenv_config &c);
+// Make the five freshly filled device buffers (robot, zone, aux, seed, room for the derived rows) of S slots the
+// handle's bank: frees the old one, derives the first rows, treats the schedule as every bank upload does.
+ZENV_INTERNAL int adopt_bank(zenv *h, void *const fresh[5], size_t S);
+
+// ---- zenv_layout.cpp
+ZENV_INTERNAL void layout_free(zenv *h);
 
 // ---- zenv_episode_log.cpp
 ZENV_INTERNAL void eplog_free(zenv *h);

@@ -32,8 +32,14 @@ def _unwrap(env):
 class ParallelEnv:
     """A batch of zone envs stepped by one MI355X kernel launch."""
 
-    def __init__(self, envs, device=0, episodes_per_env=_RING_DEPTH):
-        """episodes_per_env: only for plain seeded envs (no FixedSeedsWrapper, e.g. make_test_env, make_env.py:20-35) --
+    def __init__(self, envs, device=0, episodes_per_env=_RING_DEPTH, device_layouts=False):
+        """device_layouts: sample the maps on the device (TSP / ColourMatch envs; ValueError for TimedTSP and
+        solver-ordered envs, whose maps need the host).  Plain seeded envs then play the same unbounded stream from a
+        ring the device keeps ahead by itself (ZoneVecEnv.ring_stream / ring_refill): no host sampling, no per-env
+        counters, the same observations, rewards, dones and infos.  A map the device sampler gives up on (more than
+        DEVICE_RESTARTS restarts) is put into its slot by the host sampler before the env can reach it.
+
+        episodes_per_env: only for plain seeded envs (no FixedSeedsWrapper, e.g. make_test_env, make_env.py:20-35) --
         the depth of the ring of maps kept ahead of each env on the device.  Env i plays Engine.reset's unbounded
         stream _seed, _seed + 1, ... ([not vendored] Engine.reset: `_seed += 1` at every reset): every reset -- an
         explicit reset() or the auto-reset inside step() -- takes the next map from the env's ring and the host puts
@@ -49,6 +55,12 @@ class ParallelEnv:
             if bytes(b._cfg) != bytes(cfg):
                 raise ValueError("all envs of a ParallelEnv must share one configuration")
         self.num_envs = len(envs)
+        self._device_layouts = bool(device_layouts)
+        self._status_due = False
+        if self._device_layouts and cfg.task == nat.TASK_TIMED_TSP:
+            raise ValueError("device_layouts: TimedTSP deadlines go through the host libm's log; its maps are sampled on the host")
+        if self._device_layouts and any(isinstance(b, TSPOrderEnv) for b in bases):
+            raise ValueError("device_layouts: solver-ordered maps carry the host solver's route; they are sampled on the host")
         self._vec = ZoneVecEnv(cfg, self.num_envs, device=device)
         self._vec.host_io("if small")     # 16 procs: the kernel writes the results into host memory itself, no copies
         # solver-ordered envs (TSP_order_env.py; zone-goals' TSPOrderTestEnv): routes ride in the bank, so before it
@@ -70,7 +82,10 @@ class ParallelEnv:
                 fresh = np.random.default_rng(seed=f.rng_seed).bit_generator.state
                 if f.rng.bit_generator.state != fresh:
                     raise NotImplementedError("wrap fresh envs: a FixedSeedsWrapper already drew seeds")
-            self._vec.build_bank(int(lo), int(hi) - int(lo) + 1)
+            if self._device_layouts:
+                self._vec.build_bank_device(int(lo), int(hi) - int(lo) + 1)
+            else:
+                self._vec.build_bank(int(lo), int(hi) - int(lo) + 1)
             self._vec.schedule_fixed_seeds(np.array([f.rng_seed for f in fixed], np.uint64), int(lo), int(hi))
         elif all(f is None for f in fixed):
             # Engine semantics: reset k of env i plays seed _seed_i + k (reset() does _seed += 1)
@@ -81,9 +96,12 @@ class ParallelEnv:
                     b.seed(None)
                 seeds.append(int(b._seed) + np.arange(depth, dtype=np.int64))
             self._seed0 = np.array([s[0] for s in seeds], np.int64)     # seed of env i's episode 0
-            self._vec.build_bank_seeds(np.concatenate(seeds))
             self._ring_first = np.arange(self.num_envs, dtype=np.int32) * depth
-            self._vec.schedule_ring(self._ring_first, depth)
+            if self._device_layouts:
+                self._vec.ring_stream(self._seed0, depth)
+            else:
+                self._vec.build_bank_seeds(np.concatenate(seeds))
+                self._vec.schedule_ring(self._ring_first, depth)
             self._consumed = np.zeros(self.num_envs, np.int64)           # maps env i has taken from its ring
             self._plain_depth = depth
         else:
@@ -97,8 +115,34 @@ class ParallelEnv:
         self._vec.reset()
         self._finished = None
         if self._plain_depth is not None:
-            self._refill(np.arange(self.num_envs))
+            if self._device_layouts:
+                self._device_refill()
+            else:
+                self._refill(np.arange(self.num_envs))
         return self._obs_list()
+
+    def _device_refill(self, now=False):
+        """device_layouts: the device resamples the ring slots that fell behind (no host bookkeeping).  What it could
+        not finish is listed by sample_status(), read at the synchronisation the next step makes anyway (_repair) --
+        in time, because the slot refilled after an env took episode k is the one of episode k + depth, `depth` - 1
+        episodes ahead of the env and a step ends at most one.  Where that margin is nil (a ring of depth 1, a chunk
+        that may have ended several episodes) the status is read right away (`now`)."""
+        self._vec.ring_refill()
+        self._status_due = True
+        if now or self._plain_depth == 1:
+            self._repair()
+
+    def _repair(self):
+        """After a synchronisation: slots the device sampler left untouched get the host sampler's map (the same bits,
+        or the host's error for a seed outside Engine.seed's range / an unsatisfiable config)."""
+        while self._status_due:
+            self._status_due = False
+            st = self._vec.sample_status()
+            if st["n_failed"]:
+                self._vec.update_bank(st["slots"], st["seeds"])
+                if st["n_failed"] > len(st["slots"]):          # more than the list holds: the next pass names the rest
+                    self._vec.ring_refill()
+                    self._status_due = True
 
     def _refill(self, envs_idx):
         """envs_idx just took a map each (episode k = _consumed[i]) from their rings: put episode k + depth into the
@@ -134,7 +178,9 @@ class ParallelEnv:
         o, zo, r, d, g, exc = self._vec.step_results(None, copy=False)
         o = o.astype(np.float64)
         zo = zo.astype(np.float64)
-        if self._plain_depth is not None and reset != "never":
+        if self._device_layouts and self._plain_depth is not None:
+            self._device_refill(now=True)
+        elif self._plain_depth is not None and reset != "never":
             # maps taken from the rings: one per done flag of an auto-resetting call (every call / the last one)
             taken = done.sum(0) if reset == "every" else done[-1].astype(np.int64)
             for _ in range(int(taken.max()) if taken.size else 0):
@@ -188,7 +234,10 @@ class ParallelEnv:
         """(obs (P,8), zone_obs (P,Z,F), reward (P,), done (P,), goal_met (P,)) float32/bool."""
         res = self._vec.step_results(np.asarray(actions, np.float32).reshape(self.num_envs, 2),
                                      auto_reset=auto_reset)[:5]
-        if self._plain_depth is not None and auto_reset and res[3].any():
+        if self._device_layouts and self._plain_depth is not None:
+            self._repair()
+            self._device_refill()
+        elif self._plain_depth is not None and auto_reset and res[3].any():
             self._refill(np.flatnonzero(res[3]))
         return res
 
@@ -221,7 +270,10 @@ class ParallelEnv:
         P = self.num_envs
         was_finished = getattr(self, "_finished", None)
         any_done = bool(d.any())
-        if self._plain_depth is not None and auto_reset and any_done:
+        if self._device_layouts and self._plain_depth is not None:
+            self._repair()              # the stream is idle: step_results() has just waited for the step
+            self._device_refill()
+        elif self._plain_depth is not None and auto_reset and any_done:
             # every env that reports done was reset inside the step (also one left finished by step_no_reset: the
             # worker resets it after WaitWrapper's no-op, penv.py:8-11): each took a map from its ring
             self._refill(np.flatnonzero(d))

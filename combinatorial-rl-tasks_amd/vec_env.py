@@ -246,6 +246,30 @@ def sample_layout(cfg, seed):
     return robot, zones, aux, restarts.value
 
 
+def sample_layout_shared(cfg, seed):
+    """``sample_layout`` through the source the device sampler is compiled from (zenv_sample_layout_shared): the same
+    results, bit for bit, without a GPU.  TSP and ColourMatch configs."""
+    Z = cfg.num_zones
+    robot = np.zeros(3, np.float64)
+    zones = np.zeros((Z, 2), np.float64)
+    aux = np.zeros(Z, np.int32)
+    restarts = C.c_int32(0)
+    check(lib().zenv_sample_layout_shared(C.byref(cfg), int(seed), robot.ctypes.data, zones.ctypes.data,
+                                          aux.ctypes.data, C.byref(restarts)))
+    return robot, zones, aux, restarts.value
+
+
+def layout_thresholds(cfg):
+    """The keepout test's two right-hand sides A (a zone against the robot, a zone against a zone) and for each the
+    threshold T with ``sqrt(s) < A  <=>  s < T`` that the shared sampler compares d^2 with (zenv_layout_thresholds).
+
+    Returns (rhs[2], thr[2])."""
+    rhs = np.zeros(2, np.float64)
+    thr = np.zeros(2, np.float64)
+    check(lib().zenv_layout_thresholds(C.byref(cfg), rhs.ctypes.data, thr.ctypes.data))
+    return rhs, thr
+
+
 def route_ranks(robot_xy, zone_xy):
     """The built-in visiting order of a layout (TSPOrderEnv without OR-tools): rank[z] = position of zone z in a
     tour: TSP_Solver.get_optim_route's problem (closed tour from the robot, int64(10 x distance) arcs,
@@ -350,6 +374,68 @@ class ZoneVecEnv:
         if sl.shape != sd.shape:
             raise ValueError("one seed per slot")
         check(lib().zenv_bank_update(self._h, sl.ctypes.data, sd.ctypes.data, sl.size, int(n_threads)))
+
+    # ---- layouts sampled on the device (K20): only seeds cross the bus.  TSP / ColourMatch handles; TimedTSP and
+    # solver-ordered handles raise ZenvError(E_STATE) and stay on the host calls above
+    def build_bank_device(self, seed_first, count):
+        """``build_bank`` sampled on the device (zenv_bank_build_device; synchronous, same bank bit for bit)."""
+        check(lib().zenv_bank_build_device(self._h, int(seed_first), int(count)))
+
+    def build_bank_seeds_device(self, seeds):
+        """``build_bank_seeds`` sampled on the device (zenv_bank_build_seeds_device)."""
+        s = np.ascontiguousarray(seeds, np.int64).reshape(-1)
+        check(lib().zenv_bank_build_seeds_device(self._h, s.ctypes.data, s.size))
+
+    def update_bank_device(self, slots, seeds):
+        """``update_bank`` sampled on the device (zenv_bank_update_device; stream-ordered).  A slot whose seed the device
+        could not finish keeps its contents and shows up in ``sample_status()``."""
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        sd = np.ascontiguousarray(seeds, np.int64).reshape(-1)
+        if sl.shape != sd.shape:
+            raise ValueError("one seed per slot")
+        check(lib().zenv_bank_update_device(self._h, sl.ctypes.data, sd.ctypes.data, sl.size))
+
+    def ring_stream(self, seed0, depth):
+        """Env i's k-th episode is the layout of env seed ``seed0[i] + k``, for ever: a num_envs x depth bank sampled
+        on the device, a ring schedule over it (zenv_ring_stream) and ``ring_refill()`` to keep it ahead -- at least
+        once per `depth` episodes of an env.  Memory: 88 + 20 Z bytes per slot (588 B at Z = 25)."""
+        s = np.ascontiguousarray(seed0, np.int64)
+        if s.shape != (self.num_envs,):
+            raise ValueError("seed0 must have shape (num_envs,)")
+        check(lib().zenv_ring_stream(self._h, s.ctypes.data, int(depth)))
+
+    def ring_refill(self):
+        """Resample, on the device, every ring slot whose episode is behind its env (zenv_ring_refill): asynchronous,
+        stream-ordered, no host synchronisation."""
+        check(lib().zenv_ring_refill(self._h))
+
+    def sample_status(self):
+        """Synchronise and take the device sampler's failure list (zenv_sample_status).
+
+        Returns dict(slots, seeds, codes, n_failed, n_sampled_total): the listed entries (at most SAMPLE_STATUS_CAP;
+        codes SAMPLE_UNFINISHED / SAMPLE_SEED_RANGE), how many entries were left untouched since the last call, and
+        the layouts the device has written since the handle was made."""
+        cap = nat.SAMPLE_STATUS_CAP
+        slots, seeds, codes = np.zeros(cap, np.int32), np.zeros(cap, np.int64), np.zeros(cap, np.int32)
+        n_failed, total = C.c_int32(0), C.c_int64(0)
+        check(lib().zenv_sample_status(self._h, slots.ctypes.data, seeds.ctypes.data, codes.ctypes.data, cap,
+                                       C.byref(n_failed), C.byref(total)))
+        n = min(n_failed.value, cap)
+        return dict(slots=slots[:n].copy(), seeds=seeds[:n].copy(), codes=codes[:n].copy(), n_failed=n_failed.value,
+                    n_sampled_total=total.value)
+
+    def read_bank(self, first=0, count=None):
+        """Synchronise and copy bank rows out (zenv_bank_read): dict(robot [count,4] (x, y, cos(rot/2), sin(rot/2)),
+        zone_xy [count,Z,2], aux [count,Z], seeds [count], first [count,12] float32 (first observation, first greedy
+        action, pad))."""
+        first = int(first)
+        count = self.bank_size - first if count is None else int(count)
+        n, Z = max(count, 0), self.num_zones
+        out = dict(robot=np.zeros((n, 4), np.float64), zone_xy=np.zeros((n, Z, 2), np.float64),
+                   aux=np.zeros((n, Z), np.int32), seeds=np.zeros(n, np.int64), first=np.zeros((n, 12), np.float32))
+        check(lib().zenv_bank_read(self._h, first, count, out["robot"].ctypes.data, out["zone_xy"].ctypes.data,
+                                   out["aux"].ctypes.data, out["seeds"].ctypes.data, out["first"].ctypes.data))
+        return out
 
     def schedule_fixed_seeds(self, rng_seeds, min_seed, max_seed):
         s = np.ascontiguousarray(rng_seeds, np.uint64)
@@ -837,7 +923,7 @@ class ZoneVecEnv:
         """The same buffers as name -> (field id, shape in memory, dtype), the form of the agents' layouts."""
         return _lo_rows(self.num_envs, self.num_zones, self.zone_feat, int(frames_per_proc))
 
-    # ------------------------------------------------------------------ the collectors' per-episode logs (K19)
+    # ------------------------------------------------------------------ the collectors' per-episode logs (K20)
     def episode_log_on_device(self):
         """zenv_episode_log: the reference's ``logs`` of the last collection (any of the five collectors), left in
         device buffers.  Once per collection; waits for the device once.  Returns the ``EpisodeLogInfo`` (kept, done,

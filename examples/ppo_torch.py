@@ -97,12 +97,20 @@ def ppo_update(model, opt, exps, epochs, batch_size, clip_eps, entropy_coef, val
 
 def train(env_id="PointTSP-v0", procs=4096, frames_per_proc=64, updates=10, epochs=4, batch_size=16384, lr=3e-4,
           discount=0.99, gae_lambda=0.95, clip_eps=0.2, entropy_coef=0.003, value_loss_coef=0.5, max_grad_norm=0.5,
-          hidden=185, seed=1, log=print, device_update=False):
+          hidden=185, seed=1, log=print, device_update=False, fresh_layouts=False):
     torch.manual_seed(seed)
     dev = torch.device("cuda", 0)
     env = Z.ZoneVecEnv(env_id, procs)
-    env.build_bank(seed, 4 * procs)             # fresh layouts on every reset, as FixedSeedWrapper draws them
-    env.schedule_sequential(stride=procs)
+    if fresh_layouts:
+        # a fresh map at every reset, as the reference's training envs draw them: env i's k-th episode is the layout of
+        # seed `seed + i * 2^20 + k`, sampled on the device into a ring of frames_per_proc maps per env (a collection
+        # ends at most that many episodes of an env: the collectors' ring guard) and refilled after every collection.
+        # Memory: 88 + 20 Z bytes per slot (588 B at Z = 25), procs * frames_per_proc slots
+        import numpy as np
+        env.ring_stream(seed + (np.arange(procs, dtype=np.int64) << 20), frames_per_proc)
+    else:
+        env.build_bank(seed, 4 * procs)         # a finite bank of layouts, walked round for ever
+        env.schedule_sequential(stride=procs)
     tenv = TorchZoneEnv(env)
     tenv.reset()
     model = ActorCritic(env.zone_feat, hidden).to(dev)
@@ -120,6 +128,8 @@ def train(env_id="PointTSP-v0", procs=4096, frames_per_proc=64, updates=10, epoc
         if not device_update:
             tenv.load_state_dict(model.state_dict())
         exps = tenv.collect(frames_per_proc, policy_seed=seed * 1000003 + u, discount=discount, gae_lambda=gae_lambda)
+        if fresh_layouts:
+            env.ring_refill()                   # stream-ordered: behind the collection, before the next one
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         if device_update:
@@ -155,6 +165,9 @@ if __name__ == "__main__":
     ap.add_argument("--hidden-size", type=int, default=185)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--device-update", action="store_true", help="run the update in the library's HIP kernels")
+    ap.add_argument("--fresh-layouts", action="store_true",
+                    help="a fresh map at every reset, sampled on the device (ring_stream, depth = frames per proc; "
+                         "588 B per slot at 25 zones)")
     a = ap.parse_args()
     train(a.env, a.procs, a.frames_per_proc, a.updates, a.epochs, a.batch_size, a.lr, hidden=a.hidden_size, seed=a.seed,
-          device_update=a.device_update)
+          device_update=a.device_update, fresh_layouts=a.fresh_layouts)

@@ -326,11 +326,68 @@ int zenv_bank_size(const zenv_t *h);
  * the host puts episode k + depth into the slot that held it. */
 int zenv_bank_update(zenv_t *h, const int32_t *slots, const int64_t *seeds, int count, int n_threads);
 
+/* ---- layouts sampled on the device (K20) ----
+ * The sampler of zenv_sample_layout, compiled a second time from ONE source (csrc/layout_sampler.hpp) for the host and
+ * for gfx950: integer MT19937 and IEEE float64 add / mul / compare only, so both give the host sampler's bits.  On the
+ * device one wave samples one env seed straight into its bank slot; only the seeds cross the bus.
+ *
+ * A device wave gives up after ZENV_DEVICE_RESTARTS restarts of the rejection sampler (the host's limit is the
+ * reference's 10000) and reports the seed ZENV_SAMPLE_UNFINISHED; a seed outside [0, 2^32 - 2] (Engine.seed +
+ * Engine.reset's `_seed += 1`) is reported ZENV_SAMPLE_SEED_RANGE.  In both cases the slot keeps what it held.  The
+ * reports -- (slot, seed, code), all of them counted, the first ZENV_SAMPLE_STATUS_CAP listed -- wait on the device for
+ * zenv_sample_status; the synchronous builders read them themselves.
+ *
+ * Every device-sampling call (zenv_bank_build_device, _build_seeds_device, zenv_bank_update_device, zenv_ring_stream,
+ * zenv_ring_refill) answers ZENV_E_STATE on a TimedTSP handle -- its deadlines are int(beta * num_steps) with beta
+ * through the host libm's log, which the device's math library does not reproduce bit for bit -- and on a
+ * solver-ordered handle, whose bank rows need zenv_route_ranks.  Both stay on the host path. */
+#define ZENV_DEVICE_RESTARTS 256
+#define ZENV_SAMPLE_STATUS_CAP 1024
+enum { ZENV_SAMPLE_UNFINISHED = 1, ZENV_SAMPLE_SEED_RANGE = 2 };
+/* zenv_sample_layout through the shared source, compiled for the host (10000 restarts): same arguments, same results,
+ * usable without a GPU.  TimedTSP configs: ZENV_E_ARG. */
+int zenv_sample_layout_shared(const zenv_config *cfg, int64_t seed, double *robot_xyrot,
+                              double *zone_xy, int32_t *aux, int32_t *restarts);
+/* The keepout test of the shared source compares d^2 with a threshold instead of sqrt(d^2) with a distance.  rhs[2],
+ * thr[2]: the two right-hand sides A a config has ([0] a zone against the robot, (robot_keepout + placements_margin) +
+ * zones_keepout; [1] a zone against a zone) and for each the double T with  sqrt(s) < A <=> s < T.  Host only. */
+int zenv_layout_thresholds(const zenv_config *cfg, double *rhs, double *thr);
+/* zenv_bank_build / zenv_bank_build_seeds with the layouts sampled on the device.  Synchronous: the new bank is
+ * sampled into fresh buffers, seeds the device left unfinished are finished by the host sampler (identical bits, or
+ * ZENV_E_LAYOUT), an out-of-range seed is ZENV_E_ARG; on any error the previous bank stays in place.  The schedule is
+ * treated as zenv_bank_build treats it. */
+int zenv_bank_build_device(zenv_t *h, int64_t seed_first, int count);
+int zenv_bank_build_seeds_device(zenv_t *h, const int64_t *seeds, int count);
+/* zenv_bank_update with 12 bytes per layout over the bus.  Asynchronous and stream-ordered; slots the device could not
+ * fill keep their contents and are reported by zenv_sample_status. */
+int zenv_bank_update_device(zenv_t *h, const int32_t *slots, const int64_t *seeds, int count);
+/* Engine.reset's unbounded seed stream without the host: builds an N x depth bank on the device (slot i*depth + j <-
+ * seed0[i] + j, synchronous like zenv_bank_build_device), lays the ring schedule first[i] = i*depth over it and keeps
+ * seed0 [N] on the device.  Episode k of env i is then the layout of env seed seed0[i] + k as long as
+ * zenv_ring_refill runs at least once per `depth` episodes of an env (the ring guard of zenv_schedule_ring holds). */
+int zenv_ring_stream(zenv_t *h, const int64_t *seed0, int32_t depth);
+/* Bring every ring back ahead of its env: slot first[i] + j must hold episode e_j, the smallest e >= the env's
+ * episode index with e mod depth == j; the slots whose seed is not seed0[i] + e_j are listed on the device and sampled by
+ * a launch that reads the list's length from device memory; the derived first rows are then recomputed for the whole
+ * ring bank.  Asynchronous, stream-ordered, no host synchronisation, no host bookkeeping.  ZENV_E_STATE unless zenv_ring_stream made the current schedule. */
+int zenv_ring_refill(zenv_t *h);
+/* Synchronises, copies the device's failure list out (the first min(cap, ZENV_SAMPLE_STATUS_CAP) entries into slots /
+ * seeds / codes [cap], any of which may be NULL) and clears it.  n_failed: every entry a sampling launch left
+ * untouched since the last call; n_sampled_total: layouts the device has written since the handle was made. */
+int zenv_sample_status(zenv_t *h, int32_t *slots, int64_t *seeds, int32_t *codes, int cap, int32_t *n_failed,
+                       int64_t *n_sampled_total);
+/* Synchronises and copies bank rows slot_first .. slot_first + count - 1 out (host memory; any may be NULL):
+ * robot4 [count,4] (x, y, cos(rot/2), sin(rot/2)), zone_xy [count,Z,2], aux [count,Z], seeds [count], first12
+ * [count,12] float32 (the derived rows: first observation, first greedy action, pad). */
+int zenv_bank_read(zenv_t *h, int slot_first, int count, double *robot4, double *zone_xy, int32_t *aux,
+                   int64_t *seeds, float *first12);
+
 /* ---- episode schedule: which bank slot env i uses for its k-th episode ---- */
 /* slot = (first[i] + k*stride) mod S; first == NULL -> i mod S. */
 int zenv_schedule_sequential(zenv_t *h, const int32_t *first, int32_t stride);
 /* Ring: env i owns the slots first[i] .. first[i] + depth - 1 and takes slot first[i] + (k mod depth) for its k-th
- * episode; the host keeps the ring ahead of the env with zenv_bank_update.  Only the host refills the ring, between
+ * episode; the host keeps the ring ahead of the env with zenv_bank_update (or the device does, zenv_ring_stream /
+ * zenv_ring_refill).  The ring is only refilled between
  * calls, so a call that could end more than `depth` episodes of an env is refused with ZENV_E_STATE (it could replay
  * maps): zenv_rollout with auto_reset and zenv_step_many(RESET_EVERY) beyond `depth` steps, zenv_collect and
  * zenv_collect_hier and zenv_collect_option beyond `depth` frames, zenv_collect_skill beyond `depth` windows. */
