@@ -29,9 +29,9 @@ from ._native import (Config, ZenvError, E_ARG, E_HIP, E_STATE, E_LAYOUT, E_DONE
                       XYPPO_HI, F_SKPPO_LO_STATS, F_SKPPO_HI_STATS, SKPPO_LO, SKPPO_HI, F_OPPPO_LO_STATS,
                       F_OPPPO_HI_STATS, OPPPO_LO, OPPPO_HI, F_DIAYN_STATS, F_DIAYN_SAMPLES,
                       RenderConfig, RENDER_CURRENT, RENDER_EXPERIENCE, DEVICE_RESTARTS, SAMPLE_STATUS_CAP,
-                      SAMPLE_UNFINISHED, SAMPLE_SEED_RANGE)
+                      SAMPLE_UNFINISHED, SAMPLE_SEED_RANGE, DET_OP_LOG, DET_OP_DIV, DET_OP_SQRT)
 from .vec_env import (ZoneVecEnv, config_for_id, default_config, sample_layout, sample_layout_shared,
-                      layout_thresholds,
+                      layout_thresholds, sample_layout_timed, det_ops,
                       fixed_seed_sequence, route_ranks, zone_feat, hier_tensors_from_state_dicts,
                       hier_experience_layout, check_collect_hier_args, skill_tensors_from_state_dicts,
                       inverse_tensors_from_state_dict, skill_experience_layout, check_collect_skill_args,

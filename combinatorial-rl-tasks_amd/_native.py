@@ -150,6 +150,7 @@ RENDER_CURRENT, RENDER_EXPERIENCE = 0, 1                      # zenv_render_conf
 # layouts sampled on the device: ZENV_DEVICE_RESTARTS, ZENV_SAMPLE_STATUS_CAP, the codes of zenv_sample_status
 DEVICE_RESTARTS, SAMPLE_STATUS_CAP = 256, 1024
 SAMPLE_UNFINISHED, SAMPLE_SEED_RANGE = 1, 2
+DET_OP_LOG, DET_OP_DIV, DET_OP_SQRT = 0, 1, 2   # zenv_det_ops
 
 
 class RenderConfig(C.Structure):
@@ -225,6 +226,10 @@ _PROTOTYPES = {
     "zenv_sample_layout_shared": (C.c_int, [C.POINTER(Config), C.c_int64, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.POINTER(C.c_int32)]),
     "zenv_layout_thresholds": (C.c_int, [C.POINTER(Config), C.c_void_p, C.c_void_p]),
+    "zenv_sample_layout_timed": (C.c_int, [C.POINTER(Config), C.c_int64, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.POINTER(C.c_int32)]),
+    "zenv_timed_layouts_device": (C.c_int, [_H, C.c_int]),
+    "zenv_det_ops": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "zenv_bank_build_device": (C.c_int, [_H, C.c_int64, C.c_int]),
     "zenv_bank_build_seeds_device": (C.c_int, [_H, C.c_void_p, C.c_int]),
     "zenv_bank_update_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int]),

@@ -53,6 +53,9 @@ struct Layout {
 
 // Returns 0 or ZENV_E_LAYOUT.
 int sample_layout(const zenv_config &cfg, int64_t seed, Layout &out);
+// The same through layout_sampler.hpp's host instantiation (zenv_layout.cpp): identical for TSP and ColourMatch configs;
+// a TimedTSP config's deadlines go through the shared det_log instead of libm's log.  The caller checks the seed's range.
+int sample_layout_shared_host(const zenv_config &cfg, int64_t seed, Layout &out);
 
 // A visiting order for the solver-ordered variant (TSP_order_env.py:49-50 calls OR-tools, which is not available
 // here): closed tour from the robot, nearest-neighbour construction (what OR-tools' PATH_CHEAPEST_ARC starts

@@ -6,6 +6,8 @@
 // all lanes temper alike; placed object j (0 = the robot, 1 .. Z = the zones) sits in lane j's registers, so the
 // keepout test of a candidate against everything placed is one compare per lane and one ballot.  Control flow is
 // wave-uniform throughout: rejection loops of different seeds never share a wave, so they do not diverge.
+// TimedTSP: every lane evaluates the same serial deadline draw (beta -> gamma -> gauss, det_log.hpp), lane z + 1 keeps
+// zone z's deadline.
 #include <hip/hip_runtime.h>
 
 #include "layout_sample.hpp"
@@ -60,8 +62,8 @@ __global__ __launch_bounds__(kWave) void k_layout_sample(LayoutSampleArgs a)
         int32_t restarts = 0;
         int code = SAMPLE_SEED_RANGE;                        // Engine.seed: 'Seed must be between 0 and 2**32 - 1'
         if (seed >= 0 && seed + 1 <= 0xFFFFFFFFll)
-            code = sample_layout_shared(a.c, TASK == ZENV_TASK_COLOUR_MATCH, (uint32_t)seed, kSamplerDeviceAttempts, st,
-                                        rot, restarts);
+            code = sample_layout_shared(a.c, TASK == ZENV_TASK_COLOUR_MATCH, TASK == ZENV_TASK_TIMED_TSP, (uint32_t)seed,
+                                        kSamplerDeviceAttempts, st, rot, restarts);
         if (code == SAMPLE_OK) {
             if (lane == 0) {
                 double s, c;
@@ -110,13 +112,31 @@ __global__ __launch_bounds__(256) void k_ring_stale(DevParams p, const int64_t *
     }
 }
 
+// zenv_det_ops: det_log / det_div / det_sqrt as the device compiles them, one element per thread
+__global__ __launch_bounds__(256) void k_det_ops(int op, const double *__restrict__ a, const double *__restrict__ b,
+                                                 double *__restrict__ out, int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = op == DET_OP_LOG ? det_log(a[i]) : op == DET_OP_DIV ? det_div(a[i], b[i]) : det_sqrt(a[i]);
+}
+
 }  // namespace
+
+hipError_t launch_det_ops(int op, const double *a, const double *b, double *out, int n, hipStream_t s)
+{
+    if (n < 1) return hipSuccess;
+    hipLaunchKernelGGL(k_det_ops, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, op, a, b, out, n);
+    return hipGetLastError();
+}
 
 hipError_t launch_layout_sample(const LayoutSampleArgs &a, int grid, hipStream_t s)
 {
     if (grid < 1) return hipSuccess;
     if (a.c.task == ZENV_TASK_COLOUR_MATCH)
         hipLaunchKernelGGL(k_layout_sample<ZENV_TASK_COLOUR_MATCH>, dim3(grid), dim3(kWave), 0, s, a);
+    else if (a.c.task == ZENV_TASK_TIMED_TSP)
+        hipLaunchKernelGGL(k_layout_sample<ZENV_TASK_TIMED_TSP>, dim3(grid), dim3(kWave), 0, s, a);
     else
         hipLaunchKernelGGL(k_layout_sample<ZENV_TASK_TSP>, dim3(grid), dim3(kWave), 0, s, a);
     return hipGetLastError();

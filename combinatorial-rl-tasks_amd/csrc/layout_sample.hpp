@@ -37,6 +37,11 @@ struct LayoutSampleArgs {
 // One wave per entry, grid-stride over the list: `grid` blocks of 64 threads.
 hipError_t launch_layout_sample(const LayoutSampleArgs &a, int grid, hipStream_t s);
 
+// zenv_det_ops on the device: out[i] = det_log(a[i]) / det_div(a[i], b[i]) / det_sqrt(a[i]) (device pointers; b only
+// for DET_OP_DIV), compiled from det_log.hpp as the sampling kernel is.
+enum { DET_OP_LOG = 0, DET_OP_DIV = 1, DET_OP_SQRT = 2 };   // == ZENV_DET_OP_*
+hipError_t launch_det_ops(int op, const double *a, const double *b, double *out, int n, hipStream_t s);
+
 // The slots of a streamed ring that do not hold the episode they must (zenv_ring_refill): for env i and ring position
 // j the slot slot_first[i] + j must hold episode e_j = the smallest e >= episode_idx[i] with e mod depth == j, i.e.
 // bank_seed == seed0[i] + e_j; the others are appended to (list_slots, list_seeds), *count of them (zeroed by the

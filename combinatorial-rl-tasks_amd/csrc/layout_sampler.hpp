@@ -15,14 +15,15 @@
 //   uint32_t word(i), set_word(i,v)  the generator's state word i
 //   double px(j), py(j)              centre of placed object j, asked for by lane j mod kLanes only
 //   void place(j, x, y)              record object j (0 = the robot, 1.. = the zones)
-//   void set_aux(z, v)               the task's aux column (ColourMatch: colour 0..2)
+//   void set_aux(z, v)               the task's aux column (ColourMatch: colour 0..2; TimedTSP: the deadline in steps)
 // All arithmetic is integer or IEEE float64 add / mul / compare (the build has -ffp-contract=off): same bits on x86
-// and on CDNA4.  Every lane of a group follows the same control flow: draws, accept / reject decisions and restart
+// and on CDNA4.  The TimedTSP deadlines add det_log.hpp's det_log / det_div / det_sqrt, the same bits on both as well.  Every lane of a group follows the same control flow: draws, accept / reject decisions and restart
 // counts are group-uniform by construction (decisions go through any()).
 #pragma once
 #include <cstdint>
 
 #include "../../include/zenv.h"
+#include "det_log.hpp"
 #include "det_math.hpp"
 
 namespace zenvk {
@@ -34,8 +35,10 @@ enum { SAMPLE_OK = 0, SAMPLE_UNFINISHED = 1, SAMPLE_SEED_RANGE = 2 };   // == ZE
 // What the sampler reads of a zenv_config, with the keepout test's two thresholds (make_sampler_cfg, host only).
 struct SamplerCfg {
     int32_t task, Z;
-    int32_t n_zones_locations, n_robot_locations, robot_rot_fixed, pad_;
+    int32_t n_zones_locations, n_robot_locations, robot_rot_fixed;
+    int32_t num_steps;                                   // TimedTSP: a deadline is int(beta(beta_a, beta_b) * num_steps)
     double extent, robot_keepout, zones_keepout, robot_rot;
+    double beta_a, beta_b;
     // sqrt(s) < A  <=>  s < T for the two right-hand sides A the placement loop ever has (see keepout_threshold):
     double t_robot_zone;   // A = (robot_keepout + placements_margin) + zones_keepout: a zone against the robot
     double t_zone_zone;    // A = (zones_keepout + placements_margin) + zones_keepout: a zone against a zone
@@ -50,7 +53,9 @@ template <class P>
 struct RandomStateT {
     P &st;
     int idx;
-    ZENV_HD explicit RandomStateT(P &s) : st(s), idx(624) {}
+    bool has_gauss;      // legacy_gauss draws two normals at a time and keeps the second
+    double gauss_next;
+    ZENV_HD explicit RandomStateT(P &s) : st(s), idx(624), has_gauss(false), gauss_next(0.0) {}
 
     // init_genrand: a serial chain; every lane runs it (the values are group-uniform), lane i mod kLanes keeps word i
     ZENV_HD void seed(uint32_t seed)
@@ -62,6 +67,8 @@ struct RandomStateT {
         }
         st.sync();
         idx = 624;
+        has_gauss = false;
+        gauss_next = 0.0;
     }
 
     static ZENV_HD uint32_t mix(uint32_t hi, uint32_t lo)
@@ -133,6 +140,54 @@ struct RandomStateT {
             if (v <= top) return v;
         }
     }
+
+    // legacy_gauss, standard_gamma (shape > 1: Marsaglia-Tsang) and beta (a, b > 1) as LegacyRandomState has them in
+    // host_sampler.cpp, expression for expression, with det_log / det_div / det_sqrt where that one calls libm.  Every
+    // lane draws the same values: the loops are group-uniform.
+    ZENV_HD double gauss()
+    {
+        if (has_gauss) {
+            has_gauss = false;
+            const double g = gauss_next;
+            gauss_next = 0.0;
+            return g;
+        }
+        double x1, x2, r2;
+        do {
+            x1 = 2.0 * next_double() - 1.0;
+            x2 = 2.0 * next_double() - 1.0;
+            r2 = x1 * x1 + x2 * x2;
+        } while (r2 >= 1.0 || r2 == 0.0);
+        const double f = det_sqrt(det_div(-2.0 * det_log(r2), r2));
+        gauss_next = f * x1;
+        has_gauss = true;
+        return f * x2;
+    }
+
+    ZENV_HD double standard_gamma(double shape)
+    {
+        const double b = shape - det_div(1., 3.);
+        const double c = det_div(1., det_sqrt(9 * b));
+        for (;;) {
+            double x, v;
+            do {
+                x = gauss();
+                v = 1.0 + c * x;
+            } while (v <= 0.0);
+            v = v * v * v;
+            const double u = next_double();
+            if (u < 1.0 - 0.0331 * (x * x) * (x * x)) return b * v;
+            // u == 0 has log(u) = -inf on the host: always below the finite right-hand side
+            if (u == 0.0 || det_log(u) < 0.5 * x * x + b * (1. - v + det_log(v))) return b * v;
+        }
+    }
+
+    ZENV_HD double beta(double a, double b)
+    {
+        const double ga = standard_gamma(a);
+        const double gb = standard_gamma(b);
+        return det_div(ga, ga + gb);
+    }
 };
 
 // ------------------------------------------------------------------ the keepout test without a square root
@@ -156,13 +211,14 @@ ZENV_HD bool keepout_hit(double x, double y, double px, double py, double T)
 }
 
 // ------------------------------------------------------------------ the placement loop
-// sample_layout of host_sampler.cpp for TSP and ColourMatch configs (TimedTSP's deadlines need libm's log: host only).
-// Returns SAMPLE_OK with the objects in P (place()), the colours in P (set_aux()) and the rotation in `rot`, or
+// sample_layout of host_sampler.cpp.  With draw_deadlines (TimedTSP) the deadlines are drawn through det_log, which is
+// within an ulp of any faithful libm's log: the same deadline as the host sampler's unless beta * num_steps lands within
+// a few ulps of an integer.  Returns SAMPLE_OK with the objects in P (place()), the colours in P (set_aux()) and the rotation in `rot`, or
 // SAMPLE_UNFINISHED after max_attempts failed attempts (restarts == max_attempts then).  The caller checks the seed's
 // range (0 <= seed, seed + 1 <= 2^32 - 1) first.
 template <class P>
-ZENV_HD int sample_layout_shared(const SamplerCfg &c, bool draw_colours, uint32_t seed, int max_attempts, P &st,
-                                 double &rot, int32_t &restarts)
+ZENV_HD int sample_layout_shared(const SamplerCfg &c, bool draw_colours, bool draw_deadlines, uint32_t seed,
+                                 int max_attempts, P &st, double &rot, int32_t &restarts)
 {
     const int Z = c.Z;
     RandomStateT<P> rs(st);
@@ -171,6 +227,12 @@ ZENV_HD int sample_layout_shared(const SamplerCfg &c, bool draw_colours, uint32_
         rs.seed(seed);
         for (int z = 0; z < Z; ++z) st.set_aux(z, (int32_t)rs.randint_below(3));
         st.sync();          // the last loads of this generator before the next one's stores
+    }
+    if (draw_deadlines) {    // c.task == ZENV_TASK_TIMED_TSP, a compile-time constant in the kernel
+        // TTSP_env.py:19-21 draws from RandomState(seed) as well; the cached second normal carries over between zones
+        rs.seed(seed);
+        for (int z = 0; z < Z; ++z) st.set_aux(z, (int32_t)(rs.beta(c.beta_a, c.beta_b) * c.num_steps));
+        st.sync();
     }
     rs.seed(seed + 1u);
     restarts = 0;

@@ -658,7 +658,7 @@ int adopt_bank(zenv *h, void *const fresh[5], size_t S)
 // Engine.reset's random half for a list of env seeds, on n_threads host threads: robot (x, y, quat w, quat z), zone
 // centres, the task's aux column (tmax / colours / route ranks) per seed.
 static int sample_bank_rows(const zenv *h, const int64_t *seed_list, size_t S, int n_threads, std::vector<double> &robot4,
-                            std::vector<double> &zone, std::vector<int32_t> &aux)
+                            std::vector<double> &zone, std::vector<int32_t> &aux, bool shared_sampler = false)
 {
     const int Z = h->cfg.num_zones;
     for (size_t i = 0; i < S; ++i)
@@ -673,7 +673,7 @@ static int sample_bank_rows(const zenv *h, const int64_t *seed_list, size_t S, i
     auto work = [&](int tid) {
         for (size_t i = tid; i < S; i += n_threads) {
             Layout L;
-            status[i] = sample_layout(h->cfg, seed_list[i], L);
+            status[i] = shared_sampler ? sample_layout_shared_host(h->cfg, seed_list[i], L) : sample_layout(h->cfg, seed_list[i], L);
             double s, c;
             det_sincos(L.robot_rot / 2, s, c);   // world.py rot2quat: [cos(rot/2), 0, 0, sin(rot/2)]
             robot4[4 * i + 0] = L.robot_x;
@@ -729,7 +729,9 @@ extern "C" int zenv_bank_update(zenv_t *h, const int32_t *slots, const int64_t *
     if (rc) return rc;
     std::vector<double> robot4, zone;
     std::vector<int32_t> aux;
-    rc = sample_bank_rows(h, seed_list, (size_t)count, n_threads, robot4, zone, aux);
+    // a handle switched to device-sampled TimedTSP layouts (zenv_timed_layouts_device) refills with the shared sampler's
+    // host instantiation: what repairs a slot the device gave up on must not mix libm's deadlines into the bank
+    rc = sample_bank_rows(h, seed_list, (size_t)count, n_threads, robot4, zone, aux, h->ls.timed_device);
     if (rc) return rc;
     const size_t Z = (size_t)h->cfg.num_zones;
     const size_t rec = (4 + 2 * Z + 1) * 8 + ((Z * 4 + 7) / 8) * 8;

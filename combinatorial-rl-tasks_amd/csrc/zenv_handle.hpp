@@ -227,6 +227,7 @@ struct zenv {
         bool stage_busy = false;
         int64_t *ring_seed0 = nullptr;
         bool ring_streamed = false;
+        bool timed_device = false;           // zenv_timed_layouts_device: TimedTSP layouts with det_log's deadlines
     } ls;
     // the sharded job's communicator (zenv_comm_init): RCCL over xGMI
     ncclComm_t comm = nullptr;

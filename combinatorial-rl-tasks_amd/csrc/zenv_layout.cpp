@@ -33,12 +33,35 @@ SamplerCfg make_sampler_cfg(const zenv_config &cfg)
     c.robot_keepout = cfg.robot_keepout;
     c.zones_keepout = cfg.zones_keepout;
     c.robot_rot = cfg.robot_rot;
+    c.num_steps = cfg.num_steps;
+    c.beta_a = cfg.beta_a;
+    c.beta_b = cfg.beta_b;
     // host_sampler.cpp: placed[j].keepout + cfg.placements_margin + keepout, left to right
     c.t_robot_zone = keepout_threshold((cfg.robot_keepout + cfg.placements_margin) + cfg.zones_keepout);
     c.t_zone_zone = keepout_threshold((cfg.zones_keepout + cfg.placements_margin) + cfg.zones_keepout);
     std::memcpy(c.robot_location, cfg.robot_location, sizeof(c.robot_location));
     c.zones_locations = &cfg.zones_locations[0][0];      // the caller's config outlives the SamplerCfg
     return c;
+}
+
+int sample_layout_shared_host(const zenv_config &cfg, int64_t seed, Layout &out)
+{
+    const int Z = cfg.num_zones;
+    std::memset(&out, 0, sizeof(out));
+    const SamplerCfg c = make_sampler_cfg(cfg);
+    HostLanes st;
+    std::memset(st.aux, 0, sizeof(st.aux));
+    const int code = sample_layout_shared(c, cfg.task == ZENV_TASK_COLOUR_MATCH, cfg.task == ZENV_TASK_TIMED_TSP,
+                                          (uint32_t)seed, kSamplerHostAttempts, st, out.robot_rot, out.restarts);
+    if (code != SAMPLE_OK) return ZENV_E_LAYOUT;
+    out.robot_x = st.x[0];
+    out.robot_y = st.y[0];
+    for (int z = 0; z < Z; ++z) {
+        out.zone_xy[z][0] = st.x[z + 1];
+        out.zone_xy[z][1] = st.y[z + 1];
+        out.aux[z] = st.aux[z];
+    }
+    return 0;
 }
 
 }  // namespace zenvk
@@ -51,9 +74,10 @@ bool seed_in_range(int64_t seed) { return seed >= 0 && seed + 1 <= 0xFFFFFFFFll;
 
 int device_sampling_allowed(const zenv *h)
 {
-    if (h->cfg.task == ZENV_TASK_TIMED_TSP)
+    if (h->cfg.task == ZENV_TASK_TIMED_TSP && !h->ls.timed_device)
         return fail(ZENV_E_STATE, "TimedTSP layouts are sampled on the host: the deadlines are int(beta * num_steps) with beta "
-                                  "through the host libm's log, which the device's math library does not reproduce bit for bit");
+                                  "through the host libm's log, which the device's math library does not reproduce bit for bit "
+                                  "(zenv_timed_layouts_device switches the handle to the shared det_log's deadlines)");
     if (h->order_enabled)
         return fail(ZENV_E_STATE, "solver-ordered layouts are sampled on the host: their bank rows carry zenv_route_ranks' route");
     return ZENV_OK;
@@ -188,7 +212,8 @@ int build_on_device(zenv *h, const int64_t *seed_list, int count)
     }
     for (int32_t slot : redo) {
         Layout L;
-        if (sample_layout(h->cfg, seed_list[slot], L)) {
+        // a TimedTSP bank is defined by the shared sampler's det_log: its host instantiation finishes it, not libm's
+        if (h->ls.timed_device ? sample_layout_shared_host(h->cfg, seed_list[slot], L) : sample_layout(h->cfg, seed_list[slot], L)) {
             drop();
             return fail(ZENV_E_LAYOUT, "Failed to sample layout of objects (seed %lld)", (long long)seed_list[slot]);
         }
@@ -209,6 +234,42 @@ int build_on_device(zenv *h, const int64_t *seed_list, int count)
         }
     }
     return adopt_bank(h, fresh, S);
+}
+
+}  // namespace
+
+namespace {
+
+// numpy's beta takes Joehnk's algorithm (pow / exp) unless both parameters exceed 1; the samplers have the other branch
+int beta_branch_ok(const zenv_config &cfg)
+{
+    if (!(cfg.beta_a > 1.0) || !(cfg.beta_b > 1.0))
+        return fail(ZENV_E_ARG, "beta_a = %g, beta_b = %g: the deadline draw implements numpy's beta for a > 1 and b > 1 only",
+                    cfg.beta_a, cfg.beta_b);
+    return ZENV_OK;
+}
+
+// zenv_sample_layout's outputs from the shared sampler's host instantiation
+int shared_host_out(const zenv_config &cfg, int64_t seed, double *robot_xyrot, double *zone_xy, int32_t *aux, int32_t *restarts)
+{
+    if (!seed_in_range(seed)) return fail(ZENV_E_ARG, "Seed must be between 0 and 2**32 - 1");
+    Layout L;
+    const int rc = sample_layout_shared_host(cfg, seed, L);
+    if (restarts) *restarts = L.restarts;
+    if (rc) return fail(ZENV_E_LAYOUT, "Failed to sample layout of objects (seed %lld)", (long long)seed);
+    if (robot_xyrot) {
+        robot_xyrot[0] = L.robot_x;
+        robot_xyrot[1] = L.robot_y;
+        robot_xyrot[2] = L.robot_rot;
+    }
+    for (int z = 0; z < cfg.num_zones; ++z) {
+        if (zone_xy) {
+            zone_xy[2 * z] = L.zone_xy[z][0];
+            zone_xy[2 * z + 1] = L.zone_xy[z][1];
+        }
+        if (aux) aux[z] = L.aux[z];
+    }
+    return ZENV_OK;
 }
 
 }  // namespace
@@ -243,29 +304,54 @@ extern "C" int zenv_sample_layout_shared(const zenv_config *cfg, int64_t seed, d
     int rc = validate_config(*cfg);
     if (rc) return rc;
     if (cfg->task == ZENV_TASK_TIMED_TSP)
-        return fail(ZENV_E_ARG, "the shared sampler does not draw TimedTSP deadlines (host libm's log): use zenv_sample_layout");
-    if (!seed_in_range(seed)) return fail(ZENV_E_ARG, "Seed must be between 0 and 2**32 - 1");
-    const SamplerCfg c = make_sampler_cfg(*cfg);
-    HostLanes st;
-    std::memset(st.aux, 0, sizeof(st.aux));
-    double rot = 0.0;
-    int32_t n_restarts = 0;
-    const int code = sample_layout_shared(c, cfg->task == ZENV_TASK_COLOUR_MATCH, (uint32_t)seed, kSamplerHostAttempts, st,
-                                          rot, n_restarts);
-    if (restarts) *restarts = n_restarts;
-    if (code != SAMPLE_OK) return fail(ZENV_E_LAYOUT, "Failed to sample layout of objects (seed %lld)", (long long)seed);
-    if (robot_xyrot) {
-        robot_xyrot[0] = st.x[0];
-        robot_xyrot[1] = st.y[0];
-        robot_xyrot[2] = rot;
+        return fail(ZENV_E_ARG, "the shared sampler does not draw TimedTSP deadlines (host libm's log): use zenv_sample_layout, "
+                                "or zenv_sample_layout_timed for the shared det_log's deadlines");
+    return shared_host_out(*cfg, seed, robot_xyrot, zone_xy, aux, restarts);
+}
+
+extern "C" int zenv_sample_layout_timed(const zenv_config *cfg, int64_t seed, double *robot_xyrot, double *zone_xy,
+                                        int32_t *aux, int32_t *restarts)
+{
+    if (!cfg) return fail(ZENV_E_ARG, "null config");
+    int rc = validate_config(*cfg);
+    if (rc) return rc;
+    if (cfg->task != ZENV_TASK_TIMED_TSP) return fail(ZENV_E_ARG, "zenv_sample_layout_timed samples TimedTSP configs");
+    rc = beta_branch_ok(*cfg);
+    if (rc) return rc;
+    return shared_host_out(*cfg, seed, robot_xyrot, zone_xy, aux, restarts);
+}
+
+extern "C" int zenv_timed_layouts_device(zenv_t *h, int enable)
+{
+    if (!h) return fail(ZENV_E_ARG, "null handle");
+    if (h->cfg.task != ZENV_TASK_TIMED_TSP)
+        return fail(ZENV_E_ARG, "zenv_timed_layouts_device is for TimedTSP handles: the other tasks' layouts need no switch");
+    int rc = beta_branch_ok(h->cfg);
+    if (rc) return rc;
+    h->ls.timed_device = enable != 0;
+    return ZENV_OK;
+}
+
+extern "C" int zenv_det_ops(int op, const double *a, const double *b, double *out, int n, int on_device)
+{
+    if (op != DET_OP_LOG && op != DET_OP_DIV && op != DET_OP_SQRT) return fail(ZENV_E_ARG, "unknown det op %d", op);
+    if (n < 0) return fail(ZENV_E_ARG, "n must be >= 0");
+    if (n == 0) return ZENV_OK;
+    if (!a || !out || (op == DET_OP_DIV && !b)) return fail(ZENV_E_ARG, "null argument");
+    if (!on_device) {
+        for (int i = 0; i < n; ++i)
+            out[i] = op == DET_OP_LOG ? det_log(a[i]) : op == DET_OP_DIV ? det_div(a[i], b[i]) : det_sqrt(a[i]);
+        return ZENV_OK;
     }
-    for (int z = 0; z < cfg->num_zones; ++z) {
-        if (zone_xy) {
-            zone_xy[2 * z] = st.x[z + 1];
-            zone_xy[2 * z + 1] = st.y[z + 1];
-        }
-        if (aux) aux[z] = st.aux[z];
-    }
+    const size_t bytes = (size_t)n * sizeof(double);
+    double *d = nullptr;                                 // [a | b | out]
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), 3 * bytes));
+    hipError_t err = hipMemcpy(d, a, bytes, hipMemcpyHostToDevice);
+    if (err == hipSuccess && op == DET_OP_DIV) err = hipMemcpy(d + n, b, bytes, hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = launch_det_ops(op, d, d + n, d + 2 * (size_t)n, n, nullptr);
+    if (err == hipSuccess) err = hipMemcpy(out, d + 2 * (size_t)n, bytes, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (err != hipSuccess) return fail(ZENV_E_HIP, "zenv_det_ops: %s", hipGetErrorString(err));
     return ZENV_OK;
 }
 

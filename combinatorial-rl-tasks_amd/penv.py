@@ -8,6 +8,8 @@ it, and each env keeps its own FixedSeedsWrapper seed stream (wrappers.py:10-23)
 ``reset/step/step_no_reset`` return exactly the reference's shapes; ``step_arrays`` returns the
 struct-of-arrays results without building P Python dicts.
 """
+import functools
+
 import numpy as np
 
 from . import _native as nat
@@ -29,12 +31,27 @@ def _unwrap(env):
     return chain, fixed
 
 
+def _takes_device_deadlines(init):
+    """ParallelEnv.__init__'s keyword-only ``device_deadlines``: taken off the call here, so the constructor's own
+    parameter list stays the reference's plus ``device_layouts``."""
+    @functools.wraps(init)
+    def wrapper(self, *args, device_deadlines=False, **kwargs):
+        self._device_deadlines = bool(device_deadlines)
+        return init(self, *args, **kwargs)
+    return wrapper
+
+
 class ParallelEnv:
     """A batch of zone envs stepped by one MI355X kernel launch."""
 
+    @_takes_device_deadlines
     def __init__(self, envs, device=0, episodes_per_env=_RING_DEPTH, device_layouts=False):
         """device_layouts: sample the maps on the device (TSP / ColourMatch envs; ValueError for TimedTSP and
-        solver-ordered envs, whose maps need the host).  Plain seeded envs then play the same unbounded stream from a
+        solver-ordered envs, whose maps need the host).  TimedTSP envs are taken with the further keyword
+        device_deadlines=True: their deadlines are then drawn on the device through the shared det_log instead of the
+        host libm's log (ZoneVecEnv.timed_layouts_device; numpy's deadlines unless beta * num_steps is within a few ulps
+        of an integer), and the host repairs unfinished slots with the same shared sampler.  device_deadlines without
+        device_layouts, or with envs of another task, is a ValueError.  Plain seeded envs then play the same unbounded stream from a
         ring the device keeps ahead by itself (ZoneVecEnv.ring_stream / ring_refill): no host sampling, no per-env
         counters, the same observations, rewards, dones and infos.  A map the device sampler gives up on (more than
         DEVICE_RESTARTS restarts) is put into its slot by the host sampler before the env can reach it.
@@ -57,12 +74,19 @@ class ParallelEnv:
         self.num_envs = len(envs)
         self._device_layouts = bool(device_layouts)
         self._status_due = False
-        if self._device_layouts and cfg.task == nat.TASK_TIMED_TSP:
-            raise ValueError("device_layouts: TimedTSP deadlines go through the host libm's log; its maps are sampled on the host")
+        if self._device_deadlines and not self._device_layouts:
+            raise ValueError("device_deadlines is an option of device_layouts=True")
+        if self._device_deadlines and cfg.task != nat.TASK_TIMED_TSP:
+            raise ValueError("device_deadlines: only TimedTSP envs have deadlines to draw")
+        if self._device_layouts and cfg.task == nat.TASK_TIMED_TSP and not self._device_deadlines:
+            raise ValueError("device_layouts: TimedTSP deadlines go through the host libm's log; its maps are sampled on the host "
+                             "(device_deadlines=True draws them on the device through the shared det_log)")
         if self._device_layouts and any(isinstance(b, TSPOrderEnv) for b in bases):
             raise ValueError("device_layouts: solver-ordered maps carry the host solver's route; they are sampled on the host")
         self._vec = ZoneVecEnv(cfg, self.num_envs, device=device)
         self._vec.host_io("if small")     # 16 procs: the kernel writes the results into host memory itself, no copies
+        if self._device_deadlines:
+            self._vec.timed_layouts_device(True)
         # solver-ordered envs (TSP_order_env.py; zone-goals' TSPOrderTestEnv): routes ride in the bank, so before it
         self._order = all(isinstance(b, TSPOrderEnv) for b in bases)
         if not self._order and any(isinstance(b, TSPOrderEnv) for b in bases):

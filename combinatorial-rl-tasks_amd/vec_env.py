@@ -259,6 +259,41 @@ def sample_layout_shared(cfg, seed):
     return robot, zones, aux, restarts.value
 
 
+def sample_layout_timed(cfg, seed):
+    """``sample_layout`` of a TimedTSP config through the shared sampler (zenv_sample_layout_timed): the layout the
+    device samples once ``ZoneVecEnv.timed_layouts_device()`` is on, bit for bit, without a GPU.  The deadlines go through
+    the shared ``det_log`` instead of libm's ``log``: numpy's deadlines wherever ``beta * num_steps`` is not within a few
+    ulps of an integer."""
+    Z = cfg.num_zones
+    robot = np.zeros(3, np.float64)
+    zones = np.zeros((Z, 2), np.float64)
+    aux = np.zeros(Z, np.int32)
+    restarts = C.c_int32(0)
+    check(lib().zenv_sample_layout_timed(C.byref(cfg), int(seed), robot.ctypes.data, zones.ctypes.data,
+                                         aux.ctypes.data, C.byref(restarts)))
+    return robot, zones, aux, restarts.value
+
+
+_DET_OPS = {"log": nat.DET_OP_LOG, "div": nat.DET_OP_DIV, "sqrt": nat.DET_OP_SQRT}
+
+
+def det_ops(op, a, b=None, on_device=False):
+    """Elementwise ``det_log(a)`` / ``det_div(a, b)`` / ``det_sqrt(a)`` of csrc/det_log.hpp (zenv_det_ops; op "log",
+    "div", "sqrt" or a DET_OP_* code), as the host compiles them or, with on_device, as gfx950 does (needs a GPU).
+    A test hook: the two must agree bit for bit."""
+    code = _DET_OPS.get(op, op)
+    x = np.ascontiguousarray(a, np.float64).reshape(-1)
+    y = None
+    if code == nat.DET_OP_DIV:
+        if b is None:
+            raise ValueError("det_ops('div') takes two operands")
+        y = np.ascontiguousarray(np.broadcast_to(np.asarray(b, np.float64).reshape(-1), x.shape))
+    out = np.empty_like(x)
+    check(lib().zenv_det_ops(int(code), x.ctypes.data, None if y is None else y.ctypes.data, out.ctypes.data, x.size,
+                             int(bool(on_device))))
+    return out.reshape(np.shape(a))
+
+
 def layout_thresholds(cfg):
     """The keepout test's two right-hand sides A (a zone against the robot, a zone against a zone) and for each the
     threshold T with ``sqrt(s) < A  <=>  s < T`` that the shared sampler compares d^2 with (zenv_layout_thresholds).
@@ -376,7 +411,17 @@ class ZoneVecEnv:
         check(lib().zenv_bank_update(self._h, sl.ctypes.data, sd.ctypes.data, sl.size, int(n_threads)))
 
     # ---- layouts sampled on the device (K20): only seeds cross the bus.  TSP / ColourMatch handles; TimedTSP and
-    # solver-ordered handles raise ZenvError(E_STATE) and stay on the host calls above
+    # solver-ordered handles raise ZenvError(E_STATE) and stay on the host calls above -- a TimedTSP handle until
+    # timed_layouts_device() opts in
+    def timed_layouts_device(self, enable=True):
+        """Let the device-sampling calls below take this TimedTSP handle (zenv_timed_layouts_device): its bank is then
+        ``sample_layout_timed``'s, deadlines through the shared det_log, and ``update_bank`` refills with that sampler
+        too.  ZenvError(E_ARG) on another task's handle or unless beta_a > 1 and beta_b > 1."""
+        check(lib().zenv_timed_layouts_device(self._h, int(bool(enable))))
+
+    sample_layout_timed = staticmethod(sample_layout_timed)
+    det_ops = staticmethod(det_ops)
+
     def build_bank_device(self, seed_first, count):
         """``build_bank`` sampled on the device (zenv_bank_build_device; synchronous, same bank bit for bit)."""
         check(lib().zenv_bank_build_device(self._h, int(seed_first), int(count)))

@@ -97,10 +97,16 @@ def ppo_update(model, opt, exps, epochs, batch_size, clip_eps, entropy_coef, val
 
 def train(env_id="PointTSP-v0", procs=4096, frames_per_proc=64, updates=10, epochs=4, batch_size=16384, lr=3e-4,
           discount=0.99, gae_lambda=0.95, clip_eps=0.2, entropy_coef=0.003, value_loss_coef=0.5, max_grad_norm=0.5,
-          hidden=185, seed=1, log=print, device_update=False, fresh_layouts=False):
+          hidden=185, seed=1, log=print, device_update=False, fresh_layouts=False, device_deadlines=False):
     torch.manual_seed(seed)
     dev = torch.device("cuda", 0)
     env = Z.ZoneVecEnv(env_id, procs)
+    if device_deadlines:
+        # TimedTSP env ids: the deadlines are drawn on the device too, through the shared det_log (numpy's deadlines
+        # unless beta * num_steps is within a few ulps of an integer); without it ring_stream refuses the handle
+        if not fresh_layouts:
+            raise ValueError("--device-deadlines is an option of --fresh-layouts")
+        env.timed_layouts_device()
     if fresh_layouts:
         # a fresh map at every reset, as the reference's training envs draw them: env i's k-th episode is the layout of
         # seed `seed + i * 2^20 + k`, sampled on the device into a ring of frames_per_proc maps per env (a collection
@@ -168,6 +174,9 @@ if __name__ == "__main__":
     ap.add_argument("--fresh-layouts", action="store_true",
                     help="a fresh map at every reset, sampled on the device (ring_stream, depth = frames per proc; "
                          "588 B per slot at 25 zones)")
+    ap.add_argument("--device-deadlines", action="store_true",
+                    help="with --fresh-layouts on a TimedTSP env id (PointTTSP-v0, -v1): draw the deadlines on the device "
+                         "as well, through the shared deterministic log")
     a = ap.parse_args()
     train(a.env, a.procs, a.frames_per_proc, a.updates, a.epochs, a.batch_size, a.lr, hidden=a.hidden_size, seed=a.seed,
-          device_update=a.device_update, fresh_layouts=a.fresh_layouts)
+          device_update=a.device_update, fresh_layouts=a.fresh_layouts, device_deadlines=a.device_deadlines)

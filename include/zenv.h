@@ -340,7 +340,8 @@ int zenv_bank_update(zenv_t *h, const int32_t *slots, const int64_t *seeds, int 
  * Every device-sampling call (zenv_bank_build_device, _build_seeds_device, zenv_bank_update_device, zenv_ring_stream,
  * zenv_ring_refill) answers ZENV_E_STATE on a TimedTSP handle -- its deadlines are int(beta * num_steps) with beta
  * through the host libm's log, which the device's math library does not reproduce bit for bit -- and on a
- * solver-ordered handle, whose bank rows need zenv_route_ranks.  Both stay on the host path. */
+ * solver-ordered handle, whose bank rows need zenv_route_ranks.  Both stay on the host path -- unless a TimedTSP
+ * handle opts in with zenv_timed_layouts_device (below). */
 #define ZENV_DEVICE_RESTARTS 256
 #define ZENV_SAMPLE_STATUS_CAP 1024
 enum { ZENV_SAMPLE_UNFINISHED = 1, ZENV_SAMPLE_SEED_RANGE = 2 };
@@ -348,6 +349,27 @@ enum { ZENV_SAMPLE_UNFINISHED = 1, ZENV_SAMPLE_SEED_RANGE = 2 };
  * usable without a GPU.  TimedTSP configs: ZENV_E_ARG. */
 int zenv_sample_layout_shared(const zenv_config *cfg, int64_t seed, double *robot_xyrot,
                               double *zone_xy, int32_t *aux, int32_t *restarts);
+/* ---- TimedTSP layouts on the device: an opt-in ----
+ * The shared source draws the deadlines int(beta(beta_a, beta_b) * num_steps) through csrc/det_log.hpp: a faithfully
+ * rounded log (error below 1 ulp) written once for x86 and gfx950, and IEEE division and square root.  Host and device
+ * instantiations agree bit for bit; against numpy's stream (the host libm's log) a deadline can differ by one step where
+ * beta * num_steps lands within a few ulps of an integer -- none does over the seeds the tests pin.  A caller who needs
+ * numpy's stream by definition keeps zenv_sample_layout / zenv_bank_build*.
+ *
+ * zenv_sample_layout_timed: zenv_sample_layout_shared for TimedTSP configs (same arguments and seed rules; usable
+ * without a GPU).  ZENV_E_ARG for another task, and unless beta_a > 1 and beta_b > 1 (numpy's other branch, Joehnk's
+ * algorithm, is not implemented by either sampler). */
+int zenv_sample_layout_timed(const zenv_config *cfg, int64_t seed, double *robot_xyrot,
+                             double *zone_xy, int32_t *aux, int32_t *restarts);
+/* While enabled, the five device-sampling calls accept this TimedTSP handle (goal-conditioned ones included): its bank is
+ * then defined by zenv_sample_layout_timed.  What the device gives up on is finished by that sampler's host instantiation,
+ * and zenv_bank_update on the handle samples with it too, so a bank never mixes the two definitions.  ZENV_E_ARG on a
+ * handle of another task, and unless beta_a > 1 and beta_b > 1. */
+int zenv_timed_layouts_device(zenv_t *h, int enable);
+/* Test hook: out[i] = det_log(a[i]) / det_div(a[i], b[i]) / det_sqrt(a[i]) (host arrays of n; b only for ZENV_DET_OP_DIV),
+ * computed by the host's compilation of csrc/det_log.hpp or, with on_device != 0, by the device's (needs a GPU). */
+enum { ZENV_DET_OP_LOG = 0, ZENV_DET_OP_DIV = 1, ZENV_DET_OP_SQRT = 2 };
+int zenv_det_ops(int op, const double *a, const double *b, double *out, int n, int on_device);
 /* The keepout test of the shared source compares d^2 with a threshold instead of sqrt(d^2) with a distance.  rhs[2],
  * thr[2]: the two right-hand sides A a config has ([0] a zone against the robot, (robot_keepout + placements_margin) +
  * zones_keepout; [1] a zone against a zone) and for each the double T with  sqrt(s) < A <=> s < T.  Host only. */

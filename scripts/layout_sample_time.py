@@ -1,8 +1,10 @@
 """Layouts sampled on the device (K20, layout_sample.hip) beside the unchanged host path, same box, same run.
 
-    python scripts/layout_sample_time.py [--quick] [--slots S] [--depth D] [--out profiles/layout_sample.json]
+    python scripts/layout_sample_time.py [--quick] [--slots S] [--depth D] [--only CONFIG] [--out profiles/layout_sample.json]
 
-For PointTSP-v0, ColourMatch-v0 and 25 zones at keepout 0.40, S = 65 536 layouts.  After one warm-up of every path the
+For PointTSP-v0, ColourMatch-v0, 25 zones at keepout 0.40 and PointTTSP-v0 (its handles switched to device-drawn
+deadlines, timed_layouts_device; the host paths beside them stay the unchanged libm sampler, update_bank on a handle of
+its own without the switch), S = 65 536 layouts.  --only CONFIG times one row and keeps the others of an existing --out file.  After one warm-up of every path the
 paths are timed in turn, REPEATS rounds (>= 5), every timed call ending in a synchronise; the median is reported with
 min .. max:
 
@@ -53,12 +55,27 @@ def main():
     calls = 4 if QUICK else 20
     out_path = arg("--out", os.path.join(ROOT, "profiles", "layout_sample.json"), str)
     configs = {"PointTSP-v0": Z.config_for_id("PointTSP-v0"), "ColourMatch-v0": Z.config_for_id("ColourMatch-v0"),
-               "z25k40": Z.default_config(0, 25, zones_keepout=0.40)}
+               "z25k40": Z.default_config(0, 25, zones_keepout=0.40), "PointTTSP-v0": Z.config_for_id("PointTTSP-v0")}
     result = dict(slots=S, depth=depth, repeats=repeats, host_threads=16, quick=QUICK, configs={})
+    only = arg("--only", None, str)
+    if only is not None:
+        configs = {only: configs[only]}
+        if os.path.exists(out_path):
+            with open(out_path) as f:
+                old = json.load(f)
+            if all(old.get(k) == result[k] for k in ("slots", "depth", "quick")):
+                result["configs"] = old["configs"]
+
+    def handle(cfg, n):
+        env = Z.ZoneVecEnv(cfg, n)
+        if cfg.task == Z.TASK_TIMED_TSP:
+            env.timed_layouts_device()
+        return env
     for name, cfg in configs.items():
         row = {}
+        timed_task = cfg.task == Z.TASK_TIMED_TSP
         # ---- build
-        env = Z.ZoneVecEnv(cfg, 64)
+        env = handle(cfg, 64)
         seeds = np.arange(1, S + 1, dtype=np.int64)
         paths = {"host": lambda: env.build_bank_seeds(seeds, n_threads=16), "device": lambda: env.build_bank_seeds_device(seeds)}
         for fn in paths.values():
@@ -70,15 +87,19 @@ def main():
         row["build"] = {k: summary(v) for k, v in ms.items()}
         env.close()
         # ---- refill: one handle of S envs, a streamed ring of depth 1 = S slots
-        env = Z.ZoneVecEnv(cfg, S)
+        env = handle(cfg, S)
         env.ring_stream(np.arange(S, dtype=np.int64) * 1000 + 1, 1)
         slots = np.arange(S, dtype=np.int32)
+        host = env
+        if timed_task:       # update_bank on a switched handle samples with the shared sampler: time the unchanged one
+            host = Z.ZoneVecEnv(cfg, 64)
+            host.build_bank_seeds(np.arange(1, S + 1, dtype=np.int64), n_threads=16)
         state = dict(base=10 ** 8)
 
         def fresh():
             state["base"] += S
             return state["base"] + np.arange(S, dtype=np.int64)
-        paths = {"update_bank": lambda: env.update_bank(slots, fresh(), n_threads=16),
+        paths = {"update_bank": lambda: (host.update_bank(slots, fresh(), n_threads=16), host.sync()),
                  "update_bank_device": lambda: env.update_bank_device(slots, fresh()),
                  "ring_refill_all_stale": env.ring_refill,          # the updates before it left no slot on its ring seed
                  "ring_refill_none_stale": env.ring_refill}
@@ -96,13 +117,15 @@ def main():
         row["refill_layouts_sampled_on_device"] = {k: sorted({n for kk, n, _ in sampled if kk == k}) for k in paths}
         row["refill_unfinished"] = max(f for _, _, f in sampled)
         env.close()
+        if host is not env:
+            host.close()
         # ---- rollout: env-steps/s of `calls` calls of `depth` steps
         rates = {"sequential_bank": [], "streamed_ring": []}
         envs = {}
         envs["sequential_bank"] = e = Z.ZoneVecEnv(cfg, S)
         e.build_bank(1, 4096, n_threads=16)
         e.schedule_sequential()
-        envs["streamed_ring"] = e = Z.ZoneVecEnv(cfg, S)
+        envs["streamed_ring"] = e = handle(cfg, S)
         e.ring_stream(np.arange(S, dtype=np.int64) * 1000 + 1, depth)
 
         def run(k):
