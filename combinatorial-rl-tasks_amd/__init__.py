@@ -32,7 +32,7 @@ from ._native import (Config, ZenvError, E_ARG, E_HIP, E_STATE, E_LAYOUT, E_DONE
                       SAMPLE_UNFINISHED, SAMPLE_SEED_RANGE, DET_OP_LOG, DET_OP_DIV, DET_OP_SQRT)
 from .vec_env import (ZoneVecEnv, config_for_id, default_config, sample_layout, sample_layout_shared,
                       layout_thresholds, sample_layout_timed, det_ops,
-                      fixed_seed_sequence, route_ranks, zone_feat, hier_tensors_from_state_dicts,
+                      fixed_seed_sequence, route_ranks, route_ranks_shared, zone_feat, hier_tensors_from_state_dicts,
                       hier_experience_layout, check_collect_hier_args, skill_tensors_from_state_dicts,
                       inverse_tensors_from_state_dict, skill_experience_layout, check_collect_skill_args,
                       skill_num_frames, option_tensor_shapes, option_tensors_from_state_dicts,

@@ -254,6 +254,9 @@ _PROTOTYPES = {
     "zenv_order_enable": (C.c_int, [_H]),
     "zenv_order_configure": (C.c_int, [_H, C.c_int]),
     "zenv_route_ranks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "zenv_route_ranks_shared": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "zenv_route_ranks_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "zenv_order_routes_device": (C.c_int, [_H, C.c_int]),
     "zenv_goal_enable": (C.c_int, [_H]),
     "zenv_set_goals": (C.c_int, [_H, C.c_void_p]),
     "zenv_solver_goals": (C.c_int, [_H, C.c_void_p]),

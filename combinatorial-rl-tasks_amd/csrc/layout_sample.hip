@@ -8,9 +8,18 @@
 // wave-uniform throughout: rejection loops of different seeds never share a wave, so they do not diverge.
 // TimedTSP: every lane evaluates the same serial deadline draw (beta -> gamma -> gauss, det_log.hpp), lane z + 1 keeps
 // zone z's deadline.
+//
+// K21: the solver-ordered handles' tour (route_solver.hpp, the host's route_ranks bit for bit) by one wave64 per layout.
+// The int64 cost matrix (row stride route_stride(n): odd, a column read is conflict-free), the nodes' coordinates and
+// the tour live in dynamic LDS sized by the layout's zone count (2 496 B at 15 zones, 9 372 B at 32), so a 15-zone
+// bank still runs 32 waves per CU.  A scan evaluates 64 candidates of the host's order per step, one per lane; a ballot
+// and its lowest set bit pick the host's move; the lanes permute the tour together.  Reached two ways: the ORDER
+// instantiation of k_layout_sample (the wave that sampled a layout solves it and writes the ranks as the bank's aux
+// column) and k_route_ranks over caller-supplied layouts.
 #include <hip/hip_runtime.h>
 
 #include "layout_sample.hpp"
+#include "route_solver.hpp"
 
 namespace zenvk {
 namespace {
@@ -42,9 +51,48 @@ struct WaveLanes {
 };
 static_assert(ZENV_MAX_ZONES + 1 <= kWave, "one lane per placed object");
 
-template <int TASK>
+// The route solver's wave: [cost int64 n x stride | x double n | y double n | tour int32 n] in dynamic LDS
+// (route_lds_bytes), the ranks straight into global memory.
+struct WaveRouteLanes {
+    static constexpr int kLanes = kWave;
+    int64_t *cost;
+    double *xs, *ys;
+    int32_t *tr;
+    int32_t *rank;     // global: this layout's [Z] ranks
+    int stride, ln;
+    int32_t held;      // a permutation's staged value: tour position `ln`
+    bool held_live;
+    __device__ __forceinline__ WaveRouteLanes(int64_t *lds, int n, int lane, int32_t *rank_out)
+        : cost(lds), xs(reinterpret_cast<double *>(lds + n * route_stride(n))), ys(xs + n),
+          tr(reinterpret_cast<int32_t *>(ys + n)), rank(rank_out), stride(route_stride(n)), ln(lane), held(0), held_live(false)
+    {
+    }
+    __device__ __forceinline__ int lane() const { return ln; }
+    __device__ __forceinline__ void sync() { __syncthreads(); }
+    __device__ __forceinline__ uint64_t ballot(bool b) const { return __builtin_amdgcn_ballot_w64(b); }
+    __device__ __forceinline__ double x(int a) const { return xs[a]; }
+    __device__ __forceinline__ double y(int a) const { return ys[a]; }
+    __device__ __forceinline__ int64_t d(int a, int b) const { return cost[a * stride + b]; }
+    __device__ __forceinline__ void set_d(int a, int b, int64_t v) { cost[a * stride + b] = v; }
+    __device__ __forceinline__ int tour(int i) const { return tr[i]; }
+    __device__ __forceinline__ void set_tour(int i, int v) { tr[i] = v; }
+    __device__ __forceinline__ void stage(int, int v, bool live) { held = v; held_live = live; }   // kLanes >= n: k == ln
+    __device__ __forceinline__ void commit(int) { if (held_live) tr[ln] = held; }
+    __device__ __forceinline__ void set_rank(int z, int v) { rank[z] = v; }
+    __device__ __forceinline__ void set_xy(int a, double xx, double yy) { xs[a] = xx; ys[a] = yy; }
+};
+static_assert(kRouteMaxNodes <= kWave, "a permutation is one position per lane");
+
+__device__ __forceinline__ int64_t *route_lds()
+{
+    extern __shared__ int64_t route_lds_mem[];
+    return route_lds_mem;
+}
+
+template <int TASK, bool ORDER = false>
 __global__ __launch_bounds__(kWave) void k_layout_sample(LayoutSampleArgs a)
 {
+    static_assert(!ORDER || TASK == ZENV_TASK_TSP, "the solver-ordered variant is a PointTSP variant");
     __shared__ uint32_t mt[624];
     const int lane = threadIdx.x, Z = a.c.Z;
     const uint32_t n = a.count_dev ? *a.count_dev : (uint32_t)a.count;
@@ -75,7 +123,15 @@ __global__ __launch_bounds__(kWave) void k_layout_sample(LayoutSampleArgs a)
             } else if (lane <= Z) {
                 const size_t bi = (size_t)slot * Z + (lane - 1);
                 reinterpret_cast<double2 *>(a.bank_zone)[bi] = make_double2(st.x, st.y);
-                a.bank_aux[bi] = st.aux;
+                if constexpr (!ORDER) a.bank_aux[bi] = st.aux;
+            }
+            if constexpr (ORDER) {
+                // lane j holds node j's centre: the aux column is the tour's ranks (TSP_order_env.py:49-50)
+                WaveRouteLanes rt(route_lds(), Z + 1, lane, a.bank_aux + (size_t)slot * Z);
+                if (lane <= Z) rt.set_xy(lane, st.x, st.y);
+                rt.sync();
+                int32_t moves[ROUTE_N_OPS];
+                route_solve_shared(Z, rt, moves);
             }
             written++;
         } else if (lane == 0) {
@@ -112,6 +168,25 @@ __global__ __launch_bounds__(256) void k_ring_stale(DevParams p, const int64_t *
     }
 }
 
+// K21 over caller-supplied layouts: robot [count][2], zones [count][Z][2] -> rank [count][Z], moves [count][5] (or null)
+__global__ __launch_bounds__(kWave) void k_route_ranks(const double *__restrict__ robot, const double *__restrict__ zones,
+                                                       int count, int Z, int32_t *__restrict__ rank,
+                                                       int32_t *__restrict__ moves_out)
+{
+    const int lane = threadIdx.x;
+    for (int e = blockIdx.x; e < count; e += gridDim.x) {
+        WaveRouteLanes rt(route_lds(), Z + 1, lane, rank + (size_t)e * Z);
+        if (lane == 0) rt.set_xy(0, robot[2 * (size_t)e], robot[2 * (size_t)e + 1]);
+        else if (lane <= Z) rt.set_xy(lane, zones[((size_t)e * Z + (lane - 1)) * 2], zones[((size_t)e * Z + (lane - 1)) * 2 + 1]);
+        rt.sync();
+        int32_t moves[ROUTE_N_OPS];
+        route_solve_shared(Z, rt, moves);
+        if (moves_out && lane == 0)
+            for (int k = 0; k < ROUTE_N_OPS; ++k) moves_out[(size_t)e * ROUTE_N_OPS + k] = moves[k];
+        __syncthreads();                                     // the next layout's stores behind this one's loads
+    }
+}
+
 // zenv_det_ops: det_log / det_div / det_sqrt as the device compiles them, one element per thread
 __global__ __launch_bounds__(256) void k_det_ops(int op, const double *__restrict__ a, const double *__restrict__ b,
                                                  double *__restrict__ out, int n)
@@ -130,10 +205,27 @@ hipError_t launch_det_ops(int op, const double *a, const double *b, double *out,
     return hipGetLastError();
 }
 
-hipError_t launch_layout_sample(const LayoutSampleArgs &a, int grid, hipStream_t s)
+size_t route_lds_bytes(int Z)
+{
+    const size_t n = (size_t)Z + 1;
+    return n * route_stride((int)n) * sizeof(int64_t) + 2 * n * sizeof(double) + n * sizeof(int32_t);
+}
+
+hipError_t launch_route_ranks(const double *robot, const double *zones, int count, int Z, int32_t *rank, int32_t *moves,
+                              int grid, hipStream_t s)
+{
+    if (grid < 1 || count < 1) return hipSuccess;
+    hipLaunchKernelGGL(k_route_ranks, dim3(grid), dim3(kWave), route_lds_bytes(Z), s, robot, zones, count, Z, rank, moves);
+    return hipGetLastError();
+}
+
+hipError_t launch_layout_sample(const LayoutSampleArgs &a, int grid, hipStream_t s, bool order)
 {
     if (grid < 1) return hipSuccess;
-    if (a.c.task == ZENV_TASK_COLOUR_MATCH)
+    if (order) {
+        if (a.c.task != ZENV_TASK_TSP) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((k_layout_sample<ZENV_TASK_TSP, true>), dim3(grid), dim3(kWave), route_lds_bytes(a.c.Z), s, a);
+    } else if (a.c.task == ZENV_TASK_COLOUR_MATCH)
         hipLaunchKernelGGL(k_layout_sample<ZENV_TASK_COLOUR_MATCH>, dim3(grid), dim3(kWave), 0, s, a);
     else if (a.c.task == ZENV_TASK_TIMED_TSP)
         hipLaunchKernelGGL(k_layout_sample<ZENV_TASK_TIMED_TSP>, dim3(grid), dim3(kWave), 0, s, a);

@@ -34,8 +34,16 @@ struct LayoutSampleArgs {
     SampleStatus *status;
 };
 
-// One wave per entry, grid-stride over the list: `grid` blocks of 64 threads.
-hipError_t launch_layout_sample(const LayoutSampleArgs &a, int grid, hipStream_t s);
+// One wave per entry, grid-stride over the list: `grid` blocks of 64 threads.  order (TSP configs): the ORDER
+// instantiation -- the wave that sampled a layout also solves its tour (K21, route_solver.hpp) and the aux column it
+// writes is the tour's ranks.
+hipError_t launch_layout_sample(const LayoutSampleArgs &a, int grid, hipStream_t s, bool order = false);
+
+// K21 over caller-supplied layouts (device pointers): robot [count][2], zones [count][Z][2] -> rank [count][Z] and, unless
+// null, moves [count][5] (accepted moves per operator: or-opt 1, 2, 3, exchange, 2-opt).  One wave per layout,
+// grid-stride; 1 <= Z <= ZENV_MAX_ZONES, every coordinate finite and within +-1e9 (the caller checks).
+hipError_t launch_route_ranks(const double *robot, const double *zones, int count, int Z, int32_t *rank, int32_t *moves,
+                              int grid, hipStream_t s);
 
 // zenv_det_ops on the device: out[i] = det_log(a[i]) / det_div(a[i], b[i]) / det_sqrt(a[i]) (device pointers; b only
 // for DET_OP_DIV), compiled from det_log.hpp as the sampling kernel is.

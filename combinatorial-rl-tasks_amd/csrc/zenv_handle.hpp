@@ -228,6 +228,7 @@ struct zenv {
         int64_t *ring_seed0 = nullptr;
         bool ring_streamed = false;
         bool timed_device = false;           // zenv_timed_layouts_device: TimedTSP layouts with det_log's deadlines
+        bool order_device = false;           // zenv_order_routes_device: solver-ordered rows with the tour solved on the device (K21)
     } ls;
     // the sharded job's communicator (zenv_comm_init): RCCL over xGMI
     ncclComm_t comm = nullptr;

@@ -8,6 +8,7 @@
 
 #include "host_sampler.hpp"
 #include "layout_sample.hpp"
+#include "route_solver.hpp"
 #include "zenv_handle.hpp"
 
 namespace zenvk {
@@ -78,8 +79,41 @@ int device_sampling_allowed(const zenv *h)
         return fail(ZENV_E_STATE, "TimedTSP layouts are sampled on the host: the deadlines are int(beta * num_steps) with beta "
                                   "through the host libm's log, which the device's math library does not reproduce bit for bit "
                                   "(zenv_timed_layouts_device switches the handle to the shared det_log's deadlines)");
-    if (h->order_enabled)
-        return fail(ZENV_E_STATE, "solver-ordered layouts are sampled on the host: their bank rows carry zenv_route_ranks' route");
+    if (h->order_enabled && !h->ls.order_device)
+        return fail(ZENV_E_STATE, "solver-ordered layouts are sampled on the host: their bank rows carry zenv_route_ranks' route "
+                                  "(zenv_order_routes_device lets the device solve that tour for the rows it samples)");
+    return ZENV_OK;
+}
+
+// the ORDER instantiation of the sampling kernel: the handle is solver-ordered and has opted in
+bool device_routes(const zenv *h) { return h->order_enabled && h->ls.order_device; }
+
+// The host instantiation of the shared tour (route_solver.hpp): rank[Z] and, unless null, moves[5].
+void route_ranks_shared_host(const double *robot_xy, const double *zone_xy, int Z, int32_t *rank, int32_t *moves_or_null)
+{
+    HostRouteLanes rt;
+    rt.n = Z + 1;
+    rt.rank = rank;
+    rt.xs[0] = robot_xy[0];
+    rt.ys[0] = robot_xy[1];
+    for (int z = 0; z < Z; ++z) {
+        rt.xs[z + 1] = zone_xy[2 * z];
+        rt.ys[z + 1] = zone_xy[2 * z + 1];
+    }
+    int32_t moves[ROUTE_N_OPS];
+    route_solve_shared(Z, rt, moves);
+    if (moves_or_null) std::memcpy(moves_or_null, moves, sizeof(moves));
+}
+
+// the argument checks the two new route calls share (count layouts)
+int route_args_ok(const double *robot_xy, const double *zone_xy, int64_t count, int num_zones, const int32_t *rank)
+{
+    if (!robot_xy || !zone_xy || !rank) return fail(ZENV_E_ARG, "null argument");
+    if (num_zones < 1 || num_zones > ZENV_MAX_ZONES) return fail(ZENV_E_ARG, "num_zones outside [1,%d]", ZENV_MAX_ZONES);
+    for (int64_t i = 0; i < count * 2; ++i)
+        if (!route_coord_ok(robot_xy[i])) return fail(ZENV_E_ARG, "robot coordinate %g: not finite or beyond +-1e9", robot_xy[i]);
+    for (int64_t i = 0; i < count * num_zones * 2; ++i)
+        if (!route_coord_ok(zone_xy[i])) return fail(ZENV_E_ARG, "zone coordinate %g: not finite or beyond +-1e9", zone_xy[i]);
     return ZENV_OK;
 }
 
@@ -189,7 +223,7 @@ int build_on_device(zenv *h, const int64_t *seed_list, int count)
         LayoutSampleArgs a = sample_args(h, fresh, (int32_t)S);
         a.count = count;
         a.seeds = h->ls.list_seeds;
-        err = launch_layout_sample(a, std::min(count, kMaxGrid), h->stream);
+        err = launch_layout_sample(a, std::min(count, kMaxGrid), h->stream, device_routes(h));
     }
     if (err != hipSuccess) {
         (void)hipStreamSynchronize(h->stream);
@@ -216,6 +250,11 @@ int build_on_device(zenv *h, const int64_t *seed_list, int count)
         if (h->ls.timed_device ? sample_layout_shared_host(h->cfg, seed_list[slot], L) : sample_layout(h->cfg, seed_list[slot], L)) {
             drop();
             return fail(ZENV_E_LAYOUT, "Failed to sample layout of objects (seed %lld)", (long long)seed_list[slot]);
+        }
+        // a solver-ordered row's aux column is the tour of its layout, not the sampler's (empty) column
+        if (device_routes(h)) {
+            const double robot_xy[2] = { L.robot_x, L.robot_y };
+            route_ranks_shared_host(robot_xy, &L.zone_xy[0][0], (int)Z, L.aux, nullptr);
         }
         double s, c;
         det_sincos(L.robot_rot / 2, s, c);
@@ -332,6 +371,57 @@ extern "C" int zenv_timed_layouts_device(zenv_t *h, int enable)
     return ZENV_OK;
 }
 
+extern "C" int zenv_order_routes_device(zenv_t *h, int enable)
+{
+    if (!h) return fail(ZENV_E_ARG, "null handle");
+    if (!h->order_enabled)
+        return fail(ZENV_E_ARG, "zenv_order_routes_device is for solver-ordered handles (zenv_order_enable): the other "
+                                "handles' layouts need no switch");
+    h->ls.order_device = enable != 0;
+    return ZENV_OK;
+}
+
+extern "C" int zenv_route_ranks_shared(const double *robot_xy, const double *zone_xy, int num_zones, int32_t *rank,
+                                       int32_t *moves_or_null)
+{
+    int rc = route_args_ok(robot_xy, zone_xy, 1, num_zones, rank);
+    if (rc) return rc;
+    route_ranks_shared_host(robot_xy, zone_xy, num_zones, rank, moves_or_null);
+    return ZENV_OK;
+}
+
+extern "C" int zenv_route_ranks_device(zenv_t *h, const double *robot_xy, const double *zone_xy, int count, int num_zones,
+                                       int32_t *rank, int32_t *moves_or_null)
+{
+    if (!h) return fail(ZENV_E_ARG, "null handle");
+    if (count < 0) return fail(ZENV_E_ARG, "count must be >= 0");
+    int rc = route_args_ok(robot_xy, zone_xy, count, num_zones, rank);
+    if (rc) return rc;
+    if (count == 0) return ZENV_OK;
+    rc = use_device(h);
+    if (rc) return rc;
+    // [robot | zones | moves | rank] in one allocation: the doubles first
+    const size_t n = (size_t)count, Z = (size_t)num_zones;
+    const size_t b_robot = n * 2 * sizeof(double), b_zone = n * Z * 2 * sizeof(double);
+    const size_t b_moves = n * ROUTE_N_OPS * sizeof(int32_t), b_rank = n * Z * sizeof(int32_t);
+    char *d = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), b_robot + b_zone + b_moves + b_rank));
+    double *d_robot = reinterpret_cast<double *>(d), *d_zone = reinterpret_cast<double *>(d + b_robot);
+    int32_t *d_moves = reinterpret_cast<int32_t *>(d + b_robot + b_zone), *d_rank = d_moves + n * ROUTE_N_OPS;
+    hipError_t err = hipMemcpyAsync(d_robot, robot_xy, b_robot, hipMemcpyHostToDevice, h->stream);
+    if (err == hipSuccess) err = hipMemcpyAsync(d_zone, zone_xy, b_zone, hipMemcpyHostToDevice, h->stream);
+    if (err == hipSuccess)
+        err = launch_route_ranks(d_robot, d_zone, count, num_zones, d_rank, moves_or_null ? d_moves : nullptr,
+                                 std::min(count, kMaxGrid), h->stream);
+    if (err == hipSuccess) err = hipMemcpyAsync(rank, d_rank, b_rank, hipMemcpyDeviceToHost, h->stream);
+    if (err == hipSuccess && moves_or_null) err = hipMemcpyAsync(moves_or_null, d_moves, b_moves, hipMemcpyDeviceToHost, h->stream);
+    const hipError_t done = hipStreamSynchronize(h->stream);
+    (void)hipFree(d);
+    if (err == hipSuccess) err = done;
+    if (err != hipSuccess) return fail(ZENV_E_HIP, "zenv_route_ranks_device: %s", hipGetErrorString(err));
+    return ZENV_OK;
+}
+
 extern "C" int zenv_det_ops(int op, const double *a, const double *b, double *out, int n, int on_device)
 {
     if (op != DET_OP_LOG && op != DET_OP_DIV && op != DET_OP_SQRT) return fail(ZENV_E_ARG, "unknown det op %d", op);
@@ -414,7 +504,7 @@ extern "C" int zenv_bank_update_device(zenv_t *h, const int32_t *slots, const in
     a.count = count;
     a.slots = h->ls.list_slots;
     a.seeds = h->ls.list_seeds;
-    HIP_TRY(launch_layout_sample(a, std::min(count, kMaxGrid), h->stream));
+    HIP_TRY(launch_layout_sample(a, std::min(count, kMaxGrid), h->stream, device_routes(h)));
     // a slot the sampler left alone derives to the rows it already has
     HIP_TRY(launch_bank_derive(h->p, h->ls.list_slots, count, h->stream));
     return ZENV_OK;
@@ -461,7 +551,7 @@ extern "C" int zenv_ring_refill(zenv_t *h)
     a.count_dev = h->ls.count;
     a.slots = h->ls.list_slots;
     a.seeds = h->ls.list_seeds;
-    HIP_TRY(launch_layout_sample(a, grid, h->stream));
+    HIP_TRY(launch_layout_sample(a, grid, h->stream, device_routes(h)));
     // The derived rows: k_bank_derive takes its slot count from the launch, and how many slots were stale only the
     // device knows, so the pass covers the whole ring bank (rows of untouched slots derive to what they hold).  A
     // variant that walks the device-made list has to sit beside the device functions it shares with the step kernels,

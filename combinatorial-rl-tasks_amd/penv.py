@@ -41,9 +41,19 @@ def _takes_device_deadlines(init):
     return wrapper
 
 
+def _takes_device_routes(init):
+    """ParallelEnv.__init__'s keyword-only ``device_routes``, taken off the call the same way."""
+    @functools.wraps(init)
+    def wrapper(self, *args, device_routes=False, **kwargs):
+        self._device_routes = bool(device_routes)
+        return init(self, *args, **kwargs)
+    return wrapper
+
+
 class ParallelEnv:
     """A batch of zone envs stepped by one MI355X kernel launch."""
 
+    @_takes_device_routes
     @_takes_device_deadlines
     def __init__(self, envs, device=0, episodes_per_env=_RING_DEPTH, device_layouts=False):
         """device_layouts: sample the maps on the device (TSP / ColourMatch envs; ValueError for TimedTSP and
@@ -51,7 +61,11 @@ class ParallelEnv:
         device_deadlines=True: their deadlines are then drawn on the device through the shared det_log instead of the
         host libm's log (ZoneVecEnv.timed_layouts_device; numpy's deadlines unless beta * num_steps is within a few ulps
         of an integer), and the host repairs unfinished slots with the same shared sampler.  device_deadlines without
-        device_layouts, or with envs of another task, is a ValueError.  Plain seeded envs then play the same unbounded stream from a
+        device_layouts, or with envs of another task, is a ValueError.  Solver-ordered envs (TSPOrderEnv) are taken with the
+        further keyword device_routes=True: the wave that samples a map also solves its tour
+        (ZoneVecEnv.order_routes_device; the host's route, bit for bit), and the host repairs unfinished slots with the
+        same tour.  device_routes without device_layouts, or with envs that are not TSPOrderEnv, is a ValueError; a
+        route_fn stays NotImplementedError.  Plain seeded envs then play the same unbounded stream from a
         ring the device keeps ahead by itself (ZoneVecEnv.ring_stream / ring_refill): no host sampling, no per-env
         counters, the same observations, rewards, dones and infos.  A map the device sampler gives up on (more than
         DEVICE_RESTARTS restarts) is put into its slot by the host sampler before the env can reach it.
@@ -81,8 +95,13 @@ class ParallelEnv:
         if self._device_layouts and cfg.task == nat.TASK_TIMED_TSP and not self._device_deadlines:
             raise ValueError("device_layouts: TimedTSP deadlines go through the host libm's log; its maps are sampled on the host "
                              "(device_deadlines=True draws them on the device through the shared det_log)")
-        if self._device_layouts and any(isinstance(b, TSPOrderEnv) for b in bases):
-            raise ValueError("device_layouts: solver-ordered maps carry the host solver's route; they are sampled on the host")
+        if self._device_routes and not self._device_layouts:
+            raise ValueError("device_routes is an option of device_layouts=True")
+        if self._device_routes and not all(isinstance(b, TSPOrderEnv) for b in bases):
+            raise ValueError("device_routes: only solver-ordered envs (TSPOrderEnv) have routes to solve")
+        if self._device_layouts and any(isinstance(b, TSPOrderEnv) for b in bases) and not self._device_routes:
+            raise ValueError("device_layouts: solver-ordered maps carry the host solver's route; they are sampled on the host "
+                             "(device_routes=True solves the same tour on the device)")
         self._vec = ZoneVecEnv(cfg, self.num_envs, device=device)
         self._vec.host_io("if small")     # 16 procs: the kernel writes the results into host memory itself, no copies
         if self._device_deadlines:
@@ -97,6 +116,8 @@ class ParallelEnv:
             if len({b._fresh_first_obs for b in bases}) != 1:
                 raise ValueError("all envs of a ParallelEnv must share fresh_route_in_first_obs")
             self._vec.enable_order(fresh_route_in_first_obs=bases[0]._fresh_first_obs)
+            if self._device_routes:
+                self._vec.order_routes_device(True)
             self._order_shaped = not any(isinstance(b, TSPOrderTestEnv) for b in bases)   # TSP_order_test_env.py:72-74
         if all(f is not None for f in fixed):
             lo, hi = fixed[0].min_seed, fixed[0].max_seed

@@ -316,6 +316,19 @@ def route_ranks(robot_xy, zone_xy):
     return rank
 
 
+def route_ranks_shared(robot_xy, zone_xy, moves=False):
+    """``route_ranks`` through the source the device solver is compiled from (zenv_route_ranks_shared): the same
+    ranks, element for element, without a GPU.  moves=True: returns (rank, moves[5]) -- the accepted moves per operator
+    (or-opt of chains 1, 2, 3, exchange, 2-opt).  ZenvError(E_ARG) for a non-finite coordinate or one beyond +-1e9."""
+    r = np.ascontiguousarray(robot_xy, np.float64).reshape(-1)[:2].copy()
+    z = np.ascontiguousarray(zone_xy, np.float64).reshape(-1, 2)
+    rank = np.zeros(z.shape[0], np.int32)
+    mv = np.zeros(5, np.int32)
+    check(lib().zenv_route_ranks_shared(r.ctypes.data, z.ctypes.data, z.shape[0], rank.ctypes.data,
+                                        mv.ctypes.data if moves else None))
+    return (rank, mv) if moves else rank
+
+
 def fixed_seed_sequence(rng_seed, min_seed, max_seed, count):
     """Seeds FixedSeedsWrapper.reset (wrappers.py:20-23) would draw, without numpy's Generator."""
     out = np.zeros(count, np.int64)
@@ -412,7 +425,7 @@ class ZoneVecEnv:
 
     # ---- layouts sampled on the device (K20): only seeds cross the bus.  TSP / ColourMatch handles; TimedTSP and
     # solver-ordered handles raise ZenvError(E_STATE) and stay on the host calls above -- a TimedTSP handle until
-    # timed_layouts_device() opts in
+    # timed_layouts_device() opts in, a solver-ordered one until order_routes_device() does
     def timed_layouts_device(self, enable=True):
         """Let the device-sampling calls below take this TimedTSP handle (zenv_timed_layouts_device): its bank is then
         ``sample_layout_timed``'s, deadlines through the shared det_log, and ``update_bank`` refills with that sampler
@@ -421,6 +434,29 @@ class ZoneVecEnv:
 
     sample_layout_timed = staticmethod(sample_layout_timed)
     det_ops = staticmethod(det_ops)
+
+    def order_routes_device(self, enable=True):
+        """Let the device-sampling calls below take this solver-ordered handle (zenv_order_routes_device): the wave
+        that samples a layout solves its tour (K21) and the row's aux column is ``route_ranks``' -- the same bank as
+        ``build_bank``'s, bit for bit.  A row the device refills always carries the built-in tour, never ranks put
+        there with ``set_bank(aux=...)``.  ZenvError(E_ARG) unless ``enable_order()`` came first."""
+        check(lib().zenv_order_routes_device(self._h, int(bool(enable))))
+
+    def route_ranks_device(self, robot, zones, moves=False):
+        """``route_ranks`` of a batch on the device, one wave per layout (zenv_route_ranks_device; synchronous, any
+        handle): robot (count, 2), zones (count, Z', 2) with any 1 <= Z' <= MAX_ZONES -> rank (count, Z') int32 and,
+        with moves=True, also moves (count, 5)."""
+        z = np.ascontiguousarray(zones, np.float64)
+        if z.ndim != 3 or z.shape[2] != 2:
+            raise ValueError("zones must have shape (count, num_zones, 2)")
+        r = np.ascontiguousarray(np.asarray(robot, np.float64)[..., :2])
+        if r.shape != (z.shape[0], 2):
+            raise ValueError("robot must have shape (count, 2)")
+        rank = np.zeros(z.shape[:2], np.int32)
+        mv = np.zeros((z.shape[0], 5), np.int32)
+        check(lib().zenv_route_ranks_device(self._h, r.ctypes.data, z.ctypes.data, z.shape[0], z.shape[1],
+                                            rank.ctypes.data, mv.ctypes.data if moves else None))
+        return (rank, mv) if moves else rank
 
     def build_bank_device(self, seed_first, count):
         """``build_bank`` sampled on the device (zenv_bank_build_device; synchronous, same bank bit for bit)."""

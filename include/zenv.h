@@ -341,7 +341,7 @@ int zenv_bank_update(zenv_t *h, const int32_t *slots, const int64_t *seeds, int 
  * zenv_ring_refill) answers ZENV_E_STATE on a TimedTSP handle -- its deadlines are int(beta * num_steps) with beta
  * through the host libm's log, which the device's math library does not reproduce bit for bit -- and on a
  * solver-ordered handle, whose bank rows need zenv_route_ranks.  Both stay on the host path -- unless a TimedTSP
- * handle opts in with zenv_timed_layouts_device (below). */
+ * handle opts in with zenv_timed_layouts_device (below), or a solver-ordered one with zenv_order_routes_device. */
 #define ZENV_DEVICE_RESTARTS 256
 #define ZENV_SAMPLE_STATUS_CAP 1024
 enum { ZENV_SAMPLE_UNFINISHED = 1, ZENV_SAMPLE_SEED_RANGE = 2 };
@@ -526,6 +526,34 @@ int zenv_order_configure(zenv_t *h, int flags);
  * cost int64(10 x distance), first solution PATH_CHEAPEST_ARC, greedy-descent local search (relocate, exchange, 2-opt,
  * or-opt) to a local optimum -- solved without the library: the same kind of tour, not its bit-exact route. */
 int zenv_route_ranks(const double *robot_xy, const double *zone_xy, int num_zones, int32_t *rank);
+/* ---- the tour on the device (K21) ----
+ * zenv_route_ranks' tour -- the problem of TSP_Solver.get_optim_route (main/src/utils/TSP_Solver.py:24-62) that
+ * TSPOrderEnv.generate_route asks for at main/envs/TSP_order_env.py:49-50 -- written once for the host and for gfx950
+ * (csrc/route_solver.hpp): int64 arc costs from IEEE float64 arithmetic and a correctly rounded square root, integer
+ * comparisons after that, and a first-improvement search whose scans evaluate 64 candidates of the host's order at a
+ * time and take the first that improves.  Both instantiations give zenv_route_ranks' ranks, element for element.
+ *
+ * zenv_route_ranks_shared: the host instantiation, usable without a GPU (TSP_Solver.py:24-62, TSP_order_env.py:49-50).
+ * robot_xy[2], zone_xy[num_zones][2] -> rank[num_zones]; moves_or_null[5]: the accepted moves per operator (or-opt of
+ * chains 1, 2, 3, exchange, 2-opt).  ZENV_E_ARG for a null pointer, num_zones outside [1, ZENV_MAX_ZONES], a
+ * non-finite coordinate or one beyond +-1e9 (inside that box the cast of 10 x distance to int64 is defined). */
+int zenv_route_ranks_shared(const double *robot_xy, const double *zone_xy, int num_zones, int32_t *rank,
+                            int32_t *moves_or_null);
+/* The same tour of `count` layouts on the device, one wave64 per layout (TSP_Solver.py:24-62, TSP_order_env.py:49-50):
+ * robot_xy[count][2], zone_xy[count][num_zones][2] -> rank[count][num_zones], moves_or_null[count][5], all host
+ * pointers.  Synchronous, on the handle's stream; any handle, and num_zones is independent of the handle's.  The
+ * argument checks are zenv_route_ranks_shared's; count < 0 is ZENV_E_ARG, count == 0 does nothing. */
+int zenv_route_ranks_device(zenv_t *h, const double *robot_xy, const double *zone_xy, int count, int num_zones,
+                            int32_t *rank, int32_t *moves_or_null);
+/* While enabled, the five device-sampling calls (zenv_bank_build_device, zenv_bank_build_seeds_device,
+ * zenv_bank_update_device, zenv_ring_stream, zenv_ring_refill) accept this solver-ordered handle: the wave that
+ * samples a layout solves its tour (TSP_Solver.py:24-62, TSP_order_env.py:49-50) and writes the ranks as the row's aux
+ * column; a slot the device gives up on gets the host sampler's layout and the shared tour's host instantiation.
+ * Unlike zenv_timed_layouts_device the switch changes no value -- the rows equal zenv_bank_build's bit for bit.  It
+ * exists because a row the device (re)fills always carries the built-in tour, never ranks a caller put there with
+ * zenv_bank_set: a handle whose routes come from another solver must stay off.  ZENV_E_ARG on a handle that is not
+ * solver-ordered (zenv_order_enable first). */
+int zenv_order_routes_device(zenv_t *h, int enable);
 
 /* ---- the reference's actor network on the device ----
  * ZoneEnvModel (main/src/env_model.py:48-79) + the actor of ACModel (flat_model.py:24-37,
