@@ -5,6 +5,7 @@ host-built bank plays."""
 import numpy as np
 import pytest
 
+from tests.layout_scale_cases import PASSES3
 from tests.route_layouts import CRAFTED_Z, crafted, sampled
 
 pytestmark = pytest.mark.gpu
@@ -63,6 +64,11 @@ def test_batch_call_on_sampled_layouts(zenv_mod, solver, sampled_layouts, nz):
         assert np.array_equal(rank, want_rank[:count]), (nz, count)
         assert np.array_equal(moves, want_moves[:count]), (nz, count)
         assert np.array_equal(solver.route_ranks_device(robot[:count], zones[:count]), rank)      # moves are optional
+    # tiled past two grids: every block's wave solves a second layout in the LDS of its first, block 0's a third
+    idx = np.arange(PASSES3) % len(robot)
+    rank, moves = solver.route_ranks_device(robot[idx], zones[idx], moves=True)
+    assert np.array_equal(rank, want_rank[idx]) and np.array_equal(moves, want_moves[idx]), nz
+    assert np.array_equal(solver.route_ranks_device(robot[idx], zones[idx]), rank)                # ... without moves too
     if nz <= 2:
         assert not want_moves.any()
     if nz >= 15:
@@ -76,8 +82,9 @@ def test_batch_call_on_crafted_layouts(zenv_mod, solver, nz):
     robot = np.stack([r for _, r, _ in cases])
     zones = np.stack([z for _, _, z in cases])
     want_rank, want_moves = _host(Z, robot, zones)
-    # tiled to every count, so that each grid size and a second pass of the grid-stride loop see them
-    for count in COUNTS:
+    # tiled to every count, so that each grid size sees them; the grid is min(count, 8192) blocks, so only PASSES3
+    # takes the grid-stride loop round again (twice in block 0, once in every other block)
+    for count in COUNTS + (PASSES3,):
         idx = np.arange(count) % len(cases)
         rank, moves = solver.route_ranks_device(robot[idx], zones[idx], moves=True)
         bad = [cases[i][0] for i in idx[(rank != want_rank[idx]).any(1) | (moves != want_moves[idx]).any(1)]]
