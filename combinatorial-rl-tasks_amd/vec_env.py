@@ -479,7 +479,9 @@ class ZoneVecEnv:
     def ring_stream(self, seed0, depth):
         """Env i's k-th episode is the layout of env seed ``seed0[i] + k``, for ever: a num_envs x depth bank sampled
         on the device, a ring schedule over it (zenv_ring_stream) and ``ring_refill()`` to keep it ahead -- at least
-        once per `depth` episodes of an env.  Memory: 88 + 20 Z bytes per slot (588 B at Z = 25)."""
+        once per `depth` episodes of an env.  An explicit ``reset()`` / ``reset(mask)`` takes a map from the ring like
+        an auto-reset does, and the ring guard does not count it: call ``ring_refill()`` after it too.  Memory: 88 +
+        20 Z bytes per slot (588 B at Z = 25)."""
         s = np.ascontiguousarray(seed0, np.int64)
         if s.shape != (self.num_envs,):
             raise ValueError("seed0 must have shape (num_envs,)")

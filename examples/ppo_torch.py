@@ -119,6 +119,8 @@ def train(env_id="PointTSP-v0", procs=4096, frames_per_proc=64, updates=10, epoc
         env.schedule_sequential(stride=procs)
     tenv = TorchZoneEnv(env)
     tenv.reset()
+    if fresh_layouts:
+        env.ring_refill()                       # the reset took episode 0 of every ring: a map like any other
     model = ActorCritic(env.zone_feat, hidden).to(dev)
     opt = torch.optim.Adam(model.parameters(), lr, eps=1e-8)
     gen = torch.Generator(device=dev).manual_seed(seed)

@@ -386,7 +386,9 @@ int zenv_bank_update_device(zenv_t *h, const int32_t *slots, const int64_t *seed
 /* Engine.reset's unbounded seed stream without the host: builds an N x depth bank on the device (slot i*depth + j <-
  * seed0[i] + j, synchronous like zenv_bank_build_device), lays the ring schedule first[i] = i*depth over it and keeps
  * seed0 [N] on the device.  Episode k of env i is then the layout of env seed seed0[i] + k as long as
- * zenv_ring_refill runs at least once per `depth` episodes of an env (the ring guard of zenv_schedule_ring holds). */
+ * zenv_ring_refill runs at least once per `depth` episodes of an env (the ring guard of zenv_schedule_ring holds).  An
+ * explicit zenv_reset takes a map from the ring as an auto-reset does and the guard does not count it, so refill after
+ * it too. */
 int zenv_ring_stream(zenv_t *h, const int64_t *seed0, int32_t depth);
 /* Bring every ring back ahead of its env: slot first[i] + j must hold episode e_j, the smallest e >= the env's
  * episode index with e mod depth == j; the slots whose seed is not seed0[i] + e_j are listed on the device and sampled by
