@@ -18,8 +18,11 @@ Run (needs the reference tree, by default /root/reference, else $ZENV_REFERENCE)
 
     python tests/golden/make_agent_goldens.py            writes tests/golden/agent_<variant>_<part>.npz
 
-A second run on the same machine gives byte-identical arrays (another CPU or BLAS moves the recorded outputs, and
-the inputs derived from them, by a few ulp).  Not collected by pytest; the tests read only the .npz files.
+One run writes the whole set, and a set is self-consistent: the recorded inputs of the updates are derived from the
+float32 models' own recorded outputs.  Another CPU or BLAS moves the float32 run by float32 ulps -- up to 3e-6 of an
+array's maximum has been seen between two machines -- which is far beyond the 1e-9 float64 bound of the tests.  So sets
+from different machines are never mixed: regenerate and commit all agent_*.npz files together.  Not collected by
+pytest; the tests read only the .npz files.
 """
 import os
 import pickle
@@ -31,6 +34,20 @@ import types
 
 import numpy as np
 
+
+def _agent_goldens():
+    """tests/agent_goldens.py by its path: the children put the reference's directories first on sys.path."""
+    import importlib.util
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "agent_goldens.py")
+    spec = importlib.util.spec_from_file_location("zenv_tests_agent_goldens", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+_AG = _agent_goldens()
+sketch, SMALL = _AG.sketch, _AG.SMALL                # the probes are defined once, there; SMALL: see drive_update
+
 REFERENCE = os.environ.get("ZENV_REFERENCE", "/root/reference")
 HERE = os.path.dirname(os.path.abspath(__file__))
 VARIANTS = ("main", "zone-goals", "xy-goals", "options")
@@ -41,7 +58,6 @@ N_SKILLS = 5
 B_NET = 12                                           # rows of a network-forward batch
 SEED = 20240607
 LIMIT_FILE, LIMIT_ALL = 256 * 1024, 1024 * 1024
-SMALL = 256                                          # elements; see drive_update
 
 
 # ------------------------------------------------------------------------------------------------ the stand-in modules
@@ -201,9 +217,11 @@ def drive_update(rec, item, update, optimizer, model, index_fn_owner, index_fn_n
     """Run `update` (a bound update_* method of the reference's algorithm object) for `minibatches` optimizer steps:
     the index lists it drew, the gradient of every parameter at the first step, the per-minibatch statistics, and the
     parameters and Adam moments after the last step.  The fixtures have to stay under 1 MiB together, and one model of
-    h_dim 32 is 25 KiB in float32: the gradients of every parameter are kept only where `full` (the learners the GPU
-    tests drive), elsewhere -- and for the state after the last step everywhere -- only the tensors of at most SMALL
-    elements are: every bias and every head, which every term of the loss and every setting of the optimizer reach."""
+    h_dim 32 is 25 KiB in float32: the gradients of every parameter are kept only where `full` (the flat-plain and
+    Zone-goals learners), elsewhere -- and for the state after the last step everywhere -- only the tensors of at most SMALL
+    elements are: every bias and every head, which every term of the loss and every setting of the optimizer reach.  A
+    larger gradient that is not kept in full is kept as its sketch [G v, u^T G] (tests/agent_goldens.sketch), computed
+    in float64 from this precision's gradient."""
     drawn, grads, steps = [], {}, [0]
     names = [k for k, _ in model.named_parameters()]
     inner_index = getattr(index_fn_owner, index_fn_name)
@@ -235,6 +253,8 @@ def drive_update(rec, item, update, optimizer, model, index_fn_owner, index_fn_n
     for n in names:
         if full or grads[n].size <= SMALL:
             rec.mine(item, f"grad/{n}", grads[n])
+        else:
+            rec.mine(item, f"sketch/{n}", sketch(grads[n]))
     after = dict(model.named_parameters())
     for n, p in zip(names, model.parameters()):
         if grads[n].size > SMALL:

@@ -10,7 +10,12 @@ operations and differ only by the reassociation of dot products of at most a few
 misread formula moves results by 1e-4 or more.  float32 against float32: ``ppo_update_ref.check_rule`` with the float64
 recording as the yardstick (no equality: another machine's BLAS may order sums differently).
 
-What is pinned and what is not: DESIGN.md section 0."""
+Large gradients.  The fixtures hold the first-step gradient of every parameter of every learner: in full where it has
+at most 256 elements (and for the flat-plain and Zone-goals learners throughout), else as the sketch [G v, u^T G] of
+tests/agent_goldens.py.  The restatements' sketches are held to the recorded ones under the same two bounds, every
+update asserts that each parameter is covered one way or the other, and test_sketch_can_fail is the negative control.
+
+What is pinned and how: DESIGN.md section 0."""
 import numpy as np
 import pytest
 import torch
@@ -18,7 +23,7 @@ import torch
 from tests import collect_ref, hier_ref, hppo_update_ref as RH, option_ref, ppo_update_ref as R, skill_collect_ref
 from tests import diayn_update_ref as RD, opppo_update_ref as RO, skill_ref, skppo_update_ref as RS, xy_ref
 from tests import xyppo_update_ref as RX
-from tests.agent_goldens import load, sub
+from tests.agent_goldens import SMALL, hier_hyper as _hier_hyper, load, sketch, sub
 
 F32, F64 = torch.float32, torch.float64
 WORST = {}
@@ -218,6 +223,18 @@ BRANCHES = ("ratio_clipped_high", "ratio_clipped_low", "ratio_unclipped", "value
             "value_unclipped_term_larger")
 
 
+def _sketch_checks(rec, p, grads):
+    """[(name, the sketch of the restatement's first-step gradient)] for every sketch/<name> of precision p.  Every
+    parameter is pinned one way or the other: its gradient is recorded in full or as a sketch, never both or neither."""
+    full, sketched = set(sub(rec, f"{p}/grad/")), set(sub(rec, f"{p}/sketch/"))
+    assert full | sketched == set(grads) and not full & sketched, sorted(set(grads) ^ (full | sketched))
+    for k in sketched:
+        assert grads[k].numel() > SMALL and rec[f"{p}/sketch/{k}"].shape == (sum(grads[k].shape),), k
+    for k in full:
+        assert rec[f"{p}/grad/{k}"].shape == tuple(grads[k].shape), k
+    return [(f"sketch/{k}", sketch(grads[k].numpy())) for k in sorted(sketched)]
+
+
 def _check_update(family, rec, make_learner, make_batch, first_gradients, full):
     """Two minibatches with Adam applied.  Parameters after Adam: one step's sensitivity to a gradient error d is
     lr eps / (|g| + eps)^2 d at the first step (m / sqrt(v) = sign(g) there) and at most lr / (|g| + eps) d later;
@@ -230,10 +247,10 @@ def _check_update(family, rec, make_learner, make_batch, first_gradients, full):
         learner = make_learner(dt)
         stats = np.array([learner.minibatch(make_batch(i, dt)) for i in idx], np.float64)
         want = sub(rec, f"{p}/grad/")
-        assert len(want) == (len(grads) if full else sum(g.numel() <= 256 for g in grads.values())) and len(want) >= 9
+        assert len(want) == (len(grads) if full else sum(g.numel() <= SMALL for g in grads.values())) and len(want) >= 9
         state = {k: learner.opt.state[q] for k, q in learner.model.named_parameters()}
         after = dict(learner.model.named_parameters())
-        checks = [(f"grad/{k}", grads[k].numpy()) for k in want]
+        checks = [(f"grad/{k}", grads[k].numpy()) for k in want] + _sketch_checks(rec, p, grads)
         for k in sub(rec, f"{p}/param/"):
             checks += [(f"param/{k}", after[k].detach().numpy()), (f"exp_avg/{k}", state[k]["exp_avg"].numpy()),
                        (f"exp_avg_sq/{k}", state[k]["exp_avg_sq"].numpy())]
@@ -293,21 +310,13 @@ def test_zone_goals_update(level):
                   lambda dt, b: RH.gradients(level, RH.model_from(level, sd, F, dt), b, hyper)[0], full=True)
 
 
-def _hier_hyper(h, level):
-    """The reference clips at neither level (its clip_grad_norm_ lines are commented out in every variant)."""
-    pre = "hi_" if level == "hi" else ""
-    return dict(lr=float(h[pre + "lr"]), adam_eps=float(h["optim_eps"]), clip_eps=float(h["clip_eps"]),
-                entropy_coef=float(h[pre + "entropy_coef"]),
-                value_loss_coef=float(h["hi_value_coef" if level == "hi" else "value_loss_coef"]),
-                max_grad_norm=float("inf"))
-
-
 @pytest.mark.parametrize("level", ["hi", "lo"])
 @pytest.mark.parametrize("agent", ["xy_goals", "skills", "options"])
 def test_other_two_level_updates(agent, level):
     """update_hi_parameters / update_lo_parameters of the xy-goals, fixed-length-skills and Options variants against
-    xyppo / skppo / opppo_update_ref.RefLearner.  The fixtures keep the tensors of at most 256 elements (every bias and
-    head) for these learners; the skill families' batches leave one skill without a sample."""
+    xyppo / skppo / opppo_update_ref.RefLearner.  For these learners the fixtures keep the tensors of at most 256
+    elements (every bias and head) in full and the first-step gradient of every larger matrix as its sketch; the skill
+    families' batches leave one skill without a sample."""
     variant, part, net, RM = {"xy_goals": ("xy-goals", "updates", "networks", RX),
                               "skills": ("main", "skill_updates", "skill_networks", RS),
                               "options": ("options", "updates", "networks", RO)}[agent]
@@ -324,6 +333,30 @@ def test_other_two_level_updates(agent, level):
 
     _check_update(f"{agent}_{level}_update", rec, lambda dt: RM.RefLearner(level, sd, F, dt, hyper), batch,
                   lambda dt, b: RM.gradients(level, RM.model_from(level, sd, F, dt), b, hyper)[0], full=False)
+
+
+def test_sketch_can_fail():
+    """The negative control of the sketch, on the xy-goals low level's recorded batch: the float64 gradient of a 32 x 32
+    matrix passes the check against the recorded sketch; transposed, with two rows swapped, or with 1e-4 max|G| added to
+    a single element it does not."""
+    rec = sub(load("xy-goals", "updates"), "xy_goals_lo_update/")
+    sd = sub(load("xy-goals", "networks"), "xy_goals/lo_sd/")
+    e, hyper = sub(rec, "exp/"), _hier_hyper(sub(rec, "hyper/"), "lo")
+    b = {k: torch.as_tensor(v[rec["index0"]]) for k, v in e.items()}
+    b = {k: v.to(F64) if v.is_floating_point() else v for k, v in b.items()}
+    grads, _ = RX.gradients("lo", RX.model_from("lo", sd, e["zone_obs"].shape[2], F64), b, hyper)
+    name = "env_model.zone_net_.2.weight"
+    G, want = grads[name].numpy().copy(), rec[f"f64/sketch/{name}"]
+    assert G.shape == (32, 32) and want.shape == (64,)
+    close64("negative control", "undisturbed", sketch(G), want)
+    swapped = G.copy()
+    swapped[[3, 17]] = swapped[[17, 3]]
+    bumped = G.copy()
+    bumped[11, 20] += 1e-4 * np.abs(G).max()
+    for what, bad in (("transposed", G.T), ("rows 3 and 17 swapped", swapped), ("one element off", bumped)):
+        with pytest.raises(AssertionError):
+            close64("negative control", what, sketch(bad), want)
+    WORST.pop("negative control")
 
 
 def test_inverse_update():
@@ -344,6 +377,8 @@ def test_inverse_update():
         state = {k: learner.opt.state[q] for k, q in learner.model.named_parameters()}
         after = dict(learner.model.named_parameters())
         checks = [("log/loss", losses)] + [(f"grad/{k}", grads[k].numpy()) for k in sub(rec, f"{p}/grad/")]
+        checks += _sketch_checks(rec, p, grads)
+        assert sum(n.startswith("sketch/") for n, _ in checks) == 4
         for k in sub(rec, f"{p}/param/"):
             checks += [(f"param/{k}", after[k].detach().numpy()), (f"exp_avg/{k}", state[k]["exp_avg"].numpy()),
                        (f"exp_avg_sq/{k}", state[k]["exp_avg_sq"].numpy())]

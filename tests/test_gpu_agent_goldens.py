@@ -1,16 +1,35 @@
 """The device agents on what the reference's own code made and computed (tests/golden/agent_*.npz, recorded by
 tests/golden/make_agent_goldens.py): state_dicts exactly as the reference's modules emit them, through the project's
-loaders into the device forwards of all five agents and the inverse model at 70 envs, and the flat and Zone-goals
-learners on the reference's own experience and minibatch against the reference's own recorded gradients.  Small shapes
-only: N <= 70, T <= 33, h = 32.  The forwards are held to the tolerances of the existing forward tests (1e-5 of
-max(1, |ref|), check_rule for the flat agent) against the restatements tests/test_agent_goldens_cpu.py pins."""
+loaders into the device forwards of all five agents and the inverse model at 70 envs, and every device learner -- the
+flat one with the plain and with the distributional critic, both levels of the Zone-goals, xy-goals, fixed-length-skills
+and Options agents, DIAYN's inverse model and its skill prior -- on the reference's own experience, index lists and
+hyper-parameters against what the reference's own update functions computed.  Small shapes only: N <= 70, T <= 33,
+h = 32.  The forwards are held to the tolerances of the existing forward tests (1e-5 of max(1, |ref|), check_rule for
+the flat agent) against the restatements tests/test_agent_goldens_cpu.py pins.
+
+The learners (second half of this file).  The recorded exp/* rows are planted through TorchZoneEnv's aliases of a real
+collection's buffers, fixture row i at the learner's own sample index i (the map is the *_update_ref batch functions',
+and the batch they read back must be the fixture's rows), and read back bit for bit.  Every comparison is
+ppo_update_ref.check_rule with the reference's float64 run as the truth and its float32 run as the ruler:
+  one minibatch, apply = 0, index0   the statistics; every gradient of at most 256 elements against the recorded one;
+                                     every larger one by its sketch [G v, u^T G] against the recorded sketch (or in
+                                     full where the fixture has it) and element by element against the restatement's
+                                     gradients on the same batch, which the CPU file pins to the same sketch
+  index0 then index1 with Adam       both minibatches' statistics and the recorded (small) tensors' exp_avg, exp_avg_sq
+                                     and param; for the flat learner the clip is active (factor < 1)
+  the skill prior                    two diayn_prior_update steps on the recorded picks: logits and probabilities"""
+import math
+import types
+
 import numpy as np
 import pytest
 import torch
 
 from tests import hier_ref, option_ref, ppo_update_dev as D, ppo_update_ref as R, skill_collect_ref, skill_ref, xy_ref
-from tests import hppo_update_ref as RH
-from tests.agent_goldens import load, sub
+from tests import diayn_update_dev as DD, opppo_update_dev as DO, skppo_update_dev as DS, xyppo_update_dev as DX
+from tests import diayn_update_ref as RD, hppo_update_ref as RH, opppo_update_ref as RO, skppo_update_ref as RS
+from tests import xyppo_update_ref as RX
+from tests.agent_goldens import SMALL, hier_hyper, load, sketch, sub
 
 pytestmark = pytest.mark.gpu
 
@@ -274,3 +293,299 @@ def test_zone_goals_learner_on_the_reference_batch(zenv_mod, level):
     for key in want64:
         R.check_rule(f"golden-zg-{level}/grad.{key}", grads[key], want64[key], want32[key])
     env.close()
+
+
+# ------------------------------------------------------------------------------------------------ every device learner
+# learner -> (variant, the update's fixture, the networks' fixture, the networks' prefix, family, level)
+SOURCES = {"flat_plain": ("main", "flat_update", "networks", "flat_plain/", "flat", None),
+           "flat_dist": ("main", "flat_update", "networks", "flat_dist/", "flat", None),
+           "zone_goals_hi": ("zone-goals", "hi_update", "networks", "zone_goals/", "zg", "hi"),
+           "zone_goals_lo": ("zone-goals", "lo_update", "networks", "zone_goals/", "zg", "lo"),
+           "xy_goals_hi": ("xy-goals", "updates", "networks", "xy_goals/", "xy", "hi"),
+           "xy_goals_lo": ("xy-goals", "updates", "networks", "xy_goals/", "xy", "lo"),
+           "skills_hi": ("main", "skill_updates", "skill_networks", "skills/", "sk", "hi"),
+           "skills_lo": ("main", "skill_updates", "skill_networks", "skills/", "sk", "lo"),
+           "options_hi": ("options", "updates", "networks", "options/", "op", "hi"),
+           "options_lo": ("options", "updates", "networks", "options/", "op", "lo"),
+           "inverse": ("main", "skill_updates", "skill_networks", "inverse/", "inv", None)}
+NEW_LEARNERS = ["flat_dist", "xy_goals_hi", "xy_goals_lo", "skills_hi", "skills_lo", "options_hi", "options_lo", "inverse"]
+# family -> (the restatement, the prefix of the handle's methods, name -> tensors by state_dict key, the task)
+FAMILIES = {"zg": (RH, "hppo", D.hier_by_key, "PointTSP-v0"), "xy": (RX, "xyppo", DX.xy_by_key, "ColourMatch-v0"),
+            "sk": (RS, "skppo", DS.sk_by_key, "PointTSP-v0"), "op": (RO, "opppo", DO.op_by_key, "ColourMatch-v0")}
+H_DIM, N_SKILLS = 32, 5
+UPD_N, UPD_T, UPD_L = 6, 8, 2                       # 48 low rows; with skill_len 2, 24 high rows
+OP_T = UPD_T + 1                                    # the Options collector's low rows are frames 0 .. T - 2
+INV_N, INV_T = 8, 6                                 # 8 x (6 - 1) = 40 inverse samples, one window per collection
+ZG_HI_NT = (15, 33)                                 # a collection that closes at least the fixture's 30 transitions
+_HANDLES = {}
+REPORT = []
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _learner_teardown():
+    yield
+    for s in _HANDLES.values():
+        s["env"].close()
+    worst = {}
+    for name, e_dev, e32, ratio in REPORT:
+        key = name.split("/")[0]
+        worst[key] = max(worst.get(key, (0.0, "")), (ratio, name))
+    for k in sorted(worst):
+        print("worst e_dev / max(e32, ulp): %-28s %.3f  (%s)" % (k, worst[k][0], worst[k][1]))
+
+
+def _rule(failures, name, dev, ref64, ref32):
+    """check_rule; a miss is kept for the end of the test, so that one run shows every figure."""
+    try:
+        return R.check_rule(name, dev, ref64, ref32, REPORT)
+    except AssertionError as err:
+        failures.append(str(err))
+        return math.inf
+
+
+def _handle(Z, key, sds=None):
+    """One handle per family, with one real collection of the shape the fixtures need; its buffers are planted by every
+    learner that uses it."""
+    if key in _HANDLES:
+        return _HANDLES[key]
+    from combinatorial_rl_tasks_amd.torch_interop import TorchZoneEnv
+    tsp, cm = (Z.config_for_id(i, num_steps=12) for i in ("PointTSP-v0", "ColourMatch-v0"))
+    if key == "xy":
+        s = DX.xy_setup(Z, cm, H_DIM, UPD_N, seed=0, T=UPD_T, L=UPD_L)
+    elif key == "sk":
+        s = DS.sk_setup(Z, tsp, H_DIM, UPD_N, N_SKILLS, seed=0, T=UPD_T, L=UPD_L)
+    elif key == "op":
+        s = DO.op_setup(Z, cm, H_DIM, UPD_N, N_SKILLS, seed=0, T=OP_T, want_m=lambda m: m >= 24)
+    elif key == "inv":
+        s = DD.dy_setup(Z, tsp, H_DIM, INV_N, N_SKILLS, seed=0, T=INV_T, L=INV_T, plant=False)
+    elif key in ("flat_plain", "flat_dist"):
+        dist = key == "flat_dist"
+        s = D.flat_setup(Z, Z.config_for_id("ColourMatch-v0" if dist else "PointTSP-v0"), H_DIM, UPD_N, UPD_T, dist,
+                         seed=0, sd=sds)
+        s["tenv"] = TorchZoneEnv(s["env"])
+        s["lo_t"] = s["tenv"].collect(UPD_T, policy_seed=5)     # [N, T, ...] views aliasing the handle's buffers
+    else:                                                        # "zg_lo", "zg_hi": see the Zone-goals test above
+        N, T = (UPD_N, UPD_T + 1) if key == "zg_lo" else ZG_HI_NT
+        env = Z.ZoneVecEnv(tsp, N)
+        env.build_bank(11, N)
+        env.schedule_sequential()
+        env.enable_goals()
+        env.reset()
+        env.load_hier(Z.hier_tensors_from_state_dicts(*sds))
+        tenv = TorchZoneEnv(env)
+        lo_t, hi_t = tenv.collect_hier(T, policy_seed=5)
+        s = dict(env=env, tenv=tenv, lo_t=lo_t, hi_t=hi_t, N=N, T=T)
+    _HANDLES[key] = s
+    return s
+
+
+def _plant(views, arrays):
+    """Write arrays (name -> host array in the view's shape and dtype) through the aliases, then read the buffers back:
+    bit for bit what was written."""
+    for k, a in arrays.items():
+        assert tuple(views[k].shape) == a.shape, (k, tuple(views[k].shape), a.shape)
+        views[k].copy_(torch.as_tensor(np.ascontiguousarray(a)).to(views[k].device))
+    torch.cuda.synchronize()
+    for k, a in arrays.items():
+        got = np.ascontiguousarray(views[k].cpu().numpy())
+        assert got.dtype == a.dtype and got.tobytes() == np.ascontiguousarray(a).tobytes(), k
+
+
+def _rows(e, shape):
+    """The fixture's rows [n, ...] as the collectors' [N, frames, ...]; integers as the device holds them."""
+    return {k: (a.astype(np.int32) if a.dtype == np.int64 else a).reshape(shape + a.shape[1:]) for k, a in e.items()}
+
+
+def _learner(Z, name):
+    """The device learner `name` on a handle whose buffers hold the reference's recorded experience: the recorded rows
+    planted and read back, and what the two checks below need of it."""
+    nat = Z._native
+    variant, part, net_part, net_prefix, family, level = SOURCES[name]
+    rec = sub(load(variant, part), f"{name}_update/")
+    nets = sub(load(variant, net_part), net_prefix)
+    e, h = sub(rec, "exp/"), sub(rec, "hyper/")
+    n = len(e["obs"])
+    for k, v in sub(rec, "count/").items():
+        assert v > 0, (name, k)
+    L = types.SimpleNamespace(name=name, rec=rec, e=e, n=n, clip=None)
+    if family == "flat":
+        sd = sub(nets, "sd/")
+        s = _handle(Z, name, sd)
+        env, dist = s["env"], name == "flat_dist"
+        hyper = {k: float(h[k]) for k in ("lr", "adam_eps", "clip_eps", "entropy_coef", "value_loss_coef", "max_grad_norm")}
+        assert (UPD_N, UPD_T) == tuple(int(v) for v in rec["shape/NT"])
+        _plant(s["lo_t"], _rows(e, (UPD_N, UPD_T)))             # the reference's rows are [env][frame]
+        L.init = lambda: env.ppo_init(sd, max_batch=n, **hyper)
+        L.minibatch, L.stats, L.step = env.ppo_minibatch, env.ppo_stats, env.ppo_get_step
+        L.tensors = lambda which: D.flat_by_key(env, which)
+        L.batch = lambda idx, dt: R.as_batch(D.host(s["lo_t"]), idx, dt)
+        L.ref = lambda b, dt: R.gradients(R.model_from(sd, e["zone_obs"].shape[2], dt), b, hyper)
+        L.columns = [(i, k) for i, k in enumerate(nat.PPO_STATS) if dist or k != "value_std"]
+        L.n_keys = 20 if dist else 18
+        L.clip = {p: R.clip_coef(float(rec[f"{p}/log/grad_norm"][0]), hyper["max_grad_norm"]) for p in ("f64", "f32")}
+        assert L.clip["f64"] < 1.0 and L.clip["f32"] < 1.0       # the reference's clip was active
+    elif family == "inv":
+        sd = sub(nets, "sd/")
+        s = _handle(Z, "inv")
+        env, T1 = s["env"], INV_T - 1
+        assert n == INV_N * T1
+        lo_t = s["lo_t"]
+        rows = _rows(e, (INV_N, T1))
+        # sample (env, f) pairs the observation of frame f + 1 with the skill of frame f (diayn_update_ref.batch), and is
+        # kept where the mask of frame f + 1 is not 0 (kept_samples): all 40 are
+        views = {"obs": lo_t["obs"][:, 1:], "zone_obs": lo_t["zone_obs"][:, 1:], "skill": lo_t["skill"][:, :-1],
+                 "mask": lo_t["mask"][:, 1:]}
+        _plant(views, dict(rows, mask=np.ones((INV_N, T1), np.float32)))
+        np.testing.assert_array_equal(RD.kept_samples(D.host(lo_t)["mask"]), np.arange(n))
+        np.testing.assert_array_equal(env.diayn_samples(), np.arange(n))
+        hyper = dict(lr=float(h["lr"]), adam_eps=float(h["optim_eps"]))
+        L.init = lambda: env.diayn_init(sd, N_SKILLS, max_batch=n, **hyper)
+        L.minibatch, L.stats, L.step = env.diayn_minibatch, env.diayn_stats, env.diayn_get_step
+        L.tensors = lambda which: DD.dy_by_key(env, which)
+        L.batch = lambda idx, dt: RD.batch(D.host(lo_t), idx, dt)
+        L.ref = lambda b, dt: RD.gradients(RD.model_from(sd, e["zone_obs"].shape[2], dt), b)
+        L.columns = [(0, "loss")]
+        L.n_keys = 10
+    else:
+        RM, prefix, by_key, _ = FAMILIES[family]
+        sds = {"hi": sub(nets, "hi_sd/"), "lo": sub(nets, "lo_sd/")}
+        s = _handle(Z, family if family != "zg" else f"zg_{level}", (sds["hi"], sds["lo"]))
+        env, lv = s["env"], D.LEVELS[level]
+        if level == "lo":
+            frames = n // UPD_N
+            rows = _rows(e, (UPD_N, frames))
+            if family == "op":                                   # the third component has buffers of its own
+                rows["term_action"], rows["action"] = rows["action"][..., 2], rows["action"][..., :2]
+                rows["term_log_prob"], rows["log_prob"] = rows["log_prob"][..., 2], rows["log_prob"][..., :2]
+            _plant(s["lo_t"], rows)
+            L.batch = lambda idx, dt: RM.lo_batch(D.host(s["lo_t"]), idx, dt)
+        else:
+            rows = _rows(e, (n,))
+            assert int(s["hi_t"]["value"].shape[0]) >= n
+            _plant({k: s["hi_t"][k][:n] for k in rows}, rows)
+            L.batch = lambda idx, dt: RM.hi_batch({k: v for k, v in D.host(s["hi_t"]).items() if k != "count"}, idx, dt)
+        hyper = hier_hyper(h, level)
+        mine = dict({k: v for k, v in hyper.items() if k != "max_grad_norm"}, max_batch=64)   # no clip: the default
+        other = dict(max_batch=64)
+        L.init = lambda: getattr(env, prefix + "_init")(sds["hi"], sds["lo"], lo=mine if level == "lo" else other,
+                                                         hi=mine if level == "hi" else other)
+        L.minibatch = lambda idx, apply=False: getattr(env, prefix + "_minibatch")(lv, idx, apply)
+        L.stats = lambda: getattr(env, prefix + "_stats")(lv)
+        L.step = lambda: getattr(env, prefix + "_get_step")(lv)
+        L.tensors = lambda which: by_key(env, level, which)
+        L.ref = lambda b, dt: RM.gradients(level, RM.model_from(level, sds[level], e["zone_obs"].shape[2], dt), b, hyper)
+        L.columns = [(i, k) for i, k in enumerate(nat.PPO_STATS) if k != "value_std"]
+        L.n_keys = 18 if level == "lo" or family == "xy" else 16
+    assert (env.num_zones, env.zone_feat) == e["zone_obs"].shape[1:]
+    # the project's own index -> (env, frame) map reads the fixture's row i at sample index i
+    b = L.batch(np.arange(n), F32)
+    for k, a in e.items():
+        np.testing.assert_array_equal(b[k].numpy(), a, err_msg=f"{name}: {k}")
+    assert max(int(rec["index0"].max()), int(rec["index1"].max())) < n
+    return L
+
+
+def _stats_rule(failures, L, tag, row, i):
+    """A statistics row against the reference's i-th minibatch."""
+    for col, k in L.columns:
+        _rule(failures, f"{tag}/stat{i}.{k}", row[col], L.rec[f"f64/log/{k}"][i], L.rec[f"f32/log/{k}"][i])
+    if (2, "value_std") not in L.columns and L.name != "inverse":
+        assert row[2] == 0.0
+
+
+def _check_first_minibatch(Z, name):
+    """One minibatch (apply = 0) on the reference's first index list."""
+    nat = Z._native
+    L = _learner(Z, name)
+    rec, tag, failures = L.rec, f"golden-{name}", []
+    L.init()
+    L.minibatch(rec["index0"].astype(np.int32))
+    stats, grads = L.stats()[0], L.tensors(nat.PPO_GRAD)
+    ref = {p: L.ref(L.batch(rec["index0"], dt), dt) for p, dt in (("f64", F64), ("f32", F32))}
+    full, sketched = sub(rec, "f64/grad/"), sub(rec, "f64/sketch/")
+    assert set(grads) == set(ref["f64"][0]) == set(full) | set(sketched) and len(grads) == L.n_keys
+    assert set(full) == set(sub(rec, "f32/grad/")) and set(sketched) == set(sub(rec, "f32/sketch/"))
+    _stats_rule(failures, L, tag, stats, 0)
+    if name == "inverse":                                       # the reference logs no norm here: the restatement's
+        _rule(failures, f"{tag}/stat0.grad_norm", stats[5], ref["f64"][1]["grad_norm"], ref["f32"][1]["grad_norm"])
+        assert np.all(stats[1:5] == 0)
+    # the recorder read .grad after the flat learner's clip; the device's gradient arena holds the unclipped ones
+    c64, c32 = (L.clip["f64"], L.clip["f32"]) if L.clip else (1.0, 1.0)
+    large = 0
+    for key, g in grads.items():
+        assert g.shape == tuple(ref["f64"][0][key].shape), key
+        if key in full:
+            assert g.size <= SMALL or name not in NEW_LEARNERS
+            _rule(failures, f"{tag}/grad.{key}", g, full[key] / c64, rec[f"f32/grad/{key}"] / c32)
+        else:
+            assert g.size > SMALL
+            _rule(failures, f"{tag}/sketch.{key}", sketch(g), sketched[key] / c64, rec[f"f32/sketch/{key}"] / c32)
+        if g.size > SMALL:
+            large += 1
+            _rule(failures, f"{tag}/restated.{key}", g, ref["f64"][0][key].numpy(), ref["f32"][0][key].numpy())
+    assert large >= 4 and L.step() == 0
+    assert not failures, "\n".join(failures)
+
+
+@pytest.mark.parametrize("name", NEW_LEARNERS)
+def test_learner_on_the_reference_batch(zenv_mod, name):
+    """One minibatch (apply = 0) of each learner the reference's batches had not reached: the flat learner with the
+    distributional critic (value_std included, the recorded gradients divided by the recorded clip factor), both levels
+    of the xy-goals, fixed-length-skills and Options agents (the skill families' batches leave skill 3 without a
+    sample) and DIAYN's inverse model."""
+    _check_first_minibatch(zenv_mod, name)
+
+
+@pytest.mark.parametrize("name", list(SOURCES))
+def test_two_minibatches_with_adam(zenv_mod, name):
+    """index0 then index1, each with its clip and Adam step, as the reference's update ran them: both rows of
+    statistics, and Adam's moments and the parameters of every tensor the fixture keeps (those of at most 256 elements:
+    every bias and head) after the second step.  The flat learner's clip is active in the recording, so its moments and
+    parameters are the first comparison of the device's clip with the reference's own numbers.
+
+    param after Adam is ill-conditioned where the first-step gradient is tiny (one step's sensitivity to a gradient
+    error is lr eps / (|g| + eps)^2; in the recorded Zone-goals high level the reference's own float32 run is 48 445 ulp
+    from its float64 run in actor.2.bias, whose float64 gradient is 2.8e-17: a softmax over zones ignores a shared
+    bias).  check_rule's per-tensor base carries that through e32: every element of every recorded parameter is
+    compared, none is left out."""
+    Z = zenv_mod
+    nat = Z._native
+    L = _learner(Z, name)
+    rec, tag, failures = L.rec, f"adam-{name}", []
+    L.init()
+    for i in range(2):
+        L.minibatch(rec[f"index{i}"].astype(np.int32), True)
+        _stats_rule(failures, L, tag, L.stats()[0], i)
+    assert L.step() == 2
+    kept = sorted(sub(rec, "f64/param/"))
+    assert kept == sorted(sub(rec, "f64/exp_avg/")) == sorted(sub(rec, "f64/exp_avg_sq/")) and len(kept) >= 6
+    for which, what in ((nat.PPO_EXP_AVG, "exp_avg"), (nat.PPO_EXP_AVG_SQ, "exp_avg_sq"), (nat.PPO_PARAM, "param")):
+        dev = L.tensors(which)
+        for key in kept:
+            assert dev[key].shape == rec[f"f64/{what}/{key}"].shape
+            _rule(failures, f"{tag}/{what}.{key}", dev[key], rec[f"f64/{what}/{key}"], rec[f"f32/{what}/{key}"])
+    assert not failures, "\n".join(failures)
+
+
+def test_skill_prior_on_the_reference_picks(zenv_mod):
+    """Two diayn_prior_update steps from the reference's logits, learning rate and eps on its recorded picks (the
+    high level's 24 rows, skill 3 never among them) against the logits and probabilities its update_skill_prior left."""
+    Z = zenv_mod
+    rec = sub(load("main", "skill_updates"), "prior_update/")
+    nets = load("main", "skill_networks")
+    assert rec["count/skills_without_a_sample"] > 0
+    s = _handle(Z, "sk")
+    env, actions = s["env"], rec["actions"].astype(np.int32)
+    assert len(actions) == s["M"] == int(s["hi_t"]["action"].shape[0])
+    _plant({"action": s["hi_t"]["action"]}, {"action": actions})
+    np.testing.assert_array_equal(rec["f32/logits0"], rec["f64/logits0"])
+    env.diayn_init(sub(nets, "inverse/sd/"), N_SKILLS, prior_logits=rec["f32/logits0"],
+                   prior=dict(lr=float(rec["hyper/lr"]), adam_eps=float(rec["hyper/optim_eps"])), max_batch=64)
+    np.testing.assert_array_equal(env.diayn_prior_logits(), rec["f32/logits0"])
+    failures = []
+    for step in (1, 2):
+        logits = env.diayn_prior_update()
+        probs = torch.softmax(torch.as_tensor(logits, dtype=F64), dim=0).numpy()
+        _rule(failures, f"golden-prior/logits{step}", logits, rec[f"f64/logits{step}"], rec[f"f32/logits{step}"])
+        _rule(failures, f"golden-prior/probs{step}", probs, rec[f"f64/probs{step}"], rec[f"f32/probs{step}"])
+    assert not failures, "\n".join(failures)
