@@ -27,7 +27,7 @@ from ._native import (Config, ZenvError, E_ARG, E_HIP, E_STATE, E_LAYOUT, E_DONE
                       F_XY_BOOTSTRAP_GOAL, F_PPO_STATS, PPO_PARAM, PPO_GRAD, PPO_EXP_AVG, PPO_EXP_AVG_SQ, PPO_STATS,
                       F_HPPO_LO_STATS, F_HPPO_HI_STATS, HPPO_LO, HPPO_HI, F_XYPPO_LO_STATS, F_XYPPO_HI_STATS, XYPPO_LO,
                       XYPPO_HI, F_SKPPO_LO_STATS, F_SKPPO_HI_STATS, SKPPO_LO, SKPPO_HI, F_OPPPO_LO_STATS,
-                      F_OPPPO_HI_STATS, OPPPO_LO, OPPPO_HI, F_DIAYN_STATS, F_DIAYN_SAMPLES,
+                      F_OPPPO_HI_STATS, OPPPO_LO, OPPPO_HI, F_DIAYN_STATS, F_DIAYN_SAMPLES, F_ORDER_ROWS,
                       RenderConfig, RENDER_CURRENT, RENDER_EXPERIENCE, DEVICE_RESTARTS, SAMPLE_STATUS_CAP,
                       SAMPLE_UNFINISHED, SAMPLE_SEED_RANGE, DET_OP_LOG, DET_OP_DIV, DET_OP_SQRT)
 from .vec_env import (ZoneVecEnv, config_for_id, default_config, sample_layout, sample_layout_shared,

@@ -48,7 +48,7 @@ E_ARG, E_HIP, E_STATE, E_LAYOUT, E_DONE, E_RANGE = -1, -2, -3, -4, -5, -6
  F_XY_GOAL, F_XY_GOAL_MU, F_XY_GOAL_STD, F_XY_VALUE, F_XY_GOAL_AGE,
  F_HI_GOAL, F_LO_GOAL_DIST, F_XY_BOOTSTRAP_GOAL, F_PPO_STATS, F_HPPO_LO_STATS, F_HPPO_HI_STATS,
  F_XYPPO_LO_STATS, F_XYPPO_HI_STATS, F_SKPPO_LO_STATS, F_SKPPO_HI_STATS, F_OPPPO_LO_STATS,
- F_OPPPO_HI_STATS, F_DIAYN_STATS, F_DIAYN_SAMPLES) = range(85)
+ F_OPPPO_HI_STATS, F_DIAYN_STATS, F_DIAYN_SAMPLES, F_ORDER_ROWS) = range(86)
 (RESULT_OBS, RESULT_REWARD, RESULT_DONE, RESULT_GOAL_MET, RESULT_EXCEPTION, RESULT_ZONE_OBS) = range(6)
 N_RESULTS = 6
 
@@ -257,6 +257,7 @@ _PROTOTYPES = {
     "zenv_route_ranks_shared": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "zenv_route_ranks_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "zenv_order_routes_device": (C.c_int, [_H, C.c_int]),
+    "zenv_order_rows": (C.c_int, [_H, C.c_int]),
     "zenv_goal_enable": (C.c_int, [_H]),
     "zenv_set_goals": (C.c_int, [_H, C.c_void_p]),
     "zenv_solver_goals": (C.c_int, [_H, C.c_void_p]),

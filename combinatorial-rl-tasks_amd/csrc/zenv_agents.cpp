@@ -110,7 +110,7 @@ extern "C" int zenv_mlp_load(zenv_t *h, const zenv_mlp_weights *w)
         // for observations up to kMlpF16ObsBound and zone rows up to 2 (positions / 3, flags, timers: bounded by
         // construction) -- the zone kernel has no cycles to spare for watching them; the head kernel watches its own.
         // ZENV_MLP_F16X3, float16 halves: a weight of 65 520 or more would be inf on the device.
-        const int hd = w->h_dim, F = h->p.F;
+        const int hd = w->h_dim, F = net_row_feat(h);     // (zenv_order_rows: the order value lies in [0, 1], inside the rows' bound of 2)
         const struct { const float *t; size_t n; const char *name; bool folded; } all[] = {
             { w->zone_w1, (size_t)hd * (8 + F), "zone_net_.0.weight", 0 }, { w->zone_b1, (size_t)hd, "zone_net_.0.bias", 0 },
             { w->zone_w2, (size_t)hd * hd, "zone_net_.2.weight", 0 },      { w->zone_b2, (size_t)hd, "zone_net_.2.bias", 0 },
@@ -147,7 +147,7 @@ extern "C" int zenv_mlp_load(zenv_t *h, const zenv_mlp_weights *w)
     }
     std::vector<uint16_t> img;
     size_t offs[8];
-    if (pack_images(*w, h->p.F, img, offs, w->precision == ZENV_MLP_F16) != 0)
+    if (pack_images(*w, net_row_feat(h), img, offs, w->precision == ZENV_MLP_F16) != 0)
         return fail(ZENV_E_ARG, "h_dim %d outside [1, %d]", w->h_dim, kMlpHP - 1);
     if (w->precision == ZENV_MLP_F16)        // zone_net_.4 folded into combine_net_: a product that can leave the range
         for (size_t i = 0; i < img.size(); ++i)
@@ -158,7 +158,7 @@ extern "C" int zenv_mlp_load(zenv_t *h, const zenv_mlp_weights *w)
     size_t fo[30];
     const bool f32_grade = w->precision != ZENV_MLP_BF16 && w->precision != ZENV_MLP_F16;
     if (f32_grade) {
-        pack_f32(*w, h->p.F, f32, fo);
+        pack_f32(*w, net_row_feat(h), f32, fo);
         if (w->precision == ZENV_MLP_F16X3) {
             // the float16 images start at fo[24] (zone_net_.2): combine_net_ arrives with zone_net_.4 folded in, a product of
             // two in-range matrices that need not be in range itself
@@ -214,14 +214,54 @@ extern "C" int zenv_mlp_load(zenv_t *h, const zenv_mlp_weights *w)
     return ZENV_OK;
 }
 
+// The zone rows the flat network reads: the observation's own, or with zenv_order_rows on the (Z, 7) rows that
+// k_order_rows (K22) assembles into `dst` (null: ZENV_F_ORDER_ROWS) from the handle's 6-wide rows and the order value as
+// they stand.  Launched here, where a network is about to read them: a caller that never asks a network pays nothing.
+static int network_rows(zenv *h, float *dst, const float **rows)
+{
+    *rows = h->p.zone_obs;
+    if (!h->net_feat) return ZENV_OK;
+    if (!dst) dst = h->order_rows;
+    HIP_TRY(launch_order_rows(h->p.zone_obs, h->p.order_val, dst, (int64_t)h->n_env * h->p.Z, h->stream));
+    *rows = dst;
+    return ZENV_OK;
+}
+
+// the flat network on the current observation: `act` says what the head kernel does with (mu, std)
+static int flat_forward(zenv *h, const MlpAction &act, float *rows_dst = nullptr)
+{
+    const float *rows = nullptr;
+    if (int rc = network_rows(h, rows_dst, &rows)) return rc;
+    HIP_TRY(launch_mlp_forward(h->mlp, h->n_env, h->p.Z, net_row_feat(h), h->p.obs, rows, h->mlp_pooled, h->mlp_mu,
+                               h->mlp_std, h->mlp_value, h->mlp_value_sigma, act, h->stream));
+    return ZENV_OK;
+}
+
 extern "C" int zenv_mlp_forward(zenv_t *h)
 {
     if (!h) return fail(ZENV_E_ARG, "null handle");
     if (!h->mlp_ready) return fail(ZENV_E_STATE, "zenv_mlp_load first");
     if (!h->was_reset) return fail(ZENV_E_STATE, "reset before asking for actions");
     if (int rc = use_device(h)) return rc;
-    HIP_TRY(launch_mlp_forward(h->mlp, h->n_env, h->p.Z, h->p.F, h->p.obs, h->p.zone_obs, h->mlp_pooled, h->mlp_mu,
-                               h->mlp_std, h->mlp_value, h->mlp_value_sigma, no_mlp_action(), h->stream));
+    return flat_forward(h, no_mlp_action());
+}
+
+// zenv_order_rows toggled: what is sized by the network row width goes, and callers load it again
+int drop_flat_network(zenv *h)
+{
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->mlp_ready = false;
+    for (void **m : { &h->mlp_mem, &h->mlp_f32_mem, &h->exp_mem })
+        if (*m) {
+            HIP_TRY(hipFree(*m));
+            *m = nullptr;
+        }
+    h->mlp = MlpImages{};
+    h->exp = ExpBuffers{};
+    h->exp_hier = h->exp_xy = h->exp_skill = h->exp_option = false;
+    h->diayn_kept = -1;
+    h->eplog.source = 0;
+    ppo_free_flat(h);
     return ZENV_OK;
 }
 
@@ -577,7 +617,7 @@ static int run_xy_policy(zenv_t *h, int policy, uint32_t step_index, uint64_t se
 }
 
 // a_t = pi(obs_t, t) into pol.out, for every kind of action source
-int run_policy(zenv *h, const StepPolicy &pol, const MlpRecord *rec)
+int run_policy(zenv *h, const StepPolicy &pol, const MlpRecord *rec, float *rows)
 {
     if (!policy_is_mlp(pol.policy)) {
         HIP_TRY(launch_policy(h->p, pol, h->stream));
@@ -587,9 +627,7 @@ int run_policy(zenv *h, const StepPolicy &pol, const MlpRecord *rec)
     // the head kernel also turns (mu, std) into the action
     const MlpAction act{ pol.policy == ZENV_POLICY_MLP_SAMPLE ? 1 : 0, pol.step_index, pol.seed, pol.env_index0, pol.out,
                          rec ? *rec : MlpRecord{} };
-    HIP_TRY(launch_mlp_forward(h->mlp, h->n_env, h->p.Z, h->p.F, h->p.obs, h->p.zone_obs, h->mlp_pooled, h->mlp_mu,
-                               h->mlp_std, h->mlp_value, h->mlp_value_sigma, act, h->stream));
-    return ZENV_OK;
+    return flat_forward(h, act, rows);
 }
 
 // A ring schedule is only as deep as its `depth` slots per env, and only the HOST refills them (zenv_bank_update), between
@@ -634,24 +672,32 @@ namespace {
 // The collectors record the observations where they are produced: the policy of frame t reads slot t of the
 // ZENV_F_EXP_* buffers, the step kernel of frame t writes obs_{t+1} into slot t + 1 (the last one into the handle's own
 // buffers again).  Whatever way the call returns, the handle gets its own buffers back.
+//
+// A handle with zenv_order_rows on records 7-wide rows, which the step kernel cannot write: it keeps writing the handle's
+// own 6-wide buffer, and k_order_rows fills slot t (rows(t)) when the policy of frame t is about to read it.  `obs`
+// keeps its aliasing.
 class FrameObs {
     zenv *h_;
     float *obs_, *zone_obs_;     // the handle's own
     size_t n_obs_, n_zone_;      // floats per frame
-    void point_at(float *obs, float *zone_obs) const { h_->p.obs = obs, h_->p.zone_obs = zone_obs; }
+    bool assembled_;             // the zone rows of a slot are assembled (zenv_order_rows), not written in place
+    void point_at(float *obs, float *zone_obs) const { h_->p.obs = obs, h_->p.zone_obs = assembled_ ? zone_obs_ : zone_obs; }
 
 public:
     explicit FrameObs(zenv *h)
         : h_(h), obs_(h->p.obs), zone_obs_(h->p.zone_obs), n_obs_((size_t)h->n_env * 8),
-          n_zone_((size_t)h->n_env * h->p.Z * h->p.F) {}
+          n_zone_((size_t)h->n_env * h->p.Z * net_row_feat(h)), assembled_(h->net_feat != 0) {}
     FrameObs(const FrameObs &) = delete;
     ~FrameObs() { point_at(obs_, zone_obs_); }
     int begin() const            // obs_0 into slot 0
     {
         HIP_TRY(hipMemcpyAsync(h_->exp.obs, obs_, n_obs_ * 4, hipMemcpyDeviceToDevice, h_->stream));
-        HIP_TRY(hipMemcpyAsync(h_->exp.zone_obs, zone_obs_, n_zone_ * 4, hipMemcpyDeviceToDevice, h_->stream));
+        if (!assembled_)
+            HIP_TRY(hipMemcpyAsync(h_->exp.zone_obs, zone_obs_, n_zone_ * 4, hipMemcpyDeviceToDevice, h_->stream));
         return ZENV_OK;
     }
+    // where the policy of frame t has its rows assembled; null: they are already in place
+    float *rows(int t) const { return assembled_ ? h_->exp.zone_obs + t * n_zone_ : nullptr; }
     void read(int t) const { point_at(h_->exp.obs + t * n_obs_, h_->exp.zone_obs + t * n_zone_); }
     void write_next(int t, int T) const { t + 1 < T ? read(t + 1) : point_at(obs_, zone_obs_); }
 };
@@ -661,7 +707,7 @@ public:
 // the ZENV_F_EXP_* buffers for T frames (every collector's); self.mask survives a change of T
 static int ensure_exp(zenv_t *h, int T)
 {
-    const size_t N = (size_t)h->n_env, ZF = (size_t)h->p.Z * h->p.F;
+    const size_t N = (size_t)h->n_env, ZF = (size_t)h->p.Z * net_row_feat(h);
     h->exp_hier = false;        // zenv_collect_hier sets it once its records are complete
     h->exp_xy = false;          // zenv_collect_xy, the same
     h->exp_skill = false;       // zenv_collect_skill, the same
@@ -704,13 +750,15 @@ extern "C" int zenv_collect(zenv_t *h, int T, uint64_t policy_seed, uint64_t env
     if (T < 1) return fail(ZENV_E_ARG, "frames_per_proc must be positive");
     if (int rc = collect_ready(h, "zenv_collect", T, T, discount, gae_lambda)) return rc;     // every frame auto-resets
     if (!h->mlp_ready || !h->mlp.wv1) return fail(ZENV_E_STATE, "zenv_mlp_load with actor and critic weights first");
-    if (h->order_enabled)
+    if (h->order_enabled && !h->net_feat)
         return fail(ZENV_E_STATE, "solver-ordered envs are stepped with zenv_step (their order feature is not part of "
-                                  "the network input this call evaluates)");
+                                  "the network input this call evaluates: zenv_order_rows makes it one)");
     if (int rc = use_device(h)) return rc;
     h->act_tag.valid = false;
     if (int rc = ensure_exp(h, T)) return rc;
-    if (h->goal_enabled)
+    // the envs that report info['shaped_reward'] train on it (base.py:159-162); the env reward goes beside it
+    const bool shaped = h->goal_enabled || h->order_enabled;
+    if (shaped)
         if (int rc = eplog_flat_reward(h, T)) return rc;
     const FrameObs frames(h);
     if (int rc = frames.begin()) return rc;
@@ -720,23 +768,23 @@ extern "C" int zenv_collect(zenv_t *h, int T, uint64_t policy_seed, uint64_t env
         // dist, value = acmodel(obs); action = dist.sample(); the head kernel also records frame t (and the reward
         // of frame t-1, still in the env's reward / done buffers)
         const MlpRecord rec{ h->exp.action, h->exp.log_prob, h->exp.value, h->exp.mask, h->exp.reward, h->exp.cur_mask,
-                             h->p.reward, h->goal_enabled ? h->p.shaped : nullptr, h->p.done_out, T, t, h->n_env };
-        if (int rc = run_policy(h, pol, &rec)) return rc;
+                             h->p.reward, shaped ? h->p.shaped : nullptr, h->p.done_out, T, t, h->n_env };
+        if (int rc = run_policy(h, pol, &rec, frames.rows(t))) return rc;
         frames.write_next(t, T);
         HIP_TRY(launch_step(h->p, h->p.actions, 1, no_policy(), h->stream));     // ParallelEnv.step: auto-reset
-        if (h->goal_enabled) {
-            HIP_TRY(launch_goal_step(h->p, h->stream));
+        if (h->goal_enabled) HIP_TRY(launch_goal_step(h->p, h->stream));
+        if (h->order_enabled) HIP_TRY(launch_order_step(h->p, h->stream));
+        if (shaped) {
             // the env reward beside the shaped one the record keeps: zenv_episode_log's return (base.py:169)
             HIP_TRY(hipMemcpyAsync(h->eplog.flat_reward + (size_t)t * h->n_env, h->p.reward, (size_t)h->n_env * 4,
                                    hipMemcpyDeviceToDevice, h->stream));
         }
         h->step_count += 1;
     }
-    HIP_TRY(launch_exp_reward(h->exp, h->n_env, T - 1, h->p.reward, h->goal_enabled ? h->p.shaped : nullptr,
+    HIP_TRY(launch_exp_reward(h->exp, h->n_env, T - 1, h->p.reward, shaped ? h->p.shaped : nullptr,
                               h->p.done_out, h->stream));
     // next_value = value(obs_T) (:177-187), then the GAE recursion
-    HIP_TRY(launch_mlp_forward(h->mlp, h->n_env, h->p.Z, h->p.F, h->p.obs, h->p.zone_obs, h->mlp_pooled, h->mlp_mu,
-                               h->mlp_std, h->mlp_value, h->mlp_value_sigma, no_mlp_action(), h->stream));
+    if (int rc = flat_forward(h, no_mlp_action())) return rc;
     HIP_TRY(launch_exp_gae(h->exp, h->n_env, h->mlp_value, discount, gae_lambda, h->stream));
     h->eplog.source = 1;
     return ZENV_OK;

@@ -183,7 +183,7 @@ FieldInfo field_info(const zenv *h, int field)
     case ZENV_F_AVAILABLE_GOALS: return { p.available, p.available ? N * 4 : 0 };
     case ZENV_F_GOAL: return { p.goal, p.goal ? N * 4 : 0 };
     case ZENV_F_EXP_OBS: return { h->exp.obs, h->exp.obs ? N * h->exp.T * 8 * 4 : 0 };
-    case ZENV_F_EXP_ZONE_OBS: return { h->exp.zone_obs, h->exp.obs ? N * h->exp.T * p.Z * p.F * 4 : 0 };
+    case ZENV_F_EXP_ZONE_OBS: return { h->exp.zone_obs, h->exp.obs ? N * h->exp.T * p.Z * net_row_feat(h) * 4 : 0 };
     case ZENV_F_EXP_ACTION: return { h->exp.action, h->exp.obs ? N * h->exp.T * 2 * 4 : 0 };
     case ZENV_F_EXP_LOG_PROB: return { h->exp.log_prob, h->exp.obs ? N * h->exp.T * 2 * 4 : 0 };
     case ZENV_F_EXP_VALUE: return { h->exp.value, h->exp.obs ? N * h->exp.T * 4 : 0 };
@@ -193,6 +193,8 @@ FieldInfo field_info(const zenv *h, int field)
     case ZENV_F_EXP_RETURN: return { h->exp.returnn, h->exp.obs ? N * h->exp.T * 4 : 0 };
     case ZENV_F_ORDER_VAL: return { p.order_val, p.order_val ? N * p.Z * 4 : 0 };
     case ZENV_F_ORDER_POS: return { p.order_pos, p.order_pos ? N * p.Z : 0 };
+    case ZENV_F_ORDER_ROWS:          // (refresh_field() first)
+        return { h->net_feat ? h->order_rows : nullptr, h->net_feat ? N * p.Z * kOrderRowOut * 4 : 0 };
     case ZENV_F_CHUNK_REWARD: return { h->chunk_reward, h->chunk_reward ? N * h->chunk_steps * 4 : 0 };
     case ZENV_F_CHUNK_DONE: return { h->chunk_done, h->chunk_done ? N * h->chunk_steps : 0 };
     case ZENV_F_CHUNK_ACTIONS: return { h->chunk_actions, h->chunk_actions ? N * h->chunk_host_steps * 8 : 0 };
@@ -278,6 +280,11 @@ int refresh_field(zenv *h, int field)
         if (!h->xy_state_mem) return ZENV_OK;
         HIP_TRY(launch_skill_sync(h->p, h->sst, nullptr, 0, h->stream));
         HIP_TRY(launch_xy_age(h->p, h->sst, h->xy_age, h->stream));
+        return ZENV_OK;
+    }
+    if (field == ZENV_F_ORDER_ROWS) {   // assembled on demand, from the observation as it stands
+        if (h->net_feat)
+            HIP_TRY(launch_order_rows(h->p.zone_obs, h->p.order_val, h->order_rows, (int64_t)h->n_env * h->p.Z, h->stream));
         return ZENV_OK;
     }
     if (field != ZENV_F_EP_RETURN && field != ZENV_F_EP_LEN) return ZENV_OK;
@@ -574,7 +581,7 @@ extern "C" int zenv_destroy(zenv_t *h)
                      (void *)h->p.order_val, h->hier_mem, (void *)h->hier_logits, (void *)h->hier_value,
                      h->hframes_mem, h->hcarry_mem, h->hout_mem, h->skill_mem, h->sst_mem, (void *)h->skill_logits,
                      (void *)h->skill_value, h->skinv_mem, h->sk_mem, h->opt_mem, h->oc_mem, h->xy_mem,
-                     h->xy_state_mem, h->xc_mem })
+                     h->xy_state_mem, h->xc_mem, (void *)h->order_rows })
         if (m) (void)hipFree(m);
     for (hipEvent_t ev : h->events) (void)hipEventDestroy(ev);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
@@ -1004,6 +1011,24 @@ extern "C" int zenv_order_configure(zenv_t *h, int flags)
     return ZENV_OK;
 }
 
+// The flat network on the reference's (Z, 7) rows (TSP_order_env.py:37-47): while on, zenv_mlp_load packs
+// zone_net_.0.weight as [h][8 + 7], the MLP policies, zenv_collect and the flat learner read rows that k_order_rows
+// (K22) assembles from the 6-wide zone rows and the order value.  The switch changes no value the env produces.
+extern "C" int zenv_order_rows(zenv_t *h, int enable)
+{
+    if (!h) return fail(ZENV_E_ARG, "null handle");
+    if (!h->order_enabled)
+        return fail(ZENV_E_STATE, "zenv_order_rows is for solver-ordered handles: zenv_order_enable first");
+    if ((enable != 0) == (h->net_feat != 0)) return ZENV_OK;
+    if (int rc = use_device(h)) return rc;
+    if (int rc = drop_flat_network(h)) return rc;        // drains the stream
+    if (enable && !h->order_rows)
+        HIP_TRY(hipMalloc((void **)&h->order_rows, (size_t)h->n_env * h->p.Z * kOrderRowOut * sizeof(float)));
+    h->net_feat = enable ? h->p.F + 1 : 0;
+    h->act_tag.valid = false;
+    return ZENV_OK;
+}
+
 // ============================================================================ goal-conditioned variant
 extern "C" int zenv_goal_enable(zenv_t *h)
 {
@@ -1193,7 +1218,10 @@ extern "C" int zenv_rollout(zenv_t *h, int steps, int policy, uint64_t policy_se
     if (steps < 0) return fail(ZENV_E_ARG, "steps must be >= 0");
     if (!policy_known(policy)) return fail(ZENV_E_ARG, "unknown policy %d", policy);
     if (policy_is_mlp(policy) && !h->mlp_ready) return fail(ZENV_E_STATE, "zenv_mlp_load first");
-    if (h->goal_enabled || h->order_enabled)
+    // a solver-ordered handle whose network reads the (Z, 7) rows (zenv_order_rows) plays its network here: policy,
+    // step, order step, one launch after the other
+    const bool order_net = h->order_enabled && h->net_feat && policy_is_mlp(policy);
+    if ((h->goal_enabled || h->order_enabled) && !order_net)
         return fail(ZENV_E_STATE, "goal-conditioned / solver-ordered envs are stepped with zenv_step");
     if (int rr = ring_guard(h, steps, auto_reset)) return rr;
     int rc = use_device(h);
@@ -1265,6 +1293,7 @@ extern "C" int zenv_rollout(zenv_t *h, int steps, int policy, uint64_t policy_se
         hipEvent_t e0 = sampled ? h->events[2 + 2 * (t / event_stride)] : nullptr;
         hipEvent_t e1 = sampled ? h->events[3 + 2 * (t / event_stride)] : nullptr;
         HIP_TRY(launch_step(h->p, h->p.actions, auto_reset, next, h->stream, e0, e1));
+        if (order_net) HIP_TRY(launch_order_step(h->p, h->stream));
         h->step_count += 1;
     }
     if (own_bracket) HIP_TRY(hipEventRecord(h->events[1], h->stream));
@@ -1458,7 +1487,8 @@ extern "C" int zenv_device_ptr(zenv_t *h, int field, void **ptr)
     const FieldInfo f = field_info(h, field);
     if (!f.ptr) return fail(ZENV_E_ARG, "unknown field %d", field);
     if (field == ZENV_F_EP_RETURN || field == ZENV_F_EP_LEN || field == ZENV_F_SKILL || field == ZENV_F_SKILL_AGE ||
-        field == ZENV_F_OPTION_ENDED || field == ZENV_F_XY_GOAL || field == ZENV_F_XY_GOAL_AGE) {
+        field == ZENV_F_OPTION_ENDED || field == ZENV_F_XY_GOAL || field == ZENV_F_XY_GOAL_AGE ||
+        field == ZENV_F_ORDER_ROWS) {
         // these two live inside the step kernels' records: the pointer is to a plain copy brought up to date by THIS
         // call (stream-ordered), not a live view
         int rc = use_device(h);
@@ -1700,7 +1730,9 @@ extern "C" int zenv_render(zenv_t *h, const zenv_render_config *rc, int first, i
 {
     if (!h || !rc || !dst) return fail(ZENV_E_ARG, "null argument");
     if (int rv = zenv_render_check(&h->cfg, rc, h->n_env, first, count)) return rv;
-    const int64_t N = h->n_env, ZF = (int64_t)h->p.Z * h->p.F;
+    // the recorded frames of a handle with zenv_order_rows on are 7 wide: read at that stride (the order value is not drawn)
+    const int row_feat = rc->source == ZENV_RENDER_EXPERIENCE ? net_row_feat(h) : h->p.F;
+    const int64_t N = h->n_env, ZF = (int64_t)h->p.Z * row_feat;
     RenderParams rp{};
     if (rc->source == ZENV_RENDER_CURRENT) {
         if (!h->was_reset) return fail(ZENV_E_STATE, "reset first: the handle holds no observation");
@@ -1734,7 +1766,7 @@ extern "C" int zenv_render(zenv_t *h, const zenv_render_config *rc, int first, i
     rp.W = rc->width;
     rp.H = rc->height;
     rp.Z = h->p.Z;
-    rp.F = h->p.F;
+    rp.F = row_feat;
     rp.timed = h->cfg.task == ZENV_TASK_TIMED_TSP;
     rp.view = rc->view;
     rp.sx = (2.0f * rc->view) / (float)rc->width;

@@ -142,7 +142,7 @@ extern "C" int zenv_episode_log(zenv_t *h, zenv_episode_log_info *out)
     switch (e.source) {
     case 1:     // base.py:169-170: the env reward, self.rewards[i] (the shaped reward where the env reports one)
         k.resh = h->exp.reward;
-        k.ret = h->goal_enabled ? e.flat_reward : h->exp.reward;
+        k.ret = h->goal_enabled || h->order_enabled ? e.flat_reward : h->exp.reward;
         break;
     case 2:     // zone-goals / options _hier_policy_opt.py: both sums take the env reward
     case 4:

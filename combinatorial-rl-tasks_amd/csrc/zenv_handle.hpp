@@ -20,6 +20,7 @@
 #include "mlp_policy.hpp"
 #include "episode_log.hpp"
 #include "layout_sample.hpp"
+#include "order_rows.hpp"
 
 using namespace zenvk;
 
@@ -183,6 +184,11 @@ struct zenv {
     // goal-conditioned variant (zenv_goal_enable)
     bool goal_enabled = false;
     bool order_enabled = false;   // solver-ordered variant (zenv_order_enable)
+    // zenv_order_rows: the flat network, its collector and its learner take the reference's (Z, 7) rows -- net_feat, the
+    // handle's network row width, is p.F + 1 while on and p.F otherwise (DevParams knows nothing of it: the step kernels
+    // keep their 6-wide rows); order_rows: ZENV_F_ORDER_ROWS [N][Z][7], assembled by k_order_rows before a network reads it
+    int net_feat = 0;
+    float *order_rows = nullptr;
     int32_t *goal_in = nullptr, *goal_bad = nullptr;
     // experience buffers (zenv_collect)
     ExpBuffers exp{};
@@ -270,12 +276,17 @@ struct zenv {
 };
 
 ZENV_INTERNAL int use_device(const zenv *h);
+// the width of the rows the flat network reads, records and trains on (zenv_order_rows)
+inline int net_row_feat(const zenv *h) { return h->net_feat ? h->net_feat : h->p.F; }
 
 // ---- zenv_agents.cpp, as far as the stepping paths of zenv_api.cpp call it
 inline bool policy_known(int policy) { return policy >= ZENV_POLICY_UNIFORM && policy <= ZENV_POLICY_MLP_SAMPLE; }
 inline bool policy_is_mlp(int policy) { return policy == ZENV_POLICY_MLP_MEAN || policy == ZENV_POLICY_MLP_SAMPLE; }
 // a_t = pi(obs_t, t) into pol.out, for every kind of action source
-ZENV_INTERNAL int run_policy(zenv *h, const StepPolicy &pol, const MlpRecord *rec = nullptr);
+// (rows: where a handle with zenv_order_rows on assembles the rows the network reads, null = ZENV_F_ORDER_ROWS)
+ZENV_INTERNAL int run_policy(zenv *h, const StepPolicy &pol, const MlpRecord *rec = nullptr, float *rows = nullptr);
+// the flat network, the flat learner and the experience buffers go: all three are sized by the network row width
+ZENV_INTERNAL int drop_flat_network(zenv *h);
 // the refusal of a call whose auto-resets could outrun a ring schedule
 ZENV_INTERNAL int ring_guard(const zenv *h, int steps, int auto_reset_every_step);
 // ZENV_E_RANGE once the float16 network kernels have flagged an operand out of range
@@ -297,6 +308,8 @@ ZENV_INTERNAL int eplog_flat_reward(zenv *h, int T);
 
 // ---- zenv_train.cpp
 ZENV_INTERNAL void ppo_free(zenv *h);
+// the flat learner alone (zenv_order_rows: it is sized by the network row width)
+ZENV_INTERNAL void ppo_free_flat(zenv *h);
 // ZENV_E_ARG once an update has met (and dropped) a device-resident index out of range; mlp_range_check() asks
 ZENV_INTERNAL int ppo_index_check(zenv *h);
 // ZENV_F_PPO_STATS (which = 0), ZENV_F_HPPO_LO_STATS (1), ZENV_F_HPPO_HI_STATS (2), ZENV_F_XYPPO_LO_STATS (3),

@@ -302,6 +302,8 @@ static void learner_free(PpoState *&s)
     s = nullptr;
 }
 
+void ppo_free_flat(zenv *h) { learner_free(h->ppo); }
+
 void ppo_free(zenv *h)
 {
     learner_free(h->ppo);
@@ -359,9 +361,11 @@ static int learner_create(zenv *h, PpoState *&slot, int h_dim, const float *cons
     PpoState *s = new PpoState();
     slot = s;
     PpoNet &n = s->net;
-    const Layout l = layout_for(h_dim, h->p.Z, h->p.F, pc->max_batch, k);
-    n.h = h_dim, n.HP = l.HP, n.F = h->p.F, n.Z = h->p.Z, n.K1 = k.XD + h->p.F, n.KC = l.KC;
-    n.XD = k.XD, n.W1C = k.w1c(h->p.F), n.head = k.head, n.loss = k.loss, n.S = k.S, n.NA = k.NA, n.LDC = l.LDC;
+    // the flat learner trains on the rows the flat network reads (zenv_order_rows: 7 wide on a solver-ordered handle)
+    const int F = &slot == &h->ppo ? net_row_feat(h) : h->p.F;
+    const Layout l = layout_for(h_dim, h->p.Z, F, pc->max_batch, k);
+    n.h = h_dim, n.HP = l.HP, n.F = F, n.Z = h->p.Z, n.K1 = k.XD + F, n.KC = l.KC;
+    n.XD = k.XD, n.W1C = k.w1c(F), n.head = k.head, n.loss = k.loss, n.S = k.S, n.NA = k.NA, n.LDC = l.LDC;
     const bool inverse = k.head == PPO_HEAD_INVERSE;    // no critic: cr names a tensor that exists and is never read
     n.cr = inverse ? 0 : k.head != PPO_HEAD_GAUSSIAN ? PPO_CRITIC_W1 - 2 : PPO_CRITIC_W1;
     n.split_reduce = k.flat() ? 0 : 1;                  // the hierarchical agents' learners

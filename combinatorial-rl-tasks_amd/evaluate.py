@@ -45,8 +45,14 @@ def evaluate(env_id, policy, n_maps=100, n_runs_per_map=5, env_seed0=EVAL_SEED0,
     2 048 envs and more -- smaller ones run the float32 vector kernel either way) "bf16" (the MFMA kernels, 8x faster) or "f16" (the same kernels on
     float16 operands: within 1e-3, float16's range guarded).
 
+    env_id: a registry id or a Config.  An id whose class is ``TSPOrderEnv`` ("PointTSP-v2", the results table's
+    "Solver" row) is the task env of its config with ``enable_order()`` and ``order_rows()`` on: the network -- and a
+    host policy -- sees the reference's (Z, 7) rows (main/envs/TSP_order_env.py:37-47), so the state_dict's
+    ``zone_net_.0.weight`` is [h, 15].
+
     Returns ``{"return": [[...]], "length": [[...]], "goal_met": [[...]]}``."""
-    cfg = config_for_id(env_id) if isinstance(env_id, str) else env_id
+    base_id = order_base_id(env_id) if isinstance(env_id, str) else None
+    cfg = config_for_id(base_id or env_id) if isinstance(env_id, str) else env_id
     if isinstance(policy, str):
         policy = load_model_state(policy)
     tensors = None
@@ -56,6 +62,11 @@ def evaluate(env_id, policy, n_maps=100, n_runs_per_map=5, env_seed0=EVAL_SEED0,
         policy = nat.POLICY_MLP_MEAN if argmax else nat.POLICY_MLP_SAMPLE
     o = zo = None                          # a host policy's next input: the last step's observations
 
+    def prepare(env):                      # routes ride in the bank: before it is built
+        if base_id:
+            env.enable_order()
+            env.order_rows()
+
     def setup(env):
         nonlocal o, zo
         env.reset()
@@ -63,14 +74,34 @@ def evaluate(env_id, policy, n_maps=100, n_runs_per_map=5, env_seed0=EVAL_SEED0,
             env.load_mlp(tensors, precision=precision)
         if callable(policy):
             o, zo = env.step_results(None, copy=False)[:2]
+            if base_id:
+                zo = env.get(nat.F_ORDER_ROWS)
 
     def host_step(env):                    # one upload, one launch, one download, one synchronisation per step
         nonlocal o, zo
         o, zo, _, d, g, _ = env.step_results(np.asarray(policy(o, zo), np.float32), auto_reset=False, copy=False)
+        if base_id:
+            zo = env.get(nat.F_ORDER_ROWS)
         return d, g
 
     return _run_batched(cfg, n_maps, n_runs_per_map, env_seed0, device, max_steps, pkl_path, setup,
-                        host_step if callable(policy) else _device_step(policy, policy_seed))
+                        host_step if callable(policy) else _device_step(policy, policy_seed), prepare)
+
+
+def order_base_id(env_id):
+    """The registry id of the plain task env a solver-ordered id is built on -- same config, class ``TSPEnv`` --
+    ("PointTSP-v2" -> "PointTSP-v0"), or None for an id whose class is not ``TSPOrderEnv`` and for a Config."""
+    from .envs.registry import REGISTRY
+    from .envs.zone_envs import TSPEnv, TSPOrderEnv
+    if not isinstance(env_id, str):                          # a Config: the caller switches variants on himself
+        return None
+    cls, config = REGISTRY.get(env_id, (None, None))
+    if cls is None or not issubclass(cls, TSPOrderEnv):
+        return None
+    for other, (c, conf) in REGISTRY.items():
+        if c is TSPEnv and conf is config:
+            return other
+    raise RuntimeError(f"{env_id}: no plain TSP id with the same config")
 
 
 def _device_step(policy, policy_seed):
@@ -82,15 +113,18 @@ def _device_step(policy, policy_seed):
     return step
 
 
-def _run_batched(cfg, n_maps, n_runs_per_map, env_seed0, device, max_steps, pkl_path, setup, step):
+def _run_batched(cfg, n_maps, n_runs_per_map, env_seed0, device, max_steps, pkl_path, setup, step, prepare=None):
     """The protocol all evaluators share: one env per map and run (the maps of env seeds env_seed0 ..), every episode
     run once, to the horizon or until all are done.  setup(env) switches the variant on, resets and loads the agent;
-    step(env) advances every env by one step without auto-reset and returns that step's (done, goal_met).  Returns
+    step(env) advances every env by one step without auto-reset and returns that step's (done, goal_met);
+    prepare(env), when given, runs before the bank is built (a variant whose routes ride in it).  Returns
     ``{"return": [[...]], "length": [[...]], "goal_met": [[...]]}``, [map][run], and writes ``{"return": ...}`` to
     ``pkl_path`` as the reference's scripts do (evaluate.py:76-78)."""
     n = n_maps * n_runs_per_map
     env = ZoneVecEnv(cfg, n, device=device)
     try:
+        if prepare is not None:
+            prepare(env)
         env.build_bank(env_seed0, n_maps)
         env.schedule_sequential(first=np.repeat(np.arange(n_maps, dtype=np.int32), n_runs_per_map), stride=0)
         setup(env)

@@ -85,6 +85,26 @@ class TorchZoneEnv:
         self.env.reset(mask)
         return {"obs": self.obs, "zone_obs": self.zone_obs}
 
+    def order_rows(self, enable=True):
+        """``ZoneVecEnv.order_rows``: the flat network, ``collect`` (``zone_obs [N, T, Z, 7]``, the shaped reward) and the
+        ``ppo_*`` calls on the reference's (Z, 7) rows of a solver-ordered handle.  ``self.zone_obs`` stays the 6-wide
+        alias; ``net_rows`` shows what the network reads."""
+        self.env.order_rows(enable)
+
+    @property
+    def net_zone_feat(self):
+        """``ZoneVecEnv.net_zone_feat``: the width of the rows the flat network reads (7 with ``order_rows()`` on)."""
+        return self.env.net_zone_feat
+
+    @property
+    def net_rows(self):
+        """The rows the flat network reads, float32 ``(N, Z, net_zone_feat)``: ``zone_obs`` itself, or with
+        ``order_rows()`` on the (Z, 7) rows assembled as of this access (``_native.F_ORDER_ROWS``, stream-ordered)."""
+        if self.env.net_zone_feat == self.env.zone_feat:
+            return self.zone_obs
+        with self._torch.cuda.device(self.device):
+            return self._alias(nat.F_ORDER_ROWS)
+
     def load_state_dict(self, state_dict, precision="auto"):
         """Put an ACModel state_dict (main/src/flat_model.py:24-52 names; torch tensors on any device) into the
         device actor-critic that ``collect`` and the ``POLICY_MLP_*`` action sources run.  precision: see
@@ -149,7 +169,7 @@ class TorchZoneEnv:
     def ppo_views(self, which=nat.PPO_PARAM):
         """zenv_mlp_weights name -> CUDA tensor ALIASING that tensor of an arena, in its state_dict shape."""
         from .vec_env import mlp_tensor_shapes
-        shapes = mlp_tensor_shapes(self.env._ppo_h, self.env.zone_feat)
+        shapes = mlp_tensor_shapes(self.env._ppo_h, self.env.net_zone_feat)
         with self._torch.cuda.device(self.device):
             return {name: self._alias_ptr(self.env.ppo_tensor_ptr(which, i)[0], shapes[name])
                     for i, name in enumerate(self.env._ppo_keys)}

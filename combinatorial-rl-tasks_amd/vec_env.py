@@ -51,7 +51,7 @@ _FIELD_DTYPES = {
     nat.F_XYPPO_LO_STATS: np.float32, nat.F_XYPPO_HI_STATS: np.float32,
     nat.F_SKPPO_LO_STATS: np.float32, nat.F_SKPPO_HI_STATS: np.float32,
     nat.F_OPPPO_LO_STATS: np.float32, nat.F_OPPPO_HI_STATS: np.float32,
-    nat.F_DIAYN_STATS: np.float32, nat.F_DIAYN_SAMPLES: np.int32,
+    nat.F_DIAYN_STATS: np.float32, nat.F_DIAYN_SAMPLES: np.int32, nat.F_ORDER_ROWS: np.float32,
 }
 
 
@@ -618,6 +618,24 @@ class ZoneVecEnv:
         check(lib().zenv_order_enable(self._h))
         check(lib().zenv_order_configure(self._h, nat.ORDER_FRESH_FIRST_OBS if fresh_route_in_first_obs else 0))
 
+    def order_rows(self, enable=True):
+        """The flat network on the reference's (Z, 7) rows (zenv_order_rows; TSP_order_env.py:37-47): while on,
+        ``net_zone_feat`` is 7 and ``load_mlp``, ``mlp_forward``, the MLP policies of ``policy`` / ``rollout``,
+        ``collect`` and the ``ppo_*`` calls take rows of [zone_obs row (6), order value]; ``get(F_ORDER_ROWS)`` shows
+        them.  ``collect`` then records float32(shaped_reward) as the reward (base.py:159-162).  Toggling drops the loaded
+        network, the flat learner and the experience buffers: load them again.  ZenvError(E_STATE) unless
+        ``enable_order()`` came first."""
+        check(lib().zenv_order_rows(self._h, int(bool(enable))))
+        if bool(enable) != getattr(self, "_order_rows", False):      # (no change: nothing was dropped)
+            self._learners.pop(None, None)
+        self._order_rows = bool(enable)
+
+    @property
+    def net_zone_feat(self):
+        """The width of the zone rows the flat network reads, records and trains on: ``zone_feat``, or 7 on a
+        solver-ordered handle with ``order_rows()`` on."""
+        return self.zone_feat + (1 if getattr(self, "_order_rows", False) else 0)
+
     def order_info(self):
         """(shaped_reward float64 [N], order feature float32 [N,Z] of the last observation: 0.5^(position in the route
         that observation saw))."""
@@ -703,13 +721,18 @@ class ZoneVecEnv:
                 self.load_mlp(tensors, precision="f32")
             return
         h = int(np.asarray(tensors["zone_b1"]).shape[0])
+        cols = np.asarray(tensors["zone_w1"]).shape[-1]
+        if cols != 8 + self.net_zone_feat:
+            raise ValueError(f"zone_w1 has {cols} input columns, this handle's network reads 8 + {self.net_zone_feat}"
+                             " (obs + a zone row" + (" with the order value: order_rows() is on)"
+                                                     if self.net_zone_feat != self.zone_feat else ")"))
         w = nat.MlpWeights(h_dim=h, precision={"bf16": nat.MLP_BF16, "f32": nat.MLP_F32, "bf16x3": nat.MLP_BF16X3,
                                                    "f16x3": nat.MLP_F16X3, "f16": nat.MLP_F16}[precision])
         names = nat.MLP_TENSORS + (nat.MLP_CRITIC_TENSORS if "critic_w1" in tensors else ()) + (
             nat.MLP_SIGMA_TENSORS if "critic_sigma_w" in tensors else ())
         self._mlp_has_critic = "critic_w1" in tensors
         self._mlp_distributional = "critic_sigma_w" in tensors
-        keep = self._load_weights(w, names, tensors, mlp_tensor_shapes(h, self.zone_feat))   # alive across the load
+        keep = self._load_weights(w, names, tensors, mlp_tensor_shapes(h, self.net_zone_feat))   # alive across the load
         check(lib().zenv_mlp_load(self._h, C.byref(w)))
         self.mlp_precision = precision
 
@@ -1004,7 +1027,7 @@ class ZoneVecEnv:
 
     def _experience_rows(self, frames_per_proc):
         """The same buffers as name -> (field id, shape in memory, dtype), the form of the agents' layouts."""
-        return _lo_rows(self.num_envs, self.num_zones, self.zone_feat, int(frames_per_proc))
+        return _lo_rows(self.num_envs, self.num_zones, self.net_zone_feat, int(frames_per_proc))
 
     # ------------------------------------------------------------------ the collectors' per-episode logs (K20)
     def episode_log_on_device(self):
@@ -1071,7 +1094,7 @@ class ZoneVecEnv:
         h = int(np.asarray(tensors["zone_b1"]).shape[0])
         w = nat.MlpWeights(h_dim=h, precision=nat.MLP_F32)
         names = [n for n in nat.MLP_TENSORS + nat.MLP_CRITIC_TENSORS + nat.MLP_SIGMA_TENSORS if n in tensors]
-        keep = self._load_weights(w, names, tensors, mlp_tensor_shapes(h, self.zone_feat))   # alive across the call
+        keep = self._load_weights(w, names, tensors, mlp_tensor_shapes(h, self.net_zone_feat))   # alive across the call
         pc = nat.PpoConfig(lr=lr, adam_eps=adam_eps, clip_eps=clip_eps, entropy_coef=entropy_coef,
                            value_loss_coef=value_loss_coef, max_grad_norm=max_grad_norm, max_batch=int(max_batch),
                            distributional_value=int(bool(distributional_value)))
@@ -1079,7 +1102,7 @@ class ZoneVecEnv:
         del keep
         self._ppo_h = h
         self._ppo_keys = ppo_state_dict_keys(bool(distributional_value))
-        self._learners[None] = _Learner(self._h, None, self._ppo_keys, mlp_tensor_shapes(h, self.zone_feat), lr,
+        self._learners[None] = _Learner(self._h, None, self._ppo_keys, mlp_tensor_shapes(h, self.net_zone_feat), lr,
                                         adam_eps, nat.F_PPO_STATS)
         self.ppo_batch_num = 0          # PPOAlgo.batch_num (ppo.py:28)
 
@@ -1887,6 +1910,8 @@ class ZoneVecEnv:
             return (N, getattr(self, "_skill_n", 0))
         if field == nat.F_ZONE_OBS:
             return (N, self.num_zones, self.zone_feat)
+        if field == nat.F_ORDER_ROWS:           # empty while order_rows() is off
+            return (N if self.net_zone_feat != self.zone_feat else 0, self.num_zones, self.zone_feat + 1)
         if field in (nat.F_ACTIONS, nat.F_POLICY_MU, nat.F_POLICY_STD, nat.F_XY_GOAL, nat.F_XY_GOAL_MU,
                      nat.F_XY_GOAL_STD, nat.F_XY_BOOTSTRAP_GOAL):
             return (N, 2)
@@ -1896,6 +1921,8 @@ class ZoneVecEnv:
         if out is None:
             out = np.empty(self._shape(field), _FIELD_DTYPES[field])
         assert out.nbytes == lib().zenv_field_bytes(self._h, field)
+        if field == nat.F_ORDER_ROWS and out.nbytes == 0:
+            return out
         check(lib().zenv_get(self._h, field, out.ctypes.data, 0))
         return out
 

@@ -12,6 +12,10 @@ into either.
 ``--device-update`` (off by default) runs the update in the library's own HIP kernels instead (``ppo_init`` /
 ``ppo_update`` / ``ppo_publish``: float32 forward, loss, backward, clip and Adam on the handle's experience buffers);
 the torch module then only provides the initial parameters and receives the trained ones at the end.
+
+``--env PointTSP-v2`` trains the results table's "Solver" agent (main/envs/TSP_order_env.py): the handle is
+solver-ordered with ``order_rows()`` on, so the network reads the (Z, 7) rows and the collection records the shaped
+reward; ``--fresh-layouts`` then has the device solve the routes of the maps it samples (``order_routes_device``).
 """
 import argparse
 import os
@@ -24,6 +28,7 @@ import torch.nn as nn
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import combinatorial_rl_tasks_amd as Z  # noqa: E402
 from combinatorial_rl_tasks_amd.agents import episode_log_history  # noqa: E402
+from combinatorial_rl_tasks_amd.evaluate import order_base_id  # noqa: E402
 from combinatorial_rl_tasks_amd.torch_interop import TorchZoneEnv  # noqa: E402
 
 
@@ -100,7 +105,13 @@ def train(env_id="PointTSP-v0", procs=4096, frames_per_proc=64, updates=10, epoc
           hidden=185, seed=1, log=print, device_update=False, fresh_layouts=False, device_deadlines=False):
     torch.manual_seed(seed)
     dev = torch.device("cuda", 0)
-    env = Z.ZoneVecEnv(env_id, procs)
+    base_id = order_base_id(env_id)         # a TSPOrderEnv id (PointTSP-v2): its task env, solver-ordered
+    env = Z.ZoneVecEnv(base_id or env_id, procs)
+    if base_id:
+        env.enable_order()                  # before the bank: the routes ride in it
+        env.order_rows()                    # the network reads the (Z, 7) rows, the collection records the shaped reward
+        if fresh_layouts:
+            env.order_routes_device()       # the wave that samples a map solves its tour
     if device_deadlines:
         # TimedTSP env ids: the deadlines are drawn on the device too, through the shared det_log (numpy's deadlines
         # unless beta * num_steps is within a few ulps of an integer); without it ring_stream refuses the handle
@@ -121,7 +132,7 @@ def train(env_id="PointTSP-v0", procs=4096, frames_per_proc=64, updates=10, epoc
     tenv.reset()
     if fresh_layouts:
         env.ring_refill()                       # the reset took episode 0 of every ring: a map like any other
-    model = ActorCritic(env.zone_feat, hidden).to(dev)
+    model = ActorCritic(env.net_zone_feat, hidden).to(dev)
     opt = torch.optim.Adam(model.parameters(), lr, eps=1e-8)
     gen = torch.Generator(device=dev).manual_seed(seed)
     history = []

@@ -202,7 +202,13 @@ enum {
      */
     ZENV_F_DIAYN_STATS = 83,        /* float32 [minibatches][6] column 0 the cross-entropy loss, 5 the gradient norm, 1-4 = 0 */
     ZENV_F_DIAYN_SAMPLES = 84,      /* int32   [count]          the kept sample indexes, ascending (= env-major) */
-    ZENV_F_COUNT = 85
+    /* a solver-ordered handle's network rows (zenv_order_rows): 0 bytes while the switch is off.  Before this field,
+     * ZENV_F_COUNT = 85
+     */
+    ZENV_F_ORDER_ROWS = 85,         /* float32 [N,Z,7]  TSPOrderEnv's observation rows (TSP_order_env.py:37-47): row z =
+                                     * [ZENV_F_ZONE_OBS row z (6), ZENV_F_ORDER_VAL z], the exact bits of both as they stand
+                                     * when the field is asked for */
+    ZENV_F_COUNT = 86
 };
 
 /* scripted on-device action sources (the build's own; used by bench/tests) */
@@ -512,7 +518,7 @@ int zenv_solver_goals(zenv_t *h, int32_t *goals);
  * solved without OR-tools, which the reference calls at :49-50 and which is not available), zenv_bank_set takes the caller's.
  * Every zenv_step() then also yields info['shaped_reward'] (ZENV_F_SHAPED_REWARD, :63-72) and the order feature
  * of every zone (ZENV_F_ORDER_VAL, :37-47) -- the reference's (Z,7) row is [zone_obs row (6), order value].
- * Exclusive with zenv_goal_enable; zenv_rollout() is refused on such a handle. */
+ * Exclusive with zenv_goal_enable; zenv_rollout() is refused on such a handle (but see zenv_order_rows). */
 int zenv_order_enable(zenv_t *h);
 /* First observation of an episode.  Default (flags 0) = the reference's: TSPOrderEnv.reset() builds init_obs BEFORE
  * generate_route() (TSP_order_env.py:108-113), so the observation returned by reset() -- and by ParallelEnv's auto-reset,
@@ -556,6 +562,27 @@ int zenv_route_ranks_device(zenv_t *h, const double *robot_xy, const double *zon
  * zenv_bank_set: a handle whose routes come from another solver must stay off.  ZENV_E_ARG on a handle that is not
  * solver-ordered (zenv_order_enable first). */
 int zenv_order_routes_device(zenv_t *h, int enable);
+/* ---- the flat agent on a solver-ordered handle (K22): the results table's "Solver" row ----
+ * That agent is the flat actor-critic on TSPOrderEnv's (Z, 7) rows -- the six features of the zone row plus
+ * 0.5^(position in the solver's route), TSP_order_env.py:37-47 -- trained on info['shaped_reward']
+ * (main/src/torch_ac/algos/base.py:159-162).  While enabled, the handle's NETWORK ROW WIDTH is 7 instead of
+ * zenv_zone_feat() = 6 and every flat-network path takes such rows:
+ *   zenv_mlp_load          packs zone_net_.0.weight as [h][8 + 7] (the float16 range rule holds: the order value is in [0, 1]);
+ *   zenv_mlp_forward, zenv_policy(ZENV_POLICY_MLP_MEAN / _SAMPLE)   evaluate the network on the rows of the current
+ *                          observation, which one launch assembles first (ZENV_F_ORDER_ROWS holds them afterwards);
+ *   zenv_rollout           accepts the handle with the two MLP policies: policy, step, order step per step, no persistent
+ *                          kernel; scripted policies keep the refusal;
+ *   zenv_collect           accepts the handle: ZENV_F_EXP_ZONE_OBS is [T,N,Z,7], ZENV_F_EXP_REWARD is
+ *                          float32(shaped_reward) as on a goal-conditioned handle, and zenv_episode_log's return sums the
+ *                          env reward, its reshaped return the shaped one (base.py:169-170);
+ *   zenv_ppo_init / _minibatch / _apply / _epoch   train that network (zone_w1 [h][15]);
+ *   zenv_render            ZENV_RENDER_EXPERIENCE reads the recorded rows at their stride of 7 (the order value is not
+ *                          drawn: the frames are what a 6-wide record of the same observations gives).
+ * ZENV_F_ZONE_OBS, the stepping calls and every value the env produces are unchanged, and a handle that never calls
+ * this pays nothing: the rows are assembled only where a network is about to read them.
+ * Toggling drops the loaded flat network, the flat learner and the experience buffers -- all three are sized by the
+ * width -- and callers load them again.  ZENV_E_STATE unless zenv_order_enable came first. */
+int zenv_order_rows(zenv_t *h, int enable);
 
 /* ---- the reference's actor network on the device ----
  * ZoneEnvModel (main/src/env_model.py:48-79) + the actor of ACModel (flat_model.py:24-37,
