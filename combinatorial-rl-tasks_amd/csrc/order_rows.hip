@@ -49,7 +49,58 @@ __global__ __launch_bounds__(256) void k_order_rows(const float *__restrict__ zo
     }
 }
 
+// One lane per env, like K7 (order_rows.hpp: OrderWait).
+__global__ __launch_bounds__(256) void k_order_wait(const uint8_t *__restrict__ done_out, const Sched *__restrict__ sched,
+                                                    uint8_t *__restrict__ seen, float *__restrict__ order_val,
+                                                    double *__restrict__ shaped, int n, int zones)
+{
+    const int env = blockIdx.x * blockDim.x + threadIdx.x;
+    if (env >= n) return;
+    const bool left_alone = done_out[env] != 0 && sched[env].done_state != 0;
+    if (!left_alone) {
+        seen[env] = 0;
+    } else if (!seen[env]) {
+        seen[env] = 1;                                  // the finishing step: its observation is the real one
+    } else {
+        float *val = order_val + (size_t)env * zones;
+        for (int z = 0; z < zones; ++z) val[z] = 0.f;
+        shaped[env] = 0.0;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_order_wait_clear(uint8_t *__restrict__ seen, const uint8_t *__restrict__ mask, int n)
+{
+    const int env = blockIdx.x * blockDim.x + threadIdx.x;
+    if (env < n && mask[env]) seen[env] = 0;
+}
+
 }  // namespace
+
+hipError_t order_wait_after_step(OrderWait &w, const DevParams &p, int auto_reset, hipStream_t s)
+{
+    if (!w.seen) return hipErrorInvalidValue;
+    if (auto_reset) {
+        if (!w.live) return hipSuccess;
+        w.live = false;                                 // every waiting env came back with this step
+        return hipMemsetAsync(w.seen, 0, (size_t)p.N, s);
+    }
+    w.live = true;
+    hipLaunchKernelGGL(k_order_wait, dim3((p.N + 255) / 256), dim3(256), 0, s, p.done_out, p.sched, w.seen, p.order_val,
+                       p.shaped, p.N, p.Z);
+    return hipGetLastError();
+}
+
+hipError_t order_wait_after_reset(OrderWait &w, const DevParams &p, const uint8_t *mask, hipStream_t s)
+{
+    if (!w.seen) return hipErrorInvalidValue;
+    if (!w.live) return hipSuccess;
+    if (!mask) {
+        w.live = false;
+        return hipMemsetAsync(w.seen, 0, (size_t)p.N, s);
+    }
+    hipLaunchKernelGGL(k_order_wait_clear, dim3((p.N + 255) / 256), dim3(256), 0, s, w.seen, mask, p.N);
+    return hipGetLastError();
+}
 
 hipError_t launch_order_rows(const float *zone_obs, const float *order_val, float *dst, int64_t rows, hipStream_t s)
 {

@@ -773,7 +773,10 @@ extern "C" int zenv_collect(zenv_t *h, int T, uint64_t policy_seed, uint64_t env
         frames.write_next(t, T);
         HIP_TRY(launch_step(h->p, h->p.actions, 1, no_policy(), h->stream));     // ParallelEnv.step: auto-reset
         if (h->goal_enabled) HIP_TRY(launch_goal_step(h->p, h->stream));
-        if (h->order_enabled) HIP_TRY(launch_order_step(h->p, h->stream));
+        if (h->order_enabled) {
+            HIP_TRY(launch_order_step(h->p, h->stream));
+            HIP_TRY(order_wait_after_step(h->order_wait, h->p, 1, h->stream));
+        }
         if (shaped) {
             // the env reward beside the shaped one the record keeps: zenv_episode_log's return (base.py:169)
             HIP_TRY(hipMemcpyAsync(h->eplog.flat_reward + (size_t)t * h->n_env, h->p.reward, (size_t)h->n_env * 4,

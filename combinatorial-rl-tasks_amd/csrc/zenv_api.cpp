@@ -581,7 +581,7 @@ extern "C" int zenv_destroy(zenv_t *h)
                      (void *)h->p.order_val, h->hier_mem, (void *)h->hier_logits, (void *)h->hier_value,
                      h->hframes_mem, h->hcarry_mem, h->hout_mem, h->skill_mem, h->sst_mem, (void *)h->skill_logits,
                      (void *)h->skill_value, h->skinv_mem, h->sk_mem, h->opt_mem, h->oc_mem, h->xy_mem,
-                     h->xy_state_mem, h->xc_mem, (void *)h->order_rows })
+                     h->xy_state_mem, h->xc_mem, (void *)h->order_rows, (void *)h->order_wait.seen })
         if (m) (void)hipFree(m);
     for (hipEvent_t ev : h->events) (void)hipEventDestroy(ev);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
@@ -926,7 +926,10 @@ extern "C" int zenv_reset(zenv_t *h, const uint8_t *mask)
     h->act_tag.valid = false;
     HIP_TRY(launch_reset(h->p, dmask, h->stream));
     if (h->goal_enabled) HIP_TRY(launch_goal_clear(h->p, dmask, h->stream));
-    if (h->order_enabled) HIP_TRY(launch_order_reset(h->p, dmask, h->stream));
+    if (h->order_enabled) {
+        HIP_TRY(launch_order_reset(h->p, dmask, h->stream));
+        HIP_TRY(order_wait_after_reset(h->order_wait, h->p, dmask, h->stream));
+    }
     if (h->hcarry_mem) HIP_TRY(launch_hier_reset(h->hcarry, dmask, h->n_env, h->stream));
     if (h->sst_mem) HIP_TRY(launch_skill_sync(h->p, h->sst, dmask, 1, h->stream));
     h->was_reset = true;
@@ -956,7 +959,10 @@ extern "C" int zenv_step(zenv_t *h, const float *actions, int actions_on_device,
     }
     HIP_TRY(launch_step(h->p, d_act, auto_reset, no_policy(), h->stream));
     if (h->goal_enabled) HIP_TRY(launch_goal_step(h->p, h->stream));
-    if (h->order_enabled) HIP_TRY(launch_order_step(h->p, h->stream));
+    if (h->order_enabled) {
+        HIP_TRY(launch_order_step(h->p, h->stream));
+        HIP_TRY(order_wait_after_step(h->order_wait, h->p, auto_reset, h->stream));
+    }
     h->step_count += 1;
     return ZENV_OK;
 }
@@ -990,6 +996,8 @@ extern "C" int zenv_order_enable(zenv_t *h)
     HIP_TRY(hipMalloc((void **)&p.shaped, N * 8));
     HIP_TRY(hipMalloc((void **)&p.order_pos, N * Z));
     HIP_TRY(hipMalloc((void **)&p.order_val, N * Z * 4));
+    HIP_TRY(hipMalloc((void **)&h->order_wait.seen, N));
+    HIP_TRY(hipMemsetAsync(h->order_wait.seen, 0, N, h->stream));
     HIP_TRY(hipMemsetAsync(p.term_xy, 0, N * 16, h->stream));
     HIP_TRY(hipMemsetAsync(p.goal_xy, 0, N * 16, h->stream));
     HIP_TRY(hipMemsetAsync(p.goal_last, 0, N * 8, h->stream));
@@ -1202,7 +1210,10 @@ extern "C" int zenv_step_many(zenv_t *h, const float *actions, int actions_on_de
         const int ar = reset_mode == ZENV_CHUNK_RESET_EVERY || (reset_mode == ZENV_CHUNK_RESET_LAST && t == n_steps - 1);
         HIP_TRY(launch_step(h->p, d_act + 2 * N * (size_t)t, ar, no_policy(), h->stream));
         if (h->goal_enabled) HIP_TRY(launch_goal_step(h->p, h->stream));
-        if (h->order_enabled) HIP_TRY(launch_order_step(h->p, h->stream));
+        if (h->order_enabled) {
+            HIP_TRY(launch_order_step(h->p, h->stream));
+            HIP_TRY(order_wait_after_step(h->order_wait, h->p, ar, h->stream));
+        }
         HIP_TRY(hipMemcpyAsync(h->chunk_reward + (size_t)t * N, h->p.reward, N * sizeof(float), hipMemcpyDefault, h->stream));
         HIP_TRY(hipMemcpyAsync(h->chunk_done + (size_t)t * N, h->p.done_out, N, hipMemcpyDefault, h->stream));
         h->step_count += 1;
@@ -1293,7 +1304,10 @@ extern "C" int zenv_rollout(zenv_t *h, int steps, int policy, uint64_t policy_se
         hipEvent_t e0 = sampled ? h->events[2 + 2 * (t / event_stride)] : nullptr;
         hipEvent_t e1 = sampled ? h->events[3 + 2 * (t / event_stride)] : nullptr;
         HIP_TRY(launch_step(h->p, h->p.actions, auto_reset, next, h->stream, e0, e1));
-        if (order_net) HIP_TRY(launch_order_step(h->p, h->stream));
+        if (order_net) {
+            HIP_TRY(launch_order_step(h->p, h->stream));
+            HIP_TRY(order_wait_after_step(h->order_wait, h->p, auto_reset, h->stream));
+        }
         h->step_count += 1;
     }
     if (own_bracket) HIP_TRY(hipEventRecord(h->events[1], h->stream));

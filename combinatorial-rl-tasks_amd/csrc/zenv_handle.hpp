@@ -189,6 +189,7 @@ struct zenv {
     // keep their 6-wide rows); order_rows: ZENV_F_ORDER_ROWS [N][Z][7], assembled by k_order_rows before a network reads it
     int net_feat = 0;
     float *order_rows = nullptr;
+    OrderWait order_wait{};       // WaitWrapper's zero order column for envs left alone by zenv_step(auto_reset 0), order_rows.hpp
     int32_t *goal_in = nullptr, *goal_bad = nullptr;
     // experience buffers (zenv_collect)
     ExpBuffers exp{};

@@ -518,7 +518,13 @@ int zenv_solver_goals(zenv_t *h, int32_t *goals);
  * solved without OR-tools, which the reference calls at :49-50 and which is not available), zenv_bank_set takes the caller's.
  * Every zenv_step() then also yields info['shaped_reward'] (ZENV_F_SHAPED_REWARD, :63-72) and the order feature
  * of every zone (ZENV_F_ORDER_VAL, :37-47) -- the reference's (Z,7) row is [zone_obs row (6), order value].
- * Exclusive with zenv_goal_enable; zenv_rollout() is refused on such a handle (but see zenv_order_rows). */
+ * Exclusive with zenv_goal_enable; zenv_rollout() is refused on such a handle (but see zenv_order_rows).
+ * ZENV_F_ORDER_VAL belongs to the observation and follows it: the feature of the route as the step left it; on the
+ * step that ends an episode without an auto-reset the terminal observation's; and ALL ZERO, like ZENV_F_OBS and
+ * ZENV_F_ZONE_OBS, for an env that had finished before the step and was left alone (zenv_step with auto_reset 0:
+ * WaitWrapper.step, main/envs/wrappers.py:34-50, returns a zero (Z,7) zone_obs, reward 0, done and an empty info, so
+ * ZENV_F_SHAPED_REWARD is 0 as well) -- and with it column 6 of ZENV_F_ORDER_ROWS.  ZENV_F_ORDER_POS is state, not
+ * observation: a waiting env keeps the route its last step left, which the next reset's first observation shows. */
 int zenv_order_enable(zenv_t *h);
 /* First observation of an episode.  Default (flags 0) = the reference's: TSPOrderEnv.reset() builds init_obs BEFORE
  * generate_route() (TSP_order_env.py:108-113), so the observation returned by reset() -- and by ParallelEnv's auto-reset,

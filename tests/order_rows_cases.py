@@ -8,7 +8,12 @@ Layouts (``set_bank``): every even env starts at the centre of its zone 0 -- the
 zone are pinned to the same point, keep-outs off -- so it visits that zone on its first step whatever the action (a
 step moves the robot a few millimetres, a zone's radius is 0.2), and again after the auto-reset, on the fifth; every
 odd env has the plain config's layout of its seed.  Routes: the built-in tour for envs 0, 1 mod 4, a fixed permutation
-for the others.  test_order_rows_layouts_cpu.py checks on the CPU oracle that these layouts visit and reset as said."""
+for the others.  test_order_rows_layouts_cpu.py checks on the CPU oracle that these layouts visit and reset as said.
+
+Edge shapes (CASES, for test_gpu_order_edges.py): the same layouts and routes at batch sizes and zone counts that move
+K22's 16-byte store grid, K7's 256-thread launch edge and the zone loop's ends; ``lead_tail`` says which pieces K22
+writes for frame slot t of a collection.  Zone counts without a registry id come from ``default_config(0, zones)``, with
+zones_keepout = 0.30 at 32 zones (the default keep-out leaves no room for 32)."""
 import numpy as np
 
 N = 70
@@ -17,15 +22,40 @@ ZONES = (15, 5)
 NUM_STEPS = 4
 SEED0 = 300
 PIN = (0.5, -0.5)
+BASE_IDS = {15: "PointTSP-v0", 5: "PointTSP-v1"}
+
+# name: (envs, zones).  7 * N * Z mod 4 decides which (lead, tail) pairs K22 runs on the slots of a collection:
+#   one      3  the smallest launch, 7 floats: leads 0, 1, 2, 3 on frames 0..3, lead 3 leaves exactly one whole piece
+#   odd15    1  leads 0, 3, 2, 1 and tails 1, 2, 3, 0; N * T * Z * 7 is odd for odd T (exp.action at an odd float offset)
+#   blocks3  3  569 pieces: three workgroups, with odd leads
+#   edge257  1  past K7's 256-thread launch edge, many workgroups of K22, the compile-time Z = 15
+#   edge256  0  fully aligned control, Z = 2
+#   edge255  1  just below the launch edge
+#   z32      0  the largest zone count: the feature reaches 2^-31, int8 positions reach 31
+#   base15, base5   2  the N = 70 shapes of the older tests
+CASES = {"one": (1, 1), "odd15": (3, 5), "blocks3": (65, 5), "edge257": (257, 15), "edge256": (256, 2),
+         "edge255": (255, 5), "z32": (2, 32), "base15": (N, 15), "base5": (N, 5)}
+EDGE_CASES = ("one", "odd15", "blocks3", "edge257", "edge256", "edge255", "z32")
 
 
-def configs(Z, zones):
+def lead_tail(n, zones, t):
+    """What K22 writes around its 16-byte store grid for frame slot t of a collection on n envs: slot t starts
+    t * total floats (total = 7 * n * zones) behind a 16-byte-aligned base, so ``lead`` floats come before the first
+    aligned one and the last piece is cut to ``tail`` floats (0: the grid ends with the slot)."""
+    total = 7 * n * zones
+    lead = (-t * total) % 4
+    return lead, (total - lead) % 4
+
+
+def configs(Z, zones, num_steps=NUM_STEPS, **over):
     """(the handle's config, the config whose layouts put the robot inside zone 0)."""
-    base = {15: "PointTSP-v0", 5: "PointTSP-v1"}[zones]
-    plain = Z.config_for_id(base, num_steps=NUM_STEPS)
-    inside = Z.config_for_id(base, num_steps=NUM_STEPS, robot_locations=[PIN], zones_locations=[PIN],
-                             robot_keepout=0.0, zones_keepout=0.0)
-    return plain, inside
+    inside = dict(robot_locations=[PIN], zones_locations=[PIN], robot_keepout=0.0, zones_keepout=0.0)
+    if zones in BASE_IDS:
+        return (Z.config_for_id(BASE_IDS[zones], num_steps=num_steps, **over),
+                Z.config_for_id(BASE_IDS[zones], num_steps=num_steps, **dict(over, **inside)))
+    keepout = {"zones_keepout": 0.30} if zones == 32 else {}
+    return (Z.default_config(0, zones, num_steps=num_steps, **dict(keepout, **over)),
+            Z.default_config(0, zones, num_steps=num_steps, **dict(over, **inside)))
 
 
 def layouts(Z, zones, n=N):
@@ -42,9 +72,10 @@ def layouts(Z, zones, n=N):
     return np.array(robots), np.array(zxy), np.array(ranks, np.int32), SEED0 + np.arange(n, dtype=np.int64)
 
 
-def make_env(Z, zones, fresh=False, rows=True, n=N):
-    """A solver-ordered handle on these layouts, reset; rows: with ``order_rows()`` on."""
-    env = Z.ZoneVecEnv(configs(Z, zones)[0], n)
+def make_env(Z, zones, fresh=False, rows=True, n=N, num_steps=NUM_STEPS, **over):
+    """A solver-ordered handle on these layouts, reset; rows: with ``order_rows()`` on; over: config overrides of the
+    handle (``kernel``)."""
+    env = Z.ZoneVecEnv(configs(Z, zones, num_steps, **over)[0], n)
     env.enable_order(fresh_route_in_first_obs=fresh)
     if rows:
         env.order_rows()

@@ -75,6 +75,38 @@ def flat_check_minibatch(Z, s, sd, idx, hyper, tag, report, max_batch=384):
     return stats, s64, s32
 
 
+def decided_samples(model64, model32, exps):
+    """Which recorded samples the rule can compare gradients on: bool [N * T].
+
+    A ReLU input x is UNDECIDED when |x| in the float64 run lies within the rule's own allowance for x -- 8 times the
+    float32 run's largest deviation on that layer, or 8 ulp at the layer's scale.  There the loss is compared across a
+    jump of its gradient: float32 arithmetic in another order may open the other gate, and no tolerance on a gradient
+    tensor says anything about that (measured on the first collection of
+    test_gpu_order_rows_update.py: critic.0's unit 177 of sample 13 at
+    -3.5e-8 in float64, -7.5e-8 in torch float32; the device's gradients differed from both in exactly the tensors
+    behind that unit, by that sample's share).  Among 420 samples x 15 zones x 185 units a handful of such inputs is
+    there in every collection, so the index lists below leave the samples that hold one out -- a property of the float64
+    and float32 torch runs alone, never of the device's answer."""
+    total = exps["obs"].shape[0] * exps["obs"].shape[1]
+    pre = []
+    for model in (model64, model32):
+        seen = []
+        hooks = [m.register_forward_hook(lambda _m, inp, _out: seen.append(inp[0].detach().double().numpy()))
+                 for m in model.modules() if isinstance(m, torch.nn.ReLU)]
+        b = R.as_batch(exps, np.arange(total), next(model.parameters()).dtype)
+        with torch.no_grad():
+            model(b["obs"], b["zone_obs"])
+        for hk in hooks:
+            hk.remove()
+        pre.append(seen)
+    assert len(pre[0]) == 4                                  # zone_net_ twice, actor.enc_, critic
+    decided = np.ones(total, bool)
+    for x64, x32 in zip(*pre):
+        allowance = 8.0 * max(float(np.abs(x32 - x64).max()), 2.0 ** -24 * float(np.abs(x64).max()))
+        decided &= ~(np.abs(x64) <= allowance).reshape(total, -1).any(axis=1)
+    return decided
+
+
 # ---------------------------------------------------------------------------------------------- the Zone-goals learners
 def hier_setup(Z, cfg, h, N, seed):
     """A goal-enabled handle: fresh parameters loaded into the acting agent, one collect_hier of HIER_T frames, rows 0-7
