@@ -183,7 +183,9 @@ int take_status(zenv *h, Failures &f, unsigned long long *total, bool clear = tr
         HIP_TRY(hipMemcpy(f.slots.data(), h->ls.status->slots, listed * sizeof(int32_t), hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(f.codes.data(), h->ls.status->codes, listed * sizeof(int32_t), hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(f.seeds.data(), h->ls.status->seeds, listed * sizeof(int64_t), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemset(h->ls.status, 0, 8));      // n_failed (and its pad); n_sampled runs on
+        // n_failed (and its pad); n_sampled runs on.  The handle's stream is hipStreamNonBlocking: a null-stream memset
+        // would not be ordered before later launches on it, so the clear goes on the handle's stream itself
+        HIP_TRY(hipMemsetAsync(h->ls.status, 0, 8, h->stream));
     }
     return ZENV_OK;
 }

@@ -16,6 +16,15 @@
  * asynchronous on the handle's stream; zenv_get*(), zenv_sync() and -- unless ZENV_ROLLOUT_ASYNC is set --
  * zenv_rollout() synchronise.
  *
+ * Host buffers passed to an asynchronous call (the mask of zenv_reset, host actions of zenv_step / zenv_step_many, host
+ * indices of the *_minibatch / *_epoch calls, host marks of zenv_render): pageable memory may be reused or freed as soon
+ * as the call returns (such a call may wait for a busy stream); page-locked memory (zenv_host_alloc) is read when the
+ * stream reaches the call and must stay untouched until then (zenv_sync, or zenv_query() == 1).  Device memory, or NULL
+ * where the call takes it, keeps such a call asynchronous.  zenv_bank_update / zenv_bank_update_device copy their
+ * arguments during the call; a second refill while the first one's copy is still queued waits for it.
+ * The learners' *_get_step counts the Adam steps ENQUEUED so far; it does not wait for them.
+ * tests/stream_stall.py classifies every entry point (asynchronous / synchronises / reads host memory / host only).
+ *
  * There is no CPU fallback: every compute entry point fails with ZENV_E_HIP when no
  * gfx950 device is usable.
  */
