@@ -28,6 +28,7 @@ from ._native import (Config, ZenvError, E_ARG, E_HIP, E_STATE, E_LAYOUT, E_DONE
                       F_HPPO_LO_STATS, F_HPPO_HI_STATS, HPPO_LO, HPPO_HI, F_XYPPO_LO_STATS, F_XYPPO_HI_STATS, XYPPO_LO,
                       XYPPO_HI, F_SKPPO_LO_STATS, F_SKPPO_HI_STATS, SKPPO_LO, SKPPO_HI, F_OPPPO_LO_STATS,
                       F_OPPPO_HI_STATS, OPPPO_LO, OPPPO_HI, F_DIAYN_STATS, F_DIAYN_SAMPLES, F_ORDER_ROWS,
+                      F_A2C_STATS, A2C_PARAM, A2C_GRAD, A2C_SQUARE_AVG, A2C_STATS,
                       RenderConfig, RENDER_CURRENT, RENDER_EXPERIENCE, DEVICE_RESTARTS, SAMPLE_STATUS_CAP,
                       SAMPLE_UNFINISHED, SAMPLE_SEED_RANGE, DET_OP_LOG, DET_OP_DIV, DET_OP_SQRT)
 from .vec_env import (ZoneVecEnv, config_for_id, default_config, sample_layout, sample_layout_shared,
@@ -38,7 +39,7 @@ from .vec_env import (ZoneVecEnv, config_for_id, default_config, sample_layout, 
                       skill_num_frames, option_tensor_shapes, option_tensors_from_state_dicts,
                       check_collect_option_args, option_experience_layout, xy_tensor_shapes,
                       xy_tensors_from_state_dicts, xy_experience_layout, check_collect_xy_args,
-                      mlp_tensors_from_state_dict, ppo_state_dict_keys, ppo_batch_indexes, ppo_logs,
+                      mlp_tensors_from_state_dict, ppo_state_dict_keys, ppo_batch_indexes, ppo_logs, a2c_logs,
                       hppo_state_dict_keys, hppo_batch_indexes, xyppo_state_dict_keys, skppo_state_dict_keys,
                       opppo_state_dict_keys, diayn_state_dict_keys, diayn_kept_samples,
                       EPISODE_LOG_KEYS, episode_log_columns, episode_log_keys, synthesize_stats)

@@ -48,7 +48,7 @@ E_ARG, E_HIP, E_STATE, E_LAYOUT, E_DONE, E_RANGE = -1, -2, -3, -4, -5, -6
  F_XY_GOAL, F_XY_GOAL_MU, F_XY_GOAL_STD, F_XY_VALUE, F_XY_GOAL_AGE,
  F_HI_GOAL, F_LO_GOAL_DIST, F_XY_BOOTSTRAP_GOAL, F_PPO_STATS, F_HPPO_LO_STATS, F_HPPO_HI_STATS,
  F_XYPPO_LO_STATS, F_XYPPO_HI_STATS, F_SKPPO_LO_STATS, F_SKPPO_HI_STATS, F_OPPPO_LO_STATS,
- F_OPPPO_HI_STATS, F_DIAYN_STATS, F_DIAYN_SAMPLES, F_ORDER_ROWS) = range(86)
+ F_OPPPO_HI_STATS, F_DIAYN_STATS, F_DIAYN_SAMPLES, F_ORDER_ROWS, F_A2C_STATS) = range(87)
 (RESULT_OBS, RESULT_REWARD, RESULT_DONE, RESULT_GOAL_MET, RESULT_EXCEPTION, RESULT_ZONE_OBS) = range(6)
 N_RESULTS = 6
 
@@ -144,6 +144,17 @@ class PpoConfig(C.Structure):
     _fields_ = [("lr", C.c_double), ("adam_eps", C.c_double), ("clip_eps", C.c_double), ("entropy_coef", C.c_double),
                 ("value_loss_coef", C.c_double), ("max_grad_norm", C.c_double), ("max_batch", C.c_int32),
                 ("distributional_value", C.c_int32)]
+
+
+A2C_PARAM, A2C_GRAD, A2C_SQUARE_AVG = 0, 1, 2                 # the arenas of the zenv_a2c_* functions
+A2C_STATS = ("entropy", "value", "policy_loss", "value_loss", "grad_norm")   # ZENV_F_A2C_STATS, a2c.py:85-91's order
+
+
+class A2cConfig(C.Structure):
+    """struct zenv_a2c_config (include/zenv.h)."""
+    _fields_ = [("lr", C.c_double), ("rmsprop_alpha", C.c_double), ("rmsprop_eps", C.c_double),
+                ("entropy_coef", C.c_double), ("value_loss_coef", C.c_double), ("max_grad_norm", C.c_double),
+                ("max_batch", C.c_int32)]
 
 
 RENDER_CURRENT, RENDER_EXPERIENCE = 0, 1                      # zenv_render_config.source
@@ -382,6 +393,21 @@ _PROTOTYPES = {
     "zenv_debug_state": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# The A2C learner's entry points (zenv_a2c_*), bound with the rest in lib().  They are kept in a table of their own: the
+# stream class of every name in _PROTOTYPES is tabled in tests/stream_stall.py, theirs in tests/a2c_stream_classes.py.
+_A2C_PROTOTYPES = {
+    "zenv_a2c_check": (C.c_int, [C.POINTER(Config), C.c_void_p, C.c_void_p]),
+    "zenv_a2c_init": (C.c_int, [_H, C.c_void_p, C.c_void_p]),
+    "zenv_a2c_tensor": (C.c_int, [_H, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    "zenv_a2c_read": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p]),
+    "zenv_a2c_write": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p]),
+    "zenv_a2c_get_step": (C.c_int, [_H, C.POINTER(C.c_int64)]),
+    "zenv_a2c_set_step": (C.c_int, [_H, C.c_int64]),
+    "zenv_a2c_accumulate": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int]),
+    "zenv_a2c_apply": (C.c_int, [_H]),
+    "zenv_a2c_update": (C.c_int, [_H]),
+}
+
 _lib = None
 
 
@@ -399,7 +425,7 @@ def lib():
     if "torch" in sys.modules:
         pass
     L = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL if hasattr(C, "RTLD_GLOBAL") else 0)
-    for name, (restype, argtypes) in _PROTOTYPES.items():
+    for name, (restype, argtypes) in {**_PROTOTYPES, **_A2C_PROTOTYPES}.items():
         fn = getattr(L, name)   # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes
@@ -417,4 +443,4 @@ def check(rc):
 
 
 def exported_symbols():
-    return sorted(_PROTOTYPES)
+    return sorted({**_PROTOTYPES, **_A2C_PROTOTYPES})

@@ -19,6 +19,10 @@
 // encoder with a ReLU after combine_net.0 under an S-way cross-entropy head (PPO_HEAD_INVERSE, k_inv_loss) on the pairs
 // (observation of frame f + 1, skill of frame f) the collection kept (k_inv_count / _scan / _scatter); and the histogram
 // of the recorded picks for the learned skill prior's step (k_prior_hist).
+// And the flat actor-critic's A2C update (update_parameters, main/src/torch_ac/algos/a2c.py:21-93, recurrence 1): the
+// flat network's launches, chunk by chunk, under a loss whose means divide by the frames of the WHOLE update (k_a2c_loss),
+// the chunks' weight gradients added onto the arena in a fixed order (k_ppo_reduce<true>, k_a2c_head_bias), the
+// statistics carried as running sums (k_a2c_stats), and one clip and RMSprop step behind them (k_a2c_rmsprop).
 //
 // Every layer is a product on v_mfma_f32_32x32x2_f32, forward and backward, in one of two shapes:
 //
@@ -233,7 +237,10 @@ __global__ __launch_bounds__(448) void k_ppo_tn(const float *__restrict__ A, int
     }
 }
 
-// dst[r][dst_col0 + c] = sum over chunks of part[chunk][src_row0 + r][src_col0 + c], in chunk order, in double
+// dst[r][dst_col0 + c] = sum over chunks of part[chunk][src_row0 + r][src_col0 + c], in chunk order, in double.
+// ADD (the A2C learner's chunks after the first): the sum is added onto what dst holds -- the chain of an element runs on
+// from the chunks of the earlier launches -- and rounded once.
+template <bool ADD>
 __global__ void k_ppo_reduce(const float *__restrict__ part, int chunks, int m_rows, int ldp, int src_row0, int src_col0,
                              float *__restrict__ dst, int dst_ld, int dst_col0, int rows, int cols)
 {
@@ -243,7 +250,8 @@ __global__ void k_ppo_reduce(const float *__restrict__ part, int chunks, int m_r
     const float *p = part + (size_t)(src_row0 + r) * ldp + src_col0 + c;
     double s = 0.0;
     for (int ch = 0; ch < chunks; ++ch) s += (double)p[(size_t)ch * m_rows * ldp];
-    dst[(size_t)r * dst_ld + dst_col0 + c] = (float)s;
+    float *d = dst + (size_t)r * dst_ld + dst_col0 + c;
+    *d = ADD ? (float)((double)*d + s) : (float)s;
 }
 
 // The same sum with kPpoReduceSplit threads per element: thread (segment, element) adds the partials of its
@@ -1112,6 +1120,137 @@ __global__ void k_ppo_adam(PpoNet n, float step_size, float bc2_sqrt)
     n.exp_avg_sq[e] = v;
 }
 
+// ---- the A2C learner's statistics and step
+// The A2C loss of one sample of a chunk (main/src/torch_ac/algos/a2c.py:51-57) and its derivative with respect to the
+// head pre-activations (PRE: mu_ 0-1, std_ 2-3, critic.2 4), the head taken as k_ppo_loss takes it:
+//   loss = -mean(log_prob(a) advantage) - entropy_coef mean(entropy) + value_loss_coef mean((value - returnn)^2)
+// with log_prob(a) summed over the action's two components (as ppo.py:73-76 sums them), the entropy's mean over samples x 2,
+// no ratio, no clip, no recorded log_prob and no value clipping.  Every mean divides by `total`, the frames of the whole
+// update, not by the chunk's count: the chunk's deltas are its share of the update's.
+// Formed in double from the float32 pre-activations and rounded once, as k_skppo_lo_loss forms its loss and for its
+// reason: the gradients of actor.mu_.bias, actor.std_.bias and critic.2.bias are sums over the frames that cancel, and
+// float32 arithmetic in the head put 8.8 x 2^-24 of its scale into actor.mu_.bias' at 33 frames (DESIGN K23).  The five unrounded deltas go to DZ
+// [samples][5] for k_a2c_head_bias.
+__global__ void k_a2c_loss(PpoNet n, PpoExp x, Gather g, int bp, double inv_total)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= bp) return;
+    float ss[8] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
+    double dd[5] = { 0.0, 0.0, 0.0, 0.0, 0.0 };
+    size_t slot = 0;
+    if (sample_slot(g, b, slot)) {
+        const float *pre = n.PRE + (size_t)b * 32;
+        const PpoHyper &hy = n.hyper;
+        const double adv = (double)x.advantage[slot], ret = (double)x.returnn[slot];
+        const double half_log_2pi = 0.9189385332046727;
+        double sd[2], smu[2], ssd[2], diff[2], lp = 0.0, ent = 0.0;
+#pragma unroll
+        for (int o = 0; o < 2; ++o) {
+            smu[o] = sigmoidd((double)pre[o]);
+            ssd[o] = sigmoidd((double)pre[2 + o]);
+            const double mu = 2.0 * (smu[o] - 0.5);               // policy_network.py:46-47
+            sd[o] = ssd[o] + 1e-3;
+            diff[o] = (double)x.action[slot * 2 + o] - mu;
+            // Normal.log_prob: -(a - mu)^2 / (2 var) - log(std) - log(sqrt(2 pi))
+            lp += -(diff[o] * diff[o]) / (2.0 * (sd[o] * sd[o])) - log(sd[o]) - half_log_2pi;
+            ent += 0.5 + half_log_2pi + log(sd[o]);                // Normal.entropy
+        }
+        const double g_lp = -adv * inv_total;                     // d loss / d log_prob(a_o), the same for both o
+#pragma unroll
+        for (int o = 0; o < 2; ++o) {
+            const double var = sd[o] * sd[o];
+            const double g_mu = g_lp * (diff[o] / var);
+            const double g_sd = g_lp * ((diff[o] * diff[o]) / (var * sd[o]) - 1.0 / sd[o])
+                                - (double)hy.entropy_coef * (0.5 * inv_total) / sd[o];   // the mean is over total x 2
+            dd[o] = g_mu * 2.0 * smu[o] * (1.0 - smu[o]);
+            dd[2 + o] = g_sd * ssd[o] * (1.0 - ssd[o]);
+        }
+        const double v = (double)pre[4];
+        dd[4] = (double)hy.value_loss_coef * inv_total * (2.0 * (v - ret));
+        ss[0] = (float)ent;
+        ss[1] = pre[4];
+        ss[3] = (float)(-(lp * adv));
+        ss[4] = (float)((v - ret) * (v - ret));
+    }
+#pragma unroll
+    for (int i = 0; i < 5; ++i) n.DZ[(size_t)b * 5 + i] = dd[i];
+    float *dh = n.DH + (size_t)b * 32;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) dh[i] = i < 5 ? (float)dd[i] : 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) n.SS[(size_t)b * 8 + i] = ss[i];
+}
+
+// The gradients of actor.mu_.bias, actor.std_.bias and critic.2.bias: the chunk's sums of the unrounded deltas (DZ), in
+// double, in block_sum_256's order; the first chunk's is rounded into the arena, a later chunk's added onto what the arena
+// holds and rounded once.  Block c of 256 threads: delta c of the five.
+__global__ __launch_bounds__(256) void k_a2c_head_bias(PpoNet n, int bp, int first)
+{
+    __shared__ double sh[256];
+    const int c = blockIdx.x;
+    double s = 0.0;
+    for (int b = threadIdx.x; b < bp; b += 256) s += n.DZ[(size_t)b * 5 + c];
+    s = block_sum_256(s, sh);
+    if (threadIdx.x == 0) {
+        float *dst = c < 2 ? n.grad + n.off[PPO_MU_B] + c : c < 4 ? n.grad + n.off[PPO_STD_B] + (c - 2)
+                                                                  : n.grad + n.off[n.cr + 3];
+        *dst = first ? (float)s : (float)((double)*dst + s);
+    }
+}
+
+// sums[0 .. 4) (+)= the chunk's sums of the per-sample terms (SS columns 0, 1, 3, 4: entropy, value, policy loss, value
+// loss), in double: k_ppo_stats' sums carried from chunk to chunk instead of divided.  One block of 256 threads; the first
+// chunk overwrites.  The order within a chunk is block_sum_256's, across chunks that of the launches.
+__global__ __launch_bounds__(256) void k_a2c_stats(const float *__restrict__ SS, int count, int first, double *__restrict__ sums)
+{
+    __shared__ double sh[256];
+    for (int k = 0; k < 4; ++k) {
+        const int col = k < 2 ? k : k + 1;
+        double s = 0.0;
+        for (int b = threadIdx.x; b < count; b += 256) s += (double)SS[(size_t)b * 8 + col];
+        s = block_sum_256(s, sh);
+        if (threadIdx.x == 0) sums[k] = first ? s : sums[k] + s;
+    }
+}
+
+// stats[0 .. 4) = the means over the update's `total` frames (the entropy's over total x 2 components); stats[4], the
+// gradient norm, is k_ppo_norm's
+__global__ void k_a2c_finish(const double *__restrict__ sums, double total, float *__restrict__ stats)
+{
+    const int k = threadIdx.x;
+    if (k < 4) stats[k] = (float)(sums[k] / (k == 0 ? 2.0 * total : total));
+}
+
+// clip_grad_norm_ and torch.optim.RMSprop's single-tensor step with momentum 0, not centered, no weight decay:
+//   square_avg.mul_(alpha).addcmul_(grad, grad, value = 1 - alpha);  avg = square_avg.sqrt().add_(eps);
+//   param.addcdiv_(grad, avg, value = -lr)
+// (eps is added after the square root).  Four elements per thread and step through 16-byte loads and stores, grid-stride
+// over the arena (a multiple of 64 floats).  The padding holds zeros and stays zero: 0 / (0 + eps).  The gradient arena
+// is read only: it keeps the unclipped gradient.
+__global__ __launch_bounds__(256) void k_a2c_rmsprop(PpoNet n, float lr, float alpha, float one_minus_alpha, float eps)
+{
+    const float clip = fminf(n.hyper.max_grad_norm / (n.scalars[0] + 1e-6f), 1.0f);
+    const int64_t quads = n.arena / 4, stride = (int64_t)gridDim.x * blockDim.x;
+    float4 *param = reinterpret_cast<float4 *>(n.param), *sq = reinterpret_cast<float4 *>(n.exp_avg);
+    const float4 *grad = reinterpret_cast<const float4 *>(n.grad);
+    auto step = [&](float &p, float &v, float gr) {
+        gr *= clip;
+        v = v * alpha + (one_minus_alpha * gr) * gr;
+        const float avg = sqrtf(v) + eps;
+        p = p + ((-lr) * gr) / avg;
+    };
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += stride) {
+        float4 p = param[q], v = sq[q];
+        const float4 gr = grad[q];
+        step(p.x, v.x, gr.x);
+        step(p.y, v.y, gr.y);
+        step(p.z, v.z, gr.z);
+        step(p.w, v.w, gr.w);
+        param[q] = p;
+        sq[q] = v;
+    }
+}
+
 Gather no_gather() { return Gather{ nullptr, nullptr, nullptr, 0, 1, 1, 1, 0, nullptr, 8, 16, nullptr, 0, 0, nullptr }; }
 
 template <int MODE>
@@ -1141,7 +1280,12 @@ void reduce(const PpoNet &n, int rows_reduced, int m_tiles, int nB, int src_row0
                            rows, cols);
         return;
     }
-    hipLaunchKernelGGL(k_ppo_reduce, dim3((total + 255) / 256), dim3(256), 0, s, n.partial, chunks, m_tiles * 32,
+    if (n.accumulate) {
+        hipLaunchKernelGGL(k_ppo_reduce<true>, dim3((total + 255) / 256), dim3(256), 0, s, n.partial, chunks, m_tiles * 32,
+                           ((nB + 31) / 32) * 32, src_row0, src_col0, n.grad + n.off[tensor], dst_ld, dst_col0, rows, cols);
+        return;
+    }
+    hipLaunchKernelGGL(k_ppo_reduce<false>, dim3((total + 255) / 256), dim3(256), 0, s, n.partial, chunks, m_tiles * 32,
                        ((nB + 31) / 32) * 32, src_row0, src_col0, n.grad + n.off[tensor], dst_ld, dst_col0, rows, cols);
 }
 
@@ -1153,7 +1297,14 @@ void launch_norm(const PpoNet &n, float *stat, hipStream_t s)
 }
 
 // the two heads between the encoder's forward and backward passes: C holds the embedding going in, its delta coming out
-void gaussian_head(const PpoNet &n, const PpoExp &x, const Gather &g, int bp, float *stats, hipStream_t s)
+// the A2C learner's chunk (launch_a2c_accumulate); null for every PPO learner
+struct A2cPass {
+    int64_t total;
+    int first;
+};
+
+void gaussian_head(const PpoNet &n, const PpoExp &x, const Gather &g, int bp, float *stats, hipStream_t s,
+                   const A2cPass *a2c = nullptr)
 {
     const int h = n.h, HP = n.HP, NT = HP / 32, cr = n.cr, LDC = n.LDC;
     // the skills agent's low level: C is [emb | onehot(skill)] and actor.enc_.0.0 / critic.0 are [h][h + S]
@@ -1165,7 +1316,10 @@ void gaussian_head(const PpoNet &n, const PpoExp &x, const Gather &g, int bp, fl
     nt<NT_RELU>(I[PPO_I_WV], LDC, n.C, LDC, LDC, n.Hc, HP, bp, NT, s);                    // relu(critic.0)
     nt<NT_STORE>(I[PPO_I_HA], HP, n.Ha, HP, HP, n.PRE, 32, bp, 1, s);                     // mu_, std_
     nt<NT_ADD>(I[PPO_I_HV], HP, n.Hc, HP, HP, n.PRE, 32, bp, 1, s);                       // critic.2 / critic_mu, critic_sigma
-    if (n.loss == PPO_LOSS_JOINT_GOAL) {                      // the entropy's mean is over the rows alone
+    if (a2c) {                                                // no ratio, the means over the whole update's frames
+        hipLaunchKernelGGL(k_a2c_loss, dim3((bp + 63) / 64), dim3(64), 0, s, n, x, g, bp, 1.0 / (double)a2c->total);
+        hipLaunchKernelGGL(k_a2c_stats, dim3(1), dim3(256), 0, s, n.SS, g.count, a2c->first, n.run_sums);
+    } else if (n.loss == PPO_LOSS_JOINT_GOAL) {               // the entropy's mean is over the rows alone
         hipLaunchKernelGGL(k_xyppo_hi_loss, dim3((bp + 63) / 64), dim3(64), 0, s, n, x, g, bp);
         hipLaunchKernelGGL(k_ppo_stats, dim3(1), dim3(256), 0, s, n.SS, g.count, 1.0, stats, (float *)nullptr);
     } else {
@@ -1177,12 +1331,14 @@ void gaussian_head(const PpoNet &n, const PpoExp &x, const Gather &g, int bp, fl
     // ---- backward: every weight gradient is taken before its layer's activations are overwritten by deltas
     tn(n.DH, 32, 1, n.Ha, HP, HP, bp, n.partial, s);
     reduce(n, bp, 1, HP, 0, 0, PPO_MU_W, h, 0, NA, h, s);
-    if (!tail) reduce(n, bp, 1, HP, 0, h, PPO_MU_B, 1, 0, NA, 1, s);
+    const bool col_bias = !tail && !a2c;       // the three head biases as column h of the products (else: from DZ)
+    if (col_bias) reduce(n, bp, 1, HP, 0, h, PPO_MU_B, 1, 0, NA, 1, s);
     reduce(n, bp, 1, HP, NA, 0, PPO_STD_W, h, 0, NA, h, s);
-    if (!tail) reduce(n, bp, 1, HP, NA, h, PPO_STD_B, 1, 0, NA, 1, s);
+    if (col_bias) reduce(n, bp, 1, HP, NA, h, PPO_STD_B, 1, 0, NA, 1, s);
     tn(n.DH, 32, 1, n.Hc, HP, HP, bp, n.partial, s);
     reduce(n, bp, 1, HP, 2 * NA, 0, cr + 2, h, 0, 1, h, s);
-    if (!tail) reduce(n, bp, 1, HP, 2 * NA, h, cr + 3, 1, 0, 1, 1, s);
+    if (col_bias) reduce(n, bp, 1, HP, 2 * NA, h, cr + 3, 1, 0, 1, 1, s);
+    else if (a2c) hipLaunchKernelGGL(k_a2c_head_bias, dim3(5), dim3(256), 0, s, n, bp, a2c->first);
     else hipLaunchKernelGGL(k_skppo_head_bias, dim3(2 * NA + 1), dim3(256), 0, s, n, bp); // the three head biases
     if (n.dist) {
         reduce(n, bp, 1, HP, 5, 0, PPO_SIGMA_W, h, 0, 1, h, s);
@@ -1286,8 +1442,9 @@ void zone_head(const PpoNet &n, const PpoExp &x, const Gather &g, int rp, int bp
 
 }  // namespace
 
-hipError_t launch_ppo_minibatch(const PpoNet &n, const PpoExp &x, const int32_t *idx, int count, float *stats,
-                                hipStream_t s)
+// forward, loss and backward of one minibatch; a2c: the A2C learner's chunk, which leaves the norm to its apply
+static hipError_t minibatch(const PpoNet &n, const PpoExp &x, const int32_t *idx, int count, float *stats, hipStream_t s,
+                            const A2cPass *a2c)
 {
     const int h = n.h, HP = n.HP, KC = n.KC, NT = HP / 32, XD = n.XD, W1C = n.W1C, LDC = n.LDC;
     const int rp = (count * n.Z + 31) / 32 * 32, bp = (count + 31) / 32 * 32;
@@ -1310,7 +1467,7 @@ hipError_t launch_ppo_minibatch(const PpoNet &n, const PpoExp &x, const int32_t 
         nt<NT_STORE>(I[PPO_I_WC], KC, n.CI, KC, KC, n.C, LDC, bp, NT, s);                 // combine_net_
         if (n.head == PPO_HEAD_ZONES) zone_head(n, x, g, rp, bp, stats, s);
         else if (n.head == PPO_HEAD_SKILLS) skill_head(n, x, g, bp, stats, s);
-        else gaussian_head(n, x, g, bp, stats, s);
+        else gaussian_head(n, x, g, bp, stats, s, a2c);
     }
     // ---- the encoder's backward pass, from the embedding's delta in C
     if ((KC + 31) / 32 <= 7) {
@@ -1344,7 +1501,33 @@ hipError_t launch_ppo_minibatch(const PpoNet &n, const PpoExp &x, const int32_t 
     }
     reduce(n, rp, NT, W1C, 0, 0, PPO_ZONE_W1, n.K1, 0, h, n.K1, s);
     reduce(n, rp, NT, W1C, 0, W1C - 1, PPO_ZONE_B1, 1, 0, h, 1, s);
-    launch_norm(n, stats + 5, s);
+    if (!a2c) launch_norm(n, stats + 5, s);
+    return hipGetLastError();
+}
+
+hipError_t launch_ppo_minibatch(const PpoNet &n, const PpoExp &x, const int32_t *idx, int count, float *stats,
+                                hipStream_t s)
+{
+    return minibatch(n, x, idx, count, stats, s, nullptr);
+}
+
+hipError_t launch_a2c_accumulate(const PpoNet &net, const PpoExp &x, const int32_t *idx, int count, int64_t total,
+                                 int first, hipStream_t s)
+{
+    PpoNet n = net;
+    n.accumulate = first ? 0 : 1;
+    const A2cPass pass{ total, first };
+    return minibatch(n, x, idx, count, nullptr, s, &pass);
+}
+
+hipError_t launch_a2c_apply(const PpoNet &n, float lr, float alpha, float one_minus_alpha, float eps, int64_t total,
+                            float *stats, hipStream_t s)
+{
+    launch_norm(n, stats + 4, s);
+    hipLaunchKernelGGL(k_a2c_finish, dim3(1), dim3(64), 0, s, n.run_sums, (double)total, stats);
+    const int64_t quads = n.arena / 4;
+    const unsigned blocks = (unsigned)std::min<int64_t>((quads + 255) / 256, 1024);
+    hipLaunchKernelGGL(k_a2c_rmsprop, dim3(blocks), dim3(256), 0, s, n, lr, alpha, one_minus_alpha, eps);
     return hipGetLastError();
 }
 

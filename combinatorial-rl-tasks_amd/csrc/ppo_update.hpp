@@ -1,6 +1,7 @@
 // ppo_update.hpp -- the PPO updates on the device (ppo_update.hip): the flat actor-critic's, the Zone-goals agent's two
 // levels', the xy-goals agent's two levels', the fixed-length-skills agent's two levels' and the Options agent's two
-// levels'.  What zenv_train.cpp hands to the launches.  Internal: not installed.
+// levels'; and the flat actor-critic's A2C update (launch_a2c_*).  What zenv_train.cpp hands to the launches.  Internal:
+// not installed.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -37,6 +38,7 @@ enum {
 };
 constexpr int kPpoChunk = 256;      // rows one wave reduces into one partial of a weight gradient
 constexpr int kPpoStats = 6;        // entropy, value, value std, policy loss, value loss, gradient norm
+constexpr int kA2cStats = 5;        // the A2C learner's: entropy, value, policy loss, value loss, gradient norm
 constexpr int kPpoNormBlock = 4096; // arena elements per partial of the gradient norm
 constexpr int kPpoReduceSplit = 16; // k_ppo_reduce_split: segments of the chunk range, one thread each
 constexpr int kInvBlock = 1024;     // k_inv_count / k_inv_scatter: sample indexes per block (256 threads x 4 consecutive)
@@ -65,6 +67,8 @@ struct PpoNet {
     int cr;                  // the arena index of critic.0.weight: PPO_CRITIC_W1, or two less under PPO_HEAD_ZONES
     int split_reduce;        // the partials of a weight gradient are added by kPpoReduceSplit threads per element
                              // (k_ppo_reduce_split); 0 for the flat learner, whose sums keep their one chain and bits
+    int accumulate;          // launch_a2c_accumulate's chunks after the first: a weight gradient's partials are added onto
+                             // the gradient arena (k_ppo_reduce<true>); 0 in every other launch, which overwrites it
     int64_t off[PPO_MAX_TENSORS], count[PPO_MAX_TENSORS];   // floats, within an arena
     int64_t arena;                                          // floats of one arena (a multiple of 64)
     float *param, *grad, *exp_avg, *exp_avg_sq;
@@ -86,6 +90,8 @@ struct PpoNet {
     float *partial;          // the per-chunk partials of one weight gradient
     double *norm_partial;    // [arena / kPpoNormBlock + 1]
     float *scalars;          // [0] the gradient norm of the last launch_ppo_norm
+    double *run_sums;        // [4] the A2C learner's running sums over the chunks of an update: entropy, value, policy loss,
+                             // value loss (k_a2c_stats), finalised once by launch_a2c_apply
     int *bad_index;          // page-locked host word: a device index outside [0, N T), or a recorded goal or skill
                              // outside its range, was met (and dropped)
     PpoHyper hyper;
@@ -119,6 +125,20 @@ hipError_t launch_ppo_minibatch(const PpoNet &net, const PpoExp &exp, const int3
 // the clip and Adam step on net.grad; step_size = lr / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t), formed on the
 // host in double as torch forms them
 hipError_t launch_ppo_apply(const PpoNet &net, float step_size, float bc2_sqrt, hipStream_t stream);
+
+// ---- the flat actor-critic's A2C update (main/src/torch_ac/algos/a2c.py:21-93, recurrence 1): ONE gradient of the loss
+// averaged over `total` frames, which may be many times max_batch.  A chunk of count <= max_batch samples runs the
+// forward and backward passes of launch_ppo_minibatch under k_a2c_loss, whose means divide by `total`: the chunk's
+// gradient is its share of the whole.  first != 0 overwrites the gradient arena and the running sums of the statistics,
+// every later chunk adds onto them -- within a chunk in the partials' order, across chunks in the order of the calls.
+// net.hyper's adam_eps and clip_eps are not read.
+hipError_t launch_a2c_accumulate(const PpoNet &net, const PpoExp &exp, const int32_t *idx, int count, int64_t total,
+                                 int first, hipStream_t stream);
+// The gradient norm, clip_grad_norm_ and torch.optim.RMSprop's step (momentum 0, not centered, no weight decay) on
+// net.grad, the square average in net.exp_avg; the five statistics of the `total` frames accumulated into stats (device
+// memory).  one_minus_alpha = (float)(1.0 - alpha) as torch forms it in double.
+hipError_t launch_a2c_apply(const PpoNet &net, float lr, float alpha, float one_minus_alpha, float eps, int64_t total,
+                            float *stats, hipStream_t stream);
 
 // DIAYN's kept samples: list[0 .. *total) = the sample indexes i in [0, N (T - 1)), ascending, whose keep flag
 // mask[(i % (T - 1) + 1) N + i / (T - 1)] is not 0 (mask: [T][N]).  block_count: [blocks + 1] ints, blocks =

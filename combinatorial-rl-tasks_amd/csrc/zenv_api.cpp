@@ -263,6 +263,11 @@ FieldInfo field_info(const zenv *h, int field)
         return { ptr, bytes };
     }
     case ZENV_F_DIAYN_SAMPLES: return { h->diayn_list, h->diayn_kept > 0 ? h->diayn_kept * 4 : 0 };
+    case ZENV_F_A2C_STATS: {
+        int64_t bytes = 0;
+        void *ptr = a2c_stats(h, &bytes);
+        return { ptr, bytes };
+    }
     default: return { nullptr, 0 };
     }
 }

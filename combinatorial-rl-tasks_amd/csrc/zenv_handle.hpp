@@ -154,6 +154,8 @@ struct zenv {
     void *sk_mem = nullptr;
     // the flat actor-critic's learner (zenv_ppo_init): arenas, workspace, Adam's step count
     PpoState *ppo = nullptr;
+    // the flat actor-critic's A2C learner (zenv_a2c_init), beside the PPO one: arenas, workspace, RMSprop's step count
+    PpoState *a2c = nullptr;
     // the Zone-goals agent's two learners (zenv_hppo_init): [0] the low level, [1] the high level
     PpoState *hppo[2] = { nullptr, nullptr };
     // the xy-goals agent's two learners (zenv_xyppo_init): [0] the low level, [1] the high level
@@ -309,7 +311,7 @@ ZENV_INTERNAL int eplog_flat_reward(zenv *h, int T);
 
 // ---- zenv_train.cpp
 ZENV_INTERNAL void ppo_free(zenv *h);
-// the flat learner alone (zenv_order_rows: it is sized by the network row width)
+// the flat learners alone, PPO's and A2C's (zenv_order_rows: they are sized by the network row width)
 ZENV_INTERNAL void ppo_free_flat(zenv *h);
 // ZENV_E_ARG once an update has met (and dropped) a device-resident index out of range; mlp_range_check() asks
 ZENV_INTERNAL int ppo_index_check(zenv *h);
@@ -317,3 +319,5 @@ ZENV_INTERNAL int ppo_index_check(zenv *h);
 // ZENV_F_XYPPO_HI_STATS (4), ZENV_F_SKPPO_LO_STATS (5), ZENV_F_SKPPO_HI_STATS (6), ZENV_F_OPPPO_LO_STATS (7),
 // ZENV_F_OPPPO_HI_STATS (8), ZENV_F_DIAYN_STATS (9): the buffer and the bytes the last update call of that learner filled
 ZENV_INTERNAL void *ppo_stats(const zenv *h, int which, int64_t *bytes);
+// ZENV_F_A2C_STATS: five floats once zenv_a2c_apply / zenv_a2c_update has run
+ZENV_INTERNAL void *a2c_stats(const zenv *h, int64_t *bytes);

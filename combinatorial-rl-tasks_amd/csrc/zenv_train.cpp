@@ -3,7 +3,8 @@
 // of zenv_collect_hier, the xy-goals agent's two (zenv_xyppo_*, the same levels) on the records of zenv_collect_xy, and
 // the fixed-length-skills agent's two (zenv_skppo_*) on the records of zenv_collect_skill, and the Options agent's two
 // (zenv_opppo_*) on the records of zenv_collect_option, and DIAYN's inverse model's (zenv_diayn_*, no level) on the
-// records of zenv_collect_skill, with the kept-sample list and the learned skill prior's step beside it.
+// records of zenv_collect_skill, with the kept-sample list and the learned skill prior's step beside it; and the flat
+// actor-critic's A2C update (zenv_a2c_*) on the same buffers as zenv_ppo_*, a learner of its own beside it.
 // One PpoState each, the same code.  The kernels: ppo_update.hip.  The networks that act and collect: zenv_agents.cpp.
 #include <algorithm>
 #include <cmath>
@@ -25,6 +26,11 @@ struct PpoState {
                                     // ZENV_F_OPPPO_*_STATS
                                     // [stats_cap][6]
     int stats_cap = 0, stats_rows = 0;
+    // the A2C learner (zenv_a2c_*): square_avg lies in the exp_avg arena, the fourth arena is not used
+    double rms_alpha = 0.0, rms_eps = 0.0;
+    int64_t acc_total = 0;          // the frames the open accumulation's means divide by; 0: none since the init
+    int32_t *iota = nullptr;        // zenv_a2c_update: the indexes 0 .. iota_n on the device
+    int64_t iota_n = 0;
 };
 
 namespace {
@@ -34,6 +40,7 @@ struct NetKind {
     int XD, head, loss;
     int S = 0;                      // the fixed-length-skills and Options agents' learners: the number of skills
     int NA = 2;                     // the Gaussian head's action components: 3 for the Options agent's low level
+    int a2c = 0;                    // the flat network under the A2C learner: the head's five deltas also lie in DZ
     // XD + F + 1 <= 16 / 18 columns, rounded up to 8; the skills agent's low level: 8 + S + F + 1 <= 48 of them
     int w1c(int F) const { return S && XD > 8 ? (XD + F + 1 + 7) / 8 * 8 : XD == 8 ? 16 : 24; }
     // the skills agent's low level: actor.enc_.0.0 and critic.0 read [emb, onehot], S columns more
@@ -52,6 +59,8 @@ NetKind sk_hi(int S) { return NetKind{ 8, PPO_HEAD_SKILLS, PPO_LOSS_ACTION, S };
 NetKind op_lo(int S) { return NetKind{ 8 + S, PPO_HEAD_GAUSSIAN, PPO_LOSS_ACTION, S, 3 }; }
 // DIAYN's inverse model: the flat encoder with a ReLU on it under an S-way head, no enc_ layer and no critic
 NetKind inv_kind(int S) { return NetKind{ 8, PPO_HEAD_INVERSE, PPO_LOSS_ACTION, S }; }
+// the flat network under A2C's loss (zenv_a2c_*)
+constexpr NetKind kA2c{ 8, PPO_HEAD_GAUSSIAN, PPO_LOSS_ACTION, 0, 2, 1 };
 
 // element counts of the tensors for hidden size h and zone rows of F features: zenv_mlp_weights' member order (20; the
 // Zone-goals low level's 18 with XD = 10; the skills agent's low level's 18 with XD = 8 + S and [h, h + S] in
@@ -122,8 +131,8 @@ Layout layout_for(int h, int Z, int F, int max_batch, NetKind k)
     if (k.head == PPO_HEAD_ZONES) l.u = rp * HP, l.l = rp * 32;
     if (k.head == PPO_HEAD_SKILLS || inverse) l.l = bp * 32;       // the S logits of a sample, their deltas
     // DZ, in floats: a double per zone row (the per-zone head), or 2 NA + 1 per sample (the skills and Options agents' low
-    // level), or S per sample (the inverse model)
-    l.dz = k.tail() ? bp * 2 * (2 * k.NA + 1) : inverse ? bp * 2 * k.S : l.l / 16;
+    // level), or S per sample (the inverse model), or five per sample (the A2C learner)
+    l.dz = k.tail() ? bp * 2 * (2 * k.NA + 1) : inverse ? bp * 2 * k.S : k.a2c ? bp * 2 * 5 : l.l / 16;
     l.total = 2 * l.a1 + l.p + 2 * l.hd + l.c + l.ci + 2 * l.pre + l.ss + l.partial + l.u + 2 * l.l + l.dz;
     for (int i = 0; i < PPO_N_IMAGES; ++i) l.total += l.img[i];
     return l;
@@ -295,18 +304,23 @@ extern "C" int zenv_diayn_check(const zenv_config *cfg, const zenv_skill_inverse
 static void learner_free(PpoState *&s)
 {
     if (!s) return;
-    for (void *m : { s->arena_mem, s->ws_mem, (void *)s->idx, (void *)s->stats })
+    for (void *m : { s->arena_mem, s->ws_mem, (void *)s->idx, (void *)s->stats, (void *)s->iota })
         if (m) (void)hipFree(m);
     if (s->net.bad_index) (void)hipHostFree(s->net.bad_index);
     delete s;
     s = nullptr;
 }
 
-void ppo_free_flat(zenv *h) { learner_free(h->ppo); }
+void ppo_free_flat(zenv *h)
+{
+    learner_free(h->ppo);
+    learner_free(h->a2c);
+}
 
 void ppo_free(zenv *h)
 {
     learner_free(h->ppo);
+    learner_free(h->a2c);
     learner_free(h->hppo[0]);
     learner_free(h->hppo[1]);
     learner_free(h->xyppo[0]);
@@ -328,7 +342,7 @@ int ppo_index_check(zenv *h)
 {
     bool bad = false;
     for (PpoState *s : { h->ppo, h->hppo[0], h->hppo[1], h->xyppo[0], h->xyppo[1], h->skppo[0], h->skppo[1],
-                          h->opppo[0], h->opppo[1], h->diayn })
+                          h->opppo[0], h->opppo[1], h->diayn, h->a2c })
         if (s && s->net.bad_index && *(volatile int *)s->net.bad_index) {
             *(volatile int *)s->net.bad_index = 0;
             bad = true;
@@ -352,6 +366,13 @@ void *ppo_stats(const zenv *h, int which, int64_t *bytes)
     return s ? s->stats : nullptr;
 }
 
+void *a2c_stats(const zenv *h, int64_t *bytes)
+{
+    const PpoState *s = h->a2c;
+    *bytes = s ? (int64_t)s->stats_rows * kA2cStats * 4 : 0;
+    return s ? s->stats : nullptr;
+}
+
 // a learner of kind k in `slot` (replacing what is there) from the tensors t in arena order; checked by the caller
 static int learner_create(zenv *h, PpoState *&slot, int h_dim, const float *const *t, NetKind k, const zenv_ppo_config *pc)
 {
@@ -362,7 +383,7 @@ static int learner_create(zenv *h, PpoState *&slot, int h_dim, const float *cons
     slot = s;
     PpoNet &n = s->net;
     // the flat learner trains on the rows the flat network reads (zenv_order_rows: 7 wide on a solver-ordered handle)
-    const int F = &slot == &h->ppo ? net_row_feat(h) : h->p.F;
+    const int F = (&slot == &h->ppo || &slot == &h->a2c) ? net_row_feat(h) : h->p.F;
     const Layout l = layout_for(h_dim, h->p.Z, F, pc->max_batch, k);
     n.h = h_dim, n.HP = l.HP, n.F = F, n.Z = h->p.Z, n.K1 = k.XD + F, n.KC = l.KC;
     n.XD = k.XD, n.W1C = k.w1c(F), n.head = k.head, n.loss = k.loss, n.S = k.S, n.NA = k.NA, n.LDC = l.LDC;
@@ -410,6 +431,7 @@ static int learner_create(zenv *h, PpoState *&slot, int h_dim, const float *cons
     n.DZ = reinterpret_cast<double *>(take(l.dz));          // doubles; every piece before it is a multiple of 32 floats
     n.norm_partial = reinterpret_cast<double *>(f);      // l.total is a multiple of 8 floats: 8-byte aligned
     n.scalars = reinterpret_cast<float *>(n.norm_partial + norm_parts + 1);
+    n.run_sums = reinterpret_cast<double *>(n.scalars + 8);      // four doubles within the 256 bytes behind the partials
     HIP_TRY(hipHostMalloc((void **)&n.bad_index, sizeof(int), hipHostMallocDefault));
     *n.bad_index = 0;
     s->stats_cap = 64;
@@ -1198,4 +1220,177 @@ extern "C" int zenv_diayn_prior_write(zenv_t *h, const float *logits)
         if (!std::isfinite(logits[s])) return fail(ZENV_E_ARG, "logits[%d] is not finite", s);
     std::copy(logits, logits + h->prior.S, h->prior.logits);
     return ZENV_OK;
+}
+
+// ============================================================================ the flat actor-critic's A2C update
+// update_parameters of main/src/torch_ac/algos/a2c.py:21-93 for recurrence 1: one RMSprop step on the gradient of the
+// loss averaged over ALL frames of a collection, taken chunk by chunk through the workspace (launch_a2c_accumulate).
+namespace {
+
+// the learner's settings as the shared checks and learner_create take them; rmsprop_eps rides in adam_eps
+zenv_ppo_config a2c_as_ppo(const zenv_a2c_config *ac)
+{
+    zenv_ppo_config pc{};
+    pc.lr = ac->lr, pc.adam_eps = ac->rmsprop_eps, pc.clip_eps = 0.0, pc.entropy_coef = ac->entropy_coef;
+    pc.value_loss_coef = ac->value_loss_coef, pc.max_grad_norm = ac->max_grad_norm, pc.max_batch = ac->max_batch;
+    pc.distributional_value = 0;
+    return pc;
+}
+
+int find_a2c(zenv *h, Learner &out)
+{
+    if (!h) return fail(ZENV_E_ARG, "null handle");
+    if (!h->a2c) return fail(ZENV_E_STATE, "zenv_a2c_init first");
+    out = Learner{ h->a2c, -1, AGENT_FLAT };
+    return ZENV_OK;
+}
+
+int a2c_arena(int which)
+{
+    if (which < ZENV_A2C_PARAM || which > ZENV_A2C_SQUARE_AVG) return fail(ZENV_E_ARG, "unknown arena %d", which);
+    return ZENV_OK;
+}
+
+// one chunk behind what is enqueued; idx_dev: count indexes on the device
+int a2c_chunk(zenv *h, PpoState *s, const PpoExp &x, const int32_t *idx_dev, int count, int64_t total, int first)
+{
+    if (first) s->acc_total = total;
+    HIP_TRY(launch_a2c_accumulate(s->net, x, idx_dev, count, total, first, h->stream));
+    return ZENV_OK;
+}
+
+int a2c_step(zenv *h, PpoState *s)
+{
+    if (int rc = learner_stats_rows(h, s, 1)) return rc;
+    s->step += 1;
+    HIP_TRY(launch_a2c_apply(s->net, (float)s->lr, (float)s->rms_alpha, (float)(1.0 - s->rms_alpha), (float)s->rms_eps,
+                             std::max<int64_t>(s->acc_total, 1), s->stats, h->stream));
+    return ZENV_OK;
+}
+
+}  // namespace
+
+extern "C" int zenv_a2c_check(const zenv_config *cfg, const zenv_mlp_weights *w, const zenv_a2c_config *ac)
+{
+    if (!cfg || !w || !ac) return fail(ZENV_E_ARG, "null argument");
+    if (bad_hyper(ac->rmsprop_alpha))
+        return fail(ZENV_E_ARG, "a hyper-parameter is negative or not finite (%g)", ac->rmsprop_alpha);
+    const zenv_ppo_config pc = a2c_as_ppo(ac);
+    const float *t[PPO_MAX_TENSORS];
+    tensor_list(w, t);
+    if (int rc = learner_check(cfg, w->h_dim, t, kA2c, &pc, "")) return rc;
+    if (w->critic_sigma_w || w->critic_sigma_b)
+        return fail(ZENV_E_ARG, "critic_sigma_* given: A2CAlgo has no distributional critic");
+    return ZENV_OK;
+}
+
+extern "C" int zenv_a2c_init(zenv_t *h, const zenv_mlp_weights *w, const zenv_a2c_config *ac)
+{
+    if (!h || !w || !ac) return fail(ZENV_E_ARG, "null argument");
+    if (int rc = zenv_a2c_check(&h->cfg, w, ac)) return rc;
+    const zenv_ppo_config pc = a2c_as_ppo(ac);
+    const float *t[PPO_MAX_TENSORS];
+    tensor_list(w, t);
+    const int rc = learner_create(h, h->a2c, w->h_dim, t, kA2c, &pc);
+    if (rc) {
+        learner_free(h->a2c);           // no half-built learner
+        return rc;
+    }
+    h->a2c->rms_alpha = ac->rmsprop_alpha, h->a2c->rms_eps = ac->rmsprop_eps;
+    return ZENV_OK;
+}
+
+extern "C" int zenv_a2c_tensor(zenv_t *h, int which, int index, void **dev_ptr, int64_t *count)
+{
+    if (!h || !dev_ptr || !count) return fail(ZENV_E_ARG, "null argument");
+    Learner l;
+    if (int rc = find_a2c(h, l)) return rc;
+    if (int rc = a2c_arena(which)) return rc;
+    return learner_tensor(l, which, index, dev_ptr, count);
+}
+extern "C" int zenv_a2c_read(zenv_t *h, int which, int index, float *dst)
+{
+    if (!dst) return fail(ZENV_E_ARG, "null argument");
+    Learner l;
+    if (int rc = find_a2c(h, l)) return rc;
+    if (int rc = a2c_arena(which)) return rc;
+    return learner_copy(h, l, which, index, dst, true);
+}
+extern "C" int zenv_a2c_write(zenv_t *h, int which, int index, const float *src)
+{
+    if (!src) return fail(ZENV_E_ARG, "null argument");
+    Learner l;
+    if (int rc = find_a2c(h, l)) return rc;
+    if (int rc = a2c_arena(which)) return rc;
+    return learner_copy(h, l, which, index, const_cast<float *>(src), false);
+}
+extern "C" int zenv_a2c_get_step(zenv_t *h, int64_t *step)
+{
+    if (!h || !step) return fail(ZENV_E_ARG, "null argument");
+    Learner l;
+    if (int rc = find_a2c(h, l)) return rc;
+    *step = l.s->step;
+    return ZENV_OK;
+}
+extern "C" int zenv_a2c_set_step(zenv_t *h, int64_t step)
+{
+    Learner l;
+    if (int rc = find_a2c(h, l)) return rc;
+    return learner_set_step(l, step);
+}
+
+extern "C" int zenv_a2c_accumulate(zenv_t *h, const int32_t *idx, int count, int idx_on_device, int64_t total, int first)
+{
+    if (!h || !idx) return fail(ZENV_E_ARG, "null argument");
+    Learner l;
+    if (int rc = find_a2c(h, l)) return rc;
+    PpoState *s = l.s;
+    if (count < 1 || count > s->net.max_batch)
+        return fail(ZENV_E_ARG, "count %d outside [1, max_batch = %d]", count, s->net.max_batch);
+    if (total < count) return fail(ZENV_E_ARG, "total %lld is less than the chunk's count %d", (long long)total, count);
+    if (!first && s->acc_total == 0)
+        return fail(ZENV_E_STATE, "no accumulation is open: the update's first chunk takes first != 0");
+    if (!first && total != s->acc_total)
+        return fail(ZENV_E_ARG, "total %lld differs from the first chunk's %lld", (long long)total, (long long)s->acc_total);
+    PpoExp x{};
+    int64_t samples = 0;
+    if (int rc = learner_exp(h, l, x, samples)) return rc;
+    const int32_t *idx_dev = nullptr;
+    if (int rc = learner_indices(h, s, idx, count, idx_on_device, samples, &idx_dev)) return rc;
+    return a2c_chunk(h, s, x, idx_dev, count, total, first ? 1 : 0);
+}
+
+extern "C" int zenv_a2c_apply(zenv_t *h)
+{
+    Learner l;
+    if (int rc = find_a2c(h, l)) return rc;
+    if (int rc = use_device(h)) return rc;
+    return a2c_step(h, l.s);
+}
+
+extern "C" int zenv_a2c_update(zenv_t *h)
+{
+    Learner l;
+    if (int rc = find_a2c(h, l)) return rc;
+    PpoState *s = l.s;
+    PpoExp x{};
+    int64_t samples = 0;
+    if (int rc = learner_exp(h, l, x, samples)) return rc;
+    if (int rc = use_device(h)) return rc;
+    if (s->iota_n < samples) {          // once per size: the index order 0 .. N T - 1 (a2c.py:_get_starting_indexes)
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        if (s->iota) HIP_TRY(hipFree(s->iota));
+        s->iota = nullptr, s->iota_n = 0;
+        std::vector<int32_t> host((size_t)samples);
+        for (int64_t i = 0; i < samples; ++i) host[(size_t)i] = (int32_t)i;
+        HIP_TRY(hipMalloc((void **)&s->iota, (size_t)samples * sizeof(int32_t)));
+        HIP_TRY(hipMemcpy(s->iota, host.data(), (size_t)samples * sizeof(int32_t), hipMemcpyHostToDevice));
+        s->iota_n = samples;
+    }
+    const int64_t B = s->net.max_batch;
+    for (int64_t lo = 0; lo < samples; lo += B) {
+        const int count = (int)std::min<int64_t>(B, samples - lo);
+        if (int rc = a2c_chunk(h, s, x, s->iota + lo, count, samples, lo == 0)) return rc;
+    }
+    return a2c_step(h, s);
 }

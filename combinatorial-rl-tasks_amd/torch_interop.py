@@ -232,6 +232,69 @@ class TorchZoneEnv:
     def ppo_update(self, epochs, batch_size, rng):
         return self.env.ppo_update(epochs, batch_size, rng)
 
+    # ------------------------------------------------------------------ the flat actor-critic's A2C update
+
+    def a2c_init(self, state_dict, **hyper):
+        """``ZoneVecEnv.a2c_init`` with the three arenas -- parameters, gradients, square_avg -- as flat float32 CUDA
+        tensors ALIASING device memory in ``self.a2c_arenas`` (padding between the tensors included; valid until the
+        next a2c_init or ``env.close()``)."""
+        self.env.a2c_init(state_dict, **hyper)
+        with self._torch.cuda.device(self.device):
+            self.a2c_arenas = {}
+            for name, which in (("param", nat.A2C_PARAM), ("grad", nat.A2C_GRAD), ("square_avg", nat.A2C_SQUARE_AVG)):
+                ptr, count = self.env.a2c_tensor_ptr(which, -1)
+                self.a2c_arenas[name] = self._alias_ptr(ptr, (count,))
+
+    def a2c_views(self, which=nat.A2C_PARAM):
+        """zenv_mlp_weights name -> CUDA tensor ALIASING that tensor of an arena, in its state_dict shape."""
+        from .vec_env import mlp_tensor_shapes
+        shapes = mlp_tensor_shapes(self.env._a2c_h, self.env.net_zone_feat)
+        with self._torch.cuda.device(self.device):
+            return {name: self._alias_ptr(self.env.a2c_tensor_ptr(which, i)[0], shapes[name])
+                    for i, name in enumerate(self.env._a2c_keys)}
+
+    def a2c_state_dict(self):
+        """The learner's parameters under ACModel's state_dict names, as CUDA tensors ALIASING the parameter arena."""
+        views = self.a2c_views()
+        return {key: views[name] for name, key in self.env._a2c_keys.items()}
+
+    def a2c_load_state_dict(self, state_dict):
+        """Overwrite the learner's parameters from an ACModel state_dict (tensors on any device), on the stream."""
+        for key, dst in self.a2c_state_dict().items():
+            dst.copy_(state_dict[key])
+
+    def a2c_optimizer_state(self):
+        """RMSprop's state in the shape of ``torch.optim.RMSprop.state_dict()``: copies, parameter i the i-th of
+        ``ACModel.parameters()``."""
+        torch = self._torch
+        out = self.env.a2c_optimizer_state()
+        out["state"] = {i: {"step": torch.tensor(s["step"]), "square_avg": torch.from_numpy(s["square_avg"]).to(self.device)}
+                        for i, s in out["state"].items()}
+        return out
+
+    def a2c_load_optimizer_state(self, state):
+        self.env.a2c_load_optimizer_state(state)
+
+    def a2c_accumulate(self, idx, total, first):
+        """``ZoneVecEnv.a2c_accumulate``; idx may be an int32 CUDA tensor (never copied, checked on the device)."""
+        ptr, count = self._ppo_index_arg(idx)
+        self.env.a2c_accumulate(ptr, total, first, count=count)
+
+    def a2c_apply(self):
+        self.env.a2c_apply()
+
+    def a2c_stats(self):
+        """float32 CUDA tensor [1, 5] ALIASING the statistics of the last a2c_apply / a2c_update (not synchronised)."""
+        rows = self.env.field_bytes(nat.F_A2C_STATS) // 20
+        with self._torch.cuda.device(self.device):
+            return self._alias(nat.F_A2C_STATS, (rows, 5), np.float32)
+
+    def a2c_publish(self, precision="auto"):
+        self.env.a2c_publish(precision=precision)
+
+    def a2c_update(self):
+        return self.env.a2c_update()
+
     # ------------------------------------------------------------------ the Zone-goals agent's two PPO updates
     def hppo_init(self, hi_state_dict, lo_state_dict, lo=None, hi=None):
         """``ZoneVecEnv.hppo_init`` with each level's four arenas as flat float32 CUDA tensors ALIASING device memory in

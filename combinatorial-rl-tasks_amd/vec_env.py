@@ -52,6 +52,7 @@ _FIELD_DTYPES = {
     nat.F_SKPPO_LO_STATS: np.float32, nat.F_SKPPO_HI_STATS: np.float32,
     nat.F_OPPPO_LO_STATS: np.float32, nat.F_OPPPO_HI_STATS: np.float32,
     nat.F_DIAYN_STATS: np.float32, nat.F_DIAYN_SAMPLES: np.int32, nat.F_ORDER_ROWS: np.float32,
+    nat.F_A2C_STATS: np.float32,
 }
 
 
@@ -63,15 +64,19 @@ def _as_host_f32(v):
 class _Learner:
     """One device learner behind the ppo_* (level None: zenv_ppo_*), hppo_* (zenv_hppo_* with a level), xyppo_*
     (prefix "zenv_xyppo_"), skppo_* (prefix "zenv_skppo_") or opppo_* (prefix "zenv_opppo_") methods: the arenas' tensors under their names, Adam's
-    state, the update calls and the statistics."""
+    state, the update calls and the statistics.  The a2c_* methods' learner (prefix "zenv_a2c_", level None) is one too:
+    RMSprop's state where the others have Adam's, ``accumulate`` / ``update`` where they have ``minibatch`` / ``epoch``,
+    one row of five statistics (stats_cols)."""
 
-    def __init__(self, handle, level, keys, shapes, lr, adam_eps, stats_field, prefix="zenv_hppo_"):
+    def __init__(self, handle, level, keys, shapes, lr, adam_eps, stats_field, prefix="zenv_hppo_", stats_cols=6,
+                 rmsprop_alpha=None):
         self._h, self.level, self.keys, self.shapes = handle, level, keys, shapes
         self.lr, self.adam_eps, self.stats_field, self.prefix = lr, adam_eps, stats_field, prefix
+        self.stats_cols, self.rmsprop_alpha = stats_cols, rmsprop_alpha
 
     def _call(self, name, *args):
         if self.level is None:          # the learners without a level: the flat one's and DIAYN's inverse model's
-            prefix = self.prefix if self.prefix == "zenv_diayn_" else "zenv_ppo_"
+            prefix = self.prefix if self.prefix in ("zenv_diayn_", "zenv_a2c_") else "zenv_ppo_"
             check(getattr(lib(), prefix + name)(self._h, *args))
         else:
             check(getattr(lib(), self.prefix + name)(self._h, int(self.level), *args))
@@ -130,6 +135,30 @@ class _Learner:
                          nat.PPO_EXP_AVG_SQ)
         self.set_step(int(float(st[0]["step"])) if st else 0)
 
+    def rmsprop_state(self):
+        """``torch.optim.RMSprop.state_dict()``'s shape (momentum 0, not centered): ``step`` and ``square_avg``."""
+        v = self.tensors(nat.A2C_SQUARE_AVG)
+        step = self.get_step()
+        state = {i: {"step": float(step), "square_avg": v[name]} for i, name in enumerate(self.keys)} if step else {}
+        group = {"lr": self.lr, "momentum": 0, "alpha": self.rmsprop_alpha, "eps": self.adam_eps, "centered": False,
+                 "weight_decay": 0, "params": list(range(len(self.keys)))}
+        return {"state": state, "param_groups": [group]}
+
+    def load_rmsprop_state(self, state):
+        names = list(self.keys)
+        st = state["state"]
+        zeros = {n: np.zeros(self.shapes[n], np.float32) for n in names}
+        self.set_tensors({n: _as_host_f32(st[i]["square_avg"]) for i, n in enumerate(names)} if st else zeros,
+                         nat.A2C_SQUARE_AVG)
+        self.set_step(int(float(st[0]["step"])) if st else 0)
+
+    def accumulate(self, idx, total, first, count=None):
+        ptr, n, dev, keep = self._indices(idx, count)
+        self._call("accumulate", C.c_void_p(ptr), n, dev, int(total), int(bool(first)))
+
+    def update(self):
+        self._call("update")
+
     def get_step(self):
         n = C.c_int64()
         self._call("get_step", C.byref(n))
@@ -158,8 +187,9 @@ class _Learner:
         self._call("epoch", C.c_void_p(ptr), n, int(batch_size), dev)
 
     def stats(self):
-        rows = lib().zenv_field_bytes(self._h, self.stats_field) // 24
-        out = np.empty((rows, 6), np.float32)
+        cols = self.stats_cols
+        rows = lib().zenv_field_bytes(self._h, self.stats_field) // (4 * cols)
+        out = np.empty((rows, cols), np.float32)
         if rows:
             check(lib().zenv_get(self._h, self.stats_field, out.ctypes.data, 0))
         return out
@@ -169,6 +199,12 @@ def ppo_logs(stats, distributional):
     """The logs dict of update_parameters (ppo.py:137-153) from the [minibatches, 6] statistics of an epoch."""
     mean = np.asarray(stats, np.float64).mean(axis=0)
     return {name: float(mean[i]) for i, name in enumerate(nat.PPO_STATS) if distributional or name != "value_std"}
+
+
+def a2c_logs(stats):
+    """The logs dict of A2CAlgo.update_parameters (a2c.py:85-91) from the [1, 5] statistics of an update."""
+    row = np.asarray(stats, np.float64).reshape(-1, len(nat.A2C_STATS))[0]
+    return {name: float(row[i]) for i, name in enumerate(nat.A2C_STATS)}
 
 
 def config_for_id(env_id, **overrides):
@@ -1190,6 +1226,98 @@ class ZoneVecEnv:
             self.ppo_batch_num += 1
             self.ppo_epoch(order, batch_size)
         return ppo_logs(self.ppo_stats(), "critic_sigma_w" in self._ppo_keys)
+
+    # ------------------------------------------------------------------ the flat actor-critic's A2C update
+    def a2c_init(self, state_dict_or_tensors, lr=0.01, rmsprop_alpha=0.99, rmsprop_eps=1e-8, entropy_coef=0.01,
+                 value_loss_coef=0.5, max_grad_norm=0.5, max_batch=256):
+        """The learner of A2CAlgo.update_parameters (torch_ac/algos/a2c.py:21-93, recurrence 1) on the device, beside
+        the ``ppo_*`` one: float32 master parameters from an ACModel state_dict (or the named tensors of
+        ``mlp_tensors_from_state_dict``), their gradients and RMSprop's square_avg.  The defaults are A2CAlgo's
+        (a2c.py:10-12).  max_batch is the chunk an update walks the collection in: it sizes the activation
+        workspace, not the batch the loss is averaged over, which is always all N x T frames.  The plain critic only."""
+        d = state_dict_or_tensors
+        tensors = dict(d) if "zone_w1" in d else mlp_tensors_from_state_dict(d)
+        h = int(np.asarray(tensors["zone_b1"]).shape[0])
+        w = nat.MlpWeights(h_dim=h, precision=nat.MLP_F32)
+        names = [n for n in nat.MLP_TENSORS + nat.MLP_CRITIC_TENSORS + nat.MLP_SIGMA_TENSORS if n in tensors]
+        keep = self._load_weights(w, names, tensors, mlp_tensor_shapes(h, self.net_zone_feat))   # alive across the call
+        ac = nat.A2cConfig(lr=lr, rmsprop_alpha=rmsprop_alpha, rmsprop_eps=rmsprop_eps, entropy_coef=entropy_coef,
+                           value_loss_coef=value_loss_coef, max_grad_norm=max_grad_norm, max_batch=int(max_batch))
+        check(lib().zenv_a2c_init(self._h, C.byref(w), C.byref(ac)))
+        del keep
+        self._a2c_h = h
+        self._a2c_keys = ppo_state_dict_keys(False)
+        self._learners[("a2c", None)] = _Learner(self._h, None, self._a2c_keys, mlp_tensor_shapes(h, self.net_zone_feat),
+                                                 lr, rmsprop_eps, nat.F_A2C_STATS, "zenv_a2c_", len(nat.A2C_STATS),
+                                                 rmsprop_alpha)
+
+    @property
+    def _a2c(self):
+        found = self._learners.get(("a2c", None))
+        return found or _Learner(self._h, None, {}, {}, 0.0, 0.0, nat.F_A2C_STATS, "zenv_a2c_", len(nat.A2C_STATS))
+
+    def a2c_tensor_ptr(self, which, index):
+        """(device pointer, element count) of tensor `index` (arena order; -1: the whole arena) of arena `which`
+        (``_native.A2C_PARAM`` / ``A2C_GRAD`` / ``A2C_SQUARE_AVG``)."""
+        return self._a2c.tensor_ptr(which, index)
+
+    def a2c_tensors(self, which=nat.A2C_PARAM):
+        """Every tensor of an arena as a new host array, under its zenv_mlp_weights name."""
+        return self._a2c.tensors(which)
+
+    def a2c_set_tensors(self, tensors, which=nat.A2C_PARAM):
+        """Overwrite the tensors of an arena that `tensors` names (zenv_mlp_weights names)."""
+        self._a2c.set_tensors(tensors, which)
+
+    def a2c_state_dict(self):
+        """The learner's parameters under the reference ACModel's state_dict names (host float32 copies)."""
+        return self._a2c.state_dict()
+
+    def a2c_load_state_dict(self, state_dict):
+        """Overwrite the learner's parameters from an ACModel state_dict (every key must be there)."""
+        self._a2c.load_state_dict(state_dict)
+
+    def a2c_optimizer_state(self):
+        """RMSprop's state in the shape of ``torch.optim.RMSprop.state_dict()`` (``step``, ``square_avg``), host arrays:
+        parameter i is the i-th of ``ACModel.parameters()``."""
+        return self._a2c.rmsprop_state()
+
+    def a2c_load_optimizer_state(self, state):
+        """Restore square_avg and the step count from ``a2c_optimizer_state`` / ``torch.optim.RMSprop.state_dict()``:
+        the ``optimizer_state`` of an A2C run's status.pt resumes here."""
+        self._a2c.load_rmsprop_state(state)
+
+    def a2c_get_step(self):
+        return self._a2c.get_step()
+
+    def a2c_set_step(self, step):
+        self._a2c.set_step(step)
+
+    def a2c_accumulate(self, idx, total, first, count=None):
+        """One chunk of an update over `total` frames: forward, loss and backward on the samples idx (host int32 array,
+        or a device address with count; at most max_batch of them).  first: the chunk opens the update and overwrites
+        the gradient arena, else it adds onto it.  Every mean divides by `total`.  Asynchronous."""
+        self._a2c.accumulate(idx, total, first, count)
+
+    def a2c_apply(self):
+        """The gradient norm, clip_grad_norm_ and one RMSprop step on whatever the gradient arena holds; the five
+        statistics of the accumulated frames go to ``a2c_stats()``."""
+        self._a2c.apply()
+
+    def a2c_stats(self):
+        """float32 [1, 5] of the last a2c_apply / a2c_update ([0, 5] before the first): ``_native.A2C_STATS`` names the
+        columns.  Waits for the device."""
+        return self._a2c.stats()
+
+    def a2c_publish(self, precision="auto"):
+        """Hand the learner's parameters to the acting network (``load_mlp``), so the next collect acts with them."""
+        self.load_mlp(self.a2c_tensors(), precision=precision)
+
+    def a2c_update(self):
+        """A2CAlgo.update_parameters on the experience of the last collect: all N x T frames in index order, in
+        chunks of max_batch, one clip and RMSprop step.  Returns the reference's logs (a2c.py:85-91)."""
+        self._a2c.update()
+        return a2c_logs(self.a2c_stats())
 
     # ------------------------------------------------------------------ the Zone-goals agent's two PPO updates
     # the example's hyper-parameters (examples/zone_goals_ppo_torch.py; the reference takes the norm and does not clip)

@@ -13,6 +13,11 @@ into either.
 ``ppo_update`` / ``ppo_publish``: float32 forward, loss, backward, clip and Adam on the handle's experience buffers);
 the torch module then only provides the initial parameters and receives the trained ones at the end.
 
+``--algo a2c`` trains with the reference's other learner, ``torch_ac.A2CAlgo`` (torch_ac/algos/a2c.py, recurrence 1): ONE
+RMSprop step per collection on the loss averaged over all procs x frames-per-proc frames, its gradient accumulated over
+chunks of ``--batch-size`` frames (``--epochs`` is not used).  The torch path is ``a2c_update`` below; with
+``--device-update`` it is ``a2c_init`` / ``a2c_update`` / ``a2c_publish``.
+
 ``--env PointTSP-v2`` trains the results table's "Solver" agent (main/envs/TSP_order_env.py): the handle is
 solver-ordered with ``order_rows()`` on, so the network reads the (Z, 7) rows and the collection records the shaped
 reward; ``--fresh-layouts`` then has the device solve the routes of the maps it samples (``order_routes_device``).
@@ -100,9 +105,37 @@ def ppo_update(model, opt, exps, epochs, batch_size, clip_eps, entropy_coef, val
     return {k: float(v.detach()) for k, v in stats.items()}
 
 
+def a2c_update(model, opt, exps, chunk, entropy_coef, value_loss_coef, max_grad_norm):
+    """A2CAlgo.update_parameters() for recurrence 1: one step on the loss averaged over ALL frames, in index order.  The
+    activations of procs x frames-per-proc frames do not fit at once, so each chunk's share of the loss is
+    back-propagated in turn and autograd adds the gradients up; log_prob is summed over the action's two components as
+    the PPO update sums it."""
+    flat = {k: v.reshape((-1,) + tuple(v.shape[2:])) for k, v in exps.items()}
+    total = flat["obs"].shape[0]
+    sums = torch.zeros(4, device=flat["obs"].device, dtype=torch.float64)
+    opt.zero_grad(set_to_none=True)
+    for lo in range(0, total, chunk):
+        sl = slice(lo, lo + chunk)
+        dist, value = model(flat["obs"][sl], flat["zone_obs"][sl])
+        policy = -(dist.log_prob(flat["action"][sl]).sum(dim=1) * flat["advantage"][sl]).sum()
+        value_sq = (value - flat["returnn"][sl]).pow(2).sum()
+        entropy = dist.entropy().sum() / 2.0
+        ((policy - entropy_coef * entropy + value_loss_coef * value_sq) / total).backward()
+        sums += torch.stack([entropy, value.sum(), policy, value_sq]).detach().double()
+    grad_norm = nn.utils.clip_grad_norm_(model.parameters(), max_grad_norm)
+    opt.step()
+    entropy, value, policy, value_sq = (float(v) / total for v in sums)
+    return {"entropy": entropy, "value": value, "policy_loss": policy, "value_loss": value_sq,
+            "grad_norm": float(grad_norm)}
+
+
 def train(env_id="PointTSP-v0", procs=4096, frames_per_proc=64, updates=10, epochs=4, batch_size=16384, lr=3e-4,
           discount=0.99, gae_lambda=0.95, clip_eps=0.2, entropy_coef=0.003, value_loss_coef=0.5, max_grad_norm=0.5,
-          hidden=185, seed=1, log=print, device_update=False, fresh_layouts=False, device_deadlines=False):
+          hidden=185, seed=1, log=print, device_update=False, fresh_layouts=False, device_deadlines=False, algo="ppo",
+          rmsprop_alpha=0.99):
+    if algo not in ("ppo", "a2c"):
+        raise ValueError("--algo is ppo or a2c")
+    a2c = algo == "a2c"
     torch.manual_seed(seed)
     dev = torch.device("cuda", 0)
     base_id = order_base_id(env_id)         # a TSPOrderEnv id (PointTSP-v2): its task env, solver-ordered
@@ -133,10 +166,17 @@ def train(env_id="PointTSP-v0", procs=4096, frames_per_proc=64, updates=10, epoc
     if fresh_layouts:
         env.ring_refill()                       # the reset took episode 0 of every ring: a map like any other
     model = ActorCritic(env.net_zone_feat, hidden).to(dev)
-    opt = torch.optim.Adam(model.parameters(), lr, eps=1e-8)
+    if a2c:                                 # a2c.py:18
+        opt = torch.optim.RMSprop(model.parameters(), lr, alpha=rmsprop_alpha, eps=1e-8)
+    else:
+        opt = torch.optim.Adam(model.parameters(), lr, eps=1e-8)
     gen = torch.Generator(device=dev).manual_seed(seed)
     history = []
-    if device_update:
+    if device_update and a2c:
+        tenv.a2c_init(model.state_dict(), lr=lr, rmsprop_alpha=rmsprop_alpha, rmsprop_eps=1e-8, entropy_coef=entropy_coef,
+                      value_loss_coef=value_loss_coef, max_grad_norm=max_grad_norm, max_batch=batch_size)
+        tenv.a2c_publish()
+    elif device_update:
         import numpy as np
         rng = np.random.default_rng(seed)
         tenv.ppo_init(model.state_dict(), lr=lr, adam_eps=1e-8, clip_eps=clip_eps, entropy_coef=entropy_coef,
@@ -151,23 +191,28 @@ def train(env_id="PointTSP-v0", procs=4096, frames_per_proc=64, updates=10, epoc
             env.ring_refill()                   # stream-ordered: behind the collection, before the next one
         torch.cuda.synchronize()
         t1 = time.perf_counter()
-        if device_update:
+        if device_update and a2c:
+            st = tenv.a2c_update()
+            tenv.a2c_publish()
+        elif device_update:
             st = tenv.ppo_update(epochs, batch_size, rng)
             tenv.ppo_publish()
+        elif a2c:
+            st = a2c_update(model, opt, exps, batch_size, entropy_coef, value_loss_coef, max_grad_norm)
         else:
             st = ppo_update(model, opt, exps, epochs, batch_size, clip_eps, entropy_coef, value_loss_coef, max_grad_norm, gen)
         torch.cuda.synchronize()
         t2 = time.perf_counter()
         frames = procs * frames_per_proc
         st.update(update=u, frames=frames * (u + 1), reward_per_frame=float(exps["reward"].mean()),
-                  collect_fps=frames / (t1 - t0), update_fps=frames * epochs / (t2 - t1))
+                  collect_fps=frames / (t1 - t0), update_fps=frames * (1 if a2c else epochs) / (t2 - t1))
         # logs of collect_experiences (base.py:233-247), synthesized as train_ppo.py:175-177 does
         num_frames = tenv.episode_logs()["num_frames"]
         st.update(episode_log_history(tenv.episode_log_stats(), num_frames))
         history.append(st)
         log({k: (round(v, 4) if isinstance(v, float) else v) for k, v in st.items()})
     if device_update:
-        model.load_state_dict(tenv.ppo_state_dict())
+        model.load_state_dict(tenv.a2c_state_dict() if a2c else tenv.ppo_state_dict())
     env.close()
     return model, history
 
@@ -180,7 +225,9 @@ if __name__ == "__main__":
     ap.add_argument("--updates", type=int, default=10)
     ap.add_argument("--epochs", type=int, default=4)
     ap.add_argument("--batch-size", type=int, default=16384)
-    ap.add_argument("--lr", type=float, default=3e-4)
+    ap.add_argument("--algo", default="ppo", choices=["ppo", "a2c"], help="the learner: PPOAlgo or A2CAlgo")
+    ap.add_argument("--lr", type=float, default=None, help="default: 3e-4 for ppo, 0.01 for a2c (the reference's)")
+    ap.add_argument("--optim-alpha", type=float, default=0.99, help="a2c: RMSprop's alpha")
     ap.add_argument("--hidden-size", type=int, default=185)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--device-update", action="store_true", help="run the update in the library's HIP kernels")
@@ -191,5 +238,7 @@ if __name__ == "__main__":
                     help="with --fresh-layouts on a TimedTSP env id (PointTTSP-v0, -v1): draw the deadlines on the device "
                          "as well, through the shared deterministic log")
     a = ap.parse_args()
-    train(a.env, a.procs, a.frames_per_proc, a.updates, a.epochs, a.batch_size, a.lr, hidden=a.hidden_size, seed=a.seed,
-          device_update=a.device_update, fresh_layouts=a.fresh_layouts, device_deadlines=a.device_deadlines)
+    lr = a.lr if a.lr is not None else (0.01 if a.algo == "a2c" else 3e-4)
+    train(a.env, a.procs, a.frames_per_proc, a.updates, a.epochs, a.batch_size, lr, hidden=a.hidden_size, seed=a.seed,
+          device_update=a.device_update, fresh_layouts=a.fresh_layouts, device_deadlines=a.device_deadlines, algo=a.algo,
+          rmsprop_alpha=a.optim_alpha)

@@ -217,7 +217,13 @@ enum {
     ZENV_F_ORDER_ROWS = 85,         /* float32 [N,Z,7]  TSPOrderEnv's observation rows (TSP_order_env.py:37-47): row z =
                                      * [ZENV_F_ZONE_OBS row z (6), ZENV_F_ORDER_VAL z], the exact bits of both as they stand
                                      * when the field is asked for */
-    ZENV_F_COUNT = 86
+    /* the flat actor-critic's A2C learner (zenv_a2c_init): the statistics of the last zenv_a2c_apply / zenv_a2c_update;
+     * 0 bytes before the first.  Before this field,
+     * ZENV_F_COUNT = 86
+     */
+    ZENV_F_A2C_STATS = 86,          /* float32 [5] the reference's log order: entropy, value, policy_loss, value_loss,
+                                     * grad_norm (a2c.py:85-91), over all the frames accumulated */
+    ZENV_F_COUNT = 87
 };
 
 /* scripted on-device action sources (the build's own; used by bench/tests) */
@@ -1123,6 +1129,52 @@ int zenv_ppo_apply(zenv_t *h);
 /* The minibatches order[k B : (k + 1) B], B = batch_size, in sequence, the last one short: each forward, backward,
  * clip and Adam, with no host synchronisation; minibatch k's statistics in row k of ZENV_F_PPO_STATS. */
 int zenv_ppo_epoch(zenv_t *h, const int32_t *order, int total, int batch_size, int on_device);
+
+/* ---- the flat actor-critic's A2C update on the device: update_parameters, main/src/torch_ac/algos/a2c.py:21-93 ----
+ * A2CAlgo for recurrence 1 on the network and the ZENV_F_EXP_* buffers of zenv_ppo_*, a learner of its own that a handle
+ * may hold beside the PPO one: float32 master parameters, their gradients and RMSprop's square_avg.  A2C takes ONE step
+ * on the loss averaged over all N T frames of a collection,
+ *   loss = -mean(log_prob(a) advantage) - entropy_coef mean(entropy) + value_loss_coef mean((value - returnn)^2),
+ * log_prob(a) summed over the action's two components (as ppo.py:73-76 sums them; a2c.py:53 as written multiplies
+ * [B, 2] by [B] and raises for the two-component policy), the entropy's mean over frames x 2, no ratio, no clip.  N T is
+ * usually far beyond an activation workspace, so the gradient is accumulated over chunks of at most max_batch frames:
+ * every chunk's means divide by the update's total, chunk 0 overwrites the gradient arena and every later chunk adds
+ * onto it, within a chunk in the fixed order of the PPO learner's partial sums and across chunks in the order of the
+ * calls.  The statistics accumulate the same way and are finalised by the step.  The same calls from the same state
+ * give the same bits. */
+typedef struct zenv_a2c_config {
+    double lr, rmsprop_alpha, rmsprop_eps;      /* torch.optim.RMSprop(lr, alpha, eps), momentum 0, not centered */
+    double entropy_coef, value_loss_coef, max_grad_norm;
+    int32_t max_batch;                          /* chunk size: sizes the activation workspace */
+} zenv_a2c_config;
+enum { ZENV_A2C_PARAM = 0, ZENV_A2C_GRAD = 1, ZENV_A2C_SQUARE_AVG = 2 };
+/* zenv_ppo_check's rules on the host alone: ZENV_E_ARG for h_dim outside 1 .. 191, a null actor tensor, a missing critic,
+ * a negative or non-finite hyper-parameter, max_batch < 1, a workspace of 2^31 floats or more -- and for critic_sigma_*
+ * tensors: A2CAlgo has no distributional branch. */
+int zenv_a2c_check(const zenv_config *cfg, const zenv_mlp_weights *init, const zenv_a2c_config *ac);
+/* Three arenas in zenv_ppo_init's layout (18 tensors, zenv_mlp_weights' member order, 256-byte boundaries, zeros
+ * between): parameters, gradients, square_avg; the step count starts at 0.  On a handle with zenv_order_rows on the
+ * learner trains on the (Z, 7) rows.  A second call replaces the learner; zenv_ppo_* is not touched. */
+int zenv_a2c_init(zenv_t *h, const zenv_mlp_weights *init, const zenv_a2c_config *ac);
+/* as zenv_ppo_tensor / _read / _write / _get_step / _set_step, `which` one of ZENV_A2C_* */
+int zenv_a2c_tensor(zenv_t *h, int which, int index, void **dev_ptr, int64_t *count);
+int zenv_a2c_read(zenv_t *h, int which, int index, float *dst);
+int zenv_a2c_write(zenv_t *h, int which, int index, const float *src);
+int zenv_a2c_get_step(zenv_t *h, int64_t *step);
+int zenv_a2c_set_step(zenv_t *h, int64_t step);
+/* One chunk: forward, loss and backward on the samples idx[0 .. count) (host or device memory) of an update over
+ * `total` frames.  first != 0 opens the update (the gradient arena and the running statistics are overwritten), first = 0
+ * adds onto them.  Asynchronous on the handle's stream.  ZENV_E_STATE without zenv_a2c_init, without zenv_collect, or for
+ * first = 0 with no update open; ZENV_E_ARG for count outside 1 .. max_batch, total < count, a total other than the open
+ * update's, a host index outside [0, N T).  A device-resident index out of range is dropped and reported once, as
+ * zenv_ppo_minibatch does. */
+int zenv_a2c_accumulate(zenv_t *h, const int32_t *idx, int count, int idx_on_device, int64_t total, int first);
+/* The gradient norm, clip_grad_norm_(max_grad_norm), one step of torch's RMSprop on whatever the gradient arena holds
+ * (the arena keeps the unclipped gradient), step += 1, and the five statistics into ZENV_F_A2C_STATS. */
+int zenv_a2c_apply(zenv_t *h);
+/* All N T frames of the last zenv_collect in index order 0 .. N T - 1 (a2c.py:_get_starting_indexes, recurrence 1) in
+ * chunks of max_batch, then zenv_a2c_apply; no host synchronisation (the first call of a size uploads the index list). */
+int zenv_a2c_update(zenv_t *h);
 
 /* ---- the Zone-goals agent's two PPO updates on the device: update_lo_parameters / update_hi_parameters,
  * zone-goals/src/torch_ac/algos/_hier_policy_opt.py:214-370 ----
