@@ -212,6 +212,24 @@ class Config(C.Structure):
 
 # every symbol include/zenv.h declares: name -> (restype, argtypes)
 _H = C.c_void_p
+
+
+def _learner_prototypes(name, levels=False, updates=True):
+    """What every learner family declares: zenv_<name>_check / _init over its weights and one settings struct per
+    learner, the accessors of a learner's arenas and step count and (updates) the PPO update calls.  levels: a pair of
+    learners, whose calls take `int level` behind the handle."""
+    settings = [C.c_void_p] * (2 if levels else 1)
+    h = [_H, C.c_int] if levels else [_H]
+    out = {"check": [C.POINTER(Config), C.c_void_p] + settings, "init": [_H, C.c_void_p] + settings,
+           "tensor": h + [C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)],
+           "read": h + [C.c_int, C.c_int, C.c_void_p], "write": h + [C.c_int, C.c_int, C.c_void_p],
+           "get_step": h + [C.POINTER(C.c_int64)], "set_step": h + [C.c_int64]}
+    if updates:
+        out.update({"minibatch": h + [C.c_void_p, C.c_int, C.c_int, C.c_int], "apply": h,
+                    "epoch": h + [C.c_void_p, C.c_int, C.c_int, C.c_int]})
+    return {f"zenv_{name}_{call}": (C.c_int, argtypes) for call, argtypes in out.items()}
+
+
 _PROTOTYPES = {
     "zenv_last_error": (C.c_char_p, []),
     "zenv_version": (C.c_char_p, []),
@@ -291,67 +309,13 @@ _PROTOTYPES = {
     "zenv_collect_option": (C.c_int, [_H, C.c_int, C.c_uint64, C.c_uint64, C.c_float, C.c_float,
                                       C.POINTER(C.c_int64)]),
     "zenv_collect_xy": (C.c_int, [_H, C.c_int, C.c_uint64, C.c_uint64, C.c_float, C.c_float]),
-    "zenv_ppo_check": (C.c_int, [C.POINTER(Config), C.c_void_p, C.c_void_p]),
-    "zenv_ppo_init": (C.c_int, [_H, C.c_void_p, C.c_void_p]),
-    "zenv_ppo_tensor": (C.c_int, [_H, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
-    "zenv_ppo_read": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p]),
-    "zenv_ppo_write": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p]),
-    "zenv_ppo_get_step": (C.c_int, [_H, C.POINTER(C.c_int64)]),
-    "zenv_ppo_set_step": (C.c_int, [_H, C.c_int64]),
-    "zenv_ppo_minibatch": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int]),
-    "zenv_ppo_apply": (C.c_int, [_H]),
-    "zenv_ppo_epoch": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int]),
-    "zenv_hppo_check": (C.c_int, [C.POINTER(Config), C.c_void_p, C.c_void_p, C.c_void_p]),
-    "zenv_hppo_init": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "zenv_hppo_tensor": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
-    "zenv_hppo_read": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "zenv_hppo_write": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "zenv_hppo_get_step": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int64)]),
-    "zenv_hppo_set_step": (C.c_int, [_H, C.c_int, C.c_int64]),
-    "zenv_hppo_minibatch": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
-    "zenv_hppo_apply": (C.c_int, [_H, C.c_int]),
-    "zenv_hppo_epoch": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
-    "zenv_xyppo_check": (C.c_int, [C.POINTER(Config), C.c_void_p, C.c_void_p, C.c_void_p]),
-    "zenv_xyppo_init": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "zenv_xyppo_tensor": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
-    "zenv_xyppo_read": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "zenv_xyppo_write": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "zenv_xyppo_get_step": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int64)]),
-    "zenv_xyppo_set_step": (C.c_int, [_H, C.c_int, C.c_int64]),
-    "zenv_xyppo_minibatch": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
-    "zenv_xyppo_apply": (C.c_int, [_H, C.c_int]),
-    "zenv_xyppo_epoch": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
-    "zenv_skppo_check": (C.c_int, [C.POINTER(Config), C.c_void_p, C.c_void_p, C.c_void_p]),
-    "zenv_skppo_init": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "zenv_skppo_tensor": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
-    "zenv_skppo_read": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "zenv_skppo_write": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "zenv_skppo_get_step": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int64)]),
-    "zenv_skppo_set_step": (C.c_int, [_H, C.c_int, C.c_int64]),
-    "zenv_skppo_minibatch": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
-    "zenv_skppo_apply": (C.c_int, [_H, C.c_int]),
-    "zenv_skppo_epoch": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
-    "zenv_opppo_check": (C.c_int, [C.POINTER(Config), C.c_void_p, C.c_void_p, C.c_void_p]),
-    "zenv_opppo_init": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "zenv_opppo_tensor": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
-    "zenv_opppo_read": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "zenv_opppo_write": (C.c_int, [_H, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "zenv_opppo_get_step": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int64)]),
-    "zenv_opppo_set_step": (C.c_int, [_H, C.c_int, C.c_int64]),
-    "zenv_opppo_minibatch": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
-    "zenv_opppo_apply": (C.c_int, [_H, C.c_int]),
-    "zenv_opppo_epoch": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
-    "zenv_diayn_check": (C.c_int, [C.POINTER(Config), C.c_void_p, C.c_void_p]),
-    "zenv_diayn_init": (C.c_int, [_H, C.c_void_p, C.c_void_p]),
-    "zenv_diayn_tensor": (C.c_int, [_H, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
-    "zenv_diayn_read": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p]),
-    "zenv_diayn_write": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p]),
-    "zenv_diayn_get_step": (C.c_int, [_H, C.POINTER(C.c_int64)]),
-    "zenv_diayn_set_step": (C.c_int, [_H, C.c_int64]),
+    **_learner_prototypes("ppo"),
+    **_learner_prototypes("hppo", levels=True),
+    **_learner_prototypes("xyppo", levels=True),
+    **_learner_prototypes("skppo", levels=True),
+    **_learner_prototypes("opppo", levels=True),
+    **_learner_prototypes("diayn"),
     "zenv_diayn_samples": (C.c_int, [_H, C.POINTER(C.c_int64)]),
-    "zenv_diayn_minibatch": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int]),
-    "zenv_diayn_apply": (C.c_int, [_H]),
-    "zenv_diayn_epoch": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "zenv_diayn_prior_init": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_double, C.c_double]),
     "zenv_diayn_prior_update": (C.c_int, [_H]),
     "zenv_diayn_prior_read": (C.c_int, [_H, C.c_void_p]),
@@ -396,13 +360,7 @@ _PROTOTYPES = {
 # The A2C learner's entry points (zenv_a2c_*), bound with the rest in lib().  They are kept in a table of their own: the
 # stream class of every name in _PROTOTYPES is tabled in tests/stream_stall.py, theirs in tests/a2c_stream_classes.py.
 _A2C_PROTOTYPES = {
-    "zenv_a2c_check": (C.c_int, [C.POINTER(Config), C.c_void_p, C.c_void_p]),
-    "zenv_a2c_init": (C.c_int, [_H, C.c_void_p, C.c_void_p]),
-    "zenv_a2c_tensor": (C.c_int, [_H, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
-    "zenv_a2c_read": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p]),
-    "zenv_a2c_write": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p]),
-    "zenv_a2c_get_step": (C.c_int, [_H, C.POINTER(C.c_int64)]),
-    "zenv_a2c_set_step": (C.c_int, [_H, C.c_int64]),
+    **_learner_prototypes("a2c", updates=False),
     "zenv_a2c_accumulate": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int]),
     "zenv_a2c_apply": (C.c_int, [_H]),
     "zenv_a2c_update": (C.c_int, [_H]),

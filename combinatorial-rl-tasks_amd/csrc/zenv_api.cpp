@@ -257,17 +257,13 @@ FieldInfo field_info(const zenv *h, int field)
     case ZENV_F_SKPPO_HI_STATS:
     case ZENV_F_OPPPO_LO_STATS:
     case ZENV_F_OPPPO_HI_STATS:
-    case ZENV_F_DIAYN_STATS: {          // ten consecutive fields, ppo_stats' order
+    case ZENV_F_DIAYN_STATS:            // ten consecutive fields, LearnerSlot's order
+    case ZENV_F_A2C_STATS: {
         int64_t bytes = 0;
-        void *ptr = ppo_stats(h, field - ZENV_F_PPO_STATS, &bytes);
+        void *ptr = ppo_stats(h, field == ZENV_F_A2C_STATS ? L_A2C : field - ZENV_F_PPO_STATS, &bytes);
         return { ptr, bytes };
     }
     case ZENV_F_DIAYN_SAMPLES: return { h->diayn_list, h->diayn_kept > 0 ? h->diayn_kept * 4 : 0 };
-    case ZENV_F_A2C_STATS: {
-        int64_t bytes = 0;
-        void *ptr = a2c_stats(h, &bytes);
-        return { ptr, bytes };
-    }
     default: return { nullptr, 0 };
     }
 }

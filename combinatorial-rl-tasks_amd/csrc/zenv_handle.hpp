@@ -45,6 +45,23 @@ struct Alloc {
 };
 
 struct PpoState;   // zenv_train.cpp
+// A handle's learner slots.  The first ten follow the ZENV_F_PPO_STATS .. ZENV_F_DIAYN_STATS fields, so a statistics
+// field's slot is its distance from ZENV_F_PPO_STATS; a pair's high level is the slot behind its low level.
+enum LearnerSlot {
+    L_FLAT = 0,                     // zenv_ppo_*
+    L_HIER_LO, L_HIER_HI,           // zenv_hppo_*
+    L_XY_LO, L_XY_HI,               // zenv_xyppo_*
+    L_SKILL_LO, L_SKILL_HI,         // zenv_skppo_*
+    L_OPTION_LO, L_OPTION_HI,       // zenv_opppo_*
+    L_DIAYN,                        // zenv_diayn_*: the inverse model
+    L_A2C,                          // zenv_a2c_*: the flat actor-critic's other learner (ZENV_F_A2C_STATS)
+    N_LEARNERS
+};
+static_assert(ZENV_F_PPO_STATS + L_HIER_LO == ZENV_F_HPPO_LO_STATS && ZENV_F_PPO_STATS + L_HIER_HI == ZENV_F_HPPO_HI_STATS &&
+              ZENV_F_PPO_STATS + L_XY_LO == ZENV_F_XYPPO_LO_STATS && ZENV_F_PPO_STATS + L_XY_HI == ZENV_F_XYPPO_HI_STATS &&
+              ZENV_F_PPO_STATS + L_SKILL_LO == ZENV_F_SKPPO_LO_STATS && ZENV_F_PPO_STATS + L_SKILL_HI == ZENV_F_SKPPO_HI_STATS &&
+              ZENV_F_PPO_STATS + L_OPTION_LO == ZENV_F_OPPPO_LO_STATS && ZENV_F_PPO_STATS + L_OPTION_HI == ZENV_F_OPPPO_HI_STATS &&
+              ZENV_F_PPO_STATS + L_DIAYN == ZENV_F_DIAYN_STATS, "LearnerSlot follows the statistics fields");
 
 struct zenv {
     zenv_config cfg{};
@@ -152,20 +169,9 @@ struct zenv {
         float *diversity = nullptr, *env_reward = nullptr;
     } sk;
     void *sk_mem = nullptr;
-    // the flat actor-critic's learner (zenv_ppo_init): arenas, workspace, Adam's step count
-    PpoState *ppo = nullptr;
-    // the flat actor-critic's A2C learner (zenv_a2c_init), beside the PPO one: arenas, workspace, RMSprop's step count
-    PpoState *a2c = nullptr;
-    // the Zone-goals agent's two learners (zenv_hppo_init): [0] the low level, [1] the high level
-    PpoState *hppo[2] = { nullptr, nullptr };
-    // the xy-goals agent's two learners (zenv_xyppo_init): [0] the low level, [1] the high level
-    PpoState *xyppo[2] = { nullptr, nullptr };
-    // the fixed-length-skills agent's two learners (zenv_skppo_init): [0] the low level, [1] the high level
-    PpoState *skppo[2] = { nullptr, nullptr };
-    // the Options agent's two learners (zenv_opppo_init): [0] the low level, [1] the high level
-    PpoState *opppo[2] = { nullptr, nullptr };
-    // DIAYN's inverse-model learner (zenv_diayn_init); it never touches the acting discriminator (skinv)
-    PpoState *diayn = nullptr;
+    // the learners (zenv_*_init), by LearnerSlot: arenas, workspace, the optimiser's step count.  DIAYN's never touches
+    // the acting discriminator (skinv)
+    PpoState *learner[N_LEARNERS] = {};
     // zenv_diayn_samples: the kept sample indexes of the last zenv_collect_skill (ZENV_F_DIAYN_SAMPLES), capacity
     // diayn_cap, and the compaction's block counts behind them in the same allocation; diayn_kept < 0: not taken since
     // the last collection (every collector resets it)
@@ -315,9 +321,6 @@ ZENV_INTERNAL void ppo_free(zenv *h);
 ZENV_INTERNAL void ppo_free_flat(zenv *h);
 // ZENV_E_ARG once an update has met (and dropped) a device-resident index out of range; mlp_range_check() asks
 ZENV_INTERNAL int ppo_index_check(zenv *h);
-// ZENV_F_PPO_STATS (which = 0), ZENV_F_HPPO_LO_STATS (1), ZENV_F_HPPO_HI_STATS (2), ZENV_F_XYPPO_LO_STATS (3),
-// ZENV_F_XYPPO_HI_STATS (4), ZENV_F_SKPPO_LO_STATS (5), ZENV_F_SKPPO_HI_STATS (6), ZENV_F_OPPPO_LO_STATS (7),
-// ZENV_F_OPPPO_HI_STATS (8), ZENV_F_DIAYN_STATS (9): the buffer and the bytes the last update call of that learner filled
-ZENV_INTERNAL void *ppo_stats(const zenv *h, int which, int64_t *bytes);
-// ZENV_F_A2C_STATS: five floats once zenv_a2c_apply / zenv_a2c_update has run
-ZENV_INTERNAL void *a2c_stats(const zenv *h, int64_t *bytes);
+// the statistics field of a LearnerSlot: the buffer and the bytes the last update call of that learner filled
+// (ZENV_F_A2C_STATS: five floats once zenv_a2c_apply / zenv_a2c_update has run)
+ZENV_INTERNAL void *ppo_stats(const zenv *h, int slot, int64_t *bytes);

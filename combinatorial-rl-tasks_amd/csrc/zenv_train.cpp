@@ -169,48 +169,105 @@ int learner_check(const zenv_config *cfg, int h_dim, const float *const *t, NetK
     return ZENV_OK;
 }
 
-void hier_tensor_lists(const zenv_hier_weights *w, const float *(&lo)[PPO_MAX_TENSORS], const float *(&hi)[PPO_MAX_TENSORS])
+// the low level's tensors: zenv_hier_weights, zenv_xy_weights, zenv_skill_weights and zenv_option_weights name them alike
+template <class W>
+void lo_tensor_list(const W *w, const float *(&t)[PPO_MAX_TENSORS])
 {
     const float *l[PPO_MAX_TENSORS] = { w->lo_zone_w1, w->lo_zone_b1, w->lo_zone_w2, w->lo_zone_b2, w->lo_zone_w3,
                                         w->lo_zone_b3, w->lo_comb_w, w->lo_comb_b, w->lo_enc_w, w->lo_enc_b, w->lo_mu_w,
                                         w->lo_mu_b, w->lo_std_w, w->lo_std_b, w->lo_critic_w1, w->lo_critic_b1,
                                         w->lo_critic_w2, w->lo_critic_b2, nullptr, nullptr };
+    std::copy(l, l + PPO_MAX_TENSORS, t);
+}
+
+// the high level's, once per naming: the Zone-goals agent's per-zone actor, ...
+void hi_tensor_list(const zenv_hier_weights *w, const float *(&t)[PPO_MAX_TENSORS])
+{
     const float *u[PPO_MAX_TENSORS] = { w->hi_zone_w1, w->hi_zone_b1, w->hi_zone_w2, w->hi_zone_b2, w->hi_zone_w3,
                                         w->hi_zone_b3, w->hi_comb_w, w->hi_comb_b, w->hi_actor_w1, w->hi_actor_b1,
                                         w->hi_actor_w2, w->hi_actor_b2, w->hi_critic_w1, w->hi_critic_b1, w->hi_critic_w2,
                                         w->hi_critic_b2, nullptr, nullptr, nullptr, nullptr };
-    std::copy(l, l + PPO_MAX_TENSORS, lo);
-    std::copy(u, u + PPO_MAX_TENSORS, hi);
+    std::copy(u, u + PPO_MAX_TENSORS, t);
 }
 
-void xy_tensor_lists(const zenv_xy_weights *w, const float *(&lo)[PPO_MAX_TENSORS], const float *(&hi)[PPO_MAX_TENSORS])
+// ... the xy-goals agent's flat network, ...
+void hi_tensor_list(const zenv_xy_weights *w, const float *(&t)[PPO_MAX_TENSORS])
 {
-    const float *l[PPO_MAX_TENSORS] = { w->lo_zone_w1, w->lo_zone_b1, w->lo_zone_w2, w->lo_zone_b2, w->lo_zone_w3,
-                                        w->lo_zone_b3, w->lo_comb_w, w->lo_comb_b, w->lo_enc_w, w->lo_enc_b, w->lo_mu_w,
-                                        w->lo_mu_b, w->lo_std_w, w->lo_std_b, w->lo_critic_w1, w->lo_critic_b1,
-                                        w->lo_critic_w2, w->lo_critic_b2, nullptr, nullptr };
     const float *u[PPO_MAX_TENSORS] = { w->hi_zone_w1, w->hi_zone_b1, w->hi_zone_w2, w->hi_zone_b2, w->hi_zone_w3,
                                         w->hi_zone_b3, w->hi_comb_w, w->hi_comb_b, w->hi_enc_w, w->hi_enc_b, w->hi_mu_w,
                                         w->hi_mu_b, w->hi_std_w, w->hi_std_b, w->hi_critic_w1, w->hi_critic_b1,
                                         w->hi_critic_w2, w->hi_critic_b2, nullptr, nullptr };
-    std::copy(l, l + PPO_MAX_TENSORS, lo);
-    std::copy(u, u + PPO_MAX_TENSORS, hi);
+    std::copy(u, u + PPO_MAX_TENSORS, t);
 }
 
-// W: zenv_skill_weights or zenv_option_weights, the same members
+// ... and the skill head of zenv_skill_weights and zenv_option_weights, the same members
 template <class W>
-void skill_tensor_lists(const W *w, const float *(&lo)[PPO_MAX_TENSORS], const float *(&hi)[PPO_MAX_TENSORS])
+void hi_tensor_list(const W *w, const float *(&t)[PPO_MAX_TENSORS])
 {
-    const float *l[PPO_MAX_TENSORS] = { w->lo_zone_w1, w->lo_zone_b1, w->lo_zone_w2, w->lo_zone_b2, w->lo_zone_w3,
-                                        w->lo_zone_b3, w->lo_comb_w, w->lo_comb_b, w->lo_enc_w, w->lo_enc_b, w->lo_mu_w,
-                                        w->lo_mu_b, w->lo_std_w, w->lo_std_b, w->lo_critic_w1, w->lo_critic_b1,
-                                        w->lo_critic_w2, w->lo_critic_b2, nullptr, nullptr };
     const float *u[PPO_MAX_TENSORS] = { w->hi_zone_w1, w->hi_zone_b1, w->hi_zone_w2, w->hi_zone_b2, w->hi_zone_w3,
                                         w->hi_zone_b3, w->hi_comb_w, w->hi_comb_b, w->hi_enc_w, w->hi_enc_b,
                                         w->hi_logit_w, w->hi_logit_b, w->hi_critic_w1, w->hi_critic_b1, w->hi_critic_w2,
                                         w->hi_critic_b2, nullptr, nullptr, nullptr, nullptr };
-    std::copy(l, l + PPO_MAX_TENSORS, lo);
-    std::copy(u, u + PPO_MAX_TENSORS, hi);
+    std::copy(u, u + PPO_MAX_TENSORS, t);
+}
+
+// the number of skills the weights are of; the goal agents have none
+template <class W>
+int skills_of(const W *w) { return w->n_skills; }
+int skills_of(const zenv_hier_weights *) { return 0; }
+int skills_of(const zenv_xy_weights *) { return 0; }
+
+// ---- the learner families: what the entry points zenv_<name>_* have in common
+enum { AGENT_FLAT = 0, AGENT_HIER, AGENT_XY, AGENT_SKILL, AGENT_OPTION, AGENT_DIAYN, AGENT_A2C, N_AGENTS };
+
+struct Family {
+    const char *name;               // "zenv_<name>_init first"
+    int first;                      // its LearnerSlot; with levels: the low level's, the high level's is the next
+    bool levels;                    // a pair: the entry points take level 0 (low) or 1 (high)
+    bool skills;                    // its weights carry n_skills
+    bool net_rows;                  // trains on the rows the flat network reads (net_row_feat), not the handle's p.F
+    int arenas;                     // the arenas `which` may name: Adam's four, RMSprop's three
+    NetKind (*kind[2])(int S);      // the network of each level (the one of a family without levels in [0])
+};
+const Family kFamily[N_AGENTS] = {
+    { "ppo", L_FLAT, false, false, true, 4, { [](int) { return kFlat; }, nullptr } },
+    { "hppo", L_HIER_LO, true, false, false, 4, { [](int) { return kHierLo; }, [](int) { return kHierHi; } } },
+    { "xyppo", L_XY_LO, true, false, false, 4, { [](int) { return kXyLo; }, [](int) { return kXyHi; } } },
+    { "skppo", L_SKILL_LO, true, true, false, 4, { sk_lo, sk_hi } },
+    { "opppo", L_OPTION_LO, true, true, false, 4, { op_lo, sk_hi } },
+    { "diayn", L_DIAYN, false, true, false, 4, { inv_kind, nullptr } },
+    { "a2c", L_A2C, false, false, true, 3, { [](int) { return kA2c; }, nullptr } },
+};
+static_assert(ZENV_PPO_PARAM == 0 && ZENV_PPO_EXP_AVG_SQ == 3 && ZENV_A2C_PARAM == 0 && ZENV_A2C_SQUARE_AVG == 2,
+              "Family::arenas");
+
+int check_skills(int n_skills)
+{
+    if (n_skills < 1 || n_skills > kMaxSkills) return fail(ZENV_E_ARG, "n_skills %d outside [1, %d]", n_skills, kMaxSkills);
+    return ZENV_OK;
+}
+
+int check_zone_feat(const zenv_config *cfg, int zone_feat)
+{
+    if (zone_feat != zenv_zone_feat(cfg))
+        return fail(ZENV_E_ARG, "zone_feat %d: the handle's zone rows have %d features", zone_feat, zenv_zone_feat(cfg));
+    return ZENV_OK;
+}
+
+// zenv_hppo_check / _xyppo_ / _skppo_ / _opppo_: the two levels of a pair's weights
+template <class W>
+int pair_check(int agent, const zenv_config *cfg, const W *w, const zenv_ppo_config *lo, const zenv_ppo_config *hi)
+{
+    if (!cfg || !w || !lo || !hi) return fail(ZENV_E_ARG, "null argument");
+    const Family &f = kFamily[agent];
+    if (f.skills)
+        if (int rc = check_skills(skills_of(w))) return rc;
+    if (int rc = check_zone_feat(cfg, w->zone_feat)) return rc;
+    const float *tl[PPO_MAX_TENSORS], *th[PPO_MAX_TENSORS];
+    lo_tensor_list(w, tl);
+    hi_tensor_list(w, th);
+    if (int rc = learner_check(cfg, w->h_dim, tl, f.kind[0](skills_of(w)), lo, "low level: ")) return rc;
+    return learner_check(cfg, w->h_dim, th, f.kind[1](skills_of(w)), hi, "high level: ");
 }
 
 }  // namespace
@@ -232,53 +289,25 @@ extern "C" int zenv_ppo_check(const zenv_config *cfg, const zenv_mlp_weights *w,
 extern "C" int zenv_hppo_check(const zenv_config *cfg, const zenv_hier_weights *w, const zenv_ppo_config *lo,
                                const zenv_ppo_config *hi)
 {
-    if (!cfg || !w || !lo || !hi) return fail(ZENV_E_ARG, "null argument");
-    if (w->zone_feat != zenv_zone_feat(cfg))
-        return fail(ZENV_E_ARG, "zone_feat %d: the handle's zone rows have %d features", w->zone_feat, zenv_zone_feat(cfg));
-    const float *tl[PPO_MAX_TENSORS], *th[PPO_MAX_TENSORS];
-    hier_tensor_lists(w, tl, th);
-    if (int rc = learner_check(cfg, w->h_dim, tl, kHierLo, lo, "low level: ")) return rc;
-    return learner_check(cfg, w->h_dim, th, kHierHi, hi, "high level: ");
+    return pair_check(AGENT_HIER, cfg, w, lo, hi);
 }
 
 extern "C" int zenv_xyppo_check(const zenv_config *cfg, const zenv_xy_weights *w, const zenv_ppo_config *lo,
                                 const zenv_ppo_config *hi)
 {
-    if (!cfg || !w || !lo || !hi) return fail(ZENV_E_ARG, "null argument");
-    if (w->zone_feat != zenv_zone_feat(cfg))
-        return fail(ZENV_E_ARG, "zone_feat %d: the handle's zone rows have %d features", w->zone_feat, zenv_zone_feat(cfg));
-    const float *tl[PPO_MAX_TENSORS], *th[PPO_MAX_TENSORS];
-    xy_tensor_lists(w, tl, th);
-    if (int rc = learner_check(cfg, w->h_dim, tl, kXyLo, lo, "low level: ")) return rc;
-    return learner_check(cfg, w->h_dim, th, kXyHi, hi, "high level: ");
+    return pair_check(AGENT_XY, cfg, w, lo, hi);
 }
 
 extern "C" int zenv_skppo_check(const zenv_config *cfg, const zenv_skill_weights *w, const zenv_ppo_config *lo,
                                 const zenv_ppo_config *hi)
 {
-    if (!cfg || !w || !lo || !hi) return fail(ZENV_E_ARG, "null argument");
-    if (w->n_skills < 1 || w->n_skills > kMaxSkills)
-        return fail(ZENV_E_ARG, "n_skills %d outside [1, %d]", w->n_skills, kMaxSkills);
-    if (w->zone_feat != zenv_zone_feat(cfg))
-        return fail(ZENV_E_ARG, "zone_feat %d: the handle's zone rows have %d features", w->zone_feat, zenv_zone_feat(cfg));
-    const float *tl[PPO_MAX_TENSORS], *th[PPO_MAX_TENSORS];
-    skill_tensor_lists(w, tl, th);
-    if (int rc = learner_check(cfg, w->h_dim, tl, sk_lo(w->n_skills), lo, "low level: ")) return rc;
-    return learner_check(cfg, w->h_dim, th, sk_hi(w->n_skills), hi, "high level: ");
+    return pair_check(AGENT_SKILL, cfg, w, lo, hi);
 }
 
 extern "C" int zenv_opppo_check(const zenv_config *cfg, const zenv_option_weights *w, const zenv_ppo_config *lo,
                                 const zenv_ppo_config *hi)
 {
-    if (!cfg || !w || !lo || !hi) return fail(ZENV_E_ARG, "null argument");
-    if (w->n_skills < 1 || w->n_skills > kMaxSkills)
-        return fail(ZENV_E_ARG, "n_skills %d outside [1, %d]", w->n_skills, kMaxSkills);
-    if (w->zone_feat != zenv_zone_feat(cfg))
-        return fail(ZENV_E_ARG, "zone_feat %d: the handle's zone rows have %d features", w->zone_feat, zenv_zone_feat(cfg));
-    const float *tl[PPO_MAX_TENSORS], *th[PPO_MAX_TENSORS];
-    skill_tensor_lists(w, tl, th);
-    if (int rc = learner_check(cfg, w->h_dim, tl, op_lo(w->n_skills), lo, "low level: ")) return rc;
-    return learner_check(cfg, w->h_dim, th, sk_hi(w->n_skills), hi, "high level: ");
+    return pair_check(AGENT_OPTION, cfg, w, lo, hi);
 }
 
 static void inverse_tensor_list(const zenv_skill_inverse_weights *w, const float *(&t)[PPO_MAX_TENSORS])
@@ -291,10 +320,8 @@ static void inverse_tensor_list(const zenv_skill_inverse_weights *w, const float
 extern "C" int zenv_diayn_check(const zenv_config *cfg, const zenv_skill_inverse_weights *w, const zenv_ppo_config *pc)
 {
     if (!cfg || !w || !pc) return fail(ZENV_E_ARG, "null argument");
-    if (w->n_skills < 1 || w->n_skills > kMaxSkills)
-        return fail(ZENV_E_ARG, "n_skills %d outside [1, %d]", w->n_skills, kMaxSkills);
-    if (w->zone_feat != zenv_zone_feat(cfg))
-        return fail(ZENV_E_ARG, "zone_feat %d: the handle's zone rows have %d features", w->zone_feat, zenv_zone_feat(cfg));
+    if (int rc = check_skills(w->n_skills)) return rc;
+    if (int rc = check_zone_feat(cfg, w->zone_feat)) return rc;
     if (w->precision != ZENV_MLP_F32) return fail(ZENV_E_ARG, "precision %d: the inverse model is float32 only", w->precision);
     const float *t[PPO_MAX_TENSORS];
     inverse_tensor_list(w, t);
@@ -313,23 +340,13 @@ static void learner_free(PpoState *&s)
 
 void ppo_free_flat(zenv *h)
 {
-    learner_free(h->ppo);
-    learner_free(h->a2c);
+    for (const Family &f : kFamily)
+        if (f.net_rows) learner_free(h->learner[f.first]);
 }
 
 void ppo_free(zenv *h)
 {
-    learner_free(h->ppo);
-    learner_free(h->a2c);
-    learner_free(h->hppo[0]);
-    learner_free(h->hppo[1]);
-    learner_free(h->xyppo[0]);
-    learner_free(h->xyppo[1]);
-    learner_free(h->skppo[0]);
-    learner_free(h->skppo[1]);
-    learner_free(h->opppo[0]);
-    learner_free(h->opppo[1]);
-    learner_free(h->diayn);
+    for (PpoState *&s : h->learner) learner_free(s);
     if (h->diayn_mem) (void)hipFree(h->diayn_mem);
     if (h->diayn_counts) (void)hipFree(h->diayn_counts);
     if (h->diayn_flag) (void)hipHostFree(h->diayn_flag);
@@ -341,8 +358,7 @@ void ppo_free(zenv *h)
 int ppo_index_check(zenv *h)
 {
     bool bad = false;
-    for (PpoState *s : { h->ppo, h->hppo[0], h->hppo[1], h->xyppo[0], h->xyppo[1], h->skppo[0], h->skppo[1],
-                          h->opppo[0], h->opppo[1], h->diayn, h->a2c })
+    for (PpoState *s : h->learner)
         if (s && s->net.bad_index && *(volatile int *)s->net.bad_index) {
             *(volatile int *)s->net.bad_index = 0;
             bad = true;
@@ -357,33 +373,27 @@ int ppo_index_check(zenv *h)
                             "synchronising call is invalid");
 }
 
-void *ppo_stats(const zenv *h, int which, int64_t *bytes)
+void *ppo_stats(const zenv *h, int slot, int64_t *bytes)
 {
-    const PpoState *s = which == 0 ? h->ppo : which <= 2 ? h->hppo[which - 1] : which <= 4 ? h->xyppo[which - 3]
-                                                 : which <= 6 ? h->skppo[which - 5] : which <= 8 ? h->opppo[which - 7]
-                                                 : h->diayn;
-    *bytes = s ? (int64_t)s->stats_rows * kPpoStats * 4 : 0;
+    const PpoState *s = h->learner[slot];
+    *bytes = s ? (int64_t)s->stats_rows * (slot == L_A2C ? kA2cStats : kPpoStats) * 4 : 0;
     return s ? s->stats : nullptr;
 }
 
-void *a2c_stats(const zenv *h, int64_t *bytes)
-{
-    const PpoState *s = h->a2c;
-    *bytes = s ? (int64_t)s->stats_rows * kA2cStats * 4 : 0;
-    return s ? s->stats : nullptr;
-}
-
-// a learner of kind k in `slot` (replacing what is there) from the tensors t in arena order; checked by the caller
-static int learner_create(zenv *h, PpoState *&slot, int h_dim, const float *const *t, NetKind k, const zenv_ppo_config *pc)
+// a learner of kind k in the family's slot of `level` (replacing what is there) from the tensors t in arena order;
+// checked by the caller
+static int learner_create(zenv *h, int agent, int level, int h_dim, const float *const *t, NetKind k,
+                          const zenv_ppo_config *pc)
 {
     if (int rc = use_device(h)) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
+    PpoState *&slot = h->learner[kFamily[agent].first + level];
     learner_free(slot);
     PpoState *s = new PpoState();
     slot = s;
     PpoNet &n = s->net;
-    // the flat learner trains on the rows the flat network reads (zenv_order_rows: 7 wide on a solver-ordered handle)
-    const int F = (&slot == &h->ppo || &slot == &h->a2c) ? net_row_feat(h) : h->p.F;
+    // the flat learners train on the rows the flat network reads (zenv_order_rows: 7 wide on a solver-ordered handle)
+    const int F = kFamily[agent].net_rows ? net_row_feat(h) : h->p.F;
     const Layout l = layout_for(h_dim, h->p.Z, F, pc->max_batch, k);
     n.h = h_dim, n.HP = l.HP, n.F = F, n.Z = h->p.Z, n.K1 = k.XD + F, n.KC = l.KC;
     n.XD = k.XD, n.W1C = k.w1c(F), n.head = k.head, n.loss = k.loss, n.S = k.S, n.NA = k.NA, n.LDC = l.LDC;
@@ -446,68 +456,47 @@ extern "C" int zenv_ppo_init(zenv_t *h, const zenv_mlp_weights *w, const zenv_pp
     if (int rc = zenv_ppo_check(&h->cfg, w, pc)) return rc;
     const float *t[PPO_MAX_TENSORS];
     tensor_list(w, t);
-    return learner_create(h, h->ppo, w->h_dim, t, kFlat, pc);
+    return learner_create(h, AGENT_FLAT, 0, w->h_dim, t, kFlat, pc);
+}
+
+// zenv_hppo_init / _xyppo_ / _skppo_ / _opppo_: both learners of a pair, or neither
+template <class W>
+static int pair_init(int agent, zenv *h, const W *w, const zenv_ppo_config *lo, const zenv_ppo_config *hi)
+{
+    if (!h || !w || !lo || !hi) return fail(ZENV_E_ARG, "null argument");
+    if (int rc = pair_check(agent, &h->cfg, w, lo, hi)) return rc;
+    const Family &f = kFamily[agent];
+    const float *tl[PPO_MAX_TENSORS], *th[PPO_MAX_TENSORS];
+    lo_tensor_list(w, tl);
+    hi_tensor_list(w, th);
+    int rc = learner_create(h, agent, 0, w->h_dim, tl, f.kind[0](skills_of(w)), lo);
+    if (!rc) rc = learner_create(h, agent, 1, w->h_dim, th, f.kind[1](skills_of(w)), hi);
+    if (rc) {                   // no half-pair: a failed init leaves the handle without either learner
+        learner_free(h->learner[f.first]);
+        learner_free(h->learner[f.first + 1]);
+    }
+    return rc;
 }
 
 extern "C" int zenv_hppo_init(zenv_t *h, const zenv_hier_weights *w, const zenv_ppo_config *lo, const zenv_ppo_config *hi)
 {
-    if (!h || !w || !lo || !hi) return fail(ZENV_E_ARG, "null argument");
-    if (int rc = zenv_hppo_check(&h->cfg, w, lo, hi)) return rc;
-    const float *tl[PPO_MAX_TENSORS], *th[PPO_MAX_TENSORS];
-    hier_tensor_lists(w, tl, th);
-    int rc = learner_create(h, h->hppo[0], w->h_dim, tl, kHierLo, lo);
-    if (!rc) rc = learner_create(h, h->hppo[1], w->h_dim, th, kHierHi, hi);
-    if (rc) {                   // no half-pair: a failed init leaves the handle without either learner
-        learner_free(h->hppo[0]);
-        learner_free(h->hppo[1]);
-    }
-    return rc;
+    return pair_init(AGENT_HIER, h, w, lo, hi);
 }
 
 extern "C" int zenv_xyppo_init(zenv_t *h, const zenv_xy_weights *w, const zenv_ppo_config *lo, const zenv_ppo_config *hi)
 {
-    if (!h || !w || !lo || !hi) return fail(ZENV_E_ARG, "null argument");
-    if (int rc = zenv_xyppo_check(&h->cfg, w, lo, hi)) return rc;
-    const float *tl[PPO_MAX_TENSORS], *th[PPO_MAX_TENSORS];
-    xy_tensor_lists(w, tl, th);
-    int rc = learner_create(h, h->xyppo[0], w->h_dim, tl, kXyLo, lo);
-    if (!rc) rc = learner_create(h, h->xyppo[1], w->h_dim, th, kXyHi, hi);
-    if (rc) {                   // no half-pair
-        learner_free(h->xyppo[0]);
-        learner_free(h->xyppo[1]);
-    }
-    return rc;
+    return pair_init(AGENT_XY, h, w, lo, hi);
 }
 
 extern "C" int zenv_skppo_init(zenv_t *h, const zenv_skill_weights *w, const zenv_ppo_config *lo, const zenv_ppo_config *hi)
 {
-    if (!h || !w || !lo || !hi) return fail(ZENV_E_ARG, "null argument");
-    if (int rc = zenv_skppo_check(&h->cfg, w, lo, hi)) return rc;
-    const float *tl[PPO_MAX_TENSORS], *th[PPO_MAX_TENSORS];
-    skill_tensor_lists(w, tl, th);
-    int rc = learner_create(h, h->skppo[0], w->h_dim, tl, sk_lo(w->n_skills), lo);
-    if (!rc) rc = learner_create(h, h->skppo[1], w->h_dim, th, sk_hi(w->n_skills), hi);
-    if (rc) {                   // no half-pair
-        learner_free(h->skppo[0]);
-        learner_free(h->skppo[1]);
-    }
-    return rc;
+    return pair_init(AGENT_SKILL, h, w, lo, hi);
 }
 
 extern "C" int zenv_opppo_init(zenv_t *h, const zenv_option_weights *w, const zenv_ppo_config *lo,
                                const zenv_ppo_config *hi)
 {
-    if (!h || !w || !lo || !hi) return fail(ZENV_E_ARG, "null argument");
-    if (int rc = zenv_opppo_check(&h->cfg, w, lo, hi)) return rc;
-    const float *tl[PPO_MAX_TENSORS], *th[PPO_MAX_TENSORS];
-    skill_tensor_lists(w, tl, th);
-    int rc = learner_create(h, h->opppo[0], w->h_dim, tl, op_lo(w->n_skills), lo);
-    if (!rc) rc = learner_create(h, h->opppo[1], w->h_dim, th, sk_hi(w->n_skills), hi);
-    if (rc) {                   // no half-pair
-        learner_free(h->opppo[0]);
-        learner_free(h->opppo[1]);
-    }
-    return rc;
+    return pair_init(AGENT_OPTION, h, w, lo, hi);
 }
 
 extern "C" int zenv_diayn_init(zenv_t *h, const zenv_skill_inverse_weights *w, const zenv_ppo_config *pc)
@@ -516,55 +505,29 @@ extern "C" int zenv_diayn_init(zenv_t *h, const zenv_skill_inverse_weights *w, c
     if (int rc = zenv_diayn_check(&h->cfg, w, pc)) return rc;
     const float *t[PPO_MAX_TENSORS];
     inverse_tensor_list(w, t);
-    const int rc = learner_create(h, h->diayn, w->h_dim, t, inv_kind(w->n_skills), pc);
-    if (rc) learner_free(h->diayn);     // no half-built learner
+    const int rc = learner_create(h, AGENT_DIAYN, 0, w->h_dim, t, inv_kind(w->n_skills), pc);
+    if (rc) learner_free(h->learner[L_DIAYN]);      // no half-built learner
     return rc;
 }
 
 namespace {
 
-enum { AGENT_FLAT = 0, AGENT_HIER = 1, AGENT_XY = 2, AGENT_SKILL = 3, AGENT_OPTION = 4, AGENT_DIAYN = 5 };
-
-// What an entry point works on: the flat learner, or level 0 / 1 of the Zone-goals or the xy-goals pair with the
-// experience they read.
+// What an entry point works on: a family's learner (of a pair: level 0 or 1, else -1) with the experience it reads.
 struct Learner {
     PpoState *s = nullptr;
-    int level = -1;                 // -1: the flat learner
+    int level = -1;
     int agent = AGENT_FLAT;
 };
 
 int find_learner(zenv *h, int level, int agent, Learner &out)
 {
     if (!h) return fail(ZENV_E_ARG, "null handle");
-    const bool hier = agent != AGENT_FLAT;
-    if (!hier) {
-        if (!h->ppo) return fail(ZENV_E_STATE, "zenv_ppo_init first");
-        out = Learner{ h->ppo, -1, AGENT_FLAT };
-        return ZENV_OK;
-    }
-    if (agent == AGENT_DIAYN) {         // one learner: the inverse model's
-        if (!h->diayn) return fail(ZENV_E_STATE, "zenv_diayn_init first");
-        out = Learner{ h->diayn, 0, AGENT_DIAYN };
-        return ZENV_OK;
-    }
+    const Family &f = kFamily[agent];
+    if (!f.levels) level = 0;
     if (level != 0 && level != 1) return fail(ZENV_E_ARG, "level %d: 0 is the low level, 1 the high level", level);
-    if (agent == AGENT_XY) {
-        if (!h->xyppo[level]) return fail(ZENV_E_STATE, "zenv_xyppo_init first");
-        out = Learner{ h->xyppo[level], level, AGENT_XY };
-        return ZENV_OK;
-    }
-    if (agent == AGENT_SKILL) {
-        if (!h->skppo[level]) return fail(ZENV_E_STATE, "zenv_skppo_init first");
-        out = Learner{ h->skppo[level], level, AGENT_SKILL };
-        return ZENV_OK;
-    }
-    if (agent == AGENT_OPTION) {
-        if (!h->opppo[level]) return fail(ZENV_E_STATE, "zenv_opppo_init first");
-        out = Learner{ h->opppo[level], level, AGENT_OPTION };
-        return ZENV_OK;
-    }
-    if (!h->hppo[level]) return fail(ZENV_E_STATE, "zenv_hppo_init first");
-    out = Learner{ h->hppo[level], level, AGENT_HIER };
+    PpoState *s = h->learner[f.first + level];
+    if (!s) return fail(ZENV_E_STATE, "zenv_%s_init first", f.name);
+    out = Learner{ s, f.levels ? level : -1, agent };
     return ZENV_OK;
 }
 
@@ -572,7 +535,7 @@ int learner_tensor(const Learner &l, int which, int index, void **dev_ptr, int64
 {
     if (!dev_ptr || !count) return fail(ZENV_E_ARG, "null argument");
     const PpoNet &n = l.s->net;
-    if (which < ZENV_PPO_PARAM || which > ZENV_PPO_EXP_AVG_SQ) return fail(ZENV_E_ARG, "unknown arena %d", which);
+    if (which < 0 || which >= kFamily[l.agent].arenas) return fail(ZENV_E_ARG, "unknown arena %d", which);
     if (index < -1 || index >= n.n_tensors) return fail(ZENV_E_ARG, "tensor index %d outside [-1, %d)", index, n.n_tensors);
     float *base = n.param + (int64_t)which * n.arena;
     *dev_ptr = index < 0 ? base : base + n.off[index];
@@ -601,12 +564,34 @@ int learner_set_step(const Learner &l, int64_t step)
     return ZENV_OK;
 }
 
+// the records the handle holds are zenv_collect_skill's.  exp_skill says so by itself -- the collector sets it once its
+// buffers of exp.T frames are complete and every collector's start clears it -- the other terms are its consequences
+bool skill_records(const zenv *h)
+{
+    return h->exp_mem && h->exp_skill && h->hi_kind == 1 && h->sk_mem && h->sk.T == h->exp.T && h->hi_m >= 1;
+}
+
+int need_skill_records(const zenv *h)
+{
+    if (!skill_records(h))
+        return fail(ZENV_E_STATE, "zenv_collect_skill first: the ZENV_F_EXP_* / ZENV_F_LO_* / ZENV_F_HI_* buffers do "
+                                  "not hold its records");
+    return ZENV_OK;
+}
+
+// the records are of an agent with the learner's number of skills (ready: that agent is loaded)
+int need_learner_skills(const zenv *h, bool ready, const Learner &l)
+{
+    if (!ready || h->skill.S != l.s->net.S)
+        return fail(ZENV_E_STATE, "the records are of an agent with another number of skills than the learner's %d",
+                    l.s->net.S);
+    return ZENV_OK;
+}
+
 // what DIAYN's two updates read: a completed zenv_collect_skill of at least two frames
 int diayn_records(const zenv *h)
 {
-    if (!h->exp_mem || !h->exp_skill || h->hi_kind != 1 || !h->sk_mem || h->sk.T != h->exp.T || h->hi_m < 1)
-        return fail(ZENV_E_STATE, "zenv_collect_skill first: the ZENV_F_EXP_* / ZENV_F_LO_* / ZENV_F_HI_* buffers do "
-                                  "not hold its records");
+    if (int rc = need_skill_records(h)) return rc;
     if (h->exp.T < 2)
         return fail(ZENV_E_STATE, "a collection of one frame has no (next observation, skill) pair for the inverse model");
     return ZENV_OK;
@@ -653,98 +638,83 @@ int diayn_any_kept(zenv *h)
 int learner_exp(const zenv *h, const Learner &l, PpoExp &x, int64_t &samples)
 {
     const ExpBuffers &e = h->exp;
-    if (l.level < 0) {
-        if (!h->exp_mem) return fail(ZENV_E_STATE, "zenv_collect first: the handle holds no experience");
-        x = PpoExp{ e.obs, e.zone_obs, e.action, e.log_prob, e.value, e.advantage, e.returnn, h->n_env, e.T, nullptr,
-                    nullptr, nullptr };
-        samples = (int64_t)h->n_env * e.T;
-        return ZENV_OK;
-    }
-    if (l.agent == AGENT_DIAYN) {
+    const HierOut &o = h->hout;
+    // T frames of every env, the flat collector's columns; what else a low level reads of a frame is set by its case
+    auto frames = [&](int T) {
+        x = PpoExp{ e.obs, e.zone_obs, e.action, e.log_prob, e.value, e.advantage, e.returnn, h->n_env, T, nullptr, nullptr,
+                    nullptr };
+        samples = (int64_t)h->n_env * T;
+    };
+    // the M dense env-major rows of a high level, the pick as the action, one log_prob per row
+    auto rows = [&]() {
+        x = PpoExp{ o.obs, o.zone_obs, nullptr, o.log_prob, o.value, o.advantage, o.returnn, (int)h->hi_m, 1, nullptr, o.action,
+                    nullptr };
+        samples = h->hi_m;
+    };
+    const bool high = l.level == 1;
+    switch (l.agent) {
+    case AGENT_DIAYN:
         if (int rc = diayn_records(h)) return rc;
-        if (!h->skill_ready || h->skill.S != l.s->net.S)
-            return fail(ZENV_E_STATE, "the records are of an agent with another number of skills than the learner's %d",
-                        l.s->net.S);
+        if (int rc = need_learner_skills(h, h->skill_ready, l)) return rc;
         // the pairs (obs of frame f + 1, skill of frame f), f in 0 .. T-2, where the mask of frame f + 1 is not 0
         // (_hier_policy_opt.py:193-199)
-        x = PpoExp{ e.obs, e.zone_obs, nullptr, nullptr, nullptr, nullptr, nullptr, h->n_env, e.T - 1, nullptr, nullptr,
-                    nullptr, h->sk.lo_skill, nullptr, nullptr, 1, e.mask };
-        samples = (int64_t)h->n_env * (e.T - 1);
+        frames(e.T - 1);
+        x.action = x.log_prob = x.value = x.advantage = x.returnn = nullptr;
+        x.skill = h->sk.lo_skill, x.obs_shift = 1, x.keep = e.mask;
         return ZENV_OK;
-    }
-    if (l.agent == AGENT_XY) {
+    case AGENT_XY:
         if (!h->exp_mem || !h->exp_xy || h->hi_kind != 3 || !h->xc_mem || h->xc.T != e.T)
             return fail(ZENV_E_STATE, "zenv_collect_xy first: the ZENV_F_EXP_* / ZENV_F_LO_* / ZENV_F_HI_* buffers do not "
                                       "hold its records");
-        if (l.level == 0) {     // ALL T frames of every env (_hier_policy_opt.py:147-158), the goal the frame was acted under
-            x = PpoExp{ e.obs, e.zone_obs, e.action, e.log_prob, e.value, e.advantage, e.returnn, h->n_env, e.T,
-                        reinterpret_cast<const float *>(h->xc.lo_goal), nullptr, nullptr };
-            samples = (int64_t)h->n_env * e.T;
-            return ZENV_OK;
+        if (!high) {            // ALL T frames of every env (_hier_policy_opt.py:147-158), the goal the frame was acted under
+            frames(e.T);
+            x.goal = reinterpret_cast<const float *>(h->xc.lo_goal);
+        } else {                // the windows, M = N W: the goal is the action
+            rows();
+            x.action = reinterpret_cast<const float *>(h->xc.hi_goal), x.hi_action = nullptr;
         }
-        // the dense env-major rows of the windows: M = N W, the goal as the action, one log_prob per row
-        const HierOut &o = h->hout;
-        x = PpoExp{ o.obs, o.zone_obs, reinterpret_cast<const float *>(h->xc.hi_goal), o.log_prob, o.value, o.advantage,
-                    o.returnn, (int)h->hi_m, 1, nullptr, nullptr, nullptr };
-        samples = h->hi_m;
         return ZENV_OK;
-    }
-    if (l.agent == AGENT_SKILL) {
-        if (!h->exp_mem || !h->exp_skill || h->hi_kind != 1 || !h->sk_mem || h->sk.T != e.T || h->hi_m < 1)
-            return fail(ZENV_E_STATE, "zenv_collect_skill first: the ZENV_F_EXP_* / ZENV_F_LO_* / ZENV_F_HI_* buffers do "
-                                      "not hold its records");
-        if (!h->skill_ready || h->skill.S != l.s->net.S)
-            return fail(ZENV_E_STATE, "the records are of an agent with another number of skills than the learner's %d",
-                        l.s->net.S);
-        if (l.level == 0) {     // ALL T frames of every env (_hier_policy_opt.py:188-199), the skill the frame was acted under
-            x = PpoExp{ e.obs, e.zone_obs, e.action, e.log_prob, e.value, e.advantage, e.returnn, h->n_env, e.T, nullptr,
-                        nullptr, nullptr, h->sk.lo_skill };
-            samples = (int64_t)h->n_env * e.T;
-            return ZENV_OK;
+    case AGENT_SKILL:
+        if (int rc = need_skill_records(h)) return rc;
+        if (int rc = need_learner_skills(h, h->skill_ready, l)) return rc;
+        if (!high) {            // ALL T frames of every env (_hier_policy_opt.py:188-199), the skill the frame was acted under
+            frames(e.T);
+            x.skill = h->sk.lo_skill;
+        } else {                // the windows, M = N T / skill_len
+            rows();
         }
-        // the dense env-major rows of the windows: M = N T / skill_len, the skill as the action, one log_prob per row
-        const HierOut &o = h->hout;
-        x = PpoExp{ o.obs, o.zone_obs, nullptr, o.log_prob, o.value, o.advantage, o.returnn, (int)h->hi_m, 1, nullptr,
-                    o.action, nullptr, nullptr };
-        samples = h->hi_m;
         return ZENV_OK;
-    }
-    if (l.agent == AGENT_OPTION) {
+    case AGENT_OPTION:
         if (!h->exp_mem || !h->exp_option || h->hi_kind != 2 || !h->oc_mem || h->oc.T != e.T)
             return fail(ZENV_E_STATE, "zenv_collect_option first: the ZENV_F_EXP_* / ZENV_F_LO_* / ZENV_F_HI_* buffers do "
                                       "not hold its records");
-        if (!h->option_ready || h->skill.S != l.s->net.S)
-            return fail(ZENV_E_STATE, "the records are of an agent with another number of skills than the learner's %d",
-                        l.s->net.S);
-        if (l.level == 0) {     // frames 0 .. T-2 of every env (_hier_policy_opt.py:111-118); a_2's records are the oc ones
-            x = PpoExp{ e.obs, e.zone_obs, e.action, e.log_prob, e.value, e.advantage, e.returnn, h->n_env, e.T - 1, nullptr,
-                        nullptr, nullptr, h->oc.lo_skill, h->oc.term_action, h->oc.term_log_prob };
-            samples = (int64_t)h->n_env * (e.T - 1);
+        if (int rc = need_learner_skills(h, h->option_ready, l)) return rc;
+        if (!high) {            // frames 0 .. T-2 of every env (_hier_policy_opt.py:111-118); a_2's records are the oc ones
+            frames(e.T - 1);
+            x.skill = h->oc.lo_skill, x.term_action = h->oc.term_action, x.term_log_prob = h->oc.term_log_prob;
             return ZENV_OK;
         }
         if (h->hi_m < 1) return fail(ZENV_E_STATE, "the last zenv_collect_option closed no high-level transition (M = 0)");
-        // the dense env-major rows of the closed transitions, the skill as the action, one log_prob per row
-        const HierOut &o = h->hout;
-        x = PpoExp{ o.obs, o.zone_obs, nullptr, o.log_prob, o.value, o.advantage, o.returnn, (int)h->hi_m, 1, nullptr,
-                    o.action, nullptr, nullptr };
-        samples = h->hi_m;
+        rows();                 // the closed transitions
+        return ZENV_OK;
+    case AGENT_HIER:
+        if (!h->exp_mem || !h->exp_hier || h->hi_kind != 0 || !h->hframes.lo_goal)
+            return fail(ZENV_E_STATE, "zenv_collect_hier first: the ZENV_F_EXP_* / ZENV_F_LO_* / ZENV_F_HI_* buffers do not "
+                                      "hold its records");
+        if (!high) {            // frames 0 .. T-2 of every env (hrl_policy_planner.py:68)
+            frames(e.T - 1);
+            x.goal = h->hframes.lo_goal;
+            return ZENV_OK;
+        }
+        if (h->hi_m < 1) return fail(ZENV_E_STATE, "the last zenv_collect_hier closed no high-level transition (M = 0)");
+        rows();                 // the closed transitions, with the goals available at each pick
+        x.hi_mask = o.action_mask;
+        return ZENV_OK;
+    default:                    // AGENT_FLAT, AGENT_A2C: every frame of the flat collector
+        if (!h->exp_mem) return fail(ZENV_E_STATE, "zenv_collect first: the handle holds no experience");
+        frames(e.T);
         return ZENV_OK;
     }
-    if (!h->exp_mem || !h->exp_hier || h->hi_kind != 0 || !h->hframes.lo_goal)
-        return fail(ZENV_E_STATE, "zenv_collect_hier first: the ZENV_F_EXP_* / ZENV_F_LO_* / ZENV_F_HI_* buffers do not "
-                                  "hold its records");
-    if (l.level == 0) {         // frames 0 .. T-2 of every env (hrl_policy_planner.py:68)
-        x = PpoExp{ e.obs, e.zone_obs, e.action, e.log_prob, e.value, e.advantage, e.returnn, h->n_env, e.T - 1,
-                    h->hframes.lo_goal, nullptr, nullptr };
-        samples = (int64_t)h->n_env * (e.T - 1);
-        return ZENV_OK;
-    }
-    if (h->hi_m < 1) return fail(ZENV_E_STATE, "the last zenv_collect_hier closed no high-level transition (M = 0)");
-    const HierOut &o = h->hout;  // dense env-major rows
-    x = PpoExp{ o.obs, o.zone_obs, nullptr, o.log_prob, o.value, o.advantage, o.returnn, (int)h->hi_m, 1, nullptr, o.action,
-                o.action_mask };
-    samples = h->hi_m;
-    return ZENV_OK;
 }
 
 // the checks every update call shares; *idx_dev: the indices on the device
@@ -844,277 +814,77 @@ int learner_epoch(zenv *h, const Learner &l, const int32_t *order, int total, in
     Learner l;                                                    \
     if (int rc = find_learner(h, level, agent, l)) return rc
 
-extern "C" int zenv_ppo_tensor(zenv_t *h, int which, int index, void **dev_ptr, int64_t *count)
-{
-    if (!h || !dev_ptr || !count) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, 0, AGENT_FLAT);
-    return learner_tensor(l, which, index, dev_ptr, count);
-}
-extern "C" int zenv_ppo_read(zenv_t *h, int which, int index, float *dst)
-{
-    if (!dst) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, 0, AGENT_FLAT);
-    return learner_copy(h, l, which, index, dst, true);
-}
-extern "C" int zenv_ppo_write(zenv_t *h, int which, int index, const float *src)
-{
-    if (!src) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, 0, AGENT_FLAT);
-    return learner_copy(h, l, which, index, const_cast<float *>(src), false);
-}
-extern "C" int zenv_ppo_get_step(zenv_t *h, int64_t *step)
-{
-    if (!h || !step) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, 0, AGENT_FLAT);
-    *step = l.s->step;
-    return ZENV_OK;
-}
-extern "C" int zenv_ppo_set_step(zenv_t *h, int64_t step)
-{
-    LEARNER(h, 0, AGENT_FLAT);
-    return learner_set_step(l, step);
-}
-extern "C" int zenv_ppo_minibatch(zenv_t *h, const int32_t *idx, int count, int idx_on_device, int apply)
-{
-    if (!h || !idx) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, 0, AGENT_FLAT);
-    return learner_minibatch(h, l, idx, count, idx_on_device, apply);
-}
-extern "C" int zenv_ppo_apply(zenv_t *h)
-{
-    LEARNER(h, 0, AGENT_FLAT);
-    return learner_apply(h, l);
-}
-extern "C" int zenv_ppo_epoch(zenv_t *h, const int32_t *order, int total, int batch_size, int on_device)
-{
-    if (!h || !order) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, 0, AGENT_FLAT);
-    return learner_epoch(h, l, order, total, batch_size, on_device);
-}
+// The entry points of a family come in two shapes: LEARNER_ABI_LEVELS for a pair, whose functions take `int level`
+// behind the handle, and LEARNER_ABI for a family of one learner.  Both are the five accessors and the three PPO update
+// calls below with LV (the parameter) and lv (its value) filled in.  The order of the argument checks is part of the ABI.
+#define LEVEL_PARAM , int level
 
-extern "C" int zenv_hppo_tensor(zenv_t *h, int level, int which, int index, void **dev_ptr, int64_t *count)
-{
-    if (!h || !dev_ptr || !count) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, level, AGENT_HIER);
-    return learner_tensor(l, which, index, dev_ptr, count);
-}
-extern "C" int zenv_hppo_read(zenv_t *h, int level, int which, int index, float *dst)
-{
-    if (!dst) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, level, AGENT_HIER);
-    return learner_copy(h, l, which, index, dst, true);
-}
-extern "C" int zenv_hppo_write(zenv_t *h, int level, int which, int index, const float *src)
-{
-    if (!src) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, level, AGENT_HIER);
-    return learner_copy(h, l, which, index, const_cast<float *>(src), false);
-}
-extern "C" int zenv_hppo_get_step(zenv_t *h, int level, int64_t *step)
-{
-    if (!h || !step) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, level, AGENT_HIER);
-    *step = l.s->step;
-    return ZENV_OK;
-}
-extern "C" int zenv_hppo_set_step(zenv_t *h, int level, int64_t step)
-{
-    LEARNER(h, level, AGENT_HIER);
-    return learner_set_step(l, step);
-}
-extern "C" int zenv_hppo_minibatch(zenv_t *h, int level, const int32_t *idx, int count, int idx_on_device, int apply)
-{
-    if (!h || !idx) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, level, AGENT_HIER);
-    return learner_minibatch(h, l, idx, count, idx_on_device, apply);
-}
-extern "C" int zenv_hppo_apply(zenv_t *h, int level)
-{
-    LEARNER(h, level, AGENT_HIER);
-    return learner_apply(h, l);
-}
-extern "C" int zenv_hppo_epoch(zenv_t *h, int level, const int32_t *order, int total, int batch_size, int on_device)
-{
-    if (!h || !order) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, level, AGENT_HIER);
-    return learner_epoch(h, l, order, total, batch_size, on_device);
-}
+#define LEARNER_ACCESSORS(name, agent, LV, lv)                                                                    \
+    extern "C" int zenv_##name##_tensor(zenv_t *h LV, int which, int index, void **dev_ptr, int64_t *count)      \
+    {                                                                                                             \
+        if (!h || !dev_ptr || !count) return fail(ZENV_E_ARG, "null argument");                                   \
+        LEARNER(h, lv, agent);                                                                                    \
+        return learner_tensor(l, which, index, dev_ptr, count);                                                   \
+    }                                                                                                             \
+    extern "C" int zenv_##name##_read(zenv_t *h LV, int which, int index, float *dst)                            \
+    {                                                                                                             \
+        if (!dst) return fail(ZENV_E_ARG, "null argument");                                                       \
+        LEARNER(h, lv, agent);                                                                                    \
+        return learner_copy(h, l, which, index, dst, true);                                                       \
+    }                                                                                                             \
+    extern "C" int zenv_##name##_write(zenv_t *h LV, int which, int index, const float *src)                     \
+    {                                                                                                             \
+        if (!src) return fail(ZENV_E_ARG, "null argument");                                                       \
+        LEARNER(h, lv, agent);                                                                                    \
+        return learner_copy(h, l, which, index, const_cast<float *>(src), false);                                 \
+    }                                                                                                             \
+    extern "C" int zenv_##name##_get_step(zenv_t *h LV, int64_t *step)                                           \
+    {                                                                                                             \
+        if (!h || !step) return fail(ZENV_E_ARG, "null argument");                                                \
+        LEARNER(h, lv, agent);                                                                                    \
+        *step = l.s->step;                                                                                        \
+        return ZENV_OK;                                                                                           \
+    }                                                                                                             \
+    extern "C" int zenv_##name##_set_step(zenv_t *h LV, int64_t step)                                            \
+    {                                                                                                             \
+        LEARNER(h, lv, agent);                                                                                    \
+        return learner_set_step(l, step);                                                                         \
+    }
 
-extern "C" int zenv_xyppo_tensor(zenv_t *h, int level, int which, int index, void **dev_ptr, int64_t *count)
-{
-    if (!h || !dev_ptr || !count) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, level, AGENT_XY);
-    return learner_tensor(l, which, index, dev_ptr, count);
-}
-extern "C" int zenv_xyppo_read(zenv_t *h, int level, int which, int index, float *dst)
-{
-    if (!dst) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, level, AGENT_XY);
-    return learner_copy(h, l, which, index, dst, true);
-}
-extern "C" int zenv_xyppo_write(zenv_t *h, int level, int which, int index, const float *src)
-{
-    if (!src) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, level, AGENT_XY);
-    return learner_copy(h, l, which, index, const_cast<float *>(src), false);
-}
-extern "C" int zenv_xyppo_get_step(zenv_t *h, int level, int64_t *step)
-{
-    if (!h || !step) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, level, AGENT_XY);
-    *step = l.s->step;
-    return ZENV_OK;
-}
-extern "C" int zenv_xyppo_set_step(zenv_t *h, int level, int64_t step)
-{
-    LEARNER(h, level, AGENT_XY);
-    return learner_set_step(l, step);
-}
-extern "C" int zenv_xyppo_minibatch(zenv_t *h, int level, const int32_t *idx, int count, int idx_on_device, int apply)
-{
-    if (!h || !idx) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, level, AGENT_XY);
-    return learner_minibatch(h, l, idx, count, idx_on_device, apply);
-}
-extern "C" int zenv_xyppo_apply(zenv_t *h, int level)
-{
-    LEARNER(h, level, AGENT_XY);
-    return learner_apply(h, l);
-}
-extern "C" int zenv_xyppo_epoch(zenv_t *h, int level, const int32_t *order, int total, int batch_size, int on_device)
-{
-    if (!h || !order) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, level, AGENT_XY);
-    return learner_epoch(h, l, order, total, batch_size, on_device);
-}
+// READY: what zenv_<name>_minibatch and _epoch do between the lookup and the body (DIAYN: the kept-sample list)
+#define LEARNER_UPDATES(name, agent, LV, lv, READY)                                                               \
+    extern "C" int zenv_##name##_minibatch(zenv_t *h LV, const int32_t *idx, int count, int idx_on_device, int apply) \
+    {                                                                                                             \
+        if (!h || !idx) return fail(ZENV_E_ARG, "null argument");                                                 \
+        LEARNER(h, lv, agent);                                                                                    \
+        READY;                                                                                                    \
+        return learner_minibatch(h, l, idx, count, idx_on_device, apply);                                         \
+    }                                                                                                             \
+    extern "C" int zenv_##name##_apply(zenv_t *h LV)                                                             \
+    {                                                                                                             \
+        LEARNER(h, lv, agent);                                                                                    \
+        return learner_apply(h, l);                                                                               \
+    }                                                                                                             \
+    extern "C" int zenv_##name##_epoch(zenv_t *h LV, const int32_t *order, int total, int batch_size, int on_device) \
+    {                                                                                                             \
+        if (!h || !order) return fail(ZENV_E_ARG, "null argument");                                               \
+        LEARNER(h, lv, agent);                                                                                    \
+        READY;                                                                                                    \
+        return learner_epoch(h, l, order, total, batch_size, on_device);                                          \
+    }
 
-extern "C" int zenv_skppo_tensor(zenv_t *h, int level, int which, int index, void **dev_ptr, int64_t *count)
-{
-    if (!h || !dev_ptr || !count) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, level, AGENT_SKILL);
-    return learner_tensor(l, which, index, dev_ptr, count);
-}
-extern "C" int zenv_skppo_read(zenv_t *h, int level, int which, int index, float *dst)
-{
-    if (!dst) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, level, AGENT_SKILL);
-    return learner_copy(h, l, which, index, dst, true);
-}
-extern "C" int zenv_skppo_write(zenv_t *h, int level, int which, int index, const float *src)
-{
-    if (!src) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, level, AGENT_SKILL);
-    return learner_copy(h, l, which, index, const_cast<float *>(src), false);
-}
-extern "C" int zenv_skppo_get_step(zenv_t *h, int level, int64_t *step)
-{
-    if (!h || !step) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, level, AGENT_SKILL);
-    *step = l.s->step;
-    return ZENV_OK;
-}
-extern "C" int zenv_skppo_set_step(zenv_t *h, int level, int64_t step)
-{
-    LEARNER(h, level, AGENT_SKILL);
-    return learner_set_step(l, step);
-}
-extern "C" int zenv_skppo_minibatch(zenv_t *h, int level, const int32_t *idx, int count, int idx_on_device, int apply)
-{
-    if (!h || !idx) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, level, AGENT_SKILL);
-    return learner_minibatch(h, l, idx, count, idx_on_device, apply);
-}
-extern "C" int zenv_skppo_apply(zenv_t *h, int level)
-{
-    LEARNER(h, level, AGENT_SKILL);
-    return learner_apply(h, l);
-}
-extern "C" int zenv_skppo_epoch(zenv_t *h, int level, const int32_t *order, int total, int batch_size, int on_device)
-{
-    if (!h || !order) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, level, AGENT_SKILL);
-    return learner_epoch(h, l, order, total, batch_size, on_device);
-}
+#define LEARNER_ABI(name, agent, READY) LEARNER_ACCESSORS(name, agent, , 0) LEARNER_UPDATES(name, agent, , 0, READY)
+#define LEARNER_ABI_LEVELS(name, agent) \
+    LEARNER_ACCESSORS(name, agent, LEVEL_PARAM, level) LEARNER_UPDATES(name, agent, LEVEL_PARAM, level, )
 
-extern "C" int zenv_opppo_tensor(zenv_t *h, int level, int which, int index, void **dev_ptr, int64_t *count)
-{
-    if (!h || !dev_ptr || !count) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, level, AGENT_OPTION);
-    return learner_tensor(l, which, index, dev_ptr, count);
-}
-extern "C" int zenv_opppo_read(zenv_t *h, int level, int which, int index, float *dst)
-{
-    if (!dst) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, level, AGENT_OPTION);
-    return learner_copy(h, l, which, index, dst, true);
-}
-extern "C" int zenv_opppo_write(zenv_t *h, int level, int which, int index, const float *src)
-{
-    if (!src) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, level, AGENT_OPTION);
-    return learner_copy(h, l, which, index, const_cast<float *>(src), false);
-}
-extern "C" int zenv_opppo_get_step(zenv_t *h, int level, int64_t *step)
-{
-    if (!h || !step) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, level, AGENT_OPTION);
-    *step = l.s->step;
-    return ZENV_OK;
-}
-extern "C" int zenv_opppo_set_step(zenv_t *h, int level, int64_t step)
-{
-    LEARNER(h, level, AGENT_OPTION);
-    return learner_set_step(l, step);
-}
-extern "C" int zenv_opppo_minibatch(zenv_t *h, int level, const int32_t *idx, int count, int idx_on_device, int apply)
-{
-    if (!h || !idx) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, level, AGENT_OPTION);
-    return learner_minibatch(h, l, idx, count, idx_on_device, apply);
-}
-extern "C" int zenv_opppo_apply(zenv_t *h, int level)
-{
-    LEARNER(h, level, AGENT_OPTION);
-    return learner_apply(h, l);
-}
-extern "C" int zenv_opppo_epoch(zenv_t *h, int level, const int32_t *order, int total, int batch_size, int on_device)
-{
-    if (!h || !order) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, level, AGENT_OPTION);
-    return learner_epoch(h, l, order, total, batch_size, on_device);
-}
+LEARNER_ABI(ppo, AGENT_FLAT, )
+LEARNER_ABI_LEVELS(hppo, AGENT_HIER)
+LEARNER_ABI_LEVELS(xyppo, AGENT_XY)
+LEARNER_ABI_LEVELS(skppo, AGENT_SKILL)
+LEARNER_ABI_LEVELS(opppo, AGENT_OPTION)
+// DIAYN: the inverse model's learner (one: no level) and, below, the kept samples and the learned skill prior
+LEARNER_ABI(diayn, AGENT_DIAYN, if (int rc = diayn_any_kept(h)) return rc)
 
-// ---- DIAYN: the inverse model's learner (one: no level) and the learned skill prior
-extern "C" int zenv_diayn_tensor(zenv_t *h, int which, int index, void **dev_ptr, int64_t *count)
-{
-    if (!h || !dev_ptr || !count) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, 0, AGENT_DIAYN);
-    return learner_tensor(l, which, index, dev_ptr, count);
-}
-extern "C" int zenv_diayn_read(zenv_t *h, int which, int index, float *dst)
-{
-    if (!dst) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, 0, AGENT_DIAYN);
-    return learner_copy(h, l, which, index, dst, true);
-}
-extern "C" int zenv_diayn_write(zenv_t *h, int which, int index, const float *src)
-{
-    if (!src) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, 0, AGENT_DIAYN);
-    return learner_copy(h, l, which, index, const_cast<float *>(src), false);
-}
-extern "C" int zenv_diayn_get_step(zenv_t *h, int64_t *step)
-{
-    if (!h || !step) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, 0, AGENT_DIAYN);
-    *step = l.s->step;
-    return ZENV_OK;
-}
-extern "C" int zenv_diayn_set_step(zenv_t *h, int64_t step)
-{
-    LEARNER(h, 0, AGENT_DIAYN);
-    return learner_set_step(l, step);
-}
 extern "C" int zenv_diayn_samples(zenv_t *h, int64_t *count)
 {
     if (!h || !count) return fail(ZENV_E_ARG, "null argument");
@@ -1122,30 +892,11 @@ extern "C" int zenv_diayn_samples(zenv_t *h, int64_t *count)
     *count = h->diayn_kept;
     return mlp_range_check(h);
 }
-extern "C" int zenv_diayn_minibatch(zenv_t *h, const int32_t *idx, int count, int idx_on_device, int apply)
-{
-    if (!h || !idx) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, 0, AGENT_DIAYN);
-    if (int rc = diayn_any_kept(h)) return rc;
-    return learner_minibatch(h, l, idx, count, idx_on_device, apply);
-}
-extern "C" int zenv_diayn_apply(zenv_t *h)
-{
-    LEARNER(h, 0, AGENT_DIAYN);
-    return learner_apply(h, l);
-}
-extern "C" int zenv_diayn_epoch(zenv_t *h, const int32_t *order, int total, int batch_size, int on_device)
-{
-    if (!h || !order) return fail(ZENV_E_ARG, "null argument");
-    LEARNER(h, 0, AGENT_DIAYN);
-    if (int rc = diayn_any_kept(h)) return rc;
-    return learner_epoch(h, l, order, total, batch_size, on_device);
-}
 
 extern "C" int zenv_diayn_prior_init(zenv_t *h, const float *logits, int n_skills, double lr, double adam_eps)
 {
     if (!h || !logits) return fail(ZENV_E_ARG, "null argument");
-    if (n_skills < 1 || n_skills > kMaxSkills) return fail(ZENV_E_ARG, "n_skills %d outside [1, %d]", n_skills, kMaxSkills);
+    if (int rc = check_skills(n_skills)) return rc;
     for (double v : { lr, adam_eps })
         if (bad_hyper(v)) return fail(ZENV_E_ARG, "a hyper-parameter is negative or not finite (%g)", v);
     for (int s = 0; s < n_skills; ++s)
@@ -1172,7 +923,7 @@ extern "C" int zenv_diayn_prior_update(zenv_t *h)
     if (!h) return fail(ZENV_E_ARG, "null handle");
     auto &p = h->prior;
     if (!p.ready) return fail(ZENV_E_STATE, "zenv_diayn_prior_init first");
-    if (!h->exp_mem || !h->exp_skill || h->hi_kind != 1 || !h->sk_mem || h->hi_m < 1)
+    if (!skill_records(h))
         return fail(ZENV_E_STATE, "zenv_collect_skill first: the ZENV_F_HI_* rows do not hold its picks (M = 0)");
     if (!h->skill_ready || h->skill.S != p.S)
         return fail(ZENV_E_STATE, "the records are of an agent with another number of skills than the prior's %d", p.S);
@@ -1237,20 +988,6 @@ zenv_ppo_config a2c_as_ppo(const zenv_a2c_config *ac)
     return pc;
 }
 
-int find_a2c(zenv *h, Learner &out)
-{
-    if (!h) return fail(ZENV_E_ARG, "null handle");
-    if (!h->a2c) return fail(ZENV_E_STATE, "zenv_a2c_init first");
-    out = Learner{ h->a2c, -1, AGENT_FLAT };
-    return ZENV_OK;
-}
-
-int a2c_arena(int which)
-{
-    if (which < ZENV_A2C_PARAM || which > ZENV_A2C_SQUARE_AVG) return fail(ZENV_E_ARG, "unknown arena %d", which);
-    return ZENV_OK;
-}
-
 // one chunk behind what is enqueued; idx_dev: count indexes on the device
 int a2c_chunk(zenv *h, PpoState *s, const PpoExp &x, const int32_t *idx_dev, int count, int64_t total, int first)
 {
@@ -1291,59 +1028,22 @@ extern "C" int zenv_a2c_init(zenv_t *h, const zenv_mlp_weights *w, const zenv_a2
     const zenv_ppo_config pc = a2c_as_ppo(ac);
     const float *t[PPO_MAX_TENSORS];
     tensor_list(w, t);
-    const int rc = learner_create(h, h->a2c, w->h_dim, t, kA2c, &pc);
+    PpoState *&s = h->learner[L_A2C];
+    const int rc = learner_create(h, AGENT_A2C, 0, w->h_dim, t, kA2c, &pc);
     if (rc) {
-        learner_free(h->a2c);           // no half-built learner
+        learner_free(s);                // no half-built learner
         return rc;
     }
-    h->a2c->rms_alpha = ac->rmsprop_alpha, h->a2c->rms_eps = ac->rmsprop_eps;
+    s->rms_alpha = ac->rmsprop_alpha, s->rms_eps = ac->rmsprop_eps;
     return ZENV_OK;
 }
 
-extern "C" int zenv_a2c_tensor(zenv_t *h, int which, int index, void **dev_ptr, int64_t *count)
-{
-    if (!h || !dev_ptr || !count) return fail(ZENV_E_ARG, "null argument");
-    Learner l;
-    if (int rc = find_a2c(h, l)) return rc;
-    if (int rc = a2c_arena(which)) return rc;
-    return learner_tensor(l, which, index, dev_ptr, count);
-}
-extern "C" int zenv_a2c_read(zenv_t *h, int which, int index, float *dst)
-{
-    if (!dst) return fail(ZENV_E_ARG, "null argument");
-    Learner l;
-    if (int rc = find_a2c(h, l)) return rc;
-    if (int rc = a2c_arena(which)) return rc;
-    return learner_copy(h, l, which, index, dst, true);
-}
-extern "C" int zenv_a2c_write(zenv_t *h, int which, int index, const float *src)
-{
-    if (!src) return fail(ZENV_E_ARG, "null argument");
-    Learner l;
-    if (int rc = find_a2c(h, l)) return rc;
-    if (int rc = a2c_arena(which)) return rc;
-    return learner_copy(h, l, which, index, const_cast<float *>(src), false);
-}
-extern "C" int zenv_a2c_get_step(zenv_t *h, int64_t *step)
-{
-    if (!h || !step) return fail(ZENV_E_ARG, "null argument");
-    Learner l;
-    if (int rc = find_a2c(h, l)) return rc;
-    *step = l.s->step;
-    return ZENV_OK;
-}
-extern "C" int zenv_a2c_set_step(zenv_t *h, int64_t step)
-{
-    Learner l;
-    if (int rc = find_a2c(h, l)) return rc;
-    return learner_set_step(l, step);
-}
+LEARNER_ACCESSORS(a2c, AGENT_A2C, , 0)
 
 extern "C" int zenv_a2c_accumulate(zenv_t *h, const int32_t *idx, int count, int idx_on_device, int64_t total, int first)
 {
     if (!h || !idx) return fail(ZENV_E_ARG, "null argument");
-    Learner l;
-    if (int rc = find_a2c(h, l)) return rc;
+    LEARNER(h, 0, AGENT_A2C);
     PpoState *s = l.s;
     if (count < 1 || count > s->net.max_batch)
         return fail(ZENV_E_ARG, "count %d outside [1, max_batch = %d]", count, s->net.max_batch);
@@ -1362,16 +1062,14 @@ extern "C" int zenv_a2c_accumulate(zenv_t *h, const int32_t *idx, int count, int
 
 extern "C" int zenv_a2c_apply(zenv_t *h)
 {
-    Learner l;
-    if (int rc = find_a2c(h, l)) return rc;
+    LEARNER(h, 0, AGENT_A2C);
     if (int rc = use_device(h)) return rc;
     return a2c_step(h, l.s);
 }
 
 extern "C" int zenv_a2c_update(zenv_t *h)
 {
-    Learner l;
-    if (int rc = find_a2c(h, l)) return rc;
+    LEARNER(h, 0, AGENT_A2C);
     PpoState *s = l.s;
     PpoExp x{};
     int64_t samples = 0;

@@ -26,6 +26,195 @@ class _DeviceView:
                                          "data": (int(ptr), False), "version": 2, "strides": None}
 
 
+# The thin learner methods TorchZoneEnv has of each family (key -> calls), the rest of a family's being written out in
+# the class.  ppo / a2c name their tensor views `views`.
+_PAIR_CALLS = ("init", "tensors", "set_tensors", "state_dicts", "load_state_dicts", "optimizer_state",
+               "load_optimizer_state", "minibatch", "apply", "epoch", "stats", "publish", "update")
+_ACCESS_CALLS = ("tensor_ptr", "get_step", "set_step")
+_TORCH_CALLS = {
+    "ppo": ("views", "state_dict", "load_state_dict", "optimizer_state", "load_optimizer_state", "minibatch", "apply",
+            "epoch", "stats"),
+    "a2c": ("views", "state_dict", "load_state_dict", "optimizer_state", "load_optimizer_state", "apply", "stats"),
+    "hppo": _PAIR_CALLS, "xyppo": _PAIR_CALLS, "skppo": _PAIR_CALLS, "opppo": _PAIR_CALLS + _ACCESS_CALLS,
+    "diayn": ("tensors", "set_tensors", "state_dict", "load_state_dict", "optimizer_state", "load_optimizer_state",
+              "minibatch", "apply", "epoch", "stats") + _ACCESS_CALLS,
+}
+
+
+_WEIGHTS = {"hppo": "zenv_hier_weights", "xyppo": "zenv_xy_weights", "skppo": "zenv_skill_weights",
+            "opppo": "zenv_option_weights", "diayn": "zenv_skill_inverse_weights"}
+
+
+def _torch_docs(key, weights):
+    """call -> docstring of the installed methods that have one."""
+    if key in ("ppo", "a2c"):
+        optimiser = "Adam" if key == "ppo" else "RMSprop"
+        return {
+            "views": "zenv_mlp_weights name -> CUDA tensor ALIASING that tensor of an arena, in its state_dict shape.",
+            "state_dict": "The learner's parameters under ACModel's state_dict names, as CUDA tensors ALIASING the "
+                          f"parameter arena:\n        ``model.load_state_dict(tenv.{key}_state_dict())`` copies them "
+                          "into a torch module on the shared stream.",
+            "load_state_dict": "Overwrite the learner's parameters from an ACModel state_dict (tensors on any device), "
+                               "on the stream.",
+            "optimizer_state": f"{optimiser}'s state in the shape of ``torch.optim.{optimiser}.state_dict()``: copies, "
+                               "parameter i\n        the i-th of ``ACModel.parameters()``.",
+            "minibatch": f"``ZoneVecEnv.{key}_minibatch``; idx may be an int32 CUDA tensor (never copied, checked on the "
+                         "device).",
+            "epoch": f"``ZoneVecEnv.{key}_epoch``; order may be an int32 CUDA tensor.",
+            "stats": "float32 CUDA tensor [minibatches, 6] ALIASING the statistics of the last ppo_minibatch / ppo_epoch "
+                     "(not\n        synchronised)." if key == "ppo" else
+                     "float32 CUDA tensor [1, 5] ALIASING the statistics of the last a2c_apply / a2c_update (not "
+                     "synchronised).",
+        }
+    level = "" if key == "diayn" else "the level's "
+    docs = {
+        "tensors": f"{weights} name -> CUDA tensor ALIASING that tensor of " +
+                   ("the arena" if key == "diayn" else "a level's arena") + ", in its state_dict shape.",
+        "optimizer_state": f"``ZoneVecEnv.{key}_optimizer_state`` with the moments as CUDA copies.",
+        "minibatch": f"``ZoneVecEnv.{key}_minibatch``; idx may be an int32 CUDA tensor (never copied, checked on the "
+                     "device).",
+        "epoch": f"``ZoneVecEnv.{key}_epoch``; order may be an int32 CUDA tensor.",
+        "stats": f"float32 CUDA tensor [minibatches, 6] ALIASING the statistics of {level}last {key}_minibatch / "
+                 f"{key}_epoch\n        (not synchronised).",
+    }
+    if key == "diayn":
+        docs["state_dict"] = "InverseModel's state_dict as CUDA tensors ALIASING the parameter arena."
+        return docs
+    docs.update({
+        "init": f"``ZoneVecEnv.{key}_init`` with each level's four arenas as flat float32 CUDA tensors ALIASING device "
+                f"memory in\n        ``self.{key}_arenas[level]`` (valid until the next {key}_init or ``env.close()``).",
+        "set_tensors": "Overwrite the tensors of a level's arena that `tensors` names (tensors on any device), on the "
+                       "stream.",
+        "state_dicts": "(hi_model_state, lo_model_state) as CUDA tensors ALIASING the two parameter arenas.",
+    })
+    return docs
+
+
+def _torch_forwarders(fam):
+    """call -> the method <key>_<call> of TorchZoneEnv: the family's piece of the shared implementation, or the env's
+    own method where tensors change nothing.  A pair's take the level first."""
+    key = fam.key
+
+    def of_env(call):
+        return lambda self, *args, **kw: getattr(self.env, f"{key}_{call}")(*args, **kw)
+
+    if fam.levels:
+        def init(self, hi_state_dict, lo_state_dict, lo=None, hi=None):
+            getattr(self.env, key + "_init")(hi_state_dict, lo_state_dict, lo=lo, hi=hi)
+            setattr(self, key + "_arenas", {level: self._learner_arenas(key, level) for level in (0, 1)})
+
+        def tensors(self, level, which=nat.PPO_PARAM):
+            return self._learner_views(key, level, which)
+
+        def set_tensors(self, level, tensors, which=nat.PPO_PARAM):
+            self._learner_set_tensors(key, level, tensors, which)
+
+        def state_dicts(self):
+            return self._learner_state_dict(key, 1), self._learner_state_dict(key, 0)
+
+        def load_state_dicts(self, hi_state_dict, lo_state_dict):
+            self._learner_load_state_dict(key, 1, hi_state_dict)
+            self._learner_load_state_dict(key, 0, lo_state_dict)
+
+        def optimizer_state(self, level):
+            return self._learner_optimizer_state(key, level)
+
+        def load_optimizer_state(self, level, state):
+            of_env("load_optimizer_state")(self, level, state)
+
+        def minibatch(self, level, idx, apply=False):
+            ptr, count = self._ppo_index_arg(idx)
+            of_env("minibatch")(self, level, ptr, apply=apply, count=count)
+
+        def apply(self, level):
+            of_env("apply")(self, level)
+
+        def epoch(self, level, order, batch_size):
+            ptr, count = self._ppo_index_arg(order)
+            of_env("epoch")(self, level, ptr, batch_size, count=count)
+
+        def stats(self, level):
+            return self._learner_stats(key, level)
+
+        def publish(self):
+            of_env("publish")(self)
+
+        def update(self, epochs, batch_size, hi_epochs, hi_batch_size, rng):
+            return of_env("update")(self, epochs, batch_size, hi_epochs, hi_batch_size, rng)
+
+        def tensor_ptr(self, level, which, index):
+            return of_env("tensor_ptr")(self, level, which, index)
+
+        def get_step(self, level):
+            return of_env("get_step")(self, level)
+
+        def set_step(self, level, step):
+            of_env("set_step")(self, level, step)
+
+        return locals()
+
+    def tensors(self, which=nat.PPO_PARAM):
+        return self._learner_views(key, None, which)
+
+    def views(self, which=nat.PPO_PARAM):
+        return self._learner_views(key, None, which)
+
+    def set_tensors(self, tensors, which=nat.PPO_PARAM):
+        self._learner_set_tensors(key, None, tensors, which)
+
+    def state_dict(self):
+        return self._learner_state_dict(key)
+
+    def load_state_dict(self, state_dict):
+        self._learner_load_state_dict(key, None, state_dict)
+
+    def optimizer_state(self):
+        return self._learner_optimizer_state(key)
+
+    def load_optimizer_state(self, state):
+        of_env("load_optimizer_state")(self, state)
+
+    def minibatch(self, idx, apply=False):
+        ptr, count = self._ppo_index_arg(idx)
+        of_env("minibatch")(self, ptr, apply=apply, count=count)
+
+    def apply(self):
+        of_env("apply")(self)
+
+    def epoch(self, order, batch_size):
+        ptr, count = self._ppo_index_arg(order)
+        of_env("epoch")(self, ptr, batch_size, count=count)
+
+    def stats(self):
+        return self._learner_stats(key)
+
+    def tensor_ptr(self, which, index):
+        return of_env("tensor_ptr")(self, which, index)
+
+    def get_step(self):
+        return of_env("get_step")(self)
+
+    def set_step(self, step):
+        of_env("set_step")(self, step)
+
+    return locals()
+
+
+def _install_forwarders(cls):
+    from .vec_env import _FAMILIES
+    for key, calls in _TORCH_CALLS.items():
+        fam = _FAMILIES[key]
+        made, docs = _torch_forwarders(fam), _torch_docs(key, _WEIGHTS.get(key))
+        for call in calls:
+            f = made[call]
+            f.__name__ = f"{key}_{call}"
+            f.__qualname__ = f"{cls.__name__}.{f.__name__}"
+            f.__doc__ = docs.get(call)
+            setattr(cls, f.__name__, f)
+    return cls
+
+
+@_install_forwarders
 class TorchZoneEnv:
     """Tensor view of a ``ZoneVecEnv``: ``obs (N,8)``, ``zone_obs (N,Z,F)``, ``reward (N,)`` float32,
     ``done``/``goal_met (N,)`` uint8, ``last_return (N,)`` float64, ``episodes (N,)`` int32 -- aliases of the
@@ -152,51 +341,59 @@ class TorchZoneEnv:
         """``ZoneVecEnv.episode_log_reset``: the logs of a fresh algo object."""
         self.env.episode_log_reset()
 
-    # ------------------------------------------------------------------ the flat actor-critic's PPO update
+    # ------------------------------------------------------------------ the device learners
+    # One implementation per piece, parameterised by the family (vec_env._FAMILIES) and, for a pair, the level; the
+    # thin <key>_* methods are installed from _TORCH_CALLS (_install_forwarders).  Here follow the pieces, then what a
+    # family has of its own.
+    _ARENAS = (("param", nat.PPO_PARAM), ("grad", nat.PPO_GRAD), ("exp_avg", nat.PPO_EXP_AVG),
+               ("exp_avg_sq", nat.PPO_EXP_AVG_SQ))
+    _A2C_ARENAS = (("param", nat.A2C_PARAM), ("grad", nat.A2C_GRAD), ("square_avg", nat.A2C_SQUARE_AVG))
 
-    def ppo_init(self, state_dict, **hyper):
-        """``ZoneVecEnv.ppo_init`` with the four arenas -- parameters, gradients, exp_avg, exp_avg_sq -- as flat float32
-        CUDA tensors ALIASING device memory in ``self.ppo_arenas`` (padding between the tensors included; valid until
-        the next ppo_init or ``env.close()``)."""
-        self.env.ppo_init(state_dict, **hyper)
+    def _learner_arenas(self, family, level=None):
+        """name -> flat float32 CUDA tensor ALIASING a whole arena of the learner (padding between the tensors included)."""
+        learner = self.env._learner_of(family, level)
         with self._torch.cuda.device(self.device):
-            self.ppo_arenas = {}
-            for name, which in (("param", nat.PPO_PARAM), ("grad", nat.PPO_GRAD), ("exp_avg", nat.PPO_EXP_AVG),
-                                ("exp_avg_sq", nat.PPO_EXP_AVG_SQ)):
-                ptr, count = self.env.ppo_tensor_ptr(which, -1)
-                self.ppo_arenas[name] = self._alias_ptr(ptr, (count,))
+            out = {}
+            for name, which in (self._A2C_ARENAS if learner.family.rmsprop else self._ARENAS):
+                ptr, count = learner.tensor_ptr(which, -1)
+                out[name] = self._alias_ptr(ptr, (count,))
+            return out
 
-    def ppo_views(self, which=nat.PPO_PARAM):
-        """zenv_mlp_weights name -> CUDA tensor ALIASING that tensor of an arena, in its state_dict shape."""
-        from .vec_env import mlp_tensor_shapes
-        shapes = mlp_tensor_shapes(self.env._ppo_h, self.env.net_zone_feat)
+    def _learner_views(self, family, level=None, which=nat.PPO_PARAM):
+        """tensor name -> CUDA tensor ALIASING that tensor of an arena, in its state_dict shape."""
+        learner = self.env._learner_of(family, level)
+        learner._need_init()
         with self._torch.cuda.device(self.device):
-            return {name: self._alias_ptr(self.env.ppo_tensor_ptr(which, i)[0], shapes[name])
-                    for i, name in enumerate(self.env._ppo_keys)}
+            return {name: self._alias_ptr(learner.tensor_ptr(which, i)[0], learner.shapes[name])
+                    for i, name in enumerate(learner.keys)}
 
-    def ppo_state_dict(self):
-        """The learner's parameters under ACModel's state_dict names, as CUDA tensors ALIASING the parameter arena:
-        ``model.load_state_dict(tenv.ppo_state_dict())`` copies them into a torch module on the shared stream."""
-        views = self.ppo_views()
-        return {key: views[name] for name, key in self.env._ppo_keys.items()}
+    def _learner_set_tensors(self, family, level, tensors, which):
+        views = self._learner_views(family, level, which)
+        for name, src in tensors.items():
+            views[name].copy_(self._torch.as_tensor(src))
 
-    def ppo_load_state_dict(self, state_dict):
-        """Overwrite the learner's parameters from an ACModel state_dict (tensors on any device), on the stream."""
-        for key, dst in self.ppo_state_dict().items():
+    def _learner_state_dict(self, family, level=None):
+        views = self._learner_views(family, level)
+        return {key: views[name] for name, key in self.env._learner_of(family, level).keys.items()}
+
+    def _learner_load_state_dict(self, family, level, state_dict):
+        for key, dst in self._learner_state_dict(family, level).items():
             dst.copy_(state_dict[key])
 
-    def ppo_optimizer_state(self):
-        """Adam's state in the shape of ``torch.optim.Adam.state_dict()`` (train_ppo.py:116-122): copies, parameter i
-        the i-th of ``ACModel.parameters()``."""
+    def _learner_optimizer_state(self, family, level=None):
+        """The learner's ``optimizer_state`` with the step as a tensor and the moments as CUDA copies."""
         torch = self._torch
-        out = self.env.ppo_optimizer_state()
-        out["state"] = {i: {"step": torch.tensor(s["step"]), "exp_avg": torch.from_numpy(s["exp_avg"]).to(self.device),
-                            "exp_avg_sq": torch.from_numpy(s["exp_avg_sq"]).to(self.device)}
-                        for i, s in out["state"].items()}
+        out = self.env._learner_of(family, level).optimizer_state()
+        out["state"] = {i: {k: torch.tensor(v) if k == "step" else torch.from_numpy(v).to(self.device)
+                            for k, v in s.items()} for i, s in out["state"].items()}
         return out
 
-    def ppo_load_optimizer_state(self, state):
-        self.env.ppo_load_optimizer_state(state)
+    def _learner_stats(self, family, level=None):
+        learner = self.env._learner_of(family, level)
+        field, cols = learner.stats_field, learner.family.stats_cols
+        rows = self.env.field_bytes(field) // (4 * cols)
+        with self._torch.cuda.device(self.device):
+            return self._alias(field, (rows, cols), np.float32)
 
     def _ppo_index_arg(self, idx):
         torch = self._torch
@@ -206,25 +403,13 @@ class TorchZoneEnv:
             return idx.data_ptr(), idx.numel()
         return idx, None
 
-    def ppo_minibatch(self, idx, apply=False):
-        """``ZoneVecEnv.ppo_minibatch``; idx may be an int32 CUDA tensor (never copied, checked on the device)."""
-        ptr, count = self._ppo_index_arg(idx)
-        self.env.ppo_minibatch(ptr, apply=apply, count=count)
-
-    def ppo_apply(self):
-        self.env.ppo_apply()
-
-    def ppo_epoch(self, order, batch_size):
-        """``ZoneVecEnv.ppo_epoch``; order may be an int32 CUDA tensor."""
-        ptr, count = self._ppo_index_arg(order)
-        self.env.ppo_epoch(ptr, batch_size, count=count)
-
-    def ppo_stats(self):
-        """float32 CUDA tensor [minibatches, 6] ALIASING the statistics of the last ppo_minibatch / ppo_epoch (not
-        synchronised)."""
-        rows = self.env.field_bytes(nat.F_PPO_STATS) // 24
-        with self._torch.cuda.device(self.device):
-            return self._alias(nat.F_PPO_STATS, (rows, 6), np.float32)
+    # ------------------------------------------------------------------ the flat actor-critic's PPO and A2C updates
+    def ppo_init(self, state_dict, **hyper):
+        """``ZoneVecEnv.ppo_init`` with the four arenas -- parameters, gradients, exp_avg, exp_avg_sq -- as flat float32
+        CUDA tensors ALIASING device memory in ``self.ppo_arenas`` (padding between the tensors included; valid until
+        the next ppo_init or ``env.close()``)."""
+        self.env.ppo_init(state_dict, **hyper)
+        self.ppo_arenas = self._learner_arenas("ppo")
 
     def ppo_publish(self, precision="auto"):
         self.env.ppo_publish(precision=precision)
@@ -232,305 +417,23 @@ class TorchZoneEnv:
     def ppo_update(self, epochs, batch_size, rng):
         return self.env.ppo_update(epochs, batch_size, rng)
 
-    # ------------------------------------------------------------------ the flat actor-critic's A2C update
-
     def a2c_init(self, state_dict, **hyper):
         """``ZoneVecEnv.a2c_init`` with the three arenas -- parameters, gradients, square_avg -- as flat float32 CUDA
         tensors ALIASING device memory in ``self.a2c_arenas`` (padding between the tensors included; valid until the
         next a2c_init or ``env.close()``)."""
         self.env.a2c_init(state_dict, **hyper)
-        with self._torch.cuda.device(self.device):
-            self.a2c_arenas = {}
-            for name, which in (("param", nat.A2C_PARAM), ("grad", nat.A2C_GRAD), ("square_avg", nat.A2C_SQUARE_AVG)):
-                ptr, count = self.env.a2c_tensor_ptr(which, -1)
-                self.a2c_arenas[name] = self._alias_ptr(ptr, (count,))
-
-    def a2c_views(self, which=nat.A2C_PARAM):
-        """zenv_mlp_weights name -> CUDA tensor ALIASING that tensor of an arena, in its state_dict shape."""
-        from .vec_env import mlp_tensor_shapes
-        shapes = mlp_tensor_shapes(self.env._a2c_h, self.env.net_zone_feat)
-        with self._torch.cuda.device(self.device):
-            return {name: self._alias_ptr(self.env.a2c_tensor_ptr(which, i)[0], shapes[name])
-                    for i, name in enumerate(self.env._a2c_keys)}
-
-    def a2c_state_dict(self):
-        """The learner's parameters under ACModel's state_dict names, as CUDA tensors ALIASING the parameter arena."""
-        views = self.a2c_views()
-        return {key: views[name] for name, key in self.env._a2c_keys.items()}
-
-    def a2c_load_state_dict(self, state_dict):
-        """Overwrite the learner's parameters from an ACModel state_dict (tensors on any device), on the stream."""
-        for key, dst in self.a2c_state_dict().items():
-            dst.copy_(state_dict[key])
-
-    def a2c_optimizer_state(self):
-        """RMSprop's state in the shape of ``torch.optim.RMSprop.state_dict()``: copies, parameter i the i-th of
-        ``ACModel.parameters()``."""
-        torch = self._torch
-        out = self.env.a2c_optimizer_state()
-        out["state"] = {i: {"step": torch.tensor(s["step"]), "square_avg": torch.from_numpy(s["square_avg"]).to(self.device)}
-                        for i, s in out["state"].items()}
-        return out
-
-    def a2c_load_optimizer_state(self, state):
-        self.env.a2c_load_optimizer_state(state)
+        self.a2c_arenas = self._learner_arenas("a2c")
 
     def a2c_accumulate(self, idx, total, first):
         """``ZoneVecEnv.a2c_accumulate``; idx may be an int32 CUDA tensor (never copied, checked on the device)."""
         ptr, count = self._ppo_index_arg(idx)
         self.env.a2c_accumulate(ptr, total, first, count=count)
 
-    def a2c_apply(self):
-        self.env.a2c_apply()
-
-    def a2c_stats(self):
-        """float32 CUDA tensor [1, 5] ALIASING the statistics of the last a2c_apply / a2c_update (not synchronised)."""
-        rows = self.env.field_bytes(nat.F_A2C_STATS) // 20
-        with self._torch.cuda.device(self.device):
-            return self._alias(nat.F_A2C_STATS, (rows, 5), np.float32)
-
     def a2c_publish(self, precision="auto"):
         self.env.a2c_publish(precision=precision)
 
     def a2c_update(self):
         return self.env.a2c_update()
-
-    # ------------------------------------------------------------------ the Zone-goals agent's two PPO updates
-    def hppo_init(self, hi_state_dict, lo_state_dict, lo=None, hi=None):
-        """``ZoneVecEnv.hppo_init`` with each level's four arenas as flat float32 CUDA tensors ALIASING device memory in
-        ``self.hppo_arenas[level]`` (valid until the next hppo_init or ``env.close()``)."""
-        self.env.hppo_init(hi_state_dict, lo_state_dict, lo=lo, hi=hi)
-        with self._torch.cuda.device(self.device):
-            self.hppo_arenas = {}
-            for level in (nat.HPPO_LO, nat.HPPO_HI):
-                self.hppo_arenas[level] = {}
-                for name, which in (("param", nat.PPO_PARAM), ("grad", nat.PPO_GRAD), ("exp_avg", nat.PPO_EXP_AVG),
-                                    ("exp_avg_sq", nat.PPO_EXP_AVG_SQ)):
-                    ptr, count = self.env.hppo_tensor_ptr(level, which, -1)
-                    self.hppo_arenas[level][name] = self._alias_ptr(ptr, (count,))
-
-    def hppo_tensors(self, level, which=nat.PPO_PARAM):
-        """zenv_hier_weights name -> CUDA tensor ALIASING that tensor of a level's arena, in its state_dict shape."""
-        learner = self.env._learner(level)
-        with self._torch.cuda.device(self.device):
-            return {name: self._alias_ptr(learner.tensor_ptr(which, i)[0], learner.shapes[name])
-                    for i, name in enumerate(learner.keys)}
-
-    def hppo_set_tensors(self, level, tensors, which=nat.PPO_PARAM):
-        """Overwrite the tensors of a level's arena that `tensors` names (tensors on any device), on the stream."""
-        views = self.hppo_tensors(level, which)
-        for name, src in tensors.items():
-            views[name].copy_(self._torch.as_tensor(src))
-
-    def hppo_state_dicts(self):
-        """(hi_model_state, lo_model_state) as CUDA tensors ALIASING the two parameter arenas."""
-        out = []
-        for level in (nat.HPPO_HI, nat.HPPO_LO):
-            views = self.hppo_tensors(level)
-            out.append({key: views[name] for name, key in self.env._learner(level).keys.items()})
-        return tuple(out)
-
-    def hppo_load_state_dicts(self, hi_state_dict, lo_state_dict):
-        for dst_sd, src_sd in zip(self.hppo_state_dicts(), (hi_state_dict, lo_state_dict)):
-            for key, dst in dst_sd.items():
-                dst.copy_(src_sd[key])
-
-    def hppo_optimizer_state(self, level):
-        """``ZoneVecEnv.hppo_optimizer_state`` with the moments as CUDA copies."""
-        torch = self._torch
-        out = self.env.hppo_optimizer_state(level)
-        out["state"] = {i: {"step": torch.tensor(s["step"]), "exp_avg": torch.from_numpy(s["exp_avg"]).to(self.device),
-                            "exp_avg_sq": torch.from_numpy(s["exp_avg_sq"]).to(self.device)}
-                        for i, s in out["state"].items()}
-        return out
-
-    def hppo_load_optimizer_state(self, level, state):
-        self.env.hppo_load_optimizer_state(level, state)
-
-    def hppo_minibatch(self, level, idx, apply=False):
-        """``ZoneVecEnv.hppo_minibatch``; idx may be an int32 CUDA tensor (never copied, checked on the device)."""
-        ptr, count = self._ppo_index_arg(idx)
-        self.env.hppo_minibatch(level, ptr, apply=apply, count=count)
-
-    def hppo_apply(self, level):
-        self.env.hppo_apply(level)
-
-    def hppo_epoch(self, level, order, batch_size):
-        """``ZoneVecEnv.hppo_epoch``; order may be an int32 CUDA tensor."""
-        ptr, count = self._ppo_index_arg(order)
-        self.env.hppo_epoch(level, ptr, batch_size, count=count)
-
-    def hppo_stats(self, level):
-        """float32 CUDA tensor [minibatches, 6] ALIASING the statistics of the level's last hppo_minibatch / hppo_epoch
-        (not synchronised)."""
-        field = nat.HPPO_STATS_FIELDS[level]
-        rows = self.env.field_bytes(field) // 24
-        with self._torch.cuda.device(self.device):
-            return self._alias(field, (rows, 6), np.float32)
-
-    def hppo_publish(self):
-        self.env.hppo_publish()
-
-    def hppo_update(self, epochs, batch_size, hi_epochs, hi_batch_size, rng):
-        return self.env.hppo_update(epochs, batch_size, hi_epochs, hi_batch_size, rng)
-
-    # ------------------------------------------------------------------ the xy-goals agent's two PPO updates
-    def xyppo_init(self, hi_state_dict, lo_state_dict, lo=None, hi=None):
-        """``ZoneVecEnv.xyppo_init`` with each level's four arenas as flat float32 CUDA tensors ALIASING device memory in
-        ``self.xyppo_arenas[level]`` (valid until the next xyppo_init or ``env.close()``)."""
-        self.env.xyppo_init(hi_state_dict, lo_state_dict, lo=lo, hi=hi)
-        with self._torch.cuda.device(self.device):
-            self.xyppo_arenas = {}
-            for level in (nat.XYPPO_LO, nat.XYPPO_HI):
-                self.xyppo_arenas[level] = {}
-                for name, which in (("param", nat.PPO_PARAM), ("grad", nat.PPO_GRAD), ("exp_avg", nat.PPO_EXP_AVG),
-                                    ("exp_avg_sq", nat.PPO_EXP_AVG_SQ)):
-                    ptr, count = self.env.xyppo_tensor_ptr(level, which, -1)
-                    self.xyppo_arenas[level][name] = self._alias_ptr(ptr, (count,))
-
-    def xyppo_tensors(self, level, which=nat.PPO_PARAM):
-        """zenv_xy_weights name -> CUDA tensor ALIASING that tensor of a level's arena, in its state_dict shape."""
-        learner = self.env._xy_learner(level)
-        with self._torch.cuda.device(self.device):
-            return {name: self._alias_ptr(learner.tensor_ptr(which, i)[0], learner.shapes[name])
-                    for i, name in enumerate(learner.keys)}
-
-    def xyppo_set_tensors(self, level, tensors, which=nat.PPO_PARAM):
-        """Overwrite the tensors of a level's arena that `tensors` names (tensors on any device), on the stream."""
-        views = self.xyppo_tensors(level, which)
-        for name, src in tensors.items():
-            views[name].copy_(self._torch.as_tensor(src))
-
-    def xyppo_state_dicts(self):
-        """(hi_model_state, lo_model_state) as CUDA tensors ALIASING the two parameter arenas."""
-        out = []
-        for level in (nat.XYPPO_HI, nat.XYPPO_LO):
-            views = self.xyppo_tensors(level)
-            out.append({key: views[name] for name, key in self.env._xy_learner(level).keys.items()})
-        return tuple(out)
-
-    def xyppo_load_state_dicts(self, hi_state_dict, lo_state_dict):
-        for dst_sd, src_sd in zip(self.xyppo_state_dicts(), (hi_state_dict, lo_state_dict)):
-            for key, dst in dst_sd.items():
-                dst.copy_(src_sd[key])
-
-    def xyppo_optimizer_state(self, level):
-        """``ZoneVecEnv.xyppo_optimizer_state`` with the moments as CUDA copies."""
-        torch = self._torch
-        out = self.env.xyppo_optimizer_state(level)
-        out["state"] = {i: {"step": torch.tensor(s["step"]), "exp_avg": torch.from_numpy(s["exp_avg"]).to(self.device),
-                            "exp_avg_sq": torch.from_numpy(s["exp_avg_sq"]).to(self.device)}
-                        for i, s in out["state"].items()}
-        return out
-
-    def xyppo_load_optimizer_state(self, level, state):
-        self.env.xyppo_load_optimizer_state(level, state)
-
-    def xyppo_minibatch(self, level, idx, apply=False):
-        """``ZoneVecEnv.xyppo_minibatch``; idx may be an int32 CUDA tensor (never copied, checked on the device)."""
-        ptr, count = self._ppo_index_arg(idx)
-        self.env.xyppo_minibatch(level, ptr, apply=apply, count=count)
-
-    def xyppo_apply(self, level):
-        self.env.xyppo_apply(level)
-
-    def xyppo_epoch(self, level, order, batch_size):
-        """``ZoneVecEnv.xyppo_epoch``; order may be an int32 CUDA tensor."""
-        ptr, count = self._ppo_index_arg(order)
-        self.env.xyppo_epoch(level, ptr, batch_size, count=count)
-
-    def xyppo_stats(self, level):
-        """float32 CUDA tensor [minibatches, 6] ALIASING the statistics of the level's last xyppo_minibatch / xyppo_epoch
-        (not synchronised)."""
-        field = nat.XYPPO_STATS_FIELDS[level]
-        rows = self.env.field_bytes(field) // 24
-        with self._torch.cuda.device(self.device):
-            return self._alias(field, (rows, 6), np.float32)
-
-    def xyppo_publish(self):
-        self.env.xyppo_publish()
-
-    def xyppo_update(self, epochs, batch_size, hi_epochs, hi_batch_size, rng):
-        return self.env.xyppo_update(epochs, batch_size, hi_epochs, hi_batch_size, rng)
-
-    # ------------------------------------------------------------------ the fixed-length-skills agent's two PPO updates
-    def skppo_init(self, hi_state_dict, lo_state_dict, lo=None, hi=None):
-        """``ZoneVecEnv.skppo_init`` with each level's four arenas as flat float32 CUDA tensors ALIASING device memory in
-        ``self.skppo_arenas[level]`` (valid until the next skppo_init or ``env.close()``)."""
-        self.env.skppo_init(hi_state_dict, lo_state_dict, lo=lo, hi=hi)
-        with self._torch.cuda.device(self.device):
-            self.skppo_arenas = {}
-            for level in (nat.SKPPO_LO, nat.SKPPO_HI):
-                self.skppo_arenas[level] = {}
-                for name, which in (("param", nat.PPO_PARAM), ("grad", nat.PPO_GRAD), ("exp_avg", nat.PPO_EXP_AVG),
-                                    ("exp_avg_sq", nat.PPO_EXP_AVG_SQ)):
-                    ptr, count = self.env.skppo_tensor_ptr(level, which, -1)
-                    self.skppo_arenas[level][name] = self._alias_ptr(ptr, (count,))
-
-    def skppo_tensors(self, level, which=nat.PPO_PARAM):
-        """zenv_skill_weights name -> CUDA tensor ALIASING that tensor of a level's arena, in its state_dict shape."""
-        learner = self.env._sk_learner(level)
-        with self._torch.cuda.device(self.device):
-            return {name: self._alias_ptr(learner.tensor_ptr(which, i)[0], learner.shapes[name])
-                    for i, name in enumerate(learner.keys)}
-
-    def skppo_set_tensors(self, level, tensors, which=nat.PPO_PARAM):
-        """Overwrite the tensors of a level's arena that `tensors` names (tensors on any device), on the stream."""
-        views = self.skppo_tensors(level, which)
-        for name, src in tensors.items():
-            views[name].copy_(self._torch.as_tensor(src))
-
-    def skppo_state_dicts(self):
-        """(hi_model_state, lo_model_state) as CUDA tensors ALIASING the two parameter arenas."""
-        out = []
-        for level in (nat.SKPPO_HI, nat.SKPPO_LO):
-            views = self.skppo_tensors(level)
-            out.append({key: views[name] for name, key in self.env._sk_learner(level).keys.items()})
-        return tuple(out)
-
-    def skppo_load_state_dicts(self, hi_state_dict, lo_state_dict):
-        for dst_sd, src_sd in zip(self.skppo_state_dicts(), (hi_state_dict, lo_state_dict)):
-            for key, dst in dst_sd.items():
-                dst.copy_(src_sd[key])
-
-    def skppo_optimizer_state(self, level):
-        """``ZoneVecEnv.skppo_optimizer_state`` with the moments as CUDA copies."""
-        torch = self._torch
-        out = self.env.skppo_optimizer_state(level)
-        out["state"] = {i: {"step": torch.tensor(s["step"]), "exp_avg": torch.from_numpy(s["exp_avg"]).to(self.device),
-                            "exp_avg_sq": torch.from_numpy(s["exp_avg_sq"]).to(self.device)}
-                        for i, s in out["state"].items()}
-        return out
-
-    def skppo_load_optimizer_state(self, level, state):
-        self.env.skppo_load_optimizer_state(level, state)
-
-    def skppo_minibatch(self, level, idx, apply=False):
-        """``ZoneVecEnv.skppo_minibatch``; idx may be an int32 CUDA tensor (never copied, checked on the device)."""
-        ptr, count = self._ppo_index_arg(idx)
-        self.env.skppo_minibatch(level, ptr, apply=apply, count=count)
-
-    def skppo_apply(self, level):
-        self.env.skppo_apply(level)
-
-    def skppo_epoch(self, level, order, batch_size):
-        """``ZoneVecEnv.skppo_epoch``; order may be an int32 CUDA tensor."""
-        ptr, count = self._ppo_index_arg(order)
-        self.env.skppo_epoch(level, ptr, batch_size, count=count)
-
-    def skppo_stats(self, level):
-        """float32 CUDA tensor [minibatches, 6] ALIASING the statistics of the level's last skppo_minibatch / skppo_epoch
-        (not synchronised)."""
-        field = nat.SKPPO_STATS_FIELDS[level]
-        rows = self.env.field_bytes(field) // 24
-        with self._torch.cuda.device(self.device):
-            return self._alias(field, (rows, 6), np.float32)
-
-    def skppo_publish(self):
-        self.env.skppo_publish()
-
-    def skppo_update(self, epochs, batch_size, hi_epochs, hi_batch_size, rng):
-        return self.env.skppo_update(epochs, batch_size, hi_epochs, hi_batch_size, rng)
 
     # ------------------------------------------------------------------ DIAYN's inverse model and learned skill prior
     def diayn_init(self, inverse_state_dict, n_skills, prior_logits=None, prior=None, **hyper):
@@ -541,54 +444,7 @@ class TorchZoneEnv:
         if not any(k in inverse_state_dict for k in nat.SKILL_INVERSE_TENSORS):
             inverse_state_dict = inverse_tensors_from_state_dict(inverse_state_dict, n_skills)
         self.env.diayn_init(inverse_state_dict, n_skills, prior_logits=prior_logits, prior=prior, **hyper)
-        with self._torch.cuda.device(self.device):
-            self.diayn_arenas = {}
-            for name, which in (("param", nat.PPO_PARAM), ("grad", nat.PPO_GRAD), ("exp_avg", nat.PPO_EXP_AVG),
-                                ("exp_avg_sq", nat.PPO_EXP_AVG_SQ)):
-                ptr, count = self.env.diayn_tensor_ptr(which, -1)
-                self.diayn_arenas[name] = self._alias_ptr(ptr, (count,))
-
-    def diayn_tensors(self, which=nat.PPO_PARAM):
-        """zenv_skill_inverse_weights name -> CUDA tensor ALIASING that tensor of the arena, in its state_dict shape."""
-        learner = self.env._diayn_learner()
-        with self._torch.cuda.device(self.device):
-            return {name: self._alias_ptr(learner.tensor_ptr(which, i)[0], learner.shapes[name])
-                    for i, name in enumerate(learner.keys)}
-
-    def diayn_set_tensors(self, tensors, which=nat.PPO_PARAM):
-        views = self.diayn_tensors(which)
-        for name, src in tensors.items():
-            views[name].copy_(self._torch.as_tensor(src))
-
-    def diayn_state_dict(self):
-        """InverseModel's state_dict as CUDA tensors ALIASING the parameter arena."""
-        views = self.diayn_tensors()
-        return {key: views[name] for name, key in self.env._diayn_learner().keys.items()}
-
-    def diayn_load_state_dict(self, state_dict):
-        for key, dst in self.diayn_state_dict().items():
-            dst.copy_(state_dict[key])
-
-    def diayn_tensor_ptr(self, which, index):
-        return self.env.diayn_tensor_ptr(which, index)
-
-    def diayn_get_step(self):
-        return self.env.diayn_get_step()
-
-    def diayn_set_step(self, step):
-        self.env.diayn_set_step(step)
-
-    def diayn_optimizer_state(self):
-        """``ZoneVecEnv.diayn_optimizer_state`` with the moments as CUDA copies."""
-        torch = self._torch
-        out = self.env.diayn_optimizer_state()
-        out["state"] = {i: {"step": torch.tensor(s["step"]), "exp_avg": torch.from_numpy(s["exp_avg"]).to(self.device),
-                            "exp_avg_sq": torch.from_numpy(s["exp_avg_sq"]).to(self.device)}
-                        for i, s in out["state"].items()}
-        return out
-
-    def diayn_load_optimizer_state(self, state):
-        self.env.diayn_load_optimizer_state(state)
+        self.diayn_arenas = self._learner_arenas("diayn")
 
     def diayn_samples(self):
         """int32 CUDA tensor [count] ALIASING the kept sample indexes of the last ``collect_skills`` (compacted on the
@@ -598,26 +454,6 @@ class TorchZoneEnv:
             if not count:
                 return self._torch.empty(0, dtype=self._torch.int32, device=self.device)
             return self._alias(nat.F_DIAYN_SAMPLES, (count,), np.int32)
-
-    def diayn_minibatch(self, idx, apply=False):
-        """``ZoneVecEnv.diayn_minibatch``; idx may be an int32 CUDA tensor (never copied, checked on the device)."""
-        ptr, count = self._ppo_index_arg(idx)
-        self.env.diayn_minibatch(ptr, apply=apply, count=count)
-
-    def diayn_apply(self):
-        self.env.diayn_apply()
-
-    def diayn_epoch(self, order, batch_size):
-        """``ZoneVecEnv.diayn_epoch``; order may be an int32 CUDA tensor."""
-        ptr, count = self._ppo_index_arg(order)
-        self.env.diayn_epoch(ptr, batch_size, count=count)
-
-    def diayn_stats(self):
-        """float32 CUDA tensor [minibatches, 6] ALIASING the statistics of the last diayn_minibatch / diayn_epoch (not
-        synchronised)."""
-        rows = self.env.field_bytes(nat.F_DIAYN_STATS) // 24
-        with self._torch.cuda.device(self.device):
-            return self._alias(nat.F_DIAYN_STATS, (rows, 6), np.float32)
 
     def diayn_update(self, epochs, batch_size, generator=None):
         """``ZoneVecEnv.diayn_update`` with the list, the permutations (``torch.randperm`` from `generator`, a CUDA
@@ -646,94 +482,6 @@ class TorchZoneEnv:
 
     def diayn_publish(self):
         self.env.diayn_publish()
-
-    # ------------------------------------------------------------------ the Options agent's two PPO updates
-    def opppo_init(self, hi_state_dict, lo_state_dict, lo=None, hi=None):
-        """``ZoneVecEnv.opppo_init`` with each level's four arenas as flat float32 CUDA tensors ALIASING device memory in
-        ``self.opppo_arenas[level]`` (valid until the next opppo_init or ``env.close()``)."""
-        self.env.opppo_init(hi_state_dict, lo_state_dict, lo=lo, hi=hi)
-        with self._torch.cuda.device(self.device):
-            self.opppo_arenas = {}
-            for level in (nat.OPPPO_LO, nat.OPPPO_HI):
-                self.opppo_arenas[level] = {}
-                for name, which in (("param", nat.PPO_PARAM), ("grad", nat.PPO_GRAD), ("exp_avg", nat.PPO_EXP_AVG),
-                                    ("exp_avg_sq", nat.PPO_EXP_AVG_SQ)):
-                    ptr, count = self.env.opppo_tensor_ptr(level, which, -1)
-                    self.opppo_arenas[level][name] = self._alias_ptr(ptr, (count,))
-
-    def opppo_tensors(self, level, which=nat.PPO_PARAM):
-        """zenv_option_weights name -> CUDA tensor ALIASING that tensor of a level's arena, in its state_dict shape."""
-        learner = self.env._op_learner(level)
-        with self._torch.cuda.device(self.device):
-            return {name: self._alias_ptr(learner.tensor_ptr(which, i)[0], learner.shapes[name])
-                    for i, name in enumerate(learner.keys)}
-
-    def opppo_set_tensors(self, level, tensors, which=nat.PPO_PARAM):
-        """Overwrite the tensors of a level's arena that `tensors` names (tensors on any device), on the stream."""
-        views = self.opppo_tensors(level, which)
-        for name, src in tensors.items():
-            views[name].copy_(self._torch.as_tensor(src))
-
-    def opppo_state_dicts(self):
-        """(hi_model_state, lo_model_state) as CUDA tensors ALIASING the two parameter arenas."""
-        out = []
-        for level in (nat.OPPPO_HI, nat.OPPPO_LO):
-            views = self.opppo_tensors(level)
-            out.append({key: views[name] for name, key in self.env._op_learner(level).keys.items()})
-        return tuple(out)
-
-    def opppo_load_state_dicts(self, hi_state_dict, lo_state_dict):
-        for dst_sd, src_sd in zip(self.opppo_state_dicts(), (hi_state_dict, lo_state_dict)):
-            for key, dst in dst_sd.items():
-                dst.copy_(src_sd[key])
-
-    def opppo_tensor_ptr(self, level, which, index):
-        return self.env.opppo_tensor_ptr(level, which, index)
-
-    def opppo_get_step(self, level):
-        return self.env.opppo_get_step(level)
-
-    def opppo_set_step(self, level, step):
-        self.env.opppo_set_step(level, step)
-
-    def opppo_optimizer_state(self, level):
-        """``ZoneVecEnv.opppo_optimizer_state`` with the moments as CUDA copies."""
-        torch = self._torch
-        out = self.env.opppo_optimizer_state(level)
-        out["state"] = {i: {"step": torch.tensor(s["step"]), "exp_avg": torch.from_numpy(s["exp_avg"]).to(self.device),
-                            "exp_avg_sq": torch.from_numpy(s["exp_avg_sq"]).to(self.device)}
-                        for i, s in out["state"].items()}
-        return out
-
-    def opppo_load_optimizer_state(self, level, state):
-        self.env.opppo_load_optimizer_state(level, state)
-
-    def opppo_minibatch(self, level, idx, apply=False):
-        """``ZoneVecEnv.opppo_minibatch``; idx may be an int32 CUDA tensor (never copied, checked on the device)."""
-        ptr, count = self._ppo_index_arg(idx)
-        self.env.opppo_minibatch(level, ptr, apply=apply, count=count)
-
-    def opppo_apply(self, level):
-        self.env.opppo_apply(level)
-
-    def opppo_epoch(self, level, order, batch_size):
-        """``ZoneVecEnv.opppo_epoch``; order may be an int32 CUDA tensor."""
-        ptr, count = self._ppo_index_arg(order)
-        self.env.opppo_epoch(level, ptr, batch_size, count=count)
-
-    def opppo_stats(self, level):
-        """float32 CUDA tensor [minibatches, 6] ALIASING the statistics of the level's last opppo_minibatch / opppo_epoch
-        (not synchronised)."""
-        field = nat.OPPPO_STATS_FIELDS[level]
-        rows = self.env.field_bytes(field) // 24
-        with self._torch.cuda.device(self.device):
-            return self._alias(field, (rows, 6), np.float32)
-
-    def opppo_publish(self):
-        self.env.opppo_publish()
-
-    def opppo_update(self, epochs, batch_size, hi_epochs, hi_batch_size, rng):
-        return self.env.opppo_update(epochs, batch_size, hi_epochs, hi_batch_size, rng)
 
     def load_hier(self, hi_state_dict, lo_state_dict):
         """Put HighPolicyValueModel / LoPolicyValueModel state_dicts (zone-goals/src/hier_policy_value_models.py; torch

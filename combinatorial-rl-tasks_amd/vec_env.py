@@ -8,6 +8,7 @@ re-reset inside the same launch and report the next episode's first observation 
 terminal reward/done, exactly like ``worker`` (penv.py:7-11).
 """
 import ctypes as C
+import dataclasses
 import math
 
 import numpy as np
@@ -61,25 +62,50 @@ def _as_host_f32(v):
     return np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, np.float32)
 
 
-class _Learner:
-    """One device learner behind the ppo_* (level None: zenv_ppo_*), hppo_* (zenv_hppo_* with a level), xyppo_*
-    (prefix "zenv_xyppo_"), skppo_* (prefix "zenv_skppo_") or opppo_* (prefix "zenv_opppo_") methods: the arenas' tensors under their names, Adam's
-    state, the update calls and the statistics.  The a2c_* methods' learner (prefix "zenv_a2c_", level None) is one too:
-    RMSprop's state where the others have Adam's, ``accumulate`` / ``update`` where they have ``minibatch`` / ``epoch``,
-    one row of five statistics (stats_cols)."""
+@dataclasses.dataclass(frozen=True)
+class _LearnerFamily:
+    """What the methods <key>_* of one learner family differ in.  The C functions are zenv_<key>_*; a family with
+    levels is a pair of learners (level 0 the low one, 1 the high one) whose C functions take the level."""
+    key: str
+    stats_fields: tuple                 # the statistics field by level (one entry without levels)
+    docs: dict                          # forwarder -> its docstring, for those that have one
+    levels: bool = False
+    stats_cols: int = 6
+    rmsprop: bool = False               # the optimiser state is RMSprop's (square_avg), not Adam's
+    # a pair's init (_pair_init) and publish (_pair_publish)
+    weights: type = None                # the struct of zenv_<key>_init
+    skills: bool = False                # its weights carry n_skills
+    tensors_from: object = None         # (hi_state_dict, lo_state_dict) -> the struct's tensors by name
+    keys: object = None                 # () -> (hi, lo) dicts: tensor name -> state_dict key, in arena order
+    shapes: object = None               # (h, [S,] F) -> tensor name -> shape
+    defaults: tuple = ()                # the names of ZoneVecEnv's default settings, (low, high)
+    loader: str = None                  # the ZoneVecEnv method that hands tensors to the acting agent
+    loader_skill_len: bool = False      # ... and takes the handle's current skill_len
+    # a pair's update (_pair_update)
+    lo_drops_last: bool = False         # the low level trains on frames 0 .. T-2 of every env, not on all T
+    m_from: tuple = ()                  # (field, bytes per row): where the number of high-level rows M is read from
+    needs_rows: bool = False            # M = 0 is an error; else the high level is skipped and its logs are zeros
+    no_experience: str = ""             # the ZENV_E_STATE message when the handle holds none of the agent's records
 
-    def __init__(self, handle, level, keys, shapes, lr, adam_eps, stats_field, prefix="zenv_hppo_", stats_cols=6,
-                 rmsprop_alpha=None):
-        self._h, self.level, self.keys, self.shapes = handle, level, keys, shapes
-        self.lr, self.adam_eps, self.stats_field, self.prefix = lr, adam_eps, stats_field, prefix
-        self.stats_cols, self.rmsprop_alpha = stats_cols, rmsprop_alpha
+    @property
+    def prefix(self):
+        return f"zenv_{self.key}_"
+
+
+class _Learner:
+    """One device learner behind the <key>_* methods of a family: the arenas' tensors under their names, the optimiser's
+    state (Adam's; RMSprop's for a2c_*), the update calls and the statistics.  keys empty: a learner not created through
+    this object -- every call of it goes to the library, which answers ZENV_E_STATE (ZENV_E_ARG for a level that does
+    not exist)."""
+
+    def __init__(self, handle, family, level, keys=None, shapes=None, lr=0.0, adam_eps=0.0, rmsprop_alpha=None):
+        self._h, self.family, self.level, self.keys, self.shapes = handle, family, level, keys or {}, shapes or {}
+        self.lr, self.adam_eps, self.rmsprop_alpha = lr, adam_eps, rmsprop_alpha
+        self.stats_field = family.stats_fields[level if family.levels and level in (0, 1) else 0]
 
     def _call(self, name, *args):
-        if self.level is None:          # the learners without a level: the flat one's and DIAYN's inverse model's
-            prefix = self.prefix if self.prefix in ("zenv_diayn_", "zenv_a2c_") else "zenv_ppo_"
-            check(getattr(lib(), prefix + name)(self._h, *args))
-        else:
-            check(getattr(lib(), self.prefix + name)(self._h, int(self.level), *args))
+        level = (int(self.level),) if self.family.levels else ()
+        check(getattr(lib(), self.family.prefix + name)(self._h, *level, *args))
 
     def tensor_ptr(self, which, index):
         p, n = C.c_void_p(), C.c_int64()
@@ -117,6 +143,8 @@ class _Learner:
         self.set_tensors({name: _as_host_f32(state_dict[key]) for name, key in self.keys.items()})
 
     def optimizer_state(self):
+        if self.family.rmsprop:
+            return self._rmsprop_state()
         m, v = self.tensors(nat.PPO_EXP_AVG), self.tensors(nat.PPO_EXP_AVG_SQ)
         step = self.get_step()
         state = {i: {"step": float(step), "exp_avg": m[name], "exp_avg_sq": v[name]}
@@ -126,6 +154,8 @@ class _Learner:
         return {"state": state, "param_groups": [group]}
 
     def load_optimizer_state(self, state):
+        if self.family.rmsprop:
+            return self._load_rmsprop_state(state)
         names = list(self.keys)
         st = state["state"]
         zeros = {n: np.zeros(self.shapes[n], np.float32) for n in names}
@@ -135,7 +165,7 @@ class _Learner:
                          nat.PPO_EXP_AVG_SQ)
         self.set_step(int(float(st[0]["step"])) if st else 0)
 
-    def rmsprop_state(self):
+    def _rmsprop_state(self):
         """``torch.optim.RMSprop.state_dict()``'s shape (momentum 0, not centered): ``step`` and ``square_avg``."""
         v = self.tensors(nat.A2C_SQUARE_AVG)
         step = self.get_step()
@@ -144,7 +174,7 @@ class _Learner:
                  "weight_decay": 0, "params": list(range(len(self.keys)))}
         return {"state": state, "param_groups": [group]}
 
-    def load_rmsprop_state(self, state):
+    def _load_rmsprop_state(self, state):
         names = list(self.keys)
         st = state["state"]
         zeros = {n: np.zeros(self.shapes[n], np.float32) for n in names}
@@ -187,12 +217,224 @@ class _Learner:
         self._call("epoch", C.c_void_p(ptr), n, int(batch_size), dev)
 
     def stats(self):
-        cols = self.stats_cols
+        cols = self.family.stats_cols
         rows = lib().zenv_field_bytes(self._h, self.stats_field) // (4 * cols)
         out = np.empty((rows, cols), np.float32)
         if rows:
             check(lib().zenv_get(self._h, self.stats_field, out.ctypes.data, 0))
         return out
+
+
+def _pair_docs(key, weights, minibatch):
+    """The docstrings of a pair's forwarders; minibatch: the family's own, the index order of its two levels."""
+    return {
+        "tensor_ptr": "``ppo_tensor_ptr`` of a level's arenas.",
+        "tensors": f"Every tensor of a level's arena as a new host array, under its {weights} name (hi_* / lo_*).",
+        "state_dicts": "(hi_model_state, lo_model_state): both learners' parameters under the reference's names (host "
+                       "copies).",
+        "optimizer_state": "A level's Adam state in the shape of ``torch.optim.Adam.state_dict()``: parameter i is the "
+                           "i-th of the\n        module's ``parameters()``.",
+        "minibatch": minibatch,
+        "stats": f"float32 [minibatches, 6] of the level's last {key}_minibatch / {key}_epoch (``_native.PPO_STATS``' "
+                 "columns,\n        value_std = 0).  Waits for the device.",
+    }
+
+
+_FLAT_DOCS = {
+    "tensors": "Every tensor of an arena as a new host array, under its zenv_mlp_weights name.",
+    "set_tensors": "Overwrite the tensors of an arena that `tensors` names (zenv_mlp_weights names).",
+    "state_dict": "The learner's parameters under the reference ACModel's state_dict names (host float32 copies).",
+    "load_state_dict": "Overwrite the learner's parameters from an ACModel state_dict (every key must be there).",
+}
+
+_FAMILIES = {f.key: f for f in (
+    _LearnerFamily(
+        "ppo", (nat.F_PPO_STATS,), dict(
+            _FLAT_DOCS,
+            tensor_ptr="(device pointer, element count) of tensor `index` (arena order; -1: the whole arena) of arena "
+                       "`which`\n        (``_native.PPO_PARAM`` / ``PPO_GRAD`` / ``PPO_EXP_AVG`` / ``PPO_EXP_AVG_SQ``).",
+            optimizer_state="Adam's state in the shape of ``torch.optim.Adam.state_dict()`` (train_ppo.py:116-122), host "
+                            "arrays: parameter\n        i is the i-th of ``ACModel.parameters()``.",
+            load_optimizer_state="Restore Adam's moments and step count from ``ppo_optimizer_state`` / "
+                                 "``torch.optim.Adam.state_dict()``.",
+            minibatch="Forward, loss and backward on the samples idx (host int32 array, or a device address with count): "
+                      "the\n        gradients stay in their arena, the statistics in ``ppo_stats()[0]``; apply: the clip "
+                      "and Adam step too.\n        Index i is env i // T, frame i % T of the last collect.  Asynchronous.",
+            apply="clip_grad_norm_ and one Adam step on whatever the gradient arena holds.",
+            epoch="The minibatches order[k * batch_size : (k + 1) * batch_size] in sequence (the last one short), each "
+                  "with\n        its clip and Adam step; no host synchronisation.  ``ppo_stats()`` has a row per minibatch.",
+            stats="float32 [minibatches, 6] of the last ppo_minibatch / ppo_epoch: ``_native.PPO_STATS`` names the "
+                  "columns\n        (ppo.py:93-100, :121).  Waits for the device.")),
+    _LearnerFamily(
+        "a2c", (nat.F_A2C_STATS,), dict(
+            _FLAT_DOCS,
+            tensor_ptr="(device pointer, element count) of tensor `index` (arena order; -1: the whole arena) of arena "
+                       "`which`\n        (``_native.A2C_PARAM`` / ``A2C_GRAD`` / ``A2C_SQUARE_AVG``).",
+            optimizer_state="RMSprop's state in the shape of ``torch.optim.RMSprop.state_dict()`` (``step``, "
+                            "``square_avg``), host arrays:\n        parameter i is the i-th of ``ACModel.parameters()``.",
+            load_optimizer_state="Restore square_avg and the step count from ``a2c_optimizer_state`` / "
+                                 "``torch.optim.RMSprop.state_dict()``:\n        the ``optimizer_state`` of an A2C run's "
+                                 "status.pt resumes here.",
+            apply="The gradient norm, clip_grad_norm_ and one RMSprop step on whatever the gradient arena holds; the "
+                  "five\n        statistics of the accumulated frames go to ``a2c_stats()``.",
+            stats="float32 [1, 5] of the last a2c_apply / a2c_update ([0, 5] before the first): ``_native.A2C_STATS`` "
+                  "names the\n        columns.  Waits for the device."),
+        stats_cols=len(nat.A2C_STATS), rmsprop=True),
+    _LearnerFamily(
+        "hppo", nat.HPPO_STATS_FIELDS, _pair_docs(
+            "hppo", "zenv_hier_weights",
+            "``ppo_minibatch`` on the records of the last ``collect_hier``.  Low level: index i is env i // (T-1), frame"
+            "\n        i % (T-1) (lo_exps' order); high level: row i of the M closed transitions."),
+        levels=True, weights=nat.HierWeights, tensors_from=hier_tensors_from_state_dicts, keys=hppo_state_dict_keys,
+        shapes=hier_tensor_shapes, defaults=("HPPO_LO", "HPPO_HI"), loader="load_hier", lo_drops_last=True,
+        m_from=(nat.F_HI_VALUE, 4), no_experience="collect_hier first: the handle holds no experience"),
+    _LearnerFamily(
+        "xyppo", nat.XYPPO_STATS_FIELDS, _pair_docs(
+            "xyppo", "zenv_xy_weights",
+            "``ppo_minibatch`` on the records of the last ``collect_xy``.  Low level: index i is env i // T, frame i % T"
+            "\n        (lo_exps' order, every frame); high level: row i of the M = N T / skill_len windows."),
+        levels=True, weights=nat.XyWeights, tensors_from=xy_tensors_from_state_dicts, keys=xyppo_state_dict_keys,
+        shapes=xy_tensor_shapes, defaults=("XYPPO_LO", "XYPPO_HI"), loader="load_xy", loader_skill_len=True,
+        m_from=(nat.F_HI_GOAL, 8), needs_rows=True,
+        no_experience="collect_xy first: the handle holds no experience of the xy-goals agent"),
+    _LearnerFamily(
+        "skppo", nat.SKPPO_STATS_FIELDS, _pair_docs(
+            "skppo", "zenv_skill_weights",
+            "``ppo_minibatch`` on the records of the last ``collect_skills``.  Low level: index i is env i // T, frame "
+            "i % T\n        (lo_exps' order, every frame); high level: row i of the M = N T / skill_len windows."),
+        levels=True, weights=nat.SkillWeights, skills=True, tensors_from=skill_tensors_from_state_dicts,
+        keys=skppo_state_dict_keys, shapes=skill_tensor_shapes, defaults=("SKPPO_LO", "SKPPO_HI"), loader="load_skills",
+        loader_skill_len=True, m_from=(nat.F_HI_ACTION, 4), needs_rows=True,
+        no_experience="collect_skills first: the handle holds no experience of the fixed-length-skills agent"),
+    _LearnerFamily(
+        "opppo", nat.OPPPO_STATS_FIELDS, _pair_docs(
+            "opppo", "zenv_option_weights",
+            "``ppo_minibatch`` on the records of the last ``collect_options``.  Low level: index i is env i // (T - 1), "
+            "frame\n        i % (T - 1) (lo_exps' order; frame T - 1 is never read); high level: row i of the M closed "
+            "transitions (M >= 1)."),
+        levels=True, weights=nat.OptionWeights, skills=True, tensors_from=option_tensors_from_state_dicts,
+        keys=opppo_state_dict_keys, shapes=option_tensor_shapes, defaults=("OPPPO_LO", "OPPPO_HI"), loader="load_options",
+        lo_drops_last=True, m_from=(nat.F_HI_ACTION, 4),
+        no_experience="collect_options first: the handle holds no experience of the Options agent"),
+    _LearnerFamily(
+        "diayn", (nat.F_DIAYN_STATS,), {
+            "tensor_ptr": "``ppo_tensor_ptr`` of the inverse model's arenas.",
+            "tensors": "Every tensor of the arena as a new host array, under its zenv_skill_inverse_weights name.",
+            "state_dict": "The learner's parameters under InverseModel's names (host copies).",
+            "optimizer_state": "Adam's state in the shape of ``torch.optim.Adam.state_dict()``: parameter i is the i-th "
+                               "of ``parameters()``.",
+            "minibatch": "``ppo_minibatch`` of the inverse model on the sample indexes idx (entries of "
+                         "``diayn_samples()``).",
+            "stats": "float32 [minibatches, 6] of the last diayn_minibatch / diayn_epoch: column 0 the cross-entropy "
+                     "loss, column\n        5 the gradient norm, columns 1-4 zero.  Waits for the device."}),
+)}
+
+
+def _forwarders(fam):
+    """call -> the method <key>_<call> of ZoneVecEnv for the thin forwarders of a family: each finds the learner and
+    hands its arguments on.  A pair's take the level first and have state_dicts / load_state_dicts for both levels."""
+    key = fam.key
+    if fam.levels:
+        def tensor_ptr(self, level, which, index):
+            return self._learner_of(key, level).tensor_ptr(which, index)
+
+        def tensors(self, level, which=nat.PPO_PARAM):
+            return self._learner_of(key, level).tensors(which)
+
+        def set_tensors(self, level, tensors, which=nat.PPO_PARAM):
+            self._learner_of(key, level).set_tensors(tensors, which)
+
+        def state_dicts(self):
+            return self._learner_of(key, 1).state_dict(), self._learner_of(key, 0).state_dict()
+
+        def load_state_dicts(self, hi_state_dict, lo_state_dict):
+            self._learner_of(key, 1).load_state_dict(hi_state_dict)
+            self._learner_of(key, 0).load_state_dict(lo_state_dict)
+
+        def optimizer_state(self, level):
+            return self._learner_of(key, level).optimizer_state()
+
+        def load_optimizer_state(self, level, state):
+            self._learner_of(key, level).load_optimizer_state(state)
+
+        def get_step(self, level):
+            return self._learner_of(key, level).get_step()
+
+        def set_step(self, level, step):
+            self._learner_of(key, level).set_step(step)
+
+        def minibatch(self, level, idx, apply=False, count=None):
+            self._learner_of(key, level).minibatch(idx, apply, count)
+
+        def apply(self, level):
+            self._learner_of(key, level).apply()
+
+        def epoch(self, level, order, batch_size, count=None):
+            self._learner_of(key, level).epoch(order, batch_size, count)
+
+        def stats(self, level):
+            return self._learner_of(key, level).stats()
+
+        return dict(tensor_ptr=tensor_ptr, tensors=tensors, set_tensors=set_tensors, state_dicts=state_dicts,
+                    load_state_dicts=load_state_dicts, optimizer_state=optimizer_state,
+                    load_optimizer_state=load_optimizer_state, get_step=get_step, set_step=set_step, minibatch=minibatch,
+                    apply=apply, epoch=epoch, stats=stats)
+
+    def tensor_ptr(self, which, index):
+        return self._learner_of(key).tensor_ptr(which, index)
+
+    def tensors(self, which=nat.PPO_PARAM):
+        return self._learner_of(key).tensors(which)
+
+    def set_tensors(self, tensors, which=nat.PPO_PARAM):
+        self._learner_of(key).set_tensors(tensors, which)
+
+    def state_dict(self):
+        return self._learner_of(key).state_dict()
+
+    def load_state_dict(self, state_dict):
+        self._learner_of(key).load_state_dict(state_dict)
+
+    def optimizer_state(self):
+        return self._learner_of(key).optimizer_state()
+
+    def load_optimizer_state(self, state):
+        self._learner_of(key).load_optimizer_state(state)
+
+    def get_step(self):
+        return self._learner_of(key).get_step()
+
+    def set_step(self, step):
+        self._learner_of(key).set_step(step)
+
+    def minibatch(self, idx, apply=False, count=None):
+        self._learner_of(key).minibatch(idx, apply, count)
+
+    def apply(self):
+        self._learner_of(key).apply()
+
+    def epoch(self, order, batch_size, count=None):
+        self._learner_of(key).epoch(order, batch_size, count)
+
+    def stats(self):
+        return self._learner_of(key).stats()
+
+    out = dict(tensor_ptr=tensor_ptr, tensors=tensors, set_tensors=set_tensors, state_dict=state_dict,
+               load_state_dict=load_state_dict, optimizer_state=optimizer_state,
+               load_optimizer_state=load_optimizer_state, get_step=get_step, set_step=set_step, apply=apply, stats=stats)
+    if not fam.rmsprop:         # the A2C learner has accumulate / update instead (ZoneVecEnv.a2c_accumulate, a2c_update)
+        out.update(minibatch=minibatch, epoch=epoch)
+    return out
+
+
+def _install_forwarders(cls):
+    for fam in _FAMILIES.values():
+        for call, f in _forwarders(fam).items():
+            f.__name__ = f"{fam.key}_{call}"
+            f.__qualname__ = f"{cls.__name__}.{f.__name__}"
+            f.__doc__ = fam.docs.get(call)
+            setattr(cls, f.__name__, f)
+    return cls
 
 
 def ppo_logs(stats, distributional):
@@ -373,6 +615,7 @@ def fixed_seed_sequence(rng_seed, min_seed, max_seed, count):
     return out
 
 
+@_install_forwarders
 class ZoneVecEnv:
     """N device-resident zone envs.
 
@@ -394,7 +637,7 @@ class ZoneVecEnv:
         self.zone_feat = zone_feat(cfg)
         self.device = int(device)
         self._h = C.c_void_p()
-        self._learners = {}         # level (None: the flat learner) -> _Learner, of the learners created through this object
+        self._learners = {}         # (family key, level or None) -> _Learner, of the learners created through this object
         check(lib().zenv_create(C.byref(cfg), self.num_envs, self.device, C.byref(self._h)))
 
     # ------------------------------------------------------------------ lifecycle
@@ -663,7 +906,8 @@ class ZoneVecEnv:
         ``enable_order()`` came first."""
         check(lib().zenv_order_rows(self._h, int(bool(enable))))
         if bool(enable) != getattr(self, "_order_rows", False):      # (no change: nothing was dropped)
-            self._learners.pop(None, None)
+            for key in ("ppo", "a2c"):                                # the library dropped both flat learners
+                self._learners.pop((key, None), None)
         self._order_rows = bool(enable)
 
     @property
@@ -1115,6 +1359,32 @@ class ZoneVecEnv:
         """Zero the running sums and the tail: the logs of a fresh algo object."""
         check(lib().zenv_episode_log_reset(self._h))
 
+    # ------------------------------------------------------------------ the device learners
+    # The thin methods of the seven families -- <key>_tensor_ptr, _tensors, _set_tensors, _state_dict(s),
+    # _load_state_dict(s), _optimizer_state, _load_optimizer_state, _get_step, _set_step, _minibatch, _apply, _epoch and
+    # _stats -- are installed from _FAMILIES (_install_forwarders); here are the inits, updates and publishes.
+    def _learner_of(self, family, level=None):
+        """The learner of a family (of a pair: of its level); before its init a bare one without tensor names: every
+        call of it goes to the library, which answers ZENV_E_STATE (ZENV_E_ARG for a level that does not exist)."""
+        fam = _FAMILIES[family]
+        level = int(level) if fam.levels else None
+        return self._learners.get((fam.key, level)) or _Learner(self._h, fam, level)
+
+    # what the flat learners' tests have always reached for: the tensor names of the two, and the A2C learner itself
+    _ppo_keys = property(lambda self: self._learner_of("ppo").keys)
+    _a2c_keys = property(lambda self: self._learner_of("a2c").keys)
+    _a2c = property(lambda self: self._learner_of("a2c"))
+
+    def _flat_weights(self, state_dict_or_tensors):
+        """(struct, tensors, shapes, what to keep alive across the call) of the flat learners' inits."""
+        d = state_dict_or_tensors
+        tensors = dict(d) if "zone_w1" in d else mlp_tensors_from_state_dict(d)
+        h = int(np.asarray(tensors["zone_b1"]).shape[0])
+        w = nat.MlpWeights(h_dim=h, precision=nat.MLP_F32)
+        names = [n for n in nat.MLP_TENSORS + nat.MLP_CRITIC_TENSORS + nat.MLP_SIGMA_TENSORS if n in tensors]
+        shapes = mlp_tensor_shapes(h, self.net_zone_feat)
+        return w, tensors, shapes, self._load_weights(w, names, tensors, shapes)
+
     # ------------------------------------------------------------------ the flat actor-critic's PPO update
     def ppo_init(self, state_dict_or_tensors, lr=0.001, adam_eps=1e-8, clip_eps=0.2, entropy_coef=0.01,
                  value_loss_coef=0.5, max_grad_norm=0.5, max_batch=256, distributional_value=None):
@@ -1123,91 +1393,17 @@ class ZoneVecEnv:
         Adam's two moments, and the workspace of minibatches up to max_batch samples.  The defaults are PPOAlgo's
         (ppo.py:11-14).  distributional_value: None = whatever the tensors hold (critic_sigma).  Separate from
         ``load_mlp``: ``ppo_publish`` hands the parameters to the acting network."""
-        d = state_dict_or_tensors
-        tensors = dict(d) if "zone_w1" in d else mlp_tensors_from_state_dict(d)
+        w, tensors, shapes, keep = self._flat_weights(state_dict_or_tensors)     # keep: alive across the call
         if distributional_value is None:
             distributional_value = "critic_sigma_w" in tensors
-        h = int(np.asarray(tensors["zone_b1"]).shape[0])
-        w = nat.MlpWeights(h_dim=h, precision=nat.MLP_F32)
-        names = [n for n in nat.MLP_TENSORS + nat.MLP_CRITIC_TENSORS + nat.MLP_SIGMA_TENSORS if n in tensors]
-        keep = self._load_weights(w, names, tensors, mlp_tensor_shapes(h, self.net_zone_feat))   # alive across the call
         pc = nat.PpoConfig(lr=lr, adam_eps=adam_eps, clip_eps=clip_eps, entropy_coef=entropy_coef,
                            value_loss_coef=value_loss_coef, max_grad_norm=max_grad_norm, max_batch=int(max_batch),
                            distributional_value=int(bool(distributional_value)))
         check(lib().zenv_ppo_init(self._h, C.byref(w), C.byref(pc)))
         del keep
-        self._ppo_h = h
-        self._ppo_keys = ppo_state_dict_keys(bool(distributional_value))
-        self._learners[None] = _Learner(self._h, None, self._ppo_keys, mlp_tensor_shapes(h, self.net_zone_feat), lr,
-                                        adam_eps, nat.F_PPO_STATS)
+        self._learners[("ppo", None)] = _Learner(self._h, _FAMILIES["ppo"], None,
+                                                 ppo_state_dict_keys(bool(distributional_value)), shapes, lr, adam_eps)
         self.ppo_batch_num = 0          # PPOAlgo.batch_num (ppo.py:28)
-
-    def _learner(self, level):
-        """The learner of a level; before its init a bare one without tensor names: every call of it goes to the
-        library, which answers ZENV_E_STATE (ZENV_E_ARG for a level that does not exist)."""
-        found = self._learners.get(level if level is None else int(level))
-        field = nat.HPPO_STATS_FIELDS[level] if level in (nat.HPPO_LO, nat.HPPO_HI) else nat.F_PPO_STATS
-        return found or _Learner(self._h, level, {}, {}, 0.0, 0.0, field)
-
-    @property
-    def _ppo(self):
-        return self._learner(None)
-
-    def ppo_tensor_ptr(self, which, index):
-        """(device pointer, element count) of tensor `index` (arena order; -1: the whole arena) of arena `which`
-        (``_native.PPO_PARAM`` / ``PPO_GRAD`` / ``PPO_EXP_AVG`` / ``PPO_EXP_AVG_SQ``)."""
-        return self._ppo.tensor_ptr(which, index)
-
-    def ppo_tensors(self, which=nat.PPO_PARAM):
-        """Every tensor of an arena as a new host array, under its zenv_mlp_weights name."""
-        return self._ppo.tensors(which)
-
-    def ppo_set_tensors(self, tensors, which=nat.PPO_PARAM):
-        """Overwrite the tensors of an arena that `tensors` names (zenv_mlp_weights names)."""
-        self._ppo.set_tensors(tensors, which)
-
-    def ppo_state_dict(self):
-        """The learner's parameters under the reference ACModel's state_dict names (host float32 copies)."""
-        return self._ppo.state_dict()
-
-    def ppo_load_state_dict(self, state_dict):
-        """Overwrite the learner's parameters from an ACModel state_dict (every key must be there)."""
-        self._ppo.load_state_dict(state_dict)
-
-    def ppo_optimizer_state(self):
-        """Adam's state in the shape of ``torch.optim.Adam.state_dict()`` (train_ppo.py:116-122), host arrays: parameter
-        i is the i-th of ``ACModel.parameters()``."""
-        return self._ppo.optimizer_state()
-
-    def ppo_load_optimizer_state(self, state):
-        """Restore Adam's moments and step count from ``ppo_optimizer_state`` / ``torch.optim.Adam.state_dict()``."""
-        self._ppo.load_optimizer_state(state)
-
-    def ppo_get_step(self):
-        return self._ppo.get_step()
-
-    def ppo_set_step(self, step):
-        self._ppo.set_step(step)
-
-    def ppo_minibatch(self, idx, apply=False, count=None):
-        """Forward, loss and backward on the samples idx (host int32 array, or a device address with count): the
-        gradients stay in their arena, the statistics in ``ppo_stats()[0]``; apply: the clip and Adam step too.
-        Index i is env i // T, frame i % T of the last collect.  Asynchronous."""
-        self._ppo.minibatch(idx, apply, count)
-
-    def ppo_apply(self):
-        """clip_grad_norm_ and one Adam step on whatever the gradient arena holds."""
-        self._ppo.apply()
-
-    def ppo_epoch(self, order, batch_size, count=None):
-        """The minibatches order[k * batch_size : (k + 1) * batch_size] in sequence (the last one short), each with
-        its clip and Adam step; no host synchronisation.  ``ppo_stats()`` has a row per minibatch."""
-        self._ppo.epoch(order, batch_size, count)
-
-    def ppo_stats(self):
-        """float32 [minibatches, 6] of the last ppo_minibatch / ppo_epoch: ``_native.PPO_STATS`` names the columns
-        (ppo.py:93-100, :121).  Waits for the device."""
-        return self._ppo.stats()
 
     def ppo_publish(self, precision="auto"):
         """Hand the learner's parameters to the acting network: read them back (0.7 MB) and ``load_mlp`` them, so
@@ -1225,7 +1421,7 @@ class ZoneVecEnv:
             order = ppo_batch_indexes(self.num_envs * T, T, self.ppo_batch_num, rng)
             self.ppo_batch_num += 1
             self.ppo_epoch(order, batch_size)
-        return ppo_logs(self.ppo_stats(), "critic_sigma_w" in self._ppo_keys)
+        return ppo_logs(self.ppo_stats(), "critic_sigma_w" in self._learner_of("ppo").keys)
 
     # ------------------------------------------------------------------ the flat actor-critic's A2C update
     def a2c_init(self, state_dict_or_tensors, lr=0.01, rmsprop_alpha=0.99, rmsprop_eps=1e-8, entropy_coef=0.01,
@@ -1235,79 +1431,19 @@ class ZoneVecEnv:
         ``mlp_tensors_from_state_dict``), their gradients and RMSprop's square_avg.  The defaults are A2CAlgo's
         (a2c.py:10-12).  max_batch is the chunk an update walks the collection in: it sizes the activation
         workspace, not the batch the loss is averaged over, which is always all N x T frames.  The plain critic only."""
-        d = state_dict_or_tensors
-        tensors = dict(d) if "zone_w1" in d else mlp_tensors_from_state_dict(d)
-        h = int(np.asarray(tensors["zone_b1"]).shape[0])
-        w = nat.MlpWeights(h_dim=h, precision=nat.MLP_F32)
-        names = [n for n in nat.MLP_TENSORS + nat.MLP_CRITIC_TENSORS + nat.MLP_SIGMA_TENSORS if n in tensors]
-        keep = self._load_weights(w, names, tensors, mlp_tensor_shapes(h, self.net_zone_feat))   # alive across the call
+        w, _, shapes, keep = self._flat_weights(state_dict_or_tensors)           # keep: alive across the call
         ac = nat.A2cConfig(lr=lr, rmsprop_alpha=rmsprop_alpha, rmsprop_eps=rmsprop_eps, entropy_coef=entropy_coef,
                            value_loss_coef=value_loss_coef, max_grad_norm=max_grad_norm, max_batch=int(max_batch))
         check(lib().zenv_a2c_init(self._h, C.byref(w), C.byref(ac)))
         del keep
-        self._a2c_h = h
-        self._a2c_keys = ppo_state_dict_keys(False)
-        self._learners[("a2c", None)] = _Learner(self._h, None, self._a2c_keys, mlp_tensor_shapes(h, self.net_zone_feat),
-                                                 lr, rmsprop_eps, nat.F_A2C_STATS, "zenv_a2c_", len(nat.A2C_STATS),
-                                                 rmsprop_alpha)
-
-    @property
-    def _a2c(self):
-        found = self._learners.get(("a2c", None))
-        return found or _Learner(self._h, None, {}, {}, 0.0, 0.0, nat.F_A2C_STATS, "zenv_a2c_", len(nat.A2C_STATS))
-
-    def a2c_tensor_ptr(self, which, index):
-        """(device pointer, element count) of tensor `index` (arena order; -1: the whole arena) of arena `which`
-        (``_native.A2C_PARAM`` / ``A2C_GRAD`` / ``A2C_SQUARE_AVG``)."""
-        return self._a2c.tensor_ptr(which, index)
-
-    def a2c_tensors(self, which=nat.A2C_PARAM):
-        """Every tensor of an arena as a new host array, under its zenv_mlp_weights name."""
-        return self._a2c.tensors(which)
-
-    def a2c_set_tensors(self, tensors, which=nat.A2C_PARAM):
-        """Overwrite the tensors of an arena that `tensors` names (zenv_mlp_weights names)."""
-        self._a2c.set_tensors(tensors, which)
-
-    def a2c_state_dict(self):
-        """The learner's parameters under the reference ACModel's state_dict names (host float32 copies)."""
-        return self._a2c.state_dict()
-
-    def a2c_load_state_dict(self, state_dict):
-        """Overwrite the learner's parameters from an ACModel state_dict (every key must be there)."""
-        self._a2c.load_state_dict(state_dict)
-
-    def a2c_optimizer_state(self):
-        """RMSprop's state in the shape of ``torch.optim.RMSprop.state_dict()`` (``step``, ``square_avg``), host arrays:
-        parameter i is the i-th of ``ACModel.parameters()``."""
-        return self._a2c.rmsprop_state()
-
-    def a2c_load_optimizer_state(self, state):
-        """Restore square_avg and the step count from ``a2c_optimizer_state`` / ``torch.optim.RMSprop.state_dict()``:
-        the ``optimizer_state`` of an A2C run's status.pt resumes here."""
-        self._a2c.load_rmsprop_state(state)
-
-    def a2c_get_step(self):
-        return self._a2c.get_step()
-
-    def a2c_set_step(self, step):
-        self._a2c.set_step(step)
+        self._learners[("a2c", None)] = _Learner(self._h, _FAMILIES["a2c"], None, ppo_state_dict_keys(False), shapes, lr,
+                                                 rmsprop_eps, rmsprop_alpha)
 
     def a2c_accumulate(self, idx, total, first, count=None):
         """One chunk of an update over `total` frames: forward, loss and backward on the samples idx (host int32 array,
         or a device address with count; at most max_batch of them).  first: the chunk opens the update and overwrites
         the gradient arena, else it adds onto it.  Every mean divides by `total`.  Asynchronous."""
-        self._a2c.accumulate(idx, total, first, count)
-
-    def a2c_apply(self):
-        """The gradient norm, clip_grad_norm_ and one RMSprop step on whatever the gradient arena holds; the five
-        statistics of the accumulated frames go to ``a2c_stats()``."""
-        self._a2c.apply()
-
-    def a2c_stats(self):
-        """float32 [1, 5] of the last a2c_apply / a2c_update ([0, 5] before the first): ``_native.A2C_STATS`` names the
-        columns.  Waits for the device."""
-        return self._a2c.stats()
+        self._learner_of("a2c").accumulate(idx, total, first, count)
 
     def a2c_publish(self, precision="auto"):
         """Hand the learner's parameters to the acting network (``load_mlp``), so the next collect acts with them."""
@@ -1316,106 +1452,56 @@ class ZoneVecEnv:
     def a2c_update(self):
         """A2CAlgo.update_parameters on the experience of the last collect: all N x T frames in index order, in
         chunks of max_batch, one clip and RMSprop step.  Returns the reference's logs (a2c.py:85-91)."""
-        self._a2c.update()
+        self._learner_of("a2c").update()
         return a2c_logs(self.a2c_stats())
 
-    # ------------------------------------------------------------------ the Zone-goals agent's two PPO updates
-    # the example's hyper-parameters (examples/zone_goals_ppo_torch.py; the reference takes the norm and does not clip)
-    HPPO_LO = dict(lr=3e-4, adam_eps=1e-8, clip_eps=0.2, entropy_coef=0.003, value_loss_coef=0.5, max_grad_norm=math.inf,
-                   max_batch=16384)
-    HPPO_HI = dict(lr=3e-4, adam_eps=1e-8, clip_eps=0.2, entropy_coef=0.01, value_loss_coef=0.5, max_grad_norm=math.inf,
-                   max_batch=4096)
-
-    def hppo_init(self, hi_state_dict, lo_state_dict, lo=None, hi=None):
-        """The two learners of HierPolicyAlgo (zone-goals/src/torch_ac/algos/_hier_policy_opt.py:197-370) on the
-        device, from HighPolicyValueModel / LoPolicyValueModel state_dicts with both critics: float32 master
-        parameters, gradients, Adam's moments and a workspace per level.  lo / hi: dicts of the settings to change from
-        ``HPPO_LO`` / ``HPPO_HI`` (lr, adam_eps, clip_eps, entropy_coef, value_loss_coef, max_grad_norm, max_batch).
-        `level` in the other hppo_* methods: ``_native.HPPO_LO`` = 0, ``HPPO_HI`` = 1.  Separate from ``load_hier``:
-        ``hppo_publish`` hands the parameters to the acting agent."""
-        tensors = hier_tensors_from_state_dicts(hi_state_dict, lo_state_dict)
-        h = int(tensors["hi_zone_b1"].shape[0])
+    # ------------------------------------------------------------------ the hierarchical agents' pairs of PPO updates
+    def _pair_init(self, family, hi_state_dict, lo_state_dict, lo, hi):
+        """zenv_<family>_init from the agent's two state_dicts with both critics; lo / hi: what to change from the
+        family's default settings.  Registers the two learners."""
+        fam = _FAMILIES[family]
+        tensors = fam.tensors_from(hi_state_dict, lo_state_dict)
         F = int(tensors["hi_zone_w1"].shape[1]) - 8
-        hi_keys, lo_keys = hppo_state_dict_keys()
+        if fam.skills:
+            S, h = (int(v) for v in tensors["hi_logit_w"].shape)
+            dims, own = (h, S, F), dict(n_skills=S)
+        else:
+            h = int(tensors["hi_zone_b1"].shape[0])
+            dims, own = (h, F), {}
+        hi_keys, lo_keys = fam.keys()
         missing = [n for n in list(hi_keys) + list(lo_keys) if n not in tensors]
         if missing:
             raise ValueError(f"the update needs both critics: no {missing[0]}")
-        shapes = hier_tensor_shapes(h, F)
-        w = nat.HierWeights(h_dim=h, precision=nat.MLP_F32, zone_feat=F)
+        shapes = fam.shapes(*dims)
+        w = fam.weights(h_dim=h, zone_feat=F, precision=nat.MLP_F32, **own)
         keep = self._load_weights(w, list(hi_keys) + list(lo_keys), tensors, shapes)      # alive across the call
-        cfgs = [nat.PpoConfig(distributional_value=0, **dict(base, **(over or {})))
-                for base, over in ((self.HPPO_LO, lo), (self.HPPO_HI, hi))]
-        check(lib().zenv_hppo_init(self._h, C.byref(w), C.byref(cfgs[0]), C.byref(cfgs[1])))
+        cfgs = [nat.PpoConfig(distributional_value=0, **dict(getattr(self, base), **(over or {})))
+                for base, over in zip(fam.defaults, (lo, hi))]
+        check(getattr(lib(), fam.prefix + "init")(self._h, C.byref(w), C.byref(cfgs[0]), C.byref(cfgs[1])))
         del keep
-        for level, keys in ((nat.HPPO_LO, lo_keys), (nat.HPPO_HI, hi_keys)):
-            self._learners[level] = _Learner(self._h, level, keys, shapes, cfgs[level].lr, cfgs[level].adam_eps,
-                                             nat.HPPO_STATS_FIELDS[level])
+        for level, keys in enumerate((lo_keys, hi_keys)):
+            self._learners[(fam.key, level)] = _Learner(self._h, fam, level, keys, shapes, cfgs[level].lr,
+                                                        cfgs[level].adam_eps)
 
-    def hppo_tensor_ptr(self, level, which, index):
-        """``ppo_tensor_ptr`` of a level's arenas."""
-        return self._learner(level).tensor_ptr(which, index)
+    def _pair_publish(self, family):
+        """Read both learners' parameters back and hand them to the family's acting agent."""
+        fam = _FAMILIES[family]
+        tensors = dict(self._learner_of(family, 1).tensors(), **self._learner_of(family, 0).tensors())
+        extra = dict(skill_len=getattr(self, "_skill_len", 200)) if fam.loader_skill_len else {}
+        getattr(self, fam.loader)(tensors, **extra)
 
-    def hppo_tensors(self, level, which=nat.PPO_PARAM):
-        """Every tensor of a level's arena as a new host array, under its zenv_hier_weights name (hi_* / lo_*)."""
-        return self._learner(level).tensors(which)
-
-    def hppo_set_tensors(self, level, tensors, which=nat.PPO_PARAM):
-        self._learner(level).set_tensors(tensors, which)
-
-    def hppo_state_dicts(self):
-        """(hi_model_state, lo_model_state): both learners' parameters under the reference's names (host copies)."""
-        return self._learner(nat.HPPO_HI).state_dict(), self._learner(nat.HPPO_LO).state_dict()
-
-    def hppo_load_state_dicts(self, hi_state_dict, lo_state_dict):
-        self._learner(nat.HPPO_HI).load_state_dict(hi_state_dict)
-        self._learner(nat.HPPO_LO).load_state_dict(lo_state_dict)
-
-    def hppo_optimizer_state(self, level):
-        """A level's Adam state in the shape of ``torch.optim.Adam.state_dict()``: parameter i is the i-th of the
-        module's ``parameters()``."""
-        return self._learner(level).optimizer_state()
-
-    def hppo_load_optimizer_state(self, level, state):
-        self._learner(level).load_optimizer_state(state)
-
-    def hppo_get_step(self, level):
-        return self._learner(level).get_step()
-
-    def hppo_set_step(self, level, step):
-        self._learner(level).set_step(step)
-
-    def hppo_minibatch(self, level, idx, apply=False, count=None):
-        """``ppo_minibatch`` on the records of the last ``collect_hier``.  Low level: index i is env i // (T-1), frame
-        i % (T-1) (lo_exps' order); high level: row i of the M closed transitions."""
-        self._learner(level).minibatch(idx, apply, count)
-
-    def hppo_apply(self, level):
-        self._learner(level).apply()
-
-    def hppo_epoch(self, level, order, batch_size, count=None):
-        self._learner(level).epoch(order, batch_size, count)
-
-    def hppo_stats(self, level):
-        """float32 [minibatches, 6] of the level's last hppo_minibatch / hppo_epoch (``_native.PPO_STATS``' columns,
-        value_std = 0).  Waits for the device."""
-        return self._learner(level).stats()
-
-    def hppo_publish(self):
-        """Hand both learners' parameters to the acting agent: read them back and ``load_hier`` them, so the next
-        ``collect_hier`` acts with them."""
-        self.load_hier(dict(self.hppo_tensors(nat.HPPO_HI), **self.hppo_tensors(nat.HPPO_LO)))
-
-    def hppo_update(self, epochs, batch_size, hi_epochs, hi_batch_size, rng):
-        """update_parameters (_hier_policy_opt.py:197-212) on the records of the last ``collect_hier``: the high level
-        first, then the low level, each epoch in the order of ``hppo_batch_indexes`` from the caller's numpy Generator.
-        Returns the reference's logs under lo_* / hi_*: the low level's are means over all its minibatches (its lists
-        start before the epoch loop, :215-224), the high level's over the last epoch's (:293-300).  With M = 0 the high
-        level is skipped and its logs are 0.0."""
+    def _pair_update(self, family, epochs, batch_size, hi_epochs, hi_batch_size, rng):
+        """A pair's update_parameters on the records of the agent's last collection: the high level first (skipped, its
+        logs zeros, when no row closed and the family allows that), then the low level, each epoch in the order of
+        ``hppo_batch_indexes`` from the caller's numpy Generator.  Returns the reference's logs under lo_* / hi_*: the
+        low level's are means over all its minibatches, the high level's over the last epoch's."""
+        fam = _FAMILIES[family]
         T = lib().zenv_field_bytes(self._h, nat.F_EXP_VALUE) // (4 * self.num_envs)
-        M = lib().zenv_field_bytes(self._h, nat.F_HI_VALUE) // 4
-        if T < 2:
-            raise ZenvError(nat.E_STATE, "collect_hier first: the handle holds no experience")
-        hi, lo = self._learner(nat.HPPO_HI), self._learner(nat.HPPO_LO)
+        M = lib().zenv_field_bytes(self._h, fam.m_from[0]) // fam.m_from[1]
+        lo_frames = T - 1 if fam.lo_drops_last else T
+        if lo_frames < 1 or (fam.needs_rows and M < 1):
+            raise ZenvError(nat.E_STATE, fam.no_experience)
+        hi, lo = self._learner_of(family, 1), self._learner_of(family, 0)
         names = [(i, n) for i, n in enumerate(nat.PPO_STATS) if n != "value_std"]
         logs = {"hi_" + n: 0.0 for _, n in names}
         for _ in range(int(hi_epochs) if M else 0):
@@ -1425,142 +1511,67 @@ class ZoneVecEnv:
             logs = {"hi_" + n: float(mean[i]) for i, n in names}
         rows = []
         for _ in range(int(epochs)):
-            lo.epoch(hppo_batch_indexes(self.num_envs * (T - 1), rng), batch_size)
+            lo.epoch(hppo_batch_indexes(self.num_envs * lo_frames, rng), batch_size)
             rows.append(lo.stats())
         mean = np.concatenate(rows).astype(np.float64).mean(axis=0) if rows else np.zeros(6)
         logs.update({"lo_" + n: float(mean[i]) for i, n in names})
         return logs
 
-    # ------------------------------------------------------------------ the xy-goals agent's two PPO updates
-    # the example's hyper-parameters (examples/xy_goals_ppo_torch.py; the reference takes the norm and does not clip)
-    XYPPO_LO = dict(lr=3e-4, adam_eps=1e-8, clip_eps=0.2, entropy_coef=0.003, value_loss_coef=0.5, max_grad_norm=math.inf,
-                    max_batch=16384)
-    XYPPO_HI = dict(lr=3e-4, adam_eps=1e-8, clip_eps=0.2, entropy_coef=0.01, value_loss_coef=0.5, max_grad_norm=math.inf,
-                    max_batch=4096)
+    # the examples' hyper-parameters (examples/zone_goals_ppo_torch.py, xy_goals_, skill_planner_ and options_ppo_torch.py;
+    # the reference takes the norm and does not clip)
+    HPPO_LO = dict(lr=3e-4, adam_eps=1e-8, clip_eps=0.2, entropy_coef=0.003, value_loss_coef=0.5, max_grad_norm=math.inf,
+                   max_batch=16384)
+    HPPO_HI = dict(lr=3e-4, adam_eps=1e-8, clip_eps=0.2, entropy_coef=0.01, value_loss_coef=0.5, max_grad_norm=math.inf,
+                   max_batch=4096)
+    XYPPO_LO, XYPPO_HI = dict(HPPO_LO), dict(HPPO_HI)
+    SKPPO_LO, SKPPO_HI = dict(HPPO_LO), dict(HPPO_HI)
+    OPPPO_LO, OPPPO_HI = dict(HPPO_LO), dict(HPPO_HI)
 
-    def _xy_learner(self, level):
-        """``_learner`` for the xy-goals pair."""
-        found = self._learners.get(("xy", int(level)))
-        field = nat.XYPPO_STATS_FIELDS[level] if level in (nat.XYPPO_LO, nat.XYPPO_HI) else nat.F_XYPPO_LO_STATS
-        return found or _Learner(self._h, level, {}, {}, 0.0, 0.0, field, "zenv_xyppo_")
+    # ---- the Zone-goals agent
+    def hppo_init(self, hi_state_dict, lo_state_dict, lo=None, hi=None):
+        """The two learners of HierPolicyAlgo (zone-goals/src/torch_ac/algos/_hier_policy_opt.py:197-370) on the
+        device, from HighPolicyValueModel / LoPolicyValueModel state_dicts with both critics: float32 master
+        parameters, gradients, Adam's moments and a workspace per level.  lo / hi: dicts of the settings to change from
+        ``HPPO_LO`` / ``HPPO_HI`` (lr, adam_eps, clip_eps, entropy_coef, value_loss_coef, max_grad_norm, max_batch).
+        `level` in the other hppo_* methods: ``_native.HPPO_LO`` = 0, ``HPPO_HI`` = 1.  Separate from ``load_hier``:
+        ``hppo_publish`` hands the parameters to the acting agent."""
+        self._pair_init("hppo", hi_state_dict, lo_state_dict, lo, hi)
 
+    def hppo_publish(self):
+        """Hand both learners' parameters to the acting agent: read them back and ``load_hier`` them, so the next
+        ``collect_hier`` acts with them."""
+        self._pair_publish("hppo")
+
+    def hppo_update(self, epochs, batch_size, hi_epochs, hi_batch_size, rng):
+        """update_parameters (_hier_policy_opt.py:197-212) on the records of the last ``collect_hier``: the high level
+        first, then the low level, each epoch in the order of ``hppo_batch_indexes`` from the caller's numpy Generator.
+        Returns the reference's logs under lo_* / hi_*: the low level's are means over all its minibatches (its lists
+        start before the epoch loop, :215-224), the high level's over the last epoch's (:293-300).  With M = 0 the high
+        level is skipped and its logs are 0.0."""
+        return self._pair_update("hppo", epochs, batch_size, hi_epochs, hi_batch_size, rng)
+
+    # ---- the xy-goals agent
     def xyppo_init(self, hi_state_dict, lo_state_dict, lo=None, hi=None):
         """The two learners of the xy-goals agent (xy-goals/src/torch_ac/algos/_hier_policy_opt.py:195-363) on the
         device, from its HighPolicyValueModel / LoPolicyValueModel state_dicts with both critics: float32 master
         parameters, gradients, Adam's moments and a workspace per level.  lo / hi: dicts of the settings to change from
         ``XYPPO_LO`` / ``XYPPO_HI``.  `level` in the other xyppo_* methods: ``_native.XYPPO_LO`` = 0, ``XYPPO_HI`` = 1.
         Separate from ``load_xy``: ``xyppo_publish`` hands the parameters to the acting agent."""
-        tensors = xy_tensors_from_state_dicts(hi_state_dict, lo_state_dict)
-        h = int(tensors["hi_zone_b1"].shape[0])
-        F = int(tensors["hi_zone_w1"].shape[1]) - 8
-        hi_keys, lo_keys = xyppo_state_dict_keys()
-        missing = [n for n in list(hi_keys) + list(lo_keys) if n not in tensors]
-        if missing:
-            raise ValueError(f"the update needs both critics: no {missing[0]}")
-        shapes = xy_tensor_shapes(h, F)
-        w = nat.XyWeights(h_dim=h, zone_feat=F, precision=nat.MLP_F32)
-        keep = self._load_weights(w, list(hi_keys) + list(lo_keys), tensors, shapes)      # alive across the call
-        cfgs = [nat.PpoConfig(distributional_value=0, **dict(base, **(over or {})))
-                for base, over in ((self.XYPPO_LO, lo), (self.XYPPO_HI, hi))]
-        check(lib().zenv_xyppo_init(self._h, C.byref(w), C.byref(cfgs[0]), C.byref(cfgs[1])))
-        del keep
-        for level, keys in ((nat.XYPPO_LO, lo_keys), (nat.XYPPO_HI, hi_keys)):
-            self._learners[("xy", level)] = _Learner(self._h, level, keys, shapes, cfgs[level].lr, cfgs[level].adam_eps,
-                                                     nat.XYPPO_STATS_FIELDS[level], "zenv_xyppo_")
-
-    def xyppo_tensor_ptr(self, level, which, index):
-        """``ppo_tensor_ptr`` of a level's arenas."""
-        return self._xy_learner(level).tensor_ptr(which, index)
-
-    def xyppo_tensors(self, level, which=nat.PPO_PARAM):
-        """Every tensor of a level's arena as a new host array, under its zenv_xy_weights name (hi_* / lo_*)."""
-        return self._xy_learner(level).tensors(which)
-
-    def xyppo_set_tensors(self, level, tensors, which=nat.PPO_PARAM):
-        self._xy_learner(level).set_tensors(tensors, which)
-
-    def xyppo_state_dicts(self):
-        """(hi_model_state, lo_model_state): both learners' parameters under the reference's names (host copies)."""
-        return self._xy_learner(nat.XYPPO_HI).state_dict(), self._xy_learner(nat.XYPPO_LO).state_dict()
-
-    def xyppo_load_state_dicts(self, hi_state_dict, lo_state_dict):
-        self._xy_learner(nat.XYPPO_HI).load_state_dict(hi_state_dict)
-        self._xy_learner(nat.XYPPO_LO).load_state_dict(lo_state_dict)
-
-    def xyppo_optimizer_state(self, level):
-        """A level's Adam state in the shape of ``torch.optim.Adam.state_dict()``: parameter i is the i-th of the
-        module's ``parameters()``."""
-        return self._xy_learner(level).optimizer_state()
-
-    def xyppo_load_optimizer_state(self, level, state):
-        self._xy_learner(level).load_optimizer_state(state)
-
-    def xyppo_get_step(self, level):
-        return self._xy_learner(level).get_step()
-
-    def xyppo_set_step(self, level, step):
-        self._xy_learner(level).set_step(step)
-
-    def xyppo_minibatch(self, level, idx, apply=False, count=None):
-        """``ppo_minibatch`` on the records of the last ``collect_xy``.  Low level: index i is env i // T, frame i % T
-        (lo_exps' order, every frame); high level: row i of the M = N T / skill_len windows."""
-        self._xy_learner(level).minibatch(idx, apply, count)
-
-    def xyppo_apply(self, level):
-        self._xy_learner(level).apply()
-
-    def xyppo_epoch(self, level, order, batch_size, count=None):
-        self._xy_learner(level).epoch(order, batch_size, count)
-
-    def xyppo_stats(self, level):
-        """float32 [minibatches, 6] of the level's last xyppo_minibatch / xyppo_epoch (``_native.PPO_STATS``' columns,
-        value_std = 0).  Waits for the device."""
-        return self._xy_learner(level).stats()
+        self._pair_init("xyppo", hi_state_dict, lo_state_dict, lo, hi)
 
     def xyppo_publish(self):
         """Hand both learners' parameters to the acting agent: read them back and ``load_xy`` them with the handle's
         current skill_len, so the next ``collect_xy`` acts with them."""
-        self.load_xy(dict(self.xyppo_tensors(nat.XYPPO_HI), **self.xyppo_tensors(nat.XYPPO_LO)),
-                     skill_len=getattr(self, "_skill_len", 200))
+        self._pair_publish("xyppo")
 
     def xyppo_update(self, epochs, batch_size, hi_epochs, hi_batch_size, rng):
         """update_parameters (xy-goals' _hier_policy_opt.py:195-197) on the records of the last ``collect_xy``: the high
         level first, then the low level, each epoch in the order of ``hppo_batch_indexes`` from the caller's numpy
         Generator.  Returns the reference's logs under lo_* / hi_*: the low level's are means over all its minibatches
         (its lists start before the epoch loop), the high level's over the last epoch's."""
-        T = lib().zenv_field_bytes(self._h, nat.F_EXP_VALUE) // (4 * self.num_envs)
-        M = lib().zenv_field_bytes(self._h, nat.F_HI_GOAL) // 8
-        if T < 1 or M < 1:
-            raise ZenvError(nat.E_STATE, "collect_xy first: the handle holds no experience of the xy-goals agent")
-        hi, lo = self._xy_learner(nat.XYPPO_HI), self._xy_learner(nat.XYPPO_LO)
-        names = [(i, n) for i, n in enumerate(nat.PPO_STATS) if n != "value_std"]
-        logs = {"hi_" + n: 0.0 for _, n in names}
-        for _ in range(int(hi_epochs)):
-            hi.epoch(hppo_batch_indexes(M, rng), hi_batch_size)
-        if int(hi_epochs) > 0:
-            mean = hi.stats().astype(np.float64).mean(axis=0)
-            logs = {"hi_" + n: float(mean[i]) for i, n in names}
-        rows = []
-        for _ in range(int(epochs)):
-            lo.epoch(hppo_batch_indexes(self.num_envs * T, rng), batch_size)
-            rows.append(lo.stats())
-        mean = np.concatenate(rows).astype(np.float64).mean(axis=0) if rows else np.zeros(6)
-        logs.update({"lo_" + n: float(mean[i]) for i, n in names})
-        return logs
+        return self._pair_update("xyppo", epochs, batch_size, hi_epochs, hi_batch_size, rng)
 
-    # ------------------------------------------------------------------ the fixed-length-skills agent's two PPO updates
-    # the example's hyper-parameters (examples/skill_planner_ppo_torch.py; the reference takes the norm and does not clip)
-    SKPPO_LO = dict(lr=3e-4, adam_eps=1e-8, clip_eps=0.2, entropy_coef=0.003, value_loss_coef=0.5, max_grad_norm=math.inf,
-                    max_batch=16384)
-    SKPPO_HI = dict(lr=3e-4, adam_eps=1e-8, clip_eps=0.2, entropy_coef=0.01, value_loss_coef=0.5, max_grad_norm=math.inf,
-                    max_batch=4096)
-
-    def _sk_learner(self, level):
-        """``_learner`` for the fixed-length-skills pair."""
-        found = self._learners.get(("sk", int(level)))
-        field = nat.SKPPO_STATS_FIELDS[level] if level in (nat.SKPPO_LO, nat.SKPPO_HI) else nat.F_SKPPO_LO_STATS
-        return found or _Learner(self._h, level, {}, {}, 0.0, 0.0, field, "zenv_skppo_")
-
+    # ---- the fixed-length-skills agent
     def skppo_init(self, hi_state_dict, lo_state_dict, lo=None, hi=None):
         """The two learners of the fixed-length-skills agent (main/src/torch_ac/algos/_hier_policy_opt.py:265-419; DIAYN
         trains the same two) on the device, from its HighPolicyValueModel / LoPolicyValueModel state_dicts with both
@@ -1568,102 +1579,43 @@ class ZoneVecEnv:
         settings to change from ``SKPPO_LO`` / ``SKPPO_HI``.  `level` in the other skppo_* methods: ``_native.SKPPO_LO``
         = 0, ``SKPPO_HI`` = 1.  Separate from ``load_skills``: ``skppo_publish`` hands the parameters to the acting
         agent.  The inverse model's and the skill prior's updates are the ``diayn_*`` methods'."""
-        tensors = skill_tensors_from_state_dicts(hi_state_dict, lo_state_dict)
-        S, h = (int(v) for v in tensors["hi_logit_w"].shape)
-        F = int(tensors["hi_zone_w1"].shape[1]) - 8
-        hi_keys, lo_keys = skppo_state_dict_keys()
-        missing = [n for n in list(hi_keys) + list(lo_keys) if n not in tensors]
-        if missing:
-            raise ValueError(f"the update needs both critics: no {missing[0]}")
-        shapes = skill_tensor_shapes(h, S, F)
-        w = nat.SkillWeights(h_dim=h, n_skills=S, zone_feat=F, precision=nat.MLP_F32)
-        keep = self._load_weights(w, list(hi_keys) + list(lo_keys), tensors, shapes)      # alive across the call
-        cfgs = [nat.PpoConfig(distributional_value=0, **dict(base, **(over or {})))
-                for base, over in ((self.SKPPO_LO, lo), (self.SKPPO_HI, hi))]
-        check(lib().zenv_skppo_init(self._h, C.byref(w), C.byref(cfgs[0]), C.byref(cfgs[1])))
-        del keep
-        for level, keys in ((nat.SKPPO_LO, lo_keys), (nat.SKPPO_HI, hi_keys)):
-            self._learners[("sk", level)] = _Learner(self._h, level, keys, shapes, cfgs[level].lr, cfgs[level].adam_eps,
-                                                     nat.SKPPO_STATS_FIELDS[level], "zenv_skppo_")
-    def skppo_tensor_ptr(self, level, which, index):
-        """``ppo_tensor_ptr`` of a level's arenas."""
-        return self._sk_learner(level).tensor_ptr(which, index)
-
-    def skppo_tensors(self, level, which=nat.PPO_PARAM):
-        """Every tensor of a level's arena as a new host array, under its zenv_skill_weights name (hi_* / lo_*)."""
-        return self._sk_learner(level).tensors(which)
-
-    def skppo_set_tensors(self, level, tensors, which=nat.PPO_PARAM):
-        self._sk_learner(level).set_tensors(tensors, which)
-
-    def skppo_state_dicts(self):
-        """(hi_model_state, lo_model_state): both learners' parameters under the reference's names (host copies)."""
-        return self._sk_learner(nat.SKPPO_HI).state_dict(), self._sk_learner(nat.SKPPO_LO).state_dict()
-
-    def skppo_load_state_dicts(self, hi_state_dict, lo_state_dict):
-        self._sk_learner(nat.SKPPO_HI).load_state_dict(hi_state_dict)
-        self._sk_learner(nat.SKPPO_LO).load_state_dict(lo_state_dict)
-
-    def skppo_optimizer_state(self, level):
-        """A level's Adam state in the shape of ``torch.optim.Adam.state_dict()``: parameter i is the i-th of the
-        module's ``parameters()``."""
-        return self._sk_learner(level).optimizer_state()
-
-    def skppo_load_optimizer_state(self, level, state):
-        self._sk_learner(level).load_optimizer_state(state)
-
-    def skppo_get_step(self, level):
-        return self._sk_learner(level).get_step()
-
-    def skppo_set_step(self, level, step):
-        self._sk_learner(level).set_step(step)
-
-    def skppo_minibatch(self, level, idx, apply=False, count=None):
-        """``ppo_minibatch`` on the records of the last ``collect_skills``.  Low level: index i is env i // T, frame i % T
-        (lo_exps' order, every frame); high level: row i of the M = N T / skill_len windows."""
-        self._sk_learner(level).minibatch(idx, apply, count)
-
-    def skppo_apply(self, level):
-        self._sk_learner(level).apply()
-
-    def skppo_epoch(self, level, order, batch_size, count=None):
-        self._sk_learner(level).epoch(order, batch_size, count)
-
-    def skppo_stats(self, level):
-        """float32 [minibatches, 6] of the level's last skppo_minibatch / skppo_epoch (``_native.PPO_STATS``' columns,
-        value_std = 0).  Waits for the device."""
-        return self._sk_learner(level).stats()
+        self._pair_init("skppo", hi_state_dict, lo_state_dict, lo, hi)
 
     def skppo_publish(self):
         """Hand both learners' parameters to the acting agent: read them back and ``load_skills`` them with the
         handle's current skill_len, so the next ``collect_skills`` acts with them.  A loaded inverse model stays."""
-        self.load_skills(dict(self.skppo_tensors(nat.SKPPO_HI), **self.skppo_tensors(nat.SKPPO_LO)),
-                     skill_len=getattr(self, "_skill_len", 200))
+        self._pair_publish("skppo")
 
     def skppo_update(self, epochs, batch_size, hi_epochs, hi_batch_size, rng):
-        """update_parameters (main's _hier_policy_opt.py:254-263, train_lo and train_hi) on the records of the last ``collect_skills``: the high
-        level first, then the low level, each epoch in the order of ``hppo_batch_indexes`` from the caller's numpy
-        Generator.  Returns the reference's logs under lo_* / hi_*: the low level's are means over all its minibatches
-        (its lists start before the epoch loop), the high level's over the last epoch's."""
-        T = lib().zenv_field_bytes(self._h, nat.F_EXP_VALUE) // (4 * self.num_envs)
-        M = lib().zenv_field_bytes(self._h, nat.F_HI_ACTION) // 4
-        if T < 1 or M < 1:
-            raise ZenvError(nat.E_STATE, "collect_skills first: the handle holds no experience of the fixed-length-skills agent")
-        hi, lo = self._sk_learner(nat.SKPPO_HI), self._sk_learner(nat.SKPPO_LO)
-        names = [(i, n) for i, n in enumerate(nat.PPO_STATS) if n != "value_std"]
-        logs = {"hi_" + n: 0.0 for _, n in names}
-        for _ in range(int(hi_epochs)):
-            hi.epoch(hppo_batch_indexes(M, rng), hi_batch_size)
-        if int(hi_epochs) > 0:
-            mean = hi.stats().astype(np.float64).mean(axis=0)
-            logs = {"hi_" + n: float(mean[i]) for i, n in names}
-        rows = []
-        for _ in range(int(epochs)):
-            lo.epoch(hppo_batch_indexes(self.num_envs * T, rng), batch_size)
-            rows.append(lo.stats())
-        mean = np.concatenate(rows).astype(np.float64).mean(axis=0) if rows else np.zeros(6)
-        logs.update({"lo_" + n: float(mean[i]) for i, n in names})
-        return logs
+        """update_parameters (main's _hier_policy_opt.py:254-263, train_lo and train_hi) on the records of the last
+        ``collect_skills``: the high level first, then the low level, each epoch in the order of ``hppo_batch_indexes``
+        from the caller's numpy Generator.  Returns the reference's logs under lo_* / hi_*: the low level's are means
+        over all its minibatches (its lists start before the epoch loop), the high level's over the last epoch's."""
+        return self._pair_update("skppo", epochs, batch_size, hi_epochs, hi_batch_size, rng)
+
+    # ---- the Options agent
+    def opppo_init(self, hi_state_dict, lo_state_dict, lo=None, hi=None):
+        """The two learners of the Options agent (options/src/torch_ac/algos/_hier_policy_opt.py:208-381) on the device,
+        from its HighPolicyValueModel / LoPolicyValueModel state_dicts with both critics: float32 master parameters,
+        gradients, Adam's moments and a workspace per level.  lo / hi: dicts of the settings to change from ``OPPPO_LO``
+        / ``OPPPO_HI``.  `level` in the other opppo_* methods: ``_native.OPPPO_LO`` = 0, ``OPPPO_HI`` = 1.  Separate from
+        ``load_options``: ``opppo_publish`` hands the parameters to the acting agent."""
+        self._pair_init("opppo", hi_state_dict, lo_state_dict, lo, hi)
+
+    def opppo_publish(self):
+        """Hand both learners' parameters to the acting agent: read them back and ``load_options`` them, so the next
+        ``collect_options`` acts with them.  Like every ``load_options`` this drops the transitions the last collection
+        left open, exactly as the torch example's reload does: an option still running when a collection ends is not
+        trained on, its skill is picked again."""
+        self._pair_publish("opppo")
+
+    def opppo_update(self, epochs, batch_size, hi_epochs, hi_batch_size, rng):
+        """update_hi_parameters, then update_lo_parameters (options/src/torch_ac/algos/_hier_policy_opt.py:208-381) on the
+        records of the last ``collect_options``: the high level first and only if some transition closed (M >= 1; with
+        M = 0 the hi_* logs are zeros), then the low level over N (T - 1) indexes, each epoch in the order of
+        ``hppo_batch_indexes`` from the caller's numpy Generator.  Returns the reference's logs under lo_* / hi_*: the low
+        level's are means over all its minibatches, the high level's over the last epoch's."""
+        return self._pair_update("opppo", epochs, batch_size, hi_epochs, hi_batch_size, rng)
 
     # ------------------------------------------------------------------ DIAYN's inverse model and learned skill prior
     # the example's hyper-parameters (examples/skill_planner_ppo_torch.py; the reference does not clip this optimiser);
@@ -1671,11 +1623,6 @@ class ZoneVecEnv:
     DIAYN = dict(lr=3e-4, adam_eps=1e-8, clip_eps=0.0, entropy_coef=0.0, value_loss_coef=0.0, max_grad_norm=math.inf,
                  max_batch=16384)
     DIAYN_PRIOR = dict(lr=1e-2, adam_eps=1e-8)
-
-    def _diayn_learner(self):
-        """``_learner`` for the inverse model's."""
-        found = self._learners.get(("diayn", None))
-        return found or _Learner(self._h, None, {}, {}, 0.0, 0.0, nat.F_DIAYN_STATS, "zenv_diayn_")
 
     def diayn_init(self, inverse_tensors, n_skills, prior_logits=None, prior=None, **hyper):
         """DIAYN's two remaining updates on the device (main/src/torch_ac/algos/_hier_policy_opt.py:421-464): a learner
@@ -1699,8 +1646,7 @@ class ZoneVecEnv:
         cfg = nat.PpoConfig(distributional_value=0, **dict(self.DIAYN, **hyper))
         check(lib().zenv_diayn_init(self._h, C.byref(w), C.byref(cfg)))
         del keep
-        self._learners[("diayn", None)] = _Learner(self._h, None, keys, shapes, cfg.lr, cfg.adam_eps, nat.F_DIAYN_STATS,
-                                                   "zenv_diayn_")
+        self._learners[("diayn", None)] = _Learner(self._h, _FAMILIES["diayn"], None, keys, shapes, cfg.lr, cfg.adam_eps)
         self._diayn_S = S
         if prior_logits is not None:
             logits = np.ascontiguousarray(_as_host_f32(prior_logits).reshape(-1))
@@ -1708,37 +1654,6 @@ class ZoneVecEnv:
                 raise ValueError(f"prior_logits has {logits.size} entries, n_skills is {S}")
             p = dict(self.DIAYN_PRIOR, **(prior or {}))
             check(lib().zenv_diayn_prior_init(self._h, logits.ctypes.data, S, float(p["lr"]), float(p["adam_eps"])))
-
-    def diayn_tensor_ptr(self, which, index):
-        """``ppo_tensor_ptr`` of the inverse model's arenas."""
-        return self._diayn_learner().tensor_ptr(which, index)
-
-    def diayn_tensors(self, which=nat.PPO_PARAM):
-        """Every tensor of the arena as a new host array, under its zenv_skill_inverse_weights name."""
-        return self._diayn_learner().tensors(which)
-
-    def diayn_set_tensors(self, tensors, which=nat.PPO_PARAM):
-        self._diayn_learner().set_tensors(tensors, which)
-
-    def diayn_state_dict(self):
-        """The learner's parameters under InverseModel's names (host copies)."""
-        return self._diayn_learner().state_dict()
-
-    def diayn_load_state_dict(self, state_dict):
-        self._diayn_learner().load_state_dict(state_dict)
-
-    def diayn_optimizer_state(self):
-        """Adam's state in the shape of ``torch.optim.Adam.state_dict()``: parameter i is the i-th of ``parameters()``."""
-        return self._diayn_learner().optimizer_state()
-
-    def diayn_load_optimizer_state(self, state):
-        self._diayn_learner().load_optimizer_state(state)
-
-    def diayn_get_step(self):
-        return self._diayn_learner().get_step()
-
-    def diayn_set_step(self, step):
-        self._diayn_learner().set_step(step)
 
     def diayn_samples_on_device(self):
         """Compact the kept sample indexes of the last ``collect_skills`` on the device (``_native.F_DIAYN_SAMPLES``);
@@ -1757,21 +1672,6 @@ class ZoneVecEnv:
             check(lib().zenv_get(self._h, nat.F_DIAYN_SAMPLES, out.ctypes.data, 0))
         return out
 
-    def diayn_minibatch(self, idx, apply=False, count=None):
-        """``ppo_minibatch`` of the inverse model on the sample indexes idx (entries of ``diayn_samples()``)."""
-        self._diayn_learner().minibatch(idx, apply, count)
-
-    def diayn_apply(self):
-        self._diayn_learner().apply()
-
-    def diayn_epoch(self, order, batch_size, count=None):
-        self._diayn_learner().epoch(order, batch_size, count)
-
-    def diayn_stats(self):
-        """float32 [minibatches, 6] of the last diayn_minibatch / diayn_epoch: column 0 the cross-entropy loss, column
-        5 the gradient norm, columns 1-4 zero.  Waits for the device."""
-        return self._diayn_learner().stats()
-
     def diayn_update(self, epochs, batch_size, rng):
         """update_inverse_parameters (main's _hier_policy_opt.py:421-447) on the records of the last ``collect_skills``:
         every epoch a permutation of the kept samples from the caller's numpy Generator, cut into batches.  Stores and
@@ -1781,7 +1681,7 @@ class ZoneVecEnv:
         for e in range(int(epochs)):
             if not kept.size:
                 break
-            self._diayn_learner().epoch(kept[hppo_batch_indexes(kept.size, rng)], batch_size)
+            self.diayn_epoch(kept[hppo_batch_indexes(kept.size, rng)], batch_size)
             if e == 0:
                 rows = self.diayn_stats()
         self._diayn_first_epoch = rows
@@ -1817,126 +1717,6 @@ class ZoneVecEnv:
         """Hand the learner's parameters to the acting discriminator: read the 10 tensors back and
         ``load_skill_inverse`` them, so the next ``collect_skills`` takes its diversity reward from them."""
         self.load_skill_inverse(self.diayn_tensors())
-
-    # ------------------------------------------------------------------ the Options agent's two PPO updates
-    # the example's hyper-parameters (examples/options_ppo_torch.py; the reference takes the norm and does not clip)
-    OPPPO_LO = dict(lr=3e-4, adam_eps=1e-8, clip_eps=0.2, entropy_coef=0.003, value_loss_coef=0.5, max_grad_norm=math.inf,
-                    max_batch=16384)
-    OPPPO_HI = dict(lr=3e-4, adam_eps=1e-8, clip_eps=0.2, entropy_coef=0.01, value_loss_coef=0.5, max_grad_norm=math.inf,
-                    max_batch=4096)
-
-    def _op_learner(self, level):
-        """``_learner`` for the Options pair."""
-        found = self._learners.get(("op", int(level)))
-        field = nat.OPPPO_STATS_FIELDS[level] if level in (nat.OPPPO_LO, nat.OPPPO_HI) else nat.F_OPPPO_LO_STATS
-        return found or _Learner(self._h, level, {}, {}, 0.0, 0.0, field, "zenv_opppo_")
-
-    def opppo_init(self, hi_state_dict, lo_state_dict, lo=None, hi=None):
-        """The two learners of the Options agent (options/src/torch_ac/algos/_hier_policy_opt.py:208-381) on the device,
-        from its HighPolicyValueModel / LoPolicyValueModel state_dicts with both critics: float32 master parameters,
-        gradients, Adam's moments and a workspace per level.  lo / hi: dicts of the settings to change from ``OPPPO_LO``
-        / ``OPPPO_HI``.  `level` in the other opppo_* methods: ``_native.OPPPO_LO`` = 0, ``OPPPO_HI`` = 1.  Separate from
-        ``load_options``: ``opppo_publish`` hands the parameters to the acting agent."""
-        tensors = option_tensors_from_state_dicts(hi_state_dict, lo_state_dict)
-        S, h = (int(v) for v in tensors["hi_logit_w"].shape)
-        F = int(tensors["hi_zone_w1"].shape[1]) - 8
-        hi_keys, lo_keys = opppo_state_dict_keys()
-        missing = [n for n in list(hi_keys) + list(lo_keys) if n not in tensors]
-        if missing:
-            raise ValueError(f"the update needs both critics: no {missing[0]}")
-        shapes = option_tensor_shapes(h, S, F)
-        w = nat.OptionWeights(h_dim=h, n_skills=S, zone_feat=F, precision=nat.MLP_F32)
-        keep = self._load_weights(w, list(hi_keys) + list(lo_keys), tensors, shapes)      # alive across the call
-        cfgs = [nat.PpoConfig(distributional_value=0, **dict(base, **(over or {})))
-                for base, over in ((self.OPPPO_LO, lo), (self.OPPPO_HI, hi))]
-        check(lib().zenv_opppo_init(self._h, C.byref(w), C.byref(cfgs[0]), C.byref(cfgs[1])))
-        del keep
-        for level, keys in ((nat.OPPPO_LO, lo_keys), (nat.OPPPO_HI, hi_keys)):
-            self._learners[("op", level)] = _Learner(self._h, level, keys, shapes, cfgs[level].lr, cfgs[level].adam_eps,
-                                                     nat.OPPPO_STATS_FIELDS[level], "zenv_opppo_")
-
-    def opppo_tensor_ptr(self, level, which, index):
-        """``ppo_tensor_ptr`` of a level's arenas."""
-        return self._op_learner(level).tensor_ptr(which, index)
-
-    def opppo_tensors(self, level, which=nat.PPO_PARAM):
-        """Every tensor of a level's arena as a new host array, under its zenv_option_weights name (hi_* / lo_*)."""
-        return self._op_learner(level).tensors(which)
-
-    def opppo_set_tensors(self, level, tensors, which=nat.PPO_PARAM):
-        self._op_learner(level).set_tensors(tensors, which)
-
-    def opppo_state_dicts(self):
-        """(hi_model_state, lo_model_state): both learners' parameters under the reference's names (host copies)."""
-        return self._op_learner(nat.OPPPO_HI).state_dict(), self._op_learner(nat.OPPPO_LO).state_dict()
-
-    def opppo_load_state_dicts(self, hi_state_dict, lo_state_dict):
-        self._op_learner(nat.OPPPO_HI).load_state_dict(hi_state_dict)
-        self._op_learner(nat.OPPPO_LO).load_state_dict(lo_state_dict)
-
-    def opppo_optimizer_state(self, level):
-        """A level's Adam state in the shape of ``torch.optim.Adam.state_dict()``: parameter i is the i-th of the
-        module's ``parameters()``."""
-        return self._op_learner(level).optimizer_state()
-
-    def opppo_load_optimizer_state(self, level, state):
-        self._op_learner(level).load_optimizer_state(state)
-
-    def opppo_get_step(self, level):
-        return self._op_learner(level).get_step()
-
-    def opppo_set_step(self, level, step):
-        self._op_learner(level).set_step(step)
-
-    def opppo_minibatch(self, level, idx, apply=False, count=None):
-        """``ppo_minibatch`` on the records of the last ``collect_options``.  Low level: index i is env i // (T - 1), frame
-        i % (T - 1) (lo_exps' order; frame T - 1 is never read); high level: row i of the M closed transitions (M >= 1)."""
-        self._op_learner(level).minibatch(idx, apply, count)
-
-    def opppo_apply(self, level):
-        self._op_learner(level).apply()
-
-    def opppo_epoch(self, level, order, batch_size, count=None):
-        self._op_learner(level).epoch(order, batch_size, count)
-
-    def opppo_stats(self, level):
-        """float32 [minibatches, 6] of the level's last opppo_minibatch / opppo_epoch (``_native.PPO_STATS``' columns,
-        value_std = 0).  Waits for the device."""
-        return self._op_learner(level).stats()
-
-    def opppo_publish(self):
-        """Hand both learners' parameters to the acting agent: read them back and ``load_options`` them, so the next
-        ``collect_options`` acts with them.  Like every ``load_options`` this drops the transitions the last collection
-        left open, exactly as the torch example's reload does: an option still running when a collection ends is not
-        trained on, its skill is picked again."""
-        self.load_options(dict(self.opppo_tensors(nat.OPPPO_HI), **self.opppo_tensors(nat.OPPPO_LO)))
-
-    def opppo_update(self, epochs, batch_size, hi_epochs, hi_batch_size, rng):
-        """update_hi_parameters, then update_lo_parameters (options/src/torch_ac/algos/_hier_policy_opt.py:208-381) on the
-        records of the last ``collect_options``: the high level first and only if some transition closed (M >= 1; with
-        M = 0 the hi_* logs are zeros), then the low level over N (T - 1) indexes, each epoch in the order of
-        ``hppo_batch_indexes`` from the caller's numpy Generator.  Returns the reference's logs under lo_* / hi_*: the low
-        level's are means over all its minibatches, the high level's over the last epoch's."""
-        T = lib().zenv_field_bytes(self._h, nat.F_EXP_VALUE) // (4 * self.num_envs)
-        M = lib().zenv_field_bytes(self._h, nat.F_HI_ACTION) // 4
-        if T < 2:
-            raise ZenvError(nat.E_STATE, "collect_options first: the handle holds no experience of the Options agent")
-        hi, lo = self._op_learner(nat.OPPPO_HI), self._op_learner(nat.OPPPO_LO)
-        names = [(i, n) for i, n in enumerate(nat.PPO_STATS) if n != "value_std"]
-        logs = {"hi_" + n: 0.0 for _, n in names}
-        if M >= 1:
-            for _ in range(int(hi_epochs)):
-                hi.epoch(hppo_batch_indexes(M, rng), hi_batch_size)
-            if int(hi_epochs) > 0:
-                mean = hi.stats().astype(np.float64).mean(axis=0)
-                logs = {"hi_" + n: float(mean[i]) for i, n in names}
-        rows = []
-        for _ in range(int(epochs)):
-            lo.epoch(hppo_batch_indexes(self.num_envs * (T - 1), rng), batch_size)
-            rows.append(lo.stats())
-        mean = np.concatenate(rows).astype(np.float64).mean(axis=0) if rows else np.zeros(6)
-        logs.update({"lo_" + n: float(mean[i]) for i, n in names})
-        return logs
 
     # ------------------------------------------------------------------ Zone-goals training experience
     def collect_hier(self, frames_per_proc, policy_seed=1, env_index0=0, discount=0.99, gae_lambda=0.95):
